@@ -14,8 +14,14 @@ computes (sharding.FluxGatherer; the last one is awaited inside the timed region
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --gpus 8 --scaling strong     # BASELINE C4 as stated: 16 384 columns sharded over the 8 GPUs
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying `roofline` (dominant kernel, live HIP-event
-timing on the launch stream) and `cpu_baseline` (the oracle, a scalar CPU port, on a bounded column sample).
+Prints ONE JSON line on rank 0: `metric`, `value` (columns/s), `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the
+workload's `config`. A plain run does only that: set up, warm up, time --steps steps, print. Everything else is behind --full:
+
+    python bench.py --full        # + `stages` and `roofline` / `roofline_valu` (live HIP-event timing per stage on the launch
+                                  #   stream), `finite`, the gas-window census (`gas_window`, one extra untimed step), `fp32_vs_fp64`
+                                  #   (--dtype f32), `other_scaling` (N > 1) and `cpu_baseline` (the oracle, a scalar CPU port,
+                                  #   on a bounded column sample)
+    python bench.py --dump-outputs DIR   # after the timed steps: the broadband fluxes of the last step as DIR/<name>.npy
 """
 import argparse
 import json
@@ -253,6 +259,29 @@ def pmc_is_stale():
     return json.load(open(path)).get("sources_digest", {}).get("sha256") != sources_digest()
 
 
+FLUX_NAMES = ("lw_flux_up", "lw_flux_dn", "lw_flux_net", "sw_flux_up", "sw_flux_dn", "sw_flux_dn_dir", "sw_flux_net")
+DUMP_BYTES = 64 * 10**6         # --dump-outputs writes at most this much in all
+
+
+def output_arrays(F):
+    """--dump-outputs: the packed broadband fluxes (7, nlev, ncol) of a step as one (nlev, ncol') array per flux, in the solve's
+    precision. All columns when they fit DUMP_BYTES, otherwise the same fixed, seeded sample of columns (ascending) for every flux;
+    the sample depends on the shape alone, so two builds of the project write the same columns."""
+    nflux, nlev, ncol = F.shape
+    per_col = nflux * nlev * F.itemsize
+    budget = DUMP_BYTES - nflux * 1024                      # (room for the .npy headers)
+    if ncol * per_col > budget:
+        cols = np.sort(np.random.default_rng(20240601).choice(ncol, budget // per_col, replace=False))
+        F = F[:, :, cols]
+    return {name: np.ascontiguousarray(F[i]) for i, name in enumerate(FLUX_NAMES)}
+
+
+def dump_outputs(path, F):
+    os.makedirs(path, exist_ok=True)
+    for name, a in output_arrays(F).items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -277,7 +306,12 @@ def main():
     ap.add_argument("--bb-min-groups", type=int, default=None, help="rrx_set_broadband_min_groups (A/B of the fused broadband form)")
     ap.add_argument("--lw-variant", type=int, default=0)
     ap.add_argument("--sw-variant", type=int, default=0)
-    ap.add_argument("--cpu-cols", type=int, default=6000, help="columns of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-stage timing and rooflines, finite check, gas-window census, fp32 against fp64, "
+                         "the other scaling (N > 1) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the broadband fluxes of the last timed step as DIR/<name>.npy (a fixed column sample beyond 64 MB)")
+    ap.add_argument("--cpu-cols", type=int, default=6000, help="columns of the CPU baseline sample of --full (0 = skip)")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--sync-gather", action="store_true", help="wait for each all-gather before the next solve starts (A/B of the pipelined exchange)")
     ap.add_argument("--overlap", action="store_true", help="run the independent LW and SW chains on two HIP streams")
@@ -291,6 +325,8 @@ def main():
     ap.add_argument("--allsky", action="store_true",
                     help="BASELINE's all-sky flow (C5): cloud optics added by band after the gas optics, delta-scaled in SW; not the headline workload")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.broadband = (args.flux_mode == "broadband" or args.broadband) and not args.per_gpoint
     if args.scaling is None:
         args.scaling = "strong" if args.gpus > 1 else "weak"
@@ -368,9 +404,9 @@ def main():
             one_step()
         if gatherer is not None:
             gatherer.finish()
-        # one untimed step with the windowed gas optics' hand-back census switched on (it synchronises the stream per launch)
+        # --full: one untimed step with the windowed gas optics' hand-back census switched on (it synchronises the stream per launch)
         handed = None
-        if primary and rank == 0 and be.lib.has("rrx_gas_window_stats") and args.driver == "python":
+        if args.full and primary and rank == 0 and be.lib.has("rrx_gas_window_stats") and args.driver == "python":
             import ctypes
             os.environ["RRX_GW_STATS"] = "1"
             be.lib.cdll.rrx_gas_window_stats(None, None, 1)
@@ -383,7 +419,7 @@ def main():
             be.lib.cdll.rrx_gas_window_stats(ctypes.byref(c1), ctypes.byref(c2), 1)
             if c2.value > 0:
                 handed = {"handed_back": int(c1.value), "workgroups": int(c2.value), "frac": round(c1.value / c2.value, 4)}
-        if primary and args.driver == "python":
+        if args.full and primary and args.driver == "python":
             solver.enable_stage_events(args.steps)
 
         if world > 1:
@@ -402,14 +438,18 @@ def main():
             t = torch.tensor([dt], dtype=torch.float64, device=device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        return dict(dt=dt, ntot=ntot, ncol_local=col_e - col_s, solver=solver, handed=handed)
+        return dict(dt=dt, ntot=ntot, ncol_local=col_e - col_s, solver=solver, handed=handed, gatherer=gatherer)
 
     m = measure(args.scaling, True)
     dt, ntot, ncol_local, solver, handed = m["dt"], m["ntot"], m["ncol_local"], m["solver"], m["handed"]
-    # N > 1: the other way of growing the job, measured in the same run (BASELINE C4 shards 16 384 columns over the
-    # GPUs = strong, which is `value`; the weak line -- 16 384 columns on every GPU -- rides along)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: the all-gathered fluxes of the job, or this rank's own
+        F = m["gatherer"].result() if m["gatherer"] is not None else solver.fluxes
+        dump_outputs(args.dump_outputs, F.cpu().numpy())
+    # --full, N > 1: the other way of growing the job, measured in the same run (BASELINE C4 shards 16 384 columns over
+    # the GPUs = strong, which is `value`; the weak line -- 16 384 columns on every GPU -- rides along)
     other = None
-    if world > 1 and not args.one_scaling:
+    if args.full and world > 1 and not args.one_scaling:
         o = measure("weak" if args.scaling == "strong" else "strong", False)
         other = {"scaling": "weak" if args.scaling == "strong" else "strong", "value": round(o["ntot"] * args.steps / o["dt"], 1),
                  "ms_per_step": round(o["dt"] / args.steps * 1e3, 3), "columns_per_gpu": o["ncol_local"], "columns_total": o["ntot"]}
@@ -417,30 +457,20 @@ def main():
 
     if rank == 0 and args.driver == "cxx":
         # the C++ host classes enqueue a whole solve per call: no per-stage events from here; the kernels are the ones of the default
-        # driver, whose line carries the roofline
+        # driver, whose --full line carries the roofline
         out = {"metric": "columns/sec (LW+SW full solve, 140 lay x 256 gpt)", "value": round(ntot * args.steps / dt, 1), "unit": "columns/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
                "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
                "config": {"workload": f"C4 synthetic {ncol_local} columns/GPU ({ntot} in total) x {args.nlay} layers x {args.ngpt} g-points, "
                                       f"LW+SW {'all-sky' if args.allsky else 'clear-sky'}, RCEMIP profile, synthetic k-distribution (real shapes)",
                           "driver": "C++ host classes (Radiation_solver_longwave / _shortwave::solve_gpu) through librte_rrtmgp_hip.so",
-                          "columns_per_gpu": ncol_local, "columns_total": ntot, "nlay": args.nlay, "ngpt": args.ngpt},
-               "roofline": None, "finite": bool(torch.isfinite(solver.fluxes).all().item())}
+                          "columns_per_gpu": ncol_local, "columns_total": ntot, "nlay": args.nlay, "ngpt": args.ngpt}}
+        if args.full:
+            out.update(roofline=None, finite=bool(torch.isfinite(solver.fluxes).all().item()))
         if other is not None:
             out["other_scaling"] = other
         print(json.dumps(out), flush=True)
     elif rank == 0:
-        S = np_dtype().itemsize
-        ms = solver.stage_ms()
-        words = algo_words(args.nlay, args.ngpt, nbnd, args.broadband, solver.g_zero and args.broadband, solver.lite)
-        units = ncol_local * args.ngpt
-        kernels = {}
-        for st, w in words.items():
-            gbs = w * units * S / (max(ms[st], 1e-6)*1e-3) / 1e9
-            kernels[st] = dict(ms=round(ms[st], 4), algo_GB=round(w*units*S/1e9, 4), GBs=round(gbs, 1), frac=round(gbs/HBM_PEAK_GBS, 4))
-        single = {k: v for k, v in kernels.items() if k in STAGE_KERNEL and v["ms"] > 0}   # single-launch stages
-        dom = max(single, key=lambda k: single[k]["ms"])
-        finite = bool(torch.isfinite(solver.fluxes).all().item())
         out = {
             "metric": "columns/sec (LW+SW full solve, 140 lay x 256 gpt)",
             "value": round(ntot * args.steps / dt, 1),
@@ -456,29 +486,42 @@ def main():
                                     else "per-g-point fluxes + sum_broadband",
                        "col_spread": args.col_spread, "columns_sorted": bool(solver.sort_columns),
                        "parallelism": f"columns sharded x{world}, all-gather of broadband fluxes"},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": kernels[dom]["GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": kernels[dom]["frac"], "traffic": pmc_traffic(dom, args),
-                         "algorithmic_bytes_per_launch": int(words[dom]*units*S), "avg_launch_ms": kernels[dom]["ms"]},
-            "roofline_valu": valu_roofline(dom, args, kernels[dom]["ms"]),
-            "stages": kernels,
-            "finite": finite,
         }
-        # the PMC-derived entries come from the committed counter summary, not from this run: say so when a kernel has changed since
-        stale = pmc_is_stale()
-        if stale is not None:
-            out["roofline"]["traffic_stale"] = bool(stale)
-            if out["roofline_valu"] is not None:
-                out["roofline_valu"]["stale"] = bool(stale)
-        if handed is not None:
-            out["gas_window"] = handed
-        if args.dtype == "f32" and args.driver == "python":
-            out["fp32_vs_fp64"] = fp32_against_fp64(args, nbnd, rank, world, solver, kd_lw0, kd_sw0)
+        if args.full:
+            S = np_dtype().itemsize
+            ms = solver.stage_ms()
+            words = algo_words(args.nlay, args.ngpt, nbnd, args.broadband, solver.g_zero and args.broadband, solver.lite)
+            units = ncol_local * args.ngpt
+            kernels = {}
+            for st, w in words.items():
+                gbs = w * units * S / (max(ms[st], 1e-6)*1e-3) / 1e9
+                kernels[st] = dict(ms=round(ms[st], 4), algo_GB=round(w*units*S/1e9, 4), GBs=round(gbs, 1), frac=round(gbs/HBM_PEAK_GBS, 4))
+            single = {k: v for k, v in kernels.items() if k in STAGE_KERNEL and v["ms"] > 0}   # single-launch stages
+            dom = max(single, key=lambda k: single[k]["ms"])
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": kernels[dom]["GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": kernels[dom]["frac"], "traffic": pmc_traffic(dom, args),
+                             "algorithmic_bytes_per_launch": int(words[dom]*units*S), "avg_launch_ms": kernels[dom]["ms"]},
+                "roofline_valu": valu_roofline(dom, args, kernels[dom]["ms"]),
+                "stages": kernels,
+                "finite": bool(torch.isfinite(solver.fluxes).all().item()),
+            })
+            # the PMC-derived entries come from the committed counter summary, not from this run: say so when a kernel has changed since
+            stale = pmc_is_stale()
+            if stale is not None:
+                out["roofline"]["traffic_stale"] = bool(stale)
+                if out["roofline_valu"] is not None:
+                    out["roofline_valu"]["stale"] = bool(stale)
+            if handed is not None:
+                out["gas_window"] = handed
+            if args.dtype == "f32" and args.driver == "python":
+                out["fp32_vs_fp64"] = fp32_against_fp64(args, nbnd, rank, world, solver, kd_lw0, kd_sw0)
         if other is not None:
             out["other_scaling"] = other
         if world > 1:       # what a SCALE record can be checked against
             out["ranks_seen"] = dist.get_world_size()
             out["columns_per_rank"] = [int(e - s) for s, e in (sharding.column_range(r, world, ntot) for r in range(world))]
-        if world == 1 and args.cpu_cols > 0 and not args.allsky:      # (the CPU sample is the clear-sky headline workload)
+        if args.full and world == 1 and args.cpu_cols > 0 and not args.allsky:      # (the CPU sample is the clear-sky headline workload)
             out["cpu_baseline"] = cpu_baseline(args, kd_lw0, kd_sw0, be)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -951,13 +951,14 @@ def test_pipelined_flux_gatherer_on_rccl_single_rank():
 
 
 def test_bench_line_keeps_its_contract():
-    """bench.py as the driver runs it (its own process, default workload, few steps): ONE JSON line with the contract's fields,
-    the roofline object (live HIP-event timing, committed PMC traffic) and the CPU baseline with its same-run parity check."""
+    """bench.py --full (its own process, default workload, few steps): ONE JSON line with the contract's fields, the roofline
+    object (live HIP-event timing, committed PMC traffic) and the CPU baseline with its same-run parity check."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--cpu-cols", "24"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full",
+                        "--cpu-cols", "24"],
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -976,6 +977,42 @@ def test_bench_line_keeps_its_contract():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 1 and c["value"] > 0 and c["parity_max_rel"] <= 1e-6
     assert abs(sum(s["ms"] for s in d["stages"].values()) - d["ms_per_step"]) / d["ms_per_step"] < 0.05   # the stages account for the step
+
+
+
+def test_plain_bench_run_is_lean_and_dumps_what_it_computed(tmp_path, hip_f64):
+    """bench.py without --full: the headline line only (no per-stage events, census, rooflines or CPU baseline), and
+    --dump-outputs writes the fluxes of the last timed step -- the same numbers the resident solver gives in this process."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    ncol = 1000
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--ncol", str(ncol),
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    for k in ("roofline", "roofline_valu", "stages", "gas_window", "cpu_baseline", "fp32_vs_fp64", "other_scaling"):
+        assert k not in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f64" and d["config"]["columns_total"] == ncol
+    assert abs(d["value"] - ncol*1e3/d["ms_per_step"]) / d["value"] < 1e-3
+    got = {n: np.load(tmp_path / (n + ".npy")) for n in bench.FLUX_NAMES}
+    assert sorted(os.listdir(tmp_path)) == sorted(n + ".npy" for n in bench.FLUX_NAMES)
+    be = hip_f64
+    nbnd = 256 // 16
+    kl, ks = (be.upload_kdist(synthetic.make_kdist(k, ngpt=256, nbnd=nbnd)) for k in ("lw", "sw"))
+    import argparse
+    a = argparse.Namespace(ncol=ncol, scaling="weak", nlay=140, top_at_1=False, allsky=False, col_spread=0.0)
+    _, atm0 = bench.local_atmosphere(a, nbnd, 0, 1)
+    ref = be.to_numpy(pipeline.ResidentSolver(be, kl, ks, pipeline.upload_atmosphere(be, atm0), do_broadband=True).step())
+    for i, n in enumerate(bench.FLUX_NAMES):
+        assert got[n].dtype == np.float64 and got[n].shape == (141, ncol), n
+        assert cases.rel_err(got[n], ref[i]) <= 1e-12, n
 
 
 @pytest.mark.parametrize("dt", ["f64", "f32"])

@@ -2,8 +2,8 @@
 # The bench JSON lines of profiles/ alone (no profiler), run ON the GPU box: after tools/profile_r04.sh has produced the counters of
 # the current sources and profiles/pmc_traffic.json has been replaced by them, the lines carry traffic_stale: false.
 export TMPDIR=/tmp
-OUT=$PWD/gpurun_out/r04b; mkdir -p $OUT
-run() { name=$1; shift; timeout -k 10 400 python3 bench.py "$@" 2>/dev/null | grep '^{' | tail -1 > $OUT/r04_bench_$name.json; python3 -c "import json; d=json.load(open('$OUT/r04_bench_$name.json')); print('$name', d['value'], d['ms_per_step'], (d.get('roofline') or {}).get('traffic_stale'))"; }
+OUT=$PWD/${LOGDIR:-logs}/r04b; mkdir -p $OUT
+run() { name=$1; shift; timeout -k 10 400 python3 bench.py --full "$@" 2>/dev/null | grep '^{' | tail -1 > $OUT/r04_bench_$name.json; python3 -c "import json; d=json.load(open('$OUT/r04_bench_$name.json')); print('$name', d['value'], d['ms_per_step'], (d.get('roofline') or {}).get('traffic_stale'))"; }
 run f64_broadband
 run f64_per-gpoint --per-gpoint --cpu-cols 0
 run f32_broadband --dtype f32 --cpu-cols 0

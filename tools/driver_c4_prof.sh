@@ -1,6 +1,6 @@
 #!/bin/bash
 # Run ON the GPU box: rocprofv3 kernel statistics of the C++ driver on the C4 case (tools/driver_c4.py writes the case)
-OUT=$PWD/gpurun_out/drv; mkdir -p $OUT; REPO=$PWD
+OUT=$PWD/${LOGDIR:-logs}/drv; mkdir -p $OUT; REPO=$PWD
 python3 - <<PY
 import os, sys
 sys.path.insert(0, "$REPO")

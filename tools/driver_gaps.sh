@@ -1,7 +1,7 @@
 #!/bin/bash
 # Run ON the GPU box: kernel timeline of the C++ driver at C4 (one LW + one SW solve of the timed runs): busy time, gaps, the
 # kernels and copies in order -- where the driver's 0.3-0.5 ms per solve above the sum of its big kernels goes.
-OUT=$PWD/gpurun_out/drvgap; mkdir -p $OUT; REPO=$PWD
+OUT=$PWD/${LOGDIR:-logs}/drvgap; mkdir -p $OUT; REPO=$PWD
 python3 - <<PY
 import os, sys
 sys.path.insert(0, "$REPO")

@@ -1,15 +1,15 @@
 #!/bin/bash
 # Run ON the GPU box from the repo root: bash tools/gpu_check.sh <tag> [bench variants...]
-# GPU test suite + bench lines (stage times printed compactly). Logs under gpurun_out/<tag>/.
+# GPU test suite + bench lines (stage times printed compactly). Logs under ${LOGDIR:-logs}/<tag>/.
 TAG=${1:-chk}; shift
-OUT=gpurun_out/$TAG; mkdir -p $OUT
+OUT=${LOGDIR:-logs}/$TAG; mkdir -p $OUT
 if [ "$SKIP_TESTS" != "1" ]; then
   timeout -k 10 900 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?"; tail -3 $OUT/pytest.log
 fi
 i=0
 run_bench() {
   i=$((i+1))
-  timeout -k 10 300 python bench.py --cpu-cols 0 "$@" > $OUT/bench_$i.log 2>&1
+  timeout -k 10 300 python bench.py --full --cpu-cols 0 "$@" > $OUT/bench_$i.log 2>&1
   python - "$OUT/bench_$i.log" "$*" <<'PY'
 import json, sys
 try:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Run ON the GPU box: bash tools/pmc_kernel.sh <tag> "<counters>" [bench args] -> per-kernel mean of each counter (one rocprofv3 --pmc pass)
 TAG=$1; CTR=$2; shift; shift
-OUT=$PWD/gpurun_out/$TAG; mkdir -p $OUT; REPO=$PWD
+OUT=$PWD/${LOGDIR:-logs}/$TAG; mkdir -p $OUT; REPO=$PWD
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 500 rocprofv3 --pmc $CTR --output-format csv -d $OUT/pmc -o pmc -- python3 $REPO/bench.py --cpu-cols 0 --steps 2 --warmup 1 "$@" > $OUT/pmc.log 2>&1
 python3 - $OUT <<'PY'

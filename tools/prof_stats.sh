@@ -1,7 +1,7 @@
 #!/bin/bash
-# Run ON the GPU box: bash tools/prof_stats.sh <tag> [bench args]  -> gpurun_out/<tag>/kernel_stats.csv (rocprofv3 --kernel-trace --stats)
+# Run ON the GPU box: bash tools/prof_stats.sh <tag> [bench args]  -> ${LOGDIR:-logs}/<tag>/kernel_stats.csv (rocprofv3 --kernel-trace --stats)
 TAG=${1:-prof}; shift
-OUT=$PWD/gpurun_out/$TAG; mkdir -p $OUT; REPO=$PWD
+OUT=$PWD/${LOGDIR:-logs}/$TAG; mkdir -p $OUT; REPO=$PWD
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 $REPO/bench.py --cpu-cols 0 --steps 5 --warmup 2 "$@" > $OUT/kt.log 2>&1
 find $OUT/kt -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;

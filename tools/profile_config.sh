@@ -2,15 +2,15 @@
 # Profile ONE bench configuration on the GPU box, from the repo root:
 #   bash tools/profile_config.sh <round tag> <name> <pmc tag: dtype|mode|NCOLxNLAYxNGPT> <bench.py arguments...>
 # e.g. bash tools/profile_config.sh r04 f32_allsky_ncol32768 "f32|broadband-allsky|32768x140x256" --dtype f32 --allsky --ncol 32768
-# Writes gpurun_out/<tag>/: the bench JSON line, the rocprofv3 kernel statistics of the same command, and FETCH_SIZE / WRITE_SIZE /
+# Writes ${LOGDIR:-logs}/<tag>/: the bench JSON line, the rocprofv3 kernel statistics of the same command, and FETCH_SIZE / WRITE_SIZE /
 # SQ counter passes (separate passes, no trace domain mixed in) summarised by tools/pmc_summary.py into <tag>_pmc_<name>.txt and
 # <tag>_pmc_traffic.json (merge that into profiles/pmc_traffic.json; bench.py reads roofline.traffic / roofline_valu from it).
 set -o pipefail
 export TMPDIR=/tmp
 TAG=$1; NAME=$2; PTAG=$3; shift 3
-OUT=$PWD/gpurun_out/$TAG; REPO=$PWD
+OUT=$PWD/${LOGDIR:-logs}/$TAG; REPO=$PWD
 mkdir -p $OUT
-timeout -k 10 400 python3 bench.py "$@" > $OUT/bench_$NAME.log 2>&1 || echo "bench $NAME FAILED"
+timeout -k 10 400 python3 bench.py --full "$@" > $OUT/bench_$NAME.log 2>&1 || echo "bench $NAME FAILED"
 grep '^{' $OUT/bench_$NAME.log | tail -1 > $OUT/${TAG}_bench_$NAME.json
 cd /tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$NAME -o kt -- python3 $REPO/bench.py "$@" --cpu-cols 0 > $OUT/kt_$NAME.log 2>&1 || echo "kernel trace $NAME FAILED"

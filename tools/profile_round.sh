@@ -1,16 +1,16 @@
 #!/bin/bash
 # Round profile, run ON the GPU box from the repo root:  bash tools/profile_round.sh <round tag, e.g. r01>
-# Writes gpurun_out/<tag>/: the bench JSON lines (both flux modes, both precisions), rocprofv3 kernel-trace stats of
+# Writes ${LOGDIR:-logs}/<tag>/: the bench JSON lines (both flux modes, both precisions), rocprofv3 kernel-trace stats of
 # the default bench command, and FETCH_SIZE / WRITE_SIZE counter passes (separate passes, no trace domains mixed in).
 set -o pipefail
 export TMPDIR=/tmp
 TAG=${1:-r01}
-OUT=$PWD/gpurun_out/$TAG
+OUT=$PWD/${LOGDIR:-logs}/$TAG
 REPO=$PWD
 mkdir -p $OUT
 for dt in f64 f32; do
   for mode in broadband per-gpoint; do
-    timeout -k 10 400 python3 bench.py --dtype $dt --flux-mode $mode > $OUT/bench_${dt}_${mode}.log 2>&1 || echo "bench $dt $mode FAILED"
+    timeout -k 10 400 python3 bench.py --full --dtype $dt --flux-mode $mode > $OUT/bench_${dt}_${mode}.log 2>&1 || echo "bench $dt $mode FAILED"
     grep '^{' $OUT/bench_${dt}_${mode}.log | tail -1 > $OUT/${TAG}_bench_${dt}_${mode}.json
     echo "bench $dt $mode done"
   done

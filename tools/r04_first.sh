@@ -2,7 +2,7 @@
 # round-4 opening measurements on the GPU box: fp32 issue costs, bench lines of the four configurations, fp32 all-sky kernel stats
 set -o pipefail
 export TMPDIR=/tmp
-OUT=$PWD/gpurun_out/r04a; mkdir -p $OUT; REPO=$PWD
+OUT=$PWD/${LOGDIR:-logs}/r04a; mkdir -p $OUT; REPO=$PWD
 timeout -k 10 200 tools/_build/issue_bench > $OUT/issue_costs.txt 2>&1; echo "issue bench rc=$?"
 SKIP_TESTS=1 bash tools/gpu_check.sh r04a_bench "" "--dtype f32" "--dtype f32 --allsky --ncol 32768" "--allsky" "--ncol 2048" "--dtype f32 --ncol 32768"
 cd /tmp

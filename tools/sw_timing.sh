@@ -2,8 +2,9 @@
 # Phase clocks of the fused SW and LW solvers (diagnostic build -DRRX_SW_TIMING=1 -DRRX_LW_TIMING=1): bash tools/sw_timing.sh
 # prints clocks per (workgroup, g-point) of wavefront 0: two-stream | direct beam | albedo | source | down scan | final replay | barrier waits | loop top
 export TMPDIR=/tmp
+mkdir -p ${LOGDIR:-logs}
 touch rte-rrtmgp-cpp_amd/csrc/rrx_solver_sw.hip rte-rrtmgp-cpp_amd/csrc/rrx_solver_lw.hip
-make -C rte-rrtmgp-cpp_amd/csrc EXTRA="-DRRX_SW_TIMING=1 -DRRX_LW_TIMING=1" > gpurun_out/swt_build.log 2>&1 || { echo BUILD FAIL; tail -5 gpurun_out/swt_build.log; exit 1; }
+make -C rte-rrtmgp-cpp_amd/csrc EXTRA="-DRRX_SW_TIMING=1 -DRRX_LW_TIMING=1" > ${LOGDIR:-logs}/swt_build.log 2>&1 || { echo BUILD FAIL; tail -5 ${LOGDIR:-logs}/swt_build.log; exit 1; }
 for args in "" "--dtype f32 --allsky --ncol 32768" "--dtype f32"; do
 python3 - $args <<'PY'
 import sys, ctypes, subprocess, json, os
