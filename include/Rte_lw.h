@@ -1,5 +1,8 @@
 /* Rte_lw_gpu -- interface of /root/reference/include/Rte_lw.h:62-80. Unlike the reference GPU class, broadband mode
- * (gpt_flux arrays with third dimension 1, as the CPU path uses: src/Rte_lw.cpp:176) and n_gauss_angles 1..4 work. */
+ * (gpt_flux arrays with third dimension 1, as the CPU path uses: src/Rte_lw.cpp:176) and n_gauss_angles 1..4 work.
+ * By-band mode: flux arrays with third dimension nband < ngpt receive the band sums of the g-point fluxes (the fused solver,
+ * rrx_lw_solver_noscat_fractions_byband; Planck-lite sources and one quadrature angle). rte_lw_byband also gives the band net
+ * flux and the broadband fluxes from the same solve. */
 #ifndef RTE_LW_H
 #define RTE_LW_H
 #include <memory>
@@ -19,6 +22,19 @@ class Rte_lw_gpu
                 Array_gpu<Float,3>& gpt_flux_up,
                 Array_gpu<Float,3>& gpt_flux_dn,
                 const int n_gauss_angles);
+        // by-band fluxes (ncol, nlev, nband); bnd_flux_net (dn - up per band) and the broadband flux_up/dn (the band sums added in
+        // band order) are written when their size is not 0
+        void rte_lw_byband(
+                const std::unique_ptr<Optical_props_arry_gpu>& optical_props,
+                const Bool top_at_1,
+                const Source_func_lw_gpu& sources,
+                const Array_gpu<Float,2>& sfc_emis,
+                const Array_gpu<Float,2>& inc_flux,
+                Array_gpu<Float,3>& bnd_flux_up,
+                Array_gpu<Float,3>& bnd_flux_dn,
+                Array_gpu<Float,3>& bnd_flux_net,
+                Array_gpu<Float,2>& flux_up,
+                Array_gpu<Float,2>& flux_dn);
         void expand_and_transpose(
                 const std::unique_ptr<Optical_props_arry_gpu>& ops,
                 const Array_gpu<Float,2> arr_in,

@@ -112,6 +112,16 @@ int rrx_sw_solver_2stream##SFX( \
         F* flux_up, F* flux_dn, F* flux_dir, \
         RrxBool has_dif_bc, const F* inc_flux_dif, \
         RrxBool do_broadband, F* flux_up_loc, F* flux_dn_loc, F* flux_dir_loc, void* stream); \
+/* sw_solver_2stream_byband: by-band fluxes from the fused broadband solver -- bnd_flux_* are (ncol, nlay+1, nbnd) arrays, \
+   bnd_flux(icol, ilev, ibnd) = the sum of the band's g-point fluxes (the g-points in order, as rrx_sum_byband); band_lims_gpt is \
+   (2, nbnd), 1-based and inclusive, a band with hi < lo is empty (zeros). bnd_flux_net = bnd_flux_dn - bnd_flux_up; flux_up/dn/dir \
+   = the band sums added in band order. Those four are optional (NULL: not written). Other arguments as rrx_sw_solver_2stream. */ \
+int rrx_sw_solver_2stream_byband##SFX( \
+        int ncol, int nlay, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const F* g, const F* mu0, const F* sfc_alb_dir, const F* sfc_alb_dif, \
+        const F* inc_flux_dir, RrxBool has_dif_bc, const F* inc_flux_dif, const int* band_lims_gpt, \
+        F* bnd_flux_up, F* bnd_flux_dn, F* bnd_flux_dir, F* bnd_flux_net, \
+        F* flux_up, F* flux_dn, F* flux_dir, void* stream); \
 /* ---- Gas_optics_rrtmgp_kernels_cuda : include_kernels_cuda/gas_optics_rrtmgp_kernels_cuda.h:33-132 ---- */ \
 int rrx_reorder123x321##SFX(int ni, int nj, int nk, const F* arr_in, F* arr_out, void* stream); \
 int rrx_reorder12x21##SFX(int ni, int nj, const F* arr_in, F* arr_out, void* stream); \
@@ -322,6 +332,14 @@ int rrx_lw_solver_noscat_fractions##SFX( \
         int ncol, int nlay, int ngpt, RrxBool top_at_1, const F* secants, const F* weights, \
         const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands, \
         const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up_loc, F* flux_dn_loc, void* stream); \
+/* by-band fluxes of rrx_lw_solver_noscat_fractions: bnd_flux_up/dn are (ncol, nlay+1, nbnd) band sums (layout and band_lims_gpt as \
+   rrx_sw_solver_2stream_byband); bnd_flux_net = dn - up per band, flux_up/dn = the band sums added in band order (optional, NULL: \
+   not written) */ \
+int rrx_lw_solver_noscat_fractions_byband##SFX( \
+        int ncol, int nlay, int ngpt, int nbnd, RrxBool top_at_1, const F* secants, const F* weights, \
+        const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands, const int* band_lims_gpt, \
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, \
+        F* bnd_flux_up, F* bnd_flux_dn, F* bnd_flux_net, F* flux_up, F* flux_dn, void* stream); \
 /* ---- Optical_props_kernels_cuda : include_kernels_cuda/optical_props_kernels_cuda.h:33-56 ---- */ \
 int rrx_increment_1scalar_by_1scalar##SFX(int ncol, int nlay, int ngpt, F* tau_inout, const F* tau_in, void* stream); \
 int rrx_increment_2stream_by_2stream##SFX(int ncol, int nlay, int ngpt, F* tau_inout, F* ssa_inout, F* g_inout, const F* tau_in, const F* ssa_in, const F* g_in, void* stream); \

@@ -8,7 +8,8 @@
  *     288 GB of HBM, and bigger blocks mean fewer, larger launches;
  *   - block-sized workspaces (optical props, sources, g-point fluxes) are cached across calls;
  *   - without --output-bnd-fluxes the solvers can run in broadband mode (set_broadband_solvers(true)), the CPU path's
- *     convention (src_test/Radiation_solver.cpp:518-527), which never materialises per-g-point fluxes.
+ *     convention (src_test/Radiation_solver.cpp:518-527), which never materialises per-g-point fluxes;
+ *   - with --output-bnd-fluxes the fused solvers can write the band sums themselves (set_byband_solvers(true), default off).
  */
 #ifndef RADIATION_SOLVER_H
 #define RADIATION_SOLVER_H
@@ -61,6 +62,9 @@ class Radiation_solver_longwave
 
         void set_column_block(const int n) { n_col_block = n; }
         void set_broadband_solvers(const bool b) { broadband_solvers = b; }
+        // With switch_output_bnd_fluxes: band fluxes from the fused solvers (one slab per band in the block workspace, Planck-lite
+        // LW chain) instead of per-g-point fluxes reduced by Fluxes_byband_gpu. Default off.
+        void set_byband_solvers(const bool b) { byband_solvers = b; }
         // Host-model coupling: the solver object is persistent -- k-distribution and LUTs stay on the device, block
         // workspaces are cached across calls -- and with the vertical ordering stated (0 = surface first, 1 = top first; -1 =
         // detect with the reference's synchronous read-backs) solve_gpu() enqueues everything on the calling thread's stream
@@ -86,6 +90,7 @@ class Radiation_solver_longwave
         int vertical_ordering = -1;
         int n_col_block = 16384;
         bool broadband_solvers = true;
+        bool byband_solvers = false;
 
         struct Workspace;
         std::shared_ptr<Workspace> ws_block, ws_residual;
@@ -135,6 +140,9 @@ class Radiation_solver_shortwave
 
         void set_column_block(const int n) { n_col_block = n; }
         void set_broadband_solvers(const bool b) { broadband_solvers = b; }
+        // With switch_output_bnd_fluxes: band fluxes from the fused solvers (one slab per band in the block workspace, Planck-lite
+        // LW chain) instead of per-g-point fluxes reduced by Fluxes_byband_gpu. Default off.
+        void set_byband_solvers(const bool b) { byband_solvers = b; }
         void set_vertical_ordering(const int top_at_1) { vertical_ordering = top_at_1; kdist_gpu->set_vertical_ordering(top_at_1); }
         // column order of a solve: see Radiation_solver_longwave
         void set_column_sorting(const int mode) { column_sorting = mode; sort_decided = -1; }
@@ -150,6 +158,7 @@ class Radiation_solver_shortwave
         int vertical_ordering = -1;
         int n_col_block = 16384;
         bool broadband_solvers = true;
+        bool byband_solvers = false;
 
         struct Workspace;
         std::shared_ptr<Workspace> ws_block, ws_residual;

@@ -338,6 +338,67 @@ namespace rrx
         }
         return best;
     }
+
+    // ---- by-band outputs of the broadband solvers (rrx_*_byband entries). Band limits: band_lims(2, nbnd), 1-based, inclusive, as
+    // rrx_sum_byband takes them; a band with hi < lo is empty (zeros).
+
+    // By-band sums of per-g-point fluxes (the route outside the one-kernel tilings): blockIdx.y = band, blockIdx.z = array a (its
+    // (ncl_lev, ngpt) fluxes start at in + a*ngpt*ncl_lev). The g-points of a band are added in order from zero, as rrx_sum_byband.
+    template<typename F>
+    __global__ void sum_bands_kernel(const size_t ncl_lev, const int ngpt, const int* __restrict__ band_lims, const F* __restrict__ in,
+                                     F* const o0, F* const o1, F* const o2)
+    {
+        const size_t i = size_t(blockIdx.x)*blockDim.x + threadIdx.x;
+        if (i >= ncl_lev) return;
+        const int b = blockIdx.y, a = blockIdx.z;
+        const int lo = max(band_lims[2*b] - 1, 0), hi = min(band_lims[2*b+1], ngpt);
+        const F* __restrict__ p = in + size_t(a)*ngpt*ncl_lev;
+        F s = F(0.);
+        for (int ig=lo; ig<hi; ++ig) add_rounded(s, p[i + size_t(ig)*ncl_lev]);
+        F* __restrict__ out = (a == 0) ? o0 : ((a == 1) ? o1 : o2);
+        out[i + size_t(b)*ncl_lev] = s;
+    }
+
+    // The outputs derived from the band sums (b0 = up, b1 = dn, b2 = dir; (ncl_lev, nbnd) each), in one pass: the broadband fluxes
+    // o_a = the band sums of array a added in band order, and the band net flux dn - up (net_byband_precalc's convention). Any
+    // output may be null.
+    template<typename F, int NARR>
+    __global__ void byband_outputs_kernel(const size_t ncl_lev, const int nbnd, const F* __restrict__ b0, const F* __restrict__ b1,
+                                          const F* __restrict__ b2, F* __restrict__ net, F* __restrict__ o0, F* __restrict__ o1,
+                                          F* __restrict__ o2)
+    {
+        const size_t i = size_t(blockIdx.x)*blockDim.x + threadIdx.x;
+        if (i >= ncl_lev) return;
+        #pragma unroll
+        for (int a=0; a<NARR; ++a)
+        {
+            const F* __restrict__ in = (a == 0) ? b0 : ((a == 1) ? b1 : b2);
+            F* __restrict__ out = (a == 0) ? o0 : ((a == 1) ? o1 : o2);
+            if (out == nullptr) continue;
+            F s = F(0.);
+            for (int b=0; b<nbnd; ++b) add_rounded(s, in[i + size_t(b)*ncl_lev]);
+            out[i] = s;
+        }
+        if (net != nullptr)
+            for (int b=0; b<nbnd; ++b) net[i + size_t(b)*ncl_lev] = b1[i + size_t(b)*ncl_lev] - b0[i + size_t(b)*ncl_lev];
+    }
+
+    // argument checks of the by-band entries, before any HIP call
+    inline void check_byband_args(const int ncol, const int nlay, const int ngpt, const int nbnd, const int* band_lims)
+    {
+        if (ncol <= 0 || nlay <= 0) throw std::runtime_error("empty problem");
+        if (ngpt < 1) throw std::runtime_error("ngpt must be >= 1");
+        if (nbnd < 1) throw std::runtime_error("nbnd must be >= 1");
+        if (band_lims == nullptr) throw std::runtime_error("band_lims_gpt is null");
+    }
+
+    template<typename F, int NARR>
+    void launch_byband_outputs(hipStream_t st, const size_t ncl_lev, const int nbnd, const F* b0, const F* b1, const F* b2,
+                               F* net, F* o0, F* o1, F* o2)
+    {
+        if (net == nullptr && o0 == nullptr && o1 == nullptr && (NARR < 3 || o2 == nullptr)) return;
+        byband_outputs_kernel<F,NARR><<<unsigned(ceil_div(ncl_lev, size_t(256))), 256, 0, st>>>(ncl_lev, nbnd, b0, b1, b2, net, o0, o1, o2);
+    }
 }
 
 #define RRX_TRY try {

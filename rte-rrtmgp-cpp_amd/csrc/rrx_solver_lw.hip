@@ -370,7 +370,9 @@ __device__ unsigned long long g_lw_clk[16][8];
 #ifndef RRX_LW_F32_WAVES
 #define RRX_LW_F32_WAVES 2
 #endif
-template<typename F, int V, int K, int W, int CLT, bool LITE, bool PRE, bool GS = false, int EV = RRX_LW_EV, int NW = (W > 4 ? W : 4)>
+// BND (by-band outputs): blockIdx.y = band b, whose g-points [band_lims[2b]-1, band_lims[2b+1]) the workgroup sums in order from zero
+// (rrx_sum_byband's order); the sums go to band slab b of flux_up/flux_dn, (ncol, nlev, nbnd) arrays. An empty band writes zeros.
+template<typename F, int V, int K, int W, int CLT, bool LITE, bool PRE, bool GS = false, int EV = RRX_LW_EV, int NW = (W > 4 ? W : 4), bool BND = false>
 __global__ void __launch_bounds__(64*NW, (NW > W) ? RRX_LW_F32_WAVES : (NW > 4 ? 1 : 2))
 lw_noscat_bb_kernel(
         const int ncol, const int nlay, const int ngpt, const int top_at_1,
@@ -378,11 +380,14 @@ lw_noscat_bb_kernel(
         const F* __restrict__ tau, const F* __restrict__ lay_source /* or pfrac */, const F* __restrict__ lev_source,
         const F* __restrict__ blay, const F* __restrict__ blev, const int* __restrict__ gpoint_bands,
         const F* __restrict__ sfc_emis, const F* __restrict__ sfc_src, const F* __restrict__ inc_flux,
-        F* __restrict__ flux_up, F* __restrict__ flux_dn, const int gper, const size_t part_stride)
+        F* __restrict__ flux_up, F* __restrict__ flux_dn, const int gper, const size_t part_stride,
+        const int* __restrict__ band_lims)
 {
+    static_assert(!(GS && BND), "a by-band launch is its own g-point split");
     // GS: blockIdx.y = g-point range [g_lo, g_hi) of this workgroup; its sums go to partial array blockIdx.y
-    const int g_lo = GS ? blockIdx.y*gper : 0, g_hi = GS ? min(ngpt, g_lo + gper) : ngpt;
-    if constexpr (GS) { flux_up += blockIdx.y*part_stride; flux_dn += blockIdx.y*part_stride; }
+    const int g_lo = BND ? max(band_lims[2*blockIdx.y] - 1, 0) : (GS ? blockIdx.y*gper : 0);
+    const int g_hi = BND ? min(band_lims[2*blockIdx.y+1], ngpt) : (GS ? min(ngpt, g_lo + gper) : ngpt);
+    if constexpr (GS || BND) { flux_up += blockIdx.y*part_stride; flux_dn += blockIdx.y*part_stride; }
     constexpr int CL = CLT, LL = 64/CLT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cl = lane & (CL-1), ll = lane / CL;
@@ -456,7 +461,7 @@ lw_noscat_bb_kernel(
     };
 
     Loads nxt;
-    if constexpr (PRE) issue(g_lo, nxt);
+    if constexpr (PRE) { if (!BND || g_lo < g_hi) issue(g_lo, nxt); }     // (an empty band prefetches nothing: g_lo may be ngpt)
     int cur_bnd = -1;
     const F wgt = weights[0];
     const F scale = pi * wgt;
@@ -863,29 +868,48 @@ bool launch_bb2(
         hipStream_t st, const bool pre, const int ncol, const int nlay, const int ngpt, const int top_at_1,
         const F* secants, const F* weights, const F* tau, const F* lay_source, const F* lev_source,
         const F* blay, const F* blev, const int* gpoint_bands,
-        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn)
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn,
+        const int* band_lims = nullptr, const int nbnd = 0 /* by-band form: flux_up/dn are (ncol, nlev, nbnd) band sums */)
 {
     if (size_t(ncol)*(nlay+1) >= (size_t(1) << 31)) return false;          // 32-bit element offsets inside a g-point slab
     const int groups = ceil_div(ncol, (NW/W)*CLT*V);
     const int need = ceil_div(nlay+1, (64/CLT)*W);
     if (need > ((CLT == 16 || W == 8) ? 9 : 5)) return false;
+    const size_t nlevcol = size_t(ncol)*(nlay+1);
+    if (band_lims != nullptr)
+    {
+        // one band per workgroup (grid.y = band): no store inside the g-point loop, no partial arrays, no allocation. Always the
+        // pipelined form. Planck-lite inputs only (the by-band entry is rrx_lw_solver_noscat_fractions_byband).
+        if constexpr (LITE)
+        {
+            const dim3 grid(groups, nbnd);
+#define RRX_LW_BND(KK) if (need <= KK) { \
+            lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,true,false,RRX_LW_EV,NW,true><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, \
+                lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, 0, nlevcol, band_lims); \
+            return true; }
+            if constexpr (CLT == 16) { RRX_LW_BND(2) RRX_LW_BND(4) RRX_LW_BND(6) RRX_LW_BND(9) }
+            else if constexpr (W == 8) { RRX_LW_BND(5) RRX_LW_BND(7) RRX_LW_BND(9) }
+            else                     { RRX_LW_BND(2) RRX_LW_BND(3) RRX_LW_BND(5) }
+#undef RRX_LW_BND
+        }
+        return false;
+    }
     // few column groups: the g-point loop is split over grid.y, partial sums added in range order afterwards
     const int gper = ceil_div(ngpt, broadband_gsplit(groups, ngpt, (NW > 4) ? 256 : 512));      // (one or two workgroups per CU)
     const int nsplit = ceil_div(ngpt, gper);               // no empty range: every workgroup's first g-point exists (it is prefetched)
-    const size_t nlevcol = size_t(ncol)*(nlay+1);
     StreamScratch scratch(st);
     F* out_up = flux_up; F* out_dn = flux_dn;
     if (nsplit > 1) { out_up = scratch.get<F>(2*nsplit*nlevcol); out_dn = out_up + nsplit*nlevcol; }
     const dim3 grid(groups, nsplit);
 #define RRX_LW_B2(KK) if (need <= KK) { \
         if (nsplit > 1 && pre) lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,true,true,RRX_LW_EV,NW><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, \
-            lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, gper, nlevcol); \
+            lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, gper, nlevcol, nullptr); \
         else if (nsplit > 1) lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,false,true,RRX_LW_EV,NW><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, \
-            lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, gper, nlevcol); \
+            lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, gper, nlevcol, nullptr); \
         else if (pre) lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,true,false,RRX_LW_EV,NW><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, \
-            lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, gper, nlevcol); \
+            lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, gper, nlevcol, nullptr); \
         else lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,false,false,RRX_LW_EV,NW><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, \
-            lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, gper, nlevcol); \
+            lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, gper, nlevcol, nullptr); \
         break; }
     do {
     if constexpr (CLT == 16) { RRX_LW_B2(2) RRX_LW_B2(4) RRX_LW_B2(6) RRX_LW_B2(9) }
@@ -905,7 +929,8 @@ bool lw_fused_broadband(
         hipStream_t st, const int ncol, const int nlay, const int ngpt, const int top_at_1,
         const F* secants, const F* weights, const F* tau, const F* lay_source, const F* lev_source,
         const F* blay, const F* blev, const int* gpoint_bands,
-        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn)
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn,
+        const int* band_lims = nullptr, const int nbnd = 0 /* by-band form (launch_bb2) */)
 {
     const bool pre = tuning().lw_variant != 13;                 // 13: without the pipelined loads (A/B runs)
     // fp32: 16 x 4 lanes with two columns per lane (128-B rows, K = 9) ahead of 8 x 8 lanes with four (variant 14 = the latter
@@ -916,18 +941,18 @@ bool lw_fused_broadband(
         // (Round 4 measured six waves x six layers per column group -- 384-thread workgroups, three waves per SIMD, 168 VGPRs with
         //  108-124 B of scratch: 4.2-4.7 ms against 2.7 for this form, profiles/r04_fp32_geometry_ab.txt.)
         if (launch_bb2<F,1,4,16,LITE>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn))
+                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd))
             return true;
         // 144 ... 287 layers: eight wavefronts per column group
         if (launch_bb2<F,1,8,16,LITE>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn))
+                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd))
             return true;
         // 288 ... 575 layers (round 4: RCEMIP's default is 256 levels, LES grids with a background profile on top exceed 288): the same
         // eight waves with 8 x 8 lanes -- 64 levels per wave at nine layers per lane, 64-B rows (the other half of each 128-B line
         // belongs to the next column group: twice the L2 fetches, on a kernel that stands at a quarter of the HBM roof). Beyond that
         // the one-thread-per-column kernels take over.
         return launch_bb2<F,1,8,8,LITE>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                        blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn);
+                                        blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd);
     }
     else
     {
@@ -938,33 +963,33 @@ bool lw_fused_broadband(
         // The one-column form stays for odd column counts (variant 15 forces it for tests).
         if (tuning().lw_variant == 15 &&
             launch_bb2<F,1,4,16,LITE,8>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                        blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn))
+                                        blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd))
             return true;
         if (ncol % 2 == 0 && v2_first &&
             launch_bb2<F,2,4,16,LITE>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn))
+                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd))
             return true;
         if (ncol % 4 == 0 &&
             launch_bb2<F,4,4,8,LITE>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                     blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn))
+                                     blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd))
             return true;
         if (ncol % 2 == 0 &&
             launch_bb2<F,2,4,16,LITE>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn))
+                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd))
             return true;
         // 144 ... 287 layers: eight wavefronts per column group
         if (ncol % 2 == 0 &&
             launch_bb2<F,2,8,16,LITE>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn))
+                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd))
             return true;
         // 288 ... 575 layers: eight waves of 8 x 8 lanes (see fp64)
         if (ncol % 2 == 0 &&
             launch_bb2<F,2,8,8,LITE>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                     blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn))
+                                     blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd))
             return true;
         // odd column counts: one column per lane
         return launch_bb2<F,1,4,16,LITE,8>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                           blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn);
+                                           blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd);
     }
 }
 
@@ -1150,6 +1175,44 @@ int lw_solver_noscat_fractions_impl(
                                       flux_ws);
     return rc;
 }
+
+// by-band fluxes (rrx_lw_solver_noscat_fractions_byband): the one-kernel form with one band per workgroup where the tilings reach,
+// otherwise the route of the broadband entry there (sources rebuilt, per-g-point fluxes in the stream's workspace lease) followed by
+// the band sums. Band net and broadband outputs come from the band sums in one more pass.
+template<typename F>
+int lw_solver_noscat_fractions_byband_impl(
+        const int ncol, const int nlay, const int ngpt, const int nbnd, const Bool top_at_1,
+        const F* secants, const F* weights, const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands,
+        const int* band_lims, const F* sfc_emis, const F* sfc_src, const F* inc_flux,
+        F* bnd_up, F* bnd_dn, F* bnd_net, F* flux_up, F* flux_dn, void* stream)
+{
+    RRX_TRY
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    check_byband_args(ncol, nlay, ngpt, nbnd, band_lims);
+    if (gpoint_bands == nullptr) throw std::runtime_error("gpoint_bands is null");
+    if (bnd_up == nullptr || bnd_dn == nullptr) throw std::runtime_error("band flux outputs missing");
+    const size_t nlevcol = size_t(ncol)*(nlay+1);
+    const int var = tuning().lw_variant;
+    const bool fused = (var == 0 || (var >= 13 && var <= 15)) &&
+        lw_fused_broadband<F,true>(st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, (const F*)nullptr,
+                                   blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, bnd_up, bnd_dn, band_lims, nbnd);
+    if (!fused)
+    {
+        const size_t n_lay = size_t(ncol)*nlay*ngpt, n_lev = nlevcol*ngpt;
+        WorkspaceLease lease(st);
+        F* flux_ws = lease.get<F>(2*n_lev + n_lay + n_lev);          // [per-g-point up | dn | lay_source | lev_source]
+        F* lay = flux_ws + 2*n_lev; F* lev = lay + n_lay;
+        if (planck_sources_from_fractions_impl<F>(ncol, nlay, ngpt, gpoint_bands, pfrac, blay, blev, lay, lev, stream) != 0 ||
+            lw_solver_noscat_impl<F>(ncol, nlay, ngpt, top_at_1, 1, secants, weights, tau, lay, lev, sfc_emis, sfc_src, inc_flux,
+                                     flux_ws, flux_ws + n_lev, Bool(0), (F*)nullptr, (F*)nullptr, Bool(0), (const F*)nullptr,
+                                     (F*)nullptr, stream) != 0)
+            return 1;                                                // (the message is set)
+        sum_bands_kernel<F><<<dim3(ceil_div(nlevcol, 256), nbnd, 2), 256, 0, st>>>(nlevcol, ngpt, band_lims, flux_ws, bnd_up, bnd_dn,
+                                                                                      (F*)nullptr);
+    }
+    launch_byband_outputs<F,2>(st, nlevcol, nbnd, bnd_up, bnd_dn, (const F*)nullptr, bnd_net, flux_up, flux_dn, (F*)nullptr);
+    RRX_CATCH("rrx_lw_solver_noscat_fractions_byband")
+}
 }  // namespace
 
 
@@ -1222,7 +1285,16 @@ int rrx_lw_solver_noscat_fractions##SFX( \
 } \
 int rrx_planck_sources_from_fractions##SFX(int ncol, int nlay, int ngpt, const int* gpoint_bands, const F* pfrac, const F* blay, \
         const F* blev, F* lay_src, F* lev_src, void* stream) \
-{ return planck_sources_from_fractions_impl<F>(ncol, nlay, ngpt, gpoint_bands, pfrac, blay, blev, lay_src, lev_src, stream); }
+{ return planck_sources_from_fractions_impl<F>(ncol, nlay, ngpt, gpoint_bands, pfrac, blay, blev, lay_src, lev_src, stream); } \
+int rrx_lw_solver_noscat_fractions_byband##SFX( \
+        int ncol, int nlay, int ngpt, int nbnd, Bool top_at_1, const F* secants, const F* weights, \
+        const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands, const int* band_lims_gpt, \
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, \
+        F* bnd_flux_up, F* bnd_flux_dn, F* bnd_flux_net, F* flux_up, F* flux_dn, void* stream) \
+{ \
+    return lw_solver_noscat_fractions_byband_impl<F>(ncol, nlay, ngpt, nbnd, top_at_1, secants, weights, tau, pfrac, blay, blev, \
+            gpoint_bands, band_lims_gpt, sfc_emis, sfc_src, inc_flux, bnd_flux_up, bnd_flux_dn, bnd_flux_net, flux_up, flux_dn, stream); \
+}
 
 RRX_DEFINE_LW_FRACTIONS(double, _f64)
 RRX_DEFINE_LW_FRACTIONS(float, _f32)

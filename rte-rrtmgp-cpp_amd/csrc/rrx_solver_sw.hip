@@ -148,15 +148,20 @@ __device__ __forceinline__ TwoStream<F> two_stream(const F tau, const F ssa, con
 // three waves per SIMD against 3.8 at two (tools/issue_mix_bench.hip): 3.11 -> 2.24 ms at C4, 7.07 -> 5.53 ms all-sky at 32 768
 // columns. The 64-B rows of a group are then half a 128-B line whose other half belongs to the next workgroup (L2 serves it);
 // compiled for four waves per SIMD the same form spills (2.65 / 9.3 ms).
-template<typename F, int V, int K, int W, bool BB = false, bool GZ = false, bool PRE = false, bool GS = false, int NW = (W > 2 ? 2*W : 4), int CLT = 8>
+// BND (BB form, by-band outputs): blockIdx.y = band b, whose g-points [band_lims[2b]-1, band_lims[2b+1]) the workgroup sums in order from
+// zero (rrx_sum_byband's order) into band slab b of flux_up/dn/dir, (ncol, nlev, nbnd) arrays; an empty band writes zeros.
+template<typename F, int V, int K, int W, bool BB = false, bool GZ = false, bool PRE = false, bool GS = false, int NW = (W > 2 ? 2*W : 4), int CLT = 8,
+         bool BND = false>
 __global__ void __launch_bounds__(64*NW, (CLT == 16) ? ((NW == 4) ? RRX_SW_F32_WAVES1 : RRX_SW_F32_WAVES) : ((NW > 4) ? 1 : ((W == 2 && V*sizeof(F) <= 8) ? RRX_SW_MINWAVES2 : RRX_SW_MINWAVES)))
 sw_2stream_scan_kernel(
         const int ncol, const int nlay, const int ngpt, const int top_at_1,
         const F* __restrict__ tau, const F* __restrict__ ssa, const F* __restrict__ g, const F* __restrict__ mu0,
         const F* __restrict__ sfc_alb_dir, const F* __restrict__ sfc_alb_dif,
         const F* __restrict__ inc_flux_dir, const F* __restrict__ inc_flux_dif,
-        F* __restrict__ flux_up, F* __restrict__ flux_dn, F* __restrict__ flux_dir, const int sync_waves, const int gper)
+        F* __restrict__ flux_up, F* __restrict__ flux_dn, F* __restrict__ flux_dir, const int sync_waves, const int gper,
+        const int* __restrict__ band_lims)
 {
+    static_assert(!BND || (BB && !GS), "the by-band form is a broadband form with its own g-point split");
     constexpr int CL = CLT, LL = 64/CLT;              // shadow the default geometry
     // per-thread private LDS columns (dynamic register indexing is not needed: j is a compile-time constant, but
     // two of the six per-layer arrays live here so that the kernel fits 2 waves per SIMD)
@@ -203,8 +208,8 @@ sw_2stream_scan_kernel(
     }
 
     // BB: blockIdx.y = g-point range of this workgroup, its sums go to partial array blockIdx.y (one range: the outputs)
-    const int g_begin = BB ? (GS ? blockIdx.y*gper : 0) : blockIdx.y;
-    const int g_end = BB ? (GS ? min(ngpt, g_begin + gper) : ngpt) : blockIdx.y + 1;
+    const int g_begin = BND ? max(band_lims[2*blockIdx.y] - 1, 0) : (BB ? (GS ? blockIdx.y*gper : 0) : blockIdx.y);
+    const int g_end = BND ? min(band_lims[2*blockIdx.y+1], ngpt) : (BB ? (GS ? min(ngpt, g_begin + gper) : ngpt) : blockIdx.y + 1);
 
     // PRE: element offset of layer j inside one g-point slab, recomputed where needed (9 registers less than keeping them)
     auto off_of = [&](const int j) -> unsigned
@@ -217,6 +222,7 @@ sw_2stream_scan_kernel(
     {
         static_assert(BB && W >= 2, "the pipelined form is the fused broadband kernel");
         static_assert(GZ || sizeof(F) == 4, "fp64 with a g array: 27 prefetched doubles per lane spill (5.8 -> 7.2 ms, round 3)");
+        if (!BND || g_begin < g_end) {                      // (an empty band prefetches nothing: g_begin may be ngpt)
         const F* __restrict__ tau_0 = tau + size_t(g_begin)*ncl*nlay;
         const F* __restrict__ ssa_0 = ssa + size_t(g_begin)*ncl*nlay;
         #pragma unroll
@@ -229,6 +235,7 @@ sw_2stream_scan_kernel(
         }
         const size_t s0 = size_t(g_begin)*ncl + icol;
         n_inc = load_cols<F,V>(inc_flux_dir + s0); n_adir = load_cols<F,V>(sfc_alb_dir + s0); n_adif = load_cols<F,V>(sfc_alb_dif + s0);
+        }
     }
 
 #if RRX_SW_TIMING
@@ -658,7 +665,7 @@ sw_2stream_scan_kernel(
             if (t <= nlay)
             {
                 const int ml = top_at_1 ? t : nlay - t;
-                const size_t o = size_t(icol) + size_t(ml)*ncl + (GS ? size_t(blockIdx.y)*ncl*nlev : size_t(0));
+                const size_t o = size_t(icol) + size_t(ml)*ncl + ((GS || BND) ? size_t(blockIdx.y)*ncl*nlev : size_t(0));
                 Vec<F,V> u, d, r;
                 #pragma unroll
                 for (int v=0; v<V; ++v) { u.v[v] = lds_acc_up[j*V+v][tid]; d.v[v] = lds_acc_dn[j*V+v][tid]; r.v[v] = acc_dir[j][v]; }
@@ -789,7 +796,7 @@ bool launch_scan(hipStream_t st,
     const int need = ceil_div(nlay+1, LL*W);
 #define RRX_SW_K(KK) if (need <= KK) { sw_2stream_scan_kernel<F,V,KK,W><<<grid, 256, 0, st>>>( \
         ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, inc_flux_dif, \
-        flux_up, flux_dn, flux_dir, tuning().sync_waves, 1); return true; }
+        flux_up, flux_dn, flux_dir, tuning().sync_waves, 1, nullptr); return true; }
     if constexpr (W == 1) { RRX_SW_K(4) RRX_SW_K(8) RRX_SW_K(12) RRX_SW_K(18) RRX_SW_K(24) RRX_SW_K(33) }
     else                  { RRX_SW_K(2) RRX_SW_K(4) RRX_SW_K(6)  RRX_SW_K(9)  RRX_SW_K(12) RRX_SW_K(17) }
 #undef RRX_SW_K
@@ -805,7 +812,8 @@ template<typename F, int V, int W = 2, int CLT = 8, int NWG = (W > 2 ? 2*W : 4)>
 bool launch_scan_bb(hipStream_t st,
         const int ncol, const int nlay, const int ngpt, const int top_at_1,
         const F* tau, const F* ssa, const F* g, const F* mu0, const F* sfc_alb_dir, const F* sfc_alb_dif,
-        const F* inc_flux_dir, const F* inc_flux_dif, F* flux_up, F* flux_dn, F* flux_dir)
+        const F* inc_flux_dir, const F* inc_flux_dif, F* flux_up, F* flux_dn, F* flux_dir,
+        const int* band_lims = nullptr, const int nbnd = 0 /* by-band form: flux_* are (ncol, nlev, nbnd) band sums */)
 {
     constexpr int NW = NWG;                               // wavefronts per workgroup: two column groups (one where NWG == W)
     constexpr int KMAX = (CLT == 16) ? 12 : (W > 2 ? 9 : 12);       // (8 x 8 lanes, W = 4: nine layers per lane fill the LDS of a CU)
@@ -816,15 +824,46 @@ bool launch_scan_bb(hipStream_t st,
     // (two columns per lane: 140 B of scratch per lane, 4.00 against 3.63 ms at C4)
     const bool pre = tuning().sw_variant != 8 && size_t(ncol)*nlay < (size_t(1) << 31)
                      && (sizeof(F) == 8 ? g == nullptr : (V == 1 && CLT == 16));
+    const size_t nlevcol = size_t(ncol)*(nlay+1);
+    const int sync_waves = tuning().sync_waves;
+#define RRX_SW_K(KK) if (need <= KK) { launch(std::integral_constant<int,KK>{}); break; }
+#define RRX_SW_KS \
+    do \
+    { \
+        if constexpr (CLT == 16) { RRX_SW_K(2) RRX_SW_K(4) RRX_SW_K(6) RRX_SW_K(9) RRX_SW_K(12) } \
+        else if constexpr (W == 2) { RRX_SW_K(2) RRX_SW_K(4) RRX_SW_K(6) RRX_SW_K(9) RRX_SW_K(12) } \
+        else if constexpr (W == 8) { RRX_SW_K(5) RRX_SW_K(7) RRX_SW_K(9) }      /* (288 ... 319 / 447 / 575 layers) */ \
+        else { RRX_SW_K(9) } \
+    } while (false);
+    if (band_lims != nullptr)
+    {
+        // one band per workgroup (grid.y = band): no store inside the g-point loop, no partial arrays, no allocation. Not the fp32
+        // two-column 8 x 8 form, which only variant 9 reaches (its by-band twin at K = 12 puts one more VGPR into AGPRs): the four-wave
+        // form takes those columns.
+        if constexpr (sizeof(F) == 4 && V == 2 && W == 2) return false;
+        const dim3 grid(groups, nbnd);
+        auto launch = [&](auto kk)
+        {
+            constexpr int KK = decltype(kk)::value;
+            with_flag(g == nullptr, [&](auto gz) { with_flag(pre, [&](auto pr)
+            {
+                constexpr bool GZ = decltype(gz)::value;
+                constexpr bool PRE = decltype(pr)::value && (sizeof(F) == 8 ? GZ : (V == 1 && CLT == 16));
+                sw_2stream_scan_kernel<F,V,KK,W,true,GZ,PRE,false,NW,CLT,true><<<grid, 64*NW, 0, st>>>(
+                    ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, inc_flux_dif,
+                    flux_up, flux_dn, flux_dir, sync_waves, 0, band_lims);
+            }); });
+        };
+        RRX_SW_KS
+        return true;
+    }
     // few column groups: the g-point loop is split over grid.y, partial sums added in range order afterwards
     const int gper = ceil_div(ngpt, broadband_gsplit(groups, ngpt, (NW > 4) ? 256 : ((CLT == 16) ? 256*RRX_SW_F32_WAVES1 : 512)));      // (one or two workgroups per CU)
     const int nsplit = ceil_div(ngpt, gper);               // no empty range: every workgroup's first g-point exists (it is prefetched)
-    const size_t nlevcol = size_t(ncol)*(nlay+1);
     StreamScratch scratch(st);
     F* up = flux_up; F* dn = flux_dn; F* dr = flux_dir;
     if (nsplit > 1) { up = scratch.get<F>(3*nsplit*nlevcol); dn = up + nsplit*nlevcol; dr = dn + nsplit*nlevcol; }
     const dim3 grid(groups, nsplit);
-    const int sync_waves = tuning().sync_waves;
     auto launch = [&](auto kk)
     {
         constexpr int KK = decltype(kk)::value;
@@ -835,21 +874,58 @@ bool launch_scan_bb(hipStream_t st,
             constexpr bool PRE = decltype(pr)::value && (sizeof(F) == 8 ? GZ : (V == 1 && CLT == 16));
             sw_2stream_scan_kernel<F,V,KK,W,true,GZ,PRE,GS,NW,CLT><<<grid, 64*NW, 0, st>>>(
                 ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, inc_flux_dif,
-                up, dn, dr, sync_waves, gper);
+                up, dn, dr, sync_waves, gper, nullptr);
         }); }); });
     };
-#define RRX_SW_K(KK) if (need <= KK) { launch(std::integral_constant<int,KK>{}); break; }
-    do
-    {
-        if constexpr (CLT == 16) { RRX_SW_K(2) RRX_SW_K(4) RRX_SW_K(6) RRX_SW_K(9) RRX_SW_K(12) }
-        else if constexpr (W == 2) { RRX_SW_K(2) RRX_SW_K(4) RRX_SW_K(6) RRX_SW_K(9) RRX_SW_K(12) }
-        else if constexpr (W == 8) { RRX_SW_K(5) RRX_SW_K(7) RRX_SW_K(9) }      // (288 ... 319 / 447 / 575 layers)
-        else { RRX_SW_K(9) }
-    } while (false);
+    RRX_SW_KS
+#undef RRX_SW_KS
 #undef RRX_SW_K
     if (nsplit > 1)      // (up, dn, dr lie behind each other in the scratch block)
         sum_ranges_kernel<F,3><<<dim3(ceil_div(nlevcol, 256), 3), 256, 0, st>>>(nlevcol, nsplit, up, flux_up, flux_dn, flux_dir);
     return true;
+}
+
+// the fused broadband kernels (launch_scan_bb) in the order of preference; false when no form takes the shape. band_lims != null:
+// the by-band form, flux_* are then (ncol, nlev, nbnd) band sums
+template<typename F>
+bool sw_fused_broadband(
+        hipStream_t st, const int ncol, const int nlay, const int ngpt, const Bool top_at_1,
+        const F* tau, const F* ssa, const F* g, const F* mu0, const F* sfc_alb_dir, const F* sfc_alb_dif, const F* inc_flux_dir,
+        const F* dif, F* flux_up_loc, F* flux_dn_loc, F* flux_dir_loc, const int* band_lims = nullptr, const int nbnd = 0)
+{
+    const int g_sw_variant = tuning().sw_variant;
+    constexpr int VBB = (sizeof(F) == 8) ? 1 : 2;
+    // (variant 8: fused broadband form without the pipelined loads, for A/B runs)
+    if (g_sw_variant == 1 || g_sw_variant == 7 || (ncol % VBB != 0 && sizeof(F) != 4)) return false;
+    // fp32: one column per lane, 16 x 4 lanes, four waves per column group (up to 191 layers); variant 9 = the two-columns-
+    // per-lane form of rounds 1-3 for A/B runs
+    if constexpr (sizeof(F) == 4)
+    {
+        // up to 143 layers (nine per lane): one column group per workgroup at three waves per SIMD; 144-191 (twelve per lane, which
+        // spills at 168 VGPRs): two groups per workgroup at two waves per SIMD
+        if (g_sw_variant != 9 && ceil_div(nlay+1, 16) <= 9 &&
+            launch_scan_bb<F,1,4,16,RRX_SW_F32_NW>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif,
+                                                   inc_flux_dir, dif, flux_up_loc, flux_dn_loc, flux_dir_loc, band_lims, nbnd))
+            return true;
+        if (g_sw_variant != 9 &&
+            launch_scan_bb<F,1,4,16>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif,
+                                     inc_flux_dir, dif, flux_up_loc, flux_dn_loc, flux_dir_loc, band_lims, nbnd))
+            return true;
+    }
+    if (ncol % VBB == 0 &&
+        launch_scan_bb<F,VBB>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif,
+                              inc_flux_dir, dif, flux_up_loc, flux_dn_loc, flux_dir_loc, band_lims, nbnd))
+        return true;
+    // 192 ... 287 layers: four wavefronts per column group
+    if (ncol % VBB == 0 &&
+        launch_scan_bb<F,VBB,4>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif,
+                                inc_flux_dir, dif, flux_up_loc, flux_dn_loc, flux_dir_loc, band_lims, nbnd))
+        return true;
+    // 288 ... 575 layers (round 4): eight wavefronts on ONE column group per workgroup (64 levels per wave at nine layers per lane;
+    // the row segments are 64 B with no partner group in the workgroup: twice the L2 fetches, on a kernel bound by fp64 issue)
+    return ncol % VBB == 0 &&
+        launch_scan_bb<F,VBB,8,8,8>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif,
+                                    inc_flux_dir, dif, flux_up_loc, flux_dn_loc, flux_dir_loc, band_lims, nbnd);
 }
 
 template<typename F>
@@ -859,53 +935,24 @@ int sw_solver_2stream_impl(
         const F* sfc_alb_dir, const F* sfc_alb_dif, const F* inc_flux_dir,
         F* flux_up, F* flux_dn, F* flux_dir,
         const Bool has_dif_bc, const F* inc_flux_dif,
-        const Bool do_broadband, F* flux_up_loc, F* flux_dn_loc, F* flux_dir_loc, void* stream)
+        const Bool do_broadband, F* flux_up_loc, F* flux_dn_loc, F* flux_dir_loc, void* stream,
+        const int nbnd = 0, const int* band_lims = nullptr /* by-band sums into flux_*_loc, (ncol, nlev, nbnd): the per-g-point route only */)
 {
     RRX_TRY
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (ncol <= 0 || nlay <= 0 || ngpt <= 0) throw std::runtime_error("empty problem");
     const F* dif = has_dif_bc ? inc_flux_dif : nullptr;
     const int g_sw_variant = tuning().sw_variant;
-    const int g_bb_min_groups = tuning().bb_min_groups;
+    const bool byband = band_lims != nullptr;
 
     // broadband mode, fused form (see the kernel's BB note): one workgroup per column group sums all g-points in order when the
     // column groups alone fill the chip, otherwise the g-point range is split over grid.y (rrx::broadband_gsplit)
-    constexpr int VBB = (sizeof(F) == 8) ? 1 : 2;
-    (void)g_bb_min_groups;
-    // (variant 8: fused broadband form without the pipelined loads, for A/B runs)
-    if (do_broadband && g_sw_variant != 1 && g_sw_variant != 7 && (ncol % VBB == 0 || sizeof(F) == 4))
+    if (do_broadband && !byband)
     {
         if (flux_up_loc == nullptr || flux_dn_loc == nullptr || flux_dir_loc == nullptr)
             throw std::runtime_error("do_broadband needs flux_*_loc");
-        // fp32: one column per lane, 16 x 4 lanes, four waves per column group (up to 191 layers); variant 9 = the two-columns-
-        // per-lane form of rounds 1-3 for A/B runs
-        if constexpr (sizeof(F) == 4)
-        {
-            // up to 143 layers (nine per lane): one column group per workgroup at three waves per SIMD; 144-191 (twelve per lane, which
-            // spills at 168 VGPRs): two groups per workgroup at two waves per SIMD
-            if (g_sw_variant != 9 && ceil_div(nlay+1, 16) <= 9 &&
-                launch_scan_bb<F,1,4,16,RRX_SW_F32_NW>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif,
-                                                       inc_flux_dir, dif, flux_up_loc, flux_dn_loc, flux_dir_loc))
-                return 0;
-            if (g_sw_variant != 9 &&
-                launch_scan_bb<F,1,4,16>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif,
-                                         inc_flux_dir, dif, flux_up_loc, flux_dn_loc, flux_dir_loc))
-                return 0;
-        }
-        if (ncol % VBB == 0 &&
-            launch_scan_bb<F,VBB>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif,
-                                  inc_flux_dir, dif, flux_up_loc, flux_dn_loc, flux_dir_loc))
-            return 0;
-        // 192 ... 287 layers: four wavefronts per column group
-        if (ncol % VBB == 0 &&
-            launch_scan_bb<F,VBB,4>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif,
-                                    inc_flux_dir, dif, flux_up_loc, flux_dn_loc, flux_dir_loc))
-            return 0;
-        // 288 ... 575 layers (round 4): eight wavefronts on ONE column group per workgroup (64 levels per wave at nine layers per lane;
-        // the row segments are 64 B with no partner group in the workgroup: twice the L2 fetches, on a kernel bound by fp64 issue)
-        if (ncol % VBB == 0 &&
-            launch_scan_bb<F,VBB,8,8,8>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif,
-                                        inc_flux_dir, dif, flux_up_loc, flux_dn_loc, flux_dir_loc))
+        if (sw_fused_broadband<F>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, dif,
+                                  flux_up_loc, flux_dn_loc, flux_dir_loc))
             return 0;
     }
 
@@ -913,7 +960,8 @@ int sw_solver_2stream_impl(
     // the large temporaries of these forms come from one cached block per stream (rrx::cached_workspace): [g zeros][3 per-g-point
     // flux arrays][the serial kernel's seven cell / level arrays]
     const size_t nlevcol = size_t(ncol)*(nlay+1);
-    const size_t w_g = (g == nullptr) ? size_t(ncol)*nlay*ngpt : 0, w_flux = do_broadband ? 3*nlevcol*ngpt : 0;
+    const bool gpt_ws = do_broadband || byband;
+    const size_t w_g = (g == nullptr) ? size_t(ncol)*nlay*ngpt : 0, w_flux = gpt_ws ? 3*nlevcol*ngpt : 0;
     const size_t w_serial = 5*size_t(ncol)*nlay*ngpt + 2*nlevcol*ngpt;
     // (one lease per call: the serial kernel's part is asked for up front whenever it could be needed)
     WorkspaceLease lease(st);
@@ -926,7 +974,7 @@ int sw_solver_2stream_impl(
     }
 
     F* up = flux_up; F* dn = flux_dn; F* dr = flux_dir;
-    if (do_broadband)
+    if (gpt_ws)
     {
         if (flux_up_loc == nullptr || flux_dn_loc == nullptr || flux_dir_loc == nullptr)
             throw std::runtime_error("do_broadband needs flux_*_loc");
@@ -959,7 +1007,10 @@ int sw_solver_2stream_impl(
                 sfc_alb_dir, sfc_alb_dif, inc_flux_dir, dif, up, dn, dr, ws2);
     }
 
-    if (do_broadband)
+    if (byband)      // (up, dn, dr lie behind each other in the workspace)
+        sum_bands_kernel<F><<<dim3(ceil_div(nlevcol, 256), nbnd, 3), 256, 0, st>>>(nlevcol, ngpt, band_lims, up, flux_up_loc, flux_dn_loc,
+                                                                                  flux_dir_loc);
+    else if (do_broadband)
     {
         const int nb = ceil_div(nlevcol, 256);
         sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, up, flux_up_loc);
@@ -967,6 +1018,32 @@ int sw_solver_2stream_impl(
         sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, dr, flux_dir_loc);
     }
     RRX_CATCH("rrx_sw_solver_2stream")
+}
+
+// by-band fluxes (rrx_sw_solver_2stream_byband): the fused kernels with one band per workgroup where the tilings reach, otherwise the
+// per-g-point route of broadband mode followed by the band sums; band net and broadband outputs from the band sums in one more pass
+template<typename F>
+int sw_solver_2stream_byband_impl(
+        const int ncol, const int nlay, const int ngpt, const int nbnd, const Bool top_at_1,
+        const F* tau, const F* ssa, const F* g, const F* mu0, const F* sfc_alb_dir, const F* sfc_alb_dif,
+        const F* inc_flux_dir, const Bool has_dif_bc, const F* inc_flux_dif, const int* band_lims,
+        F* bnd_up, F* bnd_dn, F* bnd_dir, F* bnd_net, F* flux_up, F* flux_dn, F* flux_dir, void* stream)
+{
+    RRX_TRY
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    check_byband_args(ncol, nlay, ngpt, nbnd, band_lims);
+    if (bnd_up == nullptr || bnd_dn == nullptr || bnd_dir == nullptr) throw std::runtime_error("band flux outputs missing");
+    const F* dif = has_dif_bc ? inc_flux_dif : nullptr;
+    if (!sw_fused_broadband<F>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, dif,
+                               bnd_up, bnd_dn, bnd_dir, band_lims, nbnd))
+    {
+        if (sw_solver_2stream_impl<F>(ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir,
+                                      (F*)nullptr, (F*)nullptr, (F*)nullptr, has_dif_bc, inc_flux_dif, Bool(0), bnd_up, bnd_dn, bnd_dir,
+                                      stream, nbnd, band_lims) != 0)
+            return 1;                                                // (the message is set)
+    }
+    launch_byband_outputs<F,3>(st, size_t(ncol)*(nlay+1), nbnd, bnd_up, bnd_dn, bnd_dir, bnd_net, flux_up, flux_dn, flux_dir);
+    RRX_CATCH("rrx_sw_solver_2stream_byband")
 }
 
 template<typename F>
@@ -1007,6 +1084,17 @@ int rrx_sw_solver_2stream##SFX( \
 { \
     return sw_solver_2stream_impl<F>(ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, \
             flux_up, flux_dn, flux_dir, has_dif_bc, inc_flux_dif, do_broadband, flux_up_loc, flux_dn_loc, flux_dir_loc, stream); \
+} \
+int rrx_sw_solver_2stream_byband##SFX( \
+        int ncol, int nlay, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const F* g, const F* mu0, const F* sfc_alb_dir, const F* sfc_alb_dif, \
+        const F* inc_flux_dir, RrxBool has_dif_bc, const F* inc_flux_dif, const int* band_lims_gpt, \
+        F* bnd_flux_up, F* bnd_flux_dn, F* bnd_flux_dir, F* bnd_flux_net, \
+        F* flux_up, F* flux_dn, F* flux_dir, void* stream) \
+{ \
+    return sw_solver_2stream_byband_impl<F>(ncol, nlay, ngpt, nbnd, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, \
+            inc_flux_dir, has_dif_bc, inc_flux_dif, band_lims_gpt, bnd_flux_up, bnd_flux_dn, bnd_flux_dir, bnd_flux_net, \
+            flux_up, flux_dn, flux_dir, stream); \
 } \
 int rrx_apply_BC_factor##SFX(int ncol, int nlay, int ngpt, RrxBool top_at_1, const F* inc_flux_dir, const F* mu0, F* gpt_flux_dir, void* stream) \
 { return apply_BC_impl<F>(ncol, nlay, ngpt, top_at_1, inc_flux_dir, mu0, gpt_flux_dir, stream); } \

@@ -143,6 +143,27 @@ class HipKernels:
                 sfc_alb_dir, sfc_alb_dif, inc_flux_dir, flux_up, flux_dn, flux_dir,
                 BoolArg(False), None, BoolArg(False), None, None, None)
 
+    def sw_solver_2stream_byband(self, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, band_lims,
+                                 inc_flux_dif=None, out=None, net=True, broadband=True):
+        """By-band fluxes from the fused broadband solver: bnd_flux_up/dn/dir (nbnd, nlev, ncol), bnd_flux_net = dn - up, and the
+        broadband flux_up/dn/dir (the band sums added in band order). band_lims: (nbnd, 2) int32, 1-based inclusive g-point limits.
+        out=: a dict of preallocated tensors under those keys (missing optional keys are not written)."""
+        ngpt, nlay, ncol = tau.shape
+        nbnd = band_lims.shape[0]
+        if mu0.dim() == 2:
+            mu0 = mu0[0].contiguous()
+        if out is None:
+            out = {k: self.empty((nbnd, nlay+1, ncol)) for k in ("bnd_flux_up", "bnd_flux_dn", "bnd_flux_dir")}
+            if net:
+                out["bnd_flux_net"] = self.empty((nbnd, nlay+1, ncol))
+            if broadband:
+                out.update({k: self.empty((nlay+1, ncol)) for k in ("flux_up", "flux_dn", "flux_dir")})
+        self._c("sw_solver_2stream_byband", ncol, nlay, ngpt, nbnd, BoolArg(top_at_1), tau, ssa, g, mu0,
+                sfc_alb_dir, sfc_alb_dif, inc_flux_dir, BoolArg(inc_flux_dif is not None), inc_flux_dif, band_lims,
+                out["bnd_flux_up"], out["bnd_flux_dn"], out["bnd_flux_dir"], out.get("bnd_flux_net"),
+                out.get("flux_up"), out.get("flux_dn"), out.get("flux_dir"))
+        return out
+
     # ---- gas optics -------------------------------------------------------------------------------
     def interpolation(self, kd, play, tlay, col_gas):
         nlay, ncol = play.shape
@@ -272,6 +293,26 @@ class HipKernels:
         self._c("lw_solver_noscat_fractions", ncol, nlay, ngpt, BoolArg(top_at_1), secants, weights, tau,
                 fr["pfrac"], fr["blay"], fr["blev"], kd.gpoint_bands, sfc_emis, fr["sfc_src"], inc_flux, flux_up, flux_dn)
         return dict(flux_up=flux_up, flux_dn=flux_dn)
+
+    def lw_solver_noscat_fractions_byband(self, top_at_1, kd, secants, weights, tau, fr, sfc_emis, inc_flux=None, out=None,
+                                          net=True, broadband=True, band_lims=None, gpoint_bands=None):
+        """By-band fluxes of lw_solver_noscat_fractions: bnd_flux_up/dn (nbnd, nlev, ncol), bnd_flux_net = dn - up, and the broadband
+        flux_up/dn (the band sums added in band order). band_lims / gpoint_bands default to the k-distribution's. out=: a dict of
+        preallocated tensors under those keys (missing optional keys are not written)."""
+        ngpt, nlay, ncol = tau.shape
+        band_lims = kd.band_lims_gpt if band_lims is None else band_lims
+        gpoint_bands = kd.gpoint_bands if gpoint_bands is None else gpoint_bands
+        nbnd = band_lims.shape[0]
+        if out is None:
+            out = {k: self.empty((nbnd, nlay+1, ncol)) for k in ("bnd_flux_up", "bnd_flux_dn")}
+            if net:
+                out["bnd_flux_net"] = self.empty((nbnd, nlay+1, ncol))
+            if broadband:
+                out.update({k: self.empty((nlay+1, ncol)) for k in ("flux_up", "flux_dn")})
+        self._c("lw_solver_noscat_fractions_byband", ncol, nlay, ngpt, nbnd, BoolArg(top_at_1), secants, weights, tau,
+                fr["pfrac"], fr["blay"], fr["blev"], gpoint_bands, band_lims, sfc_emis, fr["sfc_src"], inc_flux,
+                out["bnd_flux_up"], out["bnd_flux_dn"], out.get("bnd_flux_net"), out.get("flux_up"), out.get("flux_dn"))
+        return out
 
     def compute_tau_rayleigh(self, kd, it, col_dry, col_gas):
         nlay, ncol = col_dry.shape

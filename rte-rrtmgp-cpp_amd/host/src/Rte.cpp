@@ -22,6 +22,15 @@ namespace
     {
         RRX_CALL(rrx_expand_and_transpose, arr_in.dim(2), ops->get_nband(), ops->get_band_lims_gpoint_gpu().ptr(), arr_in.ptr(), arr_out.ptr());
     }
+
+    // optional outputs of the by-band solvers: an array of size 0 is not written
+    template<int N> Float* opt(Array_gpu<Float,N>& a) { return a.size() == 0 ? nullptr : a.ptr(); }
+
+    // flux arrays with one slab per band (fewer bands than g-points) select the by-band form
+    bool is_byband(const std::unique_ptr<Optical_props_arry_gpu>& ops, const Array_gpu<Float,3>& flux)
+    {
+        return flux.dim(3) == ops->get_nband() && ops->get_nband() < ops->get_ngpt();
+    }
 }
 
 void Rte_lw_gpu::rte_lw(
@@ -35,6 +44,13 @@ void Rte_lw_gpu::rte_lw(
         const int n_gauss_angles)
 {
     if (n_gauss_angles < 1 || n_gauss_angles > max_gauss_pts) throw std::runtime_error("rte_lw: n_gauss_angles must be 1..4");
+    if (is_byband(optical_props, gpt_flux_up))
+    {
+        if (n_gauss_angles != 1) throw std::runtime_error("rte_lw: by-band fluxes need one quadrature angle");
+        Array_gpu<Float,3> no3; Array_gpu<Float,2> no_up, no_dn;
+        rte_lw_byband(optical_props, top_at_1, sources, sfc_emis, inc_flux, gpt_flux_up, gpt_flux_dn, no3, no_up, no_dn);
+        return;
+    }
     const int ncol = optical_props->get_ncol();
     const int nlay = optical_props->get_nlay();
     const int ngpt = optical_props->get_ngpt();
@@ -80,6 +96,45 @@ void Rte_lw_gpu::rte_lw(
             do_jacobians, nullptr, nullptr);
 }
 
+void Rte_lw_gpu::rte_lw_byband(
+        const std::unique_ptr<Optical_props_arry_gpu>& optical_props,
+        const Bool top_at_1,
+        const Source_func_lw_gpu& sources,
+        const Array_gpu<Float,2>& sfc_emis,
+        const Array_gpu<Float,2>& inc_flux,
+        Array_gpu<Float,3>& bnd_flux_up,
+        Array_gpu<Float,3>& bnd_flux_dn,
+        Array_gpu<Float,3>& bnd_flux_net,
+        Array_gpu<Float,2>& flux_up,
+        Array_gpu<Float,2>& flux_dn)
+{
+    // (the by-band solver forms the sources from the Planck fractions: the reference-shaped lay_source / lev_source have no by-band form)
+    if (!sources.holds_fractions()) throw std::runtime_error("rte_lw_byband: needs the Planck-lite sources (enable_planck_lite)");
+    const int ncol = optical_props->get_ncol();
+    const int nlay = optical_props->get_nlay();
+    const int ngpt = optical_props->get_ngpt();
+    const int nbnd = optical_props->get_nband();
+    if (bnd_flux_up.dim(3) != nbnd || bnd_flux_dn.dim(3) != nbnd) throw std::runtime_error("rte_lw_byband: flux arrays need one slab per band");
+
+    Array_gpu<Float,2> sfc_emis_gpt({ncol, ngpt});
+    expand_and_transpose(optical_props, sfc_emis, sfc_emis_gpt);
+    if (gauss_angles_cached != 1)
+    {
+        gauss_Ds_gpu = Array_gpu<Float,2>(Array<Float,2>(gauss_Ds_v, {max_gauss_pts, max_gauss_pts}));
+        const Array<Float,2> gauss_wts(gauss_wts_v, {max_gauss_pts, max_gauss_pts});
+        gauss_wts_gpu = Array_gpu<Float,2>(gauss_wts.subset({{ {1, 1}, {1, 1} }}));
+        gauss_angles_cached = 1;
+    }
+    Array_gpu<Float,3> secants({ncol, ngpt, 1});
+    Rte_solver_kernels_cuda::lw_secants_array(ncol, ngpt, 1, max_gauss_pts, gauss_Ds_gpu.ptr(), secants.ptr());
+    const Float* inc_flux_ptr = (inc_flux.size() == 0) ? nullptr : inc_flux.ptr();
+    RRX_CALL(rrx_lw_solver_noscat_fractions_byband, ncol, nlay, ngpt, nbnd, top_at_1, secants.ptr(), gauss_wts_gpu.ptr(),
+             optical_props->get_tau().ptr(), sources.get_planck_frac().ptr(), sources.get_planck_lay().ptr(), sources.get_planck_lev().ptr(),
+             optical_props->get_gpoint_bands_gpu().ptr(), optical_props->get_band_lims_gpoint_gpu().ptr(),
+             sfc_emis_gpt.ptr(), sources.get_sfc_source().ptr(), inc_flux_ptr,
+             bnd_flux_up.ptr(), bnd_flux_dn.ptr(), opt(bnd_flux_net), opt(flux_up), opt(flux_dn));
+}
+
 void Rte_lw_gpu::expand_and_transpose(const std::unique_ptr<Optical_props_arry_gpu>& ops, const Array_gpu<Float,2> arr_in, Array_gpu<Float,2>& arr_out)
 { expand(ops, arr_in, arr_out); }
 
@@ -95,6 +150,13 @@ void Rte_sw_gpu::rte_sw(
         Array_gpu<Float,3>& gpt_flux_dn,
         Array_gpu<Float,3>& gpt_flux_dir)
 {
+    if (is_byband(optical_props, gpt_flux_up))
+    {
+        Array_gpu<Float,3> no3; Array_gpu<Float,2> no_up, no_dn, no_dir;
+        rte_sw_byband(optical_props, top_at_1, mu0, inc_flux_dir, sfc_alb_dir, sfc_alb_dif, inc_flux_dif, gpt_flux_up, gpt_flux_dn,
+                      gpt_flux_dir, no3, no_up, no_dn, no_dir);
+        return;
+    }
     const int ncol = optical_props->get_ncol();
     const int nlay = optical_props->get_nlay();
     const int ngpt = optical_props->get_ngpt();
@@ -119,6 +181,41 @@ void Rte_sw_gpu::rte_sw(
             gpt_flux_up.ptr(), gpt_flux_dn.ptr(), gpt_flux_dir.ptr(),
             has_dif_bc, inc_flux_dif_ptr,
             do_broadband, gpt_flux_up.ptr(), gpt_flux_dn.ptr(), gpt_flux_dir.ptr());
+}
+
+void Rte_sw_gpu::rte_sw_byband(
+        const std::unique_ptr<Optical_props_arry_gpu>& optical_props,
+        const Bool top_at_1,
+        const Array_gpu<Float,1>& mu0,
+        const Array_gpu<Float,2>& inc_flux_dir,
+        const Array_gpu<Float,2>& sfc_alb_dir,
+        const Array_gpu<Float,2>& sfc_alb_dif,
+        const Array_gpu<Float,2>& inc_flux_dif,
+        Array_gpu<Float,3>& bnd_flux_up,
+        Array_gpu<Float,3>& bnd_flux_dn,
+        Array_gpu<Float,3>& bnd_flux_dir,
+        Array_gpu<Float,3>& bnd_flux_net,
+        Array_gpu<Float,2>& flux_up,
+        Array_gpu<Float,2>& flux_dn,
+        Array_gpu<Float,2>& flux_dir)
+{
+    const int ncol = optical_props->get_ncol();
+    const int nlay = optical_props->get_nlay();
+    const int ngpt = optical_props->get_ngpt();
+    const int nbnd = optical_props->get_nband();
+    if (bnd_flux_up.dim(3) != nbnd || bnd_flux_dn.dim(3) != nbnd || bnd_flux_dir.dim(3) != nbnd)
+        throw std::runtime_error("rte_sw_byband: flux arrays need one slab per band");
+
+    Array_gpu<Float,2> sfc_alb_dir_gpt({ncol, ngpt});
+    Array_gpu<Float,2> sfc_alb_dif_gpt({ncol, ngpt});
+    expand_and_transpose(optical_props, sfc_alb_dir, sfc_alb_dir_gpt);
+    expand_and_transpose(optical_props, sfc_alb_dif, sfc_alb_dif_gpt);
+    const Bool has_dif_bc = (inc_flux_dif.size() > 0);
+    RRX_CALL(rrx_sw_solver_2stream_byband, ncol, nlay, ngpt, nbnd, top_at_1,
+             optical_props->get_tau().ptr(), optical_props->get_ssa().ptr(), optical_props->get_g_or_null(), mu0.ptr(),
+             sfc_alb_dir_gpt.ptr(), sfc_alb_dif_gpt.ptr(), inc_flux_dir.ptr(), has_dif_bc, has_dif_bc ? inc_flux_dif.ptr() : nullptr,
+             optical_props->get_band_lims_gpoint_gpu().ptr(),
+             bnd_flux_up.ptr(), bnd_flux_dn.ptr(), bnd_flux_dir.ptr(), opt(bnd_flux_net), opt(flux_up), opt(flux_dn), opt(flux_dir));
 }
 
 void Rte_sw_gpu::expand_and_transpose(const std::unique_ptr<Optical_props_arry_gpu>& ops, const Array_gpu<Float,2> arr_in, Array_gpu<Float,2>& arr_out)

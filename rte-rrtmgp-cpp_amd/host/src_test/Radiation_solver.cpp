@@ -253,11 +253,11 @@ void compute_heating_rate(const Array_gpu<Float,2>& flux_net, const Array_gpu<Fl
 struct Radiation_solver_longwave::Workspace
 {
     int n_col = 0, n_lay = 0;
-    bool broadband = false;
+    bool broadband = false, byband = false;
     std::unique_ptr<Optical_props_arry_gpu> optical_props;
     std::unique_ptr<Optical_props_1scl_gpu> cloud_optical_props;
     std::unique_ptr<Source_func_lw_gpu> sources;
-    Array_gpu<Float,3> gpt_flux_up, gpt_flux_dn;
+    Array_gpu<Float,3> gpt_flux_up, gpt_flux_dn;       // (n_col, n_lev, 1 | n_bnd (by-band solvers) | n_gpt)
 };
 
 Radiation_solver_longwave::Radiation_solver_longwave(
@@ -293,6 +293,8 @@ void Radiation_solver_longwave::solve_gpu(
     const Bool top_at_1 = (vertical_ordering < 0) ? Bool(p_lay({1, 1}) < p_lay({1, n_lay})) : Bool(vertical_ordering == 1);
     if (switch_cloud_optics && !cloud_optics_gpu) throw std::runtime_error("cloud optics requested but no cloud coefficients loaded");
     const bool broadband = broadband_solvers && !switch_output_bnd_fluxes;
+    // by-band solvers: the band sums come straight out of the fused solver (one slab per band in the block workspace)
+    const bool byband = byband_solvers && switch_output_bnd_fluxes && switch_fluxes && n_bnd < n_gpt;
 
     // columns in another order / on a padded count: gather the inputs, solve, scatter the fluxes back (see the header)
     if (!reordered_call && !switch_output_optical && switch_fluxes)
@@ -317,17 +319,18 @@ void Radiation_solver_longwave::solve_gpu(
 
     auto prepare = [&](std::shared_ptr<Workspace>& ws, const int n)
     {
-        if (!ws || ws->n_col != n || ws->n_lay != n_lay || ws->broadband != broadband)
+        if (!ws || ws->n_col != n || ws->n_lay != n_lay || ws->broadband != broadband || ws->byband != byband)
         {
             ws = std::make_shared<Workspace>();
-            ws->n_col = n; ws->n_lay = n_lay; ws->broadband = broadband;
+            ws->n_col = n; ws->n_lay = n_lay; ws->broadband = broadband; ws->byband = byband;
             ws->optical_props = std::make_unique<Optical_props_1scl_gpu>(n, n_lay, *kdist_gpu);
             ws->sources = std::make_unique<Source_func_lw_gpu>(n, n_lay, *kdist_gpu);
-            // broadband solver: Planck fractions instead of the two source arrays (they are materialised on demand, e.g. for
-            // --output-optical)
-            ws->sources->enable_planck_lite(broadband);
-            ws->gpt_flux_up.set_dims({n, n_lev, broadband ? 1 : n_gpt});
-            ws->gpt_flux_dn.set_dims({n, n_lev, broadband ? 1 : n_gpt});
+            // broadband and by-band solvers: Planck fractions instead of the two source arrays (they are materialised on demand,
+            // e.g. for --output-optical)
+            ws->sources->enable_planck_lite(broadband || byband);
+            const int ng = broadband ? 1 : (byband ? n_bnd : n_gpt);
+            ws->gpt_flux_up.set_dims({n, n_lev, ng});
+            ws->gpt_flux_dn.set_dims({n, n_lev, ng});
         }
         if (switch_cloud_optics && !ws->cloud_optical_props)
             ws->cloud_optical_props = std::make_unique<Optical_props_1scl_gpu>(n, n_lay, *cloud_optics_gpu);
@@ -393,6 +396,40 @@ void Radiation_solver_longwave::solve_gpu(
             Fluxes_kernels_cuda::net_broadband_precalc(n_col, n_lev, lw_flux_dn.ptr(), lw_flux_up.ptr(), lw_flux_net.ptr());
             continue;
         }
+        if (byband)
+        {
+            // band sums, band net and broadband fluxes from one solve: into the caller's arrays for a single block, else into block
+            // arrays that are copied into place
+            for (Array_gpu<Float,2>* a : {&lw_flux_up, &lw_flux_dn, &lw_flux_net}) if (a->size() == 0) a->set_dims({n_col, n_lev});
+            for (Array_gpu<Float,3>* a : {&lw_bnd_flux_up, &lw_bnd_flux_dn, &lw_bnd_flux_net}) if (a->size() == 0) a->set_dims({n_col, n_lev, n_bnd});
+            Array_gpu<Float,3> bup(whole ? lw_bnd_flux_up.ptr() : ws.gpt_flux_up.ptr(), {n_in, n_lev, n_bnd});
+            Array_gpu<Float,3> bdn(whole ? lw_bnd_flux_dn.ptr() : ws.gpt_flux_dn.ptr(), {n_in, n_lev, n_bnd});
+            Array_gpu<Float,3> bnet_blk, bnet;
+            Array_gpu<Float,2> up_blk, dn_blk, net_blk, up, dn, net;
+            if (whole)
+            {
+                bnet = Array_gpu<Float,3>(lw_bnd_flux_net.ptr(), {n_in, n_lev, n_bnd});
+                up = Array_gpu<Float,2>(lw_flux_up.ptr(), {n_in, n_lev}); dn = Array_gpu<Float,2>(lw_flux_dn.ptr(), {n_in, n_lev});
+                net = Array_gpu<Float,2>(lw_flux_net.ptr(), {n_in, n_lev});
+            }
+            else
+            {
+                bnet_blk.set_dims({n_in, n_lev, n_bnd}); up_blk.set_dims({n_in, n_lev}); dn_blk.set_dims({n_in, n_lev}); net_blk.set_dims({n_in, n_lev});
+                bnet = Array_gpu<Float,3>(bnet_blk.ptr(), {n_in, n_lev, n_bnd});
+                up = Array_gpu<Float,2>(up_blk.ptr(), {n_in, n_lev}); dn = Array_gpu<Float,2>(dn_blk.ptr(), {n_in, n_lev});
+                net = Array_gpu<Float,2>(net_blk.ptr(), {n_in, n_lev});
+            }
+            rte_lw.rte_lw_byband(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), bup, bdn, bnet, up, dn);
+            Fluxes_kernels_cuda::net_broadband_precalc(n_in, n_lev, dn.ptr(), up.ptr(), net.ptr());
+            if (!whole)
+            {
+                Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_in, col_s, lw_flux_up.ptr(), lw_flux_dn.ptr(), lw_flux_net.ptr(),
+                        up.ptr(), dn.ptr(), net.ptr());
+                Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_bnd, n_in, col_s, lw_bnd_flux_up.ptr(), lw_bnd_flux_dn.ptr(),
+                        lw_bnd_flux_net.ptr(), bup.ptr(), bdn.ptr(), bnet.ptr());
+            }
+            continue;
+        }
         rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), ws.gpt_flux_up, ws.gpt_flux_dn, n_ang);
 
         Fluxes_broadband_gpu fluxes(n_in, n_lev);
@@ -415,7 +452,7 @@ void Radiation_solver_longwave::solve_gpu(
 struct Radiation_solver_shortwave::Workspace
 {
     int n_col = 0, n_lay = 0;
-    bool broadband = false;
+    bool broadband = false, byband = false;
     std::unique_ptr<Optical_props_arry_gpu> optical_props;
     std::unique_ptr<Optical_props_2str_gpu> cloud_optical_props, aerosol_optical_props;
     Array_gpu<Float,3> gpt_flux_up, gpt_flux_dn, gpt_flux_dn_dir;
@@ -475,6 +512,8 @@ void Radiation_solver_shortwave::solve_gpu(
     if (switch_cloud_optics && !cloud_optics_gpu) throw std::runtime_error("cloud optics requested but no cloud coefficients loaded");
     if (switch_aerosol_optics && !aerosol_optics_gpu) throw std::runtime_error("aerosol optics requested but no aerosol coefficients loaded");
     const bool broadband = broadband_solvers && !switch_output_bnd_fluxes;
+    // by-band solvers: the band sums come straight out of the fused solver (one slab per band in the block workspace)
+    const bool byband = byband_solvers && switch_output_bnd_fluxes && switch_fluxes && n_bnd < n_gpt;
 
     // columns in another order / on a padded count: gather the inputs, solve, scatter the fluxes back (see the header)
     if (!reordered_call && !switch_output_optical && switch_fluxes)
@@ -505,12 +544,12 @@ void Radiation_solver_shortwave::solve_gpu(
 
     auto prepare = [&](std::shared_ptr<Workspace>& ws, const int n)
     {
-        if (!ws || ws->n_col != n || ws->n_lay != n_lay || ws->broadband != broadband)
+        if (!ws || ws->n_col != n || ws->n_lay != n_lay || ws->broadband != broadband || ws->byband != byband)
         {
             ws = std::make_shared<Workspace>();
-            ws->n_col = n; ws->n_lay = n_lay; ws->broadband = broadband;
+            ws->n_col = n; ws->n_lay = n_lay; ws->broadband = broadband; ws->byband = byband;
             ws->optical_props = std::make_unique<Optical_props_2str_gpu>(n, n_lay, *kdist_gpu);
-            const int ng = broadband ? 1 : n_gpt;
+            const int ng = broadband ? 1 : (byband ? n_bnd : n_gpt);
             ws->gpt_flux_up.set_dims({n, n_lev, ng}); ws->gpt_flux_dn.set_dims({n, n_lev, ng}); ws->gpt_flux_dn_dir.set_dims({n, n_lev, ng});
         }
         if (switch_cloud_optics && !ws->cloud_optical_props)
@@ -585,6 +624,44 @@ void Radiation_solver_shortwave::solve_gpu(
             Array_gpu<Float,3> up3(sw_flux_up.ptr(), {n_col, n_lev, 1}), dn3(sw_flux_dn.ptr(), {n_col, n_lev, 1}), dir3(sw_flux_dn_dir.ptr(), {n_col, n_lev, 1});
             rte_sw.rte_sw(ws.optical_props, top_at_1, sub1(mu0), toa_src_s, sub_last(sfc_alb_dir), sub_last(sfc_alb_dif), Array_gpu<Float,2>(), up3, dn3, dir3);
             Fluxes_kernels_cuda::net_broadband_precalc(n_col, n_lev, sw_flux_dn.ptr(), sw_flux_up.ptr(), sw_flux_net.ptr());
+            continue;
+        }
+        if (byband)
+        {
+            // band sums, band net and broadband fluxes from one solve (see the longwave)
+            for (Array_gpu<Float,2>* a : {&sw_flux_up, &sw_flux_dn, &sw_flux_dn_dir, &sw_flux_net}) if (a->size() == 0) a->set_dims({n_col, n_lev});
+            for (Array_gpu<Float,3>* a : {&sw_bnd_flux_up, &sw_bnd_flux_dn, &sw_bnd_flux_dn_dir, &sw_bnd_flux_net})
+                if (a->size() == 0) a->set_dims({n_col, n_lev, n_bnd});
+            Array_gpu<Float,3> bup(whole ? sw_bnd_flux_up.ptr() : ws.gpt_flux_up.ptr(), {n_in, n_lev, n_bnd});
+            Array_gpu<Float,3> bdn(whole ? sw_bnd_flux_dn.ptr() : ws.gpt_flux_dn.ptr(), {n_in, n_lev, n_bnd});
+            Array_gpu<Float,3> bdir(whole ? sw_bnd_flux_dn_dir.ptr() : ws.gpt_flux_dn_dir.ptr(), {n_in, n_lev, n_bnd});
+            Array_gpu<Float,3> bnet_blk, bnet;
+            Array_gpu<Float,2> up_blk, dn_blk, dir_blk, net_blk, up, dn, dir, net;
+            if (whole)
+            {
+                bnet = Array_gpu<Float,3>(sw_bnd_flux_net.ptr(), {n_in, n_lev, n_bnd});
+                up = Array_gpu<Float,2>(sw_flux_up.ptr(), {n_in, n_lev}); dn = Array_gpu<Float,2>(sw_flux_dn.ptr(), {n_in, n_lev});
+                dir = Array_gpu<Float,2>(sw_flux_dn_dir.ptr(), {n_in, n_lev}); net = Array_gpu<Float,2>(sw_flux_net.ptr(), {n_in, n_lev});
+            }
+            else
+            {
+                bnet_blk.set_dims({n_in, n_lev, n_bnd});
+                for (Array_gpu<Float,2>* a : {&up_blk, &dn_blk, &dir_blk, &net_blk}) a->set_dims({n_in, n_lev});
+                bnet = Array_gpu<Float,3>(bnet_blk.ptr(), {n_in, n_lev, n_bnd});
+                up = Array_gpu<Float,2>(up_blk.ptr(), {n_in, n_lev}); dn = Array_gpu<Float,2>(dn_blk.ptr(), {n_in, n_lev});
+                dir = Array_gpu<Float,2>(dir_blk.ptr(), {n_in, n_lev}); net = Array_gpu<Float,2>(net_blk.ptr(), {n_in, n_lev});
+            }
+            rte_sw.rte_sw_byband(ws.optical_props, top_at_1, sub1(mu0), toa_src_s, sub_last(sfc_alb_dir), sub_last(sfc_alb_dif),
+                                 Array_gpu<Float,2>(), bup, bdn, bdir, bnet, up, dn, dir);
+            Fluxes_kernels_cuda::net_broadband_precalc(n_in, n_lev, dn.ptr(), up.ptr(), net.ptr());
+            if (!whole)
+            {
+                Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_in, col_s,
+                        sw_flux_up.ptr(), sw_flux_dn.ptr(), sw_flux_dn_dir.ptr(), sw_flux_net.ptr(), up.ptr(), dn.ptr(), dir.ptr(), net.ptr());
+                Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_bnd, n_in, col_s,
+                        sw_bnd_flux_up.ptr(), sw_bnd_flux_dn.ptr(), sw_bnd_flux_dn_dir.ptr(), sw_bnd_flux_net.ptr(),
+                        bup.ptr(), bdn.ptr(), bdir.ptr(), bnet.ptr());
+            }
             continue;
         }
         rte_sw.rte_sw(ws.optical_props, top_at_1, sub1(mu0), toa_src_s, sub_last(sfc_alb_dir), sub_last(sfc_alb_dif),

@@ -3,7 +3,8 @@
 // coefficients_{lw,sw} (+ cloud_coefficients_*), upload, solve on the GPU (1 warm-up + 1 timed run, 10 more with
 // --timings), download, write rte_rrtmgp_output. Files are RRXB containers (include_test/Netcdf_interface.h), extension .nc
 // kept so that run scripts need no change; two extra options: --broadband-solvers (on by default: the solvers sum the g-points
-// themselves; --no-broadband-solvers restores per-g-point fluxes + sum_broadband) and the environment variable RRX_COL_BLOCK (columns per block, default 16384).
+// themselves; --no-broadband-solvers restores per-g-point fluxes + sum_broadband), --byband-solvers (off by default: with --output-bnd-fluxes
+// the fused solvers write the band sums) and the environment variable RRX_COL_BLOCK (columns per block, default 16384).
 // --ngpus=N: the process becomes the launcher of N ranks of itself, one per GPU; rank r solves the contiguous column
 // range rrx_column_range(r, N, ncol), the broadband (and optional band / optical) outputs are all-gathered over RCCL
 // (include/rrx_rccl.h, librrx_rccl.so loaded on demand) and rank 0 writes the output file.
@@ -340,6 +341,7 @@ void solve_radiation(int argc, char** argv)
         {"delta-cloud"      , { true,  "delta-scaling of cloud optical properties"   }},
         {"delta-aerosol"    , { false, "delta-scaling of aerosol optical properties" }},
         {"broadband-solvers", { true,  "Sum g-points inside the solvers (no per-g-point fluxes; off with --output-bnd-fluxes)." }},
+        {"byband-solvers",    { false, "With --output-bnd-fluxes: band sums from the fused solvers (no per-g-point fluxes)." }},
         {"heating-rates"    , { false, "Output layer heating rates lw_heating_rate / sw_heating_rate (K/s)." }},
         {"async"            , { false, "Host-model mode: vertical ordering read once, solves enqueued without synchronising." }},
         {"sort-columns"     , { true,  "Solve the columns in order of surface pressure where neighbours differ much (outputs keep the input order)." }},
@@ -359,6 +361,7 @@ void solve_radiation(int argc, char** argv)
     const bool switch_delta_cloud       = command_line_options.at("delta-cloud"      ).first;
     const bool switch_delta_aerosol     = command_line_options.at("delta-aerosol"    ).first;
     const bool switch_broadband         = command_line_options.at("broadband-solvers").first;
+    const bool switch_byband_solvers    = command_line_options.at("byband-solvers").first;
     const bool switch_heating_rates     = command_line_options.at("heating-rates"    ).first;
     const bool switch_async             = command_line_options.at("async"            ).first;
     const bool switch_device_sort       = command_line_options.at("device-sort-columns").first;
@@ -478,6 +481,7 @@ void solve_radiation(int argc, char** argv)
         Radiation_solver_longwave rad_lw(gas_concs_gpu, "coefficients_lw.nc", switch_cloud_optics ? "cloud_coefficients_lw.nc" : "");
         rad_lw.set_column_block(col_block);
         rad_lw.set_broadband_solvers(switch_broadband);
+        rad_lw.set_byband_solvers(switch_byband_solvers);
         // (--no-sort-columns: the file's order and column count exactly; otherwise the solver pads to a multiple of 16 columns and,
         //  with --device-sort-columns, orders them itself)
         rad_lw.set_column_sorting(switch_device_sort ? 1 : (switch_sort_columns ? -1 : 0));
@@ -555,6 +559,7 @@ void solve_radiation(int argc, char** argv)
                 "coefficients_sw.nc", "cloud_coefficients_sw.nc", "aerosol_optics.nc");
         rad_sw.set_column_block(col_block);
         rad_sw.set_broadband_solvers(switch_broadband);
+        rad_sw.set_byband_solvers(switch_byband_solvers);
         rad_sw.set_column_sorting(switch_device_sort ? 1 : (switch_sort_columns ? -1 : 0));
         rad_sw.set_column_padding(switch_sort_columns || switch_device_sort);
         if (switch_async) rad_sw.set_vertical_ordering(p_lay({1, 1}) < p_lay({1, n_lay}) ? 1 : 0);

@@ -190,9 +190,12 @@ class ResidentSolver:
 
     STAGES = ("lw_gas_optics", "lw_planck", "lw_solver", "lw_reduce", "sw_gas_optics", "sw_solver", "sw_reduce")
 
-    def __init__(self, be, kd_lw, kd_sw, atm, do_broadband=False, overlap=False, cloud_luts=None, sort_columns=None):
+    def __init__(self, be, kd_lw, kd_sw, atm, do_broadband=False, overlap=False, cloud_luts=None, sort_columns=None, byband=False):
         import torch
         self.torch = torch
+        # byband: the step also fills self.bnd_fluxes (lw_up/lw_dn/lw_net/sw_up/sw_dn/sw_dir/sw_net, (nbnd, nlev, ncol) each, the
+        # caller's column order) from the fused solvers' by-band form; the seven broadband arrays come from the same solves
+        self.byband = bool(byband)
         # Column sorting. The windowed gas optics stages ONE box of LUT nodes per 256 neighbouring cells; columns
         # that differ much in pressure (RFMIP-like sites, --col-spread) do not fit one box and fall back to the gather kernels
         # (+40 % per step at +-35 % pressure spread). Columns are independent, so the step may process them in any order: sorted by
@@ -237,6 +240,8 @@ class ResidentSolver:
         self.direct = bool(int(os.environ.get("RRX_DIRECT", "1")))     # interpolation state recomputed inside its consumers
         # broadband mode: Planck fractions + band Planck functions, sources formed inside the LW solver ("Planck-lite" chain)
         self.lite = self.direct and do_broadband and bool(int(os.environ.get("RRX_LITE", "1")))
+        if self.byband and not self.lite:
+            raise ValueError("ResidentSolver(byband=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
         ncol, nlay = atm.ncol + self.npad, atm.nlay              # columns of a step (padded)
         ng_l, ng_s = kd_lw.ngpt, kd_sw.ngpt
         e = be.empty
@@ -254,6 +259,15 @@ class ResidentSolver:
         # packed broadband outputs: LW up/dn/net + SW up/dn/dir/net  (7, nlev, ncol) -> one all-gather
         self.fluxes = e((7, nlay+1, atm.ncol))
         self.fluxes_sorted = e((7, nlay+1, ncol)) if self.perm is not None else None
+        # packed band outputs: LW up/dn/net (3, nbnd_lw, nlev, ncol), SW up/dn/dir/net (4, nbnd_sw, nlev, ncol)
+        self.bnd_lw = self.bnd_sw = self.bnd_lw_sorted = self.bnd_sw_sorted = None
+        self.bnd_fluxes = None
+        if self.byband:
+            self.bnd_lw = e((3, kd_lw.nbnd, nlay+1, atm.ncol)); self.bnd_sw = e((4, kd_sw.nbnd, nlay+1, atm.ncol))
+            if self.perm is not None:
+                self.bnd_lw_sorted = e((3, kd_lw.nbnd, nlay+1, ncol)); self.bnd_sw_sorted = e((4, kd_sw.nbnd, nlay+1, ncol))
+            self.bnd_fluxes = dict(lw_up=self.bnd_lw[0], lw_dn=self.bnd_lw[1], lw_net=self.bnd_lw[2],
+                                   sw_up=self.bnd_sw[0], sw_dn=self.bnd_sw[1], sw_dir=self.bnd_sw[2], sw_net=self.bnd_sw[3])
         self.weights = be.asarray(np.ascontiguousarray(GAUSS_WTS[0, :1]))
         self.gauss_Ds = be.asarray(GAUSS_DS)
         # secants and the band -> g-point expansion of emissivity / albedos: buffers allocated once, the launches themselves are
@@ -326,6 +340,8 @@ class ResidentSolver:
 
         ncol, nlay = atm.ncol, atm.nlay
         F = self.fluxes if perm is None else self.fluxes_sorted
+        BL = self.bnd_lw if perm is None else self.bnd_lw_sorted
+        BS = self.bnd_sw if perm is None else self.bnd_sw_sorted
         main = self.torch.cuda.current_stream(be.device)
         for ichain, (kind, kd, buf) in enumerate((("lw", self.kd_lw, self.lw), ("sw", self.kd_sw, self.sw))):
             if self.overlap:
@@ -366,7 +382,11 @@ class ResidentSolver:
                 mark("lw_solver")
                 be._c("lw_secants_array", ncol, kd.ngpt, 1, MAX_GAUSS_PTS, self.gauss_Ds, self.secants)
                 be._c("expand_and_transpose", ncol, kd.nbnd, kd.band_lims_gpt, atm.emis_sfc, self.sfc_emis_gpt)
-                if self.lite:
+                if self.byband:
+                    be.lw_solver_noscat_fractions_byband(atm.top_at_1, kd, self.secants, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
+                                                         out=dict(bnd_flux_up=BL[0], bnd_flux_dn=BL[1], bnd_flux_net=BL[2],
+                                                                  flux_up=F[0], flux_dn=F[1]))
+                elif self.lite:
                     be.lw_solver_noscat_fractions(atm.top_at_1, kd, self.secants, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
                                                   flux_up=F[0], flux_dn=F[1])
                 elif self.do_broadband:
@@ -399,7 +419,11 @@ class ResidentSolver:
                 mark("sw_solver")
                 be._c("expand_and_transpose", ncol, kd.nbnd, kd.band_lims_gpt, atm.sfc_alb_dir, self.alb_dir)
                 be._c("expand_and_transpose", ncol, kd.nbnd, kd.band_lims_gpt, atm.sfc_alb_dif, self.alb_dif)
-                if self.do_broadband:
+                if self.byband:
+                    be.sw_solver_2stream_byband(atm.top_at_1, buf["tau"], buf["ssa"], gbuf, atm.mu0, self.alb_dir, self.alb_dif, toa,
+                                                kd.band_lims_gpt, out=dict(bnd_flux_up=BS[0], bnd_flux_dn=BS[1], bnd_flux_dir=BS[2],
+                                                                           bnd_flux_net=BS[3], flux_up=F[3], flux_dn=F[4], flux_dir=F[5]))
+                elif self.do_broadband:
                     be._c("sw_solver_2stream", ncol, nlay, kd.ngpt, BoolArg(atm.top_at_1), buf["tau"], buf["ssa"], gbuf, atm.mu0,
                           self.alb_dir, self.alb_dif, toa, None, None, None, BoolArg(False), None,
                           BoolArg(True), F[3], F[4], F[5])
@@ -420,4 +444,6 @@ class ResidentSolver:
             n = self.ncol_caller
             self.fluxes.index_copy_(2, perm[:n], F[:, :, :n])
             F = self.fluxes
+            if self.byband:
+                self.bnd_lw.index_copy_(3, perm[:n], BL[..., :n]); self.bnd_sw.index_copy_(3, perm[:n], BS[..., :n])
         return F
