@@ -416,7 +416,14 @@ int rrx_sort_columns##SFX(int ncol, const F* key, int npad, int* perm, void* str
 int rrx_column_spread##SFX(int ncol, const F* key, int block, F threshold, int* flag, void* stream); \
 int rrx_gather_cols##SFX(int nout, unsigned long long nrest, const int* perm, int ncol_in, const F* in, F* out, void* stream); \
 int rrx_scatter_cols##SFX(int n, unsigned long long nrest, const int* perm, int ncol_src, const F* in, int ncol_dst, F* out, void* stream); \
-int rrx_gather_lastdim##SFX(int n1, int nout, const int* perm, const F* in, F* out, void* stream);
+int rrx_gather_lastdim##SFX(int n1, int nout, const int* perm, const F* in, F* out, void* stream); \
+/* sunlit-only shortwave: perm[0 .. *count) = the entries of order(ncol) (NULL: 0 .. ncol-1) with mu0 > 0, in their order (0, -0.0, \
+   negative values and NaN are night); then repeats of the last kept entry up to a multiple of pad_to (none when nothing is kept). \
+   perm holds at least ncol rounded up to pad_to ints; *count (device) gets the unpadded count. One workgroup, no scratch memory. \
+   scatter_cols_fill: out(:, r) = 0 for all ncol_dst columns, then out(perm[i], r) = in(i, r) for i < n (n = 0: zeros only); \
+   serves every column-first layout: (col, n2), (col, nlev, nbnd), packed (k, nlev, col) with nrest = the product of the rest. */ \
+int rrx_sunlit_columns##SFX(int ncol, const F* mu0, const int* order, int pad_to, int* perm, int* count, void* stream); \
+int rrx_scatter_cols_fill##SFX(int n, unsigned long long nrest, const int* perm, int ncol_src, const F* in, int ncol_dst, F* out, void* stream);
 
 RRX_DECLARE(double, _f64)
 RRX_DECLARE(float, _f32)

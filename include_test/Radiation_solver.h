@@ -147,10 +147,15 @@ class Radiation_solver_shortwave
         // column order of a solve: see Radiation_solver_longwave
         void set_column_sorting(const int mode) { column_sorting = mode; sort_decided = -1; }
         void set_column_padding(const bool b) { column_padding = b; }
+        // Sunlit-only solve (default off): with fluxes requested and no optical output, solve_gpu lists the columns with mu0 > 0 on
+        // the device (in the sorted order when sorting is on, padded when padding is on), solves only those and writes exact zeros
+        // to every SW flux (broadband and band) of the other columns. mu0 <= 0 and NaN count as night. Reading the count back
+        // synchronises the stream once per solve in this mode. Off, the solve still requires mu0 > 0 in every column.
+        void set_sunlit_columns(const bool b);
 
     private:
         int column_sorting = -1, sort_decided = -1;
-        bool column_padding = true, reordered_call = false;
+        bool column_padding = true, reordered_call = false, sunlit_columns = false;
         std::unique_ptr<Gas_optics_rrtmgp_gpu> kdist_gpu;
         std::unique_ptr<Cloud_optics_gpu> cloud_optics_gpu;
         std::unique_ptr<Aerosol_optics_gpu> aerosol_optics_gpu;

@@ -22,6 +22,9 @@ void  rrx_cxx_driver_destroy(void* handle);
 int   rrx_cxx_driver_set_gas(void* handle, const char* name, const Real* vmr, int n1, int n2);
 /* set_column_block / set_broadband_solvers / set_column_sorting (-1 auto, 0, 1) / set_column_padding of both solvers */
 int   rrx_cxx_driver_settings(void* handle, int column_block, int broadband, int sort_mode, int pad);
+/* set_sunlit_columns of the shortwave solver (0 = off, the default): SW on the columns with mu0 > 0 only, zeros elsewhere; each solve
+   then synchronises once (the column count) */
+int   rrx_cxx_sunlit_columns(void* handle, int sunlit);
 /* one LW + one SW solve_gpu (fluxes only) enqueued on `stream`; DEVICE arrays: (ncol,nlay) / (ncol,nlay+1) fields, (ncol) vectors,
    surface properties (nbnd,ncol); lwp, iwp, rel, dei NULL without clouds; out7: seven (ncol, nlay+1) arrays for LW up, dn, net and
    SW up, dn, dn_dir, net, or NULL (the driver then keeps them: rrx_cxx_driver_fluxes) */

@@ -83,7 +83,119 @@ __global__ void gather_lastdim_kernel(const int n1, const int nout, const int* _
     }
 }
 
+// Sunlit columns: perm[0 .. count) = the entries of `order` (or 0..ncol-1) whose mu0 > 0, in order; then repeats of the last one up
+// to a multiple of pad_to. One workgroup of 16 waves walks the list in chunks of SUNLIT_PER_THREAD x 1024 entries: element
+// (j, wave, lane) of a chunk is entry base + j*1024 + wave*64 + lane, so a wave64 ballot per (j, wave) plus one scan over the
+// 16 x SUNLIT_PER_THREAD ballot counts gives every kept entry its place. Night = not (mu0 > 0): 0, -0.0, negatives and NaN.
+constexpr int SUNLIT_WAVES = 16, SUNLIT_PER_THREAD = 8, SUNLIT_SLOTS = SUNLIT_WAVES*SUNLIT_PER_THREAD;
+static_assert(SUNLIT_SLOTS == 128, "the slot scan gives two slots to each lane of one wave");
+
+template<typename F>
+__global__ void __launch_bounds__(64*SUNLIT_WAVES) sunlit_columns_kernel(
+        const int ncol, const F* __restrict__ mu0, const int* __restrict__ order, const int pad_to, int* __restrict__ perm, int* __restrict__ count)
+{
+    __shared__ int s_off[SUNLIT_SLOTS];
+    __shared__ int s_total, s_last;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int carry = 0, last = 0;
+    for (int base = 0; base < ncol; base += SUNLIT_PER_THREAD*64*SUNLIT_WAVES)
+    {
+        int col[SUNLIT_PER_THREAD];
+        bool day[SUNLIT_PER_THREAD];
+        #pragma unroll
+        for (int j=0; j<SUNLIT_PER_THREAD; ++j)
+        {
+            const int i = base + j*64*SUNLIT_WAVES + int(threadIdx.x);
+            col[j] = (i < ncol) ? (order ? order[i] : i) : 0;
+        }
+        #pragma unroll
+        for (int j=0; j<SUNLIT_PER_THREAD; ++j)
+        {
+            const int i = base + j*64*SUNLIT_WAVES + int(threadIdx.x);
+            day[j] = (i < ncol) && (mu0[col[j]] > F(0.));
+        }
+        unsigned long long mask[SUNLIT_PER_THREAD];
+        #pragma unroll
+        for (int j=0; j<SUNLIT_PER_THREAD; ++j)
+        {
+            mask[j] = __ballot(day[j]);
+            if (lane == 0) s_off[j*SUNLIT_WAVES + wave] = __popcll(mask[j]);
+        }
+        __syncthreads();
+        if (wave == 0)          // exclusive scan of the 128 slot counts: two slots per lane, then a wave64 shuffle scan
+        {
+            const int a = s_off[2*lane], b = s_off[2*lane+1];
+            int incl = a + b;
+            #pragma unroll
+            for (int d=1; d<64; d<<=1)
+            {
+                const int v = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += v;
+            }
+            const int excl = incl - (a + b);
+            s_off[2*lane] = excl; s_off[2*lane+1] = excl + a;
+            if (lane == 63) s_total = incl;
+        }
+        __syncthreads();
+        const int total = s_total;
+        #pragma unroll
+        for (int j=0; j<SUNLIT_PER_THREAD; ++j)
+            if (day[j])
+            {
+                const int p = s_off[j*SUNLIT_WAVES + wave] + __popcll(mask[j] & below);
+                perm[carry + p] = col[j];
+                if (p == total - 1) s_last = col[j];     // the chunk's last kept entry (the padding repeats the list's last)
+            }
+        carry += total;
+        __syncthreads();
+        if (total > 0) last = s_last;
+        __syncthreads();        // s_off / s_total / s_last are rewritten by the next chunk
+    }
+    const long long n_out = (carry + (long long)pad_to - 1) / pad_to * pad_to;
+    for (long long i = carry + int(threadIdx.x); i < n_out; i += 64*SUNLIT_WAVES) perm[i] = last;
+    if (threadIdx.x == 0) *count = carry;
+}
+
+// out(:, r) = 0, then out(perm[i], r) = in(i, r) for i < n: the night columns of a sunlit-only solve (and any other column not in
+// perm[0 .. n)) come out as exact zeros
+template<typename T>
+__global__ void fill_zero_kernel(const size_t n, T* __restrict__ out)
+{
+    for (size_t k = size_t(blockIdx.x)*blockDim.x + threadIdx.x; k < n; k += size_t(gridDim.x)*blockDim.x) out[k] = T(0);
+}
+
 inline dim3 grid2(const int n, const size_t nrest) { return dim3(std::min(ceil_div(n, 256), 256), unsigned(std::min<size_t>(nrest, 4096))); }
+
+template<typename F>
+int sunlit_columns_impl(const int ncol, const F* mu0, const int* order, const int pad_to, int* perm, int* count, void* stream, const char* name)
+{
+    RRX_TRY
+    if (ncol < 0) throw std::runtime_error("ncol < 0");
+    if (pad_to < 1) throw std::runtime_error("pad_to < 1");
+    if (mu0 == nullptr && ncol > 0) throw std::runtime_error("mu0 is null");
+    if (perm == nullptr) throw std::runtime_error("perm is null");
+    if (count == nullptr) throw std::runtime_error("count is null");
+    sunlit_columns_kernel<F><<<1, 64*SUNLIT_WAVES, 0, static_cast<hipStream_t>(stream)>>>(ncol, mu0, order, pad_to, perm, count);
+    RRX_CATCH(name)
+}
+
+template<typename F>
+int scatter_cols_fill_impl(const int n, const unsigned long long nrest, const int* perm, const int ncol_src, const F* in, const int ncol_dst,
+                           F* out, void* stream, const char* name)
+{
+    RRX_TRY
+    if (n < 0 || ncol_dst < 0 || ncol_src < 0) throw std::runtime_error("negative column count");
+    if (n > ncol_src) throw std::runtime_error("n > ncol_src");
+    if (n > 0 && (perm == nullptr || in == nullptr)) throw std::runtime_error("perm or in is null");
+    if (out == nullptr && ncol_dst > 0 && nrest > 0) throw std::runtime_error("out is null");
+    if (ncol_dst == 0 || nrest == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t ntot = size_t(ncol_dst)*size_t(nrest);
+    fill_zero_kernel<F><<<unsigned(std::min<size_t>(ceil_div(ntot, size_t(256)), 4096)), 256, 0, st>>>(ntot, out);
+    if (n > 0) scatter_cols_kernel<F><<<grid2(n, nrest), 256, 0, st>>>(n, size_t(nrest), perm, ncol_src, in, ncol_dst, out);
+    RRX_CATCH(name)
+}
 
 template<typename F>
 int sort_columns_impl(const int ncol, const F* key, const int npad, int* perm, void* stream)
@@ -132,7 +244,11 @@ int rrx_scatter_cols##SFX(int n, unsigned long long nrest, const int* perm, int 
   scatter_cols_kernel<F><<<grid2(n, nrest), 256, 0, static_cast<hipStream_t>(stream)>>>(n, size_t(nrest), perm, ncol_src, in, ncol_dst, out); RRX_CATCH("rrx_scatter_cols") } \
 int rrx_gather_lastdim##SFX(int n1, int nout, const int* perm, const F* in, F* out, void* stream) \
 { RRX_TRY if (n1 <= 0 || nout <= 0) return 0; \
-  gather_lastdim_kernel<F><<<rrx::ceil_div(size_t(n1)*nout, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(n1, nout, perm, in, out); RRX_CATCH("rrx_gather_lastdim") }
+  gather_lastdim_kernel<F><<<rrx::ceil_div(size_t(n1)*nout, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(n1, nout, perm, in, out); RRX_CATCH("rrx_gather_lastdim") } \
+int rrx_sunlit_columns##SFX(int ncol, const F* mu0, const int* order, int pad_to, int* perm, int* count, void* stream) \
+{ return sunlit_columns_impl<F>(ncol, mu0, order, pad_to, perm, count, stream, "rrx_sunlit_columns" #SFX); } \
+int rrx_scatter_cols_fill##SFX(int n, unsigned long long nrest, const int* perm, int ncol_src, const F* in, int ncol_dst, F* out, void* stream) \
+{ return scatter_cols_fill_impl<F>(n, nrest, perm, ncol_src, in, ncol_dst, out, stream, "rrx_scatter_cols_fill" #SFX); }
 
 RRX_DEFINE_COLUMNS(double, _f64)
 RRX_DEFINE_COLUMNS(float, _f32)

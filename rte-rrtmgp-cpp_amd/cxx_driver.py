@@ -14,7 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 class CxxDriver:
-    def __init__(self, be, kd_lw0, kd_sw0, atm, cloud_luts0=None, column_block=16384, broadband=True, sort_mode=-1, pad=True):
+    def __init__(self, be, kd_lw0, kd_sw0, atm, cloud_luts0=None, column_block=16384, broadband=True, sort_mode=-1, pad=True,
+                 sunlit=False):
         import torch
         self.torch, self.be, self.atm = torch, be, atm
         self.f64 = be.np_dtype == np.float64
@@ -38,6 +39,8 @@ class CxxDriver:
             raise RuntimeError("rrx_cxx_driver_create: " + self.lib.rrx_cxx_driver_error().decode())
         self.h = ctypes.c_void_p(self.h)
         self._check(self.lib.rrx_cxx_driver_settings(self.h, int(column_block), int(broadband), int(sort_mode), int(pad)))
+        if sunlit:                                  # SW on the columns with mu0 > 0 only, zeros elsewhere (set_sunlit_columns)
+            self._check(self.lib.rrx_cxx_sunlit_columns(self.h, 1))
         for n, t in atm.vmr.items():                # (nlay, ncol) tensors = (ncol, nlay) arrays; profiles (nlay,) = (1, nlay)
             n1, n2 = (t.shape[1], t.shape[0]) if t.dim() == 2 else ((1, t.shape[0]) if t.dim() == 1 else (1, 1))
             self._check(self.lib.rrx_cxx_driver_set_gas(self.h, n.encode(), ctypes.c_void_p(t.data_ptr()), n1, n2))

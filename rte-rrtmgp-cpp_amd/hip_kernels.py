@@ -519,6 +519,32 @@ class HipKernels:
         self._c("subset_cols", ncol_full, nrest, col_s, ncol_sub, arr, out)
         return out
 
+    def sunlit_columns(self, mu0, order=None, pad_to=1, perm=None, count=None):
+        """Stable list of the columns with mu0 > 0 (of `order`, an int32 index tensor, or of 0..ncol-1), padded to a multiple of
+        pad_to by repeats of the last one. Returns (perm, count): int32 device tensors, count[0] = the unpadded count. perm= / count=:
+        preallocated outputs (perm holds at least ncol rounded up to pad_to entries)."""
+        ncol = int(order.numel()) if order is not None else int(mu0.shape[-1])
+        for t in (order, perm, count):
+            if t is not None and t.dtype != torch.int32:
+                raise TypeError("sunlit_columns: order, perm and count are int32 tensors")
+        if perm is None:
+            perm = self.int_empty((max(-(-ncol // pad_to) * pad_to, 1),))
+        if count is None:
+            count = self.int_empty((1,))
+        self._c("sunlit_columns", ncol, mu0, order, int(pad_to), perm, count)
+        return perm, count
+
+    def scatter_cols_fill(self, n, perm, src, dst):
+        """dst[..., perm[i]] = src[..., i] for i < n, zeros in every other column of dst; column-last tensors (any leading shape,
+        contiguous), src with at least n columns."""
+        nrest = int(np.prod(dst.shape[:-1])) if dst.dim() > 1 else 1
+        if perm.dtype != torch.int32:
+            raise TypeError("scatter_cols_fill: perm is an int32 tensor")
+        if tuple(src.shape[:-1]) != tuple(dst.shape[:-1]) or not (src.is_contiguous() and dst.is_contiguous()):
+            raise ValueError("scatter_cols_fill: src and dst must be contiguous with the same leading shape")
+        self._c("scatter_cols_fill", int(n), ctypes.c_ulonglong(nrest), perm, int(src.shape[-1]), src, int(dst.shape[-1]), dst)
+        return dst
+
     supports_null_g = True      # gas_optics_sw_fused / sw_solver_2stream accept g = None (asymmetry identically zero)
 
     def set_broadband_min_groups(self, n):

@@ -171,11 +171,14 @@ namespace
 
     // ---- column order of a solve (include_test/Radiation_solver.h: set_column_sorting / set_column_padding) ----
     // A gather index over the caller's columns: sorted by surface pressure and / or padded to a multiple of 16 by repeating the last one.
+    // Sunlit-only SW (set_sunlit_columns): a subset -- perm[0 .. n_keep) lists the columns with mu0 > 0, padded to n_out -- and out()
+    // writes zeros to every other column of the caller's arrays.
     struct Column_order
     {
-        int n_col = 0, n_out = 0;
+        int n_col = 0, n_out = 0, n_keep = 0;
+        bool subset = false;
         Array_gpu<int,1> perm;
-        bool active() const { return n_out > 0; }
+        bool active() const { return n_out > 0 || subset; }
         // (col, n2) -> (n_out, n2); an absent (empty) array stays absent
         Array_gpu<Float,2> in2(const Array_gpu<Float,2>& a) const
         {
@@ -206,9 +209,33 @@ namespace
             std::array<int,N> d; d[0] = n_col; unsigned long long rest = 1;
             for (int i=1; i<N; ++i) { d[i] = src.dim(i+1); rest *= (unsigned long long)src.dim(i+1); }
             if (dst.size() == 0) dst.set_dims(d);
-            RRX_CALL(rrx_scatter_cols, n_col, rest, perm.ptr(), n_out, src.ptr(), n_col, dst.ptr());
+            if (subset) RRX_CALL(rrx_scatter_cols_fill, n_keep, rest, perm.ptr(), n_out, src.ptr(), n_col, dst.ptr());
+            else RRX_CALL(rrx_scatter_cols, n_col, rest, perm.ptr(), n_out, src.ptr(), n_col, dst.ptr());
+        }
+        // a subset without columns: the caller's (col, dims...) array is all zeros
+        template<int N> void zeros(Array_gpu<Float,N>& dst, const std::array<int,N>& d) const
+        {
+            if (dst.size() == 0) dst.set_dims(d);
+            unsigned long long rest = 1;
+            for (int i=1; i<N; ++i) rest *= (unsigned long long)d[i];
+            RRX_CALL(rrx_scatter_cols_fill, 0, rest, nullptr, 0, nullptr, n_col, dst.ptr());
         }
     };
+
+    // The sunlit columns of a solve (mu0 > 0), in the order `co` gives them (sorting) or in the caller's, padded to a multiple of 16
+    // when padding is on. The count sizes the solve, so it is read back here: this synchronises once per shortwave solve.
+    Column_order sunlit_column_order(const Column_order& co, const int n_col, const Array_gpu<Float,1>& mu0, const bool pad)
+    {
+        Column_order day;
+        const int pad_to = (pad && n_col > 16) ? 16 : 1;
+        day.n_col = n_col; day.subset = true;
+        day.perm.set_dims({std::max(1, (n_col + pad_to - 1) / pad_to * pad_to)});
+        Array_gpu<int,1> count({1});
+        RRX_CALL(rrx_sunlit_columns, n_col, mu0.ptr(), co.active() ? co.perm.ptr() : nullptr, pad_to, day.perm.ptr(), count.ptr());
+        rrx_host::check(rrx_memcpy_d2h_stream(&day.n_keep, count.ptr(), sizeof(int), rrx_host::current_stream()));
+        day.n_out = (day.n_keep + pad_to - 1) / pad_to * pad_to;
+        return day;
+    }
 
     // Should this solve reorder its columns, and how? `sort_decided` caches the automatic decision of the solver object.
     Column_order column_order(const int mode, int& sort_decided, const bool pad, const Array_gpu<Float,2>& p_lev, const Bool top_at_1)
@@ -518,7 +545,21 @@ void Radiation_solver_shortwave::solve_gpu(
     // columns in another order / on a padded count: gather the inputs, solve, scatter the fluxes back (see the header)
     if (!reordered_call && !switch_output_optical && switch_fluxes)
     {
-        const Column_order co = column_order(column_sorting, sort_decided, column_padding, p_lev, top_at_1);
+        Column_order co = column_order(column_sorting, sort_decided, column_padding, p_lev, top_at_1);
+        if (sunlit_columns)
+        {
+            // sunlit-only: the solve runs on the columns with mu0 > 0; all sunlit: the plain order below, bit for bit
+            Column_order day = sunlit_column_order(co, n_col, mu0, column_padding);
+            if (day.n_keep < n_col) co = std::move(day);
+            if (co.subset && co.n_keep == 0)
+            {
+                for (Array_gpu<Float,2>* a : {&sw_flux_up, &sw_flux_dn, &sw_flux_dn_dir, &sw_flux_net}) co.zeros<2>(*a, {n_col, n_lev});
+                if (switch_output_bnd_fluxes)
+                    for (Array_gpu<Float,3>* a : {&sw_bnd_flux_up, &sw_bnd_flux_dn, &sw_bnd_flux_dn_dir, &sw_bnd_flux_net})
+                        co.zeros<3>(*a, {n_col, n_lev, n_bnd});
+                return;
+            }
+        }
         if (co.active())
         {
             const Gas_concs_gpu gases = gas_concs.gathered(co.perm, n_col, co.n_out);
@@ -684,3 +725,5 @@ void Radiation_solver_shortwave::solve_gpu(
         }
     }
 }
+
+void Radiation_solver_shortwave::set_sunlit_columns(const bool b) { sunlit_columns = b; }

@@ -78,6 +78,11 @@ int rrx_cxx_driver_settings(void* h, const int column_block, const int broadband
     });
 }
 
+int rrx_cxx_sunlit_columns(void* h, const int sunlit)
+{
+    return guarded([&] { static_cast<Driver*>(h)->sw->set_sunlit_columns(sunlit != 0); });
+}
+
 // One LW + SW solve (fluxes only) on `stream`. Arrays: (ncol,nlay) / (ncol,nlay+1) fields, (ncol) vectors, surface properties (nbnd,ncol);
 // lwp, iwp, rel, dei may be NULL without clouds. out7: seven device arrays (ncol, nlay+1) for LW up, dn, net and SW up, dn, dn_dir, net,
 // or NULL: the driver keeps them (rrx_cxx_driver_fluxes).

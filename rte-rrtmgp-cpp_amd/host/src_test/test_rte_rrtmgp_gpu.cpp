@@ -343,6 +343,7 @@ void solve_radiation(int argc, char** argv)
         {"broadband-solvers", { true,  "Sum g-points inside the solvers (no per-g-point fluxes; off with --output-bnd-fluxes)." }},
         {"byband-solvers",    { false, "With --output-bnd-fluxes: band sums from the fused solvers (no per-g-point fluxes)." }},
         {"heating-rates"    , { false, "Output layer heating rates lw_heating_rate / sw_heating_rate (K/s)." }},
+        {"sunlit-columns"   , { false, "Shortwave on the columns with mu0 > 0 only; every SW output of the others is zero (set_sunlit_columns)." }},
         {"async"            , { false, "Host-model mode: vertical ordering read once, solves enqueued without synchronising." }},
         {"sort-columns"     , { true,  "Solve the columns in order of surface pressure where neighbours differ much (outputs keep the input order)." }},
         {"device-sort-columns", { false, "Leave the ordering to the solvers: sorted and padded on the device inside solve_gpu (Radiation_solver::set_column_sorting(1)) instead of on the host before the upload." }}};
@@ -362,6 +363,7 @@ void solve_radiation(int argc, char** argv)
     const bool switch_delta_aerosol     = command_line_options.at("delta-aerosol"    ).first;
     const bool switch_broadband         = command_line_options.at("broadband-solvers").first;
     const bool switch_byband_solvers    = command_line_options.at("byband-solvers").first;
+    const bool switch_sunlit_columns    = command_line_options.at("sunlit-columns").first;
     const bool switch_heating_rates     = command_line_options.at("heating-rates"    ).first;
     const bool switch_async             = command_line_options.at("async"            ).first;
     const bool switch_device_sort       = command_line_options.at("device-sort-columns").first;
@@ -560,6 +562,7 @@ void solve_radiation(int argc, char** argv)
         rad_sw.set_column_block(col_block);
         rad_sw.set_broadband_solvers(switch_broadband);
         rad_sw.set_byband_solvers(switch_byband_solvers);
+        rad_sw.set_sunlit_columns(switch_sunlit_columns);
         rad_sw.set_column_sorting(switch_device_sort ? 1 : (switch_sort_columns ? -1 : 0));
         rad_sw.set_column_padding(switch_sort_columns || switch_device_sort);
         if (switch_async) rad_sw.set_vertical_ordering(p_lay({1, 1}) < p_lay({1, n_lay}) ? 1 : 0);

@@ -11,7 +11,9 @@ Mirrors, call for call, what the reference's host classes do around the kernel l
 The backend is either HipKernels (product path, torch CUDA tensors) or, in tests only, a CPU checker from
 oracle/oracle_py.py (numpy). This module never imports the oracle.
 """
+import ctypes
 import os
+import time
 
 import numpy as np
 
@@ -190,7 +192,8 @@ class ResidentSolver:
 
     STAGES = ("lw_gas_optics", "lw_planck", "lw_solver", "lw_reduce", "sw_gas_optics", "sw_solver", "sw_reduce")
 
-    def __init__(self, be, kd_lw, kd_sw, atm, do_broadband=False, overlap=False, cloud_luts=None, sort_columns=None, byband=False):
+    def __init__(self, be, kd_lw, kd_sw, atm, do_broadband=False, overlap=False, cloud_luts=None, sort_columns=None, byband=False,
+                 sunlit=False):
         import torch
         self.torch = torch
         # byband: the step also fills self.bnd_fluxes (lw_up/lw_dn/lw_net/sw_up/sw_dn/sw_dir/sw_net, (nbnd, nlev, ncol) each, the
@@ -268,6 +271,30 @@ class ResidentSolver:
                 self.bnd_lw_sorted = e((3, kd_lw.nbnd, nlay+1, ncol)); self.bnd_sw_sorted = e((4, kd_sw.nbnd, nlay+1, ncol))
             self.bnd_fluxes = dict(lw_up=self.bnd_lw[0], lw_dn=self.bnd_lw[1], lw_net=self.bnd_lw[2],
                                    sw_up=self.bnd_sw[0], sw_dn=self.bnd_sw[1], sw_dir=self.bnd_sw[2], sw_net=self.bnd_sw[3])
+        # sunlit-only SW: every step lists the columns with mu0 > 0 on the device (in the step's own column order), gathers the SW
+        # inputs of those columns into the buffers below, runs the SW chain on that many columns (views of the full-size SW buffers)
+        # and scatters the SW fluxes back with zeros in the night columns. The host needs the count to size the launches: it is
+        # copied to pinned memory at the top of the step and waited for only once the LW chain has been enqueued. All columns
+        # sunlit: the plain SW path, bit for bit.
+        self.sunlit = bool(sunlit)
+        if self.sunlit:
+            # (padded to a multiple of 16 like the plain step: at most ncol rounded up to 16, which the step's buffers hold)
+            self.sun_pad = 16 if (bool(int(os.environ.get("RRX_PAD_COLUMNS", "1"))) and atm.ncol > 16) else 1
+            nmax = -(-atm.ncol // self.sun_pad) * self.sun_pad
+            assert nmax <= ncol
+            self.sun_perm = be.int_empty((nmax,))
+            self.sun_count = be.int_empty((1,))
+            self.sun_count_host = torch.empty((1,), dtype=torch.int32, pin_memory=True)
+            self.sun_event = torch.cuda.Event()
+            self.sun_wait_ms = 0.0      # host time spent waiting for the count, summed over the steps
+            self.sun_in = {}            # gathered SW inputs, (..., ncol) fields at full width
+            for k in self._SW_FIELDS:
+                v = getattr(atm, k)
+                if v is not None and (cloud_luts is not None or k not in ("lwp", "iwp", "rel", "dei")):
+                    self.sun_in[k] = e(tuple(v.shape[:-1]) + (ncol,) if self._COLUMN_FIELDS[k] < 0 else (ncol,) + tuple(v.shape[1:]))
+            self.sun_vmr = {n: e((nlay, ncol)) for n, t in atm.vmr.items() if hasattr(t, "dim") and t.dim() == 2}
+            self.sun_fluxes = e((4, nlay+1, ncol))
+            self.sun_bnd = e((4, kd_sw.nbnd, nlay+1, ncol)) if self.byband else None
         self.weights = be.asarray(np.ascontiguousarray(GAUSS_WTS[0, :1]))
         self.gauss_Ds = be.asarray(GAUSS_DS)
         # secants and the band -> g-point expansion of emissivity / albedos: buffers allocated once, the launches themselves are
@@ -293,6 +320,47 @@ class ResidentSolver:
     _COLUMN_FIELDS = {"p_lay": -1, "p_lev": -1, "t_lay": -1, "t_lev": -1, "t_sfc": 0, "mu0": 0, "tsi_scaling": 0,
                       "emis_sfc": 0, "sfc_alb_dir": 0, "sfc_alb_dif": 0, "lwp": -1, "iwp": -1, "rel": -1, "dei": -1, "rh": -1}
 
+    _SW_FIELDS = ("p_lay", "p_lev", "t_lay", "mu0", "tsi_scaling", "sfc_alb_dir", "sfc_alb_dif", "lwp", "iwp", "rel", "dei")
+
+    @staticmethod
+    def _cols(t, n):
+        """The leading part of a (..., ncol) buffer as a contiguous (..., n) tensor."""
+        lead = tuple(t.shape[:-1])
+        return t.view(-1)[:int(np.prod(lead, dtype=np.int64))*n].view(lead + (n,))
+
+    @staticmethod
+    def _rows(t, n):
+        """The leading part of an (ncol, ...) buffer as a contiguous (n, ...) tensor."""
+        rest = tuple(t.shape[1:])
+        return t.view(-1)[:int(np.prod(rest, dtype=np.int64))*n].view((n,) + rest)
+
+    def _sunlit_atmosphere(self, n_out):
+        """The SW inputs of the columns sun_perm[:n_out], gathered on the device into the resident buffers (views of n_out columns)."""
+        from .synthetic import Atmosphere
+        be, a, perm = self.be, self.atm, self.sun_perm
+        out = dict(a.__dict__)         # (fields the SW chain does not read stay as they are)
+        out["ncol"] = n_out
+        for k, buf in self.sun_in.items():
+            v = getattr(a, k)
+            if self._COLUMN_FIELDS[k] < 0 or v.dim() == 1:        # column fastest: (..., ncol) or (ncol,)
+                o = self._cols(buf, n_out) if self._COLUMN_FIELDS[k] < 0 else buf[:n_out]
+                nrest = int(np.prod(v.shape[:-1], dtype=np.int64)) if v.dim() > 1 else 1
+                be._c("gather_cols", n_out, ctypes.c_ulonglong(nrest), perm, a.ncol, v, o)
+            else:                                                  # column slowest: (ncol, nbnd)
+                o = self._rows(buf, n_out)
+                be._c("gather_lastdim", int(v.shape[1]), n_out, perm, v, o)
+            out[k] = o
+        vmr = {}
+        for n, t in a.vmr.items():
+            if n in self.sun_vmr:
+                o = self._cols(self.sun_vmr[n], n_out)
+                be._c("gather_cols", n_out, ctypes.c_ulonglong(t.shape[0]), perm, a.ncol, t, o)
+                vmr[n] = o
+            else:
+                vmr[n] = t
+        out["vmr"] = vmr
+        return Atmosphere(**out)
+
     def refresh_column_order(self):
         """(Re)build the gather index of a step: ascending surface pressure when sorting, the caller's order otherwise, padded with
         repeats of its last entry. Call it again when the pressures have changed enough to matter; the index is reused otherwise."""
@@ -305,6 +373,7 @@ class ResidentSolver:
         if self.npad:
             perm = torch.cat([perm, perm[-1:].expand(self.npad)])
         self.perm = perm.contiguous()
+        self.perm_i32 = self.perm.to(torch.int32)        # (the order of the sunlit-column list: the HIP entries take int32)
 
     def _gathered_atmosphere(self):
         """The atmosphere with its columns in the order (and count) of self.perm."""
@@ -343,6 +412,12 @@ class ResidentSolver:
         BL = self.bnd_lw if perm is None else self.bnd_lw_sorted
         BS = self.bnd_sw if perm is None else self.bnd_sw_sorted
         main = self.torch.cuda.current_stream(be.device)
+        sw_day = False                # this step's SW chain runs on the sunlit columns only
+        if self.sunlit:               # the column list and its count, on the device; the count travels to pinned host memory
+            n = self.ncol_caller
+            be.sunlit_columns(self.atm.mu0, None if perm is None else self.perm_i32[:n], self.sun_pad, perm=self.sun_perm, count=self.sun_count)
+            self.sun_count_host.copy_(self.sun_count, non_blocking=True)
+            self.sun_event.record(main)
         for ichain, (kind, kd, buf) in enumerate((("lw", self.kd_lw, self.lw), ("sw", self.kd_sw, self.sw))):
             if self.overlap:
                 self.streams[ichain].wait_stream(main)
@@ -350,6 +425,30 @@ class ResidentSolver:
                 ctx.__enter__()
             mark(kind + "_gas_optics")
             col_dry = self.col_dry2 if (self.overlap and ichain == 1) else self.col_dry
+            if kind == "sw" and self.sunlit:
+                t0 = time.perf_counter()
+                self.sun_event.synchronize()      # the LW chain is enqueued by now; the count was ready long before
+                self.sun_wait_ms += (time.perf_counter() - t0) * 1e3
+                n_day = int(self.sun_count_host[0])
+                sw_day = n_day < self.ncol_caller
+                if sw_day:
+                    n_out = -(-n_day // self.sun_pad) * self.sun_pad
+                    FS = [None, None, None] + list(self._cols(self.sun_fluxes, n_out))
+                    BSd = self._cols(self.sun_bnd, n_out) if self.byband else None
+                    if n_day == 0:                # all dark: no SW launches, only the zero fill
+                        mark("sw_gas_optics", True); mark("sw_solver"); mark("sw_solver", True); mark("sw_reduce")
+                        self._sunlit_scatter(0, 0, BSd)
+                        mark("sw_reduce", True)
+                        if self.overlap:
+                            ctx.__exit__(None, None, None)
+                        continue
+                    atm_full, ncol_full = atm, ncol
+                    atm, ncol = self._sunlit_atmosphere(n_out), n_out
+                    col_dry = self._cols(col_dry, n_out)
+                    buf = {k: self._cols(v, n_out) for k, v in buf.items()}
+                    alb_dir, alb_dif = self._cols(self.alb_dir, n_out), self._cols(self.alb_dif, n_out)
+                    F_full, BS_full = F, BS
+                    F, BS = FS, BSd
             be._c("get_col_dry", ncol, nlay, atm.vmr["h2o"], atm.p_lev, col_dry)
             col_gas = be.fill_gases(kd, atm.vmr, col_dry)
             it = None if self.direct else be.interpolation(kd, atm.p_lay, atm.t_lay, col_gas)
@@ -403,6 +502,8 @@ class ResidentSolver:
                 be.net_broadband_precalc(F[1], F[0], out=F[2])
                 mark("lw_reduce", True)
             else:
+                if not sw_day:
+                    alb_dir, alb_dif = self.alb_dir, self.alb_dif
                 # clear sky: the asymmetry parameter is identically zero; the fused broadband solver takes "no g" natively
                 gbuf = None if (self.g_zero and self.do_broadband) else buf["g"]
                 cld = None
@@ -417,24 +518,27 @@ class ResidentSolver:
                     be.inc_2stream_by_2stream_bybnd(buf["tau"], buf["ssa"], gbuf, *cld, kd.band_lims_gpt)
                 mark("sw_gas_optics", True)
                 mark("sw_solver")
-                be._c("expand_and_transpose", ncol, kd.nbnd, kd.band_lims_gpt, atm.sfc_alb_dir, self.alb_dir)
-                be._c("expand_and_transpose", ncol, kd.nbnd, kd.band_lims_gpt, atm.sfc_alb_dif, self.alb_dif)
+                be._c("expand_and_transpose", ncol, kd.nbnd, kd.band_lims_gpt, atm.sfc_alb_dir, alb_dir)
+                be._c("expand_and_transpose", ncol, kd.nbnd, kd.band_lims_gpt, atm.sfc_alb_dif, alb_dif)
                 if self.byband:
-                    be.sw_solver_2stream_byband(atm.top_at_1, buf["tau"], buf["ssa"], gbuf, atm.mu0, self.alb_dir, self.alb_dif, toa,
+                    be.sw_solver_2stream_byband(atm.top_at_1, buf["tau"], buf["ssa"], gbuf, atm.mu0, alb_dir, alb_dif, toa,
                                                 kd.band_lims_gpt, out=dict(bnd_flux_up=BS[0], bnd_flux_dn=BS[1], bnd_flux_dir=BS[2],
                                                                            bnd_flux_net=BS[3], flux_up=F[3], flux_dn=F[4], flux_dir=F[5]))
                 elif self.do_broadband:
                     be._c("sw_solver_2stream", ncol, nlay, kd.ngpt, BoolArg(atm.top_at_1), buf["tau"], buf["ssa"], gbuf, atm.mu0,
-                          self.alb_dir, self.alb_dif, toa, None, None, None, BoolArg(False), None,
+                          alb_dir, alb_dif, toa, None, None, None, BoolArg(False), None,
                           BoolArg(True), F[3], F[4], F[5])
                 else:
-                    be.sw_solver_2stream_into(atm.top_at_1, buf["tau"], buf["ssa"], gbuf, atm.mu0, self.alb_dir, self.alb_dif,
+                    be.sw_solver_2stream_into(atm.top_at_1, buf["tau"], buf["ssa"], gbuf, atm.mu0, alb_dir, alb_dif,
                                               toa, buf["gpt_up"], buf["gpt_dn"], buf["gpt_dir"])
                 mark("sw_solver", True)
                 mark("sw_reduce")
                 if not self.do_broadband:
                     be.sum_broadband(buf["gpt_up"], out=F[3]); be.sum_broadband(buf["gpt_dn"], out=F[4]); be.sum_broadband(buf["gpt_dir"], out=F[5])
                 be.net_broadband_precalc(F[4], F[3], out=F[6])
+                if sw_day:                        # back to the caller's columns, zeros in the night ones
+                    self._sunlit_scatter(n_day, ncol, BS)
+                    atm, ncol, F, BS = atm_full, ncol_full, F_full, BS_full
                 mark("sw_reduce", True)
             if self.overlap:
                 ctx.__exit__(None, None, None)
@@ -442,8 +546,18 @@ class ResidentSolver:
             main.wait_stream(self.streams[0]); main.wait_stream(self.streams[1])
         if perm is not None:                              # back to the caller's column order (padding columns dropped)
             n = self.ncol_caller
-            self.fluxes.index_copy_(2, perm[:n], F[:, :, :n])
+            nf = 3 if sw_day else 7                       # (a sunlit-only SW chain has written the caller's order already)
+            self.fluxes[:nf].index_copy_(2, perm[:n], F[:nf, :, :n])
             F = self.fluxes
             if self.byband:
-                self.bnd_lw.index_copy_(3, perm[:n], BL[..., :n]); self.bnd_sw.index_copy_(3, perm[:n], BS[..., :n])
+                self.bnd_lw.index_copy_(3, perm[:n], BL[..., :n])
+                if not sw_day:
+                    self.bnd_sw.index_copy_(3, perm[:n], BS[..., :n])
         return F
+
+    def _sunlit_scatter(self, n_day, n_out, BSd):
+        """SW fluxes of the sunlit columns (sun_fluxes, BSd: n_out columns in sun_perm order) into the caller's arrays, zeros elsewhere."""
+        be = self.be
+        be.scatter_cols_fill(n_day, self.sun_perm, self._cols(self.sun_fluxes, n_out), self.fluxes[3:7])
+        if self.byband:
+            be.scatter_cols_fill(n_day, self.sun_perm, BSd, self.bnd_sw)

@@ -223,7 +223,8 @@ def case_rfmip(data, work, threshold=5.8e-2):
     got = {}
     for expt, dims, v in rfmip_inputs(data, work, n_bnd_lw, n_bnd_sw):
         rrxio.write(os.path.join(work, "rte_rrtmgp_input.nc"), dims, v)
-        if run_driver(work) != 0:
+        # night sites reach the solver with mu0 = 0 (rfmip_init.py: max(0, cos(sza))): solved on the sunlit sites only, zeros elsewhere
+        if run_driver(work, "--sunlit-columns") != 0:
             raise RuntimeError(f"driver failed on RFMIP experiment {expt}")
         _, out = nc_read(os.path.join(work, "rte_rrtmgp_output.nc"), work)
         shutil.copyfile(os.path.join(work, "rte_rrtmgp_output.nc"), os.path.join(work, "rte_rrtmgp_output_expt_%02d.nc" % expt))
