@@ -22,6 +22,19 @@ class Rte_lw_gpu
                 Array_gpu<Float,3>& gpt_flux_up,
                 Array_gpu<Float,3>& gpt_flux_dn,
                 const int n_gauss_angles);
+        // the same plus flux_up_jac, the surface-temperature Jacobian of the upward flux [W m-2 K-1], shaped like the flux arrays:
+        // third dimension 1 = broadband (with Planck-lite sources and one angle the fused solver, rrx_lw_solver_noscat_fractions_jac),
+        // ngpt = per g-point (the general solver with do_jacobians). By-band flux arrays have no Jacobian form.
+        void rte_lw(
+                const std::unique_ptr<Optical_props_arry_gpu>& optical_props,
+                const Bool top_at_1,
+                const Source_func_lw_gpu& sources,
+                const Array_gpu<Float,2>& sfc_emis,
+                const Array_gpu<Float,2>& inc_flux,
+                Array_gpu<Float,3>& gpt_flux_up,
+                Array_gpu<Float,3>& gpt_flux_dn,
+                Array_gpu<Float,3>& flux_up_jac,
+                const int n_gauss_angles);
         // by-band fluxes (ncol, nlev, nband); bnd_flux_net (dn - up per band) and the broadband flux_up/dn (the band sums added in
         // band order) are written when their size is not 0
         void rte_lw_byband(
@@ -40,6 +53,10 @@ class Rte_lw_gpu
                 const Array_gpu<Float,2> arr_in,
                 Array_gpu<Float,2>& arr_out);
     private:
+        void solve(
+                const std::unique_ptr<Optical_props_arry_gpu>& optical_props, const Bool top_at_1, const Source_func_lw_gpu& sources,
+                const Array_gpu<Float,2>& sfc_emis, const Array_gpu<Float,2>& inc_flux,
+                Array_gpu<Float,3>& gpt_flux_up, Array_gpu<Float,3>& gpt_flux_dn, Array_gpu<Float,3>* flux_up_jac, const int n_gauss_angles);
         // Gauss-Jacobi secants and weights on the device, uploaded once per object and angle count (an upload per call is a host
         // copy the stream is synchronised for: the solver launch then waits for the gas optics to finish before it is even enqueued)
         Array_gpu<Float,2> gauss_Ds_gpu, gauss_wts_gpu;

@@ -340,6 +340,19 @@ int rrx_lw_solver_noscat_fractions_byband##SFX( \
         const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands, const int* band_lims_gpt, \
         const F* sfc_emis, const F* sfc_src, const F* inc_flux, \
         F* bnd_flux_up, F* bnd_flux_dn, F* bnd_flux_net, F* flux_up, F* flux_dn, void* stream); \
+/* rrx_lw_solver_noscat_fractions plus the surface-temperature Jacobian of the upward flux from the same solve: sfc_src_jac is \
+   (ngpt, ncol) (d sfc_src / d T_sfc over 1 K, as rrx_gas_optics_lw_fractions writes it), flux_up_jac (ncol, nlay+1) in W m-2 K-1 \
+   = sum over g-points of pi*w*J_g, J_g(surface) = sfc_emis*sfc_src_jac, J_g(level) = trans(layer below)*J_g(level below). \
+   flux_up_loc / flux_dn_loc are bit for bit those of rrx_lw_solver_noscat_fractions */ \
+int rrx_lw_solver_noscat_fractions_jac##SFX( \
+        int ncol, int nlay, int ngpt, RrxBool top_at_1, const F* secants, const F* weights, \
+        const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands, \
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up_loc, F* flux_dn_loc, \
+        const F* sfc_src_jac, F* flux_up_jac, void* stream); \
+/* host-model update between radiation calls (no counterpart in the reference library): with d = flux_up_jac * (t_sfc_new - \
+   t_sfc_old) of the level's column, flux_up += d and (flux_net not NULL) flux_net -= d; flux arrays (ncol, nlev), t_sfc (ncol) */ \
+int rrx_lw_flux_up_adjust##SFX(int ncol, int nlev, const F* flux_up_jac, const F* t_sfc_old, const F* t_sfc_new, \
+        F* flux_up, F* flux_net, void* stream); \
 /* ---- Optical_props_kernels_cuda : include_kernels_cuda/optical_props_kernels_cuda.h:33-56 ---- */ \
 int rrx_increment_1scalar_by_1scalar##SFX(int ncol, int nlay, int ngpt, F* tau_inout, const F* tau_in, void* stream); \
 int rrx_increment_2stream_by_2stream##SFX(int ncol, int nlay, int ngpt, F* tau_inout, F* ssa_inout, F* g_inout, const F* tau_in, const F* ssa_in, const F* g_in, void* stream); \

@@ -80,10 +80,18 @@ class Radiation_solver_longwave
         // Not applied when optical properties are output (switch_output_optical).
         void set_column_sorting(const int mode) { column_sorting = mode; sort_decided = -1; }
         void set_column_padding(const bool b) { column_padding = b; }
+        // Surface-temperature Jacobian of the upward flux (default off): with fluxes requested, solve_gpu also forms d flux_up /
+        // d T_sfc [W m-2 K-1] per level from the same solve (the fused broadband solver's Jacobian form, or the general solver's
+        // per-g-point Jacobians summed over the g-points); get_lw_flux_up_jac() returns the (ncol, nlev) result of the last solve in
+        // the caller's column order. A host model updates flux_up (and flux_net) with it between radiation calls
+        // (rrx_lw_flux_up_adjust). Not with set_byband_solvers(true): solve_gpu throws.
+        void set_jacobian(const bool b) { jacobian = b; }
+        const Array_gpu<Float,2>& get_lw_flux_up_jac() const { return lw_flux_up_jac; }
 
     private:
         int column_sorting = -1, sort_decided = -1;
-        bool column_padding = true, reordered_call = false;
+        bool column_padding = true, reordered_call = false, jacobian = false;
+        Array_gpu<Float,2> lw_flux_up_jac;
         std::unique_ptr<Gas_optics_rrtmgp_gpu> kdist_gpu;
         std::unique_ptr<Cloud_optics_gpu> cloud_optics_gpu;
         Rte_lw_gpu rte_lw;

@@ -341,7 +341,7 @@ lw_noscat_scan_kernel(
 //          exactly the expressions of Planck_source_kernel (gas_optics_rrtmgp_kernels.cu:196-314). Two cell arrays read per
 //          g-point instead of three, and the Planck kernel writes one instead of two (LW chain at C4: 9.9 -> 7.5 ms).
 //          The band's B values sit in per-thread LDS columns and are refreshed when the band changes.
-// One quadrature angle, no Jacobian (the general kernel above keeps those).
+// One quadrature angle (the general kernel above keeps more); the surface-temperature Jacobian in the JAC form (below).
 #ifndef RRX_LW_LACC
 #define RRX_LW_LACC 1
 #endif
@@ -372,7 +372,12 @@ __device__ unsigned long long g_lw_clk[16][8];
 #endif
 // BND (by-band outputs): blockIdx.y = band b, whose g-points [band_lims[2b]-1, band_lims[2b+1]) the workgroup sums in order from zero
 // (rrx_sum_byband's order); the sums go to band slab b of flux_up/flux_dn, (ncol, nlev, nbnd) arrays. An empty band writes zeros.
-template<typename F, int V, int K, int W, int CLT, bool LITE, bool PRE, bool GS = false, int EV = RRX_LW_EV, int NW = (W > 4 ? W : 4), bool BND = false>
+// JAC (surface-temperature Jacobian of the upward flux, rrx_lw_solver_noscat_fractions_jac): the upward scan's transmittance product
+// below the lane, times emis*sfc_src_jac, is the lane's incoming Jacobian (the general kernel's jac_in); the replay is jc = trans*jc and
+// the g-point sums go to flux_up_jac in order with add_rounded, like the fluxes. The sums sit in registers (K more per column) whatever
+// LACC says: the LDS of the four-wave fp64 form has no room for a third column at two workgroups per CU.
+template<typename F, int V, int K, int W, int CLT, bool LITE, bool PRE, bool GS = false, int EV = RRX_LW_EV, int NW = (W > 4 ? W : 4), bool BND = false,
+         bool JAC = false>
 __global__ void __launch_bounds__(64*NW, (NW > W) ? RRX_LW_F32_WAVES : (NW > 4 ? 1 : 2))
 lw_noscat_bb_kernel(
         const int ncol, const int nlay, const int ngpt, const int top_at_1,
@@ -381,13 +386,15 @@ lw_noscat_bb_kernel(
         const F* __restrict__ blay, const F* __restrict__ blev, const int* __restrict__ gpoint_bands,
         const F* __restrict__ sfc_emis, const F* __restrict__ sfc_src, const F* __restrict__ inc_flux,
         F* __restrict__ flux_up, F* __restrict__ flux_dn, const int gper, const size_t part_stride,
-        const int* __restrict__ band_lims)
+        const int* __restrict__ band_lims, const F* __restrict__ sfc_src_jac = nullptr, F* __restrict__ flux_up_jac = nullptr)
 {
     static_assert(!(GS && BND), "a by-band launch is its own g-point split");
+    static_assert(!(JAC && BND), "no by-band Jacobian");
     // GS: blockIdx.y = g-point range [g_lo, g_hi) of this workgroup; its sums go to partial array blockIdx.y
     const int g_lo = BND ? max(band_lims[2*blockIdx.y] - 1, 0) : (GS ? blockIdx.y*gper : 0);
     const int g_hi = BND ? min(band_lims[2*blockIdx.y+1], ngpt) : (GS ? min(ngpt, g_lo + gper) : ngpt);
     if constexpr (GS || BND) { flux_up += blockIdx.y*part_stride; flux_dn += blockIdx.y*part_stride; }
+    if constexpr (GS && JAC) flux_up_jac += blockIdx.y*part_stride;
     constexpr int CL = CLT, LL = 64/CLT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cl = lane & (CL-1), ll = lane / CL;
@@ -423,6 +430,14 @@ lw_noscat_bb_kernel(
             if constexpr (LACC) { lds_acc[j*V+v][tid] = F(0.); lds_acc[(K+j)*V+v][tid] = F(0.); }
             else { acc_up[j][v] = F(0.); acc_dn[j][v] = F(0.); }
         }
+    F acc_jc[JAC ? K : 1][V];
+    if constexpr (JAC)
+    {
+        #pragma unroll
+        for (int j=0; j<K; ++j)
+            #pragma unroll
+            for (int v=0; v<V; ++v) acc_jc[j][v] = F(0.);
+    }
 
     // element offsets inside one g-point slab: sweep layer s = t0+j, sweep level t = t0+j (clamped into the domain)
     auto lay_off = [&](const int j) -> unsigned
@@ -437,7 +452,7 @@ lw_noscat_bb_kernel(
     };
 
     struct Loads { Vec<F,V> a0[K], a1[K], a2[LITE ? 1 : K], x_next, x_prev, emis, ssrc, D, inc; };
-    auto issue = [&](const int g, Loads& L)
+    auto issue = [&](const int g, Loads& L, Vec<F,V>& J)
     {
         const F* __restrict__ t_g = tau + size_t(g)*ncl*nlay;
         const F* __restrict__ l_g = lay_source + size_t(g)*ncl*nlay;
@@ -458,10 +473,12 @@ lw_noscat_bb_kernel(
         const size_t sfc = size_t(g)*ncl + icol;
         L.emis = load_cols<F,V>(sfc_emis + sfc); L.ssrc = load_cols<F,V>(sfc_src + sfc); L.D = load_cols<F,V>(secants + sfc);
         if (inc_flux != nullptr) L.inc = load_cols<F,V>(inc_flux + sfc);
+        if constexpr (JAC) J = load_cols<F,V>(sfc_src_jac + sfc);
     };
 
     Loads nxt;
-    if constexpr (PRE) { if (!BND || g_lo < g_hi) issue(g_lo, nxt); }     // (an empty band prefetches nothing: g_lo may be ngpt)
+    Vec<F,V> jnxt, jcur;                                        // sfc_src_jac of the next / current g-point (JAC only)
+    if constexpr (PRE) { if (!BND || g_lo < g_hi) issue(g_lo, nxt, jnxt); }     // (an empty band prefetches nothing: g_lo may be ngpt)
     int cur_bnd = -1;
     const F wgt = weights[0];
     const F scale = pi * wgt;
@@ -474,7 +491,7 @@ lw_noscat_bb_kernel(
     RRX_LW_T(7)
     if constexpr (!PRE) __syncthreads();        // partner waves issue their load bursts together
     Loads cur;
-    if constexpr (PRE) cur = nxt; else issue(igpt, cur);
+    if constexpr (PRE) { cur = nxt; if constexpr (JAC) jcur = jnxt; } else issue(igpt, cur, jcur);
 
     if constexpr (LITE)
     {
@@ -551,7 +568,7 @@ lw_noscat_bb_kernel(
     }
 
     RRX_LW_T(0)
-    F dn_in[V], up_in[V];
+    F dn_in[V], up_in[V], jc_in[V];
     #pragma unroll
     for (int v=0; v<V; ++v)
     {
@@ -574,7 +591,7 @@ lw_noscat_bb_kernel(
             {
                 // every wave of the workgroup is here: the waves that share 128-B lines ask for them together
                 __builtin_amdgcn_sched_barrier(0);
-                issue(min(igpt + 1, g_hi - 1), nxt);            // (last iteration: a harmless re-read)
+                issue(min(igpt + 1, g_hi - 1), nxt, jnxt);      // (last iteration: a harmless re-read)
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -614,6 +631,7 @@ lw_noscat_bb_kernel(
         ae = shfl(a, lane + CL); be = shfl(b, lane + CL);
         if (ll == LL-1) { ae = xa; be = xb; }
         up_in[v] = ae*up_sfc + be;
+        if constexpr (JAC) jc_in[v] = ae * cur.emis.v[v] * jcur.v[v];
     }
 
     #pragma unroll
@@ -634,6 +652,12 @@ lw_noscat_bb_kernel(
             up = tr[j][v]*up + sup[j][v];
             if constexpr (LACC) { F a = lds_acc[j*V+v][tid]; add_rounded(a, scale*up); lds_acc[j*V+v][tid] = a; }
             else add_rounded(acc_up[j][v], scale*up);
+        }
+        if constexpr (JAC)
+        {
+            F jc = jc_in[v];
+            #pragma unroll
+            for (int j=K-1; j>=0; --j) { jc = tr[j][v]*jc; add_rounded(acc_jc[j][v], scale*jc); }
         }
     }
     RRX_LW_T(3)
@@ -659,6 +683,13 @@ lw_noscat_bb_kernel(
             }
             store_cols<F,V>(flux_up + o, u);
             store_cols<F,V>(flux_dn + o, d);
+            if constexpr (JAC)
+            {
+                Vec<F,V> jv;
+                #pragma unroll
+                for (int v=0; v<V; ++v) jv.v[v] = acc_jc[j][v];
+                store_cols<F,V>(flux_up_jac + o, jv);
+            }
         }
     }
 }
@@ -863,20 +894,23 @@ bool launch_scan_bb16(
 
 
 // second-generation fused broadband kernel (lw_noscat_bb_kernel); LITE: lay_source = pfrac, lev_source unused
-template<typename F, int V, int W, int CLT, bool LITE, int NW = (W > 4 ? W : 4)>
+// JAC: the Jacobian form, in the geometry and g-point split the fluxes alone would take (so they come out bit for bit the same),
+// always with the pipelined loads
+template<typename F, int V, int W, int CLT, bool LITE, int NW = (W > 4 ? W : 4), bool JAC = false>
 bool launch_bb2(
         hipStream_t st, const bool pre, const int ncol, const int nlay, const int ngpt, const int top_at_1,
         const F* secants, const F* weights, const F* tau, const F* lay_source, const F* lev_source,
         const F* blay, const F* blev, const int* gpoint_bands,
         const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn,
-        const int* band_lims = nullptr, const int nbnd = 0 /* by-band form: flux_up/dn are (ncol, nlev, nbnd) band sums */)
+        const int* band_lims = nullptr, const int nbnd = 0 /* by-band form: flux_up/dn are (ncol, nlev, nbnd) band sums */,
+        const F* sfc_src_jac = nullptr, F* flux_up_jac = nullptr /* JAC: (ngpt, ncol) in, (ncol, nlev) out */)
 {
     if (size_t(ncol)*(nlay+1) >= (size_t(1) << 31)) return false;          // 32-bit element offsets inside a g-point slab
     const int groups = ceil_div(ncol, (NW/W)*CLT*V);
     const int need = ceil_div(nlay+1, (64/CLT)*W);
     if (need > ((CLT == 16 || W == 8) ? 9 : 5)) return false;
     const size_t nlevcol = size_t(ncol)*(nlay+1);
-    if (band_lims != nullptr)
+    if (!JAC && band_lims != nullptr)
     {
         // one band per workgroup (grid.y = band): no store inside the g-point loop, no partial arrays, no allocation. Always the
         // pipelined form. Planck-lite inputs only (the by-band entry is rrx_lw_solver_noscat_fractions_byband).
@@ -898,11 +932,18 @@ bool launch_bb2(
     const int gper = ceil_div(ngpt, broadband_gsplit(groups, ngpt, (NW > 4) ? 256 : 512));      // (one or two workgroups per CU)
     const int nsplit = ceil_div(ngpt, gper);               // no empty range: every workgroup's first g-point exists (it is prefetched)
     StreamScratch scratch(st);
-    F* out_up = flux_up; F* out_dn = flux_dn;
-    if (nsplit > 1) { out_up = scratch.get<F>(2*nsplit*nlevcol); out_dn = out_up + nsplit*nlevcol; }
+    F* out_up = flux_up; F* out_dn = flux_dn; F* out_jc = flux_up_jac;
+    if (nsplit > 1) { out_up = scratch.get<F>((JAC ? 3 : 2)*nsplit*nlevcol); out_dn = out_up + nsplit*nlevcol; out_jc = out_dn + nsplit*nlevcol; }
     const dim3 grid(groups, nsplit);
 #define RRX_LW_B2(KK) if (need <= KK) { \
-        if (nsplit > 1 && pre) lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,true,true,RRX_LW_EV,NW><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, \
+        if constexpr (JAC) { \
+            if (nsplit > 1) lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,true,true,RRX_LW_EV,NW,false,true><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, \
+                top_at_1, secants, weights, tau, lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, \
+                gper, nlevcol, nullptr, sfc_src_jac, out_jc); \
+            else lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,true,false,RRX_LW_EV,NW,false,true><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, \
+                top_at_1, secants, weights, tau, lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, \
+                gper, nlevcol, nullptr, sfc_src_jac, out_jc); } \
+        else if (nsplit > 1 && pre) lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,true,true,RRX_LW_EV,NW><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, \
             lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, gper, nlevcol, nullptr); \
         else if (nsplit > 1) lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,false,true,RRX_LW_EV,NW><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, \
             lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, gper, nlevcol, nullptr); \
@@ -916,21 +957,24 @@ bool launch_bb2(
     else if constexpr (W == 8) { RRX_LW_B2(5) RRX_LW_B2(7) RRX_LW_B2(9) }      // (288 ... 319 / 447 / 575 layers: eight waves of 8 x 8 lanes)
     else                     { RRX_LW_B2(2) RRX_LW_B2(3) RRX_LW_B2(5) }
     } while (false);
-    if (nsplit > 1)      // (out_up, out_dn lie behind each other in the scratch block)
-        sum_ranges_kernel<F,2><<<dim3(ceil_div(nlevcol, 256), 2), 256, 0, st>>>(nlevcol, nsplit, out_up, flux_up, flux_dn, (F*)nullptr);
+    if (nsplit > 1)      // (out_up, out_dn [, out_jc] lie behind each other in the scratch block)
+        sum_ranges_kernel<F,JAC ? 3 : 2><<<dim3(ceil_div(nlevcol, 256), JAC ? 3 : 2), 256, 0, st>>>(nlevcol, nsplit, out_up, flux_up, flux_dn,
+                                                                                                   JAC ? flux_up_jac : (F*)nullptr);
     return true;
 #undef RRX_LW_B2
 }
 
 // broadband fluxes from tau + (lay_source, lev_source) [LITE = false] or tau + Planck fractions and band Planck functions
 // [LITE = true] in the one-kernel form; false when the shape is outside its tilings (the caller takes another path)
-template<typename F, bool LITE>
+// [JAC = true: flux_up_jac too, from the same forms in the same order]
+template<typename F, bool LITE, bool JAC = false>
 bool lw_fused_broadband(
         hipStream_t st, const int ncol, const int nlay, const int ngpt, const int top_at_1,
         const F* secants, const F* weights, const F* tau, const F* lay_source, const F* lev_source,
         const F* blay, const F* blev, const int* gpoint_bands,
         const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn,
-        const int* band_lims = nullptr, const int nbnd = 0 /* by-band form (launch_bb2) */)
+        const int* band_lims = nullptr, const int nbnd = 0 /* by-band form (launch_bb2) */,
+        const F* sfc_src_jac = nullptr, F* flux_up_jac = nullptr)
 {
     const bool pre = tuning().lw_variant != 13;                 // 13: without the pipelined loads (A/B runs)
     // fp32: 16 x 4 lanes with two columns per lane (128-B rows, K = 9) ahead of 8 x 8 lanes with four (variant 14 = the latter
@@ -940,19 +984,19 @@ bool lw_fused_broadband(
     {
         // (Round 4 measured six waves x six layers per column group -- 384-thread workgroups, three waves per SIMD, 168 VGPRs with
         //  108-124 B of scratch: 4.2-4.7 ms against 2.7 for this form, profiles/r04_fp32_geometry_ab.txt.)
-        if (launch_bb2<F,1,4,16,LITE>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd))
+        if (launch_bb2<F,1,4,16,LITE,4,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
+                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac))
             return true;
         // 144 ... 287 layers: eight wavefronts per column group
-        if (launch_bb2<F,1,8,16,LITE>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd))
+        if (launch_bb2<F,1,8,16,LITE,8,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
+                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac))
             return true;
         // 288 ... 575 layers (round 4: RCEMIP's default is 256 levels, LES grids with a background profile on top exceed 288): the same
         // eight waves with 8 x 8 lanes -- 64 levels per wave at nine layers per lane, 64-B rows (the other half of each 128-B line
         // belongs to the next column group: twice the L2 fetches, on a kernel that stands at a quarter of the HBM roof). Beyond that
         // the one-thread-per-column kernels take over.
-        return launch_bb2<F,1,8,8,LITE>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                        blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd);
+        return launch_bb2<F,1,8,8,LITE,8,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
+                                        blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac);
     }
     else
     {
@@ -962,34 +1006,34 @@ bool lw_fused_broadband(
         // LDS, profiles/r04_fp32_geometry_ab.txt): the LW chain per g-point is short, so halving the wavefronts per column wins.
         // The one-column form stays for odd column counts (variant 15 forces it for tests).
         if (tuning().lw_variant == 15 &&
-            launch_bb2<F,1,4,16,LITE,8>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                        blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd))
+            launch_bb2<F,1,4,16,LITE,8,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
+                                        blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac))
             return true;
         if (ncol % 2 == 0 && v2_first &&
-            launch_bb2<F,2,4,16,LITE>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd))
+            launch_bb2<F,2,4,16,LITE,4,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
+                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac))
             return true;
         if (ncol % 4 == 0 &&
-            launch_bb2<F,4,4,8,LITE>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                     blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd))
+            launch_bb2<F,4,4,8,LITE,4,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
+                                     blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac))
             return true;
         if (ncol % 2 == 0 &&
-            launch_bb2<F,2,4,16,LITE>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd))
+            launch_bb2<F,2,4,16,LITE,4,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
+                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac))
             return true;
         // 144 ... 287 layers: eight wavefronts per column group
         if (ncol % 2 == 0 &&
-            launch_bb2<F,2,8,16,LITE>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd))
+            launch_bb2<F,2,8,16,LITE,8,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
+                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac))
             return true;
         // 288 ... 575 layers: eight waves of 8 x 8 lanes (see fp64)
         if (ncol % 2 == 0 &&
-            launch_bb2<F,2,8,8,LITE>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                     blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd))
+            launch_bb2<F,2,8,8,LITE,8,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
+                                     blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac))
             return true;
         // odd column counts: one column per lane
-        return launch_bb2<F,1,4,16,LITE,8>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                           blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd);
+        return launch_bb2<F,1,4,16,LITE,8,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
+                                           blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac);
     }
 }
 
@@ -1176,6 +1220,73 @@ int lw_solver_noscat_fractions_impl(
     return rc;
 }
 
+// fluxes and the surface-temperature Jacobian of the upward flux (rrx_lw_solver_noscat_fractions_jac): the one-kernel form's JAC
+// variant where the tilings reach, otherwise the route of the broadband entry (sources rebuilt, the general kernel with do_jacobians,
+// per-g-point fluxes and Jacobians in one lease of the stream's workspace) followed by the g-point sum of the Jacobian
+template<typename F>
+int lw_solver_noscat_fractions_jac_impl(
+        const int ncol, const int nlay, const int ngpt, const Bool top_at_1,
+        const F* secants, const F* weights, const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands,
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, const F* sfc_src_jac, F* flux_up_loc, F* flux_dn_loc, F* flux_up_jac,
+        void* stream)
+{
+    RRX_TRY
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (ncol <= 0 || nlay <= 0 || ngpt <= 0) throw std::runtime_error("empty problem");
+    if (flux_up_loc == nullptr || flux_dn_loc == nullptr) throw std::runtime_error("broadband outputs missing");
+    if (sfc_src_jac == nullptr) throw std::runtime_error("sfc_src_jac is null");
+    if (flux_up_jac == nullptr) throw std::runtime_error("flux_up_jac is null");
+    const int var = tuning().lw_variant;
+    const bool fused = (var == 0 || (var >= 13 && var <= 15)) &&
+        lw_fused_broadband<F,true,true>(st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, (const F*)nullptr,
+                                        blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc,
+                                        (const int*)nullptr, 0, sfc_src_jac, flux_up_jac);
+    if (!fused)
+    {
+        const size_t nlevcol = size_t(ncol)*(nlay+1);
+        const size_t n_lay = size_t(ncol)*nlay*ngpt, n_lev = nlevcol*ngpt;
+        WorkspaceLease lease(st);
+        F* flux_ws = lease.get<F>(2*n_lev + n_lay + n_lev + n_lev);  // [per-g-point up | dn | lay_source | lev_source | Jacobian]
+        F* lay = flux_ws + 2*n_lev; F* lev = lay + n_lay; F* jac = lev + n_lev;
+        if (planck_sources_from_fractions_impl<F>(ncol, nlay, ngpt, gpoint_bands, pfrac, blay, blev, lay, lev, stream) != 0 ||
+            lw_solver_noscat_impl<F>(ncol, nlay, ngpt, top_at_1, 1, secants, weights, tau, lay, lev, sfc_emis, sfc_src, inc_flux,
+                                     (F*)nullptr, (F*)nullptr, Bool(1), flux_up_loc, flux_dn_loc, Bool(1), sfc_src_jac, jac, stream,
+                                     flux_ws) != 0)
+            return 1;                                                // (the message is set)
+        sum_gpt_kernel<F><<<ceil_div(nlevcol, 256), 256, 0, st>>>(nlevcol, ngpt, jac, flux_up_jac);
+    }
+    RRX_CATCH("rrx_lw_solver_noscat_fractions_jac")
+}
+
+// host-model update between radiation calls (rrx_lw_flux_up_adjust): d = jac * (t_new - t_old) of the level's column;
+// flux_up += d, flux_net -= d
+template<typename F>
+__global__ void lw_flux_up_adjust_kernel(const size_t n, const int ncol, const F* __restrict__ jac, const F* __restrict__ t_old,
+                                         const F* __restrict__ t_new, F* __restrict__ flux_up, F* __restrict__ flux_net)
+{
+    const size_t i = size_t(blockIdx.x)*blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int icol = int(i % size_t(ncol));
+    const F d = jac[i] * (t_new[icol] - t_old[icol]);
+    flux_up[i] += d;
+    if (flux_net != nullptr) flux_net[i] -= d;
+}
+
+template<typename F>
+int lw_flux_up_adjust_impl(const int ncol, const int nlev, const F* flux_up_jac, const F* t_sfc_old, const F* t_sfc_new,
+                           F* flux_up, F* flux_net, void* stream)
+{
+    RRX_TRY
+    if (ncol <= 0 || nlev <= 0) throw std::runtime_error("empty problem");
+    if (flux_up_jac == nullptr) throw std::runtime_error("flux_up_jac is null");
+    if (t_sfc_old == nullptr || t_sfc_new == nullptr) throw std::runtime_error("surface temperatures missing");
+    if (flux_up == nullptr) throw std::runtime_error("flux_up is null");
+    const size_t n = size_t(ncol)*nlev;
+    lw_flux_up_adjust_kernel<F><<<ceil_div(n, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(n, ncol, flux_up_jac, t_sfc_old, t_sfc_new,
+                                                                                                 flux_up, flux_net);
+    RRX_CATCH("rrx_lw_flux_up_adjust")
+}
+
 // by-band fluxes (rrx_lw_solver_noscat_fractions_byband): the one-kernel form with one band per workgroup where the tilings reach,
 // otherwise the route of the broadband entry there (sources rebuilt, per-g-point fluxes in the stream's workspace lease) followed by
 // the band sums. Band net and broadband outputs come from the band sums in one more pass.
@@ -1294,7 +1405,19 @@ int rrx_lw_solver_noscat_fractions_byband##SFX( \
 { \
     return lw_solver_noscat_fractions_byband_impl<F>(ncol, nlay, ngpt, nbnd, top_at_1, secants, weights, tau, pfrac, blay, blev, \
             gpoint_bands, band_lims_gpt, sfc_emis, sfc_src, inc_flux, bnd_flux_up, bnd_flux_dn, bnd_flux_net, flux_up, flux_dn, stream); \
-}
+} \
+int rrx_lw_solver_noscat_fractions_jac##SFX( \
+        int ncol, int nlay, int ngpt, Bool top_at_1, const F* secants, const F* weights, \
+        const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands, \
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up_loc, F* flux_dn_loc, \
+        const F* sfc_src_jac, F* flux_up_jac, void* stream) \
+{ \
+    return lw_solver_noscat_fractions_jac_impl<F>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, blay, blev, gpoint_bands, \
+            sfc_emis, sfc_src, inc_flux, sfc_src_jac, flux_up_loc, flux_dn_loc, flux_up_jac, stream); \
+} \
+int rrx_lw_flux_up_adjust##SFX(int ncol, int nlev, const F* flux_up_jac, const F* t_sfc_old, const F* t_sfc_new, \
+        F* flux_up, F* flux_net, void* stream) \
+{ return lw_flux_up_adjust_impl<F>(ncol, nlev, flux_up_jac, t_sfc_old, t_sfc_new, flux_up, flux_net, stream); }
 
 RRX_DEFINE_LW_FRACTIONS(double, _f64)
 RRX_DEFINE_LW_FRACTIONS(float, _f32)

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 class CxxDriver:
     def __init__(self, be, kd_lw0, kd_sw0, atm, cloud_luts0=None, column_block=16384, broadband=True, sort_mode=-1, pad=True,
-                 sunlit=False):
+                 sunlit=False, jacobian=False):
         import torch
         self.torch, self.be, self.atm = torch, be, atm
         self.f64 = be.np_dtype == np.float64
@@ -41,11 +41,16 @@ class CxxDriver:
         self._check(self.lib.rrx_cxx_driver_settings(self.h, int(column_block), int(broadband), int(sort_mode), int(pad)))
         if sunlit:                                  # SW on the columns with mu0 > 0 only, zeros elsewhere (set_sunlit_columns)
             self._check(self.lib.rrx_cxx_sunlit_columns(self.h, 1))
+        # jacobian: each step also fills self.lw_flux_up_jac (nlev, ncol), d lw_flux_up / d t_sfc [W m-2 K-1] (set_jacobian)
+        self.jacobian = bool(jacobian)
+        if self.jacobian:
+            self._check(self.lib.rrx_cxx_lw_jacobian(self.h, 1))
         for n, t in atm.vmr.items():                # (nlay, ncol) tensors = (ncol, nlay) arrays; profiles (nlay,) = (1, nlay)
             n1, n2 = (t.shape[1], t.shape[0]) if t.dim() == 2 else ((1, t.shape[0]) if t.dim() == 1 else (1, 1))
             self._check(self.lib.rrx_cxx_driver_set_gas(self.h, n.encode(), ctypes.c_void_p(t.data_ptr()), n1, n2))
         self.nbnd_lw, self.nbnd_sw = kd_lw0.nbnd, kd_sw0.nbnd
         self.fluxes = be.empty((7, atm.nlay + 1, atm.ncol))
+        self.lw_flux_up_jac = be.empty((atm.nlay + 1, atm.ncol)) if self.jacobian else None
         self.sort_columns = sort_mode
 
     def _check(self, rc):
@@ -61,6 +66,8 @@ class CxxDriver:
         self._check(self.lib.rrx_cxx_driver_solve(self.h, a.ncol, a.nlay, self.nbnd_lw, self.nbnd_sw, p(a.p_lay), p(a.p_lev), p(a.t_lay), p(a.t_lev),
                                                   p(a.t_sfc), p(a.emis_sfc), p(a.sfc_alb_dir), p(a.sfc_alb_dif), p(a.tsi_scaling), p(a.mu0),
                                                   p(cl[0]), p(cl[1]), p(cl[2]), p(cl[3]), out7, st))
+        if self.jacobian:
+            self._check(self.lib.rrx_cxx_lw_flux_up_jac(self.h, p(self.lw_flux_up_jac), st))
         return self.fluxes
 
     def close(self):

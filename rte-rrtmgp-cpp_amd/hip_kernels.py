@@ -294,6 +294,26 @@ class HipKernels:
                 fr["pfrac"], fr["blay"], fr["blev"], kd.gpoint_bands, sfc_emis, fr["sfc_src"], inc_flux, flux_up, flux_dn)
         return dict(flux_up=flux_up, flux_dn=flux_dn)
 
+    def lw_solver_noscat_fractions_jac(self, top_at_1, kd, secants, weights, tau, fr, sfc_emis, inc_flux=None, flux_up=None, flux_dn=None,
+                                       flux_up_jac=None):
+        """lw_solver_noscat_fractions plus flux_up_jac (nlev, ncol), the surface-temperature Jacobian of the upward flux
+        [W m-2 K-1] from the same solve (fr["sfc_src_jac"] as gas_optics_lw_fractions writes it); the fluxes are bit for bit those of
+        lw_solver_noscat_fractions"""
+        ngpt, nlay, ncol = tau.shape
+        flux_up = self.empty((nlay+1, ncol)) if flux_up is None else flux_up
+        flux_dn = self.empty((nlay+1, ncol)) if flux_dn is None else flux_dn
+        flux_up_jac = self.empty((nlay+1, ncol)) if flux_up_jac is None else flux_up_jac
+        self._c("lw_solver_noscat_fractions_jac", ncol, nlay, ngpt, BoolArg(top_at_1), secants, weights, tau,
+                fr["pfrac"], fr["blay"], fr["blev"], kd.gpoint_bands, sfc_emis, fr["sfc_src"], inc_flux, flux_up, flux_dn,
+                fr["sfc_src_jac"], flux_up_jac)
+        return dict(flux_up=flux_up, flux_dn=flux_dn, flux_up_jac=flux_up_jac)
+
+    def lw_flux_up_adjust(self, flux_up_jac, t_sfc_old, t_sfc_new, flux_up, flux_net=None):
+        """Host-model update in place: flux_up += jac*(t_new - t_old), flux_net -= the same (when given); (nlev, ncol) arrays"""
+        nlev, ncol = flux_up_jac.shape
+        self._c("lw_flux_up_adjust", ncol, nlev, flux_up_jac, t_sfc_old, t_sfc_new, flux_up, flux_net)
+        return flux_up
+
     def lw_solver_noscat_fractions_byband(self, top_at_1, kd, secants, weights, tau, fr, sfc_emis, inc_flux=None, out=None,
                                           net=True, broadband=True, band_lims=None, gpoint_bands=None):
         """By-band fluxes of lw_solver_noscat_fractions: bnd_flux_up/dn (nbnd, nlev, ncol), bnd_flux_net = dn - up, and the broadband

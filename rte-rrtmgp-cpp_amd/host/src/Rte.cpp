@@ -43,6 +43,32 @@ void Rte_lw_gpu::rte_lw(
         Array_gpu<Float,3>& gpt_flux_dn,
         const int n_gauss_angles)
 {
+    solve(optical_props, top_at_1, sources, sfc_emis, inc_flux, gpt_flux_up, gpt_flux_dn, nullptr, n_gauss_angles);
+}
+
+void Rte_lw_gpu::rte_lw(
+        const std::unique_ptr<Optical_props_arry_gpu>& optical_props,
+        const Bool top_at_1,
+        const Source_func_lw_gpu& sources,
+        const Array_gpu<Float,2>& sfc_emis,
+        const Array_gpu<Float,2>& inc_flux,
+        Array_gpu<Float,3>& gpt_flux_up,
+        Array_gpu<Float,3>& gpt_flux_dn,
+        Array_gpu<Float,3>& flux_up_jac,
+        const int n_gauss_angles)
+{
+    if (is_byband(optical_props, gpt_flux_up)) throw std::runtime_error("rte_lw: no Jacobian for by-band flux arrays");
+    if (flux_up_jac.dim(1) != gpt_flux_up.dim(1) || flux_up_jac.dim(2) != gpt_flux_up.dim(2) || flux_up_jac.dim(3) != gpt_flux_up.dim(3))
+        throw std::runtime_error("rte_lw: flux_up_jac must be shaped like the flux arrays");
+    solve(optical_props, top_at_1, sources, sfc_emis, inc_flux, gpt_flux_up, gpt_flux_dn, &flux_up_jac, n_gauss_angles);
+}
+
+// flux_up_jac: null = no Jacobian
+void Rte_lw_gpu::solve(
+        const std::unique_ptr<Optical_props_arry_gpu>& optical_props, const Bool top_at_1, const Source_func_lw_gpu& sources,
+        const Array_gpu<Float,2>& sfc_emis, const Array_gpu<Float,2>& inc_flux,
+        Array_gpu<Float,3>& gpt_flux_up, Array_gpu<Float,3>& gpt_flux_dn, Array_gpu<Float,3>* flux_up_jac, const int n_gauss_angles)
+{
     if (n_gauss_angles < 1 || n_gauss_angles > max_gauss_pts) throw std::runtime_error("rte_lw: n_gauss_angles must be 1..4");
     if (is_byband(optical_props, gpt_flux_up))
     {
@@ -72,10 +98,18 @@ void Rte_lw_gpu::rte_lw(
     Rte_solver_kernels_cuda::lw_secants_array(ncol, ngpt, n_gauss_angles, max_gauss_pts, gauss_Ds.ptr(), secants.ptr());
 
     const Bool do_broadband = (gpt_flux_up.dim(3) == 1 && ngpt != 1);
-    const Bool do_jacobians = false;
+    const Bool do_jacobians = flux_up_jac != nullptr;
     const Float* inc_flux_ptr = (inc_flux.size() == 0) ? nullptr : inc_flux.ptr();
 
     // Planck-lite state (set by Gas_optics_rrtmgp_gpu::gas_optics): the broadband solver forms the sources itself
+    if (sources.holds_fractions() && do_broadband && n_gauss_angles == 1 && do_jacobians)
+    {
+        RRX_CALL(rrx_lw_solver_noscat_fractions_jac, ncol, nlay, ngpt, top_at_1, secants.ptr(), gauss_wts_subset.ptr(),
+                 optical_props->get_tau().ptr(), sources.get_planck_frac().ptr(), sources.get_planck_lay().ptr(), sources.get_planck_lev().ptr(),
+                 optical_props->get_gpoint_bands_gpu().ptr(), sfc_emis_gpt.ptr(), sources.get_sfc_source().ptr(), inc_flux_ptr,
+                 gpt_flux_up.ptr(), gpt_flux_dn.ptr(), sources.get_sfc_source_jac().ptr(), flux_up_jac->ptr());
+        return;
+    }
     if (sources.holds_fractions() && do_broadband && n_gauss_angles == 1)
     {
         RRX_CALL(rrx_lw_solver_noscat_fractions, ncol, nlay, ngpt, top_at_1, secants.ptr(), gauss_wts_subset.ptr(),
@@ -84,6 +118,10 @@ void Rte_lw_gpu::rte_lw(
                  gpt_flux_up.ptr(), gpt_flux_dn.ptr());
         return;
     }
+    // general solver: per-g-point Jacobians (broadband flux arrays: into a block array, then summed over the g-points)
+    Array_gpu<Float,3> jac_bb;
+    Float* jac_gpt = do_jacobians ? flux_up_jac->ptr() : nullptr;
+    if (do_jacobians && do_broadband) { jac_bb.set_dims({ncol, nlay + 1, ngpt}); jac_gpt = jac_bb.ptr(); }
     Rte_solver_kernels_cuda::lw_solver_noscat(
             ncol, nlay, ngpt, top_at_1, n_gauss_angles,
             secants.ptr(), gauss_wts_subset.ptr(),
@@ -93,7 +131,8 @@ void Rte_lw_gpu::rte_lw(
             inc_flux_ptr,
             gpt_flux_up.ptr(), gpt_flux_dn.ptr(),
             do_broadband, gpt_flux_up.ptr(), gpt_flux_dn.ptr(),
-            do_jacobians, nullptr, nullptr);
+            do_jacobians, do_jacobians ? sources.get_sfc_source_jac().ptr() : nullptr, jac_gpt);
+    if (jac_bb.size() != 0) RRX_CALL(rrx_sum_broadband, ncol, nlay + 1, ngpt, jac_gpt, flux_up_jac->ptr());
 }
 
 void Rte_lw_gpu::rte_lw_byband(

@@ -280,11 +280,13 @@ void compute_heating_rate(const Array_gpu<Float,2>& flux_net, const Array_gpu<Fl
 struct Radiation_solver_longwave::Workspace
 {
     int n_col = 0, n_lay = 0;
-    bool broadband = false, byband = false;
+    bool broadband = false, byband = false, jacobian = false;
     std::unique_ptr<Optical_props_arry_gpu> optical_props;
     std::unique_ptr<Optical_props_1scl_gpu> cloud_optical_props;
     std::unique_ptr<Source_func_lw_gpu> sources;
     Array_gpu<Float,3> gpt_flux_up, gpt_flux_dn;       // (n_col, n_lev, 1 | n_bnd (by-band solvers) | n_gpt)
+    Array_gpu<Float,3> gpt_flux_up_jac;                // (n_col, n_lev, 1 | n_gpt) with the Jacobian
+    Array_gpu<Float,2> flux_up_jac;                    // (n_col, n_lev): its g-point sum (per-g-point solvers)
 };
 
 Radiation_solver_longwave::Radiation_solver_longwave(
@@ -322,6 +324,15 @@ void Radiation_solver_longwave::solve_gpu(
     const bool broadband = broadband_solvers && !switch_output_bnd_fluxes;
     // by-band solvers: the band sums come straight out of the fused solver (one slab per band in the block workspace)
     const bool byband = byband_solvers && switch_output_bnd_fluxes && switch_fluxes && n_bnd < n_gpt;
+    const bool jac = jacobian && switch_fluxes;
+    if (jac && byband_solvers)
+        throw std::runtime_error("Radiation_solver_longwave: the Jacobian (set_jacobian) is not available with the by-band solvers "
+                                 "(set_byband_solvers): no by-band Jacobians");
+    if (jac && (lw_flux_up_jac.dim(1) != n_col || lw_flux_up_jac.dim(2) != n_lev))
+    {
+        lw_flux_up_jac = Array_gpu<Float,2>();
+        lw_flux_up_jac.set_dims({n_col, n_lev});
+    }
 
     // columns in another order / on a padded count: gather the inputs, solve, scatter the fluxes back (see the header)
     if (!reordered_call && !switch_output_optical && switch_fluxes)
@@ -340,16 +351,24 @@ void Radiation_solver_longwave::solve_gpu(
                             co.in2(lwp), co.in2(iwp), co.in2(rel), co.in2(dei), no3a, no3b, no3c, no2, up, dn, net, bup, bdn, bnet);
             co.out(lw_flux_up, up); co.out(lw_flux_dn, dn); co.out(lw_flux_net, net);
             if (switch_output_bnd_fluxes) { co.out(lw_bnd_flux_up, bup); co.out(lw_bnd_flux_dn, bdn); co.out(lw_bnd_flux_net, bnet); }
+            if (jac)
+            {
+                // (the inner solve left its (n_out, n_lev) Jacobian in lw_flux_up_jac)
+                const Array_gpu<Float,2> jac_r = std::move(lw_flux_up_jac);
+                lw_flux_up_jac = Array_gpu<Float,2>();
+                lw_flux_up_jac.set_dims({n_col, n_lev});
+                co.out(lw_flux_up_jac, jac_r);
+            }
             return;
         }
     }
 
     auto prepare = [&](std::shared_ptr<Workspace>& ws, const int n)
     {
-        if (!ws || ws->n_col != n || ws->n_lay != n_lay || ws->broadband != broadband || ws->byband != byband)
+        if (!ws || ws->n_col != n || ws->n_lay != n_lay || ws->broadband != broadband || ws->byband != byband || ws->jacobian != jac)
         {
             ws = std::make_shared<Workspace>();
-            ws->n_col = n; ws->n_lay = n_lay; ws->broadband = broadband; ws->byband = byband;
+            ws->n_col = n; ws->n_lay = n_lay; ws->broadband = broadband; ws->byband = byband; ws->jacobian = jac;
             ws->optical_props = std::make_unique<Optical_props_1scl_gpu>(n, n_lay, *kdist_gpu);
             ws->sources = std::make_unique<Source_func_lw_gpu>(n, n_lay, *kdist_gpu);
             // broadband and by-band solvers: Planck fractions instead of the two source arrays (they are materialised on demand,
@@ -358,6 +377,11 @@ void Radiation_solver_longwave::solve_gpu(
             const int ng = broadband ? 1 : (byband ? n_bnd : n_gpt);
             ws->gpt_flux_up.set_dims({n, n_lev, ng});
             ws->gpt_flux_dn.set_dims({n, n_lev, ng});
+            if (jac)
+            {
+                ws->gpt_flux_up_jac.set_dims({n, n_lev, ng});
+                if (!broadband) ws->flux_up_jac.set_dims({n, n_lev});
+            }
         }
         if (switch_cloud_optics && !ws->cloud_optical_props)
             ws->cloud_optical_props = std::make_unique<Optical_props_1scl_gpu>(n, n_lay, *cloud_optics_gpu);
@@ -419,7 +443,13 @@ void Radiation_solver_longwave::solve_gpu(
             if (lw_flux_dn.size() == 0) lw_flux_dn.set_dims({n_col, n_lev});
             if (lw_flux_net.size() == 0) lw_flux_net.set_dims({n_col, n_lev});
             Array_gpu<Float,3> up3(lw_flux_up.ptr(), {n_col, n_lev, 1}), dn3(lw_flux_dn.ptr(), {n_col, n_lev, 1});
-            rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), up3, dn3, n_ang);
+            if (jac)
+            {
+                Array_gpu<Float,3> jac3(lw_flux_up_jac.ptr(), {n_col, n_lev, 1});
+                rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), up3, dn3, jac3, n_ang);
+            }
+            else
+                rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), up3, dn3, n_ang);
             Fluxes_kernels_cuda::net_broadband_precalc(n_col, n_lev, lw_flux_dn.ptr(), lw_flux_up.ptr(), lw_flux_net.ptr());
             continue;
         }
@@ -457,7 +487,20 @@ void Radiation_solver_longwave::solve_gpu(
             }
             continue;
         }
-        rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), ws.gpt_flux_up, ws.gpt_flux_dn, n_ang);
+        if (jac)
+        {
+            rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), ws.gpt_flux_up, ws.gpt_flux_dn,
+                          ws.gpt_flux_up_jac, n_ang);
+            const Float* jac_blk = ws.gpt_flux_up_jac.ptr();
+            if (!broadband)
+            {
+                RRX_CALL(rrx_sum_broadband, n_in, n_lev, n_gpt, ws.gpt_flux_up_jac.ptr(), ws.flux_up_jac.ptr());
+                jac_blk = ws.flux_up_jac.ptr();
+            }
+            Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_in, col_s, lw_flux_up_jac.ptr(), jac_blk);
+        }
+        else
+            rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), ws.gpt_flux_up, ws.gpt_flux_dn, n_ang);
 
         Fluxes_broadband_gpu fluxes(n_in, n_lev);
         fluxes.reduce(ws.gpt_flux_up, ws.gpt_flux_dn, ws.optical_props, top_at_1);

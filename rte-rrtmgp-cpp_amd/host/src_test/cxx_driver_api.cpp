@@ -83,6 +83,22 @@ int rrx_cxx_sunlit_columns(void* h, const int sunlit)
     return guarded([&] { static_cast<Driver*>(h)->sw->set_sunlit_columns(sunlit != 0); });
 }
 
+int rrx_cxx_lw_jacobian(void* h, const int on)
+{
+    return guarded([&] { static_cast<Driver*>(h)->lw->set_jacobian(on != 0); });
+}
+
+// the (ncol, nlay+1) surface-temperature Jacobian of the LW upward flux of the last solve, copied to `out` on `stream`
+int rrx_cxx_lw_flux_up_jac(void* h, Float* out, void* stream)
+{
+    return guarded([&]
+    {
+        const Array_gpu<Float,2>& j = static_cast<Driver*>(h)->lw->get_lw_flux_up_jac();
+        if (j.size() == 0) throw std::runtime_error("rrx_cxx_lw_flux_up_jac: no Jacobian (rrx_cxx_lw_jacobian, then a solve)");
+        rrx_host::check(rrx_memcpy_d2d(out, j.ptr(), (unsigned long long)j.size()*sizeof(Float), stream));
+    });
+}
+
 // One LW + SW solve (fluxes only) on `stream`. Arrays: (ncol,nlay) / (ncol,nlay+1) fields, (ncol) vectors, surface properties (nbnd,ncol);
 // lwp, iwp, rel, dei may be NULL without clouds. out7: seven device arrays (ncol, nlay+1) for LW up, dn, net and SW up, dn, dn_dir, net,
 // or NULL: the driver keeps them (rrx_cxx_driver_fluxes).

@@ -344,6 +344,7 @@ void solve_radiation(int argc, char** argv)
         {"byband-solvers",    { false, "With --output-bnd-fluxes: band sums from the fused solvers (no per-g-point fluxes)." }},
         {"heating-rates"    , { false, "Output layer heating rates lw_heating_rate / sw_heating_rate (K/s)." }},
         {"sunlit-columns"   , { false, "Shortwave on the columns with mu0 > 0 only; every SW output of the others is zero (set_sunlit_columns)." }},
+        {"lw-jacobian"      , { false, "Write lw_flux_up_jac, d lw_flux_up / d t_sfc [W m-2 K-1] from the same LW solve (set_jacobian)." }},
         {"async"            , { false, "Host-model mode: vertical ordering read once, solves enqueued without synchronising." }},
         {"sort-columns"     , { true,  "Solve the columns in order of surface pressure where neighbours differ much (outputs keep the input order)." }},
         {"device-sort-columns", { false, "Leave the ordering to the solvers: sorted and padded on the device inside solve_gpu (Radiation_solver::set_column_sorting(1)) instead of on the host before the upload." }}};
@@ -364,6 +365,7 @@ void solve_radiation(int argc, char** argv)
     const bool switch_broadband         = command_line_options.at("broadband-solvers").first;
     const bool switch_byband_solvers    = command_line_options.at("byband-solvers").first;
     const bool switch_sunlit_columns    = command_line_options.at("sunlit-columns").first;
+    const bool switch_lw_jacobian       = command_line_options.at("lw-jacobian").first;
     const bool switch_heating_rates     = command_line_options.at("heating-rates"    ).first;
     const bool switch_async             = command_line_options.at("async"            ).first;
     const bool switch_device_sort       = command_line_options.at("device-sort-columns").first;
@@ -484,6 +486,7 @@ void solve_radiation(int argc, char** argv)
         rad_lw.set_column_block(col_block);
         rad_lw.set_broadband_solvers(switch_broadband);
         rad_lw.set_byband_solvers(switch_byband_solvers);
+        rad_lw.set_jacobian(switch_lw_jacobian);
         // (--no-sort-columns: the file's order and column count exactly; otherwise the solver pads to a multiple of 16 columns and,
         //  with --device-sort-columns, orders them itself)
         rad_lw.set_column_sorting(switch_device_sort ? 1 : (switch_sort_columns ? -1 : 0));
@@ -538,6 +541,9 @@ void solve_radiation(int argc, char** argv)
             output_nc.add_variable<Float>("lw_flux_up" , {"lev", "y", "x"}).insert(input_order(Array<Float,2>(ranks.gather(lw_flux_up, n_col_glob)), perm).v(), {0, 0, 0});
             output_nc.add_variable<Float>("lw_flux_dn" , {"lev", "y", "x"}).insert(input_order(Array<Float,2>(ranks.gather(lw_flux_dn, n_col_glob)), perm).v(), {0, 0, 0});
             output_nc.add_variable<Float>("lw_flux_net", {"lev", "y", "x"}).insert(input_order(Array<Float,2>(ranks.gather(lw_flux_net, n_col_glob)), perm).v(), {0, 0, 0});
+            if (switch_lw_jacobian)
+                output_nc.add_variable<Float>("lw_flux_up_jac", {"lev", "y", "x"}).insert(
+                        input_order(Array<Float,2>(ranks.gather(rad_lw.get_lw_flux_up_jac(), n_col_glob)), perm).v(), {0, 0, 0});
             if (switch_heating_rates)
             {
                 Array_gpu<Float,2> hr;

@@ -193,12 +193,17 @@ class ResidentSolver:
     STAGES = ("lw_gas_optics", "lw_planck", "lw_solver", "lw_reduce", "sw_gas_optics", "sw_solver", "sw_reduce")
 
     def __init__(self, be, kd_lw, kd_sw, atm, do_broadband=False, overlap=False, cloud_luts=None, sort_columns=None, byband=False,
-                 sunlit=False):
+                 sunlit=False, jacobian=False):
         import torch
         self.torch = torch
         # byband: the step also fills self.bnd_fluxes (lw_up/lw_dn/lw_net/sw_up/sw_dn/sw_dir/sw_net, (nbnd, nlev, ncol) each, the
         # caller's column order) from the fused solvers' by-band form; the seven broadband arrays come from the same solves
         self.byband = bool(byband)
+        # jacobian: the step also fills self.lw_flux_up_jac (nlev, ncol, the caller's column order), the surface-temperature Jacobian
+        # of the LW upward flux [W m-2 K-1] from the same fused solve; the seven broadband arrays stay bit for bit those without it
+        self.jacobian = bool(jacobian)
+        if self.jacobian and self.byband:
+            raise ValueError("ResidentSolver: jacobian=True with byband=True is not supported (no by-band Jacobians)")
         # Column sorting. The windowed gas optics stages ONE box of LUT nodes per 256 neighbouring cells; columns
         # that differ much in pressure (RFMIP-like sites, --col-spread) do not fit one box and fall back to the gather kernels
         # (+40 % per step at +-35 % pressure spread). Columns are independent, so the step may process them in any order: sorted by
@@ -245,6 +250,8 @@ class ResidentSolver:
         self.lite = self.direct and do_broadband and bool(int(os.environ.get("RRX_LITE", "1")))
         if self.byband and not self.lite:
             raise ValueError("ResidentSolver(byband=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
+        if self.jacobian and not self.lite:
+            raise ValueError("ResidentSolver(jacobian=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
         ncol, nlay = atm.ncol + self.npad, atm.nlay              # columns of a step (padded)
         ng_l, ng_s = kd_lw.ngpt, kd_sw.ngpt
         e = be.empty
@@ -262,6 +269,8 @@ class ResidentSolver:
         # packed broadband outputs: LW up/dn/net + SW up/dn/dir/net  (7, nlev, ncol) -> one all-gather
         self.fluxes = e((7, nlay+1, atm.ncol))
         self.fluxes_sorted = e((7, nlay+1, ncol)) if self.perm is not None else None
+        self.lw_flux_up_jac = e((nlay+1, atm.ncol)) if self.jacobian else None
+        self.jac_sorted = e((nlay+1, ncol)) if (self.jacobian and self.perm is not None) else None
         # packed band outputs: LW up/dn/net (3, nbnd_lw, nlev, ncol), SW up/dn/dir/net (4, nbnd_sw, nlev, ncol)
         self.bnd_lw = self.bnd_sw = self.bnd_lw_sorted = self.bnd_sw_sorted = None
         self.bnd_fluxes = None
@@ -409,6 +418,7 @@ class ResidentSolver:
 
         ncol, nlay = atm.ncol, atm.nlay
         F = self.fluxes if perm is None else self.fluxes_sorted
+        J = self.lw_flux_up_jac if perm is None else self.jac_sorted
         BL = self.bnd_lw if perm is None else self.bnd_lw_sorted
         BS = self.bnd_sw if perm is None else self.bnd_sw_sorted
         main = self.torch.cuda.current_stream(be.device)
@@ -485,6 +495,9 @@ class ResidentSolver:
                     be.lw_solver_noscat_fractions_byband(atm.top_at_1, kd, self.secants, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
                                                          out=dict(bnd_flux_up=BL[0], bnd_flux_dn=BL[1], bnd_flux_net=BL[2],
                                                                   flux_up=F[0], flux_dn=F[1]))
+                elif self.jacobian:
+                    be.lw_solver_noscat_fractions_jac(atm.top_at_1, kd, self.secants, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
+                                                      flux_up=F[0], flux_dn=F[1], flux_up_jac=J)
                 elif self.lite:
                     be.lw_solver_noscat_fractions(atm.top_at_1, kd, self.secants, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
                                                   flux_up=F[0], flux_dn=F[1])
@@ -549,6 +562,8 @@ class ResidentSolver:
             nf = 3 if sw_day else 7                       # (a sunlit-only SW chain has written the caller's order already)
             self.fluxes[:nf].index_copy_(2, perm[:n], F[:nf, :, :n])
             F = self.fluxes
+            if self.jacobian:
+                self.lw_flux_up_jac.index_copy_(1, perm[:n], J[:, :n])
             if self.byband:
                 self.bnd_lw.index_copy_(3, perm[:n], BL[..., :n])
                 if not sw_day:
