@@ -67,11 +67,14 @@ unsigned long long rrx_workspace_bytes(void* stream);
    broadcast. sub_dims/strides/starts/spread are HOST arrays of length ndim (<= 7); strides in elements, starts 0-based. */
 int rrx_subset_nd(void* out, const void* in, int elem_bytes, int ndim, const int* sub_dims, const long long* strides,
                   const int* starts, const int* spread, void* stream);
-/* kernel-variant switches used by bench.py A/B runs (0 = default) */
+/* kernel-variant switches used by bench.py A/B runs (0 = default), per calling thread. LW: 0 default, 1 serial kernel (the test
+   reference; the path of columns too tall for the others), 4 general kernel with 64-B rows, 7 never the one-kernel broadband form
+   (per-g-point fluxes in a workspace + sum), 15 fp32: the one-column-per-lane one-kernel broadband form ahead of the others. Any
+   other value returns non-zero, leaves the setting as it was, and rrx_last_error() lists the accepted values. */
 int rrx_set_lw_variant(int v);
 int rrx_set_sw_variant(int v);
-/* column groups (8 or 16 columns x all levels) below which do_broadband falls back from the fused one-kernel form to
-   per-g-point fluxes in a workspace + sum (default 512: measured break-even at C4 shapes is 256-512; 1 = always fused) */
+/* workgroups the one-kernel broadband solvers aim for: with fewer column groups they split their g-point loop (see
+   rrx_set_broadband_gsplit; default 512; 1 = never split) */
 int rrx_set_broadband_min_groups(int n);
 /* g-point ranges per column group in the one-kernel broadband solvers: 0 (default) = as many (a power of two, at most 16) as it
    takes to reach the workgroup count above when columns are few, 1 = never split, n = n ranges. Partial sums are added in

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include <stdexcept>
+#include <type_traits>
 
 typedef signed char Bool;   // RTE_USE_CBOOL in every shipped reference config (config/ubuntu_22lts.cmake:35)
 
@@ -18,9 +19,9 @@ namespace rrx
     //      entry points change the CALLING thread's copy only; a thread that never calls them runs the defaults.
     struct Tuning
     {
-        int lw_variant = 0;        // rrx_set_lw_variant: kernel tiling for A/B runs (0 = default)
+        int lw_variant = 0;        // rrx_set_lw_variant: kernel tiling for A/B runs (0 = default; 1, 4, 7, 15)
         int sw_variant = 0;        // rrx_set_sw_variant
-        int bb_min_groups = 512;   // rrx_set_broadband_min_groups: column groups needed for the one-pass broadband form
+        int bb_min_groups = 512;   // rrx_set_broadband_min_groups: workgroups the one-kernel broadband forms aim for
         int bb_gsplit = 0;         // rrx_set_broadband_gsplit: g-point ranges per column group in that form (0 = as many as it
                                    // takes to reach bb_min_groups workgroups, 1 = never split)
         int sync_waves = 1;        // partner waves issue their load bursts together (env RRX_SYNC, default on)
@@ -240,6 +241,9 @@ namespace rrx
 
     inline int ceil_div(const long long a, const long long b) { return int((a + b - 1) / b); }
 
+    // run f with a compile-time copy of a run-time flag
+    template<typename Fn> void with_flag(const bool flag, Fn&& f) { if (flag) f(std::true_type{}); else f(std::false_type{}); }
+
     // The device's default memory pool keeps what is freed into it (its release threshold is lifted once per thread and device), so
     // that the stream-ordered scratch of one solve is reused by the next without going back to the driver. Without it the pool
     // hands everything back at each synchronisation: invisible for the few KB the fused kernels ask for, 250 ms per call for the
@@ -337,6 +341,34 @@ namespace rrx
             if (cost < best_cost) { best_cost = cost; best = n; }
         }
         return best;
+    }
+
+    // ---- g-point sums of the solvers' do_broadband outputs
+
+    // level array (ncl_lev) = sum over g-points of a (ncl_lev, ngpt) array: do_broadband outside the one-kernel forms
+    template<typename F>
+    __global__ void sum_gpt_kernel(const size_t ncl_lev, const int ngpt, const F* __restrict__ in, F* __restrict__ out)
+    {
+        const size_t i = size_t(blockIdx.x)*blockDim.x + threadIdx.x;
+        if (i >= ncl_lev) return;
+        F s = F(0.);
+        for (int ig=0; ig<ngpt; ++ig) s += in[i + size_t(ig)*ncl_lev];
+        out[i] = s;
+    }
+
+    // the partial sums of the g-point ranges of a fused broadband launch, all flux arrays in one launch (blockIdx.y = array; the
+    // partials of array a start at in + a*nsplit*ncl_lev): range order, as sum_gpt_kernel
+    template<typename F, int NARR>
+    __global__ void sum_ranges_kernel(const size_t ncl_lev, const int nsplit, const F* __restrict__ in, F* const o0, F* const o1, F* const o2)
+    {
+        const size_t i = size_t(blockIdx.x)*blockDim.x + threadIdx.x;
+        if (i >= ncl_lev) return;
+        const int a = blockIdx.y;
+        const F* __restrict__ p = in + size_t(a)*nsplit*ncl_lev;
+        F s = F(0.);
+        for (int ig=0; ig<nsplit; ++ig) s += p[i + size_t(ig)*ncl_lev];
+        F* __restrict__ out = (a == 0) ? o0 : ((a == 1 || NARR < 3) ? o1 : o2);
+        out[i] = s;
     }
 
     // ---- by-band outputs of the broadband solvers (rrx_*_byband entries). Band limits: band_lims(2, nbnd), 1-based, inclusive, as

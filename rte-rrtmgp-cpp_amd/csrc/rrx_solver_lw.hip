@@ -21,23 +21,13 @@ namespace
 {
 using namespace rrx;
 
-#ifndef RRX_LW_DEFAULT_VARIANT
-#define RRX_LW_DEFAULT_VARIANT 5
-#endif
 constexpr int CL = 8;    // column lanes
 constexpr int LL = 8;    // level lanes
 
-// W = waves per column group: 1 = the whole column in one wavefront (8 level-lanes x K layers); 2 = the levels of the
-// same 8*V columns spread over 16 level-lanes in two adjacent wavefronts (half the per-lane state, twice the resident
-// waves); the two vertical scans then exchange each wave's total through LDS, one block barrier per scan.
-// BB (broadband): the workgroup walks over ALL g-points of its columns and keeps the g-point sum of both fluxes in
-// registers (same summation order as sum_broadband over stored per-g-point fluxes, so the same bits); flux_up/flux_dn
-// are then (ncol, nlev) arrays. Saves the per-g-point flux stores and the reduction pass that reads them back.
-// CLT = column lanes per wavefront (level lanes = 64 / CLT): 8 x 8 is the default geometry; 16 x 4 with W = 4 keeps K = 9
-// layers per lane at 140 layers (the register budget of the two-wave form) and doubles the row segment of a wavefront
-// (128 B in fp64 with V = 1).
-template<typename F, int V, int K, int W, bool JAC, bool ACC, bool BB = false, int CLT = 8>
-__global__ void __launch_bounds__(256, (W >= 2) ? 2 : 1)
+// The levels of the same 8*V columns are spread over 16 level-lanes in two adjacent wavefronts (W = 2 waves per column group, two
+// column groups per workgroup); the two vertical scans exchange each wave's total through LDS, one block barrier per scan.
+template<typename F, int V, int K, bool JAC, bool ACC>
+__global__ void __launch_bounds__(256, 2)
 lw_noscat_scan_kernel(
         const int ncol, const int nlay, const int ngpt, const int top_at_1, const int imu,
         const F* __restrict__ secants, const F* __restrict__ weights,
@@ -46,18 +36,14 @@ lw_noscat_scan_kernel(
         F* __restrict__ flux_up, F* __restrict__ flux_dn,
         const F* __restrict__ sfc_src_jac, F* __restrict__ flux_up_jac, const int sync_waves)
 {
+    constexpr int W = 2;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    constexpr int CL = CLT, LL = 64 / CLT;           // shadow the default geometry
     const int cl = lane & (CL-1);
     const int ll = lane / CL;
     const int h = wave % W;                          // which part of the column this wave holds (0 = TOA side)
     const int wave_col0 = (blockIdx.x*(4/W) + wave/W) * (CL*V);
-    __shared__ F xch[(W >= 2) ? 4*V : 1][4][CL];     // wave totals of the two scans
-    // The two waves that share each 128-B line (8 columns x 8 B = 64 B per wave when V = 1) must issue their load
-    // bursts together, or the second half of every line is fetched from HBM again once L2 has turned over
-    // (measured: +26 % FETCH_SIZE without the barrier). No thread leaves before the barrier.
-    if constexpr (W == 1) { if (wave_col0 >= ncol) return; }   // wave-uniform; W == 2 keeps every wave for the barriers
+    __shared__ F xch[4*V][4][CL];                    // wave totals of the two scans
 
     int icol = wave_col0 + cl*V;
     const bool active = icol < ncol;                  // all V columns exist (ncol % V == 0) or none
@@ -68,19 +54,13 @@ lw_noscat_scan_kernel(
     const size_t ncl = size_t(ncol);
     const int t0 = (h*LL + ll)*K;
 
-    F acc_up[BB ? K : 1][V], acc_dn[BB ? K : 1][V];
-    if constexpr (BB)
+    // one g-point per workgroup row (grid.y = ngpt), written as a loop over that range: the form whose instruction stream was measured
+    const int g_end = blockIdx.y + 1;
+    for (int igpt=blockIdx.y; igpt<g_end; ++igpt)
     {
-        #pragma unroll
-        for (int j=0; j<K; ++j)
-            #pragma unroll
-            for (int v=0; v<V; ++v) { acc_up[j][v] = F(0.); acc_dn[j][v] = F(0.); }
-    }
-
-    const int g_begin = BB ? 0 : blockIdx.y;
-    const int g_end = BB ? ngpt : blockIdx.y + 1;
-    for (int igpt=g_begin; igpt<g_end; ++igpt)
-    {
+    // The two waves that share each 128-B line (8 columns x 8 B = 64 B per wave when V = 1) must issue their load
+    // bursts together, or the second half of every line is fetched from HBM again once L2 has turned over
+    // (measured: +26 % FETCH_SIZE without the barrier). No thread leaves before the barrier.
     if (sync_waves) __syncthreads();
     const size_t lay_base = size_t(igpt)*ncl*nlay + icol;
     const size_t lev_base = size_t(igpt)*ncl*nlev + icol;
@@ -105,18 +85,15 @@ lw_noscat_scan_kernel(
         lv[j] = load_cols<F,V>(lev_source + lev_base + size_t(ml)*ncl);
     }
 
-    // level below the lane's last layer: first level of the next level-lane; across the wave seam (W == 2) it is loaded
+    // level below the lane's last layer: first level of the next level-lane; across the wave seam it is loaded
     Vec<F,V> lv_next;
     #pragma unroll
     for (int v=0; v<V; ++v) lv_next.v[v] = shfl(lv[0].v[v], lane + CL);
-    if constexpr (W >= 2)
+    if (ll == LL-1)
     {
-        if (ll == LL-1)
-        {
-            const int t = min(t0 + K, nlay);
-            const int ml = top_at_1 ? t : nlay - t;
-            lv_next = load_cols<F,V>(lev_source + lev_base + size_t(ml)*ncl);
-        }
+        const int t = min(t0 + K, nlay);
+        const int ml = top_at_1 ? t : nlay - t;
+        lv_next = load_cols<F,V>(lev_source + lev_base + size_t(ml)*ncl);
     }
 
     F A[V], Bdn[V], Bup[V];
@@ -185,24 +162,20 @@ lw_noscat_scan_kernel(
             if (ll >= d) { b = a*b2 + b; a = a*a2; }
         }
         F xa = F(1.), xb = F(0.);                               // composite of the levels above this wave's
-        F fa = shfl(a, (LL-1)*CL + cl), fb = shfl(b, (LL-1)*CL + cl);   // composite of the whole column
-        if constexpr (W >= 2)
+        // every wave publishes the composite of its part; (xa, xb) = the parts above this wave's, TOA side first;
+        // (fa, fb) = all parts, composed in the same order by every wave (bit-identical dn_sfc in all of them)
+        if (ll == LL-1) { xch[4*v+0][wave][cl] = a; xch[4*v+1][wave][cl] = b; }
+        __syncthreads();
+        const int w0 = wave - h;                         // first wave of this column group
+        F fa = F(1.), fb = F(0.);                        // composite of the whole column
+        #pragma unroll
+        for (int w=0; w<W; ++w)
         {
-            // every wave publishes the composite of its part; (xa, xb) = the parts above this wave's, TOA side first;
-            // (fa, fb) = all parts, composed in the same order by every wave (bit-identical dn_sfc in all of them)
-            if (ll == LL-1) { xch[4*v+0][wave][cl] = a; xch[4*v+1][wave][cl] = b; }
-            __syncthreads();
-            const int w0 = wave - h;                     // first wave of this column group
-            fa = F(1.); fb = F(0.);
-            #pragma unroll
-            for (int w=0; w<W; ++w)
-            {
-                const F oa = xch[4*v+0][w0+w][cl], ob = xch[4*v+1][w0+w][cl];
-                if (w == h) { xa = fa; xb = fb; }
-                fb = oa*fb + ob; fa = oa*fa;
-            }
-            if (h > 0) { b = a*xb + b; a = a*xa; }
+            const F oa = xch[4*v+0][w0+w][cl], ob = xch[4*v+1][w0+w][cl];
+            if (w == h) { xa = fa; xb = fb; }
+            fb = oa*fb + ob; fa = oa*fa;
         }
+        if (h > 0) { b = a*xb + b; a = a*xa; }
         F ae = shfl(a, lane - CL), be = shfl(b, lane - CL);     // exclusive
         if (ll == 0) { ae = xa; be = xb; }
         const F dn_top = (inc_flux != nullptr) ? inc.v[v] / pi : F(0.);
@@ -222,22 +195,18 @@ lw_noscat_scan_kernel(
             if (ll + d < LL) { b = a*b2 + b; a = a*a2; }
         }
         xa = F(1.); xb = F(0.);                                 // composite of the levels below this wave's
-        if constexpr (W >= 2)
+        if (ll == 0) { xch[4*v+2][wave][cl] = a; xch[4*v+3][wave][cl] = b; }
+        __syncthreads();
+        #pragma unroll
+        for (int w=W-1; w>=1; --w)                       // the parts below this wave's, surface side first
         {
-            if (ll == 0) { xch[4*v+2][wave][cl] = a; xch[4*v+3][wave][cl] = b; }
-            __syncthreads();
-            const int w0 = wave - h;
-            #pragma unroll
-            for (int w=W-1; w>=1; --w)                   // the parts below this wave's, surface side first
+            if (w > h)
             {
-                if (w > h)
-                {
-                    const F oa = xch[4*v+2][w0+w][cl], ob = xch[4*v+3][w0+w][cl];
-                    xb = oa*xb + ob; xa = oa*xa;
-                }
+                const F oa = xch[4*v+2][w0+w][cl], ob = xch[4*v+3][w0+w][cl];
+                xb = oa*xb + ob; xa = oa*xa;
             }
-            if (h < W-1) { b = a*xb + b; a = a*xa; }
         }
+        if (h < W-1) { b = a*xb + b; a = a*xa; }
         ae = shfl(a, lane + CL); be = shfl(b, lane + CL);
         if (ll == LL-1) { ae = xa; be = xb; }
         up_in[v] = ae*up_sfc + be;
@@ -274,12 +243,7 @@ lw_noscat_scan_kernel(
             Vec<F,V> o;
             #pragma unroll
             for (int v=0; v<V; ++v) { o.v[v] = scale * dn[v]; dn[v] = tr[j][v]*dn[v] + sdn[j][v]; }
-            if constexpr (BB)
-            {
-                #pragma unroll
-                for (int v=0; v<V; ++v) add_rounded(acc_dn[j][v], o.v[v]);
-            }
-            else put(flux_dn, j, o);
+            put(flux_dn, j, o);
         }
     }
     {
@@ -297,44 +261,20 @@ lw_noscat_scan_kernel(
                 o.v[v] = scale * up[v];
                 if constexpr (JAC) { jc[v] = tr[j][v]*jc[v]; oj.v[v] = scale * jc[v]; }
             }
-            if constexpr (BB)
-            {
-                #pragma unroll
-                for (int v=0; v<V; ++v) add_rounded(acc_up[j][v], o.v[v]);
-            }
-            else put(flux_up, j, o);
+            put(flux_up, j, o);
             if constexpr (JAC) put(flux_up_jac, j, oj);
         }
     }
     }   // g-point loop
-
-    if constexpr (BB)
-    {
-        if (!writer) return;
-        #pragma unroll
-        for (int j=0; j<K; ++j)
-        {
-            const int t = t0 + j;
-            if (t <= nlay)
-            {
-                const int ml = top_at_1 ? t : nlay - t;
-                const size_t o = size_t(icol) + size_t(ml)*ncl;
-                Vec<F,V> u, d;
-                #pragma unroll
-                for (int v=0; v<V; ++v) { u.v[v] = acc_up[j][v]; d.v[v] = acc_dn[j][v]; }
-                store_cols<F,V>(flux_up + o, u);
-                store_cols<F,V>(flux_dn + o, d);
-            }
-        }
-    }
 }
 
 
-
 // ---------------------------------------------------------------------------------------------------------------------
-// Fused broadband form, second generation (round 2). Same tiling and scans as lw_noscat_scan_kernel<..., BB = true>, plus
-//   PRE  : software pipeline over the g-point loop -- the loads of g-point g+1 are requested behind the first scan barrier
-//          of g-point g and land during its scans and replays (tools/labs/lw_lab.hip: 2.78 -> 2.59 ms at C4 fp64);
+// Fused broadband form: the workgroup walks over the g-points of its columns with the tiling and scans of lw_noscat_scan_kernel and
+// keeps the g-point sums of both fluxes on chip (same summation order as sum_broadband over stored per-g-point fluxes, so the same
+// bits); flux_up/flux_dn are then (ncol, nlev) arrays. Saves the per-g-point flux stores and the reduction pass that reads them back.
+// The g-point loop is software-pipelined: the loads of g-point g+1 are requested behind the first scan barrier of g-point g and land
+// during its scans and replays (tools/labs/lw_lab.hip: 2.78 -> 2.59 ms at C4 fp64).
 //   LITE : "Planck-lite" inputs. Instead of lay_source and lev_source the kernel reads the Planck fractions pfrac(col,lay,gpt)
 //          and the band-integrated Planck functions B_lay(col,lay,bnd), B_lev(col,lev,bnd), and rebuilds
 //          lay_source = pfrac*B_lay, lev_source = sqrt(pfrac*pfrac')*B_lev (first and last level: pfrac*B_lev) itself,
@@ -376,7 +316,7 @@ __device__ unsigned long long g_lw_clk[16][8];
 // below the lane, times emis*sfc_src_jac, is the lane's incoming Jacobian (the general kernel's jac_in); the replay is jc = trans*jc and
 // the g-point sums go to flux_up_jac in order with add_rounded, like the fluxes. The sums sit in registers (K more per column) whatever
 // LACC says: the LDS of the four-wave fp64 form has no room for a third column at two workgroups per CU.
-template<typename F, int V, int K, int W, int CLT, bool LITE, bool PRE, bool GS = false, int EV = RRX_LW_EV, int NW = (W > 4 ? W : 4), bool BND = false,
+template<typename F, int V, int K, int W, int CLT, bool LITE, bool GS = false, int EV = RRX_LW_EV, int NW = (W > 4 ? W : 4), bool BND = false,
          bool JAC = false>
 __global__ void __launch_bounds__(64*NW, (NW > W) ? RRX_LW_F32_WAVES : (NW > 4 ? 1 : 2))
 lw_noscat_bb_kernel(
@@ -478,7 +418,7 @@ lw_noscat_bb_kernel(
 
     Loads nxt;
     Vec<F,V> jnxt, jcur;                                        // sfc_src_jac of the next / current g-point (JAC only)
-    if constexpr (PRE) { if (!BND || g_lo < g_hi) issue(g_lo, nxt, jnxt); }     // (an empty band prefetches nothing: g_lo may be ngpt)
+    if (!BND || g_lo < g_hi) issue(g_lo, nxt, jnxt);        // (an empty band prefetches nothing: g_lo may be ngpt)
     int cur_bnd = -1;
     const F wgt = weights[0];
     const F scale = pi * wgt;
@@ -489,9 +429,8 @@ lw_noscat_bb_kernel(
     for (int igpt=g_lo; igpt<g_hi; ++igpt)
     {
     RRX_LW_T(7)
-    if constexpr (!PRE) __syncthreads();        // partner waves issue their load bursts together
-    Loads cur;
-    if constexpr (PRE) { cur = nxt; if constexpr (JAC) jcur = jnxt; } else issue(igpt, cur, jcur);
+    Loads cur = nxt;
+    if constexpr (JAC) jcur = jnxt;
 
     if constexpr (LITE)
     {
@@ -585,15 +524,12 @@ lw_noscat_bb_kernel(
         RRX_LW_T(1)
         __syncthreads();
         RRX_LW_T(6)
-        if constexpr (PRE)
+        if (v == 0)
         {
-            if (v == 0)
-            {
-                // every wave of the workgroup is here: the waves that share 128-B lines ask for them together
-                __builtin_amdgcn_sched_barrier(0);
-                issue(min(igpt + 1, g_hi - 1), nxt, jnxt);      // (last iteration: a harmless re-read)
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            // every wave of the workgroup is here: the waves that share 128-B lines ask for them together
+            __builtin_amdgcn_sched_barrier(0);
+            issue(min(igpt + 1, g_hi - 1), nxt, jnxt);      // (last iteration: a harmless re-read)
+            __builtin_amdgcn_sched_barrier(0);
         }
         F fa = F(1.), fb = F(0.);
         #pragma unroll
@@ -783,57 +719,15 @@ __global__ void lw_secants_array_kernel(
 }
 
 
-// level array (ncol,nlay+1) += / = sum over g-points of a (ncol,nlay+1,ngpt) array; used for do_broadband
-template<typename F>
-__global__ void sum_gpt_kernel(const size_t ncl_lev, const int ngpt, const F* __restrict__ in, F* __restrict__ out)
+// f(std::integral_constant<int, K>{}) for the first K of the list with need <= K; false when the list ends first
+template<int... Ks, typename Fn> bool with_k(const int need, Fn&& f)
 {
-    const size_t i = size_t(blockIdx.x)*blockDim.x + threadIdx.x;
-    if (i >= ncl_lev) return;
-    F s = F(0.);
-    for (int ig=0; ig<ngpt; ++ig) s += in[i + size_t(ig)*ncl_lev];
-    out[i] = s;
+    return ((need <= Ks && (f(std::integral_constant<int,Ks>{}), true)) || ...);
 }
 
-// the partial sums of the g-point ranges of a fused broadband launch, all flux arrays in one launch (blockIdx.y = array; the
-// partials of array a start at in + a*nsplit*ncl_lev): range order, as sum_gpt_kernel
-template<typename F, int NARR>
-__global__ void sum_ranges_kernel(const size_t ncl_lev, const int nsplit, const F* __restrict__ in, F* const o0, F* const o1, F* const o2)
-{
-    const size_t i = size_t(blockIdx.x)*blockDim.x + threadIdx.x;
-    if (i >= ncl_lev) return;
-    const int a = blockIdx.y;
-    const F* __restrict__ p = in + size_t(a)*nsplit*ncl_lev;
-    F s = F(0.);
-    for (int ig=0; ig<nsplit; ++ig) s += p[i + size_t(ig)*ncl_lev];
-    F* __restrict__ out = (a == 0) ? o0 : ((a == 1 || NARR < 3) ? o1 : o2);
-    out[i] = s;
-}
-
-
-template<typename F, int V, int K, int W>
-void launch_scan_k(
-        hipStream_t st, const dim3 grid, const bool jac, const bool acc,
-        const int ncol, const int nlay, const int ngpt, const int top_at_1, const int imu,
-        const F* secants, const F* weights, const F* tau, const F* lay_source, const F* lev_source,
-        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn,
-        const F* sfc_src_jac, F* flux_up_jac)
-{
-#define RRX_LW_ARGS ncol, nlay, ngpt, top_at_1, imu, secants, weights, tau, lay_source, lev_source, \
-        sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, sfc_src_jac, flux_up_jac
-#define RRX_LW_KARGS RRX_LW_ARGS, tuning().sync_waves
-    if (jac)
-    {
-        if (acc) lw_noscat_scan_kernel<F,V,K,W,true,true><<<grid, 256, 0, st>>>(RRX_LW_KARGS);
-        else     lw_noscat_scan_kernel<F,V,K,W,true,false><<<grid, 256, 0, st>>>(RRX_LW_KARGS);
-    }
-    else
-    {
-        if (acc) lw_noscat_scan_kernel<F,V,K,W,false,true><<<grid, 256, 0, st>>>(RRX_LW_KARGS);
-        else     lw_noscat_scan_kernel<F,V,K,W,false,false><<<grid, 256, 0, st>>>(RRX_LW_KARGS);
-    }
-}
-
-template<typename F, int V, int W>
+// the general kernel for one quadrature angle; false when the columns are taller than its largest K (the caller takes the serial
+// kernel)
+template<typename F, int V>
 bool launch_scan(
         hipStream_t st, const bool jac, const bool acc,
         const int ncol, const int nlay, const int ngpt, const int top_at_1, const int imu,
@@ -841,127 +735,87 @@ bool launch_scan(
         const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn,
         const F* sfc_src_jac, F* flux_up_jac)
 {
-    const dim3 grid(ceil_div(ncol, (4/W)*CL*V), ngpt);
-    const int need = ceil_div(nlay+1, LL*W);
-#define RRX_LW_K(KK) if (need <= KK) { launch_scan_k<F,V,KK,W>(st, grid, jac, acc, RRX_LW_ARGS); return true; }
-    if constexpr (W == 1)      { RRX_LW_K(4) RRX_LW_K(8) RRX_LW_K(12) RRX_LW_K(18) RRX_LW_K(24) RRX_LW_K(33) }
-    else if constexpr (W == 2) { RRX_LW_K(2) RRX_LW_K(4) RRX_LW_K(6)  RRX_LW_K(9)  RRX_LW_K(12) RRX_LW_K(17) }
-    else                       { RRX_LW_K(2) RRX_LW_K(3) RRX_LW_K(5) }
-#undef RRX_LW_K
-    return false;
-}
-
-// 0 = default, 1 = serial fallback, 2 = one wave/V=1, 3 = one wave/wide rows, 4 = two waves/64-B rows,
-// 5 = two waves/128-B rows, 6 = one wave/64-B rows, 7 = default kernels but never the fused broadband form,
-// 10 = four waves/128-B rows (per-g-point form), 8 / 9 / 12 = fused broadband form with two / four waves of 8 x 8 lanes / four waves of 16 x 4 lanes
-// (default: 12 in fp64, 9 in fp32)
-// fused broadband form: one workgroup walks all g-points of its columns (grid.y = 1)
-template<typename F, int V, int W>
-bool launch_scan_bb(
-        hipStream_t st, const int ncol, const int nlay, const int ngpt, const int top_at_1,
-        const F* secants, const F* weights, const F* tau, const F* lay_source, const F* lev_source,
-        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn)
-{
-    const dim3 grid(ceil_div(ncol, (4/W)*CL*V), 1);
-    const int need = ceil_div(nlay+1, LL*W);
-    const int imu = 0;
-    const F* sfc_src_jac = nullptr; F* flux_up_jac = nullptr;
-#define RRX_LW_K(KK) if (need <= KK) { lw_noscat_scan_kernel<F,V,KK,W,false,false,true><<<grid, 256, 0, st>>>(RRX_LW_KARGS); return true; }
-    if constexpr (W == 1)      { RRX_LW_K(4) RRX_LW_K(8) RRX_LW_K(12) RRX_LW_K(18) }
-    else if constexpr (W == 2) { RRX_LW_K(2) RRX_LW_K(4) RRX_LW_K(6)  RRX_LW_K(9)  RRX_LW_K(12) }
-    else                       { RRX_LW_K(2) RRX_LW_K(3) RRX_LW_K(5) }     // taller columns spill at 128-B rows: W = 2 form
-#undef RRX_LW_K
-    return false;
-}
-
-// fused broadband form in the 16 column-lane x 4 level-lane geometry, four waves per column group
-template<typename F, int V>
-bool launch_scan_bb16(
-        hipStream_t st, const int ncol, const int nlay, const int ngpt, const int top_at_1,
-        const F* secants, const F* weights, const F* tau, const F* lay_source, const F* lev_source,
-        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn)
-{
-    const dim3 grid(ceil_div(ncol, 16*V), 1);
-    const int need = ceil_div(nlay+1, 4*4);
-    const int imu = 0;
-    const F* sfc_src_jac = nullptr; F* flux_up_jac = nullptr;
-#define RRX_LW_K(KK) if (need <= KK) { lw_noscat_scan_kernel<F,V,KK,4,false,false,true,16><<<grid, 256, 0, st>>>(RRX_LW_KARGS); return true; }
-    RRX_LW_K(2) RRX_LW_K(4) RRX_LW_K(6) RRX_LW_K(9) RRX_LW_K(12)
-#undef RRX_LW_K
-    return false;
-}
-
-
-
-// second-generation fused broadband kernel (lw_noscat_bb_kernel); LITE: lay_source = pfrac, lev_source unused
-// JAC: the Jacobian form, in the geometry and g-point split the fluxes alone would take (so they come out bit for bit the same),
-// always with the pipelined loads
-template<typename F, int V, int W, int CLT, bool LITE, int NW = (W > 4 ? W : 4), bool JAC = false>
-bool launch_bb2(
-        hipStream_t st, const bool pre, const int ncol, const int nlay, const int ngpt, const int top_at_1,
-        const F* secants, const F* weights, const F* tau, const F* lay_source, const F* lev_source,
-        const F* blay, const F* blev, const int* gpoint_bands,
-        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn,
-        const int* band_lims = nullptr, const int nbnd = 0 /* by-band form: flux_up/dn are (ncol, nlev, nbnd) band sums */,
-        const F* sfc_src_jac = nullptr, F* flux_up_jac = nullptr /* JAC: (ngpt, ncol) in, (ncol, nlev) out */)
-{
-    if (size_t(ncol)*(nlay+1) >= (size_t(1) << 31)) return false;          // 32-bit element offsets inside a g-point slab
-    const int groups = ceil_div(ncol, (NW/W)*CLT*V);
-    const int need = ceil_div(nlay+1, (64/CLT)*W);
-    if (need > ((CLT == 16 || W == 8) ? 9 : 5)) return false;
-    const size_t nlevcol = size_t(ncol)*(nlay+1);
-    if (!JAC && band_lims != nullptr)
+    const dim3 grid(ceil_div(ncol, 2*CL*V), ngpt);        // two column groups of two waves per workgroup
+    const int sync_waves = tuning().sync_waves;
+    return with_k<2, 4, 6, 9, 12, 17>(ceil_div(nlay+1, 2*LL), [&](auto kk)
     {
-        // one band per workgroup (grid.y = band): no store inside the g-point loop, no partial arrays, no allocation. Always the
-        // pipelined form. Planck-lite inputs only (the by-band entry is rrx_lw_solver_noscat_fractions_byband).
+        with_flag(jac, [&](auto j) { with_flag(acc, [&](auto a)
+        {
+            lw_noscat_scan_kernel<F,V,decltype(kk)::value,decltype(j)::value,decltype(a)::value><<<grid, 256, 0, st>>>(
+                ncol, nlay, ngpt, top_at_1, imu, secants, weights, tau, lay_source, lev_source,
+                sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, sfc_src_jac, flux_up_jac, sync_waves);
+        }); });
+    });
+}
+
+// the arguments of the fused broadband forms, the same for every tiling that lw_fused_broadband tries
+template<typename F>
+struct BbArgs
+{
+    int ncol, nlay, ngpt, top_at_1;
+    const F *secants, *weights, *tau, *lay_source /* or pfrac */, *lev_source, *blay, *blev;
+    const int* gpoint_bands;
+    const F *sfc_emis, *sfc_src, *inc_flux;
+    F *flux_up, *flux_dn;
+    const int* band_lims; int nbnd;             // by-band form: flux_up/dn are (ncol, nlev, nbnd) band sums
+    const F* sfc_src_jac; F* flux_up_jac;       // JAC: (ngpt, ncol) in, (ncol, nlev) out
+};
+
+// one tiling of the fused broadband kernel (lw_noscat_bb_kernel); false when the shape is outside it (the caller tries the next one).
+// LITE: lay_source = pfrac, lev_source unused. JAC: the Jacobian form, in the geometry and g-point split the fluxes alone would take
+// (so they come out bit for bit the same).
+template<typename F, int V, int W, int CLT, bool LITE, int NW, bool JAC>
+bool launch_bb2(hipStream_t st, const BbArgs<F>& a)
+{
+    if (size_t(a.ncol)*(a.nlay+1) >= (size_t(1) << 31)) return false;      // 32-bit element offsets inside a g-point slab
+    const int groups = ceil_div(a.ncol, (NW/W)*CLT*V);
+    const int need = ceil_div(a.nlay+1, (64/CLT)*W);
+    if (need > ((CLT == 16 || W == 8) ? 9 : 5)) return false;
+    auto with_tiling_k = [&](auto launch)      // the layers per lane of this tiling
+    {
+        if constexpr (CLT == 16) return with_k<2, 4, 6, 9>(need, launch);
+        else if constexpr (W == 8) return with_k<5, 7, 9>(need, launch);      // (288 ... 319 / 447 / 575 layers: eight waves of 8 x 8 lanes)
+        else return with_k<2, 3, 5>(need, launch);
+    };
+    const size_t nlevcol = size_t(a.ncol)*(a.nlay+1);
+    if (!JAC && a.band_lims != nullptr)
+    {
+        // one band per workgroup (grid.y = band): no store inside the g-point loop, no partial arrays, no allocation. Planck-lite
+        // inputs only (the by-band entry is rrx_lw_solver_noscat_fractions_byband).
         if constexpr (LITE)
         {
-            const dim3 grid(groups, nbnd);
-#define RRX_LW_BND(KK) if (need <= KK) { \
-            lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,true,false,RRX_LW_EV,NW,true><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, \
-                lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, 0, nlevcol, band_lims); \
-            return true; }
-            if constexpr (CLT == 16) { RRX_LW_BND(2) RRX_LW_BND(4) RRX_LW_BND(6) RRX_LW_BND(9) }
-            else if constexpr (W == 8) { RRX_LW_BND(5) RRX_LW_BND(7) RRX_LW_BND(9) }
-            else                     { RRX_LW_BND(2) RRX_LW_BND(3) RRX_LW_BND(5) }
-#undef RRX_LW_BND
+            const dim3 grid(groups, a.nbnd);
+            return with_tiling_k([&](auto kk)
+            {
+                lw_noscat_bb_kernel<F,V,decltype(kk)::value,W,CLT,LITE,false,RRX_LW_EV,NW,true><<<grid, 64*NW, 0, st>>>(
+                    a.ncol, a.nlay, a.ngpt, a.top_at_1, a.secants, a.weights, a.tau, a.lay_source, a.lev_source, a.blay, a.blev,
+                    a.gpoint_bands, a.sfc_emis, a.sfc_src, a.inc_flux, a.flux_up, a.flux_dn, 0, nlevcol, a.band_lims);
+            });
         }
         return false;
     }
     // few column groups: the g-point loop is split over grid.y, partial sums added in range order afterwards
-    const int gper = ceil_div(ngpt, broadband_gsplit(groups, ngpt, (NW > 4) ? 256 : 512));      // (one or two workgroups per CU)
-    const int nsplit = ceil_div(ngpt, gper);               // no empty range: every workgroup's first g-point exists (it is prefetched)
+    const int gper = ceil_div(a.ngpt, broadband_gsplit(groups, a.ngpt, (NW > 4) ? 256 : 512));      // (one or two workgroups per CU)
+    const int nsplit = ceil_div(a.ngpt, gper);             // no empty range: every workgroup's first g-point exists (it is prefetched)
+    constexpr int NARR = JAC ? 3 : 2;
     StreamScratch scratch(st);
-    F* out_up = flux_up; F* out_dn = flux_dn; F* out_jc = flux_up_jac;
-    if (nsplit > 1) { out_up = scratch.get<F>((JAC ? 3 : 2)*nsplit*nlevcol); out_dn = out_up + nsplit*nlevcol; out_jc = out_dn + nsplit*nlevcol; }
+    F* out_up = a.flux_up; F* out_dn = a.flux_dn; F* out_jc = a.flux_up_jac;
+    if (nsplit > 1)
+    {
+        out_up = scratch.get<F>(NARR*nsplit*nlevcol); out_dn = out_up + nsplit*nlevcol;
+        if (JAC) out_jc = out_dn + nsplit*nlevcol;
+    }
     const dim3 grid(groups, nsplit);
-#define RRX_LW_B2(KK) if (need <= KK) { \
-        if constexpr (JAC) { \
-            if (nsplit > 1) lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,true,true,RRX_LW_EV,NW,false,true><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, \
-                top_at_1, secants, weights, tau, lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, \
-                gper, nlevcol, nullptr, sfc_src_jac, out_jc); \
-            else lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,true,false,RRX_LW_EV,NW,false,true><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, \
-                top_at_1, secants, weights, tau, lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, \
-                gper, nlevcol, nullptr, sfc_src_jac, out_jc); } \
-        else if (nsplit > 1 && pre) lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,true,true,RRX_LW_EV,NW><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, \
-            lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, gper, nlevcol, nullptr); \
-        else if (nsplit > 1) lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,false,true,RRX_LW_EV,NW><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, \
-            lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, gper, nlevcol, nullptr); \
-        else if (pre) lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,true,false,RRX_LW_EV,NW><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, \
-            lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, gper, nlevcol, nullptr); \
-        else lw_noscat_bb_kernel<F,V,KK,W,CLT,LITE,false,false,RRX_LW_EV,NW><<<grid, 64*NW, 0, st>>>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, \
-            lay_source, lev_source, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, out_up, out_dn, gper, nlevcol, nullptr); \
-        break; }
-    do {
-    if constexpr (CLT == 16) { RRX_LW_B2(2) RRX_LW_B2(4) RRX_LW_B2(6) RRX_LW_B2(9) }
-    else if constexpr (W == 8) { RRX_LW_B2(5) RRX_LW_B2(7) RRX_LW_B2(9) }      // (288 ... 319 / 447 / 575 layers: eight waves of 8 x 8 lanes)
-    else                     { RRX_LW_B2(2) RRX_LW_B2(3) RRX_LW_B2(5) }
-    } while (false);
+    with_tiling_k([&](auto kk) { with_flag(nsplit > 1, [&](auto gs)
+    {
+        lw_noscat_bb_kernel<F,V,decltype(kk)::value,W,CLT,LITE,decltype(gs)::value,RRX_LW_EV,NW,false,JAC><<<grid, 64*NW, 0, st>>>(
+            a.ncol, a.nlay, a.ngpt, a.top_at_1, a.secants, a.weights, a.tau, a.lay_source, a.lev_source, a.blay, a.blev,
+            a.gpoint_bands, a.sfc_emis, a.sfc_src, a.inc_flux, out_up, out_dn, gper, nlevcol, nullptr, a.sfc_src_jac, out_jc);
+    }); });
     if (nsplit > 1)      // (out_up, out_dn [, out_jc] lie behind each other in the scratch block)
-        sum_ranges_kernel<F,JAC ? 3 : 2><<<dim3(ceil_div(nlevcol, 256), JAC ? 3 : 2), 256, 0, st>>>(nlevcol, nsplit, out_up, flux_up, flux_dn,
-                                                                                                   JAC ? flux_up_jac : (F*)nullptr);
+        sum_ranges_kernel<F,NARR><<<dim3(ceil_div(nlevcol, 256), NARR), 256, 0, st>>>(nlevcol, nsplit, out_up, a.flux_up, a.flux_dn,
+                                                                                      a.flux_up_jac);
     return true;
-#undef RRX_LW_B2
 }
 
 // broadband fluxes from tau + (lay_source, lev_source) [LITE = false] or tau + Planck fractions and band Planck functions
@@ -976,27 +830,20 @@ bool lw_fused_broadband(
         const int* band_lims = nullptr, const int nbnd = 0 /* by-band form (launch_bb2) */,
         const F* sfc_src_jac = nullptr, F* flux_up_jac = nullptr)
 {
-    const bool pre = tuning().lw_variant != 13;                 // 13: without the pipelined loads (A/B runs)
-    // fp32: 16 x 4 lanes with two columns per lane (128-B rows, K = 9) ahead of 8 x 8 lanes with four (variant 14 = the latter
-    // first, for A/B runs). Measured at C4 in the fractions form: 1.77 against 3.26 ms (the four-column lane state spills).
-    const bool v2_first = tuning().lw_variant != 14;
+    const BbArgs<F> a{ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source, blay, blev, gpoint_bands,
+                      sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac};
     if constexpr (sizeof(F) == 8)
     {
         // (Round 4 measured six waves x six layers per column group -- 384-thread workgroups, three waves per SIMD, 168 VGPRs with
         //  108-124 B of scratch: 4.2-4.7 ms against 2.7 for this form, profiles/r04_fp32_geometry_ab.txt.)
-        if (launch_bb2<F,1,4,16,LITE,4,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac))
-            return true;
+        if (launch_bb2<F,1,4,16,LITE,4,JAC>(st, a)) return true;
         // 144 ... 287 layers: eight wavefronts per column group
-        if (launch_bb2<F,1,8,16,LITE,8,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac))
-            return true;
+        if (launch_bb2<F,1,8,16,LITE,8,JAC>(st, a)) return true;
         // 288 ... 575 layers (round 4: RCEMIP's default is 256 levels, LES grids with a background profile on top exceed 288): the same
         // eight waves with 8 x 8 lanes -- 64 levels per wave at nine layers per lane, 64-B rows (the other half of each 128-B line
         // belongs to the next column group: twice the L2 fetches, on a kernel that stands at a quarter of the HBM roof). Beyond that
         // the one-thread-per-column kernels take over.
-        return launch_bb2<F,1,8,8,LITE,8,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                        blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac);
+        return launch_bb2<F,1,8,8,LITE,8,JAC>(st, a);
     }
     else
     {
@@ -1005,36 +852,25 @@ bool lw_fused_broadband(
         // W = 6 at three, K = 5 / W = 8 at four: 1.82 / 1.88 / 1.95 ms at C4 against 1.31 for two columns per lane with the sums in
         // LDS, profiles/r04_fp32_geometry_ab.txt): the LW chain per g-point is short, so halving the wavefronts per column wins.
         // The one-column form stays for odd column counts (variant 15 forces it for tests).
-        if (tuning().lw_variant == 15 &&
-            launch_bb2<F,1,4,16,LITE,8,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                        blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac))
-            return true;
-        if (ncol % 2 == 0 && v2_first &&
-            launch_bb2<F,2,4,16,LITE,4,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac))
-            return true;
-        if (ncol % 4 == 0 &&
-            launch_bb2<F,4,4,8,LITE,4,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                     blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac))
-            return true;
-        if (ncol % 2 == 0 &&
-            launch_bb2<F,2,4,16,LITE,4,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac))
-            return true;
+        if (tuning().lw_variant == 15 && launch_bb2<F,1,4,16,LITE,8,JAC>(st, a)) return true;
+        // 16 x 4 lanes with two columns per lane (128-B rows, K = 9) ahead of 8 x 8 lanes with four. Measured at C4 in the fractions
+        // form: 1.77 against 3.26 ms (the four-column lane state spills); the latter still takes 144 ... 159 layers.
+        if (ncol % 2 == 0 && launch_bb2<F,2,4,16,LITE,4,JAC>(st, a)) return true;
+        if (ncol % 4 == 0 && launch_bb2<F,4,4,8,LITE,4,JAC>(st, a)) return true;
         // 144 ... 287 layers: eight wavefronts per column group
-        if (ncol % 2 == 0 &&
-            launch_bb2<F,2,8,16,LITE,8,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                      blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac))
-            return true;
+        if (ncol % 2 == 0 && launch_bb2<F,2,8,16,LITE,8,JAC>(st, a)) return true;
         // 288 ... 575 layers: eight waves of 8 x 8 lanes (see fp64)
-        if (ncol % 2 == 0 &&
-            launch_bb2<F,2,8,8,LITE,8,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                     blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac))
-            return true;
+        if (ncol % 2 == 0 && launch_bb2<F,2,8,8,LITE,8,JAC>(st, a)) return true;
         // odd column counts: one column per lane
-        return launch_bb2<F,1,4,16,LITE,8,JAC>(st, pre, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                           blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac);
+        return launch_bb2<F,1,4,16,LITE,8,JAC>(st, a);
     }
+}
+
+// the one-kernel broadband forms serve every variant but 1 (serial kernel) and 7 (per-g-point fluxes in a workspace + sum)
+bool lw_fused_allowed()
+{
+    const int v = tuning().lw_variant;
+    return v != 1 && v != 7;
 }
 
 #define RRX_LW_ARGS_CALL ncol, nlay, ngpt, top_at_1, imu, secants, weights, tau, lay_source, lev_source, \
@@ -1049,93 +885,53 @@ int lw_solver_noscat_impl(
         F* flux_up, F* flux_dn,
         const Bool do_broadband, F* flux_up_loc, F* flux_dn_loc,
         const Bool do_jacobians, const F* sfc_src_jac, F* flux_up_jac,
-        void* stream, F* flux_ws = nullptr /* room for 2*ncol*(nlay+1)*ngpt values out of the CALLER's workspace lease, or null */)
+        void* stream)
 {
     RRX_TRY
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (ncol <= 0 || nlay <= 0 || ngpt <= 0) throw std::runtime_error("empty problem");
     if (nmus < 1 || nmus > 4) throw std::runtime_error("n_quad_angs must be 1..4");
+    if (do_broadband && (flux_up_loc == nullptr || flux_dn_loc == nullptr)) throw std::runtime_error("do_broadband needs flux_*_loc");
     const bool jac = do_jacobians && sfc_src_jac != nullptr && flux_up_jac != nullptr;
-    const int g_lw_variant = tuning().lw_variant;
-    const int g_bb_min_groups = tuning().bb_min_groups;
+    const int variant = tuning().lw_variant;
 
-    // broadband mode, fused form: g-point sums kept in registers, no per-g-point fluxes in memory. With enough column groups
+    // broadband mode, fused form: g-point sums kept on chip, no per-g-point fluxes in memory. With enough column groups
     // to fill the chip one workgroup sums all g-points in order (sum_broadband's order); with fewer the g-point range is split
     // over grid.y and the partial sums are added in range order (rrx::broadband_gsplit).
-    constexpr int VBB = (sizeof(F) == 8) ? 1 : 2;
-    const bool second_gen = (g_lw_variant == 0 || (g_lw_variant >= 13 && g_lw_variant <= 15));        // splits its g-point loop when columns are few
-    if (do_broadband && !jac && nmus == 1 && g_lw_variant != 1 && g_lw_variant != 7 && (ncol % VBB == 0 || (second_gen && sizeof(F) == 4))
-        && (second_gen || ceil_div(ncol, CL*VBB) >= g_bb_min_groups))
-    {
-        if (flux_up_loc == nullptr || flux_dn_loc == nullptr) throw std::runtime_error("do_broadband needs flux_*_loc");
-        // default: the second-generation kernel (pipelined loads); variants 8 / 9 / 12 keep the first-generation tilings
-        if (second_gen &&
-            lw_fused_broadband<F,false>(st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                        (const F*)nullptr, (const F*)nullptr, (const int*)nullptr, sfc_emis, sfc_src, inc_flux,
-                                        flux_up_loc, flux_dn_loc))
-            return 0;
-        // the first-generation tilings do not split the g-point loop: only with enough column groups
-        if (ncol % VBB == 0 && ceil_div(ncol, CL*VBB) >= g_bb_min_groups) {
-        // four waves per column group (K = 5 at 140 layers) leave room for the g-point sums AND 128-B row segments.
-        // Measured at C4: fp32 2.15 ms against 2.28 ms with two waves / 64-B rows; fp64 3.94 against 3.15 ms (256 VGPRs,
-        // 12 % idle level-lanes), so fp64 keeps two waves unless variant 9 asks for four.
-        // fp64 default: 16 x 4 lane geometry over four waves (128-B rows at K = 9: 3.00 -> 2.84 ms at C4; fp32 prefers the
-        // 8 x 8 geometry with four waves and V = 4, 2.16 against 2.28 ms)
-        if ((g_lw_variant == 12 || (g_lw_variant == 0 && sizeof(F) == 8)) && ncol % VBB == 0 &&
-            launch_scan_bb16<F,VBB>(st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                    sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc))
-            return 0;
-        const bool four = (g_lw_variant == 9) || (g_lw_variant != 8 && sizeof(F) == 4);
-        if (four && ncol % (2*VBB) == 0 &&
-            launch_scan_bb<F,2*VBB,4>(st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                      sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc))
-            return 0;
-        if (launch_scan_bb<F,VBB,2>(st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                    sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc))
-            return 0;
-        }
-    }
+    if (do_broadband && !jac && nmus == 1 && lw_fused_allowed() &&
+        lw_fused_broadband<F,false>(st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
+                                    (const F*)nullptr, (const F*)nullptr, (const int*)nullptr, sfc_emis, sfc_src, inc_flux,
+                                    flux_up_loc, flux_dn_loc))
+        return 0;
 
     // broadband mode, general form: per-g-point fluxes go to a workspace, then are summed over g-points
     F* up = flux_up; F* dn = flux_dn;
     WorkspaceLease lease(st);
     const size_t nlevcol = size_t(ncol)*(nlay+1);
-    if (do_broadband)
-    {
-        if (flux_up_loc == nullptr || flux_dn_loc == nullptr) throw std::runtime_error("do_broadband needs flux_*_loc");
-        F* ws = (flux_ws != nullptr) ? flux_ws : lease.get<F>(2*nlevcol*ngpt);
-        up = ws; dn = ws + nlevcol*ngpt;
-    }
+    if (do_broadband) { up = lease.get<F>(2*nlevcol*ngpt); dn = up + nlevcol*ngpt; }
 
     // columns per lane: VDEF*8 lanes*sizeof(F) = 64-B row segments, VMAX = 128-B segments. Measured at C4 (tools/
     // bench_solvers.py): two waves per column group with 128-B rows (2 waves/SIMD) is the fastest form in both
-    // precisions (fp64 5.4 ms vs 6.0 ms for one wave/64-B rows; fp32 2.4 vs 2.9 ms); the others stay for A/B runs.
+    // precisions (fp64 5.4 ms vs 6.0 ms for one wave/64-B rows; fp32 2.4 vs 2.9 ms); variant 4 keeps 64-B rows.
     constexpr int VDEF = (sizeof(F) == 8) ? 1 : 2;
     constexpr int VMAX = 2*VDEF;
     for (int imu=0; imu<nmus; ++imu)
     {
         const bool acc = imu > 0;
         bool done = false;
-        if (g_lw_variant != 1)
+        if (variant != 1)
         {
-            const int var = (g_lw_variant == 0) ? RRX_LW_DEFAULT_VARIANT : g_lw_variant;
-            if (var == 10 && ncol % VMAX == 0)     done = launch_scan<F,VMAX,4>(st, jac, acc, RRX_LW_ARGS_CALL);
-            else if (var == 3 && ncol % VMAX == 0) done = launch_scan<F,VMAX,1>(st, jac, acc, RRX_LW_ARGS_CALL);
-            else if (var == 6 && ncol % VDEF == 0) done = launch_scan<F,VDEF,1>(st, jac, acc, RRX_LW_ARGS_CALL);
-            else if (var == 2)                     done = launch_scan<F,1,1>(st, jac, acc, RRX_LW_ARGS_CALL);
-            else if (var != 4 && ncol % VMAX == 0) done = launch_scan<F,VMAX,2>(st, jac, acc, RRX_LW_ARGS_CALL);
-            else if (ncol % VDEF == 0)             done = launch_scan<F,VDEF,2>(st, jac, acc, RRX_LW_ARGS_CALL);
-            if (!done)                             done = launch_scan<F,1,2>(st, jac, acc, RRX_LW_ARGS_CALL);
+            if (variant != 4 && ncol % VMAX == 0) done = launch_scan<F,VMAX>(st, jac, acc, RRX_LW_ARGS_CALL);
+            else if (ncol % VDEF == 0)            done = launch_scan<F,VDEF>(st, jac, acc, RRX_LW_ARGS_CALL);
+            if (!done)                            done = launch_scan<F,1>(st, jac, acc, RRX_LW_ARGS_CALL);
         }
-        if (!done)
+        if (!done)      // beyond the general kernel's largest K, or variant 1
         {
             const dim3 grid(ceil_div(ncol, 256), ngpt);
-#define RRX_LW_SERIAL(J, A) lw_noscat_serial_kernel<F,J,A><<<grid, 256, 0, st>>>( \
-        ncol, nlay, ngpt, top_at_1, imu, secants, weights, tau, lay_source, lev_source, \
-        sfc_emis, sfc_src, inc_flux, up, dn, sfc_src_jac, flux_up_jac)
-            if (jac) { if (acc) RRX_LW_SERIAL(true, true); else RRX_LW_SERIAL(true, false); }
-            else     { if (acc) RRX_LW_SERIAL(false, true); else RRX_LW_SERIAL(false, false); }
-#undef RRX_LW_SERIAL
+            with_flag(jac, [&](auto j) { with_flag(acc, [&](auto a)
+            {
+                lw_noscat_serial_kernel<F,decltype(j)::value,decltype(a)::value><<<grid, 256, 0, st>>>(RRX_LW_ARGS_CALL);
+            }); });
         }
     }
 
@@ -1147,6 +943,7 @@ int lw_solver_noscat_impl(
     }
     RRX_CATCH("rrx_lw_solver_noscat")
 }
+#undef RRX_LW_ARGS_CALL
 
 template<typename F>
 __global__ void planck_sources_from_fractions_kernel(
@@ -1185,44 +982,57 @@ int planck_sources_from_fractions_impl(int ncol, int nlay, int ngpt, const int* 
     RRX_CATCH("rrx_planck_sources_from_fractions")
 }
 
+// The fractions entries outside the one-kernel tilings (columns taller than 575 layers, variants 1 and 7): the Planck sources are
+// rebuilt and the general entry writes per-g-point fluxes [up | dn], and the Jacobian behind them when sfc_src_jac is given, into ONE
+// lease of the stream's workspace: [up | dn | (Jacobian) | lay_source | lev_source]. Returns that block, or null with the message set;
+// the caller sums it while the lease lives.
+template<typename F>
+const F* lw_fractions_per_gpoint(
+        WorkspaceLease& lease, const int ncol, const int nlay, const int ngpt, const Bool top_at_1,
+        const F* secants, const F* weights, const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands,
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, const F* sfc_src_jac, void* stream)
+{
+    const size_t n_lay = size_t(ncol)*nlay*ngpt, n_lev = size_t(ncol)*(nlay+1)*ngpt;
+    const size_t nout = (sfc_src_jac != nullptr) ? 3 : 2;
+    F* ws = lease.get<F>(nout*n_lev + n_lay + n_lev);
+    F* lay = ws + nout*n_lev; F* lev = lay + n_lay;
+    F* jac = (sfc_src_jac != nullptr) ? ws + 2*n_lev : nullptr;
+    if (planck_sources_from_fractions_impl<F>(ncol, nlay, ngpt, gpoint_bands, pfrac, blay, blev, lay, lev, stream) != 0 ||
+        lw_solver_noscat_impl<F>(ncol, nlay, ngpt, top_at_1, 1, secants, weights, tau, lay, lev, sfc_emis, sfc_src, inc_flux,
+                                 ws, ws + n_lev, Bool(0), (F*)nullptr, (F*)nullptr, Bool(jac != nullptr), sfc_src_jac, jac, stream) != 0)
+        return nullptr;
+    return ws;
+}
+
 template<typename F>
 int lw_solver_noscat_fractions_impl(
         const int ncol, const int nlay, const int ngpt, const Bool top_at_1,
         const F* secants, const F* weights, const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands,
         const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up_loc, F* flux_dn_loc, void* stream)
 {
+    RRX_TRY
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (ncol <= 0 || nlay <= 0 || ngpt <= 0) throw std::runtime_error("empty problem");
+    if (flux_up_loc == nullptr || flux_dn_loc == nullptr) throw std::runtime_error("broadband outputs missing");
+    const bool fused = lw_fused_allowed() &&
+        lw_fused_broadband<F,true>(st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, (const F*)nullptr,
+                                   blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc);
+    if (!fused)
     {
-        RRX_TRY
-        if (ncol <= 0 || nlay <= 0 || ngpt <= 0) throw std::runtime_error("empty problem");
-        if (flux_up_loc == nullptr || flux_dn_loc == nullptr) throw std::runtime_error("broadband outputs missing");
-        const int var = tuning().lw_variant;
-        if ((var == 0 || (var >= 13 && var <= 15)) &&
-            lw_fused_broadband<F,true>(st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, (const F*)nullptr,
-                                       blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc))
-            return check_launch("rrx_lw_solver_noscat_fractions");
-        } catch (const std::exception& e) { rrx::set_error(std::string("rrx_lw_solver_noscat_fractions: ") + e.what()); return 1; }
+        WorkspaceLease lease(st);
+        const F* ws = lw_fractions_per_gpoint<F>(lease, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, blay, blev,
+                                                 gpoint_bands, sfc_emis, sfc_src, inc_flux, (const F*)nullptr, stream);
+        if (ws == nullptr) return 1;                                 // (the message is set)
+        const size_t nlevcol = size_t(ncol)*(nlay+1);
+        const int nb = ceil_div(nlevcol, 256);
+        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws, flux_up_loc);
+        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws + nlevcol*ngpt, flux_dn_loc);
     }
-    // outside the one-kernel form (few columns, very tall columns, A/B variants): rebuild the sources and take the general entry.
-    // ONE lease of the stream's workspace, carved here: [per-g-point fluxes of the general entry: 2 n_lev | lay_source | lev_source];
-    // the general entry is handed its part explicitly.
-    const size_t n_lay = size_t(ncol)*nlay*ngpt, n_lev = size_t(ncol)*(nlay+1)*ngpt;
-    WorkspaceLease lease(st);
-    F* flux_ws = nullptr;
-    try { flux_ws = lease.get<F>(2*n_lev + n_lay + n_lev); }
-    catch (const std::exception& e) { rrx::set_error(std::string("rrx_lw_solver_noscat_fractions: ") + e.what()); return 1; }
-    F* lay = flux_ws + 2*n_lev; F* lev = lay + n_lay;
-    int rc = planck_sources_from_fractions_impl<F>(ncol, nlay, ngpt, gpoint_bands, pfrac, blay, blev, lay, lev, stream);
-    if (rc == 0)
-        rc = lw_solver_noscat_impl<F>(ncol, nlay, ngpt, top_at_1, 1, secants, weights, tau, lay, lev, sfc_emis, sfc_src, inc_flux,
-                                      (F*)nullptr, (F*)nullptr, Bool(1), flux_up_loc, flux_dn_loc, Bool(0), (const F*)nullptr, (F*)nullptr, stream,
-                                      flux_ws);
-    return rc;
+    RRX_CATCH("rrx_lw_solver_noscat_fractions")
 }
 
 // fluxes and the surface-temperature Jacobian of the upward flux (rrx_lw_solver_noscat_fractions_jac): the one-kernel form's JAC
-// variant where the tilings reach, otherwise the route of the broadband entry (sources rebuilt, the general kernel with do_jacobians,
-// per-g-point fluxes and Jacobians in one lease of the stream's workspace) followed by the g-point sum of the Jacobian
+// variant where the tilings reach, otherwise the g-point sums of lw_fractions_per_gpoint's fluxes and Jacobian
 template<typename F>
 int lw_solver_noscat_fractions_jac_impl(
         const int ncol, const int nlay, const int ngpt, const Bool top_at_1,
@@ -1236,24 +1046,21 @@ int lw_solver_noscat_fractions_jac_impl(
     if (flux_up_loc == nullptr || flux_dn_loc == nullptr) throw std::runtime_error("broadband outputs missing");
     if (sfc_src_jac == nullptr) throw std::runtime_error("sfc_src_jac is null");
     if (flux_up_jac == nullptr) throw std::runtime_error("flux_up_jac is null");
-    const int var = tuning().lw_variant;
-    const bool fused = (var == 0 || (var >= 13 && var <= 15)) &&
+    const bool fused = lw_fused_allowed() &&
         lw_fused_broadband<F,true,true>(st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, (const F*)nullptr,
                                         blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc,
                                         (const int*)nullptr, 0, sfc_src_jac, flux_up_jac);
     if (!fused)
     {
-        const size_t nlevcol = size_t(ncol)*(nlay+1);
-        const size_t n_lay = size_t(ncol)*nlay*ngpt, n_lev = nlevcol*ngpt;
         WorkspaceLease lease(st);
-        F* flux_ws = lease.get<F>(2*n_lev + n_lay + n_lev + n_lev);  // [per-g-point up | dn | lay_source | lev_source | Jacobian]
-        F* lay = flux_ws + 2*n_lev; F* lev = lay + n_lay; F* jac = lev + n_lev;
-        if (planck_sources_from_fractions_impl<F>(ncol, nlay, ngpt, gpoint_bands, pfrac, blay, blev, lay, lev, stream) != 0 ||
-            lw_solver_noscat_impl<F>(ncol, nlay, ngpt, top_at_1, 1, secants, weights, tau, lay, lev, sfc_emis, sfc_src, inc_flux,
-                                     (F*)nullptr, (F*)nullptr, Bool(1), flux_up_loc, flux_dn_loc, Bool(1), sfc_src_jac, jac, stream,
-                                     flux_ws) != 0)
-            return 1;                                                // (the message is set)
-        sum_gpt_kernel<F><<<ceil_div(nlevcol, 256), 256, 0, st>>>(nlevcol, ngpt, jac, flux_up_jac);
+        const F* ws = lw_fractions_per_gpoint<F>(lease, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, blay, blev,
+                                                 gpoint_bands, sfc_emis, sfc_src, inc_flux, sfc_src_jac, stream);
+        if (ws == nullptr) return 1;                                 // (the message is set)
+        const size_t nlevcol = size_t(ncol)*(nlay+1);
+        const int nb = ceil_div(nlevcol, 256);
+        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws, flux_up_loc);
+        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws + nlevcol*ngpt, flux_dn_loc);
+        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws + 2*nlevcol*ngpt, flux_up_jac);
     }
     RRX_CATCH("rrx_lw_solver_noscat_fractions_jac")
 }
@@ -1288,8 +1095,7 @@ int lw_flux_up_adjust_impl(const int ncol, const int nlev, const F* flux_up_jac,
 }
 
 // by-band fluxes (rrx_lw_solver_noscat_fractions_byband): the one-kernel form with one band per workgroup where the tilings reach,
-// otherwise the route of the broadband entry there (sources rebuilt, per-g-point fluxes in the stream's workspace lease) followed by
-// the band sums. Band net and broadband outputs come from the band sums in one more pass.
+// otherwise the band sums of lw_fractions_per_gpoint's fluxes. Band net and broadband outputs come from the band sums in one more pass.
 template<typename F>
 int lw_solver_noscat_fractions_byband_impl(
         const int ncol, const int nlay, const int ngpt, const int nbnd, const Bool top_at_1,
@@ -1303,22 +1109,16 @@ int lw_solver_noscat_fractions_byband_impl(
     if (gpoint_bands == nullptr) throw std::runtime_error("gpoint_bands is null");
     if (bnd_up == nullptr || bnd_dn == nullptr) throw std::runtime_error("band flux outputs missing");
     const size_t nlevcol = size_t(ncol)*(nlay+1);
-    const int var = tuning().lw_variant;
-    const bool fused = (var == 0 || (var >= 13 && var <= 15)) &&
+    const bool fused = lw_fused_allowed() &&
         lw_fused_broadband<F,true>(st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, (const F*)nullptr,
                                    blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, bnd_up, bnd_dn, band_lims, nbnd);
     if (!fused)
     {
-        const size_t n_lay = size_t(ncol)*nlay*ngpt, n_lev = nlevcol*ngpt;
         WorkspaceLease lease(st);
-        F* flux_ws = lease.get<F>(2*n_lev + n_lay + n_lev);          // [per-g-point up | dn | lay_source | lev_source]
-        F* lay = flux_ws + 2*n_lev; F* lev = lay + n_lay;
-        if (planck_sources_from_fractions_impl<F>(ncol, nlay, ngpt, gpoint_bands, pfrac, blay, blev, lay, lev, stream) != 0 ||
-            lw_solver_noscat_impl<F>(ncol, nlay, ngpt, top_at_1, 1, secants, weights, tau, lay, lev, sfc_emis, sfc_src, inc_flux,
-                                     flux_ws, flux_ws + n_lev, Bool(0), (F*)nullptr, (F*)nullptr, Bool(0), (const F*)nullptr,
-                                     (F*)nullptr, stream) != 0)
-            return 1;                                                // (the message is set)
-        sum_bands_kernel<F><<<dim3(ceil_div(nlevcol, 256), nbnd, 2), 256, 0, st>>>(nlevcol, ngpt, band_lims, flux_ws, bnd_up, bnd_dn,
+        const F* ws = lw_fractions_per_gpoint<F>(lease, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, blay, blev,
+                                                 gpoint_bands, sfc_emis, sfc_src, inc_flux, (const F*)nullptr, stream);
+        if (ws == nullptr) return 1;                                 // (the message is set)
+        sum_bands_kernel<F><<<dim3(ceil_div(nlevcol, 256), nbnd, 2), 256, 0, st>>>(nlevcol, ngpt, band_lims, ws, bnd_up, bnd_dn,
                                                                                       (F*)nullptr);
     }
     launch_byband_outputs<F,2>(st, nlevcol, nbnd, bnd_up, bnd_dn, (const F*)nullptr, bnd_net, flux_up, flux_dn, (F*)nullptr);
@@ -1329,7 +1129,18 @@ int lw_solver_noscat_fractions_byband_impl(
 
 extern "C"
 {
-int rrx_set_lw_variant(int v) { rrx::tuning().lw_variant = v; return 0; }
+int rrx_set_lw_variant(int v)
+{
+    if (v != 0 && v != 1 && v != 4 && v != 7 && v != 15)
+    {
+        rrx::set_error("rrx_set_lw_variant: " + std::to_string(v) + " is not an LW variant; accepted: 0 (default), 1 (serial kernel), "
+                       "4 (general kernel with 64-B rows), 7 (no one-kernel broadband form), 15 (fp32: one column per lane in the "
+                       "one-kernel broadband form)");
+        return 1;
+    }
+    rrx::tuning().lw_variant = v;
+    return 0;
+}
 #if RRX_LW_TIMING
 // diagnostic build only: phase clocks per wavefront of a workgroup (out[16][8]: sources + transmissivities, down scan, up scan, replays + sums,
 // -, -, barrier waits, loop top) summed over the workgroups since the last call, then reset

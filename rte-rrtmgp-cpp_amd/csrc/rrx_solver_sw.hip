@@ -748,31 +748,6 @@ sw_2stream_serial_kernel(
 
 
 template<typename F>
-__global__ void sum_gpt_kernel(const size_t ncl_lev, const int ngpt, const F* __restrict__ in, F* __restrict__ out)
-{
-    const size_t i = size_t(blockIdx.x)*blockDim.x + threadIdx.x;
-    if (i >= ncl_lev) return;
-    F s = F(0.);
-    for (int ig=0; ig<ngpt; ++ig) s += in[i + size_t(ig)*ncl_lev];
-    out[i] = s;
-}
-
-// the partial sums of the g-point ranges of a fused broadband launch, all flux arrays in one launch (blockIdx.y = array; the
-// partials of array a start at in + a*nsplit*ncl_lev): range order, as sum_gpt_kernel
-template<typename F, int NARR>
-__global__ void sum_ranges_kernel(const size_t ncl_lev, const int nsplit, const F* __restrict__ in, F* const o0, F* const o1, F* const o2)
-{
-    const size_t i = size_t(blockIdx.x)*blockDim.x + threadIdx.x;
-    if (i >= ncl_lev) return;
-    const int a = blockIdx.y;
-    const F* __restrict__ p = in + size_t(a)*nsplit*ncl_lev;
-    F s = F(0.);
-    for (int ig=0; ig<nsplit; ++ig) s += p[i + size_t(ig)*ncl_lev];
-    F* __restrict__ out = (a == 0) ? o0 : ((a == 1 || NARR < 3) ? o1 : o2);
-    out[i] = s;
-}
-
-template<typename F>
 __global__ void apply_BC_kernel(const int ncol, const int nlay, const int ngpt, const int top_at_1,
         const F* __restrict__ inc_flux, const F* __restrict__ factor, F* __restrict__ flux_dn)
 {
@@ -802,9 +777,6 @@ bool launch_scan(hipStream_t st,
 #undef RRX_SW_K
     return false;
 }
-
-// run f with a compile-time copy of a run-time flag
-template<typename Fn> void with_flag(const bool flag, Fn&& f) { if (flag) f(std::true_type{}); else f(std::false_type{}); }
 
 // Fused broadband form. W waves per column group, CLT column lanes per wave (two column groups per workgroup); false when the
 // columns are taller than the form's largest K (the caller tries the next form).

@@ -82,3 +82,20 @@ def test_package_never_imports_the_oracle():
                 if "dlopen" in src:
                     # the one dynamic load inside the package: the driver loads the RCCL all-gather library on demand (--ngpus)
                     assert f == "test_rte_rrtmgp_gpu.cpp" and "librrx_rccl.so" in src and src.count("dlopen(") == 1, f
+
+
+def test_lw_variant_switch_accepts_only_live_values():
+    """rrx_set_lw_variant takes the values that still select a path and rejects the rest with a message, no GPU needed."""
+    if not os.path.exists(LIB):
+        pytest.fail(f"{LIB} not built: run __graft_entry__.build()")
+    lib = ctypes.CDLL(LIB)
+    lib.rrx_last_error.restype = ctypes.c_char_p
+    try:
+        for v in (0, 1, 4, 7, 15):
+            assert lib.rrx_set_lw_variant(v) == 0, v
+        for v in (8, 16):                       # retired / never existed
+            assert lib.rrx_set_lw_variant(v) != 0, v
+            msg = lib.rrx_last_error().decode()
+            assert "rrx_set_lw_variant" in msg and "15" in msg, msg
+    finally:
+        assert lib.rrx_set_lw_variant(0) == 0

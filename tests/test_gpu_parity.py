@@ -171,7 +171,7 @@ def test_broadband_mode_equals_sum_of_gpoints(kind, fused, ncol, nlay, top_at_1,
 
 @pytest.mark.parametrize("dt", ["f64", "f32"])
 @pytest.mark.parametrize("top_at_1", [False, True])
-def test_fused_broadband_solvers_sum_gpoints_in_order(dt, top_at_1, hip_f64, hip_f32):
+def test_fused_broadband_solvers_sum_gpoints_in_order_live_variants(dt, top_at_1, hip_f64, hip_f32):
     """do_broadband in its fused form keeps the g-point sums on chip and adds the g-points in sum_broadband's order:
     (i) bit-identical to the same kernel run one g-point at a time and summed sequentially; (ii) equal to
     sum_broadband over the stored per-g-point fluxes up to the rounding of a differently tiled kernel."""
@@ -195,12 +195,12 @@ def test_fused_broadband_solvers_sum_gpoints_in_order(dt, top_at_1, hip_f64, hip
     stored = [be.to_numpy(be.sum_broadband(x)) for x in solve(slice(None), False)]
     be.set_broadband_min_groups(1)
     try:
-        # the other tilings of the fused LW form (two waves, four waves, 16 x 4 lanes) against the stored fluxes
-        for lwv in (8, 9, 12):
+        # the other tiling of the fused LW form (fp32: one column per lane, variant 15) against the stored fluxes; fp64 has none
+        for lwv in ((15,) if dt == "f32" else ()):
             be.set_variant(lw=lwv)
             alt = [be.to_numpy(x) for x in solve(slice(None), True)]
             for name, a_, c_ in zip(names[:2], alt[:2], stored[:2]):
-                assert cases.rel_err(a_, c_) <= (1e-13 if dt == "f64" else 1e-5), (name, lwv)
+                assert cases.rel_err(a_, c_) <= 1e-5, (name, lwv)
         be.set_variant(lw=0)
         fused = [be.to_numpy(x) for x in solve(slice(None), True)]
         seq = None
@@ -375,7 +375,7 @@ def test_byband_and_subset_and_clouds(hip_f64, oracle_f64):
             assert cases.rel_err(a_, b_) <= 1e-12
 
 
-def test_solver_variants_agree(hip_f64):
+def test_live_solver_variants_agree(hip_f64):
     """scan (8 column-lanes x 8 level-lanes) vs the serial one-thread-per-column fallback kernels."""
     rng = np.random.default_rng(9)
     ngpt, nlay, ncol = 12, 140, 96
@@ -385,8 +385,8 @@ def test_solver_variants_agree(hip_f64):
     be = hip_f64; up = be.asarray
     sec = be.lw_secants_array(ncol, ngpt, 1, 4, up(pipeline.GAUSS_DS)); w = up(np.array([1.0]))
     res = []
-    # LW: 0 default, 1 serial, 2..6 the scan tilings; SW: 0 two-wave scan, 1 serial, 2 one-wave scan
-    for variant, swv in ((0, 0), (1, 1), (2, 2), (3, 2), (4, 0), (5, 0), (6, 2)):
+    # LW: 0 default, 1 serial, 4 the scan kernel with 64-B rows; SW: 0 two-wave scan, 1 serial, 2 one-wave scan
+    for variant, swv in ((0, 0), (1, 1), (4, 2)):
         be.set_variant(lw=variant, sw=swv)
         l = be.lw_solver_noscat(True, sec, w, up(tau), up(lay), up(lev), up(e2), up(e2*20))
         s = be.sw_solver_2stream(True, up(tau), up(ssa), up(g), up(mu0), up(e2*.5), up(e2*.4), up(e2*3))

@@ -12,7 +12,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--ncol", type=int, default=16384); ap.add_argument("--nlay", type=int, default=140)
 ap.add_argument("--ngpt", type=int, default=256); ap.add_argument("--dtype", default="f64")
 ap.add_argument("--rounds", type=int, default=5)
-ap.add_argument("--lw", default="0,2,1"); ap.add_argument("--sw", default="0,1")
+ap.add_argument("--lw", default="0,4,1"); ap.add_argument("--sw", default="0,1")
 a = ap.parse_args()
 dt = np.float64 if a.dtype == "f64" else np.float32
 be = R.HipKernels(dt)
