@@ -352,6 +352,18 @@ int rrx_lw_solver_noscat_fractions_jac##SFX( \
         const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands, \
         const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up_loc, F* flux_dn_loc, \
         const F* sfc_src_jac, F* flux_up_jac, void* stream); \
+/* rrx_lw_solver_noscat_fractions [_jac] with nmus = 1..4 quadrature angles in one kernel: every g-point's tau and Planck fractions \
+   are read once and the solve runs nmus times on them. secants is (ncol, ngpt, nmus) and is read per column and g-point (it need \
+   not be the broadcast of rrx_lw_secants_array), weights is (nmus). Each angle's pi*weights[imu]*radiance is added to the running \
+   g-point sum in the order (g-point, angle); the per-g-point route adds a g-point's angles first, a difference of rounding only. \
+   sfc_src_jac and flux_up_jac are both NULL (fluxes only) or both given (Jacobian as in the _jac entry, the same weights). \
+   nmus = 1 forwards to the one-angle entries: the same bits. No by-band form. Shapes outside the one-kernel tilings take the \
+   per-g-point kernels with the same nmus */ \
+int rrx_lw_solver_noscat_fractions_angles##SFX( \
+        int ncol, int nlay, int ngpt, RrxBool top_at_1, int nmus, const F* secants, const F* weights, \
+        const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands, \
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up_loc, F* flux_dn_loc, \
+        const F* sfc_src_jac, F* flux_up_jac, void* stream); \
 /* host-model update between radiation calls (no counterpart in the reference library): with d = flux_up_jac * (t_sfc_new - \
    t_sfc_old) of the level's column, flux_up += d and (flux_net not NULL) flux_net -= d; flux arrays (ncol, nlev), t_sfc (ncol) */ \
 int rrx_lw_flux_up_adjust##SFX(int ncol, int nlev, const F* flux_up_jac, const F* t_sfc_old, const F* t_sfc_new, \

@@ -14,6 +14,7 @@
 #ifndef RADIATION_SOLVER_H
 #define RADIATION_SOLVER_H
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include "Array.h"
 #include "Gas_concs.h"
@@ -87,10 +88,20 @@ class Radiation_solver_longwave
         // (rrx_lw_flux_up_adjust). Not with set_byband_solvers(true): solve_gpu throws.
         void set_jacobian(const bool b) { jacobian = b; }
         const Array_gpu<Float,2>& get_lw_flux_up_jac() const { return lw_flux_up_jac; }
+        // Quadrature angles of the LW solver (1..4 Gauss-Jacobi-5 nodes, default 1; throws otherwise). With the broadband solvers more
+        // than one takes the several-angle form of the fused solver (rrx_lw_solver_noscat_fractions_angles, Jacobian included), the
+        // per-g-point solvers take the general kernel once per angle. Not with the by-band solvers in use: solve_gpu throws.
+        void set_gauss_angles(const int n)
+        {
+            if (n < 1 || n > 4) throw std::runtime_error("Radiation_solver_longwave::set_gauss_angles: " + std::to_string(n) + " is outside 1..4");
+            n_gauss_angles = n;
+        }
+        int get_gauss_angles() const { return n_gauss_angles; }
 
     private:
         int column_sorting = -1, sort_decided = -1;
         bool column_padding = true, reordered_call = false, jacobian = false;
+        int n_gauss_angles = 1;
         Array_gpu<Float,2> lw_flux_up_jac;
         std::unique_ptr<Gas_optics_rrtmgp_gpu> kdist_gpu;
         std::unique_ptr<Cloud_optics_gpu> cloud_optics_gpu;

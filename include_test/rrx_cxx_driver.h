@@ -28,6 +28,8 @@ int   rrx_cxx_sunlit_columns(void* handle, int sunlit);
 /* set_jacobian of the longwave solver (0 = off, the default): each solve also forms d lw_flux_up / d t_sfc [W m-2 K-1];
    rrx_cxx_lw_flux_up_jac copies the (ncol, nlay+1) result of the last solve to the DEVICE array `out` on `stream` */
 int   rrx_cxx_lw_jacobian(void* handle, int on);
+/* set_gauss_angles of the longwave solver: n = 1..4 quadrature angles (default 1); another value is an error */
+int   rrx_cxx_lw_gauss_angles(void* handle, int n);
 int   rrx_cxx_lw_flux_up_jac(void* handle, Real* out, void* stream);
 /* one LW + one SW solve_gpu (fluxes only) enqueued on `stream`; DEVICE arrays: (ncol,nlay) / (ncol,nlay+1) fields, (ncol) vectors,
    surface properties (nbnd,ncol); lwp, iwp, rel, dei NULL without clouds; out7: seven (ncol, nlay+1) arrays for LW up, dn, net and

@@ -316,8 +316,16 @@ __device__ unsigned long long g_lw_clk[16][8];
 // below the lane, times emis*sfc_src_jac, is the lane's incoming Jacobian (the general kernel's jac_in); the replay is jc = trans*jc and
 // the g-point sums go to flux_up_jac in order with add_rounded, like the fluxes. The sums sit in registers (K more per column) whatever
 // LACC says: the LDS of the four-wave fp64 form has no room for a third column at two workgroups per CU.
+// MU (several quadrature angles, rrx_lw_solver_noscat_fractions_angles): the g-point's loads are issued once and the sequence evaluate ->
+// scans -> replay runs nmus times on them (a run-time, wave-uniform count), with D = secants(col, gpt, imu) read per column and g-point
+// one angle ahead and each angle's term added with pi*weights[imu] straight into the running g-point sums. The loaded g-point stays
+// in its registers through the angles (no second copy); the prefetch of the next g-point overwrites it behind the first barrier of
+// the LAST angle, when the evaluation has consumed it. Through an angle's evaluation the g-point (2K values per column) and tr / sdn /
+// sup (3K) are live together, which the one-angle form avoids: the nine-layer forms spill. The source terms pfrac*B_lay
+// and sqrt(pfrac*pfrac')*B_lev are recomputed per angle: holding them takes 2K+1 more registers per column.
+// Everything MU adds is written so that the one-angle forms keep the statements, and with them the code, they had before it.
 template<typename F, int V, int K, int W, int CLT, bool LITE, bool GS = false, int EV = RRX_LW_EV, int NW = (W > 4 ? W : 4), bool BND = false,
-         bool JAC = false>
+         bool JAC = false, bool MU = false>
 __global__ void __launch_bounds__(64*NW, (NW > W) ? RRX_LW_F32_WAVES : (NW > 4 ? 1 : 2))
 lw_noscat_bb_kernel(
         const int ncol, const int nlay, const int ngpt, const int top_at_1,
@@ -326,10 +334,12 @@ lw_noscat_bb_kernel(
         const F* __restrict__ blay, const F* __restrict__ blev, const int* __restrict__ gpoint_bands,
         const F* __restrict__ sfc_emis, const F* __restrict__ sfc_src, const F* __restrict__ inc_flux,
         F* __restrict__ flux_up, F* __restrict__ flux_dn, const int gper, const size_t part_stride,
-        const int* __restrict__ band_lims, const F* __restrict__ sfc_src_jac = nullptr, F* __restrict__ flux_up_jac = nullptr)
+        const int* __restrict__ band_lims, const F* __restrict__ sfc_src_jac = nullptr, F* __restrict__ flux_up_jac = nullptr,
+        const int nmus = 1)
 {
     static_assert(!(GS && BND), "a by-band launch is its own g-point split");
     static_assert(!(JAC && BND), "no by-band Jacobian");
+    static_assert(!MU || (LITE && !BND), "several angles: Planck-lite inputs, no by-band form");
     // GS: blockIdx.y = g-point range [g_lo, g_hi) of this workgroup; its sums go to partial array blockIdx.y
     const int g_lo = BND ? max(band_lims[2*blockIdx.y] - 1, 0) : (GS ? blockIdx.y*gper : 0);
     const int g_hi = BND ? min(band_lims[2*blockIdx.y+1], ngpt) : (GS ? min(ngpt, g_lo + gper) : ngpt);
@@ -411,7 +421,8 @@ lw_noscat_bb_kernel(
             L.x_prev = load_cols<F,V>(l_g + lay_off(-1));         // pfrac of the layer above the lane's first one
         }
         const size_t sfc = size_t(g)*ncl + icol;
-        L.emis = load_cols<F,V>(sfc_emis + sfc); L.ssrc = load_cols<F,V>(sfc_src + sfc); L.D = load_cols<F,V>(secants + sfc);
+        L.emis = load_cols<F,V>(sfc_emis + sfc); L.ssrc = load_cols<F,V>(sfc_src + sfc);
+        if constexpr (!MU) L.D = load_cols<F,V>(secants + sfc);
         if (inc_flux != nullptr) L.inc = load_cols<F,V>(inc_flux + sfc);
         if constexpr (JAC) J = load_cols<F,V>(sfc_src_jac + sfc);
     };
@@ -422,6 +433,11 @@ lw_noscat_bb_kernel(
     int cur_bnd = -1;
     const F wgt = weights[0];
     const F scale = pi * wgt;
+    // MU: the secant of the next (g-point, angle) in sequence, one angle ahead; the surface values of the current g-point (they
+    // are used behind the barrier where the prefetch overwrites the g-point); the angle's pi*weight
+    Vec<F,V> d_next, c_emis, c_ssrc, c_inc;
+    F scale_mu;
+    if constexpr (MU) d_next = load_cols<F,V>(secants + size_t(g_lo)*ncl + icol);
 
 #if RRX_LW_TIMING
     unsigned long long lw_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lw_t = __builtin_readcyclecounter();
@@ -429,8 +445,9 @@ lw_noscat_bb_kernel(
     for (int igpt=g_lo; igpt<g_hi; ++igpt)
     {
     RRX_LW_T(7)
-    Loads cur = nxt;
+    std::conditional_t<MU, Loads&, Loads> cur = nxt;            // MU: the g-point stays where it was loaded
     if constexpr (JAC) jcur = jnxt;
+    if constexpr (MU) { c_emis = cur.emis; c_ssrc = cur.ssrc; c_inc = cur.inc; }
 
     if constexpr (LITE)
     {
@@ -473,6 +490,24 @@ lw_noscat_bb_kernel(
         }
     };
 
+    int imu = 0;
+    do      // the angles (one pass unless MU)
+    {
+    if constexpr (MU)
+    {
+        cur.D = d_next;
+        scale_mu = pi * weights[imu];
+        const bool last = imu == nmus-1;
+        d_next = load_cols<F,V>(secants + (size_t(last ? 0 : imu + 1)*ngpt + (last ? min(igpt + 1, g_hi - 1) : igpt))*ncl + icol);
+        // the Planck fractions are made opaque per angle, or the compiler hoists the angle-independent source terms out of this
+        // loop and holds them: 2K+1 more registers per column, which the nine-layer forms do not have
+        #pragma unroll
+        for (int j=0; j<K; ++j)
+            #pragma unroll
+            for (int v=0; v<V; ++v) asm volatile("" : "+v"(cur.a1[j].v[v]));
+        #pragma unroll
+        for (int v=0; v<V; ++v) asm volatile("" : "+v"(cur.x_prev.v[v]), "+v"(cur.x_next.v[v]));
+    }
     F tr[K][V], sdn[K][V], sup[K][V];
     F A[V], Bdn[V], Bup[V], lva[V];
     #pragma unroll
@@ -524,7 +559,7 @@ lw_noscat_bb_kernel(
         RRX_LW_T(1)
         __syncthreads();
         RRX_LW_T(6)
-        if (v == 0)
+        if (v == 0) if (!MU || imu == nmus-1)                  // (several angles: behind the first barrier of the last one)
         {
             // every wave of the workgroup is here: the waves that share 128-B lines ask for them together
             __builtin_amdgcn_sched_barrier(0);
@@ -542,10 +577,10 @@ lw_noscat_bb_kernel(
         if (h > 0) { b = a*xb + b; a = a*xa; }
         F ae = shfl(a, lane - CL), be = shfl(b, lane - CL);
         if (ll == 0) { ae = xa; be = xb; }
-        const F dn_top = (inc_flux != nullptr) ? cur.inc.v[v] / pi : F(0.);
+        const F dn_top = (inc_flux != nullptr) ? (MU ? c_inc : cur.inc).v[v] / pi : F(0.);
         dn_in[v] = ae*dn_top + be;
         const F dn_sfc = fa*dn_top + fb;
-        const F up_sfc = dn_sfc * (F(1.) - cur.emis.v[v]) + cur.emis.v[v] * cur.ssrc.v[v];
+        const F up_sfc = dn_sfc * (F(1.) - (MU ? c_emis : cur.emis).v[v]) + (MU ? c_emis : cur.emis).v[v] * (MU ? c_ssrc : cur.ssrc).v[v];
 
         // ---- upward: inclusive suffix scan
         a = A[v]; b = Bup[v];
@@ -567,7 +602,7 @@ lw_noscat_bb_kernel(
         ae = shfl(a, lane + CL); be = shfl(b, lane + CL);
         if (ll == LL-1) { ae = xa; be = xb; }
         up_in[v] = ae*up_sfc + be;
-        if constexpr (JAC) jc_in[v] = ae * cur.emis.v[v] * jcur.v[v];
+        if constexpr (JAC) jc_in[v] = ae * (MU ? c_emis : cur.emis).v[v] * jcur.v[v];
     }
 
     #pragma unroll
@@ -577,8 +612,8 @@ lw_noscat_bb_kernel(
         #pragma unroll
         for (int j=0; j<K; ++j)
         {
-            if constexpr (LACC) { F a = lds_acc[(K+j)*V+v][tid]; add_rounded(a, scale*dn); lds_acc[(K+j)*V+v][tid] = a; }
-            else add_rounded(acc_dn[j][v], scale*dn);
+            if constexpr (LACC) { F a = lds_acc[(K+j)*V+v][tid]; add_rounded(a, (MU ? scale_mu : scale)*dn); lds_acc[(K+j)*V+v][tid] = a; }
+            else add_rounded(acc_dn[j][v], (MU ? scale_mu : scale)*dn);
             dn = tr[j][v]*dn + sdn[j][v];
         }
         F up = up_in[v];
@@ -586,17 +621,18 @@ lw_noscat_bb_kernel(
         for (int j=K-1; j>=0; --j)
         {
             up = tr[j][v]*up + sup[j][v];
-            if constexpr (LACC) { F a = lds_acc[j*V+v][tid]; add_rounded(a, scale*up); lds_acc[j*V+v][tid] = a; }
-            else add_rounded(acc_up[j][v], scale*up);
+            if constexpr (LACC) { F a = lds_acc[j*V+v][tid]; add_rounded(a, (MU ? scale_mu : scale)*up); lds_acc[j*V+v][tid] = a; }
+            else add_rounded(acc_up[j][v], (MU ? scale_mu : scale)*up);
         }
         if constexpr (JAC)
         {
             F jc = jc_in[v];
             #pragma unroll
-            for (int j=K-1; j>=0; --j) { jc = tr[j][v]*jc; add_rounded(acc_jc[j][v], scale*jc); }
+            for (int j=K-1; j>=0; --j) { jc = tr[j][v]*jc; add_rounded(acc_jc[j][v], (MU ? scale_mu : scale)*jc); }
         }
     }
     RRX_LW_T(3)
+    } while (MU && ++imu < nmus);
     }   // g-point loop
 #if RRX_LW_TIMING
     if (lane == 0) for (int k=0; k<8; ++k) atomicAdd(&g_lw_clk[wave & 15][k], lw_acc[k]);
@@ -759,14 +795,16 @@ struct BbArgs
     F *flux_up, *flux_dn;
     const int* band_lims; int nbnd;             // by-band form: flux_up/dn are (ncol, nlev, nbnd) band sums
     const F* sfc_src_jac; F* flux_up_jac;       // JAC: (ngpt, ncol) in, (ncol, nlev) out
+    int nmus;                                   // MU: quadrature angles; secants (ncol, ngpt, nmus), weights (nmus)
 };
 
 // one tiling of the fused broadband kernel (lw_noscat_bb_kernel); false when the shape is outside it (the caller tries the next one).
 // LITE: lay_source = pfrac, lev_source unused. JAC: the Jacobian form, in the geometry and g-point split the fluxes alone would take
-// (so they come out bit for bit the same).
-template<typename F, int V, int W, int CLT, bool LITE, int NW, bool JAC>
+// (so they come out bit for bit the same). MU: the several-angle form (a.nmus angles), same geometry and split again.
+template<typename F, int V, int W, int CLT, bool LITE, int NW, bool JAC, bool MU>
 bool launch_bb2(hipStream_t st, const BbArgs<F>& a)
 {
+    static_assert(!MU || LITE, "several angles: Planck-lite inputs only");
     if (size_t(a.ncol)*(a.nlay+1) >= (size_t(1) << 31)) return false;      // 32-bit element offsets inside a g-point slab
     const int groups = ceil_div(a.ncol, (NW/W)*CLT*V);
     const int need = ceil_div(a.nlay+1, (64/CLT)*W);
@@ -778,7 +816,7 @@ bool launch_bb2(hipStream_t st, const BbArgs<F>& a)
         else return with_k<2, 3, 5>(need, launch);
     };
     const size_t nlevcol = size_t(a.ncol)*(a.nlay+1);
-    if (!JAC && a.band_lims != nullptr)
+    if (!JAC && !MU && a.band_lims != nullptr)
     {
         // one band per workgroup (grid.y = band): no store inside the g-point loop, no partial arrays, no allocation. Planck-lite
         // inputs only (the by-band entry is rrx_lw_solver_noscat_fractions_byband).
@@ -808,9 +846,10 @@ bool launch_bb2(hipStream_t st, const BbArgs<F>& a)
     const dim3 grid(groups, nsplit);
     with_tiling_k([&](auto kk) { with_flag(nsplit > 1, [&](auto gs)
     {
-        lw_noscat_bb_kernel<F,V,decltype(kk)::value,W,CLT,LITE,decltype(gs)::value,RRX_LW_EV,NW,false,JAC><<<grid, 64*NW, 0, st>>>(
+        lw_noscat_bb_kernel<F,V,decltype(kk)::value,W,CLT,LITE,decltype(gs)::value,RRX_LW_EV,NW,false,JAC,MU><<<grid, 64*NW, 0, st>>>(
             a.ncol, a.nlay, a.ngpt, a.top_at_1, a.secants, a.weights, a.tau, a.lay_source, a.lev_source, a.blay, a.blev,
-            a.gpoint_bands, a.sfc_emis, a.sfc_src, a.inc_flux, out_up, out_dn, gper, nlevcol, nullptr, a.sfc_src_jac, out_jc);
+            a.gpoint_bands, a.sfc_emis, a.sfc_src, a.inc_flux, out_up, out_dn, gper, nlevcol, nullptr, a.sfc_src_jac, out_jc,
+            MU ? a.nmus : 1);
     }); });
     if (nsplit > 1)      // (out_up, out_dn [, out_jc] lie behind each other in the scratch block)
         sum_ranges_kernel<F,NARR><<<dim3(ceil_div(nlevcol, 256), NARR), 256, 0, st>>>(nlevcol, nsplit, out_up, a.flux_up, a.flux_dn,
@@ -820,30 +859,30 @@ bool launch_bb2(hipStream_t st, const BbArgs<F>& a)
 
 // broadband fluxes from tau + (lay_source, lev_source) [LITE = false] or tau + Planck fractions and band Planck functions
 // [LITE = true] in the one-kernel form; false when the shape is outside its tilings (the caller takes another path)
-// [JAC = true: flux_up_jac too, from the same forms in the same order]
-template<typename F, bool LITE, bool JAC = false>
+// [JAC = true: flux_up_jac too, from the same forms in the same order; MU = true: nmus angles, secants (ncol, ngpt, nmus)]
+template<typename F, bool LITE, bool JAC = false, bool MU = false>
 bool lw_fused_broadband(
         hipStream_t st, const int ncol, const int nlay, const int ngpt, const int top_at_1,
         const F* secants, const F* weights, const F* tau, const F* lay_source, const F* lev_source,
         const F* blay, const F* blev, const int* gpoint_bands,
         const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn,
         const int* band_lims = nullptr, const int nbnd = 0 /* by-band form (launch_bb2) */,
-        const F* sfc_src_jac = nullptr, F* flux_up_jac = nullptr)
+        const F* sfc_src_jac = nullptr, F* flux_up_jac = nullptr, const int nmus = 1)
 {
     const BbArgs<F> a{ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source, blay, blev, gpoint_bands,
-                      sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac};
+                      sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac, nmus};
     if constexpr (sizeof(F) == 8)
     {
         // (Round 4 measured six waves x six layers per column group -- 384-thread workgroups, three waves per SIMD, 168 VGPRs with
         //  108-124 B of scratch: 4.2-4.7 ms against 2.7 for this form, profiles/r04_fp32_geometry_ab.txt.)
-        if (launch_bb2<F,1,4,16,LITE,4,JAC>(st, a)) return true;
+        if (launch_bb2<F,1,4,16,LITE,4,JAC,MU>(st, a)) return true;
         // 144 ... 287 layers: eight wavefronts per column group
-        if (launch_bb2<F,1,8,16,LITE,8,JAC>(st, a)) return true;
+        if (launch_bb2<F,1,8,16,LITE,8,JAC,MU>(st, a)) return true;
         // 288 ... 575 layers (round 4: RCEMIP's default is 256 levels, LES grids with a background profile on top exceed 288): the same
         // eight waves with 8 x 8 lanes -- 64 levels per wave at nine layers per lane, 64-B rows (the other half of each 128-B line
         // belongs to the next column group: twice the L2 fetches, on a kernel that stands at a quarter of the HBM roof). Beyond that
         // the one-thread-per-column kernels take over.
-        return launch_bb2<F,1,8,8,LITE,8,JAC>(st, a);
+        return launch_bb2<F,1,8,8,LITE,8,JAC,MU>(st, a);
     }
     else
     {
@@ -852,17 +891,17 @@ bool lw_fused_broadband(
         // W = 6 at three, K = 5 / W = 8 at four: 1.82 / 1.88 / 1.95 ms at C4 against 1.31 for two columns per lane with the sums in
         // LDS, profiles/r04_fp32_geometry_ab.txt): the LW chain per g-point is short, so halving the wavefronts per column wins.
         // The one-column form stays for odd column counts (variant 15 forces it for tests).
-        if (tuning().lw_variant == 15 && launch_bb2<F,1,4,16,LITE,8,JAC>(st, a)) return true;
+        if (tuning().lw_variant == 15 && launch_bb2<F,1,4,16,LITE,8,JAC,MU>(st, a)) return true;
         // 16 x 4 lanes with two columns per lane (128-B rows, K = 9) ahead of 8 x 8 lanes with four. Measured at C4 in the fractions
         // form: 1.77 against 3.26 ms (the four-column lane state spills); the latter still takes 144 ... 159 layers.
-        if (ncol % 2 == 0 && launch_bb2<F,2,4,16,LITE,4,JAC>(st, a)) return true;
-        if (ncol % 4 == 0 && launch_bb2<F,4,4,8,LITE,4,JAC>(st, a)) return true;
+        if (ncol % 2 == 0 && launch_bb2<F,2,4,16,LITE,4,JAC,MU>(st, a)) return true;
+        if (ncol % 4 == 0 && launch_bb2<F,4,4,8,LITE,4,JAC,MU>(st, a)) return true;
         // 144 ... 287 layers: eight wavefronts per column group
-        if (ncol % 2 == 0 && launch_bb2<F,2,8,16,LITE,8,JAC>(st, a)) return true;
+        if (ncol % 2 == 0 && launch_bb2<F,2,8,16,LITE,8,JAC,MU>(st, a)) return true;
         // 288 ... 575 layers: eight waves of 8 x 8 lanes (see fp64)
-        if (ncol % 2 == 0 && launch_bb2<F,2,8,8,LITE,8,JAC>(st, a)) return true;
+        if (ncol % 2 == 0 && launch_bb2<F,2,8,8,LITE,8,JAC,MU>(st, a)) return true;
         // odd column counts: one column per lane
-        return launch_bb2<F,1,4,16,LITE,8,JAC>(st, a);
+        return launch_bb2<F,1,4,16,LITE,8,JAC,MU>(st, a);
     }
 }
 
@@ -990,7 +1029,7 @@ template<typename F>
 const F* lw_fractions_per_gpoint(
         WorkspaceLease& lease, const int ncol, const int nlay, const int ngpt, const Bool top_at_1,
         const F* secants, const F* weights, const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands,
-        const F* sfc_emis, const F* sfc_src, const F* inc_flux, const F* sfc_src_jac, void* stream)
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, const F* sfc_src_jac, void* stream, const int nmus = 1)
 {
     const size_t n_lay = size_t(ncol)*nlay*ngpt, n_lev = size_t(ncol)*(nlay+1)*ngpt;
     const size_t nout = (sfc_src_jac != nullptr) ? 3 : 2;
@@ -998,7 +1037,7 @@ const F* lw_fractions_per_gpoint(
     F* lay = ws + nout*n_lev; F* lev = lay + n_lay;
     F* jac = (sfc_src_jac != nullptr) ? ws + 2*n_lev : nullptr;
     if (planck_sources_from_fractions_impl<F>(ncol, nlay, ngpt, gpoint_bands, pfrac, blay, blev, lay, lev, stream) != 0 ||
-        lw_solver_noscat_impl<F>(ncol, nlay, ngpt, top_at_1, 1, secants, weights, tau, lay, lev, sfc_emis, sfc_src, inc_flux,
+        lw_solver_noscat_impl<F>(ncol, nlay, ngpt, top_at_1, nmus, secants, weights, tau, lay, lev, sfc_emis, sfc_src, inc_flux,
                                  ws, ws + n_lev, Bool(0), (F*)nullptr, (F*)nullptr, Bool(jac != nullptr), sfc_src_jac, jac, stream) != 0)
         return nullptr;
     return ws;
@@ -1063,6 +1102,59 @@ int lw_solver_noscat_fractions_jac_impl(
         sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws + 2*nlevcol*ngpt, flux_up_jac);
     }
     RRX_CATCH("rrx_lw_solver_noscat_fractions_jac")
+}
+
+// nmus = 1..4 quadrature angles (rrx_lw_solver_noscat_fractions_angles), with the Jacobian when the pair is given: one angle is the
+// one-angle entries themselves (the same bits); more take the one-kernel form's MU variant where the tilings reach, otherwise the
+// g-point sums of lw_fractions_per_gpoint's fluxes, which the general kernel has added up over the angles
+template<typename F>
+int lw_solver_noscat_fractions_angles_impl(
+        const int ncol, const int nlay, const int ngpt, const Bool top_at_1, const int nmus,
+        const F* secants, const F* weights, const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands,
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up_loc, F* flux_dn_loc, const F* sfc_src_jac, F* flux_up_jac,
+        void* stream)
+{
+    const char* entry = "rrx_lw_solver_noscat_fractions_angles";
+    const char* bad = nullptr;
+    if (nmus < 1 || nmus > 4) bad = "nmus must be 1..4";
+    else if (ncol <= 0) bad = "ncol must be positive";
+    else if (nlay <= 0) bad = "nlay must be positive";
+    else if (ngpt <= 0) bad = "ngpt must be positive";
+    else if (secants == nullptr || weights == nullptr) bad = "secants / weights missing";
+    else if (flux_up_loc == nullptr) bad = "flux_up_loc is null";
+    else if (flux_dn_loc == nullptr) bad = "flux_dn_loc is null";
+    else if (sfc_src_jac != nullptr && flux_up_jac == nullptr) bad = "flux_up_jac is null while sfc_src_jac is given";
+    else if (sfc_src_jac == nullptr && flux_up_jac != nullptr) bad = "sfc_src_jac is null while flux_up_jac is given";
+    if (bad != nullptr) { set_error(std::string(entry) + ": " + bad); return 1; }
+    const bool jac = sfc_src_jac != nullptr;
+    if (nmus == 1)
+        return jac ? lw_solver_noscat_fractions_jac_impl<F>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, blay, blev, gpoint_bands,
+                                                            sfc_emis, sfc_src, inc_flux, sfc_src_jac, flux_up_loc, flux_dn_loc, flux_up_jac, stream)
+                   : lw_solver_noscat_fractions_impl<F>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, blay, blev, gpoint_bands,
+                                                        sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc, stream);
+    RRX_TRY
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    bool fused = false;
+    if (lw_fused_allowed())
+        with_flag(jac, [&](auto j)
+        {
+            fused = lw_fused_broadband<F,true,decltype(j)::value,true>(
+                        st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, (const F*)nullptr, blay, blev, gpoint_bands,
+                        sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc, (const int*)nullptr, 0, sfc_src_jac, flux_up_jac, nmus);
+        });
+    if (!fused)
+    {
+        WorkspaceLease lease(st);
+        const F* ws = lw_fractions_per_gpoint<F>(lease, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, blay, blev,
+                                                 gpoint_bands, sfc_emis, sfc_src, inc_flux, sfc_src_jac, stream, nmus);
+        if (ws == nullptr) return 1;                                 // (the message is set)
+        const size_t nlevcol = size_t(ncol)*(nlay+1);
+        const int nb = ceil_div(nlevcol, 256);
+        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws, flux_up_loc);
+        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws + nlevcol*ngpt, flux_dn_loc);
+        if (jac) sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws + 2*nlevcol*ngpt, flux_up_jac);
+    }
+    RRX_CATCH(entry)
 }
 
 // host-model update between radiation calls (rrx_lw_flux_up_adjust): d = jac * (t_new - t_old) of the level's column;
@@ -1225,6 +1317,15 @@ int rrx_lw_solver_noscat_fractions_jac##SFX( \
 { \
     return lw_solver_noscat_fractions_jac_impl<F>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, blay, blev, gpoint_bands, \
             sfc_emis, sfc_src, inc_flux, sfc_src_jac, flux_up_loc, flux_dn_loc, flux_up_jac, stream); \
+} \
+int rrx_lw_solver_noscat_fractions_angles##SFX( \
+        int ncol, int nlay, int ngpt, Bool top_at_1, int nmus, const F* secants, const F* weights, \
+        const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands, \
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up_loc, F* flux_dn_loc, \
+        const F* sfc_src_jac, F* flux_up_jac, void* stream) \
+{ \
+    return lw_solver_noscat_fractions_angles_impl<F>(ncol, nlay, ngpt, top_at_1, nmus, secants, weights, tau, pfrac, blay, blev, \
+            gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc, sfc_src_jac, flux_up_jac, stream); \
 } \
 int rrx_lw_flux_up_adjust##SFX(int ncol, int nlev, const F* flux_up_jac, const F* t_sfc_old, const F* t_sfc_new, \
         F* flux_up, F* flux_net, void* stream) \

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 class CxxDriver:
     def __init__(self, be, kd_lw0, kd_sw0, atm, cloud_luts0=None, column_block=16384, broadband=True, sort_mode=-1, pad=True,
-                 sunlit=False, jacobian=False):
+                 sunlit=False, jacobian=False, n_gauss_angles=1):
         import torch
         self.torch, self.be, self.atm = torch, be, atm
         self.f64 = be.np_dtype == np.float64
@@ -41,6 +41,10 @@ class CxxDriver:
         self._check(self.lib.rrx_cxx_driver_settings(self.h, int(column_block), int(broadband), int(sort_mode), int(pad)))
         if sunlit:                                  # SW on the columns with mu0 > 0 only, zeros elsewhere (set_sunlit_columns)
             self._check(self.lib.rrx_cxx_sunlit_columns(self.h, 1))
+        # n_gauss_angles: LW quadrature angles, 1..4 (set_gauss_angles; the default launches what it always did)
+        self.n_gauss_angles = int(n_gauss_angles)
+        if self.n_gauss_angles != 1:
+            self._check(self.lib.rrx_cxx_lw_gauss_angles(self.h, self.n_gauss_angles))
         # jacobian: each step also fills self.lw_flux_up_jac (nlev, ncol), d lw_flux_up / d t_sfc [W m-2 K-1] (set_jacobian)
         self.jacobian = bool(jacobian)
         if self.jacobian:

@@ -308,6 +308,25 @@ class HipKernels:
                 fr["sfc_src_jac"], flux_up_jac)
         return dict(flux_up=flux_up, flux_dn=flux_dn, flux_up_jac=flux_up_jac)
 
+    def lw_solver_noscat_fractions_angles(self, top_at_1, kd, secants, weights, tau, fr, sfc_emis, inc_flux=None, flux_up=None,
+                                          flux_dn=None, flux_up_jac=None, jacobian=False):
+        """lw_solver_noscat_fractions [_jac with jacobian=True] for the nmus = 1..4 quadrature angles of secants (nmus, ngpt, ncol)
+        and weights (nmus), in one kernel: each g-point is read once and solved nmus times. One angle gives the bits of the
+        one-angle entries."""
+        ngpt, nlay, ncol = tau.shape
+        nmus = int(weights.shape[0])
+        if tuple(secants.shape) != (nmus, ngpt, ncol):
+            raise ValueError(f"secants {tuple(secants.shape)} is not (nmus, ngpt, ncol) = {(nmus, ngpt, ncol)}")
+        flux_up = self.empty((nlay+1, ncol)) if flux_up is None else flux_up
+        flux_dn = self.empty((nlay+1, ncol)) if flux_dn is None else flux_dn
+        out = dict(flux_up=flux_up, flux_dn=flux_dn)
+        if jacobian:
+            out["flux_up_jac"] = self.empty((nlay+1, ncol)) if flux_up_jac is None else flux_up_jac
+        self._c("lw_solver_noscat_fractions_angles", ncol, nlay, ngpt, BoolArg(top_at_1), nmus, secants, weights, tau,
+                fr["pfrac"], fr["blay"], fr["blev"], kd.gpoint_bands, sfc_emis, fr["sfc_src"], inc_flux, flux_up, flux_dn,
+                fr["sfc_src_jac"] if jacobian else None, out.get("flux_up_jac"))
+        return out
+
     def lw_flux_up_adjust(self, flux_up_jac, t_sfc_old, t_sfc_new, flux_up, flux_net=None):
         """Host-model update in place: flux_up += jac*(t_new - t_old), flux_net -= the same (when given); (nlev, ncol) arrays"""
         nlev, ncol = flux_up_jac.shape

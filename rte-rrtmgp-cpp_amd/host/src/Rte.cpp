@@ -102,6 +102,16 @@ void Rte_lw_gpu::solve(
     const Float* inc_flux_ptr = (inc_flux.size() == 0) ? nullptr : inc_flux.ptr();
 
     // Planck-lite state (set by Gas_optics_rrtmgp_gpu::gas_optics): the broadband solver forms the sources itself
+    if (sources.holds_fractions() && do_broadband && n_gauss_angles > 1)
+    {
+        // several quadrature angles: one kernel reads each g-point once and solves it n_gauss_angles times (Jacobian pair optional)
+        RRX_CALL(rrx_lw_solver_noscat_fractions_angles, ncol, nlay, ngpt, top_at_1, n_gauss_angles, secants.ptr(), gauss_wts_subset.ptr(),
+                 optical_props->get_tau().ptr(), sources.get_planck_frac().ptr(), sources.get_planck_lay().ptr(), sources.get_planck_lev().ptr(),
+                 optical_props->get_gpoint_bands_gpu().ptr(), sfc_emis_gpt.ptr(), sources.get_sfc_source().ptr(), inc_flux_ptr,
+                 gpt_flux_up.ptr(), gpt_flux_dn.ptr(), do_jacobians ? sources.get_sfc_source_jac().ptr() : nullptr,
+                 do_jacobians ? flux_up_jac->ptr() : nullptr);
+        return;
+    }
     if (sources.holds_fractions() && do_broadband && n_gauss_angles == 1 && do_jacobians)
     {
         RRX_CALL(rrx_lw_solver_noscat_fractions_jac, ncol, nlay, ngpt, top_at_1, secants.ptr(), gauss_wts_subset.ptr(),

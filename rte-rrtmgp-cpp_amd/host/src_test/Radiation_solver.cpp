@@ -328,6 +328,9 @@ void Radiation_solver_longwave::solve_gpu(
     if (jac && byband_solvers)
         throw std::runtime_error("Radiation_solver_longwave: the Jacobian (set_jacobian) is not available with the by-band solvers "
                                  "(set_byband_solvers): no by-band Jacobians");
+    if (byband && n_gauss_angles > 1)
+        throw std::runtime_error("Radiation_solver_longwave: several quadrature angles (set_gauss_angles) are not available with the "
+                                 "by-band solvers (set_byband_solvers): the by-band solver has one angle");
     if (jac && (lw_flux_up_jac.dim(1) != n_col || lw_flux_up_jac.dim(2) != n_lev))
     {
         lw_flux_up_jac = Array_gpu<Float,2>();
@@ -433,7 +436,7 @@ void Radiation_solver_longwave::solve_gpu(
         if (!switch_fluxes)
             continue;
 
-        constexpr int n_ang = 1;
+        const int n_ang = n_gauss_angles;
         Array_gpu<Float,2> emis_s = whole ? Array_gpu<Float,2>(const_cast<Float*>(emis_sfc.ptr()), {n_bnd, n_in}) : emis_sfc.subset({{ {1, n_bnd}, {col_s, col_e} }});
         if (whole && broadband && !switch_output_bnd_fluxes)
         {

@@ -83,6 +83,11 @@ int rrx_cxx_sunlit_columns(void* h, const int sunlit)
     return guarded([&] { static_cast<Driver*>(h)->sw->set_sunlit_columns(sunlit != 0); });
 }
 
+int rrx_cxx_lw_gauss_angles(void* h, const int n)
+{
+    return guarded([&] { static_cast<Driver*>(h)->lw->set_gauss_angles(n); });
+}
+
 int rrx_cxx_lw_jacobian(void* h, const int on)
 {
     return guarded([&] { static_cast<Driver*>(h)->lw->set_jacobian(on != 0); });

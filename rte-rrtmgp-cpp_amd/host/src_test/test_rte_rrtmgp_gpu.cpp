@@ -290,6 +290,29 @@ namespace
             throw std::runtime_error("Illegal dimensions of gas \"" + gas_name + "\" in input");
     }
 
+    // `--lw-gauss-angles=N` / `--lw-gauss-angles N` (LW quadrature angles, 1..4) is taken out of the argument list the same way
+    int lw_gauss_angles = 1;
+    void extract_lw_gauss_angles(std::vector<std::string>& args)
+    {
+        const std::string opt = "--lw-gauss-angles";
+        lw_gauss_angles = 1;                                     // (rrx_host_main may run more than once in a process)
+        for (size_t i=0; i<args.size(); )
+        {
+            std::string value;
+            if (args[i].compare(0, opt.size() + 1, opt + "=") == 0) { value = args[i].substr(opt.size() + 1); args.erase(args.begin() + i); }
+            else if (args[i] == opt)
+            {
+                if (i + 1 >= args.size()) throw std::runtime_error(opt + " needs a number of angles, 1..4");
+                value = args[i+1]; args.erase(args.begin() + i, args.begin() + i + 2);
+            }
+            else { ++i; continue; }
+            char* end = nullptr;
+            const long n = std::strtol(value.c_str(), &end, 10);
+            if (value.empty() || *end != 0 || n < 1 || n > 4) throw std::runtime_error(opt + " " + value + ": the number of angles must be 1..4");
+            lw_gauss_angles = int(n);
+        }
+    }
+
     bool parse_command_line_options(std::map<std::string, std::pair<bool, std::string>>& options, int argc, char** argv)
     {
         for (int i=1; i<argc; ++i)
@@ -304,6 +327,9 @@ namespace
                     ss << std::left << std::setw(30) << ("--" + clo.first) << clo.second.second;
                     Status::print_message(ss.str());
                 }
+                std::ostringstream ss;
+                ss << std::left << std::setw(30) << "--lw-gauss-angles N" << "Quadrature angles of the longwave solver, 1..4 (default 1); not with --byband-solvers.";
+                Status::print_message(ss.str());
                 return true;
             }
             if (argument.size() < 3 || argument[0] != '-' || argument[1] != '-')
@@ -366,6 +392,9 @@ void solve_radiation(int argc, char** argv)
     const bool switch_byband_solvers    = command_line_options.at("byband-solvers").first;
     const bool switch_sunlit_columns    = command_line_options.at("sunlit-columns").first;
     const bool switch_lw_jacobian       = command_line_options.at("lw-jacobian").first;
+    if (lw_gauss_angles > 1 && switch_byband_solvers)
+        throw std::runtime_error("--lw-gauss-angles " + std::to_string(lw_gauss_angles) + " is not available with --byband-solvers: "
+                                 "the by-band solver has one quadrature angle");
     const bool switch_heating_rates     = command_line_options.at("heating-rates"    ).first;
     const bool switch_async             = command_line_options.at("async"            ).first;
     const bool switch_device_sort       = command_line_options.at("device-sort-columns").first;
@@ -487,6 +516,7 @@ void solve_radiation(int argc, char** argv)
         rad_lw.set_broadband_solvers(switch_broadband);
         rad_lw.set_byband_solvers(switch_byband_solvers);
         rad_lw.set_jacobian(switch_lw_jacobian);
+        rad_lw.set_gauss_angles(lw_gauss_angles);
         // (--no-sort-columns: the file's order and column count exactly; otherwise the solver pads to a multiple of 16 columns and,
         //  with --device-sort-columns, orders them itself)
         rad_lw.set_column_sorting(switch_device_sort ? 1 : (switch_sort_columns ? -1 : 0));
@@ -695,6 +725,7 @@ extern "C" int rrx_host_main(int argc, char** argv)
         const int n_gpus = extract_ngpus(args);
         if (n_gpus > 1 && !std::getenv("RRX_RANK"))
             return launch_ranks(n_gpus, args);                       // this process only starts and awaits the ranks
+        extract_lw_gauss_angles(args);
         std::vector<char*> av{argv[0]};
         for (auto& a : args) av.push_back(const_cast<char*>(a.c_str()));
         solve_radiation(int(av.size()), av.data());

@@ -193,7 +193,7 @@ class ResidentSolver:
     STAGES = ("lw_gas_optics", "lw_planck", "lw_solver", "lw_reduce", "sw_gas_optics", "sw_solver", "sw_reduce")
 
     def __init__(self, be, kd_lw, kd_sw, atm, do_broadband=False, overlap=False, cloud_luts=None, sort_columns=None, byband=False,
-                 sunlit=False, jacobian=False):
+                 sunlit=False, jacobian=False, n_gauss_angles=1):
         import torch
         self.torch = torch
         # byband: the step also fills self.bnd_fluxes (lw_up/lw_dn/lw_net/sw_up/sw_dn/sw_dir/sw_net, (nbnd, nlev, ncol) each, the
@@ -202,6 +202,13 @@ class ResidentSolver:
         # jacobian: the step also fills self.lw_flux_up_jac (nlev, ncol, the caller's column order), the surface-temperature Jacobian
         # of the LW upward flux [W m-2 K-1] from the same fused solve; the seven broadband arrays stay bit for bit those without it
         self.jacobian = bool(jacobian)
+        # n_gauss_angles: LW quadrature angles (1..4, Gauss-Jacobi-5 nodes); more than one takes the several-angle form of the fused
+        # solver (lw_solver_noscat_fractions_angles), which has no by-band outputs
+        self.n_gauss_angles = int(n_gauss_angles)
+        if not 1 <= self.n_gauss_angles <= 4:
+            raise ValueError(f"ResidentSolver: n_gauss_angles = {n_gauss_angles} is outside 1..4")
+        if self.n_gauss_angles > 1 and self.byband:
+            raise ValueError("ResidentSolver: byband=True with n_gauss_angles > 1 is not supported (no by-band form with several angles)")
         if self.jacobian and self.byband:
             raise ValueError("ResidentSolver: jacobian=True with byband=True is not supported (no by-band Jacobians)")
         # Column sorting. The windowed gas optics stages ONE box of LUT nodes per 256 neighbouring cells; columns
@@ -304,11 +311,11 @@ class ResidentSolver:
             self.sun_vmr = {n: e((nlay, ncol)) for n, t in atm.vmr.items() if hasattr(t, "dim") and t.dim() == 2}
             self.sun_fluxes = e((4, nlay+1, ncol))
             self.sun_bnd = e((4, kd_sw.nbnd, nlay+1, ncol)) if self.byband else None
-        self.weights = be.asarray(np.ascontiguousarray(GAUSS_WTS[0, :1]))
+        self.weights = be.asarray(np.ascontiguousarray(GAUSS_WTS[self.n_gauss_angles-1, :self.n_gauss_angles]))
         self.gauss_Ds = be.asarray(GAUSS_DS)
         # secants and the band -> g-point expansion of emissivity / albedos: buffers allocated once, the launches themselves are
         # part of every step (rte_lw / rte_sw of the reference run them per solve: src_cuda/Rte_lw.cu:70-110, Rte_sw.cu:57-100)
-        self.secants = e((1, ng_l, ncol))
+        self.secants = e((self.n_gauss_angles, ng_l, ncol))
         self.sfc_emis_gpt = e((ng_l, ncol)); self.alb_dir = e((ng_s, ncol)); self.alb_dif = e((ng_s, ncol))
         self.events = None
         self.col_dry2 = None
@@ -489,12 +496,15 @@ class ResidentSolver:
                     be.compute_planck_source(kd, it, atm.t_lay, atm.t_lev, atm.t_sfc, _sfc_lay(atm), out=srcs)
                 mark("lw_planck", True)
                 mark("lw_solver")
-                be._c("lw_secants_array", ncol, kd.ngpt, 1, MAX_GAUSS_PTS, self.gauss_Ds, self.secants)
+                be._c("lw_secants_array", ncol, kd.ngpt, self.n_gauss_angles, MAX_GAUSS_PTS, self.gauss_Ds, self.secants)
                 be._c("expand_and_transpose", ncol, kd.nbnd, kd.band_lims_gpt, atm.emis_sfc, self.sfc_emis_gpt)
                 if self.byband:
                     be.lw_solver_noscat_fractions_byband(atm.top_at_1, kd, self.secants, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
                                                          out=dict(bnd_flux_up=BL[0], bnd_flux_dn=BL[1], bnd_flux_net=BL[2],
                                                                   flux_up=F[0], flux_dn=F[1]))
+                elif self.lite and self.n_gauss_angles > 1:
+                    be.lw_solver_noscat_fractions_angles(atm.top_at_1, kd, self.secants, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
+                                                         flux_up=F[0], flux_dn=F[1], flux_up_jac=J, jacobian=self.jacobian)
                 elif self.jacobian:
                     be.lw_solver_noscat_fractions_jac(atm.top_at_1, kd, self.secants, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
                                                       flux_up=F[0], flux_dn=F[1], flux_up_jac=J)
@@ -502,7 +512,7 @@ class ResidentSolver:
                     be.lw_solver_noscat_fractions(atm.top_at_1, kd, self.secants, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
                                                   flux_up=F[0], flux_dn=F[1])
                 elif self.do_broadband:
-                    be._c("lw_solver_noscat", ncol, nlay, kd.ngpt, BoolArg(atm.top_at_1), 1, self.secants, self.weights,
+                    be._c("lw_solver_noscat", ncol, nlay, kd.ngpt, BoolArg(atm.top_at_1), self.n_gauss_angles, self.secants, self.weights,
                           buf["tau"], buf["lay_src"], buf["lev_src"], self.sfc_emis_gpt, buf["sfc_src"], None, None, None,
                           BoolArg(True), F[0], F[1], BoolArg(False), None, None)
                 else:
