@@ -69,8 +69,9 @@ int rrx_subset_nd(void* out, const void* in, int elem_bytes, int ndim, const int
                   const int* starts, const int* spread, void* stream);
 /* kernel-variant switches used by bench.py A/B runs (0 = default), per calling thread. LW: 0 default, 1 serial kernel (the test
    reference; the path of columns too tall for the others), 4 general kernel with 64-B rows, 7 never the one-kernel broadband form
-   (per-g-point fluxes in a workspace + sum), 15 fp32: the one-column-per-lane one-kernel broadband form ahead of the others. Any
-   other value returns non-zero, leaves the setting as it was, and rrx_last_error() lists the accepted values. */
+   (per-g-point fluxes in a workspace + sum), 15 fp32: the one-column-per-lane one-kernel broadband form ahead of the others.
+   SW: 0 default, 1 serial kernel, 7 never the one-kernel broadband form. Any other value returns non-zero, leaves the setting as
+   it was, and rrx_last_error() lists the accepted values. */
 int rrx_set_lw_variant(int v);
 int rrx_set_sw_variant(int v);
 /* workgroups the one-kernel broadband solvers aim for: with fewer column groups they split their g-point loop (see

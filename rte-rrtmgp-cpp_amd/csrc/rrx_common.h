@@ -20,7 +20,7 @@ namespace rrx
     struct Tuning
     {
         int lw_variant = 0;        // rrx_set_lw_variant: kernel tiling for A/B runs (0 = default; 1, 4, 7, 15)
-        int sw_variant = 0;        // rrx_set_sw_variant
+        int sw_variant = 0;        // rrx_set_sw_variant: 0 = default; 1 serial kernel, 7 no one-kernel broadband form
         int bb_min_groups = 512;   // rrx_set_broadband_min_groups: workgroups the one-kernel broadband forms aim for
         int bb_gsplit = 0;         // rrx_set_broadband_gsplit: g-point ranges per column group in that form (0 = as many as it
                                    // takes to reach bb_min_groups workgroups, 1 = never split)
@@ -243,6 +243,12 @@ namespace rrx
 
     // run f with a compile-time copy of a run-time flag
     template<typename Fn> void with_flag(const bool flag, Fn&& f) { if (flag) f(std::true_type{}); else f(std::false_type{}); }
+
+    // f(std::integral_constant<int, K>{}) for the first K of the list with need <= K; false when the list ends first
+    template<int... Ks, typename Fn> bool with_k(const int need, Fn&& f)
+    {
+        return ((need <= Ks && (f(std::integral_constant<int,Ks>{}), true)) || ...);
+    }
 
     // The device's default memory pool keeps what is freed into it (its release threshold is lifted once per thread and device), so
     // that the stream-ordered scratch of one solve is reused by the next without going back to the driver. Without it the pool

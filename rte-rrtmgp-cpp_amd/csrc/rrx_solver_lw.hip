@@ -755,12 +755,6 @@ __global__ void lw_secants_array_kernel(
 }
 
 
-// f(std::integral_constant<int, K>{}) for the first K of the list with need <= K; false when the list ends first
-template<int... Ks, typename Fn> bool with_k(const int need, Fn&& f)
-{
-    return ((need <= Ks && (f(std::integral_constant<int,Ks>{}), true)) || ...);
-}
-
 // the general kernel for one quadrature angle; false when the columns are taller than its largest K (the caller takes the serial
 // kernel)
 template<typename F, int V>

@@ -33,23 +33,11 @@ constexpr int LOADG = 6;   // layers per load group
 #endif
 constexpr int BB_LOADS = RRX_SW_BB_LOADS;   // fused broadband form: layers of loads in flight ahead of the evaluation
 constexpr int BB_EVALS = RRX_SW_BB_EVALS;   // fused broadband form: two_stream evaluations the scheduler may interleave
-#ifndef RRX_SW_MINWAVES
-#define RRX_SW_MINWAVES 1
-#endif
-#ifndef RRX_SW_MINWAVES2
-#define RRX_SW_MINWAVES2 2
-#endif
-#ifndef RRX_SW_XCD_MAP
-#define RRX_SW_XCD_MAP 1
-#endif
-#ifndef RRX_SW_F32_NW
-#define RRX_SW_F32_NW 4        // wavefronts per workgroup of the fp32 geometry: 4 = ONE column group (below), 8 = two (A/B)
-#endif
 #ifndef RRX_SW_F32_WAVES1
-#define RRX_SW_F32_WAVES1 3    // ... and the waves per SIMD the one-group form is compiled for
+#define RRX_SW_F32_WAVES1 3    // waves per SIMD the fp32 geometry (16 x 4 lanes, one column per lane) is compiled for with ONE column group per workgroup
 #endif
 #ifndef RRX_SW_F32_WAVES
-#define RRX_SW_F32_WAVES 2    // waves per SIMD the fp32 geometry (16 x 4 lanes, one column per lane) is compiled for
+#define RRX_SW_F32_WAVES 2    // ... and with two (tools/ab_cases_f32_waves.txt)
 #endif
 
 #ifndef RRX_SW_TIMING
@@ -121,9 +109,10 @@ __device__ __forceinline__ TwoStream<F> two_stream(const F tau, const F ssa, con
 }
 
 
-// W = waves per column group: W = 1 keeps the whole column in one wavefront (8 level-lanes); W = 2 spreads the levels of
-// 8*V columns over 16 level-lanes in two adjacent wavefronts (half the per-lane state, so more resident waves per
-// SIMD); the four vertical scans then exchange each wave's total through LDS with one block barrier per scan.
+// W = waves per column group: W = 2 spreads the levels of 8*V columns over 16 level-lanes in two adjacent wavefronts (half the
+// per-lane state of a whole column in one wavefront, so more resident waves per SIMD; the one-wave form is retired: its layer
+// range, K <= 33 of 8 levels, lies inside this one's, K <= 17 of 16); the four vertical scans exchange each wave's total through
+// LDS with one block barrier per scan.
 // BB (broadband): the workgroup walks over ALL g-points of its columns and keeps the g-point sums of the three fluxes
 // on chip (up and dn in LDS, dir in registers), added in g-point order like sum_broadband does on stored per-g-point
 // fluxes, so the same bits; flux_up/dn/dir are then (ncol, nlev) arrays.
@@ -136,8 +125,8 @@ __device__ __forceinline__ TwoStream<F> two_stream(const F tau, const F ssa, con
 // the two-wave case of the same composition, kept as it was).
 // CLT = column lanes per wavefront (level lanes = 64 / CLT). 8 x 8 is the fp64 geometry (64-B rows per wave, two column groups per
 // workgroup share each 128-B line). Round 4, fp32: 16 x 4 lanes with ONE column per lane, four waves per column group and two groups
-// per workgroup -- the same nine cells per lane and the same 64-B rows as fp64, no scratch (the two-columns-per-lane form of rounds
-// 1-3 spilled 25-34 VGPRs): 3.70 -> 3.33 ms at C4 clear sky, 8.06 -> 7.5 ms all-sky at 32 768 columns. What was measured on the
+// per workgroup -- the same nine cells per lane and the same 64-B rows as fp64, no scratch (the two-columns-per-lane 8 x 8 form of
+// rounds 1-3, retired, spilled 25-34 VGPRs): 3.70 -> 3.33 ms at C4 clear sky, 8.06 -> 7.5 ms all-sky at 32 768 columns. What was measured on the
 // way (profiles/r04_issue_costs_fp32.txt, r04_fp32_geometry_ab.txt): packed v_pk_fma_f32 issues every 3.8 cycles against 2.0 for
 // v_fma_f32 at four waves per SIMD (5.7 against 3.5 at two), so two columns per lane on packed math buy at most a fifth of the
 // packable instructions; compiled for four waves per SIMD (128 VGPRs) this geometry spills 36-65 registers and is slower (4.44 /
@@ -152,7 +141,7 @@ __device__ __forceinline__ TwoStream<F> two_stream(const F tau, const F ssa, con
 // zero (rrx_sum_byband's order) into band slab b of flux_up/dn/dir, (ncol, nlev, nbnd) arrays; an empty band writes zeros.
 template<typename F, int V, int K, int W, bool BB = false, bool GZ = false, bool PRE = false, bool GS = false, int NW = (W > 2 ? 2*W : 4), int CLT = 8,
          bool BND = false>
-__global__ void __launch_bounds__(64*NW, (CLT == 16) ? ((NW == 4) ? RRX_SW_F32_WAVES1 : RRX_SW_F32_WAVES) : ((NW > 4) ? 1 : ((W == 2 && V*sizeof(F) <= 8) ? RRX_SW_MINWAVES2 : RRX_SW_MINWAVES)))
+__global__ void __launch_bounds__(64*NW, (CLT == 16) ? ((NW == 4) ? RRX_SW_F32_WAVES1 : RRX_SW_F32_WAVES) : ((NW > 4) ? 1 : 2))
 sw_2stream_scan_kernel(
         const int ncol, const int nlay, const int ngpt, const int top_at_1,
         const F* __restrict__ tau, const F* __restrict__ ssa, const F* __restrict__ g, const F* __restrict__ mu0,
@@ -161,13 +150,14 @@ sw_2stream_scan_kernel(
         F* __restrict__ flux_up, F* __restrict__ flux_dn, F* __restrict__ flux_dir, const int sync_waves, const int gper,
         const int* __restrict__ band_lims)
 {
+    static_assert(W == 2 || W == 4 || W == 8);
     static_assert(!BND || (BB && !GS), "the by-band form is a broadband form with its own g-point split");
     constexpr int CL = CLT, LL = 64/CLT;              // shadow the default geometry
     // per-thread private LDS columns (dynamic register indexing is not needed: j is a compile-time constant, but
     // two of the six per-layer arrays live here so that the kernel fits 2 waves per SIMD)
     __shared__ F lds_alb[K*V][64*NW];
     __shared__ F lds_dir[K*V][64*NW];
-    __shared__ F xch[(W >= 2) ? 8*V : 1][NW][CL];   // wave totals of the scans (one slot per scan component)
+    __shared__ F xch[8*V][NW][CL];   // wave totals of the scans (one slot per scan component)
     __shared__ F lds_acc_up[BB ? K*V : 1][64*NW];
     __shared__ F lds_acc_dn[BB ? K*V : 1][64*NW];
 
@@ -176,14 +166,13 @@ sw_2stream_scan_kernel(
     const int wave = threadIdx.x >> 6;
     const int cl = lane & (CL-1);
     const int ll = lane / CL;
-    const int h = (W >= 2) ? (wave % W) : 0;          // which part of the column this wave holds (0 = TOA side)
+    const int h = wave % W;                           // which part of the column this wave holds (0 = TOA side)
     [[maybe_unused]] const int w0 = wave - h;         // first wave of the column group
     // (a workgroup whose row segment is half a 128-B line: the other half belongs to the next workgroup -- rrx::xcd_contiguous)
-    const int bx = (BB && (NW/W)*CL*V*sizeof(F) < 128 && RRX_SW_XCD_MAP) ? xcd_contiguous(blockIdx.x, gridDim.x) : int(blockIdx.x);
+    const int bx = (BB && (NW/W)*CL*V*sizeof(F) < 128) ? xcd_contiguous(blockIdx.x, gridDim.x) : int(blockIdx.x);
     const int wave_col0 = (bx*(NW/W) + wave/W) * (CL*V);
-    if constexpr (W == 1) { if (wave_col0 >= ncol) return; }
 
-    // W == 2: every wave stays alive until the last barrier; lanes without a column compute on a clamped one
+    // every wave stays alive until the last barrier; lanes without a column compute on a clamped one
     int icol = wave_col0 + cl*V;
     const bool active = icol < ncol;
     if (!active) icol = (wave_col0 < ncol) ? wave_col0 : 0;
@@ -220,7 +209,7 @@ sw_2stream_scan_kernel(
     Vec<F,V> nt[PRE ? K : 1], nw[PRE ? K : 1], ng[(PRE && !GZ) ? K : 1], n_inc, n_adir, n_adif;
     if constexpr (PRE)
     {
-        static_assert(BB && W >= 2, "the pipelined form is the fused broadband kernel");
+        static_assert(BB, "the pipelined form is the fused broadband kernel");
         static_assert(GZ || sizeof(F) == 4, "fp64 with a g array: 27 prefetched doubles per lane spill (5.8 -> 7.2 ms, round 3)");
         if (!BND || g_begin < g_end) {                      // (an empty band prefetches nothing: g_begin may be ngpt)
         const F* __restrict__ tau_0 = tau + size_t(g_begin)*ncl*nlay;
@@ -375,53 +364,50 @@ sw_2stream_scan_kernel(
         F pe = shfl(pr, lane - CL);
         if (ll == 0) pe = F(1.);
         F ptot = shfl(pr, (LL-1)*CL + cl);
-        if constexpr (W >= 2)
+        if (ll == LL-1) xch[8*v+0][wave][cl] = pr;
+        RRX_SW_T(1)
+        __syncthreads();
+        RRX_SW_T(6)
+        if constexpr (PRE)
         {
-            if (ll == LL-1) xch[8*v+0][wave][cl] = pr;
-            RRX_SW_T(1)
-            __syncthreads();
-            RRX_SW_T(6)
-            if constexpr (PRE)
+            if (v == 0)
             {
-                if (v == 0)
-                {
-                    // every wave of the workgroup is here: the two waves that share each 128-B line ask for it together
-                    __builtin_amdgcn_sched_barrier(0);
-                    const int gn = min(igpt + 1, g_end - 1);          // (last iteration: a harmless re-read)
-                    const F* __restrict__ tau_n = tau + size_t(gn)*ncl*nlay;
-                    const F* __restrict__ ssa_n = ssa + size_t(gn)*ncl*nlay;
-                    #pragma unroll
-                    for (int j=0; j<K; ++j) { const unsigned o = off_of(j); nt[j] = load_cols<F,V>(tau_n + o); nw[j] = load_cols<F,V>(ssa_n + o); }
-                    if constexpr (!GZ)
-                    {
-                        const F* __restrict__ g_n = g + size_t(gn)*ncl*nlay;
-                        #pragma unroll
-                        for (int j=0; j<K; ++j) ng[j] = load_cols<F,V>(g_n + off_of(j));
-                    }
-                    const size_t sn = size_t(gn)*ncl + icol;
-                    n_inc = load_cols<F,V>(inc_flux_dir + sn); n_adir = load_cols<F,V>(sfc_alb_dir + sn); n_adif = load_cols<F,V>(sfc_alb_dif + sn);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            if constexpr (W == 2)
-            {
-                const F other = xch[8*v+0][wave^1][cl];
-                if (h == 1) pe *= other;
-                ptot *= other;
-            }
-            else
-            {
-                F above = F(1.), all = F(1.);
+                // every wave of the workgroup is here: the two waves that share each 128-B line ask for it together
+                __builtin_amdgcn_sched_barrier(0);
+                const int gn = min(igpt + 1, g_end - 1);          // (last iteration: a harmless re-read)
+                const F* __restrict__ tau_n = tau + size_t(gn)*ncl*nlay;
+                const F* __restrict__ ssa_n = ssa + size_t(gn)*ncl*nlay;
                 #pragma unroll
-                for (int w=0; w<W; ++w)
+                for (int j=0; j<K; ++j) { const unsigned o = off_of(j); nt[j] = load_cols<F,V>(tau_n + o); nw[j] = load_cols<F,V>(ssa_n + o); }
+                if constexpr (!GZ)
                 {
-                    const F o = xch[8*v+0][w0+w][cl];
-                    if (w < h) above *= o;
-                    all *= o;
+                    const F* __restrict__ g_n = g + size_t(gn)*ncl*nlay;
+                    #pragma unroll
+                    for (int j=0; j<K; ++j) ng[j] = load_cols<F,V>(g_n + off_of(j));
                 }
-                pe *= above;
-                ptot = all;
+                const size_t sn = size_t(gn)*ncl + icol;
+                n_inc = load_cols<F,V>(inc_flux_dir + sn); n_adir = load_cols<F,V>(sfc_alb_dir + sn); n_adif = load_cols<F,V>(sfc_alb_dif + sn);
+                __builtin_amdgcn_sched_barrier(0);
             }
+        }
+        if constexpr (W == 2)
+        {
+            const F other = xch[8*v+0][wave^1][cl];
+            if (h == 1) pe *= other;
+            ptot *= other;
+        }
+        else
+        {
+            F above = F(1.), all = F(1.);
+            #pragma unroll
+            for (int w=0; w<W; ++w)
+            {
+                const F o = xch[8*v+0][w0+w][cl];
+                if (w < h) above *= o;
+                all *= o;
+            }
+            pe *= above;
+            ptot = all;
         }
         const F dir_top = inc_dir.v[v] * mu.v[v];
         dir_in[v] = dir_top * pe;
@@ -761,143 +747,130 @@ __global__ void apply_BC_kernel(const int ncol, const int nlay, const int ngpt, 
     flux_dn[o] = v;
 }
 
-template<typename F, int V, int W>
-bool launch_scan(hipStream_t st,
-        const int ncol, const int nlay, const int ngpt, const int top_at_1,
-        const F* tau, const F* ssa, const F* g, const F* mu0, const F* sfc_alb_dir, const F* sfc_alb_dif,
-        const F* inc_flux_dir, const F* inc_flux_dif, F* flux_up, F* flux_dn, F* flux_dir)
+// the arguments of the scan kernels, the same for every tiling that an entry tries
+template<typename F>
+struct SwArgs
 {
-    const dim3 grid(ceil_div(ncol, (4/W)*CL*V), ngpt);
-    const int need = ceil_div(nlay+1, LL*W);
-#define RRX_SW_K(KK) if (need <= KK) { sw_2stream_scan_kernel<F,V,KK,W><<<grid, 256, 0, st>>>( \
-        ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, inc_flux_dif, \
-        flux_up, flux_dn, flux_dir, tuning().sync_waves, 1, nullptr); return true; }
-    if constexpr (W == 1) { RRX_SW_K(4) RRX_SW_K(8) RRX_SW_K(12) RRX_SW_K(18) RRX_SW_K(24) RRX_SW_K(33) }
-    else                  { RRX_SW_K(2) RRX_SW_K(4) RRX_SW_K(6)  RRX_SW_K(9)  RRX_SW_K(12) RRX_SW_K(17) }
-#undef RRX_SW_K
-    return false;
+    int ncol, nlay, ngpt, top_at_1;
+    const F *tau, *ssa, *g /* or null: asymmetry identically zero */, *mu0, *sfc_alb_dir, *sfc_alb_dif, *inc_flux_dir, *inc_flux_dif /* or null */;
+    F *flux_up, *flux_dn, *flux_dir;
+    const int* band_lims; int nbnd;             // by-band form: flux_* are (ncol, nlev, nbnd) band sums
+};
+
+// the per-g-point kernel (two waves per column group, two groups per workgroup); false when the columns are taller than its
+// largest K (the caller takes the serial kernel)
+template<typename F, int V>
+bool launch_scan(hipStream_t st, const SwArgs<F>& a)
+{
+    const dim3 grid(ceil_div(a.ncol, 2*CL*V), a.ngpt);
+    const int sync_waves = tuning().sync_waves;
+    return with_k<2, 4, 6, 9, 12, 17>(ceil_div(a.nlay+1, 2*LL), [&](auto kk)
+    {
+        sw_2stream_scan_kernel<F,V,decltype(kk)::value,2><<<grid, 256, 0, st>>>(
+            a.ncol, a.nlay, a.ngpt, a.top_at_1, a.tau, a.ssa, a.g, a.mu0, a.sfc_alb_dir, a.sfc_alb_dif, a.inc_flux_dir, a.inc_flux_dif,
+            a.flux_up, a.flux_dn, a.flux_dir, sync_waves, 1, nullptr);
+    });
 }
 
-// Fused broadband form. W waves per column group, CLT column lanes per wave (two column groups per workgroup); false when the
-// columns are taller than the form's largest K (the caller tries the next form).
-template<typename F, int V, int W = 2, int CLT = 8, int NWG = (W > 2 ? 2*W : 4)>
-bool launch_scan_bb(hipStream_t st,
-        const int ncol, const int nlay, const int ngpt, const int top_at_1,
-        const F* tau, const F* ssa, const F* g, const F* mu0, const F* sfc_alb_dir, const F* sfc_alb_dif,
-        const F* inc_flux_dir, const F* inc_flux_dif, F* flux_up, F* flux_dn, F* flux_dir,
-        const int* band_lims = nullptr, const int nbnd = 0 /* by-band form: flux_* are (ncol, nlev, nbnd) band sums */)
+// One tiling of the fused broadband form: W waves per column group, CLT column lanes per wave, NW waves per workgroup (NW/W column
+// groups); false when the columns are taller than the tiling's largest K (the caller tries the next one).
+template<typename F, int V, int W, int CLT, int NW>
+bool launch_scan_bb(hipStream_t st, const SwArgs<F>& a)
 {
-    constexpr int NW = NWG;                               // wavefronts per workgroup: two column groups (one where NWG == W)
-    constexpr int KMAX = (CLT == 16) ? 12 : (W > 2 ? 9 : 12);       // (8 x 8 lanes, W = 4: nine layers per lane fill the LDS of a CU)
-    const int groups = ceil_div(ncol, (NW/W)*CLT*V);
-    const int need = ceil_div(nlay+1, (64/CLT)*W);
-    if (need > KMAX) return false;
-    // pipelined loads: fp64 without g array only (with it 27 prefetched doubles spill); fp32 in the one-column-per-lane geometry
-    // (two columns per lane: 140 B of scratch per lane, 4.00 against 3.63 ms at C4)
-    const bool pre = tuning().sw_variant != 8 && size_t(ncol)*nlay < (size_t(1) << 31)
-                     && (sizeof(F) == 8 ? g == nullptr : (V == 1 && CLT == 16));
-    const size_t nlevcol = size_t(ncol)*(nlay+1);
-    const int sync_waves = tuning().sync_waves;
-#define RRX_SW_K(KK) if (need <= KK) { launch(std::integral_constant<int,KK>{}); break; }
-#define RRX_SW_KS \
-    do \
-    { \
-        if constexpr (CLT == 16) { RRX_SW_K(2) RRX_SW_K(4) RRX_SW_K(6) RRX_SW_K(9) RRX_SW_K(12) } \
-        else if constexpr (W == 2) { RRX_SW_K(2) RRX_SW_K(4) RRX_SW_K(6) RRX_SW_K(9) RRX_SW_K(12) } \
-        else if constexpr (W == 8) { RRX_SW_K(5) RRX_SW_K(7) RRX_SW_K(9) }      /* (288 ... 319 / 447 / 575 layers) */ \
-        else { RRX_SW_K(9) } \
-    } while (false);
-    if (band_lims != nullptr)
+    const int groups = ceil_div(a.ncol, (NW/W)*CLT*V);
+    const int need = ceil_div(a.nlay+1, (64/CLT)*W);
+    auto with_tiling_k = [&](auto launch)      // the layers per lane of this tiling
     {
-        // one band per workgroup (grid.y = band): no store inside the g-point loop, no partial arrays, no allocation. Not the fp32
-        // two-column 8 x 8 form, which only variant 9 reaches (its by-band twin at K = 12 puts one more VGPR into AGPRs): the four-wave
-        // form takes those columns.
-        if constexpr (sizeof(F) == 4 && V == 2 && W == 2) return false;
-        const dim3 grid(groups, nbnd);
-        auto launch = [&](auto kk)
+        if constexpr (CLT == 16 && NW == 4) return with_k<2, 4, 6, 9>(need, launch);      // (twelve spill at 168 VGPRs)
+        else if constexpr (CLT == 16) return with_k<12>(need, launch);                    // (up to nine: the one-group form's)
+        else if constexpr (W == 2) return with_k<2, 4, 6, 9, 12>(need, launch);
+        else if constexpr (W == 8) return with_k<5, 7, 9>(need, launch);                  // (288 ... 319 / 447 / 575 layers)
+        else return with_k<9>(need, launch);                                              // (8 x 8 lanes, W = 4: nine layers per lane fill the LDS of a CU)
+    };
+    // launch(GZ, PRE). GZ: no g array. PRE: the pipelined loads, where that form exists -- fp64 without g array only (with it 27
+    // prefetched doubles spill), fp32 in the one-column-per-lane geometry (two columns per lane: 140 B of scratch per lane, 4.00
+    // against 3.63 ms at C4) -- and 32-bit element offsets reach through a g-point slab. The not-pipelined kernels are therefore
+    // product code (ncol*nlay >= 2^31; fp64 with a g array); the run-time switch that forced them for A/B runs is retired.
+    auto with_gz_pre = [&](auto launch)
+    {
+        with_flag(a.g == nullptr, [&](auto gz)
         {
-            constexpr int KK = decltype(kk)::value;
-            with_flag(g == nullptr, [&](auto gz) { with_flag(pre, [&](auto pr)
-            {
-                constexpr bool GZ = decltype(gz)::value;
-                constexpr bool PRE = decltype(pr)::value && (sizeof(F) == 8 ? GZ : (V == 1 && CLT == 16));
-                sw_2stream_scan_kernel<F,V,KK,W,true,GZ,PRE,false,NW,CLT,true><<<grid, 64*NW, 0, st>>>(
-                    ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, inc_flux_dif,
-                    flux_up, flux_dn, flux_dir, sync_waves, 0, band_lims);
-            }); });
-        };
-        RRX_SW_KS
-        return true;
+            if constexpr (sizeof(F) == 8 ? decltype(gz)::value : (V == 1 && CLT == 16))
+                with_flag(size_t(a.ncol)*a.nlay < (size_t(1) << 31), [&](auto pre) { launch(gz, pre); });
+            else
+                launch(gz, std::false_type{});
+        });
+    };
+    const size_t nlevcol = size_t(a.ncol)*(a.nlay+1);
+    const int sync_waves = tuning().sync_waves;
+    if (a.band_lims != nullptr)
+    {
+        // one band per workgroup (grid.y = band): no store inside the g-point loop, no partial arrays, no allocation
+        const dim3 grid(groups, a.nbnd);
+        return with_tiling_k([&](auto kk) { with_gz_pre([&](auto gz, auto pre)
+        {
+            sw_2stream_scan_kernel<F,V,decltype(kk)::value,W,true,decltype(gz)::value,decltype(pre)::value,false,NW,CLT,true><<<grid, 64*NW, 0, st>>>(
+                a.ncol, a.nlay, a.ngpt, a.top_at_1, a.tau, a.ssa, a.g, a.mu0, a.sfc_alb_dir, a.sfc_alb_dif, a.inc_flux_dir, a.inc_flux_dif,
+                a.flux_up, a.flux_dn, a.flux_dir, sync_waves, 0, a.band_lims);
+        }); });
     }
     // few column groups: the g-point loop is split over grid.y, partial sums added in range order afterwards
-    const int gper = ceil_div(ngpt, broadband_gsplit(groups, ngpt, (NW > 4) ? 256 : ((CLT == 16) ? 256*RRX_SW_F32_WAVES1 : 512)));      // (one or two workgroups per CU)
-    const int nsplit = ceil_div(ngpt, gper);               // no empty range: every workgroup's first g-point exists (it is prefetched)
+    const int gper = ceil_div(a.ngpt, broadband_gsplit(groups, a.ngpt, (NW > 4) ? 256 : ((CLT == 16) ? 256*RRX_SW_F32_WAVES1 : 512)));      // (one or two workgroups per CU)
+    const int nsplit = ceil_div(a.ngpt, gper);             // no empty range: every workgroup's first g-point exists (it is prefetched)
     StreamScratch scratch(st);
-    F* up = flux_up; F* dn = flux_dn; F* dr = flux_dir;
-    if (nsplit > 1) { up = scratch.get<F>(3*nsplit*nlevcol); dn = up + nsplit*nlevcol; dr = dn + nsplit*nlevcol; }
+    F* up = a.flux_up; F* dn = a.flux_dn; F* dr = a.flux_dir;
     const dim3 grid(groups, nsplit);
-    auto launch = [&](auto kk)
+    const bool fits = with_tiling_k([&](auto kk)
     {
-        constexpr int KK = decltype(kk)::value;
-        with_flag(g == nullptr, [&](auto gz) { with_flag(pre, [&](auto pr) { with_flag(nsplit > 1, [&](auto gs)
+        if (nsplit > 1) { up = scratch.get<F>(3*nsplit*nlevcol); dn = up + nsplit*nlevcol; dr = dn + nsplit*nlevcol; }
+        with_gz_pre([&](auto gz, auto pre) { with_flag(nsplit > 1, [&](auto gs)
         {
-            constexpr bool GZ = decltype(gz)::value, GS = decltype(gs)::value;
-            // (the pipelined form exists where launch_scan_bb may pick it: fp64 without g array, fp32 with one column per lane)
-            constexpr bool PRE = decltype(pr)::value && (sizeof(F) == 8 ? GZ : (V == 1 && CLT == 16));
-            sw_2stream_scan_kernel<F,V,KK,W,true,GZ,PRE,GS,NW,CLT><<<grid, 64*NW, 0, st>>>(
-                ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, inc_flux_dif,
+            sw_2stream_scan_kernel<F,V,decltype(kk)::value,W,true,decltype(gz)::value,decltype(pre)::value,decltype(gs)::value,NW,CLT><<<grid, 64*NW, 0, st>>>(
+                a.ncol, a.nlay, a.ngpt, a.top_at_1, a.tau, a.ssa, a.g, a.mu0, a.sfc_alb_dir, a.sfc_alb_dif, a.inc_flux_dir, a.inc_flux_dif,
                 up, dn, dr, sync_waves, gper, nullptr);
-        }); }); });
-    };
-    RRX_SW_KS
-#undef RRX_SW_KS
-#undef RRX_SW_K
-    if (nsplit > 1)      // (up, dn, dr lie behind each other in the scratch block)
-        sum_ranges_kernel<F,3><<<dim3(ceil_div(nlevcol, 256), 3), 256, 0, st>>>(nlevcol, nsplit, up, flux_up, flux_dn, flux_dir);
-    return true;
+        }); });
+    });
+    if (fits && nsplit > 1)      // (up, dn, dr lie behind each other in the scratch block)
+        sum_ranges_kernel<F,3><<<dim3(ceil_div(nlevcol, 256), 3), 256, 0, st>>>(nlevcol, nsplit, up, a.flux_up, a.flux_dn, a.flux_dir);
+    return fits;
 }
 
-// the fused broadband kernels (launch_scan_bb) in the order of preference; false when no form takes the shape. band_lims != null:
-// the by-band form, flux_* are then (ncol, nlev, nbnd) band sums
-template<typename F>
-bool sw_fused_broadband(
-        hipStream_t st, const int ncol, const int nlay, const int ngpt, const Bool top_at_1,
-        const F* tau, const F* ssa, const F* g, const F* mu0, const F* sfc_alb_dir, const F* sfc_alb_dif, const F* inc_flux_dir,
-        const F* dif, F* flux_up_loc, F* flux_dn_loc, F* flux_dir_loc, const int* band_lims = nullptr, const int nbnd = 0)
+// the one-kernel broadband forms serve every variant but 1 (serial kernel) and 7 (per-g-point fluxes in a workspace + sum)
+bool sw_fused_allowed()
 {
-    const int g_sw_variant = tuning().sw_variant;
-    constexpr int VBB = (sizeof(F) == 8) ? 1 : 2;
-    // (variant 8: fused broadband form without the pipelined loads, for A/B runs)
-    if (g_sw_variant == 1 || g_sw_variant == 7 || (ncol % VBB != 0 && sizeof(F) != 4)) return false;
-    // fp32: one column per lane, 16 x 4 lanes, four waves per column group (up to 191 layers); variant 9 = the two-columns-
-    // per-lane form of rounds 1-3 for A/B runs
-    if constexpr (sizeof(F) == 4)
+    const int v = tuning().sw_variant;
+    return v != 1 && v != 7;
+}
+
+// the fused broadband kernels (launch_scan_bb) in the order of preference; false when no form takes the shape. a.band_lims != null:
+// the by-band form, a.flux_* are then (ncol, nlev, nbnd) band sums
+template<typename F>
+bool sw_fused_broadband(hipStream_t st, const SwArgs<F>& a)
+{
+    if (!sw_fused_allowed()) return false;
+    if constexpr (sizeof(F) == 8)
     {
-        // up to 143 layers (nine per lane): one column group per workgroup at three waves per SIMD; 144-191 (twelve per lane, which
-        // spills at 168 VGPRs): two groups per workgroup at two waves per SIMD
-        if (g_sw_variant != 9 && ceil_div(nlay+1, 16) <= 9 &&
-            launch_scan_bb<F,1,4,16,RRX_SW_F32_NW>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif,
-                                                   inc_flux_dir, dif, flux_up_loc, flux_dn_loc, flux_dir_loc, band_lims, nbnd))
-            return true;
-        if (g_sw_variant != 9 &&
-            launch_scan_bb<F,1,4,16>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif,
-                                     inc_flux_dir, dif, flux_up_loc, flux_dn_loc, flux_dir_loc, band_lims, nbnd))
-            return true;
+        // up to 191 layers: two waves of 8 x 8 lanes per column group, two groups per workgroup
+        if (launch_scan_bb<F,1,2,8,4>(st, a)) return true;
+        // 192 ... 287 layers: four wavefronts per column group
+        if (launch_scan_bb<F,1,4,8,8>(st, a)) return true;
+        // 288 ... 575 layers (round 4): eight wavefronts on ONE column group per workgroup (64 levels per wave at nine layers per lane;
+        // the row segments are 64 B with no partner group in the workgroup: twice the L2 fetches, on a kernel bound by fp64 issue)
+        return launch_scan_bb<F,1,8,8,8>(st, a);
     }
-    if (ncol % VBB == 0 &&
-        launch_scan_bb<F,VBB>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif,
-                              inc_flux_dir, dif, flux_up_loc, flux_dn_loc, flux_dir_loc, band_lims, nbnd))
-        return true;
-    // 192 ... 287 layers: four wavefronts per column group
-    if (ncol % VBB == 0 &&
-        launch_scan_bb<F,VBB,4>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif,
-                                inc_flux_dir, dif, flux_up_loc, flux_dn_loc, flux_dir_loc, band_lims, nbnd))
-        return true;
-    // 288 ... 575 layers (round 4): eight wavefronts on ONE column group per workgroup (64 levels per wave at nine layers per lane;
-    // the row segments are 64 B with no partner group in the workgroup: twice the L2 fetches, on a kernel bound by fp64 issue)
-    return ncol % VBB == 0 &&
-        launch_scan_bb<F,VBB,8,8,8>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif,
-                                    inc_flux_dir, dif, flux_up_loc, flux_dn_loc, flux_dir_loc, band_lims, nbnd);
+    else
+    {
+        // one column per lane, 16 x 4 lanes, four waves per column group. Up to 143 layers (nine per lane): ONE column group per
+        // workgroup at three waves per SIMD; 144-191 (twelve per lane): two groups per workgroup at two waves per SIMD (that form below
+        // 144 layers too: 3.1 / 7.1 ms at C4 / all-sky at 32 768 columns against 2.03 / 4.8, retired). The two-columns-per-lane 8 x 8
+        // form of rounds 1-3 covered the same 191 layers (3.70 against 3.33 ms when it was replaced, see the kernel's note) and is retired.
+        if (launch_scan_bb<F,1,4,16,4>(st, a)) return true;
+        if (launch_scan_bb<F,1,4,16,8>(st, a)) return true;
+        // taller columns: two columns per lane on 8 x 8 lanes, four waves per column group (192 ... 287 layers) or eight (288 ... 575), as fp64
+        if (a.ncol % 2 != 0) return false;
+        if (launch_scan_bb<F,2,4,8,8>(st, a)) return true;
+        return launch_scan_bb<F,2,8,8,8>(st, a);
+    }
 }
 
 template<typename F>
@@ -913,8 +886,10 @@ int sw_solver_2stream_impl(
     RRX_TRY
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (ncol <= 0 || nlay <= 0 || ngpt <= 0) throw std::runtime_error("empty problem");
-    const F* dif = has_dif_bc ? inc_flux_dif : nullptr;
-    const int g_sw_variant = tuning().sw_variant;
+    // (the fused form's arguments; the per-g-point route below redirects g and the outputs)
+    SwArgs<F> a{ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, has_dif_bc ? inc_flux_dif : nullptr,
+                flux_up_loc, flux_dn_loc, flux_dir_loc, nullptr, 0};
+    const bool serial = tuning().sw_variant == 1;
     const bool byband = band_lims != nullptr;
 
     // broadband mode, fused form (see the kernel's BB note): one workgroup per column group sums all g-points in order when the
@@ -923,9 +898,7 @@ int sw_solver_2stream_impl(
     {
         if (flux_up_loc == nullptr || flux_dn_loc == nullptr || flux_dir_loc == nullptr)
             throw std::runtime_error("do_broadband needs flux_*_loc");
-        if (sw_fused_broadband<F>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, dif,
-                                  flux_up_loc, flux_dn_loc, flux_dir_loc))
-            return 0;
+        if (sw_fused_broadband<F>(st, a)) return 0;
     }
 
     // g == nullptr (asymmetry identically zero) is native to the fused broadband kernels only: the other forms read zeros
@@ -937,57 +910,48 @@ int sw_solver_2stream_impl(
     const size_t w_serial = 5*size_t(ncol)*nlay*ngpt + 2*nlevcol*ngpt;
     // (one lease per call: the serial kernel's part is asked for up front whenever it could be needed)
     WorkspaceLease lease(st);
-    const bool may_go_serial = g_sw_variant == 1 || (g_sw_variant != 2 ? ceil_div(nlay+1, LL*2) > 17 : ceil_div(nlay+1, LL) > 33);   // (largest K of launch_scan)
+    const bool may_go_serial = serial || ceil_div(nlay+1, LL*2) > 17;      // (largest K of launch_scan)
     F* big = (w_g + w_flux > 0 || may_go_serial) ? lease.get<F>(w_g + w_flux + (may_go_serial ? w_serial : 0)) : nullptr;
     if (g == nullptr)
     {
         if (hipMemsetAsync(big, 0, w_g*sizeof(F), st) != hipSuccess) throw std::runtime_error("workspace memset failed");
-        g = big;
+        a.g = big;
     }
 
-    F* up = flux_up; F* dn = flux_dn; F* dr = flux_dir;
+    a.flux_up = flux_up; a.flux_dn = flux_dn; a.flux_dir = flux_dir;
     if (gpt_ws)
     {
         if (flux_up_loc == nullptr || flux_dn_loc == nullptr || flux_dir_loc == nullptr)
             throw std::runtime_error("do_broadband needs flux_*_loc");
         F* ws = big + w_g;
-        up = ws; dn = ws + nlevcol*ngpt; dr = ws + 2*nlevcol*ngpt;
+        a.flux_up = ws; a.flux_dn = ws + nlevcol*ngpt; a.flux_dir = ws + 2*nlevcol*ngpt;
     }
 
-    // g_sw_variant: 0 = default (two-wave level split), 1 = serial fallback, 2 = one wave per column group, 3 = two waves
+    // the scan kernel (fp32: two columns per lane where the column count is even), the serial kernel for taller columns and under variant 1
     bool done = false;
-    if (g_sw_variant != 1)
+    if (!serial)
     {
-#define RRX_SW_ARGS st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, dif, up, dn, dr
-        const bool two = (g_sw_variant != 2);
-        if constexpr (sizeof(F) == 4)
-        {
-            if (g_sw_variant == 4 && ncol % 4 == 0) done = launch_scan<F,4,2>(RRX_SW_ARGS);
-            else if (ncol % 2 == 0)
-                done = two ? launch_scan<F,2,2>(RRX_SW_ARGS) : launch_scan<F,2,1>(RRX_SW_ARGS);
-        }
-        if (!done)
-            done = two ? launch_scan<F,1,2>(RRX_SW_ARGS) : launch_scan<F,1,1>(RRX_SW_ARGS);
-#undef RRX_SW_ARGS
+        if constexpr (sizeof(F) == 4) { if (ncol % 2 == 0) done = launch_scan<F,2>(st, a); }
+        if (!done) done = launch_scan<F,1>(st, a);
     }
     if (!done)
     {
         if (!may_go_serial) throw std::runtime_error("internal: no tiling for this shape and no workspace for the serial form");
         F* ws2 = big + w_g + w_flux;
         const dim3 grid(ceil_div(ncol, 256), ngpt);
-        sw_2stream_serial_kernel<F><<<grid, 256, 0, st>>>(ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0,
-                sfc_alb_dir, sfc_alb_dif, inc_flux_dir, dif, up, dn, dr, ws2);
+        sw_2stream_serial_kernel<F><<<grid, 256, 0, st>>>(ncol, nlay, ngpt, top_at_1, tau, ssa, a.g, mu0,
+                sfc_alb_dir, sfc_alb_dif, inc_flux_dir, a.inc_flux_dif, a.flux_up, a.flux_dn, a.flux_dir, ws2);
     }
 
-    if (byband)      // (up, dn, dr lie behind each other in the workspace)
-        sum_bands_kernel<F><<<dim3(ceil_div(nlevcol, 256), nbnd, 3), 256, 0, st>>>(nlevcol, ngpt, band_lims, up, flux_up_loc, flux_dn_loc,
+    if (byband)      // (the three per-g-point arrays lie behind each other in the workspace)
+        sum_bands_kernel<F><<<dim3(ceil_div(nlevcol, 256), nbnd, 3), 256, 0, st>>>(nlevcol, ngpt, band_lims, a.flux_up, flux_up_loc, flux_dn_loc,
                                                                                   flux_dir_loc);
     else if (do_broadband)
     {
         const int nb = ceil_div(nlevcol, 256);
-        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, up, flux_up_loc);
-        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, dn, flux_dn_loc);
-        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, dr, flux_dir_loc);
+        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, a.flux_up, flux_up_loc);
+        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, a.flux_dn, flux_dn_loc);
+        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, a.flux_dir, flux_dir_loc);
     }
     RRX_CATCH("rrx_sw_solver_2stream")
 }
@@ -1005,9 +969,9 @@ int sw_solver_2stream_byband_impl(
     hipStream_t st = static_cast<hipStream_t>(stream);
     check_byband_args(ncol, nlay, ngpt, nbnd, band_lims);
     if (bnd_up == nullptr || bnd_dn == nullptr || bnd_dir == nullptr) throw std::runtime_error("band flux outputs missing");
-    const F* dif = has_dif_bc ? inc_flux_dif : nullptr;
-    if (!sw_fused_broadband<F>(st, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, dif,
-                               bnd_up, bnd_dn, bnd_dir, band_lims, nbnd))
+    const SwArgs<F> a{ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, has_dif_bc ? inc_flux_dif : nullptr,
+                      bnd_up, bnd_dn, bnd_dir, band_lims, nbnd};
+    if (!sw_fused_broadband<F>(st, a))
     {
         if (sw_solver_2stream_impl<F>(ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir,
                                       (F*)nullptr, (F*)nullptr, (F*)nullptr, has_dif_bc, inc_flux_dif, Bool(0), bnd_up, bnd_dn, bnd_dir,
@@ -1031,7 +995,17 @@ int apply_BC_impl(int ncol, int nlay, int ngpt, Bool top_at_1, const F* inc, con
 
 extern "C"
 {
-int rrx_set_sw_variant(int v) { rrx::tuning().sw_variant = v; return 0; }
+int rrx_set_sw_variant(int v)
+{
+    if (v != 0 && v != 1 && v != 7)
+    {
+        rrx::set_error("rrx_set_sw_variant: " + std::to_string(v) + " is not an SW variant; accepted: 0 (default), 1 (serial kernel), "
+                       "7 (no one-kernel broadband form)");
+        return 1;
+    }
+    rrx::tuning().sw_variant = v;
+    return 0;
+}
 #if RRX_SW_TIMING
 // diagnostic build only: phase clocks per wavefront of a workgroup (out[16][8]) summed over the workgroups since the last call (two-stream, direct beam, albedo, source, down scan,
 // final replay, barrier waits, loop top), then reset

@@ -99,3 +99,20 @@ def test_lw_variant_switch_accepts_only_live_values():
             assert "rrx_set_lw_variant" in msg and "15" in msg, msg
     finally:
         assert lib.rrx_set_lw_variant(0) == 0
+
+
+def test_sw_variant_switch_accepts_only_live_values():
+    """rrx_set_sw_variant: the default and the two fallback routes, everything else rejected with a message, no GPU needed."""
+    if not os.path.exists(LIB):
+        pytest.fail(f"{LIB} not built: run __graft_entry__.build()")
+    lib = ctypes.CDLL(LIB)
+    lib.rrx_last_error.restype = ctypes.c_char_p
+    try:
+        for v in (0, 1, 7):
+            assert lib.rrx_set_sw_variant(v) == 0, v
+        for v in (2, 4, 8, 9, 16):              # retired / never existed
+            assert lib.rrx_set_sw_variant(v) != 0, v
+            msg = lib.rrx_last_error().decode()
+            assert "rrx_set_sw_variant" in msg and all(f"{ok} (" in msg for ok in (0, 1, 7)), msg
+    finally:
+        assert lib.rrx_set_sw_variant(0) == 0

@@ -55,13 +55,14 @@ def test_fp32_broadband_solvers_one_column_per_lane(ncol, nlay, top_at_1, with_g
 
 
 def test_fp32_sw_geometries_agree(hip_f32):
-    """The two fp32 SW tilings (one column per lane, default; two columns per lane, variant 9) on the same inputs."""
+    """The two fp32 SW geometries on the same inputs: 16 x 4 lanes with one column per lane (the fused form, default) and 8 x 8 lanes
+    with two columns per lane (variant 7 on an even column count: the per-g-point kernel, its g-points added in the same order)."""
     rng = np.random.default_rng(5)
     ngpt, nlay, ncol = 5, 140, 64
     tau, ssa, g, _, _, e2, mu0 = _random_columns(rng, ngpt, nlay, ncol)
     be = hip_f32; up = be.asarray
     res = []
-    for v in (0, 9):
+    for v in (0, 7):
         be.set_variant(sw=v)
         try:
             s = be.sw_solver_2stream(False, up(tau), up(ssa), up(g), up(mu0), up(e2*.5), up(e2*.4), up(e2*3), do_broadband=True)
@@ -69,7 +70,7 @@ def test_fp32_sw_geometries_agree(hip_f32):
             be.set_variant(sw=0)
         res.append([be.to_numpy(s[k]) for k in ("flux_up", "flux_dn", "flux_dir")])
     for a, b in zip(*res):
-        assert cases.rel_err(a, b, floor=1e-2) <= 5e-6          # (observed 6e-7)
+        assert cases.rel_err(a, b, floor=1e-2) <= 5e-6          # (observed 6.1e-7, the figure of the retired fused two-column form)
 
 
 def test_window_tables_follow_the_contents_not_the_pointers(hip_f64, oracle_f64):

@@ -1,4 +1,4 @@
-# run bench.py for a list of --sw-variant / --lw-variant values on the GPU box: bash tools/ab_variants.sh sw 0 11 12 ...
+# run bench.py for a list of --sw-variant / --lw-variant values on the GPU box: bash tools/ab_variants.sh sw 0 7 1
 kind=$1; shift
 mkdir -p ${LOGDIR:-logs}
 for v in "$@"; do
