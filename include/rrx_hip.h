@@ -87,6 +87,11 @@ int rrx_set_gas_window(int on);
 /* diagnostic: with RRX_GW_STATS set in the environment every windowed gas-optics launch waits for its kernel and counts the
    workgroups it handed back to the gather kernel; this returns (and optionally resets) the calling thread's totals */
 int rrx_gas_window_stats(long long* handed_back, long long* workgroups, int reset);
+/* diagnostic (tests): the index tables of the calling thread's last windowed gas-optics launch, copied to the host after a device
+   synchronisation. layout[16]: ints in all (tables + header), ngpt, nmax, ncmax, the offsets of the chunk starts, contributor lists,
+   contributor metadata, usable flags, chunk order, per-g-point bands and key species, unusable-chunk counts and chunk records, then
+   ints per list, per metadata entry, per record and per record header. tables == NULL: the layout only. */
+int rrx_gas_window_tables_read(int* tables, int capacity, int* layout);
 
 #define RRX_DECLARE(F, SFX) \
 /* ---- Rte_solver_kernels_cuda : include_kernels_cuda/rte_solver_kernels_cuda.h:33-64 ---- */ \

@@ -1412,8 +1412,23 @@ struct GasWindowTables
     __host__ __device__ int off_mmeta() const { return off_lists() + 2*ncmax*LIT; }      // [2][nmax][MM]
     __host__ __device__ int off_cuni()  const { return off_mmeta() + 2*MM*nmax; }        // [2][ncmax] chunk usable by the windowed path
     __host__ __device__ int off_order() const { return off_cuni() + 2*ncmax; }           // [2][ncmax] chunk order (flavor by flavor)
-    __host__ __device__ int ints()      const { return (off_order() + 2*ncmax + 3) & ~3; }
+    // Behind the index arrays the tables kernel works on (which it builds in LDS), what the windowed kernel reads -- by scalar
+    // loads, straight from this buffer (it copies nothing into LDS): the bands and key species of every g-point (the kernel's
+    // contents check covers them), the number of chunks ahead of chunk c that do not fit the staged form, and one packed record
+    // per (regime, position): everything a workgroup needs at the top of a chunk.
+    static constexpr int GX = 6;                             // per g-point: band, by-band (cloud) band, key species (gas1, gas2) lower, upper; -1 where the launch has no such array
+    static constexpr int RH = 12;                            // record header, see below
+    static constexpr int RC = 8;                             // ... and per contributor: first g-point, end, kminor row offset, gas, scales with density, scaling gas, by complement, 0
+    static constexpr int REC = RH + RC*NXW;
+    // record header: [0] first g-point, [1] end, [2] flavor, [3] contributors (uncapped), [4] [5] key species, [6] [7] first / last
+    // band, [8] by-band band of the first g-point, [9] chunk inside that band, [10] chunk usable, [11] the chunk that runs at THIS
+    // position of the flavor-by-flavor order (a property of the position, not of the chunk)
+    __host__ __device__ int off_gx()    const { return (off_order() + 2*ncmax + 3) & ~3; }  // [ngpt][GX]; also: the ints the tables kernel builds in LDS
+    __host__ __device__ int off_bad()   const { return off_gx() + GX*ngpt; }               // [2][ncmax + 1]
+    __host__ __device__ int off_rec()   const { return (off_bad() + 2*(ncmax + 1) + 3) & ~3; }   // [2][ncmax][REC], 16-byte aligned
+    __host__ __device__ int ints()      const { return off_rec() + 2*ncmax*REC; }
 };
+static_assert(GasWindowTables::REC % 4 == 0 && GasWindowTables::RH % 4 == 0 && GasWindowTables::RC == 8, "records are read as 16- and 32-byte words");
 inline int gas_window_ncmax(const int ngpt, const int nband) { return (ngpt + GCH - 1) / GCH + std::max(nband, 0); }
 
 // The tables depend on the k-distribution alone. One small workgroup builds them; the 9 000 workgroups of the windowed
@@ -1422,12 +1437,13 @@ inline int gas_window_ncmax(const int ngpt, const int nband) { return (ngpt + GC
 // before), compares them and the shape with what the buffer was built from -- both are part of the tables -- and leaves when
 // nothing changed: 39 -> 5 us per launch, which was 4 % of a step at 2 048 columns per GPU. A k-distribution that changed in
 // place, or another one at the same addresses, is rebuilt: the check is on the contents, not on the pointers.
-constexpr int GW_TBL_HEADER = 8;                 // ints behind the tables: magic, ngpt, nminorlower, nminorupper, ncmax, nlist
-constexpr int GW_TBL_MAGIC = 0x52525834;
+constexpr int GW_TBL_HEADER = 8;                 // ints behind the tables: magic, ngpt, nminorlower, nminorupper, ncmax, nlist, nband
+constexpr int GW_TBL_MAGIC = 0x52525835;
 __global__ void __launch_bounds__(256)
 gas_window_tables_kernel(
-        const int ngpt, const int nminorlower, const int nminorupper, const int ncmax, const int nlist,
+        const int ngpt, const int nminorlower, const int nminorupper, const int ncmax, const int nlist, const int nband,
         const int* __restrict__ gpoint_flavor,
+        const int* __restrict__ flavor, const int* __restrict__ gpoint_bands, const int* __restrict__ band_lims,    // (the last two: null where the launch has none)
         const int* __restrict__ minor_limits_gpt_lower, const int* __restrict__ minor_limits_gpt_upper,
         const Bool* __restrict__ minor_scales_with_density_lower, const Bool* __restrict__ minor_scales_with_density_upper,
         const Bool* __restrict__ scale_by_complement_lower, const Bool* __restrict__ scale_by_complement_upper,
@@ -1446,9 +1462,22 @@ gas_window_tables_kernel(
     int* mmeta = lds_int + T.off_mmeta();
     int* cuni = lds_int + T.off_cuni();
     int* order = lds_int + T.off_order();
-    int* cut = lds_int + T.ints();                          // [ngpt + 1] scratch: 1 where a chunk must start
+    int* cut = lds_int + T.off_gx();                        // [ngpt + 1] scratch: 1 where a chunk must start
     const int tid = threadIdx.x;
-    const int ntab = T.ints();
+    const int ntab = T.off_gx();                            // (built in LDS; the sections behind are written straight to the buffer)
+    // bands and key species of g-point g (entry k of its GX): what the windowed kernel uses of gpoint_bands, band_lims and flavor
+    auto gx_of = [&](const int g, const int k) -> int
+    {
+        if (k == 0) return gpoint_bands != nullptr ? gpoint_bands[g] - 1 : -1;
+        if (k == 1)
+        {
+            if (band_lims == nullptr) return -1;
+            int b = 0;
+            while (b < nband-1 && g + 1 > band_lims[2*b+1]) ++b;
+            return b;
+        }
+        return flavor[2*gflav[((k - 2) >> 1)*ngpt + g] + (k & 1)];
+    };
     for (int w = tid; w < ntab + ngpt + 4 + 2*((ngpt + 63)/64); w += 256) lds_int[w] = 0;
     __syncthreads();
     {
@@ -1471,11 +1500,13 @@ gas_window_tables_kernel(
     __syncthreads();
     // ---- built from the same inputs before? (flavors and contributor metadata sit in the tables as they were read)
     {
-        int* head = tbl + ntab;
+        int* head = tbl + T.ints();
         int differs = (head[0] != GW_TBL_MAGIC || head[1] != ngpt || head[2] != nminorlower || head[3] != nminorupper
-                       || head[4] != ncmax || head[5] != nlist) ? 1 : 0;
+                       || head[4] != ncmax || head[5] != nlist || head[6] != nband) ? 1 : 0;
         for (int w = tid; w < 2*ngpt && !differs; w += 256) differs = (tbl[w] != gflav[w]) ? 1 : 0;
         for (int w = tid; w < 2*MM*nmax && !differs; w += 256) differs = (tbl[T.off_mmeta() + w] != mmeta[w]) ? 1 : 0;
+        for (int w = tid; w < GasWindowTables::GX*ngpt && !differs; w += 256)
+            differs = (tbl[T.off_gx() + w] != gx_of(w / GasWindowTables::GX, w % GasWindowTables::GX)) ? 1 : 0;
         if (!__syncthreads_or(differs)) return;
         if (tid == 0) head[0] = 0;                         // (not valid while it is being rewritten)
     }
@@ -1588,12 +1619,42 @@ gas_window_tables_kernel(
     }
 #endif
     for (int w = tid; w < ntab; w += 256) tbl[w] = lds_int[w];
+    for (int w = tid; w < GasWindowTables::GX*ngpt; w += 256) tbl[T.off_gx() + w] = gx_of(w / GasWindowTables::GX, w % GasWindowTables::GX);
+    if (tid < 2)                                            // unusable chunks ahead of chunk c, per regime
+    {
+        int* bad = tbl + T.off_bad() + tid*(ncmax + 1);
+        int k = 0;
+        for (int c=0; c<=ncmax; ++c) { bad[c] = k; if (c < nchunk && cuni[tid*ncmax + c] == 0) ++k; }
+    }
+    for (int w = tid; w < 2*ncmax; w += 256)                // the records (ordinary vector stores; places behind the last chunk: zeros)
+    {
+        constexpr int RH = GasWindowTables::RH, RC = GasWindowTables::RC, REC = GasWindowTables::REC;
+        const int r = w / ncmax, c = w % ncmax;
+        int* rec = tbl + T.off_rec() + w*REC;
+        for (int k=0; k<REC; ++k) rec[k] = 0;
+        if (c >= nchunk) continue;
+        const int c0 = cinfo[2 + c], c1 = cinfo[3 + c];
+        const int* li = lists + w*LIT;
+        rec[0] = c0; rec[1] = c1; rec[2] = gflav[r*ngpt + c0]; rec[3] = li[0];
+        rec[4] = gx_of(c0, 2 + 2*r); rec[5] = gx_of(c0, 3 + 2*r);
+        rec[6] = gx_of(c0, 0); rec[7] = gx_of(c1 - 1, 0);
+        const int b0 = gx_of(c0, 1);
+        rec[8] = b0; rec[9] = (b0 >= 0 && c1 <= band_lims[2*b0+1]) ? 1 : 0;
+        rec[10] = cuni[w]; rec[11] = order[w];
+        for (int i=0; i<min(li[0], nlist); ++i)
+        {
+            const int* m = mmeta + MM*(r*nmax + li[1 + i]);
+            int* o = rec + RH + RC*i;
+            const int lo = m[4] - 1;
+            o[0] = lo; o[1] = m[5]; o[2] = m[6] - 1 - lo; o[3] = m[0]; o[4] = m[1]; o[5] = m[2]; o[6] = m[3];
+        }
+    }
     __threadfence();
     __syncthreads();
     if (tid == 0)
     {
-        int* head = tbl + ntab;
-        head[1] = ngpt; head[2] = nminorlower; head[3] = nminorupper; head[4] = ncmax; head[5] = nlist;
+        int* head = tbl + T.ints();
+        head[1] = ngpt; head[2] = nminorlower; head[3] = nminorupper; head[4] = ncmax; head[5] = nlist; head[6] = nband;
         __threadfence();
         head[0] = GW_TBL_MAGIC;
     }
@@ -1601,31 +1662,50 @@ gas_window_tables_kernel(
 
 // The persistent table buffer of a k-distribution: one per (calling thread, device, first index array, shape), zeroed when it is
 // made, validated against the index arrays' CONTENTS by the kernel at every launch. At most 32 are kept (oldest dropped).
+// (diagnostic, rrx_gas_window_tables_read: the buffer the calling thread's last windowed launch used, and its shape)
+struct GasWindowLast { int* buf = nullptr; int ngpt = 0, nmax = 0, ncmax = 0; };
+thread_local GasWindowLast g_gw_last;
 inline int* gas_window_tables(hipStream_t st, const int* key_ptr, const int ngpt, const int nminorlower, const int nminorupper,
-                              const int ncmax, const int nlist)
+                              const int ncmax, const int nlist, const int extras)
 {
-    struct Entry { int dev; const int* key; int dims[5]; int* buf; };
+    struct Entry { int dev; const int* key; int dims[6]; int* buf; hipStream_t made_on; hipEvent_t zeroed; };
     static thread_local std::vector<Entry> cache;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) throw std::runtime_error("no device");
-    const int dims[5] = {ngpt, nminorlower, nminorupper, ncmax, nlist};
+    const int dims[6] = {ngpt, nminorlower, nminorupper, ncmax, nlist, extras};
+    g_gw_last.ngpt = ngpt; g_gw_last.nmax = std::max(nminorlower, nminorupper); g_gw_last.ncmax = ncmax;
     for (const Entry& e : cache)
-        if (e.dev == dev && e.key == key_ptr && std::equal(dims, dims + 5, e.dims)) return e.buf;
-    (void)st;
-    // (plain hipMalloc / hipMemset, once per k-distribution: the buffer may be used from any stream of this thread afterwards)
-    if (cache.size() >= 32) { (void)hipFree(cache.front().buf); cache.erase(cache.begin()); }
+        if (e.dev == dev && e.key == key_ptr && std::equal(dims, dims + 6, e.dims))
+        {
+            // (made and zeroed in the order of ANOTHER stream of this thread: this one waits for that, nothing else does)
+            if (e.made_on != st && hipStreamWaitEvent(st, e.zeroed, 0) != hipSuccess) throw std::runtime_error("stream wait failed");
+            g_gw_last.buf = e.buf;
+            return e.buf;
+        }
+    // allocated and zeroed in the order of the launch stream, once per k-distribution: no device-wide synchronisation, no work on
+    // the null stream
+    if (cache.size() >= 32)
+    {
+        Entry& old = cache.front();
+        (void)hipStreamWaitEvent(st, old.zeroed, 0); (void)hipFreeAsync(old.buf, st); (void)hipEventDestroy(old.zeroed);
+        cache.erase(cache.begin());
+    }
     const size_t n = size_t(GasWindowTables{ngpt, std::max(nminorlower, nminorupper), ncmax}.ints()) + GW_TBL_HEADER;
-    Entry e{dev, key_ptr, {dims[0], dims[1], dims[2], dims[3], dims[4]}, nullptr};
-    if (hipMalloc(reinterpret_cast<void**>(&e.buf), n*sizeof(int)) != hipSuccess) throw std::runtime_error("table allocation failed");
-    if (hipMemset(e.buf, 0, n*sizeof(int)) != hipSuccess) throw std::runtime_error("memset failed");
+    Entry e{dev, key_ptr, {dims[0], dims[1], dims[2], dims[3], dims[4], dims[5]}, nullptr, st, nullptr};
+    if (hipMallocAsync(reinterpret_cast<void**>(&e.buf), n*sizeof(int), st) != hipSuccess) throw std::runtime_error("table allocation failed");
+    if (hipMemsetAsync(e.buf, 0, n*sizeof(int), st) != hipSuccess) throw std::runtime_error("memset failed");
+    if (hipEventCreateWithFlags(&e.zeroed, hipEventDisableTiming) != hipSuccess || hipEventRecord(e.zeroed, st) != hipSuccess)
+        throw std::runtime_error("event failed");
     cache.push_back(e);
+    g_gw_last.buf = e.buf;
     return e.buf;
 }
 
 template<typename F>
 size_t gas_window_lds_bytes(const int ngpt, const int nmax, const int ncmax, const int mode, const bool pf)
 {
-    const size_t ints = size_t(GasWindowTables{ngpt, nmax, ncmax}.ints()) + 16 + 8*size_t(ncmax);      // tables, reductions, per-chunk bands and key species
+    (void)ngpt; (void)nmax; (void)ncmax;
+    const size_t ints = 16;                                  // workgroup reductions (the index tables are read from their buffer by scalar loads)
     const size_t pairs = size_t(GCH)*WBOX*(pf ? 2 : 1) + size_t(NCW)*GCH*MBOX + (mode == 1 ? size_t(GCH)*MBOX : 0);
     return ((ints*sizeof(int) + 15) & ~size_t(15)) + pairs*2*sizeof(F);
 }
@@ -1661,21 +1741,20 @@ gas_window_kernel(
     (void)sizeof(Vec2u);
     extern __shared__ int lds_int[];
     const int nmax = max(nminorlower, nminorupper);
-    const GasWindowTables T{ngpt, nmax, ncmax};             // layout of the copied tables (gas_window_tables_kernel)
-    constexpr int LIT = GasWindowTables::LIT;
-    int* gflav = lds_int;                                   // [2][ngpt]
-    const int* cinfo = lds_int + T.off_cinfo();             // [0] chunks, [1] regular (every chunk starts at a multiple of GCH), [2 + c] first g-point of chunk c
-    const int* cstart = cinfo + 2;
-    int* lists = lds_int + T.off_lists();                   // [2][ncmax][LIT]: count (uncapped), then up to NCW contributor indices
-    int* mmeta = lds_int + T.off_mmeta();                   // [2][nmax][MM]
-    int* cuni = lds_int + T.off_cuni();                     // [2][ncmax]: chunk usable by the windowed path (per regime)
-    int* red = lds_int + T.ints();                          // [16] workgroup reductions (behind the copied tables)
-    // per-chunk band numbers of the fractions form and of the by-band (all-sky) properties, looked up ONCE at set-up: read from global
-    // memory at the top of a chunk (round 3) each look-up was a dependent load that queues behind the stores of the chunk before --
-    // 3-5 k clocks, and the all-sky band search made several of them per chunk (phase clocks: chunk prologue +45 ... +85 k per workgroup)
-    int* cband = red + 16;                                  // [ncmax][8]: PF first band, PF last band, CLD band, CLD chunk in one band,
-                                                            //             key species (gas1, gas2) of the chunk's flavor in the lower / upper atmosphere
-    const size_t int_bytes = ((size_t(T.ints()) + 16 + 8*size_t(ncmax))*sizeof(int) + 15) & ~size_t(15);
+    const GasWindowTables T{ngpt, nmax, ncmax};             // layout of the tables (gas_window_tables_kernel)
+    // The index tables depend on the k-distribution alone: gas_window_tables_kernel built them, and nothing in this launch writes them.
+    // They are read where they are needed, at workgroup-uniform places, through the constant address space: scalar loads (s_load_dword
+    // x4 / x8 through the scalar cache). A scalar load is counted in lgkmcnt, so -- unlike the LDS copy of rounds 1-4, whose every
+    // value was a ds_read + v_readfirstlane, and unlike a vector load -- it neither costs vector issue nor waits behind the stores the
+    // wavefront has in flight (vmcnt retires in order). What a chunk needs is ONE record: its limits, flavor, key species, bands and,
+    // per contributor, interval, kminor rows and scaling rule (GasWindowTables).
+    typedef int Int4 __attribute__((ext_vector_type(4)));
+    typedef int Int8 __attribute__((ext_vector_type(8)));
+    typedef const __attribute__((address_space(4))) int* CInt;
+    const CInt ctbl = reinterpret_cast<CInt>(reinterpret_cast<uintptr_t>(tbl));
+    constexpr int RH = GasWindowTables::RH, RC = GasWindowTables::RC, REC = GasWindowTables::REC;
+    int* red = lds_int;                                     // [16] workgroup reductions
+    const size_t int_bytes = 16*sizeof(int);
     Vec2* Wmaj = reinterpret_cast<Vec2*>(reinterpret_cast<char*>(lds_int) + int_bytes);     // [GCH][WBOX]
     Vec2* Wpf  = Wmaj + GCH*WBOX;                                                           // [GCH][WBOX] (PF)
     Vec2* Wmin = Wpf + (PF ? GCH*WBOX : 0);                                                 // [NCW][GCH][MBOX]
@@ -1685,12 +1764,7 @@ gas_window_kernel(
 #if RRX_GW_TIMING
     unsigned long long gw_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, gw_t = __builtin_readcyclecounter();
 #endif
-    // the index tables depend on the k-distribution alone: gas_window_tables_kernel built them once for this launch
     {
-        const int n4 = T.ints() / 4;
-        const int4* __restrict__ src = reinterpret_cast<const int4*>(tbl);
-        int4* dst = reinterpret_cast<int4*>(lds_int);
-        for (int w = tid; w < n4; w += 256) dst[w] = src[w];
         if (tid < 16) red[tid] = (tid >= 6) ? 0 : ((tid & 1) ? -2147483647 : 2147483647);   // 0..5: running min / max pairs; 6, 8: presence masks
     }
 
@@ -1708,42 +1782,25 @@ gas_window_kernel(
     const int jt = cs.jt, jp = cs.jp_raw + itr;
 
     // ---- box in temperature and pressure, one regime per workgroup
-    __syncthreads();                                  // the tables and the reduction slots are in place
+    __syncthreads();                                  // the reduction slots are in place
     atomicMin(&red[0], jt); atomicMax(&red[1], jt); atomicMin(&red[2], jp); atomicMax(&red[3], jp);
     atomicMin(&red[4], itr); atomicMax(&red[5], itr);
-    if (tid < cinfo[0])
-    {
-        const int c0_ = cstart[tid], ge_ = cstart[tid+1];
-        if constexpr (PF) { cband[8*tid] = pa.gpoint_bands[c0_] - 1; cband[8*tid+1] = pa.gpoint_bands[ge_-1] - 1; }
-        if constexpr (CLD)
-        {
-            int b0 = 0;
-            while (c0_ + 1 > ia.cld_lims[2*b0+1]) ++b0;
-            cband[8*tid+2] = b0; cband[8*tid+3] = (ge_ <= ia.cld_lims[2*b0+1]) ? 1 : 0;
-        }
-        #pragma unroll
-        for (int r=0; r<2; ++r)
-        {
-            const int fl_ = gflav[r*ngpt + c0_];
-            cband[8*tid+4+2*r] = ia.flavor[2*fl_]; cband[8*tid+5+2*r] = ia.flavor[2*fl_+1];
-        }
-    }
     __syncthreads();
     const int jt_lo = red[0], jp_lo = red[2];
     // grid.z parts share out the chunks of a workgroup when the (column, layer) grid alone leaves CUs idle (few columns per GPU).
     // A part is a range of 16-g-point stretches, which the gather kernel can redo from the part's number alone; where the chunks do
     // not start at multiples of 16 (band-aligned chunks of a reduced k-distribution) part 0 takes them all and hands back "the
     // whole range" (part = gridDim.z).
-    const int nchunk = rfl(cinfo[0]);
-    const bool whole_range = gridDim.z > 1 && rfl(cinfo[1]) == 0;
+    const int nchunk = ctbl[T.off_cinfo()];
+    const bool whole_range = gridDim.z > 1 && ctbl[T.off_cinfo() + 1] == 0;           // (not regular: some chunk starts off a multiple of GCH)
     if (whole_range && blockIdx.z > 0) return;
     const int c_per = whole_range ? nchunk : (nchunk + int(gridDim.z) - 1) / int(gridDim.z);
     const int c_lo = whole_range ? 0 : int(blockIdx.z)*c_per, c_hi = min(nchunk, c_lo + c_per);
     bool fits = (red[1] - jt_lo < NTW) && (red[3] - jp_lo + 2 <= NPW) && (red[4] == red[5]);
     {
-        bool all_chunks = true;
-        for (int c=c_lo; c<c_hi; ++c) all_chunks = all_chunks && (cuni[itr*ncmax + c] != 0);
-        fits = fits && all_chunks;
+        // every chunk of this part usable in the workgroup's regime (with cells in both regimes it does not fit anyway)
+        const CInt bad = ctbl + T.off_bad() + rfl(red[4])*(ncmax + 1);
+        fits = fits && (bad[c_hi] == bad[c_lo]);
     }
     // workgroup-uniform: the gather kernel redoes this workgroup from scratch. The eight words in front of the list count the
     // reasons (0 temperature spread, 1 pressure spread, 2 both regimes, 3 a chunk outside the staged form, 4 eta spread);
@@ -1780,10 +1837,9 @@ gas_window_kernel(
     {
         stream_store(reinterpret_cast<F*>(reinterpret_cast<char*>(arr + size_t(ig)*ncl) + idx_b), v);
     };
-    auto minor_scaling = [&](const int imnr) -> F                      // gas_optics_rrtmgp_kernels.cu:505-529
+    // (imn, swd, ims, sbc: the contributor's gas, scales with density, scaling gas, by complement -- from the chunk's record)
+    auto minor_scaling = [&](const int imn, const int swd, const int ims, const int sbc) -> F      // gas_optics_rrtmgp_kernels.cu:505-529
     {
-        const int* m = mmeta + MM*(itr*nmax + imnr);
-        const int imn = rfl(m[0]), swd = rfl(m[1]), ims = rfl(m[2]), sbc = rfl(m[3]);
         F scaling = col_gas[idx + size_t(imn)*ncl];
         const F cscal = col_gas[idx + size_t(max(ims, 0))*ncl];
         if (swd)
@@ -1817,7 +1873,8 @@ gas_window_kernel(
     // in the SW form) and two fp64 divisions; now the table positions are found once and all bands' reads are in flight together.
     if constexpr (PF)
     {
-        const int b_first = rfl(cband[8*c_lo]), b_last = rfl(cband[8*(c_hi-1)+1]);
+        const CInt rec0 = ctbl + T.off_rec() + rfl(itr)*ncmax*REC;        // (band numbers: of chunk c, whatever the position)
+        const int b_first = rec0[c_lo*REC + 6], b_last = rec0[(c_hi-1)*REC + 7];
         const size_t ncv_ = size_t(ncol)*(nlay+1);
         const Interp1dPos<F> p_lay = interp1d_pos(tl, ia.temp_ref_min, pa.totplnk_delta, pa.nPlanckTemp);
         const Interp1dPos<F> p_lev = interp1d_pos(t_lev, ia.temp_ref_min, pa.totplnk_delta, pa.nPlanckTemp);
@@ -1847,22 +1904,22 @@ gas_window_kernel(
 
     if (RRX_GW_ABL == 1) return;
     RRX_GW_T(0)
-    const int* corder = lds_int + T.off_order() + rfl(itr)*ncmax;      // (one regime per workgroup here)
-    // per contributor of the chunk: first g-point, end, offset of its kminor rows (from the metadata table)
-    auto item_meta = [&](const int* items, const int i, int& lo, int& hi, int& koff)
-    {
-        const int* m = mmeta + MM*(rfl(itr)*nmax + rfl(items[i]));
-        lo = rfl(m[4]) - 1; hi = rfl(m[5]); koff = rfl(m[6]) - 1 - lo;
-    };
+    const CInt recs = ctbl + T.off_rec() + rfl(itr)*ncmax*REC;         // (one regime per workgroup here)
     for (int kc=c_lo; kc<c_hi; ++kc)
     {
-        const int c = (gridDim.z == 1 || whole_range) ? rfl(corder[kc]) : kc;   // (parts of the chunk range keep the natural order)
-        const int c0 = rfl(cstart[c]), gend = rfl(cstart[c+1]), ng = gend - c0;
-        const int fl = gflav[itr*ngpt + c0];
+        const int c = (gridDim.z == 1 || whole_range) ? recs[kc*REC + 11] : kc;   // (parts of the chunk range keep the natural order)
+        const CInt rec = recs + c*REC;                                 // the chunk's record: three 16-byte words + 32 bytes per contributor
+        const Int4 rh0 = *reinterpret_cast<const __attribute__((address_space(4))) Int4*>(rec);
+        const Int4 rh1 = *reinterpret_cast<const __attribute__((address_space(4))) Int4*>(rec + 4);
+        [[maybe_unused]] const Int4 rh2 = *reinterpret_cast<const __attribute__((address_space(4))) Int4*>(rec + 8);
+        // per contributor of the chunk: first g-point, end, offset of its kminor rows, and its scaling rule
+        auto item_rec = [&](const int i) -> Int8 { return *reinterpret_cast<const __attribute__((address_space(4))) Int8*>(rec + RH + RC*i); };
+        const int c0 = rh0.x, gend = rh0.y, ng = gend - c0;
+        const int fl = rh0.z;
         if (fl != cur_flav)                                            // workgroup-uniform
         {
             cur_flav = fl;
-            const int gas1 = rfl(cband[8*c+4+2*rfl(itr)]), gas2 = rfl(cband[8*c+5+2*rfl(itr)]);     // (= ia.flavor[2*fl], [2*fl+1], looked up at set-up)
+            const int gas1 = rh1.x, gas2 = rh1.y;                      // (= ia.flavor[2*fl], [2*fl+1])
             const F cg1 = col_gas[idx + size_t(gas1)*ncl], cg2 = col_gas[idx + size_t(gas2)*ncl];
             #pragma unroll
             for (int itemp=0; itemp<2; ++itemp)
@@ -1889,10 +1946,8 @@ gas_window_kernel(
         }
         // (the regime is the same in every lane here: readfirstlane moves the chunk's list into scalar registers, so that the
         //  contributor conditions of the g-point loop are scalar branches instead of exec-mask sequences)
-        const int itr_s = rfl(itr);
-        const int n_all = rfl(lists[(itr_s*ncmax + c)*LIT]);             // (at most NXW here: the chunk is usable)
+        const int n_all = rh0.w;                                         // (at most NXW here: the chunk is usable)
         const int n = min(n_all, NCW);                                   // contributors of the g-point loop; the others follow behind it
-        const int* items = lists + (itr_s*ncmax + c)*LIT + 1;            // contributor indices of the chunk
 
         // all-sky: the cell's by-band values, read once per chunk where the chunk lies in one band (the rule), requested HERE -- ahead
         // of the barrier and the staging, whose wait they share
@@ -1917,9 +1972,9 @@ gas_window_kernel(
         [[maybe_unused]] bool cld_one_band = false;
         if constexpr (CLD)
         {
-            const int b0 = rfl(cband[8*c+2]);
+            const int b0 = rh2.x;
             cb = b0;
-            cld_one_band = rfl(cband[8*c+3]) != 0;
+            cld_one_band = rh2.y != 0;
             if (cld_one_band && b0 != cb_have) cld_load(b0);
         }
 
@@ -1936,7 +1991,7 @@ gas_window_kernel(
             for (int i=0; i<NCW; ++i)
             {
                 sc[i] = F(0.); slo[i] = 0; shi[i] = 0; skoff[i] = 0;
-                if (i < n) { sc[i] = minor_scaling(rfl(items[i])); item_meta(items, i, slo[i], shi[i], skoff[i]); }
+                if (i < n) { const Int8 m = item_rec(i); sc[i] = minor_scaling(m.s3, m.s4, m.s5, m.s6); slo[i] = m.s0; shi[i] = m.s1; skoff[i] = m.s2; }
             }
         };
         // ---- stage the boxes: pairs (T, T+1) are adjacent words of the tables (temperature is their fastest dimension)
@@ -2050,9 +2105,9 @@ gas_window_kernel(
                 for (int i=0; i<NCW; ++i)
                     if (i < n)
                     {
-                        int lo, hi, koff; item_meta(items, i, lo, hi, koff);
-                        const int kg = min(max(c0 + gi_m, lo), hi-1);       // clamped: always a valid table row
-                        glds(byte_off(kmin_u, unsigned((kg + koff)*tn + it_m + ie_m*ntemp)*SZ), Wmin + i*GCH*MBOX + tid);
+                        const Int8 m = item_rec(i);
+                        const int kg = min(max(c0 + gi_m, m.s0), m.s1-1);   // clamped: always a valid table row
+                        glds(byte_off(kmin_u, unsigned((kg + m.s2)*tn + it_m + ie_m*ntemp)*SZ), Wmin + i*GCH*MBOX + tid);
                     }
             }
             chunk_scalings();
@@ -2104,9 +2159,9 @@ gas_window_kernel(
             const int it_m = min(jt_lo - 1 + r_m % NTW, ntemp-2), ie_m = min(max(je_lo - 1 + r_m / NTW, 0), neta-1);
             auto minor_node = [&](const int i) -> Vec2
             {
-                int lo, hi, koff; item_meta(items, i, lo, hi, koff);
-                const int kg = min(max(c0 + gi_m, lo), hi-1);                   // clamped: always a valid table row
-                return *reinterpret_cast<const Vec2u*>(kmin + size_t(kg + koff)*tn + it_m + ie_m*ntemp);
+                const Int8 m = item_rec(i);
+                const int kg = min(max(c0 + gi_m, m.s0), m.s1-1);               // clamped: always a valid table row
+                return *reinterpret_cast<const Vec2u*>(kmin + size_t(kg + m.s2)*tn + it_m + ie_m*ntemp);
             };
             if (tid < nmin)
             {
@@ -2164,7 +2219,7 @@ gas_window_kernel(
         [[maybe_unused]] bool one_band = false;
         if constexpr (PF)
         {
-            const int b0 = rfl(cband[8*c]), b1 = rfl(cband[8*c+1]);
+            const int b0 = rh1.z, b1 = rh1.w;
             one_band = b0 == b1;
             if (one_band && b0 != cur_bnd) band_update(b0);
         }
@@ -2411,7 +2466,8 @@ gas_window_kernel(
             for (int x=NCW; x<n_all; ++x)
             {
                 __syncthreads();                                        // the boxes of the loop (or of the contributor before) are free
-                int xlo, xhi, xk; item_meta(items, x, xlo, xhi, xk);
+                const Int8 xm = item_rec(x);
+                const int xlo = xm.s0, xhi = xm.s1, xk = xm.s2;
                 if (tid < GCH*MBOX)
                 {
                     const int gi_m = min(tid / MBOX, ng-1), r_m = tid % MBOX;
@@ -2419,7 +2475,7 @@ gas_window_kernel(
                     const int kg = min(max(c0 + gi_m, xlo), xhi-1);     // clamped: always a valid table row
                     Wmin[tid] = *reinterpret_cast<const Vec2u*>(kmin_u + size_t(kg + xk)*tn + it_m + ie_m*ntemp);
                 }
-                const F scx = minor_scaling(rfl(items[x]));
+                const F scx = minor_scaling(xm.s3, xm.s4, xm.s5, xm.s6);
                 __syncthreads();
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wavefront's stores of the chunk have left: they are read back
                 for (int gi=0; gi<ng; ++gi)
@@ -2527,9 +2583,10 @@ int gas_optics_lw_fractions_impl(
         todo = scratch.get<int>(size_t(9) + size_t(nblk)*nz) + 8;
         if (hipMemsetAsync(todo - 8, 0, 9*sizeof(int), st) != hipSuccess) throw std::runtime_error("memset failed");
         const GasWindowTables T{ngpt, nmax, ncmax};
-        int* tbl = gas_window_tables(st, gpoint_flavor, ngpt, nminorlower, nminorupper, ncmax, NXW);
-        gas_window_tables_kernel<<<1, 256, size_t(T.ints() + ngpt + 4 + 2*((ngpt + 63)/64))*sizeof(int), st>>>(
-                ngpt, nminorlower, nminorupper, ncmax, NXW, gpoint_flavor, minor_limits_gpt_lower, minor_limits_gpt_upper,
+        const int* lims = ia.cld_tau != nullptr ? ia.cld_lims : nullptr;
+        int* tbl = gas_window_tables(st, gpoint_flavor, ngpt, nminorlower, nminorupper, ncmax, NXW, 1 + (lims != nullptr ? 2 : 0));
+        gas_window_tables_kernel<<<1, 256, size_t(T.off_gx() + ngpt + 4 + 2*((ngpt + 63)/64))*sizeof(int), st>>>(
+                ngpt, nminorlower, nminorupper, ncmax, NXW, nband, gpoint_flavor, ia.flavor, gpoint_bands, lims, minor_limits_gpt_lower, minor_limits_gpt_upper,
                 minor_scales_with_density_lower, minor_scales_with_density_upper, scale_by_complement_lower, scale_by_complement_upper,
                 idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper,
                 kminor_start_lower, kminor_start_upper, tbl);
@@ -2609,9 +2666,10 @@ int tau_absorption_impl(
             int* todo = scratch.get<int>(size_t(9) + size_t(nblk)*nz) + 8;
             if (hipMemsetAsync(todo - 8, 0, 9*sizeof(int), st) != hipSuccess) throw std::runtime_error("memset failed");
             const GasWindowTables T{ngpt, nmax, ncmax};
-            int* tbl = gas_window_tables(st, gpoint_flavor, ngpt, nminorlower, nminorupper, ncmax, (MODE == 1) ? NCW : NXW);
-            gas_window_tables_kernel<<<1, 256, size_t(T.ints() + ngpt + 4 + 2*((ngpt + 63)/64))*sizeof(int), st>>>(
-                    ngpt, nminorlower, nminorupper, ncmax, (MODE == 1) ? NCW : NXW, gpoint_flavor, minor_limits_gpt_lower, minor_limits_gpt_upper,
+            const int* lims = ia.cld_tau != nullptr ? ia.cld_lims : nullptr;
+            int* tbl = gas_window_tables(st, gpoint_flavor, ngpt, nminorlower, nminorupper, ncmax, (MODE == 1) ? NCW : NXW, lims != nullptr ? 2 : 0);
+            gas_window_tables_kernel<<<1, 256, size_t(T.off_gx() + ngpt + 4 + 2*((ngpt + 63)/64))*sizeof(int), st>>>(
+                    ngpt, nminorlower, nminorupper, ncmax, (MODE == 1) ? NCW : NXW, nband, gpoint_flavor, ia.flavor, (const int*)nullptr, lims, minor_limits_gpt_lower, minor_limits_gpt_upper,
                     minor_scales_with_density_lower, minor_scales_with_density_upper, scale_by_complement_lower, scale_by_complement_upper,
                     idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper,
                     kminor_start_lower, kminor_start_upper, tbl);
@@ -3010,6 +3068,24 @@ int rrx_zero_array##SFX(int ni, int nj, int nk, F* arr, void* stream) \
 
 RRX_DEFINE_GAS(double, _f64)
 RRX_DEFINE_GAS(float, _f32)
+}
+
+extern "C" int rrx_gas_window_tables_read(int* tables, const int capacity, int* layout)
+{
+    RRX_TRY
+    const GasWindowLast& L = g_gw_last;
+    if (L.buf == nullptr) throw std::runtime_error("no windowed gas-optics launch on this thread yet");
+    const GasWindowTables T{L.ngpt, L.nmax, L.ncmax};
+    const int lay[16] = {T.ints() + GW_TBL_HEADER, L.ngpt, L.nmax, L.ncmax, T.off_cinfo(), T.off_lists(), T.off_mmeta(), T.off_cuni(), T.off_order(),
+                         T.off_gx(), T.off_bad(), T.off_rec(), GasWindowTables::LIT, MM, GasWindowTables::REC, GasWindowTables::RH};
+    if (layout != nullptr) std::copy(lay, lay + 16, layout);
+    if (tables != nullptr)
+    {
+        if (capacity < lay[0]) throw std::runtime_error("buffer too small for the tables");
+        if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(tables, L.buf, size_t(lay[0])*sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+            throw std::runtime_error("copy of the tables failed");
+    }
+    RRX_CATCH("rrx_gas_window_tables_read")
 }
 
 extern "C" int rrx_gas_window_stats(long long* handed_back, long long* workgroups, int reset)
