@@ -144,6 +144,15 @@ class Gas_optics_rrtmgp_gpu : public Gas_optics_gpu
                 Array_gpu<Float,2>& toa_src, const Array_gpu<Float,2>& col_dry,
                 const Optical_props_2str_gpu* add_by_band);
 
+        // Optimal-angle fit of current LW coefficient files (optimal_angle_fit, (2, nbnd), first index fastest): not a constructor
+        // argument (the reference's lists stay as they are); the loader sets it when the file has the variable. compute_optimal_angles
+        // (upstream's method of that name): optimal_angles(ncol, ngpt) = fit(1,b)*exp(-sum of tau over the layers) + fit(2,b), the
+        // secant (lw_Ds) of a one-angle solve; throws when the file had no fit.
+        void set_optimal_angle_fit(const Array<Float,2>& fit);
+        bool has_optimal_angle_fit() const { return optimal_angle_fit_gpu.size() > 0; }
+        const Array_gpu<Float,2>& get_optimal_angle_fit_gpu() const { return optimal_angle_fit_gpu; }
+        void compute_optimal_angles(const Optical_props_arry_gpu& optical_props, Array_gpu<Float,2>& optimal_angles) const;
+
         // Extras for tests / diagnostics: the reduced gas list and host copies of the index tables.
         const Array<std::string,1>& get_gas_names() const { return gas_names; }
         const Array<int,2>& get_flavor() const { return flavor; }
@@ -166,7 +175,7 @@ class Gas_optics_rrtmgp_gpu : public Gas_optics_gpu
         Array_gpu<Float,3> vmr_ref_gpu;
         Array_gpu<int,2> flavor_gpu, gpoint_flavor_gpu;
         Array_gpu<Float,4> kmajor_gpu, planck_frac_gpu, krayl_gpu;
-        Array_gpu<Float,2> totplnk_gpu;
+        Array_gpu<Float,2> totplnk_gpu, optimal_angle_fit_gpu;
         Array_gpu<Float,3> kminor_lower_gpu, kminor_upper_gpu;
         Array_gpu<int,2> minor_limits_gpt_lower_gpu, minor_limits_gpt_upper_gpu;
         Array_gpu<Bool,1> minor_scales_with_density_lower_gpu, minor_scales_with_density_upper_gpu;

@@ -35,6 +35,34 @@ class Rte_lw_gpu
                 Array_gpu<Float,3>& gpt_flux_dn,
                 Array_gpu<Float,3>& flux_up_jac,
                 const int n_gauss_angles);
+        // Optimal-angle secants (upstream's compute_optimal_angles / lw_Ds; one angle: more throws, as do by-band flux arrays). These
+        // two are named on their own, not overloads of rte_lw. flux_up_jac: null = no Jacobian.
+        // rte_lw_optimal: optimal_angle_fit (2, nbnd) of the k-distribution (Gas_optics_rrtmgp_gpu::get_optimal_angle_fit_gpu). With
+        // Planck-lite sources and broadband arrays the fused solver forms the secants itself (rrx_lw_solver_noscat_fractions_optimal);
+        // otherwise they are computed (rrx_lw_optimal_secants) and the solve runs as rte_lw_Ds.
+        void rte_lw_optimal(
+                const std::unique_ptr<Optical_props_arry_gpu>& optical_props,
+                const Bool top_at_1,
+                const Source_func_lw_gpu& sources,
+                const Array_gpu<Float,2>& sfc_emis,
+                const Array_gpu<Float,2>& inc_flux,
+                const Array_gpu<Float,2>& optimal_angle_fit,
+                Array_gpu<Float,3>& gpt_flux_up,
+                Array_gpu<Float,3>& gpt_flux_dn,
+                Array_gpu<Float,3>* flux_up_jac,
+                const int n_gauss_angles);
+        // rte_lw_Ds: lw_Ds (ncol, ngpt), the secant per column and g-point; any route of rte_lw runs with it
+        void rte_lw_Ds(
+                const std::unique_ptr<Optical_props_arry_gpu>& optical_props,
+                const Bool top_at_1,
+                const Source_func_lw_gpu& sources,
+                const Array_gpu<Float,2>& sfc_emis,
+                const Array_gpu<Float,2>& inc_flux,
+                const Array_gpu<Float,2>& lw_Ds,
+                Array_gpu<Float,3>& gpt_flux_up,
+                Array_gpu<Float,3>& gpt_flux_dn,
+                Array_gpu<Float,3>* flux_up_jac,
+                const int n_gauss_angles);
         // by-band fluxes (ncol, nlev, nband); bnd_flux_net (dn - up per band) and the broadband flux_up/dn (the band sums added in
         // band order) are written when their size is not 0
         void rte_lw_byband(
@@ -56,7 +84,8 @@ class Rte_lw_gpu
         void solve(
                 const std::unique_ptr<Optical_props_arry_gpu>& optical_props, const Bool top_at_1, const Source_func_lw_gpu& sources,
                 const Array_gpu<Float,2>& sfc_emis, const Array_gpu<Float,2>& inc_flux,
-                Array_gpu<Float,3>& gpt_flux_up, Array_gpu<Float,3>& gpt_flux_dn, Array_gpu<Float,3>* flux_up_jac, const int n_gauss_angles);
+                Array_gpu<Float,3>& gpt_flux_up, Array_gpu<Float,3>& gpt_flux_dn, Array_gpu<Float,3>* flux_up_jac, const int n_gauss_angles,
+                const Array_gpu<Float,2>* optimal_angle_fit = nullptr, const Array_gpu<Float,2>* lw_Ds = nullptr);
         // Gauss-Jacobi secants and weights on the device, uploaded once per object and angle count (an upload per call is a host
         // copy the stream is synchronised for: the solver launch then waits for the gas optics to finish before it is even enqueued)
         Array_gpu<Float,2> gauss_Ds_gpu, gauss_wts_gpu;

@@ -374,6 +374,22 @@ int rrx_lw_solver_noscat_fractions_angles##SFX( \
    t_sfc_old) of the level's column, flux_up += d and (flux_net not NULL) flux_net -= d; flux arrays (ncol, nlev), t_sfc (ncol) */ \
 int rrx_lw_flux_up_adjust##SFX(int ncol, int nlev, const F* flux_up_jac, const F* t_sfc_old, const F* t_sfc_new, \
         F* flux_up, F* flux_net, void* stream); \
+/* Optimal-angle secants (compute_optimal_angles / lw_Ds of current RTE+RRTMGP; no counterpart in the reference library): for column c \
+   and g-point g of band b = gpoint_bands[g], S = the sum of tau(c, :, g) over all layers and D(c, g) = fit(1,b)*exp(-S) + fit(2,b), \
+   the secant of a one-angle solve. optimal_angle_fit is (2, nbnd), first index fastest; D is not clamped. \
+   rrx_lw_optimal_secants writes D to secants (ncol, ngpt) in one pass over tau (layers added in index order from zero). */ \
+int rrx_lw_optimal_secants##SFX(int ncol, int nlay, int ngpt, int nbnd, const int* gpoint_bands, const F* optimal_angle_fit, \
+        const F* tau, F* secants, void* stream); \
+/* rrx_lw_solver_noscat_fractions [_jac] with those secants formed inside the kernel from the g-point it holds (tau is not read a \
+   second time, no secants array is read): one angle, weights (1). sfc_src_jac and flux_up_jac are both NULL or both given, as in \
+   the _angles entry. secants_out (ncol, ngpt) or NULL: the D the solve used. The kernel's sum over the layers is a tree over lanes \
+   and waves, so D may differ from rrx_lw_optimal_secants in the last bits. No by-band form. Shapes outside the one-kernel tilings \
+   take rrx_lw_optimal_secants and the per-g-point kernels */ \
+int rrx_lw_solver_noscat_fractions_optimal##SFX( \
+        int ncol, int nlay, int ngpt, int nbnd, RrxBool top_at_1, const F* weights, \
+        const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands, const F* optimal_angle_fit, \
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up_loc, F* flux_dn_loc, \
+        const F* sfc_src_jac, F* flux_up_jac, F* secants_out, void* stream); \
 /* ---- Optical_props_kernels_cuda : include_kernels_cuda/optical_props_kernels_cuda.h:33-56 ---- */ \
 int rrx_increment_1scalar_by_1scalar##SFX(int ncol, int nlay, int ngpt, F* tau_inout, const F* tau_in, void* stream); \
 int rrx_increment_2stream_by_2stream##SFX(int ncol, int nlay, int ngpt, F* tau_inout, F* ssa_inout, F* g_inout, const F* tau_in, const F* ssa_in, const F* g_in, void* stream); \

@@ -50,5 +50,23 @@ namespace Rte_solver_kernels_cuda
             const int ncol, const int ngpt, const int n_quad_angs, const int max_gauss_pts,
             const Float* Gauss_Ds, Float* secants)
     { RRX_CALL(rrx_lw_secants_array, ncol, ngpt, n_quad_angs, max_gauss_pts, Gauss_Ds, secants); }
+
+    /* optimal-angle secants (no counterpart in the reference): secants(ncol, ngpt) from the total optical depth of each column and
+     * g-point and the k-distribution's optimal_angle_fit(2, nbnd) */
+    inline void lw_optimal_secants(
+            const int ncol, const int nlay, const int ngpt, const int nbnd, const int* gpoint_bands,
+            const Float* optimal_angle_fit, const Float* tau, Float* secants)
+    { RRX_CALL(rrx_lw_optimal_secants, ncol, nlay, ngpt, nbnd, gpoint_bands, optimal_angle_fit, tau, secants); }
+
+    /* the fused broadband solve on Planck fractions with those secants formed inside the kernel (Jacobian pair and secants_out optional) */
+    inline void lw_solver_noscat_fractions_optimal(
+            const int ncol, const int nlay, const int ngpt, const int nbnd, const Bool top_at_1, const Float* weights,
+            const Float* tau, const Float* pfrac, const Float* blay, const Float* blev, const int* gpoint_bands,
+            const Float* optimal_angle_fit, const Float* sfc_emis, const Float* sfc_src, const Float* inc_flux,
+            Float* flux_up_loc, Float* flux_dn_loc, const Float* sfc_src_jac, Float* flux_up_jac, Float* secants_out)
+    {
+        RRX_CALL(rrx_lw_solver_noscat_fractions_optimal, ncol, nlay, ngpt, nbnd, top_at_1, weights, tau, pfrac, blay, blev, gpoint_bands,
+                 optimal_angle_fit, sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc, sfc_src_jac, flux_up_jac, secants_out);
+    }
 }
 #endif

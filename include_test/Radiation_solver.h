@@ -97,10 +97,16 @@ class Radiation_solver_longwave
             n_gauss_angles = n;
         }
         int get_gauss_angles() const { return n_gauss_angles; }
+        // Optimal angles (default off): the secant of the one LW angle is the coefficient file's optimal_angle_fit of the column's
+        // total optical depth per g-point (compute_optimal_angles / lw_Ds of current RTE+RRTMGP); with the broadband solvers the fused
+        // solver forms it itself (rrx_lw_solver_noscat_fractions_optimal). Throws for a file without the fit; solve_gpu throws with
+        // set_gauss_angles(> 1) or the by-band solvers in use.
+        void set_optimal_angles(const bool b);
+        bool get_optimal_angles() const { return optimal_angles; }
 
     private:
         int column_sorting = -1, sort_decided = -1;
-        bool column_padding = true, reordered_call = false, jacobian = false;
+        bool column_padding = true, reordered_call = false, jacobian = false, optimal_angles = false;
         int n_gauss_angles = 1;
         Array_gpu<Float,2> lw_flux_up_jac;
         std::unique_ptr<Gas_optics_rrtmgp_gpu> kdist_gpu;

@@ -30,6 +30,9 @@ int   rrx_cxx_sunlit_columns(void* handle, int sunlit);
 int   rrx_cxx_lw_jacobian(void* handle, int on);
 /* set_gauss_angles of the longwave solver: n = 1..4 quadrature angles (default 1); another value is an error */
 int   rrx_cxx_lw_gauss_angles(void* handle, int n);
+/* set_optimal_angles of the longwave solver (0 = off, the default): the one angle's secant from the coefficient file's
+   optimal_angle_fit; an error for a file without it, and at the solve together with more than one angle */
+int   rrx_cxx_lw_optimal_angles(void* handle, int on);
 int   rrx_cxx_lw_flux_up_jac(void* handle, Real* out, void* stream);
 /* one LW + one SW solve_gpu (fluxes only) enqueued on `stream`; DEVICE arrays: (ncol,nlay) / (ncol,nlay+1) fields, (ncol) vectors,
    surface properties (nbnd,ncol); lwp, iwp, rel, dei NULL without clouds; out7: seven (ncol, nlay+1) arrays for LW up, dn, net and

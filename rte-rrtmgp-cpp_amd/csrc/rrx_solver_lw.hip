@@ -324,8 +324,14 @@ __device__ unsigned long long g_lw_clk[16][8];
 // sup (3K) are live together, which the one-angle form avoids: the nine-layer forms spill. The source terms pfrac*B_lay
 // and sqrt(pfrac*pfrac')*B_lev are recomputed per angle: holding them takes 2K+1 more registers per column.
 // Everything MU adds is written so that the one-angle forms keep the statements, and with them the code, they had before it.
+// OPT (optimal-angle secants, rrx_lw_solver_noscat_fractions_optimal): no secants array is read. At the top of a g-point, when its
+// loads have landed, each lane adds the tau of its K layers, a butterfly over the level-lanes (ds_bpermute, stride CL) gives every
+// lane its wave's sum, the W waves of the column group exchange theirs through LDS (xsum) behind a barrier of their own, and every
+// lane forms D = fit(1,b)*exp(-S) + fit(2,b) from the band's two coefficients, which are refreshed where the band's Planck functions
+// are. Every lane of a column adds the same values in the same order, so all of them hold the same D. The lanes ll = 0 of the
+// column group's first wave write D to secants_out(col, gpt) when it is given. One angle, Planck-lite inputs, no by-band form.
 template<typename F, int V, int K, int W, int CLT, bool LITE, bool GS = false, int EV = RRX_LW_EV, int NW = (W > 4 ? W : 4), bool BND = false,
-         bool JAC = false, bool MU = false>
+         bool JAC = false, bool MU = false, bool OPT = false>
 __global__ void __launch_bounds__(64*NW, (NW > W) ? RRX_LW_F32_WAVES : (NW > 4 ? 1 : 2))
 lw_noscat_bb_kernel(
         const int ncol, const int nlay, const int ngpt, const int top_at_1,
@@ -335,11 +341,13 @@ lw_noscat_bb_kernel(
         const F* __restrict__ sfc_emis, const F* __restrict__ sfc_src, const F* __restrict__ inc_flux,
         F* __restrict__ flux_up, F* __restrict__ flux_dn, const int gper, const size_t part_stride,
         const int* __restrict__ band_lims, const F* __restrict__ sfc_src_jac = nullptr, F* __restrict__ flux_up_jac = nullptr,
-        const int nmus = 1)
+        const int nmus = 1, const F* __restrict__ opt_fit = nullptr, F* __restrict__ secants_out = nullptr)
 {
     static_assert(!(GS && BND), "a by-band launch is its own g-point split");
     static_assert(!(JAC && BND), "no by-band Jacobian");
     static_assert(!MU || (LITE && !BND), "several angles: Planck-lite inputs, no by-band form");
+    static_assert(!OPT || (LITE && !BND), "optimal angles: Planck-lite inputs, no by-band form");
+    static_assert(!(OPT && MU), "optimal angles are one quadrature angle");
     // GS: blockIdx.y = g-point range [g_lo, g_hi) of this workgroup; its sums go to partial array blockIdx.y
     const int g_lo = BND ? max(band_lims[2*blockIdx.y] - 1, 0) : (GS ? blockIdx.y*gper : 0);
     const int g_hi = BND ? min(band_lims[2*blockIdx.y+1], ngpt) : (GS ? min(ngpt, g_lo + gper) : ngpt);
@@ -353,6 +361,7 @@ lw_noscat_bb_kernel(
     const int bx = ((NW/W)*CL*V*sizeof(F) < 128) ? xcd_contiguous(blockIdx.x, gridDim.x) : int(blockIdx.x);
     const int wave_col0 = (bx*(NW/W) + wave/W) * (CL*V);
     __shared__ F xch[4*V][NW][CL];
+    __shared__ F xsum[OPT ? V : 1][NW][CL];              // OPT: each wave's sum of tau over its layers
     __shared__ F lds_b[LITE ? (2*K+1)*V : 1][64*NW];     // per-thread columns: B_lay[K], B_lev[K+1] of the current band
     constexpr bool ETAB = sizeof(F) == 8 && RRX_LW_EXP_TABLE;
     __shared__ F lds_etab[ETAB ? 64 : 1];
@@ -422,7 +431,7 @@ lw_noscat_bb_kernel(
         }
         const size_t sfc = size_t(g)*ncl + icol;
         L.emis = load_cols<F,V>(sfc_emis + sfc); L.ssrc = load_cols<F,V>(sfc_src + sfc);
-        if constexpr (!MU) L.D = load_cols<F,V>(secants + sfc);
+        if constexpr (!MU && !OPT) L.D = load_cols<F,V>(secants + sfc);
         if (inc_flux != nullptr) L.inc = load_cols<F,V>(inc_flux + sfc);
         if constexpr (JAC) J = load_cols<F,V>(sfc_src_jac + sfc);
     };
@@ -438,6 +447,7 @@ lw_noscat_bb_kernel(
     Vec<F,V> d_next, c_emis, c_ssrc, c_inc;
     F scale_mu;
     if constexpr (MU) d_next = load_cols<F,V>(secants + size_t(g_lo)*ncl + icol);
+    F fit1 = F(0.), fit2 = F(0.);                               // OPT: the band's two coefficients
 
 #if RRX_LW_TIMING
     unsigned long long lw_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lw_t = __builtin_readcyclecounter();
@@ -471,7 +481,45 @@ lw_noscat_bb_kernel(
                 #pragma unroll
                 for (int v=0; v<V; ++v) lds_b[(K+j)*V+v][tid] = x.v[v];
             }
+            if constexpr (OPT) { fit1 = opt_fit[2*ib]; fit2 = opt_fit[2*ib+1]; }
         }
+    }
+
+    if constexpr (OPT)
+    {
+        F s[V];
+        #pragma unroll
+        for (int v=0; v<V; ++v) s[v] = F(0.);
+        #pragma unroll
+        for (int j=0; j<K; ++j)
+        {
+            const bool valid = (t0 + j) < nlay;
+            #pragma unroll
+            for (int v=0; v<V; ++v) s[v] += valid ? cur.a0[j].v[v] : F(0.);
+        }
+        #pragma unroll
+        for (int d=1; d<LL; d<<=1)
+            #pragma unroll
+            for (int v=0; v<V; ++v) s[v] += shfl(s[v], lane ^ (d*CL));
+        if (ll == 0)
+        {
+            #pragma unroll
+            for (int v=0; v<V; ++v) xsum[v][wave][cl] = s[v];
+        }
+        RRX_LW_T(4)
+        __syncthreads();       // (the next write of xsum lies behind both scan barriers of this g-point)
+        #pragma unroll
+        for (int v=0; v<V; ++v)
+        {
+            F t = F(0.);
+            #pragma unroll
+            for (int w=0; w<W; ++w) t += xsum[v][w0+w][cl];
+            F e;
+            if constexpr (ETAB) e = exp_neg(-t, lds_etab); else e = exp_neg(-t);
+            cur.D.v[v] = fit1*e + fit2;
+        }
+        if (secants_out != nullptr && writer && ll == 0 && h == 0) store_cols<F,V>(secants_out + size_t(igpt)*ncl + icol, cur.D);
+        RRX_LW_T(5)
     }
 
     // level source at sweep level t0+j for column v
@@ -755,6 +803,48 @@ __global__ void lw_secants_array_kernel(
 }
 
 
+// Optimal-angle secants on their own (rrx_lw_optimal_secants; upstream's compute_optimal_angles): D(col, gpt) = fit(1,b)*exp(-S) +
+// fit(2,b) with S the sum of tau(col, :, gpt) over the layers, added in layer-index order from zero; b = gpoint_bands(gpt). One pass
+// over tau, the column on the lanes (128-B rows), one g-point per workgroup row. fit is (2, nbnd), first index fastest.
+template<typename F>
+__global__ void __launch_bounds__(256)
+lw_optimal_secants_kernel(
+        const int ncol, const int nlay, const int* __restrict__ gpoint_bands, const F* __restrict__ fit,
+        const F* __restrict__ tau, F* __restrict__ secants)
+{
+    const int icol = blockIdx.x*blockDim.x + threadIdx.x;
+    const int igpt = blockIdx.y;
+    if (icol >= ncol) return;
+    const size_t ncl = size_t(ncol);
+    const F* __restrict__ t = tau + size_t(igpt)*ncl*nlay + icol;
+    F s = F(0.);
+    #pragma unroll 8
+    for (int ilay=0; ilay<nlay; ++ilay) s += t[size_t(ilay)*ncl];
+    const int ib = gpoint_bands[igpt] - 1;
+    secants[size_t(igpt)*ncl + icol] = fit[2*ib] * exp(-s) + fit[2*ib+1];
+}
+
+template<typename F>
+int lw_optimal_secants_impl(const int ncol, const int nlay, const int ngpt, const int nbnd, const int* gpoint_bands,
+                            const F* optimal_angle_fit, const F* tau, F* secants, void* stream)
+{
+    const char* entry = "rrx_lw_optimal_secants";
+    const char* bad = nullptr;
+    if (ncol <= 0) bad = "ncol must be positive";
+    else if (nlay <= 0) bad = "nlay must be positive";
+    else if (ngpt <= 0 || ngpt > 65535) bad = "ngpt must be 1..65535";
+    else if (nbnd <= 0) bad = "nbnd must be positive";
+    else if (gpoint_bands == nullptr) bad = "gpoint_bands is null";
+    else if (optimal_angle_fit == nullptr) bad = "optimal_angle_fit is null";
+    else if (tau == nullptr) bad = "tau is null";
+    else if (secants == nullptr) bad = "secants is null";
+    if (bad != nullptr) { set_error(std::string(entry) + ": " + bad); return 1; }
+    RRX_TRY
+    lw_optimal_secants_kernel<F><<<dim3(ceil_div(ncol, 256), ngpt), 256, 0, static_cast<hipStream_t>(stream)>>>(
+            ncol, nlay, gpoint_bands, optimal_angle_fit, tau, secants);
+    RRX_CATCH(entry)
+}
+
 // the general kernel for one quadrature angle; false when the columns are taller than its largest K (the caller takes the serial
 // kernel)
 template<typename F, int V>
@@ -790,15 +880,18 @@ struct BbArgs
     const int* band_lims; int nbnd;             // by-band form: flux_up/dn are (ncol, nlev, nbnd) band sums
     const F* sfc_src_jac; F* flux_up_jac;       // JAC: (ngpt, ncol) in, (ncol, nlev) out
     int nmus;                                   // MU: quadrature angles; secants (ncol, ngpt, nmus), weights (nmus)
+    const F* opt_fit = nullptr; F* secants_out = nullptr;      // OPT: fit (2, nbnd) in, the secants used (ncol, ngpt) out or null
 };
 
 // one tiling of the fused broadband kernel (lw_noscat_bb_kernel); false when the shape is outside it (the caller tries the next one).
 // LITE: lay_source = pfrac, lev_source unused. JAC: the Jacobian form, in the geometry and g-point split the fluxes alone would take
-// (so they come out bit for bit the same). MU: the several-angle form (a.nmus angles), same geometry and split again.
-template<typename F, int V, int W, int CLT, bool LITE, int NW, bool JAC, bool MU>
+// (so they come out bit for bit the same). MU: the several-angle form (a.nmus angles), same geometry and split again. OPT: the
+// optimal-angle form, same geometry and split again.
+template<typename F, int V, int W, int CLT, bool LITE, int NW, bool JAC, bool MU, bool OPT = false>
 bool launch_bb2(hipStream_t st, const BbArgs<F>& a)
 {
     static_assert(!MU || LITE, "several angles: Planck-lite inputs only");
+    static_assert(!OPT || (LITE && !MU), "optimal angles: Planck-lite inputs, one angle");
     if (size_t(a.ncol)*(a.nlay+1) >= (size_t(1) << 31)) return false;      // 32-bit element offsets inside a g-point slab
     const int groups = ceil_div(a.ncol, (NW/W)*CLT*V);
     const int need = ceil_div(a.nlay+1, (64/CLT)*W);
@@ -810,7 +903,7 @@ bool launch_bb2(hipStream_t st, const BbArgs<F>& a)
         else return with_k<2, 3, 5>(need, launch);
     };
     const size_t nlevcol = size_t(a.ncol)*(a.nlay+1);
-    if (!JAC && !MU && a.band_lims != nullptr)
+    if (!JAC && !MU && !OPT && a.band_lims != nullptr)
     {
         // one band per workgroup (grid.y = band): no store inside the g-point loop, no partial arrays, no allocation. Planck-lite
         // inputs only (the by-band entry is rrx_lw_solver_noscat_fractions_byband).
@@ -840,10 +933,10 @@ bool launch_bb2(hipStream_t st, const BbArgs<F>& a)
     const dim3 grid(groups, nsplit);
     with_tiling_k([&](auto kk) { with_flag(nsplit > 1, [&](auto gs)
     {
-        lw_noscat_bb_kernel<F,V,decltype(kk)::value,W,CLT,LITE,decltype(gs)::value,RRX_LW_EV,NW,false,JAC,MU><<<grid, 64*NW, 0, st>>>(
+        lw_noscat_bb_kernel<F,V,decltype(kk)::value,W,CLT,LITE,decltype(gs)::value,RRX_LW_EV,NW,false,JAC,MU,OPT><<<grid, 64*NW, 0, st>>>(
             a.ncol, a.nlay, a.ngpt, a.top_at_1, a.secants, a.weights, a.tau, a.lay_source, a.lev_source, a.blay, a.blev,
             a.gpoint_bands, a.sfc_emis, a.sfc_src, a.inc_flux, out_up, out_dn, gper, nlevcol, nullptr, a.sfc_src_jac, out_jc,
-            MU ? a.nmus : 1);
+            MU ? a.nmus : 1, OPT ? a.opt_fit : nullptr, OPT ? a.secants_out : nullptr);
     }); });
     if (nsplit > 1)      // (out_up, out_dn [, out_jc] lie behind each other in the scratch block)
         sum_ranges_kernel<F,NARR><<<dim3(ceil_div(nlevcol, 256), NARR), 256, 0, st>>>(nlevcol, nsplit, out_up, a.flux_up, a.flux_dn,
@@ -853,30 +946,33 @@ bool launch_bb2(hipStream_t st, const BbArgs<F>& a)
 
 // broadband fluxes from tau + (lay_source, lev_source) [LITE = false] or tau + Planck fractions and band Planck functions
 // [LITE = true] in the one-kernel form; false when the shape is outside its tilings (the caller takes another path)
-// [JAC = true: flux_up_jac too, from the same forms in the same order; MU = true: nmus angles, secants (ncol, ngpt, nmus)]
-template<typename F, bool LITE, bool JAC = false, bool MU = false>
+// [JAC = true: flux_up_jac too, from the same forms in the same order; MU = true: nmus angles, secants (ncol, ngpt, nmus);
+//  OPT = true: secants formed in the kernel from opt_fit (2, nbnd), written to secants_out when it is given]
+template<typename F, bool LITE, bool JAC = false, bool MU = false, bool OPT = false>
 bool lw_fused_broadband(
         hipStream_t st, const int ncol, const int nlay, const int ngpt, const int top_at_1,
         const F* secants, const F* weights, const F* tau, const F* lay_source, const F* lev_source,
         const F* blay, const F* blev, const int* gpoint_bands,
         const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn,
         const int* band_lims = nullptr, const int nbnd = 0 /* by-band form (launch_bb2) */,
-        const F* sfc_src_jac = nullptr, F* flux_up_jac = nullptr, const int nmus = 1)
+        const F* sfc_src_jac = nullptr, F* flux_up_jac = nullptr, const int nmus = 1,
+        const F* opt_fit = nullptr, F* secants_out = nullptr)
 {
     const BbArgs<F> a{ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source, blay, blev, gpoint_bands,
-                      sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac, nmus};
+                      sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac, nmus,
+                      opt_fit, secants_out};
     if constexpr (sizeof(F) == 8)
     {
         // (Round 4 measured six waves x six layers per column group -- 384-thread workgroups, three waves per SIMD, 168 VGPRs with
         //  108-124 B of scratch: 4.2-4.7 ms against 2.7 for this form, profiles/r04_fp32_geometry_ab.txt.)
-        if (launch_bb2<F,1,4,16,LITE,4,JAC,MU>(st, a)) return true;
+        if (launch_bb2<F,1,4,16,LITE,4,JAC,MU,OPT>(st, a)) return true;
         // 144 ... 287 layers: eight wavefronts per column group
-        if (launch_bb2<F,1,8,16,LITE,8,JAC,MU>(st, a)) return true;
+        if (launch_bb2<F,1,8,16,LITE,8,JAC,MU,OPT>(st, a)) return true;
         // 288 ... 575 layers (round 4: RCEMIP's default is 256 levels, LES grids with a background profile on top exceed 288): the same
         // eight waves with 8 x 8 lanes -- 64 levels per wave at nine layers per lane, 64-B rows (the other half of each 128-B line
         // belongs to the next column group: twice the L2 fetches, on a kernel that stands at a quarter of the HBM roof). Beyond that
         // the one-thread-per-column kernels take over.
-        return launch_bb2<F,1,8,8,LITE,8,JAC,MU>(st, a);
+        return launch_bb2<F,1,8,8,LITE,8,JAC,MU,OPT>(st, a);
     }
     else
     {
@@ -885,17 +981,17 @@ bool lw_fused_broadband(
         // W = 6 at three, K = 5 / W = 8 at four: 1.82 / 1.88 / 1.95 ms at C4 against 1.31 for two columns per lane with the sums in
         // LDS, profiles/r04_fp32_geometry_ab.txt): the LW chain per g-point is short, so halving the wavefronts per column wins.
         // The one-column form stays for odd column counts (variant 15 forces it for tests).
-        if (tuning().lw_variant == 15 && launch_bb2<F,1,4,16,LITE,8,JAC,MU>(st, a)) return true;
+        if (tuning().lw_variant == 15 && launch_bb2<F,1,4,16,LITE,8,JAC,MU,OPT>(st, a)) return true;
         // 16 x 4 lanes with two columns per lane (128-B rows, K = 9) ahead of 8 x 8 lanes with four. Measured at C4 in the fractions
         // form: 1.77 against 3.26 ms (the four-column lane state spills); the latter still takes 144 ... 159 layers.
-        if (ncol % 2 == 0 && launch_bb2<F,2,4,16,LITE,4,JAC,MU>(st, a)) return true;
-        if (ncol % 4 == 0 && launch_bb2<F,4,4,8,LITE,4,JAC,MU>(st, a)) return true;
+        if (ncol % 2 == 0 && launch_bb2<F,2,4,16,LITE,4,JAC,MU,OPT>(st, a)) return true;
+        if (ncol % 4 == 0 && launch_bb2<F,4,4,8,LITE,4,JAC,MU,OPT>(st, a)) return true;
         // 144 ... 287 layers: eight wavefronts per column group
-        if (ncol % 2 == 0 && launch_bb2<F,2,8,16,LITE,8,JAC,MU>(st, a)) return true;
+        if (ncol % 2 == 0 && launch_bb2<F,2,8,16,LITE,8,JAC,MU,OPT>(st, a)) return true;
         // 288 ... 575 layers: eight waves of 8 x 8 lanes (see fp64)
-        if (ncol % 2 == 0 && launch_bb2<F,2,8,8,LITE,8,JAC,MU>(st, a)) return true;
+        if (ncol % 2 == 0 && launch_bb2<F,2,8,8,LITE,8,JAC,MU,OPT>(st, a)) return true;
         // odd column counts: one column per lane
-        return launch_bb2<F,1,4,16,LITE,8,JAC,MU>(st, a);
+        return launch_bb2<F,1,4,16,LITE,8,JAC,MU,OPT>(st, a);
     }
 }
 
@@ -1018,18 +1114,27 @@ int planck_sources_from_fractions_impl(int ncol, int nlay, int ngpt, const int* 
 // The fractions entries outside the one-kernel tilings (columns taller than 575 layers, variants 1 and 7): the Planck sources are
 // rebuilt and the general entry writes per-g-point fluxes [up | dn], and the Jacobian behind them when sfc_src_jac is given, into ONE
 // lease of the stream's workspace: [up | dn | (Jacobian) | lay_source | lev_source]. Returns that block, or null with the message set;
-// the caller sums it while the lease lives.
+// the caller sums it while the lease lives. With opt_fit the secants are the optimal-angle ones (one angle), produced by
+// lw_optimal_secants_kernel into secants_out or, when that is null, into (ncol, ngpt) more elements at the end of the lease.
 template<typename F>
 const F* lw_fractions_per_gpoint(
         WorkspaceLease& lease, const int ncol, const int nlay, const int ngpt, const Bool top_at_1,
         const F* secants, const F* weights, const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands,
-        const F* sfc_emis, const F* sfc_src, const F* inc_flux, const F* sfc_src_jac, void* stream, const int nmus = 1)
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, const F* sfc_src_jac, void* stream, const int nmus = 1,
+        const F* opt_fit = nullptr, const int nbnd = 0, F* secants_out = nullptr)
 {
     const size_t n_lay = size_t(ncol)*nlay*ngpt, n_lev = size_t(ncol)*(nlay+1)*ngpt;
     const size_t nout = (sfc_src_jac != nullptr) ? 3 : 2;
-    F* ws = lease.get<F>(nout*n_lev + n_lay + n_lev);
+    const size_t n_sec = (opt_fit != nullptr && secants_out == nullptr) ? size_t(ncol)*ngpt : 0;
+    F* ws = lease.get<F>(nout*n_lev + n_lay + n_lev + n_sec);
     F* lay = ws + nout*n_lev; F* lev = lay + n_lay;
     F* jac = (sfc_src_jac != nullptr) ? ws + 2*n_lev : nullptr;
+    if (opt_fit != nullptr)
+    {
+        F* sec = (secants_out != nullptr) ? secants_out : lev + n_lev;
+        if (lw_optimal_secants_impl<F>(ncol, nlay, ngpt, nbnd, gpoint_bands, opt_fit, tau, sec, stream) != 0) return nullptr;
+        secants = sec;
+    }
     if (planck_sources_from_fractions_impl<F>(ncol, nlay, ngpt, gpoint_bands, pfrac, blay, blev, lay, lev, stream) != 0 ||
         lw_solver_noscat_impl<F>(ncol, nlay, ngpt, top_at_1, nmus, secants, weights, tau, lay, lev, sfc_emis, sfc_src, inc_flux,
                                  ws, ws + n_lev, Bool(0), (F*)nullptr, (F*)nullptr, Bool(jac != nullptr), sfc_src_jac, jac, stream) != 0)
@@ -1151,6 +1256,58 @@ int lw_solver_noscat_fractions_angles_impl(
     RRX_CATCH(entry)
 }
 
+// One angle whose secant is the optimal-angle fit of the column's total optical depth (rrx_lw_solver_noscat_fractions_optimal), with
+// the Jacobian when the pair is given: the one-kernel form's OPT variant where the tilings reach, otherwise lw_optimal_secants_kernel
+// and the g-point sums of lw_fractions_per_gpoint's fluxes for those secants
+template<typename F>
+int lw_solver_noscat_fractions_optimal_impl(
+        const int ncol, const int nlay, const int ngpt, const int nbnd, const Bool top_at_1, const F* weights,
+        const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands, const F* optimal_angle_fit,
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up_loc, F* flux_dn_loc, const F* sfc_src_jac, F* flux_up_jac,
+        F* secants_out, void* stream)
+{
+    const char* entry = "rrx_lw_solver_noscat_fractions_optimal";
+    const char* bad = nullptr;
+    if (ncol <= 0) bad = "ncol must be positive";
+    else if (nlay <= 0) bad = "nlay must be positive";
+    else if (ngpt <= 0 || ngpt > 65535) bad = "ngpt must be 1..65535";
+    else if (nbnd <= 0) bad = "nbnd must be positive";
+    else if (weights == nullptr) bad = "weights is null";
+    else if (gpoint_bands == nullptr) bad = "gpoint_bands is null";
+    else if (optimal_angle_fit == nullptr) bad = "optimal_angle_fit is null";
+    else if (flux_up_loc == nullptr) bad = "flux_up_loc is null";
+    else if (flux_dn_loc == nullptr) bad = "flux_dn_loc is null";
+    else if (sfc_src_jac != nullptr && flux_up_jac == nullptr) bad = "flux_up_jac is null while sfc_src_jac is given";
+    else if (sfc_src_jac == nullptr && flux_up_jac != nullptr) bad = "sfc_src_jac is null while flux_up_jac is given";
+    if (bad != nullptr) { set_error(std::string(entry) + ": " + bad); return 1; }
+    const bool jac = sfc_src_jac != nullptr;
+    RRX_TRY
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    bool fused = false;
+    if (lw_fused_allowed())
+        with_flag(jac, [&](auto j)
+        {
+            fused = lw_fused_broadband<F,true,decltype(j)::value,false,true>(
+                        st, ncol, nlay, ngpt, top_at_1, (const F*)nullptr, weights, tau, pfrac, (const F*)nullptr, blay, blev, gpoint_bands,
+                        sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc, (const int*)nullptr, 0, sfc_src_jac, flux_up_jac, 1,
+                        optimal_angle_fit, secants_out);
+        });
+    if (!fused)
+    {
+        WorkspaceLease lease(st);
+        const F* ws = lw_fractions_per_gpoint<F>(lease, ncol, nlay, ngpt, top_at_1, (const F*)nullptr, weights, tau, pfrac, blay, blev,
+                                                 gpoint_bands, sfc_emis, sfc_src, inc_flux, sfc_src_jac, stream, 1,
+                                                 optimal_angle_fit, nbnd, secants_out);
+        if (ws == nullptr) return 1;                                 // (the message is set)
+        const size_t nlevcol = size_t(ncol)*(nlay+1);
+        const int nb = ceil_div(nlevcol, 256);
+        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws, flux_up_loc);
+        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws + nlevcol*ngpt, flux_dn_loc);
+        if (jac) sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws + 2*nlevcol*ngpt, flux_up_jac);
+    }
+    RRX_CATCH(entry)
+}
+
 // host-model update between radiation calls (rrx_lw_flux_up_adjust): d = jac * (t_new - t_old) of the level's column;
 // flux_up += d, flux_net -= d
 template<typename F>
@@ -1229,7 +1386,7 @@ int rrx_set_lw_variant(int v)
 }
 #if RRX_LW_TIMING
 // diagnostic build only: phase clocks per wavefront of a workgroup (out[16][8]: sources + transmissivities, down scan, up scan, replays + sums,
-// -, -, barrier waits, loop top) summed over the workgroups since the last call, then reset
+// OPT's sum of tau, OPT's barrier + secant, barrier waits, loop top) summed over the workgroups since the last call, then reset
 int rrx_lw_timing(unsigned long long* out)
 {
     unsigned long long zero[16*8] = {0};
@@ -1323,7 +1480,19 @@ int rrx_lw_solver_noscat_fractions_angles##SFX( \
 } \
 int rrx_lw_flux_up_adjust##SFX(int ncol, int nlev, const F* flux_up_jac, const F* t_sfc_old, const F* t_sfc_new, \
         F* flux_up, F* flux_net, void* stream) \
-{ return lw_flux_up_adjust_impl<F>(ncol, nlev, flux_up_jac, t_sfc_old, t_sfc_new, flux_up, flux_net, stream); }
+{ return lw_flux_up_adjust_impl<F>(ncol, nlev, flux_up_jac, t_sfc_old, t_sfc_new, flux_up, flux_net, stream); } \
+int rrx_lw_optimal_secants##SFX(int ncol, int nlay, int ngpt, int nbnd, const int* gpoint_bands, const F* optimal_angle_fit, \
+        const F* tau, F* secants, void* stream) \
+{ return lw_optimal_secants_impl<F>(ncol, nlay, ngpt, nbnd, gpoint_bands, optimal_angle_fit, tau, secants, stream); } \
+int rrx_lw_solver_noscat_fractions_optimal##SFX( \
+        int ncol, int nlay, int ngpt, int nbnd, Bool top_at_1, const F* weights, \
+        const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands, const F* optimal_angle_fit, \
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up_loc, F* flux_dn_loc, \
+        const F* sfc_src_jac, F* flux_up_jac, F* secants_out, void* stream) \
+{ \
+    return lw_solver_noscat_fractions_optimal_impl<F>(ncol, nlay, ngpt, nbnd, top_at_1, weights, tau, pfrac, blay, blev, gpoint_bands, \
+            optimal_angle_fit, sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc, sfc_src_jac, flux_up_jac, secants_out, stream); \
+}
 
 RRX_DEFINE_LW_FRACTIONS(double, _f64)
 RRX_DEFINE_LW_FRACTIONS(float, _f32)

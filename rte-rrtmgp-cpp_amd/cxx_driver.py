@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 class CxxDriver:
     def __init__(self, be, kd_lw0, kd_sw0, atm, cloud_luts0=None, column_block=16384, broadband=True, sort_mode=-1, pad=True,
-                 sunlit=False, jacobian=False, n_gauss_angles=1):
+                 sunlit=False, jacobian=False, n_gauss_angles=1, optimal_angles=False):
         import torch
         self.torch, self.be, self.atm = torch, be, atm
         self.f64 = be.np_dtype == np.float64
@@ -45,6 +45,10 @@ class CxxDriver:
         self.n_gauss_angles = int(n_gauss_angles)
         if self.n_gauss_angles != 1:
             self._check(self.lib.rrx_cxx_lw_gauss_angles(self.h, self.n_gauss_angles))
+        # optimal_angles: the one LW angle's secant from the coefficient file's optimal_angle_fit (set_optimal_angles)
+        self.optimal_angles = bool(optimal_angles)
+        if self.optimal_angles:
+            self._check(self.lib.rrx_cxx_lw_optimal_angles(self.h, 1))
         # jacobian: each step also fills self.lw_flux_up_jac (nlev, ncol), d lw_flux_up / d t_sfc [W m-2 K-1] (set_jacobian)
         self.jacobian = bool(jacobian)
         if self.jacobian:

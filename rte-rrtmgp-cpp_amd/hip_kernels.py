@@ -80,6 +80,7 @@ class HipKernels:
         out = {}
         for k, v in kd.__dict__.items():
             out[k] = self.asarray(v) if isinstance(v, np.ndarray) else v
+        out["extras"] = {n: self.asarray(a) for n, a in kd.extras.items()}          # (optimal_angle_fit)
         return KDist(**out)
 
     def _c(self, name, *args):
@@ -325,6 +326,45 @@ class HipKernels:
         self._c("lw_solver_noscat_fractions_angles", ncol, nlay, ngpt, BoolArg(top_at_1), nmus, secants, weights, tau,
                 fr["pfrac"], fr["blay"], fr["blev"], kd.gpoint_bands, sfc_emis, fr["sfc_src"], inc_flux, flux_up, flux_dn,
                 fr["sfc_src_jac"] if jacobian else None, out.get("flux_up_jac"))
+        return out
+
+    @staticmethod
+    def optimal_fit_abi(kd):
+        """kd.optimal_angle_fit (2, nbnd) in the C ABI's layout: (2, nbnd) with the first index fastest, i.e. a (nbnd, 2) tensor"""
+        if getattr(kd, "optimal_angle_fit", None) is None:
+            raise ValueError("the k-distribution carries no optimal_angle_fit")
+        return kd.optimal_angle_fit.t().contiguous()
+
+    def lw_optimal_secants(self, kd, tau, fit=None, secants=None):
+        """Optimal-angle secants (ngpt, ncol) of tau (ngpt, nlay, ncol): D = fit[0, b]*exp(-sum of tau over the layers) + fit[1, b]
+        for the band b of the g-point. fit: optimal_fit_abi(kd) (default) or a (nbnd, 2) tensor of one's own."""
+        ngpt, nlay, ncol = tau.shape
+        fit = self.optimal_fit_abi(kd) if fit is None else fit
+        secants = self.empty((ngpt, ncol)) if secants is None else secants
+        self._c("lw_optimal_secants", ncol, nlay, ngpt, int(fit.shape[0]), kd.gpoint_bands, fit, tau, secants)
+        return secants
+
+    def lw_solver_noscat_fractions_optimal(self, top_at_1, kd, weights, tau, fr, sfc_emis, fit=None, inc_flux=None, flux_up=None,
+                                           flux_dn=None, flux_up_jac=None, jacobian=False, secants_out=None, keep_secants=False):
+        """lw_solver_noscat_fractions [_jac with jacobian=True] for one angle whose secant is the optimal-angle fit, formed inside the
+        fused kernel from the g-point it holds. weights: (1,). keep_secants / secants_out: the (ngpt, ncol) secants the solve used come
+        back under "secants"."""
+        ngpt, nlay, ncol = tau.shape
+        if int(weights.shape[0]) != 1:
+            raise ValueError("optimal angles are one quadrature angle: weights must hold one value")
+        fit = self.optimal_fit_abi(kd) if fit is None else fit
+        flux_up = self.empty((nlay+1, ncol)) if flux_up is None else flux_up
+        flux_dn = self.empty((nlay+1, ncol)) if flux_dn is None else flux_dn
+        out = dict(flux_up=flux_up, flux_dn=flux_dn)
+        if jacobian:
+            out["flux_up_jac"] = self.empty((nlay+1, ncol)) if flux_up_jac is None else flux_up_jac
+        if secants_out is None and keep_secants:
+            secants_out = self.empty((ngpt, ncol))
+        if secants_out is not None:
+            out["secants"] = secants_out
+        self._c("lw_solver_noscat_fractions_optimal", ncol, nlay, ngpt, int(fit.shape[0]), BoolArg(top_at_1), weights, tau,
+                fr["pfrac"], fr["blay"], fr["blev"], kd.gpoint_bands, fit, sfc_emis, fr["sfc_src"], inc_flux, flux_up, flux_dn,
+                fr["sfc_src_jac"] if jacobian else None, out.get("flux_up_jac"), secants_out)
         return out
 
     def lw_flux_up_adjust(self, flux_up_jac, t_sfc_old, t_sfc_new, flux_up, flux_net=None):

@@ -6,6 +6,7 @@
 #include <numeric>
 #include "Gas_optics_rrtmgp.h"
 #include "gas_optics_rrtmgp_kernels_cuda.h"
+#include "rte_solver_kernels_cuda.h"
 
 namespace
 {
@@ -527,4 +528,24 @@ void Gas_optics_rrtmgp_gpu::gas_optics(
     }
     // External source function is constant in the column.
     RRX_CALL(rrx_spread_col, ncol, this->get_ngpt(), toa_src.ptr(), solar_source_gpu.ptr());
+}
+
+void Gas_optics_rrtmgp_gpu::set_optimal_angle_fit(const Array<Float,2>& fit)
+{
+    if (fit.dim(1) != 2 || fit.dim(2) != this->get_nband())
+        throw std::runtime_error("Gas_optics_rrtmgp_gpu::set_optimal_angle_fit: optimal_angle_fit must be (2, nbnd)");
+    optimal_angle_fit_gpu = Array_gpu<Float,2>(fit);
+}
+
+void Gas_optics_rrtmgp_gpu::compute_optimal_angles(const Optical_props_arry_gpu& optical_props, Array_gpu<Float,2>& optimal_angles) const
+{
+    if (!has_optimal_angle_fit())
+        throw std::runtime_error("Gas_optics_rrtmgp_gpu::compute_optimal_angles: the coefficient file has no optimal_angle_fit");
+    const int ncol = optical_props.get_ncol(), nlay = optical_props.get_nlay(), ngpt = optical_props.get_ngpt();
+    if (ngpt != this->get_ngpt())
+        throw std::runtime_error("Gas_optics_rrtmgp_gpu::compute_optimal_angles: the optical properties are not on this k-distribution's g-points");
+    if (optimal_angles.dim(1) != ncol || optimal_angles.dim(2) != ngpt)
+        throw std::runtime_error("Gas_optics_rrtmgp_gpu::compute_optimal_angles: optimal_angles must be (ncol, ngpt)");
+    Rte_solver_kernels_cuda::lw_optimal_secants(ncol, nlay, ngpt, this->get_nband(), optical_props.get_gpoint_bands_gpu().ptr(),
+                                                optimal_angle_fit_gpu.ptr(), optical_props.get_tau().ptr(), optimal_angles.ptr());
 }

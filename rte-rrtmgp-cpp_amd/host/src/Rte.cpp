@@ -63,13 +63,42 @@ void Rte_lw_gpu::rte_lw(
     solve(optical_props, top_at_1, sources, sfc_emis, inc_flux, gpt_flux_up, gpt_flux_dn, &flux_up_jac, n_gauss_angles);
 }
 
-// flux_up_jac: null = no Jacobian
+void Rte_lw_gpu::rte_lw_optimal(
+        const std::unique_ptr<Optical_props_arry_gpu>& optical_props, const Bool top_at_1, const Source_func_lw_gpu& sources,
+        const Array_gpu<Float,2>& sfc_emis, const Array_gpu<Float,2>& inc_flux, const Array_gpu<Float,2>& optimal_angle_fit,
+        Array_gpu<Float,3>& gpt_flux_up, Array_gpu<Float,3>& gpt_flux_dn, Array_gpu<Float,3>* flux_up_jac, const int n_gauss_angles)
+{
+    if (n_gauss_angles != 1) throw std::runtime_error("rte_lw_optimal: optimal angles need one quadrature angle");
+    if (optimal_angle_fit.dim(1) != 2 || optimal_angle_fit.dim(2) != optical_props->get_nband())
+        throw std::runtime_error("rte_lw_optimal: optimal_angle_fit must be (2, nbnd)");
+    solve(optical_props, top_at_1, sources, sfc_emis, inc_flux, gpt_flux_up, gpt_flux_dn, flux_up_jac, 1, &optimal_angle_fit, nullptr);
+}
+
+void Rte_lw_gpu::rte_lw_Ds(
+        const std::unique_ptr<Optical_props_arry_gpu>& optical_props, const Bool top_at_1, const Source_func_lw_gpu& sources,
+        const Array_gpu<Float,2>& sfc_emis, const Array_gpu<Float,2>& inc_flux, const Array_gpu<Float,2>& lw_Ds,
+        Array_gpu<Float,3>& gpt_flux_up, Array_gpu<Float,3>& gpt_flux_dn, Array_gpu<Float,3>* flux_up_jac, const int n_gauss_angles)
+{
+    if (n_gauss_angles != 1) throw std::runtime_error("rte_lw_Ds: lw_Ds needs one quadrature angle");
+    if (lw_Ds.dim(1) != optical_props->get_ncol() || lw_Ds.dim(2) != optical_props->get_ngpt())
+        throw std::runtime_error("rte_lw_Ds: lw_Ds must be (ncol, ngpt)");
+    solve(optical_props, top_at_1, sources, sfc_emis, inc_flux, gpt_flux_up, gpt_flux_dn, flux_up_jac, 1, nullptr, &lw_Ds);
+}
+
+// flux_up_jac: null = no Jacobian. optimal_angle_fit (2, nbnd) or lw_Ds (ncol, ngpt), at most one of them: the secants of the one angle
 void Rte_lw_gpu::solve(
         const std::unique_ptr<Optical_props_arry_gpu>& optical_props, const Bool top_at_1, const Source_func_lw_gpu& sources,
         const Array_gpu<Float,2>& sfc_emis, const Array_gpu<Float,2>& inc_flux,
-        Array_gpu<Float,3>& gpt_flux_up, Array_gpu<Float,3>& gpt_flux_dn, Array_gpu<Float,3>* flux_up_jac, const int n_gauss_angles)
+        Array_gpu<Float,3>& gpt_flux_up, Array_gpu<Float,3>& gpt_flux_dn, Array_gpu<Float,3>* flux_up_jac, const int n_gauss_angles,
+        const Array_gpu<Float,2>* optimal_angle_fit, const Array_gpu<Float,2>* lw_Ds)
 {
     if (n_gauss_angles < 1 || n_gauss_angles > max_gauss_pts) throw std::runtime_error("rte_lw: n_gauss_angles must be 1..4");
+    const bool own_secants = optimal_angle_fit != nullptr || lw_Ds != nullptr;
+    if (own_secants && is_byband(optical_props, gpt_flux_up))
+        throw std::runtime_error("rte_lw: no by-band flux arrays with optimal angles / lw_Ds");
+    if (own_secants && flux_up_jac != nullptr &&
+        (flux_up_jac->dim(1) != gpt_flux_up.dim(1) || flux_up_jac->dim(2) != gpt_flux_up.dim(2) || flux_up_jac->dim(3) != gpt_flux_up.dim(3)))
+        throw std::runtime_error("rte_lw: flux_up_jac must be shaped like the flux arrays");
     if (is_byband(optical_props, gpt_flux_up))
     {
         if (n_gauss_angles != 1) throw std::runtime_error("rte_lw: by-band fluxes need one quadrature angle");
@@ -94,12 +123,30 @@ void Rte_lw_gpu::solve(
     const Array_gpu<Float,2>& gauss_Ds = gauss_Ds_gpu;
     const Array_gpu<Float,2>& gauss_wts_subset = gauss_wts_gpu;
 
-    Array_gpu<Float,3> secants({ncol, ngpt, n_gauss_angles});
-    Rte_solver_kernels_cuda::lw_secants_array(ncol, ngpt, n_gauss_angles, max_gauss_pts, gauss_Ds.ptr(), secants.ptr());
-
     const Bool do_broadband = (gpt_flux_up.dim(3) == 1 && ngpt != 1);
     const Bool do_jacobians = flux_up_jac != nullptr;
     const Float* inc_flux_ptr = (inc_flux.size() == 0) ? nullptr : inc_flux.ptr();
+
+    if (optimal_angle_fit != nullptr && sources.holds_fractions() && do_broadband)
+    {
+        // the fused solver forms the optimal-angle secants from the g-point it holds: no secants array at all
+        Rte_solver_kernels_cuda::lw_solver_noscat_fractions_optimal(
+                ncol, nlay, ngpt, optical_props->get_nband(), top_at_1, gauss_wts_subset.ptr(),
+                optical_props->get_tau().ptr(), sources.get_planck_frac().ptr(), sources.get_planck_lay().ptr(), sources.get_planck_lev().ptr(),
+                optical_props->get_gpoint_bands_gpu().ptr(), optimal_angle_fit->ptr(), sfc_emis_gpt.ptr(), sources.get_sfc_source().ptr(),
+                inc_flux_ptr, gpt_flux_up.ptr(), gpt_flux_dn.ptr(), do_jacobians ? sources.get_sfc_source_jac().ptr() : nullptr,
+                do_jacobians ? flux_up_jac->ptr() : nullptr, nullptr);
+        return;
+    }
+    // the secants of the solve: the caller's lw_Ds as they are, else an array of this call (optimal angles or the Gauss nodes)
+    Array_gpu<Float,3> secants_own;
+    if (lw_Ds == nullptr) secants_own.set_dims({ncol, ngpt, n_gauss_angles});
+    Array_gpu<Float,3> secants(lw_Ds != nullptr ? const_cast<Float*>(lw_Ds->ptr()) : secants_own.ptr(), {ncol, ngpt, n_gauss_angles});
+    if (optimal_angle_fit != nullptr)
+        Rte_solver_kernels_cuda::lw_optimal_secants(ncol, nlay, ngpt, optical_props->get_nband(), optical_props->get_gpoint_bands_gpu().ptr(),
+                                                    optimal_angle_fit->ptr(), optical_props->get_tau().ptr(), secants.ptr());
+    else if (lw_Ds == nullptr)
+        Rte_solver_kernels_cuda::lw_secants_array(ncol, ngpt, n_gauss_angles, max_gauss_pts, gauss_Ds.ptr(), secants.ptr());
 
     // Planck-lite state (set by Gas_optics_rrtmgp_gpu::gas_optics): the broadband solver forms the sources itself
     if (sources.holds_fractions() && do_broadband && n_gauss_angles > 1)

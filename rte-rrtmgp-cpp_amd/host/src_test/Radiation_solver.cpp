@@ -92,12 +92,22 @@ namespace
             Array<Float,2> totplnk(coef_nc.get_variable<Float>("totplnk", {n_bnds, n_internal_sourcetemps}), {n_internal_sourcetemps, n_bnds});
             Array<Float,4> planck_frac(coef_nc.get_variable<Float>("plank_fraction", {n_temps, n_press+1, n_mixingfracs, n_gpts}),
                                        {n_gpts, n_mixingfracs, n_press+1, n_temps});
-            return Gas_optics_rrtmgp_gpu(
+            Gas_optics_rrtmgp_gpu kdist(
                     gas_concs, gas_names, key_species, band2gpt, band_lims, press_ref, press_ref_trop, temp_ref, temp_ref_p, temp_ref_t,
                     vmr_ref, kmajor, kminor_lower, kminor_upper, gas_minor, identifier_minor, minor_gases_lower, minor_gases_upper,
                     minor_limits_gpt_lower, minor_limits_gpt_upper, minor_scales_with_density_lower, minor_scales_with_density_upper,
                     scaling_gas_lower, scaling_gas_upper, scale_by_complement_lower, scale_by_complement_upper,
                     kminor_start_lower, kminor_start_upper, totplnk, planck_frac, rayl_lower, rayl_upper);
+            if (coef_nc.variable_exists("optimal_angle_fit"))      // (current LW files; one without it loads as before)
+            {
+                // the file's (fit_coeffs, bnd) -> (2, nbnd) with the coefficient index fastest
+                const Array<Float,2> in(coef_nc.get_variable<Float>("optimal_angle_fit", {2, n_bnds}), {n_bnds, 2});
+                Array<Float,2> fit({2, n_bnds});
+                for (int ib=1; ib<=n_bnds; ++ib)
+                    for (int k=1; k<=2; ++k) fit({k, ib}) = in({ib, k});
+                kdist.set_optimal_angle_fit(fit);
+            }
+            return kdist;
         }
         else
         {
@@ -297,6 +307,13 @@ Radiation_solver_longwave::Radiation_solver_longwave(
         this->cloud_optics_gpu = std::make_unique<Cloud_optics_gpu>(load_and_init_cloud_optics(file_name_cloud));
 }
 
+void Radiation_solver_longwave::set_optimal_angles(const bool b)
+{
+    if (b && !kdist_gpu->has_optimal_angle_fit())
+        throw std::runtime_error("Radiation_solver_longwave::set_optimal_angles: the longwave coefficient file has no optimal_angle_fit");
+    optimal_angles = b;
+}
+
 void Radiation_solver_longwave::solve_gpu(
         const bool switch_fluxes,
         const bool switch_cloud_optics,
@@ -331,6 +348,12 @@ void Radiation_solver_longwave::solve_gpu(
     if (byband && n_gauss_angles > 1)
         throw std::runtime_error("Radiation_solver_longwave: several quadrature angles (set_gauss_angles) are not available with the "
                                  "by-band solvers (set_byband_solvers): the by-band solver has one angle");
+    if (optimal_angles && n_gauss_angles > 1)
+        throw std::runtime_error("Radiation_solver_longwave: optimal angles (set_optimal_angles) are not available with several "
+                                 "quadrature angles (set_gauss_angles): optimal angles are one angle");
+    if (optimal_angles && byband_solvers)
+        throw std::runtime_error("Radiation_solver_longwave: optimal angles (set_optimal_angles) are not available with the by-band "
+                                 "solvers (set_byband_solvers): the by-band solver has the fixed angle");
     if (jac && (lw_flux_up_jac.dim(1) != n_col || lw_flux_up_jac.dim(2) != n_lev))
     {
         lw_flux_up_jac = Array_gpu<Float,2>();
@@ -438,6 +461,17 @@ void Radiation_solver_longwave::solve_gpu(
 
         const int n_ang = n_gauss_angles;
         Array_gpu<Float,2> emis_s = whole ? Array_gpu<Float,2>(const_cast<Float*>(emis_sfc.ptr()), {n_bnd, n_in}) : emis_sfc.subset({{ {1, n_bnd}, {col_s, col_e} }});
+        // the LW solve of this block: fixed Gauss angles, or the optimal-angle secants of the k-distribution's fit (jc: null = no Jacobian)
+        auto solve_block = [&](Array_gpu<Float,3>& up, Array_gpu<Float,3>& dn, Array_gpu<Float,3>* jc)
+        {
+            if (optimal_angles)
+                rte_lw.rte_lw_optimal(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(),
+                                      kdist_gpu->get_optimal_angle_fit_gpu(), up, dn, jc, n_ang);
+            else if (jc != nullptr)
+                rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), up, dn, *jc, n_ang);
+            else
+                rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), up, dn, n_ang);
+        };
         if (whole && broadband && !switch_output_bnd_fluxes)
         {
             // one block in broadband mode: the solver writes the caller's flux arrays, the net flux follows in place (no block
@@ -449,10 +483,10 @@ void Radiation_solver_longwave::solve_gpu(
             if (jac)
             {
                 Array_gpu<Float,3> jac3(lw_flux_up_jac.ptr(), {n_col, n_lev, 1});
-                rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), up3, dn3, jac3, n_ang);
+                solve_block(up3, dn3, &jac3);
             }
             else
-                rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), up3, dn3, n_ang);
+                solve_block(up3, dn3, nullptr);
             Fluxes_kernels_cuda::net_broadband_precalc(n_col, n_lev, lw_flux_dn.ptr(), lw_flux_up.ptr(), lw_flux_net.ptr());
             continue;
         }
@@ -492,8 +526,7 @@ void Radiation_solver_longwave::solve_gpu(
         }
         if (jac)
         {
-            rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), ws.gpt_flux_up, ws.gpt_flux_dn,
-                          ws.gpt_flux_up_jac, n_ang);
+            solve_block(ws.gpt_flux_up, ws.gpt_flux_dn, &ws.gpt_flux_up_jac);
             const Float* jac_blk = ws.gpt_flux_up_jac.ptr();
             if (!broadband)
             {
@@ -503,7 +536,7 @@ void Radiation_solver_longwave::solve_gpu(
             Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_in, col_s, lw_flux_up_jac.ptr(), jac_blk);
         }
         else
-            rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), ws.gpt_flux_up, ws.gpt_flux_dn, n_ang);
+            solve_block(ws.gpt_flux_up, ws.gpt_flux_dn, nullptr);
 
         Fluxes_broadband_gpu fluxes(n_in, n_lev);
         fluxes.reduce(ws.gpt_flux_up, ws.gpt_flux_dn, ws.optical_props, top_at_1);

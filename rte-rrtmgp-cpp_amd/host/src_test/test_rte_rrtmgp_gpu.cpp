@@ -370,6 +370,7 @@ void solve_radiation(int argc, char** argv)
         {"byband-solvers",    { false, "With --output-bnd-fluxes: band sums from the fused solvers (no per-g-point fluxes)." }},
         {"heating-rates"    , { false, "Output layer heating rates lw_heating_rate / sw_heating_rate (K/s)." }},
         {"sunlit-columns"   , { false, "Shortwave on the columns with mu0 > 0 only; every SW output of the others is zero (set_sunlit_columns)." }},
+        {"lw-optimal-angles", { false, "Longwave secant per column and g-point from the coefficient file's optimal_angle_fit (one angle); not with --lw-gauss-angles > 1 or --byband-solvers." }},
         {"lw-jacobian"      , { false, "Write lw_flux_up_jac, d lw_flux_up / d t_sfc [W m-2 K-1] from the same LW solve (set_jacobian)." }},
         {"async"            , { false, "Host-model mode: vertical ordering read once, solves enqueued without synchronising." }},
         {"sort-columns"     , { true,  "Solve the columns in order of surface pressure where neighbours differ much (outputs keep the input order)." }},
@@ -392,6 +393,12 @@ void solve_radiation(int argc, char** argv)
     const bool switch_byband_solvers    = command_line_options.at("byband-solvers").first;
     const bool switch_sunlit_columns    = command_line_options.at("sunlit-columns").first;
     const bool switch_lw_jacobian       = command_line_options.at("lw-jacobian").first;
+    const bool switch_lw_optimal_angles = command_line_options.at("lw-optimal-angles").first;
+    if (switch_lw_optimal_angles && lw_gauss_angles > 1)
+        throw std::runtime_error("--lw-optimal-angles is not available with --lw-gauss-angles " + std::to_string(lw_gauss_angles) + ": "
+                                 "optimal angles are one quadrature angle");
+    if (switch_lw_optimal_angles && switch_byband_solvers)
+        throw std::runtime_error("--lw-optimal-angles is not available with --byband-solvers: the by-band solver has the fixed angle");
     if (lw_gauss_angles > 1 && switch_byband_solvers)
         throw std::runtime_error("--lw-gauss-angles " + std::to_string(lw_gauss_angles) + " is not available with --byband-solvers: "
                                  "the by-band solver has one quadrature angle");
@@ -517,6 +524,7 @@ void solve_radiation(int argc, char** argv)
         rad_lw.set_byband_solvers(switch_byband_solvers);
         rad_lw.set_jacobian(switch_lw_jacobian);
         rad_lw.set_gauss_angles(lw_gauss_angles);
+        rad_lw.set_optimal_angles(switch_lw_optimal_angles);      // (throws for a coefficient file without optimal_angle_fit)
         // (--no-sort-columns: the file's order and column count exactly; otherwise the solver pads to a multiple of 16 columns and,
         //  with --device-sort-columns, orders them itself)
         rad_lw.set_column_sorting(switch_device_sort ? 1 : (switch_sort_columns ? -1 : 0));

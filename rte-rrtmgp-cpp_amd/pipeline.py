@@ -193,7 +193,7 @@ class ResidentSolver:
     STAGES = ("lw_gas_optics", "lw_planck", "lw_solver", "lw_reduce", "sw_gas_optics", "sw_solver", "sw_reduce")
 
     def __init__(self, be, kd_lw, kd_sw, atm, do_broadband=False, overlap=False, cloud_luts=None, sort_columns=None, byband=False,
-                 sunlit=False, jacobian=False, n_gauss_angles=1):
+                 sunlit=False, jacobian=False, n_gauss_angles=1, optimal_angles=False, keep_secants=False):
         import torch
         self.torch = torch
         # byband: the step also fills self.bnd_fluxes (lw_up/lw_dn/lw_net/sw_up/sw_dn/sw_dir/sw_net, (nbnd, nlev, ncol) each, the
@@ -211,6 +211,18 @@ class ResidentSolver:
             raise ValueError("ResidentSolver: byband=True with n_gauss_angles > 1 is not supported (no by-band form with several angles)")
         if self.jacobian and self.byband:
             raise ValueError("ResidentSolver: jacobian=True with byband=True is not supported (no by-band Jacobians)")
+        # optimal_angles: the one LW angle's secant is the k-distribution's optimal-angle fit of the column's total optical depth per
+        # g-point (upstream's compute_optimal_angles / lw_Ds), formed inside the fused solver (lw_solver_noscat_fractions_optimal);
+        # keep_secants: the step also fills self.lw_secants (ngpt, ncol of the step), the secants that solve used
+        self.optimal_angles = bool(optimal_angles)
+        self.keep_secants = bool(keep_secants) and self.optimal_angles
+        if self.optimal_angles:
+            if self.n_gauss_angles > 1:
+                raise ValueError("ResidentSolver: optimal_angles=True with n_gauss_angles > 1 is not supported (optimal angles are one angle)")
+            if self.byband:
+                raise ValueError("ResidentSolver: optimal_angles=True with byband=True is not supported (no by-band form with optimal angles)")
+            if getattr(kd_lw, "optimal_angle_fit", None) is None:
+                raise ValueError("ResidentSolver: optimal_angles=True needs a LW k-distribution with optimal_angle_fit")
         # Column sorting. The windowed gas optics stages ONE box of LUT nodes per 256 neighbouring cells; columns
         # that differ much in pressure (RFMIP-like sites, --col-spread) do not fit one box and fall back to the gather kernels
         # (+40 % per step at +-35 % pressure spread). Columns are independent, so the step may process them in any order: sorted by
@@ -259,6 +271,8 @@ class ResidentSolver:
             raise ValueError("ResidentSolver(byband=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
         if self.jacobian and not self.lite:
             raise ValueError("ResidentSolver(jacobian=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
+        if self.optimal_angles and not self.lite:
+            raise ValueError("ResidentSolver(optimal_angles=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
         ncol, nlay = atm.ncol + self.npad, atm.nlay              # columns of a step (padded)
         ng_l, ng_s = kd_lw.ngpt, kd_sw.ngpt
         e = be.empty
@@ -316,6 +330,8 @@ class ResidentSolver:
         # secants and the band -> g-point expansion of emissivity / albedos: buffers allocated once, the launches themselves are
         # part of every step (rte_lw / rte_sw of the reference run them per solve: src_cuda/Rte_lw.cu:70-110, Rte_sw.cu:57-100)
         self.secants = e((self.n_gauss_angles, ng_l, ncol))
+        self.optimal_fit = be.optimal_fit_abi(kd_lw) if self.optimal_angles else None
+        self.lw_secants = e((ng_l, ncol)) if self.keep_secants else None
         self.sfc_emis_gpt = e((ng_l, ncol)); self.alb_dir = e((ng_s, ncol)); self.alb_dif = e((ng_s, ncol))
         self.events = None
         self.col_dry2 = None
@@ -496,9 +512,14 @@ class ResidentSolver:
                     be.compute_planck_source(kd, it, atm.t_lay, atm.t_lev, atm.t_sfc, _sfc_lay(atm), out=srcs)
                 mark("lw_planck", True)
                 mark("lw_solver")
-                be._c("lw_secants_array", ncol, kd.ngpt, self.n_gauss_angles, MAX_GAUSS_PTS, self.gauss_Ds, self.secants)
+                if not self.optimal_angles:         # (the optimal-angle solver forms its secants itself and reads no secants array)
+                    be._c("lw_secants_array", ncol, kd.ngpt, self.n_gauss_angles, MAX_GAUSS_PTS, self.gauss_Ds, self.secants)
                 be._c("expand_and_transpose", ncol, kd.nbnd, kd.band_lims_gpt, atm.emis_sfc, self.sfc_emis_gpt)
-                if self.byband:
+                if self.optimal_angles:
+                    be.lw_solver_noscat_fractions_optimal(atm.top_at_1, kd, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
+                                                          fit=self.optimal_fit, flux_up=F[0], flux_dn=F[1], flux_up_jac=J,
+                                                          jacobian=self.jacobian, secants_out=self.lw_secants)
+                elif self.byband:
                     be.lw_solver_noscat_fractions_byband(atm.top_at_1, kd, self.secants, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
                                                          out=dict(bnd_flux_up=BL[0], bnd_flux_dn=BL[1], bnd_flux_net=BL[2],
                                                                   flux_up=F[0], flux_dn=F[1]))

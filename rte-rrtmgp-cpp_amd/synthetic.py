@@ -70,6 +70,13 @@ class KDist:
     # SW only
     krayl: np.ndarray = None        # (2, ngpt, neta, ntemp)
     solar_source: np.ndarray = None # (ngpt,)
+    # tables beside the kernel-layout ones above, by name (kept apart from them: the goldens' digest of a k-distribution covers the
+    # array fields). "optimal_angle_fit" (LW): (2, nbnd), the file's (fit_coeffs, bnd); secant D = fit[0, b]*exp(-tau_total) + fit[1, b]
+    extras: dict = field(default_factory=dict)
+
+    @property
+    def optimal_angle_fit(self):
+        return self.extras.get("optimal_angle_fit")
 
     def astype(self, dtype):
         """Copy with all floating arrays cast to ``dtype`` (float32 build = RTE_USE_SP)."""
@@ -77,6 +84,8 @@ class KDist:
         for k, v in self.__dict__.items():
             if isinstance(v, np.ndarray) and v.dtype.kind == "f":
                 out[k] = np.ascontiguousarray(v.astype(dtype))
+            elif k == "extras":
+                out[k] = {n: np.ascontiguousarray(a.astype(dtype)) for n, a in v.items()}
             else:
                 out[k] = v
         return KDist(**out)
@@ -199,6 +208,9 @@ def make_kdist(kind="lw", ngpt=256, nbnd=16, seed=1234, ntemp=14, npres=59, neta
         kd.update(nPlanckTemp=nPlanckTemp, totplnk_delta=float((temp_ref[-1]-temp_ref[0])/(nPlanckTemp-1)),
                   totplnk=np.ascontiguousarray(totplnk),
                   planck_frac=np.ascontiguousarray(pf.reshape(ngpt, npres+1, neta, ntemp)))
+        # optimal-angle fit: a generator of its own, so that every other table is drawn exactly as before it existed
+        rng_fit = np.random.default_rng([seed, 20260])
+        kd.update(extras=dict(optimal_angle_fit=np.stack([rng_fit.uniform(-0.3, 0.3, nbnd), rng_fit.uniform(1.5, 1.8, nbnd)])))
     else:
         gi = np.arange(ngpt)[None, :, None, None]
         krayl = (10.0**(-27.0 + 1.5*(gi/ngpt))

@@ -97,6 +97,9 @@ def write_kdist(path, kd):
         dims["temperature_Planck"] = kd.nPlanckTemp
         v["totplnk"] = (kd.totplnk, ["bnd", "temperature_Planck"])
         v["plank_fraction"] = (np.transpose(kd.planck_frac, (3, 1, 2, 0)), ["temperature", "pressure_interp", "mixing_fraction", "gpt"])
+        if kd.optimal_angle_fit is not None:
+            dims["fit_coeffs"] = 2
+            v["optimal_angle_fit"] = (np.asarray(kd.optimal_angle_fit), ["fit_coeffs", "bnd"])
     else:
         v["rayl_lower"] = (np.transpose(kd.krayl[0], (2, 1, 0)), ["temperature", "mixing_fraction", "gpt"])
         v["rayl_upper"] = (np.transpose(kd.krayl[1], (2, 1, 0)), ["temperature", "mixing_fraction", "gpt"])
