@@ -60,11 +60,13 @@ int rrx_stream_destroy(void* stream);
    caller created itself -- call it from the thread that made the solver calls, before destroying the stream). A block larger than
    RRX_WORKSPACE_KEEP bytes (environment, default 32 GiB) is returned at the end of the call that used it. */
 int rrx_release_workspace(void* stream);
-/* perm[i] = min(i, ncol-1), i < ncol + npad: the identity order, padded (see rrx_sort_columns) */
+/* perm[i] = min(i, ncol-1), i < ncol + npad: the identity order, padded (see rrx_sort_columns). ncol <= 0 or npad < 0: non-zero,
+   "empty problem" */
 int rrx_identity_columns(int ncol, int npad, int* perm, void* stream);
 unsigned long long rrx_workspace_bytes(void* stream);
 /* include/Array.h:311-350,579-622 (Array_gpu::subset / subset_kernel): N-D block gather, singleton dimensions are
-   broadcast. sub_dims/strides/starts/spread are HOST arrays of length ndim (<= 7); strides in elements, starts 0-based. */
+   broadcast. sub_dims/strides/starts/spread are HOST arrays of length ndim (1..7); strides in elements, starts 0-based; elem_bytes
+   1, 4 or 8 (anything else, like an ndim outside 1..7, returns non-zero). A sub_dims entry of 0: returns 0, writes nothing. */
 int rrx_subset_nd(void* out, const void* in, int elem_bytes, int ndim, const int* sub_dims, const long long* strides,
                   const int* starts, const int* spread, void* stream);
 /* kernel-variant switches used by bench.py A/B runs (0 = default), per calling thread. LW: 0 default, 1 serial kernel (the test
@@ -391,6 +393,9 @@ int rrx_lw_solver_noscat_fractions_optimal##SFX( \
         const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up_loc, F* flux_dn_loc, \
         const F* sfc_src_jac, F* flux_up_jac, F* secants_out, void* stream); \
 /* ---- Optical_props_kernels_cuda : include_kernels_cuda/optical_props_kernels_cuda.h:33-56 ---- */ \
+/* Empty problems, for the entries from here to rrx_fill that say so: an extent of 0 returns 0 and writes nothing (no launch is \
+   made, so no launch error is left behind); a negative extent returns non-zero. The _bybnd increments: the g-points of no band \
+   (outside every [lo, hi], or of a band with hi < lo) are left as they are; ncol, nlay, ngpt or nbnd = 0: returns 0. */ \
 int rrx_increment_1scalar_by_1scalar##SFX(int ncol, int nlay, int ngpt, F* tau_inout, const F* tau_in, void* stream); \
 int rrx_increment_2stream_by_2stream##SFX(int ncol, int nlay, int ngpt, F* tau_inout, F* ssa_inout, F* g_inout, const F* tau_in, const F* ssa_in, const F* g_in, void* stream); \
 int rrx_inc_1scalar_by_1scalar_bybnd##SFX(int ncol, int nlay, int ngpt, F* tau_inout, const F* tau_in, int nbnd, const int* band_lims_gpoint, void* stream); \
@@ -400,24 +405,32 @@ int rrx_delta_scale_2str_k##SFX(int ncol, int nlay, int ngpt, F* tau_inout, F* s
 int rrx_sum_broadband##SFX(int ncol, int nlev, int ngpt, const F* gpt_flux, F* flux, void* stream); \
 int rrx_net_broadband_precalc##SFX(int ncol, int nlev, const F* flux_dn, const F* flux_up, F* flux_net, void* stream); \
 /* host-model coupling (no counterpart in the reference library): layer heating rate [K/s] from the net (down - up) \
-   broadband flux flux_net(ncol,nlay+1) and the level pressures plev(ncol,nlay+1): -(g/cp) * dF_net/dp, either vertical ordering */ \
+   broadband flux flux_net(ncol,nlay+1) and the level pressures plev(ncol,nlay+1): -(g/cp) * dF_net/dp, either vertical ordering. \
+   ncol or nlay = 0: returns 0, writes nothing. */ \
 int rrx_heating_rate##SFX(int ncol, int nlay, F g_over_cp, const F* flux_net, const F* plev, F* heating_rate, void* stream); \
 /* by-band: Fortran semantics (src_kernels/mo_fluxes_byband_kernels.F90:22-71; the CUDA text is buggy): \
-   band_lims is (2,nbnd), 1-based inclusive, gpt_flux is the SPECTRAL (ncol,nlev,ngpt) array */ \
+   band_lims is (2,nbnd), 1-based inclusive, gpt_flux is the SPECTRAL (ncol,nlev,ngpt) array. The g-points of a band are added in \
+   order, starting from the band's first g-point. A band with hi < lo is empty: exact zeros are written and nothing is read (its lo \
+   may be ngpt+1), in the sum and in the net form alike. ncol, nlev or nbnd = 0: returns 0, writes nothing. */ \
 int rrx_sum_byband##SFX(int ncol, int nlev, int ngpt, int nbnd, const int* band_lims, const F* gpt_flux, F* bnd_flux, void* stream); \
 int rrx_net_byband_full##SFX(int ncol, int nlev, int ngpt, int nbnd, const int* band_lims, const F* gpt_flux_dn, const F* gpt_flux_up, F* bnd_flux_net, void* stream); \
-/* ---- Subset_kernels_cuda : include_kernels_cuda/subset_kernels_cuda.h:33-56 (n = 1..4 arrays at once) ---- */ \
+/* ---- Subset_kernels_cuda : include_kernels_cuda/subset_kernels_cuda.h:33-56 (n = 1..4 arrays at once) ---- \
+   var_full(ncol,nlay,nbnd): columns col_s_in .. col_s_in+ncol_in-1 (1-based) take var_sub(ncol_in,nlay,nbnd), the other columns are \
+   not written. A range outside 1..ncol or narr outside 1..4: non-zero. ncol_in, nlay or nbnd = 0: returns 0, writes nothing. */ \
 int rrx_get_from_subset##SFX(int ncol, int nlay, int nbnd, int ncol_in, int col_s_in, int narr, \
         F* const* var_full, const F* const* var_sub, void* stream); \
 /* ---- small kernels the reference keeps inside its host classes ---- */ \
-/* src_cuda/Gas_optics_rrtmgp.cu:392-422 fill_gases_kernel (one gas per call, igas = 0 copies col_dry) */ \
+/* src_cuda/Gas_optics_rrtmgp.cu:392-422 fill_gases_kernel (one gas per call, igas = 0 copies col_dry). ncol or nlay = 0: returns 0, \
+   writes nothing (rrx_fill_gases_all alike). */ \
 int rrx_fill_gases##SFX(int ncol, int nlay, int dim1, int dim2, int ngas, int igas, F* vmr_out, const F* vmr_in, F* col_gas, const F* col_dry, void* stream); \
 /* the same for all gases in one launch: vmr_in = HOST array of ngas device pointers, each (dim1[i], dim2[i]) = (1,1) scalar, \
-   (1,nlay) profile or (ncol,nlay) field; col_gas(ncol,nlay,0:ngas) with slot 0 = col_dry (the per-gas vmr copy is not produced) */ \
+   (1,nlay) profile or (ncol,nlay) field; col_gas(ncol,nlay,0:ngas) with slot 0 = col_dry (the per-gas vmr copy is not produced). \
+   ngas = 0 writes slot 0 only; ngas outside 0..32: non-zero */ \
 int rrx_fill_gases_all##SFX(int ncol, int nlay, int ngas, const F* const* vmr_in, const int* dim1, const int* dim2, F* col_gas, const F* col_dry, void* stream); \
 /* src_cuda/Gas_optics_rrtmgp.cu:806-903 get_col_dry (three kernels fused) */ \
 int rrx_get_col_dry##SFX(int ncol, int nlay, const F* vmr_h2o, const F* plev, F* col_dry, void* stream); \
-/* src_cuda/Rte_lw.cu:37-56, Rte_sw.cu:34-54 expand_and_transpose: (nbnd,ncol) -> (ncol,ngpt) */ \
+/* src_cuda/Rte_lw.cu:37-56, Rte_sw.cu:34-54 expand_and_transpose: (nbnd,ncol) -> (ncol,ngpt); the g-points of no band are not \
+   written. ncol or nbnd = 0: returns 0, writes nothing. */ \
 int rrx_expand_and_transpose##SFX(int ncol, int nbnd, const int* band_lims_gpt, const F* arr_in, F* arr_out, void* stream); \
 /* src_cuda/Gas_optics_rrtmgp.cu spread_col: toa_src(icol,igpt) = solar_source(igpt) */ \
 int rrx_spread_col##SFX(int ncol, int ngpt, F* toa_src, const F* solar_source, void* stream); \
@@ -451,17 +464,24 @@ int rrx_cloud_optics_1scl##SFX(int ncol, int nlay, int nbnd, int nsize_liq, int 
         const F* lut_extice, const F* lut_ssaice, const F* lut_asyice, \
         const F* clwp, const F* ciwp, const F* reliq, const F* deice, F* tau, void* stream); \
 /* include/Array.h:311-350,579-622: column-range gather (subset) of an array whose FIRST dimension is the column: \
-   out(icol, r) = in(col_s-1+icol, r), r < nrest */ \
+   out(icol, r) = in(col_s-1+icol, r), r < nrest. A range outside 1..ncol_full: non-zero, "column range outside the full array". \
+   ncol_sub or nrest = 0 (range inside): returns 0, writes nothing. */ \
 int rrx_subset_cols##SFX(int ncol_full, int nrest, int col_s, int ncol_sub, const F* in, F* out, void* stream); \
-/* same for arrays whose LAST dimension is the column, e.g. emis_sfc(nbnd,ncol) */ \
-int rrx_subset_lastdim##SFX(int n1, int col_s, int ncol_sub, const F* in, F* out, void* stream); \
+/* same for arrays in(n1, ncol_full) whose LAST dimension is the column, e.g. emis_sfc(nbnd,ncol): out(b, icol) = in(b, col_s-1+icol); \
+   the same range check against ncol_full, the same empty rule (n1 or ncol_sub = 0) */ \
+int rrx_subset_lastdim##SFX(int n1, int ncol_full, int col_s, int ncol_sub, const F* in, F* out, void* stream); \
+/* arr[0 .. n) = value; n = 0: returns 0, writes nothing */ \
 int rrx_fill##SFX(unsigned long long n, F value, F* arr, void* stream); \
 /* ---- column ordering of the product chain (csrc/rrx_columns.hip; no counterpart in the reference library): columns are independent, so \
    a solve may process them in any order. perm (ncol + npad ints on the device) is a gather index: rrx_sort_columns = ascending order of \
    key(ncol) (the surface pressure: neighbouring columns then share LUT boxes in the windowed gas optics), its last npad entries repeat \
    the last column (padding to a multiple of 16 columns); rrx_column_spread sets flag = 1 where a run of `block` consecutive columns \
    spans more than threshold x its mean. gather: out(i, r) = in(perm[i], r), i < nout, column FIRST (fastest) dimension; gather_lastdim: \
-   out(b, i) = in(b, perm[i]) for (n1, ncol) arrays; scatter: out(perm[i], r) = in(i, r), i < n (arrays of ncol_src / ncol_dst columns). */ \
+   out(b, i) = in(b, perm[i]) for (n1, ncol) arrays; scatter: out(perm[i], r) = in(i, r), i < n (arrays of ncol_src / ncol_dst columns). \
+   The sort is stable (equal keys keep their order); key is not modified. rrx_column_spread looks at FULL runs only (a trailing run \
+   of fewer than `block` columns is ignored, so ncol < block gives 0), takes the mean in the key's precision, and rewrites flag on \
+   every call (0 or 1). Empty problems: rrx_sort_columns and rrx_column_spread return non-zero ("empty problem") for ncol <= 0, \
+   npad < 0 or block <= 0; the gathers and the scatter return 0 and write nothing for nout, n, nrest or n1 = 0. */ \
 int rrx_sort_columns##SFX(int ncol, const F* key, int npad, int* perm, void* stream); \
 int rrx_column_spread##SFX(int ncol, const F* key, int block, F threshold, int* flag, void* stream); \
 int rrx_gather_cols##SFX(int nout, unsigned long long nrest, const int* perm, int ncol_in, const F* in, F* out, void* stream); \

@@ -7,6 +7,7 @@
 #include <mutex>
 #include <vector>
 #include <cstdlib>
+#include <initializer_list>
 #include "rrx_common.h"
 #include "rrx_hip.h"
 
@@ -97,6 +98,14 @@ namespace
 using namespace rrx;
 
 inline int grid1d(const size_t n) { return int(std::min<size_t>((n + 255)/256, 256*16)); }
+// Element count of an entry's problem from its extents: a negative extent throws; 0 is an empty problem, for which the element-wise
+// and data-movement entries of this file return 0 without a launch (an empty grid is a launch error).
+inline size_t extent(const std::initializer_list<long long> dims)
+{
+    size_t n = 1;
+    for (const long long d : dims) { if (d < 0) throw std::runtime_error("negative extent"); n *= size_t(d); }
+    return n;
+}
 #define RRX_GRID_STRIDE(i, n) for (size_t i = size_t(blockIdx.x)*blockDim.x + threadIdx.x; i < (n); i += size_t(gridDim.x)*blockDim.x)
 
 // heating rate of a layer from the net (down - up) broadband flux at its two levels: dT/dt = -(g/cp) d(F_dn - F_up)/dp [K/s]
@@ -210,6 +219,11 @@ __global__ void byband_kernel(const size_t nlc, const int* __restrict__ band_lim
 {
     const int ibnd = blockIdx.y;
     const int g0 = band_lims[2*ibnd]-1, g1 = band_lims[2*ibnd+1]-1;
+    if (g1 < g0)            // an empty band (hi < lo) is exact zeros and reads nothing: its lo may lie one past the last g-point
+    {
+        RRX_GRID_STRIDE(i, nlc) out[i + size_t(ibnd)*nlc] = F(0.);
+        return;
+    }
     RRX_GRID_STRIDE(i, nlc)
     {
         F s = NET ? a[i + size_t(g0)*nlc] - b[i + size_t(g0)*nlc] : a[i + size_t(g0)*nlc];
@@ -595,13 +609,17 @@ int rrx_subset_nd(void* out, const void* in, int elem_bytes, int ndim, const int
 {
     RRX_TRY
     if (ndim < 1 || ndim > 7) throw std::runtime_error("ndim must be 1..7");
+    if (elem_bytes != 1 && elem_bytes != 4 && elem_bytes != 8) throw std::runtime_error("element size must be 1, 4 or 8 bytes");
     SubsetND sd; sd.ndim = ndim; size_t n = 1;
-    for (int d=0; d<ndim; ++d) { sd.sub_dims[d] = sub_dims[d]; sd.strides[d] = strides[d]; sd.starts[d] = starts[d]; sd.spread[d] = spread[d]; n *= sub_dims[d]; }
+    for (int d=0; d<ndim; ++d)
+    {
+        if (sub_dims[d] < 0) throw std::runtime_error("negative extent");
+        sd.sub_dims[d] = sub_dims[d]; sd.strides[d] = strides[d]; sd.starts[d] = starts[d]; sd.spread[d] = spread[d]; n *= size_t(sub_dims[d]);
+    }
     if (n == 0) return 0;
     if (elem_bytes == 8) subset_nd_kernel<double><<<grid1d(n), 256, 0, ST>>>(sd, n, static_cast<const double*>(in), static_cast<double*>(out));
     else if (elem_bytes == 4) subset_nd_kernel<int><<<grid1d(n), 256, 0, ST>>>(sd, n, static_cast<const int*>(in), static_cast<int*>(out));
-    else if (elem_bytes == 1) subset_nd_kernel<signed char><<<grid1d(n), 256, 0, ST>>>(sd, n, static_cast<const signed char*>(in), static_cast<signed char*>(out));
-    else throw std::runtime_error("element size must be 1, 4 or 8 bytes");
+    else subset_nd_kernel<signed char><<<grid1d(n), 256, 0, ST>>>(sd, n, static_cast<const signed char*>(in), static_cast<signed char*>(out));
     RRX_CATCH("rrx_subset_nd")
 }
 
@@ -613,10 +631,10 @@ int rrx_increment_2stream_by_2stream##SFX(int ncol, int nlay, int ngpt, F* tau_i
 { RRX_TRY const size_t n = size_t(ncol)*nlay*ngpt; \
   inc_2str_kernel<F><<<grid1d(n), 256, 0, ST>>>(n, rrx::Lim<F>::tiny()*F(3.), tau_inout, ssa_inout, g_inout, tau_in, ssa_in, g_in); RRX_CATCH("rrx_increment_2stream_by_2stream") } \
 int rrx_inc_1scalar_by_1scalar_bybnd##SFX(int ncol, int nlay, int ngpt, F* tau_inout, const F* tau_in, int nbnd, const int* band_lims_gpoint, void* stream) \
-{ RRX_TRY const size_t ncl = size_t(ncol)*nlay; \
+{ RRX_TRY const size_t ncl = extent({ncol, nlay}); if (extent({ngpt, nbnd}) == 0 || ncl == 0) return 0; \
   inc_1scl_bybnd_kernel<F><<<dim3(std::min(grid1d(ncl), 1024), ngpt), 256, 0, ST>>>(ncl, tau_inout, tau_in, nbnd, band_lims_gpoint); RRX_CATCH("rrx_inc_1scalar_by_1scalar_bybnd") } \
 int rrx_inc_2stream_by_2stream_bybnd##SFX(int ncol, int nlay, int ngpt, F* tau_inout, F* ssa_inout, F* g_inout, const F* tau_in, const F* ssa_in, const F* g_in, int nbnd, const int* band_lims_gpoint, void* stream) \
-{ RRX_TRY const size_t ncl = size_t(ncol)*nlay; \
+{ RRX_TRY const size_t ncl = extent({ncol, nlay}); if (extent({ngpt, nbnd}) == 0 || ncl == 0) return 0; \
   inc_2str_bybnd_kernel<F><<<dim3(std::min(grid1d(ncl), 1024), ngpt), 256, 0, ST>>>(ncl, rrx::Lim<F>::tiny()*F(3.), tau_inout, ssa_inout, g_inout, tau_in, ssa_in, g_in, nbnd, band_lims_gpoint); RRX_CATCH("rrx_inc_2stream_by_2stream_bybnd") } \
 int rrx_delta_scale_2str_k##SFX(int ncol, int nlay, int ngpt, F* tau_inout, F* ssa_inout, F* g_inout, void* stream) \
 { RRX_TRY const size_t n = size_t(ncol)*nlay*ngpt; \
@@ -628,30 +646,33 @@ int rrx_net_broadband_precalc##SFX(int ncol, int nlev, const F* flux_dn, const F
 { RRX_TRY const size_t n = size_t(ncol)*nlev; \
   net_kernel<F><<<grid1d(n), 256, 0, ST>>>(n, flux_dn, flux_up, flux_net); RRX_CATCH("rrx_net_broadband_precalc") } \
 int rrx_heating_rate##SFX(int ncol, int nlay, F g_over_cp, const F* flux_net, const F* plev, F* heating_rate, void* stream) \
-{ RRX_TRY const size_t n = size_t(ncol)*nlay; \
+{ RRX_TRY const size_t n = extent({ncol, nlay}); if (n == 0) return 0; \
   heating_rate_kernel<F><<<grid1d(n), 256, 0, ST>>>(n, ncol, g_over_cp, flux_net, plev, heating_rate); RRX_CATCH("rrx_heating_rate") } \
 int rrx_sum_byband##SFX(int ncol, int nlev, int ngpt, int nbnd, const int* band_lims, const F* gpt_flux, F* bnd_flux, void* stream) \
-{ RRX_TRY (void)ngpt; const size_t n = size_t(ncol)*nlev; \
+{ RRX_TRY (void)ngpt; const size_t n = extent({ncol, nlev}); if (n == 0 || extent({nbnd}) == 0) return 0; \
   byband_kernel<F,false><<<dim3(std::min(grid1d(n), 1024), nbnd), 256, 0, ST>>>(n, band_lims, gpt_flux, (const F*)nullptr, bnd_flux); RRX_CATCH("rrx_sum_byband") } \
 int rrx_net_byband_full##SFX(int ncol, int nlev, int ngpt, int nbnd, const int* band_lims, const F* gpt_flux_dn, const F* gpt_flux_up, F* bnd_flux_net, void* stream) \
-{ RRX_TRY (void)ngpt; const size_t n = size_t(ncol)*nlev; \
+{ RRX_TRY (void)ngpt; const size_t n = extent({ncol, nlev}); if (n == 0 || extent({nbnd}) == 0) return 0; \
   byband_kernel<F,true><<<dim3(std::min(grid1d(n), 1024), nbnd), 256, 0, ST>>>(n, band_lims, gpt_flux_dn, gpt_flux_up, bnd_flux_net); RRX_CATCH("rrx_net_byband_full") } \
 int rrx_get_from_subset##SFX(int ncol, int nlay, int nbnd, int ncol_in, int col_s_in, int narr, F* const* var_full, const F* const* var_sub, void* stream) \
 { RRX_TRY if (narr < 1 || narr > 4) throw std::runtime_error("narr must be 1..4"); \
   if (col_s_in < 1 || col_s_in - 1 + ncol_in > ncol) throw std::runtime_error("column range outside the full array"); \
   PtrPack<F> p; for (int a=0; a<narr; ++a) { p.full[a] = var_full[a]; p.sub[a] = var_sub[a]; } \
-  const size_t nrest = size_t(nlay)*nbnd; \
+  const size_t nrest = extent({nlay, nbnd}); if (extent({ncol_in}) == 0 || nrest == 0) return 0; \
   get_from_subset_kernel<F><<<grid1d(size_t(ncol_in)*nrest), 256, 0, ST>>>(ncol, nrest, ncol_in, col_s_in, narr, p); RRX_CATCH("rrx_get_from_subset") } \
 int rrx_fill_gases##SFX(int ncol, int nlay, int dim1, int dim2, int ngas, int igas, F* vmr_out, const F* vmr_in, F* col_gas, const F* col_dry, void* stream) \
-{ RRX_TRY (void)ngas; fill_gases_kernel<F><<<grid1d(size_t(ncol)*nlay), 256, 0, ST>>>(ncol, nlay, dim1, dim2, igas, vmr_out, vmr_in, col_gas, col_dry); RRX_CATCH("rrx_fill_gases") } \
+{ RRX_TRY (void)ngas; if (extent({ncol, nlay}) == 0) return 0; \
+  fill_gases_kernel<F><<<grid1d(size_t(ncol)*nlay), 256, 0, ST>>>(ncol, nlay, dim1, dim2, igas, vmr_out, vmr_in, col_gas, col_dry); RRX_CATCH("rrx_fill_gases") } \
 int rrx_fill_gases_all##SFX(int ncol, int nlay, int ngas, const F* const* vmr_in, const int* dim1, const int* dim2, F* col_gas, const F* col_dry, void* stream) \
 { RRX_TRY if (ngas < 0 || ngas > RRX_MAX_GASES) throw std::runtime_error("more gases than rrx_fill_gases_all takes"); \
+  if (extent({ncol, nlay}) == 0) return 0; \
   GasTable<F> gt; for (int i=0; i<ngas; ++i) { gt.vmr[i] = vmr_in[i]; gt.dim1[i] = dim1[i]; gt.dim2[i] = dim2[i]; } \
   fill_gases_all_kernel<F><<<grid1d(size_t(ncol)*nlay), 256, 0, ST>>>(ncol, nlay, ngas, gt, col_gas, col_dry); RRX_CATCH("rrx_fill_gases_all") } \
 int rrx_get_col_dry##SFX(int ncol, int nlay, const F* vmr_h2o, const F* plev, F* col_dry, void* stream) \
 { RRX_TRY col_dry_kernel<F><<<grid1d(size_t(ncol)*nlay), 256, 0, ST>>>(ncol, nlay, vmr_h2o, plev, col_dry); RRX_CATCH("rrx_get_col_dry") } \
 int rrx_expand_and_transpose##SFX(int ncol, int nbnd, const int* band_lims_gpt, const F* arr_in, F* arr_out, void* stream) \
-{ RRX_TRY expand_and_transpose_kernel<F><<<dim3(std::min(grid1d(ncol), 1024), nbnd), 256, 0, ST>>>(ncol, nbnd, band_lims_gpt, arr_in, arr_out); RRX_CATCH("rrx_expand_and_transpose") } \
+{ RRX_TRY if (extent({ncol, nbnd}) == 0) return 0; \
+  expand_and_transpose_kernel<F><<<dim3(std::min(grid1d(ncol), 1024), nbnd), 256, 0, ST>>>(ncol, nbnd, band_lims_gpt, arr_in, arr_out); RRX_CATCH("rrx_expand_and_transpose") } \
 int rrx_spread_col##SFX(int ncol, int ngpt, F* toa_src, const F* solar_source, void* stream) \
 { RRX_TRY spread_col_kernel<F><<<dim3(std::min(ceil_div(ncol, 256), 64), ngpt), 256, 0, ST>>>(ncol, ngpt, toa_src, solar_source); RRX_CATCH("rrx_spread_col") } \
 int rrx_scaling_to_subset##SFX(int ncol, int ngpt, F* toa_src, const F* tsi_scaling, void* stream) \
@@ -693,13 +714,19 @@ int rrx_cloud_optics_1scl##SFX(int ncol, int nlay, int nbnd, int nsize_liq, int 
       radliq_lwr, (radliq_upr - radliq_lwr)/(nsize_liq - F(1.)), diamice_lwr, (diamice_upr - diamice_lwr)/(nsize_ice - F(1.)), \
       lut_extliq, lut_ssaliq, lut_asyliq, lut_extice, lut_ssaice, lut_asyice, clwp, ciwp, reliq, deice, tau, (F*)nullptr, (F*)nullptr); RRX_CATCH("rrx_cloud_optics_1scl") } \
 int rrx_subset_cols##SFX(int ncol_full, int nrest, int col_s, int ncol_sub, const F* in, F* out, void* stream) \
-{ RRX_TRY if (col_s < 1 || col_s - 1 + ncol_sub > ncol_full) throw std::runtime_error("column range outside the full array"); \
+{ RRX_TRY const size_t n = extent({ncol_sub, nrest}); \
+  if (col_s < 1 || col_s - 1 + ncol_sub > ncol_full) throw std::runtime_error("column range outside the full array"); \
+  if (n == 0) return 0; \
   subset_cols_kernel<F><<<grid1d(size_t(ncol_sub)*nrest), 256, 0, ST>>>(ncol_full, size_t(nrest), col_s, ncol_sub, in, out); RRX_CATCH("rrx_subset_cols") } \
-int rrx_subset_lastdim##SFX(int n1, int col_s, int ncol_sub, const F* in, F* out, void* stream) \
-{ RRX_TRY if (hipMemcpyAsync(out, in + size_t(col_s-1)*n1, size_t(n1)*ncol_sub*sizeof(F), hipMemcpyDeviceToDevice, ST) != hipSuccess) \
+int rrx_subset_lastdim##SFX(int n1, int ncol_full, int col_s, int ncol_sub, const F* in, F* out, void* stream) \
+{ RRX_TRY const size_t n = extent({n1, ncol_sub}); \
+  if (col_s < 1 || col_s - 1 + ncol_sub > ncol_full) throw std::runtime_error("column range outside the full array"); \
+  if (n == 0) return 0; \
+  if (hipMemcpyAsync(out, in + size_t(col_s-1)*n1, n*sizeof(F), hipMemcpyDeviceToDevice, ST) != hipSuccess) \
       throw std::runtime_error("hipMemcpyAsync failed"); RRX_CATCH("rrx_subset_lastdim") } \
 int rrx_fill##SFX(unsigned long long n, F value, F* arr, void* stream) \
-{ RRX_TRY fill_kernel<F><<<grid1d(n), 256, 0, ST>>>(n, value, arr); RRX_CATCH("rrx_fill") }
+{ RRX_TRY if (n == 0) return 0; \
+  fill_kernel<F><<<grid1d(n), 256, 0, ST>>>(n, value, arr); RRX_CATCH("rrx_fill") }
 
 RRX_DEFINE_MISC(double, _f64)
 RRX_DEFINE_MISC(float, _f32)

@@ -501,22 +501,35 @@ class HipKernels:
         self._c("get_col_dry", ncol, nlay, vmr_h2o, plev, out)
         return out
 
+    @staticmethod
+    def _vmr_dims(name, v, nlay, ncol):
+        """(dim1, dim2) of a gas concentration as rrx_fill_gases[_all] take it: a scalar (any tensor of one element) is (1, 1), a profile
+        (nlay,) or (nlay, 1) is (1, nlay), a field (nlay, ncol) is (ncol, nlay); any other shape is refused."""
+        shape = tuple(v.shape)
+        if v.numel() == 1:
+            return 1, 1
+        if shape in ((nlay,), (nlay, 1)):
+            return 1, nlay
+        if shape == (nlay, ncol):
+            return ncol, nlay
+        raise ValueError(f"fill_gases: {name} has shape {shape}; expected a scalar, a profile ({nlay},) or ({nlay}, 1), "
+                         f"or a field ({nlay}, {ncol})")
+
     def fill_gases(self, kd, vmr_by_name, col_dry):
         """col_gas(ncol,nlay,0:ngas): slot 0 = col_dry, slot i = vmr_i * col_dry
-        (/root/reference/src_cuda/Gas_optics_rrtmgp.cu:392-422,1023-1028)."""
+        (/root/reference/src_cuda/Gas_optics_rrtmgp.cu:392-422,1023-1028). A concentration is a scalar, a profile (nlay,) or
+        (nlay, 1) shared by all columns, or a field (nlay, ncol)."""
         nlay, ncol = col_dry.shape
         col_gas = self.empty((kd.ngas+1, nlay, ncol))
         vs = [vmr_by_name[name] for name in kd.gas_names]
+        dims = [self._vmr_dims(name, v, nlay, ncol) for name, v in zip(kd.gas_names, vs)]
         if len(vs) <= 32:                      # one launch for all gases
-            dims = [((v.shape[1], v.shape[0]) if v.dim() == 2 else (1, 1)) for v in vs]
             self._c("fill_gases_all", ncol, nlay, len(vs), (ctypes.c_void_p * len(vs))(*[v.data_ptr() for v in vs]),
                     (ctypes.c_int * len(vs))(*[d[0] for d in dims]), (ctypes.c_int * len(vs))(*[d[1] for d in dims]), col_gas, col_dry)
             return col_gas
         vmr = self.empty((kd.ngas, nlay, ncol))
         self._c("fill_gases", ncol, nlay, ncol, nlay, kd.ngas, 0, vmr, col_dry, col_gas, col_dry)
-        for i, name in enumerate(kd.gas_names, start=1):
-            v = vmr_by_name[name]
-            d2, d1 = (v.shape[0], v.shape[1]) if v.dim() == 2 else (1, 1)
+        for i, (v, (d1, d2)) in enumerate(zip(vs, dims), start=1):
             self._c("fill_gases", ncol, nlay, d1, d2, kd.ngas, i, vmr, v, col_gas, col_dry)
         return col_gas
 

@@ -3,7 +3,8 @@
   * fp32 fused broadband solvers in the one-column-per-lane geometry (odd column counts, with and without g, all tilings);
   * the persistent index tables of the windowed gas optics are validated against the k-distribution's CONTENTS;
   * the workspace of the any-nlay solver forms belongs to its stream and is handed back;
-  * the small kernels that were rewritten (toa source, range sums, gather grid).
+  * the small kernels that were rewritten (toa source, range sums); the gather grid and the other column-ordering and glue
+    kernels are tested directly in tests/test_gpu_support_kernels.py.
 """
 import ctypes
 import numpy as np
