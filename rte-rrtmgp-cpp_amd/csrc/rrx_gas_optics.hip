@@ -18,12 +18,16 @@
 
 namespace
 {
-#ifndef RRX_GW_NT
-#define RRX_GW_NT 1       // the cell arrays are written once and far exceed the caches: non-temporal stores keep them from evicting the LUTs
-#endif
+// Build-time switches of this file: two, both diagnostic builds (HISTORY.md 4.3 and 17, profiles/README.md). Every other choice
+// that used to be a macro is a constant next to the code it shapes.
+//   RRX_GW_ABL     ablation builds (tools/ab_extra.sh, tools/gw_timing.sh)
+//   RRX_GW_TIMING  per-phase clocks of the windowed kernel (tools/gw_timing.sh), below at gas_window_stats
+// Run-time switches that stay: the environment variables RRX_GW_STATS (gas_window_stats) and RRX_GW_GEOM (gas_window_geometry),
+// rrx_set_gas_window, and RRX_GO_SHARE / RRX_GO_WINDOW (rrx_misc.hip: the defaults of Tuning::go_share / go_window).
 #ifndef RRX_GW_ABL
-#define RRX_GW_ABL 0      // ablation builds (tools/ab_extra.sh, tools/gw_timing.sh): 1 = set-up only, 2 = no staging, 3 = no g-point loop, 7 = no stores
+#define RRX_GW_ABL 0      // 1 = set-up only, 2 = no staging, 3 = no g-point loop, 7 = no stores
 #endif
+// The cell arrays are written once and far exceed the caches: non-temporal stores keep them from evicting the LUTs.
 // The same store addressed as uniform 64-bit base + 32-bit unsigned lane offset: the instruction's own scalar-base form, written as
 // such (through C++ the compiler folds base and offset back into a 64-bit address per lane, one v_lshl_add_u64 per store). Counted by
 // the hardware's vmcnt like any store; the compiler does not know of it, which only makes its own waits conservative.
@@ -31,31 +35,19 @@ template<typename F> __device__ __forceinline__ void stream_store_sbase(const ch
 {
     static_assert(sizeof(F) == 4 || sizeof(F) == 8, "dword or dwordx2");
     if (RRX_GW_ABL == 7) { if (v == F(-12345.678)) *reinterpret_cast<F*>(const_cast<char*>(sbase) + voff) = v; return; }
-#if RRX_GW_NT
     if constexpr (sizeof(F) == 4) asm volatile("global_store_dword %0, %1, %2 nt" :: "v"(voff), "v"(v), "s"(sbase) : "memory");
     else asm volatile("global_store_dwordx2 %0, %1, %2 nt" :: "v"(voff), "v"(v), "s"(sbase) : "memory");
-#else
-    if constexpr (sizeof(F) == 4) asm volatile("global_store_dword %0, %1, %2" :: "v"(voff), "v"(v), "s"(sbase) : "memory");
-    else asm volatile("global_store_dwordx2 %0, %1, %2" :: "v"(voff), "v"(v), "s"(sbase) : "memory");
-#endif
 }
 template<typename F> __device__ __forceinline__ void stream_store(F* p, const F v)
 {
     if (RRX_GW_ABL == 7) { if (v == F(-12345.678)) *p = v; return; }
-#if RRX_GW_NT
     __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 
 using namespace rrx;
 
 constexpr int GCH = 16;          // g-points per register chunk
-#ifndef RRX_GATHER_SHARES
-#define RRX_GATHER_SHARES 4
-#endif
-constexpr int GSH = RRX_GATHER_SHARES;   // a handed-back workgroup is redone in this many shares of its g-point chunks (few entries: the launch lasts as long as one share)
+constexpr int GSH = 4;           // a handed-back workgroup is redone in this many shares of its g-point chunks (few entries: the launch lasts as long as one share)
 
 
 // /root/reference/src_kernels_cuda/gas_optics_rrtmgp_kernels.cu:317-395
@@ -146,46 +138,30 @@ struct InterpArgs
 };
 
 // the arithmetic of inc_2stream_by_2stream_bybnd for one g-point of a cell (rrx_misc.hip:inc_2str, same order of operations)
-// (FAST: the two divisions as Newton reciprocals -- the windowed kernel's own rounding, like its single-scattering albedo)
-template<typename F, bool FAST = false>
+template<typename F>
 __device__ __forceinline__ void add_by_band_2str(F& tau1, F& ssa1, F& g1, const F tau2, const F ssa2, const F g2)
 {
     const F eps = Lim<F>::tiny()*F(3.);
     const F tau12 = tau1 + tau2;
     const F tauscat12 = (tau1 * ssa1) + (tau2 * ssa2);
-    if constexpr (FAST)
-    {
-        g1 = ((tau1 * ssa1 * g1) + (tau2 * ssa2 * g2)) * fast_rcp(max(tauscat12, eps));
-        ssa1 = tauscat12 * fast_rcp(max(eps, tau12));
-    }
-    else
-    {
-        g1 = ((tau1 * ssa1 * g1) + (tau2 * ssa2 * g2)) / max(tauscat12, eps);
-        ssa1 = tauscat12 / max(eps, tau12);
-    }
+    g1 = ((tau1 * ssa1 * g1) + (tau2 * ssa2 * g2)) / max(tauscat12, eps);
+    ssa1 = tauscat12 / max(eps, tau12);
     tau1 = tau12;
 }
 
 // The same combination where the first operand is a gas (asymmetry identically zero): the term tau1 ssa1 g1 is an exact zero and is
 // not formed, and the cloud's products tau2 ssa2 and (tau2 ssa2) g2 stand alone -- loop-invariant where a chunk lies in one band.
-// Bit for bit the result of add_by_band_2str(tau1, ssa1, g1 = 0, ...).
-template<typename F, bool FAST = false>
+// The sums are those of add_by_band_2str(tau1, ssa1, g1 = 0, ...); the two divisions are Newton reciprocals -- the windowed kernel's
+// own rounding, like its single-scattering albedo.
+template<typename F>
 __device__ __forceinline__ void add_cloud_to_gas_2str(F& tau1, F& ssa1, F& g1, const F tau2, const F ssa2, const F g2)
 {
     const F eps = Lim<F>::tiny()*F(3.);
     const F cw = tau2 * ssa2, cwg = cw * g2;
     const F tau12 = tau1 + tau2;
     const F tauscat12 = (tau1 * ssa1) + cw;
-    if constexpr (FAST)
-    {
-        g1 = cwg * fast_rcp(max(tauscat12, eps));
-        ssa1 = tauscat12 * fast_rcp(max(eps, tau12));
-    }
-    else
-    {
-        g1 = cwg / max(tauscat12, eps);
-        ssa1 = tauscat12 / max(eps, tau12);
-    }
+    g1 = cwg * fast_rcp(max(tauscat12, eps));
+    ssa1 = tauscat12 * fast_rcp(max(eps, tau12));
     tau1 = tau12;
 }
 
@@ -277,13 +253,6 @@ __device__ inline MinorIndex build_minor_index(
     return mi;
 }
 
-#ifndef RRX_GO_NPRE
-#define RRX_GO_NPRE 1
-#endif
-#ifndef RRX_GO_NPRE32
-#define RRX_GO_NPRE32 1
-#endif
-[[maybe_unused]] constexpr int NPRE_F64 = RRX_GO_NPRE, NPRE_F32 = RRX_GO_NPRE32;   // minor contributors requested in the first batch of a g-point group
 constexpr int SL = 6;        // minor contributors of a chunk held in registers; further ones take a slower loop
 struct Slots { int lo[SL], hi[SL], koff[SL], mf[SL]; };
 
@@ -537,14 +506,8 @@ tau_absorption_kernel(
     //   fp64 SW fused form: 2 g-points, no contributor in the first batch  -> 157 VGPRs, 3 waves per SIMD (5.68 vs 5.80 ms)
     //   fp64 LW forms:      4 g-points + 2 contributors in the first batch -> 2 waves per SIMD          (4.30 vs 4.43 ms)
     //   fp32:               4 g-points + 1 contributor, 3 waves per SIMD
-    // RRX_GO_G / RRX_GO_NPRE / RRX_GO_NPRE32 override all of them for A/B builds.
-#ifdef RRX_GO_G
-    constexpr int G = RRX_GO_G;
-    constexpr int NPRE = (sizeof(F) == 8) ? NPRE_F64 : NPRE_F32;
-#else
     constexpr int G = (sizeof(F) == 8 && MODE == 1) ? 2 : 4;
-    constexpr int NPRE = (sizeof(F) == 8) ? ((MODE == 1) ? 0 : 2) : 1;
-#endif
+    constexpr int NPRE = (sizeof(F) == 8) ? ((MODE == 1) ? 0 : 2) : 1;   // minor contributors requested in the first batch of a g-point group
     [[maybe_unused]] int cb = 0, cb_have = -1;   // CLD: band (0-based) of the g-point being stored; g-points ascend within a pass
     [[maybe_unused]] F c_tau = F(0.), c_ssa = F(0.), c_g = F(0.);
     auto gpoint_group = [&](const int ig0, const int gend, const int c, const int n, const Slots& sl, const F (&sc)[SL])
@@ -902,20 +865,14 @@ struct CellInterp
     }
 };
 
-#ifndef RRX_PLANCK_MINWAVES
-#define RRX_PLANCK_MINWAVES 1
-#endif
-#ifndef RRX_PLANCK_PL
-#define RRX_PLANCK_PL 4
-#endif
-constexpr int PL = RRX_PLANCK_PL; // layers per Planck workgroup (64 columns x PL layers): 4 = three workgroups per CU whose gather and store phases overlap (8: one; measured 4.07 -> 3.90 ms fp64, 3.36 -> 2.53 ms fp32)
+constexpr int PL = 4;             // layers per Planck workgroup (64 columns x PL layers): 4 = three workgroups per CU whose gather and store phases overlap (8: one; measured 4.07 -> 3.90 ms fp64, 3.36 -> 2.53 ms fp32)
 
 // /root/reference/src_kernels_cuda/gas_optics_rrtmgp_kernels.cu:196-314
 // The reference recomputes the Planck fraction of the layer below for every level source (16 LUT gathers per
 // cell). Here a workgroup of 64 columns x 8 layers exchanges the fractions through LDS in chunks of 16 g-points,
 // so only the first layer of each workgroup recomputes its neighbour (9 gathers per cell on average).
 template<typename F, bool DIRECT = false>
-__global__ void __launch_bounds__(64*PL, RRX_PLANCK_MINWAVES)
+__global__ void __launch_bounds__(64*PL, 1)
 planck_source_kernel(
         const int ncol, const int nlay, const int ngpt, const int neta, const int npres, const int ntemp, const int nPlanckTemp,
         const F* __restrict__ tlay, const F* __restrict__ tlev, const F* __restrict__ tsfc, const int sfc_lay,
@@ -1303,23 +1260,6 @@ planck_fraction_kernel(
 // its id to a todo list and leaves; the gather kernel is launched behind on exactly those workgroups.
 // PF: the Planck fractions ride along (planck_frac has kmajor's layout: same box, same corner weights) together with the band
 // Planck functions and the surface terms -- the whole "Planck-lite" output of planck_fraction_kernel.
-#ifndef RRX_GW_PAIR
-#define RRX_GW_PAIR 1     // 1: g-points of a chunk go in pairs where the chunk allows it. Round 2: SW stage 3.81 -> 3.69 ms alone, but its
-                          // registers collided with the batched register staging (3.81 -> 3.37 ms), so it was off. Round 3: with the boxes
-                          // staged by LDS-DMA the registers are free: SW stage 2.50 -> 2.40 ms (same box), on.
-#endif
-#ifndef RRX_GW_LDSDMA
-#define RRX_GW_LDSDMA 1   // boxes staged by LDS-DMA (global_load_lds_dwordx4) instead of through registers
-#endif
-#ifndef RRX_GW_FAST_BYBAND
-#define RRX_GW_FAST_BYBAND 1  // all-sky SW form: the two divisions of the by-band combination as Newton reciprocals
-#endif
-#ifndef RRX_GW_BANDCHUNKS
-#define RRX_GW_BANDCHUNKS 1   // chunks end where the flavor or the contributor set changes (0: every 16 g-points, the cut of rounds 1-3; A/B runs)
-#endif
-#ifndef RRX_GW_SPARSE
-#define RRX_GW_SPARSE 1   // only the nodes the workgroup's cells reach are staged (their extent in pressure, eta and temperature), through registers
-#endif
 constexpr int NPW = 4, NEW = 4, NTW = 3;
 constexpr int WBOX = NPW*NEW*NTW;            // pair-nodes per g-point: kmajor, planck_frac
 constexpr int MBOX = NEW*NTW;                // pair-nodes per g-point: one minor contributor, Rayleigh
@@ -1330,9 +1270,7 @@ constexpr int NXW = 12;                      // ... and how many a chunk may hav
 // chip once (three resident per CU), else 2 or 4
 inline int gas_window_parts(const int nblk, const int nchunk)
 {
-    static const int forced = std::getenv("RRX_GW_PARTS") ? std::atoi(std::getenv("RRX_GW_PARTS")) : 0;      // (A/B runs)
-    if (forced > 0) return std::min(forced, nchunk);
-    // (round 4, RRX_GW_PARTS sweep at 2 048 and 4 096 columns: a split pays only while the workgroups do not fill the 768 resident
+    // (round 4, a sweep of the part count at 2 048 and 4 096 columns: a split pays only while the workgroups do not fill the 768 resident
     //  places once -- every part repeats the set-up of its workgroup, a tenth of its life; 1 120 workgroups: 0.43 ms in one part or two)
     int nz = 1;
     while (nblk*nz < 768 && nz < 4 && 2*nz <= nchunk) nz *= 2;
@@ -1342,7 +1280,8 @@ inline int gas_window_parts(const int nblk, const int nchunk)
 // Workgroup shape of the windowed kernel: 256 cells that share LUT boxes. 64 columns x 4 layers (geom 0) put a regime change or a
 // jump of the binary-species parameter BETWEEN the layers of one workgroup (at C4: 512 of 8 960 workgroups handed back, 0.8 ms of
 // gather kernels per step); 256 columns x 1 layer (geom 1) have no vertical neighbours to disagree with and at C4 every workgroup
-// fits its boxes. The wide shape is taken when the columns fill it; RRX_GW_GEOM=0/1 overrides (A/B runs).
+// fits its boxes. The wide shape is taken when the columns fill it; the environment variable RRX_GW_GEOM=0/1 overrides (it stays:
+// tests/test_gpu_round4.py runs both shapes through it, INTEGRATION.md documents it).
 inline int gas_window_geometry(const int ncol)
 {
     if (const char* e = std::getenv("RRX_GW_GEOM")) return std::atoi(e) ? 1 : 0;
@@ -1352,8 +1291,9 @@ inline int gas_window_geometry(const int ncol)
 inline dim3 gather_grid(const int entries_)
 {
     const int entries = entries_*GSH;
-    static const int cap = std::getenv("RRX_GATHER_GRID") ? std::max(1, std::atoi(std::getenv("RRX_GATHER_GRID"))) : 512;   // (A/B runs; 512 = the two workgroups per CU the kernels fit: the entries are taken from a counter anyway, and the usual launch -- nothing handed back -- costs 3 instead of 13 us)
-    return dim3(std::min(entries, cap));
+    // (512 = the two workgroups per CU the kernels fit: the entries are taken from a counter anyway, and the usual launch -- nothing
+    //  handed back -- costs 3 instead of 13 us)
+    return dim3(std::min(entries, 512));
 }
 inline dim3 gas_window_grid(const int geom, const int ncol, const int nlay)
 {
@@ -1362,9 +1302,9 @@ inline dim3 gas_window_grid(const int geom, const int ncol, const int nlay)
 
 // RRX_GW_STATS=1 (read at every launch, so a host program can switch it on for one solve): after a windowed launch, wait for it,
 // print how many workgroups were handed back to the gather kernel and why, and add them to the calling thread's totals
-// (rrx_gas_window_stats). Diagnostic only: it synchronises the stream.
+// (rrx_gas_window_stats). Diagnostic only: it synchronises the stream. It stays: bench.py and four tests read it.
 #ifndef RRX_GW_TIMING
-#define RRX_GW_TIMING 0   // diagnostic build (tools/gw_timing.sh): wavefront 0 of every workgroup adds the clocks it spends per phase to g_gw_clk, printed with RRX_GW_STATS
+#define RRX_GW_TIMING 0   // diagnostic build that stays (tools/gw_timing.sh): wavefront 0 of every workgroup adds the clocks it spends per phase to g_gw_clk, printed with RRX_GW_STATS
 #endif
 #if RRX_GW_TIMING
 __device__ unsigned long long g_gw_clk[8];
@@ -1553,7 +1493,7 @@ gas_window_tables_kernel(
             while (m != 0ull) { const int b = __ffsll((long long)m) - 1; m &= m - 1ull; emit_until(64*w + b); }
         }
         emit_until(ngpt);
-        if (!fits || !RRX_GW_BANDCHUNKS)                     // (more runs than the bound allows for: the plain 16-g-point cut; what does not
+        if (!fits)                                           // (more runs than the bound allows for: the plain 16-g-point cut; what does not
         {                                                    //  fit the staged form there is handed back, as in rounds 1-3)
             n = (ngpt + GCH - 1) / GCH;
             for (int c=0; c<n; ++c) cinfo[2 + c] = c*GCH;
@@ -1609,15 +1549,6 @@ gas_window_tables_kernel(
     }
 
     __syncthreads();
-#ifdef RRX_GW_DEBUG_TABLES
-    if (tid == 0)
-    {
-        printf("tables: ngpt %d ncmax %d chunks %d regular %d\n", ngpt, ncmax, cinfo[0], cinfo[1]);
-        for (int c=0; c<nchunk; ++c)
-            printf("  chunk %d [%d,%d) lower: n %d usable %d fl %d | upper: n %d usable %d fl %d\n", c, cinfo[2+c], cinfo[3+c],
-                   lists[c*LIT], cuni[c], gflav[cinfo[2+c]], lists[(ncmax + c)*LIT], cuni[ncmax + c], gflav[ngpt + cinfo[2+c]]);
-    }
-#endif
     for (int w = tid; w < ntab; w += 256) tbl[w] = lds_int[w];
     for (int w = tid; w < GasWindowTables::GX*ngpt; w += 256) tbl[T.off_gx() + w] = gx_of(w / GasWindowTables::GX, w % GasWindowTables::GX);
     if (tid < 2)                                            // unusable chunks ahead of chunk c, per regime
@@ -1710,11 +1641,9 @@ size_t gas_window_lds_bytes(const int ngpt, const int nmax, const int ncmax, con
     return ((ints*sizeof(int) + 15) & ~size_t(15)) + pairs*2*sizeof(F);
 }
 
-#ifndef RRX_GW_MINW
-#define RRX_GW_MINW 3
-#endif
+constexpr int GW_MINW = 3;       // workgroups per CU the windowed kernel is compiled for: three waves per SIMD
 template<typename F, int MODE, bool PF, bool CLD = false>
-__global__ void __launch_bounds__(256, RRX_GW_MINW)
+__global__ void __launch_bounds__(256, GW_MINW)
 gas_window_kernel(
         const int ncol, const int nlay, const int ngpt, const int neta, const int npres, const int ntemp,
         const int nminorlower, const int nminorupper, const int idx_h2o,
@@ -1899,7 +1828,6 @@ gas_window_kernel(
     #pragma unroll
     for (int i=0; i<8; ++i) fm[i] = F(0.);
     cm[0] = cm[1] = F(0.); fn[0] = fn[1] = fn[2] = fn[3] = F(0.);
-    const F* kmin = itr == 0 ? kminor_lower : kminor_upper;
     int red_slot = 6;                                                  // alternating pairs of reduction slots: 6/7, 8/9
 
     if (RRX_GW_ABL == 1) return;
@@ -1997,19 +1925,17 @@ gas_window_kernel(
         // ---- stage the boxes: pairs (T, T+1) are adjacent words of the tables (temperature is their fastest dimension)
         if (RRX_GW_ABL != 2)
         {
-            // The loads of a box are issued together, before its LDS writes: one memory round trip per phase (major [+ Planck
-            // fractions]; Rayleigh + contributors 0-2; contributors 3-5 where there are any) instead of one per loop iteration
-            // and box. The loops have at most GCH*WBOX/256 = 3 and 1 iterations: unrolled, the pairs held in registers.
+            // The loads of a box are issued together: one memory round trip per phase (major [+ Planck fractions]; Rayleigh +
+            // contributors 0-2; contributors 3-5 where there are any) instead of one per loop iteration and box.
             static_assert((GCH*WBOX) % 256 == 0 && GCH*MBOX <= 256 && NCW == 6, "staging phases are written for these box sizes");
             constexpr int KMAJ = GCH*WBOX/256;
-            const int nmaj = ng*WBOX, nmin = ng*MBOX;
-            // (the DMA moves 16 B per lane: fp64 pairs; the fp32 build keeps the register path)
-            constexpr bool DMA = RRX_GW_LDSDMA && sizeof(F) == 8;
-            // (the fp64 forms without fractions keep the DMA: with the staging registers they spill, and a spill reload at the top of a
-            //  chunk waits behind every store in flight)
-            if constexpr (!DMA || PF) chunk_scalings();             // (register-staged forms: their loads go out ahead of the staging loads)
-            if constexpr (RRX_GW_SPARSE && (PF || !DMA))
+            // Two ways of staging. The fp64 forms without fractions stage by LDS-DMA: it moves 16 B per lane (fp64 pairs), and with
+            // staging registers these forms spill -- a spill reload at the top of a chunk waits behind every store in flight. fp32 and
+            // every fractions form stage through registers, only the nodes in reach.
+            constexpr bool DMA = sizeof(F) == 8 && !PF;
+            if constexpr (!DMA)
             {
+                chunk_scalings();                                   // (their loads go out ahead of the staging loads)
                 // Sparse staging (round 3): a full box is 4 pressure x 4 eta nodes x 3 temperature pairs per g-point, what the cells of
                 // a workgroup reach is usually 2 x 2 x 1 (one layer of neighbouring columns). Every 16-byte pair pulls its 128-byte line
                 // through the L1, so staging the full boxes moved ~100 KB per chunk and workgroup (phase clocks: ~3 000 clocks per chunk,
@@ -2068,7 +1994,7 @@ gas_window_kernel(
                 RRX_GW_T(2)
                 RRX_GW_T(3)
             }
-            else if constexpr (DMA)
+            else
             {
             // LDS-DMA staging (round 3): every pair-node goes from the table straight into its LDS slot (`global_load_lds_dwordx4`:
             // per-lane source address, destination = a wave-uniform base + 16 B x lane -- the boxes are laid out linearly in the
@@ -2083,7 +2009,6 @@ gas_window_kernel(
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                                  (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
             };
-            (void)nmaj; (void)nmin; (void)KMAJ;
             #pragma unroll
             for (int k=0; k<KMAJ; ++k)
             {
@@ -2114,73 +2039,6 @@ gas_window_kernel(
             RRX_GW_T(2)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // the DMA writes have landed in LDS (the barrier below publishes them)
             RRX_GW_T(3)
-            }
-            else
-            {
-            auto stage_major = [&](const F* __restrict__ table, Vec2* __restrict__ W)
-            {
-                Vec2 v[KMAJ];
-                #pragma unroll
-                for (int k=0; k<KMAJ; ++k)
-                {
-                    const int q = tid + 256*k;
-                    if (q < nmaj)
-                    {
-                        const int gi = q / WBOX, r = q % WBOX;
-                        const int p = r / (NEW*NTW), e = (r / NTW) % NEW, t = r % NTW;
-                        const int it_ = min(jt_lo - 1 + t, ntemp-2), ie = min(max(je_lo - 1 + e, 0), neta-1), ip = min(max(jp_lo - 1 + p, 0), npres);
-                        v[k] = *reinterpret_cast<const Vec2u*>(table + size_t(c0 + gi)*s_gpt + size_t(it_) + size_t(ie)*ntemp + size_t(ip)*tn);
-                    }
-                }
-                #pragma unroll
-                for (int k=0; k<KMAJ; ++k)
-                {
-                    const int q = tid + 256*k;
-                    if (q < nmaj) W[q] = v[k];                                                  // gi*WBOX + r == q
-                }
-            };
-            if constexpr (!PF) stage_major(kmajor, Wmaj);
-            else
-            {
-                // (the fractions form runs at the register limit of three waves per SIMD -- batching its two major-type boxes
-                //  costs 84 B of scratch per lane and time -- so they keep the rolled loop, one pair of loads in flight per iteration)
-                for (int q = tid; q < nmaj; q += 256)
-                {
-                    const int gi = q / WBOX, r = q % WBOX;
-                    const int p = r / (NEW*NTW), e = (r / NTW) % NEW, t = r % NTW;
-                    const int it_ = min(jt_lo - 1 + t, ntemp-2), ie = min(max(je_lo - 1 + e, 0), neta-1), ip = min(max(jp_lo - 1 + p, 0), npres);
-                    const size_t off = size_t(c0 + gi)*s_gpt + size_t(it_) + size_t(ie)*ntemp + size_t(ip)*tn;
-                    Wmaj[q] = *reinterpret_cast<const Vec2u*>(kmajor + off);
-                    Wpf[q] = *reinterpret_cast<const Vec2u*>(pa.pfracin + off);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            const int gi_m = tid / MBOX, r_m = tid % MBOX;                  // this thread's node of a minor / Rayleigh box
-            const int it_m = min(jt_lo - 1 + r_m % NTW, ntemp-2), ie_m = min(max(je_lo - 1 + r_m / NTW, 0), neta-1);
-            auto minor_node = [&](const int i) -> Vec2
-            {
-                const Int8 m = item_rec(i);
-                const int kg = min(max(c0 + gi_m, m.s0), m.s1-1);               // clamped: always a valid table row
-                return *reinterpret_cast<const Vec2u*>(kmin + size_t(kg + m.s2)*tn + it_m + ie_m*ntemp);
-            };
-            if (tid < nmin)
-            {
-                Vec2 v[3]; [[maybe_unused]] Vec2 vray;
-                if constexpr (MODE == 1)
-                    vray = *reinterpret_cast<const Vec2u*>(krayl + size_t(itr)*tn*ngpt + size_t(c0 + gi_m)*tn + it_m + ie_m*ntemp);
-                #pragma unroll
-                for (int i=0; i<3; ++i) if (i < n) v[i] = minor_node(i);
-                if constexpr (MODE == 1) Wray[tid] = vray;                                       // gi*MBOX + r == tid
-                #pragma unroll
-                for (int i=0; i<3; ++i) if (i < n) Wmin[(i*GCH + gi_m)*MBOX + r_m] = v[i];
-                if (n > 3)
-                {
-                    #pragma unroll
-                    for (int i=3; i<NCW; ++i) if (i < n) v[i-3] = minor_node(i);
-                    #pragma unroll
-                    for (int i=3; i<NCW; ++i) if (i < n) Wmin[(i*GCH + gi_m)*MBOX + r_m] = v[i-3];
-                }
-            }
             }
         }
         if (RRX_GW_ABL == 2) chunk_scalings();
@@ -2228,7 +2086,7 @@ gas_window_kernel(
         // ---- the chunk's g-points, one per iteration (measured alternatives, all slower on MI355X: batches of 2-8 g-points
         // with their LDS reads issued together -- the registers cost the third wave per SIMD --, contributor reads preloaded
         // next to the major term's, per-contributor sweeps over the chunk, straight-line specialisations per contributor count)
-        // One g-point: the reference's expression order. `U` g-points at once (RRX_GW_PAIR): the same expressions per g-point,
+        // One g-point: the reference's expression order. `U` g-points at once (PAIR, below): the same expressions per g-point,
         // written side by side so that the LDS reads of both go out together and the two dependent fp64 chains interleave
         // (a single chain leaves the SIMD idle for most of each LDS round trip with three waves to cover it). The paired form
         // is taken when every contributor of the chunk spans the whole chunk (the rule: intervals are band-aligned), so it
@@ -2357,7 +2215,7 @@ gas_window_kernel(
                     if constexpr (CLD)
                     {
                         F gg = F(0.);
-                        add_cloud_to_gas_2str<F, RRX_GW_FAST_BYBAND != 0>(tt, ww, gg, c_tau, c_ssa, c_g);
+                        add_cloud_to_gas_2str(tt, ww, gg, c_tau, c_ssa, c_g);
                         if (ACT || active) { slab_put(sb_tau, u, tt); slab_put(sb_ssa, u, ww); slab_put(sb_g, u, gg); }
                     }
                     else if (ACT || active)
@@ -2402,28 +2260,19 @@ gas_window_kernel(
         bool chunk_full = true;
         #pragma unroll
         for (int i=0; i<NCW; ++i) if (i < n && !(slo[i] <= c0 && shi[i] >= gend)) chunk_full = false;
-#ifndef RRX_GW_COUNTED
-#define RRX_GW_COUNTED 1
-#endif
-#ifndef RRX_GW_PAIR32_SW
-#define RRX_GW_PAIR32_SW 0
-#endif
-#ifndef RRX_GW_PAIR32
-#define RRX_GW_PAIR32 1    // fp32 pairs the g-points of the fractions form only (LW stage 1.78 -> 1.69 ms at C4; SW 1.38 -> 1.49 paired)
-#endif
-#ifndef RRX_GW_PAIR_PF
-#define RRX_GW_PAIR_PF 1
-#endif
-#ifndef RRX_GW_NOPAIR_CLD
-#define RRX_GW_NOPAIR_CLD 1
-#endif
-        // (the fractions form and the all-sky SW form have no registers to spare in fp64: paired they spill, and a spill reload waits
-        //  behind every store in flight)
-        // (fp32: unpaired was faster in every form while the loop still carried its range tests -- LW stage 2.05 -> 1.87 ms, SW 1.56 -> 1.50 ms
-        //  at C4; with the bit masks the fractions form gains from pairs, RRX_GW_PAIR32 above, the SW forms still do not)
-        // (fractions form, fp64: paired it spills 72 B per lane and is still 3 % faster now that nothing in its loop waits on `vmcnt` --
-        //  2.76 -> 2.68 ms, two boxes; before the band look-up left the loop it was 3 % slower. Not in the all-sky form.)
-        constexpr int PAIR = (RRX_GW_PAIR && (sizeof(F) == 8 || (RRX_GW_PAIR32 && (PF || RRX_GW_PAIR32_SW))) && ((RRX_GW_PAIR_PF && !CLD) || !PF) && !(RRX_GW_NOPAIR_CLD && CLD && MODE == 1)) ? 2 : 1;
+        // Which forms take their g-points in pairs (the same expressions side by side, see above):
+        //   fp64 and the fp32 fractions form, except the two all-sky forms that have no registers to spare -- fractions and SW.
+        // What was measured (C4, stage times):
+        // * fp64, pairs against single g-points: SW stage 3.81 -> 3.69 ms alone in round 2, but the registers collided with the batched
+        //   register staging of that round; with the boxes staged by LDS-DMA they are free: 2.50 -> 2.40 ms (same box), pairs on.
+        // * the fractions form and the all-sky SW form have no registers to spare in fp64: paired they spill, and a spill reload waits
+        //   behind every store in flight.
+        // * fractions form, fp64, cloudless: paired it spills 72 B per lane and is still 3 % faster now that nothing in its loop waits on
+        //   `vmcnt` -- 2.76 -> 2.68 ms, two boxes; before the band look-up left the loop it was 3 % slower. Not in the all-sky form.
+        // * fp32: unpaired was faster in every form while the loop still carried its range tests -- LW stage 2.05 -> 1.87 ms, SW 1.56 ->
+        //   1.50 ms; with the bit masks the fractions form gains from pairs (LW stage 1.78 -> 1.69 ms), the SW forms still do not
+        //   (1.38 -> 1.49 ms paired), and the plain LW form stays with them.
+        constexpr int PAIR = ((sizeof(F) == 8 || PF) && !(CLD && PF) && !(CLD && MODE == 1)) ? 2 : 1;
         auto gloop = [&](auto SAME_, auto FAST_)
         {
             int gi = 0;
@@ -2437,7 +2286,7 @@ gas_window_kernel(
         if (RRX_GW_ABL != 3)
         {
             using T_ = std::true_type; using F_ = std::false_type;
-            bool fast = RRX_GW_COUNTED && wave_all_active && chunk_full;
+            bool fast = wave_all_active && chunk_full;
             if constexpr (CLD) fast = fast && cld_one_band;
             if constexpr (PF) fast = fast && one_band;
             if (fast)
@@ -2528,8 +2377,6 @@ __global__ void reorder12x21_kernel(const int ni, const int nj, const F* __restr
     }
 }
 
-// shared-cell path of the gather kernels (RRX_GO_SHARE=0 turns it off for A/B runs)
-
 inline int grid1d(const size_t n) { return int(std::min<size_t>((n + 255)/256, 256*8)); }
 
 template<typename F> size_t planck_lds_bytes(const int ngpt)
@@ -2537,192 +2384,191 @@ template<typename F> size_t planck_lds_bytes(const int ngpt)
     return size_t(GCH)*(PL+1)*64*sizeof(F) + size_t((2*ngpt + 3) & ~3)*sizeof(int) + size_t(PL)*2*4*GCH*2*sizeof(F);
 }
 
-// LW gas optics + Planck-lite in one pass: windowed kernel with the Planck fractions riding along; the workgroups it hands
-// back are finished by the gather kernel (tau) and planck_fraction_kernel (fractions, band Planck functions, surface terms)
+// ---- host side. The bundles below never reach a kernel: the kernels keep their flat parameter lists (the kernarg layout is part of
+// their instruction streams), and the two launch helpers are the one place where each list is spelled.
+
+// A k-distribution as the C entries receive it: spectral dimensions and table pointers, in the order of the C signatures.
 template<typename F>
-int gas_optics_lw_fractions_impl(
-        int ncol, int nlay, int nband, int ngpt, int ngas, int nflav, int neta, int npres, int ntemp, int nPlanckTemp,
-        int nminorlower, int nminorupper, int idx_h2o,
-        const int* gpoint_flavor, const int* gpoint_bands,
-        const F* kmajor, const F* kminor_lower, const F* kminor_upper,
-        const int* minor_limits_gpt_lower, const int* minor_limits_gpt_upper,
-        const Bool* minor_scales_with_density_lower, const Bool* minor_scales_with_density_upper,
-        const Bool* scale_by_complement_lower, const Bool* scale_by_complement_upper,
-        const int* idx_minor_lower, const int* idx_minor_upper,
-        const int* idx_minor_scaling_lower, const int* idx_minor_scaling_upper,
-        const int* kminor_start_lower, const int* kminor_start_upper,
-        const InterpArgs<F> ia, const F* play, const F* tlay, const F* tlev, const F* tsfc, int sfc_lay, const F* col_gas,
-        const F* pfracin, F totplnk_delta, const F* totplnk,
-        F* tau, F* pfrac, F* blay, F* blev, F* sfc_src, F* sfc_src_jac, void* stream)
+struct GasTables
 {
-    RRX_TRY
-    (void)ngas; (void)nflav;
-    if (ncol <= 0 || nlay <= 0 || ngpt <= 0) throw std::runtime_error("empty problem");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int nchunk = (ngpt + GCH - 1) / GCH;
-    const int nmax = std::max(nminorlower, nminorupper);
+    int nband, ngpt, neta, npres, ntemp, nminorlower, nminorupper, idx_h2o;
+    const int* gpoint_flavor; const int* band_lims_gpt;
+    const F* kmajor; const F* kminor_lower; const F* kminor_upper;
+    const int* minor_limits_gpt_lower; const int* minor_limits_gpt_upper;
+    const Bool* minor_scales_with_density_lower; const Bool* minor_scales_with_density_upper;
+    const Bool* scale_by_complement_lower; const Bool* scale_by_complement_upper;
+    const int* idx_minor_lower; const int* idx_minor_upper;
+    const int* idx_minor_scaling_lower; const int* idx_minor_scaling_upper;
+    const int* kminor_start_lower; const int* kminor_start_upper;
+    const F* krayl = nullptr;                    // SW forms
+};
+
+// The cells of a launch: inputs and outputs. The direct forms use the first line; the interpolation arrays behind it are read by the
+// reference-shaped entries only.
+template<typename F>
+struct GasCells
+{
+    int ncol, nlay;
+    const F* play; const F* tlay; const F* col_gas; const F* col_dry = nullptr; F* tau = nullptr; F* ssa = nullptr; F* g = nullptr;
+    const Bool* tropo = nullptr; const F* col_mix = nullptr; const F* fmajor = nullptr; const F* fminor = nullptr;
+    const int* jeta = nullptr; const int* jtemp = nullptr; const int* jpress = nullptr;
+};
+
+// The tail of a gather kernel's argument list behind a windowed launch (tau_absorption_kernel, planck_fraction_kernel); the
+// defaults are a plain launch over the whole grid.
+struct TodoTail { const int* todo = nullptr; int gx = 1, nblk = 1, nz = 1, geom = 0; };
+
+// LDS of the gather kernel: its index tables
+inline size_t gather_lds_bytes(const int ngpt, const int nminorlower, const int nminorupper)
+{
+    const int nchunk = (ngpt + GCH - 1) / GCH, nmax = std::max(nminorlower, nminorupper);
     const size_t lds = (size_t(3)*ngpt + size_t(2)*nchunk*(1 + ITEM*nmax) + size_t(2)*MM*nmax)*sizeof(int);
     if (lds > 64*1024) throw std::runtime_error("minor-gas index exceeds 64 KiB of LDS");
-    const dim3 block(64, 4);
-    const dim3 grid(ceil_div(ncol, 64), ceil_div(nlay, 4));
-    const int ncmax = gas_window_ncmax(ngpt, nband);
-    const size_t wlds = gas_window_lds_bytes<F>(ngpt, nmax, ncmax, 2, true);
+    return lds;
+}
+
+template<typename F, int MODE, bool DIRECT, bool CLD>
+void launch_tau_absorption(hipStream_t st, const dim3 grid, const size_t lds, const GasTables<F>& k, const GasCells<F>& c, const InterpArgs<F>& ia,
+                           const TodoTail& t = TodoTail())
+{
+    tau_absorption_kernel<F,MODE,DIRECT,CLD><<<grid, dim3(64, 4), lds, st>>>(
+            c.ncol, c.nlay, k.ngpt, k.neta, k.npres, k.ntemp, k.nminorlower, k.nminorupper, k.idx_h2o, k.gpoint_flavor,
+            k.kmajor, k.kminor_lower, k.kminor_upper, k.minor_limits_gpt_lower, k.minor_limits_gpt_upper,
+            k.minor_scales_with_density_lower, k.minor_scales_with_density_upper,
+            k.scale_by_complement_lower, k.scale_by_complement_upper,
+            k.idx_minor_lower, k.idx_minor_upper, k.idx_minor_scaling_lower, k.idx_minor_scaling_upper,
+            k.kminor_start_lower, k.kminor_start_upper,
+            c.tropo, c.col_mix, c.fmajor, c.fminor, c.play, c.tlay, c.col_gas, c.col_dry, c.jeta, c.jtemp, c.jpress, k.krayl,
+            c.tau, c.ssa, c.g, ia, t.todo, t.gx, t.nblk, t.nz, t.geom);
+}
+
+// What a windowed launch needs besides the kernel's own arguments; `windowed` false: the shape goes to the gather kernels alone
+struct GasWindowPlan
+{
+    bool windowed = false;
+    int geom = 0, nblk = 0, nz = 1, ncmax = 0;
+    dim3 grid;                                   // (column, layer) workgroups; the launch adds nz parts as grid.z
+    size_t lds = 0;
+    int* todo = nullptr; int* tbl = nullptr;
+    TodoTail tail() const { return windowed ? TodoTail{todo, int(grid.x), nblk, nz, geom} : TodoTail(); }
+};
+
+// Set-up of a windowed launch, on the stream: is the shape eligible; geometry, grid and parts; the todo list, zeroed; the index
+// tables, checked or rebuilt by their kernel. `mode`, `pf`: the form of gas_window_kernel that follows; `nlist`: how many
+// contributors a chunk of that form may have; `gpoint_bands`: null where the form has no use for the bands of the g-points.
+template<typename F>
+GasWindowPlan gas_window_plan(hipStream_t st, StreamScratch& scratch, const GasTables<F>& k, const GasCells<F>& c, const InterpArgs<F>& ia,
+                              const int mode, const bool pf, const int nlist, const int* gpoint_bands)
+{
+    GasWindowPlan p;
+    const int nchunk = (k.ngpt + GCH - 1) / GCH;
+    const int nmax = std::max(k.nminorlower, k.nminorupper);
+    p.ncmax = gas_window_ncmax(k.ngpt, k.nband);
+    p.lds = gas_window_lds_bytes<F>(k.ngpt, nmax, p.ncmax, mode, pf);
     // (the windowed kernel addresses a cell inside a g-point slab, and a node inside the kmajor / planck_frac tables, with 32-bit byte
     //  offsets; a table beyond 4 GB -- far above any k-distribution -- goes to the gather kernels instead of wrapping. The minor and
     //  Rayleigh tables are smaller than kmajor by the pressure dimension.)
-    const bool windowed = tuning().go_window && wlds <= 64*1024 && size_t(ncol)*nlay*sizeof(F) < (size_t(1) << 32)
-                          && size_t(ngpt)*ntemp*neta*(npres+1)*sizeof(F) < (size_t(1) << 32);
+    p.windowed = tuning().go_window && p.lds <= 64*1024 && size_t(c.ncol)*c.nlay*sizeof(F) < (size_t(1) << 32)
+                 && size_t(k.ngpt)*k.ntemp*k.neta*(k.npres+1)*sizeof(F) < (size_t(1) << 32);
+    if (!p.windowed) return p;
+    p.geom = gas_window_geometry(c.ncol);
+    p.grid = gas_window_grid(p.geom, c.ncol, c.nlay);
+    p.nblk = int(p.grid.x)*int(p.grid.y);
+    p.nz = gas_window_parts(p.nblk, nchunk);
+    p.todo = scratch.get<int>(size_t(9) + size_t(p.nblk)*p.nz) + 8;
+    if (hipMemsetAsync(p.todo - 8, 0, 9*sizeof(int), st) != hipSuccess) throw std::runtime_error("memset failed");
+    const GasWindowTables T{k.ngpt, nmax, p.ncmax};
+    const int* lims = ia.cld_tau != nullptr ? ia.cld_lims : nullptr;
+    p.tbl = gas_window_tables(st, k.gpoint_flavor, k.ngpt, k.nminorlower, k.nminorupper, p.ncmax, nlist, (pf ? 1 : 0) + (lims != nullptr ? 2 : 0));
+    gas_window_tables_kernel<<<1, 256, size_t(T.off_gx() + k.ngpt + 4 + 2*((k.ngpt + 63)/64))*sizeof(int), st>>>(
+            k.ngpt, k.nminorlower, k.nminorupper, p.ncmax, nlist, k.nband, k.gpoint_flavor, ia.flavor, gpoint_bands, lims,
+            k.minor_limits_gpt_lower, k.minor_limits_gpt_upper,
+            k.minor_scales_with_density_lower, k.minor_scales_with_density_upper, k.scale_by_complement_lower, k.scale_by_complement_upper,
+            k.idx_minor_lower, k.idx_minor_upper, k.idx_minor_scaling_lower, k.idx_minor_scaling_upper,
+            k.kminor_start_lower, k.kminor_start_upper, p.tbl);
+    return p;
+}
+
+template<typename F, int MODE, bool PF, bool CLD>
+void launch_gas_window(hipStream_t st, const GasWindowPlan& p, const GasTables<F>& k, const GasCells<F>& c, const InterpArgs<F>& ia,
+                       const PlanckArgs<F>& pa = PlanckArgs<F>())
+{
+    gas_window_kernel<F,MODE,PF,CLD><<<dim3(p.grid.x, p.grid.y, p.nz), dim3(64, 4), p.lds, st>>>(
+            c.ncol, c.nlay, k.ngpt, k.neta, k.npres, k.ntemp, k.nminorlower, k.nminorupper, k.idx_h2o, k.gpoint_flavor,
+            k.kmajor, k.kminor_lower, k.kminor_upper, k.minor_limits_gpt_lower, k.minor_limits_gpt_upper,
+            k.minor_scales_with_density_lower, k.minor_scales_with_density_upper,
+            k.scale_by_complement_lower, k.scale_by_complement_upper,
+            k.idx_minor_lower, k.idx_minor_upper, k.idx_minor_scaling_lower, k.idx_minor_scaling_upper,
+            k.kminor_start_lower, k.kminor_start_upper, c.play, c.tlay, c.col_gas, c.col_dry, k.krayl, ia,
+            c.tau, c.ssa, c.g, pa, p.todo, p.geom, p.tbl, p.ncmax);
+}
+
+// The all-sky (CLD) forms exist where ALLOWED and are taken when the launch has by-band cloud properties: fn(std::true_type) or
+// fn(std::false_type), and no instantiation of the former where it is not allowed.
+template<bool ALLOWED, typename F, typename Fn>
+void with_cld(const InterpArgs<F>& ia, Fn&& fn)
+{
+    if constexpr (ALLOWED) { if (ia.cld_tau != nullptr) { fn(std::bool_constant<true>{}); return; } }
+    fn(std::bool_constant<false>{});
+}
+
+// LW gas optics + Planck-lite in one pass: windowed kernel with the Planck fractions riding along; the workgroups it hands
+// back are finished by the gather kernel (tau) and planck_fraction_kernel (fractions, band Planck functions, surface terms)
+template<typename F>
+int gas_optics_lw_fractions_impl(const GasTables<F>& k, const GasCells<F>& c, const InterpArgs<F>& ia, const PlanckArgs<F>& pa, void* stream)
+{
+    RRX_TRY
+    if (c.ncol <= 0 || c.nlay <= 0 || k.ngpt <= 0) throw std::runtime_error("empty problem");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t lds = gather_lds_bytes(k.ngpt, k.nminorlower, k.nminorupper);
     StreamScratch scratch(st);
-    const int geom = gas_window_geometry(ncol);
-    const dim3 wgrid = gas_window_grid(geom, ncol, nlay);
-    const int nblk = windowed ? int(wgrid.x)*int(wgrid.y) : int(grid.x)*int(grid.y);
-    const int nz = gas_window_parts(nblk, nchunk);
-    int* todo = nullptr;
-    if (windowed)
+    const GasWindowPlan p = gas_window_plan<F>(st, scratch, k, c, ia, 2, true, NXW, pa.gpoint_bands);
+    const dim3 g2 = p.windowed ? gather_grid(p.nblk*p.nz) : dim3(ceil_div(c.ncol, 64), ceil_div(c.nlay, 4));
+    const TodoTail t = p.tail();
+    with_cld<true>(ia, [&](auto CLD_)
     {
-        todo = scratch.get<int>(size_t(9) + size_t(nblk)*nz) + 8;
-        if (hipMemsetAsync(todo - 8, 0, 9*sizeof(int), st) != hipSuccess) throw std::runtime_error("memset failed");
-        const GasWindowTables T{ngpt, nmax, ncmax};
-        const int* lims = ia.cld_tau != nullptr ? ia.cld_lims : nullptr;
-        int* tbl = gas_window_tables(st, gpoint_flavor, ngpt, nminorlower, nminorupper, ncmax, NXW, 1 + (lims != nullptr ? 2 : 0));
-        gas_window_tables_kernel<<<1, 256, size_t(T.off_gx() + ngpt + 4 + 2*((ngpt + 63)/64))*sizeof(int), st>>>(
-                ngpt, nminorlower, nminorupper, ncmax, NXW, nband, gpoint_flavor, ia.flavor, gpoint_bands, lims, minor_limits_gpt_lower, minor_limits_gpt_upper,
-                minor_scales_with_density_lower, minor_scales_with_density_upper, scale_by_complement_lower, scale_by_complement_upper,
-                idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper,
-                kminor_start_lower, kminor_start_upper, tbl);
-        const PlanckArgs<F> pa{pfracin, tlev, tsfc, sfc_lay, nPlanckTemp, gpoint_bands, totplnk_delta, totplnk, pfrac, blay, blev, sfc_src, sfc_src_jac};
-#define RRX_GW_PF_ARGS ncol, nlay, ngpt, neta, npres, ntemp, nminorlower, nminorupper, idx_h2o, gpoint_flavor, \
-                kmajor, kminor_lower, kminor_upper, minor_limits_gpt_lower, minor_limits_gpt_upper, \
-                minor_scales_with_density_lower, minor_scales_with_density_upper, \
-                scale_by_complement_lower, scale_by_complement_upper, \
-                idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper, \
-                kminor_start_lower, kminor_start_upper, play, tlay, col_gas, (const F*)nullptr, (const F*)nullptr, ia, \
-                tau, (F*)nullptr, (F*)nullptr, pa, todo, geom, tbl, ncmax
-        if (ia.cld_tau != nullptr) gas_window_kernel<F,2,true,true><<<dim3(wgrid.x, wgrid.y, nz), block, wlds, st>>>(RRX_GW_PF_ARGS);
-        else gas_window_kernel<F,2,true><<<dim3(wgrid.x, wgrid.y, nz), block, wlds, st>>>(RRX_GW_PF_ARGS);
-#undef RRX_GW_PF_ARGS
-        gas_window_stats("lw + fractions", todo, nblk*nz, st);
-    }
-    const dim3 g2 = windowed ? gather_grid(nblk*nz) : grid;
-#define RRX_TA_PF_ARGS ncol, nlay, ngpt, neta, npres, ntemp, nminorlower, nminorupper, idx_h2o, gpoint_flavor, \
-            kmajor, kminor_lower, kminor_upper, minor_limits_gpt_lower, minor_limits_gpt_upper, \
-            minor_scales_with_density_lower, minor_scales_with_density_upper, \
-            scale_by_complement_lower, scale_by_complement_upper, \
-            idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper, \
-            kminor_start_lower, kminor_start_upper, \
-            (const Bool*)nullptr, (const F*)nullptr, (const F*)nullptr, (const F*)nullptr, play, tlay, col_gas, (const F*)nullptr, \
-            (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, (const F*)nullptr, \
-            tau, (F*)nullptr, (F*)nullptr, ia, todo, int(wgrid.x), nblk, nz, windowed ? geom : 0
-    if (ia.cld_tau != nullptr) tau_absorption_kernel<F,2,true,true><<<g2, block, lds, st>>>(RRX_TA_PF_ARGS);
-    else tau_absorption_kernel<F,2,true><<<g2, block, lds, st>>>(RRX_TA_PF_ARGS);
-#undef RRX_TA_PF_ARGS
-    planck_fraction_kernel<F><<<g2, block, size_t(2)*ngpt*sizeof(int), st>>>(
-            ncol, nlay, ngpt, neta, npres, ntemp, nPlanckTemp, play, tlay, tlev, tsfc, sfc_lay, col_gas, ia, gpoint_bands, pfracin,
-            totplnk_delta, totplnk, gpoint_flavor, pfrac, blay, blev, sfc_src, sfc_src_jac, todo, int(wgrid.x), nblk, nz, windowed ? geom : 0);
+        constexpr bool CLD = decltype(CLD_)::value;
+        if (p.windowed)
+        {
+            launch_gas_window<F,2,true,CLD>(st, p, k, c, ia, pa);
+            gas_window_stats("lw + fractions", p.todo, p.nblk*p.nz, st);
+        }
+        launch_tau_absorption<F,2,true,CLD>(st, g2, lds, k, c, ia, t);
+    });
+    planck_fraction_kernel<F><<<g2, dim3(64, 4), size_t(2)*k.ngpt*sizeof(int), st>>>(
+            c.ncol, c.nlay, k.ngpt, k.neta, k.npres, k.ntemp, pa.nPlanckTemp, c.play, c.tlay, pa.tlev, pa.tsfc, pa.sfc_lay, c.col_gas, ia,
+            pa.gpoint_bands, pa.pfracin, pa.totplnk_delta, pa.totplnk, k.gpoint_flavor, pa.pfrac, pa.blay, pa.blev, pa.sfc_src, pa.sfc_src_jac,
+            t.todo, t.gx, t.nblk, t.nz, t.geom);
     RRX_CATCH("rrx_gas_optics_lw_fractions")
 }
 
 template<typename F, int MODE, bool DIRECT = false>
-int tau_absorption_impl(
-        int ncol, int nlay, int nband, int ngpt, int ngas, int nflav, int neta, int npres, int ntemp,
-        int nminorlower, int nminorklower, int nminorupper, int nminorkupper, int idx_h2o,
-        const int* gpoint_flavor, const int* band_lims_gpt,
-        const F* kmajor, const F* kminor_lower, const F* kminor_upper,
-        const int* minor_limits_gpt_lower, const int* minor_limits_gpt_upper,
-        const Bool* minor_scales_with_density_lower, const Bool* minor_scales_with_density_upper,
-        const Bool* scale_by_complement_lower, const Bool* scale_by_complement_upper,
-        const int* idx_minor_lower, const int* idx_minor_upper,
-        const int* idx_minor_scaling_lower, const int* idx_minor_scaling_upper,
-        const int* kminor_start_lower, const int* kminor_start_upper,
-        const Bool* tropo, const F* col_mix, const F* fmajor, const F* fminor,
-        const F* play, const F* tlay, const F* col_gas, const F* col_dry,
-        const int* jeta, const int* jtemp, const int* jpress, const F* krayl,
-        F* tau, F* ssa, F* g, void* stream, const char* name, const InterpArgs<F> ia = InterpArgs<F>())
+int tau_absorption_impl(const GasTables<F>& k, const GasCells<F>& c, void* stream, const char* name, const InterpArgs<F>& ia = InterpArgs<F>())
 {
     RRX_TRY
-    (void)ngas; (void)nflav; (void)band_lims_gpt; (void)nminorklower; (void)nminorkupper;
-    if (ncol <= 0 || nlay <= 0 || ngpt <= 0) throw std::runtime_error("empty problem");
-    const int nchunk = (ngpt + GCH - 1) / GCH;
-    const int nmax = std::max(nminorlower, nminorupper);
-    const size_t lds = (size_t(3)*ngpt + size_t(2)*nchunk*(1 + ITEM*nmax) + size_t(2)*MM*nmax)*sizeof(int);
-    if (lds > 64*1024) throw std::runtime_error("minor-gas index exceeds 64 KiB of LDS");
-    const dim3 block(64, 4);
-    const dim3 grid(ceil_div(ncol, 64), ceil_div(nlay, 4));
-    if constexpr (DIRECT && MODE != 0)
+    if (c.ncol <= 0 || c.nlay <= 0 || k.ngpt <= 0) throw std::runtime_error("empty problem");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t lds = gather_lds_bytes(k.ngpt, k.nminorlower, k.nminorupper);
+    constexpr bool HAS_CLD = DIRECT && MODE != 0;
+    StreamScratch scratch(st);
+    GasWindowPlan p;
+    // windowed kernel first; the gather kernel then finishes the workgroups it handed back (usually none)
+    if constexpr (DIRECT && MODE != 0) p = gas_window_plan<F>(st, scratch, k, c, ia, MODE, false, (MODE == 1) ? NCW : NXW, nullptr);
+    with_cld<HAS_CLD>(ia, [&](auto CLD_)
     {
-        // windowed kernel first; the gather kernel then finishes the workgroups it handed back (usually none)
-        const int ncmax = gas_window_ncmax(ngpt, nband);
-        const size_t wlds = gas_window_lds_bytes<F>(ngpt, nmax, ncmax, MODE, false);
-        // (32-bit byte offsets inside a g-point slab and inside the kmajor table, see gas_optics_lw_fractions_impl)
-        if (tuning().go_window && wlds <= 64*1024 && size_t(ncol)*nlay*sizeof(F) < (size_t(1) << 32)
-            && size_t(ngpt)*ntemp*neta*(npres+1)*sizeof(F) < (size_t(1) << 32))
+        constexpr bool CLD = decltype(CLD_)::value;
+        if constexpr (DIRECT && MODE != 0)
         {
-            hipStream_t st = static_cast<hipStream_t>(stream);
-            StreamScratch scratch(st);
-            const int geom = gas_window_geometry(ncol);
-            const dim3 wgrid = gas_window_grid(geom, ncol, nlay);
-            const int nblk = int(wgrid.x)*int(wgrid.y);
-            const int nz = gas_window_parts(nblk, nchunk);
-            int* todo = scratch.get<int>(size_t(9) + size_t(nblk)*nz) + 8;
-            if (hipMemsetAsync(todo - 8, 0, 9*sizeof(int), st) != hipSuccess) throw std::runtime_error("memset failed");
-            const GasWindowTables T{ngpt, nmax, ncmax};
-            const int* lims = ia.cld_tau != nullptr ? ia.cld_lims : nullptr;
-            int* tbl = gas_window_tables(st, gpoint_flavor, ngpt, nminorlower, nminorupper, ncmax, (MODE == 1) ? NCW : NXW, lims != nullptr ? 2 : 0);
-            gas_window_tables_kernel<<<1, 256, size_t(T.off_gx() + ngpt + 4 + 2*((ngpt + 63)/64))*sizeof(int), st>>>(
-                    ngpt, nminorlower, nminorupper, ncmax, (MODE == 1) ? NCW : NXW, nband, gpoint_flavor, ia.flavor, (const int*)nullptr, lims, minor_limits_gpt_lower, minor_limits_gpt_upper,
-                    minor_scales_with_density_lower, minor_scales_with_density_upper, scale_by_complement_lower, scale_by_complement_upper,
-                    idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper,
-                    kminor_start_lower, kminor_start_upper, tbl);
-#define RRX_GW_ARGS ncol, nlay, ngpt, neta, npres, ntemp, nminorlower, nminorupper, idx_h2o, gpoint_flavor, \
-                    kmajor, kminor_lower, kminor_upper, minor_limits_gpt_lower, minor_limits_gpt_upper, \
-                    minor_scales_with_density_lower, minor_scales_with_density_upper, \
-                    scale_by_complement_lower, scale_by_complement_upper, \
-                    idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper, \
-                    kminor_start_lower, kminor_start_upper, play, tlay, col_gas, col_dry, krayl, ia, tau, ssa, g, \
-                    PlanckArgs<F>(), todo, geom, tbl, ncmax
-#define RRX_TA_ARGS ncol, nlay, ngpt, neta, npres, ntemp, nminorlower, nminorupper, idx_h2o, gpoint_flavor, \
-                    kmajor, kminor_lower, kminor_upper, minor_limits_gpt_lower, minor_limits_gpt_upper, \
-                    minor_scales_with_density_lower, minor_scales_with_density_upper, \
-                    scale_by_complement_lower, scale_by_complement_upper, \
-                    idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper, \
-                    kminor_start_lower, kminor_start_upper, \
-                    tropo, col_mix, fmajor, fminor, play, tlay, col_gas, col_dry, jeta, jtemp, jpress, krayl, \
-                    tau, ssa, g, ia, todo, int(wgrid.x), nblk, nz, geom
-            const bool cld = DIRECT && MODE != 0 && ia.cld_tau != nullptr;
-            if constexpr (DIRECT && MODE != 0)
+            if (p.windowed)
             {
-                if (cld) gas_window_kernel<F,MODE,false,true><<<dim3(wgrid.x, wgrid.y, nz), block, wlds, st>>>(RRX_GW_ARGS);
+                launch_gas_window<F,MODE,false,CLD>(st, p, k, c, ia);
+                gas_window_stats(MODE == 1 ? "sw" : "lw", p.todo, p.nblk*p.nz, st);
+                launch_tau_absorption<F,MODE,DIRECT,CLD>(st, gather_grid(p.nblk*p.nz), lds, k, c, ia, p.tail());
+                return;
             }
-            if (!cld) gas_window_kernel<F,MODE,false><<<dim3(wgrid.x, wgrid.y, nz), block, wlds, st>>>(RRX_GW_ARGS);
-            gas_window_stats(MODE == 1 ? "sw" : "lw", todo, nblk*nz, st);
-            if constexpr (DIRECT && MODE != 0)
-            {
-                if (cld) tau_absorption_kernel<F,MODE,DIRECT,true><<<gather_grid(nblk*nz), block, lds, st>>>(RRX_TA_ARGS);
-            }
-            if (!cld) tau_absorption_kernel<F,MODE,DIRECT><<<gather_grid(nblk*nz), block, lds, st>>>(RRX_TA_ARGS);
-#undef RRX_GW_ARGS
-#undef RRX_TA_ARGS
-            return check_launch(name);
         }
-    }
-#define RRX_TA_ARGS ncol, nlay, ngpt, neta, npres, ntemp, nminorlower, nminorupper, idx_h2o, gpoint_flavor, \
-            kmajor, kminor_lower, kminor_upper, minor_limits_gpt_lower, minor_limits_gpt_upper, \
-            minor_scales_with_density_lower, minor_scales_with_density_upper, \
-            scale_by_complement_lower, scale_by_complement_upper, \
-            idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper, \
-            kminor_start_lower, kminor_start_upper, \
-            tropo, col_mix, fmajor, fminor, play, tlay, col_gas, col_dry, jeta, jtemp, jpress, krayl, \
-            tau, ssa, g, ia
-    if constexpr (DIRECT && MODE != 0)
-    {
-        if (ia.cld_tau != nullptr)
-        {
-            tau_absorption_kernel<F,MODE,DIRECT,true><<<grid, block, lds, static_cast<hipStream_t>(stream)>>>(RRX_TA_ARGS);
-            return check_launch(name);
-        }
-    }
-    tau_absorption_kernel<F,MODE,DIRECT><<<grid, block, lds, static_cast<hipStream_t>(stream)>>>(RRX_TA_ARGS);
-#undef RRX_TA_ARGS
+        launch_tau_absorption<F,MODE,DIRECT,CLD>(st, dim3(ceil_div(c.ncol, 64), ceil_div(c.nlay, 4)), lds, k, c, ia);
+    });
     RRX_CATCH(name)
 }
 }  // namespace
@@ -2730,6 +2576,11 @@ int tau_absorption_impl(
 
 extern "C"
 {
+// The leading members of GasTables<F>, by the names every entry below gives them: the one place where a parameter meets its member.
+#define RRX_GAS_TABLES nband, ngpt, neta, npres, ntemp, nminorlower, nminorupper, idx_h2o, gpoint_flavor, band_lims_gpt, \
+        kmajor, kminor_lower, kminor_upper, minor_limits_gpt_lower, minor_limits_gpt_upper, \
+        minor_scales_with_density_lower, minor_scales_with_density_upper, scale_by_complement_lower, scale_by_complement_upper, \
+        idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper, kminor_start_lower, kminor_start_upper
 #define RRX_DEFINE_GAS(F, SFX) \
 int rrx_interpolation##SFX( \
         int ncol, int nlay, int ngas, int nflav, int neta, int npres, int ntemp, \
@@ -2761,13 +2612,9 @@ int rrx_compute_tau_absorption##SFX( \
         const F* play, const F* tlay, const F* col_gas, \
         const int* jeta, const int* jtemp, const int* jpress, F* tau, void* stream) \
 { \
-    return tau_absorption_impl<F,0>(ncol, nlay, nband, ngpt, ngas, nflav, neta, npres, ntemp, \
-            nminorlower, nminorklower, nminorupper, nminorkupper, idx_h2o, gpoint_flavor, band_lims_gpt, \
-            kmajor, kminor_lower, kminor_upper, minor_limits_gpt_lower, minor_limits_gpt_upper, \
-            minor_scales_with_density_lower, minor_scales_with_density_upper, scale_by_complement_lower, scale_by_complement_upper, \
-            idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper, kminor_start_lower, kminor_start_upper, \
-            tropo, col_mix, fmajor, fminor, play, tlay, col_gas, (const F*)nullptr, jeta, jtemp, jpress, (const F*)nullptr, \
-            tau, (F*)nullptr, (F*)nullptr, stream, "rrx_compute_tau_absorption"); \
+    const GasTables<F> kd{RRX_GAS_TABLES}; \
+    const GasCells<F> cells{ncol, nlay, play, tlay, col_gas, nullptr, tau, nullptr, nullptr, tropo, col_mix, fmajor, fminor, jeta, jtemp, jpress}; \
+    return tau_absorption_impl<F,0>(kd, cells, stream, "rrx_compute_tau_absorption"); \
 } \
 int rrx_compute_tau_absorption_set##SFX( \
         int ncol, int nlay, int nband, int ngpt, int ngas, int nflav, int neta, int npres, int ntemp, \
@@ -2784,13 +2631,9 @@ int rrx_compute_tau_absorption_set##SFX( \
         const F* play, const F* tlay, const F* col_gas, \
         const int* jeta, const int* jtemp, const int* jpress, F* tau, void* stream) \
 { \
-    return tau_absorption_impl<F,2>(ncol, nlay, nband, ngpt, ngas, nflav, neta, npres, ntemp, \
-            nminorlower, nminorklower, nminorupper, nminorkupper, idx_h2o, gpoint_flavor, band_lims_gpt, \
-            kmajor, kminor_lower, kminor_upper, minor_limits_gpt_lower, minor_limits_gpt_upper, \
-            minor_scales_with_density_lower, minor_scales_with_density_upper, scale_by_complement_lower, scale_by_complement_upper, \
-            idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper, kminor_start_lower, kminor_start_upper, \
-            tropo, col_mix, fmajor, fminor, play, tlay, col_gas, (const F*)nullptr, jeta, jtemp, jpress, (const F*)nullptr, \
-            tau, (F*)nullptr, (F*)nullptr, stream, "rrx_compute_tau_absorption_set"); \
+    const GasTables<F> kd{RRX_GAS_TABLES}; \
+    const GasCells<F> cells{ncol, nlay, play, tlay, col_gas, nullptr, tau, nullptr, nullptr, tropo, col_mix, fmajor, fminor, jeta, jtemp, jpress}; \
+    return tau_absorption_impl<F,2>(kd, cells, stream, "rrx_compute_tau_absorption_set"); \
 } \
 int rrx_gas_optics_sw_fused##SFX( \
         int ncol, int nlay, int nband, int ngpt, int ngas, int nflav, int neta, int npres, int ntemp, \
@@ -2808,13 +2651,9 @@ int rrx_gas_optics_sw_fused##SFX( \
         const int* jeta, const int* jtemp, const int* jpress, const F* krayl, \
         F* tau, F* ssa, F* g, void* stream) \
 { \
-    return tau_absorption_impl<F,1>(ncol, nlay, nband, ngpt, ngas, nflav, neta, npres, ntemp, \
-            nminorlower, nminorklower, nminorupper, nminorkupper, idx_h2o, gpoint_flavor, band_lims_gpt, \
-            kmajor, kminor_lower, kminor_upper, minor_limits_gpt_lower, minor_limits_gpt_upper, \
-            minor_scales_with_density_lower, minor_scales_with_density_upper, scale_by_complement_lower, scale_by_complement_upper, \
-            idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper, kminor_start_lower, kminor_start_upper, \
-            tropo, col_mix, fmajor, fminor, play, tlay, col_gas, col_dry, jeta, jtemp, jpress, krayl, \
-            tau, ssa, g, stream, "rrx_gas_optics_sw_fused"); \
+    const GasTables<F> kd{RRX_GAS_TABLES, krayl}; \
+    const GasCells<F> cells{ncol, nlay, play, tlay, col_gas, col_dry, tau, ssa, g, tropo, col_mix, fmajor, fminor, jeta, jtemp, jpress}; \
+    return tau_absorption_impl<F,1>(kd, cells, stream, "rrx_gas_optics_sw_fused"); \
 } \
 int rrx_gas_optics_lw_direct##SFX( \
         int ncol, int nlay, int nband, int ngpt, int ngas, int nflav, int neta, int npres, int ntemp, \
@@ -2831,15 +2670,9 @@ int rrx_gas_optics_lw_direct##SFX( \
         F press_ref_log_delta, F temp_ref_min, F temp_ref_delta, F press_ref_trop_log, const F* vmr_ref, \
         const F* play, const F* tlay, const F* col_gas, F* tau, void* stream) \
 { \
+    const GasTables<F> kd{RRX_GAS_TABLES}; \
     const InterpArgs<F> ia{ngas, flavor, press_ref_log, temp_ref, press_ref_log_delta, temp_ref_min, temp_ref_delta, press_ref_trop_log, vmr_ref}; \
-    return tau_absorption_impl<F,2,true>(ncol, nlay, nband, ngpt, ngas, nflav, neta, npres, ntemp, \
-            nminorlower, nminorklower, nminorupper, nminorkupper, idx_h2o, gpoint_flavor, band_lims_gpt, \
-            kmajor, kminor_lower, kminor_upper, minor_limits_gpt_lower, minor_limits_gpt_upper, \
-            minor_scales_with_density_lower, minor_scales_with_density_upper, scale_by_complement_lower, scale_by_complement_upper, \
-            idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper, kminor_start_lower, kminor_start_upper, \
-            (const RrxBool*)nullptr, (const F*)nullptr, (const F*)nullptr, (const F*)nullptr, play, tlay, col_gas, (const F*)nullptr, \
-            (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, (const F*)nullptr, \
-            tau, (F*)nullptr, (F*)nullptr, stream, "rrx_gas_optics_lw_direct", ia); \
+    return tau_absorption_impl<F,2,true>(kd, GasCells<F>{ncol, nlay, play, tlay, col_gas, nullptr, tau}, stream, "rrx_gas_optics_lw_direct", ia); \
 } \
 int rrx_gas_optics_lw_direct_allsky##SFX( \
         int ncol, int nlay, int nband, int ngpt, int ngas, int nflav, int neta, int npres, int ntemp, \
@@ -2856,16 +2689,10 @@ int rrx_gas_optics_lw_direct_allsky##SFX( \
         F press_ref_log_delta, F temp_ref_min, F temp_ref_delta, F press_ref_trop_log, const F* vmr_ref, \
         const F* play, const F* tlay, const F* col_gas, F* tau, const F* cld_tau, void* stream) \
 { \
+    const GasTables<F> kd{RRX_GAS_TABLES}; \
     const InterpArgs<F> ia{ngas, flavor, press_ref_log, temp_ref, press_ref_log_delta, temp_ref_min, temp_ref_delta, press_ref_trop_log, vmr_ref, \
             cld_tau, (const F*)nullptr, (const F*)nullptr, band_lims_gpt}; \
-    return tau_absorption_impl<F,2,true>(ncol, nlay, nband, ngpt, ngas, nflav, neta, npres, ntemp, \
-            nminorlower, nminorklower, nminorupper, nminorkupper, idx_h2o, gpoint_flavor, band_lims_gpt, \
-            kmajor, kminor_lower, kminor_upper, minor_limits_gpt_lower, minor_limits_gpt_upper, \
-            minor_scales_with_density_lower, minor_scales_with_density_upper, scale_by_complement_lower, scale_by_complement_upper, \
-            idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper, kminor_start_lower, kminor_start_upper, \
-            (const RrxBool*)nullptr, (const F*)nullptr, (const F*)nullptr, (const F*)nullptr, play, tlay, col_gas, (const F*)nullptr, \
-            (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, (const F*)nullptr, \
-            tau, (F*)nullptr, (F*)nullptr, stream, "rrx_gas_optics_lw_direct_allsky", ia); \
+    return tau_absorption_impl<F,2,true>(kd, GasCells<F>{ncol, nlay, play, tlay, col_gas, nullptr, tau}, stream, "rrx_gas_optics_lw_direct_allsky", ia); \
 } \
 int rrx_gas_optics_sw_direct##SFX( \
         int ncol, int nlay, int nband, int ngpt, int ngas, int nflav, int neta, int npres, int ntemp, \
@@ -2883,15 +2710,9 @@ int rrx_gas_optics_sw_direct##SFX( \
         const F* play, const F* tlay, const F* col_gas, const F* col_dry, const F* krayl, \
         F* tau, F* ssa, F* g, void* stream) \
 { \
+    const GasTables<F> kd{RRX_GAS_TABLES, krayl}; \
     const InterpArgs<F> ia{ngas, flavor, press_ref_log, temp_ref, press_ref_log_delta, temp_ref_min, temp_ref_delta, press_ref_trop_log, vmr_ref}; \
-    return tau_absorption_impl<F,1,true>(ncol, nlay, nband, ngpt, ngas, nflav, neta, npres, ntemp, \
-            nminorlower, nminorklower, nminorupper, nminorkupper, idx_h2o, gpoint_flavor, band_lims_gpt, \
-            kmajor, kminor_lower, kminor_upper, minor_limits_gpt_lower, minor_limits_gpt_upper, \
-            minor_scales_with_density_lower, minor_scales_with_density_upper, scale_by_complement_lower, scale_by_complement_upper, \
-            idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper, kminor_start_lower, kminor_start_upper, \
-            (const RrxBool*)nullptr, (const F*)nullptr, (const F*)nullptr, (const F*)nullptr, play, tlay, col_gas, col_dry, \
-            (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, krayl, \
-            tau, ssa, g, stream, "rrx_gas_optics_sw_direct", ia); \
+    return tau_absorption_impl<F,1,true>(kd, GasCells<F>{ncol, nlay, play, tlay, col_gas, col_dry, tau, ssa, g}, stream, "rrx_gas_optics_sw_direct", ia); \
 } \
 int rrx_gas_optics_sw_direct_allsky##SFX( \
         int ncol, int nlay, int nband, int ngpt, int ngas, int nflav, int neta, int npres, int ntemp, \
@@ -2910,16 +2731,10 @@ int rrx_gas_optics_sw_direct_allsky##SFX( \
         F* tau, F* ssa, F* g, const F* cld_tau, const F* cld_ssa, const F* cld_g, void* stream) \
 { \
     if (cld_tau != nullptr && (cld_ssa == nullptr || cld_g == nullptr || g == nullptr)) { rrx::set_error("rrx_gas_optics_sw_direct_allsky: by-band ssa, g and the g output are needed with by-band tau"); return 1; } \
+    const GasTables<F> kd{RRX_GAS_TABLES, krayl}; \
     const InterpArgs<F> ia{ngas, flavor, press_ref_log, temp_ref, press_ref_log_delta, temp_ref_min, temp_ref_delta, press_ref_trop_log, vmr_ref, \
             cld_tau, cld_ssa, cld_g, band_lims_gpt}; \
-    return tau_absorption_impl<F,1,true>(ncol, nlay, nband, ngpt, ngas, nflav, neta, npres, ntemp, \
-            nminorlower, nminorklower, nminorupper, nminorkupper, idx_h2o, gpoint_flavor, band_lims_gpt, \
-            kmajor, kminor_lower, kminor_upper, minor_limits_gpt_lower, minor_limits_gpt_upper, \
-            minor_scales_with_density_lower, minor_scales_with_density_upper, scale_by_complement_lower, scale_by_complement_upper, \
-            idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper, kminor_start_lower, kminor_start_upper, \
-            (const RrxBool*)nullptr, (const F*)nullptr, (const F*)nullptr, (const F*)nullptr, play, tlay, col_gas, col_dry, \
-            (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, krayl, \
-            tau, ssa, g, stream, "rrx_gas_optics_sw_direct_allsky", ia); \
+    return tau_absorption_impl<F,1,true>(kd, GasCells<F>{ncol, nlay, play, tlay, col_gas, col_dry, tau, ssa, g}, stream, "rrx_gas_optics_sw_direct_allsky", ia); \
 } \
 int rrx_planck_source_direct##SFX( \
         int ncol, int nlay, int nbnd, int ngpt, int ngas, int nflav, int neta, int npres, int ntemp, int nPlanckTemp, \
@@ -2957,13 +2772,10 @@ int rrx_gas_optics_lw_fractions##SFX( \
         const F* pfracin, F totplnk_delta, const F* totplnk, \
         F* tau, F* pfrac, F* blay, F* blev, F* sfc_src, F* sfc_src_jac, void* stream) \
 { \
-    (void)nminorklower; (void)nminorkupper; (void)band_lims_gpt; \
+    const GasTables<F> kd{RRX_GAS_TABLES}; \
     const InterpArgs<F> ia{ngas, flavor, press_ref_log, temp_ref, press_ref_log_delta, temp_ref_min, temp_ref_delta, press_ref_trop_log, vmr_ref}; \
-    return gas_optics_lw_fractions_impl<F>(ncol, nlay, nband, ngpt, ngas, nflav, neta, npres, ntemp, nPlanckTemp, nminorlower, nminorupper, idx_h2o, \
-            gpoint_flavor, gpoint_bands, kmajor, kminor_lower, kminor_upper, minor_limits_gpt_lower, minor_limits_gpt_upper, \
-            minor_scales_with_density_lower, minor_scales_with_density_upper, scale_by_complement_lower, scale_by_complement_upper, \
-            idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper, kminor_start_lower, kminor_start_upper, \
-            ia, play, tlay, tlev, tsfc, sfc_lay, col_gas, pfracin, totplnk_delta, totplnk, tau, pfrac, blay, blev, sfc_src, sfc_src_jac, stream); \
+    const PlanckArgs<F> pa{pfracin, tlev, tsfc, sfc_lay, nPlanckTemp, gpoint_bands, totplnk_delta, totplnk, pfrac, blay, blev, sfc_src, sfc_src_jac}; \
+    return gas_optics_lw_fractions_impl<F>(kd, GasCells<F>{ncol, nlay, play, tlay, col_gas, nullptr, tau}, ia, pa, stream); \
 } \
 int rrx_gas_optics_lw_fractions_allsky##SFX( \
         int ncol, int nlay, int nband, int ngpt, int ngas, int nflav, int neta, int npres, int ntemp, int nPlanckTemp, \
@@ -2982,14 +2794,11 @@ int rrx_gas_optics_lw_fractions_allsky##SFX( \
         const F* pfracin, F totplnk_delta, const F* totplnk, \
         F* tau, F* pfrac, F* blay, F* blev, F* sfc_src, F* sfc_src_jac, const F* cld_tau, void* stream) \
 { \
-    (void)nminorklower; (void)nminorkupper; \
+    const GasTables<F> kd{RRX_GAS_TABLES}; \
     const InterpArgs<F> ia{ngas, flavor, press_ref_log, temp_ref, press_ref_log_delta, temp_ref_min, temp_ref_delta, press_ref_trop_log, vmr_ref, \
             cld_tau, (const F*)nullptr, (const F*)nullptr, band_lims_gpt}; \
-    return gas_optics_lw_fractions_impl<F>(ncol, nlay, nband, ngpt, ngas, nflav, neta, npres, ntemp, nPlanckTemp, nminorlower, nminorupper, idx_h2o, \
-            gpoint_flavor, gpoint_bands, kmajor, kminor_lower, kminor_upper, minor_limits_gpt_lower, minor_limits_gpt_upper, \
-            minor_scales_with_density_lower, minor_scales_with_density_upper, scale_by_complement_lower, scale_by_complement_upper, \
-            idx_minor_lower, idx_minor_upper, idx_minor_scaling_lower, idx_minor_scaling_upper, kminor_start_lower, kminor_start_upper, \
-            ia, play, tlay, tlev, tsfc, sfc_lay, col_gas, pfracin, totplnk_delta, totplnk, tau, pfrac, blay, blev, sfc_src, sfc_src_jac, stream); \
+    const PlanckArgs<F> pa{pfracin, tlev, tsfc, sfc_lay, nPlanckTemp, gpoint_bands, totplnk_delta, totplnk, pfrac, blay, blev, sfc_src, sfc_src_jac}; \
+    return gas_optics_lw_fractions_impl<F>(kd, GasCells<F>{ncol, nlay, play, tlay, col_gas, nullptr, tau}, ia, pa, stream); \
 } \
 int rrx_planck_fractions##SFX( \
         int ncol, int nlay, int nbnd, int ngpt, int ngas, int nflav, int neta, int npres, int ntemp, int nPlanckTemp, \
@@ -3068,6 +2877,8 @@ int rrx_zero_array##SFX(int ni, int nj, int nk, F* arr, void* stream) \
 
 RRX_DEFINE_GAS(double, _f64)
 RRX_DEFINE_GAS(float, _f32)
+#undef RRX_GAS_TABLES
+#undef RRX_DEFINE_GAS
 }
 
 extern "C" int rrx_gas_window_tables_read(int* tables, const int capacity, int* layout)
