@@ -76,6 +76,19 @@ class Rte_lw_gpu
                 Array_gpu<Float,3>& bnd_flux_net,
                 Array_gpu<Float,2>& flux_up,
                 Array_gpu<Float,2>& flux_dn);
+        // LW two-stream solve WITH scattering (rrx_lw_solver_2stream_fractions; a name of its own, not an overload of rte_lw): the clear
+        // gas optical depth of optical_props, Planck-lite sources (throws otherwise) and broadband flux arrays (third dimension 1;
+        // throws otherwise). cloud: LW cloud tau / ssa / g by band, (ncol, nlay, nbnd), combined with the gas inside the kernel; null =
+        // no clouds (ssa = 0). No quadrature angles, no Jacobian, no by-band form.
+        void rte_lw_2stream(
+                const std::unique_ptr<Optical_props_arry_gpu>& optical_props,
+                const Bool top_at_1,
+                const Source_func_lw_gpu& sources,
+                const Array_gpu<Float,2>& sfc_emis,
+                const Array_gpu<Float,2>& inc_flux,
+                const Optical_props_2str_gpu* cloud,
+                Array_gpu<Float,3>& gpt_flux_up,
+                Array_gpu<Float,3>& gpt_flux_dn);
         void expand_and_transpose(
                 const std::unique_ptr<Optical_props_arry_gpu>& ops,
                 const Array_gpu<Float,2> arr_in,

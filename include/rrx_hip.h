@@ -392,6 +392,41 @@ int rrx_lw_solver_noscat_fractions_optimal##SFX( \
         const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands, const F* optimal_angle_fit, \
         const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up_loc, F* flux_dn_loc, \
         const F* sfc_src_jac, F* flux_up_jac, F* secants_out, void* stream); \
+/* lw_solver_2stream: the LW two-stream solver WITH scattering (current RTE+RRTMGP; the reference has none). Per g-point and column, \
+   layers and levels in sweep order from the top, D = 1.66: \
+     gamma1 = D (1 - ssa (1 + g)/2), gamma2 = D ssa (1 - g)/2, k = sqrt(max((gamma1 - gamma2)(gamma1 + gamma2), 1e-12)), \
+     e1 = exp(-tau k), e2 = e1 e1, RT = 1/(k (1 + e2) + gamma1 (1 - e2)), Rdif = RT gamma2 (1 - e2), Tdif = 2 RT k e1; \
+     tau > 1e-8: Z = (lev_bot - lev_top)/(tau (gamma1 + gamma2)), src_up = pi ((Z + lev_top) - Rdif (-Z + lev_top) - Tdif (Z + lev_bot)), \
+     src_dn = pi ((-Z + lev_bot) - Rdif (Z + lev_bot) - Tdif (-Z + lev_top)), otherwise both 0 (lev_* = lev_source at the layer's upper \
+     and lower level; no layer source is used); surface albedo 1 - sfc_emis and source pi sfc_emis sfc_src; flux_dn at the top = \
+     inc_flux, or 0 when it is NULL; transport by the adding recurrences of rrx_sw_solver_2stream's diffuse part. \
+   (The kernels evaluate the sources in a regrouped form of the same function that does not multiply a rounding error by Z.) \
+   No secants and no weights: the outputs are fluxes. tau, ssa, g (ncol, nlay, ngpt), lev_source (ncol, nlay+1, ngpt); sfc_emis, \
+   sfc_src, inc_flux (ncol, ngpt) as rrx_lw_solver_noscat takes them. do_broadband = 0: flux_up / flux_dn (ncol, nlay+1, ngpt). \
+   do_broadband = 1: flux_up_loc / flux_dn_loc (ncol, nlay+1) = the g-point sums in rrx_sum_broadband's order; flux_up / flux_dn are \
+   then optional per-g-point outputs (both NULL: the stream's workspace holds them). Any nlay, one thread per (column, g-point). \
+   A NULL required pointer or a negative extent: non-zero, rrx_last_error() names the entry and the argument; an extent of 0 \
+   returns 0 and writes nothing. */ \
+int rrx_lw_solver_2stream##SFX( \
+        int ncol, int nlay, int ngpt, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const F* g, const F* lev_source, \
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, \
+        F* flux_up, F* flux_dn, RrxBool do_broadband, F* flux_up_loc, F* flux_dn_loc, void* stream); \
+/* The same solve from Planck-lite inputs with band cloud properties, broadband outputs, in one kernel: tau (ncol, nlay, ngpt) is the \
+   clear gas optical depth, lev_source is formed as rrx_planck_sources_from_fractions forms lev_src from pfrac (ncol, nlay, ngpt) and \
+   blev (ncol, nlay+1, nbnd), and cld_tau / cld_ssa / cld_g (ncol, nlay, nbnd) are combined per g-point of their band with the \
+   arithmetic of rrx_inc_2stream_by_2stream_bybnd on gas (tau, 0, 0): tau' = tau + tau_c, ssa = tau_c ssa_c / max(eps, tau'), \
+   g = tau_c ssa_c g_c / max(eps, tau_c ssa_c) (the one-kernel form takes ssa = 0 where tau_c ssa_c = 0 and g = g_c: where these \
+   differ from the formulas by more than a rounding, tau_c ssa_c is below eps, ssa = 0 and g multiplies nothing). The three cloud arrays are all NULL (pure absorption, ssa = 0: the bits of all-zero \
+   arrays) or all given; a partly-NULL triple is refused. gpoint_bands (ngpt) and band_lims_gpt (2, nbnd) as everywhere, 1-based. \
+   flux_up / flux_dn (ncol, nlay+1): g-point sums in rrx_sum_broadband's order. One-kernel tilings up to 575 layers; taller columns \
+   and LW variants 1 and 7 materialise the combined properties and lev_source in the stream's workspace and take \
+   rrx_lw_solver_2stream. Argument checks and empty problems as there. */ \
+int rrx_lw_solver_2stream_fractions##SFX( \
+        int ncol, int nlay, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* pfrac, const F* blev, const int* gpoint_bands, const int* band_lims_gpt, \
+        const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn, void* stream); \
 /* ---- Optical_props_kernels_cuda : include_kernels_cuda/optical_props_kernels_cuda.h:33-56 ---- */ \
 /* Empty problems, for the entries from here to rrx_fill that say so: an extent of 0 returns 0 and writes nothing (no launch is \
    made, so no launch error is left behind); a negative extent returns non-zero. The _bybnd increments: the g-points of no band \

@@ -103,10 +103,16 @@ class Radiation_solver_longwave
         // set_gauss_angles(> 1) or the by-band solvers in use.
         void set_optimal_angles(const bool b);
         bool get_optimal_angles() const { return optimal_angles; }
+        // LW cloud scattering (default off): solve_gpu takes the clear gas optics, the LW cloud tau / ssa / g by band from
+        // Cloud_optics_gpu (with cloud optics in use; else ssa = 0) and the two-stream solver with scattering
+        // (Rte_lw_gpu::rte_lw_2stream, rrx_lw_solver_2stream_fractions). Broadband solvers only. solve_gpu throws with
+        // set_gauss_angles(> 1), set_optimal_angles, set_jacobian, the by-band solvers, or per-g-point / band flux output.
+        void set_lw_scattering(const bool b) { lw_scattering = b; }
+        bool get_lw_scattering() const { return lw_scattering; }
 
     private:
         int column_sorting = -1, sort_decided = -1;
-        bool column_padding = true, reordered_call = false, jacobian = false, optimal_angles = false;
+        bool column_padding = true, reordered_call = false, jacobian = false, optimal_angles = false, lw_scattering = false;
         int n_gauss_angles = 1;
         Array_gpu<Float,2> lw_flux_up_jac;
         std::unique_ptr<Gas_optics_rrtmgp_gpu> kdist_gpu;

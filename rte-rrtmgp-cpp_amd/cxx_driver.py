@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 class CxxDriver:
     def __init__(self, be, kd_lw0, kd_sw0, atm, cloud_luts0=None, column_block=16384, broadband=True, sort_mode=-1, pad=True,
-                 sunlit=False, jacobian=False, n_gauss_angles=1, optimal_angles=False):
+                 sunlit=False, jacobian=False, n_gauss_angles=1, optimal_angles=False, lw_scattering=False):
         import torch
         self.torch, self.be, self.atm = torch, be, atm
         self.f64 = be.np_dtype == np.float64
@@ -49,6 +49,10 @@ class CxxDriver:
         self.optimal_angles = bool(optimal_angles)
         if self.optimal_angles:
             self._check(self.lib.rrx_cxx_lw_optimal_angles(self.h, 1))
+        # lw_scattering: LW two-stream solve with cloud scattering (set_lw_scattering); the refused pairs fail at the first step
+        self.lw_scattering = bool(lw_scattering)
+        if self.lw_scattering:
+            self._check(self.lib.rrx_cxx_lw_scattering(self.h, 1))
         # jacobian: each step also fills self.lw_flux_up_jac (nlev, ncol), d lw_flux_up / d t_sfc [W m-2 K-1] (set_jacobian)
         self.jacobian = bool(jacobian)
         if self.jacobian:

@@ -393,6 +393,36 @@ class HipKernels:
                 out["bnd_flux_up"], out["bnd_flux_dn"], out.get("bnd_flux_net"), out.get("flux_up"), out.get("flux_dn"))
         return out
 
+    def lw_solver_2stream(self, top_at_1, tau, ssa, g, lev_source, sfc_emis, sfc_src, inc_flux=None, do_broadband=False,
+                          flux_up=None, flux_dn=None):
+        """LW two-stream solver with scattering, general entry (rrx_lw_solver_2stream): tau, ssa, g (ngpt, nlay, ncol), lev_source
+        (ngpt, nlay+1, ncol), sfc_emis / sfc_src / inc_flux (ngpt, ncol). Fluxes per g-point (ngpt, nlev, ncol), or their g-point
+        sums (nlev, ncol) with do_broadband."""
+        ngpt, nlay, ncol = tau.shape
+        shape = (nlay+1, ncol) if do_broadband else (ngpt, nlay+1, ncol)
+        flux_up = self.empty(shape) if flux_up is None else flux_up
+        flux_dn = self.empty(shape) if flux_dn is None else flux_dn
+        gpt = (None, None) if do_broadband else (flux_up, flux_dn)
+        loc = (flux_up, flux_dn) if do_broadband else (None, None)
+        self._c("lw_solver_2stream", ncol, nlay, ngpt, BoolArg(top_at_1), tau, ssa, g, lev_source, sfc_emis, sfc_src, inc_flux,
+                *gpt, BoolArg(do_broadband), *loc)
+        return dict(flux_up=flux_up, flux_dn=flux_dn)
+
+    def lw_solver_2stream_fractions(self, top_at_1, kd, tau, fr, sfc_emis, cloud=None, inc_flux=None, flux_up=None, flux_dn=None,
+                                    band_lims=None, gpoint_bands=None):
+        """The same solve from Planck-lite inputs in one kernel, broadband fluxes (nlev, ncol): tau = clear gas optical depth
+        (ngpt, nlay, ncol), fr = the Planck-lite outputs (pfrac, blev, sfc_src), cloud = None (pure absorption) or (tau, ssa, g) by
+        band, (nbnd, nlay, ncol) each, combined with the gas inside the kernel."""
+        ngpt, nlay, ncol = tau.shape
+        band_lims = kd.band_lims_gpt if band_lims is None else band_lims
+        gpoint_bands = kd.gpoint_bands if gpoint_bands is None else gpoint_bands
+        flux_up = self.empty((nlay+1, ncol)) if flux_up is None else flux_up
+        flux_dn = self.empty((nlay+1, ncol)) if flux_dn is None else flux_dn
+        ct, cw, cg = (None, None, None) if cloud is None else cloud
+        self._c("lw_solver_2stream_fractions", ncol, nlay, ngpt, int(band_lims.shape[0]), BoolArg(top_at_1), tau, fr["pfrac"], fr["blev"],
+                gpoint_bands, band_lims, ct, cw, cg, sfc_emis, fr["sfc_src"], inc_flux, flux_up, flux_dn)
+        return dict(flux_up=flux_up, flux_dn=flux_dn)
+
     def compute_tau_rayleigh(self, kd, it, col_dry, col_gas):
         nlay, ncol = col_dry.shape
         tr = self.empty((kd.ngpt, nlay, ncol))

@@ -293,6 +293,7 @@ struct Radiation_solver_longwave::Workspace
     bool broadband = false, byband = false, jacobian = false;
     std::unique_ptr<Optical_props_arry_gpu> optical_props;
     std::unique_ptr<Optical_props_1scl_gpu> cloud_optical_props;
+    std::unique_ptr<Optical_props_2str_gpu> cloud_optical_props_2str;      // LW scattering: tau / ssa / g by band
     std::unique_ptr<Source_func_lw_gpu> sources;
     Array_gpu<Float,3> gpt_flux_up, gpt_flux_dn;       // (n_col, n_lev, 1 | n_bnd (by-band solvers) | n_gpt)
     Array_gpu<Float,3> gpt_flux_up_jac;                // (n_col, n_lev, 1 | n_gpt) with the Jacobian
@@ -354,6 +355,22 @@ void Radiation_solver_longwave::solve_gpu(
     if (optimal_angles && byband_solvers)
         throw std::runtime_error("Radiation_solver_longwave: optimal angles (set_optimal_angles) are not available with the by-band "
                                  "solvers (set_byband_solvers): the by-band solver has the fixed angle");
+    if (lw_scattering && n_gauss_angles > 1)
+        throw std::runtime_error("Radiation_solver_longwave: LW scattering (set_lw_scattering) is not available with several quadrature "
+                                 "angles (set_gauss_angles): the two-stream solver has no angles");
+    if (lw_scattering && optimal_angles)
+        throw std::runtime_error("Radiation_solver_longwave: LW scattering (set_lw_scattering) is not available with optimal angles "
+                                 "(set_optimal_angles): the two-stream solver has no angles");
+    if (lw_scattering && jacobian)
+        throw std::runtime_error("Radiation_solver_longwave: LW scattering (set_lw_scattering) is not available with the Jacobian "
+                                 "(set_jacobian): no Jacobian form of the two-stream solver");
+    if (lw_scattering && byband_solvers)
+        throw std::runtime_error("Radiation_solver_longwave: LW scattering (set_lw_scattering) is not available with the by-band "
+                                 "solvers (set_byband_solvers): no by-band form of the two-stream solver");
+    if (lw_scattering && switch_fluxes && !broadband)
+        throw std::runtime_error("Radiation_solver_longwave: LW scattering (set_lw_scattering) needs the broadband solvers "
+                                 "(set_broadband_solvers) without band flux output: the two-stream solver gives broadband fluxes");
+    const bool scat = lw_scattering && switch_fluxes;
     if (jac && (lw_flux_up_jac.dim(1) != n_col || lw_flux_up_jac.dim(2) != n_lev))
     {
         lw_flux_up_jac = Array_gpu<Float,2>();
@@ -409,8 +426,10 @@ void Radiation_solver_longwave::solve_gpu(
                 if (!broadband) ws->flux_up_jac.set_dims({n, n_lev});
             }
         }
-        if (switch_cloud_optics && !ws->cloud_optical_props)
+        if (switch_cloud_optics && !scat && !ws->cloud_optical_props)
             ws->cloud_optical_props = std::make_unique<Optical_props_1scl_gpu>(n, n_lay, *cloud_optics_gpu);
+        if (switch_cloud_optics && scat && !ws->cloud_optical_props_2str)
+            ws->cloud_optical_props_2str = std::make_unique<Optical_props_2str_gpu>(n, n_lay, *cloud_optics_gpu);
     };
 
     for (const auto& blk : column_blocks(n_col, std::max(1, n_col_block)))
@@ -439,10 +458,13 @@ void Radiation_solver_longwave::solve_gpu(
 
         // (cloud optics first: its by-band optical depth is added inside gas_optics where tau is stored -- the add_to() of
         //  Radiation_solver.cu:508-511 folded into the producer)
-        if (switch_cloud_optics)
+        // LW scattering: the gas optics stay clear; the band cloud tau / ssa / g (not delta-scaled) go to the two-stream solver
+        if (switch_cloud_optics && scat)
+            cloud_optics_gpu->cloud_optics(sub2(lwp, n_lay), sub2(iwp, n_lay), sub2(rel, n_lay), sub2(dei, n_lay), *ws.cloud_optical_props_2str);
+        else if (switch_cloud_optics)
             cloud_optics_gpu->cloud_optics(sub2(lwp, n_lay), sub2(iwp, n_lay), sub2(rel, n_lay), sub2(dei, n_lay), *ws.cloud_optical_props);
         kdist_gpu->gas_optics(p_lay_s, p_lev_s, t_lay_s, t_sfc_s, gas_concs_subset, ws.optical_props, *ws.sources, col_dry_s, t_lev_s,
-                              switch_cloud_optics ? ws.cloud_optical_props.get() : nullptr);
+                              (switch_cloud_optics && !scat) ? ws.cloud_optical_props.get() : nullptr);
 
         if (switch_output_optical)
         {
@@ -464,7 +486,10 @@ void Radiation_solver_longwave::solve_gpu(
         // the LW solve of this block: fixed Gauss angles, or the optimal-angle secants of the k-distribution's fit (jc: null = no Jacobian)
         auto solve_block = [&](Array_gpu<Float,3>& up, Array_gpu<Float,3>& dn, Array_gpu<Float,3>* jc)
         {
-            if (optimal_angles)
+            if (scat)
+                rte_lw.rte_lw_2stream(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(),
+                                      switch_cloud_optics ? ws.cloud_optical_props_2str.get() : nullptr, up, dn);
+            else if (optimal_angles)
                 rte_lw.rte_lw_optimal(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(),
                                       kdist_gpu->get_optimal_angle_fit_gpu(), up, dn, jc, n_ang);
             else if (jc != nullptr)

@@ -371,6 +371,7 @@ void solve_radiation(int argc, char** argv)
         {"heating-rates"    , { false, "Output layer heating rates lw_heating_rate / sw_heating_rate (K/s)." }},
         {"sunlit-columns"   , { false, "Shortwave on the columns with mu0 > 0 only; every SW output of the others is zero (set_sunlit_columns)." }},
         {"lw-optimal-angles", { false, "Longwave secant per column and g-point from the coefficient file's optimal_angle_fit (one angle); not with --lw-gauss-angles > 1 or --byband-solvers." }},
+        {"lw-scattering"    , { false, "Longwave two-stream solve with cloud scattering (set_lw_scattering): band cloud tau / ssa / g; not with --lw-gauss-angles > 1, --lw-optimal-angles, --lw-jacobian, --byband-solvers or per-g-point solvers." }},
         {"lw-jacobian"      , { false, "Write lw_flux_up_jac, d lw_flux_up / d t_sfc [W m-2 K-1] from the same LW solve (set_jacobian)." }},
         {"async"            , { false, "Host-model mode: vertical ordering read once, solves enqueued without synchronising." }},
         {"sort-columns"     , { true,  "Solve the columns in order of surface pressure where neighbours differ much (outputs keep the input order)." }},
@@ -399,6 +400,18 @@ void solve_radiation(int argc, char** argv)
                                  "optimal angles are one quadrature angle");
     if (switch_lw_optimal_angles && switch_byband_solvers)
         throw std::runtime_error("--lw-optimal-angles is not available with --byband-solvers: the by-band solver has the fixed angle");
+    const bool switch_lw_scattering     = command_line_options.at("lw-scattering").first;
+    if (switch_lw_scattering && lw_gauss_angles > 1)
+        throw std::runtime_error("--lw-scattering is not available with --lw-gauss-angles " + std::to_string(lw_gauss_angles) + ": "
+                                 "the two-stream solver has no quadrature angles");
+    if (switch_lw_scattering && switch_lw_optimal_angles)
+        throw std::runtime_error("--lw-scattering is not available with --lw-optimal-angles: the two-stream solver has no quadrature angles");
+    if (switch_lw_scattering && switch_lw_jacobian)
+        throw std::runtime_error("--lw-scattering is not available with --lw-jacobian: no Jacobian form of the two-stream solver");
+    if (switch_lw_scattering && switch_byband_solvers)
+        throw std::runtime_error("--lw-scattering is not available with --byband-solvers: no by-band form of the two-stream solver");
+    if (switch_lw_scattering && (!switch_broadband || switch_output_bnd_fluxes))
+        throw std::runtime_error("--lw-scattering needs --broadband-solvers without --output-bnd-fluxes: the two-stream solver gives broadband fluxes");
     if (lw_gauss_angles > 1 && switch_byband_solvers)
         throw std::runtime_error("--lw-gauss-angles " + std::to_string(lw_gauss_angles) + " is not available with --byband-solvers: "
                                  "the by-band solver has one quadrature angle");
@@ -524,6 +537,7 @@ void solve_radiation(int argc, char** argv)
         rad_lw.set_byband_solvers(switch_byband_solvers);
         rad_lw.set_jacobian(switch_lw_jacobian);
         rad_lw.set_gauss_angles(lw_gauss_angles);
+        rad_lw.set_lw_scattering(switch_lw_scattering);
         rad_lw.set_optimal_angles(switch_lw_optimal_angles);      // (throws for a coefficient file without optimal_angle_fit)
         // (--no-sort-columns: the file's order and column count exactly; otherwise the solver pads to a multiple of 16 columns and,
         //  with --device-sort-columns, orders them itself)

@@ -193,9 +193,19 @@ class ResidentSolver:
     STAGES = ("lw_gas_optics", "lw_planck", "lw_solver", "lw_reduce", "sw_gas_optics", "sw_solver", "sw_reduce")
 
     def __init__(self, be, kd_lw, kd_sw, atm, do_broadband=False, overlap=False, cloud_luts=None, sort_columns=None, byband=False,
-                 sunlit=False, jacobian=False, n_gauss_angles=1, optimal_angles=False, keep_secants=False):
+                 sunlit=False, jacobian=False, n_gauss_angles=1, optimal_angles=False, keep_secants=False, lw_scattering=False):
         import torch
         self.torch = torch
+        # lw_scattering: the LW chain lets clouds scatter -- clear gas optics, LW cloud tau / ssa / g by band (cloud_optics_2str on the LW
+        # table, not delta-scaled) and the fused two-stream solver (lw_solver_2stream_fractions); without cloud LUTs the same solver with
+        # ssa = 0. One solve without quadrature angles: no by-band form, no Jacobian, no several or optimal angles.
+        self.lw_scattering = bool(lw_scattering)
+        if self.lw_scattering:
+            for flag, name in ((byband, "byband=True"), (jacobian, "jacobian=True"), (int(n_gauss_angles) > 1, "n_gauss_angles > 1"),
+                               (optimal_angles, "optimal_angles=True")):
+                if flag:
+                    raise ValueError(f"ResidentSolver: lw_scattering=True with {name} is not supported (the two-stream LW solver has "
+                                     "one broadband form without quadrature angles)")
         # byband: the step also fills self.bnd_fluxes (lw_up/lw_dn/lw_net/sw_up/sw_dn/sw_dir/sw_net, (nbnd, nlev, ncol) each, the
         # caller's column order) from the fused solvers' by-band form; the seven broadband arrays come from the same solves
         self.byband = bool(byband)
@@ -271,6 +281,8 @@ class ResidentSolver:
             raise ValueError("ResidentSolver(byband=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
         if self.jacobian and not self.lite:
             raise ValueError("ResidentSolver(jacobian=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
+        if self.lw_scattering and not self.lite:
+            raise ValueError("ResidentSolver(lw_scattering=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
         if self.optimal_angles and not self.lite:
             raise ValueError("ResidentSolver(optimal_angles=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
         ncol, nlay = atm.ncol + self.npad, atm.nlay              # columns of a step (padded)
@@ -489,8 +501,10 @@ class ResidentSolver:
             # RRX_FUSE_CLOUDS=0 by the reference's separate increment kernels afterwards
             fuse = self.cloud_luts is not None and self.direct and self.fuse_clouds
             if kind == "lw":
-                tc = None
-                if self.cloud_luts is not None:     # /root/reference/src_test/Radiation_solver.cu:497-512
+                tc = cld_lw = None
+                if self.cloud_luts is not None and self.lw_scattering:      # tau, ssa, g by band: the solver combines them itself
+                    cld_lw = be.cloud_optics_2str(self.cloud_luts[0], atm.lwp, atm.iwp, atm.rel, atm.dei)
+                elif self.cloud_luts is not None:     # /root/reference/src_test/Radiation_solver.cu:497-512
                     tc = be.cloud_optics_1scl(self.cloud_luts[0], atm.lwp, atm.iwp, atm.rel, atm.dei)
                 if self.lite:
                     be.gas_optics_lw_fractions(kd, atm.p_lay, atm.t_lay, atm.t_lev, atm.t_sfc, _sfc_lay(atm), col_gas, buf["tau"], out=buf,
@@ -512,10 +526,13 @@ class ResidentSolver:
                     be.compute_planck_source(kd, it, atm.t_lay, atm.t_lev, atm.t_sfc, _sfc_lay(atm), out=srcs)
                 mark("lw_planck", True)
                 mark("lw_solver")
-                if not self.optimal_angles:         # (the optimal-angle solver forms its secants itself and reads no secants array)
+                if not (self.optimal_angles or self.lw_scattering):      # (neither solver reads a secants array)
                     be._c("lw_secants_array", ncol, kd.ngpt, self.n_gauss_angles, MAX_GAUSS_PTS, self.gauss_Ds, self.secants)
                 be._c("expand_and_transpose", ncol, kd.nbnd, kd.band_lims_gpt, atm.emis_sfc, self.sfc_emis_gpt)
-                if self.optimal_angles:
+                if self.lw_scattering:
+                    be.lw_solver_2stream_fractions(atm.top_at_1, kd, buf["tau"], buf, self.sfc_emis_gpt, cloud=cld_lw,
+                                                   flux_up=F[0], flux_dn=F[1])
+                elif self.optimal_angles:
                     be.lw_solver_noscat_fractions_optimal(atm.top_at_1, kd, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
                                                           fit=self.optimal_fit, flux_up=F[0], flux_dn=F[1], flux_up_jac=J,
                                                           jacobian=self.jacobian, secants_out=self.lw_secants)
