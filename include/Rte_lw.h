@@ -89,6 +89,17 @@ class Rte_lw_gpu
                 const Optical_props_2str_gpu* cloud,
                 Array_gpu<Float,3>& gpt_flux_up,
                 Array_gpu<Float,3>& gpt_flux_dn);
+        // LW no-scattering solve on rescaled optical depths with one correction sweep (rrx_lw_solver_noscat_fractions_rescaled; one
+        // fixed Gauss angle): arguments and requirements as rte_lw_2stream.
+        void rte_lw_rescaled(
+                const std::unique_ptr<Optical_props_arry_gpu>& optical_props,
+                const Bool top_at_1,
+                const Source_func_lw_gpu& sources,
+                const Array_gpu<Float,2>& sfc_emis,
+                const Array_gpu<Float,2>& inc_flux,
+                const Optical_props_2str_gpu* cloud,
+                Array_gpu<Float,3>& gpt_flux_up,
+                Array_gpu<Float,3>& gpt_flux_dn);
         void expand_and_transpose(
                 const std::unique_ptr<Optical_props_arry_gpu>& ops,
                 const Array_gpu<Float,2> arr_in,

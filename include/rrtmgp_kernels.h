@@ -70,7 +70,8 @@ namespace rrtmgp_kernels
 
     /* solvers: :219-279. Served with the semantics of the CPU path: do_broadband honoured (flux_*_loc are (ncol,nlay+1) g-point
        sums, src/Rte_lw.cpp:176), nmus 1..4, a non-zero incident flux kept, mu0 given as (ncol,nlay) (src/Rte_sw.cpp:160-163;
-       it must not vary with height: the device layer keeps the GPU boundary's mu0(ncol)); do_rescaling must be false */
+       it must not vary with height: the device layer keeps the GPU boundary's mu0(ncol)); do_rescaling set: the rescaled solve with
+       one correction sweep on ssa, g (ncol,nlay,ngpt), rrx_lw_solver_noscat_rescaled in rrx_hip.h, with every other option as without it */
     extern "C" void rte_lw_solver_noscat(
             const int& ncol, const int& nlay, const int& ngpt, const Bool& top_at_1, const int& n_quad_angs,
             const Float* secants, const Float* gauss_wts_subset,

@@ -427,6 +427,37 @@ int rrx_lw_solver_2stream_fractions##SFX( \
         const F* tau, const F* pfrac, const F* blev, const int* gpoint_bands, const int* band_lims_gpt, \
         const F* cld_tau, const F* cld_ssa, const F* cld_g, \
         const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn, void* stream); \
+/* lw_solver_noscat_rescaled: the no-scattering solve on a rescaled optical depth with one correction sweep (Tang et al. 2018; \
+   current RTE+RRTMGP's "1rescl" answer to two-stream optical properties in the longwave; do_rescaling of the reference's CPU \
+   boundary). Per g-point, column and angle, layers i and levels in sweep order from the top: \
+     wb = ssa (1 - g)/2, st = 1 - ssa + wb, Cn = 0.4 wb / max(st, 3 tiny), tl = tau D st, tr = exp(-tl), An = 1 - tr tr; \
+     sdn, sup = rrx_lw_solver_noscat's layer sources evaluated with tl, tr; \
+     pass 1 (down) dn[i+1] = tr dn[i] + sdn; surface up[nlay] = dn[nlay] (1 - sfc_emis) + sfc_emis sfc_src (pass 1's dn); \
+     pass 2 (up)   up[i]   = tr up[i+1] + sup + Cn (An dn[i]   - tr sdn - sup)   (pass 1's dn); \
+     pass 3 (down) dn[i+1] = tr dn[i]   + sdn + Cn (An up[i+1] - tr sup - sdn)   (pass 2's up; dn[0] as in pass 1); \
+     Jacobian J[nlay] = sfc_emis sfc_src_jac, J[i] = tr J[i+1]. \
+   Everything else (D = secants, top boundary from inc_flux, scaling by pi weights, the sum over the angles) is \
+   rrx_lw_solver_noscat's; with ssa = 0 the solve is that one. Arguments as rrx_lw_solver_noscat takes them, plus ssa, g (ncol, nlay, \
+   ngpt). nmus 1..4. One thread per (column, g-point), any nlay. With several angles or do_broadband one angle's radiances (and with \
+   do_broadband the per-g-point fluxes; flux_up / flux_dn are not used then) live in the stream's workspace. do_jacobians with \
+   sfc_src_jac and flux_up_jac (ncol, nlay+1, ngpt) given: the per-g-point Jacobian, also with do_broadband. Argument checks and \
+   empty problems as rrx_lw_solver_2stream. */ \
+int rrx_lw_solver_noscat_rescaled##SFX( \
+        int ncol, int nlay, int ngpt, RrxBool top_at_1, int nmus, const F* secants, const F* weights, \
+        const F* tau, const F* ssa, const F* g, const F* lay_source, const F* lev_source, \
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn, \
+        RrxBool do_broadband, F* flux_up_loc, F* flux_dn_loc, RrxBool do_jacobians, const F* sfc_src_jac, F* flux_up_jac, void* stream); \
+/* The same solve for one angle from Planck-lite inputs with band cloud properties, broadband outputs, in one kernel: the inputs of \
+   rrx_lw_solver_noscat_fractions (tau = the clear gas optical depth) plus the band cloud triple of rrx_lw_solver_2stream_fractions, \
+   combined per g-point with the arithmetic and eps stated there (all NULL: ssa = 0, the bits of all-zero arrays; a partly-NULL \
+   triple is refused). flux_up / flux_dn (ncol, nlay+1): g-point sums in rrx_sum_broadband's order. One-kernel tilings up to 575 \
+   layers; taller columns and LW variants 1 and 7 materialise [tau | ssa | g | lay_source | lev_source] in the stream's workspace \
+   (rrx_inc_2stream_by_2stream_bybnd, rrx_planck_sources_from_fractions) and take rrx_lw_solver_noscat_rescaled. */ \
+int rrx_lw_solver_noscat_fractions_rescaled##SFX( \
+        int ncol, int nlay, int ngpt, int nbnd, RrxBool top_at_1, const F* secants, const F* weights, \
+        const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands, const int* band_lims_gpt, \
+        const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn, void* stream); \
 /* ---- Optical_props_kernels_cuda : include_kernels_cuda/optical_props_kernels_cuda.h:33-56 ---- */ \
 /* Empty problems, for the entries from here to rrx_fill that say so: an extent of 0 returns 0 and writes nothing (no launch is \
    made, so no launch error is left behind); a negative extent returns non-zero. The _bybnd increments: the g-points of no band \

@@ -109,10 +109,17 @@ class Radiation_solver_longwave
         // set_gauss_angles(> 1), set_optimal_angles, set_jacobian, the by-band solvers, or per-g-point / band flux output.
         void set_lw_scattering(const bool b) { lw_scattering = b; }
         bool get_lw_scattering() const { return lw_scattering; }
+        // LW rescaled scattering (default off): solve_gpu takes the clear gas optics, the LW cloud tau / ssa / g by band from
+        // Cloud_optics_gpu (with cloud optics in use; else ssa = 0) and the no-scattering solver on rescaled optical depths with one
+        // correction sweep (Rte_lw_gpu::rte_lw_rescaled, rrx_lw_solver_noscat_fractions_rescaled). Broadband solvers only. solve_gpu
+        // throws with set_lw_scattering, set_gauss_angles(> 1), set_optimal_angles, set_jacobian, the by-band solvers, or per-g-point /
+        // band flux output.
+        void set_lw_rescaling(const bool b) { lw_rescaling = b; }
+        bool get_lw_rescaling() const { return lw_rescaling; }
 
     private:
         int column_sorting = -1, sort_decided = -1;
-        bool column_padding = true, reordered_call = false, jacobian = false, optimal_angles = false, lw_scattering = false;
+        bool column_padding = true, reordered_call = false, jacobian = false, optimal_angles = false, lw_scattering = false, lw_rescaling = false;
         int n_gauss_angles = 1;
         Array_gpu<Float,2> lw_flux_up_jac;
         std::unique_ptr<Gas_optics_rrtmgp_gpu> kdist_gpu;

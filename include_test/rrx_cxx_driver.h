@@ -36,6 +36,10 @@ int   rrx_cxx_lw_optimal_angles(void* handle, int on);
 /* set_lw_scattering of the longwave solver (0 = off, the default): clear gas optics, LW cloud tau / ssa / g by band and the
    two-stream solver with scattering; the solve fails with several or optimal angles, the Jacobian or per-g-point solvers */
 int   rrx_cxx_lw_scattering(void* handle, int on);
+/* set_lw_rescaling of the longwave solver (0 = off, the default): clear gas optics, LW cloud tau / ssa / g by band and the
+   no-scattering solve on rescaled optical depths with one correction sweep; the solve fails with LW scattering, several or optimal
+   angles, the Jacobian or per-g-point solvers */
+int   rrx_cxx_lw_rescaling(void* handle, int on);
 int   rrx_cxx_lw_flux_up_jac(void* handle, Real* out, void* stream);
 /* one LW + one SW solve_gpu (fluxes only) enqueued on `stream`; DEVICE arrays: (ncol,nlay) / (ncol,nlay+1) fields, (ncol) vectors,
    surface properties (nbnd,ncol); lwp, iwp, rel, dei NULL without clouds; out7: seven (ncol, nlay+1) arrays for LW up, dn, net and

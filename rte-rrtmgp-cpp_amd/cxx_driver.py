@@ -15,7 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 class CxxDriver:
     def __init__(self, be, kd_lw0, kd_sw0, atm, cloud_luts0=None, column_block=16384, broadband=True, sort_mode=-1, pad=True,
-                 sunlit=False, jacobian=False, n_gauss_angles=1, optimal_angles=False, lw_scattering=False):
+                 sunlit=False, jacobian=False, n_gauss_angles=1, optimal_angles=False, lw_scattering=False,
+                 lw_rescaling=False):
         import torch
         self.torch, self.be, self.atm = torch, be, atm
         self.f64 = be.np_dtype == np.float64
@@ -53,6 +54,11 @@ class CxxDriver:
         self.lw_scattering = bool(lw_scattering)
         if self.lw_scattering:
             self._check(self.lib.rrx_cxx_lw_scattering(self.h, 1))
+        # lw_rescaling: LW no-scattering solve on rescaled optical depths with one correction sweep (set_lw_rescaling); the refused
+        # pairs fail at the first step
+        self.lw_rescaling = bool(lw_rescaling)
+        if self.lw_rescaling:
+            self._check(self.lib.rrx_cxx_lw_rescaling(self.h, 1))
         # jacobian: each step also fills self.lw_flux_up_jac (nlev, ncol), d lw_flux_up / d t_sfc [W m-2 K-1] (set_jacobian)
         self.jacobian = bool(jacobian)
         if self.jacobian:

@@ -423,6 +423,43 @@ class HipKernels:
                 gpoint_bands, band_lims, ct, cw, cg, sfc_emis, fr["sfc_src"], inc_flux, flux_up, flux_dn)
         return dict(flux_up=flux_up, flux_dn=flux_dn)
 
+    def lw_solver_noscat_rescaled(self, top_at_1, secants, weights, tau, ssa, g, lay_source, lev_source, sfc_emis, sfc_src,
+                                  inc_flux=None, do_broadband=False, do_jacobians=False, sfc_src_jac=None):
+        """No-scattering LW solve on rescaled optical depths with one correction sweep, general entry
+        (rrx_lw_solver_noscat_rescaled): the arguments of lw_solver_noscat plus ssa, g (ngpt, nlay, ncol)."""
+        ngpt, nlay, ncol = tau.shape
+        out = {}
+        flux_up = flux_dn = up_loc = dn_loc = jac = None
+        if do_broadband:
+            up_loc = self.empty((nlay+1, ncol)); dn_loc = self.empty((nlay+1, ncol))
+            out.update(flux_up=up_loc, flux_dn=dn_loc)
+        else:
+            flux_up = self.empty((ngpt, nlay+1, ncol)); flux_dn = self.empty((ngpt, nlay+1, ncol))
+            out.update(flux_up=flux_up, flux_dn=flux_dn)
+        if do_jacobians:
+            jac = self.empty((ngpt, nlay+1, ncol))
+            out["flux_up_jac"] = jac
+        self._c("lw_solver_noscat_rescaled", ncol, nlay, ngpt, BoolArg(top_at_1), weights.shape[0], secants, weights,
+                tau, ssa, g, lay_source, lev_source, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn,
+                BoolArg(do_broadband), up_loc, dn_loc, BoolArg(do_jacobians), sfc_src_jac, jac)
+        return out
+
+    def lw_solver_noscat_fractions_rescaled(self, top_at_1, kd, secants, weights, tau, fr, sfc_emis, cloud=None, inc_flux=None,
+                                            flux_up=None, flux_dn=None, band_lims=None, gpoint_bands=None):
+        """The same solve for one angle from Planck-lite inputs in one kernel, broadband fluxes (nlev, ncol): tau = clear gas optical
+        depth (ngpt, nlay, ncol), fr = the Planck-lite outputs (pfrac, blay, blev, sfc_src), cloud = None (ssa = 0) or (tau, ssa, g)
+        by band, (nbnd, nlay, ncol) each, combined with the gas inside the kernel."""
+        ngpt, nlay, ncol = tau.shape
+        band_lims = kd.band_lims_gpt if band_lims is None else band_lims
+        gpoint_bands = kd.gpoint_bands if gpoint_bands is None else gpoint_bands
+        flux_up = self.empty((nlay+1, ncol)) if flux_up is None else flux_up
+        flux_dn = self.empty((nlay+1, ncol)) if flux_dn is None else flux_dn
+        ct, cw, cg = (None, None, None) if cloud is None else cloud
+        self._c("lw_solver_noscat_fractions_rescaled", ncol, nlay, ngpt, int(band_lims.shape[0]), BoolArg(top_at_1), secants, weights,
+                tau, fr["pfrac"], fr["blay"], fr["blev"], gpoint_bands, band_lims, ct, cw, cg, sfc_emis, fr["sfc_src"], inc_flux,
+                flux_up, flux_dn)
+        return dict(flux_up=flux_up, flux_dn=flux_dn)
+
     def compute_tau_rayleigh(self, kd, it, col_dry, col_gas):
         nlay, ncol = col_dry.shape
         tr = self.empty((kd.ngpt, nlay, ncol))

@@ -256,6 +256,40 @@ void Rte_lw_gpu::rte_lw_2stream(
              sfc_emis_gpt.ptr(), sources.get_sfc_source().ptr(), inc_flux_ptr, gpt_flux_up.ptr(), gpt_flux_dn.ptr());
 }
 
+void Rte_lw_gpu::rte_lw_rescaled(
+        const std::unique_ptr<Optical_props_arry_gpu>& optical_props, const Bool top_at_1, const Source_func_lw_gpu& sources,
+        const Array_gpu<Float,2>& sfc_emis, const Array_gpu<Float,2>& inc_flux, const Optical_props_2str_gpu* cloud,
+        Array_gpu<Float,3>& gpt_flux_up, Array_gpu<Float,3>& gpt_flux_dn)
+{
+    if (!sources.holds_fractions()) throw std::runtime_error("rte_lw_rescaled: needs the Planck-lite sources (enable_planck_lite)");
+    if (gpt_flux_up.dim(3) != 1 || gpt_flux_dn.dim(3) != 1) throw std::runtime_error("rte_lw_rescaled: needs broadband flux arrays (third dimension 1)");
+    const int ncol = optical_props->get_ncol();
+    const int nlay = optical_props->get_nlay();
+    const int ngpt = optical_props->get_ngpt();
+    const int nbnd = optical_props->get_nband();
+    if (cloud != nullptr && (cloud->get_ncol() != ncol || cloud->get_nlay() != nlay || cloud->get_tau().dim(3) != nbnd))
+        throw std::runtime_error("rte_lw_rescaled: the cloud optical properties must be (ncol, nlay, nbnd)");
+
+    Array_gpu<Float,2> sfc_emis_gpt({ncol, ngpt});
+    expand_and_transpose(optical_props, sfc_emis, sfc_emis_gpt);
+    if (gauss_angles_cached != 1)
+    {
+        gauss_Ds_gpu = Array_gpu<Float,2>(Array<Float,2>(gauss_Ds_v, {max_gauss_pts, max_gauss_pts}));
+        const Array<Float,2> gauss_wts(gauss_wts_v, {max_gauss_pts, max_gauss_pts});
+        gauss_wts_gpu = Array_gpu<Float,2>(gauss_wts.subset({{ {1, 1}, {1, 1} }}));
+        gauss_angles_cached = 1;
+    }
+    Array_gpu<Float,3> secants({ncol, ngpt, 1});
+    Rte_solver_kernels_cuda::lw_secants_array(ncol, ngpt, 1, max_gauss_pts, gauss_Ds_gpu.ptr(), secants.ptr());
+    const Float* inc_flux_ptr = (inc_flux.size() == 0) ? nullptr : inc_flux.ptr();
+    const Float* none = nullptr;
+    RRX_CALL(rrx_lw_solver_noscat_fractions_rescaled, ncol, nlay, ngpt, nbnd, top_at_1, secants.ptr(), gauss_wts_gpu.ptr(),
+             optical_props->get_tau().ptr(), sources.get_planck_frac().ptr(), sources.get_planck_lay().ptr(), sources.get_planck_lev().ptr(),
+             optical_props->get_gpoint_bands_gpu().ptr(), optical_props->get_band_lims_gpoint_gpu().ptr(),
+             cloud ? cloud->get_tau().ptr() : none, cloud ? cloud->get_ssa().ptr() : none, cloud ? cloud->get_g().ptr() : none,
+             sfc_emis_gpt.ptr(), sources.get_sfc_source().ptr(), inc_flux_ptr, gpt_flux_up.ptr(), gpt_flux_dn.ptr());
+}
+
 void Rte_lw_gpu::expand_and_transpose(const std::unique_ptr<Optical_props_arry_gpu>& ops, const Array_gpu<Float,2> arr_in, Array_gpu<Float,2>& arr_out)
 { expand(ops, arr_in, arr_out); }
 

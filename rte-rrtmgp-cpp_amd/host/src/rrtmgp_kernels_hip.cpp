@@ -279,9 +279,9 @@ void rte_lw_solver_noscat(
         Float* gpt_flux_up, Float* gpt_flux_dn,
         const Bool& do_broadband, Float* flux_up_loc, Float* flux_dn_loc,
         const Bool& do_jacobians, const Float* sfc_source_jac, Float* gpt_flux_up_jac,
-        const Bool& do_rescaling, const Float* /*ssa*/, const Float* /*g*/)
+        const Bool& do_rescaling, const Float* ssa, const Float* g)
 {
-    if (do_rescaling) fail("rte_lw_solver_noscat: do_rescaling is not served (the reference's callers pass false, src/Rte_lw.cpp:186)");
+    if (do_rescaling && (ssa == nullptr || g == nullptr)) fail("rte_lw_solver_noscat: do_rescaling needs ssa and g");
     Stage S;
     const size_t n = sz(ncol, nlay), ng = sz(ncol, ngpt), nlev = sz(ncol, nlay + 1);
     const Float* d_sec = S.in(secants, ng*size_t(n_quad_angs)); const Float* d_wts = S.in(gauss_wts_subset, n_quad_angs);
@@ -301,8 +301,16 @@ void rte_lw_solver_noscat(
         if (do_broadband) { d_jac = S.alloc<Float>(nlev*size_t(ngpt)); d_jac_bb = S.out(gpt_flux_up_jac, nlev); }
         else d_jac = S.out(gpt_flux_up_jac, nlev*size_t(ngpt));
     }
-    RRX_K(rrx_lw_solver_noscat, ncol, nlay, ngpt, top_at_1, n_quad_angs, d_sec, d_wts, d_tau, d_lay, d_lev, d_emis, d_src, d_inc,
-          d_up, d_dn, do_broadband, d_bup, d_bdn, do_jacobians, d_sjac, d_jac);
+    // do_rescaling: the rescaled solve (rrx_lw_solver_noscat_rescaled, the general entry: any n_quad_angs, do_broadband, do_jacobians)
+    if (do_rescaling)
+    {
+        const Float* d_ssa = S.in(ssa, n*size_t(ngpt)); const Float* d_g = S.in(g, n*size_t(ngpt));
+        RRX_K(rrx_lw_solver_noscat_rescaled, ncol, nlay, ngpt, top_at_1, n_quad_angs, d_sec, d_wts, d_tau, d_ssa, d_g, d_lay, d_lev,
+              d_emis, d_src, d_inc, d_up, d_dn, do_broadband, d_bup, d_bdn, do_jacobians, d_sjac, d_jac);
+    }
+    else
+        RRX_K(rrx_lw_solver_noscat, ncol, nlay, ngpt, top_at_1, n_quad_angs, d_sec, d_wts, d_tau, d_lay, d_lev, d_emis, d_src, d_inc,
+              d_up, d_dn, do_broadband, d_bup, d_bdn, do_jacobians, d_sjac, d_jac);
     if (d_jac_bb != nullptr) RRX_K(rrx_sum_broadband, ncol, nlay + 1, ngpt, d_jac, d_jac_bb);
     S.finish();
 }

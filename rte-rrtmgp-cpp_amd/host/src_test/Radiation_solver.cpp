@@ -370,7 +370,26 @@ void Radiation_solver_longwave::solve_gpu(
     if (lw_scattering && switch_fluxes && !broadband)
         throw std::runtime_error("Radiation_solver_longwave: LW scattering (set_lw_scattering) needs the broadband solvers "
                                  "(set_broadband_solvers) without band flux output: the two-stream solver gives broadband fluxes");
-    const bool scat = lw_scattering && switch_fluxes;
+    if (lw_rescaling && lw_scattering)
+        throw std::runtime_error("Radiation_solver_longwave: LW rescaling (set_lw_rescaling) is not available with LW scattering "
+                                 "(set_lw_scattering): one treatment of cloud scattering at a time");
+    if (lw_rescaling && n_gauss_angles > 1)
+        throw std::runtime_error("Radiation_solver_longwave: LW rescaling (set_lw_rescaling) is not available with several quadrature "
+                                 "angles (set_gauss_angles): the fused rescaled solver has one angle");
+    if (lw_rescaling && optimal_angles)
+        throw std::runtime_error("Radiation_solver_longwave: LW rescaling (set_lw_rescaling) is not available with optimal angles "
+                                 "(set_optimal_angles): the fused rescaled solver has the fixed angle");
+    if (lw_rescaling && jacobian)
+        throw std::runtime_error("Radiation_solver_longwave: LW rescaling (set_lw_rescaling) is not available with the Jacobian "
+                                 "(set_jacobian): no Jacobian form of the fused rescaled solver");
+    if (lw_rescaling && byband_solvers)
+        throw std::runtime_error("Radiation_solver_longwave: LW rescaling (set_lw_rescaling) is not available with the by-band "
+                                 "solvers (set_byband_solvers): no by-band form of the rescaled solver");
+    if (lw_rescaling && switch_fluxes && !broadband)
+        throw std::runtime_error("Radiation_solver_longwave: LW rescaling (set_lw_rescaling) needs the broadband solvers "
+                                 "(set_broadband_solvers) without band flux output: the fused rescaled solver gives broadband fluxes");
+    const bool resc = lw_rescaling && switch_fluxes;
+    const bool scat = (lw_scattering || lw_rescaling) && switch_fluxes;      // the cloud goes to the solver as tau / ssa / g by band
     if (jac && (lw_flux_up_jac.dim(1) != n_col || lw_flux_up_jac.dim(2) != n_lev))
     {
         lw_flux_up_jac = Array_gpu<Float,2>();
@@ -486,7 +505,10 @@ void Radiation_solver_longwave::solve_gpu(
         // the LW solve of this block: fixed Gauss angles, or the optimal-angle secants of the k-distribution's fit (jc: null = no Jacobian)
         auto solve_block = [&](Array_gpu<Float,3>& up, Array_gpu<Float,3>& dn, Array_gpu<Float,3>* jc)
         {
-            if (scat)
+            if (resc)
+                rte_lw.rte_lw_rescaled(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(),
+                                       switch_cloud_optics ? ws.cloud_optical_props_2str.get() : nullptr, up, dn);
+            else if (scat)
                 rte_lw.rte_lw_2stream(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(),
                                       switch_cloud_optics ? ws.cloud_optical_props_2str.get() : nullptr, up, dn);
             else if (optimal_angles)

@@ -93,6 +93,11 @@ int rrx_cxx_lw_scattering(void* h, const int on)
     return guarded([&] { static_cast<Driver*>(h)->lw->set_lw_scattering(on != 0); });
 }
 
+int rrx_cxx_lw_rescaling(void* h, const int on)
+{
+    return guarded([&] { static_cast<Driver*>(h)->lw->set_lw_rescaling(on != 0); });
+}
+
 int rrx_cxx_lw_optimal_angles(void* h, const int on)
 {
     return guarded([&] { static_cast<Driver*>(h)->lw->set_optimal_angles(on != 0); });

@@ -372,6 +372,7 @@ void solve_radiation(int argc, char** argv)
         {"sunlit-columns"   , { false, "Shortwave on the columns with mu0 > 0 only; every SW output of the others is zero (set_sunlit_columns)." }},
         {"lw-optimal-angles", { false, "Longwave secant per column and g-point from the coefficient file's optimal_angle_fit (one angle); not with --lw-gauss-angles > 1 or --byband-solvers." }},
         {"lw-scattering"    , { false, "Longwave two-stream solve with cloud scattering (set_lw_scattering): band cloud tau / ssa / g; not with --lw-gauss-angles > 1, --lw-optimal-angles, --lw-jacobian, --byband-solvers or per-g-point solvers." }},
+        {"lw-rescaling"     , { false, "Longwave no-scattering solve on rescaled optical depths with one correction sweep (set_lw_rescaling): band cloud tau / ssa / g; not with --lw-scattering, --lw-gauss-angles > 1, --lw-optimal-angles, --lw-jacobian, --byband-solvers or per-g-point solvers." }},
         {"lw-jacobian"      , { false, "Write lw_flux_up_jac, d lw_flux_up / d t_sfc [W m-2 K-1] from the same LW solve (set_jacobian)." }},
         {"async"            , { false, "Host-model mode: vertical ordering read once, solves enqueued without synchronising." }},
         {"sort-columns"     , { true,  "Solve the columns in order of surface pressure where neighbours differ much (outputs keep the input order)." }},
@@ -412,6 +413,20 @@ void solve_radiation(int argc, char** argv)
         throw std::runtime_error("--lw-scattering is not available with --byband-solvers: no by-band form of the two-stream solver");
     if (switch_lw_scattering && (!switch_broadband || switch_output_bnd_fluxes))
         throw std::runtime_error("--lw-scattering needs --broadband-solvers without --output-bnd-fluxes: the two-stream solver gives broadband fluxes");
+    const bool switch_lw_rescaling      = command_line_options.at("lw-rescaling").first;
+    if (switch_lw_rescaling && switch_lw_scattering)
+        throw std::runtime_error("--lw-rescaling is not available with --lw-scattering: one treatment of cloud scattering at a time");
+    if (switch_lw_rescaling && lw_gauss_angles > 1)
+        throw std::runtime_error("--lw-rescaling is not available with --lw-gauss-angles " + std::to_string(lw_gauss_angles) + ": "
+                                 "the fused rescaled solver has one angle");
+    if (switch_lw_rescaling && switch_lw_optimal_angles)
+        throw std::runtime_error("--lw-rescaling is not available with --lw-optimal-angles: the fused rescaled solver has the fixed angle");
+    if (switch_lw_rescaling && switch_lw_jacobian)
+        throw std::runtime_error("--lw-rescaling is not available with --lw-jacobian: no Jacobian form of the fused rescaled solver");
+    if (switch_lw_rescaling && switch_byband_solvers)
+        throw std::runtime_error("--lw-rescaling is not available with --byband-solvers: no by-band form of the rescaled solver");
+    if (switch_lw_rescaling && (!switch_broadband || switch_output_bnd_fluxes))
+        throw std::runtime_error("--lw-rescaling needs --broadband-solvers without --output-bnd-fluxes: the fused rescaled solver gives broadband fluxes");
     if (lw_gauss_angles > 1 && switch_byband_solvers)
         throw std::runtime_error("--lw-gauss-angles " + std::to_string(lw_gauss_angles) + " is not available with --byband-solvers: "
                                  "the by-band solver has one quadrature angle");
@@ -538,6 +553,7 @@ void solve_radiation(int argc, char** argv)
         rad_lw.set_jacobian(switch_lw_jacobian);
         rad_lw.set_gauss_angles(lw_gauss_angles);
         rad_lw.set_lw_scattering(switch_lw_scattering);
+        rad_lw.set_lw_rescaling(switch_lw_rescaling);
         rad_lw.set_optimal_angles(switch_lw_optimal_angles);      // (throws for a coefficient file without optimal_angle_fit)
         // (--no-sort-columns: the file's order and column count exactly; otherwise the solver pads to a multiple of 16 columns and,
         //  with --device-sort-columns, orders them itself)

@@ -193,9 +193,21 @@ class ResidentSolver:
     STAGES = ("lw_gas_optics", "lw_planck", "lw_solver", "lw_reduce", "sw_gas_optics", "sw_solver", "sw_reduce")
 
     def __init__(self, be, kd_lw, kd_sw, atm, do_broadband=False, overlap=False, cloud_luts=None, sort_columns=None, byband=False,
-                 sunlit=False, jacobian=False, n_gauss_angles=1, optimal_angles=False, keep_secants=False, lw_scattering=False):
+                 sunlit=False, jacobian=False, n_gauss_angles=1, optimal_angles=False, keep_secants=False, lw_scattering=False,
+                 lw_rescaling=False):
         import torch
         self.torch = torch
+        # lw_rescaling: the LW chain treats cloud scattering by rescaling -- clear gas optics, LW cloud tau / ssa / g by band
+        # (cloud_optics_2str on the LW table, not delta-scaled) and the fused no-scattering solve on rescaled optical depths with one
+        # correction sweep (lw_solver_noscat_fractions_rescaled); without cloud LUTs the same solver with ssa = 0. One angle, broadband:
+        # no by-band form, no Jacobian, no several or optimal angles, and not together with lw_scattering.
+        self.lw_rescaling = bool(lw_rescaling)
+        if self.lw_rescaling:
+            for flag, name in ((lw_scattering, "lw_scattering=True"), (byband, "byband=True"), (jacobian, "jacobian=True"),
+                               (int(n_gauss_angles) > 1, "n_gauss_angles > 1"), (optimal_angles, "optimal_angles=True")):
+                if flag:
+                    raise ValueError(f"ResidentSolver: lw_rescaling=True with {name} is not supported (the rescaled LW solver has "
+                                     "one broadband form with one fixed angle)")
         # lw_scattering: the LW chain lets clouds scatter -- clear gas optics, LW cloud tau / ssa / g by band (cloud_optics_2str on the LW
         # table, not delta-scaled) and the fused two-stream solver (lw_solver_2stream_fractions); without cloud LUTs the same solver with
         # ssa = 0. One solve without quadrature angles: no by-band form, no Jacobian, no several or optimal angles.
@@ -281,6 +293,8 @@ class ResidentSolver:
             raise ValueError("ResidentSolver(byband=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
         if self.jacobian and not self.lite:
             raise ValueError("ResidentSolver(jacobian=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
+        if self.lw_rescaling and not self.lite:
+            raise ValueError("ResidentSolver(lw_rescaling=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
         if self.lw_scattering and not self.lite:
             raise ValueError("ResidentSolver(lw_scattering=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
         if self.optimal_angles and not self.lite:
@@ -502,7 +516,7 @@ class ResidentSolver:
             fuse = self.cloud_luts is not None and self.direct and self.fuse_clouds
             if kind == "lw":
                 tc = cld_lw = None
-                if self.cloud_luts is not None and self.lw_scattering:      # tau, ssa, g by band: the solver combines them itself
+                if self.cloud_luts is not None and (self.lw_scattering or self.lw_rescaling):      # tau, ssa, g by band: the solver combines them itself
                     cld_lw = be.cloud_optics_2str(self.cloud_luts[0], atm.lwp, atm.iwp, atm.rel, atm.dei)
                 elif self.cloud_luts is not None:     # /root/reference/src_test/Radiation_solver.cu:497-512
                     tc = be.cloud_optics_1scl(self.cloud_luts[0], atm.lwp, atm.iwp, atm.rel, atm.dei)
@@ -529,7 +543,10 @@ class ResidentSolver:
                 if not (self.optimal_angles or self.lw_scattering):      # (neither solver reads a secants array)
                     be._c("lw_secants_array", ncol, kd.ngpt, self.n_gauss_angles, MAX_GAUSS_PTS, self.gauss_Ds, self.secants)
                 be._c("expand_and_transpose", ncol, kd.nbnd, kd.band_lims_gpt, atm.emis_sfc, self.sfc_emis_gpt)
-                if self.lw_scattering:
+                if self.lw_rescaling:
+                    be.lw_solver_noscat_fractions_rescaled(atm.top_at_1, kd, self.secants, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
+                                                           cloud=cld_lw, flux_up=F[0], flux_dn=F[1])
+                elif self.lw_scattering:
                     be.lw_solver_2stream_fractions(atm.top_at_1, kd, buf["tau"], buf, self.sfc_emis_gpt, cloud=cld_lw,
                                                    flux_up=F[0], flux_dn=F[1])
                 elif self.optimal_angles:
