@@ -63,6 +63,9 @@ int rrx_release_workspace(void* stream);
 /* perm[i] = min(i, ncol-1), i < ncol + npad: the identity order, padded (see rrx_sort_columns). ncol <= 0 or npad < 0: non-zero,
    "empty problem" */
 int rrx_identity_columns(int ncol, int npad, int* perm, void* stream);
+/* McICA cloud sampling (rrx_mcica_*): the identities of columns taken through a gather index, col_id[i] = perm[i] + offset, i < n
+   (device ints). n = 0: returns 0, writes nothing; n < 0 or a NULL: non-zero. */
+int rrx_mcica_column_ids(int n, const int* perm, int offset, int* col_id, void* stream);
 unsigned long long rrx_workspace_bytes(void* stream);
 /* include/Array.h:311-350,579-622 (Array_gpu::subset / subset_kernel): N-D block gather, singleton dimensions are
    broadcast. sub_dims/strides/starts/spread are HOST arrays of length ndim (1..7); strides in elements, starts 0-based; elem_bytes
@@ -559,7 +562,31 @@ int rrx_gather_lastdim##SFX(int n1, int nout, const int* perm, const F* in, F* o
    scatter_cols_fill: out(:, r) = 0 for all ncol_dst columns, then out(perm[i], r) = in(i, r) for i < n (n = 0: zeros only); \
    serves every column-first layout: (col, n2), (col, nlev, nbnd), packed (k, nlev, col) with nrest = the product of the rest. */ \
 int rrx_sunlit_columns##SFX(int ncol, const F* mu0, const int* order, int pad_to, int* perm, int* count, void* stream); \
-int rrx_scatter_cols_fill##SFX(int n, unsigned long long nrest, const int* perm, int ncol_src, const F* in, int ncol_dst, F* out, void* stream);
+int rrx_scatter_cols_fill##SFX(int n, unsigned long long nrest, const int* perm, int ncol_src, const F* in, int ncol_dst, F* out, void* stream); \
+/* ---- McICA cloud sampling (csrc/rrx_mcica.hip; no counterpart in the reference library): every g-point of a \
+   column sees one sub-column, cloudy or clear per layer, drawn from cloud_frac(ncol,nlay) under an overlap rule, and the band cloud \
+   properties cld_*(ncol,nlay,nbnd) are combined into the g-point arrays (ncol,nlay,ngpt) IN PLACE in the cloudy cells only, with the \
+   arithmetic of rrx_increment_1scalar_by_1scalar / rrx_increment_2stream_by_2stream. Clear cells are not written; the layers with \
+   cloud_frac <= 0 are not read either. Run the clear gas optics (with the g array written in SW), then this. \
+   Random numbers: Philox4x32-10, key = (low, high) 32 bits of seed, counter = (column identity, igpt, ilay/4, 2*domain + which), \
+   the cell's word is output word ilay%4; which = 0 is the rank draw u, 1 the overlap draw v; all indices are 0-based array indices \
+   (ilay the array's layer index whatever the vertical ordering); domain is the caller's (the drivers: 0 = LW, 1 = SW). The column \
+   identity is col_id[icol] (ncol ints on the device), or col_id0 + icol with col_id = NULL: pass the columns' global indices and \
+   a column draws the same sub-columns in any launch, order or split. uniform = ((x >> 9) + 0.5) * 2^-23, the same value in both \
+   precisions. Walk ilay = 0 .. nlay-1 in array order with a rank: rank = u at ilay = 0 and below a layer with cloud_frac <= 0; \
+   else the rank from above is kept when v < alpha(icol, ilay-1) and redrawn (rank = u) otherwise. alpha(ncol,nlay-1) in [0, 1] is the \
+   overlap parameter between array layers l and l+1 (exponential-random overlap, Raisanen et al. 2004, two-draw form); alpha = NULL \
+   means 1 everywhere: maximum-random overlap. The cell is cloudy iff cloud_frac > 0 and rank > 1 - cloud_frac. \
+   mask_out (unsigned char (ncol,nlay,ngpt)) may be NULL; given, it is written in full (0 or 1, clear layers included). The g-points \
+   of no band (outside every [lo, hi], or of a band with hi < lo) are sampled but left as they are. ncol, nlay, ngpt or (the \
+   increments) nbnd = 0: returns 0 without a launch; a negative extent or a NULL that is needed: non-zero, before any HIP call. */ \
+int rrx_mcica_increment_1scalar##SFX(int ncol, int nlay, int ngpt, int nbnd, const int* band_lims_gpt, const F* cloud_frac, const F* alpha, \
+        unsigned long long seed, int domain, const int* col_id, int col_id0, F* tau_inout, const F* cld_tau, unsigned char* mask_out, void* stream); \
+int rrx_mcica_increment_2stream##SFX(int ncol, int nlay, int ngpt, int nbnd, const int* band_lims_gpt, const F* cloud_frac, const F* alpha, \
+        unsigned long long seed, int domain, const int* col_id, int col_id0, F* tau_inout, F* ssa_inout, F* g_inout, \
+        const F* cld_tau, const F* cld_ssa, const F* cld_g, unsigned char* mask_out, void* stream); \
+int rrx_mcica_cloud_mask##SFX(int ncol, int nlay, int ngpt, const F* cloud_frac, const F* alpha, unsigned long long seed, int domain, \
+        const int* col_id, int col_id0, unsigned char* mask_out, void* stream);
 
 RRX_DECLARE(double, _f64)
 RRX_DECLARE(float, _f32)

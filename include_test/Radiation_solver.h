@@ -13,6 +13,7 @@
  */
 #ifndef RADIATION_SOLVER_H
 #define RADIATION_SOLVER_H
+#include <cstdint>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -116,8 +117,24 @@ class Radiation_solver_longwave
         // band flux output.
         void set_lw_rescaling(const bool b) { lw_rescaling = b; }
         bool get_lw_rescaling() const { return lw_rescaling; }
+        // McICA cloud sampling (default off): with cloud optics in use, solve_gpu runs the CLEAR gas optics and then
+        // rrx_mcica_increment_1scalar, which gives every g-point its own sub-column drawn from cloud_frac (ncol, nlay) and adds the band
+        // cloud optical depth in the cloudy cells only. overlap: 0 = maximum-random (overlap_param unused, may be nullptr), 1 =
+        // exponential-random with overlap_param (ncol, nlay-1), the overlap parameter between array layers l and l+1. The arrays are
+        // BORROWED: they stay the caller's, are read at every solve (update them in place) and must outlive the solves; nullptr as
+        // cloud_frac turns the sampling off. The mask is redrawn at every solve from `seed` (call again to advance it; domain 0). A
+        // column's draws are keyed by col_offset + its index in the caller's arrays and follow it through the column blocks, the
+        // device sort and the padding. solve_gpu throws without cloud optics, with set_lw_scattering or with set_lw_rescaling (those
+        // solvers combine the band clouds themselves).
+        void set_cloud_sampling(const Array_gpu<Float,2>* cloud_frac, const int overlap, const Array_gpu<Float,2>* overlap_param,
+                                const uint64_t seed, const int col_offset = 0);
 
     private:
+        const Array_gpu<Float,2>* mcica_frac = nullptr;
+        const Array_gpu<Float,2>* mcica_alpha = nullptr;
+        uint64_t mcica_seed = 0;
+        int mcica_col_offset = 0;
+        const int* mcica_col_id = nullptr;       // (a reordered solve: the identities of its columns, on the device)
         int column_sorting = -1, sort_decided = -1;
         bool column_padding = true, reordered_call = false, jacobian = false, optimal_angles = false, lw_scattering = false, lw_rescaling = false;
         int n_gauss_angles = 1;
@@ -190,8 +207,24 @@ class Radiation_solver_shortwave
         // to every SW flux (broadband and band) of the other columns. mu0 <= 0 and NaN count as night. Reading the count back
         // synchronises the stream once per solve in this mode. Off, the solve still requires mu0 > 0 in every column.
         void set_sunlit_columns(const bool b);
+        // McICA cloud sampling (default off): with cloud optics in use, solve_gpu runs the CLEAR gas optics and then
+        // rrx_mcica_increment_2stream, which gives every g-point its own sub-column drawn from cloud_frac (ncol, nlay) and combines the band
+        // cloud tau / ssa / g into the cloudy cells only. overlap: 0 = maximum-random (overlap_param unused, may be nullptr), 1 =
+        // exponential-random with overlap_param (ncol, nlay-1), the overlap parameter between array layers l and l+1. The arrays are
+        // BORROWED: they stay the caller's, are read at every solve (update them in place) and must outlive the solves; nullptr as
+        // cloud_frac turns the sampling off. The mask is redrawn at every solve from `seed` (call again to advance it; domain 1). A
+        // column's draws are keyed by col_offset + its index in the caller's arrays and follow it through the column blocks, the
+        // device sort and the padding. solve_gpu throws without cloud optics, or with set_sunlit_columns (the sunlit-only solve
+        // does not carry the column identities).
+        void set_cloud_sampling(const Array_gpu<Float,2>* cloud_frac, const int overlap, const Array_gpu<Float,2>* overlap_param,
+                                const uint64_t seed, const int col_offset = 0);
 
     private:
+        const Array_gpu<Float,2>* mcica_frac = nullptr;
+        const Array_gpu<Float,2>* mcica_alpha = nullptr;
+        uint64_t mcica_seed = 0;
+        int mcica_col_offset = 0;
+        const int* mcica_col_id = nullptr;       // (a reordered solve: the identities of its columns, on the device)
         int column_sorting = -1, sort_decided = -1;
         bool column_padding = true, reordered_call = false, sunlit_columns = false;
         std::unique_ptr<Gas_optics_rrtmgp_gpu> kdist_gpu;

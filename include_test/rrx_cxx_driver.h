@@ -41,6 +41,12 @@ int   rrx_cxx_lw_scattering(void* handle, int on);
    angles, the Jacobian or per-g-point solvers */
 int   rrx_cxx_lw_rescaling(void* handle, int on);
 int   rrx_cxx_lw_flux_up_jac(void* handle, Real* out, void* stream);
+/* set_cloud_sampling of both solvers (McICA): cloud_frac DEVICE (ncol, nlay), or NULL = off; overlap 0 = maximum-random, 1 =
+   exponential-random with overlap_param DEVICE (ncol, nlay-1); the arrays are borrowed (read at every solve, they must outlive the
+   solves); seed: the mask of the next solves (call again to advance it); col_offset: the global index of the first column. Needs
+   clouds; the solve fails with LW scattering, LW rescaling or sunlit columns */
+int   rrx_cxx_cloud_sampling(void* handle, const Real* cloud_frac, int ncol, int nlay, int overlap, const Real* overlap_param,
+        unsigned long long seed, int col_offset);
 /* one LW + one SW solve_gpu (fluxes only) enqueued on `stream`; DEVICE arrays: (ncol,nlay) / (ncol,nlay+1) fields, (ncol) vectors,
    surface properties (nbnd,ncol); lwp, iwp, rel, dei NULL without clouds; out7: seven (ncol, nlay+1) arrays for LW up, dn, net and
    SW up, dn, dn_dir, net, or NULL (the driver then keeps them: rrx_cxx_driver_fluxes) */

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 class CxxDriver:
     def __init__(self, be, kd_lw0, kd_sw0, atm, cloud_luts0=None, column_block=16384, broadband=True, sort_mode=-1, pad=True,
                  sunlit=False, jacobian=False, n_gauss_angles=1, optimal_angles=False, lw_scattering=False,
-                 lw_rescaling=False):
+                 lw_rescaling=False, cloud_fraction=None, cloud_overlap="max_ran", overlap_param=None, mcica_seed=0, mcica_col_offset=0):
         import torch
         self.torch, self.be, self.atm = torch, be, atm
         self.f64 = be.np_dtype == np.float64
@@ -63,6 +63,14 @@ class CxxDriver:
         self.jacobian = bool(jacobian)
         if self.jacobian:
             self._check(self.lib.rrx_cxx_lw_jacobian(self.h, 1))
+        # cloud_fraction: McICA cloud sampling (set_cloud_sampling of both solvers), as pipeline.ResidentSolver takes it; the tensors
+        # are borrowed by the solvers, set self.mcica_seed to advance the mask between steps
+        self.cloud_fraction, self.overlap_param, self.cloud_overlap = cloud_fraction, overlap_param, cloud_overlap
+        self.mcica_seed, self.mcica_col_offset = int(mcica_seed), int(mcica_col_offset)
+        if cloud_fraction is not None:
+            if cloud_overlap not in ("max_ran", "exp_ran"):
+                raise ValueError(f"CxxDriver: cloud_overlap = {cloud_overlap!r} is not 'max_ran' or 'exp_ran'")
+            self._set_cloud_sampling()
         for n, t in atm.vmr.items():                # (nlay, ncol) tensors = (ncol, nlay) arrays; profiles (nlay,) = (1, nlay)
             n1, n2 = (t.shape[1], t.shape[0]) if t.dim() == 2 else ((1, t.shape[0]) if t.dim() == 1 else (1, 1))
             self._check(self.lib.rrx_cxx_driver_set_gas(self.h, n.encode(), ctypes.c_void_p(t.data_ptr()), n1, n2))
@@ -75,8 +83,18 @@ class CxxDriver:
         if rc != 0:
             raise RuntimeError("cxx driver: " + self.lib.rrx_cxx_driver_error().decode())
 
+    def _set_cloud_sampling(self):
+        f, al = self.cloud_fraction, self.overlap_param
+        self._check(self.lib.rrx_cxx_cloud_sampling(
+            self.h, ctypes.c_void_p(f.data_ptr()), int(f.shape[1]), int(f.shape[0]), 1 if self.cloud_overlap == "exp_ran" else 0,
+            ctypes.c_void_p(al.data_ptr() if al is not None else 0), ctypes.c_ulonglong(self.mcica_seed & 0xFFFFFFFFFFFFFFFF),
+            self.mcica_col_offset))
+        self._seed_set = self.mcica_seed
+
     def step(self):
         a = self.atm
+        if self.cloud_fraction is not None and self._seed_set != self.mcica_seed:
+            self._set_cloud_sampling()
         p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
         st = ctypes.c_void_p(self.torch.cuda.current_stream(self.be.device).cuda_stream)
         cl = (a.lwp, a.iwp, a.rel, a.dei) if self.clouds else (None, None, None, None)

@@ -525,6 +525,42 @@ class HipKernels:
         ngpt, nlay, ncol = t1.shape
         self._c("inc_2stream_by_2stream_bybnd", ncol, nlay, ngpt, t1, w1, g1, t2, w2, g2, band_lims.shape[0], band_lims)
 
+    # McICA cloud sampling (rrx_mcica_*): cloud_frac (nlay, ncol), alpha None (maximum-random) or (nlay-1, ncol) (exponential-random),
+    # col_id None (identity = col_id0 + column) or an int32 tensor (ncol,) of global column indices; mask: None, True (allocated)
+    # or a uint8 tensor (ngpt, nlay, ncol). The g-point arrays are updated in place in the cloudy cells only; returns the mask or None.
+    def _mcica_args(self, cloud_frac, alpha, seed, domain, col_id, col_id0, ngpt, mask):
+        nlay, ncol = cloud_frac.shape
+        if alpha is not None and tuple(alpha.shape) != (max(nlay-1, 0), ncol):
+            raise ValueError(f"mcica: alpha {tuple(alpha.shape)} is not (nlay-1, ncol) = {(nlay-1, ncol)}")
+        if col_id is not None and (col_id.dtype != torch.int32 or col_id.numel() != ncol):
+            raise TypeError("mcica: col_id is an int32 tensor of ncol entries")
+        if mask is True:
+            mask = torch.empty((ngpt, nlay, ncol), dtype=torch.uint8, device=self.device)
+        elif mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (ngpt, nlay, ncol)):
+            raise TypeError("mcica: mask is a uint8 tensor (ngpt, nlay, ncol)")
+        head = (cloud_frac, alpha, ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), int(domain), col_id, int(col_id0))
+        return head, mask
+
+    def mcica_increment_1scalar(self, tau, cld_tau, band_lims, cloud_frac, alpha=None, seed=0, domain=0, col_id=None, col_id0=0, mask=None):
+        ngpt, nlay, ncol = tau.shape
+        head, mask = self._mcica_args(cloud_frac, alpha, seed, domain, col_id, col_id0, ngpt, mask)
+        self._c("mcica_increment_1scalar", ncol, nlay, ngpt, int(band_lims.shape[0]), band_lims, *head, tau, cld_tau, mask)
+        return mask
+
+    def mcica_increment_2stream(self, tau, ssa, g, cld_tau, cld_ssa, cld_g, band_lims, cloud_frac, alpha=None, seed=0, domain=0,
+                                col_id=None, col_id0=0, mask=None):
+        ngpt, nlay, ncol = tau.shape
+        head, mask = self._mcica_args(cloud_frac, alpha, seed, domain, col_id, col_id0, ngpt, mask)
+        self._c("mcica_increment_2stream", ncol, nlay, ngpt, int(band_lims.shape[0]), band_lims, *head, tau, ssa, g,
+                cld_tau, cld_ssa, cld_g, mask)
+        return mask
+
+    def mcica_cloud_mask(self, ngpt, cloud_frac, alpha=None, seed=0, domain=0, col_id=None, col_id0=0, mask=True):
+        nlay, ncol = cloud_frac.shape
+        head, mask = self._mcica_args(cloud_frac, alpha, seed, domain, col_id, col_id0, ngpt, mask)
+        self._c("mcica_cloud_mask", ncol, nlay, int(ngpt), *head, mask)
+        return mask
+
     def delta_scale_2str_k(self, tau, ssa, g):
         ngpt, nlay, ncol = tau.shape
         self._c("delta_scale_2str_k", ncol, nlay, ngpt, tau, ssa, g)

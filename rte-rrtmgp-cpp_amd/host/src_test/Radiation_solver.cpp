@@ -247,6 +247,36 @@ namespace
         return day;
     }
 
+    // McICA cloud sampling of a reordered solve (set_cloud_sampling): the solver's borrowed fields are replaced by their gathered
+    // copies and the columns' identities (perm + offset) for the duration of the inner solve, and put back afterwards.
+    struct Sampling_reordered
+    {
+        const Array_gpu<Float,2>*& frac; const Array_gpu<Float,2>*& alpha; const int*& col_id;
+        const Array_gpu<Float,2>* frac0; const Array_gpu<Float,2>* alpha0; const int* col_id0;
+        Array_gpu<Float,2> frac_r, alpha_r; Array_gpu<int,1> ids;
+        Sampling_reordered(const Array_gpu<Float,2>*& f, const Array_gpu<Float,2>*& a, const int*& id, const int offset, const Column_order& co) :
+            frac(f), alpha(a), col_id(id), frac0(f), alpha0(a), col_id0(id)
+        {
+            if (frac0 == nullptr) return;
+            frac_r = co.in2(*frac0); frac = &frac_r;
+            if (alpha0 != nullptr) { alpha_r = co.in2(*alpha0); alpha = &alpha_r; }
+            ids.set_dims({co.n_out});
+            rrx_host::check(rrx_mcica_column_ids(co.n_out, co.perm.ptr(), offset, ids.ptr(), rrx_host::current_stream()));
+            col_id = ids.ptr();
+        }
+        ~Sampling_reordered() { frac = frac0; alpha = alpha0; col_id = col_id0; }
+    };
+
+    void check_cloud_sampling(const char* who, const Array_gpu<Float,2>* frac, const Array_gpu<Float,2>* alpha, const int n_col, const int n_lay,
+                              const bool cloud_optics)
+    {
+        const std::string w(who);
+        if (!cloud_optics) throw std::runtime_error(w + ": cloud sampling (set_cloud_sampling) needs cloud optics: it samples their band properties");
+        if (frac->dim(1) != n_col || frac->dim(2) != n_lay) throw std::runtime_error(w + ": set_cloud_sampling: cloud_frac is not (ncol, nlay)");
+        if (alpha != nullptr && n_lay > 1 && (alpha->dim(1) != n_col || alpha->dim(2) != n_lay-1))
+            throw std::runtime_error(w + ": set_cloud_sampling: overlap_param is not (ncol, nlay-1)");
+    }
+
     // Should this solve reorder its columns, and how? `sort_decided` caches the automatic decision of the solver object.
     Column_order column_order(const int mode, int& sort_decided, const bool pad, const Array_gpu<Float,2>& p_lev, const Bool top_at_1)
     {
@@ -306,6 +336,17 @@ Radiation_solver_longwave::Radiation_solver_longwave(
     this->kdist_gpu = std::make_unique<Gas_optics_rrtmgp_gpu>(load_and_init_gas_optics(gas_concs, file_name_gas));
     if (!file_name_cloud.empty())
         this->cloud_optics_gpu = std::make_unique<Cloud_optics_gpu>(load_and_init_cloud_optics(file_name_cloud));
+}
+
+void Radiation_solver_longwave::set_cloud_sampling(const Array_gpu<Float,2>* cloud_frac, const int overlap, const Array_gpu<Float,2>* overlap_param,
+                                                   const uint64_t seed, const int col_offset)
+{
+    if (overlap != 0 && overlap != 1)
+        throw std::runtime_error("Radiation_solver_longwave::set_cloud_sampling: overlap " + std::to_string(overlap) + " is not 0 (maximum-random) or 1 (exponential-random)");
+    if (cloud_frac != nullptr && overlap == 1 && overlap_param == nullptr)
+        throw std::runtime_error("Radiation_solver_longwave::set_cloud_sampling: exponential-random overlap needs overlap_param");
+    mcica_frac = cloud_frac; mcica_alpha = (cloud_frac != nullptr && overlap == 1) ? overlap_param : nullptr;
+    mcica_seed = seed; mcica_col_offset = col_offset;
 }
 
 void Radiation_solver_longwave::set_optimal_angles(const bool b)
@@ -388,6 +429,14 @@ void Radiation_solver_longwave::solve_gpu(
     if (lw_rescaling && switch_fluxes && !broadband)
         throw std::runtime_error("Radiation_solver_longwave: LW rescaling (set_lw_rescaling) needs the broadband solvers "
                                  "(set_broadband_solvers) without band flux output: the fused rescaled solver gives broadband fluxes");
+    const bool mcica = mcica_frac != nullptr;
+    if (mcica && lw_scattering)
+        throw std::runtime_error("Radiation_solver_longwave: cloud sampling (set_cloud_sampling) is not available with LW scattering "
+                                 "(set_lw_scattering): the two-stream solver combines the band clouds itself");
+    if (mcica && lw_rescaling)
+        throw std::runtime_error("Radiation_solver_longwave: cloud sampling (set_cloud_sampling) is not available with LW rescaling "
+                                 "(set_lw_rescaling): the rescaled solver combines the band clouds itself");
+    if (mcica) check_cloud_sampling("Radiation_solver_longwave", mcica_frac, mcica_alpha, n_col, n_lay, switch_cloud_optics);
     const bool resc = lw_rescaling && switch_fluxes;
     const bool scat = (lw_scattering || lw_rescaling) && switch_fluxes;      // the cloud goes to the solver as tau / ssa / g by band
     if (jac && (lw_flux_up_jac.dim(1) != n_col || lw_flux_up_jac.dim(2) != n_lev))
@@ -408,6 +457,7 @@ void Radiation_solver_longwave::solve_gpu(
             up.set_dims({co.n_out, n_lev}); dn.set_dims({co.n_out, n_lev}); net.set_dims({co.n_out, n_lev});
             if (switch_output_bnd_fluxes) { bup.set_dims({co.n_out, n_lev, n_bnd}); bdn.set_dims({co.n_out, n_lev, n_bnd}); bnet.set_dims({co.n_out, n_lev, n_bnd}); }
             struct Guard { bool& f; Guard(bool& f_) : f(f_) { f = true; } ~Guard() { f = false; } } guard(reordered_call);
+            Sampling_reordered sampling(mcica_frac, mcica_alpha, mcica_col_id, mcica_col_offset, co);
             this->solve_gpu(switch_fluxes, switch_cloud_optics, switch_output_optical, switch_output_bnd_fluxes, gases,
                             co.in2(p_lay), co.in2(p_lev), co.in2(t_lay), co.in2(t_lev), co.in2(col_dry), co.in1(t_sfc), co.in_last(emis_sfc),
                             co.in2(lwp), co.in2(iwp), co.in2(rel), co.in2(dei), no3a, no3b, no3c, no2, up, dn, net, bup, bdn, bnet);
@@ -483,7 +533,16 @@ void Radiation_solver_longwave::solve_gpu(
         else if (switch_cloud_optics)
             cloud_optics_gpu->cloud_optics(sub2(lwp, n_lay), sub2(iwp, n_lay), sub2(rel, n_lay), sub2(dei, n_lay), *ws.cloud_optical_props);
         kdist_gpu->gas_optics(p_lay_s, p_lev_s, t_lay_s, t_sfc_s, gas_concs_subset, ws.optical_props, *ws.sources, col_dry_s, t_lev_s,
-                              (switch_cloud_optics && !scat) ? ws.cloud_optical_props.get() : nullptr);
+                              (switch_cloud_optics && !scat && !mcica) ? ws.cloud_optical_props.get() : nullptr);
+        if (mcica)      // every g-point its own sub-column: the band cloud optical depth is added in the cloudy cells only
+        {
+            const Array_gpu<Float,2> frac_s = sub2(*mcica_frac, n_lay);
+            const Array_gpu<Float,2> alpha_s = (mcica_alpha != nullptr && n_lay > 1) ? sub2(*mcica_alpha, n_lay-1) : Array_gpu<Float,2>();
+            RRX_CALL(rrx_mcica_increment_1scalar, n_in, n_lay, n_gpt, n_bnd, ws.optical_props->get_band_lims_gpoint_gpu().ptr(),
+                     frac_s.ptr(), mcica_alpha != nullptr ? alpha_s.ptr() : nullptr, (unsigned long long)mcica_seed, 0,
+                     mcica_col_id != nullptr ? mcica_col_id + (col_s-1) : nullptr, mcica_col_offset + col_s-1,
+                     ws.optical_props->get_tau().ptr(), ws.cloud_optical_props->get_tau().ptr(), static_cast<unsigned char*>(nullptr));
+        }
 
         if (switch_output_optical)
         {
@@ -667,6 +726,11 @@ void Radiation_solver_shortwave::solve_gpu(
     const bool broadband = broadband_solvers && !switch_output_bnd_fluxes;
     // by-band solvers: the band sums come straight out of the fused solver (one slab per band in the block workspace)
     const bool byband = byband_solvers && switch_output_bnd_fluxes && switch_fluxes && n_bnd < n_gpt;
+    const bool mcica = mcica_frac != nullptr;
+    if (mcica && sunlit_columns)
+        throw std::runtime_error("Radiation_solver_shortwave: cloud sampling (set_cloud_sampling) is not available with the sunlit-only "
+                                 "solve (set_sunlit_columns): it does not carry the column identities");
+    if (mcica) check_cloud_sampling("Radiation_solver_shortwave", mcica_frac, mcica_alpha, n_col, n_lay, switch_cloud_optics);
 
     // columns in another order / on a padded count: gather the inputs, solve, scatter the fluxes back (see the header)
     if (!reordered_call && !switch_output_optical && switch_fluxes)
@@ -696,6 +760,7 @@ void Radiation_solver_shortwave::solve_gpu(
             if (switch_output_bnd_fluxes)
             { bup.set_dims({co.n_out, n_lev, n_bnd}); bdn.set_dims({co.n_out, n_lev, n_bnd}); bdir.set_dims({co.n_out, n_lev, n_bnd}); bnet.set_dims({co.n_out, n_lev, n_bnd}); }
             struct Guard { bool& f; Guard(bool& f_) : f(f_) { f = true; } ~Guard() { f = false; } } guard(reordered_call);
+            Sampling_reordered sampling(mcica_frac, mcica_alpha, mcica_col_id, mcica_col_offset, co);
             this->solve_gpu(switch_fluxes, switch_cloud_optics, switch_aerosol_optics, switch_output_optical, switch_output_bnd_fluxes,
                             switch_delta_cloud, switch_delta_aerosol, gases,
                             co.in2(p_lay), co.in2(p_lev), co.in2(t_lay), co.in2(t_lev), co.in2(col_dry),
@@ -758,7 +823,19 @@ void Radiation_solver_shortwave::solve_gpu(
         }
         Array_gpu<Float,2> toa_src_s({n_in, n_gpt});
         kdist_gpu->gas_optics(p_lay_s, p_lev_s, t_lay_s, gas_concs_subset, ws.optical_props, toa_src_s, col_dry_s,
-                              switch_cloud_optics ? ws.cloud_optical_props.get() : nullptr);
+                              (switch_cloud_optics && !mcica) ? ws.cloud_optical_props.get() : nullptr);
+        if (mcica)      // every g-point its own sub-column: the band cloud tau / ssa / g are combined in the cloudy cells only
+        {
+            Optical_props_2str_gpu& op = dynamic_cast<Optical_props_2str_gpu&>(*ws.optical_props);
+            const Array_gpu<Float,2> frac_s = sub2(*mcica_frac, n_lay);
+            const Array_gpu<Float,2> alpha_s = (mcica_alpha != nullptr && n_lay > 1) ? sub2(*mcica_alpha, n_lay-1) : Array_gpu<Float,2>();
+            // (get_g(): the clear gas optics' g == 0 is materialised here, the kernel reads and writes the array)
+            RRX_CALL(rrx_mcica_increment_2stream, n_in, n_lay, n_gpt, n_bnd, op.get_band_lims_gpoint_gpu().ptr(),
+                     frac_s.ptr(), mcica_alpha != nullptr ? alpha_s.ptr() : nullptr, (unsigned long long)mcica_seed, 1,
+                     mcica_col_id != nullptr ? mcica_col_id + (col_s-1) : nullptr, mcica_col_offset + col_s-1,
+                     op.get_tau().ptr(), op.get_ssa().ptr(), op.get_g().ptr(), ws.cloud_optical_props->get_tau().ptr(),
+                     ws.cloud_optical_props->get_ssa().ptr(), ws.cloud_optical_props->get_g().ptr(), static_cast<unsigned char*>(nullptr));
+        }
         Array_gpu<Float,1> tsi_s = sub1(tsi_scaling);
         RRX_CALL(rrx_scaling_to_subset, n_in, n_gpt, toa_src_s.ptr(), tsi_s.ptr());
 
@@ -853,3 +930,15 @@ void Radiation_solver_shortwave::solve_gpu(
 }
 
 void Radiation_solver_shortwave::set_sunlit_columns(const bool b) { sunlit_columns = b; }
+
+void Radiation_solver_shortwave::set_cloud_sampling(const Array_gpu<Float,2>* cloud_frac, const int overlap, const Array_gpu<Float,2>* overlap_param,
+                                                   const uint64_t seed, const int col_offset)
+{
+    if (overlap != 0 && overlap != 1)
+        throw std::runtime_error("Radiation_solver_shortwave::set_cloud_sampling: overlap " + std::to_string(overlap) + " is not 0 (maximum-random) or 1 (exponential-random)");
+    if (cloud_frac != nullptr && overlap == 1 && overlap_param == nullptr)
+        throw std::runtime_error("Radiation_solver_shortwave::set_cloud_sampling: exponential-random overlap needs overlap_param");
+    mcica_frac = cloud_frac; mcica_alpha = (cloud_frac != nullptr && overlap == 1) ? overlap_param : nullptr;
+    mcica_seed = seed; mcica_col_offset = col_offset;
+}
+

@@ -22,6 +22,7 @@ namespace
         int ncol = 0, nlay = 0;
         // broadband outputs of the last solve, (ncol, nlay+1) each: LW up, dn, net; SW up, dn, dn_dir, net
         Array_gpu<Float,2> lw_up, lw_dn, lw_net, sw_up, sw_dn, sw_dir, sw_net;
+        Array_gpu<Float,2> cloud_frac, overlap_param;        // views of the caller's McICA fields (rrx_cxx_cloud_sampling)
     };
 
     template<typename Fn> int guarded(Fn&& f)
@@ -106,6 +107,21 @@ int rrx_cxx_lw_optimal_angles(void* h, const int on)
 int rrx_cxx_lw_jacobian(void* h, const int on)
 {
     return guarded([&] { static_cast<Driver*>(h)->lw->set_jacobian(on != 0); });
+}
+
+int rrx_cxx_cloud_sampling(void* h, const Float* cloud_frac, const int ncol, const int nlay, const int overlap, const Float* overlap_param,
+                           const unsigned long long seed, const int col_offset)
+{
+    return guarded([&]
+    {
+        Driver& d = *static_cast<Driver*>(h);
+        d.cloud_frac = view2(cloud_frac, ncol, nlay);
+        d.overlap_param = view2(overlap_param, ncol, nlay-1);
+        const Array_gpu<Float,2>* f = cloud_frac ? &d.cloud_frac : nullptr;
+        const Array_gpu<Float,2>* a = overlap_param ? &d.overlap_param : nullptr;
+        d.lw->set_cloud_sampling(f, overlap, a, seed, col_offset);
+        d.sw->set_cloud_sampling(f, overlap, a, seed, col_offset);
+    });
 }
 
 // the (ncol, nlay+1) surface-temperature Jacobian of the LW upward flux of the last solve, copied to `out` on `stream`

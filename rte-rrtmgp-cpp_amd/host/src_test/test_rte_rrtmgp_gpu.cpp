@@ -313,6 +313,42 @@ namespace
         }
     }
 
+    // `--cloud-overlap max-ran|exp-ran` and `--mcica-seed N` (McICA cloud sampling, with --cloud-fraction), taken out the same way
+    int cloud_overlap = 0;                       // 0 = maximum-random, 1 = exponential-random
+    unsigned long long mcica_seed = 0;
+    bool extract_value(std::vector<std::string>& args, const std::string& opt, std::string& value)
+    {
+        bool found = false;
+        for (size_t i=0; i<args.size(); )
+        {
+            if (args[i].compare(0, opt.size() + 1, opt + "=") == 0) { value = args[i].substr(opt.size() + 1); args.erase(args.begin() + i); }
+            else if (args[i] == opt)
+            {
+                if (i + 1 >= args.size()) throw std::runtime_error(opt + " needs a value");
+                value = args[i+1]; args.erase(args.begin() + i, args.begin() + i + 2);
+            }
+            else { ++i; continue; }
+            found = true;
+        }
+        return found;
+    }
+    void extract_cloud_sampling(std::vector<std::string>& args)
+    {
+        cloud_overlap = 0; mcica_seed = 0;
+        std::string value;
+        if (extract_value(args, "--cloud-overlap", value))
+        {
+            if (value != "max-ran" && value != "exp-ran") throw std::runtime_error("--cloud-overlap " + value + ": the overlap is max-ran or exp-ran");
+            cloud_overlap = value == "exp-ran" ? 1 : 0;
+        }
+        if (extract_value(args, "--mcica-seed", value))
+        {
+            char* end = nullptr;
+            mcica_seed = std::strtoull(value.c_str(), &end, 0);
+            if (value.empty() || *end != 0 || value[0] == '-') throw std::runtime_error("--mcica-seed " + value + ": the seed is an unsigned 64-bit integer");
+        }
+    }
+
     bool parse_command_line_options(std::map<std::string, std::pair<bool, std::string>>& options, int argc, char** argv)
     {
         for (int i=1; i<argc; ++i)
@@ -329,6 +365,10 @@ namespace
                 }
                 std::ostringstream ss;
                 ss << std::left << std::setw(30) << "--lw-gauss-angles N" << "Quadrature angles of the longwave solver, 1..4 (default 1); not with --byband-solvers.";
+                Status::print_message(ss.str());
+                ss.str(""); ss << std::left << std::setw(30) << "--cloud-overlap max-ran|exp-ran" << "Overlap of --cloud-fraction (default max-ran); exp-ran reads overlap_param(lay-1, y, x).";
+                Status::print_message(ss.str());
+                ss.str(""); ss << std::left << std::setw(30) << "--mcica-seed N" << "Seed of the cloud mask of --cloud-fraction (unsigned 64-bit, default 0).";
                 Status::print_message(ss.str());
                 return true;
             }
@@ -373,6 +413,7 @@ void solve_radiation(int argc, char** argv)
         {"lw-optimal-angles", { false, "Longwave secant per column and g-point from the coefficient file's optimal_angle_fit (one angle); not with --lw-gauss-angles > 1 or --byband-solvers." }},
         {"lw-scattering"    , { false, "Longwave two-stream solve with cloud scattering (set_lw_scattering): band cloud tau / ssa / g; not with --lw-gauss-angles > 1, --lw-optimal-angles, --lw-jacobian, --byband-solvers or per-g-point solvers." }},
         {"lw-rescaling"     , { false, "Longwave no-scattering solve on rescaled optical depths with one correction sweep (set_lw_rescaling): band cloud tau / ssa / g; not with --lw-scattering, --lw-gauss-angles > 1, --lw-optimal-angles, --lw-jacobian, --byband-solvers or per-g-point solvers." }},
+        {"cloud-fraction"   , { false, "McICA cloud sampling (set_cloud_sampling): every g-point sees a sub-column drawn from cloud_frac(lay, y, x) of the input file; needs --cloud-optics; not with --lw-scattering, --lw-rescaling or --sunlit-columns. Columns are then ordered on the device only." }},
         {"lw-jacobian"      , { false, "Write lw_flux_up_jac, d lw_flux_up / d t_sfc [W m-2 K-1] from the same LW solve (set_jacobian)." }},
         {"async"            , { false, "Host-model mode: vertical ordering read once, solves enqueued without synchronising." }},
         {"sort-columns"     , { true,  "Solve the columns in order of surface pressure where neighbours differ much (outputs keep the input order)." }},
@@ -430,10 +471,21 @@ void solve_radiation(int argc, char** argv)
     if (lw_gauss_angles > 1 && switch_byband_solvers)
         throw std::runtime_error("--lw-gauss-angles " + std::to_string(lw_gauss_angles) + " is not available with --byband-solvers: "
                                  "the by-band solver has one quadrature angle");
+    const bool switch_cloud_fraction    = command_line_options.at("cloud-fraction").first;
+    if (switch_cloud_fraction && !switch_cloud_optics)
+        throw std::runtime_error("--cloud-fraction needs --cloud-optics: it samples the band cloud properties");
+    if (switch_cloud_fraction && switch_lw_scattering)
+        throw std::runtime_error("--cloud-fraction is not available with --lw-scattering: the two-stream solver combines the band clouds itself");
+    if (switch_cloud_fraction && switch_lw_rescaling)
+        throw std::runtime_error("--cloud-fraction is not available with --lw-rescaling: the rescaled solver combines the band clouds itself");
+    if (switch_cloud_fraction && switch_sunlit_columns)
+        throw std::runtime_error("--cloud-fraction is not available with --sunlit-columns: the sunlit-only solve does not carry the column identities");
     const bool switch_heating_rates     = command_line_options.at("heating-rates"    ).first;
     const bool switch_async             = command_line_options.at("async"            ).first;
     const bool switch_device_sort       = command_line_options.at("device-sort-columns").first;
-    const bool switch_sort_columns      = command_line_options.at("sort-columns"     ).first && !switch_device_sort;
+    // (cloud sampling keys a column's draws by its index in the input file: the host-side ordering is left to the solvers then)
+    const bool sort_requested           = command_line_options.at("sort-columns"     ).first && !switch_device_sort;
+    const bool switch_sort_columns      = sort_requested && !switch_cloud_fraction;
 
     Status::print_message("Solver settings:");
     for (const auto& option : command_line_options)
@@ -511,6 +563,20 @@ void solve_radiation(int argc, char** argv)
         dei = shard2(Array<Float,2>(input_nc.get_variable<Float>("dei", {n_lay, n_col_y, n_col_x}), {n_col_glob, n_lay}));
     }
 
+    Array<Float,2> cloud_frac, overlap_param;
+    if (switch_cloud_fraction)
+    {
+        if (!input_nc.variable_exists("cloud_frac"))
+            throw std::runtime_error("--cloud-fraction: variable \"cloud_frac\" is not in the input file");
+        cloud_frac = shard2(Array<Float,2>(input_nc.get_variable<Float>("cloud_frac", {n_lay, n_col_y, n_col_x}), {n_col_glob, n_lay}));
+        if (cloud_overlap == 1)
+        {
+            if (!input_nc.variable_exists("overlap_param"))
+                throw std::runtime_error("--cloud-overlap exp-ran: variable \"overlap_param\" is not in the input file");
+            overlap_param = shard2(Array<Float,2>(input_nc.get_variable<Float>("overlap_param", {n_lay-1, n_col_y, n_col_x}), {n_col_glob, n_lay-1}));
+        }
+    }
+
     ////// CREATE THE OUTPUT FILE //////
     Status::print_message("Preparing NetCDF output file.");
     // every rank runs the same output code on the gathered arrays; only rank 0's file is kept
@@ -527,6 +593,7 @@ void solve_radiation(int argc, char** argv)
     Gas_concs_gpu gas_concs_gpu(gas_concs);
     Array_gpu<Float,2> p_lay_gpu(p_lay), p_lev_gpu(p_lev), t_lay_gpu(t_lay), t_lev_gpu(t_lev), col_dry_gpu(col_dry);
     Array_gpu<Float,2> lwp_gpu(lwp), iwp_gpu(iwp), rel_gpu(rel), dei_gpu(dei);
+    Array_gpu<Float,2> cloud_frac_gpu(cloud_frac), overlap_param_gpu(overlap_param);
 
     auto time_runs = [&](const std::string& name, const std::function<void()>& run)
     {
@@ -557,8 +624,10 @@ void solve_radiation(int argc, char** argv)
         rad_lw.set_optimal_angles(switch_lw_optimal_angles);      // (throws for a coefficient file without optimal_angle_fit)
         // (--no-sort-columns: the file's order and column count exactly; otherwise the solver pads to a multiple of 16 columns and,
         //  with --device-sort-columns, orders them itself)
-        rad_lw.set_column_sorting(switch_device_sort ? 1 : (switch_sort_columns ? -1 : 0));
-        rad_lw.set_column_padding(switch_sort_columns || switch_device_sort);
+        rad_lw.set_column_sorting(switch_device_sort ? 1 : (sort_requested ? -1 : 0));
+        rad_lw.set_column_padding(sort_requested || switch_device_sort);
+        if (switch_cloud_fraction)
+            rad_lw.set_cloud_sampling(&cloud_frac_gpu, cloud_overlap, cloud_overlap == 1 ? &overlap_param_gpu : nullptr, mcica_seed, ranks.col_s);
         if (switch_async) rad_lw.set_vertical_ordering(p_lay({1, 1}) < p_lay({1, n_lay}) ? 1 : 0);    // known on the host: no read-backs per solve
 
         const int n_bnd_lw = rad_lw.get_n_bnd_gpu();
@@ -637,8 +706,10 @@ void solve_radiation(int argc, char** argv)
         rad_sw.set_broadband_solvers(switch_broadband);
         rad_sw.set_byband_solvers(switch_byband_solvers);
         rad_sw.set_sunlit_columns(switch_sunlit_columns);
-        rad_sw.set_column_sorting(switch_device_sort ? 1 : (switch_sort_columns ? -1 : 0));
-        rad_sw.set_column_padding(switch_sort_columns || switch_device_sort);
+        rad_sw.set_column_sorting(switch_device_sort ? 1 : (sort_requested ? -1 : 0));
+        rad_sw.set_column_padding(sort_requested || switch_device_sort);
+        if (switch_cloud_fraction)
+            rad_sw.set_cloud_sampling(&cloud_frac_gpu, cloud_overlap, cloud_overlap == 1 ? &overlap_param_gpu : nullptr, mcica_seed, ranks.col_s);
         if (switch_async) rad_sw.set_vertical_ordering(p_lay({1, 1}) < p_lay({1, n_lay}) ? 1 : 0);
 
         const int n_bnd_sw = rad_sw.get_n_bnd_gpu();
@@ -764,6 +835,7 @@ extern "C" int rrx_host_main(int argc, char** argv)
         if (n_gpus > 1 && !std::getenv("RRX_RANK"))
             return launch_ranks(n_gpus, args);                       // this process only starts and awaits the ranks
         extract_lw_gauss_angles(args);
+        extract_cloud_sampling(args);
         std::vector<char*> av{argv[0]};
         for (auto& a : args) av.push_back(const_cast<char*>(a.c_str()));
         solve_radiation(int(av.size()), av.data());

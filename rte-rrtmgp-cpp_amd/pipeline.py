@@ -194,9 +194,35 @@ class ResidentSolver:
 
     def __init__(self, be, kd_lw, kd_sw, atm, do_broadband=False, overlap=False, cloud_luts=None, sort_columns=None, byband=False,
                  sunlit=False, jacobian=False, n_gauss_angles=1, optimal_angles=False, keep_secants=False, lw_scattering=False,
-                 lw_rescaling=False):
+                 lw_rescaling=False, cloud_fraction=None, cloud_overlap="max_ran", overlap_param=None, mcica_seed=0, mcica_col_offset=0):
         import torch
         self.torch = torch
+        # cloud_fraction: McICA cloud sampling. (nlay, ncol) cloud fractions in the caller's column order; each step runs
+        # the CLEAR gas optics and then rrx_mcica_increment_*, which gives every g-point its own sub-column and adds the band cloud
+        # properties in the cloudy cells only. cloud_overlap: "max_ran", or "exp_ran" with overlap_param (nlay-1, ncol), the overlap
+        # parameter between array layers l and l+1. The mask is redrawn every step from the current self.mcica_seed (a host advances it
+        # between calls; domain 0 = LW, 1 = SW); a column's draws are keyed by mcica_col_offset + its index in the caller's order, so
+        # sorting, padding and sharding do not change them. The fields stay attributes: replace or update them between steps.
+        self.cloud_fraction, self.overlap_param = cloud_fraction, overlap_param
+        self.mcica_seed, self.mcica_col_offset = int(mcica_seed), int(mcica_col_offset)
+        if cloud_fraction is None:
+            if overlap_param is not None:
+                raise ValueError("ResidentSolver: overlap_param without cloud_fraction")
+        else:
+            if cloud_luts is None:
+                raise ValueError("ResidentSolver: cloud_fraction needs cloud_luts (the cloud optics whose band properties are sampled)")
+            if cloud_overlap not in ("max_ran", "exp_ran"):
+                raise ValueError(f"ResidentSolver: cloud_overlap = {cloud_overlap!r} is not 'max_ran' or 'exp_ran'")
+            if (cloud_overlap == "exp_ran") != (overlap_param is not None):
+                raise ValueError("ResidentSolver: cloud_overlap='exp_ran' takes overlap_param (nlay-1, ncol), 'max_ran' takes none")
+            if tuple(cloud_fraction.shape) != (atm.nlay, atm.ncol):
+                raise ValueError(f"ResidentSolver: cloud_fraction {tuple(cloud_fraction.shape)} is not (nlay, ncol) = {(atm.nlay, atm.ncol)}")
+            if overlap_param is not None and tuple(overlap_param.shape) != (atm.nlay-1, atm.ncol):
+                raise ValueError(f"ResidentSolver: overlap_param {tuple(overlap_param.shape)} is not (nlay-1, ncol) = {(atm.nlay-1, atm.ncol)}")
+            for flag, name in ((lw_scattering, "lw_scattering=True"), (lw_rescaling, "lw_rescaling=True"), (sunlit, "sunlit=True")):
+                if flag:
+                    raise ValueError(f"ResidentSolver: cloud_fraction with {name} is not supported (the scattering LW solvers combine "
+                                     "the band clouds themselves; the sunlit-only SW chain does not carry the column identities)")
         # lw_rescaling: the LW chain treats cloud scattering by rescaling -- clear gas optics, LW cloud tau / ssa / g by band
         # (cloud_optics_2str on the LW table, not delta-scaled) and the fused no-scattering solve on rescaled optical depths with one
         # correction sweep (lw_solver_noscat_fractions_rescaled); without cloud LUTs the same solver with ssa = 0. One angle, broadband:
@@ -466,6 +492,14 @@ class ResidentSolver:
                 rec[stage][1 if end else 0].record(self.torch.cuda.current_stream(be.device))   # the chain's stream when overlapping
 
         ncol, nlay = atm.ncol, atm.nlay
+        mcica = self.cloud_fraction is not None
+        if mcica:     # the sampled fields in the step's column order, and the identities that go with it
+            cfrac, alpha = self.cloud_fraction, self.overlap_param
+            col_id = None
+            if perm is not None:
+                cfrac = cfrac.index_select(1, perm)
+                alpha = None if alpha is None else alpha.index_select(1, perm)
+                col_id = self.perm_i32 + self.mcica_col_offset
         F = self.fluxes if perm is None else self.fluxes_sorted
         J = self.lw_flux_up_jac if perm is None else self.jac_sorted
         BL = self.bnd_lw if perm is None else self.bnd_lw_sorted
@@ -513,7 +547,7 @@ class ResidentSolver:
             it = None if self.direct else be.interpolation(kd, atm.p_lay, atm.t_lay, col_gas)
             # all-sky: the by-band cloud properties are computed first and added where the gas optics is stored (fused); with
             # RRX_FUSE_CLOUDS=0 by the reference's separate increment kernels afterwards
-            fuse = self.cloud_luts is not None and self.direct and self.fuse_clouds
+            fuse = self.cloud_luts is not None and self.direct and self.fuse_clouds and not mcica
             if kind == "lw":
                 tc = cld_lw = None
                 if self.cloud_luts is not None and (self.lw_scattering or self.lw_rescaling):      # tau, ssa, g by band: the solver combines them itself
@@ -527,7 +561,9 @@ class ResidentSolver:
                     be.gas_optics_lw_direct(kd, atm.p_lay, atm.t_lay, col_gas, buf["tau"], by_band=tc if fuse else None)
                 else:
                     be.compute_tau_absorption_set(kd, it, atm.p_lay, atm.t_lay, col_gas, buf["tau"])
-                if tc is not None and not fuse:
+                if tc is not None and mcica:
+                    be.mcica_increment_1scalar(buf["tau"], tc, kd.band_lims_gpt, cfrac, alpha, self.mcica_seed, 0, col_id, self.mcica_col_offset)
+                elif tc is not None and not fuse:
                     be.inc_1scalar_by_1scalar_bybnd(buf["tau"], tc, kd.band_lims_gpt)
                 mark("lw_gas_optics", True)
                 mark("lw_planck")
@@ -592,7 +628,10 @@ class ResidentSolver:
                 else:
                     be.gas_optics_sw_fused(kd, it, atm.p_lay, atm.t_lay, col_gas, col_dry, buf["tau"], buf["ssa"], gbuf)
                 toa = be.toa_source(ncol, kd.solar_source, atm.tsi_scaling)     # spread_col + scaling_to_subset, one launch
-                if cld is not None and not fuse:
+                if cld is not None and mcica:
+                    be.mcica_increment_2stream(buf["tau"], buf["ssa"], gbuf, *cld, kd.band_lims_gpt, cfrac, alpha, self.mcica_seed, 1, col_id,
+                                               self.mcica_col_offset)
+                elif cld is not None and not fuse:
                     be.inc_2stream_by_2stream_bybnd(buf["tau"], buf["ssa"], gbuf, *cld, kd.band_lims_gpt)
                 mark("sw_gas_optics", True)
                 mark("sw_solver")

@@ -36,6 +36,15 @@ def shard_atmosphere(atm, rank, world):
     return Atmosphere(**out)
 
 
+def shard_cloud_sampling(cloud_fraction, overlap_param, rank, world):
+    """This rank's McICA arguments of pipeline.ResidentSolver from the whole domain's cloud_fraction (nlay, ncol) and overlap_param
+    ((nlay-1, ncol) or None), numpy or torch: the column slices and mcica_col_offset = the rank's first column, so that a column
+    draws the same sub-columns on any number of ranks."""
+    s, e = column_range(rank, world, cloud_fraction.shape[-1])
+    cut = lambda a: None if a is None else (a[..., s:e].contiguous() if hasattr(a, "contiguous") else a[..., s:e].copy())
+    return dict(cloud_fraction=cut(cloud_fraction), overlap_param=cut(overlap_param), mcica_col_offset=s)
+
+
 def gather_fluxes(local, ncol_total, group=None):
     """All-gather packed fluxes (nflux, nlev, ncol_local) -> (nflux, nlev, ncol_total) on every rank.
     Uneven shards are padded to the largest one so that a single all_gather_into_tensor suffices."""
