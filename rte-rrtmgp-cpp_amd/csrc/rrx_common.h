@@ -10,6 +10,9 @@
 #include <vector>
 #include <stdexcept>
 #include <type_traits>
+#include <initializer_list>
+#include <utility>
+#include "rrx_hip.h"
 
 typedef signed char Bool;   // RTE_USE_CBOOL in every shipped reference config (config/ubuntu_22lts.cmake:35)
 
@@ -377,6 +380,31 @@ namespace rrx
         out[i] = s;
     }
 
+    // One tiling of a one-kernel broadband solver with its g-point loop split over grid.y, whole: the number of ranges
+    // (broadband_gsplit for `groups` column groups on `slots` resident places), the partial arrays, the launch and the sum of the
+    // partials. with_tiling_k is the tiling's with_k<...> list (it takes a callable and returns whether a K took the shape: false
+    // launches and allocates nothing, the caller tries its next tiling). launch(kk, gs, grid, gper, p0, p1, p2) starts the solver
+    // kernel for K = decltype(kk)::value on `grid` with the compile-time flag GS = decltype(gs)::value: each workgroup row sums gper
+    // g-points into p0, p1 [, p2]. Unsplit these are the NARR (ncol, nlev) outputs o0, o1 [, o2] themselves (an array beyond NARR is
+    // passed through as it is); split they are partials in stream-ordered scratch, one (nlev, ncol) slab per range and the arrays
+    // behind each other, which sum_ranges_kernel<F,NARR> then adds into the outputs in range order.
+    template<typename F, int NARR, typename WithK, typename Launch>
+    bool launch_gsplit(hipStream_t st, const int groups, const int ngpt, const int slots, const size_t nlevcol,
+                       F* const o0, F* const o1, F* const o2, WithK&& with_tiling_k, Launch&& launch)
+    {
+        const int gper = ceil_div(ngpt, broadband_gsplit(groups, ngpt, slots));
+        const int nsplit = ceil_div(ngpt, gper);             // no empty range: every workgroup's first g-point exists (it is prefetched)
+        const dim3 grid(groups, nsplit);
+        StreamScratch scratch(st);
+        return with_tiling_k([&](auto kk)
+        {
+            if (nsplit == 1) { launch(kk, std::false_type{}, grid, gper, o0, o1, o2); return; }
+            F* const p = scratch.get<F>(NARR*nsplit*nlevcol);
+            launch(kk, std::true_type{}, grid, gper, p, p + nsplit*nlevcol, (NARR > 2) ? p + 2*nsplit*nlevcol : o2);
+            sum_ranges_kernel<F,NARR><<<dim3(ceil_div(nlevcol, 256), NARR), 256, 0, st>>>(nlevcol, nsplit, p, o0, o1, o2);
+        });
+    }
+
     // ---- by-band outputs of the broadband solvers (rrx_*_byband entries). Band limits: band_lims(2, nbnd), 1-based, inclusive, as
     // rrx_sum_byband takes them; a band with hi < lo is empty (zeros).
 
@@ -436,6 +464,64 @@ namespace rrx
     {
         if (net == nullptr && o0 == nullptr && o1 == nullptr && (NARR < 3 || o2 == nullptr)) return;
         byband_outputs_kernel<F,NARR><<<unsigned(ceil_div(ncl_lev, size_t(256))), 256, 0, st>>>(ncl_lev, nbnd, b0, b1, b2, net, o0, o1, o2);
+    }
+}
+
+// ---- host pieces shared by the LW solver files (rrx_solver_lw.hip, rrx_solver_lw1r.hip, rrx_solver_lw2s.hip)
+namespace rrx
+{
+    // the one-kernel broadband forms serve every LW variant but 1 (serial kernels) and 7 (per-g-point fluxes in a workspace + sum)
+    inline bool lw_fused_allowed()
+    {
+        const int v = tuning().lw_variant;
+        return v != 1 && v != 7;
+    }
+
+    // argument checks of the scattering entries: throws with the argument's name, returns true for an empty problem (nothing to do)
+    inline bool empty_problem(std::initializer_list<std::pair<const char*, int>> extents,
+                              std::initializer_list<std::pair<const char*, const void*>> required)
+    {
+        bool empty = false;
+        for (const auto& e : extents)
+        {
+            if (e.second < 0) throw std::runtime_error(std::string(e.first) + " is negative");
+            if (e.second == 0) empty = true;
+        }
+        if (empty) return true;
+        for (const auto& p : required)
+            if (p.second == nullptr) throw std::runtime_error(std::string(p.first) + " is null");
+        return false;
+    }
+
+    // the C entries of other files by the type of their arrays
+    inline int inc_bybnd(int ncol, int nlay, int ngpt, double* t, double* w, double* g, const double* t2, const double* w2, const double* g2,
+                         int nbnd, const int* lims, void* stream)
+    { return rrx_inc_2stream_by_2stream_bybnd_f64(ncol, nlay, ngpt, t, w, g, t2, w2, g2, nbnd, lims, stream); }
+    inline int inc_bybnd(int ncol, int nlay, int ngpt, float* t, float* w, float* g, const float* t2, const float* w2, const float* g2,
+                         int nbnd, const int* lims, void* stream)
+    { return rrx_inc_2stream_by_2stream_bybnd_f32(ncol, nlay, ngpt, t, w, g, t2, w2, g2, nbnd, lims, stream); }
+    inline int planck_sources(int ncol, int nlay, int ngpt, const int* gb, const double* pf, const double* bl, const double* bv, double* ls,
+                              double* vs, void* stream)
+    { return rrx_planck_sources_from_fractions_f64(ncol, nlay, ngpt, gb, pf, bl, bv, ls, vs, stream); }
+    inline int planck_sources(int ncol, int nlay, int ngpt, const int* gb, const float* pf, const float* bl, const float* bv, float* ls,
+                              float* vs, void* stream)
+    { return rrx_planck_sources_from_fractions_f32(ncol, nlay, ngpt, gb, pf, bl, bv, ls, vs, stream); }
+
+    // The fused scattering entries outside their tilings (and LW variants 1, 7): the g-point properties of gas plus band cloud,
+    // materialised as [tau | ssa | g], (ncol, nlay, ngpt) each, at c_tau in the entry's workspace lease: the gas optical depth with
+    // ssa = g = 0, incremented by the band cloud when its three arrays are given
+    template<typename F>
+    void gas_plus_cloud(void* stream, const int ncol, const int nlay, const int ngpt, const int nbnd, const int* band_lims,
+                        const F* tau, const F* cld_tau, const F* cld_ssa, const F* cld_g, F* c_tau)
+    {
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        const size_t n_lay = size_t(ncol)*nlay*ngpt;
+        F* c_ssa = c_tau + n_lay; F* c_g = c_ssa + n_lay;
+        if (hipMemcpyAsync(c_tau, tau, n_lay*sizeof(F), hipMemcpyDeviceToDevice, st) != hipSuccess ||
+            hipMemsetAsync(c_ssa, 0, 2*n_lay*sizeof(F), st) != hipSuccess)
+            throw std::runtime_error("workspace fill failed");
+        if (cld_tau != nullptr && inc_bybnd(ncol, nlay, ngpt, c_tau, c_ssa, c_g, cld_tau, cld_ssa, cld_g, nbnd, band_lims, stream) != 0)
+            throw std::runtime_error(std::string("combining gas and cloud failed: ") + rrx_last_error());
     }
 }
 

@@ -877,10 +877,11 @@ struct BbArgs
     const int* gpoint_bands;
     const F *sfc_emis, *sfc_src, *inc_flux;
     F *flux_up, *flux_dn;
-    const int* band_lims; int nbnd;             // by-band form: flux_up/dn are (ncol, nlev, nbnd) band sums
-    const F* sfc_src_jac; F* flux_up_jac;       // JAC: (ngpt, ncol) in, (ncol, nlev) out
-    int nmus;                                   // MU: quadrature angles; secants (ncol, ngpt, nmus), weights (nmus)
-    const F* opt_fit = nullptr; F* secants_out = nullptr;      // OPT: fit (2, nbnd) in, the secants used (ncol, ngpt) out or null
+    // what is given below chooses the form (lw_fractions_solve)
+    const F* sfc_src_jac = nullptr; F* flux_up_jac = nullptr;      // JAC: (ngpt, ncol) in, (ncol, nlev) out
+    int nmus = 1;                                                   // MU: quadrature angles; secants (ncol, ngpt, nmus), weights (nmus)
+    const F* opt_fit = nullptr; F* secants_out = nullptr;          // OPT: fit (2, nbnd) in, the secants used (ncol, ngpt) out or null
+    const int* band_lims = nullptr; int nbnd = 0;                  // by-band form: flux_up/dn are (ncol, nlev, nbnd) band sums (OPT: nbnd of the fit)
 };
 
 // one tiling of the fused broadband kernel (lw_noscat_bb_kernel); false when the shape is outside it (the caller tries the next one).
@@ -895,7 +896,6 @@ bool launch_bb2(hipStream_t st, const BbArgs<F>& a)
     if (size_t(a.ncol)*(a.nlay+1) >= (size_t(1) << 31)) return false;      // 32-bit element offsets inside a g-point slab
     const int groups = ceil_div(a.ncol, (NW/W)*CLT*V);
     const int need = ceil_div(a.nlay+1, (64/CLT)*W);
-    if (need > ((CLT == 16 || W == 8) ? 9 : 5)) return false;
     auto with_tiling_k = [&](auto launch)      // the layers per lane of this tiling
     {
         if constexpr (CLT == 16) return with_k<2, 4, 6, 9>(need, launch);
@@ -919,29 +919,15 @@ bool launch_bb2(hipStream_t st, const BbArgs<F>& a)
         }
         return false;
     }
-    // few column groups: the g-point loop is split over grid.y, partial sums added in range order afterwards
-    const int gper = ceil_div(a.ngpt, broadband_gsplit(groups, a.ngpt, (NW > 4) ? 256 : 512));      // (one or two workgroups per CU)
-    const int nsplit = ceil_div(a.ngpt, gper);             // no empty range: every workgroup's first g-point exists (it is prefetched)
-    constexpr int NARR = JAC ? 3 : 2;
-    StreamScratch scratch(st);
-    F* out_up = a.flux_up; F* out_dn = a.flux_dn; F* out_jc = a.flux_up_jac;
-    if (nsplit > 1)
-    {
-        out_up = scratch.get<F>(NARR*nsplit*nlevcol); out_dn = out_up + nsplit*nlevcol;
-        if (JAC) out_jc = out_dn + nsplit*nlevcol;
-    }
-    const dim3 grid(groups, nsplit);
-    with_tiling_k([&](auto kk) { with_flag(nsplit > 1, [&](auto gs)
+    // few column groups: the g-point loop is split over grid.y (rrx::launch_gsplit; one or two workgroups per CU)
+    return launch_gsplit<F,(JAC ? 3 : 2)>(st, groups, a.ngpt, (NW > 4) ? 256 : 512, nlevcol, a.flux_up, a.flux_dn, a.flux_up_jac, with_tiling_k,
+        [&](auto kk, auto gs, const dim3 grid, const int gper, F* out_up, F* out_dn, F* out_jc)
     {
         lw_noscat_bb_kernel<F,V,decltype(kk)::value,W,CLT,LITE,decltype(gs)::value,RRX_LW_EV,NW,false,JAC,MU,OPT><<<grid, 64*NW, 0, st>>>(
             a.ncol, a.nlay, a.ngpt, a.top_at_1, a.secants, a.weights, a.tau, a.lay_source, a.lev_source, a.blay, a.blev,
             a.gpoint_bands, a.sfc_emis, a.sfc_src, a.inc_flux, out_up, out_dn, gper, nlevcol, nullptr, a.sfc_src_jac, out_jc,
             MU ? a.nmus : 1, OPT ? a.opt_fit : nullptr, OPT ? a.secants_out : nullptr);
-    }); });
-    if (nsplit > 1)      // (out_up, out_dn [, out_jc] lie behind each other in the scratch block)
-        sum_ranges_kernel<F,NARR><<<dim3(ceil_div(nlevcol, 256), NARR), 256, 0, st>>>(nlevcol, nsplit, out_up, a.flux_up, a.flux_dn,
-                                                                                      a.flux_up_jac);
-    return true;
+    });
 }
 
 // broadband fluxes from tau + (lay_source, lev_source) [LITE = false] or tau + Planck fractions and band Planck functions
@@ -949,18 +935,8 @@ bool launch_bb2(hipStream_t st, const BbArgs<F>& a)
 // [JAC = true: flux_up_jac too, from the same forms in the same order; MU = true: nmus angles, secants (ncol, ngpt, nmus);
 //  OPT = true: secants formed in the kernel from opt_fit (2, nbnd), written to secants_out when it is given]
 template<typename F, bool LITE, bool JAC = false, bool MU = false, bool OPT = false>
-bool lw_fused_broadband(
-        hipStream_t st, const int ncol, const int nlay, const int ngpt, const int top_at_1,
-        const F* secants, const F* weights, const F* tau, const F* lay_source, const F* lev_source,
-        const F* blay, const F* blev, const int* gpoint_bands,
-        const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up, F* flux_dn,
-        const int* band_lims = nullptr, const int nbnd = 0 /* by-band form (launch_bb2) */,
-        const F* sfc_src_jac = nullptr, F* flux_up_jac = nullptr, const int nmus = 1,
-        const F* opt_fit = nullptr, F* secants_out = nullptr)
+bool lw_fused_broadband(hipStream_t st, const BbArgs<F>& a)
 {
-    const BbArgs<F> a{ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source, blay, blev, gpoint_bands,
-                      sfc_emis, sfc_src, inc_flux, flux_up, flux_dn, band_lims, nbnd, sfc_src_jac, flux_up_jac, nmus,
-                      opt_fit, secants_out};
     if constexpr (sizeof(F) == 8)
     {
         // (Round 4 measured six waves x six layers per column group -- 384-thread workgroups, three waves per SIMD, 168 VGPRs with
@@ -984,22 +960,15 @@ bool lw_fused_broadband(
         if (tuning().lw_variant == 15 && launch_bb2<F,1,4,16,LITE,8,JAC,MU,OPT>(st, a)) return true;
         // 16 x 4 lanes with two columns per lane (128-B rows, K = 9) ahead of 8 x 8 lanes with four. Measured at C4 in the fractions
         // form: 1.77 against 3.26 ms (the four-column lane state spills); the latter still takes 144 ... 159 layers.
-        if (ncol % 2 == 0 && launch_bb2<F,2,4,16,LITE,4,JAC,MU,OPT>(st, a)) return true;
-        if (ncol % 4 == 0 && launch_bb2<F,4,4,8,LITE,4,JAC,MU,OPT>(st, a)) return true;
+        if (a.ncol % 2 == 0 && launch_bb2<F,2,4,16,LITE,4,JAC,MU,OPT>(st, a)) return true;
+        if (a.ncol % 4 == 0 && launch_bb2<F,4,4,8,LITE,4,JAC,MU,OPT>(st, a)) return true;
         // 144 ... 287 layers: eight wavefronts per column group
-        if (ncol % 2 == 0 && launch_bb2<F,2,8,16,LITE,8,JAC,MU,OPT>(st, a)) return true;
+        if (a.ncol % 2 == 0 && launch_bb2<F,2,8,16,LITE,8,JAC,MU,OPT>(st, a)) return true;
         // 288 ... 575 layers: eight waves of 8 x 8 lanes (see fp64)
-        if (ncol % 2 == 0 && launch_bb2<F,2,8,8,LITE,8,JAC,MU,OPT>(st, a)) return true;
+        if (a.ncol % 2 == 0 && launch_bb2<F,2,8,8,LITE,8,JAC,MU,OPT>(st, a)) return true;
         // odd column counts: one column per lane
         return launch_bb2<F,1,4,16,LITE,8,JAC,MU,OPT>(st, a);
     }
-}
-
-// the one-kernel broadband forms serve every variant but 1 (serial kernel) and 7 (per-g-point fluxes in a workspace + sum)
-bool lw_fused_allowed()
-{
-    const int v = tuning().lw_variant;
-    return v != 1 && v != 7;
 }
 
 #define RRX_LW_ARGS_CALL ncol, nlay, ngpt, top_at_1, imu, secants, weights, tau, lay_source, lev_source, \
@@ -1028,9 +997,8 @@ int lw_solver_noscat_impl(
     // to fill the chip one workgroup sums all g-points in order (sum_broadband's order); with fewer the g-point range is split
     // over grid.y and the partial sums are added in range order (rrx::broadband_gsplit).
     if (do_broadband && !jac && nmus == 1 && lw_fused_allowed() &&
-        lw_fused_broadband<F,false>(st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source,
-                                    (const F*)nullptr, (const F*)nullptr, (const int*)nullptr, sfc_emis, sfc_src, inc_flux,
-                                    flux_up_loc, flux_dn_loc))
+        lw_fused_broadband<F,false>(st, BbArgs<F>{ncol, nlay, ngpt, top_at_1, secants, weights, tau, lay_source, lev_source, nullptr, nullptr,
+                                                  nullptr, sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc}))
         return 0;
 
     // broadband mode, general form: per-g-point fluxes go to a workspace, then are summed over g-points
@@ -1112,34 +1080,70 @@ int planck_sources_from_fractions_impl(int ncol, int nlay, int ngpt, const int* 
 }
 
 // The fractions entries outside the one-kernel tilings (columns taller than 575 layers, variants 1 and 7): the Planck sources are
-// rebuilt and the general entry writes per-g-point fluxes [up | dn], and the Jacobian behind them when sfc_src_jac is given, into ONE
+// rebuilt and the general entry writes per-g-point fluxes [up | dn], and the Jacobian behind them when a.sfc_src_jac is given, into ONE
 // lease of the stream's workspace: [up | dn | (Jacobian) | lay_source | lev_source]. Returns that block, or null with the message set;
-// the caller sums it while the lease lives. With opt_fit the secants are the optimal-angle ones (one angle), produced by
-// lw_optimal_secants_kernel into secants_out or, when that is null, into (ncol, ngpt) more elements at the end of the lease.
+// the caller sums it while the lease lives. With a.opt_fit the secants are the optimal-angle ones (one angle), produced by
+// lw_optimal_secants_kernel into a.secants_out or, when that is null, into (ncol, ngpt) more elements at the end of the lease.
 template<typename F>
-const F* lw_fractions_per_gpoint(
-        WorkspaceLease& lease, const int ncol, const int nlay, const int ngpt, const Bool top_at_1,
-        const F* secants, const F* weights, const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands,
-        const F* sfc_emis, const F* sfc_src, const F* inc_flux, const F* sfc_src_jac, void* stream, const int nmus = 1,
-        const F* opt_fit = nullptr, const int nbnd = 0, F* secants_out = nullptr)
+const F* lw_fractions_per_gpoint(WorkspaceLease& lease, const BbArgs<F>& a, void* stream)
 {
-    const size_t n_lay = size_t(ncol)*nlay*ngpt, n_lev = size_t(ncol)*(nlay+1)*ngpt;
-    const size_t nout = (sfc_src_jac != nullptr) ? 3 : 2;
-    const size_t n_sec = (opt_fit != nullptr && secants_out == nullptr) ? size_t(ncol)*ngpt : 0;
+    const size_t n_lay = size_t(a.ncol)*a.nlay*a.ngpt, n_lev = size_t(a.ncol)*(a.nlay+1)*a.ngpt;
+    const size_t nout = (a.sfc_src_jac != nullptr) ? 3 : 2;
+    const size_t n_sec = (a.opt_fit != nullptr && a.secants_out == nullptr) ? size_t(a.ncol)*a.ngpt : 0;
     F* ws = lease.get<F>(nout*n_lev + n_lay + n_lev + n_sec);
     F* lay = ws + nout*n_lev; F* lev = lay + n_lay;
-    F* jac = (sfc_src_jac != nullptr) ? ws + 2*n_lev : nullptr;
-    if (opt_fit != nullptr)
+    F* jac = (a.sfc_src_jac != nullptr) ? ws + 2*n_lev : nullptr;
+    const F* secants = a.secants;
+    if (a.opt_fit != nullptr)
     {
-        F* sec = (secants_out != nullptr) ? secants_out : lev + n_lev;
-        if (lw_optimal_secants_impl<F>(ncol, nlay, ngpt, nbnd, gpoint_bands, opt_fit, tau, sec, stream) != 0) return nullptr;
+        F* sec = (a.secants_out != nullptr) ? a.secants_out : lev + n_lev;
+        if (lw_optimal_secants_impl<F>(a.ncol, a.nlay, a.ngpt, a.nbnd, a.gpoint_bands, a.opt_fit, a.tau, sec, stream) != 0) return nullptr;
         secants = sec;
     }
-    if (planck_sources_from_fractions_impl<F>(ncol, nlay, ngpt, gpoint_bands, pfrac, blay, blev, lay, lev, stream) != 0 ||
-        lw_solver_noscat_impl<F>(ncol, nlay, ngpt, top_at_1, nmus, secants, weights, tau, lay, lev, sfc_emis, sfc_src, inc_flux,
-                                 ws, ws + n_lev, Bool(0), (F*)nullptr, (F*)nullptr, Bool(jac != nullptr), sfc_src_jac, jac, stream) != 0)
+    if (planck_sources_from_fractions_impl<F>(a.ncol, a.nlay, a.ngpt, a.gpoint_bands, a.lay_source, a.blay, a.blev, lay, lev, stream) != 0 ||
+        lw_solver_noscat_impl<F>(a.ncol, a.nlay, a.ngpt, a.top_at_1, a.nmus, secants, a.weights, a.tau, lay, lev, a.sfc_emis, a.sfc_src,
+                                 a.inc_flux, ws, ws + n_lev, Bool(0), (F*)nullptr, (F*)nullptr, Bool(jac != nullptr), a.sfc_src_jac, jac,
+                                 stream) != 0)
         return nullptr;
     return ws;
+}
+
+// The solve behind the five fractions entries (plain, _jac, _angles, _optimal, _byband), their argument checks done; a.lay_source is
+// pfrac. What the struct holds chooses the form: the Jacobian pair -> JAC; nmus > 1 -> MU (one angle through the _angles entry is the
+// one-angle form: the same bits); opt_fit -> OPT; band_lims -> the by-band form, a.flux_up / a.flux_dn being the band sums. Exactly
+// these instantiations exist: JAC x {one angle, MU, OPT}, and the by-band form without the other three. The one-kernel form where the
+// variant allows it and a tiling reaches; otherwise the g-point sums (band sums) of lw_fractions_per_gpoint's fluxes and Jacobian,
+// which the general kernel has added up over the angles. False: the message is set.
+template<typename F>
+bool lw_fractions_solve(void* stream, const BbArgs<F>& a)
+{
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool jac = a.sfc_src_jac != nullptr;
+    bool fused = false;
+    if (lw_fused_allowed() && a.band_lims != nullptr) fused = lw_fused_broadband<F,true>(st, a);
+    else if (lw_fused_allowed()) with_flag(jac, [&](auto j)
+    {
+        constexpr bool JAC = decltype(j)::value;
+        if (a.opt_fit != nullptr) fused = lw_fused_broadband<F,true,JAC,false,true>(st, a);
+        else if (a.nmus > 1)      fused = lw_fused_broadband<F,true,JAC,true>(st, a);
+        else                      fused = lw_fused_broadband<F,true,JAC>(st, a);
+    });
+    if (fused) return true;
+
+    WorkspaceLease lease(st);
+    const F* ws = lw_fractions_per_gpoint<F>(lease, a, stream);
+    if (ws == nullptr) return false;
+    const size_t nlevcol = size_t(a.ncol)*(a.nlay+1);
+    const int nb = ceil_div(nlevcol, 256);
+    if (a.band_lims != nullptr)
+        sum_bands_kernel<F><<<dim3(nb, a.nbnd, 2), 256, 0, st>>>(nlevcol, a.ngpt, a.band_lims, ws, a.flux_up, a.flux_dn, (F*)nullptr);
+    else
+    {
+        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, a.ngpt, ws, a.flux_up);
+        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, a.ngpt, ws + nlevcol*a.ngpt, a.flux_dn);
+        if (jac) sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, a.ngpt, ws + 2*nlevcol*a.ngpt, a.flux_up_jac);
+    }
+    return true;
 }
 
 template<typename F>
@@ -1149,28 +1153,15 @@ int lw_solver_noscat_fractions_impl(
         const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up_loc, F* flux_dn_loc, void* stream)
 {
     RRX_TRY
-    hipStream_t st = static_cast<hipStream_t>(stream);
     if (ncol <= 0 || nlay <= 0 || ngpt <= 0) throw std::runtime_error("empty problem");
     if (flux_up_loc == nullptr || flux_dn_loc == nullptr) throw std::runtime_error("broadband outputs missing");
-    const bool fused = lw_fused_allowed() &&
-        lw_fused_broadband<F,true>(st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, (const F*)nullptr,
-                                   blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc);
-    if (!fused)
-    {
-        WorkspaceLease lease(st);
-        const F* ws = lw_fractions_per_gpoint<F>(lease, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, blay, blev,
-                                                 gpoint_bands, sfc_emis, sfc_src, inc_flux, (const F*)nullptr, stream);
-        if (ws == nullptr) return 1;                                 // (the message is set)
-        const size_t nlevcol = size_t(ncol)*(nlay+1);
-        const int nb = ceil_div(nlevcol, 256);
-        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws, flux_up_loc);
-        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws + nlevcol*ngpt, flux_dn_loc);
-    }
+    if (!lw_fractions_solve<F>(stream, {ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, nullptr, blay, blev, gpoint_bands,
+                                        sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc}))
+        return 1;                                                    // (the message is set)
     RRX_CATCH("rrx_lw_solver_noscat_fractions")
 }
 
-// fluxes and the surface-temperature Jacobian of the upward flux (rrx_lw_solver_noscat_fractions_jac): the one-kernel form's JAC
-// variant where the tilings reach, otherwise the g-point sums of lw_fractions_per_gpoint's fluxes and Jacobian
+// fluxes and the surface-temperature Jacobian of the upward flux (rrx_lw_solver_noscat_fractions_jac)
 template<typename F>
 int lw_solver_noscat_fractions_jac_impl(
         const int ncol, const int nlay, const int ngpt, const Bool top_at_1,
@@ -1179,33 +1170,17 @@ int lw_solver_noscat_fractions_jac_impl(
         void* stream)
 {
     RRX_TRY
-    hipStream_t st = static_cast<hipStream_t>(stream);
     if (ncol <= 0 || nlay <= 0 || ngpt <= 0) throw std::runtime_error("empty problem");
     if (flux_up_loc == nullptr || flux_dn_loc == nullptr) throw std::runtime_error("broadband outputs missing");
     if (sfc_src_jac == nullptr) throw std::runtime_error("sfc_src_jac is null");
     if (flux_up_jac == nullptr) throw std::runtime_error("flux_up_jac is null");
-    const bool fused = lw_fused_allowed() &&
-        lw_fused_broadband<F,true,true>(st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, (const F*)nullptr,
-                                        blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc,
-                                        (const int*)nullptr, 0, sfc_src_jac, flux_up_jac);
-    if (!fused)
-    {
-        WorkspaceLease lease(st);
-        const F* ws = lw_fractions_per_gpoint<F>(lease, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, blay, blev,
-                                                 gpoint_bands, sfc_emis, sfc_src, inc_flux, sfc_src_jac, stream);
-        if (ws == nullptr) return 1;                                 // (the message is set)
-        const size_t nlevcol = size_t(ncol)*(nlay+1);
-        const int nb = ceil_div(nlevcol, 256);
-        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws, flux_up_loc);
-        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws + nlevcol*ngpt, flux_dn_loc);
-        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws + 2*nlevcol*ngpt, flux_up_jac);
-    }
+    if (!lw_fractions_solve<F>(stream, {ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, nullptr, blay, blev, gpoint_bands,
+                                        sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc, sfc_src_jac, flux_up_jac}))
+        return 1;                                                    // (the message is set)
     RRX_CATCH("rrx_lw_solver_noscat_fractions_jac")
 }
 
-// nmus = 1..4 quadrature angles (rrx_lw_solver_noscat_fractions_angles), with the Jacobian when the pair is given: one angle is the
-// one-angle entries themselves (the same bits); more take the one-kernel form's MU variant where the tilings reach, otherwise the
-// g-point sums of lw_fractions_per_gpoint's fluxes, which the general kernel has added up over the angles
+// nmus = 1..4 quadrature angles (rrx_lw_solver_noscat_fractions_angles), with the Jacobian when the pair is given
 template<typename F>
 int lw_solver_noscat_fractions_angles_impl(
         const int ncol, const int nlay, const int ngpt, const Bool top_at_1, const int nmus,
@@ -1225,40 +1200,15 @@ int lw_solver_noscat_fractions_angles_impl(
     else if (sfc_src_jac != nullptr && flux_up_jac == nullptr) bad = "flux_up_jac is null while sfc_src_jac is given";
     else if (sfc_src_jac == nullptr && flux_up_jac != nullptr) bad = "sfc_src_jac is null while flux_up_jac is given";
     if (bad != nullptr) { set_error(std::string(entry) + ": " + bad); return 1; }
-    const bool jac = sfc_src_jac != nullptr;
-    if (nmus == 1)
-        return jac ? lw_solver_noscat_fractions_jac_impl<F>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, blay, blev, gpoint_bands,
-                                                            sfc_emis, sfc_src, inc_flux, sfc_src_jac, flux_up_loc, flux_dn_loc, flux_up_jac, stream)
-                   : lw_solver_noscat_fractions_impl<F>(ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, blay, blev, gpoint_bands,
-                                                        sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc, stream);
     RRX_TRY
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    bool fused = false;
-    if (lw_fused_allowed())
-        with_flag(jac, [&](auto j)
-        {
-            fused = lw_fused_broadband<F,true,decltype(j)::value,true>(
-                        st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, (const F*)nullptr, blay, blev, gpoint_bands,
-                        sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc, (const int*)nullptr, 0, sfc_src_jac, flux_up_jac, nmus);
-        });
-    if (!fused)
-    {
-        WorkspaceLease lease(st);
-        const F* ws = lw_fractions_per_gpoint<F>(lease, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, blay, blev,
-                                                 gpoint_bands, sfc_emis, sfc_src, inc_flux, sfc_src_jac, stream, nmus);
-        if (ws == nullptr) return 1;                                 // (the message is set)
-        const size_t nlevcol = size_t(ncol)*(nlay+1);
-        const int nb = ceil_div(nlevcol, 256);
-        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws, flux_up_loc);
-        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws + nlevcol*ngpt, flux_dn_loc);
-        if (jac) sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws + 2*nlevcol*ngpt, flux_up_jac);
-    }
+    if (!lw_fractions_solve<F>(stream, {ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, nullptr, blay, blev, gpoint_bands,
+                                        sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc, sfc_src_jac, flux_up_jac, nmus}))
+        return 1;                                                    // (the message is set)
     RRX_CATCH(entry)
 }
 
 // One angle whose secant is the optimal-angle fit of the column's total optical depth (rrx_lw_solver_noscat_fractions_optimal), with
-// the Jacobian when the pair is given: the one-kernel form's OPT variant where the tilings reach, otherwise lw_optimal_secants_kernel
-// and the g-point sums of lw_fractions_per_gpoint's fluxes for those secants
+// the Jacobian when the pair is given
 template<typename F>
 int lw_solver_noscat_fractions_optimal_impl(
         const int ncol, const int nlay, const int ngpt, const int nbnd, const Bool top_at_1, const F* weights,
@@ -1280,31 +1230,11 @@ int lw_solver_noscat_fractions_optimal_impl(
     else if (sfc_src_jac != nullptr && flux_up_jac == nullptr) bad = "flux_up_jac is null while sfc_src_jac is given";
     else if (sfc_src_jac == nullptr && flux_up_jac != nullptr) bad = "sfc_src_jac is null while flux_up_jac is given";
     if (bad != nullptr) { set_error(std::string(entry) + ": " + bad); return 1; }
-    const bool jac = sfc_src_jac != nullptr;
     RRX_TRY
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    bool fused = false;
-    if (lw_fused_allowed())
-        with_flag(jac, [&](auto j)
-        {
-            fused = lw_fused_broadband<F,true,decltype(j)::value,false,true>(
-                        st, ncol, nlay, ngpt, top_at_1, (const F*)nullptr, weights, tau, pfrac, (const F*)nullptr, blay, blev, gpoint_bands,
-                        sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc, (const int*)nullptr, 0, sfc_src_jac, flux_up_jac, 1,
-                        optimal_angle_fit, secants_out);
-        });
-    if (!fused)
-    {
-        WorkspaceLease lease(st);
-        const F* ws = lw_fractions_per_gpoint<F>(lease, ncol, nlay, ngpt, top_at_1, (const F*)nullptr, weights, tau, pfrac, blay, blev,
-                                                 gpoint_bands, sfc_emis, sfc_src, inc_flux, sfc_src_jac, stream, 1,
-                                                 optimal_angle_fit, nbnd, secants_out);
-        if (ws == nullptr) return 1;                                 // (the message is set)
-        const size_t nlevcol = size_t(ncol)*(nlay+1);
-        const int nb = ceil_div(nlevcol, 256);
-        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws, flux_up_loc);
-        sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws + nlevcol*ngpt, flux_dn_loc);
-        if (jac) sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, ws + 2*nlevcol*ngpt, flux_up_jac);
-    }
+    if (!lw_fractions_solve<F>(stream, {ncol, nlay, ngpt, top_at_1, nullptr, weights, tau, pfrac, nullptr, blay, blev, gpoint_bands,
+                                        sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc, sfc_src_jac, flux_up_jac, 1,
+                                        optimal_angle_fit, secants_out, nullptr, nbnd}))
+        return 1;                                                    // (the message is set)
     RRX_CATCH(entry)
 }
 
@@ -1337,8 +1267,7 @@ int lw_flux_up_adjust_impl(const int ncol, const int nlev, const F* flux_up_jac,
     RRX_CATCH("rrx_lw_flux_up_adjust")
 }
 
-// by-band fluxes (rrx_lw_solver_noscat_fractions_byband): the one-kernel form with one band per workgroup where the tilings reach,
-// otherwise the band sums of lw_fractions_per_gpoint's fluxes. Band net and broadband outputs come from the band sums in one more pass.
+// by-band fluxes (rrx_lw_solver_noscat_fractions_byband). Band net and broadband outputs come from the band sums in one more pass.
 template<typename F>
 int lw_solver_noscat_fractions_byband_impl(
         const int ncol, const int nlay, const int ngpt, const int nbnd, const Bool top_at_1,
@@ -1347,24 +1276,14 @@ int lw_solver_noscat_fractions_byband_impl(
         F* bnd_up, F* bnd_dn, F* bnd_net, F* flux_up, F* flux_dn, void* stream)
 {
     RRX_TRY
-    hipStream_t st = static_cast<hipStream_t>(stream);
     check_byband_args(ncol, nlay, ngpt, nbnd, band_lims);
     if (gpoint_bands == nullptr) throw std::runtime_error("gpoint_bands is null");
     if (bnd_up == nullptr || bnd_dn == nullptr) throw std::runtime_error("band flux outputs missing");
-    const size_t nlevcol = size_t(ncol)*(nlay+1);
-    const bool fused = lw_fused_allowed() &&
-        lw_fused_broadband<F,true>(st, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, (const F*)nullptr,
-                                   blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux, bnd_up, bnd_dn, band_lims, nbnd);
-    if (!fused)
-    {
-        WorkspaceLease lease(st);
-        const F* ws = lw_fractions_per_gpoint<F>(lease, ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, blay, blev,
-                                                 gpoint_bands, sfc_emis, sfc_src, inc_flux, (const F*)nullptr, stream);
-        if (ws == nullptr) return 1;                                 // (the message is set)
-        sum_bands_kernel<F><<<dim3(ceil_div(nlevcol, 256), nbnd, 2), 256, 0, st>>>(nlevcol, ngpt, band_lims, ws, bnd_up, bnd_dn,
-                                                                                      (F*)nullptr);
-    }
-    launch_byband_outputs<F,2>(st, nlevcol, nbnd, bnd_up, bnd_dn, (const F*)nullptr, bnd_net, flux_up, flux_dn, (F*)nullptr);
+    if (!lw_fractions_solve<F>(stream, {ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, nullptr, blay, blev, gpoint_bands,
+                                        sfc_emis, sfc_src, inc_flux, bnd_up, bnd_dn, nullptr, nullptr, 1, nullptr, nullptr, band_lims, nbnd}))
+        return 1;                                                    // (the message is set)
+    launch_byband_outputs<F,2>(static_cast<hipStream_t>(stream), size_t(ncol)*(nlay+1), nbnd, bnd_up, bnd_dn, (const F*)nullptr,
+                               bnd_net, flux_up, flux_dn, (F*)nullptr);
     RRX_CATCH("rrx_lw_solver_noscat_fractions_byband")
 }
 }  // namespace

@@ -17,8 +17,6 @@
 #include "rrx_common.h"
 #include "rrx_hip.h"
 #include <type_traits>
-#include <initializer_list>
-#include <utility>
 
 #pragma clang fp contract(fast)
 
@@ -430,26 +428,15 @@ bool launch_lw1r(hipStream_t st, const Lw1rArgs<F>& a)
         if constexpr (NW == 4) return with_k<2, 4, 6, 9>(need, launch);
         else return with_k<5, 7, 9>(need, launch);
     };
-    // few column groups: the g-point loop is split over grid.y, partial sums added in range order afterwards
-    const int gper = ceil_div(a.ngpt, broadband_gsplit(groups, a.ngpt, (NW > 4) ? 256 : 512));
-    const int nsplit = ceil_div(a.ngpt, gper);             // no empty range: every workgroup's first g-point exists (it is prefetched)
+    // few column groups: the g-point loop is split over grid.y (rrx::launch_gsplit)
     const size_t nlevcol = size_t(a.ncol)*(a.nlay+1);
-    StreamScratch scratch(st);
-    F* up = a.flux_up; F* dn = a.flux_dn;
-    const dim3 grid(groups, nsplit);
-    const bool fits = with_tiling_k([&](auto kk)
+    return launch_gsplit<F,2>(st, groups, a.ngpt, (NW > 4) ? 256 : 512, nlevcol, a.flux_up, a.flux_dn, (F*)nullptr, with_tiling_k,
+        [&](auto kk, auto gs, const dim3 grid, const int gper, F* up, F* dn, F*)
     {
-        if (nsplit > 1) { up = scratch.get<F>(2*nsplit*nlevcol); dn = up + nsplit*nlevcol; }
-        with_flag(nsplit > 1, [&](auto gs)
-        {
-            lw_rescaled_bb_kernel<F,decltype(kk)::value,W,NW,CLT,decltype(gs)::value><<<grid, 64*NW, 0, st>>>(
-                a.ncol, a.nlay, a.ngpt, a.top_at_1, a.secants, a.weights, a.tau, a.pfrac, a.blay, a.blev, a.gpoint_bands,
-                a.cld_tau, a.cld_ssa, a.cld_g, a.sfc_emis, a.sfc_src, a.inc_flux, up, dn, gper, nlevcol);
-        });
+        lw_rescaled_bb_kernel<F,decltype(kk)::value,W,NW,CLT,decltype(gs)::value><<<grid, 64*NW, 0, st>>>(
+            a.ncol, a.nlay, a.ngpt, a.top_at_1, a.secants, a.weights, a.tau, a.pfrac, a.blay, a.blev, a.gpoint_bands,
+            a.cld_tau, a.cld_ssa, a.cld_g, a.sfc_emis, a.sfc_src, a.inc_flux, up, dn, gper, nlevcol);
     });
-    if (fits && nsplit > 1)      // (up, dn lie behind each other in the scratch block)
-        sum_ranges_kernel<F,2><<<dim3(ceil_div(nlevcol, 256), 2), 256, 0, st>>>(nlevcol, nsplit, up, a.flux_up, a.flux_dn, (F*)nullptr);
-    return fits;
 }
 
 // the fused kernels in the order of preference; false when no form takes the shape
@@ -472,22 +459,6 @@ bool lw1r_fused(hipStream_t st, const Lw1rArgs<F>& a)
         if (launch_lw1r<F,8,16,8>(st, a)) return true;
         return launch_lw1r<F,8,8,8>(st, a);
     }
-}
-
-// argument checks shared by the two entries (as rrx_lw_solver_2stream's): throws with the argument's name, returns true for an empty
-// problem (nothing to do)
-bool lw1r_empty(std::initializer_list<std::pair<const char*, int>> extents, std::initializer_list<std::pair<const char*, const void*>> required)
-{
-    bool empty = false;
-    for (const auto& e : extents)
-    {
-        if (e.second < 0) throw std::runtime_error(std::string(e.first) + " is negative");
-        if (e.second == 0) empty = true;
-    }
-    if (empty) return true;
-    for (const auto& p : required)
-        if (p.second == nullptr) throw std::runtime_error(std::string(p.first) + " is null");
-    return false;
 }
 
 template<typename F>
@@ -545,16 +516,16 @@ int lw_solver_noscat_rescaled_impl(
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (do_broadband)
     {
-        if (lw1r_empty({{"ncol", ncol}, {"nlay", nlay}, {"ngpt", ngpt}},
-                       {{"secants", secants}, {"weights", weights}, {"tau", tau}, {"ssa", ssa}, {"g", g}, {"lay_source", lay_source},
-                        {"lev_source", lev_source}, {"sfc_emis", sfc_emis}, {"sfc_src", sfc_src},
-                        {"flux_up_loc", flux_up_loc}, {"flux_dn_loc", flux_dn_loc}}))
+        if (empty_problem({{"ncol", ncol}, {"nlay", nlay}, {"ngpt", ngpt}},
+                          {{"secants", secants}, {"weights", weights}, {"tau", tau}, {"ssa", ssa}, {"g", g}, {"lay_source", lay_source},
+                           {"lev_source", lev_source}, {"sfc_emis", sfc_emis}, {"sfc_src", sfc_src},
+                           {"flux_up_loc", flux_up_loc}, {"flux_dn_loc", flux_dn_loc}}))
             return 0;
     }
-    else if (lw1r_empty({{"ncol", ncol}, {"nlay", nlay}, {"ngpt", ngpt}},
-                        {{"secants", secants}, {"weights", weights}, {"tau", tau}, {"ssa", ssa}, {"g", g}, {"lay_source", lay_source},
-                         {"lev_source", lev_source}, {"sfc_emis", sfc_emis}, {"sfc_src", sfc_src},
-                         {"flux_up", flux_up}, {"flux_dn", flux_dn}}))
+    else if (empty_problem({{"ncol", ncol}, {"nlay", nlay}, {"ngpt", ngpt}},
+                           {{"secants", secants}, {"weights", weights}, {"tau", tau}, {"ssa", ssa}, {"g", g}, {"lay_source", lay_source},
+                            {"lev_source", lev_source}, {"sfc_emis", sfc_emis}, {"sfc_src", sfc_src},
+                            {"flux_up", flux_up}, {"flux_dn", flux_dn}}))
         return 0;
     if (nmus < 1 || nmus > 4) throw std::runtime_error("n_quad_angs must be 1..4");
     const bool jac = do_jacobians && sfc_src_jac != nullptr && flux_up_jac != nullptr;
@@ -564,26 +535,6 @@ int lw_solver_noscat_rescaled_impl(
     const size_t n = lw1r_workspace(a);
     lw1r_general<F>(st, a, n > 0 ? lease.get<F>(n) : nullptr);
     RRX_CATCH("rrx_lw_solver_noscat_rescaled")
-}
-
-int inc_bybnd(int ncol, int nlay, int ngpt, double* t, double* w, double* g, const double* t2, const double* w2, const double* g2, int nbnd,
-              const int* lims, void* stream)
-{ return rrx_inc_2stream_by_2stream_bybnd_f64(ncol, nlay, ngpt, t, w, g, t2, w2, g2, nbnd, lims, stream); }
-int inc_bybnd(int ncol, int nlay, int ngpt, float* t, float* w, float* g, const float* t2, const float* w2, const float* g2, int nbnd,
-              const int* lims, void* stream)
-{ return rrx_inc_2stream_by_2stream_bybnd_f32(ncol, nlay, ngpt, t, w, g, t2, w2, g2, nbnd, lims, stream); }
-int planck_sources(int ncol, int nlay, int ngpt, const int* gb, const double* pf, const double* bl, const double* bv, double* ls, double* vs,
-                   void* stream)
-{ return rrx_planck_sources_from_fractions_f64(ncol, nlay, ngpt, gb, pf, bl, bv, ls, vs, stream); }
-int planck_sources(int ncol, int nlay, int ngpt, const int* gb, const float* pf, const float* bl, const float* bv, float* ls, float* vs,
-                   void* stream)
-{ return rrx_planck_sources_from_fractions_f32(ncol, nlay, ngpt, gb, pf, bl, bv, ls, vs, stream); }
-
-// the fused kernels serve every LW variant but 1 (serial kernels) and 7 (per-g-point fluxes in a workspace + sum)
-bool lw1r_fused_allowed()
-{
-    const int v = tuning().lw_variant;
-    return v != 1 && v != 7;
 }
 
 template<typename F>
@@ -596,10 +547,10 @@ int lw_solver_noscat_fractions_rescaled_impl(
     const char* entry = "rrx_lw_solver_noscat_fractions_rescaled";
     RRX_TRY
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (lw1r_empty({{"ncol", ncol}, {"nlay", nlay}, {"ngpt", ngpt}, {"nbnd", nbnd}},
-                   {{"secants", secants}, {"weights", weights}, {"tau", tau}, {"pfrac", pfrac}, {"blay", blay}, {"blev", blev},
-                    {"gpoint_bands", gpoint_bands}, {"band_lims_gpt", band_lims}, {"sfc_emis", sfc_emis}, {"sfc_src", sfc_src},
-                    {"flux_up", flux_up}, {"flux_dn", flux_dn}}))
+    if (empty_problem({{"ncol", ncol}, {"nlay", nlay}, {"ngpt", ngpt}, {"nbnd", nbnd}},
+                      {{"secants", secants}, {"weights", weights}, {"tau", tau}, {"pfrac", pfrac}, {"blay", blay}, {"blev", blev},
+                       {"gpoint_bands", gpoint_bands}, {"band_lims_gpt", band_lims}, {"sfc_emis", sfc_emis}, {"sfc_src", sfc_src},
+                       {"flux_up", flux_up}, {"flux_dn", flux_dn}}))
         return 0;
     const int ncld = (cld_tau != nullptr) + (cld_ssa != nullptr) + (cld_g != nullptr);
     if (ncld != 0 && ncld != 3)
@@ -607,7 +558,7 @@ int lw_solver_noscat_fractions_rescaled_impl(
                                  " is null while another cloud array is given (cld_tau, cld_ssa, cld_g: all three or none)");
     const Lw1rArgs<F> a{ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, blay, blev, gpoint_bands, cld_tau, cld_ssa, cld_g,
                         sfc_emis, sfc_src, inc_flux, flux_up, flux_dn};
-    if (lw1r_fused_allowed() && lw1r_fused<F>(st, a)) return check_launch(entry);
+    if (lw_fused_allowed() && lw1r_fused<F>(st, a)) return check_launch(entry);
 
     // outside the tilings (and LW variants 1, 7): the combined g-point properties and the sources are materialised in ONE lease of
     // the stream's workspace, [the general solve's part | tau | ssa | g | lay_source | lev_source], and the general kernel solves them
@@ -618,11 +569,7 @@ int lw_solver_noscat_fractions_rescaled_impl(
     WorkspaceLease lease(st);
     F* ws = lease.get<F>(n_gen + 4*n_lay + n_lev);
     F* c_tau = ws + n_gen; F* c_ssa = c_tau + n_lay; F* c_g = c_ssa + n_lay; F* lay = c_g + n_lay; F* lev = lay + n_lay;
-    if (hipMemcpyAsync(c_tau, tau, n_lay*sizeof(F), hipMemcpyDeviceToDevice, st) != hipSuccess ||
-        hipMemsetAsync(c_ssa, 0, 2*n_lay*sizeof(F), st) != hipSuccess)
-        throw std::runtime_error("workspace fill failed");
-    if (ncld == 3 && inc_bybnd(ncol, nlay, ngpt, c_tau, c_ssa, c_g, cld_tau, cld_ssa, cld_g, nbnd, band_lims, stream) != 0)
-        throw std::runtime_error(std::string("combining gas and cloud failed: ") + rrx_last_error());
+    gas_plus_cloud<F>(stream, ncol, nlay, ngpt, nbnd, band_lims, tau, cld_tau, cld_ssa, cld_g, c_tau);
     if (planck_sources(ncol, nlay, ngpt, gpoint_bands, pfrac, blay, blev, lay, lev, stream) != 0)
         throw std::runtime_error(std::string("forming the sources failed: ") + rrx_last_error());
     ga.tau = c_tau; ga.ssa = c_ssa; ga.g = c_g; ga.lay_source = lay; ga.lev_source = lev;

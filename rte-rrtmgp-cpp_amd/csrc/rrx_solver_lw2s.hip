@@ -17,8 +17,6 @@
 #include "rrx_common.h"
 #include "rrx_hip.h"
 #include <type_traits>
-#include <initializer_list>
-#include <utility>
 
 #pragma clang fp contract(fast)
 
@@ -490,26 +488,15 @@ bool launch_lw2s(hipStream_t st, const Lw2sArgs<F>& a)
         else if constexpr (W == 8) return with_k<5, 7, 9>(need, launch);
         else return with_k<9>(need, launch);
     };
-    // few column groups: the g-point loop is split over grid.y, partial sums added in range order afterwards
-    const int gper = ceil_div(a.ngpt, broadband_gsplit(groups, a.ngpt, (NW > 4) ? 256 : 512));
-    const int nsplit = ceil_div(a.ngpt, gper);             // no empty range: every workgroup's first g-point exists (it is prefetched)
+    // few column groups: the g-point loop is split over grid.y (rrx::launch_gsplit)
     const size_t nlevcol = size_t(a.ncol)*(a.nlay+1);
-    StreamScratch scratch(st);
-    F* up = a.flux_up; F* dn = a.flux_dn;
-    const dim3 grid(groups, nsplit);
-    const bool fits = with_tiling_k([&](auto kk)
+    return launch_gsplit<F,2>(st, groups, a.ngpt, (NW > 4) ? 256 : 512, nlevcol, a.flux_up, a.flux_dn, (F*)nullptr, with_tiling_k,
+        [&](auto kk, auto gs, const dim3 grid, const int gper, F* up, F* dn, F*)
     {
-        if (nsplit > 1) { up = scratch.get<F>(2*nsplit*nlevcol); dn = up + nsplit*nlevcol; }
-        with_flag(nsplit > 1, [&](auto gs)
-        {
-            lw_2stream_bb_kernel<F,decltype(kk)::value,W,NW,CLT,decltype(gs)::value><<<grid, 64*NW, 0, st>>>(
-                a.ncol, a.nlay, a.ngpt, a.top_at_1, a.tau, a.pfrac, a.blev, a.gpoint_bands, a.cld_tau, a.cld_ssa, a.cld_g,
-                a.sfc_emis, a.sfc_src, a.inc_flux, up, dn, gper, nlevcol);
-        });
+        lw_2stream_bb_kernel<F,decltype(kk)::value,W,NW,CLT,decltype(gs)::value><<<grid, 64*NW, 0, st>>>(
+            a.ncol, a.nlay, a.ngpt, a.top_at_1, a.tau, a.pfrac, a.blev, a.gpoint_bands, a.cld_tau, a.cld_ssa, a.cld_g,
+            a.sfc_emis, a.sfc_src, a.inc_flux, up, dn, gper, nlevcol);
     });
-    if (fits && nsplit > 1)      // (up, dn lie behind each other in the scratch block)
-        sum_ranges_kernel<F,2><<<dim3(ceil_div(nlevcol, 256), 2), 256, 0, st>>>(nlevcol, nsplit, up, a.flux_up, a.flux_dn, (F*)nullptr);
-    return fits;
 }
 
 // the fused kernels in the order of preference; false when no form takes the shape
@@ -535,21 +522,6 @@ bool lw2s_fused(hipStream_t st, const Lw2sArgs<F>& a)
     }
 }
 
-// argument checks shared by the two entries: throws with the argument's name, returns true for an empty problem (nothing to do)
-bool lw2s_empty(std::initializer_list<std::pair<const char*, int>> extents, std::initializer_list<std::pair<const char*, const void*>> required)
-{
-    bool empty = false;
-    for (const auto& e : extents)
-    {
-        if (e.second < 0) throw std::runtime_error(std::string(e.first) + " is negative");
-        if (e.second == 0) empty = true;
-    }
-    if (empty) return true;
-    for (const auto& p : required)
-        if (p.second == nullptr) throw std::runtime_error(std::string(p.first) + " is null");
-    return false;
-}
-
 template<typename F>
 int lw_solver_2stream_impl(
         const int ncol, const int nlay, const int ngpt, const Bool top_at_1,
@@ -560,14 +532,14 @@ int lw_solver_2stream_impl(
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (do_broadband)
     {
-        if (lw2s_empty({{"ncol", ncol}, {"nlay", nlay}, {"ngpt", ngpt}},
-                       {{"tau", tau}, {"ssa", ssa}, {"g", g}, {"lev_source", lev_source}, {"sfc_emis", sfc_emis}, {"sfc_src", sfc_src},
-                        {"flux_up_loc", flux_up_loc}, {"flux_dn_loc", flux_dn_loc}}))
+        if (empty_problem({{"ncol", ncol}, {"nlay", nlay}, {"ngpt", ngpt}},
+                          {{"tau", tau}, {"ssa", ssa}, {"g", g}, {"lev_source", lev_source}, {"sfc_emis", sfc_emis}, {"sfc_src", sfc_src},
+                           {"flux_up_loc", flux_up_loc}, {"flux_dn_loc", flux_dn_loc}}))
             return 0;
     }
-    else if (lw2s_empty({{"ncol", ncol}, {"nlay", nlay}, {"ngpt", ngpt}},
-                        {{"tau", tau}, {"ssa", ssa}, {"g", g}, {"lev_source", lev_source}, {"sfc_emis", sfc_emis}, {"sfc_src", sfc_src},
-                         {"flux_up", flux_up}, {"flux_dn", flux_dn}}))
+    else if (empty_problem({{"ncol", ncol}, {"nlay", nlay}, {"ngpt", ngpt}},
+                           {{"tau", tau}, {"ssa", ssa}, {"g", g}, {"lev_source", lev_source}, {"sfc_emis", sfc_emis}, {"sfc_src", sfc_src},
+                            {"flux_up", flux_up}, {"flux_dn", flux_dn}}))
         return 0;
     // broadband mode: per-g-point fluxes go to the stream's workspace (the caller's flux_up / flux_dn when it gives both), then are summed
     const size_t nlevcol = size_t(ncol)*(nlay+1);
@@ -585,20 +557,6 @@ int lw_solver_2stream_impl(
     RRX_CATCH(entry)
 }
 
-int inc_bybnd(int ncol, int nlay, int ngpt, double* t, double* w, double* g, const double* t2, const double* w2, const double* g2, int nbnd,
-              const int* lims, void* stream)
-{ return rrx_inc_2stream_by_2stream_bybnd_f64(ncol, nlay, ngpt, t, w, g, t2, w2, g2, nbnd, lims, stream); }
-int inc_bybnd(int ncol, int nlay, int ngpt, float* t, float* w, float* g, const float* t2, const float* w2, const float* g2, int nbnd,
-              const int* lims, void* stream)
-{ return rrx_inc_2stream_by_2stream_bybnd_f32(ncol, nlay, ngpt, t, w, g, t2, w2, g2, nbnd, lims, stream); }
-
-// the fused kernels serve every LW variant but 1 (serial kernels) and 7 (per-g-point fluxes in a workspace + sum)
-bool lw2s_fused_allowed()
-{
-    const int v = tuning().lw_variant;
-    return v != 1 && v != 7;
-}
-
 template<typename F>
 int lw_solver_2stream_fractions_impl(
         const int ncol, const int nlay, const int ngpt, const int nbnd, const Bool top_at_1,
@@ -609,9 +567,9 @@ int lw_solver_2stream_fractions_impl(
     const char* entry = "rrx_lw_solver_2stream_fractions";
     RRX_TRY
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (lw2s_empty({{"ncol", ncol}, {"nlay", nlay}, {"ngpt", ngpt}, {"nbnd", nbnd}},
-                   {{"tau", tau}, {"pfrac", pfrac}, {"blev", blev}, {"gpoint_bands", gpoint_bands}, {"band_lims_gpt", band_lims},
-                    {"sfc_emis", sfc_emis}, {"sfc_src", sfc_src}, {"flux_up", flux_up}, {"flux_dn", flux_dn}}))
+    if (empty_problem({{"ncol", ncol}, {"nlay", nlay}, {"ngpt", ngpt}, {"nbnd", nbnd}},
+                      {{"tau", tau}, {"pfrac", pfrac}, {"blev", blev}, {"gpoint_bands", gpoint_bands}, {"band_lims_gpt", band_lims},
+                       {"sfc_emis", sfc_emis}, {"sfc_src", sfc_src}, {"flux_up", flux_up}, {"flux_dn", flux_dn}}))
         return 0;
     const int ncld = (cld_tau != nullptr) + (cld_ssa != nullptr) + (cld_g != nullptr);
     if (ncld != 0 && ncld != 3)
@@ -619,7 +577,7 @@ int lw_solver_2stream_fractions_impl(
                                  " is null while another cloud array is given (cld_tau, cld_ssa, cld_g: all three or none)");
     const Lw2sArgs<F> a{ncol, nlay, ngpt, top_at_1, tau, pfrac, blev, gpoint_bands, cld_tau, cld_ssa, cld_g, sfc_emis, sfc_src, inc_flux,
                         flux_up, flux_dn};
-    if (lw2s_fused_allowed() && lw2s_fused<F>(st, a)) return check_launch(entry);
+    if (lw_fused_allowed() && lw2s_fused<F>(st, a)) return check_launch(entry);
 
     // outside the tilings (and LW variants 1, 7): the combined g-point properties and the level sources are materialised in ONE
     // lease of the stream's workspace, [up | dn | tau | ssa | g | lev_source], and the general kernel solves them
@@ -627,11 +585,7 @@ int lw_solver_2stream_fractions_impl(
     WorkspaceLease lease(st);
     F* ws = lease.get<F>(2*n_lev + 3*n_lay + n_lev);
     F* c_tau = ws + 2*n_lev; F* c_ssa = c_tau + n_lay; F* c_g = c_ssa + n_lay; F* lev = c_g + n_lay;
-    if (hipMemcpyAsync(c_tau, tau, n_lay*sizeof(F), hipMemcpyDeviceToDevice, st) != hipSuccess ||
-        hipMemsetAsync(c_ssa, 0, 2*n_lay*sizeof(F), st) != hipSuccess)
-        throw std::runtime_error("workspace fill failed");
-    if (ncld == 3 && inc_bybnd(ncol, nlay, ngpt, c_tau, c_ssa, c_g, cld_tau, cld_ssa, cld_g, nbnd, band_lims, stream) != 0)
-        throw std::runtime_error(std::string("combining gas and cloud failed: ") + rrx_last_error());      // (named after this entry below)
+    gas_plus_cloud<F>(stream, ncol, nlay, ngpt, nbnd, band_lims, tau, cld_tau, cld_ssa, cld_g, c_tau);      // (a failure is named after this entry below)
     lw2s_level_sources_kernel<F><<<int(std::min<size_t>((n_lev + 255)/256, 256*16)), 256, 0, st>>>(ncol, nlay, ngpt, gpoint_bands, pfrac, blev, lev);
     if (lw_solver_2stream_impl<F>(ncol, nlay, ngpt, top_at_1, c_tau, c_ssa, c_g, lev, sfc_emis, sfc_src, inc_flux, ws, ws + n_lev,
                                   Bool(1), flux_up, flux_dn, stream, entry) != 0)

@@ -814,25 +814,18 @@ bool launch_scan_bb(hipStream_t st, const SwArgs<F>& a)
                 a.flux_up, a.flux_dn, a.flux_dir, sync_waves, 0, a.band_lims);
         }); });
     }
-    // few column groups: the g-point loop is split over grid.y, partial sums added in range order afterwards
-    const int gper = ceil_div(a.ngpt, broadband_gsplit(groups, a.ngpt, (NW > 4) ? 256 : ((CLT == 16) ? 256*RRX_SW_F32_WAVES1 : 512)));      // (one or two workgroups per CU)
-    const int nsplit = ceil_div(a.ngpt, gper);             // no empty range: every workgroup's first g-point exists (it is prefetched)
-    StreamScratch scratch(st);
-    F* up = a.flux_up; F* dn = a.flux_dn; F* dr = a.flux_dir;
-    const dim3 grid(groups, nsplit);
-    const bool fits = with_tiling_k([&](auto kk)
+    // few column groups: the g-point loop is split over grid.y (rrx::launch_gsplit; one or two workgroups per CU)
+    return launch_gsplit<F,3>(st, groups, a.ngpt, (NW > 4) ? 256 : ((CLT == 16) ? 256*RRX_SW_F32_WAVES1 : 512), nlevcol,
+                              a.flux_up, a.flux_dn, a.flux_dir, with_tiling_k,
+        [&](auto kk, auto gs, const dim3 grid, const int gper, F* up, F* dn, F* dr)
     {
-        if (nsplit > 1) { up = scratch.get<F>(3*nsplit*nlevcol); dn = up + nsplit*nlevcol; dr = dn + nsplit*nlevcol; }
-        with_gz_pre([&](auto gz, auto pre) { with_flag(nsplit > 1, [&](auto gs)
+        with_gz_pre([&](auto gz, auto pre)
         {
             sw_2stream_scan_kernel<F,V,decltype(kk)::value,W,true,decltype(gz)::value,decltype(pre)::value,decltype(gs)::value,NW,CLT><<<grid, 64*NW, 0, st>>>(
                 a.ncol, a.nlay, a.ngpt, a.top_at_1, a.tau, a.ssa, a.g, a.mu0, a.sfc_alb_dir, a.sfc_alb_dif, a.inc_flux_dir, a.inc_flux_dif,
                 up, dn, dr, sync_waves, gper, nullptr);
-        }); });
+        });
     });
-    if (fits && nsplit > 1)      // (up, dn, dr lie behind each other in the scratch block)
-        sum_ranges_kernel<F,3><<<dim3(ceil_div(nlevcol, 256), 3), 256, 0, st>>>(nlevcol, nsplit, up, a.flux_up, a.flux_dn, a.flux_dir);
-    return fits;
 }
 
 // the one-kernel broadband forms serve every variant but 1 (serial kernel) and 7 (per-g-point fluxes in a workspace + sum)
