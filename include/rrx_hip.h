@@ -136,6 +136,30 @@ int rrx_sw_solver_2stream_byband##SFX( \
         const F* inc_flux_dir, RrxBool has_dif_bc, const F* inc_flux_dif, const int* band_lims_gpt, \
         F* bnd_flux_up, F* bnd_flux_dn, F* bnd_flux_dir, F* bnd_flux_net, \
         F* flux_up, F* flux_dn, F* flux_dir, void* stream); \
+/* mu0 by layer (upstream RTE's mu0(ncol,nlay), no counterpart on the reference GPU path): the two solvers above with \
+   mu0_lay (ncol, nlay) in the place of mu0. Layer l of a column takes mu0_lay(icol, l) in its two-stream coefficients and its direct \
+   transmission; the direct beam at the top level is inc_flux_dir x mu0_lay(icol, top layer) (layer 0 with top_at_1, nlay-1 without). \
+   All other arguments, do_broadband, has_dif_bc and g == NULL as there; with identical rows the fluxes of the 1-D entries. */ \
+int rrx_sw_solver_2stream_mu0lay##SFX( \
+        int ncol, int nlay, int ngpt, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const F* g, const F* mu0_lay, \
+        const F* sfc_alb_dir, const F* sfc_alb_dif, const F* inc_flux_dir, \
+        F* flux_up, F* flux_dn, F* flux_dir, \
+        RrxBool has_dif_bc, const F* inc_flux_dif, \
+        RrxBool do_broadband, F* flux_up_loc, F* flux_dn_loc, F* flux_dir_loc, void* stream); \
+int rrx_sw_solver_2stream_byband_mu0lay##SFX( \
+        int ncol, int nlay, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const F* g, const F* mu0_lay, const F* sfc_alb_dir, const F* sfc_alb_dif, \
+        const F* inc_flux_dir, RrxBool has_dif_bc, const F* inc_flux_dif, const int* band_lims_gpt, \
+        F* bnd_flux_up, F* bnd_flux_dn, F* bnd_flux_dir, F* bnd_flux_net, \
+        F* flux_up, F* flux_dn, F* flux_dir, void* stream); \
+/* Spherical-geometry correction of the solar zenith angle (upstream RTE's zenith_angle_spherical_correction): \
+   mu0_lay(icol, l) = sqrt(max(0, 1 - (1 - ref_mu^2) ((R + ref_alt) / (R + alt(icol, l)))^2)) where ref_mu(icol) > 0, and ref_mu(icol) \
+   otherwise (a dark column stays dark). alt (ncol, nlay): layer altitudes in metres; ref_alt (ncol): the altitude at which ref_mu \
+   holds, NULL = 0; planet_radius R in metres (the Earth: 6.37123e6). ncol or nlay = 0: returns 0 without a launch; a negative \
+   extent, a NULL that is needed or R <= 0: non-zero, before any HIP call. */ \
+int rrx_zenith_angle_spherical_correction##SFX(int ncol, int nlay, const F* ref_alt, const F* ref_mu, const F* alt, F planet_radius, \
+        F* mu0_lay, void* stream); \
 /* ---- Gas_optics_rrtmgp_kernels_cuda : include_kernels_cuda/gas_optics_rrtmgp_kernels_cuda.h:33-132 ---- */ \
 int rrx_reorder123x321##SFX(int ni, int nj, int nk, const F* arr_in, F* arr_out, void* stream); \
 int rrx_reorder12x21##SFX(int ni, int nj, const F* arr_in, F* arr_out, void* stream); \

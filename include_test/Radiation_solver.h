@@ -218,6 +218,13 @@ class Radiation_solver_shortwave
         // does not carry the column identities).
         void set_cloud_sampling(const Array_gpu<Float,2>* cloud_frac, const int overlap, const Array_gpu<Float,2>* overlap_param,
                                 const uint64_t seed, const int col_offset = 0);
+        // Spherical-geometry correction of the solar zenith angle (default off): solve_gpu forms a cosine per layer from
+        // its mu0 (ncol), which holds at ref_alt (ncol; nullptr = altitude 0), and the layer altitudes alt_lay (ncol, nlay), metres, with
+        // rrx_zenith_angle_spherical_correction, and the solvers take that cosine layer by layer (Rte_sw_gpu's mu0 (ncol, nlay) overloads).
+        // The arrays are BORROWED like set_cloud_sampling's: read at every solve, sorted, padded, gathered to the sunlit columns (whose
+        // list is still made from mu0) and cut into column blocks with the other inputs; nullptr as alt_lay turns it off. Altitudes
+        // below a column's reference altitude are not looked for: the kernel clamps the radicand at 0.
+        void set_spherical_mu0(const Array_gpu<Float,2>* alt_lay, const Array_gpu<Float,1>* ref_alt = nullptr, const Float planet_radius = Float(6.37123e6));
 
     private:
         const Array_gpu<Float,2>* mcica_frac = nullptr;
@@ -225,6 +232,9 @@ class Radiation_solver_shortwave
         uint64_t mcica_seed = 0;
         int mcica_col_offset = 0;
         const int* mcica_col_id = nullptr;       // (a reordered solve: the identities of its columns, on the device)
+        const Array_gpu<Float,2>* sph_alt = nullptr;
+        const Array_gpu<Float,1>* sph_ref_alt = nullptr;
+        Float sph_radius = Float(6.37123e6);
         int column_sorting = -1, sort_decided = -1;
         bool column_padding = true, reordered_call = false, sunlit_columns = false;
         std::unique_ptr<Gas_optics_rrtmgp_gpu> kdist_gpu;

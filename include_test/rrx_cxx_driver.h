@@ -47,6 +47,10 @@ int   rrx_cxx_lw_flux_up_jac(void* handle, Real* out, void* stream);
    clouds; the solve fails with LW scattering, LW rescaling or sunlit columns */
 int   rrx_cxx_cloud_sampling(void* handle, const Real* cloud_frac, int ncol, int nlay, int overlap, const Real* overlap_param,
         unsigned long long seed, int col_offset);
+/* set_spherical_mu0 of the shortwave solver: alt_lay DEVICE (ncol, nlay) layer altitudes [m], or NULL = off; ref_alt DEVICE (ncol), the
+   altitude at which mu0 holds, or NULL = 0; the arrays are borrowed (read at every solve, they must outlive the solves). The solve
+   then takes a cosine of the solar zenith angle per layer, corrected for the planet's curvature from its mu0 */
+int   rrx_cxx_spherical_mu0(void* handle, const Real* alt_lay, int ncol, int nlay, const Real* ref_alt, double planet_radius);
 /* one LW + one SW solve_gpu (fluxes only) enqueued on `stream`; DEVICE arrays: (ncol,nlay) / (ncol,nlay+1) fields, (ncol) vectors,
    surface properties (nbnd,ncol); lwp, iwp, rel, dei NULL without clouds; out7: seven (ncol, nlay+1) arrays for LW up, dn, net and
    SW up, dn, dn_dir, net, or NULL (the driver then keeps them: rrx_cxx_driver_fluxes) */

@@ -197,6 +197,45 @@ int scatter_cols_fill_impl(const int n, const unsigned long long nrest, const in
     RRX_CATCH(name)
 }
 
+// Spherical-geometry correction of the solar zenith angle: one thread per (column, layer), the column on the lanes.
+// The operations are written one by one in the order of the formula (no contraction), so that a host evaluation in the same
+// precision rounds alike.
+template<typename F>
+__global__ void __launch_bounds__(256)
+zenith_spherical_kernel(const int ncol, const int nlay, const F* __restrict__ ref_alt, const F* __restrict__ ref_mu,
+                        const F* __restrict__ alt, const F radius, F* __restrict__ mu0_lay)
+{
+    #pragma clang fp contract(off)
+    const int icol = blockIdx.x*blockDim.x + threadIdx.x;
+    if (icol >= ncol) return;
+    const F m = ref_mu[icol];
+    const F r0 = radius + ((ref_alt != nullptr) ? ref_alt[icol] : F(0.));
+    const F sin2 = F(1.) - m*m;
+    for (int ilay = blockIdx.y; ilay < nlay; ilay += gridDim.y)
+    {
+        const size_t o = size_t(ilay)*size_t(ncol) + icol;
+        const F ratio = r0 / (radius + alt[o]);
+        const F c2 = F(1.) - sin2*(ratio*ratio);
+        mu0_lay[o] = (m > F(0.)) ? sqrt(max(F(0.), c2)) : m;
+    }
+}
+
+template<typename F>
+int zenith_spherical_impl(const int ncol, const int nlay, const F* ref_alt, const F* ref_mu, const F* alt, const F radius, F* mu0_lay,
+                          void* stream, const char* name)
+{
+    RRX_TRY
+    if (ncol < 0 || nlay < 0) throw std::runtime_error("negative extent");
+    if (!(radius > F(0.))) throw std::runtime_error("planet_radius must be positive");
+    if (ncol == 0 || nlay == 0) return 0;
+    if (ref_mu == nullptr) throw std::runtime_error("ref_mu is NULL");
+    if (alt == nullptr) throw std::runtime_error("alt is NULL");
+    if (mu0_lay == nullptr) throw std::runtime_error("mu0_lay is NULL");
+    zenith_spherical_kernel<F><<<dim3(ceil_div(ncol, 256), std::min(nlay, 4096)), 256, 0, static_cast<hipStream_t>(stream)>>>(
+            ncol, nlay, ref_alt, ref_mu, alt, radius, mu0_lay);
+    RRX_CATCH(name)
+}
+
 template<typename F>
 int sort_columns_impl(const int ncol, const F* key, const int npad, int* perm, void* stream)
 {
@@ -248,7 +287,10 @@ int rrx_gather_lastdim##SFX(int n1, int nout, const int* perm, const F* in, F* o
 int rrx_sunlit_columns##SFX(int ncol, const F* mu0, const int* order, int pad_to, int* perm, int* count, void* stream) \
 { return sunlit_columns_impl<F>(ncol, mu0, order, pad_to, perm, count, stream, "rrx_sunlit_columns" #SFX); } \
 int rrx_scatter_cols_fill##SFX(int n, unsigned long long nrest, const int* perm, int ncol_src, const F* in, int ncol_dst, F* out, void* stream) \
-{ return scatter_cols_fill_impl<F>(n, nrest, perm, ncol_src, in, ncol_dst, out, stream, "rrx_scatter_cols_fill" #SFX); }
+{ return scatter_cols_fill_impl<F>(n, nrest, perm, ncol_src, in, ncol_dst, out, stream, "rrx_scatter_cols_fill" #SFX); } \
+int rrx_zenith_angle_spherical_correction##SFX(int ncol, int nlay, const F* ref_alt, const F* ref_mu, const F* alt, F planet_radius, \
+        F* mu0_lay, void* stream) \
+{ return zenith_spherical_impl<F>(ncol, nlay, ref_alt, ref_mu, alt, planet_radius, mu0_lay, stream, "rrx_zenith_angle_spherical_correction" #SFX); }
 
 RRX_DEFINE_COLUMNS(double, _f64)
 RRX_DEFINE_COLUMNS(float, _f32)

@@ -139,8 +139,12 @@ __device__ __forceinline__ TwoStream<F> two_stream(const F tau, const F ssa, con
 // compiled for four waves per SIMD the same form spills (2.65 / 9.3 ms).
 // BND (BB form, by-band outputs): blockIdx.y = band b, whose g-points [band_lims[2b]-1, band_lims[2b+1]) the workgroup sums in order from
 // zero (rrx_sum_byband's order) into band slab b of flux_up/dn/dir, (ncol, nlev, nbnd) arrays; an empty band writes zeros.
+// ML (mu0 by layer): mu0 is (ncol, nlay), layer l of a column takes its own cosine in the two-stream coefficients and
+// the direct transmission, the beam at the top level is inc_flux_dir x the top layer's. The cosine of a cell is loaded in phase (a)
+// beside tau and ssa (it does not depend on the g-point: the workgroup's slice stays in cache) and is not prefetched across g-points;
+// its reciprocal is formed per cell (fast_rcp). Across the g-point loop the lane keeps the top layer's cosine instead of mu and 1/mu.
 template<typename F, int V, int K, int W, bool BB = false, bool GZ = false, bool PRE = false, bool GS = false, int NW = (W > 2 ? 2*W : 4), int CLT = 8,
-         bool BND = false>
+         bool BND = false, bool ML = false>
 __global__ void __launch_bounds__(64*NW, (CLT == 16) ? ((NW == 4) ? RRX_SW_F32_WAVES1 : RRX_SW_F32_WAVES) : ((NW > 4) ? 1 : 2))
 sw_2stream_scan_kernel(
         const int ncol, const int nlay, const int ngpt, const int top_at_1,
@@ -182,10 +186,14 @@ sw_2stream_scan_kernel(
     const size_t ncl = size_t(ncol);
     const int t0 = (h*LL + ll)*K;
 
-    const Vec<F,V> mu = load_cols<F,V>(mu0 + icol);
-    F mu_inv[V];
-    #pragma unroll
-    for (int v=0; v<V; ++v) mu_inv[v] = F(1.)/mu.v[v];
+    // ML: the top layer's cosine (the direct beam at the top level), otherwise the column's
+    const Vec<F,V> mu = load_cols<F,V>(mu0 + (ML ? size_t(top_at_1 ? 0 : nlay-1)*ncl : size_t(0)) + icol);
+    [[maybe_unused]] F mu_inv[V];
+    if constexpr (!ML)
+    {
+        #pragma unroll
+        for (int v=0; v<V; ++v) mu_inv[v] = F(1.)/mu.v[v];
+    }
 
     F acc_dir[BB ? K : 1][V];
     if constexpr (BB)
@@ -288,6 +296,12 @@ sw_2stream_scan_kernel(
         }
         else gv = load_cols<F,V>(g + off);
         }
+        [[maybe_unused]] Vec<F,V> mv;
+        if constexpr (ML)
+        {
+            if constexpr (PRE) mv = load_cols<F,V>(mu0 + off_of(j));
+            else mv = load_cols<F,V>(mu0 + (off - size_t(igpt)*ncl*nlay));       // (behind the tie on off, like this layer's other loads)
+        }
         // (V == 1: the tie sits ahead of the evaluation loop, V > 1: on each column's tau. Same dependence, but the
         //  register allocator lands differently: measured fp64 6.3 vs 8.3 ms and fp32 6.4 vs 4.4 ms, tools/ab_sw.sh)
         if constexpr (BB && V == 1)
@@ -305,7 +319,9 @@ sw_2stream_scan_kernel(
             // a padding layer (level slot beyond the surface) is made transparent through its optical depth: tau = 0 gives
             // r_dif = 0, t_noscat = 1 exactly, t_dif = 1 to an ulp and r_dir = t_dir = the eps floor of the clamps (2e-16 of the
             // direct beam) -- one select on the input instead of five on the outputs
-            const TwoStream<F> ts = two_stream<F,GZ>(valid ? tv.v[v] : F(0.), wv.v[v], gv.v[v], mu.v[v], mu_inv[v]);
+            const F mu_c = ML ? mv.v[v] : mu.v[v];
+            const F mu_inv_c = ML ? fast_rcp(mv.v[v]) : mu_inv[v];       // (a Newton reciprocal like the cell's other one: the registers of a division, about ten fp64 instructions fewer)
+            const TwoStream<F> ts = two_stream<F,GZ>(valid ? tv.v[v] : F(0.), wv.v[v], gv.v[v], mu_c, mu_inv_c);
             rp[j][v] = ts.r_dif;
             al[j][v] = ts.t_dif;
             sb[j][v] = ts.r_dir;
@@ -666,7 +682,7 @@ sw_2stream_scan_kernel(
 
 // Any-nlay fallback: one thread per (col, gpt); r_dif, t_dif, source_up/dn, albedo, src, denom kept in a
 // caller-provided global workspace laid out like the reference's temporaries.
-template<typename F>
+template<typename F, bool ML = false>
 __global__ void __launch_bounds__(256)
 sw_2stream_serial_kernel(
         const int ncol, const int nlay, const int ngpt, const int top_at_1,
@@ -692,11 +708,13 @@ sw_2stream_serial_kernel(
     auto mlev = [&](const int t) { return lev_base + size_t(top_at_1 ? t : nlay - t)*ncl; };
     auto mlay = [&](const int s) { return lay_base + size_t(top_at_1 ? s : nlay-1-s)*ncl; };
 
-    const F mu = mu0[icol];
+    // ML: mu0 is (ncol, nlay), s = 0 is the top layer
+    F mu = ML ? mu0[mlay(0) - size_t(igpt)*ncl*nlay] : mu0[icol];
     F dir = inc_flux_dir[sfc_idx] * mu;
     for (int s=0; s<nlay; ++s)
     {
         const size_t il = mlay(s);
+        if constexpr (ML) mu = mu0[il - size_t(igpt)*ncl*nlay];
         const TwoStream<F> ts = two_stream<F>(tau[il], ssa[il], g[il], mu, F(1.)/mu);
         w_r[il] = ts.r_dif; w_t[il] = ts.t_dif;
         w_su[il] = ts.r_dir * dir; w_sd[il] = ts.t_dir * dir;
@@ -755,6 +773,7 @@ struct SwArgs
     const F *tau, *ssa, *g /* or null: asymmetry identically zero */, *mu0, *sfc_alb_dir, *sfc_alb_dif, *inc_flux_dir, *inc_flux_dif /* or null */;
     F *flux_up, *flux_dn, *flux_dir;
     const int* band_lims; int nbnd;             // by-band form: flux_* are (ncol, nlev, nbnd) band sums
+    bool mu0_lay = false;                       // mu0 is (ncol, nlay): the kernels' ML forms
 };
 
 // the per-g-point kernel (two waves per column group, two groups per workgroup); false when the columns are taller than its
@@ -764,17 +783,17 @@ bool launch_scan(hipStream_t st, const SwArgs<F>& a)
 {
     const dim3 grid(ceil_div(a.ncol, 2*CL*V), a.ngpt);
     const int sync_waves = tuning().sync_waves;
-    return with_k<2, 4, 6, 9, 12, 17>(ceil_div(a.nlay+1, 2*LL), [&](auto kk)
+    return with_k<2, 4, 6, 9, 12, 17>(ceil_div(a.nlay+1, 2*LL), [&](auto kk) { with_flag(a.mu0_lay, [&](auto ml)
     {
-        sw_2stream_scan_kernel<F,V,decltype(kk)::value,2><<<grid, 256, 0, st>>>(
+        sw_2stream_scan_kernel<F,V,decltype(kk)::value,2,false,false,false,false,4,8,false,decltype(ml)::value><<<grid, 256, 0, st>>>(
             a.ncol, a.nlay, a.ngpt, a.top_at_1, a.tau, a.ssa, a.g, a.mu0, a.sfc_alb_dir, a.sfc_alb_dif, a.inc_flux_dir, a.inc_flux_dif,
             a.flux_up, a.flux_dn, a.flux_dir, sync_waves, 1, nullptr);
-    });
+    }); });
 }
 
 // One tiling of the fused broadband form: W waves per column group, CLT column lanes per wave, NW waves per workgroup (NW/W column
 // groups); false when the columns are taller than the tiling's largest K (the caller tries the next one).
-template<typename F, int V, int W, int CLT, int NW>
+template<typename F, int V, int W, int CLT, int NW, bool ML = false>
 bool launch_scan_bb(hipStream_t st, const SwArgs<F>& a)
 {
     const int groups = ceil_div(a.ncol, (NW/W)*CLT*V);
@@ -795,7 +814,11 @@ bool launch_scan_bb(hipStream_t st, const SwArgs<F>& a)
     {
         with_flag(a.g == nullptr, [&](auto gz)
         {
-            if constexpr (sizeof(F) == 8 ? decltype(gz)::value : (V == 1 && CLT == 16))
+            // (mu0 by layer: one more load and its address per cell. The pipelined fp64 form then spills 22-28 VGPRs and loses to the
+            //  not-pipelined one, which fits: 5.06 against 4.91 ms at 16 384 x 140 x 224. fp32 stays pipelined: with a g array it spills
+            //  8-14 VGPRs and still wins, 5.70 against 5.93 ms all-sky at 32 768 x 140 x 256; without one it fits. DESIGN.md 4.13)
+            constexpr bool ml_fits = !ML || sizeof(F) == 4;
+            if constexpr (ml_fits && (sizeof(F) == 8 ? decltype(gz)::value : (V == 1 && CLT == 16)))
                 with_flag(size_t(a.ncol)*a.nlay < (size_t(1) << 31), [&](auto pre) { launch(gz, pre); });
             else
                 launch(gz, std::false_type{});
@@ -809,7 +832,7 @@ bool launch_scan_bb(hipStream_t st, const SwArgs<F>& a)
         const dim3 grid(groups, a.nbnd);
         return with_tiling_k([&](auto kk) { with_gz_pre([&](auto gz, auto pre)
         {
-            sw_2stream_scan_kernel<F,V,decltype(kk)::value,W,true,decltype(gz)::value,decltype(pre)::value,false,NW,CLT,true><<<grid, 64*NW, 0, st>>>(
+            sw_2stream_scan_kernel<F,V,decltype(kk)::value,W,true,decltype(gz)::value,decltype(pre)::value,false,NW,CLT,true,ML><<<grid, 64*NW, 0, st>>>(
                 a.ncol, a.nlay, a.ngpt, a.top_at_1, a.tau, a.ssa, a.g, a.mu0, a.sfc_alb_dir, a.sfc_alb_dif, a.inc_flux_dir, a.inc_flux_dif,
                 a.flux_up, a.flux_dn, a.flux_dir, sync_waves, 0, a.band_lims);
         }); });
@@ -821,7 +844,7 @@ bool launch_scan_bb(hipStream_t st, const SwArgs<F>& a)
     {
         with_gz_pre([&](auto gz, auto pre)
         {
-            sw_2stream_scan_kernel<F,V,decltype(kk)::value,W,true,decltype(gz)::value,decltype(pre)::value,decltype(gs)::value,NW,CLT><<<grid, 64*NW, 0, st>>>(
+            sw_2stream_scan_kernel<F,V,decltype(kk)::value,W,true,decltype(gz)::value,decltype(pre)::value,decltype(gs)::value,NW,CLT,false,ML><<<grid, 64*NW, 0, st>>>(
                 a.ncol, a.nlay, a.ngpt, a.top_at_1, a.tau, a.ssa, a.g, a.mu0, a.sfc_alb_dir, a.sfc_alb_dif, a.inc_flux_dir, a.inc_flux_dif,
                 up, dn, dr, sync_waves, gper, nullptr);
         });
@@ -841,6 +864,12 @@ template<typename F>
 bool sw_fused_broadband(hipStream_t st, const SwArgs<F>& a)
 {
     if (!sw_fused_allowed()) return false;
+    // mu0 by layer: the tilings of up to 191 layers; taller columns take the per-g-point route and its sums
+    if (a.mu0_lay)
+    {
+        if constexpr (sizeof(F) == 8) return launch_scan_bb<F,1,2,8,4,true>(st, a);
+        else return launch_scan_bb<F,1,4,16,4,true>(st, a) || launch_scan_bb<F,1,4,16,8,true>(st, a);
+    }
     if constexpr (sizeof(F) == 8)
     {
         // up to 191 layers: two waves of 8 x 8 lanes per column group, two groups per workgroup
@@ -874,14 +903,15 @@ int sw_solver_2stream_impl(
         F* flux_up, F* flux_dn, F* flux_dir,
         const Bool has_dif_bc, const F* inc_flux_dif,
         const Bool do_broadband, F* flux_up_loc, F* flux_dn_loc, F* flux_dir_loc, void* stream,
-        const int nbnd = 0, const int* band_lims = nullptr /* by-band sums into flux_*_loc, (ncol, nlev, nbnd): the per-g-point route only */)
+        const int nbnd = 0, const int* band_lims = nullptr /* by-band sums into flux_*_loc, (ncol, nlev, nbnd): the per-g-point route only */,
+        const bool mu0_lay = false /* mu0 is (ncol, nlay) */)
 {
     RRX_TRY
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (ncol <= 0 || nlay <= 0 || ngpt <= 0) throw std::runtime_error("empty problem");
     // (the fused form's arguments; the per-g-point route below redirects g and the outputs)
     SwArgs<F> a{ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, has_dif_bc ? inc_flux_dif : nullptr,
-                flux_up_loc, flux_dn_loc, flux_dir_loc, nullptr, 0};
+                flux_up_loc, flux_dn_loc, flux_dir_loc, nullptr, 0, mu0_lay};
     const bool serial = tuning().sw_variant == 1;
     const bool byband = band_lims != nullptr;
 
@@ -932,8 +962,11 @@ int sw_solver_2stream_impl(
         if (!may_go_serial) throw std::runtime_error("internal: no tiling for this shape and no workspace for the serial form");
         F* ws2 = big + w_g + w_flux;
         const dim3 grid(ceil_div(ncol, 256), ngpt);
-        sw_2stream_serial_kernel<F><<<grid, 256, 0, st>>>(ncol, nlay, ngpt, top_at_1, tau, ssa, a.g, mu0,
-                sfc_alb_dir, sfc_alb_dif, inc_flux_dir, a.inc_flux_dif, a.flux_up, a.flux_dn, a.flux_dir, ws2);
+        with_flag(mu0_lay, [&](auto ml)
+        {
+            sw_2stream_serial_kernel<F,decltype(ml)::value><<<grid, 256, 0, st>>>(ncol, nlay, ngpt, top_at_1, tau, ssa, a.g, mu0,
+                    sfc_alb_dir, sfc_alb_dif, inc_flux_dir, a.inc_flux_dif, a.flux_up, a.flux_dn, a.flux_dir, ws2);
+        });
     }
 
     if (byband)      // (the three per-g-point arrays lie behind each other in the workspace)
@@ -946,7 +979,7 @@ int sw_solver_2stream_impl(
         sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, a.flux_dn, flux_dn_loc);
         sum_gpt_kernel<F><<<nb, 256, 0, st>>>(nlevcol, ngpt, a.flux_dir, flux_dir_loc);
     }
-    RRX_CATCH("rrx_sw_solver_2stream")
+    RRX_CATCH(mu0_lay ? "rrx_sw_solver_2stream_mu0lay" : "rrx_sw_solver_2stream")
 }
 
 // by-band fluxes (rrx_sw_solver_2stream_byband): the fused kernels with one band per workgroup where the tilings reach, otherwise the
@@ -956,23 +989,23 @@ int sw_solver_2stream_byband_impl(
         const int ncol, const int nlay, const int ngpt, const int nbnd, const Bool top_at_1,
         const F* tau, const F* ssa, const F* g, const F* mu0, const F* sfc_alb_dir, const F* sfc_alb_dif,
         const F* inc_flux_dir, const Bool has_dif_bc, const F* inc_flux_dif, const int* band_lims,
-        F* bnd_up, F* bnd_dn, F* bnd_dir, F* bnd_net, F* flux_up, F* flux_dn, F* flux_dir, void* stream)
+        F* bnd_up, F* bnd_dn, F* bnd_dir, F* bnd_net, F* flux_up, F* flux_dn, F* flux_dir, void* stream, const bool mu0_lay = false)
 {
     RRX_TRY
     hipStream_t st = static_cast<hipStream_t>(stream);
     check_byband_args(ncol, nlay, ngpt, nbnd, band_lims);
     if (bnd_up == nullptr || bnd_dn == nullptr || bnd_dir == nullptr) throw std::runtime_error("band flux outputs missing");
     const SwArgs<F> a{ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, has_dif_bc ? inc_flux_dif : nullptr,
-                      bnd_up, bnd_dn, bnd_dir, band_lims, nbnd};
+                      bnd_up, bnd_dn, bnd_dir, band_lims, nbnd, mu0_lay};
     if (!sw_fused_broadband<F>(st, a))
     {
         if (sw_solver_2stream_impl<F>(ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir,
                                       (F*)nullptr, (F*)nullptr, (F*)nullptr, has_dif_bc, inc_flux_dif, Bool(0), bnd_up, bnd_dn, bnd_dir,
-                                      stream, nbnd, band_lims) != 0)
+                                      stream, nbnd, band_lims, mu0_lay) != 0)
             return 1;                                                // (the message is set)
     }
     launch_byband_outputs<F,3>(st, size_t(ncol)*(nlay+1), nbnd, bnd_up, bnd_dn, bnd_dir, bnd_net, flux_up, flux_dn, flux_dir);
-    RRX_CATCH("rrx_sw_solver_2stream_byband")
+    RRX_CATCH(mu0_lay ? "rrx_sw_solver_2stream_byband_mu0lay" : "rrx_sw_solver_2stream_byband")
 }
 
 template<typename F>
@@ -1034,6 +1067,28 @@ int rrx_sw_solver_2stream_byband##SFX( \
     return sw_solver_2stream_byband_impl<F>(ncol, nlay, ngpt, nbnd, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, \
             inc_flux_dir, has_dif_bc, inc_flux_dif, band_lims_gpt, bnd_flux_up, bnd_flux_dn, bnd_flux_dir, bnd_flux_net, \
             flux_up, flux_dn, flux_dir, stream); \
+} \
+int rrx_sw_solver_2stream_mu0lay##SFX( \
+        int ncol, int nlay, int ngpt, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const F* g, const F* mu0_lay, \
+        const F* sfc_alb_dir, const F* sfc_alb_dif, const F* inc_flux_dir, \
+        F* flux_up, F* flux_dn, F* flux_dir, \
+        RrxBool has_dif_bc, const F* inc_flux_dif, \
+        RrxBool do_broadband, F* flux_up_loc, F* flux_dn_loc, F* flux_dir_loc, void* stream) \
+{ \
+    return sw_solver_2stream_impl<F>(ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0_lay, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, \
+            flux_up, flux_dn, flux_dir, has_dif_bc, inc_flux_dif, do_broadband, flux_up_loc, flux_dn_loc, flux_dir_loc, stream, 0, nullptr, true); \
+} \
+int rrx_sw_solver_2stream_byband_mu0lay##SFX( \
+        int ncol, int nlay, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const F* g, const F* mu0_lay, const F* sfc_alb_dir, const F* sfc_alb_dif, \
+        const F* inc_flux_dir, RrxBool has_dif_bc, const F* inc_flux_dif, const int* band_lims_gpt, \
+        F* bnd_flux_up, F* bnd_flux_dn, F* bnd_flux_dir, F* bnd_flux_net, \
+        F* flux_up, F* flux_dn, F* flux_dir, void* stream) \
+{ \
+    return sw_solver_2stream_byband_impl<F>(ncol, nlay, ngpt, nbnd, top_at_1, tau, ssa, g, mu0_lay, sfc_alb_dir, sfc_alb_dif, \
+            inc_flux_dir, has_dif_bc, inc_flux_dif, band_lims_gpt, bnd_flux_up, bnd_flux_dn, bnd_flux_dir, bnd_flux_net, \
+            flux_up, flux_dn, flux_dir, stream, true); \
 } \
 int rrx_apply_BC_factor##SFX(int ncol, int nlay, int ngpt, RrxBool top_at_1, const F* inc_flux_dir, const F* mu0, F* gpt_flux_dir, void* stream) \
 { return apply_BC_impl<F>(ncol, nlay, ngpt, top_at_1, inc_flux_dir, mu0, gpt_flux_dir, stream); } \

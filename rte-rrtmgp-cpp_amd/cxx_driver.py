@@ -16,7 +16,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 class CxxDriver:
     def __init__(self, be, kd_lw0, kd_sw0, atm, cloud_luts0=None, column_block=16384, broadband=True, sort_mode=-1, pad=True,
                  sunlit=False, jacobian=False, n_gauss_angles=1, optimal_angles=False, lw_scattering=False,
-                 lw_rescaling=False, cloud_fraction=None, cloud_overlap="max_ran", overlap_param=None, mcica_seed=0, mcica_col_offset=0):
+                 lw_rescaling=False, cloud_fraction=None, cloud_overlap="max_ran", overlap_param=None, mcica_seed=0, mcica_col_offset=0,
+                 altitude=None, ref_altitude=None, planet_radius=6.37123e6):
         import torch
         self.torch, self.be, self.atm = torch, be, atm
         self.f64 = be.np_dtype == np.float64
@@ -71,6 +72,17 @@ class CxxDriver:
             if cloud_overlap not in ("max_ran", "exp_ran"):
                 raise ValueError(f"CxxDriver: cloud_overlap = {cloud_overlap!r} is not 'max_ran' or 'exp_ran'")
             self._set_cloud_sampling()
+        # altitude: the SW solve takes a cosine of the solar zenith angle per layer, corrected for the planet's curvature from mu0
+        # (set_spherical_mu0), as pipeline.ResidentSolver(altitude=, ref_altitude=) does; the tensors are borrowed by the solver
+        self.altitude, self.ref_altitude = altitude, ref_altitude
+        if ref_altitude is not None and altitude is None:
+            raise ValueError("CxxDriver: ref_altitude without altitude")
+        if altitude is not None:
+            if tuple(altitude.shape) != (atm.nlay, atm.ncol) or (ref_altitude is not None and tuple(ref_altitude.shape) != (atm.ncol,)):
+                raise ValueError("CxxDriver: altitude must be (nlay, ncol) and ref_altitude (ncol)")
+            self._check(self.lib.rrx_cxx_spherical_mu0(
+                self.h, ctypes.c_void_p(altitude.data_ptr()), atm.ncol, atm.nlay,
+                ctypes.c_void_p(ref_altitude.data_ptr() if ref_altitude is not None else 0), ctypes.c_double(float(planet_radius))))
         for n, t in atm.vmr.items():                # (nlay, ncol) tensors = (ncol, nlay) arrays; profiles (nlay,) = (1, nlay)
             n1, n2 = (t.shape[1], t.shape[0]) if t.dim() == 2 else ((1, t.shape[0]) if t.dim() == 1 else (1, 1))
             self._check(self.lib.rrx_cxx_driver_set_gas(self.h, n.encode(), ctypes.c_void_p(t.data_ptr()), n1, n2))

@@ -165,6 +165,57 @@ class HipKernels:
                 out.get("flux_up"), out.get("flux_dn"), out.get("flux_dir"))
         return out
 
+    # mu0 by layer: mu0_lay is (nlay, ncol), every layer of a column with its own cosine
+    def _mu0_lay(self, mu0_lay, nlay, ncol):
+        if tuple(mu0_lay.shape) != (nlay, ncol):
+            raise ValueError(f"mu0_lay must be (nlay, ncol) = ({nlay}, {ncol}), got {tuple(mu0_lay.shape)}")
+        return mu0_lay
+
+    def sw_solver_2stream_mu0lay(self, top_at_1, tau, ssa, g, mu0_lay, sfc_alb_dir, sfc_alb_dif, inc_flux_dir,
+                                 inc_flux_dif=None, do_broadband=False, out=None):
+        """sw_solver_2stream with the cosine of the solar zenith angle per layer. g may be None (asymmetry identically zero).
+        out=: preallocated flux_up/dn/dir, (nlev, ncol) in broadband mode and (ngpt, nlev, ncol) otherwise."""
+        ngpt, nlay, ncol = tau.shape
+        mu0_lay = self._mu0_lay(mu0_lay, nlay, ncol)
+        shape = (nlay+1, ncol) if do_broadband else (ngpt, nlay+1, ncol)
+        if out is None:
+            out = {k: self.empty(shape) for k in ("flux_up", "flux_dn", "flux_dir")}
+        per_gpt = (None, None, None) if do_broadband else (out["flux_up"], out["flux_dn"], out["flux_dir"])
+        loc = (out["flux_up"], out["flux_dn"], out["flux_dir"]) if do_broadband else (None, None, None)
+        self._c("sw_solver_2stream_mu0lay", ncol, nlay, ngpt, BoolArg(top_at_1), tau, ssa, g, mu0_lay,
+                sfc_alb_dir, sfc_alb_dif, inc_flux_dir, *per_gpt,
+                BoolArg(inc_flux_dif is not None), inc_flux_dif, BoolArg(do_broadband), *loc)
+        return out
+
+    def sw_solver_2stream_byband_mu0lay(self, top_at_1, tau, ssa, g, mu0_lay, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, band_lims,
+                                        inc_flux_dif=None, out=None, net=True, broadband=True):
+        """sw_solver_2stream_byband with the cosine of the solar zenith angle per layer; outputs as there."""
+        ngpt, nlay, ncol = tau.shape
+        nbnd = band_lims.shape[0]
+        mu0_lay = self._mu0_lay(mu0_lay, nlay, ncol)
+        if out is None:
+            out = {k: self.empty((nbnd, nlay+1, ncol)) for k in ("bnd_flux_up", "bnd_flux_dn", "bnd_flux_dir")}
+            if net:
+                out["bnd_flux_net"] = self.empty((nbnd, nlay+1, ncol))
+            if broadband:
+                out.update({k: self.empty((nlay+1, ncol)) for k in ("flux_up", "flux_dn", "flux_dir")})
+        self._c("sw_solver_2stream_byband_mu0lay", ncol, nlay, ngpt, nbnd, BoolArg(top_at_1), tau, ssa, g, mu0_lay,
+                sfc_alb_dir, sfc_alb_dif, inc_flux_dir, BoolArg(inc_flux_dif is not None), inc_flux_dif, band_lims,
+                out["bnd_flux_up"], out["bnd_flux_dn"], out["bnd_flux_dir"], out.get("bnd_flux_net"),
+                out.get("flux_up"), out.get("flux_dn"), out.get("flux_dir"))
+        return out
+
+    def zenith_angle_spherical_correction(self, ref_mu, alt, ref_alt=None, planet_radius=6.37123e6, out=None):
+        """mu0_lay (nlay, ncol) from the cosine ref_mu (ncol) that holds at altitude ref_alt (ncol, None = 0) and the layer
+        altitudes alt (nlay, ncol), metres: the sun rises with altitude over a spherical planet; ref_mu <= 0 is passed through."""
+        nlay, ncol = alt.shape
+        if tuple(ref_mu.shape) != (ncol,) or (ref_alt is not None and tuple(ref_alt.shape) != (ncol,)):
+            raise ValueError("ref_mu and ref_alt must be (ncol)")
+        if out is None:
+            out = self.empty((nlay, ncol))
+        self._c("zenith_angle_spherical_correction", ncol, nlay, ref_alt, ref_mu, alt, float(planet_radius), out)
+        return out
+
     # ---- gas optics -------------------------------------------------------------------------------
     def interpolation(self, kd, play, tlay, col_gas):
         nlay, ncol = play.shape

@@ -373,5 +373,82 @@ void Rte_sw_gpu::rte_sw_byband(
              bnd_flux_up.ptr(), bnd_flux_dn.ptr(), bnd_flux_dir.ptr(), opt(bnd_flux_net), opt(flux_up), opt(flux_dn), opt(flux_dir));
 }
 
+// mu0 (ncol, nlay): a cosine of the solar zenith angle per layer. The two methods above with the by-layer entries of
+// the device layer in the place of the 1-D ones.
+void Rte_sw_gpu::rte_sw(
+        const std::unique_ptr<Optical_props_arry_gpu>& optical_props,
+        const Bool top_at_1,
+        const Array_gpu<Float,2>& mu0,
+        const Array_gpu<Float,2>& inc_flux_dir,
+        const Array_gpu<Float,2>& sfc_alb_dir,
+        const Array_gpu<Float,2>& sfc_alb_dif,
+        const Array_gpu<Float,2>& inc_flux_dif,
+        Array_gpu<Float,3>& gpt_flux_up,
+        Array_gpu<Float,3>& gpt_flux_dn,
+        Array_gpu<Float,3>& gpt_flux_dir)
+{
+    if (is_byband(optical_props, gpt_flux_up))
+    {
+        Array_gpu<Float,3> no3; Array_gpu<Float,2> no_up, no_dn, no_dir;
+        rte_sw_byband(optical_props, top_at_1, mu0, inc_flux_dir, sfc_alb_dir, sfc_alb_dif, inc_flux_dif, gpt_flux_up, gpt_flux_dn,
+                      gpt_flux_dir, no3, no_up, no_dn, no_dir);
+        return;
+    }
+    const int ncol = optical_props->get_ncol();
+    const int nlay = optical_props->get_nlay();
+    const int ngpt = optical_props->get_ngpt();
+    if (mu0.dim(1) != ncol || mu0.dim(2) != nlay) throw std::runtime_error("rte_sw: mu0 by layer must be (ncol, nlay)");
+
+    Array_gpu<Float,2> sfc_alb_dir_gpt({ncol, ngpt});
+    Array_gpu<Float,2> sfc_alb_dif_gpt({ncol, ngpt});
+    expand_and_transpose(optical_props, sfc_alb_dir, sfc_alb_dir_gpt);
+    expand_and_transpose(optical_props, sfc_alb_dif, sfc_alb_dif_gpt);
+
+    const Bool has_dif_bc = (inc_flux_dif.size() > 0);
+    const Bool do_broadband = (gpt_flux_up.dim(3) == 1 && ngpt != 1);
+    RRX_CALL(rrx_sw_solver_2stream_mu0lay, ncol, nlay, ngpt, top_at_1,
+             optical_props->get_tau().ptr(), optical_props->get_ssa().ptr(),
+             do_broadband ? optical_props->get_g_or_null() : static_cast<const Float*>(optical_props->get_g().ptr()),
+             mu0.ptr(), sfc_alb_dir_gpt.ptr(), sfc_alb_dif_gpt.ptr(), inc_flux_dir.ptr(),
+             gpt_flux_up.ptr(), gpt_flux_dn.ptr(), gpt_flux_dir.ptr(), has_dif_bc, has_dif_bc ? inc_flux_dif.ptr() : nullptr,
+             do_broadband, gpt_flux_up.ptr(), gpt_flux_dn.ptr(), gpt_flux_dir.ptr());
+}
+
+void Rte_sw_gpu::rte_sw_byband(
+        const std::unique_ptr<Optical_props_arry_gpu>& optical_props,
+        const Bool top_at_1,
+        const Array_gpu<Float,2>& mu0,
+        const Array_gpu<Float,2>& inc_flux_dir,
+        const Array_gpu<Float,2>& sfc_alb_dir,
+        const Array_gpu<Float,2>& sfc_alb_dif,
+        const Array_gpu<Float,2>& inc_flux_dif,
+        Array_gpu<Float,3>& bnd_flux_up,
+        Array_gpu<Float,3>& bnd_flux_dn,
+        Array_gpu<Float,3>& bnd_flux_dir,
+        Array_gpu<Float,3>& bnd_flux_net,
+        Array_gpu<Float,2>& flux_up,
+        Array_gpu<Float,2>& flux_dn,
+        Array_gpu<Float,2>& flux_dir)
+{
+    const int ncol = optical_props->get_ncol();
+    const int nlay = optical_props->get_nlay();
+    const int ngpt = optical_props->get_ngpt();
+    const int nbnd = optical_props->get_nband();
+    if (mu0.dim(1) != ncol || mu0.dim(2) != nlay) throw std::runtime_error("rte_sw_byband: mu0 by layer must be (ncol, nlay)");
+    if (bnd_flux_up.dim(3) != nbnd || bnd_flux_dn.dim(3) != nbnd || bnd_flux_dir.dim(3) != nbnd)
+        throw std::runtime_error("rte_sw_byband: flux arrays need one slab per band");
+
+    Array_gpu<Float,2> sfc_alb_dir_gpt({ncol, ngpt});
+    Array_gpu<Float,2> sfc_alb_dif_gpt({ncol, ngpt});
+    expand_and_transpose(optical_props, sfc_alb_dir, sfc_alb_dir_gpt);
+    expand_and_transpose(optical_props, sfc_alb_dif, sfc_alb_dif_gpt);
+    const Bool has_dif_bc = (inc_flux_dif.size() > 0);
+    RRX_CALL(rrx_sw_solver_2stream_byband_mu0lay, ncol, nlay, ngpt, nbnd, top_at_1,
+             optical_props->get_tau().ptr(), optical_props->get_ssa().ptr(), optical_props->get_g_or_null(), mu0.ptr(),
+             sfc_alb_dir_gpt.ptr(), sfc_alb_dif_gpt.ptr(), inc_flux_dir.ptr(), has_dif_bc, has_dif_bc ? inc_flux_dif.ptr() : nullptr,
+             optical_props->get_band_lims_gpoint_gpu().ptr(),
+             bnd_flux_up.ptr(), bnd_flux_dn.ptr(), bnd_flux_dir.ptr(), opt(bnd_flux_net), opt(flux_up), opt(flux_dn), opt(flux_dir));
+}
+
 void Rte_sw_gpu::expand_and_transpose(const std::unique_ptr<Optical_props_arry_gpu>& ops, const Array_gpu<Float,2> arr_in, Array_gpu<Float,2>& arr_out)
 { expand(ops, arr_in, arr_out); }

@@ -323,21 +323,26 @@ void rte_sw_solver_2stream(
         const Bool& has_dif_bc, const Float* inc_flux_dif,
         const Bool& do_broadband, Float* flux_up_loc, Float* flux_dn_loc, Float* flux_dir_loc)
 {
-    // mu0 arrives as (ncol,nlay), a copy of mu0(ncol) per layer (src/Rte_sw.cpp:160-163); the device layer takes mu0(ncol)
-    for (int ilay=1; ilay<nlay; ++ilay)
-        if (std::memcmp(mu0, mu0 + size_t(ilay)*ncol, size_t(ncol)*sizeof(Float)) != 0)
-            fail("rte_sw_solver_2stream: mu0 varying with height is not served (the device layer keeps mu0(ncol))");
+    // mu0 arrives as (ncol,nlay): a copy of mu0(ncol) per layer from the reference's classes (src/Rte_sw.cpp:160-163), which goes to
+    // the device layer's mu0(ncol) entry as ever; rows that differ (a cosine per layer) go to its by-layer entry
+    bool by_layer = false;
+    for (int ilay=1; ilay<nlay && !by_layer; ++ilay)
+        by_layer = std::memcmp(mu0, mu0 + size_t(ilay)*ncol, size_t(ncol)*sizeof(Float)) != 0;
     Stage S;
     const size_t n = sz(ncol, nlay, ngpt), ng = sz(ncol, ngpt), nlev = sz(ncol, nlay + 1);
     const Float* d_tau = S.in(tau, n); const Float* d_ssa = S.in(ssa, n); const Float* d_g = S.in(g, n);
-    const Float* d_mu0 = S.in(mu0, ncol);
+    const Float* d_mu0 = S.in(mu0, by_layer ? sz(ncol, nlay) : size_t(ncol));
     const Float* d_adir = S.in(sfc_alb_dir_gpt, ng); const Float* d_adif = S.in(sfc_alb_dif_gpt, ng); const Float* d_inc = S.in(inc_flux_dir, ng);
     const Float* d_incdif = has_dif_bc ? S.in(inc_flux_dif, ng) : nullptr;
     Float *d_up = nullptr, *d_dn = nullptr, *d_dir = nullptr, *d_bup = nullptr, *d_bdn = nullptr, *d_bdir = nullptr;
     if (do_broadband) { d_bup = S.out(flux_up_loc, nlev); d_bdn = S.out(flux_dn_loc, nlev); d_bdir = S.out(flux_dir_loc, nlev); }
     else { d_up = S.out(gpt_flux_up, nlev*size_t(ngpt)); d_dn = S.out(gpt_flux_dn, nlev*size_t(ngpt)); d_dir = S.out(gpt_flux_dir, nlev*size_t(ngpt)); }
-    RRX_K(rrx_sw_solver_2stream, ncol, nlay, ngpt, top_at_1, d_tau, d_ssa, d_g, d_mu0, d_adir, d_adif, d_inc, d_up, d_dn, d_dir,
-          has_dif_bc, d_incdif, do_broadband, d_bup, d_bdn, d_bdir);
+    if (by_layer)
+        RRX_K(rrx_sw_solver_2stream_mu0lay, ncol, nlay, ngpt, top_at_1, d_tau, d_ssa, d_g, d_mu0, d_adir, d_adif, d_inc, d_up, d_dn, d_dir,
+              has_dif_bc, d_incdif, do_broadband, d_bup, d_bdn, d_bdir);
+    else
+        RRX_K(rrx_sw_solver_2stream, ncol, nlay, ngpt, top_at_1, d_tau, d_ssa, d_g, d_mu0, d_adir, d_adif, d_inc, d_up, d_dn, d_dir,
+              has_dif_bc, d_incdif, do_broadband, d_bup, d_bdn, d_bdir);
     S.finish();
 }
 

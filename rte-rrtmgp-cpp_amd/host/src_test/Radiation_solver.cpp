@@ -267,6 +267,22 @@ namespace
         ~Sampling_reordered() { frac = frac0; alpha = alpha0; col_id = col_id0; }
     };
 
+    // The borrowed altitude fields of a reordered shortwave solve (set_spherical_mu0): replaced by their gathered copies for the
+    // duration of the inner solve, and put back afterwards.
+    struct Altitudes_reordered
+    {
+        const Array_gpu<Float,2>*& alt; const Array_gpu<Float,1>*& ref;
+        const Array_gpu<Float,2>* alt0; const Array_gpu<Float,1>* ref0;
+        Array_gpu<Float,2> alt_r; Array_gpu<Float,1> ref_r;
+        Altitudes_reordered(const Array_gpu<Float,2>*& a, const Array_gpu<Float,1>*& r, const Column_order& co) : alt(a), ref(r), alt0(a), ref0(r)
+        {
+            if (alt0 == nullptr) return;
+            alt_r = co.in2(*alt0); alt = &alt_r;
+            if (ref0 != nullptr) { ref_r = co.in1(*ref0); ref = &ref_r; }
+        }
+        ~Altitudes_reordered() { alt = alt0; ref = ref0; }
+    };
+
     void check_cloud_sampling(const char* who, const Array_gpu<Float,2>* frac, const Array_gpu<Float,2>* alpha, const int n_col, const int n_lay,
                               const bool cloud_optics)
     {
@@ -731,6 +747,11 @@ void Radiation_solver_shortwave::solve_gpu(
         throw std::runtime_error("Radiation_solver_shortwave: cloud sampling (set_cloud_sampling) is not available with the sunlit-only "
                                  "solve (set_sunlit_columns): it does not carry the column identities");
     if (mcica) check_cloud_sampling("Radiation_solver_shortwave", mcica_frac, mcica_alpha, n_col, n_lay, switch_cloud_optics);
+    const bool spherical = sph_alt != nullptr;
+    if (spherical && (sph_alt->dim(1) != n_col || sph_alt->dim(2) != n_lay))
+        throw std::runtime_error("Radiation_solver_shortwave: set_spherical_mu0: alt_lay is not (ncol, nlay)");
+    if (spherical && sph_ref_alt != nullptr && sph_ref_alt->dim(1) != n_col)
+        throw std::runtime_error("Radiation_solver_shortwave: set_spherical_mu0: ref_alt is not (ncol)");
 
     // columns in another order / on a padded count: gather the inputs, solve, scatter the fluxes back (see the header)
     if (!reordered_call && !switch_output_optical && switch_fluxes)
@@ -761,6 +782,7 @@ void Radiation_solver_shortwave::solve_gpu(
             { bup.set_dims({co.n_out, n_lev, n_bnd}); bdn.set_dims({co.n_out, n_lev, n_bnd}); bdir.set_dims({co.n_out, n_lev, n_bnd}); bnet.set_dims({co.n_out, n_lev, n_bnd}); }
             struct Guard { bool& f; Guard(bool& f_) : f(f_) { f = true; } ~Guard() { f = false; } } guard(reordered_call);
             Sampling_reordered sampling(mcica_frac, mcica_alpha, mcica_col_id, mcica_col_offset, co);
+            Altitudes_reordered altitudes(sph_alt, sph_ref_alt, co);
             this->solve_gpu(switch_fluxes, switch_cloud_optics, switch_aerosol_optics, switch_output_optical, switch_output_bnd_fluxes,
                             switch_delta_cloud, switch_delta_aerosol, gases,
                             co.in2(p_lay), co.in2(p_lev), co.in2(t_lay), co.in2(t_lev), co.in2(col_dry),
@@ -861,12 +883,30 @@ void Radiation_solver_shortwave::solve_gpu(
 
         auto sub_last = [&](const Array_gpu<Float,2>& a) { return whole ? Array_gpu<Float,2>(const_cast<Float*>(a.ptr()), {n_bnd, n_in})
                                                                           : a.subset({{ {1, n_bnd}, {col_s, col_e} }}); };
+        // set_spherical_mu0: the block's cosines layer by layer, from its mu0, its altitudes and its reference altitudes
+        Array_gpu<Float,2> mu0_lay_s;
+        if (spherical)
+        {
+            mu0_lay_s.set_dims({n_in, n_lay});
+            const Array_gpu<Float,2> alt_s = sub2(*sph_alt, n_lay);
+            const Array_gpu<Float,1> ref_s = (sph_ref_alt != nullptr) ? sub1(*sph_ref_alt) : Array_gpu<Float,1>();
+            const Array_gpu<Float,1> mu0_s = sub1(mu0);
+            RRX_CALL(rrx_zenith_angle_spherical_correction, n_in, n_lay, sph_ref_alt != nullptr ? ref_s.ptr() : nullptr, mu0_s.ptr(), alt_s.ptr(),
+                     sph_radius, mu0_lay_s.ptr());
+        }
+        auto solve = [&](Array_gpu<Float,3>& up3, Array_gpu<Float,3>& dn3, Array_gpu<Float,3>& dir3)
+        {
+            if (spherical)
+                rte_sw.rte_sw(ws.optical_props, top_at_1, mu0_lay_s, toa_src_s, sub_last(sfc_alb_dir), sub_last(sfc_alb_dif), Array_gpu<Float,2>(), up3, dn3, dir3);
+            else
+                rte_sw.rte_sw(ws.optical_props, top_at_1, sub1(mu0), toa_src_s, sub_last(sfc_alb_dir), sub_last(sfc_alb_dif), Array_gpu<Float,2>(), up3, dn3, dir3);
+        };
         if (whole && broadband && !switch_output_bnd_fluxes)
         {
             // one block in broadband mode: the solver writes the caller's flux arrays, the net flux follows in place
             for (Array_gpu<Float,2>* a : {&sw_flux_up, &sw_flux_dn, &sw_flux_dn_dir, &sw_flux_net}) if (a->size() == 0) a->set_dims({n_col, n_lev});
             Array_gpu<Float,3> up3(sw_flux_up.ptr(), {n_col, n_lev, 1}), dn3(sw_flux_dn.ptr(), {n_col, n_lev, 1}), dir3(sw_flux_dn_dir.ptr(), {n_col, n_lev, 1});
-            rte_sw.rte_sw(ws.optical_props, top_at_1, sub1(mu0), toa_src_s, sub_last(sfc_alb_dir), sub_last(sfc_alb_dif), Array_gpu<Float,2>(), up3, dn3, dir3);
+            solve(up3, dn3, dir3);
             Fluxes_kernels_cuda::net_broadband_precalc(n_col, n_lev, sw_flux_dn.ptr(), sw_flux_up.ptr(), sw_flux_net.ptr());
             continue;
         }
@@ -895,8 +935,12 @@ void Radiation_solver_shortwave::solve_gpu(
                 up = Array_gpu<Float,2>(up_blk.ptr(), {n_in, n_lev}); dn = Array_gpu<Float,2>(dn_blk.ptr(), {n_in, n_lev});
                 dir = Array_gpu<Float,2>(dir_blk.ptr(), {n_in, n_lev}); net = Array_gpu<Float,2>(net_blk.ptr(), {n_in, n_lev});
             }
-            rte_sw.rte_sw_byband(ws.optical_props, top_at_1, sub1(mu0), toa_src_s, sub_last(sfc_alb_dir), sub_last(sfc_alb_dif),
-                                 Array_gpu<Float,2>(), bup, bdn, bdir, bnet, up, dn, dir);
+            if (spherical)
+                rte_sw.rte_sw_byband(ws.optical_props, top_at_1, mu0_lay_s, toa_src_s, sub_last(sfc_alb_dir), sub_last(sfc_alb_dif),
+                                     Array_gpu<Float,2>(), bup, bdn, bdir, bnet, up, dn, dir);
+            else
+                rte_sw.rte_sw_byband(ws.optical_props, top_at_1, sub1(mu0), toa_src_s, sub_last(sfc_alb_dir), sub_last(sfc_alb_dif),
+                                     Array_gpu<Float,2>(), bup, bdn, bdir, bnet, up, dn, dir);
             Fluxes_kernels_cuda::net_broadband_precalc(n_in, n_lev, dn.ptr(), up.ptr(), net.ptr());
             if (!whole)
             {
@@ -908,8 +952,7 @@ void Radiation_solver_shortwave::solve_gpu(
             }
             continue;
         }
-        rte_sw.rte_sw(ws.optical_props, top_at_1, sub1(mu0), toa_src_s, sub_last(sfc_alb_dir), sub_last(sfc_alb_dif),
-                Array_gpu<Float,2>(), ws.gpt_flux_up, ws.gpt_flux_dn, ws.gpt_flux_dn_dir);
+        solve(ws.gpt_flux_up, ws.gpt_flux_dn, ws.gpt_flux_dn_dir);
 
         Fluxes_broadband_gpu fluxes(n_in, n_lev);
         fluxes.reduce(ws.gpt_flux_up, ws.gpt_flux_dn, ws.gpt_flux_dn_dir, ws.optical_props, top_at_1);
@@ -930,6 +973,15 @@ void Radiation_solver_shortwave::solve_gpu(
 }
 
 void Radiation_solver_shortwave::set_sunlit_columns(const bool b) { sunlit_columns = b; }
+
+void Radiation_solver_shortwave::set_spherical_mu0(const Array_gpu<Float,2>* alt_lay, const Array_gpu<Float,1>* ref_alt, const Float planet_radius)
+{
+    if (alt_lay == nullptr && ref_alt != nullptr)
+        throw std::runtime_error("Radiation_solver_shortwave::set_spherical_mu0: ref_alt without alt_lay");
+    if (!(planet_radius > Float(0.)))
+        throw std::runtime_error("Radiation_solver_shortwave::set_spherical_mu0: planet_radius must be positive");
+    sph_alt = alt_lay; sph_ref_alt = (alt_lay != nullptr) ? ref_alt : nullptr; sph_radius = planet_radius;
+}
 
 void Radiation_solver_shortwave::set_cloud_sampling(const Array_gpu<Float,2>* cloud_frac, const int overlap, const Array_gpu<Float,2>* overlap_param,
                                                    const uint64_t seed, const int col_offset)

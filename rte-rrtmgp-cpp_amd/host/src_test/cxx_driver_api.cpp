@@ -23,6 +23,7 @@ namespace
         // broadband outputs of the last solve, (ncol, nlay+1) each: LW up, dn, net; SW up, dn, dn_dir, net
         Array_gpu<Float,2> lw_up, lw_dn, lw_net, sw_up, sw_dn, sw_dir, sw_net;
         Array_gpu<Float,2> cloud_frac, overlap_param;        // views of the caller's McICA fields (rrx_cxx_cloud_sampling)
+        Array_gpu<Float,2> alt_lay; Array_gpu<Float,1> ref_alt;   // views of the caller's altitudes (rrx_cxx_spherical_mu0)
     };
 
     template<typename Fn> int guarded(Fn&& f)
@@ -121,6 +122,17 @@ int rrx_cxx_cloud_sampling(void* h, const Float* cloud_frac, const int ncol, con
         const Array_gpu<Float,2>* a = overlap_param ? &d.overlap_param : nullptr;
         d.lw->set_cloud_sampling(f, overlap, a, seed, col_offset);
         d.sw->set_cloud_sampling(f, overlap, a, seed, col_offset);
+    });
+}
+
+int rrx_cxx_spherical_mu0(void* h, const Float* alt_lay, const int ncol, const int nlay, const Float* ref_alt, const double planet_radius)
+{
+    return guarded([&]
+    {
+        Driver& d = *static_cast<Driver*>(h);
+        d.alt_lay = view2(alt_lay, ncol, nlay);
+        d.ref_alt = view1(ref_alt, ncol);
+        d.sw->set_spherical_mu0(alt_lay ? &d.alt_lay : nullptr, ref_alt ? &d.ref_alt : nullptr, Float(planet_radius));
     });
 }
 

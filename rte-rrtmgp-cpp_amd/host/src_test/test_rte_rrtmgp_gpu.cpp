@@ -414,6 +414,7 @@ void solve_radiation(int argc, char** argv)
         {"lw-scattering"    , { false, "Longwave two-stream solve with cloud scattering (set_lw_scattering): band cloud tau / ssa / g; not with --lw-gauss-angles > 1, --lw-optimal-angles, --lw-jacobian, --byband-solvers or per-g-point solvers." }},
         {"lw-rescaling"     , { false, "Longwave no-scattering solve on rescaled optical depths with one correction sweep (set_lw_rescaling): band cloud tau / ssa / g; not with --lw-scattering, --lw-gauss-angles > 1, --lw-optimal-angles, --lw-jacobian, --byband-solvers or per-g-point solvers." }},
         {"cloud-fraction"   , { false, "McICA cloud sampling (set_cloud_sampling): every g-point sees a sub-column drawn from cloud_frac(lay, y, x) of the input file; needs --cloud-optics; not with --lw-scattering, --lw-rescaling or --sunlit-columns. Columns are then ordered on the device only." }},
+        {"sw-spherical-mu0" , { false, "Shortwave with a cosine of the solar zenith angle per layer (set_spherical_mu0): mu0 corrected for the planet's curvature with the layer altitudes z_lay(lay, y, x) [m] of the input file, mu0 holding at z_ref(y, x) if present, else at altitude 0." }},
         {"lw-jacobian"      , { false, "Write lw_flux_up_jac, d lw_flux_up / d t_sfc [W m-2 K-1] from the same LW solve (set_jacobian)." }},
         {"async"            , { false, "Host-model mode: vertical ordering read once, solves enqueued without synchronising." }},
         {"sort-columns"     , { true,  "Solve the columns in order of surface pressure where neighbours differ much (outputs keep the input order)." }},
@@ -480,6 +481,7 @@ void solve_radiation(int argc, char** argv)
         throw std::runtime_error("--cloud-fraction is not available with --lw-rescaling: the rescaled solver combines the band clouds itself");
     if (switch_cloud_fraction && switch_sunlit_columns)
         throw std::runtime_error("--cloud-fraction is not available with --sunlit-columns: the sunlit-only solve does not carry the column identities");
+    const bool switch_spherical_mu0     = command_line_options.at("sw-spherical-mu0").first;
     const bool switch_heating_rates     = command_line_options.at("heating-rates"    ).first;
     const bool switch_async             = command_line_options.at("async"            ).first;
     const bool switch_device_sort       = command_line_options.at("device-sort-columns").first;
@@ -577,6 +579,17 @@ void solve_radiation(int argc, char** argv)
         }
     }
 
+    Array<Float,2> z_lay;
+    Array<Float,1> z_ref;
+    if (switch_spherical_mu0)
+    {
+        if (!input_nc.variable_exists("z_lay"))
+            throw std::runtime_error("--sw-spherical-mu0: variable \"z_lay\" is not in the input file");
+        z_lay = shard2(Array<Float,2>(input_nc.get_variable<Float>("z_lay", {n_lay, n_col_y, n_col_x}), {n_col_glob, n_lay}));
+        if (input_nc.variable_exists("z_ref"))
+            z_ref = shard1(Array<Float,1>(input_nc.get_variable<Float>("z_ref", {n_col_y, n_col_x}), {n_col_glob}));
+    }
+
     ////// CREATE THE OUTPUT FILE //////
     Status::print_message("Preparing NetCDF output file.");
     // every rank runs the same output code on the gathered arrays; only rank 0's file is kept
@@ -594,6 +607,8 @@ void solve_radiation(int argc, char** argv)
     Array_gpu<Float,2> p_lay_gpu(p_lay), p_lev_gpu(p_lev), t_lay_gpu(t_lay), t_lev_gpu(t_lev), col_dry_gpu(col_dry);
     Array_gpu<Float,2> lwp_gpu(lwp), iwp_gpu(iwp), rel_gpu(rel), dei_gpu(dei);
     Array_gpu<Float,2> cloud_frac_gpu(cloud_frac), overlap_param_gpu(overlap_param);
+    Array_gpu<Float,2> z_lay_gpu(z_lay);
+    Array_gpu<Float,1> z_ref_gpu(z_ref);
 
     auto time_runs = [&](const std::string& name, const std::function<void()>& run)
     {
@@ -710,6 +725,8 @@ void solve_radiation(int argc, char** argv)
         rad_sw.set_column_padding(sort_requested || switch_device_sort);
         if (switch_cloud_fraction)
             rad_sw.set_cloud_sampling(&cloud_frac_gpu, cloud_overlap, cloud_overlap == 1 ? &overlap_param_gpu : nullptr, mcica_seed, ranks.col_s);
+        if (switch_spherical_mu0)
+            rad_sw.set_spherical_mu0(&z_lay_gpu, z_ref.size() > 0 ? &z_ref_gpu : nullptr);
         if (switch_async) rad_sw.set_vertical_ordering(p_lay({1, 1}) < p_lay({1, n_lay}) ? 1 : 0);
 
         const int n_bnd_sw = rad_sw.get_n_bnd_gpu();

@@ -184,6 +184,20 @@ def solve_sw(be, kd, atm, col_dry=None, cloud_lut=None, delta_cloud=False, do_br
     return out
 
 
+_STEP_ATMOSPHERE = None
+
+
+def _step_atmosphere_type():
+    """synthetic.Atmosphere with the per-column fields of ResidentSolver(mu0_lay= / altitude= / ref_altitude=) (private to the step)."""
+    global _STEP_ATMOSPHERE
+    if _STEP_ATMOSPHERE is None:
+        import dataclasses
+        from .synthetic import Atmosphere
+        _STEP_ATMOSPHERE = dataclasses.make_dataclass("StepAtmosphere", [(n, object, None) for n in ("mu0_lay", "altitude", "ref_altitude")],
+                                                      bases=(Atmosphere,))
+    return _STEP_ATMOSPHERE
+
+
 class ResidentSolver:
     """One full clear-sky LW+SW solve per ``step()`` with every buffer allocated once (what a host model keeps
     resident between radiation calls, cf. the cached subsets in /root/reference/src_test/Radiation_solver.cu:450-466).
@@ -194,9 +208,27 @@ class ResidentSolver:
 
     def __init__(self, be, kd_lw, kd_sw, atm, do_broadband=False, overlap=False, cloud_luts=None, sort_columns=None, byband=False,
                  sunlit=False, jacobian=False, n_gauss_angles=1, optimal_angles=False, keep_secants=False, lw_scattering=False,
-                 lw_rescaling=False, cloud_fraction=None, cloud_overlap="max_ran", overlap_param=None, mcica_seed=0, mcica_col_offset=0):
+                 lw_rescaling=False, cloud_fraction=None, cloud_overlap="max_ran", overlap_param=None, mcica_seed=0, mcica_col_offset=0,
+                 mu0_lay=None, altitude=None, ref_altitude=None, planet_radius=6.37123e6):
         import torch
         self.torch = torch
+        # mu0 by layer: the SW solver takes a cosine of the solar zenith angle per layer. mu0_lay: (nlay, ncol) in the
+        # caller's column order, used as it is. altitude: (nlay, ncol) layer altitudes in metres, with ref_altitude (ncol, default 0) the
+        # altitude at which atm.mu0 holds: every step forms mu0_lay on the device from the current atm.mu0 by the spherical-geometry
+        # correction (zenith_angle_spherical_correction). The fields stay attributes: replace or update them between steps. They are
+        # per-column fields (_COLUMN_FIELDS): sorted, padded and gathered to the sunlit columns with the others. The sunlit list is
+        # made from atm.mu0 in either case; the LW chain does not see any of this.
+        self.mu0_lay, self.altitude, self.ref_altitude, self.planet_radius = mu0_lay, altitude, ref_altitude, float(planet_radius)
+        if mu0_lay is not None and altitude is not None:
+            raise ValueError("ResidentSolver: mu0_lay and altitude are two ways to the same thing: give one")
+        if ref_altitude is not None and altitude is None:
+            raise ValueError("ResidentSolver: ref_altitude without altitude")
+        for name, v, want in (("mu0_lay", mu0_lay, (atm.nlay, atm.ncol)), ("altitude", altitude, (atm.nlay, atm.ncol)),
+                              ("ref_altitude", ref_altitude, (atm.ncol,))):
+            if v is not None and tuple(v.shape) != want:
+                raise ValueError(f"ResidentSolver: {name} {tuple(v.shape)} is not {want}")
+        if altitude is not None and bool((altitude < (0. if ref_altitude is None else ref_altitude)).any()):
+            raise ValueError("ResidentSolver: an altitude lies below its column's reference altitude")
         # cloud_fraction: McICA cloud sampling. (nlay, ncol) cloud fractions in the caller's column order; each step runs
         # the CLEAR gas optics and then rrx_mcica_increment_*, which gives every g-point its own sub-column and adds the band cloud
         # properties in the cloudy cells only. cloud_overlap: "max_ran", or "exp_ran" with overlap_param (nlay-1, ncol), the overlap
@@ -371,7 +403,7 @@ class ResidentSolver:
             self.sun_wait_ms = 0.0      # host time spent waiting for the count, summed over the steps
             self.sun_in = {}            # gathered SW inputs, (..., ncol) fields at full width
             for k in self._SW_FIELDS:
-                v = getattr(atm, k)
+                v = getattr(self._step_atmosphere(), k, None)
                 if v is not None and (cloud_luts is not None or k not in ("lwp", "iwp", "rel", "dei")):
                     self.sun_in[k] = e(tuple(v.shape[:-1]) + (ncol,) if self._COLUMN_FIELDS[k] < 0 else (ncol,) + tuple(v.shape[1:]))
             self.sun_vmr = {n: e((nlay, ncol)) for n, t in atm.vmr.items() if hasattr(t, "dim") and t.dim() == 2}
@@ -385,6 +417,7 @@ class ResidentSolver:
         self.optimal_fit = be.optimal_fit_abi(kd_lw) if self.optimal_angles else None
         self.lw_secants = e((ng_l, ncol)) if self.keep_secants else None
         self.sfc_emis_gpt = e((ng_l, ncol)); self.alb_dir = e((ng_s, ncol)); self.alb_dif = e((ng_s, ncol))
+        self.mu0_lay_step = e((nlay, ncol)) if self.altitude is not None else None      # the step's corrected cosines
         self.events = None
         self.col_dry2 = None
 
@@ -402,9 +435,19 @@ class ResidentSolver:
 
     # per-column fields of an Atmosphere and the axis their column index sits on (everything else is shared by all columns)
     _COLUMN_FIELDS = {"p_lay": -1, "p_lev": -1, "t_lay": -1, "t_lev": -1, "t_sfc": 0, "mu0": 0, "tsi_scaling": 0,
-                      "emis_sfc": 0, "sfc_alb_dir": 0, "sfc_alb_dif": 0, "lwp": -1, "iwp": -1, "rel": -1, "dei": -1, "rh": -1}
+                      "emis_sfc": 0, "sfc_alb_dir": 0, "sfc_alb_dif": 0, "lwp": -1, "iwp": -1, "rel": -1, "dei": -1, "rh": -1,
+                      "mu0_lay": -1, "altitude": -1, "ref_altitude": 0}
 
-    _SW_FIELDS = ("p_lay", "p_lev", "t_lay", "mu0", "tsi_scaling", "sfc_alb_dir", "sfc_alb_dif", "lwp", "iwp", "rel", "dei")
+    _SW_FIELDS = ("p_lay", "p_lev", "t_lay", "mu0", "tsi_scaling", "sfc_alb_dir", "sfc_alb_dif", "lwp", "iwp", "rel", "dei",
+                  "mu0_lay", "altitude", "ref_altitude")
+
+    def _step_atmosphere(self):
+        """The caller's atmosphere; with mu0_lay= / altitude=, a view of it that carries the solver's own per-column fields (mu0_lay,
+        altitude, ref_altitude) beside the atmosphere's, so that the gathers below take them along. The fields exist on that view
+        only: the solver's arguments are the one way in, an Atmosphere has no such fields."""
+        if self.mu0_lay is None and self.altitude is None:
+            return self.atm
+        return _step_atmosphere_type()(**self.atm.__dict__, mu0_lay=self.mu0_lay, altitude=self.altitude, ref_altitude=self.ref_altitude)
 
     @staticmethod
     def _cols(t, n):
@@ -421,11 +464,13 @@ class ResidentSolver:
     def _sunlit_atmosphere(self, n_out):
         """The SW inputs of the columns sun_perm[:n_out], gathered on the device into the resident buffers (views of n_out columns)."""
         from .synthetic import Atmosphere
-        be, a, perm = self.be, self.atm, self.sun_perm
+        be, a, perm = self.be, self._step_atmosphere(), self.sun_perm
         out = dict(a.__dict__)         # (fields the SW chain does not read stay as they are)
         out["ncol"] = n_out
         for k, buf in self.sun_in.items():
-            v = getattr(a, k)
+            v = getattr(a, k, None)
+            if v is None:                  # (a field of the solver's that the host has taken away since)
+                continue
             if self._COLUMN_FIELDS[k] < 0 or v.dim() == 1:        # column fastest: (..., ncol) or (ncol,)
                 o = self._cols(buf, n_out) if self._COLUMN_FIELDS[k] < 0 else buf[:n_out]
                 nrest = int(np.prod(v.shape[:-1], dtype=np.int64)) if v.dim() > 1 else 1
@@ -443,7 +488,7 @@ class ResidentSolver:
             else:
                 vmr[n] = t
         out["vmr"] = vmr
-        return Atmosphere(**out)
+        return type(a)(**out)
 
     def refresh_column_order(self):
         """(Re)build the gather index of a step: ascending surface pressure when sorting, the caller's order otherwise, padded with
@@ -462,7 +507,7 @@ class ResidentSolver:
     def _gathered_atmosphere(self):
         """The atmosphere with its columns in the order (and count) of self.perm."""
         from .synthetic import Atmosphere
-        a, perm = self.atm, self.perm
+        a, perm = self._step_atmosphere(), self.perm
         out = {}
         for k, v in a.__dict__.items():
             if k == "ncol":
@@ -473,10 +518,10 @@ class ResidentSolver:
                 out[k] = {n: (t.index_select(1, perm) if (hasattr(t, "dim") and t.dim() == 2) else t) for n, t in v.items()}
             else:
                 out[k] = v
-        return Atmosphere(**out)
+        return type(a)(**out)
 
     def step(self):
-        be, atm = self.be, self.atm
+        be, atm = self.be, self._step_atmosphere()
         perm = self.perm
         if perm is not None:
             atm = self._gathered_atmosphere()
@@ -637,7 +682,20 @@ class ResidentSolver:
                 mark("sw_solver")
                 be._c("expand_and_transpose", ncol, kd.nbnd, kd.band_lims_gpt, atm.sfc_alb_dir, alb_dir)
                 be._c("expand_and_transpose", ncol, kd.nbnd, kd.band_lims_gpt, atm.sfc_alb_dif, alb_dif)
-                if self.byband:
+                mu0_lay = getattr(atm, "mu0_lay", None)      # (a field of the step's view: None without mu0_lay= / altitude=)
+                if self.altitude is not None:     # the sun rises with altitude: this step's cosines from the current mu0
+                    mu0_lay = be.zenith_angle_spherical_correction(atm.mu0, atm.altitude, atm.ref_altitude, self.planet_radius,
+                                                                   out=self._cols(self.mu0_lay_step, ncol))
+                if mu0_lay is not None and self.byband:
+                    be.sw_solver_2stream_byband_mu0lay(atm.top_at_1, buf["tau"], buf["ssa"], gbuf, mu0_lay, alb_dir, alb_dif, toa,
+                                                       kd.band_lims_gpt, out=dict(bnd_flux_up=BS[0], bnd_flux_dn=BS[1], bnd_flux_dir=BS[2],
+                                                                                  bnd_flux_net=BS[3], flux_up=F[3], flux_dn=F[4], flux_dir=F[5]))
+                elif mu0_lay is not None:
+                    be.sw_solver_2stream_mu0lay(atm.top_at_1, buf["tau"], buf["ssa"], gbuf, mu0_lay, alb_dir, alb_dif, toa,
+                                                do_broadband=self.do_broadband,
+                                                out=dict(flux_up=F[3], flux_dn=F[4], flux_dir=F[5]) if self.do_broadband else
+                                                dict(flux_up=buf["gpt_up"], flux_dn=buf["gpt_dn"], flux_dir=buf["gpt_dir"]))
+                elif self.byband:
                     be.sw_solver_2stream_byband(atm.top_at_1, buf["tau"], buf["ssa"], gbuf, atm.mu0, alb_dir, alb_dif, toa,
                                                 kd.band_lims_gpt, out=dict(bnd_flux_up=BS[0], bnd_flux_dn=BS[1], bnd_flux_dir=BS[2],
                                                                            bnd_flux_net=BS[3], flux_up=F[3], flux_dn=F[4], flux_dir=F[5]))

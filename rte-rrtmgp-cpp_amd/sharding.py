@@ -45,6 +45,18 @@ def shard_cloud_sampling(cloud_fraction, overlap_param, rank, world):
     return dict(cloud_fraction=cut(cloud_fraction), overlap_param=cut(overlap_param), mcica_col_offset=s)
 
 
+def shard_sw_geometry(rank, world, mu0_lay=None, altitude=None, ref_altitude=None):
+    """This rank's mu0-by-layer arguments of pipeline.ResidentSolver from the whole domain's mu0_lay or altitude (nlay, ncol) and
+    ref_altitude ((ncol,) or None), numpy or torch: the column slices of what is given (the column index is the last axis of each)."""
+    first = next((a for a in (mu0_lay, altitude, ref_altitude) if a is not None), None)
+    if first is None:
+        return {}
+    s, e = column_range(rank, world, first.shape[-1])
+    cut = lambda a: a[..., s:e].contiguous() if hasattr(a, "contiguous") else a[..., s:e].copy()
+    given = dict(mu0_lay=mu0_lay, altitude=altitude, ref_altitude=ref_altitude)
+    return {k: cut(a) for k, a in given.items() if a is not None}
+
+
 def gather_fluxes(local, ncol_total, group=None):
     """All-gather packed fluxes (nflux, nlev, ncol_local) -> (nflux, nlev, ncol_total) on every rank.
     Uneven shards are padded to the largest one so that a single all_gather_into_tensor suffices."""

@@ -129,8 +129,9 @@ def write_cloud_lut(path, lut):
     rrxio.write(path, dims, v)
 
 
-def write_input(path, atm, nbnd_lw, nbnd_sw, cloud_frac=None, overlap_param=None):
-    """cloud_frac (nlay, ncol) / overlap_param (nlay-1, ncol): the McICA fields the driver reads with --cloud-fraction."""
+def write_input(path, atm, nbnd_lw, nbnd_sw, cloud_frac=None, overlap_param=None, z_lay=None, z_ref=None):
+    """cloud_frac (nlay, ncol) / overlap_param (nlay-1, ncol): the McICA fields the driver reads with --cloud-fraction.
+    z_lay (nlay, ncol) / z_ref (ncol): layer altitudes and the altitude at which mu0 holds [m], read with --sw-spherical-mu0."""
     ncol, nlay = atm.ncol, atm.nlay
     dims = dict(x=ncol, y=1, lay=nlay, lev=nlay+1, band_lw=nbnd_lw, band_sw=nbnd_sw)
     f3 = lambda a: a.reshape(a.shape[0], 1, ncol)
@@ -153,6 +154,10 @@ def write_input(path, atm, nbnd_lw, nbnd_sw, cloud_frac=None, overlap_param=None
     if overlap_param is not None:
         dims["lay_below"] = nlay - 1
         v["overlap_param"] = (f3(np.ascontiguousarray(overlap_param)), ["lay_below", "y", "x"])
+    if z_lay is not None:
+        v["z_lay"] = (f3(np.ascontiguousarray(z_lay)), ["lay", "y", "x"])
+    if z_ref is not None:
+        v["z_ref"] = (np.ascontiguousarray(z_ref).reshape(1, ncol), ["y", "x"])
     if atm.rh is not None:
         v["rh"] = (f3(atm.rh), ["lay", "y", "x"])
         for k, a in atm.aermr.items():
@@ -172,7 +177,8 @@ def write_aerosol_lut(path, lut):
     rrxio.write(path, dims, v)
 
 
-def write_case(directory, atm, kd_lw, kd_sw, lut_lw=None, lut_sw=None, lut_aerosol=None, cloud_frac=None, overlap_param=None):
+def write_case(directory, atm, kd_lw, kd_sw, lut_lw=None, lut_sw=None, lut_aerosol=None, cloud_frac=None, overlap_param=None,
+               z_lay=None, z_ref=None):
     """Everything the C++ driver expects in its working directory (file names of the reference's make_links.sh)."""
     os.makedirs(directory, exist_ok=True)
     write_kdist(os.path.join(directory, "coefficients_lw.nc"), kd_lw)
@@ -182,4 +188,4 @@ def write_case(directory, atm, kd_lw, kd_sw, lut_lw=None, lut_sw=None, lut_aeros
         write_cloud_lut(os.path.join(directory, "cloud_coefficients_sw.nc"), lut_sw)
     if lut_aerosol is not None:
         write_aerosol_lut(os.path.join(directory, "aerosol_optics.nc"), lut_aerosol)
-    write_input(os.path.join(directory, "rte_rrtmgp_input.nc"), atm, kd_lw.nbnd, kd_sw.nbnd, cloud_frac, overlap_param)
+    write_input(os.path.join(directory, "rte_rrtmgp_input.nc"), atm, kd_lw.nbnd, kd_sw.nbnd, cloud_frac, overlap_param, z_lay, z_ref)

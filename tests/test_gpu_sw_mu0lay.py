@@ -1,0 +1,501 @@
+"""GPU tests of the SW two-stream solver with a cosine of the solar zenith angle per layer (rrx_sw_solver_2stream_mu0lay,
+rrx_sw_solver_2stream_byband_mu0lay), the spherical-geometry correction that makes such cosines (rrx_zenith_angle_spherical_correction),
+the CPU boundary's by-layer route and pipeline.ResidentSolver(mu0_lay= / altitude=).
+
+The solver tests draw mu0_lay independently per layer and column from [0.05, 1] (tests/sw_mu0_ref.py): less physical than a smooth
+profile, but every index slip shows. Reference: the CPU oracle, whose rte_sw_solver_2stream has the per-layer semantics.
+
+Tolerances (cases.rel_err with the floors of the random golden comparison): 1e-10 in fp64, 1e-3 in fp32, with one exception that is
+stated where it applies. Like the random golden case these inputs have a g-point (index 1) that scatters conservatively (ssa = 1, the
+k_min clamp), and there the reference is ill-conditioned: the oracle itself moves by 2e-12 ... 3e-11 when every tau moves by ONE ulp
+(1e-15 in the other g-points), while the kernels' exp and Newton reciprocals differ from libm's by several ulps. So
+  - every comparison of the by-layer entries with the 1-D entries (constant rows) is held to 1e-10 / 1e-3;
+  - per-g-point fluxes: every g-point but the conservative one is held to 1e-10 / 1e-3; the conservative one to CONS64 in fp64;
+  - g-point sums (broadband, by band): the same kernels are run on the inputs WITHOUT the conservative g-point and held to
+    1e-10 / 1e-3; the sums over all g-points are held to CONS64 in fp64 and TOL32_BB in fp32.
+CONS64 = 1e-9: a few tens of ulps of tau at the oracle's 3e-11 per ulp; measured on the MI355X, worst over all cases, 4.4e-10 per
+g-point and 4.6e-10 in the sums (the 1-D entry on the same inputs with constant rows: 1.2e-10, as the by-layer entry), so the bound is
+twice what is observed."""
+import functools
+
+import numpy as np
+import pytest
+
+import cases
+import cpu_boundary
+import support_ref
+import sw_mu0_ref
+from rte_rrtmgp_cpp_amd import synthetic, pipeline
+
+pytestmark = pytest.mark.gpu
+TOL = {"f64": 1e-10, "f32": 1e-3}
+FLOOR = {"f64": 1e-6, "f32": 1e-2}
+CONS64 = 1e-9             # fp64 fluxes that hold the conservative-scattering g-point: see the module's docstring (measured 4.6e-10)
+# fp32 does not hold 1e-3 in the g-point sums over ALL g-points of these inputs: they carry the conservative-scattering g-point, whose
+# fluxes have few digits in single precision (k_min = 1e-4 there: 1 - exp(-2 k tau) cancels). Measured on the MI355X, worst over g / no g
+# and both orderings, flux_up: by-layer entry 2.97e-3; the 1-D entry on the same inputs with constant rows 2.41e-3
+# (test_fp32_broadband_error_of_the_one_dimensional_entry prints them). By the project's fp32 rule the bound is twice the by-layer figure.
+TOL32_BB = 6e-3
+CONS = {"f64": CONS64, "f32": TOL["f32"]}             # per-g-point fluxes of the conservative g-point
+SUMS = {"f64": CONS64, "f32": TOL32_BB}               # sums over all g-points
+KEYS = ("flux_up", "flux_dn", "flux_dir")
+BKEYS = ("bnd_flux_up", "bnd_flux_dn", "bnd_flux_dir")
+
+
+def _np_dtype(dt):
+    return np.float64 if dt == "f64" else np.float32
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs(dt, ncol, nlay, ngpt, rest=False):
+    """The seeded inputs in the precision of the run (shared by the tests, never written to). rest: the same inputs without the
+    conservative-scattering g-point (ngpt - 1 g-points)."""
+    if rest:
+        full = _inputs(dt, ncol, nlay, ngpt)
+        d = {k: (v if k == "mu0_lay" else np.ascontiguousarray(np.delete(v, 1, axis=0))) for k, v in full.items()}
+    else:
+        d = sw_mu0_ref.solver_inputs(1000*ncol + 10*nlay + ngpt, ncol, nlay, ngpt)
+        d = {k: np.ascontiguousarray(v.astype(_np_dtype(dt))) for k, v in d.items()}
+    for v in d.values():
+        v.setflags(write=False)
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(dt, ncol, nlay, ngpt, top_at_1, dif=False, rest=False):
+    """The oracle's per-g-point fluxes with mu0 (nlay, ncol), computed once per case."""
+    import oracle_py
+    orc = oracle_py.CpuKernels("oracle", _np_dtype(dt))
+    I = _inputs(dt, ncol, nlay, ngpt, rest)
+    r = orc.sw_solver_2stream(top_at_1, I["tau"], I["ssa"], I["g"], I["mu0_lay"], I["adir"], I["adif"], I["inc"],
+                              I["inc_dif"] if dif else None)
+    for v in r.values():
+        v.setflags(write=False)
+    return r
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_broadband(dt, ncol, nlay, ngpt, top_at_1, with_g, rest=False):
+    import oracle_py
+    orc = oracle_py.CpuKernels("oracle", _np_dtype(dt))
+    I = _inputs(dt, ncol, nlay, ngpt, rest)
+    g = I["g"] if with_g else np.zeros_like(I["g"])
+    return orc.sw_solver_2stream(top_at_1, I["tau"], I["ssa"], g, I["mu0_lay"], I["adir"], I["adif"], I["inc"], do_broadband=True)
+
+
+def _be(dt, hip_f64, hip_f32):
+    return hip_f64 if dt == "f64" else hip_f32
+
+
+def _args(be, I, g=True):
+    up = be.asarray
+    return (up(I["tau"]), up(I["ssa"]), up(I["g"]) if g else None, up(I["mu0_lay"]), up(I["adir"]), up(I["adif"]), up(I["inc"]))
+
+
+def _check(be, dt, got, want, what, tol, keys=KEYS):
+    """Every figure is printed before any is asserted."""
+    errs = {k: cases.rel_err(got[k] if isinstance(got[k], np.ndarray) else be.to_numpy(got[k]), want[k], FLOOR[dt]) for k in keys}
+    for k, e in errs.items():
+        print(f"{what} {dt} {k}: rel err {e:.3e} (bound {tol:.0e})")
+    for k, e in errs.items():
+        assert e <= tol, f"{what} {k}: rel err {e:.3e} > {tol:.1e}"
+
+
+def _check_per_gpoint(be, dt, got, want, what):
+    """(ngpt, nlev, ncol) fluxes: the conservative-scattering g-point (index 1) at CONS, every other g-point at the plain tolerance."""
+    ngpt = want[KEYS[0]].shape[0]
+    rest = [ig for ig in range(ngpt) if ig != 1]
+    N = be.to_numpy
+    _check(be, dt, {k: N(got[k])[rest] for k in KEYS}, {k: want[k][rest] for k in KEYS}, what + ", all but the conservative g-point", TOL[dt])
+    if ngpt > 1:
+        _check(be, dt, {k: N(got[k])[1:2] for k in KEYS}, {k: want[k][1:2] for k in KEYS}, what + ", the conservative g-point", CONS[dt])
+
+
+# ---- 1, 4: the per-g-point entry (scan kernel: K = 2, 4, 9 layers per lane; serial kernel) ----------------------------------------
+PER_GPT_SHAPES = [(17, 1, 3), (17, 33, 5), (17, 140, 4)]
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("top_at_1", [False, True])
+@pytest.mark.parametrize("shape", PER_GPT_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_per_gpoint_entry_matches_the_oracle(shape, top_at_1, dt, hip_f64, hip_f32, oracle_built):
+    be = _be(dt, hip_f64, hip_f32)
+    I = _inputs(dt, *shape)
+    got = be.sw_solver_2stream_mu0lay(top_at_1, *_args(be, I))
+    _check_per_gpoint(be, dt, got, _oracle(dt, *shape, top_at_1), f"per-g-point {shape} top_at_1={top_at_1}")
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+def test_per_gpoint_entry_with_diffuse_incident_flux(dt, hip_f64, hip_f32, oracle_built):
+    be = _be(dt, hip_f64, hip_f32)
+    shape = (17, 33, 5)
+    I = _inputs(dt, *shape)
+    got = be.sw_solver_2stream_mu0lay(True, *_args(be, I), inc_flux_dif=be.asarray(I["inc_dif"]))
+    want = _oracle(dt, *shape, True, True)
+    assert not np.array_equal(want["flux_dn"], _oracle(dt, *shape, True)["flux_dn"])
+    _check_per_gpoint(be, dt, got, want, "has_dif_bc")
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("top_at_1", [False, True])
+def test_serial_kernel_matches_the_oracle(top_at_1, dt, hip_f64, hip_f32, oracle_built):
+    be = _be(dt, hip_f64, hip_f32)
+    shape = (17, 33, 5)
+    I, R = _inputs(dt, *shape), _inputs(dt, *shape, True)
+    be.set_variant(sw=1)
+    try:
+        got = be.sw_solver_2stream_mu0lay(top_at_1, *_args(be, I))
+        bb = be.sw_solver_2stream_mu0lay(top_at_1, *_args(be, I), do_broadband=True)
+        bb_rest = be.sw_solver_2stream_mu0lay(top_at_1, *_args(be, R), do_broadband=True)
+    finally:
+        be.set_variant(sw=0)
+    _check_per_gpoint(be, dt, got, _oracle(dt, *shape, top_at_1), "serial kernel")
+    _check(be, dt, bb_rest, _oracle_broadband(dt, *shape, top_at_1, True, True), "serial kernel + sums, without the conservative g-point", TOL[dt])
+    _check(be, dt, bb, _oracle_broadband(dt, *shape, top_at_1, True), "serial kernel + sums", max(CONS64, TOL[dt]))
+
+
+# ---- 2: fused broadband form; taller columns: the per-g-point route and its sums ----------------------------------------------------
+BB_SHAPES = [(17, 140, 16), (40, 33, 16), (16, 200, 8), (16, 300, 4)]
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("with_g", [True, False], ids=["g", "g_null"])
+@pytest.mark.parametrize("top_at_1", [False, True])
+@pytest.mark.parametrize("shape", BB_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_broadband_entry_matches_the_oracle(shape, top_at_1, with_g, dt, hip_f64, hip_f32, oracle_built):
+    be = _be(dt, hip_f64, hip_f32)
+    what = f"broadband {shape} top_at_1={top_at_1} g={with_g}"
+    # the same kernels on the inputs without the conservative-scattering g-point: the plain tolerance
+    rest = be.sw_solver_2stream_mu0lay(top_at_1, *_args(be, _inputs(dt, *shape, True), g=with_g), do_broadband=True)
+    # ... and on all g-points
+    got = be.sw_solver_2stream_mu0lay(top_at_1, *_args(be, _inputs(dt, *shape), g=with_g), do_broadband=True)
+    for k in KEYS:
+        assert tuple(got[k].shape) == (shape[1]+1, shape[0])
+    _check(be, dt, rest, _oracle_broadband(dt, *shape, top_at_1, with_g, True), what + ", without the conservative g-point", TOL[dt])
+    _check(be, dt, got, _oracle_broadband(dt, *shape, top_at_1, with_g), what, SUMS[dt])
+
+
+@pytest.mark.parametrize("shape", [(17, 140, 16), (16, 200, 8)], ids=lambda s: "x".join(map(str, s)))
+def test_fp32_broadband_error_of_the_one_dimensional_entry(shape, hip_f32, oracle_built):
+    """The measurement behind TOL32_BB: the 1-D entry's own broadband error on the same inputs with constant rows (row 3 of mu0_lay)."""
+    import oracle_py
+    be, orc = hip_f32, oracle_py.CpuKernels("oracle", np.float32)
+    I = _inputs("f32", *shape)
+    mu0 = np.ascontiguousarray(I["mu0_lay"][3])
+    up = be.asarray
+    for top_at_1 in (False, True):
+        for with_g in (True, False):
+            g = I["g"] if with_g else np.zeros_like(I["g"])
+            want = orc.sw_solver_2stream(top_at_1, I["tau"], I["ssa"], g, mu0, I["adir"], I["adif"], I["inc"], do_broadband=True)
+            got = be.sw_solver_2stream(top_at_1, up(I["tau"]), up(I["ssa"]), up(I["g"]) if with_g else None, up(mu0), up(I["adir"]), up(I["adif"]),
+                                       up(I["inc"]), do_broadband=True)
+            _check(be, "f32", got, want, f"1-D entry, broadband {shape} top_at_1={top_at_1} g={with_g}", TOL32_BB)
+
+
+# ---- 3: by band ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("top_at_1", [False, True])
+def test_byband_entry_matches_the_band_sums_of_the_oracle(top_at_1, dt, hip_f64, hip_f32, oracle_built):
+    be = _be(dt, hip_f64, hip_f32)
+    shape = (17, 140, 16)
+    N = be.to_numpy
+    # (the middle band is empty; the first band holds the conservative-scattering g-point)
+    for rest, lims, what, tol in ((True, [[1, 6], [7, 6], [7, 15]], "by band, without the conservative g-point", TOL[dt]),
+                                  (False, [[1, 7], [8, 7], [8, 16]], "by band", None)):
+        lims = np.array(lims, dtype=np.int32)
+        got = be.sw_solver_2stream_byband_mu0lay(top_at_1, *_args(be, _inputs(dt, *shape, rest)), be.asarray(lims))
+        per_gpt = _oracle(dt, *shape, top_at_1, False, rest)
+        want = {"bnd_" + k: support_ref.sum_byband(per_gpt[k], lims) for k in KEYS}
+        if rest:
+            _check(be, dt, got, want, what, tol, keys=BKEYS)
+        else:        # the band without the conservative g-point at the plain tolerance, the band with it at the sums' bound
+            _check(be, dt, {k: N(got[k])[2] for k in BKEYS}, {k: want[k][2] for k in BKEYS}, what + ", last band", TOL[dt], keys=BKEYS)
+            _check(be, dt, {k: N(got[k])[0] for k in BKEYS}, {k: want[k][0] for k in BKEYS}, what + ", first band", max(CONS64, TOL[dt]), keys=BKEYS)
+        for k in KEYS:
+            assert not N(got["bnd_" + k])[1].any()                           # the empty band: zeros
+            b = N(got["bnd_" + k])
+            acc = b[0].copy()
+            for ib in range(1, 3):
+                acc += b[ib]
+            assert np.array_equal(N(got[k]), acc), k                         # broadband = the band sums added in band order
+        assert np.array_equal(N(got["bnd_flux_net"]), N(got["bnd_flux_dn"]) - N(got["bnd_flux_up"]))
+
+
+# ---- 5: constant rows = the 1-D entries --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("top_at_1", [False, True])
+def test_constant_rows_agree_with_the_one_dimensional_entries(top_at_1, dt, hip_f64, hip_f32, oracle_built):
+    """Kernel against kernel on the same inputs, the conservative g-point included: the plain tolerance (observed 1.6e-13 per g-point and
+    1.4e-15 in broadband mode in fp64, 1.6e-5 / 2.8e-7 in fp32)."""
+    be = _be(dt, hip_f64, hip_f32)
+    shape = (17, 140, 16)
+    I = dict(_inputs(dt, *shape))
+    mu0 = np.ascontiguousarray(I["mu0_lay"][3])
+    I["mu0_lay"] = np.ascontiguousarray(np.repeat(mu0[None, :], shape[1], axis=0))
+    a = _args(be, I)
+    one = a[:3] + (be.asarray(mu0),) + a[4:]
+    lims = be.asarray(np.array([[1, 7], [8, 7], [8, 16]], dtype=np.int32))
+    N = be.to_numpy
+    for what, lay, ref, keys in (
+            ("per g-point", be.sw_solver_2stream_mu0lay(top_at_1, *a), be.sw_solver_2stream(top_at_1, *one), KEYS),
+            ("broadband", be.sw_solver_2stream_mu0lay(top_at_1, *a, do_broadband=True), be.sw_solver_2stream(top_at_1, *one, do_broadband=True), KEYS),
+            ("by band", be.sw_solver_2stream_byband_mu0lay(top_at_1, *a, lims), be.sw_solver_2stream_byband(top_at_1, *one, lims),
+             KEYS + BKEYS + ("bnd_flux_net",))):
+        _check(be, dt, lay, {k: N(ref[k]) for k in keys}, "constant rows, " + what, TOL[dt], keys=keys)
+    # how far either entry is from the oracle on these inputs (the docstring's figures)
+    import oracle_py
+    want = oracle_py.CpuKernels("oracle", _np_dtype(dt)).sw_solver_2stream(top_at_1, I["tau"], I["ssa"], I["g"], I["mu0_lay"], I["adir"], I["adif"], I["inc"])
+    _check_per_gpoint(be, dt, be.sw_solver_2stream(top_at_1, *one), want, "1-D entry against the oracle")
+    _check_per_gpoint(be, dt, be.sw_solver_2stream_mu0lay(top_at_1, *a), want, "by-layer entry, constant rows, against the oracle")
+
+
+# ---- 6: the top boundary takes the top layer's cosine ------------------------------------------------------------------------------
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("top_at_1", [False, True])
+def test_direct_beam_at_the_top_is_the_incident_flux_times_the_top_layers_cosine(top_at_1, dt, hip_f64, hip_f32):
+    be = _be(dt, hip_f64, hip_f32)
+    shape = (17, 33, 5)
+    I = _inputs(dt, *shape)
+    top_lay, top_lev = (0, 0) if top_at_1 else (shape[1]-1, shape[1])
+    assert not np.allclose(I["mu0_lay"][0], I["mu0_lay"][-1])
+    want = I["inc"] * I["mu0_lay"][top_lay][None, :]                       # one product per g-point: exact in the run's precision
+    got = be.to_numpy(be.sw_solver_2stream_mu0lay(top_at_1, *_args(be, I))["flux_dir"])
+    assert np.array_equal(got[:, top_lev, :], want)
+    bb = be.to_numpy(be.sw_solver_2stream_mu0lay(top_at_1, *_args(be, I), do_broadband=True)["flux_dir"])
+    # summed over the g-points (five positive terms, in ranges when the g-point loop is split: a few roundings of the sum)
+    acc = want.astype(np.float64).sum(axis=0)
+    assert np.all(np.abs(bb[top_lev] - acc) <= 8*np.finfo(_np_dtype(dt)).eps*acc)
+    # the other end's row would not do
+    other = (I["inc"] * I["mu0_lay"][shape[1]-1-top_lay][None, :]).astype(np.float64).sum(axis=0)
+    assert np.abs(bb[top_lev] - other).max() > 1e-2*acc.max()
+
+
+# ---- 7: the correction kernel ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("with_ref_alt", [True, False])
+def test_spherical_correction_matches_the_numpy_reference(with_ref_alt, dt, hip_f64, hip_f32):
+    be = _be(dt, hip_f64, hip_f32)
+    F = _np_dtype(dt)
+    ncol, nlay = 70, 5
+    rng = np.random.default_rng(70)
+    ref_mu = rng.uniform(0.0, 1.0, ncol)
+    ref_mu[::9] = 0.0; ref_mu[4::13] = -rng.uniform(0., 1., ref_mu[4::13].size); ref_mu[5] = -0.0; ref_mu[7] = 1.0
+    ref_mu = ref_mu.astype(F)
+    ref_alt = rng.uniform(0., 4000., ncol).astype(F) if with_ref_alt else None
+    alt = ((np.zeros(ncol) if ref_alt is None else ref_alt)[None, :] + np.sort(rng.uniform(0., 70e3, (nlay, ncol)), axis=0)).astype(F)
+    want = sw_mu0_ref.spherical_mu0(ref_mu, alt, ref_alt)
+    got = be.to_numpy(be.zenith_angle_spherical_correction(be.asarray(ref_mu), be.asarray(alt), None if ref_alt is None else be.asarray(ref_alt)))
+    assert got.shape == (nlay, ncol) and got.dtype == F
+    dark = ref_mu <= 0
+    assert dark.sum() >= 10 and np.array_equal(got[:, dark], np.broadcast_to(ref_mu[None, dark], (nlay, int(dark.sum()))))
+    e = float(np.max(np.abs(got.astype(np.float64) - want.astype(np.float64))))
+    print(f"spherical correction {dt} ref_alt={with_ref_alt}: max abs diff {e:.3e}")
+    assert e <= (1e-14 if dt == "f64" else 1e-6)
+    other = be.to_numpy(be.zenith_angle_spherical_correction(be.asarray(ref_mu), be.asarray(alt), None if ref_alt is None else be.asarray(ref_alt),
+                                                             planet_radius=3.3895e6))
+    assert np.all(other[:, ~dark & (ref_mu < 1)] > got[:, ~dark & (ref_mu < 1)])        # a smaller planet curves away faster
+
+
+# ---- 8: the CPU boundary -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+def test_cpu_boundary_serves_rows_that_differ_and_keeps_identical_rows_as_they_were(dt, hip_f64, hip_f32, oracle_built):
+    b = cpu_boundary.HipCpuBoundary(_np_dtype(dt))
+    be = _be(dt, hip_f64, hip_f32)
+    shape = (17, 33, 5)
+    I = _inputs(dt, *shape)
+    a = (I["tau"], I["ssa"], I["g"], I["mu0_lay"], I["adir"], I["adif"], I["inc"])
+    R = _inputs(dt, *shape, True)
+    r = (R["tau"], R["ssa"], R["g"], R["mu0_lay"], R["adir"], R["adif"], R["inc"])
+    for top_at_1 in (False, True):
+        _check_per_gpoint(b, dt, b.sw_solver_2stream(top_at_1, *a), _oracle(dt, *shape, top_at_1), "CPU boundary")
+        _check(b, dt, b.sw_solver_2stream(top_at_1, *r, do_broadband=True), _oracle_broadband(dt, *shape, top_at_1, True, True),
+               "CPU boundary, broadband, without the conservative g-point", TOL[dt])
+        _check(b, dt, b.sw_solver_2stream(top_at_1, *a, do_broadband=True), _oracle_broadband(dt, *shape, top_at_1, True),
+               "CPU boundary, broadband", max(CONS64, TOL[dt]))
+    # identical rows: the 1-D device entry, bit for bit
+    mu0 = np.ascontiguousarray(I["mu0_lay"][2])
+    rows = np.ascontiguousarray(np.repeat(mu0[None, :], shape[1], axis=0))
+    got = b.sw_solver_2stream(False, *a[:3], rows, *a[4:])
+    up = be.asarray
+    want = be.sw_solver_2stream(False, up(a[0]), up(a[1]), up(a[2]), up(mu0), up(a[4]), up(a[5]), up(a[6]))
+    for k in KEYS:
+        assert np.array_equal(got[k], be.to_numpy(want[k])), k
+
+
+# ---- 9: ResidentSolver -------------------------------------------------------------------------------------------------------------
+KW = dict(ngpt=48, nbnd=4, npres=16, nflav=4, nminor_lower=7, nminor_upper=4)
+NCOL, NLAY = 40, 24
+
+
+@functools.lru_cache(maxsize=None)
+def _resident_case(dt, night):
+    F = _np_dtype(dt)
+    atm0 = synthetic.make_atmosphere(NCOL, NLAY, nbnd_lw=KW["nbnd"], nbnd_sw=KW["nbnd"], seed=5)
+    rng = np.random.default_rng(9)
+    f = rng.uniform(0.65, 1.35, NCOL)                                     # surface pressures far apart: sorting has work to do
+    atm0.p_lay = np.ascontiguousarray(atm0.p_lay * f); atm0.p_lev = np.ascontiguousarray(atm0.p_lev * f)
+    mu0 = rng.uniform(0.05, 1.0, NCOL)
+    if night:
+        mu0[::3] = 0.0; mu0[1::7] = -0.3
+    atm0.mu0 = mu0
+    atm0 = atm0.astype(F)
+    # layer altitudes from the pressures (scale height 7.5 km), reference altitudes that differ per column
+    ps = atm0.p_lev.max(axis=0)
+    ref_alt = rng.uniform(0., 2000., NCOL).astype(F)
+    alt = (ref_alt[None, :] + 7500.*np.log(ps[None, :].astype(np.float64) / atm0.p_lay)).astype(F)
+    return atm0, np.ascontiguousarray(alt), ref_alt, synthetic.make_kdist("lw", **KW), synthetic.make_kdist("sw", **KW)
+
+
+def _solve(be, dt, night=False, **kw):
+    atm0, _, _, kl0, ks0 = _resident_case(dt, night)
+    kw = {k: (be.asarray(v) if isinstance(v, np.ndarray) else v) for k, v in kw.items()}
+    kw.setdefault("sort_columns", "0")
+    sv = pipeline.ResidentSolver(be, be.upload_kdist(kl0), be.upload_kdist(ks0), pipeline.upload_atmosphere(be, atm0), do_broadband=True, **kw)
+    F = be.to_numpy(sv.step()).copy()
+    B = {k: be.to_numpy(v).copy() for k, v in sv.bnd_fluxes.items()} if sv.bnd_fluxes is not None else None
+    return sv, F, B
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+def test_resident_solver_with_cosines_by_layer(dt, hip_f64, hip_f32):
+    be = _be(dt, hip_f64, hip_f32)
+    atm0, alt, ref_alt, _, _ = _resident_case(dt, False)
+    mu_lay = sw_mu0_ref.spherical_mu0(atm0.mu0, alt, ref_alt)
+    assert np.all(np.ptp(mu_lay, axis=0) > 0) and np.unique(mu_lay[0]).size == NCOL      # a profile of its own in every column
+    base_sv, base, _ = _solve(be, dt)
+    assert base_sv.npad == 8                                             # 40 columns: padded to 48
+    # constant rows: the plain solver
+    _, const, _ = _solve(be, dt, mu0_lay=np.ascontiguousarray(np.repeat(atm0.mu0[None, :], NLAY, axis=0)))
+    for i in range(3):
+        assert np.array_equal(const[i], base[i]), i                      # LW: the same launches
+    for i in range(3, 7):
+        e = cases.rel_err(const[i], base[i], FLOOR[dt]); print(f"constant rows {dt} row {i}: {e:.3e}")
+        assert e <= TOL[dt], i
+    # profiles: altitude= (corrected on the device) equals mu0_lay= from the NumPy reference; LW untouched; SW differs from the plain one
+    sv_m, lay, _ = _solve(be, dt, mu0_lay=mu_lay)
+    sv_a, alt_f, _ = _solve(be, dt, altitude=alt, ref_altitude=ref_alt)
+    e = float(np.max(np.abs(be.to_numpy(sv_a.mu0_lay_step)[:, :NCOL].astype(np.float64) - mu_lay)))
+    assert e <= (1e-14 if dt == "f64" else 1e-6), e
+    for i in range(3):
+        assert np.array_equal(lay[i], base[i]) and np.array_equal(alt_f[i], base[i]), i
+    for i in range(3, 7):
+        # the two sets of cosines differ by the correction's rounding (1e-14 / 1e-6 above): the fluxes by a like amount
+        e = cases.rel_err(alt_f[i], lay[i], FLOOR[dt]); print(f"altitude= against mu0_lay= {dt} row {i}: {e:.3e}")
+        assert e <= (1e-12 if dt == "f64" else 1e-4), i
+    assert cases.rel_err(lay[4], base[4], FLOOR[dt]) > 1e-3               # (a higher sun aloft: more flux comes down)
+    assert np.all(lay[5][0 if atm0.top_at_1 else -1] >= base[5][0 if atm0.top_at_1 else -1])
+    # sorted and padded: the same fluxes per caller column
+    sv_s, srt, _ = _solve(be, dt, mu0_lay=mu_lay, sort_columns=True)
+    assert sv_s.sort_columns and not np.array_equal(be.to_numpy(sv_s.perm)[:NCOL], np.arange(NCOL))
+    for i in range(7):
+        e = cases.rel_err(srt[i], lay[i], FLOOR[dt]); print(f"sorted {dt} row {i}: {e:.3e}")
+        assert e <= (1e-11 if dt == "f64" else 1e-4), i                  # (the windowed gas optics stage other neighbours: the project's bound)
+    _, srt_a, _ = _solve(be, dt, altitude=alt, ref_altitude=ref_alt, sort_columns=True)
+    for i in range(3, 7):
+        assert cases.rel_err(srt_a[i], alt_f[i], FLOOR[dt]) <= (1e-11 if dt == "f64" else 1e-4), i
+    # by band: the band sums add up to the broadband arrays, which are those of the broadband solve
+    _, bb, B = _solve(be, dt, mu0_lay=mu_lay, byband=True)
+    for i, k in ((3, "sw_up"), (4, "sw_dn"), (5, "sw_dir")):
+        acc = B[k][0].copy()
+        for ib in range(1, KW["nbnd"]):
+            acc += B[k][ib]
+        assert np.array_equal(bb[i], acc), k
+        assert cases.rel_err(bb[i], lay[i], FLOOR[dt]) <= TOL[dt], k
+    # per-g-point mode of the step
+    sv_g = pipeline.ResidentSolver(be, sv_m.kd_lw, sv_m.kd_sw, sv_m.atm, do_broadband=False, sort_columns="0", mu0_lay=be.asarray(mu_lay))
+    G = be.to_numpy(sv_g.step())
+    for i in range(3, 7):
+        assert cases.rel_err(G[i], lay[i], FLOOR[dt]) <= TOL[dt], i
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("mode", ["mu0_lay", "altitude"])
+def test_resident_solver_on_the_sunlit_columns_only(mode, dt, hip_f64, hip_f32):
+    be = _be(dt, hip_f64, hip_f32)
+    atm0, alt, ref_alt, _, _ = _resident_case(dt, True)
+    day = atm0.mu0 > 0
+    assert 5 < day.sum() < NCOL - 5
+    kw = dict(altitude=alt, ref_altitude=ref_alt) if mode == "altitude" else dict(mu0_lay=sw_mu0_ref.spherical_mu0(atm0.mu0, alt, ref_alt))
+    _, full, _ = _solve(be, dt, night=True, **kw)
+    for sort in ("0", True):
+        sv, sun, _ = _solve(be, dt, night=True, sunlit=True, sort_columns=sort, **kw)
+        assert not sun[3:, :, ~day].any()                                 # exact zeros in the dark
+        for i in range(3):
+            assert cases.rel_err(sun[i], full[i], FLOOR[dt]) <= (1e-11 if dt == "f64" else 1e-4), i
+        for i in range(3, 7):
+            e = cases.rel_err(sun[i][:, day], full[i][:, day], FLOOR[dt]); print(f"sunlit {mode} {dt} sort={sort} row {i}: {e:.3e}")
+            assert e <= (1e-11 if dt == "f64" else 1e-4), i              # (other neighbours in the gas optics, as when sorting)
+
+
+# ---- 10: the C++ host classes and the driver ---------------------------------------------------------------------------------------
+def _run_driver(workdir, *flags):
+    import ctypes
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lib = ctypes.CDLL(os.path.join(root, "rte-rrtmgp-cpp_amd", "lib", "librte_rrtmgp_hip.so"))
+    argv = [b"test_rte_rrtmgp_gpu"] + [f.encode() for f in flags]
+    old = os.getcwd()
+    try:
+        os.chdir(workdir)
+        return lib.rrx_host_main(len(argv), (ctypes.c_char_p * len(argv))(*argv))
+    finally:
+        os.chdir(old)
+
+
+def test_driver_with_spherical_mu0_matches_the_resident_solver(tmp_path, hip_f64):
+    import os
+    from rte_rrtmgp_cpp_amd import synthetic_files, rrxio, cxx_driver
+    be = hip_f64
+    atm0, alt, ref_alt, kl0, ks0 = _resident_case("f64", False)
+    d = str(tmp_path)
+    synthetic_files.write_case(d, atm0, kl0, ks0, z_lay=alt, z_ref=ref_alt)
+    _, ref, _ = _solve(be, "f64", altitude=alt, ref_altitude=ref_alt)
+    _, plain, _ = _solve(be, "f64")
+    names = ("lw_flux_up", "lw_flux_dn", "lw_flux_net", "sw_flux_up", "sw_flux_dn", "sw_flux_dn_dir", "sw_flux_net")
+
+    def output():
+        _, v = rrxio.read(os.path.join(d, "rte_rrtmgp_output.nc"))
+        return {k: v[k][0].squeeze(axis=-2) for k in names}
+
+    # (the driver against the Python pipeline on the same kernels: the tolerances of tests/test_gpu_host_classes.py)
+    for flags in ((), ("--no-broadband-solvers",), ("--output-bnd-fluxes", "--byband-solvers"), ("--device-sort-columns",)):
+        assert _run_driver(d, "--sw-spherical-mu0", *flags) == 0, flags
+        out = output()
+        for i, k in enumerate(names):
+            e = cases.rel_err(out[k], ref[i]); print(f"driver {flags} {k}: {e:.3e}")
+            assert e <= (1e-7 if k.startswith("sw_") else 1e-11), (flags, k)
+    assert cases.rel_err(out["sw_flux_dn"], plain[4]) > 1e-3             # (the flag does something)
+    # without the flag: the plain solve; z_lay missing: a message and a non-zero status
+    assert _run_driver(d) == 0
+    assert cases.rel_err(output()["sw_flux_dn"], plain[4]) <= 1e-7
+    synthetic_files.write_input(os.path.join(d, "rte_rrtmgp_input.nc"), atm0, kl0.nbnd, ks0.nbnd)
+    assert _run_driver(d, "--sw-spherical-mu0") != 0
+    # z_ref absent: mu0 holds at altitude 0
+    synthetic_files.write_input(os.path.join(d, "rte_rrtmgp_input.nc"), atm0, kl0.nbnd, ks0.nbnd, z_lay=alt)
+    assert _run_driver(d, "--sw-spherical-mu0") == 0
+    _, ref0, _ = _solve(be, "f64", altitude=alt)
+    out = output()
+    for i, k in enumerate(names):
+        assert cases.rel_err(out[k], ref0[i]) <= (1e-7 if k.startswith("sw_") else 1e-11), k
+    # the class API on device arrays (CxxDriver), sunlit columns included
+    atm_n, _, _, _, _ = _resident_case("f64", True)
+    _, ref_n, _ = _solve(be, "f64", night=True, sunlit=True, altitude=alt, ref_altitude=ref_alt)
+    drv = cxx_driver.CxxDriver(be, kl0, ks0, pipeline.upload_atmosphere(be, atm_n), sunlit=True, altitude=be.asarray(alt),
+                               ref_altitude=be.asarray(ref_alt))
+    try:
+        F = be.to_numpy(drv.step())
+    finally:
+        drv.close()
+    for i, k in enumerate(names):
+        assert cases.rel_err(F[i], ref_n[i]) <= (1e-7 if k.startswith("sw_") else 1e-11), k
+    assert not F[3:, :, atm_n.mu0 <= 0].any()
+    # column blocks: 40 columns in blocks of 16 (two full blocks and a residual of 8), the borrowed altitudes cut with the other inputs
+    drv = cxx_driver.CxxDriver(be, kl0, ks0, pipeline.upload_atmosphere(be, atm0), column_block=16, sort_mode=0, pad=False,
+                               altitude=be.asarray(alt), ref_altitude=be.asarray(ref_alt))
+    try:
+        F = be.to_numpy(drv.step())
+    finally:
+        drv.close()
+    for i, k in enumerate(names):
+        e = cases.rel_err(F[i], ref[i]); print(f"column blocks {k}: {e:.3e}")
+        assert e <= (1e-7 if k.startswith("sw_") else 1e-11), k
