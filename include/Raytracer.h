@@ -1,0 +1,32 @@
+/* Raytracer_gpu -- forward Monte Carlo ray tracer for 3-D shortwave fluxes (rrx_raytracer_sw). A class of this
+ * project's own shape: it takes the clear g-point arrays and the band cloud triple as the gas and cloud optics write them. (The
+ * reference's Raytracer::trace_rays takes the structures of its _rt pipeline, which this project does not have: INTEGRATION.md.) */
+#ifndef RAYTRACER_H
+#define RAYTRACER_H
+#include "Array.h"
+#include "rrx_forward.h"
+
+class Raytracer_gpu
+{
+    public:
+        Raytracer_gpu() {}
+
+        // tau, ssa (ncol = nx ny, nz, ngpt); band_lims_gpt (2, nbnd); cld_* (ncol, nz, nbnd), all three of size 0 for a clear sky;
+        // sfc_albedo (ncol); inc_dir, inc_dif (ngpt) on the host; the flux arrays (ncol) in W m-2 and the absorption arrays
+        // (ncol, nz) in W m-3 are overwritten. Returns the number of photons dropped at max_events (0 in a healthy run).
+        unsigned long long trace_rays(
+                const int nx, const int ny, const int nz,
+                const Float dx, const Float dy, const Float dz,
+                const bool top_at_1, const bool independent_column,
+                const Array_gpu<Float,3>& tau, const Array_gpu<Float,3>& ssa,
+                const Array_gpu<int,2>& band_lims_gpt,
+                const Array_gpu<Float,3>& cld_tau, const Array_gpu<Float,3>& cld_ssa, const Array_gpu<Float,3>& cld_g,
+                const Array_gpu<Float,1>& sfc_albedo,
+                const Float mu0, const Float azimuth,
+                const Array<Float,1>& inc_dir, const Array<Float,1>& inc_dif,
+                const int knx, const int kny, const int knz,
+                const long long photons_per_pixel, const unsigned long long seed, const int max_events,
+                Array_gpu<Float,1>& sfc_dn_dir, Array_gpu<Float,1>& sfc_dn_dif, Array_gpu<Float,1>& sfc_up, Array_gpu<Float,1>& tod_up,
+                Array_gpu<Float,2>& abs_dir, Array_gpu<Float,2>& abs_dif);
+};
+#endif

@@ -610,7 +610,47 @@ int rrx_mcica_increment_2stream##SFX(int ncol, int nlay, int ngpt, int nbnd, con
         unsigned long long seed, int domain, const int* col_id, int col_id0, F* tau_inout, F* ssa_inout, F* g_inout, \
         const F* cld_tau, const F* cld_ssa, const F* cld_g, unsigned char* mask_out, void* stream); \
 int rrx_mcica_cloud_mask##SFX(int ncol, int nlay, int ngpt, const F* cloud_frac, const F* alpha, unsigned long long seed, int domain, \
-        const int* col_id, int col_id0, unsigned char* mask_out, void* stream);
+        const int* col_id, int col_id0, unsigned char* mask_out, void* stream); \
+/* ---- Forward Monte Carlo ray tracer for 3-D shortwave fluxes (csrc/rrx_raytracer.hip; the algorithm of the \
+   reference's ray_tracer_kernel on this project's arrays). The domain is nx x ny x nz cells of dx x dy x dz metres, periodic in \
+   x and y; column icol = ix + nx iy. tau, ssa (ncol, nz, ngpt): the clear g-point arrays of the SW gas optics (Rayleigh \
+   scattering); cld_tau, cld_ssa, cld_g (ncol, nz, nbnd): the band cloud triple (Henyey-Greenstein, g = min(cld_g, 1 - eps)), all \
+   NULL or all given, with band_lims_gpt (2, nbnd), 1-based, on the device (a g-point of no band sees no cloud). Per g-point \
+   k_ext = (tau + cld_tau)/dz, k_sca = (tau ssa + cld_tau cld_ssa)/dz. sfc_albedo (ncol): Lambertian. The sun: one mu0 in (0, 1] for \
+   the domain, the direct beam travels along (sin cos(azimuth), sin sin(azimuth), -mu0), azimuth in radians from +x. \
+   independent_column freezes the horizontal motion. igpt is 0-based. All arrays are on the device but inc_dir / inc_dif of \
+   rrx_raytracer_sw, which are ngpt numbers on the HOST (the entry skips the g-points without incident flux). \
+   rrx_rt_k_null: k_null (knx, kny, knz), x fastest, kn counted UPWARD from the surface, = the maximum of k_ext over the block's \
+   cells for g-point igpt; knx, kny, knz divide nx, ny, nz. \
+   rrx_rt_trace_counts: traces the photons [photon0, photon0 + nphotons) of g-point igpt (photon p starts in pixel p mod ncol; \
+   Philox4x32-10 keyed by seed with counter (p low, p high, igpt, block); draw order: the header of rrx_raytracer.hip) and ADDS \
+   into six caller-zeroed arrays of unsigned 64-bit counts in units of 2^-32 photon: sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up (ncol) \
+   and abs_dir, abs_dif (ncol, nz) (dir / dif: the photon had not / had been scattered or reflected or started diffuse). Integer \
+   adds: the result is independent of the order of arrival and additive over photon ranges. A photon still alive after max_events \
+   events is dropped and counted in n_capped (one device counter, added into). inc_dir, inc_dif >= 0 set the diffuse share \
+   inc_dif/(inc_dir + inc_dif) of the starts. \
+   rrx_rt_counts_to_flux: out[i] += F(counts[i] 2^-32) scale, i < n. \
+   rrx_raytracer_sw: the spectral loop. Zeroes the six outputs and n_capped, then for igpt = 0 .. ngpt-1 with \
+   inc_dir[igpt] + inc_dif[igpt] > 0: zeroes counts in the stream's workspace, rrx_rt_k_null, rrx_rt_trace_counts of \
+   photons_per_pixel ncol photons from 0, rrx_rt_counts_to_flux with scale = (inc_dir + inc_dif)/F(photons_per_pixel) for the \
+   four surface / top arrays (W m-2) and scale/dz for the absorption (W m-3): the same bits as that loop made by hand. \
+   An extent of 0 (nx, ny, nz, ngpt, nphotons, photons_per_pixel, n): returns 0 without a launch; a negative extent, a NULL that \
+   is needed, a partly-NULL cloud triple, mu0 outside (0, 1], a non-positive dx / dy / dz, a kn grid that does not divide the grid: \
+   non-zero, before any HIP call. */ \
+int rrx_rt_k_null##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, const F* tau, const int* band_lims_gpt, \
+        const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, void* stream); \
+int rrx_rt_trace_counts##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, F inc_dir, F inc_dif, int knx, int kny, int knz, const F* k_null, \
+        unsigned long long seed, long long photon0, long long nphotons, int max_events, \
+        unsigned long long* sfc_dn_dir, unsigned long long* sfc_dn_dif, unsigned long long* sfc_up, unsigned long long* tod_up, \
+        unsigned long long* abs_dir, unsigned long long* abs_dif, unsigned long long* n_capped, void* stream); \
+int rrx_rt_counts_to_flux##SFX(long long n, const unsigned long long* counts, F scale, F* out, void* stream); \
+int rrx_raytracer_sw##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
+        long long photons_per_pixel, unsigned long long seed, int max_events, \
+        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, void* stream);
 
 RRX_DECLARE(double, _f64)
 RRX_DECLARE(float, _f32)

@@ -51,6 +51,13 @@ int   rrx_cxx_cloud_sampling(void* handle, const Real* cloud_frac, int ncol, int
    altitude at which mu0 holds, or NULL = 0; the arrays are borrowed (read at every solve, they must outlive the solves). The solve
    then takes a cosine of the solar zenith angle per layer, corrected for the planet's curvature from its mu0 */
 int   rrx_cxx_spherical_mu0(void* handle, const Real* alt_lay, int ncol, int nlay, const Real* ref_alt, double planet_radius);
+/* Raytracer_gpu::trace_rays (include/Raytracer.h) on device arrays of the caller; needs no handle. inc_dir, inc_dif: ngpt numbers on the
+ * host; out6: sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up (ncol), abs_dir, abs_dif (ncol, nz) on the device; n_capped: one number on the host. */
+int   rrx_cxx_trace_rays(int nx, int ny, int nz, int ngpt, int nbnd, Real dx, Real dy, Real dz, int top_at_1, int independent_column,
+                         const Real* tau, const Real* ssa, const int* band_lims_gpt, const Real* cld_tau, const Real* cld_ssa, const Real* cld_g,
+                         const Real* sfc_albedo, Real mu0, Real azimuth, const Real* inc_dir, const Real* inc_dif, int knx, int kny, int knz,
+                         long long photons_per_pixel, unsigned long long seed, int max_events, Real* const* out6, unsigned long long* n_capped,
+                         void* stream);
 /* one LW + one SW solve_gpu (fluxes only) enqueued on `stream`; DEVICE arrays: (ncol,nlay) / (ncol,nlay+1) fields, (ncol) vectors,
    surface properties (nbnd,ncol); lwp, iwp, rel, dei NULL without clouds; out7: seven (ncol, nlay+1) arrays for LW up, dn, net and
    SW up, dn, dn_dir, net, or NULL (the driver then keeps them: rrx_cxx_driver_fluxes) */

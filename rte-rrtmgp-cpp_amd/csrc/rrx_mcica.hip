@@ -9,31 +9,12 @@
 // row segment, one cell per lane -- the store shape that streams at the full rate, profiles/r04_store_pattern.txt), one g-point
 // per block row with its band found once, and each thread walks the layers of its (column, g-point) with the rank in a register.
 #include "rrx_common.h"
+#include "rrx_philox.h"
 #include "rrx_hip.h"
 
 namespace
 {
 using namespace rrx;
-
-struct Philox { unsigned w[4]; };
-
-// Philox4x32-10 (Salmon et al. 2011)
-__device__ __forceinline__ Philox philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1)
-{
-    #pragma unroll
-    for (int r=0; r<10; ++r)
-    {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return Philox{{c0, c1, c2, c3}};
-}
-
-// 24 significant bits: exact in fp32 and fp64, in (0, 1), the same value in both
-template<typename F>
-__device__ __forceinline__ F uniform(const unsigned x) { return (F(x >> 9) + F(0.5)) * F(1.1920928955078125e-07); }
 
 // rrx_increment_2stream_by_2stream's arithmetic (inc_2str of rrx_misc.hip), operation for operation
 template<typename F>

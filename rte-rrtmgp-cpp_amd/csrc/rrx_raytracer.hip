@@ -1,0 +1,536 @@
+// Forward Monte Carlo ray tracer for 3-D shortwave fluxes. The algorithm is that of the reference's
+// ray_tracer_kernel (src_kernels_cuda_rt/raytracer_kernels.cu): null-collision tracking on a coarse grid of maximum extinction,
+// expected-value absorption at every collision (Iwabuchi 2006), Russian roulette below weight 0.5, a Lambertian surface, periodic
+// x / y, an independent-column switch. Written for this project's arrays and with these departures:
+//   - inputs are the clear g-point arrays tau, ssa (ncol = nx ny with x fastest, nz, ngpt) and the band cloud triple (ncol, nz, nbnd);
+//     k_ext = (tau + tau_c)/dz, k_sca = (tau ssa + tau_c ssa_c)/dz, k_sca_cld = (tau_c ssa_c)/dz; gas scattering is Rayleigh, cloud
+//     scattering Henyey-Greenstein with min(g_c, 1 - eps);
+//   - nothing is divided by the local extinction: f_no_abs = 1 - (k_ext - k_sca)/k_null (clamped to [0, 1]), a surviving photon
+//     scatters iff u (k_sca + (k_null - k_ext)) < k_sca and the scatterer is cloud iff u k_sca < k_sca_cld, so a cell with k_ext = 0
+//     inside a block with k_null > 0 is well defined; a block with k_null = 0 is crossed without a collision;
+//   - a photon carries the integer indices (in, jn, kn) of its block of the k_null grid; a crossing moves the index by one (wrapping
+//     in x / y) and puts the coordinate on the face, a collision clamps the position into the block, and the fine cell is
+//     clamp(int(x/dx), block's first cell, block's last cell): no epsilon nudges, no fmod, the same code in both precisions;
+//   - photon p of a g-point starts in pixel p mod (nx ny): every pixel gets exactly photons_per_pixel photons;
+//   - tallies are unsigned 64-bit integers in units of 2^-32 photon, llrint(weight 2^32) added with integer atomics: the result of
+//     a launch does not depend on the order of arrival, is bit-reproducible and additive over photon ranges;
+//   - a photon is dropped after max_events events (collisions + crossings, surface hits and exits among them) and counted in
+//     n_capped, and a thread traces a fixed list of photons: every loop is bounded by construction.
+//
+// Coordinates: x, y, z in metres, z upward from the surface (z = 0) to the domain top; block kn = 0 is the lowest. Fine cell
+// k (counted upward) is array layer nz-1-k with top_at_1, k otherwise. k_null(knx, kny, knz): x fastest, kn upward.
+//
+// Random numbers: Philox4x32-10, key = (low, high) words of the seed, counter = (photon index low, photon index high, g-point,
+// block number 0, 1, 2, ...); the four words of a block are consumed in order, uniform = ((x >> 9) + 0.5) 2^-23. DRAW ORDER of a
+// photon (part of the specification; tests/raytracer_ref.py restates it):
+//   start:     u -> x = (ix + u) dx;  u -> y = (iy + u) dy;  u -> diffuse iff u < inc_dif/(inc_dir + inc_dif);
+//              diffuse only: u -> mu = sqrt(u);  u -> phi = 2 pi u;  direction (s cos phi, s sin phi, -mu), s = sqrt(1 - mu^2)
+//   each event: u -> tau = -log(u), unless the previous event was a crossing between blocks (the remaining tau is carried)
+//     crossing (tau >= d_max k_null, or k_null = 0): tau -= d_max k_null; at the surface: tally, weight *= albedo, tally,
+//              weight < 0.5: u -> survives (weight = 1) iff u <= weight;  survivor: u -> mu = sqrt(u);  u -> phi; direction upward
+//     collision: deposit weight (1 - f_no_abs), weight *= f_no_abs;  weight < 0.5: u -> roulette as above;
+//              survivor: u -> scatter or null collision;  scatter: u -> species;  u -> cos of the scattering angle;  u -> phi
+//
+// Shape: one photon per lane at a time; a lane whose photon ends takes the next one of its list in the same loop, so the lanes
+// of a wave stay busy until the lists run out (the grid is capped and the photons dealt round-robin over the threads).
+#include "rrx_common.h"
+#include "rrx_philox.h"
+#include "rrx_hip.h"
+
+namespace
+{
+using namespace rrx;
+typedef unsigned long long u64;
+
+constexpr int RT_BLOCK = 256;
+constexpr int RT_MAX_BLOCKS = 1024;         // 256 CUs x 4 workgroups: one wave per SIMD and workgroup
+
+// workgroups a trace launch is capped at (the photons beyond are the threads' second, third, ... ones). Measured on the
+// broken-cloud field of tools/raytracer_bench.py (profiles/raytracer_bench_caps.txt): 1 024 / 2 048 / 4 096 / 8 192 workgroups take
+// 22.0 / 23.7 / 26.7 / 26.8 ms in fp64 and 15.6 / 16.1 / 16.9 / 16.8 ms in fp32 (3-D mode; one photon per thread from 4 096 on).
+// RRX_RT_MAX_BLOCKS in the environment overrides it, read at every launch (tests run deep lists on a few threads).
+int max_blocks()
+{
+    if (const char* e = std::getenv("RRX_RT_MAX_BLOCKS")) { const int n = std::atoi(e); if (n >= 1) return n; }
+    return RT_MAX_BLOCKS;
+}
+
+struct Stream
+{
+    unsigned c0, c1, c2, block, k0, k1;
+    int used;
+    Philox words;
+    __device__ __forceinline__ void start(const u64 photon, const unsigned igpt)
+    {
+        c0 = unsigned(photon & 0xFFFFFFFFull); c1 = unsigned(photon >> 32); c2 = igpt; block = 0u; used = 4;
+    }
+    template<typename F> __device__ __forceinline__ F next()
+    {
+        if (used == 4) { words = philox4x32_10(c0, c1, c2, block, k0, k1); ++block; used = 0; }
+        const int s = used++;
+        const unsigned x = s == 0 ? words.w[0] : (s == 1 ? words.w[1] : (s == 2 ? words.w[2] : words.w[3]));
+        return uniform<F>(x);
+    }
+};
+
+template<typename F> __device__ __forceinline__ F clampf(const F v, const F lo, const F hi) { return min(max(v, lo), hi); }
+__device__ __forceinline__ int clampi(const int v, const int lo, const int hi) { return min(max(v, lo), hi); }
+
+// the fine cell of a coordinate inside block `blk` of r cells of width d
+template<typename F> __device__ __forceinline__ int fine_cell(const F pos, const F d, const int blk, const int r)
+{
+    return clampi(int(pos / d), blk*r, blk*r + r - 1);
+}
+
+template<typename F> __device__ __forceinline__ u64 to_count(const F weight)
+{
+    return u64(llrint(double(weight) * 4294967296.0));
+}
+
+__device__ __forceinline__ void tally(u64* __restrict__ counts, const size_t i, const u64 c)
+{
+    if (c != 0ull) atomicAdd(&counts[i], c);
+}
+
+// 0-based band of 0-based g-point igpt, -1 when it lies in no band; band_lims_gpt (2, nbnd), 1-based inclusive
+__device__ __forceinline__ int band_of(const int igpt, const int nbnd, const int* __restrict__ band_lims_gpt)
+{
+    int ibnd = -1;
+    for (int b=nbnd-1; b>=0; --b)
+        if (igpt+1 >= band_lims_gpt[2*b] && igpt+1 <= band_lims_gpt[2*b+1]) ibnd = b;
+    return ibnd;
+}
+
+template<typename F> __device__ __forceinline__ F k_ext_of(const F tau, const F tau_c, const F dz) { return (tau + tau_c) / dz; }
+
+// k_null(in, jn, kn) = the maximum of k_ext over the block's cells, for one g-point
+template<typename F>
+__global__ void __launch_bounds__(256) k_null_kernel(
+        const int nx, const int ny, const int nz, const int nbnd, const int igpt, const int top_at_1,
+        const F* __restrict__ tau, const int* __restrict__ band_lims_gpt, const F* __restrict__ cld_tau, const F dz,
+        const int knx, const int kny, const int knz, F* __restrict__ k_null)
+{
+    const int n = blockIdx.x*blockDim.x + threadIdx.x;
+    if (n >= knx*kny*knz) return;
+    const int in = n % knx, jn = (n / knx) % kny, kn = n / (knx*kny);
+    const int rx = nx/knx, ry = ny/kny, rz = nz/knz;
+    const size_t ncol = size_t(nx)*ny;
+    const int ibnd = cld_tau != nullptr ? band_of(igpt, nbnd, band_lims_gpt) : -1;
+    F m = F(0.);
+    for (int k=kn*rz; k<(kn+1)*rz; ++k)
+    {
+        const int lay = top_at_1 ? nz-1-k : k;
+        for (int j=jn*ry; j<(jn+1)*ry; ++j)
+            for (int i=in*rx; i<(in+1)*rx; ++i)
+            {
+                const size_t cell = size_t(i) + size_t(j)*nx + ncol*lay;
+                const F tc = ibnd >= 0 ? cld_tau[cell + ncol*nz*ibnd] : F(0.);
+                m = max(m, k_ext_of(tau[cell + ncol*nz*igpt], tc, dz));
+            }
+    }
+    k_null[n] = m;
+}
+
+template<typename F>
+struct TraceArgs
+{
+    int nx, ny, nz, nbnd, igpt, top_at_1, independent_column;
+    const F* tau; const F* ssa; const int* band_lims_gpt; const F* cld_tau; const F* cld_ssa; const F* cld_g;
+    F dx, dy, dz;
+    const F* sfc_albedo;
+    F sun_x, sun_y, sun_z, dif_frac;
+    int knx, kny, knz;
+    const F* k_null;
+    unsigned k0, k1;
+    u64 photon0; long long nphotons; int max_events;
+    u64* sfc_dn_dir; u64* sfc_dn_dif; u64* sfc_up; u64* tod_up; u64* abs_dir; u64* abs_dif; u64* n_capped;
+};
+
+// cosine-weighted direction about the vertical; sign = -1 downward, +1 upward
+template<typename F>
+__device__ __forceinline__ void lambert(Stream& rng, const F sign, F& ux, F& uy, F& uz)
+{
+    const F mu = sqrt(rng.next<F>());
+    const F phi = F(6.283185307179586) * rng.next<F>();
+    const F s = sqrt(F(1.) - mu*mu);
+    ux = s*cos(phi); uy = s*sin(phi); uz = sign*mu;
+}
+
+template<typename F>
+__global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a)
+{
+    const long long nthreads = (long long)gridDim.x*blockDim.x;
+    long long next_photon = (long long)blockIdx.x*blockDim.x + threadIdx.x;
+
+    const int nx = a.nx, ny = a.ny, nz = a.nz;
+    const size_t ncol = size_t(nx)*ny;
+    const int rx = nx/a.knx, ry = ny/a.kny, rz = nz/a.knz;
+    const F kdx = F(rx)*a.dx, kdy = F(ry)*a.dy, kdz = F(rz)*a.dz;
+    const bool ic = a.independent_column != 0;
+    const int ibnd = a.cld_tau != nullptr ? band_of(a.igpt, a.nbnd, a.band_lims_gpt) : -1;
+    const F* __restrict__ tau_g = a.tau + ncol*nz*a.igpt;
+    const F* __restrict__ ssa_g = a.ssa + ncol*nz*a.igpt;
+    const F inf = F(INFINITY);
+    const F g_max = F(1.) - Lim<F>::eps();
+
+    Stream rng; rng.k0 = a.k0; rng.k1 = a.k1; rng.used = 4; rng.block = 0u; rng.c0 = rng.c1 = rng.c2 = 0u;
+    bool alive = false, pending = false;
+    int in = 0, jn = 0, kn = 0, kind = 0, nev = 0;
+    F x = F(0.), y = F(0.), z = F(0.), ux = F(0.), uy = F(0.), uz = F(-1.), weight = F(0.), tau = F(0.);
+
+    for (;;)
+    {
+        if (!alive)
+        {
+            if (next_photon >= a.nphotons) break;          // the list is finite and every photon ends within max_events events
+            const u64 p = a.photon0 + u64(next_photon);
+            next_photon += nthreads;
+            rng.start(p, unsigned(a.igpt));
+            const int pix = int(p % u64(ncol));
+            const int ix = pix % nx, iy = pix / nx;
+            in = ix / rx; jn = iy / ry; kn = a.knz - 1;
+            x = clampf((F(ix) + rng.next<F>())*a.dx, F(in)*kdx, F(in+1)*kdx);
+            y = clampf((F(iy) + rng.next<F>())*a.dy, F(jn)*kdy, F(jn+1)*kdy);
+            z = F(a.knz)*kdz;
+            if (rng.next<F>() < a.dif_frac) { lambert(rng, F(-1.), ux, uy, uz); kind = 1; }
+            else { ux = a.sun_x; uy = a.sun_y; uz = a.sun_z; kind = 0; }
+            weight = F(1.); pending = false; nev = 0; alive = true;
+        }
+        if (nev >= a.max_events) { atomicAdd(a.n_capped, 1ull); alive = false; continue; }
+        ++nev;
+
+        const F x_lo = F(in)*kdx, x_hi = F(in+1)*kdx, y_lo = F(jn)*kdy, y_hi = F(jn+1)*kdy, z_lo = F(kn)*kdz, z_hi = F(kn+1)*kdz;
+        const F sz = uz > F(0.) ? (z_hi - z)/uz : (uz < F(0.) ? (z_lo - z)/uz : inf);
+        const F sx = ic ? inf : (ux > F(0.) ? (x_hi - x)/ux : (ux < F(0.) ? (x_lo - x)/ux : inf));
+        const F sy = ic ? inf : (uy > F(0.) ? (y_hi - y)/uy : (uy < F(0.) ? (y_lo - y)/uy : inf));
+        const F d_max = min(sz, min(sx, sy));
+        const int axis = (sz <= sx && sz <= sy) ? 2 : (sx <= sy ? 0 : 1);
+        const F kn_val = a.k_null[in + a.knx*(jn + a.kny*kn)];
+        if (!pending) tau = -log(rng.next<F>());
+        pending = false;
+        const bool empty = !(kn_val > F(0.));
+        const F tau_cell = empty ? F(0.) : d_max*kn_val;
+
+        if (empty || tau >= tau_cell)
+        {
+            // ---- the photon leaves the block through the face of `axis`
+            if (!(d_max < inf)) { atomicAdd(a.n_capped, 1ull); alive = false; continue; }      // (a direction along no axis it may move on)
+            tau = tau - tau_cell; pending = true;
+            if (!ic) { x = clampf(x + ux*d_max, x_lo, x_hi); y = clampf(y + uy*d_max, y_lo, y_hi); }
+            z = clampf(z + uz*d_max, z_lo, z_hi);
+            if (axis == 0)
+            {
+                if (ux > F(0.)) { in = (in + 1 == a.knx) ? 0 : in + 1; x = F(in)*kdx; }
+                else { in = (in == 0) ? a.knx - 1 : in - 1; x = F(in+1)*kdx; }
+            }
+            else if (axis == 1)
+            {
+                if (uy > F(0.)) { jn = (jn + 1 == a.kny) ? 0 : jn + 1; y = F(jn)*kdy; }
+                else { jn = (jn == 0) ? a.kny - 1 : jn - 1; y = F(jn+1)*kdy; }
+            }
+            else if (uz > F(0.))
+            {
+                if (kn == a.knz - 1)          // out through the domain top
+                {
+                    const int pix = fine_cell(x, a.dx, in, rx) + nx*fine_cell(y, a.dy, jn, ry);
+                    tally(a.tod_up, pix, to_count(weight));
+                    alive = false;
+                }
+                else { ++kn; z = F(kn)*kdz; }
+            }
+            else if (kn == 0)                 // the surface
+            {
+                z = F(0.);
+                const int pix = fine_cell(x, a.dx, in, rx) + nx*fine_cell(y, a.dy, jn, ry);
+                tally(kind == 0 ? a.sfc_dn_dir : a.sfc_dn_dif, pix, to_count(weight));
+                weight = weight * a.sfc_albedo[pix];
+                tally(a.sfc_up, pix, to_count(weight));
+                if (weight < F(0.5)) weight = (rng.next<F>() > weight) ? F(0.) : F(1.);
+                if (weight > F(0.)) { lambert(rng, F(1.), ux, uy, uz); kind = 1; pending = false; }
+                else alive = false;
+            }
+            else { --kn; z = F(kn+1)*kdz; }
+        }
+        else
+        {
+            // ---- a collision inside the block
+            const F dn = tau / kn_val;
+            if (!ic) { x = clampf(x + ux*dn, x_lo, x_hi); y = clampf(y + uy*dn, y_lo, y_hi); }
+            z = clampf(z + uz*dn, z_lo, z_hi);
+            const int i = fine_cell(x, a.dx, in, rx), j = fine_cell(y, a.dy, jn, ry), k = fine_cell(z, a.dz, kn, rz);
+            const int lay = a.top_at_1 ? nz-1-k : k;
+            const size_t cell = size_t(i) + size_t(j)*nx + ncol*lay;
+            const F t = tau_g[cell], w0 = ssa_g[cell];
+            F tc = F(0.), wc = F(0.), gc = F(0.);
+            if (ibnd >= 0)
+            {
+                const size_t cb = cell + ncol*nz*ibnd;
+                tc = a.cld_tau[cb]; wc = a.cld_ssa[cb]; gc = a.cld_g[cb];
+            }
+            const F k_ext = k_ext_of(t, tc, a.dz);
+            const F k_sca = (t*w0 + tc*wc) / a.dz;
+            const F k_sca_cld = (tc*wc) / a.dz;
+            const F f_no_abs = clampf(F(1.) - (k_ext - k_sca)/kn_val, F(0.), F(1.));
+            tally(kind == 0 ? a.abs_dir : a.abs_dif, cell, to_count(weight*(F(1.) - f_no_abs)));
+            weight = weight * f_no_abs;
+            if (weight < F(0.5)) weight = (rng.next<F>() > weight) ? F(0.) : F(1.);
+            if (!(weight > F(0.))) { alive = false; continue; }
+            if (rng.next<F>()*(k_sca + (kn_val - k_ext)) < k_sca)
+            {
+                const bool cloud = rng.next<F>()*k_sca < k_sca_cld;
+                const F u = rng.next<F>();
+                F cos_s;
+                if (cloud)
+                {
+                    const F g = min(gc, g_max);
+                    if (fabs(g) < F(1.e-6)) cos_s = F(2.)*u - F(1.);
+                    else
+                    {
+                        const F s = (F(1.) - g*g) / ((F(1.) - g) + (F(2.)*g)*u);
+                        cos_s = ((F(1.) + g*g) - s*s) / (F(2.)*g);
+                    }
+                }
+                else          // Rayleigh: the root of mu^3 + 3 mu = 2 q, q = 4u - 2
+                {
+                    const F q = F(4.)*u - F(2.);
+                    const F A = cbrt(q + sqrt(F(1.) + q*q));
+                    cos_s = A - F(1.)/A;
+                }
+                cos_s = clampf(cos_s, F(-1.), F(1.));
+                const F sin_s = sqrt(max(F(0.), F(1.) - cos_s*cos_s));
+                const F phi = F(6.283185307179586) * rng.next<F>();
+                const F cp = cos(phi), sp = sin(phi);
+                F vx, vy, vz;
+                if (fabs(uz) > F(0.99999))
+                {
+                    vx = sin_s*cp; vy = sin_s*sp; vz = uz > F(0.) ? cos_s : -cos_s;
+                }
+                else
+                {
+                    const F den = sqrt(F(1.) - uz*uz);
+                    vx = (sin_s*((ux*uz)*cp - uy*sp))/den + ux*cos_s;
+                    vy = (sin_s*((uy*uz)*cp + ux*sp))/den + uy*cos_s;
+                    vz = uz*cos_s - (sin_s*cp)*den;
+                }
+                const F nrm = sqrt((vx*vx + vy*vy) + vz*vz);
+                ux = vx/nrm; uy = vy/nrm; uz = vz/nrm;
+                kind = 1;
+            }
+        }
+    }
+}
+
+template<typename F>
+__global__ void counts_to_flux_kernel(const size_t n, const u64* __restrict__ counts, const F scale, F* __restrict__ out)
+{
+    const size_t i = size_t(blockIdx.x)*blockDim.x + threadIdx.x;
+    if (i < n) out[i] = out[i] + F(double(counts[i]) * 2.3283064365386963e-10) * scale;
+}
+
+// ---- host side
+
+void check_grid(const int nx, const int ny, const int nz, const int knx, const int kny, const int knz)
+{
+    if (knx < 1 || kny < 1 || knz < 1) throw std::runtime_error("knx, kny, knz must be >= 1");
+    if (nx % knx != 0) throw std::runtime_error("knx does not divide nx");
+    if (ny % kny != 0) throw std::runtime_error("kny does not divide ny");
+    if (nz % knz != 0) throw std::runtime_error("knz does not divide nz");
+    if ((long long)nx*ny*nz > 0x7FFFFFFFll) throw std::runtime_error("nx ny nz exceeds 2^31 - 1");
+}
+
+template<typename F>
+void check_cloud(const int nbnd, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g)
+{
+    const int given = (cld_tau != nullptr) + (cld_ssa != nullptr) + (cld_g != nullptr);
+    if (given != 0 && given != 3) throw std::runtime_error("cld_tau, cld_ssa, cld_g must be all NULL or all given");
+    if (given == 3 && band_lims_gpt == nullptr) throw std::runtime_error("band_lims_gpt is NULL");
+    if (given == 3 && nbnd < 1) throw std::runtime_error("nbnd must be >= 1 with a cloud triple");
+}
+
+// true: nothing to do
+bool check_extents(std::initializer_list<std::pair<const char*, long long>> extents)
+{
+    bool empty = false;
+    for (const auto& e : extents)
+    {
+        if (e.second < 0) throw std::runtime_error(std::string(e.first) + " is negative");
+        if (e.second == 0) empty = true;
+    }
+    return empty;
+}
+
+void check_needed(std::initializer_list<std::pair<const char*, const void*>> needed)
+{
+    for (const auto& p : needed)
+        if (p.second == nullptr) throw std::runtime_error(std::string(p.first) + " is NULL");
+}
+
+template<typename F>
+void check_scene(const F dx, const F dy, const F dz, const F mu0)
+{
+    if (!(dx > F(0.)) || !(dy > F(0.)) || !(dz > F(0.))) throw std::runtime_error("dx, dy, dz must be > 0");
+    if (!(mu0 > F(0.)) || mu0 > F(1.)) throw std::runtime_error("mu0 must be in (0, 1]");
+}
+
+template<typename F>
+void launch_k_null(int nx, int ny, int nz, int nbnd, int igpt, int top_at_1, const F* tau, const int* band_lims_gpt,
+                   const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, hipStream_t st)
+{
+    const int n = knx*kny*knz;
+    k_null_kernel<F><<<ceil_div(n, 256), 256, 0, st>>>(nx, ny, nz, nbnd, igpt, top_at_1, tau, band_lims_gpt, cld_tau, dz,
+                                                       knx, kny, knz, k_null);
+}
+
+template<typename F>
+void launch_trace(TraceArgs<F> a, const F mu0, const F azimuth, const F inc_dir, const F inc_dif, const u64 seed, hipStream_t st)
+{
+    const double st_ = std::sqrt(std::max(0.0, 1.0 - double(mu0)*double(mu0)));
+    a.sun_x = F(st_*std::cos(double(azimuth))); a.sun_y = F(st_*std::sin(double(azimuth))); a.sun_z = -mu0;
+    a.dif_frac = inc_dif / (inc_dir + inc_dif);
+    a.k0 = unsigned(seed & 0xFFFFFFFFull); a.k1 = unsigned(seed >> 32);
+    const int blocks = int(std::min<long long>((a.nphotons + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
+    trace_kernel<F><<<blocks, RT_BLOCK, 0, st>>>(a);
+}
+
+template<typename F>
+void launch_counts_to_flux(const size_t n, const u64* counts, const F scale, F* out, hipStream_t st)
+{
+    counts_to_flux_kernel<F><<<unsigned(ceil_div((long long)n, 256)), 256, 0, st>>>(n, counts, scale, out);
+}
+
+template<typename F>
+int k_null_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, const F* tau,
+                 const int* band_lims_gpt, const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, void* stream)
+{
+    RRX_TRY
+    if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}})) return 0;
+    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
+    check_needed({{"tau", tau}, {"k_null", k_null}});
+    if (cld_tau != nullptr && band_lims_gpt == nullptr) throw std::runtime_error("band_lims_gpt is NULL");
+    if (igpt < 0 || igpt >= ngpt) throw std::runtime_error("igpt is outside [0, ngpt)");
+    if (!(dz > F(0.))) throw std::runtime_error("dz must be > 0");
+    check_grid(nx, ny, nz, knx, kny, knz);
+    launch_k_null<F>(nx, ny, nz, nbnd, igpt, top_at_1 ? 1 : 0, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null,
+                     static_cast<hipStream_t>(stream));
+    RRX_CATCH(entry)
+}
+
+template<typename F>
+int trace_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, RrxBool independent_column,
+                const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
+                F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, F inc_dir, F inc_dif,
+                int knx, int kny, int knz, const F* k_null, u64 seed, long long photon0, long long nphotons, int max_events,
+                u64* sfc_dn_dir, u64* sfc_dn_dif, u64* sfc_up, u64* tod_up, u64* abs_dir, u64* abs_dif, u64* n_capped, void* stream)
+{
+    RRX_TRY
+    if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"nphotons", nphotons}})) return 0;
+    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
+    if (photon0 < 0) throw std::runtime_error("photon0 is negative");
+    check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"k_null", k_null}, {"sfc_dn_dir", sfc_dn_dir},
+                  {"sfc_dn_dif", sfc_dn_dif}, {"sfc_up", sfc_up}, {"tod_up", tod_up}, {"abs_dir", abs_dir}, {"abs_dif", abs_dif},
+                  {"n_capped", n_capped}});
+    check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
+    if (igpt < 0 || igpt >= ngpt) throw std::runtime_error("igpt is outside [0, ngpt)");
+    check_scene(dx, dy, dz, mu0);
+    if (inc_dir < F(0.) || inc_dif < F(0.) || !(inc_dir + inc_dif > F(0.))) throw std::runtime_error("inc_dir, inc_dif must be >= 0 with a positive sum");
+    if (max_events < 1) throw std::runtime_error("max_events must be >= 1");
+    check_grid(nx, ny, nz, knx, kny, knz);
+    TraceArgs<F> a{nx, ny, nz, nbnd, igpt, top_at_1 ? 1 : 0, independent_column ? 1 : 0, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g,
+                   dx, dy, dz, sfc_albedo, F(0.), F(0.), F(0.), F(0.), knx, kny, knz, k_null, 0u, 0u, u64(photon0), nphotons, max_events,
+                   sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped};
+    launch_trace<F>(a, mu0, azimuth, inc_dir, inc_dif, seed, static_cast<hipStream_t>(stream));
+    RRX_CATCH(entry)
+}
+
+template<typename F>
+int counts_to_flux_entry(const char* entry, long long n, const u64* counts, F scale, F* out, void* stream)
+{
+    RRX_TRY
+    if (check_extents({{"n", n}})) return 0;
+    check_needed({{"counts", counts}, {"out", out}});
+    launch_counts_to_flux<F>(size_t(n), counts, scale, out, static_cast<hipStream_t>(stream));
+    RRX_CATCH(entry)
+}
+
+template<typename F>
+int raytracer_sw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column,
+                       const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
+                       F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif,
+                       int knx, int kny, int knz, long long photons_per_pixel, u64 seed, int max_events,
+                       F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, u64* n_capped, void* stream)
+{
+    RRX_TRY
+    if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"photons_per_pixel", photons_per_pixel}})) return 0;
+    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
+    check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"inc_dir", inc_dir}, {"inc_dif", inc_dif},
+                  {"sfc_dn_dir", sfc_dn_dir}, {"sfc_dn_dif", sfc_dn_dif}, {"sfc_up", sfc_up}, {"tod_up", tod_up}, {"abs_dir", abs_dir},
+                  {"abs_dif", abs_dif}, {"n_capped", n_capped}});
+    check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
+    check_scene(dx, dy, dz, mu0);
+    for (int g=0; g<ngpt; ++g)
+        if (inc_dir[g] < F(0.) || inc_dif[g] < F(0.)) throw std::runtime_error("inc_dir, inc_dif must be >= 0");
+    if (max_events < 1) throw std::runtime_error("max_events must be >= 1");
+    check_grid(nx, ny, nz, knx, kny, knz);
+
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t ncol = size_t(nx)*ny, n_sfc = 4*ncol, n_abs = 2*ncol*nz, n_counts = n_sfc + n_abs;
+    const size_t n_kn = (size_t(knx)*kny*knz*sizeof(F) + sizeof(u64) - 1) / sizeof(u64);
+    WorkspaceLease lease(st);
+    u64* counts = lease.get<u64>(n_counts + n_kn);
+    F* k_null = reinterpret_cast<F*>(counts + n_counts);
+    bool ok = hipMemsetAsync(n_capped, 0, sizeof(u64), st) == hipSuccess;
+    for (F* out : {sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up}) ok = ok && hipMemsetAsync(out, 0, ncol*sizeof(F), st) == hipSuccess;
+    for (F* out : {abs_dir, abs_dif}) ok = ok && hipMemsetAsync(out, 0, ncol*nz*sizeof(F), st) == hipSuccess;
+    if (!ok) throw std::runtime_error("zeroing the outputs failed");
+    const long long nphotons = photons_per_pixel*(long long)ncol;
+    for (int g=0; g<ngpt; ++g)
+    {
+        if (!(inc_dir[g] + inc_dif[g] > F(0.))) continue;
+        if (hipMemsetAsync(counts, 0, n_counts*sizeof(u64), st) != hipSuccess) throw std::runtime_error("zeroing the counts failed");
+        launch_k_null<F>(nx, ny, nz, nbnd, g, top_at_1 ? 1 : 0, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null, st);
+        u64* c = counts;
+        TraceArgs<F> a{nx, ny, nz, nbnd, g, top_at_1 ? 1 : 0, independent_column ? 1 : 0, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g,
+                       dx, dy, dz, sfc_albedo, F(0.), F(0.), F(0.), F(0.), knx, kny, knz, k_null, 0u, 0u, 0ull, nphotons, max_events,
+                       c, c + ncol, c + 2*ncol, c + 3*ncol, c + n_sfc, c + n_sfc + ncol*nz, n_capped};
+        launch_trace<F>(a, mu0, azimuth, inc_dir[g], inc_dif[g], seed, st);
+        const F scale = (inc_dir[g] + inc_dif[g]) / F(photons_per_pixel);
+        launch_counts_to_flux<F>(ncol, a.sfc_dn_dir, scale, sfc_dn_dir, st);
+        launch_counts_to_flux<F>(ncol, a.sfc_dn_dif, scale, sfc_dn_dif, st);
+        launch_counts_to_flux<F>(ncol, a.sfc_up, scale, sfc_up, st);
+        launch_counts_to_flux<F>(ncol, a.tod_up, scale, tod_up, st);
+        launch_counts_to_flux<F>(ncol*nz, a.abs_dir, scale / dz, abs_dir, st);
+        launch_counts_to_flux<F>(ncol*nz, a.abs_dif, scale / dz, abs_dif, st);
+    }
+    RRX_CATCH(entry)
+}
+}  // namespace
+
+extern "C"
+{
+#define RRX_DEFINE_RT(F, SFX) \
+int rrx_rt_k_null##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, const F* tau, const int* band_lims_gpt, \
+        const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, void* stream) \
+{ return k_null_entry<F>("rrx_rt_k_null" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null, stream); } \
+int rrx_rt_trace_counts##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, F inc_dir, F inc_dif, int knx, int kny, int knz, const F* k_null, \
+        unsigned long long seed, long long photon0, long long nphotons, int max_events, \
+        unsigned long long* sfc_dn_dir, unsigned long long* sfc_dn_dif, unsigned long long* sfc_up, unsigned long long* tod_up, \
+        unsigned long long* abs_dir, unsigned long long* abs_dif, unsigned long long* n_capped, void* stream) \
+{ return trace_entry<F>("rrx_rt_trace_counts" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
+                        cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, k_null, seed, \
+                        photon0, nphotons, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream); } \
+int rrx_rt_counts_to_flux##SFX(long long n, const unsigned long long* counts, F scale, F* out, void* stream) \
+{ return counts_to_flux_entry<F>("rrx_rt_counts_to_flux" #SFX, n, counts, scale, out, stream); } \
+int rrx_raytracer_sw##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
+        long long photons_per_pixel, unsigned long long seed, int max_events, \
+        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, void* stream) \
+{ return raytracer_sw_entry<F>("rrx_raytracer_sw" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
+                               cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, \
+                               photons_per_pixel, seed, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream); }
+
+RRX_DEFINE_RT(double, _f64)
+RRX_DEFINE_RT(float, _f32)
+}

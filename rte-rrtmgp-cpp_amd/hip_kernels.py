@@ -612,6 +612,75 @@ class HipKernels:
         self._c("mcica_cloud_mask", ncol, nlay, int(ngpt), *head, mask)
         return mask
 
+    # Forward Monte Carlo ray tracer (rrx_rt_*, rrx_raytracer_sw). tau, ssa (ngpt, nz, ncol) with ncol = nx ny, x fastest;
+    # cloud None or (tau, ssa, g), (nbnd, nz, ncol) each, with band_lims (nbnd, 2); sfc_albedo (ncol,); kn_grid = (knx, kny, knz).
+    # Counts are int64 tensors holding the unsigned 64-bit tallies (units of 2^-32 photon).
+    RT_COUNTS = ("sfc_dn_dir", "sfc_dn_dif", "sfc_up", "tod_up", "abs_dir", "abs_dif")
+    RT_MAX_EVENTS = 1 << 22
+
+    def _rt_scene(self, tau, nx, ny, cloud, band_lims):
+        ngpt, nz, ncol = tau.shape
+        if ncol != nx*ny:
+            raise ValueError(f"raytracer: ncol = {ncol} is not nx ny = {nx}*{ny}")
+        ct, cw, cg = (None, None, None) if cloud is None else cloud
+        if cloud is not None and band_lims is None:
+            raise ValueError("raytracer: a cloud triple needs band_lims")
+        nbnd = int(band_lims.shape[0]) if band_lims is not None else 0
+        return (int(nx), int(ny), nz, ngpt, nbnd), (band_lims if cloud is not None else None, ct, cw, cg)
+
+    def rt_zero_counts(self, nz, ncol):
+        out = {k: torch.zeros((ncol,), dtype=torch.int64, device=self.device) for k in self.RT_COUNTS[:4]}
+        out.update({k: torch.zeros((nz, ncol), dtype=torch.int64, device=self.device) for k in self.RT_COUNTS[4:]})
+        out["n_capped"] = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        return out
+
+    def rt_k_null(self, tau, igpt, nx, ny, dz, kn_grid, top_at_1, cloud=None, band_lims=None):
+        """k_null (knz, kny, knx), kn counted upward from the surface, for g-point igpt (0-based)."""
+        dims, (lims, ct, _, _) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        knx, kny, knz = (int(k) for k in kn_grid)
+        out = self.empty((knz, kny, knx))
+        self._c("rt_k_null", *dims, int(igpt), BoolArg(top_at_1), tau, lims, ct, float(dz), knx, kny, knz, out)
+        return out
+
+    def rt_trace_counts(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, k_null, seed,
+                        photon0, nphotons, top_at_1=False, independent_column=False, cloud=None, band_lims=None, counts=None,
+                        max_events=None):
+        """Adds the photons [photon0, photon0 + nphotons) of g-point igpt into counts (rt_zero_counts; made when None)."""
+        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        knx, kny, knz = (int(k) for k in kn_grid)
+        counts = self.rt_zero_counts(dims[2], dims[0]*dims[1]) if counts is None else counts
+        self._c("rt_trace_counts", *dims, int(igpt), BoolArg(top_at_1), BoolArg(independent_column), tau, ssa, lims, ct, cw, cg,
+                float(dx), float(dy), float(dz), sfc_albedo, float(mu0), float(azimuth), float(inc_dir), float(inc_dif), knx, kny, knz,
+                k_null, ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.c_longlong(int(photon0)), ctypes.c_longlong(int(nphotons)),
+                int(self.RT_MAX_EVENTS if max_events is None else max_events), *(counts[k] for k in self.RT_COUNTS), counts["n_capped"])
+        return counts
+
+    def rt_counts_to_flux(self, counts, scale, out):
+        """out += counts 2^-32 scale"""
+        self._c("rt_counts_to_flux", ctypes.c_longlong(counts.numel()), counts, float(scale), out)
+        return out
+
+    def raytracer_sw(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, photons_per_pixel, seed,
+                     top_at_1=False, independent_column=False, cloud=None, band_lims=None, max_events=None):
+        """The spectral loop in one call. inc_dir, inc_dif: (ngpt,) numbers on the host. Returns the four surface / top fluxes
+        (ncol,) in W m-2, abs_dir / abs_dif (nz, ncol) in W m-3 and n_capped (int)."""
+        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        nz, ngpt, ncol = dims[2], dims[3], dims[0]*dims[1]
+        knx, kny, knz = (int(k) for k in kn_grid)
+        inc_dir = np.ascontiguousarray(np.asarray(inc_dir, dtype=self.np_dtype).reshape(-1))
+        inc_dif = np.ascontiguousarray(np.asarray(inc_dif, dtype=self.np_dtype).reshape(-1))
+        if inc_dir.size != ngpt or inc_dif.size != ngpt:
+            raise ValueError("raytracer: inc_dir, inc_dif are (ngpt,)")
+        out = {k: self.empty((ncol,)) for k in self.RT_COUNTS[:4]}
+        out.update({k: self.empty((nz, ncol)) for k in self.RT_COUNTS[4:]})
+        n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        self._c("raytracer_sw", *dims, BoolArg(top_at_1), BoolArg(independent_column), tau, ssa, lims, ct, cw, cg,
+                float(dx), float(dy), float(dz), sfc_albedo, float(mu0), float(azimuth), inc_dir, inc_dif, knx, kny, knz,
+                ctypes.c_longlong(int(photons_per_pixel)), ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                int(self.RT_MAX_EVENTS if max_events is None else max_events), *(out[k] for k in self.RT_COUNTS), n_capped)
+        out["n_capped"] = int(n_capped.item())
+        return out
+
     def delta_scale_2str_k(self, tau, ssa, g):
         ngpt, nlay, ncol = tau.shape
         self._c("delta_scale_2str_k", ncol, nlay, ngpt, tau, ssa, g)

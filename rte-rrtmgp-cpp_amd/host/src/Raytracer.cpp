@@ -1,0 +1,46 @@
+// Raytracer_gpu: checks the shapes and forwards to rrx_raytracer_sw; a non-zero status becomes std::runtime_error.
+#include "Raytracer.h"
+
+unsigned long long Raytracer_gpu::trace_rays(
+        const int nx, const int ny, const int nz,
+        const Float dx, const Float dy, const Float dz,
+        const bool top_at_1, const bool independent_column,
+        const Array_gpu<Float,3>& tau, const Array_gpu<Float,3>& ssa,
+        const Array_gpu<int,2>& band_lims_gpt,
+        const Array_gpu<Float,3>& cld_tau, const Array_gpu<Float,3>& cld_ssa, const Array_gpu<Float,3>& cld_g,
+        const Array_gpu<Float,1>& sfc_albedo,
+        const Float mu0, const Float azimuth,
+        const Array<Float,1>& inc_dir, const Array<Float,1>& inc_dif,
+        const int knx, const int kny, const int knz,
+        const long long photons_per_pixel, const unsigned long long seed, const int max_events,
+        Array_gpu<Float,1>& sfc_dn_dir, Array_gpu<Float,1>& sfc_dn_dif, Array_gpu<Float,1>& sfc_up, Array_gpu<Float,1>& tod_up,
+        Array_gpu<Float,2>& abs_dir, Array_gpu<Float,2>& abs_dif)
+{
+    if (nx < 0 || ny < 0 || nz < 0) throw std::runtime_error("Raytracer_gpu::trace_rays: negative extent");
+    const long long ncol = (long long)nx*ny;
+    const int ngpt = tau.dim(3);
+    const int nbnd = band_lims_gpt.dim(2);
+    if (tau.dim(1) != ncol || tau.dim(2) != nz || ssa.get_dims() != tau.get_dims())
+        throw std::runtime_error("Raytracer_gpu::trace_rays: tau, ssa are not (nx ny, nz, ngpt)");
+    const bool cloudy = cld_tau.size() > 0;
+    if (cloudy && (cld_tau.dim(1) != ncol || cld_tau.dim(2) != nz || cld_tau.dim(3) != nbnd || cld_ssa.get_dims() != cld_tau.get_dims() ||
+                   cld_g.get_dims() != cld_tau.get_dims()))
+        throw std::runtime_error("Raytracer_gpu::trace_rays: the cloud arrays are not (nx ny, nz, nbnd)");
+    if (!cloudy && (cld_ssa.size() > 0 || cld_g.size() > 0))
+        throw std::runtime_error("Raytracer_gpu::trace_rays: the cloud arrays are all empty or all given");
+    if (sfc_albedo.size() != ncol || inc_dir.size() != ngpt || inc_dif.size() != ngpt)
+        throw std::runtime_error("Raytracer_gpu::trace_rays: sfc_albedo is not (nx ny) or inc_dir, inc_dif are not (ngpt)");
+    for (const Array_gpu<Float,1>* a : {&sfc_dn_dir, &sfc_dn_dif, &sfc_up, &tod_up})
+        if (a->size() != ncol) throw std::runtime_error("Raytracer_gpu::trace_rays: a flux array is not (nx ny)");
+    for (const Array_gpu<Float,2>* a : {&abs_dir, &abs_dif})
+        if (a->dim(1) != ncol || a->dim(2) != nz) throw std::runtime_error("Raytracer_gpu::trace_rays: an absorption array is not (nx ny, nz)");
+
+    Array_gpu<unsigned long long,1> n_capped({1});
+    RRX_CALL(rrx_raytracer_sw, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
+             tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
+             cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
+             dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), inc_dif.ptr(), knx, kny, knz,
+             photons_per_pixel, seed, max_events,
+             sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr());
+    return n_capped({1});
+}

@@ -7,6 +7,7 @@
 #include <memory>
 #include <string>
 #include "Radiation_solver.h"
+#include "Raytracer.h"
 #include "rrx_cxx_driver.h"
 
 namespace
@@ -192,6 +193,38 @@ int rrx_cxx_driver_fluxes(void* h, const Float** ptrs)
         Driver& d = *static_cast<Driver*>(h);
         const Array_gpu<Float,2>* a[7] = {&d.lw_up, &d.lw_dn, &d.lw_net, &d.sw_up, &d.sw_dn, &d.sw_dir, &d.sw_net};
         for (int i=0; i<7; ++i) ptrs[i] = a[i]->ptr();
+    });
+}
+
+// Raytracer_gpu::trace_rays on device arrays the caller owns (views; needs no driver handle). tau, ssa (ncol, nz, ngpt); band_lims_gpt
+// (2, nbnd); cld_* (ncol, nz, nbnd) or all NULL; sfc_albedo (ncol); inc_dir, inc_dif (ngpt) on the HOST; out6: device arrays sfc_dn_dir,
+// sfc_dn_dif, sfc_up, tod_up (ncol), abs_dir, abs_dif (ncol, nz). Runs on `stream` and waits for the count of dropped photons.
+int rrx_cxx_trace_rays(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+        const int top_at_1, const int independent_column, const Float* tau, const Float* ssa, const int* band_lims_gpt,
+        const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
+        const Float* inc_dir, const Float* inc_dif, const int knx, const int kny, const int knz, const long long photons_per_pixel,
+        const unsigned long long seed, const int max_events, Float* const* out6, unsigned long long* n_capped, void* stream)
+{
+    return guarded([&]
+    {
+        void* const before = rrx_host::current_stream();
+        rrx_host::set_stream(stream);
+        try
+        {
+            const int ncol = nx*ny;
+            auto view3 = [](const Float* p, int a, int b, int c) { return p ? Array_gpu<Float,3>(const_cast<Float*>(p), {a, b, c}) : Array_gpu<Float,3>(); };
+            Array<Float,1> h_dir({ngpt}), h_dif({ngpt});
+            for (int g=1; g<=ngpt; ++g) { h_dir({g}) = inc_dir[g-1]; h_dif({g}) = inc_dif[g-1]; }
+            Array_gpu<Float,1> o0 = view1(out6[0], ncol), o1 = view1(out6[1], ncol), o2 = view1(out6[2], ncol), o3 = view1(out6[3], ncol);
+            Array_gpu<Float,2> o4 = view2(out6[4], ncol, nz), o5 = view2(out6[5], ncol, nz);
+            Raytracer_gpu raytracer;
+            *n_capped = raytracer.trace_rays(nx, ny, nz, dx, dy, dz, top_at_1 != 0, independent_column != 0,
+                    view3(tau, ncol, nz, ngpt), view3(ssa, ncol, nz, ngpt), Array_gpu<int,2>(const_cast<int*>(band_lims_gpt), {2, nbnd}),
+                    view3(cld_tau, ncol, nz, nbnd), view3(cld_ssa, ncol, nz, nbnd), view3(cld_g, ncol, nz, nbnd), view1(sfc_albedo, ncol),
+                    mu0, azimuth, h_dir, h_dif, knx, kny, knz, photons_per_pixel, seed, max_events, o0, o1, o2, o3, o4, o5);
+        }
+        catch (...) { rrx_host::set_stream(before); throw; }
+        rrx_host::set_stream(before);
     });
 }
 }

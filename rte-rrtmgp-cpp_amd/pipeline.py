@@ -184,6 +184,45 @@ def solve_sw(be, kd, atm, col_dry=None, cloud_lut=None, delta_cloud=False, do_br
     return out
 
 
+def raytrace_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, photons_per_pixel, seed, cloud_lut=None, kn_grid=None,
+                independent_column=False, sfc_albedo=None, max_events=None):
+    """3-D shortwave surface / top fluxes and absorption from the forward Monte Carlo ray tracer (rrx_raytracer_sw).
+
+    The atmosphere's columns are the pixels of an nx x ny domain (column = ix + nx iy) of cells dx x dy x dz metres, periodic in x
+    and y, under one sun: mu0 and tsi_scaling must be the same in every column. The clear per-g-point SW gas optics and (with
+    cloud_lut) the band cloud optics, not delta-scaled, feed the tracer; inc_dir[g] = solar_source[g] tsi_scaling mu0, no diffuse
+    incident flux. azimuth: direction of travel of the direct beam, radians from +x. kn_grid = (knx, kny, knz) dividing (nx, ny,
+    nlay), default one block per cell. sfc_albedo (ncol,): default the atmosphere's, which must then be the same in every band and
+    for direct and diffuse light (the tracer's surface is Lambertian with one broadband albedo per pixel).
+    Returns sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up (ncol,) in W m-2, abs_dir, abs_dif (nlay, ncol) in W m-3 and n_capped."""
+    ncol, nlay, ngpt = atm.ncol, atm.nlay, kd_sw.ngpt
+    if ncol != nx*ny:
+        raise ValueError(f"raytrace_sw: ncol = {ncol} is not nx ny = {nx}*{ny}")
+    mu0 = be.to_numpy(atm.mu0).reshape(-1)
+    tsi = be.to_numpy(atm.tsi_scaling).reshape(-1)
+    if np.any(mu0 != mu0[0]) or np.any(tsi != tsi[0]):
+        raise ValueError("raytrace_sw: mu0 and tsi_scaling must be the same in every column (one sun for the domain)")
+    if sfc_albedo is None:
+        a_dir, a_dif = be.to_numpy(atm.sfc_alb_dir), be.to_numpy(atm.sfc_alb_dif)
+        if np.any(a_dir != a_dif) or np.any(a_dif != a_dif[:, :1]):
+            raise ValueError("raytrace_sw: the atmosphere's albedo differs between bands or between direct and diffuse; pass sfc_albedo")
+        sfc_albedo = np.ascontiguousarray(a_dif[:, 0])
+    sfc_albedo = be.asarray(sfc_albedo)
+    kn_grid = (nx, ny, nlay) if kn_grid is None else tuple(int(k) for k in kn_grid)
+
+    col_dry, col_gas, _ = gas_state(be, kd_sw, atm, None, interpolate=False)
+    tau = be.empty((ngpt, nlay, ncol)); ssa = be.empty((ngpt, nlay, ncol))
+    g = None if getattr(be, "supports_null_g", False) else be.empty((ngpt, nlay, ncol))
+    be.gas_optics_sw_direct(kd_sw, atm.p_lay, atm.t_lay, col_gas, col_dry, tau, ssa, g)
+    cld = be.cloud_optics_2str(cloud_lut, atm.lwp, atm.iwp, atm.rel, atm.dei) if cloud_lut is not None else None
+
+    F = be.np_dtype.type
+    inc_dir = (be.to_numpy(kd_sw.solar_source).astype(be.np_dtype) * F(tsi[0])) * F(mu0[0])
+    return be.raytracer_sw(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, float(mu0[0]), azimuth, inc_dir, np.zeros_like(inc_dir), kn_grid,
+                           photons_per_pixel, seed, top_at_1=atm.top_at_1, independent_column=independent_column, cloud=cld,
+                           band_lims=kd_sw.band_lims_gpt, max_events=max_events)
+
+
 _STEP_ATMOSPHERE = None
 
 
