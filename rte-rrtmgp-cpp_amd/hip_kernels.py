@@ -87,123 +87,112 @@ class HipKernels:
         return self.lib.call("rrx_" + name + self.sfx, *args, self._st())
 
     # ---- solvers ----------------------------------------------------------------------------------
-    def lw_secants_array(self, ncol, ngpt, n_quad, max_pts, gauss_Ds):
-        sec = self.empty((n_quad, ngpt, ncol))
-        self._c("lw_secants_array", ncol, ngpt, n_quad, max_pts, gauss_Ds, sec)
-        return sec
+    def lw_secants_array(self, ncol, ngpt, n_quad, max_pts, gauss_Ds, out=None):
+        out = self.empty((n_quad, ngpt, ncol)) if out is None else out
+        self._c("lw_secants_array", ncol, ngpt, n_quad, max_pts, gauss_Ds, out)
+        return out
+
+    def _lw_noscat(self, entry, top_at_1, secants, weights, tau, scat, lay_source, lev_source, sfc_emis, sfc_src, inc_flux,
+                   do_broadband, do_jacobians, sfc_src_jac, out):
+        """The argument list of rrx_lw_solver_noscat and, with scat = (ssa, g), of its _rescaled twin. out=: preallocated flux_up /
+        flux_dn [/ flux_up_jac]; the fluxes are (nlev, ncol) in broadband mode and (ngpt, nlev, ncol) otherwise."""
+        ngpt, nlay, ncol = tau.shape
+        if out is None:
+            shape = (nlay+1, ncol) if do_broadband else (ngpt, nlay+1, ncol)
+            out = dict(flux_up=self.empty(shape), flux_dn=self.empty(shape))
+            if do_jacobians:
+                out["flux_up_jac"] = self.empty((ngpt, nlay+1, ncol))
+        fl = (out["flux_up"], out["flux_dn"])
+        per_gpt, loc = ((None, None), fl) if do_broadband else (fl, (None, None))
+        self._c(entry, ncol, nlay, ngpt, BoolArg(top_at_1), weights.shape[0], secants, weights, tau, *scat, lay_source, lev_source,
+                sfc_emis, sfc_src, inc_flux, *per_gpt, BoolArg(do_broadband), *loc, BoolArg(do_jacobians), sfc_src_jac,
+                out.get("flux_up_jac"))
+        return out
 
     def lw_solver_noscat(self, top_at_1, secants, weights, tau, lay_source, lev_source, sfc_emis, sfc_src,
-                         inc_flux=None, do_broadband=False, do_jacobians=False, sfc_src_jac=None):
-        ngpt, nlay, ncol = tau.shape
-        nmus = weights.shape[0]
-        out = {}
-        flux_up = flux_dn = up_loc = dn_loc = jac = None
-        if do_broadband:
-            up_loc = self.empty((nlay+1, ncol)); dn_loc = self.empty((nlay+1, ncol))
-            out.update(flux_up=up_loc, flux_dn=dn_loc)
-        else:
-            flux_up = self.empty((ngpt, nlay+1, ncol)); flux_dn = self.empty((ngpt, nlay+1, ncol))
-            out.update(flux_up=flux_up, flux_dn=flux_dn)
-        if do_jacobians:
-            jac = self.empty((ngpt, nlay+1, ncol))
-            out["flux_up_jac"] = jac
-        self._c("lw_solver_noscat", ncol, nlay, ngpt, BoolArg(top_at_1), nmus, secants, weights,
-                tau, lay_source, lev_source, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn,
-                BoolArg(do_broadband), up_loc, dn_loc, BoolArg(do_jacobians), sfc_src_jac, jac)
-        return out
+                         inc_flux=None, do_broadband=False, do_jacobians=False, sfc_src_jac=None, out=None):
+        return self._lw_noscat("lw_solver_noscat", top_at_1, secants, weights, tau, (), lay_source, lev_source, sfc_emis, sfc_src,
+                               inc_flux, do_broadband, do_jacobians, sfc_src_jac, out)
 
     def lw_solver_noscat_into(self, top_at_1, secants, weights, tau, lay_source, lev_source, sfc_emis, sfc_src,
                               flux_up, flux_dn):
         """Allocation-free form used inside timed regions."""
+        self.lw_solver_noscat(top_at_1, secants, weights, tau, lay_source, lev_source, sfc_emis, sfc_src,
+                              out=dict(flux_up=flux_up, flux_dn=flux_dn))
+
+    def _sw_2stream(self, entry, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, inc_flux_dif, do_broadband, out):
+        """The argument list of rrx_sw_solver_2stream and its _mu0lay twin (mu0 per column or per layer)."""
         ngpt, nlay, ncol = tau.shape
-        self._c("lw_solver_noscat", ncol, nlay, ngpt, BoolArg(top_at_1), weights.shape[0], secants, weights,
-                tau, lay_source, lev_source, sfc_emis, sfc_src, None, flux_up, flux_dn,
-                BoolArg(False), None, None, BoolArg(False), None, None)
+        if out is None:
+            shape = (nlay+1, ncol) if do_broadband else (ngpt, nlay+1, ncol)
+            out = {k: self.empty(shape) for k in ("flux_up", "flux_dn", "flux_dir")}
+        fl = (out["flux_up"], out["flux_dn"], out["flux_dir"])
+        per_gpt, loc = ((None, None, None), fl) if do_broadband else (fl, (None, None, None))
+        self._c(entry, ncol, nlay, ngpt, BoolArg(top_at_1), tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, *per_gpt,
+                BoolArg(inc_flux_dif is not None), inc_flux_dif, BoolArg(do_broadband), *loc)
+        return out
 
     def sw_solver_2stream(self, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir,
-                          inc_flux_dif=None, do_broadband=False):
-        ngpt, nlay, ncol = tau.shape
+                          inc_flux_dif=None, do_broadband=False, out=None):
+        """g may be None (asymmetry identically zero). out=: preallocated flux_up/dn/dir, (nlev, ncol) in broadband mode and
+        (ngpt, nlev, ncol) otherwise."""
         if mu0.dim() == 2:          # (nlay, ncol) CPU-style: the GPU boundary takes mu0(ncol)
             mu0 = mu0[0].contiguous()
-        fu = fd = fr = ul = dl = rl = None
-        if do_broadband:
-            ul = self.empty((nlay+1, ncol)); dl = self.empty((nlay+1, ncol)); rl = self.empty((nlay+1, ncol))
-            out = dict(flux_up=ul, flux_dn=dl, flux_dir=rl)
-        else:
-            fu = self.empty((ngpt, nlay+1, ncol)); fd = self.empty((ngpt, nlay+1, ncol)); fr = self.empty((ngpt, nlay+1, ncol))
-            out = dict(flux_up=fu, flux_dn=fd, flux_dir=fr)
-        self._c("sw_solver_2stream", ncol, nlay, ngpt, BoolArg(top_at_1), tau, ssa, g, mu0,
-                sfc_alb_dir, sfc_alb_dif, inc_flux_dir, fu, fd, fr,
-                BoolArg(inc_flux_dif is not None), inc_flux_dif, BoolArg(do_broadband), ul, dl, rl)
-        return out
+        return self._sw_2stream("sw_solver_2stream", top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, inc_flux_dif,
+                                do_broadband, out)
 
     def sw_solver_2stream_into(self, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir,
                                flux_up, flux_dn, flux_dir):
+        self.sw_solver_2stream(top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir,
+                               out=dict(flux_up=flux_up, flux_dn=flux_dn, flux_dir=flux_dir))
+
+    def _byband_out(self, out, names, nbnd, nlay, ncol, net, broadband):
+        """The outputs of a by-band solver entry: out as given, or bnd_flux_<name> (nbnd, nlev, ncol) for the names [and net], and
+        with broadband flux_<name> (nlev, ncol)."""
+        if out is None:
+            out = {"bnd_flux_" + k: self.empty((nbnd, nlay+1, ncol)) for k in names + (("net",) if net else ())}
+            if broadband:
+                out.update({"flux_" + k: self.empty((nlay+1, ncol)) for k in names})
+        return out
+
+    def _sw_2stream_byband(self, entry, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, band_lims, inc_flux_dif,
+                           out, net, broadband):
         ngpt, nlay, ncol = tau.shape
-        self._c("sw_solver_2stream", ncol, nlay, ngpt, BoolArg(top_at_1), tau, ssa, g, mu0,
-                sfc_alb_dir, sfc_alb_dif, inc_flux_dir, flux_up, flux_dn, flux_dir,
-                BoolArg(False), None, BoolArg(False), None, None, None)
+        nbnd = band_lims.shape[0]
+        out = self._byband_out(out, ("up", "dn", "dir"), nbnd, nlay, ncol, net, broadband)
+        self._c(entry, ncol, nlay, ngpt, nbnd, BoolArg(top_at_1), tau, ssa, g, mu0,
+                sfc_alb_dir, sfc_alb_dif, inc_flux_dir, BoolArg(inc_flux_dif is not None), inc_flux_dif, band_lims,
+                out["bnd_flux_up"], out["bnd_flux_dn"], out["bnd_flux_dir"], out.get("bnd_flux_net"),
+                out.get("flux_up"), out.get("flux_dn"), out.get("flux_dir"))
+        return out
 
     def sw_solver_2stream_byband(self, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, band_lims,
                                  inc_flux_dif=None, out=None, net=True, broadband=True):
         """By-band fluxes from the fused broadband solver: bnd_flux_up/dn/dir (nbnd, nlev, ncol), bnd_flux_net = dn - up, and the
         broadband flux_up/dn/dir (the band sums added in band order). band_lims: (nbnd, 2) int32, 1-based inclusive g-point limits.
         out=: a dict of preallocated tensors under those keys (missing optional keys are not written)."""
-        ngpt, nlay, ncol = tau.shape
-        nbnd = band_lims.shape[0]
         if mu0.dim() == 2:
             mu0 = mu0[0].contiguous()
-        if out is None:
-            out = {k: self.empty((nbnd, nlay+1, ncol)) for k in ("bnd_flux_up", "bnd_flux_dn", "bnd_flux_dir")}
-            if net:
-                out["bnd_flux_net"] = self.empty((nbnd, nlay+1, ncol))
-            if broadband:
-                out.update({k: self.empty((nlay+1, ncol)) for k in ("flux_up", "flux_dn", "flux_dir")})
-        self._c("sw_solver_2stream_byband", ncol, nlay, ngpt, nbnd, BoolArg(top_at_1), tau, ssa, g, mu0,
-                sfc_alb_dir, sfc_alb_dif, inc_flux_dir, BoolArg(inc_flux_dif is not None), inc_flux_dif, band_lims,
-                out["bnd_flux_up"], out["bnd_flux_dn"], out["bnd_flux_dir"], out.get("bnd_flux_net"),
-                out.get("flux_up"), out.get("flux_dn"), out.get("flux_dir"))
-        return out
+        return self._sw_2stream_byband("sw_solver_2stream_byband", top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir,
+                                       band_lims, inc_flux_dif, out, net, broadband)
 
     # mu0 by layer (DESIGN.md 4.13): mu0_lay is (nlay, ncol), every layer of a column with its own cosine
-    def _mu0_lay(self, mu0_lay, nlay, ncol):
-        if tuple(mu0_lay.shape) != (nlay, ncol):
-            raise ValueError(f"mu0_lay must be (nlay, ncol) = ({nlay}, {ncol}), got {tuple(mu0_lay.shape)}")
+    def _mu0_lay(self, mu0_lay, tau):
+        if tuple(mu0_lay.shape) != tuple(tau.shape[1:]):
+            raise ValueError(f"mu0_lay must be (nlay, ncol) = ({tau.shape[1]}, {tau.shape[2]}), got {tuple(mu0_lay.shape)}")
         return mu0_lay
 
     def sw_solver_2stream_mu0lay(self, top_at_1, tau, ssa, g, mu0_lay, sfc_alb_dir, sfc_alb_dif, inc_flux_dir,
                                  inc_flux_dif=None, do_broadband=False, out=None):
-        """sw_solver_2stream with the cosine of the solar zenith angle per layer. g may be None (asymmetry identically zero).
-        out=: preallocated flux_up/dn/dir, (nlev, ncol) in broadband mode and (ngpt, nlev, ncol) otherwise."""
-        ngpt, nlay, ncol = tau.shape
-        mu0_lay = self._mu0_lay(mu0_lay, nlay, ncol)
-        shape = (nlay+1, ncol) if do_broadband else (ngpt, nlay+1, ncol)
-        if out is None:
-            out = {k: self.empty(shape) for k in ("flux_up", "flux_dn", "flux_dir")}
-        per_gpt = (None, None, None) if do_broadband else (out["flux_up"], out["flux_dn"], out["flux_dir"])
-        loc = (out["flux_up"], out["flux_dn"], out["flux_dir"]) if do_broadband else (None, None, None)
-        self._c("sw_solver_2stream_mu0lay", ncol, nlay, ngpt, BoolArg(top_at_1), tau, ssa, g, mu0_lay,
-                sfc_alb_dir, sfc_alb_dif, inc_flux_dir, *per_gpt,
-                BoolArg(inc_flux_dif is not None), inc_flux_dif, BoolArg(do_broadband), *loc)
-        return out
+        """sw_solver_2stream with the cosine of the solar zenith angle per layer; g and out= as there."""
+        return self._sw_2stream("sw_solver_2stream_mu0lay", top_at_1, tau, ssa, g, self._mu0_lay(mu0_lay, tau), sfc_alb_dir, sfc_alb_dif,
+                                inc_flux_dir, inc_flux_dif, do_broadband, out)
 
     def sw_solver_2stream_byband_mu0lay(self, top_at_1, tau, ssa, g, mu0_lay, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, band_lims,
                                         inc_flux_dif=None, out=None, net=True, broadband=True):
         """sw_solver_2stream_byband with the cosine of the solar zenith angle per layer; outputs as there."""
-        ngpt, nlay, ncol = tau.shape
-        nbnd = band_lims.shape[0]
-        mu0_lay = self._mu0_lay(mu0_lay, nlay, ncol)
-        if out is None:
-            out = {k: self.empty((nbnd, nlay+1, ncol)) for k in ("bnd_flux_up", "bnd_flux_dn", "bnd_flux_dir")}
-            if net:
-                out["bnd_flux_net"] = self.empty((nbnd, nlay+1, ncol))
-            if broadband:
-                out.update({k: self.empty((nlay+1, ncol)) for k in ("flux_up", "flux_dn", "flux_dir")})
-        self._c("sw_solver_2stream_byband_mu0lay", ncol, nlay, ngpt, nbnd, BoolArg(top_at_1), tau, ssa, g, mu0_lay,
-                sfc_alb_dir, sfc_alb_dif, inc_flux_dir, BoolArg(inc_flux_dif is not None), inc_flux_dif, band_lims,
-                out["bnd_flux_up"], out["bnd_flux_dn"], out["bnd_flux_dir"], out.get("bnd_flux_net"),
-                out.get("flux_up"), out.get("flux_dn"), out.get("flux_dir"))
-        return out
+        return self._sw_2stream_byband("sw_solver_2stream_byband_mu0lay", top_at_1, tau, ssa, g, self._mu0_lay(mu0_lay, tau), sfc_alb_dir,
+                                       sfc_alb_dif, inc_flux_dir, band_lims, inc_flux_dif, out, net, broadband)
 
     def zenith_angle_spherical_correction(self, ref_mu, alt, ref_alt=None, planet_radius=6.37123e6, out=None):
         """mu0_lay (nlay, ncol) from the cosine ref_mu (ncol) that holds at altitude ref_alt (ncol, None = 0) and the layer
@@ -234,17 +223,7 @@ class HipKernels:
         return r
 
     def _absorption_args(self, kd, it, play, tlay, col_gas):
-        nlay, ncol = play.shape
-        return (ncol, nlay, kd.nbnd, kd.ngpt, kd.ngas, kd.nflav, kd.neta, kd.npres, kd.ntemp,
-                kd.minor_limits_gpt_lower.shape[0], kd.kminor_lower.shape[0],
-                kd.minor_limits_gpt_upper.shape[0], kd.kminor_upper.shape[0], kd.idx_h2o,
-                kd.gpoint_flavor, kd.band_lims_gpt, kd.kmajor, kd.kminor_lower, kd.kminor_upper,
-                kd.minor_limits_gpt_lower, kd.minor_limits_gpt_upper,
-                kd.minor_scales_with_density_lower, kd.minor_scales_with_density_upper,
-                kd.scale_by_complement_lower, kd.scale_by_complement_upper,
-                kd.idx_minor_lower, kd.idx_minor_upper, kd.idx_minor_scaling_lower, kd.idx_minor_scaling_upper,
-                kd.kminor_start_lower, kd.kminor_start_upper,
-                it["tropo"], it["col_mix"], it["fmajor"], it["fminor"], play, tlay, col_gas)
+        return self._minor_args(kd, play) + (it["tropo"], it["col_mix"], it["fmajor"], it["fminor"], play, tlay, col_gas)
 
     def compute_tau_absorption(self, kd, it, play, tlay, col_gas, tau):
         self._c("compute_tau_absorption", *self._absorption_args(kd, it, play, tlay, col_gas),
@@ -295,11 +274,17 @@ class HipKernels:
             self._c("gas_optics_sw_direct_allsky", *self._minor_args(kd, play), *self._direct_args(kd), play, tlay, col_gas, col_dry,
                     kd.krayl, tau, ssa, g, *by_band)
 
+    def _planck_sources(self, kd, nlay, ncol):
+        return dict(sfc_src=self.empty((kd.ngpt, ncol)), lay_src=self.empty((kd.ngpt, nlay, ncol)),
+                    lev_src=self.empty((kd.ngpt, nlay+1, ncol)), sfc_src_jac=self.empty((kd.ngpt, ncol)))
+
+    def _planck_lite(self, kd, nlay, ncol):
+        return dict(pfrac=self.empty((kd.ngpt, nlay, ncol)), blay=self.empty((kd.nbnd, nlay, ncol)),
+                    blev=self.empty((kd.nbnd, nlay+1, ncol)), sfc_src=self.empty((kd.ngpt, ncol)), sfc_src_jac=self.empty((kd.ngpt, ncol)))
+
     def planck_source_direct(self, kd, play, tlay, tlev, tsfc, sfc_lay, col_gas, out=None):
         nlay, ncol = tlay.shape
-        if out is None:
-            out = dict(sfc_src=self.empty((kd.ngpt, ncol)), lay_src=self.empty((kd.ngpt, nlay, ncol)),
-                       lev_src=self.empty((kd.ngpt, nlay+1, ncol)), sfc_src_jac=self.empty((kd.ngpt, ncol)))
+        out = self._planck_sources(kd, nlay, ncol) if out is None else out
         self._c("planck_source_direct", ncol, nlay, kd.nbnd, kd.ngpt, kd.ngas, kd.nflav, kd.neta, kd.npres, kd.ntemp, kd.nPlanckTemp,
                 play, tlay, tlev, tsfc, sfc_lay, col_gas, *self._direct_args(kd),
                 kd.gpoint_bands, kd.band_lims_gpt, kd.planck_frac, float(kd.totplnk_delta), kd.totplnk, kd.gpoint_flavor,
@@ -309,9 +294,7 @@ class HipKernels:
     # "Planck-lite" LW chain: fractions + band Planck functions, sources formed inside the broadband solver
     def planck_fractions(self, kd, play, tlay, tlev, tsfc, sfc_lay, col_gas, out=None):
         nlay, ncol = tlay.shape
-        if out is None:
-            out = dict(pfrac=self.empty((kd.ngpt, nlay, ncol)), blay=self.empty((kd.nbnd, nlay, ncol)),
-                       blev=self.empty((kd.nbnd, nlay+1, ncol)), sfc_src=self.empty((kd.ngpt, ncol)), sfc_src_jac=self.empty((kd.ngpt, ncol)))
+        out = self._planck_lite(kd, nlay, ncol) if out is None else out
         self._c("planck_fractions", ncol, nlay, kd.nbnd, kd.ngpt, kd.ngas, kd.nflav, kd.neta, kd.npres, kd.ntemp, kd.nPlanckTemp,
                 play, tlay, tlev, tsfc, sfc_lay, col_gas, *self._direct_args(kd),
                 kd.gpoint_bands, kd.band_lims_gpt, kd.planck_frac, float(kd.totplnk_delta), kd.totplnk, kd.gpoint_flavor,
@@ -321,9 +304,7 @@ class HipKernels:
     def gas_optics_lw_fractions(self, kd, play, tlay, tlev, tsfc, sfc_lay, col_gas, tau, out=None, by_band=None):
         """tau and the Planck-lite outputs in one pass (rrx_gas_optics_lw_fractions); by_band as in gas_optics_lw_direct"""
         nlay, ncol = tlay.shape
-        if out is None:
-            out = dict(pfrac=self.empty((kd.ngpt, nlay, ncol)), blay=self.empty((kd.nbnd, nlay, ncol)),
-                       blev=self.empty((kd.nbnd, nlay+1, ncol)), sfc_src=self.empty((kd.ngpt, ncol)), sfc_src_jac=self.empty((kd.ngpt, ncol)))
+        out = self._planck_lite(kd, nlay, ncol) if out is None else out
         a = self._minor_args(kd, play)
         extra = () if by_band is None else (by_band,)
         self._c("gas_optics_lw_fractions" + ("" if by_band is None else "_allsky"), *a[:9], kd.nPlanckTemp, *a[9:16], kd.gpoint_bands, *a[16:],
@@ -433,12 +414,7 @@ class HipKernels:
         band_lims = kd.band_lims_gpt if band_lims is None else band_lims
         gpoint_bands = kd.gpoint_bands if gpoint_bands is None else gpoint_bands
         nbnd = band_lims.shape[0]
-        if out is None:
-            out = {k: self.empty((nbnd, nlay+1, ncol)) for k in ("bnd_flux_up", "bnd_flux_dn")}
-            if net:
-                out["bnd_flux_net"] = self.empty((nbnd, nlay+1, ncol))
-            if broadband:
-                out.update({k: self.empty((nlay+1, ncol)) for k in ("flux_up", "flux_dn")})
+        out = self._byband_out(out, ("up", "dn"), nbnd, nlay, ncol, net, broadband)
         self._c("lw_solver_noscat_fractions_byband", ncol, nlay, ngpt, nbnd, BoolArg(top_at_1), secants, weights, tau,
                 fr["pfrac"], fr["blay"], fr["blev"], gpoint_bands, band_lims, sfc_emis, fr["sfc_src"], inc_flux,
                 out["bnd_flux_up"], out["bnd_flux_dn"], out.get("bnd_flux_net"), out.get("flux_up"), out.get("flux_dn"))
@@ -475,25 +451,11 @@ class HipKernels:
         return dict(flux_up=flux_up, flux_dn=flux_dn)
 
     def lw_solver_noscat_rescaled(self, top_at_1, secants, weights, tau, ssa, g, lay_source, lev_source, sfc_emis, sfc_src,
-                                  inc_flux=None, do_broadband=False, do_jacobians=False, sfc_src_jac=None):
+                                  inc_flux=None, do_broadband=False, do_jacobians=False, sfc_src_jac=None, out=None):
         """No-scattering LW solve on rescaled optical depths with one correction sweep, general entry
         (rrx_lw_solver_noscat_rescaled): the arguments of lw_solver_noscat plus ssa, g (ngpt, nlay, ncol)."""
-        ngpt, nlay, ncol = tau.shape
-        out = {}
-        flux_up = flux_dn = up_loc = dn_loc = jac = None
-        if do_broadband:
-            up_loc = self.empty((nlay+1, ncol)); dn_loc = self.empty((nlay+1, ncol))
-            out.update(flux_up=up_loc, flux_dn=dn_loc)
-        else:
-            flux_up = self.empty((ngpt, nlay+1, ncol)); flux_dn = self.empty((ngpt, nlay+1, ncol))
-            out.update(flux_up=flux_up, flux_dn=flux_dn)
-        if do_jacobians:
-            jac = self.empty((ngpt, nlay+1, ncol))
-            out["flux_up_jac"] = jac
-        self._c("lw_solver_noscat_rescaled", ncol, nlay, ngpt, BoolArg(top_at_1), weights.shape[0], secants, weights,
-                tau, ssa, g, lay_source, lev_source, sfc_emis, sfc_src, inc_flux, flux_up, flux_dn,
-                BoolArg(do_broadband), up_loc, dn_loc, BoolArg(do_jacobians), sfc_src_jac, jac)
-        return out
+        return self._lw_noscat("lw_solver_noscat_rescaled", top_at_1, secants, weights, tau, (ssa, g), lay_source, lev_source, sfc_emis,
+                               sfc_src, inc_flux, do_broadband, do_jacobians, sfc_src_jac, out)
 
     def lw_solver_noscat_fractions_rescaled(self, top_at_1, kd, secants, weights, tau, fr, sfc_emis, cloud=None, inc_flux=None,
                                             flux_up=None, flux_dn=None, band_lims=None, gpoint_bands=None):
@@ -527,9 +489,7 @@ class HipKernels:
 
     def compute_planck_source(self, kd, it, tlay, tlev, tsfc, sfc_lay, out=None):
         nlay, ncol = tlay.shape
-        if out is None:
-            out = dict(sfc_src=self.empty((kd.ngpt, ncol)), lay_src=self.empty((kd.ngpt, nlay, ncol)),
-                       lev_src=self.empty((kd.ngpt, nlay+1, ncol)), sfc_src_jac=self.empty((kd.ngpt, ncol)))
+        out = self._planck_sources(kd, nlay, ncol) if out is None else out
         self._c("compute_planck_source", ncol, nlay, kd.nbnd, kd.ngpt, kd.nflav, kd.neta, kd.npres, kd.ntemp, kd.nPlanckTemp,
                 tlay, tlev, tsfc, sfc_lay, it["fmajor"], it["jeta"], it["tropo"], it["jtemp"], it["jpress"],
                 kd.gpoint_bands, kd.band_lims_gpt, kd.planck_frac, float(kd.temp_ref_min), float(kd.totplnk_delta),
@@ -718,9 +678,9 @@ class HipKernels:
         return out
 
     # ---- host-class helpers --------------------------------------------------------------------------
-    def get_col_dry(self, vmr_h2o, plev):
+    def get_col_dry(self, vmr_h2o, plev, out=None):
         nlay, ncol = vmr_h2o.shape
-        out = self.empty((nlay, ncol))
+        out = self.empty((nlay, ncol)) if out is None else out
         self._c("get_col_dry", ncol, nlay, vmr_h2o, plev, out)
         return out
 
@@ -756,9 +716,9 @@ class HipKernels:
             self._c("fill_gases", ncol, nlay, d1, d2, kd.ngas, i, vmr, v, col_gas, col_dry)
         return col_gas
 
-    def expand_and_transpose(self, band_lims, arr_in, ngpt):
+    def expand_and_transpose(self, band_lims, arr_in, ngpt, out=None):
         ncol, nbnd = arr_in.shape
-        out = self.empty((ngpt, ncol))
+        out = self.empty((ngpt, ncol)) if out is None else out
         self._c("expand_and_transpose", ncol, nbnd, band_lims, arr_in, out)
         return out
 
@@ -832,6 +792,17 @@ class HipKernels:
         nrest = int(np.prod(arr.shape[:-1])) if arr.dim() > 1 else 1
         out = self.empty(tuple(arr.shape[:-1]) + (ncol_sub,))
         self._c("subset_cols", ncol_full, nrest, col_s, ncol_sub, arr, out)
+        return out
+
+    def gather_cols(self, perm, src, out):
+        """out[..., i] = src[..., perm[i]] for every column of out; column-last tensors with the same leading shape, perm int32."""
+        nrest = int(np.prod(src.shape[:-1], dtype=np.int64)) if src.dim() > 1 else 1
+        self._c("gather_cols", int(out.shape[-1]), ctypes.c_ulonglong(nrest), perm, int(src.shape[-1]), src, out)
+        return out
+
+    def gather_lastdim(self, perm, src, out):
+        """out[i, :] = src[perm[i], :] for every row of out; column-first (ncol, n1) tensors, perm int32."""
+        self._c("gather_lastdim", int(src.shape[1]), int(out.shape[0]), perm, src, out)
         return out
 
     def sunlit_columns(self, mu0, order=None, pad_to=1, perm=None, count=None):

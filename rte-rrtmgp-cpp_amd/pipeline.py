@@ -11,13 +11,11 @@ Mirrors, call for call, what the reference's host classes do around the kernel l
 The backend is either HipKernels (product path, torch CUDA tensors) or, in tests only, a CPU checker from
 oracle/oracle_py.py (numpy). This module never imports the oracle.
 """
-import ctypes
+import contextlib
 import os
 import time
 
 import numpy as np
-
-from ._ffi import BoolArg
 
 # Gauss-Jacobi-5 quadrature, R. J. Hogan 2023 (values as in /root/reference/src/Rte_lw.cpp:140-152); (n_angles, point)
 MAX_GAUSS_PTS = 4
@@ -237,45 +235,77 @@ def _step_atmosphere_type():
     return _STEP_ATMOSPHERE
 
 
+# The LW solve of a resident step takes exactly one form. In order of precedence: name -> (the option that chooses it, the options it
+# admits beside that one, why it admits no others). ResidentSolver.resolve_options reads the rules from here and step() dispatches on
+# the name. The last two forms refuse nothing: whatever they could not serve has chosen a form above them.
+_LW_FORMS = {
+    "per_gpoint": ("do_broadband=False", {"n_gauss_angles > 1"}, "only the broadband LW solvers, fed by the Planck-lite chain, have that form"),
+    "rescaled": ("lw_rescaling=True", set(), "the rescaled LW solver has one broadband form with one fixed angle"),
+    "two_stream": ("lw_scattering=True", set(), "the two-stream LW solver has one broadband form without quadrature angles"),
+    "optimal": ("optimal_angles=True", {"jacobian=True"}, "optimal angles are one angle and have no by-band form"),
+    "byband": ("byband=True", set(), "no by-band Jacobians and no by-band form with several angles"),
+    "angles": ("n_gauss_angles > 1", {"jacobian=True"}, None),
+    "fractions": ("do_broadband=True", {"jacobian=True"}, None),
+}
+
+
 class ResidentSolver:
     """One full clear-sky LW+SW solve per ``step()`` with every buffer allocated once (what a host model keeps
     resident between radiation calls, cf. the cached subsets in /root/reference/src_test/Radiation_solver.cu:450-466).
     HIP backend only; used by bench.py and the full-size tests. ``stage_events`` (torch.cuda.Event pairs on the
-    launch stream) give per-stage device durations without synchronising inside the step."""
+    launch stream) give per-stage device durations without synchronising inside the step.
+
+    The options, beside do_broadband (fused broadband solvers; the LW sources are then formed inside the solver from Planck fractions
+    and band Planck functions, the "Planck-lite" chain) and overlap (the LW and SW chains on two streams):
+    cloud_luts: all-sky (BASELINE C5), (lw_lut, sw_lut) of cloud optics; clouds are added by band where the gas optics is stored,
+      delta-scaled in SW.
+    byband: the step also fills self.bnd_fluxes (lw_up/lw_dn/lw_net/sw_up/sw_dn/sw_dir/sw_net, (nbnd, nlev, ncol) each, the caller's
+      column order) from the fused solvers' by-band form; the seven broadband arrays come from the same solves.
+    jacobian: the step also fills self.lw_flux_up_jac (nlev, ncol, the caller's column order), the surface-temperature Jacobian of the
+      LW upward flux [W m-2 K-1] from the same fused solve; the seven broadband arrays stay bit for bit those without it.
+    n_gauss_angles: LW quadrature angles (1..4, Gauss-Jacobi-5 nodes); more than one takes the several-angle form of the fused solver
+      (lw_solver_noscat_fractions_angles), which has no by-band outputs.
+    optimal_angles: the one LW angle's secant is the k-distribution's optimal-angle fit of the column's total optical depth per
+      g-point (upstream's compute_optimal_angles / lw_Ds), formed inside the fused solver (lw_solver_noscat_fractions_optimal);
+      keep_secants: the step also fills self.lw_secants (ngpt, ncol of the step), the secants that solve used.
+    lw_scattering: the LW chain lets clouds scatter -- clear gas optics, LW cloud tau / ssa / g by band (cloud_optics_2str on the LW
+      table, not delta-scaled) and the fused two-stream solver (lw_solver_2stream_fractions); without cloud LUTs the same solver with
+      ssa = 0. One solve without quadrature angles.
+    lw_rescaling: the LW chain treats cloud scattering by rescaling -- the same inputs and the fused no-scattering solve on rescaled
+      optical depths with one correction sweep (lw_solver_noscat_fractions_rescaled); without cloud LUTs the same solver with ssa = 0.
+    cloud_fraction: McICA cloud sampling. (nlay, ncol) cloud fractions in the caller's column order; each step runs the
+      CLEAR gas optics and then rrx_mcica_increment_*, which gives every g-point its own sub-column and adds the band cloud properties
+      in the cloudy cells only. cloud_overlap: "max_ran", or "exp_ran" with overlap_param (nlay-1, ncol), the overlap parameter between
+      array layers l and l+1. The mask is redrawn every step from the current self.mcica_seed (a host advances it between calls;
+      domain 0 = LW, 1 = SW); a column's draws are keyed by mcica_col_offset + its index in the caller's order, so sorting, padding
+      and sharding do not change them. The fields stay attributes: replace or update them between steps.
+    mu0_lay / altitude / ref_altitude: mu0 by layer, the SW solver takes a cosine of the solar zenith angle per layer.
+      mu0_lay: (nlay, ncol) in the caller's column order, used as it is. altitude: (nlay, ncol) layer altitudes in metres, with
+      ref_altitude (ncol, default 0) the altitude at which atm.mu0 holds: every step forms mu0_lay on the device from the current
+      atm.mu0 by the spherical-geometry correction (zenith_angle_spherical_correction). The fields stay attributes: replace or update
+      them between steps. They are per-column fields (_COLUMN_FIELDS): sorted, padded and gathered to the sunlit columns with the
+      others. The sunlit list is made from atm.mu0 in either case; the LW chain does not see any of this.
+    sunlit, sort_columns: see __init__."""
 
     STAGES = ("lw_gas_optics", "lw_planck", "lw_solver", "lw_reduce", "sw_gas_optics", "sw_solver", "sw_reduce")
 
-    def __init__(self, be, kd_lw, kd_sw, atm, do_broadband=False, overlap=False, cloud_luts=None, sort_columns=None, byband=False,
-                 sunlit=False, jacobian=False, n_gauss_angles=1, optimal_angles=False, keep_secants=False, lw_scattering=False,
-                 lw_rescaling=False, cloud_fraction=None, cloud_overlap="max_ran", overlap_param=None, mcica_seed=0, mcica_col_offset=0,
-                 mu0_lay=None, altitude=None, ref_altitude=None, planet_radius=6.37123e6):
-        import torch
-        self.torch = torch
-        # mu0 by layer (DESIGN 4.13): the SW solver takes a cosine of the solar zenith angle per layer. mu0_lay: (nlay, ncol) in the
-        # caller's column order, used as it is. altitude: (nlay, ncol) layer altitudes in metres, with ref_altitude (ncol, default 0) the
-        # altitude at which atm.mu0 holds: every step forms mu0_lay on the device from the current atm.mu0 by the spherical-geometry
-        # correction (zenith_angle_spherical_correction). The fields stay attributes: replace or update them between steps. They are
-        # per-column fields (_COLUMN_FIELDS): sorted, padded and gathered to the sunlit columns with the others. The sunlit list is
-        # made from atm.mu0 in either case; the LW chain does not see any of this.
-        self.mu0_lay, self.altitude, self.ref_altitude, self.planet_radius = mu0_lay, altitude, ref_altitude, float(planet_radius)
+    @staticmethod
+    def resolve_options(atm, kd_lw, do_broadband=False, cloud_luts=None, byband=False, sunlit=False, jacobian=False, n_gauss_angles=1,
+                        optimal_angles=False, lw_scattering=False, lw_rescaling=False, cloud_fraction=None, cloud_overlap="max_ran",
+                        overlap_param=None, mu0_lay=None, altitude=None, ref_altitude=None):
+        """The option rules of ResidentSolver, in this one place: returns the name of the LW form (a key of _LW_FORMS) that the options
+        choose, or raises ValueError. Reads atm.nlay / atm.ncol and kd_lw.optimal_angle_fit; needs no backend and no device."""
         if mu0_lay is not None and altitude is not None:
             raise ValueError("ResidentSolver: mu0_lay and altitude are two ways to the same thing: give one")
         if ref_altitude is not None and altitude is None:
             raise ValueError("ResidentSolver: ref_altitude without altitude")
         for name, v, want in (("mu0_lay", mu0_lay, (atm.nlay, atm.ncol)), ("altitude", altitude, (atm.nlay, atm.ncol)),
-                              ("ref_altitude", ref_altitude, (atm.ncol,))):
+                              ("ref_altitude", ref_altitude, (atm.ncol,)), ("cloud_fraction", cloud_fraction, (atm.nlay, atm.ncol)),
+                              ("overlap_param", overlap_param, (atm.nlay-1, atm.ncol))):
             if v is not None and tuple(v.shape) != want:
                 raise ValueError(f"ResidentSolver: {name} {tuple(v.shape)} is not {want}")
         if altitude is not None and bool((altitude < (0. if ref_altitude is None else ref_altitude)).any()):
             raise ValueError("ResidentSolver: an altitude lies below its column's reference altitude")
-        # cloud_fraction: McICA cloud sampling (DESIGN 4.12). (nlay, ncol) cloud fractions in the caller's column order; each step runs
-        # the CLEAR gas optics and then rrx_mcica_increment_*, which gives every g-point its own sub-column and adds the band cloud
-        # properties in the cloudy cells only. cloud_overlap: "max_ran", or "exp_ran" with overlap_param (nlay-1, ncol), the overlap
-        # parameter between array layers l and l+1. The mask is redrawn every step from the current self.mcica_seed (a host advances it
-        # between calls; domain 0 = LW, 1 = SW); a column's draws are keyed by mcica_col_offset + its index in the caller's order, so
-        # sorting, padding and sharding do not change them. The fields stay attributes: replace or update them between steps.
-        self.cloud_fraction, self.overlap_param = cloud_fraction, overlap_param
-        self.mcica_seed, self.mcica_col_offset = int(mcica_seed), int(mcica_col_offset)
         if cloud_fraction is None:
             if overlap_param is not None:
                 raise ValueError("ResidentSolver: overlap_param without cloud_fraction")
@@ -286,68 +316,52 @@ class ResidentSolver:
                 raise ValueError(f"ResidentSolver: cloud_overlap = {cloud_overlap!r} is not 'max_ran' or 'exp_ran'")
             if (cloud_overlap == "exp_ran") != (overlap_param is not None):
                 raise ValueError("ResidentSolver: cloud_overlap='exp_ran' takes overlap_param (nlay-1, ncol), 'max_ran' takes none")
-            if tuple(cloud_fraction.shape) != (atm.nlay, atm.ncol):
-                raise ValueError(f"ResidentSolver: cloud_fraction {tuple(cloud_fraction.shape)} is not (nlay, ncol) = {(atm.nlay, atm.ncol)}")
-            if overlap_param is not None and tuple(overlap_param.shape) != (atm.nlay-1, atm.ncol):
-                raise ValueError(f"ResidentSolver: overlap_param {tuple(overlap_param.shape)} is not (nlay-1, ncol) = {(atm.nlay-1, atm.ncol)}")
             for flag, name in ((lw_scattering, "lw_scattering=True"), (lw_rescaling, "lw_rescaling=True"), (sunlit, "sunlit=True")):
                 if flag:
                     raise ValueError(f"ResidentSolver: cloud_fraction with {name} is not supported (the scattering LW solvers combine "
                                      "the band clouds themselves; the sunlit-only SW chain does not carry the column identities)")
-        # lw_rescaling: the LW chain treats cloud scattering by rescaling -- clear gas optics, LW cloud tau / ssa / g by band
-        # (cloud_optics_2str on the LW table, not delta-scaled) and the fused no-scattering solve on rescaled optical depths with one
-        # correction sweep (lw_solver_noscat_fractions_rescaled); without cloud LUTs the same solver with ssa = 0. One angle, broadband:
-        # no by-band form, no Jacobian, no several or optimal angles, and not together with lw_scattering.
-        self.lw_rescaling = bool(lw_rescaling)
-        if self.lw_rescaling:
-            for flag, name in ((lw_scattering, "lw_scattering=True"), (byband, "byband=True"), (jacobian, "jacobian=True"),
-                               (int(n_gauss_angles) > 1, "n_gauss_angles > 1"), (optimal_angles, "optimal_angles=True")):
-                if flag:
-                    raise ValueError(f"ResidentSolver: lw_rescaling=True with {name} is not supported (the rescaled LW solver has "
-                                     "one broadband form with one fixed angle)")
-        # lw_scattering: the LW chain lets clouds scatter -- clear gas optics, LW cloud tau / ssa / g by band (cloud_optics_2str on the LW
-        # table, not delta-scaled) and the fused two-stream solver (lw_solver_2stream_fractions); without cloud LUTs the same solver with
-        # ssa = 0. One solve without quadrature angles: no by-band form, no Jacobian, no several or optimal angles.
-        self.lw_scattering = bool(lw_scattering)
-        if self.lw_scattering:
-            for flag, name in ((byband, "byband=True"), (jacobian, "jacobian=True"), (int(n_gauss_angles) > 1, "n_gauss_angles > 1"),
-                               (optimal_angles, "optimal_angles=True")):
-                if flag:
-                    raise ValueError(f"ResidentSolver: lw_scattering=True with {name} is not supported (the two-stream LW solver has "
-                                     "one broadband form without quadrature angles)")
-        # byband: the step also fills self.bnd_fluxes (lw_up/lw_dn/lw_net/sw_up/sw_dn/sw_dir/sw_net, (nbnd, nlev, ncol) each, the
-        # caller's column order) from the fused solvers' by-band form; the seven broadband arrays come from the same solves
-        self.byband = bool(byband)
-        # jacobian: the step also fills self.lw_flux_up_jac (nlev, ncol, the caller's column order), the surface-temperature Jacobian
-        # of the LW upward flux [W m-2 K-1] from the same fused solve; the seven broadband arrays stay bit for bit those without it
-        self.jacobian = bool(jacobian)
-        # n_gauss_angles: LW quadrature angles (1..4, Gauss-Jacobi-5 nodes); more than one takes the several-angle form of the fused
-        # solver (lw_solver_noscat_fractions_angles), which has no by-band outputs
-        self.n_gauss_angles = int(n_gauss_angles)
-        if not 1 <= self.n_gauss_angles <= 4:
+        if not 1 <= int(n_gauss_angles) <= 4:
             raise ValueError(f"ResidentSolver: n_gauss_angles = {n_gauss_angles} is outside 1..4")
-        if self.n_gauss_angles > 1 and self.byband:
-            raise ValueError("ResidentSolver: byband=True with n_gauss_angles > 1 is not supported (no by-band form with several angles)")
-        if self.jacobian and self.byband:
-            raise ValueError("ResidentSolver: jacobian=True with byband=True is not supported (no by-band Jacobians)")
-        # optimal_angles: the one LW angle's secant is the k-distribution's optimal-angle fit of the column's total optical depth per
-        # g-point (upstream's compute_optimal_angles / lw_Ds), formed inside the fused solver (lw_solver_noscat_fractions_optimal);
-        # keep_secants: the step also fills self.lw_secants (ngpt, ncol of the step), the secants that solve used
-        self.optimal_angles = bool(optimal_angles)
+        given = [name for name, on in (("lw_rescaling=True", lw_rescaling), ("lw_scattering=True", lw_scattering),
+                                       ("optimal_angles=True", optimal_angles), ("byband=True", byband),
+                                       ("n_gauss_angles > 1", int(n_gauss_angles) > 1), ("jacobian=True", jacobian)) if on]
+        form = "per_gpoint" if not do_broadband else next((f for f, rule in _LW_FORMS.items() if rule[0] in given), "fractions")
+        chooser, admits, why = _LW_FORMS[form]
+        for name in given:
+            if name != chooser and name not in admits:
+                raise ValueError(f"ResidentSolver: {chooser} with {name} is not supported ({why})")
+        if form == "optimal" and getattr(kd_lw, "optimal_angle_fit", None) is None:
+            raise ValueError("ResidentSolver: optimal_angles=True needs a LW k-distribution with optimal_angle_fit")
+        return form
+
+    def __init__(self, be, kd_lw, kd_sw, atm, do_broadband=False, overlap=False, cloud_luts=None, sort_columns=None, byband=False,
+                 sunlit=False, jacobian=False, n_gauss_angles=1, optimal_angles=False, keep_secants=False, lw_scattering=False,
+                 lw_rescaling=False, cloud_fraction=None, cloud_overlap="max_ran", overlap_param=None, mcica_seed=0, mcica_col_offset=0,
+                 mu0_lay=None, altitude=None, ref_altitude=None, planet_radius=6.37123e6):
+        import torch
+        self.torch = torch
+        self.lw_form = self.resolve_options(
+            atm, kd_lw, do_broadband=do_broadband, cloud_luts=cloud_luts, byband=byband, sunlit=sunlit, jacobian=jacobian,
+            n_gauss_angles=n_gauss_angles, optimal_angles=optimal_angles, lw_scattering=lw_scattering, lw_rescaling=lw_rescaling,
+            cloud_fraction=cloud_fraction, cloud_overlap=cloud_overlap, overlap_param=overlap_param, mu0_lay=mu0_lay, altitude=altitude,
+            ref_altitude=ref_altitude)
+        self.be, self.kd_lw, self.kd_sw, self.atm = be, kd_lw, kd_sw, atm
+        self.do_broadband, self.cloud_luts = do_broadband, cloud_luts
+        self.lite = do_broadband                 # the Planck-lite chain feeds every broadband LW solver
+        self.g_zero = cloud_luts is None         # clear sky: g == 0 is neither written nor read
+        self.byband, self.jacobian, self.sunlit = bool(byband), bool(jacobian), bool(sunlit)
+        self.n_gauss_angles, self.optimal_angles = int(n_gauss_angles), bool(optimal_angles)
         self.keep_secants = bool(keep_secants) and self.optimal_angles
-        if self.optimal_angles:
-            if self.n_gauss_angles > 1:
-                raise ValueError("ResidentSolver: optimal_angles=True with n_gauss_angles > 1 is not supported (optimal angles are one angle)")
-            if self.byband:
-                raise ValueError("ResidentSolver: optimal_angles=True with byband=True is not supported (no by-band form with optimal angles)")
-            if getattr(kd_lw, "optimal_angle_fit", None) is None:
-                raise ValueError("ResidentSolver: optimal_angles=True needs a LW k-distribution with optimal_angle_fit")
-        # Column sorting. The windowed gas optics stages ONE box of LUT nodes per 256 neighbouring cells; columns
-        # that differ much in pressure (RFMIP-like sites, --col-spread) do not fit one box and fall back to the gather kernels
-        # (+40 % per step at +-35 % pressure spread). Columns are independent, so the step may process them in any order: sorted by
-        # surface pressure, neighbours are alike again. The inputs are gathered into sorted order at the top of the step and the seven
-        # broadband flux arrays scattered back at its end (0.5 ms per step at C4: ~30 gathers of (nlay, ncol) arrays). "auto" (default,
-        # or RRX_SORT_COLUMNS): decided once from the initial atmosphere -- on when the surface pressure varies by more than 20 % inside
+        self.lw_scattering, self.lw_rescaling = bool(lw_scattering), bool(lw_rescaling)
+        self.cloud_fraction, self.overlap_param = cloud_fraction, overlap_param
+        self.mcica_seed, self.mcica_col_offset = int(mcica_seed), int(mcica_col_offset)
+        self.mu0_lay, self.altitude, self.ref_altitude, self.planet_radius = mu0_lay, altitude, ref_altitude, float(planet_radius)
+        # Column sorting. The windowed gas optics stages ONE box of LUT nodes per 256 neighbouring cells; columns that differ much in
+        # pressure (RFMIP-like sites, --col-spread) do not fit one box and fall back to the gather kernels (+40 % per step at +-35 %
+        # pressure spread). Columns are independent, so the step may process them in any order: sorted by surface pressure, neighbours
+        # are alike again. The inputs are gathered into sorted order at the top of the step and the seven broadband flux arrays
+        # scattered back at its end (0.5 ms per step at C4: ~30 gathers of (nlay, ncol) arrays). "auto" (default, or
+        # RRX_SORT_COLUMNS): decided once from the initial atmosphere -- on when the surface pressure varies by more than 20 % inside
         # some 256-column block, about one cell of the LUT's pressure grid (ln p spacing 0.2): below that the boxes still fit and
         # sorting costs more than it brings (measured: +-5 % spread 15.1 ms unsorted, 15.6 sorted; +-35 %: 19.4 -> 16.0 ms).
         if sort_columns is None:
@@ -361,56 +375,40 @@ class ResidentSolver:
             else:
                 sort_columns = False
         self.sort_columns = bool(sort_columns) and str(sort_columns) != "0"
-        # Padding (round 4): the step runs on a multiple of 16 columns -- the rows of the (col, lay, gpt) intermediates then start on
-        # 128-B lines (16 385 columns cost 20 % more than 16 384 otherwise); the extra columns repeat the last one and are dropped
-        # when the fluxes go back to the caller's order. One gather index serves both (built once, not per step, and
-        # applied to an explicit list of per-column fields): refresh_column_order() rebuilds it when the host model's pressures
-        # have changed enough to matter.
-        pad = bool(int(os.environ.get("RRX_PAD_COLUMNS", "1"))) and atm.ncol > 16 and atm.ncol % 16 != 0
-        self.npad = (16 - atm.ncol % 16) if pad else 0
+        # Padding: the step runs on a multiple of 16 columns -- the rows of the (col, lay, gpt) intermediates then start on 128-B lines
+        # (16 385 columns cost 20 % more than 16 384 otherwise); the extra columns repeat the last one and are dropped when the fluxes
+        # go back to the caller's order. One gather index serves sorting and padding, built once and applied to an explicit list of
+        # per-column fields: refresh_column_order() rebuilds it when the host model's pressures have changed enough to matter.
+        pad16 = bool(int(os.environ.get("RRX_PAD_COLUMNS", "1"))) and atm.ncol > 16
+        self.npad = (16 - atm.ncol % 16) if (pad16 and atm.ncol % 16 != 0) else 0
         self.ncol_caller = atm.ncol
         self.perm = None
-        self.atm = atm
         if self.sort_columns or self.npad:
             self.refresh_column_order()
         # overlap: LW and SW chains are independent, so they can run on two HIP streams and share the chip (the gather-
         # bound gas-optics kernels of one chain fill in next to the HBM-bound solver of the other)
         self.overlap = overlap
         self.streams = [torch.cuda.Stream(device=be.device), torch.cuda.Stream(device=be.device)] if overlap else None
-        self.be, self.kd_lw, self.kd_sw, self.atm = be, kd_lw, kd_sw, atm
-        self.do_broadband = do_broadband
-        # all-sky (BASELINE C5): (lw_lut, sw_lut) of cloud optics; clouds are added by band after the gas optics, delta-scaled in SW
-        self.cloud_luts = cloud_luts
-        self.fuse_clouds = bool(int(os.environ.get("RRX_FUSE_CLOUDS", "1")))
-        self.g_zero = cloud_luts is None and bool(int(os.environ.get("RRX_G_ZERO", "1")))     # clear sky: g == 0 is neither written nor read
-        self.direct = bool(int(os.environ.get("RRX_DIRECT", "1")))     # interpolation state recomputed inside its consumers
-        # broadband mode: Planck fractions + band Planck functions, sources formed inside the LW solver ("Planck-lite" chain)
-        self.lite = self.direct and do_broadband and bool(int(os.environ.get("RRX_LITE", "1")))
-        if self.byband and not self.lite:
-            raise ValueError("ResidentSolver(byband=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
-        if self.jacobian and not self.lite:
-            raise ValueError("ResidentSolver(jacobian=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
-        if self.lw_rescaling and not self.lite:
-            raise ValueError("ResidentSolver(lw_rescaling=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
-        if self.lw_scattering and not self.lite:
-            raise ValueError("ResidentSolver(lw_scattering=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
-        if self.optimal_angles and not self.lite:
-            raise ValueError("ResidentSolver(optimal_angles=True) needs do_broadband=True and the Planck-lite chain (RRX_DIRECT, RRX_LITE)")
+
+        # ---- what a step owns -------------------------------------------------------------------------------------------------
         ncol, nlay = atm.ncol + self.npad, atm.nlay              # columns of a step (padded)
         ng_l, ng_s = kd_lw.ngpt, kd_sw.ngpt
         e = be.empty
         self.col_dry = e((nlay, ncol))
-        if self.lite:
+        self.col_dry2 = None                                     # the SW chain's own when overlapping (allocated by the first step)
+        # LW gas optics: optical depth and the sources as the form's solver takes them
+        if do_broadband:
             self.lw = dict(tau=e((ng_l, nlay, ncol)), pfrac=e((ng_l, nlay, ncol)), blay=e((kd_lw.nbnd, nlay, ncol)),
                            blev=e((kd_lw.nbnd, nlay+1, ncol)), sfc_src=e((ng_l, ncol)), sfc_src_jac=e((ng_l, ncol)))
         else:
             self.lw = dict(tau=e((ng_l, nlay, ncol)), lay_src=e((ng_l, nlay, ncol)), lev_src=e((ng_l, nlay+1, ncol)),
                            sfc_src=e((ng_l, ncol)), sfc_src_jac=e((ng_l, ncol)))
         self.sw = dict(tau=e((ng_s, nlay, ncol)), ssa=e((ng_s, nlay, ncol)), g=e((ng_s, nlay, ncol)))
-        if not do_broadband:
+        if not do_broadband:                                     # fluxes per g-point, summed by the reduce stage
             self.lw.update(gpt_up=e((ng_l, nlay+1, ncol)), gpt_dn=e((ng_l, nlay+1, ncol)))
             self.sw.update(gpt_up=e((ng_s, nlay+1, ncol)), gpt_dn=e((ng_s, nlay+1, ncol)), gpt_dir=e((ng_s, nlay+1, ncol)))
-        # packed broadband outputs: LW up/dn/net + SW up/dn/dir/net  (7, nlev, ncol) -> one all-gather
+        # packed broadband outputs: LW up/dn/net + SW up/dn/dir/net  (7, nlev, ncol) -> one all-gather; the *_sorted twins hold the
+        # step's own column order when that is not the caller's
         self.fluxes = e((7, nlay+1, atm.ncol))
         self.fluxes_sorted = e((7, nlay+1, ncol)) if self.perm is not None else None
         self.lw_flux_up_jac = e((nlay+1, atm.ncol)) if self.jacobian else None
@@ -424,15 +422,20 @@ class ResidentSolver:
                 self.bnd_lw_sorted = e((3, kd_lw.nbnd, nlay+1, ncol)); self.bnd_sw_sorted = e((4, kd_sw.nbnd, nlay+1, ncol))
             self.bnd_fluxes = dict(lw_up=self.bnd_lw[0], lw_dn=self.bnd_lw[1], lw_net=self.bnd_lw[2],
                                    sw_up=self.bnd_sw[0], sw_dn=self.bnd_sw[1], sw_dir=self.bnd_sw[2], sw_net=self.bnd_sw[3])
+        # the chains' flux targets, in the step's column order, as views made once (a step indexes them some twenty times, and
+        # making a tensor view each time is host work that shows in the 1.7 ms step at 2 048 columns)
+        own = self.perm is None
+        self._F = tuple(self.fluxes if own else self.fluxes_sorted)
+        self._BL = tuple(self.bnd_lw if own else self.bnd_lw_sorted) if self.byband else None
+        self._BS = tuple(self.bnd_sw if own else self.bnd_sw_sorted) if self.byband else None
         # sunlit-only SW: every step lists the columns with mu0 > 0 on the device (in the step's own column order), gathers the SW
         # inputs of those columns into the buffers below, runs the SW chain on that many columns (views of the full-size SW buffers)
         # and scatters the SW fluxes back with zeros in the night columns. The host needs the count to size the launches: it is
         # copied to pinned memory at the top of the step and waited for only once the LW chain has been enqueued. All columns
         # sunlit: the plain SW path, bit for bit.
-        self.sunlit = bool(sunlit)
         if self.sunlit:
             # (padded to a multiple of 16 like the plain step: at most ncol rounded up to 16, which the step's buffers hold)
-            self.sun_pad = 16 if (bool(int(os.environ.get("RRX_PAD_COLUMNS", "1"))) and atm.ncol > 16) else 1
+            self.sun_pad = 16 if pad16 else 1
             nmax = -(-atm.ncol // self.sun_pad) * self.sun_pad
             assert nmax <= ncol
             self.sun_perm = be.int_empty((nmax,))
@@ -457,8 +460,9 @@ class ResidentSolver:
         self.lw_secants = e((ng_l, ncol)) if self.keep_secants else None
         self.sfc_emis_gpt = e((ng_l, ncol)); self.alb_dir = e((ng_s, ncol)); self.alb_dif = e((ng_s, ncol))
         self.mu0_lay_step = e((nlay, ncol)) if self.altitude is not None else None      # the step's corrected cosines
-        self.events = None
-        self.col_dry2 = None
+        self.events = self._rec = None
+
+
 
     def enable_stage_events(self, nsteps):
         ev = self.torch.cuda.Event
@@ -502,7 +506,6 @@ class ResidentSolver:
 
     def _sunlit_atmosphere(self, n_out):
         """The SW inputs of the columns sun_perm[:n_out], gathered on the device into the resident buffers (views of n_out columns)."""
-        from .synthetic import Atmosphere
         be, a, perm = self.be, self._step_atmosphere(), self.sun_perm
         out = dict(a.__dict__)         # (fields the SW chain does not read stay as they are)
         out["ncol"] = n_out
@@ -511,22 +514,11 @@ class ResidentSolver:
             if v is None:                  # (a field of the solver's that the host has taken away since)
                 continue
             if self._COLUMN_FIELDS[k] < 0 or v.dim() == 1:        # column fastest: (..., ncol) or (ncol,)
-                o = self._cols(buf, n_out) if self._COLUMN_FIELDS[k] < 0 else buf[:n_out]
-                nrest = int(np.prod(v.shape[:-1], dtype=np.int64)) if v.dim() > 1 else 1
-                be._c("gather_cols", n_out, ctypes.c_ulonglong(nrest), perm, a.ncol, v, o)
+                out[k] = be.gather_cols(perm, v, self._cols(buf, n_out) if self._COLUMN_FIELDS[k] < 0 else buf[:n_out])
             else:                                                  # column slowest: (ncol, nbnd)
-                o = self._rows(buf, n_out)
-                be._c("gather_lastdim", int(v.shape[1]), n_out, perm, v, o)
-            out[k] = o
-        vmr = {}
-        for n, t in a.vmr.items():
-            if n in self.sun_vmr:
-                o = self._cols(self.sun_vmr[n], n_out)
-                be._c("gather_cols", n_out, ctypes.c_ulonglong(t.shape[0]), perm, a.ncol, t, o)
-                vmr[n] = o
-            else:
-                vmr[n] = t
-        out["vmr"] = vmr
+                out[k] = be.gather_lastdim(perm, v, self._rows(buf, n_out))
+        out["vmr"] = {n: (be.gather_cols(perm, t, self._cols(self.sun_vmr[n], n_out)) if n in self.sun_vmr else t)
+                      for n, t in a.vmr.items()}
         return type(a)(**out)
 
     def refresh_column_order(self):
@@ -545,7 +537,6 @@ class ResidentSolver:
 
     def _gathered_atmosphere(self):
         """The atmosphere with its columns in the order (and count) of self.perm."""
-        from .synthetic import Atmosphere
         a, perm = self._step_atmosphere(), self.perm
         out = {}
         for k, v in a.__dict__.items():
@@ -559,6 +550,17 @@ class ResidentSolver:
                 out[k] = v
         return type(a)(**out)
 
+    def _mark(self, stage, end=False):
+        if self._rec is not None:
+            self._rec[stage][1 if end else 0].record(self.torch.cuda.current_stream(self.be.device))   # the chain's stream when overlapping
+
+    def _chain_stream(self, ichain, main):
+        """The context a chain is enqueued in: its own stream, behind what main holds so far, when overlapping."""
+        if not self.overlap:
+            return contextlib.nullcontext()
+        self.streams[ichain].wait_stream(main)
+        return self.torch.cuda.stream(self.streams[ichain])
+
     def step(self):
         be, atm = self.be, self._step_atmosphere()
         perm = self.perm
@@ -566,210 +568,174 @@ class ResidentSolver:
             atm = self._gathered_atmosphere()
         if self.overlap and self.col_dry2 is None:
             self.col_dry2 = be.empty(tuple(self.col_dry.shape))
-        rec = None
+        self._rec = None
         if self.events is not None and self._istep < len(self.events):
-            rec = self.events[self._istep]
+            self._rec = self.events[self._istep]
             self._istep += 1
-
-        def mark(stage, end=False):
-            if rec is not None:
-                rec[stage][1 if end else 0].record(self.torch.cuda.current_stream(be.device))   # the chain's stream when overlapping
-
-        ncol, nlay = atm.ncol, atm.nlay
-        mcica = self.cloud_fraction is not None
-        if mcica:     # the sampled fields in the step's column order, and the identities that go with it
-            cfrac, alpha = self.cloud_fraction, self.overlap_param
-            col_id = None
+        mcica = None
+        if self.cloud_fraction is not None:     # the sampled fields in the step's column order, and the identities that go with it
+            cfrac, alpha, col_id = self.cloud_fraction, self.overlap_param, None
             if perm is not None:
                 cfrac = cfrac.index_select(1, perm)
                 alpha = None if alpha is None else alpha.index_select(1, perm)
                 col_id = self.perm_i32 + self.mcica_col_offset
-        F = self.fluxes if perm is None else self.fluxes_sorted
+            mcica = (cfrac, alpha, col_id)
+        F, BL, BS = self._F, self._BL, self._BS
         J = self.lw_flux_up_jac if perm is None else self.jac_sorted
-        BL = self.bnd_lw if perm is None else self.bnd_lw_sorted
-        BS = self.bnd_sw if perm is None else self.bnd_sw_sorted
         main = self.torch.cuda.current_stream(be.device)
-        sw_day = False                # this step's SW chain runs on the sunlit columns only
         if self.sunlit:               # the column list and its count, on the device; the count travels to pinned host memory
             n = self.ncol_caller
             be.sunlit_columns(self.atm.mu0, None if perm is None else self.perm_i32[:n], self.sun_pad, perm=self.sun_perm, count=self.sun_count)
             self.sun_count_host.copy_(self.sun_count, non_blocking=True)
             self.sun_event.record(main)
-        for ichain, (kind, kd, buf) in enumerate((("lw", self.kd_lw, self.lw), ("sw", self.kd_sw, self.sw))):
-            if self.overlap:
-                self.streams[ichain].wait_stream(main)
-                ctx = self.torch.cuda.stream(self.streams[ichain])
-                ctx.__enter__()
-            mark(kind + "_gas_optics")
-            col_dry = self.col_dry2 if (self.overlap and ichain == 1) else self.col_dry
-            if kind == "sw" and self.sunlit:
+        with self._chain_stream(0, main):
+            self._lw_chain(atm, self.col_dry, self.lw, F, J, BL, mcica)
+        sw_day = False                # this step's SW chain runs on the sunlit columns only
+        with self._chain_stream(1, main):
+            self._mark("sw_gas_optics")
+            col_dry = self.col_dry2 if self.overlap else self.col_dry
+            if self.sunlit:
                 t0 = time.perf_counter()
                 self.sun_event.synchronize()      # the LW chain is enqueued by now; the count was ready long before
                 self.sun_wait_ms += (time.perf_counter() - t0) * 1e3
                 n_day = int(self.sun_count_host[0])
                 sw_day = n_day < self.ncol_caller
-                if sw_day:
-                    n_out = -(-n_day // self.sun_pad) * self.sun_pad
-                    FS = [None, None, None] + list(self._cols(self.sun_fluxes, n_out))
-                    BSd = self._cols(self.sun_bnd, n_out) if self.byband else None
-                    if n_day == 0:                # all dark: no SW launches, only the zero fill
-                        mark("sw_gas_optics", True); mark("sw_solver"); mark("sw_solver", True); mark("sw_reduce")
-                        self._sunlit_scatter(0, 0, BSd)
-                        mark("sw_reduce", True)
-                        if self.overlap:
-                            ctx.__exit__(None, None, None)
-                        continue
-                    atm_full, ncol_full = atm, ncol
-                    atm, ncol = self._sunlit_atmosphere(n_out), n_out
-                    col_dry = self._cols(col_dry, n_out)
-                    buf = {k: self._cols(v, n_out) for k, v in buf.items()}
-                    alb_dir, alb_dif = self._cols(self.alb_dir, n_out), self._cols(self.alb_dif, n_out)
-                    F_full, BS_full = F, BS
-                    F, BS = FS, BSd
-            be._c("get_col_dry", ncol, nlay, atm.vmr["h2o"], atm.p_lev, col_dry)
-            col_gas = be.fill_gases(kd, atm.vmr, col_dry)
-            it = None if self.direct else be.interpolation(kd, atm.p_lay, atm.t_lay, col_gas)
-            # all-sky: the by-band cloud properties are computed first and added where the gas optics is stored (fused); with
-            # RRX_FUSE_CLOUDS=0 by the reference's separate increment kernels afterwards
-            fuse = self.cloud_luts is not None and self.direct and self.fuse_clouds and not mcica
-            if kind == "lw":
-                tc = cld_lw = None
-                if self.cloud_luts is not None and (self.lw_scattering or self.lw_rescaling):      # tau, ssa, g by band: the solver combines them itself
-                    cld_lw = be.cloud_optics_2str(self.cloud_luts[0], atm.lwp, atm.iwp, atm.rel, atm.dei)
-                elif self.cloud_luts is not None:     # /root/reference/src_test/Radiation_solver.cu:497-512
-                    tc = be.cloud_optics_1scl(self.cloud_luts[0], atm.lwp, atm.iwp, atm.rel, atm.dei)
-                if self.lite:
-                    be.gas_optics_lw_fractions(kd, atm.p_lay, atm.t_lay, atm.t_lev, atm.t_sfc, _sfc_lay(atm), col_gas, buf["tau"], out=buf,
-                                               by_band=tc if fuse else None)
-                elif self.direct:
-                    be.gas_optics_lw_direct(kd, atm.p_lay, atm.t_lay, col_gas, buf["tau"], by_band=tc if fuse else None)
-                else:
-                    be.compute_tau_absorption_set(kd, it, atm.p_lay, atm.t_lay, col_gas, buf["tau"])
-                if tc is not None and mcica:
-                    be.mcica_increment_1scalar(buf["tau"], tc, kd.band_lims_gpt, cfrac, alpha, self.mcica_seed, 0, col_id, self.mcica_col_offset)
-                elif tc is not None and not fuse:
-                    be.inc_1scalar_by_1scalar_bybnd(buf["tau"], tc, kd.band_lims_gpt)
-                mark("lw_gas_optics", True)
-                mark("lw_planck")
-                srcs = None if self.lite else dict(sfc_src=buf["sfc_src"], lay_src=buf["lay_src"], lev_src=buf["lev_src"], sfc_src_jac=buf["sfc_src_jac"])
-                if self.lite:
-                    pass                                   # the fractions came with the optical depths
-                elif self.direct:
-                    be.planck_source_direct(kd, atm.p_lay, atm.t_lay, atm.t_lev, atm.t_sfc, _sfc_lay(atm), col_gas, out=srcs)
-                else:
-                    be.compute_planck_source(kd, it, atm.t_lay, atm.t_lev, atm.t_sfc, _sfc_lay(atm), out=srcs)
-                mark("lw_planck", True)
-                mark("lw_solver")
-                if not (self.optimal_angles or self.lw_scattering):      # (neither solver reads a secants array)
-                    be._c("lw_secants_array", ncol, kd.ngpt, self.n_gauss_angles, MAX_GAUSS_PTS, self.gauss_Ds, self.secants)
-                be._c("expand_and_transpose", ncol, kd.nbnd, kd.band_lims_gpt, atm.emis_sfc, self.sfc_emis_gpt)
-                if self.lw_rescaling:
-                    be.lw_solver_noscat_fractions_rescaled(atm.top_at_1, kd, self.secants, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
-                                                           cloud=cld_lw, flux_up=F[0], flux_dn=F[1])
-                elif self.lw_scattering:
-                    be.lw_solver_2stream_fractions(atm.top_at_1, kd, buf["tau"], buf, self.sfc_emis_gpt, cloud=cld_lw,
-                                                   flux_up=F[0], flux_dn=F[1])
-                elif self.optimal_angles:
-                    be.lw_solver_noscat_fractions_optimal(atm.top_at_1, kd, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
-                                                          fit=self.optimal_fit, flux_up=F[0], flux_dn=F[1], flux_up_jac=J,
-                                                          jacobian=self.jacobian, secants_out=self.lw_secants)
-                elif self.byband:
-                    be.lw_solver_noscat_fractions_byband(atm.top_at_1, kd, self.secants, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
-                                                         out=dict(bnd_flux_up=BL[0], bnd_flux_dn=BL[1], bnd_flux_net=BL[2],
-                                                                  flux_up=F[0], flux_dn=F[1]))
-                elif self.lite and self.n_gauss_angles > 1:
-                    be.lw_solver_noscat_fractions_angles(atm.top_at_1, kd, self.secants, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
-                                                         flux_up=F[0], flux_dn=F[1], flux_up_jac=J, jacobian=self.jacobian)
-                elif self.jacobian:
-                    be.lw_solver_noscat_fractions_jac(atm.top_at_1, kd, self.secants, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
-                                                      flux_up=F[0], flux_dn=F[1], flux_up_jac=J)
-                elif self.lite:
-                    be.lw_solver_noscat_fractions(atm.top_at_1, kd, self.secants, self.weights, buf["tau"], buf, self.sfc_emis_gpt,
-                                                  flux_up=F[0], flux_dn=F[1])
-                elif self.do_broadband:
-                    be._c("lw_solver_noscat", ncol, nlay, kd.ngpt, BoolArg(atm.top_at_1), self.n_gauss_angles, self.secants, self.weights,
-                          buf["tau"], buf["lay_src"], buf["lev_src"], self.sfc_emis_gpt, buf["sfc_src"], None, None, None,
-                          BoolArg(True), F[0], F[1], BoolArg(False), None, None)
-                else:
-                    be.lw_solver_noscat_into(atm.top_at_1, self.secants, self.weights, buf["tau"], buf["lay_src"],
-                                             buf["lev_src"], self.sfc_emis_gpt, buf["sfc_src"], buf["gpt_up"], buf["gpt_dn"])
-                mark("lw_solver", True)
-                mark("lw_reduce")
-                if not self.do_broadband:
-                    be.sum_broadband(buf["gpt_up"], out=F[0]); be.sum_broadband(buf["gpt_dn"], out=F[1])
-                be.net_broadband_precalc(F[1], F[0], out=F[2])
-                mark("lw_reduce", True)
+            if sw_day:      # the gathered inputs, views of n_out columns of the SW buffers, the sunlit targets (no McICA: refused)
+                n_out = -(-n_day // self.sun_pad) * self.sun_pad
+                self._sw_chain(self._sunlit_atmosphere(n_out) if n_day else None, self._cols(col_dry, n_out),
+                               {k: self._cols(v, n_out) for k, v in self.sw.items()}, self._cols(self.alb_dir, n_out),
+                               self._cols(self.alb_dif, n_out), self._cols(self.sun_fluxes, n_out),
+                               self._cols(self.sun_bnd, n_out) if self.byband else None, None, n_day=n_day)
             else:
-                if not sw_day:
-                    alb_dir, alb_dif = self.alb_dir, self.alb_dif
-                # clear sky: the asymmetry parameter is identically zero; the fused broadband solver takes "no g" natively
-                gbuf = None if (self.g_zero and self.do_broadband) else buf["g"]
-                cld = None
-                if self.cloud_luts is not None:     # Radiation_solver.cu:773-792
-                    cld = be.cloud_optics_2str(self.cloud_luts[1], atm.lwp, atm.iwp, atm.rel, atm.dei, delta_scale=True)
-                if self.direct:
-                    be.gas_optics_sw_direct(kd, atm.p_lay, atm.t_lay, col_gas, col_dry, buf["tau"], buf["ssa"], gbuf, by_band=cld if fuse else None)
-                else:
-                    be.gas_optics_sw_fused(kd, it, atm.p_lay, atm.t_lay, col_gas, col_dry, buf["tau"], buf["ssa"], gbuf)
-                toa = be.toa_source(ncol, kd.solar_source, atm.tsi_scaling)     # spread_col + scaling_to_subset, one launch
-                if cld is not None and mcica:
-                    be.mcica_increment_2stream(buf["tau"], buf["ssa"], gbuf, *cld, kd.band_lims_gpt, cfrac, alpha, self.mcica_seed, 1, col_id,
-                                               self.mcica_col_offset)
-                elif cld is not None and not fuse:
-                    be.inc_2stream_by_2stream_bybnd(buf["tau"], buf["ssa"], gbuf, *cld, kd.band_lims_gpt)
-                mark("sw_gas_optics", True)
-                mark("sw_solver")
-                be._c("expand_and_transpose", ncol, kd.nbnd, kd.band_lims_gpt, atm.sfc_alb_dir, alb_dir)
-                be._c("expand_and_transpose", ncol, kd.nbnd, kd.band_lims_gpt, atm.sfc_alb_dif, alb_dif)
-                mu0_lay = getattr(atm, "mu0_lay", None)      # (a field of the step's view: None without mu0_lay= / altitude=)
-                if self.altitude is not None:     # the sun rises with altitude: this step's cosines from the current mu0
-                    mu0_lay = be.zenith_angle_spherical_correction(atm.mu0, atm.altitude, atm.ref_altitude, self.planet_radius,
-                                                                   out=self._cols(self.mu0_lay_step, ncol))
-                if mu0_lay is not None and self.byband:
-                    be.sw_solver_2stream_byband_mu0lay(atm.top_at_1, buf["tau"], buf["ssa"], gbuf, mu0_lay, alb_dir, alb_dif, toa,
-                                                       kd.band_lims_gpt, out=dict(bnd_flux_up=BS[0], bnd_flux_dn=BS[1], bnd_flux_dir=BS[2],
-                                                                                  bnd_flux_net=BS[3], flux_up=F[3], flux_dn=F[4], flux_dir=F[5]))
-                elif mu0_lay is not None:
-                    be.sw_solver_2stream_mu0lay(atm.top_at_1, buf["tau"], buf["ssa"], gbuf, mu0_lay, alb_dir, alb_dif, toa,
-                                                do_broadband=self.do_broadband,
-                                                out=dict(flux_up=F[3], flux_dn=F[4], flux_dir=F[5]) if self.do_broadband else
-                                                dict(flux_up=buf["gpt_up"], flux_dn=buf["gpt_dn"], flux_dir=buf["gpt_dir"]))
-                elif self.byband:
-                    be.sw_solver_2stream_byband(atm.top_at_1, buf["tau"], buf["ssa"], gbuf, atm.mu0, alb_dir, alb_dif, toa,
-                                                kd.band_lims_gpt, out=dict(bnd_flux_up=BS[0], bnd_flux_dn=BS[1], bnd_flux_dir=BS[2],
-                                                                           bnd_flux_net=BS[3], flux_up=F[3], flux_dn=F[4], flux_dir=F[5]))
-                elif self.do_broadband:
-                    be._c("sw_solver_2stream", ncol, nlay, kd.ngpt, BoolArg(atm.top_at_1), buf["tau"], buf["ssa"], gbuf, atm.mu0,
-                          alb_dir, alb_dif, toa, None, None, None, BoolArg(False), None,
-                          BoolArg(True), F[3], F[4], F[5])
-                else:
-                    be.sw_solver_2stream_into(atm.top_at_1, buf["tau"], buf["ssa"], gbuf, atm.mu0, alb_dir, alb_dif,
-                                              toa, buf["gpt_up"], buf["gpt_dn"], buf["gpt_dir"])
-                mark("sw_solver", True)
-                mark("sw_reduce")
-                if not self.do_broadband:
-                    be.sum_broadband(buf["gpt_up"], out=F[3]); be.sum_broadband(buf["gpt_dn"], out=F[4]); be.sum_broadband(buf["gpt_dir"], out=F[5])
-                be.net_broadband_precalc(F[4], F[3], out=F[6])
-                if sw_day:                        # back to the caller's columns, zeros in the night ones
-                    self._sunlit_scatter(n_day, ncol, BS)
-                    atm, ncol, F, BS = atm_full, ncol_full, F_full, BS_full
-                mark("sw_reduce", True)
-            if self.overlap:
-                ctx.__exit__(None, None, None)
+                self._sw_chain(atm, col_dry, self.sw, self.alb_dir, self.alb_dif, F[3:], BS, mcica)
         if self.overlap:
             main.wait_stream(self.streams[0]); main.wait_stream(self.streams[1])
         if perm is not None:                              # back to the caller's column order (padding columns dropped)
             n = self.ncol_caller
             nf = 3 if sw_day else 7                       # (a sunlit-only SW chain has written the caller's order already)
-            self.fluxes[:nf].index_copy_(2, perm[:n], F[:nf, :, :n])
-            F = self.fluxes
+            self.fluxes[:nf].index_copy_(2, perm[:n], self.fluxes_sorted[:nf, :, :n])
             if self.jacobian:
                 self.lw_flux_up_jac.index_copy_(1, perm[:n], J[:, :n])
             if self.byband:
-                self.bnd_lw.index_copy_(3, perm[:n], BL[..., :n])
+                self.bnd_lw.index_copy_(3, perm[:n], self.bnd_lw_sorted[..., :n])
                 if not sw_day:
-                    self.bnd_sw.index_copy_(3, perm[:n], BS[..., :n])
-        return F
+                    self.bnd_sw.index_copy_(3, perm[:n], self.bnd_sw_sorted[..., :n])
+        return self.fluxes
+
+    def _lw_chain(self, atm, col_dry, buf, F, J, BL, mcica):
+        """The LW launches of a step on atm's columns: gas optics into buf, the solve of self.lw_form, fluxes into F[0:3] (up, dn,
+        net) and, where the form has them, J (Jacobian) and BL (by band). mcica: None or (cloud fraction, overlap parameter,
+        column identities) in atm's column order."""
+        be, kd, mark = self.be, self.kd_lw, self._mark
+        form = self.lw_form
+        mark("lw_gas_optics")
+        be.get_col_dry(atm.vmr["h2o"], atm.p_lev, out=col_dry)
+        col_gas = be.fill_gases(kd, atm.vmr, col_dry)
+        tc = cld = None
+        if self.cloud_luts is not None and form in ("two_stream", "rescaled"):      # tau, ssa, g by band: the solver combines them itself
+            cld = be.cloud_optics_2str(self.cloud_luts[0], atm.lwp, atm.iwp, atm.rel, atm.dei)
+        elif self.cloud_luts is not None:     # /root/reference/src_test/Radiation_solver.cu:497-512
+            tc = be.cloud_optics_1scl(self.cloud_luts[0], atm.lwp, atm.iwp, atm.rel, atm.dei)
+        # all-sky: the by-band cloud optical depth is added where the gas optics is stored; McICA adds it afterwards, cell by cell
+        fused = tc if mcica is None else None
+        if form == "per_gpoint":
+            be.gas_optics_lw_direct(kd, atm.p_lay, atm.t_lay, col_gas, buf["tau"], by_band=fused)
+        else:
+            be.gas_optics_lw_fractions(kd, atm.p_lay, atm.t_lay, atm.t_lev, atm.t_sfc, _sfc_lay(atm), col_gas, buf["tau"], out=buf,
+                                       by_band=fused)
+        if tc is not None and mcica is not None:
+            be.mcica_increment_1scalar(buf["tau"], tc, kd.band_lims_gpt, mcica[0], mcica[1], self.mcica_seed, 0, mcica[2], self.mcica_col_offset)
+        mark("lw_gas_optics", True)
+        mark("lw_planck")
+        if form == "per_gpoint":                  # (the broadband forms got their fractions with the optical depths)
+            be.planck_source_direct(kd, atm.p_lay, atm.t_lay, atm.t_lev, atm.t_sfc, _sfc_lay(atm), col_gas, out=buf)
+        mark("lw_planck", True)
+        mark("lw_solver")
+        if form not in ("optimal", "two_stream"):      # (neither solver reads a secants array)
+            be.lw_secants_array(atm.ncol, kd.ngpt, self.n_gauss_angles, MAX_GAUSS_PTS, self.gauss_Ds, out=self.secants)
+        be.expand_and_transpose(kd.band_lims_gpt, atm.emis_sfc, kd.ngpt, out=self.sfc_emis_gpt)
+        top, sec, wts, tau, emis = atm.top_at_1, self.secants, self.weights, buf["tau"], self.sfc_emis_gpt
+        if form == "rescaled":
+            be.lw_solver_noscat_fractions_rescaled(top, kd, sec, wts, tau, buf, emis, cloud=cld, flux_up=F[0], flux_dn=F[1])
+        elif form == "two_stream":
+            be.lw_solver_2stream_fractions(top, kd, tau, buf, emis, cloud=cld, flux_up=F[0], flux_dn=F[1])
+        elif form == "optimal":
+            be.lw_solver_noscat_fractions_optimal(top, kd, wts, tau, buf, emis, fit=self.optimal_fit, flux_up=F[0], flux_dn=F[1],
+                                                  flux_up_jac=J, jacobian=self.jacobian, secants_out=self.lw_secants)
+        elif form == "byband":
+            be.lw_solver_noscat_fractions_byband(top, kd, sec, wts, tau, buf, emis,
+                                                 out=dict(bnd_flux_up=BL[0], bnd_flux_dn=BL[1], bnd_flux_net=BL[2], flux_up=F[0], flux_dn=F[1]))
+        elif form == "angles":
+            be.lw_solver_noscat_fractions_angles(top, kd, sec, wts, tau, buf, emis, flux_up=F[0], flux_dn=F[1], flux_up_jac=J,
+                                                 jacobian=self.jacobian)
+        elif form == "fractions" and self.jacobian:
+            be.lw_solver_noscat_fractions_jac(top, kd, sec, wts, tau, buf, emis, flux_up=F[0], flux_dn=F[1], flux_up_jac=J)
+        elif form == "fractions":
+            be.lw_solver_noscat_fractions(top, kd, sec, wts, tau, buf, emis, flux_up=F[0], flux_dn=F[1])
+        else:
+            be.lw_solver_noscat(top, sec, wts, tau, buf["lay_src"], buf["lev_src"], emis, buf["sfc_src"],
+                                out=dict(flux_up=buf["gpt_up"], flux_dn=buf["gpt_dn"]))
+        mark("lw_solver", True)
+        mark("lw_reduce")
+        if form == "per_gpoint":
+            be.sum_broadband(buf["gpt_up"], out=F[0]); be.sum_broadband(buf["gpt_dn"], out=F[1])
+        be.net_broadband_precalc(F[1], F[0], out=F[2])
+        mark("lw_reduce", True)
+
+    def _sw_chain(self, atm, col_dry, buf, alb_dir, alb_dif, F, BS, mcica, n_day=None):
+        """The SW launches of a step on atm's columns, after the caller's mark("sw_gas_optics"): gas optics into buf, the solve, fluxes
+        into F (up, dn, dir, net) and with byband into BS. mcica as in _lw_chain. n_day: atm holds the sunlit columns only (n_day of
+        them, padded), and F / BS are scattered to the caller's arrays with zeros in the night columns; 0 = all dark, atm is not read."""
+        be, kd, mark = self.be, self.kd_sw, self._mark
+        if n_day == 0:                # all dark: no SW launches, only the zero fill
+            mark("sw_gas_optics", True); mark("sw_solver"); mark("sw_solver", True); mark("sw_reduce")
+            self._sunlit_scatter(0, 0, BS)
+            mark("sw_reduce", True)
+            return
+        be.get_col_dry(atm.vmr["h2o"], atm.p_lev, out=col_dry)
+        col_gas = be.fill_gases(kd, atm.vmr, col_dry)
+        # clear sky: the asymmetry parameter is identically zero; the fused broadband solver takes "no g" natively
+        gbuf = None if (self.g_zero and self.do_broadband) else buf["g"]
+        cld = None
+        if self.cloud_luts is not None:     # Radiation_solver.cu:773-792
+            cld = be.cloud_optics_2str(self.cloud_luts[1], atm.lwp, atm.iwp, atm.rel, atm.dei, delta_scale=True)
+        # all-sky: the by-band cloud properties are added where the gas optics is stored; McICA adds them afterwards, cell by cell
+        be.gas_optics_sw_direct(kd, atm.p_lay, atm.t_lay, col_gas, col_dry, buf["tau"], buf["ssa"], gbuf, by_band=cld if mcica is None else None)
+        toa = be.toa_source(atm.ncol, kd.solar_source, atm.tsi_scaling)     # spread_col + scaling_to_subset, one launch
+        if cld is not None and mcica is not None:
+            be.mcica_increment_2stream(buf["tau"], buf["ssa"], gbuf, *cld, kd.band_lims_gpt, mcica[0], mcica[1], self.mcica_seed, 1, mcica[2],
+                                       self.mcica_col_offset)
+        mark("sw_gas_optics", True)
+        mark("sw_solver")
+        be.expand_and_transpose(kd.band_lims_gpt, atm.sfc_alb_dir, kd.ngpt, out=alb_dir)
+        be.expand_and_transpose(kd.band_lims_gpt, atm.sfc_alb_dif, kd.ngpt, out=alb_dif)
+        mu0_lay = getattr(atm, "mu0_lay", None)      # (a field of the step's view: None without mu0_lay= / altitude=)
+        if self.altitude is not None:     # the sun rises with altitude: this step's cosines from the current mu0
+            mu0_lay = be.zenith_angle_spherical_correction(atm.mu0, atm.altitude, atm.ref_altitude, self.planet_radius,
+                                                           out=self._cols(self.mu0_lay_step, atm.ncol))
+        if self.do_broadband:
+            out = dict(flux_up=F[0], flux_dn=F[1], flux_dir=F[2])
+        else:
+            out = dict(flux_up=buf["gpt_up"], flux_dn=buf["gpt_dn"], flux_dir=buf["gpt_dir"])
+        if self.byband:
+            out.update(bnd_flux_up=BS[0], bnd_flux_dn=BS[1], bnd_flux_dir=BS[2], bnd_flux_net=BS[3])
+        top, tau, ssa = atm.top_at_1, buf["tau"], buf["ssa"]
+        if mu0_lay is not None and self.byband:
+            be.sw_solver_2stream_byband_mu0lay(top, tau, ssa, gbuf, mu0_lay, alb_dir, alb_dif, toa, kd.band_lims_gpt, out=out)
+        elif mu0_lay is not None:
+            be.sw_solver_2stream_mu0lay(top, tau, ssa, gbuf, mu0_lay, alb_dir, alb_dif, toa, do_broadband=self.do_broadband, out=out)
+        elif self.byband:
+            be.sw_solver_2stream_byband(top, tau, ssa, gbuf, atm.mu0, alb_dir, alb_dif, toa, kd.band_lims_gpt, out=out)
+        else:
+            be.sw_solver_2stream(top, tau, ssa, gbuf, atm.mu0, alb_dir, alb_dif, toa, do_broadband=self.do_broadband, out=out)
+        mark("sw_solver", True)
+        mark("sw_reduce")
+        if not self.do_broadband:
+            be.sum_broadband(buf["gpt_up"], out=F[0]); be.sum_broadband(buf["gpt_dn"], out=F[1]); be.sum_broadband(buf["gpt_dir"], out=F[2])
+        be.net_broadband_precalc(F[1], F[0], out=F[3])
+        if n_day is not None:                 # back to the caller's columns, zeros in the night ones
+            self._sunlit_scatter(n_day, atm.ncol, BS)
+        mark("sw_reduce", True)
 
     def _sunlit_scatter(self, n_day, n_out, BSd):
         """SW fluxes of the sunlit columns (sun_fluxes, BSd: n_out columns in sun_perm order) into the caller's arrays, zeros elsewhere."""
@@ -777,3 +743,4 @@ class ResidentSolver:
         be.scatter_cols_fill(n_day, self.sun_perm, self._cols(self.sun_fluxes, n_out), self.fluxes[3:7])
         if self.byband:
             be.scatter_cols_fill(n_day, self.sun_perm, BSd, self.bnd_sw)
+
