@@ -230,6 +230,23 @@ namespace rrx
     // fp32: v_sqrt_f32 (1 ulp) without the library's scaling of denormal arguments
     __device__ __forceinline__ float sqrt_pos(const float x) { return __builtin_amdgcn_sqrtf(x); }
 
+    // sqrt(x) for x >= 0 where x = 0 occurs: the product of two Planck fractions, which a k-distribution may hold as exact zeros.
+    // sqrt_pos leaves the select for zero out (fp64: rsq(0) = inf, 0 * inf = NaN, and the whole column's broadband sums with it).
+    // Here the seed is capped at 2^511 = rsq(DBL_MIN), which no normal x reaches, so every normal x gives sqrt_pos's bits; x = 0 then
+    // runs through as g = 0 * 2^511 = 0, h = 2^510, r = 1/2, d = 0 and returns an exact 0 (a denormal x gives a finite value below
+    // 1e-154 of reduced accuracy). One v_min_f64 per level source; a select on the result (v_cmp_f64 + two v_cndmask) cost 0.5 % of
+    // the C4 step (profiles/lw_zero_fractions_bench.txt). fp32: v_sqrt_f32(0) = 0 as it is.
+    __device__ __forceinline__ double sqrt_nonneg(const double x)
+    {
+        const double y = __builtin_fmin(__builtin_amdgcn_rsq(x), 0x1p+511);
+        double g = x*y, h = 0.5*y;
+        const double r = fma(-h, g, 0.5);
+        g = fma(g, r, g); h = fma(h, r, h);
+        const double d = fma(-g, g, x);
+        return fma(d, h, g);
+    }
+    __device__ __forceinline__ float sqrt_nonneg(const float x) { return sqrt_pos(x); }
+
     // Workgroup index -> work item such that items handled by ONE XCD (its own L2) are consecutive. The dispatcher deals
     // workgroups round-robin over the eight XCDs (workgroup w runs on XCD w % 8), so neighbouring items of the natural order sit
     // behind eight different L2s; where neighbours share cache lines (a column group of 16 fp32 columns is half a 128-B line) every

@@ -533,8 +533,8 @@ lw_noscat_bb_kernel(
             const F bvv = lds_b[(K+j)*V+v][tid];
             // The first and the last level take the fraction of their one layer (gas_optics_rrtmgp_kernels.cu:260-306). No select for
             // that (round 4; rounds 2-3 spent four v_cndmask per level on it): the loads of the neighbouring layer are clamped into the
-            // column (lay_off), so there pa == pb and sqrt_pos(p*p) returns p -- the residual of its last Newton step is exact.
-            return sqrt_pos(pa*pb) * bvv;
+            // column (lay_off), so there pa == pb and sqrt_nonneg(p*p) returns p -- the residual of its last Newton step is exact.
+            return sqrt_nonneg(pa*pb) * bvv;
         }
     };
 

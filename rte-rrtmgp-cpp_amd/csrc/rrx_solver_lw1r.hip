@@ -235,10 +235,10 @@ lw_rescaled_bb_kernel(
     F cn[K];      // Cn  -> c = Cn An
 
     // ---- (a) layers: every one independent of the others. The first and the last level source take the fraction of their one
-    // layer: the neighbour's load is clamped into the column, so there pa == pb and sqrt_pos(p*p) returns p (lw_noscat_bb_kernel's note)
+    // layer: the neighbour's load is clamped into the column, so there pa == pb and sqrt_nonneg(p*p) returns p (lw_noscat_bb_kernel's note)
     const F D = n_D;
     F A = F(1.), Bdn = F(0.);
-    F lva = sqrt_pos(n_prev*np[0]) * lds_blev[0][tid];
+    F lva = sqrt_nonneg(n_prev*np[0]) * lds_blev[0][tid];
     #pragma unroll
     for (int j=0; j<K; ++j)
     {
@@ -260,7 +260,7 @@ lw_rescaled_bb_kernel(
         const F st = F(1.) - w + wb;
         cn[j] = F(.4) * wb * fast_rcp(max(st, F(3.)*Lim<F>::tiny()));
         const F pb = (j+1 == K) ? n_next : np[min(j+1, K-1)];
-        const F lvb = sqrt_pos(np[j]*pb) * lds_blev[j+1][tid];
+        const F lvb = sqrt_nonneg(np[j]*pb) * lds_blev[j+1][tid];
         const F lsj = np[j] * lds_blay[j][tid];
         const F tau_loc = tt * D * st;
         F trans;

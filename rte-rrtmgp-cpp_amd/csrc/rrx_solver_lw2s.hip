@@ -260,12 +260,12 @@ lw_2stream_bb_kernel(
     }
 
     // level source at sweep level t0+j. The first and the last level take the fraction of their one layer: the neighbour's load is
-    // clamped into the column, so there pa == pb and sqrt_pos(p*p) returns p (lw_noscat_bb_kernel's note)
+    // clamped into the column, so there pa == pb and sqrt_nonneg(p*p) returns p (lw_noscat_bb_kernel's note)
     auto level_src = [&](const int j) -> F
     {
         const F pa = (j == 0) ? n_prev : np[max(j-1, 0)];
         const F pb = (j == K) ? n_next : np[min(j, K-1)];
-        return sqrt_pos(pa*pb) * lds_blev[j][tid];
+        return sqrt_nonneg(pa*pb) * lds_blev[j][tid];
     };
 
     constexpr int EV = 2;
@@ -296,7 +296,7 @@ lw_2stream_bb_kernel(
         const F ssa = (ts > F(0.)) ? ts * fast_rcp(tt) : F(0.);
         F pb = (j+1 == K) ? n_next : np[min(j+1, K-1)];
         if (j >= EV) asm volatile("" : "+v"(pb) : "v"(qb[max(j-EV, 0)]));      // ... and their level sources
-        const F lvb = sqrt_pos(np[j]*pb) * lds_blev[j+1][tid];
+        const F lvb = sqrt_nonneg(np[j]*pb) * lds_blev[j+1][tid];
         const Lw2sLayer<F> L = lw_two_stream<F,ETAB>(tt, ssa, gc, lva, lvb, lds_etab);
         lva = lvb;
         rp[j] = L.r; al[j] = L.t; sb[j] = L.su; qb[j] = L.sd;
