@@ -1,0 +1,46 @@
+/* Raytracer_bw_gpu -- backward Monte Carlo ray tracer: shortwave radiances for a virtual camera or a flux sensor (rrx_raytracer_bw,
+ * DESIGN.md 4.15). A class of this project's own shape, the twin of Raytracer_gpu: it takes the clear g-point arrays and the band
+ * cloud triple as the gas and cloud optics write them. (The reference's Raytracer_bw::trace_rays_bw takes the structures of its _rt
+ * pipeline and a Camera of its own, which this project does not have: INTEGRATION.md.) */
+#ifndef RAYTRACER_BW_H
+#define RAYTRACER_BW_H
+#include "Array.h"
+#include "rrx_forward.h"
+
+// sensor_type 0 perspective, 1 fisheye, 2 orthographic, 3 flux sensor; npx x npy pixels; fov in radians (fisheye only); the image
+// axes e_w, e_h and the viewing direction e_d as include/rrx_hip.h describes them
+struct Sensor_bw
+{
+    int sensor_type = 0;
+    int npx = 0, npy = 0;
+    Float fov = Float(0.);
+    Float position[3] = {Float(0.), Float(0.), Float(0.)};
+    Float e_w[3] = {Float(1.), Float(0.), Float(0.)};
+    Float e_h[3] = {Float(0.), Float(1.), Float(0.)};
+    Float e_d[3] = {Float(0.), Float(0.), Float(-1.)};
+};
+
+class Raytracer_bw_gpu
+{
+    public:
+        Raytracer_bw_gpu() {}
+
+        // tau, ssa (ncol = nx ny, nz, ngpt); band_lims_gpt (2, nbnd); cld_* (ncol, nz, nbnd), all three of size 0 for a clear sky;
+        // sfc_albedo (ncol); inc_dir (ngpt) on the host; radiance (npx, npy) in W m-2 sr-1 is overwritten. Returns the number of rays
+        // dropped at max_events (0 in a healthy run); n_clamped, when given, receives the number of deposits clamped at 2^20.
+        unsigned long long trace_rays_bw(
+                const int nx, const int ny, const int nz,
+                const Float dx, const Float dy, const Float dz,
+                const bool top_at_1,
+                const Array_gpu<Float,3>& tau, const Array_gpu<Float,3>& ssa,
+                const Array_gpu<int,2>& band_lims_gpt,
+                const Array_gpu<Float,3>& cld_tau, const Array_gpu<Float,3>& cld_ssa, const Array_gpu<Float,3>& cld_g,
+                const Array_gpu<Float,1>& sfc_albedo,
+                const Float mu0, const Float azimuth,
+                const Array<Float,1>& inc_dir,
+                const int knx, const int kny, const int knz,
+                const Sensor_bw& sensor,
+                const long long rays_per_pixel, const unsigned long long seed, const int max_events,
+                Array_gpu<Float,2>& radiance, unsigned long long* n_clamped = nullptr);
+};
+#endif

@@ -650,7 +650,40 @@ int rrx_raytracer_sw##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool to
         const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
         F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
         long long photons_per_pixel, unsigned long long seed, int max_events, \
-        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, void* stream);
+        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, void* stream); \
+/* ---- Backward Monte Carlo ray tracer: radiances for a virtual camera or a flux sensor (csrc/rrx_raytracer_bw.hip). \
+   The scene arguments are those of the forward entries (no independent-column switch, no diffuse incident light), k_null is that \
+   of rrx_rt_k_null. Rays start at the sensor, travel against the light and are scored by local estimates of the direct beam at \
+   every surface hit and every scattering, with the EXACT transmission to the sun, walked cell by cell (the estimator, the draw \
+   order and the bound of the walk: the header of rrx_raytracer_bw.hip). \
+   The sensor: sensor_type 0 perspective, 1 fisheye, 2 orthographic, 3 flux sensor; npx x npy pixels (pixel = ipx + npx ipy); fov in \
+   radians (fisheye only: the full opening angle, in (0, 2 pi]); sensor: 12 numbers on the HOST, position (m; z upward from the \
+   surface), e_w, e_h, e_d. Perspective: direction normalize(e_w (2a-1) + e_h (2b-1) + e_d) from position, (a, b) in [0,1]^2 across \
+   the image. Fisheye: theta = a fov/2, phi = 2 pi b about e_d. Orthographic: direction e_d (unit, e_d.z < 0) from (a Lx, b Ly, top). \
+   Flux sensor: cosine-weighted, at the surface facing up (e_d.z > 0) or at the top facing down (e_d.z < 0); pi x the mean radiance \
+   is an irradiance. A position with z < 0 is refused; one above the top is moved along the ray to the top. \
+   rrx_rt_bw_trace_counts: traces the rays [ray0, ray0 + nrays) of g-point igpt (ray r belongs to pixel r mod (npx npy); \
+   Philox4x32-10 keyed by seed with counter (r low, r high, igpt | 0x80000000, block)) and ADDS into the caller-zeroed counts (npx npy), \
+   unsigned 64-bit in units of 2^-32: llrint(min(d, 2^20) 2^32) per deposit d; a clamped deposit is counted in n_clamped, a ray \
+   dropped after max_events events in n_capped (one device counter each, added into). Integer adds: independent of the order of \
+   arrival, additive over ray ranges. Radiance = counts 2^-32 / rays_per_pixel inc_dir/mu0, W m-2 sr-1. \
+   rrx_raytracer_bw: the spectral loop. Zeroes radiance (npx npy), n_capped and n_clamped, then for igpt = 0 .. ngpt-1 with \
+   inc_dir[igpt] > 0 (ngpt numbers on the HOST): zeroes counts in the stream's workspace, rrx_rt_k_null, rrx_rt_bw_trace_counts of \
+   rays_per_pixel npx npy rays from 0, rrx_rt_counts_to_flux with scale = inc_dir/(mu0 F(rays_per_pixel)): the same bits as that loop \
+   made by hand. An extent of 0 (nx, ny, nz, ngpt, npx, npy, nrays, rays_per_pixel): returns 0 without a launch; a negative extent, \
+   a NULL that is needed, a scene the forward entries refuse, a sensor_type outside 0..3, a sensor that is not finite, lies below \
+   the surface, has e_d = 0, is orthographic without a unit downward e_d or a flux sensor with e_d.z = 0, a fisheye fov outside \
+   (0, 2 pi]: non-zero, before any HIP call. */ \
+int rrx_rt_bw_trace_counts##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
+        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream); \
+int rrx_raytracer_bw##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
+        F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream);
 
 RRX_DECLARE(double, _f64)
 RRX_DECLARE(float, _f32)

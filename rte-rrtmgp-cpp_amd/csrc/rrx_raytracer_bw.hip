@@ -1,0 +1,481 @@
+// Backward Monte Carlo ray tracer: shortwave radiances for a virtual camera or a flux sensor. The counterpart of
+// the reference's ray_tracer_kernel_bw (src_kernels_cuda_rt/raytracer_kernels_bw.cu) on this project's arrays, with the medium, the
+// tracking and the scattering of the forward tracer (rrx_raytracer.hip) and one deliberate departure (T_sun below).
+//
+// THE ESTIMATOR. Rays start at the sensor and travel AGAINST the light, along u, through the medium of the forward tracer: per
+// g-point k_ext = (tau + tau_c)/dz, k_sca = (tau ssa + tau_c ssa_c)/dz, k_sca_cld = (tau_c ssa_c)/dz from the clear tau, ssa
+// (ncol, nz, ngpt) and the band cloud triple; null-collision tracking on the k_null grid with integer block indices (in, jn, kn);
+// f_no_abs = 1 - (k_ext - k_sca)/k_null; Russian roulette below weight 0.5; a Lambertian surface; periodic x / y; the same
+// scatter-or-null and species decisions and the same Rayleigh / Henyey-Greenstein sampling. No absorption tallies, no
+// independent-column switch. A ray is scored by LOCAL ESTIMATES OF THE DIRECT SOLAR BEAM, which travels along
+// s = (sin cos(azimuth), sin sin(azimuth), -mu0). A deposit d is made
+//   - at a surface hit: first weight *= albedo[pixel], then d = weight mu0/pi T_sun, before the roulette draw;
+//   - at a collision that scatters (after weight *= f_no_abs, the roulette, the scatter-or-null draw and the species draw, before
+//     the new direction is drawn): d = weight P(cos)/(4 pi) T_sun, cos = -(u.s) clamped to [-1, 1], Rayleigh P = 3/4 (1 + cos^2),
+//     cloud P = (1 - g^2)/(q sqrt(q)), q = 1 + g^2 - 2 g cos, g = min(g_c, 1 - eps): only + - x / and sqrt.
+// T_sun = exp(-tau_sun), tau_sun the EXACT optical path from the event's position to the domain top along -s, cell by cell through
+// the fine grid: the walk carries integer cell indices (i, j, k), wrapping in x / y by index, and the three distances to the next
+// face along each axis (a first distance that rounding made negative is 0), and steps one index at a time until k = nz. It draws
+// no random numbers and takes at most nz + ceil(H tan/dx) + ceil(H tan/dy) + 2 steps (H = nz dz, tan of the solar zenith angle);
+// a walk that exceeds this count (only a NaN among the inputs can do it) drops the ray into n_capped. The reference estimates this
+// transmission stochastically; here the shadow term has no variance. The sun's disk is not imaged, there is no diffuse incident
+// light.
+//
+// TALLY. One unsigned 64-bit count per camera pixel in units of 2^-32: llrint(min(d, 2^20) 2^32), added with an integer atomic; a
+// clamped deposit is counted in n_clamped; a ray alive after max_events events (collisions + crossings) is dropped and counted in
+// n_capped. Radiance of a g-point = counts 2^-32 / rays_per_pixel inc_dir/mu0 (W m-2 sr-1). Bit-reproducible, independent of the
+// order of arrival, additive over ray ranges.
+//
+// RANDOM NUMBERS. Philox4x32-10, key = seed, counter (ray low, ray high, igpt | 0x80000000, block). Ray r belongs to camera pixel
+// pix = r mod npix, ipx = pix mod npx, ipy = pix / npx. DRAW ORDER (tests/raytracer_bw_ref.py restates it):
+//   start:     u -> a = (ipx + u)/npx;  u -> b = (ipy + u)/npy;  sensor type 3 only: u -> mu = sqrt(u);  u -> phi = 2 pi u
+//   each event: u -> tau = -log(u), unless the previous event was a crossing between blocks
+//     surface:   weight *= albedo; deposit; weight < 0.5: u -> survives (weight = 1) iff u <= weight; survivor: u -> mu; u -> phi
+//     collision: weight *= f_no_abs; weight < 0.5: u -> roulette; survivor: u -> scatter or null; scatter: u -> species; deposit;
+//                u -> cos of the scattering angle; u -> phi
+//
+// SENSORS (12 host numbers: position, e_w, e_h, e_d; Lx = nx dx, Ly = ny dy, z_top = nz dz):
+//   0 perspective    direction normalize(e_w (2a-1) + e_h (2b-1) + e_d), from position
+//   1 fisheye        theta = a fov/2, phi = 2 pi b; direction normalize(e_d cos(theta) + sin(theta) (e_w cos(phi) + e_h sin(phi)))
+//   2 orthographic   direction e_d (unit, e_d.z < 0), from (a Lx, b Ly, z_top)
+//   3 flux sensor    cosine-weighted about +z from (a Lx, b Ly, 0) when e_d.z > 0, about -z from (a Lx, b Ly, z_top) when
+//                    e_d.z < 0: pi x the mean radiance is an irradiance
+// A start at or above the top with a downward direction is moved along the ray to the top; one that does not point downward ends
+// at once. x, y are wrapped into the domain and the block found by integer division and clamping.
+//
+// SHAPE. One ray per lane, lanes refill from a round-robin list inside the event loop, the grid is capped as in trace_kernel. The
+// sun walk is a STATE of that one loop, which has one back edge: in a pass a lane either traces one event or walks one cell to the
+// sun, so that one lane's long walk does not idle the other 63 behind an inner loop (measured both ways: DESIGN 4.15).
+#include "rrx_rt_common.h"
+#include "rrx_hip.h"
+
+namespace
+{
+using namespace rrx;
+using namespace rrx::rt;
+
+template<typename F>
+struct BwArgs
+{
+    int nx, ny, nz, nbnd, igpt, top_at_1;
+    const F* tau; const F* ssa; const int* band_lims_gpt; const F* cld_tau; const F* cld_ssa; const F* cld_g;
+    F dx, dy, dz;
+    const F* sfc_albedo;
+    F mu0, sun_x, sun_y, sun_z;
+    int knx, kny, knz;
+    const F* k_null;
+    unsigned k0, k1;
+    u64 ray0; long long nrays; int max_events, max_walk;
+    int type, npx, npy;
+    F fov, px, py, pz, wx, wy, wz, hx, hy, hz, ex, ey, ez;
+    u64* counts; u64* n_capped; u64* n_clamped;
+};
+
+// the state of a walk to the sun: cell indices, the distances along -s to the next face of each axis, the distance covered, the
+// optical path so far, the deposit's factor in front of T_sun, and what follows the deposit (0: the surface's roulette, 1: a
+// Rayleigh scattering, 2: a cloud scattering with asymmetry gc)
+template<typename F>
+struct Walk
+{
+    int i, j, k, steps, then;
+    F tx, ty, tz, t, tau, dep, gc;
+};
+
+template<typename F>
+__device__ __forceinline__ void begin_walk(Walk<F>& w, const BwArgs<F>& a, const F vx, const F vy, const F vz,
+                                           const F x, const F y, const F z, const int i, const int j, const int k,
+                                           const F dep, const int then, const F gc)
+{
+    const F inf = F(INFINITY);
+    w.i = i; w.j = j; w.k = k; w.steps = 0; w.then = then; w.t = F(0.); w.tau = F(0.); w.dep = dep; w.gc = gc;
+    w.tx = vx > F(0.) ? max(F(0.), (F(i+1)*a.dx - x)/vx) : (vx < F(0.) ? max(F(0.), (F(i)*a.dx - x)/vx) : inf);
+    w.ty = vy > F(0.) ? max(F(0.), (F(j+1)*a.dy - y)/vy) : (vy < F(0.) ? max(F(0.), (F(j)*a.dy - y)/vy) : inf);
+    w.tz = max(F(0.), (F(k+1)*a.dz - z)/vz);
+}
+
+// what follows the deposit of a surface hit: the roulette and the reflected direction; false: the ray ends
+template<typename F>
+__device__ __forceinline__ bool after_surface(Stream& rng, F& weight, F& ux, F& uy, F& uz)
+{
+    if (weight < F(0.5)) weight = (rng.next<F>() > weight) ? F(0.) : F(1.);
+    if (!(weight > F(0.))) return false;
+    lambert(rng, F(1.), ux, uy, uz);
+    return true;
+}
+
+template<typename F>
+__global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a)
+{
+    const long long nthreads = (long long)gridDim.x*blockDim.x;
+    long long next_ray = (long long)blockIdx.x*blockDim.x + threadIdx.x;
+
+    const int nx = a.nx, ny = a.ny, nz = a.nz;
+    const size_t ncol = size_t(nx)*ny;
+    const int rx = nx/a.knx, ry = ny/a.kny, rz = nz/a.knz;
+    const F kdx = F(rx)*a.dx, kdy = F(ry)*a.dy, kdz = F(rz)*a.dz;
+    const F len_x = F(a.knx)*kdx, len_y = F(a.kny)*kdy, z_top = F(a.knz)*kdz;
+    const int npix = a.npx*a.npy;
+    const int ibnd = a.cld_tau != nullptr ? band_of(a.igpt, a.nbnd, a.band_lims_gpt) : -1;
+    const F* __restrict__ tau_g = a.tau + ncol*nz*a.igpt;
+    const F* __restrict__ ssa_g = a.ssa + ncol*nz*a.igpt;
+    const F* __restrict__ ctau_b = ibnd >= 0 ? a.cld_tau + ncol*nz*ibnd : nullptr;
+    const F inf = F(INFINITY);
+    const F g_max = F(1.) - Lim<F>::eps();
+    const F pi = F(3.141592653589793);
+    // towards the sun, and the distance along it across one cell of each axis
+    const F vx = -a.sun_x, vy = -a.sun_y, vz = -a.sun_z;
+    const F dtx = vx != F(0.) ? a.dx/fabs(vx) : inf, dty = vy != F(0.) ? a.dy/fabs(vy) : inf, dtz = a.dz/vz;
+
+    Stream rng; rng.k0 = a.k0; rng.k1 = a.k1; rng.used = 4; rng.block = 0u; rng.c0 = rng.c1 = rng.c2 = 0u;
+    bool alive = false, pending = false, walking = false;
+    int in = 0, jn = 0, kn = 0, nev = 0, pix = 0;
+    F x = F(0.), y = F(0.), z = F(0.), ux = F(0.), uy = F(0.), uz = F(-1.), weight = F(0.), tau = F(0.);
+    Walk<F> w; w.i = w.j = w.k = w.steps = w.then = 0; w.tx = w.ty = w.tz = w.t = w.tau = w.dep = w.gc = F(0.);
+
+    // One loop with ONE back edge: in a pass a lane either walks one cell towards the sun or traces one event. The form matters:
+    // with the walk first and `continue` after it the compiler makes the walk an inner loop of the wave (the same instructions as a
+    // `do while` around it) and the tracking lanes wait for the longest walk; profiles/raytracer_bw_bench.txt has the times.
+    bool done = false;
+    for (;;)
+    {
+        if (walking)
+        {
+            // ---- one cell of the walk to the sun
+            const F tn = min(w.tz, min(w.tx, w.ty));
+            const int axis = (w.tz <= w.tx && w.tz <= w.ty) ? 2 : (w.tx <= w.ty ? 0 : 1);
+            const int lay = a.top_at_1 ? nz-1-w.k : w.k;
+            const size_t cell = size_t(w.i) + size_t(w.j)*nx + ncol*lay;
+            const F tc = ibnd >= 0 ? ctau_b[cell] : F(0.);
+            w.tau = w.tau + k_ext_of(tau_g[cell], tc, a.dz)*(tn - w.t);
+            w.t = tn;
+            if (axis == 0)
+            {
+                w.i = vx > F(0.) ? (w.i + 1 == nx ? 0 : w.i + 1) : (w.i == 0 ? nx - 1 : w.i - 1);
+                w.tx = w.tx + dtx;
+            }
+            else if (axis == 1)
+            {
+                w.j = vy > F(0.) ? (w.j + 1 == ny ? 0 : w.j + 1) : (w.j == 0 ? ny - 1 : w.j - 1);
+                w.ty = w.ty + dty;
+            }
+            else { ++w.k; w.tz = w.tz + dtz; }
+            ++w.steps;
+            if (w.k == nz)
+            {
+                const F d = w.dep*exp(-w.tau);
+                const bool clamped = d > F(1048576.);
+                if (clamped) atomicAdd(a.n_clamped, 1ull);
+                tally(a.counts, size_t(pix), to_count(clamped ? F(1048576.) : d));
+                walking = false;
+                if (w.then == 0) { alive = after_surface(rng, weight, ux, uy, uz); pending = false; }
+                else scatter_direction(rng, w.then == 2, w.gc, g_max, ux, uy, uz);
+            }
+            else if (w.steps >= a.max_walk) { atomicAdd(a.n_capped, 1ull); walking = false; alive = false; }
+        }
+        else
+        {
+            // one event of a tracking lane: a block that the lane leaves with `break` when the event is over (or, with done, when its
+            // list has run out)
+            do
+            {
+                if (!alive)
+                {
+                    if (next_ray >= a.nrays) { done = true; break; }          // the list is finite, every ray ends within max_events events and every walk is bounded
+                    const u64 r = a.ray0 + u64(next_ray);
+                    next_ray += nthreads;
+                    rng.start(r, unsigned(a.igpt) | 0x80000000u);
+                    pix = int(r % u64(npix));
+                    const int ipx = pix % a.npx, ipy = pix / a.npx;
+                    const F fa = (F(ipx) + rng.next<F>()) / F(a.npx);
+                    const F fb = (F(ipy) + rng.next<F>()) / F(a.npy);
+                    F sx = a.px, sy = a.py, sz = a.pz;
+                    if (a.type == 0 || a.type == 1)
+                    {
+                        F qx, qy, qz;
+                        if (a.type == 0)
+                        {
+                            const F ca = F(2.)*fa - F(1.), cb = F(2.)*fb - F(1.);
+                            qx = (a.wx*ca + a.hx*cb) + a.ex; qy = (a.wy*ca + a.hy*cb) + a.ey; qz = (a.wz*ca + a.hz*cb) + a.ez;
+                        }
+                        else
+                        {
+                            const F th = (fa*a.fov)*F(0.5), ph = F(6.283185307179586)*fb;
+                            const F ct = cos(th), st = sin(th), cp = cos(ph), sp = sin(ph);
+                            qx = a.ex*ct + st*(a.wx*cp + a.hx*sp); qy = a.ey*ct + st*(a.wy*cp + a.hy*sp); qz = a.ez*ct + st*(a.wz*cp + a.hz*sp);
+                        }
+                        const F nrm = sqrt((qx*qx + qy*qy) + qz*qz);
+                        ux = qx/nrm; uy = qy/nrm; uz = qz/nrm;
+                    }
+                    else
+                    {
+                        sx = fa*len_x; sy = fb*len_y;
+                        if (a.type == 2) { ux = a.ex; uy = a.ey; uz = a.ez; sz = z_top; }
+                        else if (a.ez > F(0.)) { lambert(rng, F(1.), ux, uy, uz); sz = F(0.); }
+                        else { lambert(rng, F(-1.), ux, uy, uz); sz = z_top; }
+                    }
+                    if (sz >= z_top)
+                    {
+                        if (!(uz < F(0.))) break;          // it looks away from the domain: the ray ends with nothing
+                        if (sz > z_top) { const F t = (z_top - sz)/uz; sx = sx + ux*t; sy = sy + uy*t; }
+                        sz = z_top;
+                    }
+                    sx = sx - floor(sx/len_x)*len_x; sy = sy - floor(sy/len_y)*len_y;
+                    in = clampi(int(sx/kdx), 0, a.knx - 1); jn = clampi(int(sy/kdy), 0, a.kny - 1); kn = clampi(int(sz/kdz), 0, a.knz - 1);
+                    x = clampf(sx, F(in)*kdx, F(in+1)*kdx); y = clampf(sy, F(jn)*kdy, F(jn+1)*kdy); z = clampf(sz, F(kn)*kdz, F(kn+1)*kdz);
+                    weight = F(1.); pending = false; nev = 0; alive = true;
+                }
+                if (nev >= a.max_events) { atomicAdd(a.n_capped, 1ull); alive = false; break; }
+                ++nev;
+
+                const F x_lo = F(in)*kdx, x_hi = F(in+1)*kdx, y_lo = F(jn)*kdy, y_hi = F(jn+1)*kdy, z_lo = F(kn)*kdz, z_hi = F(kn+1)*kdz;
+                const F sz = uz > F(0.) ? (z_hi - z)/uz : (uz < F(0.) ? (z_lo - z)/uz : inf);
+                const F sx = ux > F(0.) ? (x_hi - x)/ux : (ux < F(0.) ? (x_lo - x)/ux : inf);
+                const F sy = uy > F(0.) ? (y_hi - y)/uy : (uy < F(0.) ? (y_lo - y)/uy : inf);
+                const F d_max = min(sz, min(sx, sy));
+                const int axis = (sz <= sx && sz <= sy) ? 2 : (sx <= sy ? 0 : 1);
+                const F kn_val = a.k_null[in + a.knx*(jn + a.kny*kn)];
+                if (!pending) tau = -log(rng.next<F>());
+                pending = false;
+                const bool empty = !(kn_val > F(0.));
+                const F tau_cell = empty ? F(0.) : d_max*kn_val;
+
+                if (empty || tau >= tau_cell)
+                {
+                    // ---- the ray leaves the block through the face of `axis`
+                    if (!(d_max < inf)) { atomicAdd(a.n_capped, 1ull); alive = false; break; }
+                    tau = tau - tau_cell; pending = true;
+                    x = clampf(x + ux*d_max, x_lo, x_hi); y = clampf(y + uy*d_max, y_lo, y_hi); z = clampf(z + uz*d_max, z_lo, z_hi);
+                    if (axis == 0)
+                    {
+                        if (ux > F(0.)) { in = (in + 1 == a.knx) ? 0 : in + 1; x = F(in)*kdx; }
+                        else { in = (in == 0) ? a.knx - 1 : in - 1; x = F(in+1)*kdx; }
+                    }
+                    else if (axis == 1)
+                    {
+                        if (uy > F(0.)) { jn = (jn + 1 == a.kny) ? 0 : jn + 1; y = F(jn)*kdy; }
+                        else { jn = (jn == 0) ? a.kny - 1 : jn - 1; y = F(jn+1)*kdy; }
+                    }
+                    else if (uz > F(0.))
+                    {
+                        if (kn == a.knz - 1) alive = false;          // out through the domain top
+                        else { ++kn; z = F(kn)*kdz; }
+                    }
+                    else if (kn == 0)                 // the surface
+                    {
+                        z = F(0.);
+                        const int i = fine_cell(x, a.dx, in, rx), j = fine_cell(y, a.dy, jn, ry);
+                        weight = weight * a.sfc_albedo[i + nx*j];
+                        const F dep = (weight*a.mu0)/pi;
+                        if (dep > F(0.)) { begin_walk(w, a, vx, vy, vz, x, y, z, i, j, 0, dep, 0, F(0.)); walking = true; }
+                        else { alive = after_surface(rng, weight, ux, uy, uz); pending = false; }
+                    }
+                    else { --kn; z = F(kn+1)*kdz; }
+                }
+                else
+                {
+                    // ---- a collision inside the block
+                    const F dn = tau / kn_val;
+                    x = clampf(x + ux*dn, x_lo, x_hi); y = clampf(y + uy*dn, y_lo, y_hi); z = clampf(z + uz*dn, z_lo, z_hi);
+                    const int i = fine_cell(x, a.dx, in, rx), j = fine_cell(y, a.dy, jn, ry), k = fine_cell(z, a.dz, kn, rz);
+                    const int lay = a.top_at_1 ? nz-1-k : k;
+                    const size_t cell = size_t(i) + size_t(j)*nx + ncol*lay;
+                    const F t = tau_g[cell], w0 = ssa_g[cell];
+                    F tc = F(0.), wc = F(0.), gc = F(0.);
+                    if (ibnd >= 0)
+                    {
+                        const size_t cb = cell + ncol*nz*ibnd;
+                        tc = a.cld_tau[cb]; wc = a.cld_ssa[cb]; gc = a.cld_g[cb];
+                    }
+                    const F k_ext = k_ext_of(t, tc, a.dz);
+                    const F k_sca = (t*w0 + tc*wc) / a.dz;
+                    const F k_sca_cld = (tc*wc) / a.dz;
+                    const F f_no_abs = clampf(F(1.) - (k_ext - k_sca)/kn_val, F(0.), F(1.));
+                    weight = weight * f_no_abs;
+                    if (weight < F(0.5)) weight = (rng.next<F>() > weight) ? F(0.) : F(1.);
+                    if (!(weight > F(0.))) { alive = false; break; }
+                    if (rng.next<F>()*(k_sca + (kn_val - k_ext)) < k_sca)
+                    {
+                        const bool cloud = rng.next<F>()*k_sca < k_sca_cld;
+                        const F cs = clampf(-((ux*a.sun_x + uy*a.sun_y) + uz*a.sun_z), F(-1.), F(1.));
+                        F phase;
+                        if (cloud)
+                        {
+                            const F g = min(gc, g_max);
+                            const F q = (F(1.) + g*g) - (F(2.)*g)*cs;
+                            phase = (F(1.) - g*g) / (q*sqrt(q));
+                        }
+                        else phase = F(0.75)*(F(1.) + cs*cs);
+                        begin_walk(w, a, vx, vy, vz, x, y, z, i, j, k, (weight*phase)/(F(4.)*pi), cloud ? 2 : 1, gc);
+                        walking = true;
+                    }
+                }
+            } while (false);
+            if (done) break;
+        }
+    }
+}
+
+// ---- host side
+
+template<typename F>
+void check_sensor(const int type, const F fov, const F* s, const F dx, const F dy, const F dz, const int nx, const int ny, const int nz,
+                  const F mu0, int& max_walk)
+{
+    if (type < 0 || type > 3) throw std::runtime_error("sensor_type must be 0 (perspective), 1 (fisheye), 2 (orthographic) or 3 (flux sensor)");
+    for (int i=0; i<12; ++i)
+        if (!std::isfinite(double(s[i]))) throw std::runtime_error("sensor holds a number that is not finite");
+    const double ex = s[9], ey = s[10], ez = s[11];
+    const double len = std::sqrt(ex*ex + ey*ey + ez*ez);
+    if (type == 0 || type == 1)
+    {
+        if (!(len > 0.)) throw std::runtime_error("sensor e_d is zero");
+        if (s[2] < F(0.)) throw std::runtime_error("sensor position lies below the surface");
+    }
+    if (type == 1 && (!(fov > F(0.)) || double(fov) > 6.283185307179586 + 1e-6)) throw std::runtime_error("fov must be in (0, 2 pi] for a fisheye sensor");
+    if (type == 2 && (std::fabs(len - 1.) > 1.e-5 || !(ez < 0.))) throw std::runtime_error("sensor e_d must be a unit vector with e_d.z < 0 for an orthographic sensor");
+    if (type == 3 && ez == 0.) throw std::runtime_error("sensor e_d.z must be > 0 (at the surface, facing up) or < 0 (at the top, facing down) for a flux sensor");
+    // the bound of the walk to the sun: nz + ceil(H tan / dx) + ceil(H tan / dy) + 2
+    const double tn = std::sqrt(std::max(0., 1. - double(mu0)*double(mu0))) / double(mu0), height = double(nz)*double(dz);
+    const double bound = double(nz) + std::ceil(height*tn/double(dx)) + std::ceil(height*tn/double(dy)) + 2.;
+    if (!(bound < 2.0e9)) throw std::runtime_error("mu0 is too small for this domain: the walk to the sun would take more than 2e9 cells");
+    max_walk = int(bound);
+}
+
+template<typename F>
+void launch_trace_bw(BwArgs<F> a, const F mu0, const F azimuth, const int type, const int npx, const int npy, const F fov, const F* s,
+                     const u64 seed, hipStream_t st)
+{
+    const double st_ = std::sqrt(std::max(0.0, 1.0 - double(mu0)*double(mu0)));
+    a.mu0 = mu0; a.sun_x = F(st_*std::cos(double(azimuth))); a.sun_y = F(st_*std::sin(double(azimuth))); a.sun_z = -mu0;
+    a.k0 = unsigned(seed & 0xFFFFFFFFull); a.k1 = unsigned(seed >> 32);
+    a.type = type; a.npx = npx; a.npy = npy; a.fov = fov;
+    a.px = s[0]; a.py = s[1]; a.pz = s[2]; a.wx = s[3]; a.wy = s[4]; a.wz = s[5]; a.hx = s[6]; a.hy = s[7]; a.hz = s[8];
+    a.ex = s[9]; a.ey = s[10]; a.ez = s[11];
+    const int blocks = int(std::min<long long>((a.nrays + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
+    trace_bw_kernel<F><<<blocks, RT_BLOCK, 0, st>>>(a);
+}
+
+template<typename F>
+BwArgs<F> scene_args(int nx, int ny, int nz, int nbnd, int igpt, RrxBool top_at_1, const F* tau, const F* ssa, const int* band_lims_gpt,
+                     const F* cld_tau, const F* cld_ssa, const F* cld_g, F dx, F dy, F dz, const F* sfc_albedo,
+                     int knx, int kny, int knz, const F* k_null, u64 ray0, long long nrays, int max_events, int max_walk,
+                     u64* counts, u64* n_capped, u64* n_clamped)
+{
+    BwArgs<F> a{};
+    a.nx = nx; a.ny = ny; a.nz = nz; a.nbnd = nbnd; a.igpt = igpt; a.top_at_1 = top_at_1 ? 1 : 0;
+    a.tau = tau; a.ssa = ssa; a.band_lims_gpt = band_lims_gpt; a.cld_tau = cld_tau; a.cld_ssa = cld_ssa; a.cld_g = cld_g;
+    a.dx = dx; a.dy = dy; a.dz = dz; a.sfc_albedo = sfc_albedo; a.knx = knx; a.kny = kny; a.knz = knz; a.k_null = k_null;
+    a.ray0 = ray0; a.nrays = nrays; a.max_events = max_events; a.max_walk = max_walk;
+    a.counts = counts; a.n_capped = n_capped; a.n_clamped = n_clamped;
+    return a;
+}
+
+template<typename F>
+int trace_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1,
+                   const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
+                   F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null,
+                   int sensor_type, int npx, int npy, F fov, const F* sensor, u64 seed, long long ray0, long long nrays, int max_events,
+                   u64* counts, u64* n_capped, u64* n_clamped, void* stream)
+{
+    RRX_TRY
+    if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"npx", npx}, {"npy", npy}, {"nrays", nrays}})) return 0;
+    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
+    if (ray0 < 0) throw std::runtime_error("ray0 is negative");
+    check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"k_null", k_null}, {"sensor", sensor}, {"counts", counts},
+                  {"n_capped", n_capped}, {"n_clamped", n_clamped}});
+    check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
+    if (igpt < 0 || igpt >= ngpt) throw std::runtime_error("igpt is outside [0, ngpt)");
+    check_scene(dx, dy, dz, mu0);
+    if (max_events < 1) throw std::runtime_error("max_events must be >= 1");
+    check_grid(nx, ny, nz, knx, kny, knz);
+    if ((long long)npx*npy > 0x7FFFFFFFll) throw std::runtime_error("npx npy exceeds 2^31 - 1");
+    int max_walk = 0;
+    check_sensor(sensor_type, fov, sensor, dx, dy, dz, nx, ny, nz, mu0, max_walk);
+    BwArgs<F> a = scene_args<F>(nx, ny, nz, nbnd, igpt, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo,
+                                knx, kny, knz, k_null, u64(ray0), nrays, max_events, max_walk, counts, n_capped, n_clamped);
+    launch_trace_bw<F>(a, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, static_cast<hipStream_t>(stream));
+    RRX_CATCH(entry)
+}
+
+// the two small entries of the forward file that the spectral loop is made of, by precision
+inline int k_null_of(int nx, int ny, int nz, int ngpt, int nbnd, int g, RrxBool t, const double* tau, const int* lims, const double* ct,
+                     double dz, int knx, int kny, int knz, double* kn, void* st)
+{ return rrx_rt_k_null_f64(nx, ny, nz, ngpt, nbnd, g, t, tau, lims, ct, dz, knx, kny, knz, kn, st); }
+inline int k_null_of(int nx, int ny, int nz, int ngpt, int nbnd, int g, RrxBool t, const float* tau, const int* lims, const float* ct,
+                     float dz, int knx, int kny, int knz, float* kn, void* st)
+{ return rrx_rt_k_null_f32(nx, ny, nz, ngpt, nbnd, g, t, tau, lims, ct, dz, knx, kny, knz, kn, st); }
+inline int counts_to_flux_of(long long n, const u64* c, double scale, double* out, void* st) { return rrx_rt_counts_to_flux_f64(n, c, scale, out, st); }
+inline int counts_to_flux_of(long long n, const u64* c, float scale, float* out, void* st) { return rrx_rt_counts_to_flux_f32(n, c, scale, out, st); }
+
+template<typename F>
+int raytracer_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1,
+                       const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
+                       F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz,
+                       int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, u64 seed, int max_events,
+                       F* radiance, u64* n_capped, u64* n_clamped, void* stream)
+{
+    RRX_TRY
+    if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"npx", npx}, {"npy", npy}, {"rays_per_pixel", rays_per_pixel}})) return 0;
+    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
+    check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"inc_dir", inc_dir}, {"sensor", sensor}, {"radiance", radiance},
+                  {"n_capped", n_capped}, {"n_clamped", n_clamped}});
+    check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
+    check_scene(dx, dy, dz, mu0);
+    for (int g=0; g<ngpt; ++g)
+        if (inc_dir[g] < F(0.)) throw std::runtime_error("inc_dir must be >= 0");
+    if (max_events < 1) throw std::runtime_error("max_events must be >= 1");
+    check_grid(nx, ny, nz, knx, kny, knz);
+    if ((long long)npx*npy > 0x7FFFFFFFll) throw std::runtime_error("npx npy exceeds 2^31 - 1");
+    int max_walk = 0;
+    check_sensor(sensor_type, fov, sensor, dx, dy, dz, nx, ny, nz, mu0, max_walk);
+
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t npix = size_t(npx)*npy;
+    const size_t n_kn = (size_t(knx)*kny*knz*sizeof(F) + sizeof(u64) - 1) / sizeof(u64);
+    WorkspaceLease lease(st);
+    u64* counts = lease.get<u64>(npix + n_kn);
+    F* k_null = reinterpret_cast<F*>(counts + npix);
+    bool ok = hipMemsetAsync(n_capped, 0, sizeof(u64), st) == hipSuccess;
+    ok = ok && hipMemsetAsync(n_clamped, 0, sizeof(u64), st) == hipSuccess;
+    ok = ok && hipMemsetAsync(radiance, 0, npix*sizeof(F), st) == hipSuccess;
+    if (!ok) throw std::runtime_error("zeroing the outputs failed");
+    const long long nrays = rays_per_pixel*(long long)npix;
+    for (int g=0; g<ngpt; ++g)
+    {
+        if (!(inc_dir[g] > F(0.))) continue;
+        if (hipMemsetAsync(counts, 0, npix*sizeof(u64), st) != hipSuccess) throw std::runtime_error("zeroing the counts failed");
+        if (k_null_of(nx, ny, nz, ngpt, nbnd, g, top_at_1, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null, stream) != 0)
+            throw std::runtime_error(rrx_last_error());
+        BwArgs<F> a = scene_args<F>(nx, ny, nz, nbnd, g, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo,
+                                    knx, kny, knz, k_null, 0ull, nrays, max_events, max_walk, counts, n_capped, n_clamped);
+        launch_trace_bw<F>(a, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, st);
+        const F scale = inc_dir[g] / (mu0*F(rays_per_pixel));
+        if (counts_to_flux_of((long long)npix, counts, scale, radiance, stream) != 0) throw std::runtime_error(rrx_last_error());
+    }
+    RRX_CATCH(entry)
+}
+}  // namespace
+
+extern "C"
+{
+#define RRX_DEFINE_RT_BW(F, SFX) \
+int rrx_rt_bw_trace_counts##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
+        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream) \
+{ return trace_bw_entry<F>("rrx_rt_bw_trace_counts" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, \
+                           cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, knx, kny, knz, k_null, sensor_type, npx, npy, fov, sensor, seed, ray0, \
+                           nrays, max_events, counts, n_capped, n_clamped, stream); } \
+int rrx_raytracer_bw##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
+        F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream) \
+{ return raytracer_bw_entry<F>("rrx_raytracer_bw" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, \
+                               dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, \
+                               rays_per_pixel, seed, max_events, radiance, n_capped, n_clamped, stream); }
+
+RRX_DEFINE_RT_BW(double, _f64)
+RRX_DEFINE_RT_BW(float, _f32)
+}

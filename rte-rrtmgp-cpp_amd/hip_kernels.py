@@ -641,6 +641,48 @@ class HipKernels:
         out["n_capped"] = int(n_capped.item())
         return out
 
+    # Backward Monte Carlo ray tracer (rrx_rt_bw_trace_counts, rrx_raytracer_bw): the scene arguments of the forward
+    # tracer, k_null from rt_k_null, and a sensor (camera.Camera, or any object with type, npx, npy, fov, position, e_w, e_h, e_d).
+    def _rt_sensor(self, camera):
+        numbers = np.concatenate([np.asarray(v, dtype=np.float64).reshape(3) for v in (camera.position, camera.e_w, camera.e_h, camera.e_d)])
+        return (int(camera.type), int(camera.npx), int(camera.npy), float(camera.fov), np.ascontiguousarray(numbers.astype(self.np_dtype)))
+
+    def rt_bw_zero_counts(self, npix):
+        return {k: torch.zeros((n,), dtype=torch.int64, device=self.device) for k, n in (("counts", npix), ("n_capped", 1), ("n_clamped", 1))}
+
+    def rt_bw_trace_counts(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, kn_grid, k_null, camera, seed, ray0, nrays,
+                           top_at_1=False, cloud=None, band_lims=None, counts=None, max_events=None):
+        """Adds the rays [ray0, ray0 + nrays) of g-point igpt into counts (rt_bw_zero_counts; made when None): counts (npix,),
+        n_capped, n_clamped, int64 tensors holding unsigned 64-bit numbers."""
+        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        knx, kny, knz = (int(k) for k in kn_grid)
+        sensor = self._rt_sensor(camera)
+        counts = self.rt_bw_zero_counts(sensor[1]*sensor[2]) if counts is None else counts
+        self._c("rt_bw_trace_counts", *dims, int(igpt), BoolArg(top_at_1), tau, ssa, lims, ct, cw, cg, float(dx), float(dy), float(dz),
+                sfc_albedo, float(mu0), float(azimuth), knx, kny, knz, k_null, *sensor,
+                ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.c_longlong(int(ray0)), ctypes.c_longlong(int(nrays)),
+                int(self.RT_MAX_EVENTS if max_events is None else max_events), counts["counts"], counts["n_capped"], counts["n_clamped"])
+        return counts
+
+    def raytracer_bw(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
+                     top_at_1=False, cloud=None, band_lims=None, max_events=None):
+        """The spectral loop in one call. inc_dir: (ngpt,) numbers on the host. Returns radiance (npy, npx) in W m-2 sr-1, n_capped and
+        n_clamped (ints)."""
+        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        knx, kny, knz = (int(k) for k in kn_grid)
+        inc_dir = np.ascontiguousarray(np.asarray(inc_dir, dtype=self.np_dtype).reshape(-1))
+        if inc_dir.size != dims[3]:
+            raise ValueError("raytracer: inc_dir is (ngpt,)")
+        sensor = self._rt_sensor(camera)
+        radiance = self.empty((sensor[2], sensor[1]))
+        n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        n_clamped = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        self._c("raytracer_bw", *dims, BoolArg(top_at_1), tau, ssa, lims, ct, cw, cg, float(dx), float(dy), float(dz), sfc_albedo,
+                float(mu0), float(azimuth), inc_dir, knx, kny, knz, *sensor, ctypes.c_longlong(int(rays_per_pixel)),
+                ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), int(self.RT_MAX_EVENTS if max_events is None else max_events),
+                radiance, n_capped, n_clamped)
+        return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
+
     def delta_scale_2str_k(self, tau, ssa, g):
         ngpt, nlay, ncol = tau.shape
         self._c("delta_scale_2str_k", ncol, nlay, ngpt, tau, ssa, g)

@@ -8,6 +8,7 @@
 #include <string>
 #include "Radiation_solver.h"
 #include "Raytracer.h"
+#include "Raytracer_bw.h"
 #include "rrx_cxx_driver.h"
 
 namespace
@@ -222,6 +223,41 @@ int rrx_cxx_trace_rays(const int nx, const int ny, const int nz, const int ngpt,
                     view3(tau, ncol, nz, ngpt), view3(ssa, ncol, nz, ngpt), Array_gpu<int,2>(const_cast<int*>(band_lims_gpt), {2, nbnd}),
                     view3(cld_tau, ncol, nz, nbnd), view3(cld_ssa, ncol, nz, nbnd), view3(cld_g, ncol, nz, nbnd), view1(sfc_albedo, ncol),
                     mu0, azimuth, h_dir, h_dif, knx, kny, knz, photons_per_pixel, seed, max_events, o0, o1, o2, o3, o4, o5);
+        }
+        catch (...) { rrx_host::set_stream(before); throw; }
+        rrx_host::set_stream(before);
+    });
+}
+
+// Raytracer_bw_gpu::trace_rays_bw on device arrays the caller owns (views; needs no driver handle). The scene as for rrx_cxx_trace_rays;
+// inc_dir (ngpt) and sensor (12 numbers: position, e_w, e_h, e_d) on the HOST; radiance: a device array (npx, npy). Runs on `stream`
+// and waits for the counts of dropped rays and clamped deposits.
+int rrx_cxx_trace_rays_bw(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+        const int top_at_1, const Float* tau, const Float* ssa, const int* band_lims_gpt,
+        const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
+        const Float* inc_dir, const int knx, const int kny, const int knz, const int sensor_type, const int npx, const int npy, const Float fov,
+        const Float* sensor, const long long rays_per_pixel, const unsigned long long seed, const int max_events, Float* radiance,
+        unsigned long long* n_capped, unsigned long long* n_clamped, void* stream)
+{
+    return guarded([&]
+    {
+        void* const before = rrx_host::current_stream();
+        rrx_host::set_stream(stream);
+        try
+        {
+            const int ncol = nx*ny;
+            auto view3 = [](const Float* p, int a, int b, int c) { return p ? Array_gpu<Float,3>(const_cast<Float*>(p), {a, b, c}) : Array_gpu<Float,3>(); };
+            Array<Float,1> h_dir({ngpt});
+            for (int g=1; g<=ngpt; ++g) h_dir({g}) = inc_dir[g-1];
+            Sensor_bw s;
+            s.sensor_type = sensor_type; s.npx = npx; s.npy = npy; s.fov = fov;
+            for (int i=0; i<3; ++i) { s.position[i] = sensor[i]; s.e_w[i] = sensor[3+i]; s.e_h[i] = sensor[6+i]; s.e_d[i] = sensor[9+i]; }
+            Array_gpu<Float,2> out = view2(radiance, npx, npy);
+            Raytracer_bw_gpu raytracer;
+            *n_capped = raytracer.trace_rays_bw(nx, ny, nz, dx, dy, dz, top_at_1 != 0,
+                    view3(tau, ncol, nz, ngpt), view3(ssa, ncol, nz, ngpt), Array_gpu<int,2>(const_cast<int*>(band_lims_gpt), {2, nbnd}),
+                    view3(cld_tau, ncol, nz, nbnd), view3(cld_ssa, ncol, nz, nbnd), view3(cld_g, ncol, nz, nbnd), view1(sfc_albedo, ncol),
+                    mu0, azimuth, h_dir, knx, kny, knz, s, rays_per_pixel, seed, max_events, out, n_clamped);
         }
         catch (...) { rrx_host::set_stream(before); throw; }
         rrx_host::set_stream(before);

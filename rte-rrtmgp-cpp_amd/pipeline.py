@@ -193,17 +193,37 @@ def raytrace_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, photons_per_pixel, 
     nlay), default one block per cell. sfc_albedo (ncol,): default the atmosphere's, which must then be the same in every band and
     for direct and diffuse light (the tracer's surface is Lambertian with one broadband albedo per pixel).
     Returns sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up (ncol,) in W m-2, abs_dir, abs_dif (nlay, ncol) in W m-3 and n_capped."""
+    tau, ssa, cld, sfc_albedo, mu0, inc_dir, kn_grid = _raytracer_inputs("raytrace_sw", be, kd_sw, atm, nx, ny, cloud_lut, kn_grid, sfc_albedo)
+    return be.raytracer_sw(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, np.zeros_like(inc_dir), kn_grid,
+                           photons_per_pixel, seed, top_at_1=atm.top_at_1, independent_column=independent_column, cloud=cld,
+                           band_lims=kd_sw.band_lims_gpt, max_events=max_events)
+
+
+def render_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, camera, rays_per_pixel, seed, cloud_lut=None, kn_grid=None,
+              sfc_albedo=None, max_events=None):
+    """Shortwave radiances for a virtual camera or a flux sensor from the backward Monte Carlo ray tracer (rrx_raytracer_bw, DESIGN
+    4.15): the twin of raytrace_sw, on the same domain, sun, optics and albedo, with the same checks. camera: camera.perspective /
+    fisheye / orthographic / flux_sensor. Returns radiance (npy, npx) in W m-2 sr-1 (scattered and reflected sunlight; the sun's
+    disk is not imaged), n_capped and n_clamped."""
+    tau, ssa, cld, sfc_albedo, mu0, inc_dir, kn_grid = _raytracer_inputs("render_sw", be, kd_sw, atm, nx, ny, cloud_lut, kn_grid, sfc_albedo)
+    return be.raytracer_bw(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
+                           top_at_1=atm.top_at_1, cloud=cld, band_lims=kd_sw.band_lims_gpt, max_events=max_events)
+
+
+def _raytracer_inputs(who, be, kd_sw, atm, nx, ny, cloud_lut, kn_grid, sfc_albedo):
+    """What both ray tracers take from the chain: the clear g-point tau, ssa, the band cloud triple (or None), the albedo (ncol,),
+    the one mu0, inc_dir (ngpt,) on the host and the k_null grid; one sun and one albedo are checked."""
     ncol, nlay, ngpt = atm.ncol, atm.nlay, kd_sw.ngpt
     if ncol != nx*ny:
-        raise ValueError(f"raytrace_sw: ncol = {ncol} is not nx ny = {nx}*{ny}")
+        raise ValueError(f"{who}: ncol = {ncol} is not nx ny = {nx}*{ny}")
     mu0 = be.to_numpy(atm.mu0).reshape(-1)
     tsi = be.to_numpy(atm.tsi_scaling).reshape(-1)
     if np.any(mu0 != mu0[0]) or np.any(tsi != tsi[0]):
-        raise ValueError("raytrace_sw: mu0 and tsi_scaling must be the same in every column (one sun for the domain)")
+        raise ValueError(f"{who}: mu0 and tsi_scaling must be the same in every column (one sun for the domain)")
     if sfc_albedo is None:
         a_dir, a_dif = be.to_numpy(atm.sfc_alb_dir), be.to_numpy(atm.sfc_alb_dif)
         if np.any(a_dir != a_dif) or np.any(a_dif != a_dif[:, :1]):
-            raise ValueError("raytrace_sw: the atmosphere's albedo differs between bands or between direct and diffuse; pass sfc_albedo")
+            raise ValueError(f"{who}: the atmosphere's albedo differs between bands or between direct and diffuse; pass sfc_albedo")
         sfc_albedo = np.ascontiguousarray(a_dif[:, 0])
     sfc_albedo = be.asarray(sfc_albedo)
     kn_grid = (nx, ny, nlay) if kn_grid is None else tuple(int(k) for k in kn_grid)
@@ -216,9 +236,7 @@ def raytrace_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, photons_per_pixel, 
 
     F = be.np_dtype.type
     inc_dir = (be.to_numpy(kd_sw.solar_source).astype(be.np_dtype) * F(tsi[0])) * F(mu0[0])
-    return be.raytracer_sw(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, float(mu0[0]), azimuth, inc_dir, np.zeros_like(inc_dir), kn_grid,
-                           photons_per_pixel, seed, top_at_1=atm.top_at_1, independent_column=independent_column, cloud=cld,
-                           band_lims=kd_sw.band_lims_gpt, max_events=max_events)
+    return tau, ssa, cld, sfc_albedo, float(mu0[0]), inc_dir, kn_grid
 
 
 _STEP_ATMOSPHERE = None
