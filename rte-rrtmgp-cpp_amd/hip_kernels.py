@@ -12,7 +12,7 @@ import os
 import numpy as np
 import torch
 
-from ._ffi import Lib, BoolArg, PtrArg
+from ._ffi import Lib, PtrArg, HEADER_PATH
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "librrx_hip.so")
@@ -38,10 +38,10 @@ class HipKernels:
         self.sfx = "_f64" if self.np_dtype == np.float64 else "_f32"
         self.tdtype = torch.float64 if self.np_dtype == np.float64 else torch.float32
         self.device = torch.device(device)
-        cdll = load_library()
-        cdll.rrx_last_error.restype = ctypes.c_char_p
-        self.lib = Lib(LIB_PATH, self.np_dtype, by_ref=False, returns_status=True,
-                       error_fn=lambda: cdll.rrx_last_error().decode())
+        load_library()
+        # every call is checked against the entry's declaration in include/rrx_hip.h before it reaches the library (_ffi.py)
+        self.lib = Lib(LIB_PATH, self.np_dtype, returns_status=True, header=HEADER_PATH,
+                       error_fn=lambda: self.lib.call("rrx_last_error").decode())
         self.stream = stream          # torch.cuda.Stream or None (= torch current stream)
 
     # ---- memory helpers -------------------------------------------------------------------------
@@ -104,8 +104,8 @@ class HipKernels:
                 out["flux_up_jac"] = self.empty((ngpt, nlay+1, ncol))
         fl = (out["flux_up"], out["flux_dn"])
         per_gpt, loc = ((None, None), fl) if do_broadband else (fl, (None, None))
-        self._c(entry, ncol, nlay, ngpt, BoolArg(top_at_1), weights.shape[0], secants, weights, tau, *scat, lay_source, lev_source,
-                sfc_emis, sfc_src, inc_flux, *per_gpt, BoolArg(do_broadband), *loc, BoolArg(do_jacobians), sfc_src_jac,
+        self._c(entry, ncol, nlay, ngpt, top_at_1, weights.shape[0], secants, weights, tau, *scat, lay_source, lev_source,
+                sfc_emis, sfc_src, inc_flux, *per_gpt, do_broadband, *loc, do_jacobians, sfc_src_jac,
                 out.get("flux_up_jac"))
         return out
 
@@ -128,8 +128,8 @@ class HipKernels:
             out = {k: self.empty(shape) for k in ("flux_up", "flux_dn", "flux_dir")}
         fl = (out["flux_up"], out["flux_dn"], out["flux_dir"])
         per_gpt, loc = ((None, None, None), fl) if do_broadband else (fl, (None, None, None))
-        self._c(entry, ncol, nlay, ngpt, BoolArg(top_at_1), tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, *per_gpt,
-                BoolArg(inc_flux_dif is not None), inc_flux_dif, BoolArg(do_broadband), *loc)
+        self._c(entry, ncol, nlay, ngpt, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir, *per_gpt,
+                inc_flux_dif is not None, inc_flux_dif, do_broadband, *loc)
         return out
 
     def sw_solver_2stream(self, top_at_1, tau, ssa, g, mu0, sfc_alb_dir, sfc_alb_dif, inc_flux_dir,
@@ -160,8 +160,8 @@ class HipKernels:
         ngpt, nlay, ncol = tau.shape
         nbnd = band_lims.shape[0]
         out = self._byband_out(out, ("up", "dn", "dir"), nbnd, nlay, ncol, net, broadband)
-        self._c(entry, ncol, nlay, ngpt, nbnd, BoolArg(top_at_1), tau, ssa, g, mu0,
-                sfc_alb_dir, sfc_alb_dif, inc_flux_dir, BoolArg(inc_flux_dif is not None), inc_flux_dif, band_lims,
+        self._c(entry, ncol, nlay, ngpt, nbnd, top_at_1, tau, ssa, g, mu0,
+                sfc_alb_dir, sfc_alb_dif, inc_flux_dir, inc_flux_dif is not None, inc_flux_dif, band_lims,
                 out["bnd_flux_up"], out["bnd_flux_dn"], out["bnd_flux_dir"], out.get("bnd_flux_net"),
                 out.get("flux_up"), out.get("flux_dn"), out.get("flux_dir"))
         return out
@@ -202,7 +202,7 @@ class HipKernels:
             raise ValueError("ref_mu and ref_alt must be (ncol)")
         if out is None:
             out = self.empty((nlay, ncol))
-        self._c("zenith_angle_spherical_correction", ncol, nlay, ref_alt, ref_mu, alt, float(planet_radius), out)
+        self._c("zenith_angle_spherical_correction", ncol, nlay, ref_alt, ref_mu, alt, planet_radius, out)
         return out
 
     # ---- gas optics -------------------------------------------------------------------------------
@@ -215,10 +215,7 @@ class HipKernels:
             col_mix=self.empty((kd.nflav, nlay, ncol, 2)),
             fminor=self.empty((kd.nflav, nlay, ncol, 2, 2)),
             fmajor=self.empty((kd.nflav, nlay, ncol, 2, 2, 2)))
-        self._c("interpolation", ncol, nlay, kd.ngas, kd.nflav, kd.neta, kd.npres, kd.ntemp,
-                kd.flavor, kd.press_ref_log, kd.temp_ref,
-                float(kd.press_ref_log_delta), float(kd.temp_ref_min), float(kd.temp_ref_delta), float(kd.press_ref_trop_log),
-                kd.vmr_ref, play, tlay, col_gas,
+        self._c("interpolation", ncol, nlay, kd.ngas, kd.nflav, kd.neta, kd.npres, kd.ntemp, *self._direct_args(kd), play, tlay, col_gas,
                 r["jtemp"], r["fmajor"], r["fminor"], r["col_mix"], r["tropo"], r["jeta"], r["jpress"])
         return r
 
@@ -242,8 +239,8 @@ class HipKernels:
 
     # "direct" forms: interpolation state computed inside the consumer (no intermediate arrays)
     def _direct_args(self, kd):
-        return (kd.flavor, kd.press_ref_log, kd.temp_ref, float(kd.press_ref_log_delta), float(kd.temp_ref_min),
-                float(kd.temp_ref_delta), float(kd.press_ref_trop_log), kd.vmr_ref)
+        return (kd.flavor, kd.press_ref_log, kd.temp_ref, kd.press_ref_log_delta, kd.temp_ref_min, kd.temp_ref_delta, kd.press_ref_trop_log,
+                kd.vmr_ref)
 
     def _minor_args(self, kd, play):
         nlay, ncol = play.shape
@@ -287,7 +284,7 @@ class HipKernels:
         out = self._planck_sources(kd, nlay, ncol) if out is None else out
         self._c("planck_source_direct", ncol, nlay, kd.nbnd, kd.ngpt, kd.ngas, kd.nflav, kd.neta, kd.npres, kd.ntemp, kd.nPlanckTemp,
                 play, tlay, tlev, tsfc, sfc_lay, col_gas, *self._direct_args(kd),
-                kd.gpoint_bands, kd.band_lims_gpt, kd.planck_frac, float(kd.totplnk_delta), kd.totplnk, kd.gpoint_flavor,
+                kd.gpoint_bands, kd.band_lims_gpt, kd.planck_frac, kd.totplnk_delta, kd.totplnk, kd.gpoint_flavor,
                 out["sfc_src"], out["lay_src"], out["lev_src"], out["sfc_src_jac"])
         return out
 
@@ -297,7 +294,7 @@ class HipKernels:
         out = self._planck_lite(kd, nlay, ncol) if out is None else out
         self._c("planck_fractions", ncol, nlay, kd.nbnd, kd.ngpt, kd.ngas, kd.nflav, kd.neta, kd.npres, kd.ntemp, kd.nPlanckTemp,
                 play, tlay, tlev, tsfc, sfc_lay, col_gas, *self._direct_args(kd),
-                kd.gpoint_bands, kd.band_lims_gpt, kd.planck_frac, float(kd.totplnk_delta), kd.totplnk, kd.gpoint_flavor,
+                kd.gpoint_bands, kd.band_lims_gpt, kd.planck_frac, kd.totplnk_delta, kd.totplnk, kd.gpoint_flavor,
                 out["pfrac"], out["blay"], out["blev"], out["sfc_src"], out["sfc_src_jac"])
         return out
 
@@ -308,7 +305,7 @@ class HipKernels:
         a = self._minor_args(kd, play)
         extra = () if by_band is None else (by_band,)
         self._c("gas_optics_lw_fractions" + ("" if by_band is None else "_allsky"), *a[:9], kd.nPlanckTemp, *a[9:16], kd.gpoint_bands, *a[16:],
-                *self._direct_args(kd), play, tlay, tlev, tsfc, sfc_lay, col_gas, kd.planck_frac, float(kd.totplnk_delta), kd.totplnk,
+                *self._direct_args(kd), play, tlay, tlev, tsfc, sfc_lay, col_gas, kd.planck_frac, kd.totplnk_delta, kd.totplnk,
                 tau, out["pfrac"], out["blay"], out["blev"], out["sfc_src"], out["sfc_src_jac"], *extra)
         return out
 
@@ -323,7 +320,7 @@ class HipKernels:
         ngpt, nlay, ncol = tau.shape
         flux_up = self.empty((nlay+1, ncol)) if flux_up is None else flux_up
         flux_dn = self.empty((nlay+1, ncol)) if flux_dn is None else flux_dn
-        self._c("lw_solver_noscat_fractions", ncol, nlay, ngpt, BoolArg(top_at_1), secants, weights, tau,
+        self._c("lw_solver_noscat_fractions", ncol, nlay, ngpt, top_at_1, secants, weights, tau,
                 fr["pfrac"], fr["blay"], fr["blev"], kd.gpoint_bands, sfc_emis, fr["sfc_src"], inc_flux, flux_up, flux_dn)
         return dict(flux_up=flux_up, flux_dn=flux_dn)
 
@@ -336,7 +333,7 @@ class HipKernels:
         flux_up = self.empty((nlay+1, ncol)) if flux_up is None else flux_up
         flux_dn = self.empty((nlay+1, ncol)) if flux_dn is None else flux_dn
         flux_up_jac = self.empty((nlay+1, ncol)) if flux_up_jac is None else flux_up_jac
-        self._c("lw_solver_noscat_fractions_jac", ncol, nlay, ngpt, BoolArg(top_at_1), secants, weights, tau,
+        self._c("lw_solver_noscat_fractions_jac", ncol, nlay, ngpt, top_at_1, secants, weights, tau,
                 fr["pfrac"], fr["blay"], fr["blev"], kd.gpoint_bands, sfc_emis, fr["sfc_src"], inc_flux, flux_up, flux_dn,
                 fr["sfc_src_jac"], flux_up_jac)
         return dict(flux_up=flux_up, flux_dn=flux_dn, flux_up_jac=flux_up_jac)
@@ -355,7 +352,7 @@ class HipKernels:
         out = dict(flux_up=flux_up, flux_dn=flux_dn)
         if jacobian:
             out["flux_up_jac"] = self.empty((nlay+1, ncol)) if flux_up_jac is None else flux_up_jac
-        self._c("lw_solver_noscat_fractions_angles", ncol, nlay, ngpt, BoolArg(top_at_1), nmus, secants, weights, tau,
+        self._c("lw_solver_noscat_fractions_angles", ncol, nlay, ngpt, top_at_1, nmus, secants, weights, tau,
                 fr["pfrac"], fr["blay"], fr["blev"], kd.gpoint_bands, sfc_emis, fr["sfc_src"], inc_flux, flux_up, flux_dn,
                 fr["sfc_src_jac"] if jacobian else None, out.get("flux_up_jac"))
         return out
@@ -373,7 +370,7 @@ class HipKernels:
         ngpt, nlay, ncol = tau.shape
         fit = self.optimal_fit_abi(kd) if fit is None else fit
         secants = self.empty((ngpt, ncol)) if secants is None else secants
-        self._c("lw_optimal_secants", ncol, nlay, ngpt, int(fit.shape[0]), kd.gpoint_bands, fit, tau, secants)
+        self._c("lw_optimal_secants", ncol, nlay, ngpt, fit.shape[0], kd.gpoint_bands, fit, tau, secants)
         return secants
 
     def lw_solver_noscat_fractions_optimal(self, top_at_1, kd, weights, tau, fr, sfc_emis, fit=None, inc_flux=None, flux_up=None,
@@ -394,7 +391,7 @@ class HipKernels:
             secants_out = self.empty((ngpt, ncol))
         if secants_out is not None:
             out["secants"] = secants_out
-        self._c("lw_solver_noscat_fractions_optimal", ncol, nlay, ngpt, int(fit.shape[0]), BoolArg(top_at_1), weights, tau,
+        self._c("lw_solver_noscat_fractions_optimal", ncol, nlay, ngpt, fit.shape[0], top_at_1, weights, tau,
                 fr["pfrac"], fr["blay"], fr["blev"], kd.gpoint_bands, fit, sfc_emis, fr["sfc_src"], inc_flux, flux_up, flux_dn,
                 fr["sfc_src_jac"] if jacobian else None, out.get("flux_up_jac"), secants_out)
         return out
@@ -415,7 +412,7 @@ class HipKernels:
         gpoint_bands = kd.gpoint_bands if gpoint_bands is None else gpoint_bands
         nbnd = band_lims.shape[0]
         out = self._byband_out(out, ("up", "dn"), nbnd, nlay, ncol, net, broadband)
-        self._c("lw_solver_noscat_fractions_byband", ncol, nlay, ngpt, nbnd, BoolArg(top_at_1), secants, weights, tau,
+        self._c("lw_solver_noscat_fractions_byband", ncol, nlay, ngpt, nbnd, top_at_1, secants, weights, tau,
                 fr["pfrac"], fr["blay"], fr["blev"], gpoint_bands, band_lims, sfc_emis, fr["sfc_src"], inc_flux,
                 out["bnd_flux_up"], out["bnd_flux_dn"], out.get("bnd_flux_net"), out.get("flux_up"), out.get("flux_dn"))
         return out
@@ -431,8 +428,8 @@ class HipKernels:
         flux_dn = self.empty(shape) if flux_dn is None else flux_dn
         gpt = (None, None) if do_broadband else (flux_up, flux_dn)
         loc = (flux_up, flux_dn) if do_broadband else (None, None)
-        self._c("lw_solver_2stream", ncol, nlay, ngpt, BoolArg(top_at_1), tau, ssa, g, lev_source, sfc_emis, sfc_src, inc_flux,
-                *gpt, BoolArg(do_broadband), *loc)
+        self._c("lw_solver_2stream", ncol, nlay, ngpt, top_at_1, tau, ssa, g, lev_source, sfc_emis, sfc_src, inc_flux, *gpt, do_broadband,
+                *loc)
         return dict(flux_up=flux_up, flux_dn=flux_dn)
 
     def lw_solver_2stream_fractions(self, top_at_1, kd, tau, fr, sfc_emis, cloud=None, inc_flux=None, flux_up=None, flux_dn=None,
@@ -446,7 +443,7 @@ class HipKernels:
         flux_up = self.empty((nlay+1, ncol)) if flux_up is None else flux_up
         flux_dn = self.empty((nlay+1, ncol)) if flux_dn is None else flux_dn
         ct, cw, cg = (None, None, None) if cloud is None else cloud
-        self._c("lw_solver_2stream_fractions", ncol, nlay, ngpt, int(band_lims.shape[0]), BoolArg(top_at_1), tau, fr["pfrac"], fr["blev"],
+        self._c("lw_solver_2stream_fractions", ncol, nlay, ngpt, band_lims.shape[0], top_at_1, tau, fr["pfrac"], fr["blev"],
                 gpoint_bands, band_lims, ct, cw, cg, sfc_emis, fr["sfc_src"], inc_flux, flux_up, flux_dn)
         return dict(flux_up=flux_up, flux_dn=flux_dn)
 
@@ -468,7 +465,7 @@ class HipKernels:
         flux_up = self.empty((nlay+1, ncol)) if flux_up is None else flux_up
         flux_dn = self.empty((nlay+1, ncol)) if flux_dn is None else flux_dn
         ct, cw, cg = (None, None, None) if cloud is None else cloud
-        self._c("lw_solver_noscat_fractions_rescaled", ncol, nlay, ngpt, int(band_lims.shape[0]), BoolArg(top_at_1), secants, weights,
+        self._c("lw_solver_noscat_fractions_rescaled", ncol, nlay, ngpt, band_lims.shape[0], top_at_1, secants, weights,
                 tau, fr["pfrac"], fr["blay"], fr["blev"], gpoint_bands, band_lims, ct, cw, cg, sfc_emis, fr["sfc_src"], inc_flux,
                 flux_up, flux_dn)
         return dict(flux_up=flux_up, flux_dn=flux_dn)
@@ -492,7 +489,7 @@ class HipKernels:
         out = self._planck_sources(kd, nlay, ncol) if out is None else out
         self._c("compute_planck_source", ncol, nlay, kd.nbnd, kd.ngpt, kd.nflav, kd.neta, kd.npres, kd.ntemp, kd.nPlanckTemp,
                 tlay, tlev, tsfc, sfc_lay, it["fmajor"], it["jeta"], it["tropo"], it["jtemp"], it["jpress"],
-                kd.gpoint_bands, kd.band_lims_gpt, kd.planck_frac, float(kd.temp_ref_min), float(kd.totplnk_delta),
+                kd.gpoint_bands, kd.band_lims_gpt, kd.planck_frac, kd.temp_ref_min, kd.totplnk_delta,
                 kd.totplnk, kd.gpoint_flavor, out["sfc_src"], out["lay_src"], out["lev_src"], out["sfc_src_jac"])
         return out
 
@@ -500,11 +497,11 @@ class HipKernels:
     def apply_BC(self, nlay, top_at_1, flux_dn, inc_flux=None, factor=None):
         ngpt, nlev, ncol = flux_dn.shape
         if inc_flux is None:
-            self._c("apply_BC_0", ncol, nlay, ngpt, BoolArg(top_at_1), flux_dn)
+            self._c("apply_BC_0", ncol, nlay, ngpt, top_at_1, flux_dn)
         elif factor is None:
-            self._c("apply_BC_gpt", ncol, nlay, ngpt, BoolArg(top_at_1), inc_flux, flux_dn)
+            self._c("apply_BC_gpt", ncol, nlay, ngpt, top_at_1, inc_flux, flux_dn)
         else:
-            self._c("apply_BC_factor", ncol, nlay, ngpt, BoolArg(top_at_1), inc_flux, factor, flux_dn)
+            self._c("apply_BC_factor", ncol, nlay, ngpt, top_at_1, inc_flux, factor, flux_dn)
         return flux_dn
 
     def reorder123x321(self, arr_in):
@@ -549,27 +546,27 @@ class HipKernels:
             mask = torch.empty((ngpt, nlay, ncol), dtype=torch.uint8, device=self.device)
         elif mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (ngpt, nlay, ncol)):
             raise TypeError("mcica: mask is a uint8 tensor (ngpt, nlay, ncol)")
-        head = (cloud_frac, alpha, ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), int(domain), col_id, int(col_id0))
+        head = (cloud_frac, alpha, int(seed) & 0xFFFFFFFFFFFFFFFF, domain, col_id, col_id0)
         return head, mask
 
     def mcica_increment_1scalar(self, tau, cld_tau, band_lims, cloud_frac, alpha=None, seed=0, domain=0, col_id=None, col_id0=0, mask=None):
         ngpt, nlay, ncol = tau.shape
         head, mask = self._mcica_args(cloud_frac, alpha, seed, domain, col_id, col_id0, ngpt, mask)
-        self._c("mcica_increment_1scalar", ncol, nlay, ngpt, int(band_lims.shape[0]), band_lims, *head, tau, cld_tau, mask)
+        self._c("mcica_increment_1scalar", ncol, nlay, ngpt, band_lims.shape[0], band_lims, *head, tau, cld_tau, mask)
         return mask
 
     def mcica_increment_2stream(self, tau, ssa, g, cld_tau, cld_ssa, cld_g, band_lims, cloud_frac, alpha=None, seed=0, domain=0,
                                 col_id=None, col_id0=0, mask=None):
         ngpt, nlay, ncol = tau.shape
         head, mask = self._mcica_args(cloud_frac, alpha, seed, domain, col_id, col_id0, ngpt, mask)
-        self._c("mcica_increment_2stream", ncol, nlay, ngpt, int(band_lims.shape[0]), band_lims, *head, tau, ssa, g,
+        self._c("mcica_increment_2stream", ncol, nlay, ngpt, band_lims.shape[0], band_lims, *head, tau, ssa, g,
                 cld_tau, cld_ssa, cld_g, mask)
         return mask
 
     def mcica_cloud_mask(self, ngpt, cloud_frac, alpha=None, seed=0, domain=0, col_id=None, col_id0=0, mask=True):
         nlay, ncol = cloud_frac.shape
         head, mask = self._mcica_args(cloud_frac, alpha, seed, domain, col_id, col_id0, ngpt, mask)
-        self._c("mcica_cloud_mask", ncol, nlay, int(ngpt), *head, mask)
+        self._c("mcica_cloud_mask", ncol, nlay, ngpt, *head, mask)
         return mask
 
     # Forward Monte Carlo ray tracer (rrx_rt_*, rrx_raytracer_sw). tau, ssa (ngpt, nz, ncol) with ncol = nx ny, x fastest;
@@ -599,7 +596,7 @@ class HipKernels:
         dims, (lims, ct, _, _) = self._rt_scene(tau, nx, ny, cloud, band_lims)
         knx, kny, knz = (int(k) for k in kn_grid)
         out = self.empty((knz, kny, knx))
-        self._c("rt_k_null", *dims, int(igpt), BoolArg(top_at_1), tau, lims, ct, float(dz), knx, kny, knz, out)
+        self._c("rt_k_null", *dims, igpt, top_at_1, tau, lims, ct, dz, knx, kny, knz, out)
         return out
 
     def rt_trace_counts(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, k_null, seed,
@@ -609,15 +606,14 @@ class HipKernels:
         dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
         knx, kny, knz = (int(k) for k in kn_grid)
         counts = self.rt_zero_counts(dims[2], dims[0]*dims[1]) if counts is None else counts
-        self._c("rt_trace_counts", *dims, int(igpt), BoolArg(top_at_1), BoolArg(independent_column), tau, ssa, lims, ct, cw, cg,
-                float(dx), float(dy), float(dz), sfc_albedo, float(mu0), float(azimuth), float(inc_dir), float(inc_dif), knx, kny, knz,
-                k_null, ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.c_longlong(int(photon0)), ctypes.c_longlong(int(nphotons)),
-                int(self.RT_MAX_EVENTS if max_events is None else max_events), *(counts[k] for k in self.RT_COUNTS), counts["n_capped"])
+        self._c("rt_trace_counts", *dims, igpt, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth,
+                inc_dir, inc_dif, knx, kny, knz, k_null, int(seed) & 0xFFFFFFFFFFFFFFFF, photon0, nphotons,
+                self.RT_MAX_EVENTS if max_events is None else max_events, *(counts[k] for k in self.RT_COUNTS), counts["n_capped"])
         return counts
 
     def rt_counts_to_flux(self, counts, scale, out):
         """out += counts 2^-32 scale"""
-        self._c("rt_counts_to_flux", ctypes.c_longlong(counts.numel()), counts, float(scale), out)
+        self._c("rt_counts_to_flux", counts.numel(), counts, scale, out)
         return out
 
     def raytracer_sw(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, photons_per_pixel, seed,
@@ -634,10 +630,9 @@ class HipKernels:
         out = {k: self.empty((ncol,)) for k in self.RT_COUNTS[:4]}
         out.update({k: self.empty((nz, ncol)) for k in self.RT_COUNTS[4:]})
         n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        self._c("raytracer_sw", *dims, BoolArg(top_at_1), BoolArg(independent_column), tau, ssa, lims, ct, cw, cg,
-                float(dx), float(dy), float(dz), sfc_albedo, float(mu0), float(azimuth), inc_dir, inc_dif, knx, kny, knz,
-                ctypes.c_longlong(int(photons_per_pixel)), ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                int(self.RT_MAX_EVENTS if max_events is None else max_events), *(out[k] for k in self.RT_COUNTS), n_capped)
+        self._c("raytracer_sw", *dims, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir,
+                inc_dif, knx, kny, knz, photons_per_pixel, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                self.RT_MAX_EVENTS if max_events is None else max_events, *(out[k] for k in self.RT_COUNTS), n_capped)
         out["n_capped"] = int(n_capped.item())
         return out
 
@@ -645,7 +640,7 @@ class HipKernels:
     # tracer, k_null from rt_k_null, and a sensor (camera.Camera, or any object with type, npx, npy, fov, position, e_w, e_h, e_d).
     def _rt_sensor(self, camera):
         numbers = np.concatenate([np.asarray(v, dtype=np.float64).reshape(3) for v in (camera.position, camera.e_w, camera.e_h, camera.e_d)])
-        return (int(camera.type), int(camera.npx), int(camera.npy), float(camera.fov), np.ascontiguousarray(numbers.astype(self.np_dtype)))
+        return (int(camera.type), int(camera.npx), int(camera.npy), camera.fov, np.ascontiguousarray(numbers.astype(self.np_dtype)))
 
     def rt_bw_zero_counts(self, npix):
         return {k: torch.zeros((n,), dtype=torch.int64, device=self.device) for k, n in (("counts", npix), ("n_capped", 1), ("n_clamped", 1))}
@@ -658,10 +653,9 @@ class HipKernels:
         knx, kny, knz = (int(k) for k in kn_grid)
         sensor = self._rt_sensor(camera)
         counts = self.rt_bw_zero_counts(sensor[1]*sensor[2]) if counts is None else counts
-        self._c("rt_bw_trace_counts", *dims, int(igpt), BoolArg(top_at_1), tau, ssa, lims, ct, cw, cg, float(dx), float(dy), float(dz),
-                sfc_albedo, float(mu0), float(azimuth), knx, kny, knz, k_null, *sensor,
-                ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.c_longlong(int(ray0)), ctypes.c_longlong(int(nrays)),
-                int(self.RT_MAX_EVENTS if max_events is None else max_events), counts["counts"], counts["n_capped"], counts["n_clamped"])
+        self._c("rt_bw_trace_counts", *dims, igpt, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, knx, kny, knz,
+                k_null, *sensor, int(seed) & 0xFFFFFFFFFFFFFFFF, ray0, nrays, self.RT_MAX_EVENTS if max_events is None else max_events,
+                counts["counts"], counts["n_capped"], counts["n_clamped"])
         return counts
 
     def raytracer_bw(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
@@ -677,9 +671,8 @@ class HipKernels:
         radiance = self.empty((sensor[2], sensor[1]))
         n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
         n_clamped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        self._c("raytracer_bw", *dims, BoolArg(top_at_1), tau, ssa, lims, ct, cw, cg, float(dx), float(dy), float(dz), sfc_albedo,
-                float(mu0), float(azimuth), inc_dir, knx, kny, knz, *sensor, ctypes.c_longlong(int(rays_per_pixel)),
-                ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), int(self.RT_MAX_EVENTS if max_events is None else max_events),
+        self._c("raytracer_bw", *dims, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz,
+                *sensor, rays_per_pixel, int(seed) & 0xFFFFFFFFFFFFFFFF, self.RT_MAX_EVENTS if max_events is None else max_events,
                 radiance, n_capped, n_clamped)
         return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
 
@@ -702,7 +695,7 @@ class HipKernels:
     def heating_rate(self, flux_net, plev, g_over_cp=9.80665/1004.64):
         nlev, ncol = flux_net.shape
         out = self.empty((nlev-1, ncol))
-        self._c("heating_rate", ncol, nlev-1, float(g_over_cp), flux_net, plev, out)
+        self._c("heating_rate", ncol, nlev-1, g_over_cp, flux_net, plev, out)
         return out
 
     def sum_byband(self, gpt_flux, band_lims):
@@ -785,7 +778,7 @@ class HipKernels:
         nbnd = lut["lut_extliq"].shape[0]
         tau = self.empty((nbnd, nlay, ncol)); ssa = self.empty((nbnd, nlay, ncol)); g = self.empty((nbnd, nlay, ncol))
         self._c("cloud_optics_2str_delta" if delta_scale else "cloud_optics_2str", ncol, nlay, nbnd, lut["nsize_liq"], lut["nsize_ice"],
-                float(lut["radliq_lwr"]), float(lut["radliq_upr"]), float(lut["diamice_lwr"]), float(lut["diamice_upr"]),
+                lut["radliq_lwr"], lut["radliq_upr"], lut["diamice_lwr"], lut["diamice_upr"],
                 lut["lut_extliq"], lut["lut_ssaliq"], lut["lut_asyliq"], lut["lut_extice"], lut["lut_ssaice"], lut["lut_asyice"],
                 clwp, ciwp, reliq, deice, tau, ssa, g)
         return tau, ssa, g
@@ -814,7 +807,7 @@ class HipKernels:
         nbnd = lut["lut_extliq"].shape[0]
         tau = self.empty((nbnd, nlay, ncol))
         self._c("cloud_optics_1scl", ncol, nlay, nbnd, lut["nsize_liq"], lut["nsize_ice"],
-                float(lut["radliq_lwr"]), float(lut["radliq_upr"]), float(lut["diamice_lwr"]), float(lut["diamice_upr"]),
+                lut["radliq_lwr"], lut["radliq_upr"], lut["diamice_lwr"], lut["diamice_upr"],
                 lut["lut_extliq"], lut["lut_ssaliq"], lut["lut_asyliq"], lut["lut_extice"], lut["lut_ssaice"], lut["lut_asyice"],
                 clwp, ciwp, reliq, deice, tau)
         return tau
@@ -839,12 +832,12 @@ class HipKernels:
     def gather_cols(self, perm, src, out):
         """out[..., i] = src[..., perm[i]] for every column of out; column-last tensors with the same leading shape, perm int32."""
         nrest = int(np.prod(src.shape[:-1], dtype=np.int64)) if src.dim() > 1 else 1
-        self._c("gather_cols", int(out.shape[-1]), ctypes.c_ulonglong(nrest), perm, int(src.shape[-1]), src, out)
+        self._c("gather_cols", out.shape[-1], nrest, perm, src.shape[-1], src, out)
         return out
 
     def gather_lastdim(self, perm, src, out):
         """out[i, :] = src[perm[i], :] for every row of out; column-first (ncol, n1) tensors, perm int32."""
-        self._c("gather_lastdim", int(src.shape[1]), int(out.shape[0]), perm, src, out)
+        self._c("gather_lastdim", src.shape[1], out.shape[0], perm, src, out)
         return out
 
     def sunlit_columns(self, mu0, order=None, pad_to=1, perm=None, count=None):
@@ -859,7 +852,7 @@ class HipKernels:
             perm = self.int_empty((max(-(-ncol // pad_to) * pad_to, 1),))
         if count is None:
             count = self.int_empty((1,))
-        self._c("sunlit_columns", ncol, mu0, order, int(pad_to), perm, count)
+        self._c("sunlit_columns", ncol, mu0, order, pad_to, perm, count)
         return perm, count
 
     def scatter_cols_fill(self, n, perm, src, dst):
@@ -870,20 +863,20 @@ class HipKernels:
             raise TypeError("scatter_cols_fill: perm is an int32 tensor")
         if tuple(src.shape[:-1]) != tuple(dst.shape[:-1]) or not (src.is_contiguous() and dst.is_contiguous()):
             raise ValueError("scatter_cols_fill: src and dst must be contiguous with the same leading shape")
-        self._c("scatter_cols_fill", int(n), ctypes.c_ulonglong(nrest), perm, int(src.shape[-1]), src, int(dst.shape[-1]), dst)
+        self._c("scatter_cols_fill", n, nrest, perm, src.shape[-1], src, dst.shape[-1], dst)
         return dst
 
     supports_null_g = True      # gas_optics_sw_fused / sw_solver_2stream accept g = None (asymmetry identically zero)
 
     def set_broadband_min_groups(self, n):
         """column groups needed before do_broadband takes the fused one-kernel form (default 512; 1 = always)"""
-        self.lib.call("rrx_set_broadband_min_groups", int(n))
+        self.lib.call("rrx_set_broadband_min_groups", n)
 
     def set_broadband_gsplit(self, n):
-        self.lib.call("rrx_set_broadband_gsplit", int(n))
+        self.lib.call("rrx_set_broadband_gsplit", n)
 
     def set_variant(self, lw=None, sw=None):
         if lw is not None:
-            self.lib.call("rrx_set_lw_variant", int(lw))
+            self.lib.call("rrx_set_lw_variant", lw)
         if sw is not None:
-            self.lib.call("rrx_set_sw_variant", int(sw))
+            self.lib.call("rrx_set_sw_variant", sw)

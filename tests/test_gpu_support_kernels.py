@@ -758,3 +758,24 @@ def test_sum_byband_is_the_fused_sw_solvers_band_sum(layout, hip_f64):
         for ib, n in enumerate(sizes):
             if n == 0:
                 assert not want[ib].any() and not got[ib].any(), (k, ib)
+
+
+# ==== the binding itself (rte-rrtmgp-cpp_amd/_ffi.py) =============================================================================
+def test_binding_refuses_a_tensor_of_the_other_precision(be):
+    """HipKernels calls go through the declarations of include/rrx_hip.h: gauss_Ds in the other precision is a TypeError that names
+    the parameter, raised before the library is entered; with the right tensors the entry gives secants[imu, g, c] =
+    gauss_Ds[n_quad-1, imu] as ever (rte_solver_kernels_launchers.cu:48-58)."""
+    ncol, ngpt, n_quad = 4, 8, 1
+    other = torch.float32 if be.tdtype == torch.float64 else torch.float64
+    Ds = np.ascontiguousarray(pipeline.GAUSS_DS.astype(be.np_dtype))
+    buf, out = guarded(be, (n_quad, ngpt, ncol))
+    with pytest.raises(TypeError, match="gauss_Ds"):
+        be.lw_secants_array(ncol, ngpt, n_quad, pipeline.MAX_GAUSS_PTS, dev(be, Ds).to(other), out=out)
+    assert bool((buf == GUARD).all().item())                                                   # nothing ran
+    with pytest.raises(TypeError, match="secants"):
+        be.lw_secants_array(ncol, ngpt, n_quad, pipeline.MAX_GAUSS_PTS, dev(be, Ds), out=out.to(other))
+    got = be.lw_secants_array(ncol, ngpt, n_quad, pipeline.MAX_GAUSS_PTS, dev(be, Ds), out=out)
+    want = np.empty((n_quad, ngpt, ncol), dtype=be.np_dtype)
+    want[:] = Ds.reshape(pipeline.MAX_GAUSS_PTS, pipeline.MAX_GAUSS_PTS)[n_quad-1, :n_quad, None, None]
+    assert same_bits(got.cpu().numpy(), want) and tail_untouched(buf, out)
+    assert same_bits(be.lw_secants_array(ncol, ngpt, n_quad, pipeline.MAX_GAUSS_PTS, dev(be, Ds)).cpu().numpy(), want)

@@ -1,74 +1,43 @@
 """CPU tests of the surface-temperature Jacobian entries (rrx_lw_solver_noscat_fractions_jac, rrx_lw_flux_up_adjust): declared in both
 precisions and exported, their argument checks answer without a GPU, and the host layer declares, exports and offers the switch."""
-import ctypes
 import os
 import re
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rrx_hip.h")
-LIB = os.path.join(ROOT, "rte-rrtmgp-cpp_amd", "lib", "librrx_hip.so")
+import abi
+
+ROOT = abi.ROOT
 HOSTLIB = os.path.join(ROOT, "rte-rrtmgp-cpp_amd", "lib", "librte_rrtmgp_hip.so")
 DRIVER = os.path.join(ROOT, "rte-rrtmgp-cpp_amd", "lib", "test_rte_rrtmgp_gpu")
 ENTRIES = ("rrx_lw_solver_noscat_fractions_jac", "rrx_lw_flux_up_adjust")
 
 
-def _lib():
-    if not os.path.exists(LIB):
-        pytest.fail(f"{LIB} not built: run __graft_entry__.build()")
-    lib = ctypes.CDLL(LIB)
-    lib.rrx_last_error.restype = ctypes.c_char_p
-    return lib
-
-
-def _buf():
-    """a host buffer standing in for a device pointer: the checks fail before anything dereferences it"""
-    b = (ctypes.c_double * 4)()
-    return ctypes.cast(b, ctypes.c_void_p), b
-
-
 def test_header_declares_the_jacobian_entries_in_both_precisions():
-    text = open(HEADER).read()
-    macro = text[text.index("#define RRX_DECLARE"):text.index("RRX_DECLARE(double")]
     for name in ENTRIES:
-        assert re.search(r"\b" + name + r"##SFX\s*\(", macro), name
+        assert abi.declares(name), name
 
 
 def test_library_exports_the_jacobian_entries():
-    lib = _lib()
+    lib = abi.lib()
     for name in ENTRIES:
-        for sfx in ("_f64", "_f32"):
-            assert hasattr(lib, name + sfx), name + sfx
+        for sfx in abi.SFXS:
+            assert lib.has(name + sfx), name + sfx
 
 
 @pytest.mark.parametrize("sfx", ["_f64", "_f32"])
 @pytest.mark.parametrize("case", ["null_sfc_src_jac", "null_flux_up_jac", "ncol0", "nlay0", "null_broadband"])
 def test_lw_jac_rejects_bad_arguments_without_a_gpu(sfx, case):
     """Arguments are checked before any HIP call: a status and a message, on a machine without a GPU too."""
-    lib = _lib()
-    p, keep = _buf()
-    null = ctypes.c_void_p(0)
-    ncol, nlay, ngpt = 4, 3, 8
-    sjac, jac, up, dn = p, p, p, p
-    if case == "null_sfc_src_jac":
-        sjac = null
-    elif case == "null_flux_up_jac":
-        jac = null
-    elif case == "ncol0":
-        ncol = 0
-    elif case == "nlay0":
-        nlay = 0
+    lib = abi.lib()
+    null, extents = ["inc_flux"], {}                 # no flux from above; every other pointer is given
+    if case in ("ncol0", "nlay0"):
+        extents[case[:-1]] = 0
     else:
-        up = null
-    fn = getattr(lib, "rrx_lw_solver_noscat_fractions_jac" + sfx)
-    fn.restype = ctypes.c_int
-    # ncol, nlay, ngpt, top_at_1, secants, weights, tau, pfrac, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux,
-    # flux_up_loc, flux_dn_loc, sfc_src_jac, flux_up_jac, stream
-    rc = fn(ncol, nlay, ngpt, ctypes.c_byte(1), *([p] * 9), null, up, dn, sjac, jac, null)
+        null.append({"null_sfc_src_jac": "sfc_src_jac", "null_flux_up_jac": "flux_up_jac", "null_broadband": "flux_up_loc"}[case])
+    rc, msg = abi.call(lib, "rrx_lw_solver_noscat_fractions_jac", sfx, null=null, top_at_1=1, **extents)
     assert rc != 0
-    msg = lib.rrx_last_error().decode()
     assert "rrx_lw_solver_noscat_fractions_jac" in msg
     want = {"null_sfc_src_jac": "sfc_src_jac", "null_flux_up_jac": "flux_up_jac", "ncol0": "empty", "nlay0": "empty",
             "null_broadband": "broadband"}[case]
@@ -78,18 +47,12 @@ def test_lw_jac_rejects_bad_arguments_without_a_gpu(sfx, case):
 @pytest.mark.parametrize("sfx", ["_f64", "_f32"])
 @pytest.mark.parametrize("case", ["null_jac", "null_t_old", "null_t_new", "null_flux_up", "nlev0"])
 def test_flux_up_adjust_rejects_bad_arguments_without_a_gpu(sfx, case):
-    lib = _lib()
-    p, keep = _buf()
-    null = ctypes.c_void_p(0)
-    args = dict(jac=p, t_old=p, t_new=p, up=p)
-    nlev = 0 if case == "nlev0" else 5
+    lib = abi.lib()
+    null = ["flux_net"]                              # (optional)
     if case != "nlev0":
-        args[{"null_jac": "jac", "null_t_old": "t_old", "null_t_new": "t_new", "null_flux_up": "up"}[case]] = null
-    fn = getattr(lib, "rrx_lw_flux_up_adjust" + sfx)
-    fn.restype = ctypes.c_int
-    rc = fn(4, nlev, args["jac"], args["t_old"], args["t_new"], args["up"], null, null)
+        null.append({"null_jac": "flux_up_jac", "null_t_old": "t_sfc_old", "null_t_new": "t_sfc_new", "null_flux_up": "flux_up"}[case])
+    rc, msg = abi.call(lib, "rrx_lw_flux_up_adjust", sfx, null=null, ncol=4, nlev=0 if case == "nlev0" else 5)
     assert rc != 0
-    msg = lib.rrx_last_error().decode()
     assert "rrx_lw_flux_up_adjust" in msg
     want = {"null_jac": "flux_up_jac", "null_t_old": "surface temperatures", "null_t_new": "surface temperatures",
             "null_flux_up": "flux_up", "nlev0": "empty"}[case]

@@ -2,35 +2,26 @@
 precisions with their semantics, exported, bound in hip_kernels.py, pipeline.ResidentSolver and the C++ classes and driver with
 default off, and their argument checks answer with the entry's name and the offending argument without a GPU. The CPU boundary no
 longer refuses do_rescaling."""
-import ctypes
 import inspect
 import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rrx_hip.h")
-LIB = os.path.join(ROOT, "rte-rrtmgp-cpp_amd", "lib", "librrx_hip.so")
+import abi
+
+ROOT = abi.ROOT
 GENERAL, FUSED = "rrx_lw_solver_noscat_rescaled", "rrx_lw_solver_noscat_fractions_rescaled"
-GENERAL_ARGS = ["secants", "weights", "tau", "ssa", "g", "lay_source", "lev_source", "sfc_emis", "sfc_src", "inc_flux", "flux_up", "flux_dn"]
-FUSED_ARGS = ["secants", "weights", "tau", "pfrac", "blay", "blev", "gpoint_bands", "band_lims_gpt", "cld_tau", "cld_ssa", "cld_g",
-              "sfc_emis", "sfc_src", "inc_flux", "flux_up", "flux_dn"]
-
-
-def _lib():
-    if not os.path.exists(LIB):
-        pytest.fail(f"{LIB} not built: run __graft_entry__.build()")
-    lib = ctypes.CDLL(LIB)
-    lib.rrx_last_error.restype = ctypes.c_char_p
-    return lib
+# pointers that may be NULL, so no null-pointer check names them: the top boundary, the cloud triple (all or none), and the general
+# entry's outputs of the modes these calls leave off
+OPTIONAL_GENERAL = ("inc_flux", "flux_up_loc", "flux_dn_loc", "sfc_src_jac", "flux_up_jac")
+OPTIONAL_FUSED = ("inc_flux", "cld_tau", "cld_ssa", "cld_g")
 
 
 @pytest.mark.parametrize("entry", [GENERAL, FUSED])
 def test_header_declares_the_entries_with_their_semantics(entry):
-    text = open(HEADER).read()
-    macro = text[text.index("#define RRX_DECLARE"):text.index("RRX_DECLARE(double")]
-    assert re.search(r"\b" + entry + r"##SFX\s*\(", macro)
+    macro = abi.header_macro()
+    assert abi.declares(entry)
     for word in ("wb = ssa (1 - g)/2", "st = 1 - ssa + wb", "Cn = 0.4 wb / max(st, 3 tiny)", "tl = tau D st", "An = 1 - tr tr",
                  "Cn (An dn[i]   - tr sdn - sup)", "Cn (An up[i+1] - tr sup - sdn)", "J[i] = tr J[i+1]"):
         assert word in macro, word
@@ -38,61 +29,55 @@ def test_header_declares_the_entries_with_their_semantics(entry):
 
 @pytest.mark.parametrize("entry", [GENERAL, FUSED])
 def test_library_exports_the_entries(entry):
-    lib = _lib()
-    for sfx in ("_f64", "_f32"):
-        assert hasattr(lib, entry + sfx), entry + sfx
+    lib = abi.lib()
+    for sfx in abi.SFXS:
+        assert lib.has(entry + sfx), entry + sfx
 
 
-def _call_general(lib, sfx, ncol=4, nlay=3, ngpt=8, nmus=1, null=(), broadband=False):
-    keep = (ctypes.c_double * 4)()
-    p, z = ctypes.cast(keep, ctypes.c_void_p), ctypes.c_void_p(0)
-    a = {n: (z if n in null else p) for n in GENERAL_ARGS}
-    loc = {n: (z if (n in null or not broadband) else p) for n in ("flux_up_loc", "flux_dn_loc")}
-    fn = getattr(lib, GENERAL + sfx); fn.restype = ctypes.c_int
-    return fn(ncol, nlay, ngpt, ctypes.c_byte(1), nmus, *[a[n] for n in GENERAL_ARGS], ctypes.c_byte(1 if broadband else 0),
-              loc["flux_up_loc"], loc["flux_dn_loc"], ctypes.c_byte(0), z, z, z)
+def _call_general(lib, sfx, null=(), broadband=False, nmus=1, **extents):
+    """no Jacobian; the broadband outputs are given with broadband only"""
+    off = ("sfc_src_jac", "flux_up_jac") + (() if broadband else ("flux_up_loc", "flux_dn_loc"))
+    return abi.call(lib, GENERAL, sfx, null=tuple(null) + off, top_at_1=1, nmus=nmus, do_broadband=int(broadband), do_jacobians=0,
+                    **extents)
 
 
-def _call_fused(lib, sfx, ncol=4, nlay=3, ngpt=8, nbnd=2, null=()):
-    keep = (ctypes.c_double * 4)()
-    p, z = ctypes.cast(keep, ctypes.c_void_p), ctypes.c_void_p(0)
-    fn = getattr(lib, FUSED + sfx); fn.restype = ctypes.c_int
-    return fn(ncol, nlay, ngpt, nbnd, ctypes.c_byte(1), *[(z if n in null else p) for n in FUSED_ARGS], z)
+def _call_fused(lib, sfx, null=(), **extents):
+    return abi.call(lib, FUSED, sfx, null=null, top_at_1=1, **extents)
 
 
 @pytest.mark.parametrize("sfx", ["_f64", "_f32"])
-@pytest.mark.parametrize("arg", [a for a in GENERAL_ARGS if a != "inc_flux"])
+@pytest.mark.parametrize("arg", [a for a in abi.pointers(GENERAL) if a not in OPTIONAL_GENERAL])
 def test_general_entry_names_a_null_pointer(sfx, arg):
     """Arguments are checked before any HIP call (host buffers stand in for device pointers: nothing dereferences them)."""
-    lib = _lib()
-    assert _call_general(lib, sfx, null=(arg,)) != 0
-    msg = lib.rrx_last_error().decode()
+    lib = abi.lib()
+    rc, msg = _call_general(lib, sfx, null=(arg,))
+    assert rc != 0
     assert msg.startswith(GENERAL + ":") and re.search(r"\b" + arg + r"\b", msg), msg
 
 
 @pytest.mark.parametrize("sfx", ["_f64", "_f32"])
 def test_general_entry_broadband_needs_its_outputs_only(sfx):
-    lib = _lib()
-    assert _call_general(lib, sfx, null=("flux_up_loc",), broadband=True) != 0
-    msg = lib.rrx_last_error().decode()
+    lib = abi.lib()
+    rc, msg = _call_general(lib, sfx, null=("flux_up_loc",), broadband=True)
+    assert rc != 0
     assert msg.startswith(GENERAL + ":") and "flux_up_loc" in msg, msg
 
 
 @pytest.mark.parametrize("sfx", ["_f64", "_f32"])
 @pytest.mark.parametrize("nmus", [0, 5])
 def test_general_entry_refuses_other_angle_counts(sfx, nmus):
-    lib = _lib()
-    assert _call_general(lib, sfx, nmus=nmus) != 0
-    msg = lib.rrx_last_error().decode()
+    lib = abi.lib()
+    rc, msg = _call_general(lib, sfx, nmus=nmus)
+    assert rc != 0
     assert msg.startswith(GENERAL + ":") and "n_quad_angs" in msg, msg
 
 
 @pytest.mark.parametrize("sfx", ["_f64", "_f32"])
-@pytest.mark.parametrize("arg", [a for a in FUSED_ARGS if a != "inc_flux" and not a.startswith("cld_")])
+@pytest.mark.parametrize("arg", [a for a in abi.pointers(FUSED) if a not in OPTIONAL_FUSED])
 def test_fused_entry_names_a_null_pointer(sfx, arg):
-    lib = _lib()
-    assert _call_fused(lib, sfx, null=(arg,)) != 0
-    msg = lib.rrx_last_error().decode()
+    lib = abi.lib()
+    rc, msg = _call_fused(lib, sfx, null=(arg,))
+    assert rc != 0
     assert msg.startswith(FUSED + ":") and re.search(r"\b" + arg + r"\b", msg), msg
 
 
@@ -100,26 +85,26 @@ def test_fused_entry_names_a_null_pointer(sfx, arg):
 @pytest.mark.parametrize("null,named", [(("cld_tau",), "cld_tau"), (("cld_ssa",), "cld_ssa"), (("cld_g",), "cld_g"),
                                         (("cld_tau", "cld_g"), "cld_tau"), (("cld_ssa", "cld_g"), "cld_ssa")])
 def test_fused_entry_refuses_a_partly_null_cloud_triple(sfx, null, named):
-    lib = _lib()
-    assert _call_fused(lib, sfx, null=null) != 0
-    msg = lib.rrx_last_error().decode()
+    lib = abi.lib()
+    rc, msg = _call_fused(lib, sfx, null=null)
+    assert rc != 0
     assert msg.startswith(FUSED + ":") and named in msg, msg
 
 
 @pytest.mark.parametrize("sfx", ["_f64", "_f32"])
 @pytest.mark.parametrize("extent", ["ncol", "nlay", "ngpt", "nbnd"])
 def test_negative_extents_are_refused_and_zero_extents_do_nothing(sfx, extent):
-    lib = _lib()
-    everything = tuple(set(GENERAL_ARGS) | set(FUSED_ARGS))
-    assert _call_fused(lib, sfx, **{extent: -1}) != 0
-    msg = lib.rrx_last_error().decode()
+    lib = abi.lib()
+    everything = tuple(set(abi.pointers(GENERAL)) | set(abi.pointers(FUSED)))
+    rc, msg = _call_fused(lib, sfx, **{extent: -1})
+    assert rc != 0
     assert msg.startswith(FUSED + ":") and extent in msg, msg
-    assert _call_fused(lib, sfx, **{extent: 0}, null=everything) == 0          # nothing is read, written or launched
+    assert _call_fused(lib, sfx, **{extent: 0}, null=everything)[0] == 0          # nothing is read, written or launched
     if extent != "nbnd":
-        assert _call_general(lib, sfx, **{extent: -1}) != 0
-        msg = lib.rrx_last_error().decode()
+        rc, msg = _call_general(lib, sfx, **{extent: -1})
+        assert rc != 0
         assert msg.startswith(GENERAL + ":") and extent in msg, msg
-        assert _call_general(lib, sfx, **{extent: 0}, null=everything) == 0
+        assert _call_general(lib, sfx, **{extent: 0}, null=everything)[0] == 0
 
 
 def test_python_bindings_carry_the_new_names_and_default_off():

@@ -1,39 +1,28 @@
 """CPU tests of the several-angle LW entry (rrx_lw_solver_noscat_fractions_angles): declared in both precisions and exported, and its
 argument checks answer with the entry's name and the offending argument without a GPU; the host layer declares and exports the
 setter and offers the option."""
-import ctypes
 import os
 import re
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rrx_hip.h")
-LIB = os.path.join(ROOT, "rte-rrtmgp-cpp_amd", "lib", "librrx_hip.so")
+import abi
+
+ROOT = abi.ROOT
 HOSTLIB = os.path.join(ROOT, "rte-rrtmgp-cpp_amd", "lib", "librte_rrtmgp_hip.so")
 DRIVER = os.path.join(ROOT, "rte-rrtmgp-cpp_amd", "lib", "test_rte_rrtmgp_gpu")
 ENTRY = "rrx_lw_solver_noscat_fractions_angles"
 
 
-def _lib():
-    if not os.path.exists(LIB):
-        pytest.fail(f"{LIB} not built: run __graft_entry__.build()")
-    lib = ctypes.CDLL(LIB)
-    lib.rrx_last_error.restype = ctypes.c_char_p
-    return lib
-
-
 def test_header_declares_the_entry_in_both_precisions():
-    text = open(HEADER).read()
-    macro = text[text.index("#define RRX_DECLARE"):text.index("RRX_DECLARE(double")]
-    assert re.search(r"\b" + ENTRY + r"##SFX\s*\(", macro)
+    assert abi.declares(ENTRY)
 
 
 def test_library_exports_the_entry():
-    lib = _lib()
-    for sfx in ("_f64", "_f32"):
-        assert hasattr(lib, ENTRY + sfx), ENTRY + sfx
+    lib = abi.lib()
+    for sfx in abi.SFXS:
+        assert lib.has(ENTRY + sfx), ENTRY + sfx
 
 
 @pytest.mark.parametrize("sfx", ["_f64", "_f32"])
@@ -41,36 +30,21 @@ def test_library_exports_the_entry():
                                   "only_flux_up_jac"])
 def test_entry_rejects_bad_arguments_without_a_gpu(sfx, case):
     """Arguments are checked before any HIP call (host buffers stand in for device pointers: nothing dereferences them)."""
-    lib = _lib()
-    keep = (ctypes.c_double * 4)()
-    p, null = ctypes.cast(keep, ctypes.c_void_p), ctypes.c_void_p(0)
-    ncol, nlay, ngpt, nmus = 4, 3, 8, 3
-    up, dn, sjac, jac = p, p, null, null
+    lib = abi.lib()
     want = {"nmus0": "nmus", "nmus5": "nmus", "ncol0": "ncol", "nlay0": "nlay", "null_flux_up": "flux_up_loc",
             "null_flux_dn": "flux_dn_loc", "only_sfc_src_jac": "flux_up_jac", "only_flux_up_jac": "sfc_src_jac"}[case]
-    if case == "nmus0":
-        nmus = 0
-    elif case == "nmus5":
-        nmus = 5
-    elif case == "ncol0":
-        ncol = 0
-    elif case == "nlay0":
-        nlay = 0
-    elif case == "null_flux_up":
-        up = null
-    elif case == "null_flux_dn":
-        dn = null
-    elif case == "only_sfc_src_jac":
-        sjac = p
+    null = ["inc_flux", "sfc_src_jac", "flux_up_jac"]              # three angles, fluxes only, no flux from above
+    scalars = dict(top_at_1=1, nmus=3)
+    if case.startswith("nmus"):
+        scalars["nmus"] = int(case[4:])
+    elif case.endswith("0"):
+        scalars[case[:-1]] = 0
+    elif case.startswith("null_"):
+        null.append(case[5:] + "_loc")
     else:
-        jac = p
-    fn = getattr(lib, ENTRY + sfx)
-    fn.restype = ctypes.c_int
-    # ncol, nlay, ngpt, top_at_1, nmus, secants, weights, tau, pfrac, blay, blev, gpoint_bands, sfc_emis, sfc_src, inc_flux,
-    # flux_up_loc, flux_dn_loc, sfc_src_jac, flux_up_jac, stream
-    rc = fn(ncol, nlay, ngpt, ctypes.c_byte(1), nmus, *([p] * 9), null, up, dn, sjac, jac, null)
+        null.remove(case[5:])
+    rc, msg = abi.call(lib, ENTRY, sfx, null=null, **scalars)
     assert rc != 0
-    msg = lib.rrx_last_error().decode()
     assert ENTRY in msg and want in msg, msg
 
 

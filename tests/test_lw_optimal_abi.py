@@ -2,7 +2,6 @@
 precisions and exported, argument checks that answer with the entry's name without a GPU, the forwarders and Python bindings, the
 synthetic k-distribution's optimal_angle_fit (every other table bit for bit what it was before the fit existed) and its round trip
 through the coefficient file."""
-import ctypes
 import hashlib
 import inspect
 import os
@@ -11,11 +10,11 @@ import re
 import numpy as np
 import pytest
 
+import abi
+
 from rte_rrtmgp_cpp_amd import synthetic, synthetic_files, rrxio
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rrx_hip.h")
-LIB = os.path.join(ROOT, "rte-rrtmgp-cpp_amd", "lib", "librrx_hip.so")
+ROOT = abi.ROOT
 PRODUCER = "rrx_lw_optimal_secants"
 SOLVER = "rrx_lw_solver_noscat_fractions_optimal"
 SMALL = dict(ngpt=32, nbnd=4, npres=20, nflav=4, nminor_lower=9, nminor_upper=5)
@@ -44,48 +43,31 @@ def kdist_digest(kd):
     return h.hexdigest()
 
 
-def _lib():
-    if not os.path.exists(LIB):
-        pytest.fail(f"{LIB} not built: run __graft_entry__.build()")
-    lib = ctypes.CDLL(LIB)
-    lib.rrx_last_error.restype = ctypes.c_char_p
-    return lib
-
-
 @pytest.mark.parametrize("entry", [PRODUCER, SOLVER])
 def test_header_declares_the_entries_in_both_precisions(entry):
-    text = open(HEADER).read()
-    macro = text[text.index("#define RRX_DECLARE"):text.index("RRX_DECLARE(double")]
-    assert re.search(r"\b" + entry + r"##SFX\s*\(", macro)
-    assert "RRX_DECLARE(float" in text
+    assert abi.declares(entry)
+    assert "RRX_DECLARE(float" in abi.header_text()
 
 
 @pytest.mark.parametrize("entry", [PRODUCER, SOLVER])
 def test_library_exports_the_entries(entry):
-    lib = _lib()
-    for sfx in ("_f64", "_f32"):
-        assert hasattr(lib, entry + sfx), entry + sfx
+    lib = abi.lib()
+    for sfx in abi.SFXS:
+        assert lib.has(entry + sfx), entry + sfx
 
 
 @pytest.mark.parametrize("sfx", ["_f64", "_f32"])
 @pytest.mark.parametrize("case", ["ncol0", "nlay0", "ngpt0", "nbnd0", "null_fit", "null_tau", "null_secants"])
 def test_producer_rejects_bad_arguments_without_a_gpu(sfx, case):
     """Arguments are checked before any HIP call (host buffers stand in for device pointers: nothing dereferences them)."""
-    lib = _lib()
-    keep = (ctypes.c_double * 4)()
-    p, null = ctypes.cast(keep, ctypes.c_void_p), ctypes.c_void_p(0)
-    a = dict(ncol=4, nlay=3, ngpt=8, nbnd=2, gb=p, fit=p, tau=p, sec=p)
+    lib = abi.lib()
     want = {"ncol0": "ncol", "nlay0": "nlay", "ngpt0": "ngpt", "nbnd0": "nbnd", "null_fit": "optimal_angle_fit", "null_tau": "tau",
             "null_secants": "secants"}[case]
     if case.endswith("0"):
-        a[case[:-1]] = 0
+        rc, msg = abi.call(lib, PRODUCER, sfx, **{case[:-1]: 0})
     else:
-        a[{"null_fit": "fit", "null_tau": "tau", "null_secants": "sec"}[case]] = null
-    fn = getattr(lib, PRODUCER + sfx)
-    fn.restype = ctypes.c_int
-    rc = fn(a["ncol"], a["nlay"], a["ngpt"], a["nbnd"], a["gb"], a["fit"], a["tau"], a["sec"], null)
+        rc, msg = abi.call(lib, PRODUCER, sfx, null=(want,))
     assert rc == 1
-    msg = lib.rrx_last_error().decode()
     assert PRODUCER in msg and want in msg, msg
 
 
@@ -93,29 +75,20 @@ def test_producer_rejects_bad_arguments_without_a_gpu(sfx, case):
 @pytest.mark.parametrize("case", ["ncol0", "nlay0", "ngpt0", "nbnd0", "null_fit", "null_weights", "null_flux_up", "null_flux_dn",
                                   "only_sfc_src_jac", "only_flux_up_jac"])
 def test_solver_rejects_bad_arguments_without_a_gpu(sfx, case):
-    lib = _lib()
-    keep = (ctypes.c_double * 4)()
-    p, null = ctypes.cast(keep, ctypes.c_void_p), ctypes.c_void_p(0)
-    a = dict(ncol=4, nlay=3, ngpt=8, nbnd=2, weights=p, fit=p, up=p, dn=p, sjac=null, jac=null)
+    lib = abi.lib()
     want = {"ncol0": "ncol", "nlay0": "nlay", "ngpt0": "ngpt", "nbnd0": "nbnd", "null_fit": "optimal_angle_fit",
             "null_weights": "weights", "null_flux_up": "flux_up_loc", "null_flux_dn": "flux_dn_loc", "only_sfc_src_jac": "flux_up_jac",
             "only_flux_up_jac": "sfc_src_jac"}[case]
+    null = ["inc_flux", "sfc_src_jac", "flux_up_jac", "secants_out"]          # fluxes only, no flux from above
+    extents = {}
     if case.endswith("0"):
-        a[case[:-1]] = 0
-    elif case == "only_sfc_src_jac":
-        a["sjac"] = p
-    elif case == "only_flux_up_jac":
-        a["jac"] = p
+        extents[case[:-1]] = 0
+    elif case.startswith("only_"):
+        null.remove(case[5:])
     else:
-        a[{"null_fit": "fit", "null_weights": "weights", "null_flux_up": "up", "null_flux_dn": "dn"}[case]] = null
-    fn = getattr(lib, SOLVER + sfx)
-    fn.restype = ctypes.c_int
-    # ncol, nlay, ngpt, nbnd, top_at_1, weights, tau, pfrac, blay, blev, gpoint_bands, optimal_angle_fit, sfc_emis, sfc_src, inc_flux,
-    # flux_up_loc, flux_dn_loc, sfc_src_jac, flux_up_jac, secants_out, stream
-    rc = fn(a["ncol"], a["nlay"], a["ngpt"], a["nbnd"], ctypes.c_byte(1), a["weights"], p, p, p, p, p, a["fit"], p, p, null,
-            a["up"], a["dn"], a["sjac"], a["jac"], null, null)
+        null.append(want)
+    rc, msg = abi.call(lib, SOLVER, sfx, null=null, top_at_1=1, **extents)
     assert rc == 1
-    msg = lib.rrx_last_error().decode()
     assert SOLVER in msg and want in msg, msg
 
 

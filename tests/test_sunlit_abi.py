@@ -7,34 +7,25 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rrx_hip.h")
-LIB = os.path.join(ROOT, "rte-rrtmgp-cpp_amd", "lib", "librrx_hip.so")
+import abi
+
+ROOT = abi.ROOT
 HOSTLIB = os.path.join(ROOT, "rte-rrtmgp-cpp_amd", "lib", "librte_rrtmgp_hip.so")
 ENTRIES = ("rrx_sunlit_columns", "rrx_scatter_cols_fill")
 
 
-def _lib():
-    if not os.path.exists(LIB):
-        pytest.fail(f"{LIB} not built: run __graft_entry__.build()")
-    lib = ctypes.CDLL(LIB)
-    lib.rrx_last_error.restype = ctypes.c_char_p
-    return lib
-
-
 def test_header_declares_the_sunlit_entries_in_both_precisions():
-    text = open(HEADER).read()
-    macro = text[text.index("#define RRX_DECLARE"):text.index("RRX_DECLARE(double")]
+    text = abi.header_text()
     for name in ENTRIES:
-        assert re.search(r"\b" + name + r"##SFX\s*\(", macro), name
+        assert abi.declares(name), name
     assert "RRX_DECLARE(double, _f64)" in text and "RRX_DECLARE(float, _f32)" in text
 
 
 def test_library_exports_the_sunlit_entries():
-    lib = _lib()
+    lib = abi.lib()
     for name in ENTRIES:
-        for sfx in ("_f64", "_f32"):
-            assert hasattr(lib, name + sfx), name + sfx
+        for sfx in abi.SFXS:
+            assert lib.has(name + sfx), name + sfx
 
 
 @pytest.mark.parametrize("sfx", ["_f64", "_f32"])
@@ -42,19 +33,11 @@ def test_library_exports_the_sunlit_entries():
 def test_sunlit_columns_rejects_bad_arguments_without_a_gpu(sfx, case):
     """Arguments are checked before any HIP call: a status and a message, on a machine without a GPU too (the pointers are
     host memory and are never touched)."""
-    lib = _lib()
-    mu0 = (ctypes.c_double * 4)() if sfx == "_f64" else (ctypes.c_float * 4)()
-    perm, count = (ctypes.c_int * 4)(), (ctypes.c_int * 1)()
-    args = dict(ncol=4, mu0=ctypes.cast(mu0, ctypes.c_void_p), pad_to=1, perm=ctypes.cast(perm, ctypes.c_void_p),
-                count=ctypes.cast(count, ctypes.c_void_p))
-    bad = {"negative_ncol": ("ncol", -1), "null_mu0": ("mu0", ctypes.c_void_p(0)), "null_perm": ("perm", ctypes.c_void_p(0)),
-           "null_count": ("count", ctypes.c_void_p(0)), "pad_to0": ("pad_to", 0)}[case]
-    args[bad[0]] = bad[1]
-    fn = getattr(lib, "rrx_sunlit_columns" + sfx)
-    fn.restype = ctypes.c_int
-    rc = fn(args["ncol"], args["mu0"], ctypes.c_void_p(0), args["pad_to"], args["perm"], args["count"], ctypes.c_void_p(0))
+    lib = abi.lib()
+    bad = {"negative_ncol": dict(ncol=-1), "null_mu0": dict(null=("order", "mu0")), "null_perm": dict(null=("order", "perm")),
+           "null_count": dict(null=("order", "count")), "pad_to0": dict(pad_to=0)}[case]
+    rc, msg = abi.call(lib, "rrx_sunlit_columns", sfx, **{**dict(null=("order",), ncol=4, pad_to=1), **bad})        # (no order: 0 .. ncol-1)
     assert rc != 0
-    msg = lib.rrx_last_error().decode()
     assert "rrx_sunlit_columns" + sfx in msg, msg
     assert {"negative_ncol": "ncol", "null_mu0": "mu0", "null_perm": "perm", "null_count": "count", "pad_to0": "pad_to"}[case] in msg, msg
 
@@ -62,24 +45,10 @@ def test_sunlit_columns_rejects_bad_arguments_without_a_gpu(sfx, case):
 @pytest.mark.parametrize("sfx", ["_f64", "_f32"])
 @pytest.mark.parametrize("case", ["negative_n", "n_above_src", "null_perm", "null_out"])
 def test_scatter_cols_fill_rejects_bad_arguments_without_a_gpu(sfx, case):
-    lib = _lib()
-    buf = (ctypes.c_double * 16)()
-    perm = (ctypes.c_int * 4)()
-    p = lambda a: ctypes.cast(a, ctypes.c_void_p)
-    # n, nrest, perm, ncol_src, in, ncol_dst, out
-    a = [2, ctypes.c_ulonglong(2), p(perm), 4, p(buf), 4, p(buf)]
-    if case == "negative_n":
-        a[0] = -1
-    elif case == "n_above_src":
-        a[0] = 5
-    elif case == "null_perm":
-        a[2] = ctypes.c_void_p(0)
-    else:
-        a[6] = ctypes.c_void_p(0)
-    fn = getattr(lib, "rrx_scatter_cols_fill" + sfx)
-    fn.restype = ctypes.c_int
-    assert fn(*a, ctypes.c_void_p(0)) != 0
-    msg = lib.rrx_last_error().decode()
+    lib = abi.lib()
+    bad = {"negative_n": dict(n=-1), "n_above_src": dict(n=5), "null_perm": dict(null=("perm",)), "null_out": dict(null=("out",))}[case]
+    rc, msg = abi.call(lib, "rrx_scatter_cols_fill", sfx, **{**dict(n=2, nrest=2, ncol_src=4, ncol_dst=4), **bad})
+    assert rc != 0
     assert "rrx_scatter_cols_fill" + sfx in msg, msg
 
 
@@ -88,7 +57,7 @@ def test_host_library_exports_set_sunlit_columns_and_the_driver_knows_the_flag()
     assert text.count("void set_sunlit_columns(const bool b)") == 1          # shortwave only
     if not os.path.exists(HOSTLIB):
         pytest.fail(f"{HOSTLIB} not built: run __graft_entry__.build()")
-    ctypes.CDLL(LIB)                      # (its dependency, by rpath; loaded here so the check does not depend on the loader path)
+    abi.lib()                             # (its dependency, by rpath; loaded here so the check does not depend on the loader path)
     host = ctypes.CDLL(HOSTLIB)
     assert hasattr(host, "rrx_cxx_sunlit_columns")
     syms = subprocess.run(["nm", "-DC", "--defined-only", HOSTLIB], capture_output=True, text=True).stdout
