@@ -32,6 +32,36 @@
 // -(g/cp) dF_net/dp with g = 9.80665 m s-2, cp = 1004.64 J kg-1 K-1 (dry air). flux_net, p_lev: (ncol, nlay+1); out: (ncol, nlay).
 void compute_heating_rate(const Array_gpu<Float,2>& flux_net, const Array_gpu<Float,2>& p_lev, Array_gpu<Float,2>& heating_rate);
 
+// ---- behind the two classes (Radiation_solver.cpp); not part of the argument lists a host model calls ----
+// The LW options of a solve_gpu call -- the solver's settings, the call's switches, n_bnd < n_gpt -- and what lw_solve_plan() makes of
+// them: it throws the refusal of a pair that is not available (the one table lw_refusals) or returns what the solve does. A pure host
+// function: solve_gpu reads the plan from there on, and rrx_host_selftest_lw_plan serves it to tests/test_host_lw_options.py.
+struct Lw_solve_options
+{
+    bool broadband_solvers, byband_solvers, jacobian; int n_gauss_angles; bool optimal_angles, lw_scattering, lw_rescaling, cloud_sampling;
+    bool switch_fluxes, switch_output_bnd_fluxes, switch_cloud_optics, fewer_bands_than_gpoints;
+};
+enum class Lw_form { per_gpoint, fractions, angles, optimal, byband, two_stream, rescaled };   // per_gpoint: the general kernel; else a fused form
+struct Lw_solve_plan
+{
+    Lw_form form;
+    bool broadband, byband, jac;    // in effect: the solvers sum the g-points; the by-band solver is in use; the Jacobian is formed
+    bool cloud_to_solver;           // the cloud goes to the solver as tau / ssa / g by band, the gas optics stay clear
+};
+Lw_solve_plan lw_solve_plan(const Lw_solve_options& o);
+
+// McICA cloud sampling of either solver (set_cloud_sampling): the borrowed fields, the seed and the columns' identities.
+struct Cloud_sampling
+{
+    const Array_gpu<Float,2>* frac = nullptr; const Array_gpu<Float,2>* alpha = nullptr;
+    uint64_t seed = 0; int col_offset = 0;
+    const int* col_id = nullptr;       // (a reordered solve: the identities of its columns, on the device)
+    bool on() const { return frac != nullptr; }
+    void set(const char* who, const Array_gpu<Float,2>* cloud_frac, const int overlap, const Array_gpu<Float,2>* overlap_param,
+             const uint64_t seed_in, const int col_offset_in);
+    void check(const char* who, const int n_col, const int n_lay, const bool cloud_optics) const;
+};
+
 class Radiation_solver_longwave
 {
     public:
@@ -82,16 +112,18 @@ class Radiation_solver_longwave
         // Not applied when optical properties are output (switch_output_optical).
         void set_column_sorting(const int mode) { column_sorting = mode; sort_decided = -1; }
         void set_column_padding(const bool b) { column_padding = b; }
+        // The options below do not all combine: solve_gpu throws for the pairs of the table lw_refusals in Radiation_solver.cpp
+        // (lw_solve_plan above), each with its reason.
         // Surface-temperature Jacobian of the upward flux (default off): with fluxes requested, solve_gpu also forms d flux_up /
         // d T_sfc [W m-2 K-1] per level from the same solve (the fused broadband solver's Jacobian form, or the general solver's
         // per-g-point Jacobians summed over the g-points); get_lw_flux_up_jac() returns the (ncol, nlev) result of the last solve in
         // the caller's column order. A host model updates flux_up (and flux_net) with it between radiation calls
-        // (rrx_lw_flux_up_adjust). Not with set_byband_solvers(true): solve_gpu throws.
+        // (rrx_lw_flux_up_adjust).
         void set_jacobian(const bool b) { jacobian = b; }
         const Array_gpu<Float,2>& get_lw_flux_up_jac() const { return lw_flux_up_jac; }
         // Quadrature angles of the LW solver (1..4 Gauss-Jacobi-5 nodes, default 1; throws otherwise). With the broadband solvers more
         // than one takes the several-angle form of the fused solver (rrx_lw_solver_noscat_fractions_angles, Jacobian included), the
-        // per-g-point solvers take the general kernel once per angle. Not with the by-band solvers in use: solve_gpu throws.
+        // per-g-point solvers take the general kernel once per angle.
         void set_gauss_angles(const int n)
         {
             if (n < 1 || n > 4) throw std::runtime_error("Radiation_solver_longwave::set_gauss_angles: " + std::to_string(n) + " is outside 1..4");
@@ -100,21 +132,17 @@ class Radiation_solver_longwave
         int get_gauss_angles() const { return n_gauss_angles; }
         // Optimal angles (default off): the secant of the one LW angle is the coefficient file's optimal_angle_fit of the column's
         // total optical depth per g-point (compute_optimal_angles / lw_Ds of current RTE+RRTMGP); with the broadband solvers the fused
-        // solver forms it itself (rrx_lw_solver_noscat_fractions_optimal). Throws for a file without the fit; solve_gpu throws with
-        // set_gauss_angles(> 1) or the by-band solvers in use.
+        // solver forms it itself (rrx_lw_solver_noscat_fractions_optimal). Throws for a file without the fit.
         void set_optimal_angles(const bool b);
         bool get_optimal_angles() const { return optimal_angles; }
         // LW cloud scattering (default off): solve_gpu takes the clear gas optics, the LW cloud tau / ssa / g by band from
         // Cloud_optics_gpu (with cloud optics in use; else ssa = 0) and the two-stream solver with scattering
-        // (Rte_lw_gpu::rte_lw_2stream, rrx_lw_solver_2stream_fractions). Broadband solvers only. solve_gpu throws with
-        // set_gauss_angles(> 1), set_optimal_angles, set_jacobian, the by-band solvers, or per-g-point / band flux output.
+        // (Rte_lw_gpu::rte_lw_2stream, rrx_lw_solver_2stream_fractions). Broadband solvers only.
         void set_lw_scattering(const bool b) { lw_scattering = b; }
         bool get_lw_scattering() const { return lw_scattering; }
         // LW rescaled scattering (default off): solve_gpu takes the clear gas optics, the LW cloud tau / ssa / g by band from
         // Cloud_optics_gpu (with cloud optics in use; else ssa = 0) and the no-scattering solver on rescaled optical depths with one
-        // correction sweep (Rte_lw_gpu::rte_lw_rescaled, rrx_lw_solver_noscat_fractions_rescaled). Broadband solvers only. solve_gpu
-        // throws with set_lw_scattering, set_gauss_angles(> 1), set_optimal_angles, set_jacobian, the by-band solvers, or per-g-point /
-        // band flux output.
+        // correction sweep (Rte_lw_gpu::rte_lw_rescaled, rrx_lw_solver_noscat_fractions_rescaled). Broadband solvers only.
         void set_lw_rescaling(const bool b) { lw_rescaling = b; }
         bool get_lw_rescaling() const { return lw_rescaling; }
         // McICA cloud sampling (default off): with cloud optics in use, solve_gpu runs the CLEAR gas optics and then
@@ -124,17 +152,12 @@ class Radiation_solver_longwave
         // BORROWED: they stay the caller's, are read at every solve (update them in place) and must outlive the solves; nullptr as
         // cloud_frac turns the sampling off. The mask is redrawn at every solve from `seed` (call again to advance it; domain 0). A
         // column's draws are keyed by col_offset + its index in the caller's arrays and follow it through the column blocks, the
-        // device sort and the padding. solve_gpu throws without cloud optics, with set_lw_scattering or with set_lw_rescaling (those
-        // solvers combine the band clouds themselves).
+        // device sort and the padding. solve_gpu throws without cloud optics.
         void set_cloud_sampling(const Array_gpu<Float,2>* cloud_frac, const int overlap, const Array_gpu<Float,2>* overlap_param,
                                 const uint64_t seed, const int col_offset = 0);
 
     private:
-        const Array_gpu<Float,2>* mcica_frac = nullptr;
-        const Array_gpu<Float,2>* mcica_alpha = nullptr;
-        uint64_t mcica_seed = 0;
-        int mcica_col_offset = 0;
-        const int* mcica_col_id = nullptr;       // (a reordered solve: the identities of its columns, on the device)
+        Cloud_sampling mcica;
         int column_sorting = -1, sort_decided = -1;
         bool column_padding = true, reordered_call = false, jacobian = false, optimal_angles = false, lw_scattering = false, lw_rescaling = false;
         int n_gauss_angles = 1;
@@ -227,11 +250,7 @@ class Radiation_solver_shortwave
         void set_spherical_mu0(const Array_gpu<Float,2>* alt_lay, const Array_gpu<Float,1>* ref_alt = nullptr, const Float planet_radius = Float(6.37123e6));
 
     private:
-        const Array_gpu<Float,2>* mcica_frac = nullptr;
-        const Array_gpu<Float,2>* mcica_alpha = nullptr;
-        uint64_t mcica_seed = 0;
-        int mcica_col_offset = 0;
-        const int* mcica_col_id = nullptr;       // (a reordered solve: the identities of its columns, on the device)
+        Cloud_sampling mcica;
         const Array_gpu<Float,2>* sph_alt = nullptr;
         const Array_gpu<Float,1>* sph_ref_alt = nullptr;
         Float sph_radius = Float(6.37123e6);

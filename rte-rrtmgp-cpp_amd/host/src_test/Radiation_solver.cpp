@@ -251,20 +251,18 @@ namespace
     // copies and the columns' identities (perm + offset) for the duration of the inner solve, and put back afterwards.
     struct Sampling_reordered
     {
-        const Array_gpu<Float,2>*& frac; const Array_gpu<Float,2>*& alpha; const int*& col_id;
-        const Array_gpu<Float,2>* frac0; const Array_gpu<Float,2>* alpha0; const int* col_id0;
+        Cloud_sampling& s; const Cloud_sampling s0;
         Array_gpu<Float,2> frac_r, alpha_r; Array_gpu<int,1> ids;
-        Sampling_reordered(const Array_gpu<Float,2>*& f, const Array_gpu<Float,2>*& a, const int*& id, const int offset, const Column_order& co) :
-            frac(f), alpha(a), col_id(id), frac0(f), alpha0(a), col_id0(id)
+        Sampling_reordered(Cloud_sampling& s_, const Column_order& co) : s(s_), s0(s_)
         {
-            if (frac0 == nullptr) return;
-            frac_r = co.in2(*frac0); frac = &frac_r;
-            if (alpha0 != nullptr) { alpha_r = co.in2(*alpha0); alpha = &alpha_r; }
+            if (!s0.on()) return;
+            frac_r = co.in2(*s0.frac); s.frac = &frac_r;
+            if (s0.alpha != nullptr) { alpha_r = co.in2(*s0.alpha); s.alpha = &alpha_r; }
             ids.set_dims({co.n_out});
-            rrx_host::check(rrx_mcica_column_ids(co.n_out, co.perm.ptr(), offset, ids.ptr(), rrx_host::current_stream()));
-            col_id = ids.ptr();
+            rrx_host::check(rrx_mcica_column_ids(co.n_out, co.perm.ptr(), s0.col_offset, ids.ptr(), rrx_host::current_stream()));
+            s.col_id = ids.ptr();
         }
-        ~Sampling_reordered() { frac = frac0; alpha = alpha0; col_id = col_id0; }
+        ~Sampling_reordered() { s = s0; }
     };
 
     // The borrowed altitude fields of a reordered shortwave solve (set_spherical_mu0): replaced by their gathered copies for the
@@ -283,14 +281,139 @@ namespace
         ~Altitudes_reordered() { alt = alt0; ref = ref0; }
     };
 
-    void check_cloud_sampling(const char* who, const Array_gpu<Float,2>* frac, const Array_gpu<Float,2>* alpha, const int n_col, const int n_lay,
-                              const bool cloud_optics)
+    // Marks the inner solve of a reordered one, which takes its columns as they come.
+    struct Guard { bool& f; Guard(bool& f_) : f(f_) { f = true; } ~Guard() { f = false; } };
+
+    // One column block of a solve: columns col_s .. col_s + n_in - 1 (1-based) of the caller's n_col. A single block (whole) views the
+    // caller's arrays and gases -- no gather of the inputs, no device copies of the mixing-ratio fields -- and any other gets copies of
+    // its columns.
+    struct Block
     {
-        const std::string w(who);
-        if (!cloud_optics) throw std::runtime_error(w + ": cloud sampling (set_cloud_sampling) needs cloud optics: it samples their band properties");
-        if (frac->dim(1) != n_col || frac->dim(2) != n_lay) throw std::runtime_error(w + ": set_cloud_sampling: cloud_frac is not (ncol, nlay)");
-        if (alpha != nullptr && n_lay > 1 && (alpha->dim(1) != n_col || alpha->dim(2) != n_lay-1))
-            throw std::runtime_error(w + ": set_cloud_sampling: overlap_param is not (ncol, nlay-1)");
+        int n_col, col_s, n_in;
+        bool whole;
+        std::unique_ptr<Gas_concs_gpu> gases_copy;
+        const Gas_concs_gpu& gases;
+        Block(const int n_col_, const std::pair<int,int>& b, const Gas_concs_gpu& all) :
+            n_col(n_col_), col_s(b.first), n_in(b.second), whole(b.second == n_col_),
+            gases_copy(whole ? nullptr : std::make_unique<Gas_concs_gpu>(all, col_s, n_in)), gases(whole ? all : *gases_copy) {}
+        int col_e() const { return col_s + n_in - 1; }
+        Array_gpu<Float,1> sub1(const Array_gpu<Float,1>& a) const
+        { return whole ? Array_gpu<Float,1>(const_cast<Float*>(a.ptr()), {n_in}) : a.subset({{ {col_s, col_e()} }}); }
+        // (col, n2)
+        Array_gpu<Float,2> sub2(const Array_gpu<Float,2>& a, const int n2) const
+        { return whole ? Array_gpu<Float,2>(const_cast<Float*>(a.ptr()), {n_in, n2}) : a.subset({{ {col_s, col_e()}, {1, n2} }}); }
+        // (n_bnd, col)
+        Array_gpu<Float,2> sub_last(const Array_gpu<Float,2>& a, const int n_bnd) const
+        { return whole ? Array_gpu<Float,2>(const_cast<Float*>(a.ptr()), {n_bnd, n_in}) : a.subset({{ {1, n_bnd}, {col_s, col_e()} }}); }
+        // the caller's dry-air column amounts, or those of the block's water vapour and pressures
+        Array_gpu<Float,2> col_dry(const Array_gpu<Float,2>& col_dry, const Array_gpu<Float,2>& p_lev_s, const int n_lay) const
+        {
+            Array_gpu<Float,2> col_dry_s({n_in, n_lay});
+            if (col_dry.size() == 0)
+                Gas_optics_rrtmgp_gpu::get_col_dry(col_dry_s, gases.get_vmr("h2o"), p_lev_s);
+            else
+                col_dry_s = sub2(col_dry, n_lay);
+            return col_dry_s;
+        }
+    };
+
+    // Flux arrays, broadband (col, lev) and by band (col, lev, bnd), in the order of the solve_gpu argument lists: up, dn[, dn_dir], net.
+    template<typename A2, typename A3> struct Flux_set { std::vector<A2> bb; std::vector<A3> bnd; };
+    using Flux_arrays = Flux_set<Array_gpu<Float,2>, Array_gpu<Float,3>>;        // arrays of a solve's own
+    struct Flux_outputs : Flux_set<Array_gpu<Float,2>*, Array_gpu<Float,3>*>     // the caller's
+    {
+        int n_col, n_lev, n_bnd;
+        void allocate_bb() const { for (Array_gpu<Float,2>* a : bb) if (a->size() == 0) a->set_dims({n_col, n_lev}); }
+        void allocate_bnd() const { for (Array_gpu<Float,3>* a : bnd) if (a->size() == 0) a->set_dims({n_col, n_lev, n_bnd}); }
+        // a reordered solve: its output arrays on n_out columns, and their way back into the caller's
+        Flux_arrays reordered(const int n_out, const bool with_bnd) const
+        {
+            Flux_arrays r{std::vector<Array_gpu<Float,2>>(bb.size()), std::vector<Array_gpu<Float,3>>(bnd.size())};
+            for (auto& a : r.bb) a.set_dims({n_out, n_lev});
+            if (with_bnd) for (auto& a : r.bnd) a.set_dims({n_out, n_lev, n_bnd});
+            return r;
+        }
+        void from_reordered(const Column_order& co, const Flux_arrays& r, const bool with_bnd) const
+        {
+            for (size_t i=0; i<bb.size(); ++i) co.out(*bb[i], r.bb[i]);
+            if (with_bnd) for (size_t i=0; i<bnd.size(); ++i) co.out(*bnd[i], r.bnd[i]);
+        }
+        // a sunlit-only solve without sunlit columns
+        void zeros(const Column_order& co, const bool with_bnd) const
+        {
+            for (Array_gpu<Float,2>* a : bb) co.zeros<2>(*a, {n_col, n_lev});
+            if (with_bnd) for (Array_gpu<Float,3>* a : bnd) co.zeros<3>(*a, {n_col, n_lev, n_bnd});
+        }
+        // a block's arrays into its columns of the caller's: the three- and four-array get_from_subset
+        void from_block(const Block& b, const std::vector<const Float*>& s) const
+        {
+            if (s.size() == 3) Subset_kernels_cuda::get_from_subset(n_col, n_lev, b.n_in, b.col_s, bb[0]->ptr(), bb[1]->ptr(), bb[2]->ptr(), s[0], s[1], s[2]);
+            else Subset_kernels_cuda::get_from_subset(n_col, n_lev, b.n_in, b.col_s, bb[0]->ptr(), bb[1]->ptr(), bb[2]->ptr(), bb[3]->ptr(), s[0], s[1], s[2], s[3]);
+        }
+        void bnd_from_block(const Block& b, const std::vector<const Float*>& s) const
+        {
+            if (s.size() == 3) Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_bnd, b.n_in, b.col_s, bnd[0]->ptr(), bnd[1]->ptr(), bnd[2]->ptr(), s[0], s[1], s[2]);
+            else Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_bnd, b.n_in, b.col_s, bnd[0]->ptr(), bnd[1]->ptr(), bnd[2]->ptr(), bnd[3]->ptr(), s[0], s[1], s[2], s[3]);
+        }
+        // The general tail of a block: the g-point fluxes of the workspace (dir: null in the longwave) reduced to broadband and, where
+        // asked for, band fluxes, and copied into the block's columns of the caller's arrays.
+        void reduce_block(const Block& b, const bool with_bnd, const Array_gpu<Float,3>& up, const Array_gpu<Float,3>& dn, const Array_gpu<Float,3>* dir,
+                          const std::unique_ptr<Optical_props_arry_gpu>& optical_props, const Bool top_at_1) const
+        {
+            Fluxes_broadband_gpu fluxes(b.n_in, n_lev);
+            if (dir == nullptr) fluxes.reduce(up, dn, optical_props, top_at_1); else fluxes.reduce(up, dn, *dir, optical_props, top_at_1);
+            if (dir == nullptr) from_block(b, {fluxes.get_flux_up().ptr(), fluxes.get_flux_dn().ptr(), fluxes.get_flux_net().ptr()});
+            else from_block(b, {fluxes.get_flux_up().ptr(), fluxes.get_flux_dn().ptr(), fluxes.get_flux_dn_dir().ptr(), fluxes.get_flux_net().ptr()});
+            if (!with_bnd) return;
+            Fluxes_byband_gpu bnd_fluxes(b.n_in, n_lev, n_bnd);
+            if (dir == nullptr) bnd_fluxes.reduce(up, dn, optical_props, top_at_1); else bnd_fluxes.reduce(up, dn, *dir, optical_props, top_at_1);
+            if (dir == nullptr) bnd_from_block(b, {bnd_fluxes.get_bnd_flux_up().ptr(), bnd_fluxes.get_bnd_flux_dn().ptr(), bnd_fluxes.get_bnd_flux_net().ptr()});
+            else bnd_from_block(b, {bnd_fluxes.get_bnd_flux_up().ptr(), bnd_fluxes.get_bnd_flux_dn().ptr(), bnd_fluxes.get_bnd_flux_dn_dir().ptr(),
+                                    bnd_fluxes.get_bnd_flux_net().ptr()});
+        }
+    };
+
+    // What the by-band solver of one block writes, as views in the order of Flux_outputs: the caller's arrays for a single block, else
+    // block arrays -- the workspace's band slabs `ws_bnd` for all but the band net flux -- that finish() copies into place.
+    struct Byband_block : Flux_arrays
+    {
+        Flux_arrays blk;
+        Byband_block(const Block& b, const Flux_outputs& out, const std::vector<Array_gpu<Float,3>*>& ws_bnd)
+        {
+            out.allocate_bb(); out.allocate_bnd();
+            const size_t n = out.bb.size();
+            if (!b.whole)
+            {
+                blk.bnd.resize(1); blk.bnd[0].set_dims({b.n_in, out.n_lev, out.n_bnd});
+                blk.bb.resize(n); for (auto& a : blk.bb) a.set_dims({b.n_in, out.n_lev});
+            }
+            for (size_t i=0; i<n; ++i)
+            {
+                Float* band = b.whole ? out.bnd[i]->ptr() : (i+1 < n ? ws_bnd[i]->ptr() : blk.bnd[0].ptr());
+                bnd.emplace_back(band, std::array<int,3>{b.n_in, out.n_lev, out.n_bnd});
+                bb.emplace_back(b.whole ? out.bb[i]->ptr() : blk.bb[i].ptr(), std::array<int,2>{b.n_in, out.n_lev});
+            }
+        }
+        // the broadband net flux from the solver's up and dn; the block arrays into the caller's
+        void finish(const Block& b, const Flux_outputs& out)
+        {
+            Fluxes_kernels_cuda::net_broadband_precalc(b.n_in, out.n_lev, bb[1].ptr(), bb[0].ptr(), bb.back().ptr());
+            if (b.whole) return;
+            std::vector<const Float*> s2, s3;
+            for (const auto& a : bb) s2.push_back(a.ptr());
+            for (const auto& a : bnd) s3.push_back(a.ptr());
+            out.from_block(b, s2); out.bnd_from_block(b, s3);
+        }
+    };
+
+    // The sub-columns of one block (rrx_mcica_increment_1scalar / _2stream): `launch` gets the arguments the two domains share.
+    template<typename Launch> void sample_clouds(const Cloud_sampling& s, const Block& b, const int n_lay, const int n_gpt, const int n_bnd,
+                                                 const int* band_lims_gpt, const int domain, Launch&& launch)
+    {
+        const Array_gpu<Float,2> frac_s = b.sub2(*s.frac, n_lay);
+        const Array_gpu<Float,2> alpha_s = (s.alpha != nullptr && n_lay > 1) ? b.sub2(*s.alpha, n_lay-1) : Array_gpu<Float,2>();
+        launch(b.n_in, n_lay, n_gpt, n_bnd, band_lims_gpt, frac_s.ptr(), s.alpha != nullptr ? alpha_s.ptr() : nullptr, (unsigned long long)s.seed, domain,
+               s.col_id != nullptr ? s.col_id + (b.col_s-1) : nullptr, s.col_offset + b.col_s-1);
     }
 
     // Should this solve reorder its columns, and how? `sort_decided` caches the automatic decision of the solver object.
@@ -354,15 +477,95 @@ Radiation_solver_longwave::Radiation_solver_longwave(
         this->cloud_optics_gpu = std::make_unique<Cloud_optics_gpu>(load_and_init_cloud_optics(file_name_cloud));
 }
 
+void Cloud_sampling::set(const char* who, const Array_gpu<Float,2>* cloud_frac, const int overlap, const Array_gpu<Float,2>* overlap_param,
+                         const uint64_t seed_in, const int col_offset_in)
+{
+    const std::string w = std::string(who) + "::set_cloud_sampling: ";
+    if (overlap != 0 && overlap != 1)
+        throw std::runtime_error(w + "overlap " + std::to_string(overlap) + " is not 0 (maximum-random) or 1 (exponential-random)");
+    if (cloud_frac != nullptr && overlap == 1 && overlap_param == nullptr)
+        throw std::runtime_error(w + "exponential-random overlap needs overlap_param");
+    frac = cloud_frac; alpha = (cloud_frac != nullptr && overlap == 1) ? overlap_param : nullptr;
+    seed = seed_in; col_offset = col_offset_in;
+}
+
+void Cloud_sampling::check(const char* who, const int n_col, const int n_lay, const bool cloud_optics) const
+{
+    const std::string w(who);
+    if (!cloud_optics) throw std::runtime_error(w + ": cloud sampling (set_cloud_sampling) needs cloud optics: it samples their band properties");
+    if (frac->dim(1) != n_col || frac->dim(2) != n_lay) throw std::runtime_error(w + ": set_cloud_sampling: cloud_frac is not (ncol, nlay)");
+    if (alpha != nullptr && n_lay > 1 && (alpha->dim(1) != n_col || alpha->dim(2) != n_lay-1))
+        throw std::runtime_error(w + ": set_cloud_sampling: overlap_param is not (ncol, nlay-1)");
+}
+
 void Radiation_solver_longwave::set_cloud_sampling(const Array_gpu<Float,2>* cloud_frac, const int overlap, const Array_gpu<Float,2>* overlap_param,
                                                    const uint64_t seed, const int col_offset)
+{ mcica.set("Radiation_solver_longwave", cloud_frac, overlap, overlap_param, seed, col_offset); }
+
+// ---- the LW options of the class API: what a solve_gpu call does, or why it is refused ----
+namespace
 {
-    if (overlap != 0 && overlap != 1)
-        throw std::runtime_error("Radiation_solver_longwave::set_cloud_sampling: overlap " + std::to_string(overlap) + " is not 0 (maximum-random) or 1 (exponential-random)");
-    if (cloud_frac != nullptr && overlap == 1 && overlap_param == nullptr)
-        throw std::runtime_error("Radiation_solver_longwave::set_cloud_sampling: exponential-random overlap needs overlap_param");
-    mcica_frac = cloud_frac; mcica_alpha = (cloud_frac != nullptr && overlap == 1) ? overlap_param : nullptr;
-    mcica_seed = seed; mcica_col_offset = col_offset;
+    // An option as the refusals see it. Some look at the solver's setting, some at what the call makes of it (`in use`): the by-band
+    // solvers and the Jacobian come in both kinds, and each row below says which one it means.
+    enum Lw_option { jacobian_in_use, jacobian_set, byband_in_use, byband_set, several_angles, optimal, scattering, rescaling,
+                     no_broadband_fluxes, sampling, n_lw_options };
+    const char* const lw_option_name[n_lw_options] = {
+        "the Jacobian (set_jacobian)", "the Jacobian (set_jacobian)", "the by-band solvers (set_byband_solvers)", "the by-band solvers (set_byband_solvers)",
+        "several quadrature angles (set_gauss_angles)", "optimal angles (set_optimal_angles)", "LW scattering (set_lw_scattering)",
+        "LW rescaling (set_lw_rescaling)", "the broadband solvers (set_broadband_solvers) without band flux output", "cloud sampling (set_cloud_sampling)"};
+    // `option` is (are) not available with `other`; with no_broadband_fluxes as the other: `option` needs the broadband solvers ...
+    struct Lw_refusal { Lw_option option, other; const char* reason; };
+    const Lw_refusal lw_refusals[] = {
+        {jacobian_in_use, byband_set,          "no by-band Jacobians"},
+        {several_angles,  byband_in_use,       "the by-band solver has one angle"},
+        {optimal,         several_angles,      "optimal angles are one angle"},
+        {optimal,         byband_set,          "the by-band solver has the fixed angle"},
+        {scattering,      several_angles,      "the two-stream solver has no angles"},
+        {scattering,      optimal,             "the two-stream solver has no angles"},
+        {scattering,      jacobian_set,        "no Jacobian form of the two-stream solver"},
+        {scattering,      byband_set,          "no by-band form of the two-stream solver"},
+        {scattering,      no_broadband_fluxes, "the two-stream solver gives broadband fluxes"},
+        {rescaling,       scattering,          "one treatment of cloud scattering at a time"},
+        {rescaling,       several_angles,      "the fused rescaled solver has one angle"},
+        {rescaling,       optimal,             "the fused rescaled solver has the fixed angle"},
+        {rescaling,       jacobian_set,        "no Jacobian form of the fused rescaled solver"},
+        {rescaling,       byband_set,          "no by-band form of the rescaled solver"},
+        {rescaling,       no_broadband_fluxes, "the fused rescaled solver gives broadband fluxes"},
+        {sampling,        scattering,          "the two-stream solver combines the band clouds itself"},
+        {sampling,        rescaling,           "the rescaled solver combines the band clouds itself"}};
+}
+
+Lw_solve_plan lw_solve_plan(const Lw_solve_options& o)
+{
+    Lw_solve_plan p;
+    p.broadband = o.broadband_solvers && !o.switch_output_bnd_fluxes;
+    p.byband = o.byband_solvers && o.switch_output_bnd_fluxes && o.switch_fluxes && o.fewer_bands_than_gpoints;
+    p.jac = o.jacobian && o.switch_fluxes;
+    p.cloud_to_solver = (o.lw_scattering || o.lw_rescaling) && o.switch_fluxes;
+
+    bool on[n_lw_options];
+    on[jacobian_in_use] = p.jac;                    on[jacobian_set] = o.jacobian;
+    on[byband_in_use] = p.byband;                   on[byband_set] = o.byband_solvers;
+    on[several_angles] = o.n_gauss_angles > 1;      on[optimal] = o.optimal_angles;
+    on[scattering] = o.lw_scattering;               on[rescaling] = o.lw_rescaling;
+    on[no_broadband_fluxes] = o.switch_fluxes && !p.broadband;
+    on[sampling] = o.cloud_sampling;
+    for (const Lw_refusal& r : lw_refusals)
+        if (on[r.option] && on[r.other])
+        {
+            const bool plural = r.option == several_angles || r.option == optimal;
+            throw std::runtime_error(std::string("Radiation_solver_longwave: ") + lw_option_name[r.option] +
+                                     (r.other == no_broadband_fluxes ? " needs " : plural ? " are not available with " : " is not available with ") +
+                                     lw_option_name[r.other] + ": " + r.reason);
+        }
+
+    if (p.byband) p.form = Lw_form::byband;
+    else if (o.lw_rescaling && o.switch_fluxes) p.form = Lw_form::rescaled;
+    else if (p.cloud_to_solver) p.form = Lw_form::two_stream;
+    else if (o.optimal_angles) p.form = Lw_form::optimal;
+    else if (!p.broadband) p.form = Lw_form::per_gpoint;
+    else p.form = o.n_gauss_angles > 1 ? Lw_form::angles : Lw_form::fractions;
+    return p;
 }
 
 void Radiation_solver_longwave::set_optimal_angles(const bool b)
@@ -396,70 +599,16 @@ void Radiation_solver_longwave::solve_gpu(
     const int n_bnd = this->kdist_gpu->get_nband();
     const Bool top_at_1 = (vertical_ordering < 0) ? Bool(p_lay({1, 1}) < p_lay({1, n_lay})) : Bool(vertical_ordering == 1);
     if (switch_cloud_optics && !cloud_optics_gpu) throw std::runtime_error("cloud optics requested but no cloud coefficients loaded");
-    const bool broadband = broadband_solvers && !switch_output_bnd_fluxes;
-    // by-band solvers: the band sums come straight out of the fused solver (one slab per band in the block workspace)
-    const bool byband = byband_solvers && switch_output_bnd_fluxes && switch_fluxes && n_bnd < n_gpt;
-    const bool jac = jacobian && switch_fluxes;
-    if (jac && byband_solvers)
-        throw std::runtime_error("Radiation_solver_longwave: the Jacobian (set_jacobian) is not available with the by-band solvers "
-                                 "(set_byband_solvers): no by-band Jacobians");
-    if (byband && n_gauss_angles > 1)
-        throw std::runtime_error("Radiation_solver_longwave: several quadrature angles (set_gauss_angles) are not available with the "
-                                 "by-band solvers (set_byband_solvers): the by-band solver has one angle");
-    if (optimal_angles && n_gauss_angles > 1)
-        throw std::runtime_error("Radiation_solver_longwave: optimal angles (set_optimal_angles) are not available with several "
-                                 "quadrature angles (set_gauss_angles): optimal angles are one angle");
-    if (optimal_angles && byband_solvers)
-        throw std::runtime_error("Radiation_solver_longwave: optimal angles (set_optimal_angles) are not available with the by-band "
-                                 "solvers (set_byband_solvers): the by-band solver has the fixed angle");
-    if (lw_scattering && n_gauss_angles > 1)
-        throw std::runtime_error("Radiation_solver_longwave: LW scattering (set_lw_scattering) is not available with several quadrature "
-                                 "angles (set_gauss_angles): the two-stream solver has no angles");
-    if (lw_scattering && optimal_angles)
-        throw std::runtime_error("Radiation_solver_longwave: LW scattering (set_lw_scattering) is not available with optimal angles "
-                                 "(set_optimal_angles): the two-stream solver has no angles");
-    if (lw_scattering && jacobian)
-        throw std::runtime_error("Radiation_solver_longwave: LW scattering (set_lw_scattering) is not available with the Jacobian "
-                                 "(set_jacobian): no Jacobian form of the two-stream solver");
-    if (lw_scattering && byband_solvers)
-        throw std::runtime_error("Radiation_solver_longwave: LW scattering (set_lw_scattering) is not available with the by-band "
-                                 "solvers (set_byband_solvers): no by-band form of the two-stream solver");
-    if (lw_scattering && switch_fluxes && !broadband)
-        throw std::runtime_error("Radiation_solver_longwave: LW scattering (set_lw_scattering) needs the broadband solvers "
-                                 "(set_broadband_solvers) without band flux output: the two-stream solver gives broadband fluxes");
-    if (lw_rescaling && lw_scattering)
-        throw std::runtime_error("Radiation_solver_longwave: LW rescaling (set_lw_rescaling) is not available with LW scattering "
-                                 "(set_lw_scattering): one treatment of cloud scattering at a time");
-    if (lw_rescaling && n_gauss_angles > 1)
-        throw std::runtime_error("Radiation_solver_longwave: LW rescaling (set_lw_rescaling) is not available with several quadrature "
-                                 "angles (set_gauss_angles): the fused rescaled solver has one angle");
-    if (lw_rescaling && optimal_angles)
-        throw std::runtime_error("Radiation_solver_longwave: LW rescaling (set_lw_rescaling) is not available with optimal angles "
-                                 "(set_optimal_angles): the fused rescaled solver has the fixed angle");
-    if (lw_rescaling && jacobian)
-        throw std::runtime_error("Radiation_solver_longwave: LW rescaling (set_lw_rescaling) is not available with the Jacobian "
-                                 "(set_jacobian): no Jacobian form of the fused rescaled solver");
-    if (lw_rescaling && byband_solvers)
-        throw std::runtime_error("Radiation_solver_longwave: LW rescaling (set_lw_rescaling) is not available with the by-band "
-                                 "solvers (set_byband_solvers): no by-band form of the rescaled solver");
-    if (lw_rescaling && switch_fluxes && !broadband)
-        throw std::runtime_error("Radiation_solver_longwave: LW rescaling (set_lw_rescaling) needs the broadband solvers "
-                                 "(set_broadband_solvers) without band flux output: the fused rescaled solver gives broadband fluxes");
-    const bool mcica = mcica_frac != nullptr;
-    if (mcica && lw_scattering)
-        throw std::runtime_error("Radiation_solver_longwave: cloud sampling (set_cloud_sampling) is not available with LW scattering "
-                                 "(set_lw_scattering): the two-stream solver combines the band clouds itself");
-    if (mcica && lw_rescaling)
-        throw std::runtime_error("Radiation_solver_longwave: cloud sampling (set_cloud_sampling) is not available with LW rescaling "
-                                 "(set_lw_rescaling): the rescaled solver combines the band clouds itself");
-    if (mcica) check_cloud_sampling("Radiation_solver_longwave", mcica_frac, mcica_alpha, n_col, n_lay, switch_cloud_optics);
-    const bool resc = lw_rescaling && switch_fluxes;
-    const bool scat = (lw_scattering || lw_rescaling) && switch_fluxes;      // the cloud goes to the solver as tau / ssa / g by band
-    if (jac && (lw_flux_up_jac.dim(1) != n_col || lw_flux_up_jac.dim(2) != n_lev))
+    // (throws what is not available: the one table of refusals)
+    const Lw_solve_plan plan = lw_solve_plan({broadband_solvers, byband_solvers, jacobian, n_gauss_angles, optimal_angles, lw_scattering, lw_rescaling,
+                                              mcica.on(), switch_fluxes, switch_output_bnd_fluxes, switch_cloud_optics, n_bnd < n_gpt});
+    if (mcica.on()) mcica.check("Radiation_solver_longwave", n_col, n_lay, switch_cloud_optics);
+    if (plan.jac && (lw_flux_up_jac.dim(1) != n_col || lw_flux_up_jac.dim(2) != n_lev))
     {
         lw_flux_up_jac = Array_gpu<Float,2>();
         lw_flux_up_jac.set_dims({n_col, n_lev});
     }
+    const Flux_outputs out{{{&lw_flux_up, &lw_flux_dn, &lw_flux_net}, {&lw_bnd_flux_up, &lw_bnd_flux_dn, &lw_bnd_flux_net}}, n_col, n_lev, n_bnd};
 
     // columns in another order / on a padded count: gather the inputs, solve, scatter the fluxes back (see the header)
     if (!reordered_call && !switch_output_optical && switch_fluxes)
@@ -469,17 +618,15 @@ void Radiation_solver_longwave::solve_gpu(
         {
             const Gas_concs_gpu gases = gas_concs.gathered(co.perm, n_col, co.n_out);
             Array_gpu<Float,3> no3a, no3b, no3c; Array_gpu<Float,2> no2;
-            Array_gpu<Float,2> up, dn, net; Array_gpu<Float,3> bup, bdn, bnet;
-            up.set_dims({co.n_out, n_lev}); dn.set_dims({co.n_out, n_lev}); net.set_dims({co.n_out, n_lev});
-            if (switch_output_bnd_fluxes) { bup.set_dims({co.n_out, n_lev, n_bnd}); bdn.set_dims({co.n_out, n_lev, n_bnd}); bnet.set_dims({co.n_out, n_lev, n_bnd}); }
-            struct Guard { bool& f; Guard(bool& f_) : f(f_) { f = true; } ~Guard() { f = false; } } guard(reordered_call);
-            Sampling_reordered sampling(mcica_frac, mcica_alpha, mcica_col_id, mcica_col_offset, co);
+            Flux_arrays r = out.reordered(co.n_out, switch_output_bnd_fluxes);
+            Guard guard(reordered_call);
+            Sampling_reordered sampling(mcica, co);
             this->solve_gpu(switch_fluxes, switch_cloud_optics, switch_output_optical, switch_output_bnd_fluxes, gases,
                             co.in2(p_lay), co.in2(p_lev), co.in2(t_lay), co.in2(t_lev), co.in2(col_dry), co.in1(t_sfc), co.in_last(emis_sfc),
-                            co.in2(lwp), co.in2(iwp), co.in2(rel), co.in2(dei), no3a, no3b, no3c, no2, up, dn, net, bup, bdn, bnet);
-            co.out(lw_flux_up, up); co.out(lw_flux_dn, dn); co.out(lw_flux_net, net);
-            if (switch_output_bnd_fluxes) { co.out(lw_bnd_flux_up, bup); co.out(lw_bnd_flux_dn, bdn); co.out(lw_bnd_flux_net, bnet); }
-            if (jac)
+                            co.in2(lwp), co.in2(iwp), co.in2(rel), co.in2(dei), no3a, no3b, no3c, no2,
+                            r.bb[0], r.bb[1], r.bb[2], r.bnd[0], r.bnd[1], r.bnd[2]);
+            out.from_reordered(co, r, switch_output_bnd_fluxes);
+            if (plan.jac)
             {
                 // (the inner solve left its (n_out, n_lev) Jacobian in lw_flux_up_jac)
                 const Array_gpu<Float,2> jac_r = std::move(lw_flux_up_jac);
@@ -491,74 +638,60 @@ void Radiation_solver_longwave::solve_gpu(
         }
     }
 
+    const bool cloud_1scl = switch_cloud_optics && !plan.cloud_to_solver, cloud_2str = switch_cloud_optics && plan.cloud_to_solver;
     auto prepare = [&](std::shared_ptr<Workspace>& ws, const int n)
     {
-        if (!ws || ws->n_col != n || ws->n_lay != n_lay || ws->broadband != broadband || ws->byband != byband || ws->jacobian != jac)
+        if (!ws || ws->n_col != n || ws->n_lay != n_lay || ws->broadband != plan.broadband || ws->byband != plan.byband || ws->jacobian != plan.jac)
         {
             ws = std::make_shared<Workspace>();
-            ws->n_col = n; ws->n_lay = n_lay; ws->broadband = broadband; ws->byband = byband; ws->jacobian = jac;
+            ws->n_col = n; ws->n_lay = n_lay; ws->broadband = plan.broadband; ws->byband = plan.byband; ws->jacobian = plan.jac;
             ws->optical_props = std::make_unique<Optical_props_1scl_gpu>(n, n_lay, *kdist_gpu);
             ws->sources = std::make_unique<Source_func_lw_gpu>(n, n_lay, *kdist_gpu);
             // broadband and by-band solvers: Planck fractions instead of the two source arrays (they are materialised on demand,
             // e.g. for --output-optical)
-            ws->sources->enable_planck_lite(broadband || byband);
-            const int ng = broadband ? 1 : (byband ? n_bnd : n_gpt);
+            ws->sources->enable_planck_lite(plan.broadband || plan.byband);
+            const int ng = plan.broadband ? 1 : (plan.byband ? n_bnd : n_gpt);
             ws->gpt_flux_up.set_dims({n, n_lev, ng});
             ws->gpt_flux_dn.set_dims({n, n_lev, ng});
-            if (jac)
+            if (plan.jac)
             {
                 ws->gpt_flux_up_jac.set_dims({n, n_lev, ng});
-                if (!broadband) ws->flux_up_jac.set_dims({n, n_lev});
+                if (!plan.broadband) ws->flux_up_jac.set_dims({n, n_lev});
             }
         }
-        if (switch_cloud_optics && !scat && !ws->cloud_optical_props)
+        if (cloud_1scl && !ws->cloud_optical_props)
             ws->cloud_optical_props = std::make_unique<Optical_props_1scl_gpu>(n, n_lay, *cloud_optics_gpu);
-        if (switch_cloud_optics && scat && !ws->cloud_optical_props_2str)
+        if (cloud_2str && !ws->cloud_optical_props_2str)
             ws->cloud_optical_props_2str = std::make_unique<Optical_props_2str_gpu>(n, n_lay, *cloud_optics_gpu);
     };
 
-    for (const auto& blk : column_blocks(n_col, std::max(1, n_col_block)))
+    for (const auto& columns : column_blocks(n_col, std::max(1, n_col_block)))
     {
-        const int col_s = blk.first, n_in = blk.second, col_e = col_s + n_in - 1;
+        const int col_s = columns.first, n_in = columns.second;
         std::shared_ptr<Workspace>& wsp = (n_in == std::min(n_col_block, n_col)) ? ws_block : ws_residual;
         prepare(wsp, n_in);
         Workspace& ws = *wsp;
-        const bool whole = (n_in == n_col);      // a single block needs no gather of the inputs
-
-        // (a single block takes the caller's gases as they are: no device copies of the mixing-ratio fields)
-        std::unique_ptr<Gas_concs_gpu> gas_concs_copy;
-        if (!whole) gas_concs_copy = std::make_unique<Gas_concs_gpu>(gas_concs, col_s, n_in);
-        const Gas_concs_gpu& gas_concs_subset = whole ? gas_concs : *gas_concs_copy;
-        auto sub2 = [&](const Array_gpu<Float,2>& a, const int n2) { return whole ? Array_gpu<Float,2>(const_cast<Float*>(a.ptr()), {n_in, n2})
-                                                                                  : a.subset({{ {col_s, col_e}, {1, n2} }}); };
-        Array_gpu<Float,2> p_lay_s = sub2(p_lay, n_lay), t_lay_s = sub2(t_lay, n_lay);
-        Array_gpu<Float,2> p_lev_s = sub2(p_lev, n_lev), t_lev_s = sub2(t_lev, n_lev);
-        Array_gpu<Float,1> t_sfc_s = whole ? Array_gpu<Float,1>(const_cast<Float*>(t_sfc.ptr()), {n_in}) : t_sfc.subset({{ {col_s, col_e} }});
-
-        Array_gpu<Float,2> col_dry_s({n_in, n_lay});
-        if (col_dry.size() == 0)
-            Gas_optics_rrtmgp_gpu::get_col_dry(col_dry_s, gas_concs_subset.get_vmr("h2o"), p_lev_s);
-        else
-            col_dry_s = sub2(col_dry, n_lay);
+        const Block blk(n_col, columns, gas_concs);
+        Array_gpu<Float,2> p_lay_s = blk.sub2(p_lay, n_lay), t_lay_s = blk.sub2(t_lay, n_lay);
+        Array_gpu<Float,2> p_lev_s = blk.sub2(p_lev, n_lev), t_lev_s = blk.sub2(t_lev, n_lev);
+        Array_gpu<Float,1> t_sfc_s = blk.sub1(t_sfc);
+        Array_gpu<Float,2> col_dry_s = blk.col_dry(col_dry, p_lev_s, n_lay);
 
         // (cloud optics first: its by-band optical depth is added inside gas_optics where tau is stored -- the add_to() of
         //  Radiation_solver.cu:508-511 folded into the producer)
         // LW scattering: the gas optics stay clear; the band cloud tau / ssa / g (not delta-scaled) go to the two-stream solver
-        if (switch_cloud_optics && scat)
-            cloud_optics_gpu->cloud_optics(sub2(lwp, n_lay), sub2(iwp, n_lay), sub2(rel, n_lay), sub2(dei, n_lay), *ws.cloud_optical_props_2str);
-        else if (switch_cloud_optics)
-            cloud_optics_gpu->cloud_optics(sub2(lwp, n_lay), sub2(iwp, n_lay), sub2(rel, n_lay), sub2(dei, n_lay), *ws.cloud_optical_props);
-        kdist_gpu->gas_optics(p_lay_s, p_lev_s, t_lay_s, t_sfc_s, gas_concs_subset, ws.optical_props, *ws.sources, col_dry_s, t_lev_s,
-                              (switch_cloud_optics && !scat && !mcica) ? ws.cloud_optical_props.get() : nullptr);
-        if (mcica)      // every g-point its own sub-column: the band cloud optical depth is added in the cloudy cells only
-        {
-            const Array_gpu<Float,2> frac_s = sub2(*mcica_frac, n_lay);
-            const Array_gpu<Float,2> alpha_s = (mcica_alpha != nullptr && n_lay > 1) ? sub2(*mcica_alpha, n_lay-1) : Array_gpu<Float,2>();
-            RRX_CALL(rrx_mcica_increment_1scalar, n_in, n_lay, n_gpt, n_bnd, ws.optical_props->get_band_lims_gpoint_gpu().ptr(),
-                     frac_s.ptr(), mcica_alpha != nullptr ? alpha_s.ptr() : nullptr, (unsigned long long)mcica_seed, 0,
-                     mcica_col_id != nullptr ? mcica_col_id + (col_s-1) : nullptr, mcica_col_offset + col_s-1,
-                     ws.optical_props->get_tau().ptr(), ws.cloud_optical_props->get_tau().ptr(), static_cast<unsigned char*>(nullptr));
-        }
+        if (cloud_2str)
+            cloud_optics_gpu->cloud_optics(blk.sub2(lwp, n_lay), blk.sub2(iwp, n_lay), blk.sub2(rel, n_lay), blk.sub2(dei, n_lay), *ws.cloud_optical_props_2str);
+        else if (cloud_1scl)
+            cloud_optics_gpu->cloud_optics(blk.sub2(lwp, n_lay), blk.sub2(iwp, n_lay), blk.sub2(rel, n_lay), blk.sub2(dei, n_lay), *ws.cloud_optical_props);
+        kdist_gpu->gas_optics(p_lay_s, p_lev_s, t_lay_s, t_sfc_s, blk.gases, ws.optical_props, *ws.sources, col_dry_s, t_lev_s,
+                              (cloud_1scl && !mcica.on()) ? ws.cloud_optical_props.get() : nullptr);
+        if (mcica.on())      // every g-point its own sub-column: the band cloud optical depth is added in the cloudy cells only
+            sample_clouds(mcica, blk, n_lay, n_gpt, n_bnd, ws.optical_props->get_band_lims_gpoint_gpu().ptr(), 0, [&](auto... common)
+            {
+                RRX_CALL(rrx_mcica_increment_1scalar, common..., ws.optical_props->get_tau().ptr(), ws.cloud_optical_props->get_tau().ptr(),
+                         static_cast<unsigned char*>(nullptr));
+            });
 
         if (switch_output_optical)
         {
@@ -576,102 +709,55 @@ void Radiation_solver_longwave::solve_gpu(
             continue;
 
         const int n_ang = n_gauss_angles;
-        Array_gpu<Float,2> emis_s = whole ? Array_gpu<Float,2>(const_cast<Float*>(emis_sfc.ptr()), {n_bnd, n_in}) : emis_sfc.subset({{ {1, n_bnd}, {col_s, col_e} }});
-        // the LW solve of this block: fixed Gauss angles, or the optimal-angle secants of the k-distribution's fit (jc: null = no Jacobian)
+        Array_gpu<Float,2> emis_s = blk.sub_last(emis_sfc, n_bnd);
+        const Array_gpu<Float,2> no_inc_flux;
+        if (plan.byband)
+        {
+            // band sums, band net and broadband fluxes from one solve
+            Byband_block v(blk, out, {&ws.gpt_flux_up, &ws.gpt_flux_dn});
+            rte_lw.rte_lw_byband(ws.optical_props, top_at_1, *ws.sources, emis_s, no_inc_flux, v.bnd[0], v.bnd[1], v.bnd[2], v.bb[0], v.bb[1]);
+            v.finish(blk, out);
+            continue;
+        }
+        // every other form of the LW solve of this block (jc: null = no Jacobian)
         auto solve_block = [&](Array_gpu<Float,3>& up, Array_gpu<Float,3>& dn, Array_gpu<Float,3>* jc)
         {
-            if (resc)
-                rte_lw.rte_lw_rescaled(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(),
-                                       switch_cloud_optics ? ws.cloud_optical_props_2str.get() : nullptr, up, dn);
-            else if (scat)
-                rte_lw.rte_lw_2stream(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(),
-                                      switch_cloud_optics ? ws.cloud_optical_props_2str.get() : nullptr, up, dn);
-            else if (optimal_angles)
-                rte_lw.rte_lw_optimal(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(),
-                                      kdist_gpu->get_optimal_angle_fit_gpu(), up, dn, jc, n_ang);
-            else if (jc != nullptr)
-                rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), up, dn, *jc, n_ang);
-            else
-                rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), up, dn, n_ang);
+            const Optical_props_2str_gpu* cloud = cloud_2str ? ws.cloud_optical_props_2str.get() : nullptr;
+            switch (plan.form)
+            {
+                case Lw_form::rescaled:   rte_lw.rte_lw_rescaled(ws.optical_props, top_at_1, *ws.sources, emis_s, no_inc_flux, cloud, up, dn); break;
+                case Lw_form::two_stream: rte_lw.rte_lw_2stream(ws.optical_props, top_at_1, *ws.sources, emis_s, no_inc_flux, cloud, up, dn); break;
+                case Lw_form::optimal:    // the secants of the k-distribution's fit
+                    rte_lw.rte_lw_optimal(ws.optical_props, top_at_1, *ws.sources, emis_s, no_inc_flux, kdist_gpu->get_optimal_angle_fit_gpu(), up, dn, jc, n_ang);
+                    break;
+                default:                  // fixed Gauss angles: per g-point, or the fused fractions form with one or several angles
+                    if (jc != nullptr) rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, no_inc_flux, up, dn, *jc, n_ang);
+                    else rte_lw.rte_lw(ws.optical_props, top_at_1, *ws.sources, emis_s, no_inc_flux, up, dn, n_ang);
+            }
         };
-        if (whole && broadband && !switch_output_bnd_fluxes)
+        if (blk.whole && plan.broadband)
         {
             // one block in broadband mode: the solver writes the caller's flux arrays, the net flux follows in place (no block
             // workspace, no copies: Fluxes_broadband_gpu::reduce + get_from_subset of the general path are 7 passes over the fluxes)
-            if (lw_flux_up.size() == 0) lw_flux_up.set_dims({n_col, n_lev});
-            if (lw_flux_dn.size() == 0) lw_flux_dn.set_dims({n_col, n_lev});
-            if (lw_flux_net.size() == 0) lw_flux_net.set_dims({n_col, n_lev});
+            out.allocate_bb();
             Array_gpu<Float,3> up3(lw_flux_up.ptr(), {n_col, n_lev, 1}), dn3(lw_flux_dn.ptr(), {n_col, n_lev, 1});
-            if (jac)
-            {
-                Array_gpu<Float,3> jac3(lw_flux_up_jac.ptr(), {n_col, n_lev, 1});
-                solve_block(up3, dn3, &jac3);
-            }
-            else
-                solve_block(up3, dn3, nullptr);
+            Array_gpu<Float,3> jac3(lw_flux_up_jac.ptr(), {n_col, n_lev, 1});      // (a view: not used without the Jacobian)
+            solve_block(up3, dn3, plan.jac ? &jac3 : nullptr);
             Fluxes_kernels_cuda::net_broadband_precalc(n_col, n_lev, lw_flux_dn.ptr(), lw_flux_up.ptr(), lw_flux_net.ptr());
             continue;
         }
-        if (byband)
+        solve_block(ws.gpt_flux_up, ws.gpt_flux_dn, plan.jac ? &ws.gpt_flux_up_jac : nullptr);
+        if (plan.jac)
         {
-            // band sums, band net and broadband fluxes from one solve: into the caller's arrays for a single block, else into block
-            // arrays that are copied into place
-            for (Array_gpu<Float,2>* a : {&lw_flux_up, &lw_flux_dn, &lw_flux_net}) if (a->size() == 0) a->set_dims({n_col, n_lev});
-            for (Array_gpu<Float,3>* a : {&lw_bnd_flux_up, &lw_bnd_flux_dn, &lw_bnd_flux_net}) if (a->size() == 0) a->set_dims({n_col, n_lev, n_bnd});
-            Array_gpu<Float,3> bup(whole ? lw_bnd_flux_up.ptr() : ws.gpt_flux_up.ptr(), {n_in, n_lev, n_bnd});
-            Array_gpu<Float,3> bdn(whole ? lw_bnd_flux_dn.ptr() : ws.gpt_flux_dn.ptr(), {n_in, n_lev, n_bnd});
-            Array_gpu<Float,3> bnet_blk, bnet;
-            Array_gpu<Float,2> up_blk, dn_blk, net_blk, up, dn, net;
-            if (whole)
-            {
-                bnet = Array_gpu<Float,3>(lw_bnd_flux_net.ptr(), {n_in, n_lev, n_bnd});
-                up = Array_gpu<Float,2>(lw_flux_up.ptr(), {n_in, n_lev}); dn = Array_gpu<Float,2>(lw_flux_dn.ptr(), {n_in, n_lev});
-                net = Array_gpu<Float,2>(lw_flux_net.ptr(), {n_in, n_lev});
-            }
-            else
-            {
-                bnet_blk.set_dims({n_in, n_lev, n_bnd}); up_blk.set_dims({n_in, n_lev}); dn_blk.set_dims({n_in, n_lev}); net_blk.set_dims({n_in, n_lev});
-                bnet = Array_gpu<Float,3>(bnet_blk.ptr(), {n_in, n_lev, n_bnd});
-                up = Array_gpu<Float,2>(up_blk.ptr(), {n_in, n_lev}); dn = Array_gpu<Float,2>(dn_blk.ptr(), {n_in, n_lev});
-                net = Array_gpu<Float,2>(net_blk.ptr(), {n_in, n_lev});
-            }
-            rte_lw.rte_lw_byband(ws.optical_props, top_at_1, *ws.sources, emis_s, Array_gpu<Float,2>(), bup, bdn, bnet, up, dn);
-            Fluxes_kernels_cuda::net_broadband_precalc(n_in, n_lev, dn.ptr(), up.ptr(), net.ptr());
-            if (!whole)
-            {
-                Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_in, col_s, lw_flux_up.ptr(), lw_flux_dn.ptr(), lw_flux_net.ptr(),
-                        up.ptr(), dn.ptr(), net.ptr());
-                Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_bnd, n_in, col_s, lw_bnd_flux_up.ptr(), lw_bnd_flux_dn.ptr(),
-                        lw_bnd_flux_net.ptr(), bup.ptr(), bdn.ptr(), bnet.ptr());
-            }
-            continue;
-        }
-        if (jac)
-        {
-            solve_block(ws.gpt_flux_up, ws.gpt_flux_dn, &ws.gpt_flux_up_jac);
             const Float* jac_blk = ws.gpt_flux_up_jac.ptr();
-            if (!broadband)
+            if (!plan.broadband)
             {
                 RRX_CALL(rrx_sum_broadband, n_in, n_lev, n_gpt, ws.gpt_flux_up_jac.ptr(), ws.flux_up_jac.ptr());
                 jac_blk = ws.flux_up_jac.ptr();
             }
             Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_in, col_s, lw_flux_up_jac.ptr(), jac_blk);
         }
-        else
-            solve_block(ws.gpt_flux_up, ws.gpt_flux_dn, nullptr);
-
-        Fluxes_broadband_gpu fluxes(n_in, n_lev);
-        fluxes.reduce(ws.gpt_flux_up, ws.gpt_flux_dn, ws.optical_props, top_at_1);
-        Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_in, col_s, lw_flux_up.ptr(), lw_flux_dn.ptr(), lw_flux_net.ptr(),
-                fluxes.get_flux_up().ptr(), fluxes.get_flux_dn().ptr(), fluxes.get_flux_net().ptr());
-
-        if (switch_output_bnd_fluxes)
-        {
-            Fluxes_byband_gpu bnd_fluxes(n_in, n_lev, n_bnd);
-            bnd_fluxes.reduce(ws.gpt_flux_up, ws.gpt_flux_dn, ws.optical_props, top_at_1);
-            Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_bnd, n_in, col_s, lw_bnd_flux_up.ptr(), lw_bnd_flux_dn.ptr(), lw_bnd_flux_net.ptr(),
-                    bnd_fluxes.get_bnd_flux_up().ptr(), bnd_fluxes.get_bnd_flux_dn().ptr(), bnd_fluxes.get_bnd_flux_net().ptr());
-        }
+        out.reduce_block(blk, switch_output_bnd_fluxes, ws.gpt_flux_up, ws.gpt_flux_dn, nullptr, ws.optical_props, top_at_1);
     }
 }
 
@@ -742,16 +828,17 @@ void Radiation_solver_shortwave::solve_gpu(
     const bool broadband = broadband_solvers && !switch_output_bnd_fluxes;
     // by-band solvers: the band sums come straight out of the fused solver (one slab per band in the block workspace)
     const bool byband = byband_solvers && switch_output_bnd_fluxes && switch_fluxes && n_bnd < n_gpt;
-    const bool mcica = mcica_frac != nullptr;
-    if (mcica && sunlit_columns)
+    if (mcica.on() && sunlit_columns)
         throw std::runtime_error("Radiation_solver_shortwave: cloud sampling (set_cloud_sampling) is not available with the sunlit-only "
                                  "solve (set_sunlit_columns): it does not carry the column identities");
-    if (mcica) check_cloud_sampling("Radiation_solver_shortwave", mcica_frac, mcica_alpha, n_col, n_lay, switch_cloud_optics);
+    if (mcica.on()) mcica.check("Radiation_solver_shortwave", n_col, n_lay, switch_cloud_optics);
     const bool spherical = sph_alt != nullptr;
     if (spherical && (sph_alt->dim(1) != n_col || sph_alt->dim(2) != n_lay))
         throw std::runtime_error("Radiation_solver_shortwave: set_spherical_mu0: alt_lay is not (ncol, nlay)");
     if (spherical && sph_ref_alt != nullptr && sph_ref_alt->dim(1) != n_col)
         throw std::runtime_error("Radiation_solver_shortwave: set_spherical_mu0: ref_alt is not (ncol)");
+    const Flux_outputs out{{{&sw_flux_up, &sw_flux_dn, &sw_flux_dn_dir, &sw_flux_net}, {&sw_bnd_flux_up, &sw_bnd_flux_dn, &sw_bnd_flux_dn_dir, &sw_bnd_flux_net}},
+                           n_col, n_lev, n_bnd};
 
     // columns in another order / on a padded count: gather the inputs, solve, scatter the fluxes back (see the header)
     if (!reordered_call && !switch_output_optical && switch_fluxes)
@@ -764,10 +851,7 @@ void Radiation_solver_shortwave::solve_gpu(
             if (day.n_keep < n_col) co = std::move(day);
             if (co.subset && co.n_keep == 0)
             {
-                for (Array_gpu<Float,2>* a : {&sw_flux_up, &sw_flux_dn, &sw_flux_dn_dir, &sw_flux_net}) co.zeros<2>(*a, {n_col, n_lev});
-                if (switch_output_bnd_fluxes)
-                    for (Array_gpu<Float,3>* a : {&sw_bnd_flux_up, &sw_bnd_flux_dn, &sw_bnd_flux_dn_dir, &sw_bnd_flux_net})
-                        co.zeros<3>(*a, {n_col, n_lev, n_bnd});
+                out.zeros(co, switch_output_bnd_fluxes);
                 return;
             }
         }
@@ -776,22 +860,17 @@ void Radiation_solver_shortwave::solve_gpu(
             const Gas_concs_gpu gases = gas_concs.gathered(co.perm, n_col, co.n_out);
             Aerosol_concs_gpu aerosols = aerosol_concs.gathered(co.perm, n_col, co.n_out);
             Array_gpu<Float,3> no3a, no3b, no3c; Array_gpu<Float,2> no2;
-            Array_gpu<Float,2> up, dn, dir, net; Array_gpu<Float,3> bup, bdn, bdir, bnet;
-            up.set_dims({co.n_out, n_lev}); dn.set_dims({co.n_out, n_lev}); dir.set_dims({co.n_out, n_lev}); net.set_dims({co.n_out, n_lev});
-            if (switch_output_bnd_fluxes)
-            { bup.set_dims({co.n_out, n_lev, n_bnd}); bdn.set_dims({co.n_out, n_lev, n_bnd}); bdir.set_dims({co.n_out, n_lev, n_bnd}); bnet.set_dims({co.n_out, n_lev, n_bnd}); }
-            struct Guard { bool& f; Guard(bool& f_) : f(f_) { f = true; } ~Guard() { f = false; } } guard(reordered_call);
-            Sampling_reordered sampling(mcica_frac, mcica_alpha, mcica_col_id, mcica_col_offset, co);
+            Flux_arrays r = out.reordered(co.n_out, switch_output_bnd_fluxes);
+            Guard guard(reordered_call);
+            Sampling_reordered sampling(mcica, co);
             Altitudes_reordered altitudes(sph_alt, sph_ref_alt, co);
             this->solve_gpu(switch_fluxes, switch_cloud_optics, switch_aerosol_optics, switch_output_optical, switch_output_bnd_fluxes,
                             switch_delta_cloud, switch_delta_aerosol, gases,
                             co.in2(p_lay), co.in2(p_lev), co.in2(t_lay), co.in2(t_lev), co.in2(col_dry),
                             co.in_last(sfc_alb_dir), co.in_last(sfc_alb_dif), co.in1(tsi_scaling), co.in1(mu0),
                             co.in2(lwp), co.in2(iwp), co.in2(rel), co.in2(dei), co.in2(rh), aerosols,
-                            no3a, no3b, no3c, no2, up, dn, dir, net, bup, bdn, bdir, bnet);
-            co.out(sw_flux_up, up); co.out(sw_flux_dn, dn); co.out(sw_flux_dn_dir, dir); co.out(sw_flux_net, net);
-            if (switch_output_bnd_fluxes)
-            { co.out(sw_bnd_flux_up, bup); co.out(sw_bnd_flux_dn, bdn); co.out(sw_bnd_flux_dn_dir, bdir); co.out(sw_bnd_flux_net, bnet); }
+                            no3a, no3b, no3c, no2, r.bb[0], r.bb[1], r.bb[2], r.bb[3], r.bnd[0], r.bnd[1], r.bnd[2], r.bnd[3]);
+            out.from_reordered(co, r, switch_output_bnd_fluxes);
             return;
         }
     }
@@ -812,53 +891,39 @@ void Radiation_solver_shortwave::solve_gpu(
             ws->aerosol_optical_props = std::make_unique<Optical_props_2str_gpu>(n, n_lay, *aerosol_optics_gpu);
     };
 
-    for (const auto& blk : column_blocks(n_col, std::max(1, n_col_block)))
+    for (const auto& columns : column_blocks(n_col, std::max(1, n_col_block)))
     {
-        const int col_s = blk.first, n_in = blk.second, col_e = col_s + n_in - 1;
+        const int col_s = columns.first, n_in = columns.second;
         std::shared_ptr<Workspace>& wsp = (n_in == std::min(n_col_block, n_col)) ? ws_block : ws_residual;
         prepare(wsp, n_in);
         Workspace& ws = *wsp;
-        const bool whole = (n_in == n_col);
-
-        // (a single block takes the caller's gases as they are: no device copies of the mixing-ratio fields)
-        std::unique_ptr<Gas_concs_gpu> gas_concs_copy;
-        if (!whole) gas_concs_copy = std::make_unique<Gas_concs_gpu>(gas_concs, col_s, n_in);
-        const Gas_concs_gpu& gas_concs_subset = whole ? gas_concs : *gas_concs_copy;
-        auto sub2 = [&](const Array_gpu<Float,2>& a, const int n2) { return whole ? Array_gpu<Float,2>(const_cast<Float*>(a.ptr()), {n_in, n2})
-                                                                                  : a.subset({{ {col_s, col_e}, {1, n2} }}); };
-        auto sub1 = [&](const Array_gpu<Float,1>& a) { return whole ? Array_gpu<Float,1>(const_cast<Float*>(a.ptr()), {n_in}) : a.subset({{ {col_s, col_e} }}); };
-        Array_gpu<Float,2> p_lay_s = sub2(p_lay, n_lay), t_lay_s = sub2(t_lay, n_lay), p_lev_s = sub2(p_lev, n_lev);
-
-        Array_gpu<Float,2> col_dry_s({n_in, n_lay});
-        if (col_dry.size() == 0)
-            Gas_optics_rrtmgp_gpu::get_col_dry(col_dry_s, gas_concs_subset.get_vmr("h2o"), p_lev_s);
-        else
-            col_dry_s = sub2(col_dry, n_lay);
+        const Block blk(n_col, columns, gas_concs);
+        Array_gpu<Float,2> p_lay_s = blk.sub2(p_lay, n_lay), t_lay_s = blk.sub2(t_lay, n_lay), p_lev_s = blk.sub2(p_lev, n_lev);
+        Array_gpu<Float,2> col_dry_s = blk.col_dry(col_dry, p_lev_s, n_lay);
 
         // (cloud optics first: gas and cloud properties are combined inside gas_optics where the g-point arrays are stored --
         //  the add_to() of Radiation_solver.cu:788-791 folded into the producer)
         if (switch_cloud_optics)
         {
             // (delta_scale() of Radiation_solver.cu:785 rides along in the same kernel)
-            cloud_optics_gpu->cloud_optics(sub2(lwp, n_lay), sub2(iwp, n_lay), sub2(rel, n_lay), sub2(dei, n_lay), *ws.cloud_optical_props,
+            cloud_optics_gpu->cloud_optics(blk.sub2(lwp, n_lay), blk.sub2(iwp, n_lay), blk.sub2(rel, n_lay), blk.sub2(dei, n_lay), *ws.cloud_optical_props,
                                            switch_delta_cloud);
         }
         Array_gpu<Float,2> toa_src_s({n_in, n_gpt});
-        kdist_gpu->gas_optics(p_lay_s, p_lev_s, t_lay_s, gas_concs_subset, ws.optical_props, toa_src_s, col_dry_s,
-                              (switch_cloud_optics && !mcica) ? ws.cloud_optical_props.get() : nullptr);
-        if (mcica)      // every g-point its own sub-column: the band cloud tau / ssa / g are combined in the cloudy cells only
+        kdist_gpu->gas_optics(p_lay_s, p_lev_s, t_lay_s, blk.gases, ws.optical_props, toa_src_s, col_dry_s,
+                              (switch_cloud_optics && !mcica.on()) ? ws.cloud_optical_props.get() : nullptr);
+        if (mcica.on())      // every g-point its own sub-column: the band cloud tau / ssa / g are combined in the cloudy cells only
         {
             Optical_props_2str_gpu& op = dynamic_cast<Optical_props_2str_gpu&>(*ws.optical_props);
-            const Array_gpu<Float,2> frac_s = sub2(*mcica_frac, n_lay);
-            const Array_gpu<Float,2> alpha_s = (mcica_alpha != nullptr && n_lay > 1) ? sub2(*mcica_alpha, n_lay-1) : Array_gpu<Float,2>();
             // (get_g(): the clear gas optics' g == 0 is materialised here, the kernel reads and writes the array)
-            RRX_CALL(rrx_mcica_increment_2stream, n_in, n_lay, n_gpt, n_bnd, op.get_band_lims_gpoint_gpu().ptr(),
-                     frac_s.ptr(), mcica_alpha != nullptr ? alpha_s.ptr() : nullptr, (unsigned long long)mcica_seed, 1,
-                     mcica_col_id != nullptr ? mcica_col_id + (col_s-1) : nullptr, mcica_col_offset + col_s-1,
-                     op.get_tau().ptr(), op.get_ssa().ptr(), op.get_g().ptr(), ws.cloud_optical_props->get_tau().ptr(),
-                     ws.cloud_optical_props->get_ssa().ptr(), ws.cloud_optical_props->get_g().ptr(), static_cast<unsigned char*>(nullptr));
+            sample_clouds(mcica, blk, n_lay, n_gpt, n_bnd, op.get_band_lims_gpoint_gpu().ptr(), 1, [&](auto... common)
+            {
+                RRX_CALL(rrx_mcica_increment_2stream, common..., op.get_tau().ptr(), op.get_ssa().ptr(), op.get_g().ptr(),
+                         ws.cloud_optical_props->get_tau().ptr(), ws.cloud_optical_props->get_ssa().ptr(), ws.cloud_optical_props->get_g().ptr(),
+                         static_cast<unsigned char*>(nullptr));
+            });
         }
-        Array_gpu<Float,1> tsi_s = sub1(tsi_scaling);
+        Array_gpu<Float,1> tsi_s = blk.sub1(tsi_scaling);
         RRX_CALL(rrx_scaling_to_subset, n_in, n_gpt, toa_src_s.ptr(), tsi_s.ptr());
 
         if (switch_aerosol_optics)
@@ -866,7 +931,7 @@ void Radiation_solver_shortwave::solve_gpu(
             // the block's own columns (the reference subsets (1, n_col) here, Radiation_solver.cu:796, which is only right for
             // a single block)
             Aerosol_concs_gpu aerosol_concs_subset(aerosol_concs, col_s, n_in);
-            aerosol_optics_gpu->aerosol_optics(aerosol_concs_subset, sub2(rh, n_lay), p_lev_s, *ws.aerosol_optical_props);
+            aerosol_optics_gpu->aerosol_optics(aerosol_concs_subset, blk.sub2(rh, n_lay), p_lev_s, *ws.aerosol_optical_props);
             if (switch_delta_aerosol)
                 ws.aerosol_optical_props->delta_scale();
             add_to(dynamic_cast<Optical_props_2str_gpu&>(*ws.optical_props), *ws.aerosol_optical_props);
@@ -881,94 +946,46 @@ void Radiation_solver_shortwave::solve_gpu(
         if (!switch_fluxes)
             continue;
 
-        auto sub_last = [&](const Array_gpu<Float,2>& a) { return whole ? Array_gpu<Float,2>(const_cast<Float*>(a.ptr()), {n_bnd, n_in})
-                                                                          : a.subset({{ {1, n_bnd}, {col_s, col_e} }}); };
         // set_spherical_mu0: the block's cosines layer by layer, from its mu0, its altitudes and its reference altitudes
         Array_gpu<Float,2> mu0_lay_s;
         if (spherical)
         {
             mu0_lay_s.set_dims({n_in, n_lay});
-            const Array_gpu<Float,2> alt_s = sub2(*sph_alt, n_lay);
-            const Array_gpu<Float,1> ref_s = (sph_ref_alt != nullptr) ? sub1(*sph_ref_alt) : Array_gpu<Float,1>();
-            const Array_gpu<Float,1> mu0_s = sub1(mu0);
+            const Array_gpu<Float,2> alt_s = blk.sub2(*sph_alt, n_lay);
+            const Array_gpu<Float,1> ref_s = (sph_ref_alt != nullptr) ? blk.sub1(*sph_ref_alt) : Array_gpu<Float,1>();
+            const Array_gpu<Float,1> mu0_s = blk.sub1(mu0);
             RRX_CALL(rrx_zenith_angle_spherical_correction, n_in, n_lay, sph_ref_alt != nullptr ? ref_s.ptr() : nullptr, mu0_s.ptr(), alt_s.ptr(),
                      sph_radius, mu0_lay_s.ptr());
         }
+        const Array_gpu<Float,2> no_inc_flux;
+        // (the solvers take mu0 per column or, spherical, per column and layer)
+        auto with_mu0 = [&](auto&& rte) { if (spherical) rte(mu0_lay_s); else rte(blk.sub1(mu0)); };
+        if (byband)
+        {
+            // band sums, band net and broadband fluxes from one solve
+            Byband_block v(blk, out, {&ws.gpt_flux_up, &ws.gpt_flux_dn, &ws.gpt_flux_dn_dir});
+            with_mu0([&](const auto& mu) {
+                rte_sw.rte_sw_byband(ws.optical_props, top_at_1, mu, toa_src_s, blk.sub_last(sfc_alb_dir, n_bnd), blk.sub_last(sfc_alb_dif, n_bnd),
+                                     no_inc_flux, v.bnd[0], v.bnd[1], v.bnd[2], v.bnd[3], v.bb[0], v.bb[1], v.bb[2]); });
+            v.finish(blk, out);
+            continue;
+        }
         auto solve = [&](Array_gpu<Float,3>& up3, Array_gpu<Float,3>& dn3, Array_gpu<Float,3>& dir3)
         {
-            if (spherical)
-                rte_sw.rte_sw(ws.optical_props, top_at_1, mu0_lay_s, toa_src_s, sub_last(sfc_alb_dir), sub_last(sfc_alb_dif), Array_gpu<Float,2>(), up3, dn3, dir3);
-            else
-                rte_sw.rte_sw(ws.optical_props, top_at_1, sub1(mu0), toa_src_s, sub_last(sfc_alb_dir), sub_last(sfc_alb_dif), Array_gpu<Float,2>(), up3, dn3, dir3);
+            with_mu0([&](const auto& mu) {
+                rte_sw.rte_sw(ws.optical_props, top_at_1, mu, toa_src_s, blk.sub_last(sfc_alb_dir, n_bnd), blk.sub_last(sfc_alb_dif, n_bnd), no_inc_flux, up3, dn3, dir3); });
         };
-        if (whole && broadband && !switch_output_bnd_fluxes)
+        if (blk.whole && broadband)
         {
             // one block in broadband mode: the solver writes the caller's flux arrays, the net flux follows in place
-            for (Array_gpu<Float,2>* a : {&sw_flux_up, &sw_flux_dn, &sw_flux_dn_dir, &sw_flux_net}) if (a->size() == 0) a->set_dims({n_col, n_lev});
+            out.allocate_bb();
             Array_gpu<Float,3> up3(sw_flux_up.ptr(), {n_col, n_lev, 1}), dn3(sw_flux_dn.ptr(), {n_col, n_lev, 1}), dir3(sw_flux_dn_dir.ptr(), {n_col, n_lev, 1});
             solve(up3, dn3, dir3);
             Fluxes_kernels_cuda::net_broadband_precalc(n_col, n_lev, sw_flux_dn.ptr(), sw_flux_up.ptr(), sw_flux_net.ptr());
             continue;
         }
-        if (byband)
-        {
-            // band sums, band net and broadband fluxes from one solve (see the longwave)
-            for (Array_gpu<Float,2>* a : {&sw_flux_up, &sw_flux_dn, &sw_flux_dn_dir, &sw_flux_net}) if (a->size() == 0) a->set_dims({n_col, n_lev});
-            for (Array_gpu<Float,3>* a : {&sw_bnd_flux_up, &sw_bnd_flux_dn, &sw_bnd_flux_dn_dir, &sw_bnd_flux_net})
-                if (a->size() == 0) a->set_dims({n_col, n_lev, n_bnd});
-            Array_gpu<Float,3> bup(whole ? sw_bnd_flux_up.ptr() : ws.gpt_flux_up.ptr(), {n_in, n_lev, n_bnd});
-            Array_gpu<Float,3> bdn(whole ? sw_bnd_flux_dn.ptr() : ws.gpt_flux_dn.ptr(), {n_in, n_lev, n_bnd});
-            Array_gpu<Float,3> bdir(whole ? sw_bnd_flux_dn_dir.ptr() : ws.gpt_flux_dn_dir.ptr(), {n_in, n_lev, n_bnd});
-            Array_gpu<Float,3> bnet_blk, bnet;
-            Array_gpu<Float,2> up_blk, dn_blk, dir_blk, net_blk, up, dn, dir, net;
-            if (whole)
-            {
-                bnet = Array_gpu<Float,3>(sw_bnd_flux_net.ptr(), {n_in, n_lev, n_bnd});
-                up = Array_gpu<Float,2>(sw_flux_up.ptr(), {n_in, n_lev}); dn = Array_gpu<Float,2>(sw_flux_dn.ptr(), {n_in, n_lev});
-                dir = Array_gpu<Float,2>(sw_flux_dn_dir.ptr(), {n_in, n_lev}); net = Array_gpu<Float,2>(sw_flux_net.ptr(), {n_in, n_lev});
-            }
-            else
-            {
-                bnet_blk.set_dims({n_in, n_lev, n_bnd});
-                for (Array_gpu<Float,2>* a : {&up_blk, &dn_blk, &dir_blk, &net_blk}) a->set_dims({n_in, n_lev});
-                bnet = Array_gpu<Float,3>(bnet_blk.ptr(), {n_in, n_lev, n_bnd});
-                up = Array_gpu<Float,2>(up_blk.ptr(), {n_in, n_lev}); dn = Array_gpu<Float,2>(dn_blk.ptr(), {n_in, n_lev});
-                dir = Array_gpu<Float,2>(dir_blk.ptr(), {n_in, n_lev}); net = Array_gpu<Float,2>(net_blk.ptr(), {n_in, n_lev});
-            }
-            if (spherical)
-                rte_sw.rte_sw_byband(ws.optical_props, top_at_1, mu0_lay_s, toa_src_s, sub_last(sfc_alb_dir), sub_last(sfc_alb_dif),
-                                     Array_gpu<Float,2>(), bup, bdn, bdir, bnet, up, dn, dir);
-            else
-                rte_sw.rte_sw_byband(ws.optical_props, top_at_1, sub1(mu0), toa_src_s, sub_last(sfc_alb_dir), sub_last(sfc_alb_dif),
-                                     Array_gpu<Float,2>(), bup, bdn, bdir, bnet, up, dn, dir);
-            Fluxes_kernels_cuda::net_broadband_precalc(n_in, n_lev, dn.ptr(), up.ptr(), net.ptr());
-            if (!whole)
-            {
-                Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_in, col_s,
-                        sw_flux_up.ptr(), sw_flux_dn.ptr(), sw_flux_dn_dir.ptr(), sw_flux_net.ptr(), up.ptr(), dn.ptr(), dir.ptr(), net.ptr());
-                Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_bnd, n_in, col_s,
-                        sw_bnd_flux_up.ptr(), sw_bnd_flux_dn.ptr(), sw_bnd_flux_dn_dir.ptr(), sw_bnd_flux_net.ptr(),
-                        bup.ptr(), bdn.ptr(), bdir.ptr(), bnet.ptr());
-            }
-            continue;
-        }
         solve(ws.gpt_flux_up, ws.gpt_flux_dn, ws.gpt_flux_dn_dir);
-
-        Fluxes_broadband_gpu fluxes(n_in, n_lev);
-        fluxes.reduce(ws.gpt_flux_up, ws.gpt_flux_dn, ws.gpt_flux_dn_dir, ws.optical_props, top_at_1);
-        Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_in, col_s,
-                sw_flux_up.ptr(), sw_flux_dn.ptr(), sw_flux_dn_dir.ptr(), sw_flux_net.ptr(),
-                fluxes.get_flux_up().ptr(), fluxes.get_flux_dn().ptr(), fluxes.get_flux_dn_dir().ptr(), fluxes.get_flux_net().ptr());
-
-        if (switch_output_bnd_fluxes)
-        {
-            Fluxes_byband_gpu bnd_fluxes(n_in, n_lev, n_bnd);
-            bnd_fluxes.reduce(ws.gpt_flux_up, ws.gpt_flux_dn, ws.gpt_flux_dn_dir, ws.optical_props, top_at_1);
-            Subset_kernels_cuda::get_from_subset(n_col, n_lev, n_bnd, n_in, col_s,
-                    sw_bnd_flux_up.ptr(), sw_bnd_flux_dn.ptr(), sw_bnd_flux_dn_dir.ptr(), sw_bnd_flux_net.ptr(),
-                    bnd_fluxes.get_bnd_flux_up().ptr(), bnd_fluxes.get_bnd_flux_dn().ptr(),
-                    bnd_fluxes.get_bnd_flux_dn_dir().ptr(), bnd_fluxes.get_bnd_flux_net().ptr());
-        }
+        out.reduce_block(blk, switch_output_bnd_fluxes, ws.gpt_flux_up, ws.gpt_flux_dn, &ws.gpt_flux_dn_dir, ws.optical_props, top_at_1);
     }
 }
 
@@ -985,12 +1002,5 @@ void Radiation_solver_shortwave::set_spherical_mu0(const Array_gpu<Float,2>* alt
 
 void Radiation_solver_shortwave::set_cloud_sampling(const Array_gpu<Float,2>* cloud_frac, const int overlap, const Array_gpu<Float,2>* overlap_param,
                                                    const uint64_t seed, const int col_offset)
-{
-    if (overlap != 0 && overlap != 1)
-        throw std::runtime_error("Radiation_solver_shortwave::set_cloud_sampling: overlap " + std::to_string(overlap) + " is not 0 (maximum-random) or 1 (exponential-random)");
-    if (cloud_frac != nullptr && overlap == 1 && overlap_param == nullptr)
-        throw std::runtime_error("Radiation_solver_shortwave::set_cloud_sampling: exponential-random overlap needs overlap_param");
-    mcica_frac = cloud_frac; mcica_alpha = (cloud_frac != nullptr && overlap == 1) ? overlap_param : nullptr;
-    mcica_seed = seed; mcica_col_offset = col_offset;
-}
+{ mcica.set("Radiation_solver_shortwave", cloud_frac, overlap, overlap_param, seed, col_offset); }
 

@@ -8,6 +8,7 @@
 #include "Array.h"
 #include "Optical_props.h"
 #include "Netcdf_interface.h"
+#include "Radiation_solver.h"
 
 namespace
 {
@@ -59,6 +60,25 @@ int rrx_host_selftest_delta_scale_gzero(void)
         return 0;
     }
     catch (const std::exception&) { return 100; }
+}
+
+// lw_solve_plan() of Radiation_solver.cpp for tests/test_host_lw_options.py; no device involved. flags, from bit 0: broadband_solvers,
+// byband_solvers, jacobian, optimal_angles, lw_scattering, lw_rescaling, cloud sampling, switch_fluxes, switch_output_bnd_fluxes,
+// switch_cloud_optics, n_bnd < n_gpt; bits 11.. hold n_gauss_angles. Returns broadband | byband << 1 | jac << 2 | cloud_to_solver << 3 |
+// form << 4 (Lw_form in the order of its declaration), or -1 with the refusal in msg.
+int rrx_host_selftest_lw_plan(const unsigned flags, char* msg, const int msglen)
+{
+    const auto bit = [flags](const int i) { return ((flags >> i) & 1u) != 0; };
+    Lw_solve_options o;
+    o.broadband_solvers = bit(0); o.byband_solvers = bit(1); o.jacobian = bit(2); o.optimal_angles = bit(3); o.lw_scattering = bit(4);
+    o.lw_rescaling = bit(5); o.cloud_sampling = bit(6); o.switch_fluxes = bit(7); o.switch_output_bnd_fluxes = bit(8);
+    o.switch_cloud_optics = bit(9); o.fewer_bands_than_gpoints = bit(10); o.n_gauss_angles = int(flags >> 11);
+    try
+    {
+        const Lw_solve_plan p = lw_solve_plan(o);
+        return int(p.broadband) | int(p.byband) << 1 | int(p.jac) << 2 | int(p.cloud_to_solver) << 3 | int(p.form) << 4;
+    }
+    catch (const std::exception& e) { std::snprintf(msg, size_t(msglen), "%s", e.what()); return -1; }
 }
 
 // Any supported file (NetCDF-4 or RRXB, recognised by its first bytes) rewritten in the other format: "rrxb" or "netcdf4".

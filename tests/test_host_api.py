@@ -54,6 +54,7 @@ def test_host_library_exports_driver_entry():
     assert os.path.exists(lib), "run __graft_entry__.build()"
     assert hasattr(ctypes.CDLL(lib), "rrx_host_main")
     assert hasattr(ctypes.CDLL(lib), "rrx_host_selftest_delta_scale_gzero")
+    assert hasattr(ctypes.CDLL(lib), "rrx_host_selftest_lw_plan")
     assert os.path.exists(os.path.join(ROOT, "rte-rrtmgp-cpp_amd", "lib", "test_rte_rrtmgp_gpu"))
 
 
