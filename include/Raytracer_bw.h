@@ -42,5 +42,19 @@ class Raytracer_bw_gpu
                 const Sensor_bw& sensor,
                 const long long rays_per_pixel, const unsigned long long seed, const int max_events,
                 Array_gpu<Float,2>& radiance, unsigned long long* n_clamped = nullptr);
+
+        // Tabulated cloud phase functions (rrx_*_phase): with a table set, cloud scatters by the phase function of the
+        // cell's radius in place of Henyey-Greenstein. mu (nmu); phase, cdf (nmu, nre, nbnd) as rrx_rt_phase_tables makes them
+        // (rrx_rt_phase_tables); the radii re0 + dre ire; cld_re (ncol, nz) in the unit of re0. The arrays are copied.
+        void set_phase_table(const Array_gpu<Float,1>& mu, const Array_gpu<Float,3>& phase, const Array_gpu<Float,3>& cdf,
+                             const Float re0, const Float dre, const Array_gpu<Float,2>& cld_re);
+        void clear_phase_table() { has_table = false; mu = Array_gpu<Float,1>(); phase = Array_gpu<Float,3>(); cdf = Array_gpu<Float,3>(); cld_re = Array_gpu<Float,2>(); }
+
+    private:
+        bool has_table = false;
+        Float re0 = Float(0.), dre = Float(0.);
+        Array_gpu<Float,1> mu;
+        Array_gpu<Float,3> phase, cdf;
+        Array_gpu<Float,2> cld_re;
 };
 #endif

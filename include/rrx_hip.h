@@ -683,7 +683,57 @@ int rrx_raytracer_bw##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool to
         const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
         F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz, \
         int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
-        F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream);
+        F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream); \
+/* ---- Tabulated cloud phase functions for both ray tracers (csrc/rrx_rt_phase.h, rrx_rt_phase.hip). ONE table is \
+   sampled for the scattering angle and evaluated towards the sun. mu (nmu): the cosines of the scattering angle, strictly \
+   increasing from -1 to +1, shared by all tables; P is piecewise linear in mu between them. phase, cdf (nmu, nre, nbnd), nmu fastest: \
+   1/2 int P dmu = 1 and C_i = 1/2 int_{-1}^{mu_i} P dmu (C_0 = 0, C_last = 1), one table per effective radius re0 + dre ire and band. \
+   A cell of radius re (cld_re (ncol, nz), the layout of one band of the cloud triple, the unit of re0 and dre) uses \
+   X_lo + f (X_hi - X_lo) of the tables ire = clamp(int((re - re0)/dre), 0, nre-2) and ire + 1, f = clamp((re - re0)/dre - ire, 0, 1) \
+   (a NaN radius: ire = 0, f = 0; nre = 1: no blend). Sampling inverts the piecewise-quadratic blended CDF exactly with + - x / sqrt \
+   from the one uniform that gives the cosine today; no further random number is drawn. Rayleigh scattering on gas is unchanged; \
+   cld_g is not read but the triple stays all or none. \
+   rrx_rt_phase_tables: phase_raw (nmu, nre, nbnd) >= 0 of any normalisation -> phase and cdf; the trapezoid sums are accumulated in \
+   double in node order in both precisions. It waits for its launch: nodes that do not increase strictly from -1 to +1, a table \
+   whose integral is not > 0 or not finite or that holds a negative number: non-zero. nbnd = 0: returns 0 without a launch. \
+   rrx_rt_phase_sample: cos_out[i] = the cosine that the tracers draw from the uniform u[i] in a cell of radius re[i], band ibnd \
+   (0-based), i < n. rrx_rt_phase_eval: p_out[i] = P(clamp(cs[i], -1, 1)) at radius re[i], the density of that draw. n = 0: \
+   returns 0 without a launch. \
+   rrx_rt_trace_counts_phase, rrx_raytracer_sw_phase, rrx_rt_bw_trace_counts_phase, rrx_raytracer_bw_phase: the entries above with \
+   nmu, nre, re0, dre, mu, phase, cdf, cld_re in front of the stream. With the four pointers NULL they are the entries above (nmu, \
+   nre, re0, dre are not read); otherwise the cloud species scatters by the table. The spectral loops give the same bits as their \
+   loops made by hand. Refused, before any HIP call: a partly-NULL table, a table without a cloud triple, nmu < 2, nmu > 4096 (the \
+   backward tracer keeps the nodes in LDS), nre < 1, dre <= 0 with nre > 1, a negative extent, and what the entries above refuse. */ \
+int rrx_rt_phase_tables##SFX(int nmu, int nre, int nbnd, const F* mu, const F* phase_raw, F* phase, F* cdf, void* stream); \
+int rrx_rt_phase_sample##SFX(long long n, int nmu, int nre, int nbnd, int ibnd, F re0, F dre, const F* mu, const F* phase, const F* cdf, \
+        const F* u, const F* re, F* cos_out, void* stream); \
+int rrx_rt_phase_eval##SFX(long long n, int nmu, int nre, int nbnd, int ibnd, F re0, F dre, const F* mu, const F* phase, const F* cdf, \
+        const F* cs, const F* re, F* p_out, void* stream); \
+int rrx_rt_trace_counts_phase##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, F inc_dir, F inc_dif, int knx, int kny, int knz, const F* k_null, \
+        unsigned long long seed, long long photon0, long long nphotons, int max_events, \
+        unsigned long long* sfc_dn_dir, unsigned long long* sfc_dn_dif, unsigned long long* sfc_up, unsigned long long* tod_up, \
+        unsigned long long* abs_dir, unsigned long long* abs_dif, unsigned long long* n_capped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, void* stream); \
+int rrx_raytracer_sw_phase##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
+        long long photons_per_pixel, unsigned long long seed, int max_events, \
+        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, void* stream); \
+int rrx_rt_bw_trace_counts_phase##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
+        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, void* stream); \
+int rrx_raytracer_bw_phase##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
+        F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, void* stream);
 
 RRX_DECLARE(double, _f64)
 RRX_DECLARE(float, _f32)

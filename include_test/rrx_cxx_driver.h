@@ -58,6 +58,13 @@ int   rrx_cxx_trace_rays(int nx, int ny, int nz, int ngpt, int nbnd, Real dx, Re
                          const Real* sfc_albedo, Real mu0, Real azimuth, const Real* inc_dir, const Real* inc_dif, int knx, int kny, int knz,
                          long long photons_per_pixel, unsigned long long seed, int max_events, Real* const* out6, unsigned long long* n_capped,
                          void* stream);
+/* the same after Raytracer_gpu::set_phase_table: mu (nmu), phase, cdf (nmu, nre, nbnd), cld_re (ncol, nz) on the device; mu
+ * NULL: no table. rrx_cxx_trace_rays_bw_phase below likewise. */
+int   rrx_cxx_trace_rays_phase(int nx, int ny, int nz, int ngpt, int nbnd, Real dx, Real dy, Real dz, int top_at_1, int independent_column,
+                         const Real* tau, const Real* ssa, const int* band_lims_gpt, const Real* cld_tau, const Real* cld_ssa, const Real* cld_g,
+                         const Real* sfc_albedo, Real mu0, Real azimuth, const Real* inc_dir, const Real* inc_dif, int knx, int kny, int knz,
+                         long long photons_per_pixel, unsigned long long seed, int max_events, Real* const* out6, unsigned long long* n_capped,
+                         int nmu, int nre, Real re0, Real dre, const Real* mu, const Real* phase, const Real* cdf, const Real* cld_re, void* stream);
 /* Raytracer_bw_gpu::trace_rays_bw (include/Raytracer_bw.h) on device arrays of the caller; needs no handle. inc_dir: ngpt numbers and
  * sensor: 12 numbers (position, e_w, e_h, e_d) on the host; radiance (npx, npy) on the device; n_capped, n_clamped: one number each on
  * the host. */
@@ -66,6 +73,12 @@ int   rrx_cxx_trace_rays_bw(int nx, int ny, int nz, int ngpt, int nbnd, Real dx,
                             const Real* sfc_albedo, Real mu0, Real azimuth, const Real* inc_dir, int knx, int kny, int knz,
                             int sensor_type, int npx, int npy, Real fov, const Real* sensor, long long rays_per_pixel, unsigned long long seed,
                             int max_events, Real* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream);
+int   rrx_cxx_trace_rays_bw_phase(int nx, int ny, int nz, int ngpt, int nbnd, Real dx, Real dy, Real dz, int top_at_1,
+                            const Real* tau, const Real* ssa, const int* band_lims_gpt, const Real* cld_tau, const Real* cld_ssa, const Real* cld_g,
+                            const Real* sfc_albedo, Real mu0, Real azimuth, const Real* inc_dir, int knx, int kny, int knz,
+                            int sensor_type, int npx, int npy, Real fov, const Real* sensor, long long rays_per_pixel, unsigned long long seed,
+                            int max_events, Real* radiance, unsigned long long* n_capped, unsigned long long* n_clamped,
+                            int nmu, int nre, Real re0, Real dre, const Real* mu, const Real* phase, const Real* cdf, const Real* cld_re, void* stream);
 /* one LW + one SW solve_gpu (fluxes only) enqueued on `stream`; DEVICE arrays: (ncol,nlay) / (ncol,nlay+1) fields, (ncol) vectors,
    surface properties (nbnd,ncol); lwp, iwp, rel, dei NULL without clouds; out7: seven (ncol, nlay+1) arrays for LW up, dn, net and
    SW up, dn, dn_dir, net, or NULL (the driver then keeps them: rrx_cxx_driver_fluxes) */

@@ -6,5 +6,5 @@ shim module ``rte_rrtmgp_cpp_amd`` (rte_rrtmgp_cpp_amd.py at the repo root).
 Python here is test/bench plumbing only. ``HipKernels`` raises if the HIP library or a GPU is missing: the
 product path has no CPU fallback. The CPU oracle lives in oracle/ and is never imported from this package.
 """
-from . import synthetic, pipeline, camera    # noqa: F401
+from . import synthetic, pipeline, camera, phase_tables    # noqa: F401
 from .hip_kernels import HipKernels, LIB_PATH, load_library   # noqa: F401

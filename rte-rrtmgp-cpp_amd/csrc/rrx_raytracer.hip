@@ -33,7 +33,7 @@
 //
 // Shape: one photon per lane at a time; a lane whose photon ends takes the next one of its list in the same loop, so the lanes
 // of a wave stay busy until the lists run out (the grid is capped and the photons dealt round-robin over the threads).
-#include "rrx_rt_common.h"
+#include "rrx_rt_phase.h"
 #include "rrx_hip.h"
 
 namespace
@@ -84,8 +84,10 @@ struct TraceArgs
     u64* sfc_dn_dir; u64* sfc_dn_dif; u64* sfc_up; u64* tod_up; u64* abs_dir; u64* abs_dif; u64* n_capped;
 };
 
-template<typename F>
-__global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a)
+// TABLE: cloud scatters by the tabulated phase function of the cell's radius (rrx_rt_phase.h) in place of
+// Henyey-Greenstein; cld_g is then not read, and the radius only once the scatterer has been drawn as cloud
+template<typename F, bool TABLE>
+__global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, const PhaseArgs<F,TABLE> ph)
 {
     const long long nthreads = (long long)gridDim.x*blockDim.x;
     long long next_photon = (long long)blockIdx.x*blockDim.x + threadIdx.x;
@@ -99,7 +101,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a)
     const F* __restrict__ tau_g = a.tau + ncol*nz*a.igpt;
     const F* __restrict__ ssa_g = a.ssa + ncol*nz*a.igpt;
     const F inf = F(INFINITY);
-    const F g_max = F(1.) - Lim<F>::eps();
+    [[maybe_unused]] const F g_max = F(1.) - Lim<F>::eps();
 
     Stream rng; rng.k0 = a.k0; rng.k1 = a.k1; rng.used = 4; rng.block = 0u; rng.c0 = rng.c1 = rng.c2 = 0u;
     bool alive = false, pending = false;
@@ -189,11 +191,13 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a)
             const int lay = a.top_at_1 ? nz-1-k : k;
             const size_t cell = size_t(i) + size_t(j)*nx + ncol*lay;
             const F t = tau_g[cell], w0 = ssa_g[cell];
-            F tc = F(0.), wc = F(0.), gc = F(0.);
+            F tc = F(0.), wc = F(0.);
+            [[maybe_unused]] F gc = F(0.);
             if (ibnd >= 0)
             {
                 const size_t cb = cell + ncol*nz*ibnd;
-                tc = a.cld_tau[cb]; wc = a.cld_ssa[cb]; gc = a.cld_g[cb];
+                tc = a.cld_tau[cb]; wc = a.cld_ssa[cb];
+                if constexpr (!TABLE) gc = a.cld_g[cb];
             }
             const F k_ext = k_ext_of(t, tc, a.dz);
             const F k_sca = (t*w0 + tc*wc) / a.dz;
@@ -206,7 +210,12 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a)
             if (rng.next<F>()*(k_sca + (kn_val - k_ext)) < k_sca)
             {
                 const bool cloud = rng.next<F>()*k_sca < k_sca_cld;
-                scatter_direction(rng, cloud, gc, g_max, ux, uy, uz);
+                if constexpr (TABLE)
+                {
+                    const F re = cloud ? ph.in.cld_re[cell] : F(0.);          // cld_re (ncol, nz): one radius for all bands
+                    scatter_direction_table(rng, cloud, table_of_band(ph.in, ibnd), ph.in.mu, re, ux, uy, uz);
+                }
+                else scatter_direction(rng, cloud, gc, g_max, ux, uy, uz);
                 kind = 1;
             }
         }
@@ -232,14 +241,16 @@ void launch_k_null(int nx, int ny, int nz, int nbnd, int igpt, int top_at_1, con
 }
 
 template<typename F>
-void launch_trace(TraceArgs<F> a, const F mu0, const F azimuth, const F inc_dir, const F inc_dif, const u64 seed, hipStream_t st)
+void launch_trace(TraceArgs<F> a, const PhaseIn<F>& ph, const F mu0, const F azimuth, const F inc_dir, const F inc_dif, const u64 seed,
+                  hipStream_t st)
 {
     const double st_ = std::sqrt(std::max(0.0, 1.0 - double(mu0)*double(mu0)));
     a.sun_x = F(st_*std::cos(double(azimuth))); a.sun_y = F(st_*std::sin(double(azimuth))); a.sun_z = -mu0;
     a.dif_frac = inc_dif / (inc_dir + inc_dif);
     a.k0 = unsigned(seed & 0xFFFFFFFFull); a.k1 = unsigned(seed >> 32);
     const int blocks = int(std::min<long long>((a.nphotons + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
-    trace_kernel<F><<<blocks, RT_BLOCK, 0, st>>>(a);
+    if (ph.given()) trace_kernel<F,true><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,true>{ph});
+    else trace_kernel<F,false><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,false>{});
 }
 
 template<typename F>
@@ -270,7 +281,8 @@ int trace_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, i
                 const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
                 F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, F inc_dir, F inc_dif,
                 int knx, int kny, int knz, const F* k_null, u64 seed, long long photon0, long long nphotons, int max_events,
-                u64* sfc_dn_dir, u64* sfc_dn_dif, u64* sfc_up, u64* tod_up, u64* abs_dir, u64* abs_dif, u64* n_capped, void* stream)
+                u64* sfc_dn_dir, u64* sfc_dn_dif, u64* sfc_up, u64* tod_up, u64* abs_dir, u64* abs_dif, u64* n_capped, void* stream,
+                const PhaseIn<F> ph = PhaseIn<F>{})
 {
     RRX_TRY
     if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"nphotons", nphotons}})) return 0;
@@ -280,6 +292,7 @@ int trace_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, i
                   {"sfc_dn_dif", sfc_dn_dif}, {"sfc_up", sfc_up}, {"tod_up", tod_up}, {"abs_dir", abs_dir}, {"abs_dif", abs_dif},
                   {"n_capped", n_capped}});
     check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
+    check_phase(ph, cld_tau);
     if (igpt < 0 || igpt >= ngpt) throw std::runtime_error("igpt is outside [0, ngpt)");
     check_scene(dx, dy, dz, mu0);
     if (inc_dir < F(0.) || inc_dif < F(0.) || !(inc_dir + inc_dif > F(0.))) throw std::runtime_error("inc_dir, inc_dif must be >= 0 with a positive sum");
@@ -288,7 +301,7 @@ int trace_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, i
     TraceArgs<F> a{nx, ny, nz, nbnd, igpt, top_at_1 ? 1 : 0, independent_column ? 1 : 0, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g,
                    dx, dy, dz, sfc_albedo, F(0.), F(0.), F(0.), F(0.), knx, kny, knz, k_null, 0u, 0u, u64(photon0), nphotons, max_events,
                    sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped};
-    launch_trace<F>(a, mu0, azimuth, inc_dir, inc_dif, seed, static_cast<hipStream_t>(stream));
+    launch_trace<F>(a, ph, mu0, azimuth, inc_dir, inc_dif, seed, static_cast<hipStream_t>(stream));
     RRX_CATCH(entry)
 }
 
@@ -307,7 +320,8 @@ int raytracer_sw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
                        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
                        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif,
                        int knx, int kny, int knz, long long photons_per_pixel, u64 seed, int max_events,
-                       F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, u64* n_capped, void* stream)
+                       F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, u64* n_capped, void* stream,
+                       const PhaseIn<F> ph = PhaseIn<F>{})
 {
     RRX_TRY
     if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"photons_per_pixel", photons_per_pixel}})) return 0;
@@ -316,6 +330,7 @@ int raytracer_sw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
                   {"sfc_dn_dir", sfc_dn_dir}, {"sfc_dn_dif", sfc_dn_dif}, {"sfc_up", sfc_up}, {"tod_up", tod_up}, {"abs_dir", abs_dir},
                   {"abs_dif", abs_dif}, {"n_capped", n_capped}});
     check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
+    check_phase(ph, cld_tau);
     check_scene(dx, dy, dz, mu0);
     for (int g=0; g<ngpt; ++g)
         if (inc_dir[g] < F(0.) || inc_dif[g] < F(0.)) throw std::runtime_error("inc_dir, inc_dif must be >= 0");
@@ -342,7 +357,7 @@ int raytracer_sw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
         TraceArgs<F> a{nx, ny, nz, nbnd, g, top_at_1 ? 1 : 0, independent_column ? 1 : 0, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g,
                        dx, dy, dz, sfc_albedo, F(0.), F(0.), F(0.), F(0.), knx, kny, knz, k_null, 0u, 0u, 0ull, nphotons, max_events,
                        c, c + ncol, c + 2*ncol, c + 3*ncol, c + n_sfc, c + n_sfc + ncol*nz, n_capped};
-        launch_trace<F>(a, mu0, azimuth, inc_dir[g], inc_dif[g], seed, st);
+        launch_trace<F>(a, ph, mu0, azimuth, inc_dir[g], inc_dif[g], seed, st);
         const F scale = (inc_dir[g] + inc_dif[g]) / F(photons_per_pixel);
         launch_counts_to_flux<F>(ncol, a.sfc_dn_dir, scale, sfc_dn_dir, st);
         launch_counts_to_flux<F>(ncol, a.sfc_dn_dif, scale, sfc_dn_dif, st);
@@ -379,7 +394,28 @@ int rrx_raytracer_sw##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool to
         F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, void* stream) \
 { return raytracer_sw_entry<F>("rrx_raytracer_sw" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
                                cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, \
-                               photons_per_pixel, seed, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream); }
+                               photons_per_pixel, seed, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream); } \
+int rrx_rt_trace_counts_phase##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, F inc_dir, F inc_dif, int knx, int kny, int knz, const F* k_null, \
+        unsigned long long seed, long long photon0, long long nphotons, int max_events, \
+        unsigned long long* sfc_dn_dir, unsigned long long* sfc_dn_dif, unsigned long long* sfc_up, unsigned long long* tod_up, \
+        unsigned long long* abs_dir, unsigned long long* abs_dif, unsigned long long* n_capped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, void* stream) \
+{ return trace_entry<F>("rrx_rt_trace_counts_phase" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
+                        cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, k_null, seed, \
+                        photon0, nphotons, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
+                        PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}); } \
+int rrx_raytracer_sw_phase##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
+        long long photons_per_pixel, unsigned long long seed, int max_events, \
+        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, void* stream) \
+{ return raytracer_sw_entry<F>("rrx_raytracer_sw_phase" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
+                               cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, \
+                               photons_per_pixel, seed, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
+                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}); }
 
 RRX_DEFINE_RT(double, _f64)
 RRX_DEFINE_RT(float, _f32)

@@ -46,7 +46,11 @@
 // SHAPE. One ray per lane, lanes refill from a round-robin list inside the event loop, the grid is capped as in trace_kernel. The
 // sun walk is a STATE of that one loop, which has one back edge: in a pass a lane either traces one event or walks one cell to the
 // sun, so that one lane's long walk does not idle the other 63 behind an inner loop (measured both ways: DESIGN 4.15).
-#include "rrx_rt_common.h"
+//
+// TABLE (trace_bw_kernel<F,true>; rrx_rt_phase.h): the cloud species scatters by the tabulated phase function of the
+// cell's radius: phase_eval towards the sun in the deposit, phase_sample for the new direction, the same draws in the same order.
+// The walk carries the radius where the Henyey-Greenstein form carries g_c; the nodes are staged in LDS once per workgroup.
+#include "rrx_rt_phase.h"
 #include "rrx_hip.h"
 
 namespace
@@ -73,7 +77,7 @@ struct BwArgs
 
 // the state of a walk to the sun: cell indices, the distances along -s to the next face of each axis, the distance covered, the
 // optical path so far, the deposit's factor in front of T_sun, and what follows the deposit (0: the surface's roulette, 1: a
-// Rayleigh scattering, 2: a cloud scattering with asymmetry gc)
+// Rayleigh scattering, 2: a cloud scattering with asymmetry gc; with a phase table gc holds the cell's radius)
 template<typename F>
 struct Walk
 {
@@ -103,11 +107,23 @@ __device__ __forceinline__ bool after_surface(Stream& rng, F& weight, F& ux, F& 
     return true;
 }
 
-template<typename F>
-__global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a)
+template<typename F, bool TABLE>
+__global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, const PhaseArgs<F,TABLE> ph)
 {
     const long long nthreads = (long long)gridDim.x*blockDim.x;
     long long next_ray = (long long)blockIdx.x*blockDim.x + threadIdx.x;
+
+    // the nodes, searched by every cloud scattering and shared by all lanes: nmu numbers of dynamic LDS (nmu <= 4096 on the host)
+    [[maybe_unused]] const F* mu_s = nullptr;
+    [[maybe_unused]] PhaseTable<F> tab{};
+    if constexpr (TABLE)
+    {
+        extern __shared__ double phase_lds[];
+        F* stage = reinterpret_cast<F*>(phase_lds);
+        for (int n=threadIdx.x; n<ph.in.nmu; n+=blockDim.x) stage[n] = ph.in.mu[n];
+        __syncthreads();
+        mu_s = stage;
+    }
 
     const int nx = a.nx, ny = a.ny, nz = a.nz;
     const size_t ncol = size_t(nx)*ny;
@@ -119,8 +135,9 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a)
     const F* __restrict__ tau_g = a.tau + ncol*nz*a.igpt;
     const F* __restrict__ ssa_g = a.ssa + ncol*nz*a.igpt;
     const F* __restrict__ ctau_b = ibnd >= 0 ? a.cld_tau + ncol*nz*ibnd : nullptr;
+    if constexpr (TABLE) tab = table_of_band(ph.in, ibnd);
     const F inf = F(INFINITY);
-    const F g_max = F(1.) - Lim<F>::eps();
+    [[maybe_unused]] const F g_max = F(1.) - Lim<F>::eps();
     const F pi = F(3.141592653589793);
     // towards the sun, and the distance along it across one cell of each axis
     const F vx = -a.sun_x, vy = -a.sun_y, vz = -a.sun_z;
@@ -168,6 +185,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a)
                 tally(a.counts, size_t(pix), to_count(clamped ? F(1048576.) : d));
                 walking = false;
                 if (w.then == 0) { alive = after_surface(rng, weight, ux, uy, uz); pending = false; }
+                else if constexpr (TABLE) scatter_direction_table(rng, w.then == 2, tab, mu_s, w.gc, ux, uy, uz);
                 else scatter_direction(rng, w.then == 2, w.gc, g_max, ux, uy, uz);
             }
             else if (w.steps >= a.max_walk) { atomicAdd(a.n_capped, 1ull); walking = false; alive = false; }
@@ -284,7 +302,8 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a)
                     if (ibnd >= 0)
                     {
                         const size_t cb = cell + ncol*nz*ibnd;
-                        tc = a.cld_tau[cb]; wc = a.cld_ssa[cb]; gc = a.cld_g[cb];
+                        tc = a.cld_tau[cb]; wc = a.cld_ssa[cb];
+                        if constexpr (!TABLE) gc = a.cld_g[cb];
                     }
                     const F k_ext = k_ext_of(t, tc, a.dz);
                     const F k_sca = (t*w0 + tc*wc) / a.dz;
@@ -298,7 +317,12 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a)
                         const bool cloud = rng.next<F>()*k_sca < k_sca_cld;
                         const F cs = clampf(-((ux*a.sun_x + uy*a.sun_y) + uz*a.sun_z), F(-1.), F(1.));
                         F phase;
-                        if (cloud)
+                        if constexpr (TABLE)
+                        {
+                            if (cloud) { gc = ph.in.cld_re[cell]; phase = phase_eval(tab, mu_s, gc, cs); }          // cld_re (ncol, nz): one radius for all bands
+                            else phase = F(0.75)*(F(1.) + cs*cs);
+                        }
+                        else if (cloud)
                         {
                             const F g = min(gc, g_max);
                             const F q = (F(1.) + g*g) - (F(2.)*g)*cs;
@@ -342,8 +366,8 @@ void check_sensor(const int type, const F fov, const F* s, const F dx, const F d
 }
 
 template<typename F>
-void launch_trace_bw(BwArgs<F> a, const F mu0, const F azimuth, const int type, const int npx, const int npy, const F fov, const F* s,
-                     const u64 seed, hipStream_t st)
+void launch_trace_bw(BwArgs<F> a, const PhaseIn<F>& ph, const F mu0, const F azimuth, const int type, const int npx, const int npy, const F fov,
+                     const F* s, const u64 seed, hipStream_t st)
 {
     const double st_ = std::sqrt(std::max(0.0, 1.0 - double(mu0)*double(mu0)));
     a.mu0 = mu0; a.sun_x = F(st_*std::cos(double(azimuth))); a.sun_y = F(st_*std::sin(double(azimuth))); a.sun_z = -mu0;
@@ -352,7 +376,8 @@ void launch_trace_bw(BwArgs<F> a, const F mu0, const F azimuth, const int type, 
     a.px = s[0]; a.py = s[1]; a.pz = s[2]; a.wx = s[3]; a.wy = s[4]; a.wz = s[5]; a.hx = s[6]; a.hy = s[7]; a.hz = s[8];
     a.ex = s[9]; a.ey = s[10]; a.ez = s[11];
     const int blocks = int(std::min<long long>((a.nrays + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
-    trace_bw_kernel<F><<<blocks, RT_BLOCK, 0, st>>>(a);
+    if (ph.given()) trace_bw_kernel<F,true><<<blocks, RT_BLOCK, size_t(ph.nmu)*sizeof(F), st>>>(a, PhaseArgs<F,true>{ph});
+    else trace_bw_kernel<F,false><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,false>{});
 }
 
 template<typename F>
@@ -375,7 +400,7 @@ int trace_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd
                    const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
                    F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null,
                    int sensor_type, int npx, int npy, F fov, const F* sensor, u64 seed, long long ray0, long long nrays, int max_events,
-                   u64* counts, u64* n_capped, u64* n_clamped, void* stream)
+                   u64* counts, u64* n_capped, u64* n_clamped, void* stream, const PhaseIn<F> ph = PhaseIn<F>{})
 {
     RRX_TRY
     if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"npx", npx}, {"npy", npy}, {"nrays", nrays}})) return 0;
@@ -384,6 +409,7 @@ int trace_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd
     check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"k_null", k_null}, {"sensor", sensor}, {"counts", counts},
                   {"n_capped", n_capped}, {"n_clamped", n_clamped}});
     check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
+    check_phase(ph, cld_tau);
     if (igpt < 0 || igpt >= ngpt) throw std::runtime_error("igpt is outside [0, ngpt)");
     check_scene(dx, dy, dz, mu0);
     if (max_events < 1) throw std::runtime_error("max_events must be >= 1");
@@ -393,7 +419,7 @@ int trace_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd
     check_sensor(sensor_type, fov, sensor, dx, dy, dz, nx, ny, nz, mu0, max_walk);
     BwArgs<F> a = scene_args<F>(nx, ny, nz, nbnd, igpt, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo,
                                 knx, kny, knz, k_null, u64(ray0), nrays, max_events, max_walk, counts, n_capped, n_clamped);
-    launch_trace_bw<F>(a, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, static_cast<hipStream_t>(stream));
+    launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, static_cast<hipStream_t>(stream));
     RRX_CATCH(entry)
 }
 
@@ -412,7 +438,7 @@ int raytracer_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
                        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
                        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz,
                        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, u64 seed, int max_events,
-                       F* radiance, u64* n_capped, u64* n_clamped, void* stream)
+                       F* radiance, u64* n_capped, u64* n_clamped, void* stream, const PhaseIn<F> ph = PhaseIn<F>{})
 {
     RRX_TRY
     if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"npx", npx}, {"npy", npy}, {"rays_per_pixel", rays_per_pixel}})) return 0;
@@ -420,6 +446,7 @@ int raytracer_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
     check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"inc_dir", inc_dir}, {"sensor", sensor}, {"radiance", radiance},
                   {"n_capped", n_capped}, {"n_clamped", n_clamped}});
     check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
+    check_phase(ph, cld_tau);
     check_scene(dx, dy, dz, mu0);
     for (int g=0; g<ngpt; ++g)
         if (inc_dir[g] < F(0.)) throw std::runtime_error("inc_dir must be >= 0");
@@ -448,7 +475,7 @@ int raytracer_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
             throw std::runtime_error(rrx_last_error());
         BwArgs<F> a = scene_args<F>(nx, ny, nz, nbnd, g, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo,
                                     knx, kny, knz, k_null, 0ull, nrays, max_events, max_walk, counts, n_capped, n_clamped);
-        launch_trace_bw<F>(a, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, st);
+        launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, st);
         const F scale = inc_dir[g] / (mu0*F(rays_per_pixel));
         if (counts_to_flux_of((long long)npix, counts, scale, radiance, stream) != 0) throw std::runtime_error(rrx_last_error());
     }
@@ -474,7 +501,26 @@ int rrx_raytracer_bw##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool to
         F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream) \
 { return raytracer_bw_entry<F>("rrx_raytracer_bw" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, \
                                dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, \
-                               rays_per_pixel, seed, max_events, radiance, n_capped, n_clamped, stream); }
+                               rays_per_pixel, seed, max_events, radiance, n_capped, n_clamped, stream); } \
+int rrx_rt_bw_trace_counts_phase##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
+        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, void* stream) \
+{ return trace_bw_entry<F>("rrx_rt_bw_trace_counts_phase" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, \
+                           cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, knx, kny, knz, k_null, sensor_type, npx, npy, fov, sensor, seed, ray0, \
+                           nrays, max_events, counts, n_capped, n_clamped, stream, PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}); } \
+int rrx_raytracer_bw_phase##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
+        F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, void* stream) \
+{ return raytracer_bw_entry<F>("rrx_raytracer_bw_phase" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, \
+                               dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, \
+                               rays_per_pixel, seed, max_events, radiance, n_capped, n_clamped, stream, \
+                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}); }
 
 RRX_DEFINE_RT_BW(double, _f64)
 RRX_DEFINE_RT_BW(float, _f32)

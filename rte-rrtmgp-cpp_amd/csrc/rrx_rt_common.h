@@ -85,30 +85,18 @@ __device__ __forceinline__ void lambert(Stream& rng, const F sign, F& ux, F& uy,
     ux = s*cos(phi); uy = s*sin(phi); uz = sign*mu;
 }
 
-// the new direction after a scattering: u -> cos of the scattering angle (Henyey-Greenstein with g = min(gc, g_max) for cloud,
-// Rayleigh otherwise), u -> phi
-template<typename F>
-__device__ __forceinline__ void scatter_direction(Stream& rng, const bool cloud, const F gc, const F g_max, F& ux, F& uy, F& uz)
+// the cosine of a Rayleigh scattering angle from one uniform: the root of mu^3 + 3 mu = 2 q, q = 4u - 2
+template<typename F> __device__ __forceinline__ F rayleigh_cos(const F u)
 {
-    const F u = rng.next<F>();
-    F cos_s;
-    if (cloud)
-    {
-        const F g = min(gc, g_max);
-        if (fabs(g) < F(1.e-6)) cos_s = F(2.)*u - F(1.);
-        else
-        {
-            const F s = (F(1.) - g*g) / ((F(1.) - g) + (F(2.)*g)*u);
-            cos_s = ((F(1.) + g*g) - s*s) / (F(2.)*g);
-        }
-    }
-    else          // Rayleigh: the root of mu^3 + 3 mu = 2 q, q = 4u - 2
-    {
-        const F q = F(4.)*u - F(2.);
-        const F A = cbrt(q + sqrt(F(1.) + q*q));
-        cos_s = A - F(1.)/A;
-    }
-    cos_s = clampf(cos_s, F(-1.), F(1.));
+    const F q = F(4.)*u - F(2.);
+    const F A = cbrt(q + sqrt(F(1.) + q*q));
+    return A - F(1.)/A;
+}
+
+// the direction at the angle acos(cos_s) from u: u -> phi
+template<typename F>
+__device__ __forceinline__ void rotate_direction(Stream& rng, const F cos_s, F& ux, F& uy, F& uz)
+{
     const F sin_s = sqrt(max(F(0.), F(1.) - cos_s*cos_s));
     const F phi = F(6.283185307179586) * rng.next<F>();
     const F cp = cos(phi), sp = sin(phi);
@@ -126,6 +114,27 @@ __device__ __forceinline__ void scatter_direction(Stream& rng, const bool cloud,
     }
     const F nrm = sqrt((vx*vx + vy*vy) + vz*vz);
     ux = vx/nrm; uy = vy/nrm; uz = vz/nrm;
+}
+
+// the new direction after a scattering: u -> cos of the scattering angle (Henyey-Greenstein with g = min(gc, g_max) for cloud,
+// Rayleigh otherwise), u -> phi
+template<typename F>
+__device__ __forceinline__ void scatter_direction(Stream& rng, const bool cloud, const F gc, const F g_max, F& ux, F& uy, F& uz)
+{
+    const F u = rng.next<F>();
+    F cos_s;
+    if (cloud)
+    {
+        const F g = min(gc, g_max);
+        if (fabs(g) < F(1.e-6)) cos_s = F(2.)*u - F(1.);
+        else
+        {
+            const F s = (F(1.) - g*g) / ((F(1.) - g) + (F(2.)*g)*u);
+            cos_s = ((F(1.) + g*g) - s*s) / (F(2.)*g);
+        }
+    }
+    else cos_s = rayleigh_cos(u);
+    rotate_direction(rng, clampf(cos_s, F(-1.), F(1.)), ux, uy, uz);
 }
 
 // ---- host side: the argument checks of the entries (they throw; RRX_CATCH names the entry)

@@ -585,6 +585,44 @@ class HipKernels:
         nbnd = int(band_lims.shape[0]) if band_lims is not None else 0
         return (int(nx), int(ny), nz, ngpt, nbnd), (band_lims if cloud is not None else None, ct, cw, cg)
 
+    # Tabulated cloud phase functions (rrx_rt_phase_*, the rrx_*_phase twins of the four tracer entries). phase=: None
+    # (Henyey-Greenstein from cld_g, the entries above) or an object with mu (nmu,), phase, cdf (nbnd, nre, nmu), re0, dre and
+    # cld_re (nz, ncol), such as phase_tables.PhaseTable.
+    def _rt_phase(self, who, phase, dims):
+        """(the entry's name, the eight arguments in front of the stream)"""
+        if phase is None:
+            return who, ()
+        if phase.cld_re is None:
+            raise ValueError(f"{who}: the phase table has no cell radius (PhaseTable.with_radius)")
+        nbnd, nre, nmu = phase.phase.shape
+        if nbnd != dims[4] or tuple(phase.cdf.shape) != (nbnd, nre, nmu) or tuple(phase.mu.shape) != (nmu,):
+            raise ValueError(f"{who}: phase, cdf are (nbnd = {dims[4]}, nre, nmu) and mu (nmu,), got {tuple(phase.phase.shape)}, "
+                             f"{tuple(phase.cdf.shape)}, {tuple(phase.mu.shape)}")
+        if tuple(phase.cld_re.shape) != (dims[2], dims[0]*dims[1]):
+            raise ValueError(f"{who}: cld_re is (nz, ncol) = {(dims[2], dims[0]*dims[1])}, got {tuple(phase.cld_re.shape)}")
+        return who + "_phase", (nmu, nre, phase.re0, phase.dre, phase.mu, phase.phase, phase.cdf, phase.cld_re)
+
+    def rt_phase_tables(self, mu, phase_raw):
+        """phase, cdf (nbnd, nre, nmu) from the nodes mu (nmu,) and phase_raw (nbnd, nre, nmu) >= 0 of any normalisation."""
+        nbnd, nre, nmu = phase_raw.shape
+        phase, cdf = self.empty((nbnd, nre, nmu)), self.empty((nbnd, nre, nmu))
+        self._c("rt_phase_tables", nmu, nre, nbnd, mu, phase_raw, phase, cdf)
+        return phase, cdf
+
+    def _rt_phase_array(self, entry, table, ibnd, values, re):
+        nbnd, nre, nmu = table.phase.shape
+        out = self.empty(tuple(values.shape))
+        self._c(entry, values.numel(), nmu, nre, nbnd, ibnd, table.re0, table.dre, table.mu, table.phase, table.cdf, values, re, out)
+        return out
+
+    def rt_phase_sample(self, table, ibnd, u, re):
+        """The cosines that the tracers draw from the uniforms u in cells of radius re (the same shape), band ibnd (0-based)."""
+        return self._rt_phase_array("rt_phase_sample", table, ibnd, u, re)
+
+    def rt_phase_eval(self, table, ibnd, cs, re):
+        """P(cs) at radius re: the density of rt_phase_sample."""
+        return self._rt_phase_array("rt_phase_eval", table, ibnd, cs, re)
+
     def rt_zero_counts(self, nz, ncol):
         out = {k: torch.zeros((ncol,), dtype=torch.int64, device=self.device) for k in self.RT_COUNTS[:4]}
         out.update({k: torch.zeros((nz, ncol), dtype=torch.int64, device=self.device) for k in self.RT_COUNTS[4:]})
@@ -601,14 +639,15 @@ class HipKernels:
 
     def rt_trace_counts(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, k_null, seed,
                         photon0, nphotons, top_at_1=False, independent_column=False, cloud=None, band_lims=None, counts=None,
-                        max_events=None):
+                        max_events=None, phase=None):
         """Adds the photons [photon0, photon0 + nphotons) of g-point igpt into counts (rt_zero_counts; made when None)."""
         dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
         knx, kny, knz = (int(k) for k in kn_grid)
         counts = self.rt_zero_counts(dims[2], dims[0]*dims[1]) if counts is None else counts
-        self._c("rt_trace_counts", *dims, igpt, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth,
+        entry, table = self._rt_phase("rt_trace_counts", phase, dims)
+        self._c(entry, *dims, igpt, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth,
                 inc_dir, inc_dif, knx, kny, knz, k_null, int(seed) & 0xFFFFFFFFFFFFFFFF, photon0, nphotons,
-                self.RT_MAX_EVENTS if max_events is None else max_events, *(counts[k] for k in self.RT_COUNTS), counts["n_capped"])
+                self.RT_MAX_EVENTS if max_events is None else max_events, *(counts[k] for k in self.RT_COUNTS), counts["n_capped"], *table)
         return counts
 
     def rt_counts_to_flux(self, counts, scale, out):
@@ -617,7 +656,7 @@ class HipKernels:
         return out
 
     def raytracer_sw(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, photons_per_pixel, seed,
-                     top_at_1=False, independent_column=False, cloud=None, band_lims=None, max_events=None):
+                     top_at_1=False, independent_column=False, cloud=None, band_lims=None, max_events=None, phase=None):
         """The spectral loop in one call. inc_dir, inc_dif: (ngpt,) numbers on the host. Returns the four surface / top fluxes
         (ncol,) in W m-2, abs_dir / abs_dif (nz, ncol) in W m-3 and n_capped (int)."""
         dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
@@ -630,9 +669,10 @@ class HipKernels:
         out = {k: self.empty((ncol,)) for k in self.RT_COUNTS[:4]}
         out.update({k: self.empty((nz, ncol)) for k in self.RT_COUNTS[4:]})
         n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        self._c("raytracer_sw", *dims, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir,
+        entry, table = self._rt_phase("raytracer_sw", phase, dims)
+        self._c(entry, *dims, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir,
                 inc_dif, knx, kny, knz, photons_per_pixel, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                self.RT_MAX_EVENTS if max_events is None else max_events, *(out[k] for k in self.RT_COUNTS), n_capped)
+                self.RT_MAX_EVENTS if max_events is None else max_events, *(out[k] for k in self.RT_COUNTS), n_capped, *table)
         out["n_capped"] = int(n_capped.item())
         return out
 
@@ -646,20 +686,21 @@ class HipKernels:
         return {k: torch.zeros((n,), dtype=torch.int64, device=self.device) for k, n in (("counts", npix), ("n_capped", 1), ("n_clamped", 1))}
 
     def rt_bw_trace_counts(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, kn_grid, k_null, camera, seed, ray0, nrays,
-                           top_at_1=False, cloud=None, band_lims=None, counts=None, max_events=None):
+                           top_at_1=False, cloud=None, band_lims=None, counts=None, max_events=None, phase=None):
         """Adds the rays [ray0, ray0 + nrays) of g-point igpt into counts (rt_bw_zero_counts; made when None): counts (npix,),
         n_capped, n_clamped, int64 tensors holding unsigned 64-bit numbers."""
         dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
         knx, kny, knz = (int(k) for k in kn_grid)
         sensor = self._rt_sensor(camera)
         counts = self.rt_bw_zero_counts(sensor[1]*sensor[2]) if counts is None else counts
-        self._c("rt_bw_trace_counts", *dims, igpt, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, knx, kny, knz,
+        entry, table = self._rt_phase("rt_bw_trace_counts", phase, dims)
+        self._c(entry, *dims, igpt, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, knx, kny, knz,
                 k_null, *sensor, int(seed) & 0xFFFFFFFFFFFFFFFF, ray0, nrays, self.RT_MAX_EVENTS if max_events is None else max_events,
-                counts["counts"], counts["n_capped"], counts["n_clamped"])
+                counts["counts"], counts["n_capped"], counts["n_clamped"], *table)
         return counts
 
     def raytracer_bw(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
-                     top_at_1=False, cloud=None, band_lims=None, max_events=None):
+                     top_at_1=False, cloud=None, band_lims=None, max_events=None, phase=None):
         """The spectral loop in one call. inc_dir: (ngpt,) numbers on the host. Returns radiance (npy, npx) in W m-2 sr-1, n_capped and
         n_clamped (ints)."""
         dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
@@ -671,9 +712,10 @@ class HipKernels:
         radiance = self.empty((sensor[2], sensor[1]))
         n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
         n_clamped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        self._c("raytracer_bw", *dims, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz,
+        entry, table = self._rt_phase("raytracer_bw", phase, dims)
+        self._c(entry, *dims, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz,
                 *sensor, rays_per_pixel, int(seed) & 0xFFFFFFFFFFFFFFFF, self.RT_MAX_EVENTS if max_events is None else max_events,
-                radiance, n_capped, n_clamped)
+                radiance, n_capped, n_clamped, *table)
         return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
 
     def delta_scale_2str_k(self, tau, ssa, g):

@@ -35,7 +35,19 @@ unsigned long long Raytracer_gpu::trace_rays(
     for (const Array_gpu<Float,2>* a : {&abs_dir, &abs_dif})
         if (a->dim(1) != ncol || a->dim(2) != nz) throw std::runtime_error("Raytracer_gpu::trace_rays: an absorption array is not (nx ny, nz)");
 
+    if (has_table && (cld_re.dim(1) != ncol || cld_re.dim(2) != nz || phase.dim(3) != nbnd))
+        throw std::runtime_error("Raytracer_gpu::trace_rays: the phase table's cld_re is not (nx ny, nz) or its tables are not (nmu, nre, nbnd)");
+
     Array_gpu<unsigned long long,1> n_capped({1});
+    if (has_table)
+        RRX_CALL(rrx_raytracer_sw_phase, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
+                 tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
+                 cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
+                 dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), inc_dif.ptr(), knx, kny, knz,
+                 photons_per_pixel, seed, max_events,
+                 sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr(),
+                 mu.dim(1), phase.dim(2), re0, dre, mu.ptr(), phase.ptr(), cdf.ptr(), cld_re.ptr());
+    else
     RRX_CALL(rrx_raytracer_sw, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
              tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
              cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
@@ -43,4 +55,14 @@ unsigned long long Raytracer_gpu::trace_rays(
              photons_per_pixel, seed, max_events,
              sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr());
     return n_capped({1});
+}
+
+void Raytracer_gpu::set_phase_table(const Array_gpu<Float,1>& mu_in, const Array_gpu<Float,3>& phase_in, const Array_gpu<Float,3>& cdf_in,
+                            const Float re0_in, const Float dre_in, const Array_gpu<Float,2>& cld_re_in)
+{
+    if (mu_in.size() < 2 || phase_in.dim(1) != mu_in.size() || cdf_in.get_dims() != phase_in.get_dims())
+        throw std::runtime_error("Raytracer_gpu::set_phase_table: mu is not (nmu >= 2) or phase, cdf are not (nmu, nre, nbnd)");
+    if (cld_re_in.size() == 0) throw std::runtime_error("Raytracer_gpu::set_phase_table: cld_re is empty");
+    mu = mu_in; phase = phase_in; cdf = cdf_in; cld_re = cld_re_in; re0 = re0_in; dre = dre_in;
+    has_table = true;
 }

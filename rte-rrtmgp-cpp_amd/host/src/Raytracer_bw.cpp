@@ -35,7 +35,18 @@ unsigned long long Raytracer_bw_gpu::trace_rays_bw(
 
     const Float numbers[12] = {sensor.position[0], sensor.position[1], sensor.position[2], sensor.e_w[0], sensor.e_w[1], sensor.e_w[2],
                                sensor.e_h[0], sensor.e_h[1], sensor.e_h[2], sensor.e_d[0], sensor.e_d[1], sensor.e_d[2]};
+    if (has_table && (cld_re.dim(1) != ncol || cld_re.dim(2) != nz || phase.dim(3) != nbnd))
+        throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: the phase table's cld_re is not (nx ny, nz) or its tables are not (nmu, nre, nbnd)");
     Array_gpu<unsigned long long,1> tallies({2});
+    if (has_table)
+        RRX_CALL(rrx_raytracer_bw_phase, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1),
+                 tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
+                 cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
+                 dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), knx, kny, knz,
+                 sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers, rays_per_pixel, seed, max_events,
+                 radiance.ptr(), tallies.ptr(), tallies.ptr() + 1,
+                 mu.dim(1), phase.dim(2), re0, dre, mu.ptr(), phase.ptr(), cdf.ptr(), cld_re.ptr());
+    else
     RRX_CALL(rrx_raytracer_bw, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1),
              tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
              cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
@@ -44,4 +55,14 @@ unsigned long long Raytracer_bw_gpu::trace_rays_bw(
              radiance.ptr(), tallies.ptr(), tallies.ptr() + 1);
     if (n_clamped_out != nullptr) *n_clamped_out = tallies({2});
     return tallies({1});
+}
+
+void Raytracer_bw_gpu::set_phase_table(const Array_gpu<Float,1>& mu_in, const Array_gpu<Float,3>& phase_in, const Array_gpu<Float,3>& cdf_in,
+                            const Float re0_in, const Float dre_in, const Array_gpu<Float,2>& cld_re_in)
+{
+    if (mu_in.size() < 2 || phase_in.dim(1) != mu_in.size() || cdf_in.get_dims() != phase_in.get_dims())
+        throw std::runtime_error("Raytracer_bw_gpu::set_phase_table: mu is not (nmu >= 2) or phase, cdf are not (nmu, nre, nbnd)");
+    if (cld_re_in.size() == 0) throw std::runtime_error("Raytracer_bw_gpu::set_phase_table: cld_re is empty");
+    mu = mu_in; phase = phase_in; cdf = cdf_in; cld_re = cld_re_in; re0 = re0_in; dre = dre_in;
+    has_table = true;
 }

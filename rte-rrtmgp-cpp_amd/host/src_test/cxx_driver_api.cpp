@@ -200,11 +200,15 @@ int rrx_cxx_driver_fluxes(void* h, const Float** ptrs)
 // Raytracer_gpu::trace_rays on device arrays the caller owns (views; needs no driver handle). tau, ssa (ncol, nz, ngpt); band_lims_gpt
 // (2, nbnd); cld_* (ncol, nz, nbnd) or all NULL; sfc_albedo (ncol); inc_dir, inc_dif (ngpt) on the HOST; out6: device arrays sfc_dn_dir,
 // sfc_dn_dif, sfc_up, tod_up (ncol), abs_dir, abs_dif (ncol, nz). Runs on `stream` and waits for the count of dropped photons.
-int rrx_cxx_trace_rays(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+// rrx_cxx_trace_rays_phase: the same after Raytracer_gpu::set_phase_table(mu (nmu), phase, cdf (nmu, nre, nbnd), re0, dre, cld_re (ncol, nz)),
+// device arrays; with mu NULL no table is set.
+int rrx_cxx_trace_rays_phase(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
         const int top_at_1, const int independent_column, const Float* tau, const Float* ssa, const int* band_lims_gpt,
         const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
         const Float* inc_dir, const Float* inc_dif, const int knx, const int kny, const int knz, const long long photons_per_pixel,
-        const unsigned long long seed, const int max_events, Float* const* out6, unsigned long long* n_capped, void* stream)
+        const unsigned long long seed, const int max_events, Float* const* out6, unsigned long long* n_capped,
+        const int nmu, const int nre, const Float re0, const Float dre, const Float* mu, const Float* phase, const Float* cdf, const Float* cld_re,
+        void* stream)
 {
     return guarded([&]
     {
@@ -219,6 +223,8 @@ int rrx_cxx_trace_rays(const int nx, const int ny, const int nz, const int ngpt,
             Array_gpu<Float,1> o0 = view1(out6[0], ncol), o1 = view1(out6[1], ncol), o2 = view1(out6[2], ncol), o3 = view1(out6[3], ncol);
             Array_gpu<Float,2> o4 = view2(out6[4], ncol, nz), o5 = view2(out6[5], ncol, nz);
             Raytracer_gpu raytracer;
+            if (mu != nullptr)
+                raytracer.set_phase_table(view1(mu, nmu), view3(phase, nmu, nre, nbnd), view3(cdf, nmu, nre, nbnd), re0, dre, view2(cld_re, ncol, nz));
             *n_capped = raytracer.trace_rays(nx, ny, nz, dx, dy, dz, top_at_1 != 0, independent_column != 0,
                     view3(tau, ncol, nz, ngpt), view3(ssa, ncol, nz, ngpt), Array_gpu<int,2>(const_cast<int*>(band_lims_gpt), {2, nbnd}),
                     view3(cld_tau, ncol, nz, nbnd), view3(cld_ssa, ncol, nz, nbnd), view3(cld_g, ncol, nz, nbnd), view1(sfc_albedo, ncol),
@@ -229,15 +235,29 @@ int rrx_cxx_trace_rays(const int nx, const int ny, const int nz, const int ngpt,
     });
 }
 
+int rrx_cxx_trace_rays(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+        const int top_at_1, const int independent_column, const Float* tau, const Float* ssa, const int* band_lims_gpt,
+        const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
+        const Float* inc_dir, const Float* inc_dif, const int knx, const int kny, const int knz, const long long photons_per_pixel,
+        const unsigned long long seed, const int max_events, Float* const* out6, unsigned long long* n_capped, void* stream)
+{
+    return rrx_cxx_trace_rays_phase(nx, ny, nz, ngpt, nbnd, dx, dy, dz, top_at_1, independent_column, tau, ssa, band_lims_gpt, cld_tau, cld_ssa,
+                                    cld_g, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, photons_per_pixel, seed, max_events, out6,
+                                    n_capped, 0, 0, Float(0.), Float(0.), nullptr, nullptr, nullptr, nullptr, stream);
+}
+
 // Raytracer_bw_gpu::trace_rays_bw on device arrays the caller owns (views; needs no driver handle). The scene as for rrx_cxx_trace_rays;
 // inc_dir (ngpt) and sensor (12 numbers: position, e_w, e_h, e_d) on the HOST; radiance: a device array (npx, npy). Runs on `stream`
 // and waits for the counts of dropped rays and clamped deposits.
-int rrx_cxx_trace_rays_bw(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+// rrx_cxx_trace_rays_bw_phase: the same after Raytracer_bw_gpu::set_phase_table, as rrx_cxx_trace_rays_phase.
+int rrx_cxx_trace_rays_bw_phase(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
         const int top_at_1, const Float* tau, const Float* ssa, const int* band_lims_gpt,
         const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
         const Float* inc_dir, const int knx, const int kny, const int knz, const int sensor_type, const int npx, const int npy, const Float fov,
         const Float* sensor, const long long rays_per_pixel, const unsigned long long seed, const int max_events, Float* radiance,
-        unsigned long long* n_capped, unsigned long long* n_clamped, void* stream)
+        unsigned long long* n_capped, unsigned long long* n_clamped,
+        const int nmu, const int nre, const Float re0, const Float dre, const Float* mu, const Float* phase, const Float* cdf, const Float* cld_re,
+        void* stream)
 {
     return guarded([&]
     {
@@ -254,6 +274,8 @@ int rrx_cxx_trace_rays_bw(const int nx, const int ny, const int nz, const int ng
             for (int i=0; i<3; ++i) { s.position[i] = sensor[i]; s.e_w[i] = sensor[3+i]; s.e_h[i] = sensor[6+i]; s.e_d[i] = sensor[9+i]; }
             Array_gpu<Float,2> out = view2(radiance, npx, npy);
             Raytracer_bw_gpu raytracer;
+            if (mu != nullptr)
+                raytracer.set_phase_table(view1(mu, nmu), view3(phase, nmu, nre, nbnd), view3(cdf, nmu, nre, nbnd), re0, dre, view2(cld_re, ncol, nz));
             *n_capped = raytracer.trace_rays_bw(nx, ny, nz, dx, dy, dz, top_at_1 != 0,
                     view3(tau, ncol, nz, ngpt), view3(ssa, ncol, nz, ngpt), Array_gpu<int,2>(const_cast<int*>(band_lims_gpt), {2, nbnd}),
                     view3(cld_tau, ncol, nz, nbnd), view3(cld_ssa, ncol, nz, nbnd), view3(cld_g, ncol, nz, nbnd), view1(sfc_albedo, ncol),
@@ -262,5 +284,17 @@ int rrx_cxx_trace_rays_bw(const int nx, const int ny, const int nz, const int ng
         catch (...) { rrx_host::set_stream(before); throw; }
         rrx_host::set_stream(before);
     });
+}
+
+int rrx_cxx_trace_rays_bw(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+        const int top_at_1, const Float* tau, const Float* ssa, const int* band_lims_gpt,
+        const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
+        const Float* inc_dir, const int knx, const int kny, const int knz, const int sensor_type, const int npx, const int npy, const Float fov,
+        const Float* sensor, const long long rays_per_pixel, const unsigned long long seed, const int max_events, Float* radiance,
+        unsigned long long* n_capped, unsigned long long* n_clamped, void* stream)
+{
+    return rrx_cxx_trace_rays_bw_phase(nx, ny, nz, ngpt, nbnd, dx, dy, dz, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, sfc_albedo,
+                                       mu0, azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, rays_per_pixel, seed, max_events,
+                                       radiance, n_capped, n_clamped, 0, 0, Float(0.), Float(0.), nullptr, nullptr, nullptr, nullptr, stream);
 }
 }

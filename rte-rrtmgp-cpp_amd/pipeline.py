@@ -183,7 +183,7 @@ def solve_sw(be, kd, atm, col_dry=None, cloud_lut=None, delta_cloud=False, do_br
 
 
 def raytrace_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, photons_per_pixel, seed, cloud_lut=None, kn_grid=None,
-                independent_column=False, sfc_albedo=None, max_events=None):
+                independent_column=False, sfc_albedo=None, max_events=None, phase_table=None):
     """3-D shortwave surface / top fluxes and absorption from the forward Monte Carlo ray tracer (rrx_raytracer_sw).
 
     The atmosphere's columns are the pixels of an nx x ny domain (column = ix + nx iy) of cells dx x dy x dz metres, periodic in x
@@ -192,22 +192,35 @@ def raytrace_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, photons_per_pixel, 
     incident flux. azimuth: direction of travel of the direct beam, radians from +x. kn_grid = (knx, kny, knz) dividing (nx, ny,
     nlay), default one block per cell. sfc_albedo (ncol,): default the atmosphere's, which must then be the same in every band and
     for direct and diffuse light (the tracer's surface is Lambertian with one broadband albedo per pixel).
+    phase_table (phase_tables.PhaseTable, needs cloud_lut): cloud scatters by the tabulated phase function of the liquid radius
+    atm.rel in place of Henyey-Greenstein.
     Returns sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up (ncol,) in W m-2, abs_dir, abs_dif (nlay, ncol) in W m-3 and n_capped."""
     tau, ssa, cld, sfc_albedo, mu0, inc_dir, kn_grid = _raytracer_inputs("raytrace_sw", be, kd_sw, atm, nx, ny, cloud_lut, kn_grid, sfc_albedo)
+    phase = _raytracer_phase("raytrace_sw", atm, cloud_lut, phase_table)
     return be.raytracer_sw(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, np.zeros_like(inc_dir), kn_grid,
                            photons_per_pixel, seed, top_at_1=atm.top_at_1, independent_column=independent_column, cloud=cld,
-                           band_lims=kd_sw.band_lims_gpt, max_events=max_events)
+                           band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase)
 
 
 def render_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, camera, rays_per_pixel, seed, cloud_lut=None, kn_grid=None,
-              sfc_albedo=None, max_events=None):
+              sfc_albedo=None, max_events=None, phase_table=None):
     """Shortwave radiances for a virtual camera or a flux sensor from the backward Monte Carlo ray tracer (rrx_raytracer_bw, DESIGN
     4.15): the twin of raytrace_sw, on the same domain, sun, optics and albedo, with the same checks. camera: camera.perspective /
     fisheye / orthographic / flux_sensor. Returns radiance (npy, npx) in W m-2 sr-1 (scattered and reflected sunlight; the sun's
-    disk is not imaged), n_capped and n_clamped."""
+    disk is not imaged), n_capped and n_clamped. phase_table: as in raytrace_sw."""
     tau, ssa, cld, sfc_albedo, mu0, inc_dir, kn_grid = _raytracer_inputs("render_sw", be, kd_sw, atm, nx, ny, cloud_lut, kn_grid, sfc_albedo)
+    phase = _raytracer_phase("render_sw", atm, cloud_lut, phase_table)
     return be.raytracer_bw(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
-                           top_at_1=atm.top_at_1, cloud=cld, band_lims=kd_sw.band_lims_gpt, max_events=max_events)
+                           top_at_1=atm.top_at_1, cloud=cld, band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase)
+
+
+def _raytracer_phase(who, atm, cloud_lut, phase_table):
+    """The table with the cells' radius: the liquid effective radius atm.rel (nlay, ncol), as in the reference."""
+    if phase_table is None:
+        return None
+    if cloud_lut is None:
+        raise ValueError(f"{who}: a phase table needs cloud_lut (the table replaces the phase function of the cloud optics)")
+    return phase_table.with_radius(atm.rel)
 
 
 def _raytracer_inputs(who, be, kd_sw, atm, nx, ny, cloud_lut, kn_grid, sfc_albedo):
