@@ -10,34 +10,12 @@ import pytest
 
 import raytracer_ref as R
 import raytracer_scenes as S
+from raytracer_dev import _be, _dev, _u64, forward, solve_fw
 from rte_rrtmgp_cpp_amd import synthetic, pipeline
 
 pytestmark = pytest.mark.gpu
 ONE = float(1 << 32)
 NAMES = R.COUNT_NAMES
-
-
-def _be(dt, hip_f64, hip_f32):
-    return hip_f64 if dt == "f64" else hip_f32
-
-
-def _dev(be, sc):
-    A = be.asarray
-    return dict(tau=A(sc.tau), ssa=A(sc.ssa), alb=A(sc.sfc_albedo), cloud=None if sc.cloud is None else tuple(A(c) for c in sc.cloud),
-                lims=None if sc.band_lims is None else A(sc.band_lims))
-
-
-def _u64(be, t):
-    return be.to_numpy(t).view(np.uint64)
-
-
-def trace(be, sc, d, g, photon0, nphotons, k_null=None, counts=None):
-    if k_null is None:
-        k_null = be.rt_k_null(d["tau"], g, sc.nx, sc.ny, sc.dz, sc.kn_grid, sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"])
-    return be.rt_trace_counts(d["tau"], d["ssa"], g, sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth,
-                              float(sc.inc_dir[g]), float(sc.inc_dif[g]), sc.kn_grid, k_null, sc.seed, photon0, nphotons,
-                              top_at_1=sc.top_at_1, independent_column=sc.independent_column, cloud=d["cloud"], band_lims=d["lims"],
-                              counts=counts)
 
 
 def hand_loop(be, sc, d, ppp):
@@ -51,7 +29,7 @@ def hand_loop(be, sc, d, ppp):
         if not inc > 0:
             per_g.append(None)
             continue
-        c = trace(be, sc, d, g, 0, ppp*sc.ncol)
+        c = forward(be, sc, d, g, 0, ppp*sc.ncol)
         scale = inc / F(ppp)
         for k in NAMES:
             be.rt_counts_to_flux(c[k], float(scale if k in NAMES[:4] else scale / F(sc.dz)), flux[k])
@@ -61,11 +39,9 @@ def hand_loop(be, sc, d, ppp):
 
 
 def solve(be, sc, d, ppp):
-    r = be.raytracer_sw(d["tau"], d["ssa"], sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, sc.inc_dir, sc.inc_dif,
-                        sc.kn_grid, ppp, sc.seed, top_at_1=sc.top_at_1, independent_column=sc.independent_column, cloud=d["cloud"],
-                        band_lims=d["lims"])
+    r = solve_fw(be, sc, d, ppp)
     assert r["n_capped"] == 0
-    return {k: (be.to_numpy(v) if k != "n_capped" else v) for k, v in r.items()}
+    return r
 
 
 def check_beer(sc, per_g, ppp, label):
@@ -128,7 +104,7 @@ def test_c_shadow_displacement(along, top_at_1, hip_f64):
     lit, dark = hi == 0.0, lo > 40.0           # (a full chord through the block is tau = 70: 256 e^-40 photons are none)
     assert lit.sum() == sc.ncol - 8 and dark.sum() == 4
     ppp = 256
-    c = trace(be, sc, _dev(be, sc), 0, 0, ppp*sc.ncol)
+    c = forward(be, sc, _dev(be, sc), 0, 0, ppp*sc.ncol)
     direct = _u64(be, c["sfc_dn_dir"])
     assert int(_u64(be, c["n_capped"])[0]) == 0
     assert np.all(direct[lit] == ppp << 32), direct[lit] / ONE
@@ -193,10 +169,10 @@ def test_f_counts_are_additive_reproducible_and_the_loop_is_the_entry(hip_f64):
     n = 32*sc.ncol
     kn = be.rt_k_null(d["tau"], 1, sc.nx, sc.ny, sc.dz, sc.kn_grid, sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"])
     assert np.array_equal(be.to_numpy(kn), R.k_null(sc, 1))
-    whole = trace(be, sc, d, 1, 0, n, k_null=kn)
-    again = trace(be, sc, d, 1, 0, n, k_null=kn)
-    parts = trace(be, sc, d, 1, 0, n//3, k_null=kn)
-    parts = trace(be, sc, d, 1, n//3, n - n//3, k_null=kn, counts=parts)
+    whole = forward(be, sc, d, 1, 0, n, kn=kn)
+    again = forward(be, sc, d, 1, 0, n, kn=kn)
+    parts = forward(be, sc, d, 1, 0, n//3, kn=kn)
+    parts = forward(be, sc, d, 1, n//3, n - n//3, kn=kn, counts=parts)
     for k in NAMES + ("n_capped",):
         assert np.array_equal(_u64(be, whole[k]), _u64(be, again[k])), k
         assert np.array_equal(_u64(be, whole[k]), _u64(be, parts[k])), k
@@ -342,9 +318,9 @@ def test_deep_photon_lists_on_few_threads_give_the_same_integers(hip_f64, monkey
     sc = S.general(np.float64)
     d = _dev(be, sc)
     n = 32*sc.ncol
-    wide = trace(be, sc, d, 0, 7, n)
+    wide = forward(be, sc, d, 0, 7, n)
     monkeypatch.setenv("RRX_RT_MAX_BLOCKS", "1")
-    deep = trace(be, sc, d, 0, 7, n)
+    deep = forward(be, sc, d, 0, 7, n)
     monkeypatch.delenv("RRX_RT_MAX_BLOCKS")
     for k in NAMES + ("n_capped",):
         assert np.array_equal(_u64(be, wide[k]), _u64(be, deep[k])), k

@@ -17,35 +17,11 @@ import raytracer_ref as R
 import raytracer_bw_ref as B
 import raytracer_scenes as FS
 import raytracer_bw_scenes as S
+from raytracer_dev import _be, _dev, _u64, k_null, backward, solve_bw
 from rte_rrtmgp_cpp_amd import synthetic, pipeline, camera as C
 
 pytestmark = pytest.mark.gpu
 ONE = float(1 << 32)
-
-
-def _be(dt, hip_f64, hip_f32):
-    return hip_f64 if dt == "f64" else hip_f32
-
-
-def _dev(be, sc):
-    A = be.asarray
-    return dict(tau=A(sc.tau), ssa=A(sc.ssa), alb=A(sc.sfc_albedo), cloud=None if sc.cloud is None else tuple(A(c) for c in sc.cloud),
-                lims=None if sc.band_lims is None else A(sc.band_lims))
-
-
-def _u64(be, t):
-    return be.to_numpy(t).view(np.uint64)
-
-
-def k_null(be, sc, d, g):
-    return be.rt_k_null(d["tau"], g, sc.nx, sc.ny, sc.dz, sc.kn_grid, sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"])
-
-
-def trace(be, sc, d, sensor, g, ray0, nrays, kn=None, counts=None, max_events=None):
-    kn = k_null(be, sc, d, g) if kn is None else kn
-    return be.rt_bw_trace_counts(d["tau"], d["ssa"], g, sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, sc.kn_grid, kn,
-                                 sensor, sc.seed, ray0, nrays, top_at_1=sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"], counts=counts,
-                                 max_events=max_events)
 
 
 def clean(be, c):
@@ -64,15 +40,10 @@ def hand_loop(be, sc, d, sensor, rpp):
         if not F(sc.inc_dir[g]) > 0:
             per_g.append(None)
             continue
-        c = trace(be, sc, d, sensor, g, 0, rpp*npix)
+        c = backward(be, sc, d, sensor, g, 0, rpp*npix)
         be.rt_counts_to_flux(c["counts"], float(F(sc.inc_dir[g]) / (F(sc.mu0)*F(rpp))), radiance)
         per_g.append(clean(be, c))
     return be.to_numpy(radiance), per_g
-
-
-def solve(be, sc, d, sensor, rpp, max_events=None):
-    return be.raytracer_bw(d["tau"], d["ssa"], sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, sc.inc_dir, sc.kn_grid,
-                           sensor, rpp, sc.seed, top_at_1=sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"], max_events=max_events)
 
 
 # ---- S1: the Bernoulli surface
@@ -85,7 +56,7 @@ def test_s1_bernoulli_surface(view, dt, hip_f64, hip_f32):
     d = _dev(be, sc)
     sensor = S.bernoulli_sensors()[view]
     for g in range(2):
-        counts = clean(be, trace(be, sc, d, sensor, g, 0, S.S1_RAYS*16))
+        counts = clean(be, backward(be, sc, d, sensor, g, 0, S.S1_RAYS*16))
         S.check_bernoulli(sc, sensor, g, counts, f"{dt} {view}")
 
 
@@ -99,7 +70,7 @@ def test_s2_shadow_in_integers(along, top_at_1, hip_f64):
     dark, full = S.shadow_classes(sc)
     assert dark.sum() == 10 and full.sum() == sc.ncol - 14
     rays = 256
-    counts = clean(be, trace(be, sc, _dev(be, sc), C.orthographic(sc.nx, sc.ny), 0, 0, rays*sc.ncol))
+    counts = clean(be, backward(be, sc, _dev(be, sc), C.orthographic(sc.nx, sc.ny), 0, 0, rays*sc.ncol))
     assert np.all(counts[dark] == 0), counts[dark] / ONE
     assert rays*int(np.rint(0.5*sc.mu0/math.pi*ONE)) == S.shadow_full_count(sc, rays)
     assert np.all(counts[full] == S.shadow_full_count(sc, rays)), counts[full] / ONE
@@ -122,7 +93,7 @@ def test_s3_forward_against_backward(dt, hip_f64, hip_f32):
                                  band_lims=d["lims"])
         assert int(_u64(be, fwd["n_capped"])[0]) == 0
         for name, sensor in S.flux_sensors(sc).items():
-            parts = np.stack([clean(be, trace(be, sc, d, sensor, g, r*per_range, per_range, kn=kn)) for r in range(S.S3_RANGES)])
+            parts = np.stack([clean(be, backward(be, sc, d, sensor, g, r*per_range, per_range, kn=kn)) for r in range(S.S3_RANGES)])
             worst = max(worst, S.compare_forward_backward(sc, g, name, _u64(be, fwd[name]), parts, dt))
     print(f"raytracer_bw S3 {dt}: worst {worst:.2f} combined sigma (bound 5)")
 
@@ -142,7 +113,7 @@ def test_ray_for_ray(kind, hip_f64):
     rpp = 32
     ref = B.raytracer_bw(sc, sensor, rpp)
     assert ref["n_capped"] == 0 and ref["n_clamped"] == 0
-    r = solve(be, sc, _dev(be, sc), sensor, rpp)
+    r = solve_bw(be, sc, _dev(be, sc), sensor, rpp)
     assert r["n_capped"] == 0 and r["n_clamped"] == 0
     got = be.to_numpy(r["radiance"]).reshape(-1)
     eps = np.finfo(np.float64).eps
@@ -165,17 +136,17 @@ def test_counts_are_additive_reproducible_and_the_loop_is_the_entry(hip_f64):
     sensor = SENSORS["perspective"]()
     n = 32*sensor.npix
     kn = k_null(be, sc, d, 1)
-    whole = trace(be, sc, d, sensor, 1, 0, n, kn=kn)
-    again = trace(be, sc, d, sensor, 1, 0, n, kn=kn)
-    parts = trace(be, sc, d, sensor, 1, 0, n//3, kn=kn)
-    parts = trace(be, sc, d, sensor, 1, n//3, n - n//3, kn=kn, counts=parts)
+    whole = backward(be, sc, d, sensor, 1, 0, n, kn=kn)
+    again = backward(be, sc, d, sensor, 1, 0, n, kn=kn)
+    parts = backward(be, sc, d, sensor, 1, 0, n//3, kn=kn)
+    parts = backward(be, sc, d, sensor, 1, n//3, n - n//3, kn=kn, counts=parts)
     for k in ("counts", "n_capped", "n_clamped"):
         assert np.array_equal(_u64(be, whole[k]), _u64(be, again[k])), k
         assert np.array_equal(_u64(be, whole[k]), _u64(be, parts[k])), k
     assert clean(be, whole).all()
     rpp = 32
     radiance, _ = hand_loop(be, sc, d, sensor, rpp)
-    r = solve(be, sc, d, sensor, rpp)
+    r = solve_bw(be, sc, d, sensor, rpp)
     assert r["radiance"].shape == (sensor.npy, sensor.npx)
     assert np.array_equal(radiance.view(np.uint8), be.to_numpy(r["radiance"]).reshape(-1).view(np.uint8))
 
@@ -189,10 +160,10 @@ def test_a_g_point_without_incident_flux_is_skipped_and_the_cap_is_counted(hip_f
     one.inc_dir = np.array([sc.inc_dir[0], 0.0])
     radiance, per_g = hand_loop(be, one, d, sensor, 8)
     assert per_g[1] is None and per_g[0].any()
-    r = solve(be, one, d, sensor, 8)
+    r = solve_bw(be, one, d, sensor, 8)
     assert np.array_equal(radiance.view(np.uint8), be.to_numpy(r["radiance"]).reshape(-1).view(np.uint8))
     # one event each: every ray that the first event does not end is dropped and counted, none loops
-    capped = solve(be, sc, d, sensor, 8, max_events=1)
+    capped = solve_bw(be, sc, d, sensor, 8, max_events=1)
     assert 0 < capped["n_capped"] == B.raytracer_bw(sc, sensor, 8, max_events=1)["n_capped"] <= 2*8*sensor.npix
 
 
@@ -204,9 +175,9 @@ def test_deep_ray_lists_on_few_threads_give_the_same_integers(hip_f64, monkeypat
     d = _dev(be, sc)
     sensor = SENSORS["fisheye"]()
     n = 32*sensor.npix
-    wide = trace(be, sc, d, sensor, 0, 5, n)
+    wide = backward(be, sc, d, sensor, 0, 5, n)
     monkeypatch.setenv("RRX_RT_MAX_BLOCKS", "1")
-    deep = trace(be, sc, d, sensor, 0, 5, n)
+    deep = backward(be, sc, d, sensor, 0, 5, n)
     monkeypatch.delenv("RRX_RT_MAX_BLOCKS")
     for k in ("counts", "n_capped", "n_clamped"):
         assert np.array_equal(_u64(be, wide[k]), _u64(be, deep[k])), k
@@ -261,7 +232,7 @@ def test_raytracer_bw_gpu_class_gives_the_entry_bit_for_bit_and_throws(dt, hip_f
     d = _dev(be, sc)
     sensor = SENSORS["perspective"]()
     rpp = 16
-    want = solve(be, sc, d, sensor, rpp)
+    want = solve_bw(be, sc, d, sensor, rpp)
     out = be.empty((sensor.npy, sensor.npx))
     inc_dir = np.ascontiguousarray(sc.inc_dir, dtype=be.np_dtype)
     numbers = sensor.numbers(be.np_dtype)

@@ -19,10 +19,12 @@ import numpy as np
 import pytest
 
 import raytracer_ref as R
+import raytracer_bw_ref as B
 import raytracer_phase_ref as P
 import raytracer_phase_scenes as PS
 import raytracer_scenes as S
 import raytracer_bw_scenes as BS
+from raytracer_dev import _be, _dev, _u64, k_null, forward, backward, solve_fw, solve_bw
 from rte_rrtmgp_cpp_amd import synthetic, pipeline, phase_tables, camera as C
 
 pytestmark = pytest.mark.gpu
@@ -31,19 +33,6 @@ NAMES = R.COUNT_NAMES
 SENSORS = {"perspective": lambda: C.perspective(6, 4, (330., 250., 170.), yaw=0.6, pitch=-0.5, roll=0.2, fov=math.radians(70.)),
            "fisheye": lambda: C.fisheye(6, 4, (420., 130., 0.)),
            "orthographic": lambda: C.orthographic(6, 4, yaw=2.0, pitch=-1.0)}
-
-
-def _be(dt, hip_f64, hip_f32):
-    return hip_f64 if dt == "f64" else hip_f32
-
-
-def _dev(be, sc):
-    A = be.asarray
-    return dict(tau=A(sc.tau), ssa=A(sc.ssa), alb=A(sc.sfc_albedo), cloud=tuple(A(c) for c in sc.cloud), lims=A(sc.band_lims))
-
-
-def _u64(be, t):
-    return be.to_numpy(t).view(np.uint64)
 
 
 def table(be, mu, raw, cld_re=None, re0=PS.RE0, dre=PS.DRE):
@@ -55,37 +44,6 @@ def ref_table(be, mu, raw, cld_re=None):
     t = P.build_tables(mu, raw, be.np_dtype, PS.RE0, PS.DRE)
     t.cld_re = cld_re
     return t
-
-
-def k_null(be, sc, d, g):
-    return be.rt_k_null(d["tau"], g, sc.nx, sc.ny, sc.dz, sc.kn_grid, sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"])
-
-
-def forward(be, sc, d, g, photon0, nphotons, phase=None, kn=None, counts=None, inc_dif=None):
-    kn = k_null(be, sc, d, g) if kn is None else kn
-    return be.rt_trace_counts(d["tau"], d["ssa"], g, sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, float(sc.inc_dir[g]),
-                              float(sc.inc_dif[g]) if inc_dif is None else inc_dif, sc.kn_grid, kn, sc.seed, photon0, nphotons,
-                              top_at_1=sc.top_at_1, independent_column=sc.independent_column, cloud=d["cloud"], band_lims=d["lims"],
-                              counts=counts, phase=phase)
-
-
-def backward(be, sc, d, sensor, g, ray0, nrays, phase=None, kn=None, counts=None):
-    kn = k_null(be, sc, d, g) if kn is None else kn
-    return be.rt_bw_trace_counts(d["tau"], d["ssa"], g, sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, sc.kn_grid, kn,
-                                 sensor, sc.seed, ray0, nrays, top_at_1=sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"], counts=counts,
-                                 phase=phase)
-
-
-def solve_fw(be, sc, d, ppp, phase=None):
-    r = be.raytracer_sw(d["tau"], d["ssa"], sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, sc.inc_dir, sc.inc_dif, sc.kn_grid,
-                        ppp, sc.seed, top_at_1=sc.top_at_1, independent_column=sc.independent_column, cloud=d["cloud"], band_lims=d["lims"],
-                        phase=phase)
-    return {k: (be.to_numpy(v) if k != "n_capped" else v) for k, v in r.items()}
-
-
-def solve_bw(be, sc, d, sensor, rpp, phase=None):
-    return be.raytracer_bw(d["tau"], d["ssa"], sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, sc.inc_dir, sc.kn_grid,
-                           sensor, rpp, sc.seed, top_at_1=sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"], phase=phase)
 
 
 def same_counts(be, a, b, keys):
@@ -243,7 +201,7 @@ def test_4_forward_ray_for_ray(peaked, hip_f64):
     ref.update({k: np.zeros((sc.nz, sc.ncol)) for k in NAMES[4:]})
     events = np.zeros(2)
     for g in range(2):
-        c = P.forward_counts(sc, ref_t, g, 0, ppp*sc.ncol)
+        c = R.trace_counts(sc, g, 0, ppp*sc.ncol, table=ref_t)
         assert c["n_capped"] == 0
         scale = (sc.inc_dir[g] + sc.inc_dif[g]) / ppp
         for k in NAMES:
@@ -273,7 +231,7 @@ def test_4_backward_ray_for_ray(kind, peaked, hip_f64):
     tol = np.zeros(npix)
     eps = np.finfo(np.float64).eps
     for g in range(2):
-        c = P.backward_counts(sc, ref_t, sensor, g, 0, rpp*npix)
+        c = B.trace_counts(sc, sensor, g, 0, rpp*npix, table=ref_t)
         assert c["n_capped"] == 0 and c["n_clamped"] == 0
         scale = sc.inc_dir[g] / (sc.mu0*rpp)
         want = R.counts_to_flux(c["counts"], scale, want)

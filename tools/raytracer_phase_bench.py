@@ -6,10 +6,10 @@ the two cameras of tools/raytracer_bw_bench.py (128 x 128 x 32 cells, 256 x 256 
 The table: 1 800 nodes (phase_tables.nodes, spacing shrinking towards +1) x 20 radii 2.5 + 1 i, HG(0.85) at every radius, so that
 the tabulated runs estimate what the Henyey-Greenstein runs estimate (the means are printed); the cells' radius is a smooth field
 across the whole grid, so that neighbouring lanes read different tables. fp64 and fp32, device events around --steps calls after
---warmup, --rounds times, the median. Counted by the numpy restatement (tests/raytracer_phase_ref.py) on the 32 x 32 cut of the
-field, g-point 0: the cloud scatterings per photon / ray, from which the extra time per tabulated cloud scattering follows (an
-aggregate over the whole machine, not a latency). --lib times the Henyey-Greenstein entries of another build of librrx_hip.so
-(the parent commit's) in the same way. One JSON line each, printed and appended to --out. A record, not a target.
+--warmup, --rounds times, the median. Counted by the numpy restatements (tests/raytracer_ref.py, raytracer_bw_ref.py) on the
+32 x 32 cut of the field, g-point 0: the cloud scatterings per photon / ray, from which the extra time per tabulated cloud
+scattering follows (an aggregate over the whole machine, not a latency). --lib times the Henyey-Greenstein entries of another build
+of librrx_hip.so (the parent commit's) in the same way. One JSON line each, printed and appended to --out. A record, not a target.
 
   python tools/raytracer_phase_bench.py
   python tools/raytracer_phase_bench.py --lib /path/to/parent/librrx_hip.so --label parent
@@ -36,8 +36,9 @@ def radius_field(nx, ny, nz):
     return np.ascontiguousarray(base.reshape(1, -1) + np.linspace(-2.5, 2.5, nz)[:, None])
 
 
-def scatterings_on_cut(C, P, tau, ssa, cloud, lims, albedo, re, nx, nz, cut, table_np):
+def scatterings_on_cut(C, tau, ssa, cloud, lims, albedo, re, nx, nz, cut, table_np):
     import raytracer_ref as R
+    import raytracer_bw_ref as B
     from raytracer_bw_bench import cameras, DX, DY, DZ, MU0, AZIMUTH, SEED
     col = (np.arange(cut)[None, :] + nx*np.arange(cut)[:, None]).reshape(-1)
     take = lambda a: np.ascontiguousarray(a[..., col])
@@ -46,10 +47,10 @@ def scatterings_on_cut(C, P, tau, ssa, cloud, lims, albedo, re, nx, nz, cut, tab
                  cloud=tuple(take(c) for c in cloud), band_lims=lims.reshape(-1, 2), top_at_1=False, seed=SEED)
     table_np.cld_re = take(re)
     n = 4*cut*cut
-    f = P.forward_counts(sc, table_np, 0, 0, n)
+    f = R.trace_counts(sc, 0, 0, n, table=table_np)
     out = {"forward": dict(photons=n, events_per_photon=round(f["events"]/n, 3), cloud_scatterings_per_photon=round(f["cloud_scatterings"]/n, 3))}
     for name, cam in cameras(C, cut, cut, nz, cut, cut).items():
-        b = P.backward_counts(sc, table_np, cam, 0, 0, 4*cam.npix)
+        b = B.trace_counts(sc, cam, 0, 0, 4*cam.npix, table=table_np)
         out[name] = dict(rays=4*cam.npix, events_per_ray=round(b["events"]/(4*cam.npix), 3),
                          cloud_scatterings_per_ray=round(b["cloud_scatterings"]/(4*cam.npix), 3))
     return out
@@ -148,7 +149,7 @@ def main():
                           mean_radiance=round(float(r["radiance"].double().mean().item()), 4)))
     if args.cut > 0 and args.lib is None:
         import raytracer_phase_ref as P
-        counts = scatterings_on_cut(C, P, tau, ssa, cloud, lims, albedo, re, nx, nz, args.cut, P.build_tables(mu, raw, np.float64, RE0, DRE))
+        counts = scatterings_on_cut(C, tau, ssa, cloud, lims, albedo, re, nx, nz, args.cut, P.build_tables(mu, raw, np.float64, RE0, DRE))
         emit(dict(restatement_on_cut=args.cut, g_point=0, **counts))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "a") as f:
