@@ -36,7 +36,36 @@ class Raytracer_gpu
                              const Float re0, const Float dre, const Array_gpu<Float,2>& cld_re);
         void clear_phase_table() { has_table = false; mu = Array_gpu<Float,1>(); phase = Array_gpu<Float,3>(); cdf = Array_gpu<Float,3>(); cld_re = Array_gpu<Float,2>(); }
 
+        // A background atmosphere between the domain top and TOA (rrx_raytracer_sw_bg): nbg horizontally uniform layers
+        // counted upward from the domain top. dz_bg (nbg) on the host, all > 0; bg_tau, bg_ssa (nbg, ngpt); bg_cld_* (nbg, nbnd), all
+        // three of size 0 for a clear background. The arrays are copied. With a background set, photons start at TOA and trace_rays is
+        // called in the form below, which also fills toa_up, tod_dn_dir, tod_dn_dif (ncol) in W m-2 and bg_abs_dir, bg_abs_dif (nbg) in
+        // W m-3 of a domain-wide layer; tod_up is then the flux through the domain top.
+        void set_background(const Array<Float,1>& dz_bg, const Array_gpu<Float,2>& bg_tau, const Array_gpu<Float,2>& bg_ssa,
+                            const Array_gpu<Float,2>& bg_cld_tau, const Array_gpu<Float,2>& bg_cld_ssa, const Array_gpu<Float,2>& bg_cld_g);
+        void clear_background() { has_bg = false; dz_bg = Array<Float,1>(); bg_tau = Array_gpu<Float,2>(); bg_ssa = Array_gpu<Float,2>();
+                                  bg_cld_tau = Array_gpu<Float,2>(); bg_cld_ssa = Array_gpu<Float,2>(); bg_cld_g = Array_gpu<Float,2>(); }
+        unsigned long long trace_rays(
+                const int nx, const int ny, const int nz,
+                const Float dx, const Float dy, const Float dz,
+                const bool top_at_1, const bool independent_column,
+                const Array_gpu<Float,3>& tau, const Array_gpu<Float,3>& ssa,
+                const Array_gpu<int,2>& band_lims_gpt,
+                const Array_gpu<Float,3>& cld_tau, const Array_gpu<Float,3>& cld_ssa, const Array_gpu<Float,3>& cld_g,
+                const Array_gpu<Float,1>& sfc_albedo,
+                const Float mu0, const Float azimuth,
+                const Array<Float,1>& inc_dir, const Array<Float,1>& inc_dif,
+                const int knx, const int kny, const int knz,
+                const long long photons_per_pixel, const unsigned long long seed, const int max_events,
+                Array_gpu<Float,1>& sfc_dn_dir, Array_gpu<Float,1>& sfc_dn_dif, Array_gpu<Float,1>& sfc_up, Array_gpu<Float,1>& tod_up,
+                Array_gpu<Float,2>& abs_dir, Array_gpu<Float,2>& abs_dif,
+                Array_gpu<Float,1>& toa_up, Array_gpu<Float,1>& tod_dn_dir, Array_gpu<Float,1>& tod_dn_dif,
+                Array_gpu<Float,1>& bg_abs_dir, Array_gpu<Float,1>& bg_abs_dif);
+
     private:
+        bool has_bg = false;
+        Array<Float,1> dz_bg;
+        Array_gpu<Float,2> bg_tau, bg_ssa, bg_cld_tau, bg_cld_ssa, bg_cld_g;
         bool has_table = false;
         Float re0 = Float(0.), dre = Float(0.);
         Array_gpu<Float,1> mu;

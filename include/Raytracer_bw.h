@@ -50,7 +50,18 @@ class Raytracer_bw_gpu
                              const Float re0, const Float dre, const Array_gpu<Float,2>& cld_re);
         void clear_phase_table() { has_table = false; mu = Array_gpu<Float,1>(); phase = Array_gpu<Float,3>(); cdf = Array_gpu<Float,3>(); cld_re = Array_gpu<Float,2>(); }
 
+        // A background atmosphere between the domain top and TOA (rrx_raytracer_bw_bg), as Raytracer_gpu::set_background
+        // takes it. With a background set, rays end only at TOA, a sensor may sit inside the background, and the orthographic and the
+        // downward flux sensor start at clamp(position[2], domain top, TOA). The arrays are copied.
+        void set_background(const Array<Float,1>& dz_bg, const Array_gpu<Float,2>& bg_tau, const Array_gpu<Float,2>& bg_ssa,
+                            const Array_gpu<Float,2>& bg_cld_tau, const Array_gpu<Float,2>& bg_cld_ssa, const Array_gpu<Float,2>& bg_cld_g);
+        void clear_background() { has_bg = false; dz_bg = Array<Float,1>(); bg_tau = Array_gpu<Float,2>(); bg_ssa = Array_gpu<Float,2>();
+                                  bg_cld_tau = Array_gpu<Float,2>(); bg_cld_ssa = Array_gpu<Float,2>(); bg_cld_g = Array_gpu<Float,2>(); }
+
     private:
+        bool has_bg = false;
+        Array<Float,1> dz_bg;
+        Array_gpu<Float,2> bg_tau, bg_ssa, bg_cld_tau, bg_cld_ssa, bg_cld_g;
         bool has_table = false;
         Float re0 = Float(0.), dre = Float(0.);
         Array_gpu<Float,1> mu;

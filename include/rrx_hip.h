@@ -733,7 +733,70 @@ int rrx_raytracer_bw_phase##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxB
         F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz, \
         int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
         F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
-        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, void* stream);
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, void* stream); \
+/* ---- A background atmosphere between the domain top and TOA, for both ray tracers (csrc/rrx_rt_common.h). \
+   nbg >= 1 plane-parallel, horizontally uniform layers above the grid, counted UPWARD from the domain top whatever top_at_1 is; \
+   nbg <= 256. dz_bg (nbg): the thicknesses in metres, all > 0, on the HOST. Layer b lies between z_bg[b] and z_bg[b+1] with \
+   z_bg[0] = F(knz) (F(nz/knz) dz), the domain top as the kernels form it, z_bg[b+1] = z_bg[b] + dz_bg[b], z_bg[nbg] = TOA. On the \
+   device: the clear bg_tau, bg_ssa (nbg, ngpt), layer fastest, and the optional band triple bg_cld_tau, bg_cld_ssa, bg_cld_g \
+   (nbg, nbnd), all NULL or all given (it needs band_lims_gpt and scatters by Henyey-Greenstein always: a phase table applies inside \
+   the grid only). \
+   rrx_rt_bg_profile: bg_profile (5, nbg+1), layer fastest, for g-point igpt: rows k_ext = (tau + tau_c)/dz_bg, \
+   k_sca = (tau ssa + tau_c ssa_c)/dz_bg, k_sca_cld = (tau_c ssa_c)/dz_bg, g = min(g_c, 1 - eps), and tau_above[b] = the sum of \
+   tau + tau_c over the layers b+1 .. nbg-1 in index order; slot nbg of tau_above holds the sum over all layers, slot nbg of the \
+   other rows 0. nbg or ngpt = 0: returns 0 without a launch. \
+   The _bg entries are the _phase entries (the table arguments may be NULL) with nbg, dz_bg and the background in front of the \
+   stream, and the new outputs behind the existing ones. Transport in the background, the new tallies and the sensors: the headers \
+   of rrx_rt_common.h, rrx_raytracer.hip and rrx_raytracer_bw.hip. In short: photons start at TOA; a background layer is a block \
+   with z faces only whose k_null is its own k_ext; x and y run unwrapped there and are wrapped on entering the grid; a backward \
+   ray ends only at TOA, a scattering in layer b deposits with T_sun = exp(-(k_ext_b (z_bg[b+1] - z) + tau_above[b])/mu0) and a \
+   deposit from inside the grid multiplies its walked transmission by exp(-tau_above[nbg]/mu0), formed as one exp. \
+   rrx_rt_trace_counts_bg: beside the six tallies (tod_up now counts EVERY upward crossing of the domain top), toa_up, tod_dn_dir, \
+   tod_dn_dif (ncol) and bg_abs_dir, bg_abs_dif (nbg), caller-zeroed, added into, the same 2^-32 units; bg_profile from \
+   rrx_rt_bg_profile for the same igpt. \
+   rrx_raytracer_sw_bg: the spectral loop with rrx_rt_bg_profile in it; toa_up, tod_dn_dir, tod_dn_dif (ncol) in W m-2 with the \
+   scale of the other fluxes; bg_abs_dir, bg_abs_dif (nbg) in W m-3 of a DOMAIN-WIDE layer: the counts of all columns times \
+   (scale/dz_bg[b])/F(ncol). The same bits as the loop made by hand. \
+   rrx_rt_bw_trace_counts_bg, rrx_raytracer_bw_bg: the top of the medium is TOA: a sensor at or above it is moved along the ray to it, \
+   a sensor may sit inside the background, and the orthographic sensor and the flux sensor facing down start at the height \
+   clamp(position.z, domain top, TOA) (position.z = 0: the domain top, as without a background; any position.z >= TOA: TOA). \
+   nbg = 0: the medium without a background, the integers of the existing entries; dz_bg, the background arrays and the new \
+   outputs are not read. Refused before any HIP call: nbg < 0 or > 256, a NULL that is needed, a partly-NULL background triple, a \
+   dz_bg that is not > 0 and finite, and what the _phase entries refuse. */ \
+int rrx_rt_bg_profile##SFX(int nbg, int ngpt, int nbnd, int igpt, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const int* band_lims_gpt, \
+        const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* bg_profile, void* stream); \
+int rrx_rt_trace_counts_bg##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, F inc_dir, F inc_dif, int knx, int kny, int knz, const F* k_null, \
+        unsigned long long seed, long long photon0, long long nphotons, int max_events, \
+        unsigned long long* sfc_dn_dir, unsigned long long* sfc_dn_dif, unsigned long long* sfc_up, unsigned long long* tod_up, \
+        unsigned long long* abs_dir, unsigned long long* abs_dif, unsigned long long* n_capped, \
+        unsigned long long* toa_up, unsigned long long* tod_dn_dir, unsigned long long* tod_dn_dif, \
+        unsigned long long* bg_abs_dir, unsigned long long* bg_abs_dif, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_profile, void* stream); \
+int rrx_raytracer_sw_bg##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
+        long long photons_per_pixel, unsigned long long seed, int max_events, \
+        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, \
+        F* toa_up, F* tod_dn_dir, F* tod_dn_dif, F* bg_abs_dir, F* bg_abs_dif, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, void* stream); \
+int rrx_rt_bw_trace_counts_bg##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
+        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_profile, void* stream); \
+int rrx_raytracer_bw_bg##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
+        F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, void* stream);
 
 RRX_DECLARE(double, _f64)
 RRX_DECLARE(float, _f32)

@@ -31,6 +31,23 @@
 //     collision: deposit weight (1 - f_no_abs), weight *= f_no_abs;  weight < 0.5: u -> roulette as above;
 //              survivor: u -> scatter or null collision;  scatter: u -> species;  u -> cos of the scattering angle;  u -> phi
 //
+// WITH A BACKGROUND (trace_kernel<F,TABLE,true>, the rrx_*_bg entries; rrx_rt_common.h; tests/raytracer_bg_ref.py
+// restates it) the DRAW ORDER is the same:
+//   start:     the same draws; the photon starts at TOA, z = z_bg[nbg], in layer nbg-1 (block index knz + nbg - 1) with the x, y,
+//              pixel and block (in, jn) of the start without a background
+//   each event in layer b: u -> tau = -log(u), unless the previous event was a crossing (between layers, between blocks, or
+//              through the domain top in either direction: the remaining tau is carried)
+//     crossing (tau >= d_max k_ext_b with d_max the distance to the z face, or k_ext_b = 0): tau -= d_max k_ext_b; no draw. Upward
+//              from layer nbg-1: toa_up, the photon ends. Downward from layer 0: enter_grid (x, y wrapped, their block by integer
+//              division and clamping; not under independent_column), block knz-1, z = the domain top, tod_dn_dir / tod_dn_dif.
+//              Upward out of block knz-1 of the grid: tod_up, then layer 0 (the photon ends there only when nbg = 0).
+//     collision: deposit weight (1 - f_no_abs) into bg_abs_dir / bg_abs_dif [b], weight *= f_no_abs, f_no_abs = 1 - (k_ext_b - k_sca_b)/k_ext_b;
+//              weight < 0.5: u -> roulette;  survivor: u -> scatter or null collision (it always scatters);  u -> species;
+//              u -> cos of the scattering angle (Rayleigh, or Henyey-Greenstein with the layer's g, with a phase table too);  u -> phi
+//   uz = 0 in a layer with k_ext = 0: the photon is dropped into n_capped.
+// The spectral loop scales toa_up, tod_dn_dir, tod_dn_dif like the other fluxes and bg_abs_* [b] by (scale/dz_bg[b])/F(ncol): W m-3 of
+// a layer that spans the whole domain.
+//
 // Shape: one photon per lane at a time; a lane whose photon ends takes the next one of its list in the same loop, so the lanes
 // of a wave stay busy until the lists run out (the grid is capped and the photons dealt round-robin over the threads).
 #include "rrx_rt_phase.h"
@@ -86,9 +103,26 @@ struct TraceArgs
 
 // TABLE: cloud scatters by the tabulated phase function of the cell's radius (rrx_rt_phase.h) in place of
 // Henyey-Greenstein; cld_g is then not read, and the radius only once the scatterer has been drawn as cloud
-template<typename F, bool TABLE>
-__global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, const PhaseArgs<F,TABLE> ph)
+//
+// BG: the background atmosphere above the grid (rrx_rt_common.h). Photons start at TOA in layer nbg-1 with the same
+// pixel and the same start draws; tod_up tallies every upward crossing of the domain top (those photons may come back), tod_dn_dir /
+// tod_dn_dif every downward one by the pixel they enter, toa_up the photons that leave through TOA by the pixel of the wrapped exit
+// position, bg_abs_dir / bg_abs_dif (nbg) the expected absorbed share at background collisions. With nbg = 0 it is the medium
+// without a background: the integers of the other instantiations.
+template<typename F>
+struct BgTallies { u64* toa_up; u64* tod_dn_dir; u64* tod_dn_dif; u64* bg_abs_dir; u64* bg_abs_dif; };
+template<typename F, bool BG> struct FwBg {};
+template<typename F> struct FwBg<F,true> { BgIn<F> in; BgTallies<F> t; };
+
+template<typename F, bool TABLE, bool BG>
+__global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, const PhaseArgs<F,TABLE> ph, const FwBg<F,BG> bgin)
 {
+    [[maybe_unused]] BgView<F> bg{};
+    if constexpr (BG)
+    {
+        extern __shared__ double bg_lds[];
+        bg = stage_background(bgin.in, reinterpret_cast<F*>(bg_lds));
+    }
     const long long nthreads = (long long)gridDim.x*blockDim.x;
     long long next_photon = (long long)blockIdx.x*blockDim.x + threadIdx.x;
 
@@ -96,6 +130,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
     const size_t ncol = size_t(nx)*ny;
     const int rx = nx/a.knx, ry = ny/a.kny, rz = nz/a.knz;
     const F kdx = F(rx)*a.dx, kdy = F(ry)*a.dy, kdz = F(rz)*a.dz;
+    [[maybe_unused]] const F len_x = F(a.knx)*kdx, len_y = F(a.kny)*kdy;
     const bool ic = a.independent_column != 0;
     const int ibnd = a.cld_tau != nullptr ? band_of(a.igpt, a.nbnd, a.band_lims_gpt) : -1;
     const F* __restrict__ tau_g = a.tau + ncol*nz*a.igpt;
@@ -122,6 +157,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
             x = clampf((F(ix) + rng.next<F>())*a.dx, F(in)*kdx, F(in+1)*kdx);
             y = clampf((F(iy) + rng.next<F>())*a.dy, F(jn)*kdy, F(jn+1)*kdy);
             z = F(a.knz)*kdz;
+            if constexpr (BG) { if (bg.nbg > 0) { kn = a.knz + bg.nbg - 1; z = bg.z[bg.nbg]; } }
             if (rng.next<F>() < a.dif_frac) { lambert(rng, F(-1.), ux, uy, uz); kind = 1; }
             else { ux = a.sun_x; uy = a.sun_y; uz = a.sun_z; kind = 0; }
             weight = F(1.); pending = false; nev = 0; alive = true;
@@ -129,13 +165,21 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
         if (nev >= a.max_events) { atomicAdd(a.n_capped, 1ull); alive = false; continue; }
         ++nev;
 
-        const F x_lo = F(in)*kdx, x_hi = F(in+1)*kdx, y_lo = F(jn)*kdy, y_hi = F(jn+1)*kdy, z_lo = F(kn)*kdz, z_hi = F(kn+1)*kdz;
+        // in_bg: the photon is in background layer kn - knz, a block with z faces only whose k_null is its own k_ext
+        [[maybe_unused]] bool in_bg = false;
+        if constexpr (BG) in_bg = kn >= a.knz;
+        const F x_lo = F(in)*kdx, x_hi = F(in+1)*kdx, y_lo = F(jn)*kdy, y_hi = F(jn+1)*kdy;
+        F z_lo = F(kn)*kdz, z_hi = F(kn+1)*kdz;
+        if constexpr (BG) { if (in_bg) { z_lo = bg.z[kn - a.knz]; z_hi = bg.z[kn - a.knz + 1]; } }
+        const bool flat = ic || in_bg;
         const F sz = uz > F(0.) ? (z_hi - z)/uz : (uz < F(0.) ? (z_lo - z)/uz : inf);
-        const F sx = ic ? inf : (ux > F(0.) ? (x_hi - x)/ux : (ux < F(0.) ? (x_lo - x)/ux : inf));
-        const F sy = ic ? inf : (uy > F(0.) ? (y_hi - y)/uy : (uy < F(0.) ? (y_lo - y)/uy : inf));
+        const F sx = flat ? inf : (ux > F(0.) ? (x_hi - x)/ux : (ux < F(0.) ? (x_lo - x)/ux : inf));
+        const F sy = flat ? inf : (uy > F(0.) ? (y_hi - y)/uy : (uy < F(0.) ? (y_lo - y)/uy : inf));
         const F d_max = min(sz, min(sx, sy));
         const int axis = (sz <= sx && sz <= sy) ? 2 : (sx <= sy ? 0 : 1);
-        const F kn_val = a.k_null[in + a.knx*(jn + a.kny*kn)];
+        F kn_val;
+        if constexpr (BG) kn_val = in_bg ? bg.k_ext[kn - a.knz] : a.k_null[in + a.knx*(jn + a.kny*min(kn, a.knz - 1))];
+        else kn_val = a.k_null[in + a.knx*(jn + a.kny*kn)];
         if (!pending) tau = -log(rng.next<F>());
         pending = false;
         const bool empty = !(kn_val > F(0.));
@@ -146,9 +190,41 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
             // ---- the photon leaves the block through the face of `axis`
             if (!(d_max < inf)) { atomicAdd(a.n_capped, 1ull); alive = false; continue; }      // (a direction along no axis it may move on)
             tau = tau - tau_cell; pending = true;
-            if (!ic) { x = clampf(x + ux*d_max, x_lo, x_hi); y = clampf(y + uy*d_max, y_lo, y_hi); }
+            if (!ic)
+            {
+                if (in_bg) { x = x + ux*d_max; y = y + uy*d_max; }
+                else { x = clampf(x + ux*d_max, x_lo, x_hi); y = clampf(y + uy*d_max, y_lo, y_hi); }
+            }
             z = clampf(z + uz*d_max, z_lo, z_hi);
-            if (axis == 0)
+            [[maybe_unused]] bool handled = false;
+            if constexpr (BG)
+            {
+                if (in_bg)
+                {
+                    // ---- a z face of a background layer: TOA, the next layer, or the domain top from above
+                    handled = true;
+                    if (uz > F(0.))
+                    {
+                        if (kn == a.knz + bg.nbg - 1)
+                        {
+                            const int pix = wrapped_cell(x, len_x, a.dx, nx) + nx*wrapped_cell(y, len_y, a.dy, ny);
+                            tally(bgin.t.toa_up, pix, to_count(weight));
+                            alive = false;
+                        }
+                        else { ++kn; z = bg.z[kn - a.knz]; }
+                    }
+                    else if (kn == a.knz)
+                    {
+                        if (!ic) { enter_grid(x, in, len_x, kdx, a.knx); enter_grid(y, jn, len_y, kdy, a.kny); }
+                        kn = a.knz - 1; z = F(a.knz)*kdz;
+                        const int pix = fine_cell(x, a.dx, in, rx) + nx*fine_cell(y, a.dy, jn, ry);
+                        tally(kind == 0 ? bgin.t.tod_dn_dir : bgin.t.tod_dn_dif, pix, to_count(weight));
+                    }
+                    else { --kn; z = bg.z[kn - a.knz + 1]; }
+                }
+            }
+            if (handled) {}          // (the background's face, above)
+            else if (axis == 0)
             {
                 if (ux > F(0.)) { in = (in + 1 == a.knx) ? 0 : in + 1; x = F(in)*kdx; }
                 else { in = (in == 0) ? a.knx - 1 : in - 1; x = F(in+1)*kdx; }
@@ -165,6 +241,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
                     const int pix = fine_cell(x, a.dx, in, rx) + nx*fine_cell(y, a.dy, jn, ry);
                     tally(a.tod_up, pix, to_count(weight));
                     alive = false;
+                    if constexpr (BG) { if (bg.nbg > 0) { alive = true; kn = a.knz; z = bg.z[0]; } }
                 }
                 else { ++kn; z = F(kn)*kdz; }
             }
@@ -185,25 +262,45 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
         {
             // ---- a collision inside the block
             const F dn = tau / kn_val;
-            if (!ic) { x = clampf(x + ux*dn, x_lo, x_hi); y = clampf(y + uy*dn, y_lo, y_hi); }
-            z = clampf(z + uz*dn, z_lo, z_hi);
-            const int i = fine_cell(x, a.dx, in, rx), j = fine_cell(y, a.dy, jn, ry), k = fine_cell(z, a.dz, kn, rz);
-            const int lay = a.top_at_1 ? nz-1-k : k;
-            const size_t cell = size_t(i) + size_t(j)*nx + ncol*lay;
-            const F t = tau_g[cell], w0 = ssa_g[cell];
-            F tc = F(0.), wc = F(0.);
-            [[maybe_unused]] F gc = F(0.);
-            if (ibnd >= 0)
+            if (!ic)
             {
-                const size_t cb = cell + ncol*nz*ibnd;
-                tc = a.cld_tau[cb]; wc = a.cld_ssa[cb];
-                if constexpr (!TABLE) gc = a.cld_g[cb];
+                if (in_bg) { x = x + ux*dn; y = y + uy*dn; }
+                else { x = clampf(x + ux*dn, x_lo, x_hi); y = clampf(y + uy*dn, y_lo, y_hi); }
             }
-            const F k_ext = k_ext_of(t, tc, a.dz);
-            const F k_sca = (t*w0 + tc*wc) / a.dz;
-            const F k_sca_cld = (tc*wc) / a.dz;
+            z = clampf(z + uz*dn, z_lo, z_hi);
+            // the cell and its k_ext, k_sca, k_sca_cld: a cell of the grid, or the photon's background layer
+            size_t cell = 0;
+            F k_ext = F(0.), k_sca = F(0.), k_sca_cld = F(0.);
+            [[maybe_unused]] F gc = F(0.);
+            u64* abs_to = kind == 0 ? a.abs_dir : a.abs_dif;
+            if (in_bg)
+            {
+                if constexpr (BG)
+                {
+                    cell = size_t(kn - a.knz);
+                    k_ext = kn_val; k_sca = bg.k_sca[cell]; k_sca_cld = bg.k_sca_cld[cell]; gc = bg.g[cell];
+                    abs_to = kind == 0 ? bgin.t.bg_abs_dir : bgin.t.bg_abs_dif;
+                }
+            }
+            else
+            {
+                const int i = fine_cell(x, a.dx, in, rx), j = fine_cell(y, a.dy, jn, ry), k = fine_cell(z, a.dz, kn, rz);
+                const int lay = a.top_at_1 ? nz-1-k : k;
+                cell = size_t(i) + size_t(j)*nx + ncol*lay;
+                const F t = tau_g[cell], w0 = ssa_g[cell];
+                F tc = F(0.), wc = F(0.);
+                if (ibnd >= 0)
+                {
+                    const size_t cb = cell + ncol*nz*ibnd;
+                    tc = a.cld_tau[cb]; wc = a.cld_ssa[cb];
+                    if constexpr (!TABLE) gc = a.cld_g[cb];
+                }
+                k_ext = k_ext_of(t, tc, a.dz);
+                k_sca = (t*w0 + tc*wc) / a.dz;
+                k_sca_cld = (tc*wc) / a.dz;
+            }
             const F f_no_abs = clampf(F(1.) - (k_ext - k_sca)/kn_val, F(0.), F(1.));
-            tally(kind == 0 ? a.abs_dir : a.abs_dif, cell, to_count(weight*(F(1.) - f_no_abs)));
+            tally(abs_to, cell, to_count(weight*(F(1.) - f_no_abs)));
             weight = weight * f_no_abs;
             if (weight < F(0.5)) weight = (rng.next<F>() > weight) ? F(0.) : F(1.);
             if (!(weight > F(0.))) { alive = false; continue; }
@@ -212,8 +309,12 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
                 const bool cloud = rng.next<F>()*k_sca < k_sca_cld;
                 if constexpr (TABLE)
                 {
-                    const F re = cloud ? ph.in.cld_re[cell] : F(0.);          // cld_re (ncol, nz): one radius for all bands
-                    scatter_direction_table(rng, cloud, table_of_band(ph.in, ibnd), ph.in.mu, re, ux, uy, uz);
+                    if (in_bg) scatter_direction(rng, cloud, gc, g_max, ux, uy, uz);          // the table applies inside the grid only
+                    else
+                    {
+                        const F re = cloud ? ph.in.cld_re[cell] : F(0.);          // cld_re (ncol, nz): one radius for all bands
+                        scatter_direction_table(rng, cloud, table_of_band(ph.in, ibnd), ph.in.mu, re, ux, uy, uz);
+                    }
                 }
                 else scatter_direction(rng, cloud, gc, g_max, ux, uy, uz);
                 kind = 1;
@@ -242,15 +343,92 @@ void launch_k_null(int nx, int ny, int nz, int nbnd, int igpt, int top_at_1, con
 
 template<typename F>
 void launch_trace(TraceArgs<F> a, const PhaseIn<F>& ph, const F mu0, const F azimuth, const F inc_dir, const F inc_dif, const u64 seed,
-                  hipStream_t st)
+                  hipStream_t st, const FwBg<F,true>* bg = nullptr)
 {
     const double st_ = std::sqrt(std::max(0.0, 1.0 - double(mu0)*double(mu0)));
     a.sun_x = F(st_*std::cos(double(azimuth))); a.sun_y = F(st_*std::sin(double(azimuth))); a.sun_z = -mu0;
     a.dif_frac = inc_dif / (inc_dir + inc_dif);
     a.k0 = unsigned(seed & 0xFFFFFFFFull); a.k1 = unsigned(seed >> 32);
     const int blocks = int(std::min<long long>((a.nphotons + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
-    if (ph.given()) trace_kernel<F,true><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,true>{ph});
-    else trace_kernel<F,false><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,false>{});
+    if (bg != nullptr)
+    {
+        const size_t lds = bg_lds_numbers(bg->in.nbg)*sizeof(F);
+        if (ph.given()) trace_kernel<F,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, *bg);
+        else trace_kernel<F,false,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, *bg);
+    }
+    else if (ph.given()) trace_kernel<F,true,false><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,true>{ph}, FwBg<F,false>{});
+    else trace_kernel<F,false,false><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,false>{}, FwBg<F,false>{});
+}
+
+// one number per background layer: out[b] += F(counts[b] 2^-32) scale[b]
+template<typename F>
+__global__ void bg_counts_to_flux_kernel(const int nbg, const u64* __restrict__ counts, const BgLevels<F> scale, F* __restrict__ out)
+{
+    const int b = blockIdx.x*blockDim.x + threadIdx.x;
+    if (b < nbg) out[b] = out[b] + F(double(counts[b]) * 2.3283064365386963e-10) * scale.v[b];
+}
+
+// the profile of the background for one g-point (rrx_rt_common.h): one thread per layer
+template<typename F>
+__global__ void bg_profile_kernel(const int nbg, const int ngpt, const int nbnd, const int igpt, const BgLevels<F> dz_bg,
+        const F* __restrict__ bg_tau, const F* __restrict__ bg_ssa, const int* __restrict__ band_lims_gpt,
+        const F* __restrict__ bg_cld_tau, const F* __restrict__ bg_cld_ssa, const F* __restrict__ bg_cld_g, F* __restrict__ profile)
+{
+    const int b = blockIdx.x*blockDim.x + threadIdx.x;
+    if (b > nbg) return;
+    const int n1 = nbg + 1;
+    const int ibnd = bg_cld_tau != nullptr ? band_of(igpt, nbnd, band_lims_gpt) : -1;
+    const F* __restrict__ tau_g = bg_tau + size_t(nbg)*igpt;
+    const F* __restrict__ ctau_b = ibnd >= 0 ? bg_cld_tau + size_t(nbg)*ibnd : nullptr;
+    // the layers above b in index order; slot nbg: all of them
+    F above = F(0.);
+    for (int l = (b == nbg ? 0 : b + 1); l < nbg; ++l) above = above + (tau_g[l] + (ctau_b != nullptr ? ctau_b[l] : F(0.)));
+    profile[BG_TAU_ABOVE*n1 + b] = above;
+    F k_ext = F(0.), k_sca = F(0.), k_sca_cld = F(0.), g = F(0.);
+    if (b < nbg)
+    {
+        const F t = tau_g[b], w0 = bg_ssa[size_t(nbg)*igpt + b], dz = dz_bg.v[b];
+        F tc = F(0.), wc = F(0.), gc = F(0.);
+        if (ibnd >= 0) { tc = ctau_b[b]; wc = bg_cld_ssa[size_t(nbg)*ibnd + b]; gc = bg_cld_g[size_t(nbg)*ibnd + b]; }
+        k_ext = k_ext_of(t, tc, dz);
+        k_sca = (t*w0 + tc*wc) / dz;
+        k_sca_cld = (tc*wc) / dz;
+        g = min(gc, F(1.) - Lim<F>::eps());
+    }
+    profile[BG_K_EXT*n1 + b] = k_ext; profile[BG_K_SCA*n1 + b] = k_sca; profile[BG_K_SCA_CLD*n1 + b] = k_sca_cld; profile[BG_G*n1 + b] = g;
+}
+
+template<typename F>
+BgLevels<F> bg_thicknesses(const int nbg, const F* dz_bg)
+{
+    BgLevels<F> d{};
+    for (int b=0; b<nbg; ++b) d.v[b] = dz_bg[b];
+    return d;
+}
+
+template<typename F>
+void launch_bg_profile(int nbg, int ngpt, int nbnd, int igpt, const BgLevels<F>& dz_bg, const F* bg_tau, const F* bg_ssa,
+                       const int* band_lims_gpt, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* profile, hipStream_t st)
+{
+    bg_profile_kernel<F><<<ceil_div(nbg + 1, 64), 64, 0, st>>>(nbg, ngpt, nbnd, igpt, dz_bg, bg_tau, bg_ssa, band_lims_gpt,
+                                                              bg_cld_tau, bg_cld_ssa, bg_cld_g, profile);
+}
+
+template<typename F>
+int bg_profile_entry(const char* entry, int nbg, int ngpt, int nbnd, int igpt, const F* dz_bg, const F* bg_tau, const F* bg_ssa,
+                     const int* band_lims_gpt, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* profile, void* stream)
+{
+    RRX_TRY
+    check_nbg(nbg);
+    if (check_extents({{"nbg", nbg}, {"ngpt", ngpt}})) return 0;
+    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
+    if (igpt < 0 || igpt >= ngpt) throw std::runtime_error("igpt is outside [0, ngpt)");
+    check_bg_medium(nbg, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g);
+    check_needed({{"bg_profile", profile}});
+    bg_levels<F>(nbg, dz_bg, 1, 1, F(1.));          // (the thicknesses are > 0)
+    launch_bg_profile<F>(nbg, ngpt, nbnd, igpt, bg_thicknesses(nbg, dz_bg), bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa,
+                         bg_cld_g, profile, static_cast<hipStream_t>(stream));
+    RRX_CATCH(entry)
 }
 
 template<typename F>
@@ -282,9 +460,11 @@ int trace_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, i
                 F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, F inc_dir, F inc_dif,
                 int knx, int kny, int knz, const F* k_null, u64 seed, long long photon0, long long nphotons, int max_events,
                 u64* sfc_dn_dir, u64* sfc_dn_dif, u64* sfc_up, u64* tod_up, u64* abs_dir, u64* abs_dif, u64* n_capped, void* stream,
-                const PhaseIn<F> ph = PhaseIn<F>{})
+                const PhaseIn<F> ph = PhaseIn<F>{}, const bool with_bg = false, const BgTallies<F> bt = BgTallies<F>{},
+                const int nbg = 0, const F* dz_bg = nullptr, const F* bg_profile = nullptr)
 {
     RRX_TRY
+    check_nbg(nbg);
     if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"nphotons", nphotons}})) return 0;
     if (nbnd < 0) throw std::runtime_error("nbnd is negative");
     if (photon0 < 0) throw std::runtime_error("photon0 is negative");
@@ -301,6 +481,18 @@ int trace_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, i
     TraceArgs<F> a{nx, ny, nz, nbnd, igpt, top_at_1 ? 1 : 0, independent_column ? 1 : 0, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g,
                    dx, dy, dz, sfc_albedo, F(0.), F(0.), F(0.), F(0.), knx, kny, knz, k_null, 0u, 0u, u64(photon0), nphotons, max_events,
                    sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped};
+    if (with_bg)
+    {
+        FwBg<F,true> bg{BgIn<F>{nbg, bg_profile, BgLevels<F>{}}, bt};
+        if (nbg > 0)
+        {
+            check_needed({{"dz_bg", dz_bg}, {"bg_profile", bg_profile}, {"toa_up", bt.toa_up}, {"tod_dn_dir", bt.tod_dn_dir},
+                          {"tod_dn_dif", bt.tod_dn_dif}, {"bg_abs_dir", bt.bg_abs_dir}, {"bg_abs_dif", bt.bg_abs_dif}});
+            bg.in.z = bg_levels<F>(nbg, dz_bg, nz, knz, dz);
+        }
+        launch_trace<F>(a, ph, mu0, azimuth, inc_dir, inc_dif, seed, static_cast<hipStream_t>(stream), &bg);
+        return 0;
+    }
     launch_trace<F>(a, ph, mu0, azimuth, inc_dir, inc_dif, seed, static_cast<hipStream_t>(stream));
     RRX_CATCH(entry)
 }
@@ -321,9 +513,13 @@ int raytracer_sw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
                        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif,
                        int knx, int kny, int knz, long long photons_per_pixel, u64 seed, int max_events,
                        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, u64* n_capped, void* stream,
-                       const PhaseIn<F> ph = PhaseIn<F>{})
+                       const PhaseIn<F> ph = PhaseIn<F>{}, const bool with_bg = false, F* const* bg_out = nullptr, const int nbg = 0,
+                       const F* dz_bg = nullptr, const F* bg_tau = nullptr, const F* bg_ssa = nullptr, const F* bg_cld_tau = nullptr,
+                       const F* bg_cld_ssa = nullptr, const F* bg_cld_g = nullptr)
 {
+    // bg_out: toa_up, tod_dn_dir, tod_dn_dif (ncol), bg_abs_dir, bg_abs_dif (nbg)
     RRX_TRY
+    check_nbg(nbg);
     if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"photons_per_pixel", photons_per_pixel}})) return 0;
     if (nbnd < 0) throw std::runtime_error("nbnd is negative");
     check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"inc_dir", inc_dir}, {"inc_dif", inc_dif},
@@ -336,14 +532,32 @@ int raytracer_sw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
         if (inc_dir[g] < F(0.) || inc_dif[g] < F(0.)) throw std::runtime_error("inc_dir, inc_dif must be >= 0");
     if (max_events < 1) throw std::runtime_error("max_events must be >= 1");
     check_grid(nx, ny, nz, knx, kny, knz);
+    const bool bg_on = with_bg && nbg > 0;
+    BgLevels<F> lev{}, thick{};
+    if (bg_on)
+    {
+        check_bg_medium(nbg, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g);
+        check_needed({{"toa_up", bg_out[0]}, {"tod_dn_dir", bg_out[1]}, {"tod_dn_dif", bg_out[2]}, {"bg_abs_dir", bg_out[3]},
+                      {"bg_abs_dif", bg_out[4]}});
+        lev = bg_levels<F>(nbg, dz_bg, nz, knz, dz);
+        thick = bg_thicknesses(nbg, dz_bg);
+    }
 
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t ncol = size_t(nx)*ny, n_sfc = 4*ncol, n_abs = 2*ncol*nz, n_counts = n_sfc + n_abs;
+    const size_t ncol = size_t(nx)*ny, n_sfc = 4*ncol, n_abs = 2*ncol*nz;
+    const size_t n_bgc = bg_on ? 3*ncol + 2*size_t(nbg) : 0, n_counts = n_sfc + n_abs + n_bgc;
     const size_t n_kn = (size_t(knx)*kny*knz*sizeof(F) + sizeof(u64) - 1) / sizeof(u64);
+    const size_t n_prof = bg_on ? (size_t(BG_ROWS)*(nbg + 1)*sizeof(F) + sizeof(u64) - 1) / sizeof(u64) : 0;
     WorkspaceLease lease(st);
-    u64* counts = lease.get<u64>(n_counts + n_kn);
+    u64* counts = lease.get<u64>(n_counts + n_kn + n_prof);
     F* k_null = reinterpret_cast<F*>(counts + n_counts);
+    F* profile = reinterpret_cast<F*>(counts + n_counts + n_kn);
     bool ok = hipMemsetAsync(n_capped, 0, sizeof(u64), st) == hipSuccess;
+    if (bg_on)
+    {
+        for (int n=0; n<3; ++n) ok = ok && hipMemsetAsync(bg_out[n], 0, ncol*sizeof(F), st) == hipSuccess;
+        for (int n=3; n<5; ++n) ok = ok && hipMemsetAsync(bg_out[n], 0, size_t(nbg)*sizeof(F), st) == hipSuccess;
+    }
     for (F* out : {sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up}) ok = ok && hipMemsetAsync(out, 0, ncol*sizeof(F), st) == hipSuccess;
     for (F* out : {abs_dir, abs_dif}) ok = ok && hipMemsetAsync(out, 0, ncol*nz*sizeof(F), st) == hipSuccess;
     if (!ok) throw std::runtime_error("zeroing the outputs failed");
@@ -357,8 +571,26 @@ int raytracer_sw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
         TraceArgs<F> a{nx, ny, nz, nbnd, g, top_at_1 ? 1 : 0, independent_column ? 1 : 0, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g,
                        dx, dy, dz, sfc_albedo, F(0.), F(0.), F(0.), F(0.), knx, kny, knz, k_null, 0u, 0u, 0ull, nphotons, max_events,
                        c, c + ncol, c + 2*ncol, c + 3*ncol, c + n_sfc, c + n_sfc + ncol*nz, n_capped};
-        launch_trace<F>(a, ph, mu0, azimuth, inc_dir[g], inc_dif[g], seed, st);
         const F scale = (inc_dir[g] + inc_dif[g]) / F(photons_per_pixel);
+        if (with_bg)
+        {
+            u64* cb = c + n_sfc + n_abs;
+            FwBg<F,true> bg{BgIn<F>{bg_on ? nbg : 0, profile, lev}, BgTallies<F>{cb, cb + ncol, cb + 2*ncol, cb + 3*ncol, cb + 3*ncol + nbg}};
+            if (bg_on) launch_bg_profile<F>(nbg, ngpt, nbnd, g, thick, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, profile, st);
+            launch_trace<F>(a, ph, mu0, azimuth, inc_dir[g], inc_dif[g], seed, st, &bg);
+            if (bg_on)
+            {
+                launch_counts_to_flux<F>(ncol, bg.t.toa_up, scale, bg_out[0], st);
+                launch_counts_to_flux<F>(ncol, bg.t.tod_dn_dir, scale, bg_out[1], st);
+                launch_counts_to_flux<F>(ncol, bg.t.tod_dn_dif, scale, bg_out[2], st);
+                // W m-3 of a domain-wide layer: the counts of all columns over the layer's thickness and the number of columns
+                BgLevels<F> per_layer{};
+                for (int b=0; b<nbg; ++b) per_layer.v[b] = (scale / dz_bg[b]) / F(ncol);
+                bg_counts_to_flux_kernel<F><<<ceil_div(nbg, 64), 64, 0, st>>>(nbg, bg.t.bg_abs_dir, per_layer, bg_out[3]);
+                bg_counts_to_flux_kernel<F><<<ceil_div(nbg, 64), 64, 0, st>>>(nbg, bg.t.bg_abs_dif, per_layer, bg_out[4]);
+            }
+        }
+        else launch_trace<F>(a, ph, mu0, azimuth, inc_dir[g], inc_dif[g], seed, st);
         launch_counts_to_flux<F>(ncol, a.sfc_dn_dir, scale, sfc_dn_dir, st);
         launch_counts_to_flux<F>(ncol, a.sfc_dn_dif, scale, sfc_dn_dif, st);
         launch_counts_to_flux<F>(ncol, a.sfc_up, scale, sfc_up, st);
@@ -415,7 +647,40 @@ int rrx_raytracer_sw_phase##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxB
 { return raytracer_sw_entry<F>("rrx_raytracer_sw_phase" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
                                cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, \
                                photons_per_pixel, seed, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
-                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}); }
+                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}); } \
+int rrx_rt_bg_profile##SFX(int nbg, int ngpt, int nbnd, int igpt, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const int* band_lims_gpt, \
+        const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* bg_profile, void* stream) \
+{ return bg_profile_entry<F>("rrx_rt_bg_profile" #SFX, nbg, ngpt, nbnd, igpt, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, \
+                             bg_cld_g, bg_profile, stream); } \
+int rrx_rt_trace_counts_bg##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, F inc_dir, F inc_dif, int knx, int kny, int knz, const F* k_null, \
+        unsigned long long seed, long long photon0, long long nphotons, int max_events, \
+        unsigned long long* sfc_dn_dir, unsigned long long* sfc_dn_dif, unsigned long long* sfc_up, unsigned long long* tod_up, \
+        unsigned long long* abs_dir, unsigned long long* abs_dif, unsigned long long* n_capped, \
+        unsigned long long* toa_up, unsigned long long* tod_dn_dir, unsigned long long* tod_dn_dif, \
+        unsigned long long* bg_abs_dir, unsigned long long* bg_abs_dif, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_profile, void* stream) \
+{ return trace_entry<F>("rrx_rt_trace_counts_bg" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
+                        cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, k_null, seed, \
+                        photon0, nphotons, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
+                        PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, true, \
+                        BgTallies<F>{toa_up, tod_dn_dir, tod_dn_dif, bg_abs_dir, bg_abs_dif}, nbg, dz_bg, bg_profile); } \
+int rrx_raytracer_sw_bg##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
+        long long photons_per_pixel, unsigned long long seed, int max_events, \
+        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, \
+        F* toa_up, F* tod_dn_dir, F* tod_dn_dif, F* bg_abs_dir, F* bg_abs_dif, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, void* stream) \
+{ F* const bg_out[5] = {toa_up, tod_dn_dir, tod_dn_dif, bg_abs_dir, bg_abs_dif}; \
+  return raytracer_sw_entry<F>("rrx_raytracer_sw_bg" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
+                               cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, \
+                               photons_per_pixel, seed, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
+                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, true, bg_out, nbg, dz_bg, bg_tau, bg_ssa, \
+                               bg_cld_tau, bg_cld_ssa, bg_cld_g); }
 
 RRX_DEFINE_RT(double, _f64)
 RRX_DEFINE_RT(float, _f32)

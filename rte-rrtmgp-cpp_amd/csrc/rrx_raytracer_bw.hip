@@ -107,22 +107,43 @@ __device__ __forceinline__ bool after_surface(Stream& rng, F& weight, F& ux, F& 
     return true;
 }
 
-template<typename F, bool TABLE>
-__global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, const PhaseArgs<F,TABLE> ph)
+// DRAW ORDER WITH A BACKGROUND (tests/raytracer_bg_ref.py restates it): that of the header. start: the same draws. each event in layer b: u -> tau = -log(u) unless the
+// previous event was a crossing (between layers, between blocks or through the domain top in either direction); a crossing draws
+// nothing; collision: weight *= f_no_abs; weight < 0.5: u -> roulette; survivor: u -> scatter or null (it always scatters);
+// u -> species; deposit (no walk); u -> cos of the scattering angle; u -> phi.
+//
+// BG (trace_bw_kernel<F,TABLE,true>; rrx_rt_common.h): the background atmosphere above the grid. A ray that leaves the
+// grid upward goes on through the layers and ends only at TOA; one that comes down through the domain top enters the grid by
+// enter_grid. The top of the medium is TOA: a start at or above it is moved along the ray to it. The orthographic sensor and the
+// flux sensor facing down start at the height clamp(position.z, domain top, TOA): position.z = 0 is the domain top as without a
+// background, any position.z >= TOA is TOA. A start above the domain top lies in layer bg_layer_of(z) with x, y as they are.
+// A scattering in layer b at height z deposits as a grid scattering does, with T_sun = exp(-(k_ext_b (z[b+1] - z) + tau_above[b])/mu0)
+// and no walk: it is made inside the event, Henyey-Greenstein for the cloud species. A deposit from inside the grid ends its walk
+// with exp(-(tau_walk + tau_above[nbg]/mu0)): one exp of the summed path. The draw order is that of the header. nbg = 0: the
+// integers of the other instantiations.
+template<typename F, bool TABLE, bool BG>
+__global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, const PhaseArgs<F,TABLE> ph, const BgArgs<F,BG> bgin)
 {
     const long long nthreads = (long long)gridDim.x*blockDim.x;
     long long next_ray = (long long)blockIdx.x*blockDim.x + threadIdx.x;
 
-    // the nodes, searched by every cloud scattering and shared by all lanes: nmu numbers of dynamic LDS (nmu <= 4096 on the host)
+    // the nodes, searched by every cloud scattering and shared by all lanes: nmu numbers of dynamic LDS (nmu <= 4096 on the host);
+    // behind them the background's profile and levels
     [[maybe_unused]] const F* mu_s = nullptr;
     [[maybe_unused]] PhaseTable<F> tab{};
-    if constexpr (TABLE)
+    [[maybe_unused]] BgView<F> bg{};
+    if constexpr (TABLE || BG)
     {
         extern __shared__ double phase_lds[];
         F* stage = reinterpret_cast<F*>(phase_lds);
-        for (int n=threadIdx.x; n<ph.in.nmu; n+=blockDim.x) stage[n] = ph.in.mu[n];
-        __syncthreads();
-        mu_s = stage;
+        if constexpr (TABLE)
+        {
+            for (int n=threadIdx.x; n<ph.in.nmu; n+=blockDim.x) stage[n] = ph.in.mu[n];
+            if constexpr (!BG) __syncthreads();
+            mu_s = stage;
+            stage += ph.in.nmu;
+        }
+        if constexpr (BG) bg = stage_background(bgin.in, stage);
     }
 
     const int nx = a.nx, ny = a.ny, nz = a.nz;
@@ -142,6 +163,9 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
     // towards the sun, and the distance along it across one cell of each axis
     const F vx = -a.sun_x, vy = -a.sun_y, vz = -a.sun_z;
     const F dtx = vx != F(0.) ? a.dx/fabs(vx) : inf, dty = vy != F(0.) ? a.dy/fabs(vy) : inf, dtz = a.dz/vz;
+    // the top of the medium, and the slant optical path of the whole background
+    [[maybe_unused]] F z_toa = z_top, tau_bg_sun = F(0.);
+    if constexpr (BG) { if (bg.nbg > 0) { z_toa = bg.z[bg.nbg]; tau_bg_sun = bg.tau_above[bg.nbg]/a.mu0; } }
 
     Stream rng; rng.k0 = a.k0; rng.k1 = a.k1; rng.used = 4; rng.block = 0u; rng.c0 = rng.c1 = rng.c2 = 0u;
     bool alive = false, pending = false, walking = false;
@@ -179,7 +203,9 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
             ++w.steps;
             if (w.k == nz)
             {
-                const F d = w.dep*exp(-w.tau);
+                F d;
+                if constexpr (BG) d = w.dep*exp(-(w.tau + tau_bg_sun));
+                else d = w.dep*exp(-w.tau);
                 const bool clamped = d > F(1048576.);
                 if (clamped) atomicAdd(a.n_clamped, 1ull);
                 tally(a.counts, size_t(pix), to_count(clamped ? F(1048576.) : d));
@@ -227,31 +253,58 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
                     else
                     {
                         sx = fa*len_x; sy = fb*len_y;
-                        if (a.type == 2) { ux = a.ex; uy = a.ey; uz = a.ez; sz = z_top; }
+                        if constexpr (BG)
+                        {
+                            if (a.type == 2) { ux = a.ex; uy = a.ey; uz = a.ez; sz = clampf(a.pz, z_top, z_toa); }
+                            else if (a.ez > F(0.)) { lambert(rng, F(1.), ux, uy, uz); sz = F(0.); }
+                            else { lambert(rng, F(-1.), ux, uy, uz); sz = clampf(a.pz, z_top, z_toa); }
+                        }
+                        else if (a.type == 2) { ux = a.ex; uy = a.ey; uz = a.ez; sz = z_top; }
                         else if (a.ez > F(0.)) { lambert(rng, F(1.), ux, uy, uz); sz = F(0.); }
                         else { lambert(rng, F(-1.), ux, uy, uz); sz = z_top; }
                     }
-                    if (sz >= z_top)
+                    if (sz >= z_toa)
                     {
-                        if (!(uz < F(0.))) break;          // it looks away from the domain: the ray ends with nothing
-                        if (sz > z_top) { const F t = (z_top - sz)/uz; sx = sx + ux*t; sy = sy + uy*t; }
-                        sz = z_top;
+                        if (!(uz < F(0.))) break;          // it looks away from the medium: the ray ends with nothing
+                        if (sz > z_toa) { const F t = (z_toa - sz)/uz; sx = sx + ux*t; sy = sy + uy*t; }
+                        sz = z_toa;
                     }
-                    sx = sx - floor(sx/len_x)*len_x; sy = sy - floor(sy/len_y)*len_y;
-                    in = clampi(int(sx/kdx), 0, a.knx - 1); jn = clampi(int(sy/kdy), 0, a.kny - 1); kn = clampi(int(sz/kdz), 0, a.knz - 1);
-                    x = clampf(sx, F(in)*kdx, F(in+1)*kdx); y = clampf(sy, F(jn)*kdy, F(jn+1)*kdy); z = clampf(sz, F(kn)*kdz, F(kn+1)*kdz);
+                    [[maybe_unused]] bool starts_in_bg = false;
+                    if constexpr (BG) starts_in_bg = sz > z_top;
+                    if (starts_in_bg)
+                    {
+                        if constexpr (BG)
+                        {
+                            const int b = bg_layer_of(bg, sz);
+                            in = 0; jn = 0; kn = a.knz + b;
+                            x = sx; y = sy; z = clampf(sz, bg.z[b], bg.z[b+1]);
+                        }
+                    }
+                    else
+                    {
+                        sx = sx - floor(sx/len_x)*len_x; sy = sy - floor(sy/len_y)*len_y;
+                        in = clampi(int(sx/kdx), 0, a.knx - 1); jn = clampi(int(sy/kdy), 0, a.kny - 1); kn = clampi(int(sz/kdz), 0, a.knz - 1);
+                        x = clampf(sx, F(in)*kdx, F(in+1)*kdx); y = clampf(sy, F(jn)*kdy, F(jn+1)*kdy); z = clampf(sz, F(kn)*kdz, F(kn+1)*kdz);
+                    }
                     weight = F(1.); pending = false; nev = 0; alive = true;
                 }
                 if (nev >= a.max_events) { atomicAdd(a.n_capped, 1ull); alive = false; break; }
                 ++nev;
 
-                const F x_lo = F(in)*kdx, x_hi = F(in+1)*kdx, y_lo = F(jn)*kdy, y_hi = F(jn+1)*kdy, z_lo = F(kn)*kdz, z_hi = F(kn+1)*kdz;
+                // in_bg: the ray is in background layer kn - knz, a block with z faces only whose k_null is its own k_ext
+                [[maybe_unused]] bool in_bg = false;
+                if constexpr (BG) in_bg = kn >= a.knz;
+                const F x_lo = F(in)*kdx, x_hi = F(in+1)*kdx, y_lo = F(jn)*kdy, y_hi = F(jn+1)*kdy;
+                F z_lo = F(kn)*kdz, z_hi = F(kn+1)*kdz;
+                if constexpr (BG) { if (in_bg) { z_lo = bg.z[kn - a.knz]; z_hi = bg.z[kn - a.knz + 1]; } }
                 const F sz = uz > F(0.) ? (z_hi - z)/uz : (uz < F(0.) ? (z_lo - z)/uz : inf);
-                const F sx = ux > F(0.) ? (x_hi - x)/ux : (ux < F(0.) ? (x_lo - x)/ux : inf);
-                const F sy = uy > F(0.) ? (y_hi - y)/uy : (uy < F(0.) ? (y_lo - y)/uy : inf);
+                const F sx = in_bg ? inf : (ux > F(0.) ? (x_hi - x)/ux : (ux < F(0.) ? (x_lo - x)/ux : inf));
+                const F sy = in_bg ? inf : (uy > F(0.) ? (y_hi - y)/uy : (uy < F(0.) ? (y_lo - y)/uy : inf));
                 const F d_max = min(sz, min(sx, sy));
                 const int axis = (sz <= sx && sz <= sy) ? 2 : (sx <= sy ? 0 : 1);
-                const F kn_val = a.k_null[in + a.knx*(jn + a.kny*kn)];
+                F kn_val;
+                if constexpr (BG) kn_val = in_bg ? bg.k_ext[kn - a.knz] : a.k_null[in + a.knx*(jn + a.kny*min(kn, a.knz - 1))];
+                else kn_val = a.k_null[in + a.knx*(jn + a.kny*kn)];
                 if (!pending) tau = -log(rng.next<F>());
                 pending = false;
                 const bool empty = !(kn_val > F(0.));
@@ -262,8 +315,31 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
                     // ---- the ray leaves the block through the face of `axis`
                     if (!(d_max < inf)) { atomicAdd(a.n_capped, 1ull); alive = false; break; }
                     tau = tau - tau_cell; pending = true;
-                    x = clampf(x + ux*d_max, x_lo, x_hi); y = clampf(y + uy*d_max, y_lo, y_hi); z = clampf(z + uz*d_max, z_lo, z_hi);
-                    if (axis == 0)
+                    if (in_bg) { x = x + ux*d_max; y = y + uy*d_max; }
+                    else { x = clampf(x + ux*d_max, x_lo, x_hi); y = clampf(y + uy*d_max, y_lo, y_hi); }
+                    z = clampf(z + uz*d_max, z_lo, z_hi);
+                    [[maybe_unused]] bool handled = false;
+                    if constexpr (BG)
+                    {
+                        if (in_bg)
+                        {
+                            // ---- a z face of a background layer: TOA, the next layer, or the domain top from above
+                            handled = true;
+                            if (uz > F(0.))
+                            {
+                                if (kn == a.knz + bg.nbg - 1) alive = false;
+                                else { ++kn; z = bg.z[kn - a.knz]; }
+                            }
+                            else if (kn == a.knz)
+                            {
+                                enter_grid(x, in, len_x, kdx, a.knx); enter_grid(y, jn, len_y, kdy, a.kny);
+                                kn = a.knz - 1; z = z_top;
+                            }
+                            else { --kn; z = bg.z[kn - a.knz + 1]; }
+                        }
+                    }
+                    if (handled) {}          // (the background's face, above)
+                    else if (axis == 0)
                     {
                         if (ux > F(0.)) { in = (in + 1 == a.knx) ? 0 : in + 1; x = F(in)*kdx; }
                         else { in = (in == 0) ? a.knx - 1 : in - 1; x = F(in+1)*kdx; }
@@ -275,7 +351,11 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
                     }
                     else if (uz > F(0.))
                     {
-                        if (kn == a.knz - 1) alive = false;          // out through the domain top
+                        if (kn == a.knz - 1)          // out through the domain top
+                        {
+                            alive = false;
+                            if constexpr (BG) { if (bg.nbg > 0) { alive = true; kn = a.knz; z = bg.z[0]; } }
+                        }
                         else { ++kn; z = F(kn)*kdz; }
                     }
                     else if (kn == 0)                 // the surface
@@ -293,21 +373,38 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
                 {
                     // ---- a collision inside the block
                     const F dn = tau / kn_val;
-                    x = clampf(x + ux*dn, x_lo, x_hi); y = clampf(y + uy*dn, y_lo, y_hi); z = clampf(z + uz*dn, z_lo, z_hi);
-                    const int i = fine_cell(x, a.dx, in, rx), j = fine_cell(y, a.dy, jn, ry), k = fine_cell(z, a.dz, kn, rz);
-                    const int lay = a.top_at_1 ? nz-1-k : k;
-                    const size_t cell = size_t(i) + size_t(j)*nx + ncol*lay;
-                    const F t = tau_g[cell], w0 = ssa_g[cell];
-                    F tc = F(0.), wc = F(0.), gc = F(0.);
-                    if (ibnd >= 0)
+                    if (in_bg) { x = x + ux*dn; y = y + uy*dn; }
+                    else { x = clampf(x + ux*dn, x_lo, x_hi); y = clampf(y + uy*dn, y_lo, y_hi); }
+                    z = clampf(z + uz*dn, z_lo, z_hi);
+                    // the cell and its k_ext, k_sca, k_sca_cld: a cell of the grid, or the ray's background layer
+                    int i = 0, j = 0, k = 0;
+                    size_t cell = 0;
+                    F k_ext = F(0.), k_sca = F(0.), k_sca_cld = F(0.), gc = F(0.);
+                    if (in_bg)
                     {
-                        const size_t cb = cell + ncol*nz*ibnd;
-                        tc = a.cld_tau[cb]; wc = a.cld_ssa[cb];
-                        if constexpr (!TABLE) gc = a.cld_g[cb];
+                        if constexpr (BG)
+                        {
+                            cell = size_t(kn - a.knz);
+                            k_ext = kn_val; k_sca = bg.k_sca[cell]; k_sca_cld = bg.k_sca_cld[cell]; gc = bg.g[cell];
+                        }
                     }
-                    const F k_ext = k_ext_of(t, tc, a.dz);
-                    const F k_sca = (t*w0 + tc*wc) / a.dz;
-                    const F k_sca_cld = (tc*wc) / a.dz;
+                    else
+                    {
+                        i = fine_cell(x, a.dx, in, rx); j = fine_cell(y, a.dy, jn, ry); k = fine_cell(z, a.dz, kn, rz);
+                        const int lay = a.top_at_1 ? nz-1-k : k;
+                        cell = size_t(i) + size_t(j)*nx + ncol*lay;
+                        const F t = tau_g[cell], w0 = ssa_g[cell];
+                        F tc = F(0.), wc = F(0.);
+                        if (ibnd >= 0)
+                        {
+                            const size_t cb = cell + ncol*nz*ibnd;
+                            tc = a.cld_tau[cb]; wc = a.cld_ssa[cb];
+                            if constexpr (!TABLE) gc = a.cld_g[cb];
+                        }
+                        k_ext = k_ext_of(t, tc, a.dz);
+                        k_sca = (t*w0 + tc*wc) / a.dz;
+                        k_sca_cld = (tc*wc) / a.dz;
+                    }
                     const F f_no_abs = clampf(F(1.) - (k_ext - k_sca)/kn_val, F(0.), F(1.));
                     weight = weight * f_no_abs;
                     if (weight < F(0.5)) weight = (rng.next<F>() > weight) ? F(0.) : F(1.);
@@ -317,6 +414,29 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
                         const bool cloud = rng.next<F>()*k_sca < k_sca_cld;
                         const F cs = clampf(-((ux*a.sun_x + uy*a.sun_y) + uz*a.sun_z), F(-1.), F(1.));
                         F phase;
+                        [[maybe_unused]] bool bg_done = false;
+                        if constexpr (BG)
+                        {
+                            if (in_bg)
+                            {
+                                // ---- a scattering in background layer b: the deposit needs no walk (the layers are horizontally uniform)
+                                bg_done = true;
+                                if (cloud)
+                                {
+                                    const F g = min(gc, g_max);
+                                    const F q = (F(1.) + g*g) - (F(2.)*g)*cs;
+                                    phase = (F(1.) - g*g) / (q*sqrt(q));
+                                }
+                                else phase = F(0.75)*(F(1.) + cs*cs);
+                                const F dep = (weight*phase)/(F(4.)*pi);
+                                const F d = dep*exp(-((k_ext*(z_hi - z) + bg.tau_above[cell])/a.mu0));
+                                const bool clamped = d > F(1048576.);
+                                if (clamped) atomicAdd(a.n_clamped, 1ull);
+                                tally(a.counts, size_t(pix), to_count(clamped ? F(1048576.) : d));
+                                scatter_direction(rng, cloud, gc, g_max, ux, uy, uz);
+                            }
+                        }
+                        if (bg_done) break;
                         if constexpr (TABLE)
                         {
                             if (cloud) { gc = ph.in.cld_re[cell]; phase = phase_eval(tab, mu_s, gc, cs); }          // cld_re (ncol, nz): one radius for all bands
@@ -367,7 +487,7 @@ void check_sensor(const int type, const F fov, const F* s, const F dx, const F d
 
 template<typename F>
 void launch_trace_bw(BwArgs<F> a, const PhaseIn<F>& ph, const F mu0, const F azimuth, const int type, const int npx, const int npy, const F fov,
-                     const F* s, const u64 seed, hipStream_t st)
+                     const F* s, const u64 seed, hipStream_t st, const BgArgs<F,true>* bg = nullptr)
 {
     const double st_ = std::sqrt(std::max(0.0, 1.0 - double(mu0)*double(mu0)));
     a.mu0 = mu0; a.sun_x = F(st_*std::cos(double(azimuth))); a.sun_y = F(st_*std::sin(double(azimuth))); a.sun_z = -mu0;
@@ -376,8 +496,14 @@ void launch_trace_bw(BwArgs<F> a, const PhaseIn<F>& ph, const F mu0, const F azi
     a.px = s[0]; a.py = s[1]; a.pz = s[2]; a.wx = s[3]; a.wy = s[4]; a.wz = s[5]; a.hx = s[6]; a.hy = s[7]; a.hz = s[8];
     a.ex = s[9]; a.ey = s[10]; a.ez = s[11];
     const int blocks = int(std::min<long long>((a.nrays + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
-    if (ph.given()) trace_bw_kernel<F,true><<<blocks, RT_BLOCK, size_t(ph.nmu)*sizeof(F), st>>>(a, PhaseArgs<F,true>{ph});
-    else trace_bw_kernel<F,false><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,false>{});
+    if (bg != nullptr)
+    {
+        const size_t lds = bg_lds_numbers(bg->in.nbg)*sizeof(F);
+        if (ph.given()) trace_bw_kernel<F,true,true><<<blocks, RT_BLOCK, size_t(ph.nmu)*sizeof(F) + lds, st>>>(a, PhaseArgs<F,true>{ph}, *bg);
+        else trace_bw_kernel<F,false,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, *bg);
+    }
+    else if (ph.given()) trace_bw_kernel<F,true,false><<<blocks, RT_BLOCK, size_t(ph.nmu)*sizeof(F), st>>>(a, PhaseArgs<F,true>{ph}, BgArgs<F,false>{});
+    else trace_bw_kernel<F,false,false><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,false>{}, BgArgs<F,false>{});
 }
 
 template<typename F>
@@ -400,9 +526,11 @@ int trace_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd
                    const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
                    F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null,
                    int sensor_type, int npx, int npy, F fov, const F* sensor, u64 seed, long long ray0, long long nrays, int max_events,
-                   u64* counts, u64* n_capped, u64* n_clamped, void* stream, const PhaseIn<F> ph = PhaseIn<F>{})
+                   u64* counts, u64* n_capped, u64* n_clamped, void* stream, const PhaseIn<F> ph = PhaseIn<F>{},
+                   const bool with_bg = false, const int nbg = 0, const F* dz_bg = nullptr, const F* bg_profile = nullptr)
 {
     RRX_TRY
+    check_nbg(nbg);
     if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"npx", npx}, {"npy", npy}, {"nrays", nrays}})) return 0;
     if (nbnd < 0) throw std::runtime_error("nbnd is negative");
     if (ray0 < 0) throw std::runtime_error("ray0 is negative");
@@ -419,6 +547,17 @@ int trace_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd
     check_sensor(sensor_type, fov, sensor, dx, dy, dz, nx, ny, nz, mu0, max_walk);
     BwArgs<F> a = scene_args<F>(nx, ny, nz, nbnd, igpt, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo,
                                 knx, kny, knz, k_null, u64(ray0), nrays, max_events, max_walk, counts, n_capped, n_clamped);
+    if (with_bg)
+    {
+        BgArgs<F,true> bg{BgIn<F>{nbg, bg_profile, BgLevels<F>{}}};
+        if (nbg > 0)
+        {
+            check_needed({{"dz_bg", dz_bg}, {"bg_profile", bg_profile}});
+            bg.in.z = bg_levels<F>(nbg, dz_bg, nz, knz, dz);
+        }
+        launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, static_cast<hipStream_t>(stream), &bg);
+        return 0;
+    }
     launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, static_cast<hipStream_t>(stream));
     RRX_CATCH(entry)
 }
@@ -430,6 +569,12 @@ inline int k_null_of(int nx, int ny, int nz, int ngpt, int nbnd, int g, RrxBool 
 inline int k_null_of(int nx, int ny, int nz, int ngpt, int nbnd, int g, RrxBool t, const float* tau, const int* lims, const float* ct,
                      float dz, int knx, int kny, int knz, float* kn, void* st)
 { return rrx_rt_k_null_f32(nx, ny, nz, ngpt, nbnd, g, t, tau, lims, ct, dz, knx, kny, knz, kn, st); }
+inline int bg_profile_of(int nbg, int ngpt, int nbnd, int g, const double* dzb, const double* t, const double* w, const int* lims, const double* ct,
+                         const double* cw, const double* cg, double* prof, void* st)
+{ return rrx_rt_bg_profile_f64(nbg, ngpt, nbnd, g, dzb, t, w, lims, ct, cw, cg, prof, st); }
+inline int bg_profile_of(int nbg, int ngpt, int nbnd, int g, const float* dzb, const float* t, const float* w, const int* lims, const float* ct,
+                         const float* cw, const float* cg, float* prof, void* st)
+{ return rrx_rt_bg_profile_f32(nbg, ngpt, nbnd, g, dzb, t, w, lims, ct, cw, cg, prof, st); }
 inline int counts_to_flux_of(long long n, const u64* c, double scale, double* out, void* st) { return rrx_rt_counts_to_flux_f64(n, c, scale, out, st); }
 inline int counts_to_flux_of(long long n, const u64* c, float scale, float* out, void* st) { return rrx_rt_counts_to_flux_f32(n, c, scale, out, st); }
 
@@ -438,9 +583,12 @@ int raytracer_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
                        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
                        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz,
                        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, u64 seed, int max_events,
-                       F* radiance, u64* n_capped, u64* n_clamped, void* stream, const PhaseIn<F> ph = PhaseIn<F>{})
+                       F* radiance, u64* n_capped, u64* n_clamped, void* stream, const PhaseIn<F> ph = PhaseIn<F>{},
+                       const bool with_bg = false, const int nbg = 0, const F* dz_bg = nullptr, const F* bg_tau = nullptr,
+                       const F* bg_ssa = nullptr, const F* bg_cld_tau = nullptr, const F* bg_cld_ssa = nullptr, const F* bg_cld_g = nullptr)
 {
     RRX_TRY
+    check_nbg(nbg);
     if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"npx", npx}, {"npy", npy}, {"rays_per_pixel", rays_per_pixel}})) return 0;
     if (nbnd < 0) throw std::runtime_error("nbnd is negative");
     check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"inc_dir", inc_dir}, {"sensor", sensor}, {"radiance", radiance},
@@ -455,13 +603,22 @@ int raytracer_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
     if ((long long)npx*npy > 0x7FFFFFFFll) throw std::runtime_error("npx npy exceeds 2^31 - 1");
     int max_walk = 0;
     check_sensor(sensor_type, fov, sensor, dx, dy, dz, nx, ny, nz, mu0, max_walk);
+    const bool bg_on = with_bg && nbg > 0;
+    BgLevels<F> lev{};
+    if (bg_on)
+    {
+        check_bg_medium(nbg, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g);
+        lev = bg_levels<F>(nbg, dz_bg, nz, knz, dz);
+    }
 
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t npix = size_t(npx)*npy;
     const size_t n_kn = (size_t(knx)*kny*knz*sizeof(F) + sizeof(u64) - 1) / sizeof(u64);
+    const size_t n_prof = bg_on ? (size_t(BG_ROWS)*(nbg + 1)*sizeof(F) + sizeof(u64) - 1) / sizeof(u64) : 0;
     WorkspaceLease lease(st);
-    u64* counts = lease.get<u64>(npix + n_kn);
+    u64* counts = lease.get<u64>(npix + n_kn + n_prof);
     F* k_null = reinterpret_cast<F*>(counts + npix);
+    F* profile = reinterpret_cast<F*>(counts + npix + n_kn);
     bool ok = hipMemsetAsync(n_capped, 0, sizeof(u64), st) == hipSuccess;
     ok = ok && hipMemsetAsync(n_clamped, 0, sizeof(u64), st) == hipSuccess;
     ok = ok && hipMemsetAsync(radiance, 0, npix*sizeof(F), st) == hipSuccess;
@@ -475,7 +632,14 @@ int raytracer_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
             throw std::runtime_error(rrx_last_error());
         BwArgs<F> a = scene_args<F>(nx, ny, nz, nbnd, g, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo,
                                     knx, kny, knz, k_null, 0ull, nrays, max_events, max_walk, counts, n_capped, n_clamped);
-        launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, st);
+        if (with_bg)
+        {
+            BgArgs<F,true> bg{BgIn<F>{bg_on ? nbg : 0, profile, lev}};
+            if (bg_on && bg_profile_of(nbg, ngpt, nbnd, g, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, profile, stream) != 0)
+                throw std::runtime_error(rrx_last_error());
+            launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, st, &bg);
+        }
+        else launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, st);
         const F scale = inc_dir[g] / (mu0*F(rays_per_pixel));
         if (counts_to_flux_of((long long)npix, counts, scale, radiance, stream) != 0) throw std::runtime_error(rrx_last_error());
     }
@@ -520,7 +684,30 @@ int rrx_raytracer_bw_phase##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxB
 { return raytracer_bw_entry<F>("rrx_raytracer_bw_phase" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, \
                                dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, \
                                rays_per_pixel, seed, max_events, radiance, n_capped, n_clamped, stream, \
-                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}); }
+                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}); } \
+int rrx_rt_bw_trace_counts_bg##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
+        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_profile, void* stream) \
+{ return trace_bw_entry<F>("rrx_rt_bw_trace_counts_bg" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, \
+                           cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, knx, kny, knz, k_null, sensor_type, npx, npy, fov, sensor, seed, ray0, \
+                           nrays, max_events, counts, n_capped, n_clamped, stream, PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, \
+                           true, nbg, dz_bg, bg_profile); } \
+int rrx_raytracer_bw_bg##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
+        F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, void* stream) \
+{ return raytracer_bw_entry<F>("rrx_raytracer_bw_bg" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, \
+                               dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, \
+                               rays_per_pixel, seed, max_events, radiance, n_capped, n_clamped, stream, \
+                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, true, nbg, dz_bg, bg_tau, bg_ssa, bg_cld_tau, \
+                               bg_cld_ssa, bg_cld_g); }
 
 RRX_DEFINE_RT_BW(double, _f64)
 RRX_DEFINE_RT_BW(float, _f32)

@@ -137,6 +137,81 @@ __device__ __forceinline__ void scatter_direction(Stream& rng, const bool cloud,
     rotate_direction(rng, clampf(cos_s, F(-1.), F(1.)), ux, uy, uz);
 }
 
+// ---- the background atmosphere between the domain top and TOA: nbg plane-parallel, horizontally uniform layers of
+// unequal thickness above the grid, counted UPWARD from the domain top whatever top_at_1 is. Layer b lies between z[b] and z[b+1];
+// z[0] = F(knz) (F(nz/knz) dz), the domain top exactly as the kernels form it, z[b+1] = z[b] + dz_bg[b] in index order, z[nbg] is TOA.
+// Per g-point rrx_rt_bg_profile writes the profile (BG_ROWS, nbg+1), layer fastest: k_ext, k_sca, k_sca_cld by the formulas of the
+// grid with dz_bg[b] in place of dz, g = min(g_c, 1 - eps), and tau_above[b] = the vertical optical depth tau + tau_c of the layers
+// b+1 .. nbg-1 added in index order from 0; slot nbg of tau_above holds the sum over all layers (what a walk that starts in the grid
+// reads), slot nbg of the other rows is 0.
+//
+// TRANSPORT (both kernels): a background layer is a block whose k_null is its own k_ext and that has z faces only. A photon or ray
+// in layer b carries the block index kn = knz + b. The collision is the grid's, draw for draw: f_no_abs = 1 - (k_ext - k_sca)/k_null,
+// the roulette, the scatter-or-null draw (still made; it always scatters), the species draw, then Rayleigh or Henyey-Greenstein
+// (the phase table applies inside the grid only). A layer with k_ext = 0 is crossed without a collision. A face crossing carries the
+// rest of tau, between layers and through the domain top in either direction, and counts as an event. x and y advance UNWRAPPED and
+// unclamped in the background (frozen under independent_column); on entering the grid from above they are wrapped by
+// x - floor(x/Lx) Lx and the block found by integer division and clamping (enter_grid; under independent_column the photon keeps
+// its x, y and block). uz = 0 in a layer with k_ext = 0: dropped into n_capped. No epsilon nudges.
+constexpr int RT_BG_MAX = 256;         // the largest nbg: the levels travel to the kernels by value and live in LDS with the profile
+enum { BG_K_EXT = 0, BG_K_SCA = 1, BG_K_SCA_CLD = 2, BG_G = 3, BG_TAU_ABOVE = 4, BG_ROWS = 5 };
+
+// nbg + 1 numbers by value: the levels z (trace kernels), or one number per layer (rrx_rt_bg_profile: dz_bg)
+template<typename F> struct BgLevels { F v[RT_BG_MAX + 1]; };
+
+template<typename F> struct BgIn { int nbg; const F* profile; BgLevels<F> z; };
+
+// the kernels' background argument: empty in the instantiations without one
+template<typename F, bool BG> struct BgArgs {};
+template<typename F> struct BgArgs<F,true> { BgIn<F> in; };
+
+// the profile and the levels in LDS: 6 (nbg + 1) numbers
+template<typename F>
+struct BgView
+{
+    int nbg;
+    const F* k_ext; const F* k_sca; const F* k_sca_cld; const F* g; const F* tau_above; const F* z;
+};
+
+inline size_t bg_lds_numbers(const int nbg) { return nbg > 0 ? size_t(BG_ROWS + 1)*(nbg + 1) : size_t(0); }
+
+// every thread of the workgroup calls it before its loop; lds: bg_lds_numbers(nbg) numbers
+template<typename F>
+__device__ __forceinline__ BgView<F> stage_background(const BgIn<F>& in, F* lds)
+{
+    const int n1 = in.nbg + 1;
+    if (in.nbg > 0)
+    {
+        for (int n=threadIdx.x; n<BG_ROWS*n1; n+=blockDim.x) lds[n] = in.profile[n];
+        for (int n=threadIdx.x; n<n1; n+=blockDim.x) lds[BG_ROWS*n1 + n] = in.z.v[n];
+    }
+    __syncthreads();
+    return BgView<F>{in.nbg, lds + BG_K_EXT*n1, lds + BG_K_SCA*n1, lds + BG_K_SCA_CLD*n1, lds + BG_G*n1, lds + BG_TAU_ABOVE*n1,
+                     lds + BG_ROWS*n1};
+}
+
+// the layer of a height above the domain top: the largest b <= nbg-1 with z[b] <= height (nbg >= 1)
+template<typename F> __device__ __forceinline__ int bg_layer_of(const BgView<F>& v, const F height)
+{
+    int b = 0;
+    while (b + 1 < v.nbg && v.z[b+1] <= height) ++b;
+    return b;
+}
+
+// a coordinate that comes down into the grid: wrapped into [0, len], its block of width kd and clamped into it
+template<typename F> __device__ __forceinline__ void enter_grid(F& pos, int& blk, const F len, const F kd, const int nblk)
+{
+    pos = pos - floor(pos/len)*len;
+    blk = clampi(int(pos/kd), 0, nblk - 1);
+    pos = clampf(pos, F(blk)*kd, F(blk+1)*kd);
+}
+
+// the fine cell (of n, width d) of an unwrapped coordinate
+template<typename F> __device__ __forceinline__ int wrapped_cell(const F pos, const F len, const F d, const int n)
+{
+    return clampi(int((pos - floor(pos/len)*len) / d), 0, n - 1);
+}
+
 // ---- host side: the argument checks of the entries (they throw; RRX_CATCH names the entry)
 
 inline void check_grid(const int nx, const int ny, const int nz, const int knx, const int kny, const int knz)
@@ -180,6 +255,41 @@ void check_scene(const F dx, const F dy, const F dz, const F mu0)
 {
     if (!(dx > F(0.)) || !(dy > F(0.)) || !(dz > F(0.))) throw std::runtime_error("dx, dy, dz must be > 0");
     if (!(mu0 > F(0.)) || mu0 > F(1.)) throw std::runtime_error("mu0 must be in (0, 1]");
+}
+
+// ---- the background's arguments
+
+// the levels of a background: throws on a non-positive (or NaN) thickness
+template<typename F>
+BgLevels<F> bg_levels(const int nbg, const F* dz_bg, const int nz, const int knz, const F dz)
+{
+    BgLevels<F> lev{};
+    lev.v[0] = F(knz)*(F(nz/knz)*dz);
+    for (int b=0; b<nbg; ++b)
+    {
+        if (!(dz_bg[b] > F(0.)) || !(dz_bg[b] < F(INFINITY))) throw std::runtime_error("dz_bg must be > 0");
+        lev.v[b+1] = lev.v[b] + dz_bg[b];
+    }
+    return lev;
+}
+
+// what the _bg entries check of their background arguments; nbg = 0: none of them is read
+template<typename F>
+void check_bg_medium(const int nbg, const int nbnd, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const int* band_lims_gpt,
+                     const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g)
+{
+    if (nbg == 0) return;
+    check_needed({{"dz_bg", dz_bg}, {"bg_tau", bg_tau}, {"bg_ssa", bg_ssa}});
+    const int given = (bg_cld_tau != nullptr) + (bg_cld_ssa != nullptr) + (bg_cld_g != nullptr);
+    if (given != 0 && given != 3) throw std::runtime_error("bg_cld_tau, bg_cld_ssa, bg_cld_g must be all NULL or all given");
+    if (given == 3 && band_lims_gpt == nullptr) throw std::runtime_error("band_lims_gpt is NULL");
+    if (given == 3 && nbnd < 1) throw std::runtime_error("nbnd must be >= 1 with a background cloud triple");
+}
+
+inline void check_nbg(const int nbg)
+{
+    if (nbg < 0) throw std::runtime_error("nbg is negative");
+    if (nbg > RT_BG_MAX) throw std::runtime_error("nbg must be <= 256");
 }
 }  // namespace rt
 }  // namespace rrx

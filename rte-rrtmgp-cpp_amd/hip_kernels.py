@@ -718,6 +718,131 @@ class HipKernels:
                 radiance, n_capped, n_clamped, *table)
         return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
 
+    # A background atmosphere between the domain top and TOA (the rrx_*_bg entries). background=: None (nbg = 0, the
+    # medium of the entries above) or an object with dz (nbg,) numbers on the host, tau, ssa (ngpt, nbg) and cloud, None or
+    # (tau, ssa, g) of (nbnd, nbg) each; everything is counted upward from the domain top.
+    RT_BG_COUNTS = ("toa_up", "tod_dn_dir", "tod_dn_dif", "bg_abs_dir", "bg_abs_dif")
+
+    def _rt_table_args(self, who, phase, dims):
+        table = self._rt_phase(who, phase, dims)[1]
+        return table if table else (0, 0, 0.0, 0.0, None, None, None, None)
+
+    def _rt_bg_dz(self, background):
+        dz = np.ascontiguousarray(np.asarray(background.dz, dtype=self.np_dtype).reshape(-1))
+        if tuple(background.tau.shape[1:]) != (dz.size,) or tuple(background.ssa.shape) != tuple(background.tau.shape):
+            raise ValueError(f"raytracer: the background's tau, ssa are (ngpt, nbg = {dz.size}), got {tuple(background.tau.shape)}, "
+                             f"{tuple(background.ssa.shape)}")
+        return dz
+
+    def _rt_bg_medium(self, background):
+        """nbg, dz_bg, bg_tau, bg_ssa and the background's cloud triple, as the spectral _bg entries take them"""
+        if background is None:
+            return (0, None, None, None, None, None, None)
+        dz = self._rt_bg_dz(background)
+        cloud = (None, None, None) if background.cloud is None else tuple(background.cloud)
+        return (dz.size, dz, background.tau, background.ssa, *cloud)
+
+    def rt_bg_profile(self, background, igpt, band_lims=None):
+        """The profile (5, nbg+1) of g-point igpt: k_ext, k_sca, k_sca_cld, g, tau_above."""
+        dz = self._rt_bg_dz(background)
+        ngpt = background.tau.shape[0]
+        if background.cloud is not None and band_lims is None:
+            raise ValueError("raytracer: a background cloud triple needs band_lims")
+        nbnd = int(band_lims.shape[0]) if band_lims is not None else 0
+        cloud = (None, None, None) if background.cloud is None else tuple(background.cloud)
+        out = self.empty((5, dz.size + 1))
+        self._c("rt_bg_profile", dz.size, ngpt, nbnd, igpt, dz, background.tau, background.ssa,
+                band_lims if background.cloud is not None else None, *cloud, out)
+        return out
+
+    def rt_zero_counts_bg(self, nz, ncol, nbg):
+        out = self.rt_zero_counts(nz, ncol)
+        out.update({k: torch.zeros((ncol,), dtype=torch.int64, device=self.device) for k in self.RT_BG_COUNTS[:3]})
+        out.update({k: torch.zeros((max(nbg, 1),), dtype=torch.int64, device=self.device) for k in self.RT_BG_COUNTS[3:]})
+        return out
+
+    def rt_trace_counts_bg(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, k_null, seed,
+                           photon0, nphotons, top_at_1=False, independent_column=False, cloud=None, band_lims=None, counts=None,
+                           max_events=None, phase=None, background=None, bg_profile=None):
+        """rt_trace_counts with a background: bg_profile is rt_bg_profile's for igpt (made when None). The counts gain RT_BG_COUNTS."""
+        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        knx, kny, knz = (int(k) for k in kn_grid)
+        nbg, dzb = (0, None) if background is None else (len(background.dz), self._rt_bg_dz(background))
+        if background is not None and bg_profile is None:
+            bg_profile = self.rt_bg_profile(background, igpt, band_lims)
+        counts = self.rt_zero_counts_bg(dims[2], dims[0]*dims[1], nbg) if counts is None else counts
+        self._c("rt_trace_counts_bg", *dims, igpt, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0,
+                azimuth, inc_dir, inc_dif, knx, kny, knz, k_null, int(seed) & 0xFFFFFFFFFFFFFFFF, photon0, nphotons,
+                self.RT_MAX_EVENTS if max_events is None else max_events, *(counts[k] for k in self.RT_COUNTS), counts["n_capped"],
+                *(counts[k] for k in self.RT_BG_COUNTS), *self._rt_table_args("rt_trace_counts_bg", phase, dims), nbg, dzb, bg_profile)
+        return counts
+
+    def raytracer_sw_bg(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, photons_per_pixel, seed,
+                        top_at_1=False, independent_column=False, cloud=None, band_lims=None, max_events=None, phase=None,
+                        background=None):
+        """raytracer_sw with a background. Beside its outputs: toa_up, tod_dn_dir, tod_dn_dif (ncol,) in W m-2 and bg_abs_dir,
+        bg_abs_dif (nbg,) in W m-3 of a domain-wide layer (zeros without a background)."""
+        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        nz, ngpt, ncol = dims[2], dims[3], dims[0]*dims[1]
+        knx, kny, knz = (int(k) for k in kn_grid)
+        inc_dir = np.ascontiguousarray(np.asarray(inc_dir, dtype=self.np_dtype).reshape(-1))
+        inc_dif = np.ascontiguousarray(np.asarray(inc_dif, dtype=self.np_dtype).reshape(-1))
+        if inc_dir.size != ngpt or inc_dif.size != ngpt:
+            raise ValueError("raytracer: inc_dir, inc_dif are (ngpt,)")
+        medium = self._rt_bg_medium(background)
+        if background is not None and background.cloud is not None and band_lims is None:
+            raise ValueError("raytracer: a background cloud triple needs band_lims")
+        lims_all = band_lims if (cloud is not None or (background is not None and background.cloud is not None)) else None
+        out = {k: self.empty((ncol,)) for k in self.RT_COUNTS[:4]}
+        out.update({k: self.empty((nz, ncol)) for k in self.RT_COUNTS[4:]})
+        out.update({k: self.zeros((ncol,)) for k in self.RT_BG_COUNTS[:3]})
+        out.update({k: self.zeros((medium[0],)) for k in self.RT_BG_COUNTS[3:]})
+        n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        self._c("raytracer_sw_bg", *dims, top_at_1, independent_column, tau, ssa, lims_all, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth,
+                inc_dir, inc_dif, knx, kny, knz, photons_per_pixel, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                self.RT_MAX_EVENTS if max_events is None else max_events, *(out[k] for k in self.RT_COUNTS), n_capped,
+                *(out[k] if medium[0] else None for k in self.RT_BG_COUNTS), *self._rt_table_args("raytracer_sw_bg", phase, dims), *medium)
+        out["n_capped"] = int(n_capped.item())
+        return out
+
+    def rt_bw_trace_counts_bg(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, kn_grid, k_null, camera, seed, ray0, nrays,
+                              top_at_1=False, cloud=None, band_lims=None, counts=None, max_events=None, phase=None, background=None,
+                              bg_profile=None):
+        """rt_bw_trace_counts with a background: bg_profile is rt_bg_profile's for igpt (made when None)."""
+        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        knx, kny, knz = (int(k) for k in kn_grid)
+        sensor = self._rt_sensor(camera)
+        nbg, dzb = (0, None) if background is None else (len(background.dz), self._rt_bg_dz(background))
+        if background is not None and bg_profile is None:
+            bg_profile = self.rt_bg_profile(background, igpt, band_lims)
+        counts = self.rt_bw_zero_counts(sensor[1]*sensor[2]) if counts is None else counts
+        self._c("rt_bw_trace_counts_bg", *dims, igpt, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, knx, kny, knz,
+                k_null, *sensor, int(seed) & 0xFFFFFFFFFFFFFFFF, ray0, nrays, self.RT_MAX_EVENTS if max_events is None else max_events,
+                counts["counts"], counts["n_capped"], counts["n_clamped"], *self._rt_table_args("rt_bw_trace_counts_bg", phase, dims),
+                nbg, dzb, bg_profile)
+        return counts
+
+    def raytracer_bw_bg(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
+                        top_at_1=False, cloud=None, band_lims=None, max_events=None, phase=None, background=None):
+        """raytracer_bw with a background: radiance (npy, npx) in W m-2 sr-1, n_capped and n_clamped (ints)."""
+        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        knx, kny, knz = (int(k) for k in kn_grid)
+        inc_dir = np.ascontiguousarray(np.asarray(inc_dir, dtype=self.np_dtype).reshape(-1))
+        if inc_dir.size != dims[3]:
+            raise ValueError("raytracer: inc_dir is (ngpt,)")
+        medium = self._rt_bg_medium(background)
+        if background is not None and background.cloud is not None and band_lims is None:
+            raise ValueError("raytracer: a background cloud triple needs band_lims")
+        lims_all = band_lims if (cloud is not None or (background is not None and background.cloud is not None)) else None
+        sensor = self._rt_sensor(camera)
+        radiance = self.empty((sensor[2], sensor[1]))
+        n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        n_clamped = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        self._c("raytracer_bw_bg", *dims, top_at_1, tau, ssa, lims_all, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz,
+                *sensor, rays_per_pixel, int(seed) & 0xFFFFFFFFFFFFFFFF, self.RT_MAX_EVENTS if max_events is None else max_events,
+                radiance, n_capped, n_clamped, *self._rt_table_args("raytracer_bw_bg", phase, dims), *medium)
+        return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
+
     def delta_scale_2str_k(self, tau, ssa, g):
         ngpt, nlay, ncol = tau.shape
         self._c("delta_scale_2str_k", ncol, nlay, ngpt, tau, ssa, g)

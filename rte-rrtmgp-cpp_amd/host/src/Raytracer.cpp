@@ -38,6 +38,7 @@ unsigned long long Raytracer_gpu::trace_rays(
     if (has_table && (cld_re.dim(1) != ncol || cld_re.dim(2) != nz || phase.dim(3) != nbnd))
         throw std::runtime_error("Raytracer_gpu::trace_rays: the phase table's cld_re is not (nx ny, nz) or its tables are not (nmu, nre, nbnd)");
 
+    if (has_bg) throw std::runtime_error("Raytracer_gpu::trace_rays: a background is set: call the form with the background's outputs");
     Array_gpu<unsigned long long,1> n_capped({1});
     if (has_table)
         RRX_CALL(rrx_raytracer_sw_phase, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
@@ -55,6 +56,81 @@ unsigned long long Raytracer_gpu::trace_rays(
              photons_per_pixel, seed, max_events,
              sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr());
     return n_capped({1});
+}
+
+unsigned long long Raytracer_gpu::trace_rays(
+        const int nx, const int ny, const int nz,
+        const Float dx, const Float dy, const Float dz,
+        const bool top_at_1, const bool independent_column,
+        const Array_gpu<Float,3>& tau, const Array_gpu<Float,3>& ssa,
+        const Array_gpu<int,2>& band_lims_gpt,
+        const Array_gpu<Float,3>& cld_tau, const Array_gpu<Float,3>& cld_ssa, const Array_gpu<Float,3>& cld_g,
+        const Array_gpu<Float,1>& sfc_albedo,
+        const Float mu0, const Float azimuth,
+        const Array<Float,1>& inc_dir, const Array<Float,1>& inc_dif,
+        const int knx, const int kny, const int knz,
+        const long long photons_per_pixel, const unsigned long long seed, const int max_events,
+        Array_gpu<Float,1>& sfc_dn_dir, Array_gpu<Float,1>& sfc_dn_dif, Array_gpu<Float,1>& sfc_up, Array_gpu<Float,1>& tod_up,
+        Array_gpu<Float,2>& abs_dir, Array_gpu<Float,2>& abs_dif,
+        Array_gpu<Float,1>& toa_up, Array_gpu<Float,1>& tod_dn_dir, Array_gpu<Float,1>& tod_dn_dif,
+        Array_gpu<Float,1>& bg_abs_dir, Array_gpu<Float,1>& bg_abs_dif)
+{
+    if (!has_bg) throw std::runtime_error("Raytracer_gpu::trace_rays: no background is set (set_background)");
+    if (nx < 0 || ny < 0 || nz < 0) throw std::runtime_error("Raytracer_gpu::trace_rays: negative extent");
+    const long long ncol = (long long)nx*ny;
+    const int ngpt = tau.dim(3);
+    const int nbnd = band_lims_gpt.dim(2);
+    const int nbg = dz_bg.size();
+    if (tau.dim(1) != ncol || tau.dim(2) != nz || ssa.get_dims() != tau.get_dims())
+        throw std::runtime_error("Raytracer_gpu::trace_rays: tau, ssa are not (nx ny, nz, ngpt)");
+    const bool cloudy = cld_tau.size() > 0;
+    if (cloudy && (cld_tau.dim(1) != ncol || cld_tau.dim(2) != nz || cld_tau.dim(3) != nbnd || cld_ssa.get_dims() != cld_tau.get_dims() ||
+                   cld_g.get_dims() != cld_tau.get_dims()))
+        throw std::runtime_error("Raytracer_gpu::trace_rays: the cloud arrays are not (nx ny, nz, nbnd)");
+    if (!cloudy && (cld_ssa.size() > 0 || cld_g.size() > 0))
+        throw std::runtime_error("Raytracer_gpu::trace_rays: the cloud arrays are all empty or all given");
+    if (sfc_albedo.size() != ncol || inc_dir.size() != ngpt || inc_dif.size() != ngpt)
+        throw std::runtime_error("Raytracer_gpu::trace_rays: sfc_albedo is not (nx ny) or inc_dir, inc_dif are not (ngpt)");
+    for (const Array_gpu<Float,1>* a : {&sfc_dn_dir, &sfc_dn_dif, &sfc_up, &tod_up, &toa_up, &tod_dn_dir, &tod_dn_dif})
+        if (a->size() != ncol) throw std::runtime_error("Raytracer_gpu::trace_rays: a flux array is not (nx ny)");
+    for (const Array_gpu<Float,2>* a : {&abs_dir, &abs_dif})
+        if (a->dim(1) != ncol || a->dim(2) != nz) throw std::runtime_error("Raytracer_gpu::trace_rays: an absorption array is not (nx ny, nz)");
+    for (const Array_gpu<Float,1>* a : {&bg_abs_dir, &bg_abs_dif})
+        if (a->size() != nbg) throw std::runtime_error("Raytracer_gpu::trace_rays: a background absorption array is not (nbg)");
+    if (bg_tau.dim(2) != ngpt) throw std::runtime_error("Raytracer_gpu::trace_rays: the background's bg_tau, bg_ssa are not (nbg, ngpt)");
+    const bool bg_cloudy = bg_cld_tau.size() > 0;
+    if (bg_cloudy && bg_cld_tau.dim(2) != nbnd) throw std::runtime_error("Raytracer_gpu::trace_rays: the background's cloud arrays are not (nbg, nbnd)");
+    if (has_table && (cld_re.dim(1) != ncol || cld_re.dim(2) != nz || phase.dim(3) != nbnd))
+        throw std::runtime_error("Raytracer_gpu::trace_rays: the phase table's cld_re is not (nx ny, nz) or its tables are not (nmu, nre, nbnd)");
+
+    Array_gpu<unsigned long long,1> n_capped({1});
+    const Float* none = nullptr;
+    RRX_CALL(rrx_raytracer_sw_bg, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
+             tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
+             cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
+             dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), inc_dif.ptr(), knx, kny, knz,
+             photons_per_pixel, seed, max_events,
+             sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr(),
+             toa_up.ptr(), tod_dn_dir.ptr(), tod_dn_dif.ptr(), bg_abs_dir.ptr(), bg_abs_dif.ptr(),
+             has_table ? mu.dim(1) : 0, has_table ? phase.dim(2) : 0, re0, dre, has_table ? mu.ptr() : none, has_table ? phase.ptr() : none,
+             has_table ? cdf.ptr() : none, has_table ? cld_re.ptr() : none,
+             nbg, dz_bg.ptr(), bg_tau.ptr(), bg_ssa.ptr(), bg_cloudy ? bg_cld_tau.ptr() : none, bg_cloudy ? bg_cld_ssa.ptr() : none,
+             bg_cloudy ? bg_cld_g.ptr() : none);
+    return n_capped({1});
+}
+
+void Raytracer_gpu::set_background(const Array<Float,1>& dz_in, const Array_gpu<Float,2>& tau_in, const Array_gpu<Float,2>& ssa_in,
+                                   const Array_gpu<Float,2>& ctau_in, const Array_gpu<Float,2>& cssa_in, const Array_gpu<Float,2>& cg_in)
+{
+    const int nbg = dz_in.size();
+    if (nbg < 1 || tau_in.dim(1) != nbg || ssa_in.get_dims() != tau_in.get_dims())
+        throw std::runtime_error("Raytracer_gpu::set_background: dz_bg is not (nbg >= 1) or bg_tau, bg_ssa are not (nbg, ngpt)");
+    const bool cloudy = ctau_in.size() > 0;
+    if (cloudy ? (ctau_in.dim(1) != nbg || cssa_in.get_dims() != ctau_in.get_dims() || cg_in.get_dims() != ctau_in.get_dims())
+               : (cssa_in.size() > 0 || cg_in.size() > 0))
+        throw std::runtime_error("Raytracer_gpu::set_background: the background's cloud arrays are all empty or all (nbg, nbnd)");
+    dz_bg = dz_in; bg_tau = tau_in; bg_ssa = ssa_in; bg_cld_tau = ctau_in; bg_cld_ssa = cssa_in; bg_cld_g = cg_in;
+    has_bg = true;
 }
 
 void Raytracer_gpu::set_phase_table(const Array_gpu<Float,1>& mu_in, const Array_gpu<Float,3>& phase_in, const Array_gpu<Float,3>& cdf_in,

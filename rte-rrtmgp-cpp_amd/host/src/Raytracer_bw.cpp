@@ -38,7 +38,24 @@ unsigned long long Raytracer_bw_gpu::trace_rays_bw(
     if (has_table && (cld_re.dim(1) != ncol || cld_re.dim(2) != nz || phase.dim(3) != nbnd))
         throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: the phase table's cld_re is not (nx ny, nz) or its tables are not (nmu, nre, nbnd)");
     Array_gpu<unsigned long long,1> tallies({2});
-    if (has_table)
+    if (has_bg)
+    {
+        const bool bg_cloudy = bg_cld_tau.size() > 0;
+        if (bg_tau.dim(2) != ngpt || (bg_cloudy && bg_cld_tau.dim(2) != nbnd))
+            throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: the background's arrays are not (nbg, ngpt) and (nbg, nbnd)");
+        const Float* none = nullptr;
+        RRX_CALL(rrx_raytracer_bw_bg, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1),
+                 tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
+                 cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
+                 dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), knx, kny, knz,
+                 sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers, rays_per_pixel, seed, max_events,
+                 radiance.ptr(), tallies.ptr(), tallies.ptr() + 1,
+                 has_table ? mu.dim(1) : 0, has_table ? phase.dim(2) : 0, re0, dre, has_table ? mu.ptr() : none, has_table ? phase.ptr() : none,
+                 has_table ? cdf.ptr() : none, has_table ? cld_re.ptr() : none,
+                 dz_bg.size(), dz_bg.ptr(), bg_tau.ptr(), bg_ssa.ptr(), bg_cloudy ? bg_cld_tau.ptr() : none,
+                 bg_cloudy ? bg_cld_ssa.ptr() : none, bg_cloudy ? bg_cld_g.ptr() : none);
+    }
+    else if (has_table)
         RRX_CALL(rrx_raytracer_bw_phase, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1),
                  tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
                  cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
@@ -55,6 +72,20 @@ unsigned long long Raytracer_bw_gpu::trace_rays_bw(
              radiance.ptr(), tallies.ptr(), tallies.ptr() + 1);
     if (n_clamped_out != nullptr) *n_clamped_out = tallies({2});
     return tallies({1});
+}
+
+void Raytracer_bw_gpu::set_background(const Array<Float,1>& dz_in, const Array_gpu<Float,2>& tau_in, const Array_gpu<Float,2>& ssa_in,
+                                      const Array_gpu<Float,2>& ctau_in, const Array_gpu<Float,2>& cssa_in, const Array_gpu<Float,2>& cg_in)
+{
+    const int nbg = dz_in.size();
+    if (nbg < 1 || tau_in.dim(1) != nbg || ssa_in.get_dims() != tau_in.get_dims())
+        throw std::runtime_error("Raytracer_bw_gpu::set_background: dz_bg is not (nbg >= 1) or bg_tau, bg_ssa are not (nbg, ngpt)");
+    const bool cloudy = ctau_in.size() > 0;
+    if (cloudy ? (ctau_in.dim(1) != nbg || cssa_in.get_dims() != ctau_in.get_dims() || cg_in.get_dims() != ctau_in.get_dims())
+               : (cssa_in.size() > 0 || cg_in.size() > 0))
+        throw std::runtime_error("Raytracer_bw_gpu::set_background: the background's cloud arrays are all empty or all (nbg, nbnd)");
+    dz_bg = dz_in; bg_tau = tau_in; bg_ssa = ssa_in; bg_cld_tau = ctau_in; bg_cld_ssa = cssa_in; bg_cld_g = cg_in;
+    has_bg = true;
 }
 
 void Raytracer_bw_gpu::set_phase_table(const Array_gpu<Float,1>& mu_in, const Array_gpu<Float,3>& phase_in, const Array_gpu<Float,3>& cdf_in,

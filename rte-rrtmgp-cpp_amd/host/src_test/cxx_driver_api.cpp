@@ -202,6 +202,58 @@ int rrx_cxx_driver_fluxes(void* h, const Float** ptrs)
 // sfc_dn_dif, sfc_up, tod_up (ncol), abs_dir, abs_dif (ncol, nz). Runs on `stream` and waits for the count of dropped photons.
 // rrx_cxx_trace_rays_phase: the same after Raytracer_gpu::set_phase_table(mu (nmu), phase, cdf (nmu, nre, nbnd), re0, dre, cld_re (ncol, nz)),
 // device arrays; with mu NULL no table is set.
+// rrx_cxx_trace_rays_bg: the same after Raytracer_gpu::set_background(dz_bg (nbg) on the HOST, bg_tau, bg_ssa (nbg, ngpt), bg_cld_* (nbg, nbnd)
+// or all NULL); out5: device arrays toa_up, tod_dn_dir, tod_dn_dif (ncol), bg_abs_dir, bg_abs_dif (nbg). nbg = 0: no background is set
+// and out5 is not written.
+int rrx_cxx_trace_rays_bg(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+        const int top_at_1, const int independent_column, const Float* tau, const Float* ssa, const int* band_lims_gpt,
+        const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
+        const Float* inc_dir, const Float* inc_dif, const int knx, const int kny, const int knz, const long long photons_per_pixel,
+        const unsigned long long seed, const int max_events, Float* const* out6, unsigned long long* n_capped, Float* const* out5,
+        const int nmu, const int nre, const Float re0, const Float dre, const Float* mu, const Float* phase, const Float* cdf, const Float* cld_re,
+        const int nbg, const Float* dz_bg, const Float* bg_tau, const Float* bg_ssa, const Float* bg_cld_tau, const Float* bg_cld_ssa,
+        const Float* bg_cld_g, void* stream)
+{
+    return guarded([&]
+    {
+        void* const before = rrx_host::current_stream();
+        rrx_host::set_stream(stream);
+        try
+        {
+            const int ncol = nx*ny;
+            auto view3 = [](const Float* p, int a, int b, int c) { return p ? Array_gpu<Float,3>(const_cast<Float*>(p), {a, b, c}) : Array_gpu<Float,3>(); };
+            auto bview = [](const Float* p, int a, int b) { return p ? Array_gpu<Float,2>(const_cast<Float*>(p), {a, b}) : Array_gpu<Float,2>(); };
+            Array<Float,1> h_dir({ngpt}), h_dif({ngpt});
+            for (int g=1; g<=ngpt; ++g) { h_dir({g}) = inc_dir[g-1]; h_dif({g}) = inc_dif[g-1]; }
+            Array_gpu<Float,1> o0 = view1(out6[0], ncol), o1 = view1(out6[1], ncol), o2 = view1(out6[2], ncol), o3 = view1(out6[3], ncol);
+            Array_gpu<Float,2> o4 = view2(out6[4], ncol, nz), o5 = view2(out6[5], ncol, nz);
+            Raytracer_gpu raytracer;
+            if (mu != nullptr)
+                raytracer.set_phase_table(view1(mu, nmu), view3(phase, nmu, nre, nbnd), view3(cdf, nmu, nre, nbnd), re0, dre, view2(cld_re, ncol, nz));
+            if (nbg > 0)
+            {
+                Array<Float,1> h_dz({nbg});
+                for (int b=1; b<=nbg; ++b) h_dz({b}) = dz_bg[b-1];
+                raytracer.set_background(h_dz, bview(bg_tau, nbg, ngpt), bview(bg_ssa, nbg, ngpt), bview(bg_cld_tau, nbg, nbnd),
+                                         bview(bg_cld_ssa, nbg, nbnd), bview(bg_cld_g, nbg, nbnd));
+                Array_gpu<Float,1> b0 = view1(out5[0], ncol), b1 = view1(out5[1], ncol), b2 = view1(out5[2], ncol);
+                Array_gpu<Float,1> b3 = view1(out5[3], nbg), b4 = view1(out5[4], nbg);
+                *n_capped = raytracer.trace_rays(nx, ny, nz, dx, dy, dz, top_at_1 != 0, independent_column != 0,
+                        view3(tau, ncol, nz, ngpt), view3(ssa, ncol, nz, ngpt), Array_gpu<int,2>(const_cast<int*>(band_lims_gpt), {2, nbnd}),
+                        view3(cld_tau, ncol, nz, nbnd), view3(cld_ssa, ncol, nz, nbnd), view3(cld_g, ncol, nz, nbnd), view1(sfc_albedo, ncol),
+                        mu0, azimuth, h_dir, h_dif, knx, kny, knz, photons_per_pixel, seed, max_events, o0, o1, o2, o3, o4, o5, b0, b1, b2, b3, b4);
+            }
+            else
+                *n_capped = raytracer.trace_rays(nx, ny, nz, dx, dy, dz, top_at_1 != 0, independent_column != 0,
+                        view3(tau, ncol, nz, ngpt), view3(ssa, ncol, nz, ngpt), Array_gpu<int,2>(const_cast<int*>(band_lims_gpt), {2, nbnd}),
+                        view3(cld_tau, ncol, nz, nbnd), view3(cld_ssa, ncol, nz, nbnd), view3(cld_g, ncol, nz, nbnd), view1(sfc_albedo, ncol),
+                        mu0, azimuth, h_dir, h_dif, knx, kny, knz, photons_per_pixel, seed, max_events, o0, o1, o2, o3, o4, o5);
+        }
+        catch (...) { rrx_host::set_stream(before); throw; }
+        rrx_host::set_stream(before);
+    });
+}
+
 int rrx_cxx_trace_rays_phase(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
         const int top_at_1, const int independent_column, const Float* tau, const Float* ssa, const int* band_lims_gpt,
         const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
@@ -250,6 +302,16 @@ int rrx_cxx_trace_rays(const int nx, const int ny, const int nz, const int ngpt,
 // inc_dir (ngpt) and sensor (12 numbers: position, e_w, e_h, e_d) on the HOST; radiance: a device array (npx, npy). Runs on `stream`
 // and waits for the counts of dropped rays and clamped deposits.
 // rrx_cxx_trace_rays_bw_phase: the same after Raytracer_bw_gpu::set_phase_table, as rrx_cxx_trace_rays_phase.
+int rrx_cxx_trace_rays_bw_bg(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+        const int top_at_1, const Float* tau, const Float* ssa, const int* band_lims_gpt,
+        const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
+        const Float* inc_dir, const int knx, const int kny, const int knz, const int sensor_type, const int npx, const int npy, const Float fov,
+        const Float* sensor, const long long rays_per_pixel, const unsigned long long seed, const int max_events, Float* radiance,
+        unsigned long long* n_capped, unsigned long long* n_clamped,
+        const int nmu, const int nre, const Float re0, const Float dre, const Float* mu, const Float* phase, const Float* cdf, const Float* cld_re,
+        const int nbg, const Float* dz_bg, const Float* bg_tau, const Float* bg_ssa, const Float* bg_cld_tau, const Float* bg_cld_ssa,
+        const Float* bg_cld_g, void* stream);
+
 int rrx_cxx_trace_rays_bw_phase(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
         const int top_at_1, const Float* tau, const Float* ssa, const int* band_lims_gpt,
         const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
@@ -258,6 +320,23 @@ int rrx_cxx_trace_rays_bw_phase(const int nx, const int ny, const int nz, const 
         unsigned long long* n_capped, unsigned long long* n_clamped,
         const int nmu, const int nre, const Float re0, const Float dre, const Float* mu, const Float* phase, const Float* cdf, const Float* cld_re,
         void* stream)
+{
+    return rrx_cxx_trace_rays_bw_bg(nx, ny, nz, ngpt, nbnd, dx, dy, dz, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, sfc_albedo,
+                                    mu0, azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, rays_per_pixel, seed, max_events,
+                                    radiance, n_capped, n_clamped, nmu, nre, re0, dre, mu, phase, cdf, cld_re, 0, nullptr, nullptr, nullptr,
+                                    nullptr, nullptr, nullptr, stream);
+}
+
+// rrx_cxx_trace_rays_bw_bg: rrx_cxx_trace_rays_bw_phase after Raytracer_bw_gpu::set_background, as rrx_cxx_trace_rays_bg; nbg = 0: no background
+int rrx_cxx_trace_rays_bw_bg(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+        const int top_at_1, const Float* tau, const Float* ssa, const int* band_lims_gpt,
+        const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
+        const Float* inc_dir, const int knx, const int kny, const int knz, const int sensor_type, const int npx, const int npy, const Float fov,
+        const Float* sensor, const long long rays_per_pixel, const unsigned long long seed, const int max_events, Float* radiance,
+        unsigned long long* n_capped, unsigned long long* n_clamped,
+        const int nmu, const int nre, const Float re0, const Float dre, const Float* mu, const Float* phase, const Float* cdf, const Float* cld_re,
+        const int nbg, const Float* dz_bg, const Float* bg_tau, const Float* bg_ssa, const Float* bg_cld_tau, const Float* bg_cld_ssa,
+        const Float* bg_cld_g, void* stream)
 {
     return guarded([&]
     {
@@ -276,6 +355,14 @@ int rrx_cxx_trace_rays_bw_phase(const int nx, const int ny, const int nz, const 
             Raytracer_bw_gpu raytracer;
             if (mu != nullptr)
                 raytracer.set_phase_table(view1(mu, nmu), view3(phase, nmu, nre, nbnd), view3(cdf, nmu, nre, nbnd), re0, dre, view2(cld_re, ncol, nz));
+            if (nbg > 0)
+            {
+                auto bview = [](const Float* p, int a, int b) { return p ? Array_gpu<Float,2>(const_cast<Float*>(p), {a, b}) : Array_gpu<Float,2>(); };
+                Array<Float,1> h_dz({nbg});
+                for (int b=1; b<=nbg; ++b) h_dz({b}) = dz_bg[b-1];
+                raytracer.set_background(h_dz, bview(bg_tau, nbg, ngpt), bview(bg_ssa, nbg, ngpt), bview(bg_cld_tau, nbg, nbnd),
+                                         bview(bg_cld_ssa, nbg, nbnd), bview(bg_cld_g, nbg, nbnd));
+            }
             *n_capped = raytracer.trace_rays_bw(nx, ny, nz, dx, dy, dz, top_at_1 != 0,
                     view3(tau, ncol, nz, ngpt), view3(ssa, ncol, nz, ngpt), Array_gpu<int,2>(const_cast<int*>(band_lims_gpt), {2, nbnd}),
                     view3(cld_tau, ncol, nz, nbnd), view3(cld_ssa, ncol, nz, nbnd), view3(cld_g, ncol, nz, nbnd), view1(sfc_albedo, ncol),

@@ -183,7 +183,7 @@ def solve_sw(be, kd, atm, col_dry=None, cloud_lut=None, delta_cloud=False, do_br
 
 
 def raytrace_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, photons_per_pixel, seed, cloud_lut=None, kn_grid=None,
-                independent_column=False, sfc_albedo=None, max_events=None, phase_table=None):
+                independent_column=False, sfc_albedo=None, max_events=None, phase_table=None, n_domain=None, z_lev=None):
     """3-D shortwave surface / top fluxes and absorption from the forward Monte Carlo ray tracer (rrx_raytracer_sw).
 
     The atmosphere's columns are the pixels of an nx x ny domain (column = ix + nx iy) of cells dx x dy x dz metres, periodic in x
@@ -194,8 +194,21 @@ def raytrace_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, photons_per_pixel, 
     for direct and diffuse light (the tracer's surface is Lambertian with one broadband albedo per pixel).
     phase_table (phase_tables.PhaseTable, needs cloud_lut): cloud scatters by the tabulated phase function of the liquid radius
     atm.rel in place of Henyey-Greenstein.
-    Returns sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up (ncol,) in W m-2, abs_dir, abs_dif (nlay, ncol) in W m-3 and n_capped."""
+    n_domain < atm.nlay with z_lev (nlay+1,), the heights of the atmosphere's levels in metres in array order: the
+    lowest n_domain layers are the grid (of thickness dz) and the layers above are a horizontally uniform background up to TOA, taken
+    from column 0, with the thicknesses of z_lev; kn_grid then divides (nx, ny, n_domain) and inc_dir is incident at TOA.
+    Returns sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up (ncol,) in W m-2, abs_dir, abs_dif (nlay, ncol) in W m-3 and n_capped; with
+    n_domain also toa_up, tod_dn_dir, tod_dn_dif (ncol,) in W m-2 and bg_abs_dir, bg_abs_dif (nbg,) in W m-3 of a domain-wide layer,
+    counted upward from the domain top (abs_dir, abs_dif are then (n_domain, ncol), and tod_up is the flux through the domain top)."""
+    if n_domain is not None and kn_grid is None:
+        kn_grid = (nx, ny, int(n_domain))
     tau, ssa, cld, sfc_albedo, mu0, inc_dir, kn_grid = _raytracer_inputs("raytrace_sw", be, kd_sw, atm, nx, ny, cloud_lut, kn_grid, sfc_albedo)
+    if n_domain is not None:
+        tau, ssa, cld, rel, background = _raytracer_split("raytrace_sw", be, atm, tau, ssa, cld, n_domain, z_lev)
+        phase = _raytracer_phase("raytrace_sw", atm, cloud_lut, phase_table, rel)
+        return be.raytracer_sw_bg(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, np.zeros_like(inc_dir), kn_grid,
+                                  photons_per_pixel, seed, top_at_1=atm.top_at_1, independent_column=independent_column, cloud=cld,
+                                  band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase, background=background)
     phase = _raytracer_phase("raytrace_sw", atm, cloud_lut, phase_table)
     return be.raytracer_sw(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, np.zeros_like(inc_dir), kn_grid,
                            photons_per_pixel, seed, top_at_1=atm.top_at_1, independent_column=independent_column, cloud=cld,
@@ -203,24 +216,65 @@ def raytrace_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, photons_per_pixel, 
 
 
 def render_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, camera, rays_per_pixel, seed, cloud_lut=None, kn_grid=None,
-              sfc_albedo=None, max_events=None, phase_table=None):
+              sfc_albedo=None, max_events=None, phase_table=None, n_domain=None, z_lev=None):
     """Shortwave radiances for a virtual camera or a flux sensor from the backward Monte Carlo ray tracer (rrx_raytracer_bw, DESIGN
     4.15): the twin of raytrace_sw, on the same domain, sun, optics and albedo, with the same checks. camera: camera.perspective /
     fisheye / orthographic / flux_sensor. Returns radiance (npy, npx) in W m-2 sr-1 (scattered and reflected sunlight; the sun's
-    disk is not imaged), n_capped and n_clamped. phase_table: as in raytrace_sw."""
+    disk is not imaged), n_capped and n_clamped. phase_table, n_domain, z_lev: as in raytrace_sw; with a background the camera may
+    sit inside it, and the orthographic and the downward flux sensor start at clamp(position.z, domain top, TOA)."""
+    if n_domain is not None and kn_grid is None:
+        kn_grid = (nx, ny, int(n_domain))
     tau, ssa, cld, sfc_albedo, mu0, inc_dir, kn_grid = _raytracer_inputs("render_sw", be, kd_sw, atm, nx, ny, cloud_lut, kn_grid, sfc_albedo)
+    if n_domain is not None:
+        tau, ssa, cld, rel, background = _raytracer_split("render_sw", be, atm, tau, ssa, cld, n_domain, z_lev)
+        phase = _raytracer_phase("render_sw", atm, cloud_lut, phase_table, rel)
+        return be.raytracer_bw_bg(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
+                                  top_at_1=atm.top_at_1, cloud=cld, band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase,
+                                  background=background)
     phase = _raytracer_phase("render_sw", atm, cloud_lut, phase_table)
     return be.raytracer_bw(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
                            top_at_1=atm.top_at_1, cloud=cld, band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase)
 
 
-def _raytracer_phase(who, atm, cloud_lut, phase_table):
-    """The table with the cells' radius: the liquid effective radius atm.rel (nlay, ncol), as in the reference."""
+def _raytracer_phase(who, atm, cloud_lut, phase_table, rel=None):
+    """The table with the cells' radius: the liquid effective radius atm.rel (nlay, ncol), as in the reference (rel: that of the
+    grid's layers when the atmosphere is split into a grid and a background)."""
     if phase_table is None:
         return None
     if cloud_lut is None:
         raise ValueError(f"{who}: a phase table needs cloud_lut (the table replaces the phase function of the cloud optics)")
-    return phase_table.with_radius(atm.rel)
+    return phase_table.with_radius(atm.rel if rel is None else rel)
+
+
+class Background:
+    """The background atmosphere of the ray tracers, counted upward from the domain top: dz (nbg,) on the host, tau, ssa (ngpt, nbg)
+    and cloud, None or (tau, ssa, g) of (nbnd, nbg) each, on the device."""
+    def __init__(self, dz, tau, ssa, cloud=None):
+        self.dz, self.tau, self.ssa, self.cloud = dz, tau, ssa, cloud
+
+
+def _raytracer_split(who, be, atm, tau, ssa, cld, n_domain, z_lev):
+    """The lowest n_domain layers as the grid's arrays (in the atmosphere's layer order) and the layers above as a Background from
+    column 0; also the grid's part of atm.rel."""
+    nlay, n_domain = atm.nlay, int(n_domain)
+    if not 1 <= n_domain < nlay:
+        raise ValueError(f"{who}: n_domain must be in [1, nlay = {nlay})")
+    if z_lev is None:
+        raise ValueError(f"{who}: n_domain needs z_lev (nlay+1,), the heights of the levels")
+    z_lev = np.asarray(z_lev, dtype=np.float64).reshape(-1)
+    if z_lev.size != nlay + 1:
+        raise ValueError(f"{who}: z_lev is (nlay+1,) = ({nlay + 1},), got {z_lev.size}")
+    # array layers of the grid, and of the background counted upward from the domain top
+    grid = slice(nlay - n_domain, nlay) if atm.top_at_1 else slice(0, n_domain)
+    above = list(range(nlay - n_domain - 1, -1, -1)) if atm.top_at_1 else list(range(n_domain, nlay))
+    dz_bg = np.abs(z_lev[1:] - z_lev[:-1])[above].astype(be.np_dtype)
+    if not np.all(dz_bg > 0):
+        raise ValueError(f"{who}: z_lev must be strictly monotonic")
+    column0 = lambda t: t[:, above, 0].contiguous()
+    background = Background(dz_bg, column0(tau), column0(ssa), None if cld is None else tuple(column0(c) for c in cld))
+    part = lambda t: t[:, grid, :].contiguous()
+    rel = atm.rel[grid, :].contiguous() if getattr(atm, "rel", None) is not None else None
+    return part(tau), part(ssa), None if cld is None else tuple(part(c) for c in cld), rel, background
 
 
 def _raytracer_inputs(who, be, kd_sw, atm, nx, ny, cloud_lut, kn_grid, sfc_albedo):
