@@ -62,7 +62,19 @@ class Raytracer_gpu
                 Array_gpu<Float,1>& toa_up, Array_gpu<Float,1>& tod_dn_dir, Array_gpu<Float,1>& tod_dn_dif,
                 Array_gpu<Float,1>& bg_abs_dir, Array_gpu<Float,1>& bg_abs_dif);
 
+        // Aerosol as a third scattering species (rrx_raytracer_sw_aer): the grid's band triple aer_* (ncol, nz, nbnd) and
+        // the background's bg_aer_* (nbg, nbnd); either triple may be three arrays of size 0. The arrays are copied. A background
+        // aerosol needs a background (set_background first): without one it throws. With aerosol set both forms of trace_rays go
+        // through rrx_raytracer_sw_aer; aerosol scatters by Henyey-Greenstein with its own g, with a phase table too.
+        void set_aerosol(const Array_gpu<Float,3>& aer_tau, const Array_gpu<Float,3>& aer_ssa, const Array_gpu<Float,3>& aer_g,
+                         const Array_gpu<Float,2>& bg_aer_tau, const Array_gpu<Float,2>& bg_aer_ssa, const Array_gpu<Float,2>& bg_aer_g);
+        void clear_aerosol() { has_aer = false; aer_tau = Array_gpu<Float,3>(); aer_ssa = Array_gpu<Float,3>(); aer_g = Array_gpu<Float,3>();
+                               bg_aer_tau = Array_gpu<Float,2>(); bg_aer_ssa = Array_gpu<Float,2>(); bg_aer_g = Array_gpu<Float,2>(); }
+
     private:
+        bool has_aer = false;
+        Array_gpu<Float,3> aer_tau, aer_ssa, aer_g;
+        Array_gpu<Float,2> bg_aer_tau, bg_aer_ssa, bg_aer_g;
         bool has_bg = false;
         Array<Float,1> dz_bg;
         Array_gpu<Float,2> bg_tau, bg_ssa, bg_cld_tau, bg_cld_ssa, bg_cld_g;

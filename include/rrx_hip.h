@@ -796,7 +796,67 @@ int rrx_raytracer_bw_bg##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool
         int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
         F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
         int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
-        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, void* stream);
+        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, void* stream); \
+/* ---- Aerosol as a third scattering species of both ray tracers (csrc/rrx_rt_common.h). Opt-in: a band triple \
+   aer_tau, aer_ssa, aer_g (ncol, nz, nbnd) in the grid, the layout of the cloud triple, and bg_aer_tau, bg_aer_ssa, bg_aer_g \
+   (nbg, nbnd) in the background, the layout of the background's cloud triple. Each triple is all NULL or all given and needs \
+   band_lims_gpt and nbnd >= 1; a g-point that lies in no band has no aerosol. Per cell, with the parentheses as written: \
+   k_ext = ((tau + tau_c) + tau_a)/dz, k_sca = ((tau ssa + tau_c ssa_c) + tau_a ssa_a)/dz, k_sca_cld = (tau_c ssa_c)/dz, \
+   k_sca_aer = (tau_a ssa_a)/dz (dz_bg[b] in a background layer); tau_a = 0 gives the bits of the medium without aerosol. The \
+   species draw stays one uniform u: cloud iff u k_sca < k_sca_cld, otherwise aerosol iff u k_sca < k_sca_cld + k_sca_aer, \
+   otherwise gas. Aerosol scatters by Henyey-Greenstein with min(g_a, 1 - eps), in the grid and in the background, with a phase \
+   table too (the table stays the cloud's), and the backward deposit uses the same density. No new tallies: abs_* and bg_abs_* \
+   include what aerosol absorbs. Each entry is its _bg (or plain) counterpart with the aerosol arguments in front of the stream. \
+   rrx_rt_k_null_aer: the block maximum of the k_ext above. \
+   rrx_rt_bg_profile_aer: bg_profile (7, nbg+1): the five rows of rrx_rt_bg_profile in its order by the formulas above (tau_above \
+   sums (tau + tau_c) + tau_a in index order), then k_sca_aer and g_aer = min(g_a, 1 - eps); slot nbg of the two new rows is 0. \
+   rrx_rt_trace_counts_aer, rrx_rt_bw_trace_counts_aer: the grid's triple; with nbg > 0 bg_profile is the 7-row profile. \
+   rrx_raytracer_sw_aer, rrx_raytracer_bw_aer: the spectral loops with both triples; the same bits as the loops made by hand from \
+   the entries above. rrx_raytracer_sw_aer alone takes each triple as ONE argument, a HOST array of its three device pointers in \
+   the order tau, ssa, g: aer = {aer_tau, aer_ssa, aer_g}, bg_aer = {bg_aer_tau, bg_aer_ssa, bg_aer_g}; a NULL array is a triple of \
+   NULLs. (With six pointers it would have 61 parameters; the longest entry of this header has 58, and the binding's signature \
+   test pins that.) With nbg = 0 the background's aerosol arguments are not read. With every aerosol pointer NULL the loops are \
+   the _bg entries and every entry gives the integers of its _bg (or plain) counterpart. Refused before any HIP call: a \
+   partly-NULL aerosol triple, an aerosol triple without band_lims_gpt or with nbnd < 1, and what the counterpart refuses. */ \
+int rrx_rt_k_null_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, const F* tau, const int* band_lims_gpt, \
+        const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, const F* aer_tau, void* stream); \
+int rrx_rt_bg_profile_aer##SFX(int nbg, int ngpt, int nbnd, int igpt, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const int* band_lims_gpt, \
+        const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* bg_profile, \
+        const F* bg_aer_tau, const F* bg_aer_ssa, const F* bg_aer_g, void* stream); \
+int rrx_rt_trace_counts_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, F inc_dir, F inc_dif, int knx, int kny, int knz, const F* k_null, \
+        unsigned long long seed, long long photon0, long long nphotons, int max_events, \
+        unsigned long long* sfc_dn_dir, unsigned long long* sfc_dn_dif, unsigned long long* sfc_up, unsigned long long* tod_up, \
+        unsigned long long* abs_dir, unsigned long long* abs_dif, unsigned long long* n_capped, \
+        unsigned long long* toa_up, unsigned long long* tod_dn_dir, unsigned long long* tod_dn_dif, \
+        unsigned long long* bg_abs_dir, unsigned long long* bg_abs_dif, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_profile, const F* aer_tau, const F* aer_ssa, const F* aer_g, void* stream); \
+int rrx_raytracer_sw_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
+        long long photons_per_pixel, unsigned long long seed, int max_events, \
+        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, \
+        F* toa_up, F* tod_dn_dir, F* tod_dn_dif, F* bg_abs_dir, F* bg_abs_dif, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, \
+        const F* const* aer, const F* const* bg_aer, void* stream); \
+int rrx_rt_bw_trace_counts_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
+        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_profile, const F* aer_tau, const F* aer_ssa, const F* aer_g, void* stream); \
+int rrx_raytracer_bw_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
+        F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, \
+        const F* aer_tau, const F* aer_ssa, const F* aer_g, const F* bg_aer_tau, const F* bg_aer_ssa, const F* bg_aer_g, void* stream);
 
 RRX_DECLARE(double, _f64)
 RRX_DECLARE(float, _f32)

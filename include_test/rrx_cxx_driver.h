@@ -96,6 +96,25 @@ int   rrx_cxx_trace_rays_bw_bg(int nx, int ny, int nz, int ngpt, int nbnd, Real 
                             int nmu, int nre, Real re0, Real dre, const Real* mu, const Real* phase, const Real* cdf, const Real* cld_re,
                             int nbg, const Real* dz_bg, const Real* bg_tau, const Real* bg_ssa, const Real* bg_cld_tau, const Real* bg_cld_ssa,
                             const Real* bg_cld_g, void* stream);
+/* the same after set_aerosol: aer_* (ncol, nz, nbnd) and bg_aer_* (nbg, nbnd) on the device, each triple all NULL or all given;
+ * set_aerosol is called when any of the six is given, after set_background; a background aerosol with nbg = 0 is refused by the class. */
+int   rrx_cxx_trace_rays_aer(int nx, int ny, int nz, int ngpt, int nbnd, Real dx, Real dy, Real dz, int top_at_1, int independent_column,
+                         const Real* tau, const Real* ssa, const int* band_lims_gpt, const Real* cld_tau, const Real* cld_ssa, const Real* cld_g,
+                         const Real* sfc_albedo, Real mu0, Real azimuth, const Real* inc_dir, const Real* inc_dif, int knx, int kny, int knz,
+                         long long photons_per_pixel, unsigned long long seed, int max_events, Real* const* out6, unsigned long long* n_capped,
+                         Real* const* out5, int nmu, int nre, Real re0, Real dre, const Real* mu, const Real* phase, const Real* cdf,
+                         const Real* cld_re, int nbg, const Real* dz_bg, const Real* bg_tau, const Real* bg_ssa, const Real* bg_cld_tau,
+                         const Real* bg_cld_ssa, const Real* bg_cld_g, const Real* aer_tau, const Real* aer_ssa, const Real* aer_g,
+                         const Real* bg_aer_tau, const Real* bg_aer_ssa, const Real* bg_aer_g, void* stream);
+int   rrx_cxx_trace_rays_bw_aer(int nx, int ny, int nz, int ngpt, int nbnd, Real dx, Real dy, Real dz, int top_at_1,
+                            const Real* tau, const Real* ssa, const int* band_lims_gpt, const Real* cld_tau, const Real* cld_ssa, const Real* cld_g,
+                            const Real* sfc_albedo, Real mu0, Real azimuth, const Real* inc_dir, int knx, int kny, int knz,
+                            int sensor_type, int npx, int npy, Real fov, const Real* sensor, long long rays_per_pixel, unsigned long long seed,
+                            int max_events, Real* radiance, unsigned long long* n_capped, unsigned long long* n_clamped,
+                            int nmu, int nre, Real re0, Real dre, const Real* mu, const Real* phase, const Real* cdf, const Real* cld_re,
+                            int nbg, const Real* dz_bg, const Real* bg_tau, const Real* bg_ssa, const Real* bg_cld_tau, const Real* bg_cld_ssa,
+                            const Real* bg_cld_g, const Real* aer_tau, const Real* aer_ssa, const Real* aer_g,
+                            const Real* bg_aer_tau, const Real* bg_aer_ssa, const Real* bg_aer_g, void* stream);
 /* one LW + one SW solve_gpu (fluxes only) enqueued on `stream`; DEVICE arrays: (ncol,nlay) / (ncol,nlay+1) fields, (ncol) vectors,
    surface properties (nbnd,ncol); lwp, iwp, rel, dei NULL without clouds; out7: seven (ncol, nlay+1) arrays for LW up, dn, net and
    SW up, dn, dn_dir, net, or NULL (the driver then keeps them: rrx_cxx_driver_fluxes) */

@@ -48,6 +48,14 @@
 // The spectral loop scales toa_up, tod_dn_dir, tod_dn_dif like the other fluxes and bg_abs_* [b] by (scale/dz_bg[b])/F(ncol): W m-3 of
 // a layer that spans the whole domain.
 //
+// WITH AEROSOL (trace_kernel<F,TABLE,true,true>, the rrx_*_aer entries; rrx_rt_common.h; tests/raytracer_aer_ref.py restates
+// it): a third species with its own band triple in the grid and in the background. k_ext, k_sca and k_null take tau_a as
+// rrx_rt_common.h writes them, abs_* and bg_abs_* take what aerosol absorbs through f_no_abs, and the draw count and DRAW ORDER are
+// unchanged: the species uniform u picks cloud iff u k_sca < k_sca_cld, otherwise aerosol iff u k_sca < k_sca_cld + k_sca_aer,
+// otherwise gas; aerosol scatters by Henyey-Greenstein with min(g_a, 1 - eps), in the grid and aloft, with a phase table too.
+// DEPARTURE: the reference draws aerosol, cloud, gas in that order; cloud comes first here so that a scene without aerosol draws
+// exactly what it draws without this form.
+//
 // Shape: one photon per lane at a time; a lane whose photon ends takes the next one of its list in the same loop, so the lanes
 // of a wave stay busy until the lists run out (the grid is capped and the photons dealt round-robin over the threads).
 #include "rrx_rt_phase.h"
@@ -57,6 +65,35 @@ namespace
 {
 using namespace rrx;
 using namespace rrx::rt;
+
+// k_null_kernel with aerosol: the maximum of ((tau + tau_c) + tau_a)/dz
+template<typename F>
+__global__ void __launch_bounds__(256) k_null_aer_kernel(
+        const int nx, const int ny, const int nz, const int nbnd, const int igpt, const int top_at_1,
+        const F* __restrict__ tau, const int* __restrict__ band_lims_gpt, const F* __restrict__ cld_tau, const F* __restrict__ aer_tau,
+        const F dz, const int knx, const int kny, const int knz, F* __restrict__ k_null)
+{
+    const int n = blockIdx.x*blockDim.x + threadIdx.x;
+    if (n >= knx*kny*knz) return;
+    const int in = n % knx, jn = (n / knx) % kny, kn = n / (knx*kny);
+    const int rx = nx/knx, ry = ny/kny, rz = nz/knz;
+    const size_t ncol = size_t(nx)*ny;
+    const int ibnd = (cld_tau != nullptr || aer_tau != nullptr) ? band_of(igpt, nbnd, band_lims_gpt) : -1;
+    F m = F(0.);
+    for (int k=kn*rz; k<(kn+1)*rz; ++k)
+    {
+        const int lay = top_at_1 ? nz-1-k : k;
+        for (int j=jn*ry; j<(jn+1)*ry; ++j)
+            for (int i=in*rx; i<(in+1)*rx; ++i)
+            {
+                const size_t cell = size_t(i) + size_t(j)*nx + ncol*lay;
+                const F tc = (ibnd >= 0 && cld_tau != nullptr) ? cld_tau[cell + ncol*nz*ibnd] : F(0.);
+                const F ta = (ibnd >= 0 && aer_tau != nullptr) ? aer_tau[cell + ncol*nz*ibnd] : F(0.);
+                m = max(m, k_ext_of(tau[cell + ncol*nz*igpt], tc, ta, dz));
+            }
+    }
+    k_null[n] = m;
+}
 
 // k_null(in, jn, kn) = the maximum of k_ext over the block's cells, for one g-point
 template<typename F>
@@ -111,17 +148,21 @@ struct TraceArgs
 // without a background: the integers of the other instantiations.
 template<typename F>
 struct BgTallies { u64* toa_up; u64* tod_dn_dir; u64* tod_dn_dif; u64* bg_abs_dir; u64* bg_abs_dif; };
-template<typename F, bool BG> struct FwBg {};
-template<typename F> struct FwBg<F,true> { BgIn<F> in; BgTallies<F> t; };
+template<typename F, bool BG, bool AER = false> struct FwBg {};
+template<typename F> struct FwBg<F,true,false> { BgIn<F> in; BgTallies<F> t; };
+template<typename F> struct FwBg<F,true,true> { BgIn<F> in; BgTallies<F> t; AerIn<F> aer; };
 
-template<typename F, bool TABLE, bool BG>
-__global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, const PhaseArgs<F,TABLE> ph, const FwBg<F,BG> bgin)
+// AER: aerosol as a third species (rrx_rt_common.h), built on top of the BG form only, which handles nbg = 0: the grid's
+// triple in bgin.aer (NULL: none in the grid), the background's in rows BG_K_SCA_AER and BG_G_AER of the 7-row profile.
+template<typename F, bool TABLE, bool BG, bool AER>
+__global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, const PhaseArgs<F,TABLE> ph, const FwBg<F,BG,AER> bgin)
 {
+    static_assert(BG || !AER, "the aerosol form is built on the background form");
     [[maybe_unused]] BgView<F> bg{};
     if constexpr (BG)
     {
         extern __shared__ double bg_lds[];
-        bg = stage_background(bgin.in, reinterpret_cast<F*>(bg_lds));
+        bg = stage_background<F, AER ? BG_ROWS_AER : BG_ROWS>(bgin.in, reinterpret_cast<F*>(bg_lds));
     }
     const long long nthreads = (long long)gridDim.x*blockDim.x;
     long long next_photon = (long long)blockIdx.x*blockDim.x + threadIdx.x;
@@ -137,6 +178,8 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
     const F* __restrict__ ssa_g = a.ssa + ncol*nz*a.igpt;
     const F inf = F(INFINITY);
     [[maybe_unused]] const F g_max = F(1.) - Lim<F>::eps();
+    [[maybe_unused]] int ibnd_a = -1;
+    if constexpr (AER) ibnd_a = bgin.aer.tau != nullptr ? band_of(a.igpt, a.nbnd, a.band_lims_gpt) : -1;
 
     Stream rng; rng.k0 = a.k0; rng.k1 = a.k1; rng.used = 4; rng.block = 0u; rng.c0 = rng.c1 = rng.c2 = 0u;
     bool alive = false, pending = false;
@@ -271,7 +314,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
             // the cell and its k_ext, k_sca, k_sca_cld: a cell of the grid, or the photon's background layer
             size_t cell = 0;
             F k_ext = F(0.), k_sca = F(0.), k_sca_cld = F(0.);
-            [[maybe_unused]] F gc = F(0.);
+            [[maybe_unused]] F gc = F(0.), k_sca_aer = F(0.), ga = F(0.);
             u64* abs_to = kind == 0 ? a.abs_dir : a.abs_dif;
             if (in_bg)
             {
@@ -279,6 +322,10 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
                 {
                     cell = size_t(kn - a.knz);
                     k_ext = kn_val; k_sca = bg.k_sca[cell]; k_sca_cld = bg.k_sca_cld[cell]; gc = bg.g[cell];
+                    if constexpr (AER)
+                    {
+                        k_sca_aer = bg.k_ext[BG_K_SCA_AER*(bg.nbg + 1) + cell]; ga = bg.k_ext[BG_G_AER*(bg.nbg + 1) + cell];
+                    }
                     abs_to = kind == 0 ? bgin.t.bg_abs_dir : bgin.t.bg_abs_dif;
                 }
             }
@@ -295,8 +342,23 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
                     tc = a.cld_tau[cb]; wc = a.cld_ssa[cb];
                     if constexpr (!TABLE) gc = a.cld_g[cb];
                 }
-                k_ext = k_ext_of(t, tc, a.dz);
-                k_sca = (t*w0 + tc*wc) / a.dz;
+                if constexpr (AER)
+                {
+                    F ta = F(0.), wa = F(0.);
+                    if (ibnd_a >= 0)
+                    {
+                        const size_t cb = cell + ncol*nz*ibnd_a;
+                        ta = bgin.aer.tau[cb]; wa = bgin.aer.ssa[cb]; ga = bgin.aer.g[cb];
+                    }
+                    k_ext = k_ext_of(t, tc, ta, a.dz);
+                    k_sca = k_sca_of(t, w0, tc, wc, ta, wa, a.dz);
+                    k_sca_aer = (ta*wa) / a.dz;
+                }
+                else
+                {
+                    k_ext = k_ext_of(t, tc, a.dz);
+                    k_sca = (t*w0 + tc*wc) / a.dz;
+                }
                 k_sca_cld = (tc*wc) / a.dz;
             }
             const F f_no_abs = clampf(F(1.) - (k_ext - k_sca)/kn_val, F(0.), F(1.));
@@ -306,8 +368,12 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
             if (!(weight > F(0.))) { alive = false; continue; }
             if (rng.next<F>()*(k_sca + (kn_val - k_ext)) < k_sca)
             {
-                const bool cloud = rng.next<F>()*k_sca < k_sca_cld;
-                if constexpr (TABLE)
+                const F us = rng.next<F>()*k_sca;
+                const bool cloud = us < k_sca_cld;
+                [[maybe_unused]] bool aerosol = false;
+                if constexpr (AER) aerosol = !cloud && us < k_sca_cld + k_sca_aer;
+                if (aerosol) scatter_direction(rng, true, ga, g_max, ux, uy, uz);          // Henyey-Greenstein, with a phase table too
+                else if constexpr (TABLE)
                 {
                     if (in_bg) scatter_direction(rng, cloud, gc, g_max, ux, uy, uz);          // the table applies inside the grid only
                     else
@@ -334,30 +400,42 @@ __global__ void counts_to_flux_kernel(const size_t n, const u64* __restrict__ co
 
 template<typename F>
 void launch_k_null(int nx, int ny, int nz, int nbnd, int igpt, int top_at_1, const F* tau, const int* band_lims_gpt,
-                   const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, hipStream_t st)
+                   const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, hipStream_t st, const F* aer_tau = nullptr)
 {
     const int n = knx*kny*knz;
-    k_null_kernel<F><<<ceil_div(n, 256), 256, 0, st>>>(nx, ny, nz, nbnd, igpt, top_at_1, tau, band_lims_gpt, cld_tau, dz,
-                                                       knx, kny, knz, k_null);
+    if (aer_tau != nullptr)
+        k_null_aer_kernel<F><<<ceil_div(n, 256), 256, 0, st>>>(nx, ny, nz, nbnd, igpt, top_at_1, tau, band_lims_gpt, cld_tau, aer_tau, dz,
+                                                               knx, kny, knz, k_null);
+    else
+        k_null_kernel<F><<<ceil_div(n, 256), 256, 0, st>>>(nx, ny, nz, nbnd, igpt, top_at_1, tau, band_lims_gpt, cld_tau, dz,
+                                                           knx, kny, knz, k_null);
 }
 
 template<typename F>
 void launch_trace(TraceArgs<F> a, const PhaseIn<F>& ph, const F mu0, const F azimuth, const F inc_dir, const F inc_dif, const u64 seed,
-                  hipStream_t st, const FwBg<F,true>* bg = nullptr)
+                  hipStream_t st, const FwBg<F,true>* bg = nullptr, const AerIn<F>* aer = nullptr)
 {
     const double st_ = std::sqrt(std::max(0.0, 1.0 - double(mu0)*double(mu0)));
     a.sun_x = F(st_*std::cos(double(azimuth))); a.sun_y = F(st_*std::sin(double(azimuth))); a.sun_z = -mu0;
     a.dif_frac = inc_dif / (inc_dir + inc_dif);
     a.k0 = unsigned(seed & 0xFFFFFFFFull); a.k1 = unsigned(seed >> 32);
     const int blocks = int(std::min<long long>((a.nphotons + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
-    if (bg != nullptr)
+    if (bg != nullptr && aer != nullptr)
+    {
+        // the aerosol form: the background's profile has BG_ROWS_AER rows
+        const size_t lds = bg_lds_numbers(bg->in.nbg, BG_ROWS_AER)*sizeof(F);
+        const FwBg<F,true,true> ba{bg->in, bg->t, *aer};
+        if (ph.given()) trace_kernel<F,true,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, ba);
+        else trace_kernel<F,false,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, ba);
+    }
+    else if (bg != nullptr)
     {
         const size_t lds = bg_lds_numbers(bg->in.nbg)*sizeof(F);
-        if (ph.given()) trace_kernel<F,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, *bg);
-        else trace_kernel<F,false,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, *bg);
+        if (ph.given()) trace_kernel<F,true,true,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, *bg);
+        else trace_kernel<F,false,true,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, *bg);
     }
-    else if (ph.given()) trace_kernel<F,true,false><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,true>{ph}, FwBg<F,false>{});
-    else trace_kernel<F,false,false><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,false>{}, FwBg<F,false>{});
+    else if (ph.given()) trace_kernel<F,true,false,false><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,true>{ph}, FwBg<F,false>{});
+    else trace_kernel<F,false,false,false><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,false>{}, FwBg<F,false>{});
 }
 
 // one number per background layer: out[b] += F(counts[b] 2^-32) scale[b]
@@ -369,10 +447,12 @@ __global__ void bg_counts_to_flux_kernel(const int nbg, const u64* __restrict__ 
 }
 
 // the profile of the background for one g-point (rrx_rt_common.h): one thread per layer
-template<typename F>
-__global__ void bg_profile_kernel(const int nbg, const int ngpt, const int nbnd, const int igpt, const BgLevels<F> dz_bg,
+// AER: the 7-row profile with the background's aerosol triple (rrx_rt_common.h); a NULL triple writes zeros into the two new rows
+template<typename F, bool AER>
+__device__ __forceinline__ void bg_profile_layer(const int nbg, const int nbnd, const int igpt, const BgLevels<F>& dz_bg,
         const F* __restrict__ bg_tau, const F* __restrict__ bg_ssa, const int* __restrict__ band_lims_gpt,
-        const F* __restrict__ bg_cld_tau, const F* __restrict__ bg_cld_ssa, const F* __restrict__ bg_cld_g, F* __restrict__ profile)
+        const F* __restrict__ bg_cld_tau, const F* __restrict__ bg_cld_ssa, const F* __restrict__ bg_cld_g,
+        const AerIn<F> aer, F* __restrict__ profile)
 {
     const int b = blockIdx.x*blockDim.x + threadIdx.x;
     if (b > nbg) return;
@@ -380,22 +460,64 @@ __global__ void bg_profile_kernel(const int nbg, const int ngpt, const int nbnd,
     const int ibnd = bg_cld_tau != nullptr ? band_of(igpt, nbnd, band_lims_gpt) : -1;
     const F* __restrict__ tau_g = bg_tau + size_t(nbg)*igpt;
     const F* __restrict__ ctau_b = ibnd >= 0 ? bg_cld_tau + size_t(nbg)*ibnd : nullptr;
+    [[maybe_unused]] int ibnd_a = -1;
+    [[maybe_unused]] const F* __restrict__ atau_b = nullptr;
+    if constexpr (AER)
+    {
+        ibnd_a = aer.tau != nullptr ? band_of(igpt, nbnd, band_lims_gpt) : -1;
+        atau_b = ibnd_a >= 0 ? aer.tau + size_t(nbg)*ibnd_a : nullptr;
+    }
     // the layers above b in index order; slot nbg: all of them
     F above = F(0.);
-    for (int l = (b == nbg ? 0 : b + 1); l < nbg; ++l) above = above + (tau_g[l] + (ctau_b != nullptr ? ctau_b[l] : F(0.)));
+    for (int l = (b == nbg ? 0 : b + 1); l < nbg; ++l)
+    {
+        if constexpr (AER) above = above + ((tau_g[l] + (ctau_b != nullptr ? ctau_b[l] : F(0.))) + (atau_b != nullptr ? atau_b[l] : F(0.)));
+        else above = above + (tau_g[l] + (ctau_b != nullptr ? ctau_b[l] : F(0.)));
+    }
     profile[BG_TAU_ABOVE*n1 + b] = above;
     F k_ext = F(0.), k_sca = F(0.), k_sca_cld = F(0.), g = F(0.);
+    [[maybe_unused]] F k_sca_aer = F(0.), g_aer = F(0.);
     if (b < nbg)
     {
         const F t = tau_g[b], w0 = bg_ssa[size_t(nbg)*igpt + b], dz = dz_bg.v[b];
         F tc = F(0.), wc = F(0.), gc = F(0.);
         if (ibnd >= 0) { tc = ctau_b[b]; wc = bg_cld_ssa[size_t(nbg)*ibnd + b]; gc = bg_cld_g[size_t(nbg)*ibnd + b]; }
-        k_ext = k_ext_of(t, tc, dz);
-        k_sca = (t*w0 + tc*wc) / dz;
+        if constexpr (AER)
+        {
+            F ta = F(0.), wa = F(0.), ga = F(0.);
+            if (ibnd_a >= 0) { ta = atau_b[b]; wa = aer.ssa[size_t(nbg)*ibnd_a + b]; ga = aer.g[size_t(nbg)*ibnd_a + b]; }
+            k_ext = k_ext_of(t, tc, ta, dz);
+            k_sca = k_sca_of(t, w0, tc, wc, ta, wa, dz);
+            k_sca_aer = (ta*wa) / dz;
+            g_aer = min(ga, F(1.) - Lim<F>::eps());
+        }
+        else
+        {
+            k_ext = k_ext_of(t, tc, dz);
+            k_sca = (t*w0 + tc*wc) / dz;
+        }
         k_sca_cld = (tc*wc) / dz;
         g = min(gc, F(1.) - Lim<F>::eps());
     }
     profile[BG_K_EXT*n1 + b] = k_ext; profile[BG_K_SCA*n1 + b] = k_sca; profile[BG_K_SCA_CLD*n1 + b] = k_sca_cld; profile[BG_G*n1 + b] = g;
+    if constexpr (AER) { profile[BG_K_SCA_AER*n1 + b] = k_sca_aer; profile[BG_G_AER*n1 + b] = g_aer; }
+}
+
+template<typename F>
+__global__ void bg_profile_kernel(const int nbg, const int ngpt, const int nbnd, const int igpt, const BgLevels<F> dz_bg,
+        const F* __restrict__ bg_tau, const F* __restrict__ bg_ssa, const int* __restrict__ band_lims_gpt,
+        const F* __restrict__ bg_cld_tau, const F* __restrict__ bg_cld_ssa, const F* __restrict__ bg_cld_g, F* __restrict__ profile)
+{
+    bg_profile_layer<F,false>(nbg, nbnd, igpt, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, AerIn<F>{}, profile);
+}
+
+template<typename F>
+__global__ void bg_profile_aer_kernel(const int nbg, const int ngpt, const int nbnd, const int igpt, const BgLevels<F> dz_bg,
+        const F* __restrict__ bg_tau, const F* __restrict__ bg_ssa, const int* __restrict__ band_lims_gpt,
+        const F* __restrict__ bg_cld_tau, const F* __restrict__ bg_cld_ssa, const F* __restrict__ bg_cld_g, const AerIn<F> aer,
+        F* __restrict__ profile)
+{
+    bg_profile_layer<F,true>(nbg, nbnd, igpt, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, aer, profile);
 }
 
 template<typename F>
@@ -408,26 +530,34 @@ BgLevels<F> bg_thicknesses(const int nbg, const F* dz_bg)
 
 template<typename F>
 void launch_bg_profile(int nbg, int ngpt, int nbnd, int igpt, const BgLevels<F>& dz_bg, const F* bg_tau, const F* bg_ssa,
-                       const int* band_lims_gpt, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* profile, hipStream_t st)
+                       const int* band_lims_gpt, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* profile, hipStream_t st,
+                       const AerIn<F>* aer = nullptr)
 {
-    bg_profile_kernel<F><<<ceil_div(nbg + 1, 64), 64, 0, st>>>(nbg, ngpt, nbnd, igpt, dz_bg, bg_tau, bg_ssa, band_lims_gpt,
-                                                              bg_cld_tau, bg_cld_ssa, bg_cld_g, profile);
+    if (aer != nullptr)
+        bg_profile_aer_kernel<F><<<ceil_div(nbg + 1, 64), 64, 0, st>>>(nbg, ngpt, nbnd, igpt, dz_bg, bg_tau, bg_ssa, band_lims_gpt,
+                                                                      bg_cld_tau, bg_cld_ssa, bg_cld_g, *aer, profile);
+    else
+        bg_profile_kernel<F><<<ceil_div(nbg + 1, 64), 64, 0, st>>>(nbg, ngpt, nbnd, igpt, dz_bg, bg_tau, bg_ssa, band_lims_gpt,
+                                                                  bg_cld_tau, bg_cld_ssa, bg_cld_g, profile);
 }
 
 template<typename F>
 int bg_profile_entry(const char* entry, int nbg, int ngpt, int nbnd, int igpt, const F* dz_bg, const F* bg_tau, const F* bg_ssa,
-                     const int* band_lims_gpt, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* profile, void* stream)
+                     const int* band_lims_gpt, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* profile, void* stream,
+                     const AerIn<F>* aer = nullptr)
 {
+    // aer: the 7-row profile of rrx_rt_bg_profile_aer (its triple may be NULL)
     RRX_TRY
     check_nbg(nbg);
     if (check_extents({{"nbg", nbg}, {"ngpt", ngpt}})) return 0;
     if (nbnd < 0) throw std::runtime_error("nbnd is negative");
     if (igpt < 0 || igpt >= ngpt) throw std::runtime_error("igpt is outside [0, ngpt)");
     check_bg_medium(nbg, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g);
+    if (aer != nullptr) check_aerosol("bg_aer_", nbnd, band_lims_gpt, aer->tau, aer->ssa, aer->g);
     check_needed({{"bg_profile", profile}});
     bg_levels<F>(nbg, dz_bg, 1, 1, F(1.));          // (the thicknesses are > 0)
     launch_bg_profile<F>(nbg, ngpt, nbnd, igpt, bg_thicknesses(nbg, dz_bg), bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa,
-                         bg_cld_g, profile, static_cast<hipStream_t>(stream));
+                         bg_cld_g, profile, static_cast<hipStream_t>(stream), aer);
     RRX_CATCH(entry)
 }
 
@@ -439,18 +569,21 @@ void launch_counts_to_flux(const size_t n, const u64* counts, const F scale, F* 
 
 template<typename F>
 int k_null_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, const F* tau,
-                 const int* band_lims_gpt, const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, void* stream)
+                 const int* band_lims_gpt, const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, void* stream,
+                 const F* aer_tau = nullptr)
 {
     RRX_TRY
     if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}})) return 0;
     if (nbnd < 0) throw std::runtime_error("nbnd is negative");
     check_needed({{"tau", tau}, {"k_null", k_null}});
     if (cld_tau != nullptr && band_lims_gpt == nullptr) throw std::runtime_error("band_lims_gpt is NULL");
+    if (aer_tau != nullptr && band_lims_gpt == nullptr) throw std::runtime_error("band_lims_gpt is NULL");
+    if (aer_tau != nullptr && nbnd < 1) throw std::runtime_error("nbnd must be >= 1 with an aerosol triple");
     if (igpt < 0 || igpt >= ngpt) throw std::runtime_error("igpt is outside [0, ngpt)");
     if (!(dz > F(0.))) throw std::runtime_error("dz must be > 0");
     check_grid(nx, ny, nz, knx, kny, knz);
     launch_k_null<F>(nx, ny, nz, nbnd, igpt, top_at_1 ? 1 : 0, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null,
-                     static_cast<hipStream_t>(stream));
+                     static_cast<hipStream_t>(stream), aer_tau);
     RRX_CATCH(entry)
 }
 
@@ -461,8 +594,10 @@ int trace_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, i
                 int knx, int kny, int knz, const F* k_null, u64 seed, long long photon0, long long nphotons, int max_events,
                 u64* sfc_dn_dir, u64* sfc_dn_dif, u64* sfc_up, u64* tod_up, u64* abs_dir, u64* abs_dif, u64* n_capped, void* stream,
                 const PhaseIn<F> ph = PhaseIn<F>{}, const bool with_bg = false, const BgTallies<F> bt = BgTallies<F>{},
-                const int nbg = 0, const F* dz_bg = nullptr, const F* bg_profile = nullptr)
+                const int nbg = 0, const F* dz_bg = nullptr, const F* bg_profile = nullptr, const AerIn<F>* aer = nullptr)
 {
+    // aer: rrx_rt_trace_counts_aer. With nbg > 0 bg_profile then has BG_ROWS_AER rows and the aerosol form runs whatever the grid's
+    // triple is; with nbg = 0 and a NULL triple it is the _bg entry.
     RRX_TRY
     check_nbg(nbg);
     if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"nphotons", nphotons}})) return 0;
@@ -472,6 +607,7 @@ int trace_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, i
                   {"sfc_dn_dif", sfc_dn_dif}, {"sfc_up", sfc_up}, {"tod_up", tod_up}, {"abs_dir", abs_dir}, {"abs_dif", abs_dif},
                   {"n_capped", n_capped}});
     check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
+    if (aer != nullptr) check_aerosol("aer_", nbnd, band_lims_gpt, aer->tau, aer->ssa, aer->g);
     check_phase(ph, cld_tau);
     if (igpt < 0 || igpt >= ngpt) throw std::runtime_error("igpt is outside [0, ngpt)");
     check_scene(dx, dy, dz, mu0);
@@ -489,6 +625,11 @@ int trace_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, i
             check_needed({{"dz_bg", dz_bg}, {"bg_profile", bg_profile}, {"toa_up", bt.toa_up}, {"tod_dn_dir", bt.tod_dn_dir},
                           {"tod_dn_dif", bt.tod_dn_dif}, {"bg_abs_dir", bt.bg_abs_dir}, {"bg_abs_dif", bt.bg_abs_dif}});
             bg.in.z = bg_levels<F>(nbg, dz_bg, nz, knz, dz);
+        }
+        if (aer != nullptr && (aer->tau != nullptr || nbg > 0))
+        {
+            launch_trace<F>(a, ph, mu0, azimuth, inc_dir, inc_dif, seed, static_cast<hipStream_t>(stream), &bg, aer);
+            return 0;
         }
         launch_trace<F>(a, ph, mu0, azimuth, inc_dir, inc_dif, seed, static_cast<hipStream_t>(stream), &bg);
         return 0;
@@ -515,9 +656,11 @@ int raytracer_sw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
                        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, u64* n_capped, void* stream,
                        const PhaseIn<F> ph = PhaseIn<F>{}, const bool with_bg = false, F* const* bg_out = nullptr, const int nbg = 0,
                        const F* dz_bg = nullptr, const F* bg_tau = nullptr, const F* bg_ssa = nullptr, const F* bg_cld_tau = nullptr,
-                       const F* bg_cld_ssa = nullptr, const F* bg_cld_g = nullptr)
+                       const F* bg_cld_ssa = nullptr, const F* bg_cld_g = nullptr, const AerIn<F>* aer = nullptr,
+                       const AerIn<F>* bg_aer = nullptr)
 {
     // bg_out: toa_up, tod_dn_dir, tod_dn_dif (ncol), bg_abs_dir, bg_abs_dif (nbg)
+    // aer, bg_aer: rrx_raytracer_sw_aer; with both triples NULL (bg_aer is not read when nbg = 0) it is the _bg entry
     RRX_TRY
     check_nbg(nbg);
     if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"photons_per_pixel", photons_per_pixel}})) return 0;
@@ -526,6 +669,7 @@ int raytracer_sw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
                   {"sfc_dn_dir", sfc_dn_dir}, {"sfc_dn_dif", sfc_dn_dif}, {"sfc_up", sfc_up}, {"tod_up", tod_up}, {"abs_dir", abs_dir},
                   {"abs_dif", abs_dif}, {"n_capped", n_capped}});
     check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
+    if (aer != nullptr) check_aerosol("aer_", nbnd, band_lims_gpt, aer->tau, aer->ssa, aer->g);
     check_phase(ph, cld_tau);
     check_scene(dx, dy, dz, mu0);
     for (int g=0; g<ngpt; ++g)
@@ -534,6 +678,10 @@ int raytracer_sw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
     check_grid(nx, ny, nz, knx, kny, knz);
     const bool bg_on = with_bg && nbg > 0;
     BgLevels<F> lev{}, thick{};
+    if (bg_on && bg_aer != nullptr) check_aerosol("bg_aer_", nbnd, band_lims_gpt, bg_aer->tau, bg_aer->ssa, bg_aer->g);
+    // the aerosol form runs when either triple is given
+    const AerIn<F> aer_grid = aer != nullptr ? *aer : AerIn<F>{}, aer_bg = (bg_on && bg_aer != nullptr) ? *bg_aer : AerIn<F>{};
+    const bool aer_on = with_bg && (aer_grid.tau != nullptr || aer_bg.tau != nullptr);
     if (bg_on)
     {
         check_bg_medium(nbg, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g);
@@ -547,7 +695,7 @@ int raytracer_sw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
     const size_t ncol = size_t(nx)*ny, n_sfc = 4*ncol, n_abs = 2*ncol*nz;
     const size_t n_bgc = bg_on ? 3*ncol + 2*size_t(nbg) : 0, n_counts = n_sfc + n_abs + n_bgc;
     const size_t n_kn = (size_t(knx)*kny*knz*sizeof(F) + sizeof(u64) - 1) / sizeof(u64);
-    const size_t n_prof = bg_on ? (size_t(BG_ROWS)*(nbg + 1)*sizeof(F) + sizeof(u64) - 1) / sizeof(u64) : 0;
+    const size_t n_prof = bg_on ? (size_t(aer_on ? BG_ROWS_AER : BG_ROWS)*(nbg + 1)*sizeof(F) + sizeof(u64) - 1) / sizeof(u64) : 0;
     WorkspaceLease lease(st);
     u64* counts = lease.get<u64>(n_counts + n_kn + n_prof);
     F* k_null = reinterpret_cast<F*>(counts + n_counts);
@@ -566,7 +714,7 @@ int raytracer_sw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
     {
         if (!(inc_dir[g] + inc_dif[g] > F(0.))) continue;
         if (hipMemsetAsync(counts, 0, n_counts*sizeof(u64), st) != hipSuccess) throw std::runtime_error("zeroing the counts failed");
-        launch_k_null<F>(nx, ny, nz, nbnd, g, top_at_1 ? 1 : 0, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null, st);
+        launch_k_null<F>(nx, ny, nz, nbnd, g, top_at_1 ? 1 : 0, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null, st, aer_grid.tau);
         u64* c = counts;
         TraceArgs<F> a{nx, ny, nz, nbnd, g, top_at_1 ? 1 : 0, independent_column ? 1 : 0, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g,
                        dx, dy, dz, sfc_albedo, F(0.), F(0.), F(0.), F(0.), knx, kny, knz, k_null, 0u, 0u, 0ull, nphotons, max_events,
@@ -576,8 +724,9 @@ int raytracer_sw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
         {
             u64* cb = c + n_sfc + n_abs;
             FwBg<F,true> bg{BgIn<F>{bg_on ? nbg : 0, profile, lev}, BgTallies<F>{cb, cb + ncol, cb + 2*ncol, cb + 3*ncol, cb + 3*ncol + nbg}};
-            if (bg_on) launch_bg_profile<F>(nbg, ngpt, nbnd, g, thick, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, profile, st);
-            launch_trace<F>(a, ph, mu0, azimuth, inc_dir[g], inc_dif[g], seed, st, &bg);
+            if (bg_on) launch_bg_profile<F>(nbg, ngpt, nbnd, g, thick, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, profile, st,
+                                            aer_on ? &aer_bg : nullptr);
+            launch_trace<F>(a, ph, mu0, azimuth, inc_dir[g], inc_dif[g], seed, st, &bg, aer_on ? &aer_grid : nullptr);
             if (bg_on)
             {
                 launch_counts_to_flux<F>(ncol, bg.t.toa_up, scale, bg_out[0], st);
@@ -680,7 +829,51 @@ int rrx_raytracer_sw_bg##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool
                                cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, \
                                photons_per_pixel, seed, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
                                PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, true, bg_out, nbg, dz_bg, bg_tau, bg_ssa, \
-                               bg_cld_tau, bg_cld_ssa, bg_cld_g); }
+                               bg_cld_tau, bg_cld_ssa, bg_cld_g); } \
+int rrx_rt_k_null_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, const F* tau, const int* band_lims_gpt, \
+        const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, const F* aer_tau, void* stream) \
+{ return k_null_entry<F>("rrx_rt_k_null_aer" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null, \
+                         stream, aer_tau); } \
+int rrx_rt_bg_profile_aer##SFX(int nbg, int ngpt, int nbnd, int igpt, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const int* band_lims_gpt, \
+        const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* bg_profile, \
+        const F* bg_aer_tau, const F* bg_aer_ssa, const F* bg_aer_g, void* stream) \
+{ const AerIn<F> bg_aer{bg_aer_tau, bg_aer_ssa, bg_aer_g}; \
+  return bg_profile_entry<F>("rrx_rt_bg_profile_aer" #SFX, nbg, ngpt, nbnd, igpt, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, \
+                             bg_cld_g, bg_profile, stream, &bg_aer); } \
+int rrx_rt_trace_counts_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, F inc_dir, F inc_dif, int knx, int kny, int knz, const F* k_null, \
+        unsigned long long seed, long long photon0, long long nphotons, int max_events, \
+        unsigned long long* sfc_dn_dir, unsigned long long* sfc_dn_dif, unsigned long long* sfc_up, unsigned long long* tod_up, \
+        unsigned long long* abs_dir, unsigned long long* abs_dif, unsigned long long* n_capped, \
+        unsigned long long* toa_up, unsigned long long* tod_dn_dir, unsigned long long* tod_dn_dif, \
+        unsigned long long* bg_abs_dir, unsigned long long* bg_abs_dif, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_profile, const F* aer_tau, const F* aer_ssa, const F* aer_g, void* stream) \
+{ const AerIn<F> aer{aer_tau, aer_ssa, aer_g}; \
+  return trace_entry<F>("rrx_rt_trace_counts_aer" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
+                        cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, k_null, seed, \
+                        photon0, nphotons, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
+                        PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, true, \
+                        BgTallies<F>{toa_up, tod_dn_dir, tod_dn_dif, bg_abs_dir, bg_abs_dif}, nbg, dz_bg, bg_profile, &aer); } \
+int rrx_raytracer_sw_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
+        long long photons_per_pixel, unsigned long long seed, int max_events, \
+        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, \
+        F* toa_up, F* tod_dn_dir, F* tod_dn_dif, F* bg_abs_dir, F* bg_abs_dif, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, \
+        const F* const* aer3, const F* const* bg_aer3, void* stream) \
+{ F* const bg_out[5] = {toa_up, tod_dn_dir, tod_dn_dif, bg_abs_dir, bg_abs_dif}; \
+  /* each triple is a host array of three device pointers (tau, ssa, g); a NULL array is a triple of NULLs */ \
+  const AerIn<F> aer = aer3 != nullptr ? AerIn<F>{aer3[0], aer3[1], aer3[2]} : AerIn<F>{}; \
+  const AerIn<F> bg_aer = bg_aer3 != nullptr ? AerIn<F>{bg_aer3[0], bg_aer3[1], bg_aer3[2]} : AerIn<F>{}; \
+  return raytracer_sw_entry<F>("rrx_raytracer_sw_aer" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
+                               cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, \
+                               photons_per_pixel, seed, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
+                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, true, bg_out, nbg, dz_bg, bg_tau, bg_ssa, \
+                               bg_cld_tau, bg_cld_ssa, bg_cld_g, &aer, &bg_aer); }
 
 RRX_DEFINE_RT(double, _f64)
 RRX_DEFINE_RT(float, _f32)

@@ -77,7 +77,8 @@ struct BwArgs
 
 // the state of a walk to the sun: cell indices, the distances along -s to the next face of each axis, the distance covered, the
 // optical path so far, the deposit's factor in front of T_sun, and what follows the deposit (0: the surface's roulette, 1: a
-// Rayleigh scattering, 2: a cloud scattering with asymmetry gc; with a phase table gc holds the cell's radius)
+// Rayleigh scattering, 2: a cloud scattering with asymmetry gc; with a phase table gc holds the cell's radius, 3: an aerosol
+// scattering, Henyey-Greenstein with gc = g_a whether there is a table or not)
 template<typename F>
 struct Walk
 {
@@ -121,9 +122,19 @@ __device__ __forceinline__ bool after_surface(Stream& rng, F& weight, F& ux, F& 
 // and no walk: it is made inside the event, Henyey-Greenstein for the cloud species. A deposit from inside the grid ends its walk
 // with exp(-(tau_walk + tau_above[nbg]/mu0)): one exp of the summed path. The draw order is that of the header. nbg = 0: the
 // integers of the other instantiations.
-template<typename F, bool TABLE, bool BG>
-__global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, const PhaseArgs<F,TABLE> ph, const BgArgs<F,BG> bgin)
+//
+// AER (trace_bw_kernel<F,TABLE,true,true>, the rrx_*_aer entries; rrx_rt_common.h; tests/raytracer_aer_ref.py restates it):
+// aerosol as a third species, built on top of the BG form only, which handles nbg = 0. k_ext and k_sca take tau_a as rrx_rt_common.h
+// writes them, the walk to the sun sums that k_ext and tau_above holds the aerosol's share. The draw count and DRAW ORDER are
+// unchanged: the species uniform u picks cloud iff u k_sca < k_sca_cld, otherwise aerosol iff u k_sca < k_sca_cld + k_sca_aer,
+// otherwise gas. An aerosol scattering deposits with the Henyey-Greenstein density of g = min(g_a, 1 - eps) and draws its new
+// direction from it, in the grid (after the walk: then = 3) and aloft, with a phase table too. DEPARTURE: the reference draws
+// aerosol, cloud, gas in that order; cloud comes first here so that a scene without aerosol draws exactly what it draws without
+// this form.
+template<typename F, bool TABLE, bool BG, bool AER>
+__global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, const PhaseArgs<F,TABLE> ph, const BgArgs<F,BG,AER> bgin)
 {
+    static_assert(BG || !AER, "the aerosol form is built on the background form");
     const long long nthreads = (long long)gridDim.x*blockDim.x;
     long long next_ray = (long long)blockIdx.x*blockDim.x + threadIdx.x;
 
@@ -143,7 +154,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
             mu_s = stage;
             stage += ph.in.nmu;
         }
-        if constexpr (BG) bg = stage_background(bgin.in, stage);
+        if constexpr (BG) bg = stage_background<F, AER ? BG_ROWS_AER : BG_ROWS>(bgin.in, stage);
     }
 
     const int nx = a.nx, ny = a.ny, nz = a.nz;
@@ -157,6 +168,13 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
     const F* __restrict__ ssa_g = a.ssa + ncol*nz*a.igpt;
     const F* __restrict__ ctau_b = ibnd >= 0 ? a.cld_tau + ncol*nz*ibnd : nullptr;
     if constexpr (TABLE) tab = table_of_band(ph.in, ibnd);
+    [[maybe_unused]] int ibnd_a = -1;
+    [[maybe_unused]] const F* __restrict__ atau_b = nullptr;
+    if constexpr (AER)
+    {
+        ibnd_a = bgin.aer.tau != nullptr ? band_of(a.igpt, a.nbnd, a.band_lims_gpt) : -1;
+        atau_b = ibnd_a >= 0 ? bgin.aer.tau + ncol*nz*ibnd_a : nullptr;
+    }
     const F inf = F(INFINITY);
     [[maybe_unused]] const F g_max = F(1.) - Lim<F>::eps();
     const F pi = F(3.141592653589793);
@@ -187,7 +205,8 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
             const int lay = a.top_at_1 ? nz-1-w.k : w.k;
             const size_t cell = size_t(w.i) + size_t(w.j)*nx + ncol*lay;
             const F tc = ibnd >= 0 ? ctau_b[cell] : F(0.);
-            w.tau = w.tau + k_ext_of(tau_g[cell], tc, a.dz)*(tn - w.t);
+            if constexpr (AER) w.tau = w.tau + k_ext_of(tau_g[cell], tc, ibnd_a >= 0 ? atau_b[cell] : F(0.), a.dz)*(tn - w.t);
+            else w.tau = w.tau + k_ext_of(tau_g[cell], tc, a.dz)*(tn - w.t);
             w.t = tn;
             if (axis == 0)
             {
@@ -211,6 +230,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
                 tally(a.counts, size_t(pix), to_count(clamped ? F(1048576.) : d));
                 walking = false;
                 if (w.then == 0) { alive = after_surface(rng, weight, ux, uy, uz); pending = false; }
+                else if (AER && w.then == 3) scatter_direction(rng, true, w.gc, g_max, ux, uy, uz);
                 else if constexpr (TABLE) scatter_direction_table(rng, w.then == 2, tab, mu_s, w.gc, ux, uy, uz);
                 else scatter_direction(rng, w.then == 2, w.gc, g_max, ux, uy, uz);
             }
@@ -380,12 +400,17 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
                     int i = 0, j = 0, k = 0;
                     size_t cell = 0;
                     F k_ext = F(0.), k_sca = F(0.), k_sca_cld = F(0.), gc = F(0.);
+                    [[maybe_unused]] F k_sca_aer = F(0.), ga = F(0.);
                     if (in_bg)
                     {
                         if constexpr (BG)
                         {
                             cell = size_t(kn - a.knz);
                             k_ext = kn_val; k_sca = bg.k_sca[cell]; k_sca_cld = bg.k_sca_cld[cell]; gc = bg.g[cell];
+                            if constexpr (AER)
+                            {
+                                k_sca_aer = bg.k_ext[BG_K_SCA_AER*(bg.nbg + 1) + cell]; ga = bg.k_ext[BG_G_AER*(bg.nbg + 1) + cell];
+                            }
                         }
                     }
                     else
@@ -401,8 +426,23 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
                             tc = a.cld_tau[cb]; wc = a.cld_ssa[cb];
                             if constexpr (!TABLE) gc = a.cld_g[cb];
                         }
-                        k_ext = k_ext_of(t, tc, a.dz);
-                        k_sca = (t*w0 + tc*wc) / a.dz;
+                        if constexpr (AER)
+                        {
+                            F ta = F(0.), wa = F(0.);
+                            if (ibnd_a >= 0)
+                            {
+                                const size_t cb = cell + ncol*nz*ibnd_a;
+                                ta = bgin.aer.tau[cb]; wa = bgin.aer.ssa[cb]; ga = bgin.aer.g[cb];
+                            }
+                            k_ext = k_ext_of(t, tc, ta, a.dz);
+                            k_sca = k_sca_of(t, w0, tc, wc, ta, wa, a.dz);
+                            k_sca_aer = (ta*wa) / a.dz;
+                        }
+                        else
+                        {
+                            k_ext = k_ext_of(t, tc, a.dz);
+                            k_sca = (t*w0 + tc*wc) / a.dz;
+                        }
                         k_sca_cld = (tc*wc) / a.dz;
                     }
                     const F f_no_abs = clampf(F(1.) - (k_ext - k_sca)/kn_val, F(0.), F(1.));
@@ -411,7 +451,10 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
                     if (!(weight > F(0.))) { alive = false; break; }
                     if (rng.next<F>()*(k_sca + (kn_val - k_ext)) < k_sca)
                     {
-                        const bool cloud = rng.next<F>()*k_sca < k_sca_cld;
+                        const F us = rng.next<F>()*k_sca;
+                        const bool cloud = us < k_sca_cld;
+                        [[maybe_unused]] bool aerosol = false;
+                        if constexpr (AER) aerosol = !cloud && us < k_sca_cld + k_sca_aer;
                         const F cs = clampf(-((ux*a.sun_x + uy*a.sun_y) + uz*a.sun_z), F(-1.), F(1.));
                         F phase;
                         [[maybe_unused]] bool bg_done = false;
@@ -421,7 +464,8 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
                             {
                                 // ---- a scattering in background layer b: the deposit needs no walk (the layers are horizontally uniform)
                                 bg_done = true;
-                                if (cloud)
+                                if (aerosol) { gc = ga; phase = hg_phase(min(ga, g_max), cs); }
+                                else if (cloud)
                                 {
                                     const F g = min(gc, g_max);
                                     const F q = (F(1.) + g*g) - (F(2.)*g)*cs;
@@ -433,11 +477,12 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
                                 const bool clamped = d > F(1048576.);
                                 if (clamped) atomicAdd(a.n_clamped, 1ull);
                                 tally(a.counts, size_t(pix), to_count(clamped ? F(1048576.) : d));
-                                scatter_direction(rng, cloud, gc, g_max, ux, uy, uz);
+                                scatter_direction(rng, cloud || aerosol, gc, g_max, ux, uy, uz);
                             }
                         }
                         if (bg_done) break;
-                        if constexpr (TABLE)
+                        if (aerosol) { gc = ga; phase = hg_phase(min(ga, g_max), cs); }
+                        else if constexpr (TABLE)
                         {
                             if (cloud) { gc = ph.in.cld_re[cell]; phase = phase_eval(tab, mu_s, gc, cs); }          // cld_re (ncol, nz): one radius for all bands
                             else phase = F(0.75)*(F(1.) + cs*cs);
@@ -449,7 +494,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
                             phase = (F(1.) - g*g) / (q*sqrt(q));
                         }
                         else phase = F(0.75)*(F(1.) + cs*cs);
-                        begin_walk(w, a, vx, vy, vz, x, y, z, i, j, k, (weight*phase)/(F(4.)*pi), cloud ? 2 : 1, gc);
+                        begin_walk(w, a, vx, vy, vz, x, y, z, i, j, k, (weight*phase)/(F(4.)*pi), aerosol ? 3 : (cloud ? 2 : 1), gc);
                         walking = true;
                     }
                 }
@@ -487,7 +532,7 @@ void check_sensor(const int type, const F fov, const F* s, const F dx, const F d
 
 template<typename F>
 void launch_trace_bw(BwArgs<F> a, const PhaseIn<F>& ph, const F mu0, const F azimuth, const int type, const int npx, const int npy, const F fov,
-                     const F* s, const u64 seed, hipStream_t st, const BgArgs<F,true>* bg = nullptr)
+                     const F* s, const u64 seed, hipStream_t st, const BgArgs<F,true>* bg = nullptr, const AerIn<F>* aer = nullptr)
 {
     const double st_ = std::sqrt(std::max(0.0, 1.0 - double(mu0)*double(mu0)));
     a.mu0 = mu0; a.sun_x = F(st_*std::cos(double(azimuth))); a.sun_y = F(st_*std::sin(double(azimuth))); a.sun_z = -mu0;
@@ -496,14 +541,22 @@ void launch_trace_bw(BwArgs<F> a, const PhaseIn<F>& ph, const F mu0, const F azi
     a.px = s[0]; a.py = s[1]; a.pz = s[2]; a.wx = s[3]; a.wy = s[4]; a.wz = s[5]; a.hx = s[6]; a.hy = s[7]; a.hz = s[8];
     a.ex = s[9]; a.ey = s[10]; a.ez = s[11];
     const int blocks = int(std::min<long long>((a.nrays + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
-    if (bg != nullptr)
+    if (bg != nullptr && aer != nullptr)
+    {
+        // the aerosol form: the background's profile has BG_ROWS_AER rows
+        const size_t lds = bg_lds_numbers(bg->in.nbg, BG_ROWS_AER)*sizeof(F);
+        const BgArgs<F,true,true> ba{bg->in, *aer};
+        if (ph.given()) trace_bw_kernel<F,true,true,true><<<blocks, RT_BLOCK, size_t(ph.nmu)*sizeof(F) + lds, st>>>(a, PhaseArgs<F,true>{ph}, ba);
+        else trace_bw_kernel<F,false,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, ba);
+    }
+    else if (bg != nullptr)
     {
         const size_t lds = bg_lds_numbers(bg->in.nbg)*sizeof(F);
-        if (ph.given()) trace_bw_kernel<F,true,true><<<blocks, RT_BLOCK, size_t(ph.nmu)*sizeof(F) + lds, st>>>(a, PhaseArgs<F,true>{ph}, *bg);
-        else trace_bw_kernel<F,false,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, *bg);
+        if (ph.given()) trace_bw_kernel<F,true,true,false><<<blocks, RT_BLOCK, size_t(ph.nmu)*sizeof(F) + lds, st>>>(a, PhaseArgs<F,true>{ph}, *bg);
+        else trace_bw_kernel<F,false,true,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, *bg);
     }
-    else if (ph.given()) trace_bw_kernel<F,true,false><<<blocks, RT_BLOCK, size_t(ph.nmu)*sizeof(F), st>>>(a, PhaseArgs<F,true>{ph}, BgArgs<F,false>{});
-    else trace_bw_kernel<F,false,false><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,false>{}, BgArgs<F,false>{});
+    else if (ph.given()) trace_bw_kernel<F,true,false,false><<<blocks, RT_BLOCK, size_t(ph.nmu)*sizeof(F), st>>>(a, PhaseArgs<F,true>{ph}, BgArgs<F,false>{});
+    else trace_bw_kernel<F,false,false,false><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,false>{}, BgArgs<F,false>{});
 }
 
 template<typename F>
@@ -527,8 +580,11 @@ int trace_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd
                    F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null,
                    int sensor_type, int npx, int npy, F fov, const F* sensor, u64 seed, long long ray0, long long nrays, int max_events,
                    u64* counts, u64* n_capped, u64* n_clamped, void* stream, const PhaseIn<F> ph = PhaseIn<F>{},
-                   const bool with_bg = false, const int nbg = 0, const F* dz_bg = nullptr, const F* bg_profile = nullptr)
+                   const bool with_bg = false, const int nbg = 0, const F* dz_bg = nullptr, const F* bg_profile = nullptr,
+                   const AerIn<F>* aer = nullptr)
 {
+    // aer: rrx_rt_bw_trace_counts_aer. With nbg > 0 bg_profile then has BG_ROWS_AER rows and the aerosol form runs whatever the grid's
+    // triple is; with nbg = 0 and a NULL triple it is the _bg entry.
     RRX_TRY
     check_nbg(nbg);
     if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"npx", npx}, {"npy", npy}, {"nrays", nrays}})) return 0;
@@ -537,6 +593,7 @@ int trace_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd
     check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"k_null", k_null}, {"sensor", sensor}, {"counts", counts},
                   {"n_capped", n_capped}, {"n_clamped", n_clamped}});
     check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
+    if (aer != nullptr) check_aerosol("aer_", nbnd, band_lims_gpt, aer->tau, aer->ssa, aer->g);
     check_phase(ph, cld_tau);
     if (igpt < 0 || igpt >= ngpt) throw std::runtime_error("igpt is outside [0, ngpt)");
     check_scene(dx, dy, dz, mu0);
@@ -554,6 +611,11 @@ int trace_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd
         {
             check_needed({{"dz_bg", dz_bg}, {"bg_profile", bg_profile}});
             bg.in.z = bg_levels<F>(nbg, dz_bg, nz, knz, dz);
+        }
+        if (aer != nullptr && (aer->tau != nullptr || nbg > 0))
+        {
+            launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, static_cast<hipStream_t>(stream), &bg, aer);
+            return 0;
         }
         launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, static_cast<hipStream_t>(stream), &bg);
         return 0;
@@ -575,6 +637,18 @@ inline int bg_profile_of(int nbg, int ngpt, int nbnd, int g, const double* dzb, 
 inline int bg_profile_of(int nbg, int ngpt, int nbnd, int g, const float* dzb, const float* t, const float* w, const int* lims, const float* ct,
                          const float* cw, const float* cg, float* prof, void* st)
 { return rrx_rt_bg_profile_f32(nbg, ngpt, nbnd, g, dzb, t, w, lims, ct, cw, cg, prof, st); }
+inline int k_null_aer_of(int nx, int ny, int nz, int ngpt, int nbnd, int g, RrxBool t, const double* tau, const int* lims, const double* ct,
+                         double dz, int knx, int kny, int knz, double* kn, const double* at, void* st)
+{ return rrx_rt_k_null_aer_f64(nx, ny, nz, ngpt, nbnd, g, t, tau, lims, ct, dz, knx, kny, knz, kn, at, st); }
+inline int k_null_aer_of(int nx, int ny, int nz, int ngpt, int nbnd, int g, RrxBool t, const float* tau, const int* lims, const float* ct,
+                         float dz, int knx, int kny, int knz, float* kn, const float* at, void* st)
+{ return rrx_rt_k_null_aer_f32(nx, ny, nz, ngpt, nbnd, g, t, tau, lims, ct, dz, knx, kny, knz, kn, at, st); }
+inline int bg_profile_aer_of(int nbg, int ngpt, int nbnd, int g, const double* dzb, const double* t, const double* w, const int* lims,
+                             const double* ct, const double* cw, const double* cg, double* prof, const AerIn<double>& a, void* st)
+{ return rrx_rt_bg_profile_aer_f64(nbg, ngpt, nbnd, g, dzb, t, w, lims, ct, cw, cg, prof, a.tau, a.ssa, a.g, st); }
+inline int bg_profile_aer_of(int nbg, int ngpt, int nbnd, int g, const float* dzb, const float* t, const float* w, const int* lims,
+                             const float* ct, const float* cw, const float* cg, float* prof, const AerIn<float>& a, void* st)
+{ return rrx_rt_bg_profile_aer_f32(nbg, ngpt, nbnd, g, dzb, t, w, lims, ct, cw, cg, prof, a.tau, a.ssa, a.g, st); }
 inline int counts_to_flux_of(long long n, const u64* c, double scale, double* out, void* st) { return rrx_rt_counts_to_flux_f64(n, c, scale, out, st); }
 inline int counts_to_flux_of(long long n, const u64* c, float scale, float* out, void* st) { return rrx_rt_counts_to_flux_f32(n, c, scale, out, st); }
 
@@ -585,8 +659,10 @@ int raytracer_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
                        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, u64 seed, int max_events,
                        F* radiance, u64* n_capped, u64* n_clamped, void* stream, const PhaseIn<F> ph = PhaseIn<F>{},
                        const bool with_bg = false, const int nbg = 0, const F* dz_bg = nullptr, const F* bg_tau = nullptr,
-                       const F* bg_ssa = nullptr, const F* bg_cld_tau = nullptr, const F* bg_cld_ssa = nullptr, const F* bg_cld_g = nullptr)
+                       const F* bg_ssa = nullptr, const F* bg_cld_tau = nullptr, const F* bg_cld_ssa = nullptr, const F* bg_cld_g = nullptr,
+                       const AerIn<F>* aer = nullptr, const AerIn<F>* bg_aer = nullptr)
 {
+    // aer, bg_aer: rrx_raytracer_bw_aer; with both triples NULL (bg_aer is not read when nbg = 0) it is the _bg entry
     RRX_TRY
     check_nbg(nbg);
     if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"npx", npx}, {"npy", npy}, {"rays_per_pixel", rays_per_pixel}})) return 0;
@@ -594,6 +670,7 @@ int raytracer_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
     check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"inc_dir", inc_dir}, {"sensor", sensor}, {"radiance", radiance},
                   {"n_capped", n_capped}, {"n_clamped", n_clamped}});
     check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
+    if (aer != nullptr) check_aerosol("aer_", nbnd, band_lims_gpt, aer->tau, aer->ssa, aer->g);
     check_phase(ph, cld_tau);
     check_scene(dx, dy, dz, mu0);
     for (int g=0; g<ngpt; ++g)
@@ -605,6 +682,10 @@ int raytracer_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
     check_sensor(sensor_type, fov, sensor, dx, dy, dz, nx, ny, nz, mu0, max_walk);
     const bool bg_on = with_bg && nbg > 0;
     BgLevels<F> lev{};
+    if (bg_on && bg_aer != nullptr) check_aerosol("bg_aer_", nbnd, band_lims_gpt, bg_aer->tau, bg_aer->ssa, bg_aer->g);
+    // the aerosol form runs when either triple is given
+    const AerIn<F> aer_grid = aer != nullptr ? *aer : AerIn<F>{}, aer_bg = (bg_on && bg_aer != nullptr) ? *bg_aer : AerIn<F>{};
+    const bool aer_on = with_bg && (aer_grid.tau != nullptr || aer_bg.tau != nullptr);
     if (bg_on)
     {
         check_bg_medium(nbg, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g);
@@ -614,7 +695,7 @@ int raytracer_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t npix = size_t(npx)*npy;
     const size_t n_kn = (size_t(knx)*kny*knz*sizeof(F) + sizeof(u64) - 1) / sizeof(u64);
-    const size_t n_prof = bg_on ? (size_t(BG_ROWS)*(nbg + 1)*sizeof(F) + sizeof(u64) - 1) / sizeof(u64) : 0;
+    const size_t n_prof = bg_on ? (size_t(aer_on ? BG_ROWS_AER : BG_ROWS)*(nbg + 1)*sizeof(F) + sizeof(u64) - 1) / sizeof(u64) : 0;
     WorkspaceLease lease(st);
     u64* counts = lease.get<u64>(npix + n_kn + n_prof);
     F* k_null = reinterpret_cast<F*>(counts + npix);
@@ -628,16 +709,20 @@ int raytracer_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
     {
         if (!(inc_dir[g] > F(0.))) continue;
         if (hipMemsetAsync(counts, 0, npix*sizeof(u64), st) != hipSuccess) throw std::runtime_error("zeroing the counts failed");
-        if (k_null_of(nx, ny, nz, ngpt, nbnd, g, top_at_1, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null, stream) != 0)
+        if ((aer_grid.tau != nullptr
+                 ? k_null_aer_of(nx, ny, nz, ngpt, nbnd, g, top_at_1, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null, aer_grid.tau, stream)
+                 : k_null_of(nx, ny, nz, ngpt, nbnd, g, top_at_1, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null, stream)) != 0)
             throw std::runtime_error(rrx_last_error());
         BwArgs<F> a = scene_args<F>(nx, ny, nz, nbnd, g, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo,
                                     knx, kny, knz, k_null, 0ull, nrays, max_events, max_walk, counts, n_capped, n_clamped);
         if (with_bg)
         {
             BgArgs<F,true> bg{BgIn<F>{bg_on ? nbg : 0, profile, lev}};
-            if (bg_on && bg_profile_of(nbg, ngpt, nbnd, g, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, profile, stream) != 0)
+            if (bg_on && (aer_on
+                    ? bg_profile_aer_of(nbg, ngpt, nbnd, g, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, profile, aer_bg, stream)
+                    : bg_profile_of(nbg, ngpt, nbnd, g, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, profile, stream)) != 0)
                 throw std::runtime_error(rrx_last_error());
-            launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, st, &bg);
+            launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, st, &bg, aer_on ? &aer_grid : nullptr);
         }
         else launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, st);
         const F scale = inc_dir[g] / (mu0*F(rays_per_pixel));
@@ -707,7 +792,33 @@ int rrx_raytracer_bw_bg##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool
                                dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, \
                                rays_per_pixel, seed, max_events, radiance, n_capped, n_clamped, stream, \
                                PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, true, nbg, dz_bg, bg_tau, bg_ssa, bg_cld_tau, \
-                               bg_cld_ssa, bg_cld_g); }
+                               bg_cld_ssa, bg_cld_g); } \
+int rrx_rt_bw_trace_counts_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
+        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_profile, const F* aer_tau, const F* aer_ssa, const F* aer_g, void* stream) \
+{ const AerIn<F> aer{aer_tau, aer_ssa, aer_g}; \
+  return trace_bw_entry<F>("rrx_rt_bw_trace_counts_aer" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, \
+                           cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, knx, kny, knz, k_null, sensor_type, npx, npy, fov, sensor, seed, ray0, \
+                           nrays, max_events, counts, n_capped, n_clamped, stream, PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, \
+                           true, nbg, dz_bg, bg_profile, &aer); } \
+int rrx_raytracer_bw_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
+        F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, \
+        const F* aer_tau, const F* aer_ssa, const F* aer_g, const F* bg_aer_tau, const F* bg_aer_ssa, const F* bg_aer_g, void* stream) \
+{ const AerIn<F> aer{aer_tau, aer_ssa, aer_g}, bg_aer{bg_aer_tau, bg_aer_ssa, bg_aer_g}; \
+  return raytracer_bw_entry<F>("rrx_raytracer_bw_aer" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, \
+                               dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, \
+                               rays_per_pixel, seed, max_events, radiance, n_capped, n_clamped, stream, \
+                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, true, nbg, dz_bg, bg_tau, bg_ssa, bg_cld_tau, \
+                               bg_cld_ssa, bg_cld_g, &aer, &bg_aer); }
 
 RRX_DEFINE_RT_BW(double, _f64)
 RRX_DEFINE_RT_BW(float, _f32)

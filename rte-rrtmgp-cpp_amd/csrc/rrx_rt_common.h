@@ -75,6 +75,28 @@ __device__ __forceinline__ int band_of(const int igpt, const int nbnd, const int
 
 template<typename F> __device__ __forceinline__ F k_ext_of(const F tau, const F tau_c, const F dz) { return (tau + tau_c) / dz; }
 
+// ---- aerosol as a third scattering species: a band triple aer_tau, aer_ssa, aer_g with the layout of the cloud triple,
+// in the grid and (bg_aer_*) in the background. Per cell, with the parentheses as written:
+//   k_ext = ((tau + tau_c) + tau_a)/dz,  k_sca = ((tau ssa + tau_c ssa_c) + tau_a ssa_a)/dz,  k_sca_aer = (tau_a ssa_a)/dz;
+// tau_a = 0 gives the bits of the medium without aerosol. SPECIES DRAW from the one uniform u that is drawn today: cloud iff
+// u k_sca < k_sca_cld (unchanged), otherwise aerosol iff u k_sca < k_sca_cld + k_sca_aer, otherwise gas. Aerosol scatters by
+// Henyey-Greenstein with min(g_a, 1 - eps) everywhere: a phase table stays the cloud's alone.
+template<typename F> __device__ __forceinline__ F k_ext_of(const F tau, const F tau_c, const F tau_a, const F dz) { return ((tau + tau_c) + tau_a) / dz; }
+template<typename F> __device__ __forceinline__ F k_sca_of(const F tau, const F ssa, const F tau_c, const F ssa_c, const F tau_a, const F ssa_a, const F dz)
+{
+    return ((tau*ssa + tau_c*ssa_c) + tau_a*ssa_a) / dz;
+}
+
+// the grid's aerosol triple as the kernels take it, behind their background argument (NULL: no aerosol in the grid)
+template<typename F> struct AerIn { const F* tau; const F* ssa; const F* g; };
+
+// the Henyey-Greenstein density of cos_s, 4 pi normalised, g already limited: only + - x / and sqrt
+template<typename F> __device__ __forceinline__ F hg_phase(const F g, const F cos_s)
+{
+    const F q = (F(1.) + g*g) - (F(2.)*g)*cos_s;
+    return (F(1.) - g*g) / (q*sqrt(q));
+}
+
 // cosine-weighted direction about the vertical; sign = -1 downward, +1 upward
 template<typename F>
 __device__ __forceinline__ void lambert(Stream& rng, const F sign, F& ux, F& uy, F& uz)
@@ -155,15 +177,19 @@ __device__ __forceinline__ void scatter_direction(Stream& rng, const bool cloud,
 // its x, y and block). uz = 0 in a layer with k_ext = 0: dropped into n_capped. No epsilon nudges.
 constexpr int RT_BG_MAX = 256;         // the largest nbg: the levels travel to the kernels by value and live in LDS with the profile
 enum { BG_K_EXT = 0, BG_K_SCA = 1, BG_K_SCA_CLD = 2, BG_G = 3, BG_TAU_ABOVE = 4, BG_ROWS = 5 };
+// with aerosol (rrx_rt_bg_profile_aer) the profile is (BG_ROWS_AER, nbg+1): the five rows above by the formulas with tau_a, tau_above
+// the sum of (tau + tau_c) + tau_a, then k_sca_aer = (tau_a ssa_a)/dz_bg and g_aer = min(g_a, 1 - eps); slot nbg of the two is 0
+enum { BG_K_SCA_AER = 5, BG_G_AER = 6, BG_ROWS_AER = 7 };
 
 // nbg + 1 numbers by value: the levels z (trace kernels), or one number per layer (rrx_rt_bg_profile: dz_bg)
 template<typename F> struct BgLevels { F v[RT_BG_MAX + 1]; };
 
 template<typename F> struct BgIn { int nbg; const F* profile; BgLevels<F> z; };
 
-// the kernels' background argument: empty in the instantiations without one
-template<typename F, bool BG> struct BgArgs {};
-template<typename F> struct BgArgs<F,true> { BgIn<F> in; };
+// the kernels' background argument: empty in the instantiations without one; AER: the aerosol form, built on the background form
+template<typename F, bool BG, bool AER = false> struct BgArgs {};
+template<typename F> struct BgArgs<F,true,false> { BgIn<F> in; };
+template<typename F> struct BgArgs<F,true,true> { BgIn<F> in; AerIn<F> aer; };
 
 // the profile and the levels in LDS: 6 (nbg + 1) numbers
 template<typename F>
@@ -173,21 +199,22 @@ struct BgView
     const F* k_ext; const F* k_sca; const F* k_sca_cld; const F* g; const F* tau_above; const F* z;
 };
 
-inline size_t bg_lds_numbers(const int nbg) { return nbg > 0 ? size_t(BG_ROWS + 1)*(nbg + 1) : size_t(0); }
+inline size_t bg_lds_numbers(const int nbg, const int rows = BG_ROWS) { return nbg > 0 ? size_t(rows + 1)*(nbg + 1) : size_t(0); }
 
-// every thread of the workgroup calls it before its loop; lds: bg_lds_numbers(nbg) numbers
-template<typename F>
+// every thread of the workgroup calls it before its loop; lds: bg_lds_numbers(nbg, ROWS) numbers. ROWS = BG_ROWS_AER: the rows
+// k_sca_aer and g_aer lie behind tau_above, at k_ext + BG_K_SCA_AER (nbg + 1) and k_ext + BG_G_AER (nbg + 1), the levels behind them
+template<typename F, int ROWS = BG_ROWS>
 __device__ __forceinline__ BgView<F> stage_background(const BgIn<F>& in, F* lds)
 {
     const int n1 = in.nbg + 1;
     if (in.nbg > 0)
     {
-        for (int n=threadIdx.x; n<BG_ROWS*n1; n+=blockDim.x) lds[n] = in.profile[n];
-        for (int n=threadIdx.x; n<n1; n+=blockDim.x) lds[BG_ROWS*n1 + n] = in.z.v[n];
+        for (int n=threadIdx.x; n<ROWS*n1; n+=blockDim.x) lds[n] = in.profile[n];
+        for (int n=threadIdx.x; n<n1; n+=blockDim.x) lds[ROWS*n1 + n] = in.z.v[n];
     }
     __syncthreads();
     return BgView<F>{in.nbg, lds + BG_K_EXT*n1, lds + BG_K_SCA*n1, lds + BG_K_SCA_CLD*n1, lds + BG_G*n1, lds + BG_TAU_ABOVE*n1,
-                     lds + BG_ROWS*n1};
+                     lds + ROWS*n1};
 }
 
 // the layer of a height above the domain top: the largest b <= nbg-1 with z[b] <= height (nbg >= 1)
@@ -284,6 +311,17 @@ void check_bg_medium(const int nbg, const int nbnd, const F* dz_bg, const F* bg_
     if (given != 0 && given != 3) throw std::runtime_error("bg_cld_tau, bg_cld_ssa, bg_cld_g must be all NULL or all given");
     if (given == 3 && band_lims_gpt == nullptr) throw std::runtime_error("band_lims_gpt is NULL");
     if (given == 3 && nbnd < 1) throw std::runtime_error("nbnd must be >= 1 with a background cloud triple");
+}
+
+// what the _aer entries check of an aerosol triple (the grid's: aer_*, the background's: bg_aer_*)
+template<typename F>
+void check_aerosol(const char* which, const int nbnd, const int* band_lims_gpt, const F* tau, const F* ssa, const F* g)
+{
+    const int given = (tau != nullptr) + (ssa != nullptr) + (g != nullptr);
+    const std::string w(which);
+    if (given != 0 && given != 3) throw std::runtime_error(w + "tau, " + w + "ssa, " + w + "g must be all NULL or all given");
+    if (given == 3 && band_lims_gpt == nullptr) throw std::runtime_error("band_lims_gpt is NULL");
+    if (given == 3 && nbnd < 1) throw std::runtime_error("nbnd must be >= 1 with an aerosol triple");
 }
 
 inline void check_nbg(const int nbg)

@@ -629,12 +629,19 @@ class HipKernels:
         out["n_capped"] = torch.zeros((1,), dtype=torch.int64, device=self.device)
         return out
 
-    def rt_k_null(self, tau, igpt, nx, ny, dz, kn_grid, top_at_1, cloud=None, band_lims=None):
-        """k_null (knz, kny, knx), kn counted upward from the surface, for g-point igpt (0-based)."""
+    def rt_k_null(self, tau, igpt, nx, ny, dz, kn_grid, top_at_1, cloud=None, band_lims=None, aerosol=None):
+        """k_null (knz, kny, knx), kn counted upward from the surface, for g-point igpt (0-based). aerosol=: None, or the grid's
+        aerosol triple (rrx_rt_k_null_aer; a triple of None: its NULL pointer)."""
         dims, (lims, ct, _, _) = self._rt_scene(tau, nx, ny, cloud, band_lims)
         knx, kny, knz = (int(k) for k in kn_grid)
         out = self.empty((knz, kny, knx))
-        self._c("rt_k_null", *dims, igpt, top_at_1, tau, lims, ct, dz, knx, kny, knz, out)
+        if aerosol is None:
+            self._c("rt_k_null", *dims, igpt, top_at_1, tau, lims, ct, dz, knx, kny, knz, out)
+        else:
+            if aerosol[0] is not None and band_lims is None:
+                raise ValueError("raytracer: an aerosol triple needs band_lims")
+            self._c("rt_k_null_aer", *dims, igpt, top_at_1, tau, band_lims if (cloud is not None or aerosol[0] is not None) else None, ct, dz,
+                    knx, kny, knz, out, aerosol[0])
         return out
 
     def rt_trace_counts(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, k_null, seed,
@@ -742,18 +749,52 @@ class HipKernels:
         cloud = (None, None, None) if background.cloud is None else tuple(background.cloud)
         return (dz.size, dz, background.tau, background.ssa, *cloud)
 
-    def rt_bg_profile(self, background, igpt, band_lims=None):
-        """The profile (5, nbg+1) of g-point igpt: k_ext, k_sca, k_sca_cld, g, tau_above."""
+    def rt_bg_profile(self, background, igpt, band_lims=None, aerosol=None):
+        """The profile (5, nbg+1) of g-point igpt: k_ext, k_sca, k_sca_cld, g, tau_above. aerosol=: the background's aerosol triple
+        (a triple of None: no aerosol aloft) gives the profile (7, nbg+1) of rrx_rt_bg_profile_aer, which the _aer trace entries
+        take: k_sca_aer and g_aer behind the five rows."""
         dz = self._rt_bg_dz(background)
         ngpt = background.tau.shape[0]
         if background.cloud is not None and band_lims is None:
             raise ValueError("raytracer: a background cloud triple needs band_lims")
         nbnd = int(band_lims.shape[0]) if band_lims is not None else 0
         cloud = (None, None, None) if background.cloud is None else tuple(background.cloud)
-        out = self.empty((5, dz.size + 1))
-        self._c("rt_bg_profile", dz.size, ngpt, nbnd, igpt, dz, background.tau, background.ssa,
-                band_lims if background.cloud is not None else None, *cloud, out)
+        if aerosol is None:
+            out = self.empty((5, dz.size + 1))
+            self._c("rt_bg_profile", dz.size, ngpt, nbnd, igpt, dz, background.tau, background.ssa,
+                    band_lims if background.cloud is not None else None, *cloud, out)
+            return out
+        bg_aer = tuple(aerosol)
+        if bg_aer[0] is not None and band_lims is None:
+            raise ValueError("raytracer: a background aerosol triple needs band_lims")
+        out = self.empty((7, dz.size + 1))
+        self._c("rt_bg_profile_aer", dz.size, ngpt, nbnd, igpt, dz, background.tau, background.ssa,
+                band_lims if (background.cloud is not None or bg_aer[0] is not None) else None, *cloud, out, *bg_aer)
         return out
+
+    # Aerosol as a third scattering species (the rrx_*_aer entries; DESIGN 4.18). aerosol=: None or the grid's band triple
+    # (tau, ssa, g) of (nbnd, nz, ncol) each; the background's is background.aerosol, None or (tau, ssa, g) of (nbnd, nbg) each.
+    # The four wrappers below go through the _aer entries when either is given; a triple of None is given too: NULL pointers.
+    @staticmethod
+    def _rt_bg_aerosol(background):
+        aer = None if background is None else getattr(background, "aerosol", None)
+        return (None, None, None) if aer is None else tuple(aer)
+
+    @staticmethod
+    def _rt_triple(triple):
+        """a triple as rrx_raytracer_sw_aer takes it: a host array of its three device pointers, None for no triple"""
+        if triple[0] is None:
+            return None
+        return (ctypes.c_void_p * 3)(*[t.data_ptr() for t in triple])
+
+    def _rt_aerosol(self, aerosol, background, band_lims):
+        """(use the _aer entries, the grid's triple, the background's triple)"""
+        given = aerosol is not None or (background is not None and getattr(background, "aerosol", None) is not None)
+        grid = (None, None, None) if aerosol is None else tuple(aerosol)
+        bg = self._rt_bg_aerosol(background)
+        if (grid[0] is not None or bg[0] is not None) and band_lims is None:
+            raise ValueError("raytracer: an aerosol triple needs band_lims")
+        return given, grid, bg
 
     def rt_zero_counts_bg(self, nz, ncol, nbg):
         out = self.rt_zero_counts(nz, ncol)
@@ -763,14 +804,25 @@ class HipKernels:
 
     def rt_trace_counts_bg(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, k_null, seed,
                            photon0, nphotons, top_at_1=False, independent_column=False, cloud=None, band_lims=None, counts=None,
-                           max_events=None, phase=None, background=None, bg_profile=None):
-        """rt_trace_counts with a background: bg_profile is rt_bg_profile's for igpt (made when None). The counts gain RT_BG_COUNTS."""
+                           max_events=None, phase=None, background=None, bg_profile=None, aerosol=None):
+        """rt_trace_counts with a background: bg_profile is rt_bg_profile's for igpt (made when None). The counts gain RT_BG_COUNTS.
+        With aerosol= or background.aerosol it is rrx_rt_trace_counts_aer: k_null is then rt_k_null's with
+        aerosol= and bg_profile the 7-row profile."""
         dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
         knx, kny, knz = (int(k) for k in kn_grid)
         nbg, dzb = (0, None) if background is None else (len(background.dz), self._rt_bg_dz(background))
+        aer, aer_grid, aer_bg = self._rt_aerosol(aerosol, background, band_lims)
         if background is not None and bg_profile is None:
-            bg_profile = self.rt_bg_profile(background, igpt, band_lims)
+            bg_profile = self.rt_bg_profile(background, igpt, band_lims, aerosol=aer_bg if aer else None)
         counts = self.rt_zero_counts_bg(dims[2], dims[0]*dims[1], nbg) if counts is None else counts
+        if aer:
+            self._c("rt_trace_counts_aer", *dims, igpt, top_at_1, independent_column, tau, ssa,
+                    band_lims if (cloud is not None or aer_grid[0] is not None) else None, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0,
+                    azimuth, inc_dir, inc_dif, knx, kny, knz, k_null, int(seed) & 0xFFFFFFFFFFFFFFFF, photon0, nphotons,
+                    self.RT_MAX_EVENTS if max_events is None else max_events, *(counts[k] for k in self.RT_COUNTS), counts["n_capped"],
+                    *(counts[k] for k in self.RT_BG_COUNTS), *self._rt_table_args("rt_trace_counts_bg", phase, dims), nbg, dzb, bg_profile,
+                    *aer_grid)
+            return counts
         self._c("rt_trace_counts_bg", *dims, igpt, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0,
                 azimuth, inc_dir, inc_dif, knx, kny, knz, k_null, int(seed) & 0xFFFFFFFFFFFFFFFF, photon0, nphotons,
                 self.RT_MAX_EVENTS if max_events is None else max_events, *(counts[k] for k in self.RT_COUNTS), counts["n_capped"],
@@ -779,9 +831,10 @@ class HipKernels:
 
     def raytracer_sw_bg(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, photons_per_pixel, seed,
                         top_at_1=False, independent_column=False, cloud=None, band_lims=None, max_events=None, phase=None,
-                        background=None):
+                        background=None, aerosol=None):
         """raytracer_sw with a background. Beside its outputs: toa_up, tod_dn_dir, tod_dn_dif (ncol,) in W m-2 and bg_abs_dir,
-        bg_abs_dif (nbg,) in W m-3 of a domain-wide layer (zeros without a background)."""
+        bg_abs_dif (nbg,) in W m-3 of a domain-wide layer (zeros without a background). With aerosol= or
+        background.aerosol it is rrx_raytracer_sw_aer."""
         dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
         nz, ngpt, ncol = dims[2], dims[3], dims[0]*dims[1]
         knx, kny, knz = (int(k) for k in kn_grid)
@@ -792,39 +845,49 @@ class HipKernels:
         medium = self._rt_bg_medium(background)
         if background is not None and background.cloud is not None and band_lims is None:
             raise ValueError("raytracer: a background cloud triple needs band_lims")
-        lims_all = band_lims if (cloud is not None or (background is not None and background.cloud is not None)) else None
+        aer, aer_grid, aer_bg = self._rt_aerosol(aerosol, background, band_lims)
+        lims_all = band_lims if (cloud is not None or (background is not None and background.cloud is not None)
+                                 or aer_grid[0] is not None or aer_bg[0] is not None) else None
         out = {k: self.empty((ncol,)) for k in self.RT_COUNTS[:4]}
         out.update({k: self.empty((nz, ncol)) for k in self.RT_COUNTS[4:]})
         out.update({k: self.zeros((ncol,)) for k in self.RT_BG_COUNTS[:3]})
         out.update({k: self.zeros((medium[0],)) for k in self.RT_BG_COUNTS[3:]})
         n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        self._c("raytracer_sw_bg", *dims, top_at_1, independent_column, tau, ssa, lims_all, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth,
-                inc_dir, inc_dif, knx, kny, knz, photons_per_pixel, int(seed) & 0xFFFFFFFFFFFFFFFF,
+        self._c("raytracer_sw_aer" if aer else "raytracer_sw_bg", *dims, top_at_1, independent_column, tau, ssa, lims_all, ct, cw, cg, dx, dy,
+                dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, photons_per_pixel, int(seed) & 0xFFFFFFFFFFFFFFFF,
                 self.RT_MAX_EVENTS if max_events is None else max_events, *(out[k] for k in self.RT_COUNTS), n_capped,
-                *(out[k] if medium[0] else None for k in self.RT_BG_COUNTS), *self._rt_table_args("raytracer_sw_bg", phase, dims), *medium)
+                *(out[k] if medium[0] else None for k in self.RT_BG_COUNTS), *self._rt_table_args("raytracer_sw_bg", phase, dims), *medium,
+                *((self._rt_triple(aer_grid), self._rt_triple(aer_bg)) if aer else ()))
         out["n_capped"] = int(n_capped.item())
         return out
 
     def rt_bw_trace_counts_bg(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, kn_grid, k_null, camera, seed, ray0, nrays,
                               top_at_1=False, cloud=None, band_lims=None, counts=None, max_events=None, phase=None, background=None,
-                              bg_profile=None):
-        """rt_bw_trace_counts with a background: bg_profile is rt_bg_profile's for igpt (made when None)."""
+                              bg_profile=None, aerosol=None):
+        """rt_bw_trace_counts with a background: bg_profile is rt_bg_profile's for igpt (made when None). With aerosol= or
+        background.aerosol it is rrx_rt_bw_trace_counts_aer: k_null is then rt_k_null's with aerosol= and
+        bg_profile the 7-row profile."""
         dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
         knx, kny, knz = (int(k) for k in kn_grid)
         sensor = self._rt_sensor(camera)
         nbg, dzb = (0, None) if background is None else (len(background.dz), self._rt_bg_dz(background))
+        aer, aer_grid, aer_bg = self._rt_aerosol(aerosol, background, band_lims)
         if background is not None and bg_profile is None:
-            bg_profile = self.rt_bg_profile(background, igpt, band_lims)
+            bg_profile = self.rt_bg_profile(background, igpt, band_lims, aerosol=aer_bg if aer else None)
         counts = self.rt_bw_zero_counts(sensor[1]*sensor[2]) if counts is None else counts
-        self._c("rt_bw_trace_counts_bg", *dims, igpt, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, knx, kny, knz,
+        if aer and aer_grid[0] is not None:
+            lims = band_lims
+        self._c("rt_bw_trace_counts_aer" if aer else "rt_bw_trace_counts_bg", *dims, igpt, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz,
+                sfc_albedo, mu0, azimuth, knx, kny, knz,
                 k_null, *sensor, int(seed) & 0xFFFFFFFFFFFFFFFF, ray0, nrays, self.RT_MAX_EVENTS if max_events is None else max_events,
                 counts["counts"], counts["n_capped"], counts["n_clamped"], *self._rt_table_args("rt_bw_trace_counts_bg", phase, dims),
-                nbg, dzb, bg_profile)
+                nbg, dzb, bg_profile, *(aer_grid if aer else ()))
         return counts
 
     def raytracer_bw_bg(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
-                        top_at_1=False, cloud=None, band_lims=None, max_events=None, phase=None, background=None):
-        """raytracer_bw with a background: radiance (npy, npx) in W m-2 sr-1, n_capped and n_clamped (ints)."""
+                        top_at_1=False, cloud=None, band_lims=None, max_events=None, phase=None, background=None, aerosol=None):
+        """raytracer_bw with a background: radiance (npy, npx) in W m-2 sr-1, n_capped and n_clamped (ints). With aerosol= or
+        background.aerosol it is rrx_raytracer_bw_aer."""
         dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
         knx, kny, knz = (int(k) for k in kn_grid)
         inc_dir = np.ascontiguousarray(np.asarray(inc_dir, dtype=self.np_dtype).reshape(-1))
@@ -833,14 +896,18 @@ class HipKernels:
         medium = self._rt_bg_medium(background)
         if background is not None and background.cloud is not None and band_lims is None:
             raise ValueError("raytracer: a background cloud triple needs band_lims")
-        lims_all = band_lims if (cloud is not None or (background is not None and background.cloud is not None)) else None
+        aer, aer_grid, aer_bg = self._rt_aerosol(aerosol, background, band_lims)
+        lims_all = band_lims if (cloud is not None or (background is not None and background.cloud is not None)
+                                 or aer_grid[0] is not None or aer_bg[0] is not None) else None
         sensor = self._rt_sensor(camera)
         radiance = self.empty((sensor[2], sensor[1]))
         n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
         n_clamped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        self._c("raytracer_bw_bg", *dims, top_at_1, tau, ssa, lims_all, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz,
+        self._c("raytracer_bw_aer" if aer else "raytracer_bw_bg", *dims, top_at_1, tau, ssa, lims_all, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0,
+                azimuth, inc_dir, knx, kny, knz,
                 *sensor, rays_per_pixel, int(seed) & 0xFFFFFFFFFFFFFFFF, self.RT_MAX_EVENTS if max_events is None else max_events,
-                radiance, n_capped, n_clamped, *self._rt_table_args("raytracer_bw_bg", phase, dims), *medium)
+                radiance, n_capped, n_clamped, *self._rt_table_args("raytracer_bw_bg", phase, dims), *medium,
+                *((*aer_grid, *aer_bg) if aer else ()))
         return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
 
     def delta_scale_2str_k(self, tau, ssa, g):

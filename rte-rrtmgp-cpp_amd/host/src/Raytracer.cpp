@@ -40,7 +40,27 @@ unsigned long long Raytracer_gpu::trace_rays(
 
     if (has_bg) throw std::runtime_error("Raytracer_gpu::trace_rays: a background is set: call the form with the background's outputs");
     Array_gpu<unsigned long long,1> n_capped({1});
-    if (has_table)
+    const bool hazy = has_aer && aer_tau.size() > 0;
+    if (hazy && (aer_tau.dim(1) != ncol || aer_tau.dim(2) != nz || aer_tau.dim(3) != nbnd))
+        throw std::runtime_error("Raytracer_gpu::trace_rays: the aerosol arrays are not (nx ny, nz, nbnd)");
+    const Float* none = nullptr;
+    Float* no_out = nullptr;
+    if (has_aer && bg_aer_tau.size() > 0) throw std::runtime_error("Raytracer_gpu::trace_rays: a background aerosol is set without a background");
+    // (rrx_raytracer_sw_aer takes each triple as a host array of its three device pointers)
+    const Float* const grid3[3] = {hazy ? aer_tau.ptr() : none, hazy ? aer_ssa.ptr() : none, hazy ? aer_g.ptr() : none};
+    const Float* const* no_triple = nullptr;
+    if (has_aer)
+        RRX_CALL(rrx_raytracer_sw_aer, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
+                 tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
+                 cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
+                 dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), inc_dif.ptr(), knx, kny, knz,
+                 photons_per_pixel, seed, max_events,
+                 sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr(),
+                 no_out, no_out, no_out, no_out, no_out,
+                 has_table ? mu.dim(1) : 0, has_table ? phase.dim(2) : 0, re0, dre, has_table ? mu.ptr() : none, has_table ? phase.ptr() : none,
+                 has_table ? cdf.ptr() : none, has_table ? cld_re.ptr() : none,
+                 0, none, none, none, none, none, none, grid3, no_triple);
+    else if (has_table)
         RRX_CALL(rrx_raytracer_sw_phase, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
                  tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
                  cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
@@ -105,17 +125,38 @@ unsigned long long Raytracer_gpu::trace_rays(
 
     Array_gpu<unsigned long long,1> n_capped({1});
     const Float* none = nullptr;
-    RRX_CALL(rrx_raytracer_sw_bg, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
-             tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
-             cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
-             dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), inc_dif.ptr(), knx, kny, knz,
-             photons_per_pixel, seed, max_events,
-             sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr(),
-             toa_up.ptr(), tod_dn_dir.ptr(), tod_dn_dif.ptr(), bg_abs_dir.ptr(), bg_abs_dif.ptr(),
-             has_table ? mu.dim(1) : 0, has_table ? phase.dim(2) : 0, re0, dre, has_table ? mu.ptr() : none, has_table ? phase.ptr() : none,
-             has_table ? cdf.ptr() : none, has_table ? cld_re.ptr() : none,
-             nbg, dz_bg.ptr(), bg_tau.ptr(), bg_ssa.ptr(), bg_cloudy ? bg_cld_tau.ptr() : none, bg_cloudy ? bg_cld_ssa.ptr() : none,
-             bg_cloudy ? bg_cld_g.ptr() : none);
+    const bool hazy = has_aer && aer_tau.size() > 0;
+    if (hazy && (aer_tau.dim(1) != ncol || aer_tau.dim(2) != nz || aer_tau.dim(3) != nbnd))
+        throw std::runtime_error("Raytracer_gpu::trace_rays: the aerosol arrays are not (nx ny, nz, nbnd)");
+    const bool bg_hazy = has_aer && bg_aer_tau.size() > 0;
+    if (bg_hazy && (bg_aer_tau.dim(1) != nbg || bg_aer_tau.dim(2) != nbnd))
+        throw std::runtime_error("Raytracer_gpu::trace_rays: the background's aerosol arrays are not (nbg, nbnd)");
+    const Float* const grid3[3] = {hazy ? aer_tau.ptr() : none, hazy ? aer_ssa.ptr() : none, hazy ? aer_g.ptr() : none};
+    const Float* const aloft3[3] = {bg_hazy ? bg_aer_tau.ptr() : none, bg_hazy ? bg_aer_ssa.ptr() : none, bg_hazy ? bg_aer_g.ptr() : none};
+    if (has_aer)
+        RRX_CALL(rrx_raytracer_sw_aer, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
+                 tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
+                 cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
+                 dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), inc_dif.ptr(), knx, kny, knz,
+                 photons_per_pixel, seed, max_events,
+                 sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr(),
+                 toa_up.ptr(), tod_dn_dir.ptr(), tod_dn_dif.ptr(), bg_abs_dir.ptr(), bg_abs_dif.ptr(),
+                 has_table ? mu.dim(1) : 0, has_table ? phase.dim(2) : 0, re0, dre, has_table ? mu.ptr() : none, has_table ? phase.ptr() : none,
+                 has_table ? cdf.ptr() : none, has_table ? cld_re.ptr() : none,
+                 nbg, dz_bg.ptr(), bg_tau.ptr(), bg_ssa.ptr(), bg_cloudy ? bg_cld_tau.ptr() : none, bg_cloudy ? bg_cld_ssa.ptr() : none,
+                 bg_cloudy ? bg_cld_g.ptr() : none, grid3, aloft3);
+    else
+        RRX_CALL(rrx_raytracer_sw_bg, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
+                 tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
+                 cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
+                 dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), inc_dif.ptr(), knx, kny, knz,
+                 photons_per_pixel, seed, max_events,
+                 sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr(),
+                 toa_up.ptr(), tod_dn_dir.ptr(), tod_dn_dif.ptr(), bg_abs_dir.ptr(), bg_abs_dif.ptr(),
+                 has_table ? mu.dim(1) : 0, has_table ? phase.dim(2) : 0, re0, dre, has_table ? mu.ptr() : none, has_table ? phase.ptr() : none,
+                 has_table ? cdf.ptr() : none, has_table ? cld_re.ptr() : none,
+                 nbg, dz_bg.ptr(), bg_tau.ptr(), bg_ssa.ptr(), bg_cloudy ? bg_cld_tau.ptr() : none, bg_cloudy ? bg_cld_ssa.ptr() : none,
+                 bg_cloudy ? bg_cld_g.ptr() : none);
     return n_capped({1});
 }
 
@@ -131,6 +172,22 @@ void Raytracer_gpu::set_background(const Array<Float,1>& dz_in, const Array_gpu<
         throw std::runtime_error("Raytracer_gpu::set_background: the background's cloud arrays are all empty or all (nbg, nbnd)");
     dz_bg = dz_in; bg_tau = tau_in; bg_ssa = ssa_in; bg_cld_tau = ctau_in; bg_cld_ssa = cssa_in; bg_cld_g = cg_in;
     has_bg = true;
+}
+
+
+void Raytracer_gpu::set_aerosol(const Array_gpu<Float,3>& tau_in, const Array_gpu<Float,3>& ssa_in, const Array_gpu<Float,3>& g_in,
+                        const Array_gpu<Float,2>& btau_in, const Array_gpu<Float,2>& bssa_in, const Array_gpu<Float,2>& bg_in)
+{
+    const bool grid = tau_in.size() > 0, aloft = btau_in.size() > 0;
+    if (grid ? (ssa_in.get_dims() != tau_in.get_dims() || g_in.get_dims() != tau_in.get_dims()) : (ssa_in.size() > 0 || g_in.size() > 0))
+        throw std::runtime_error("Raytracer_gpu::set_aerosol: the aerosol arrays are all empty or all (nx ny, nz, nbnd)");
+    if (aloft ? (bssa_in.get_dims() != btau_in.get_dims() || bg_in.get_dims() != btau_in.get_dims()) : (bssa_in.size() > 0 || bg_in.size() > 0))
+        throw std::runtime_error("Raytracer_gpu::set_aerosol: the background's aerosol arrays are all empty or all (nbg, nbnd)");
+    if (aloft && !has_bg) throw std::runtime_error("Raytracer_gpu::set_aerosol: a background aerosol needs a background (set_background)");
+    if (aloft && btau_in.dim(1) != dz_bg.size())
+        throw std::runtime_error("Raytracer_gpu::set_aerosol: the background's aerosol arrays are not (nbg, nbnd)");
+    aer_tau = tau_in; aer_ssa = ssa_in; aer_g = g_in; bg_aer_tau = btau_in; bg_aer_ssa = bssa_in; bg_aer_g = bg_in;
+    has_aer = grid || aloft;
 }
 
 void Raytracer_gpu::set_phase_table(const Array_gpu<Float,1>& mu_in, const Array_gpu<Float,3>& phase_in, const Array_gpu<Float,3>& cdf_in,

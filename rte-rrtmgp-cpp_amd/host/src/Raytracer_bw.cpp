@@ -38,7 +38,34 @@ unsigned long long Raytracer_bw_gpu::trace_rays_bw(
     if (has_table && (cld_re.dim(1) != ncol || cld_re.dim(2) != nz || phase.dim(3) != nbnd))
         throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: the phase table's cld_re is not (nx ny, nz) or its tables are not (nmu, nre, nbnd)");
     Array_gpu<unsigned long long,1> tallies({2});
-    if (has_bg)
+    const bool hazy = has_aer && aer_tau.size() > 0;
+    if (hazy && (aer_tau.dim(1) != ncol || aer_tau.dim(2) != nz || aer_tau.dim(3) != nbnd))
+        throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: the aerosol arrays are not (nx ny, nz, nbnd)");
+    if (has_aer)
+    {
+        const bool bg_cloudy = has_bg && bg_cld_tau.size() > 0, bg_hazy = has_bg && bg_aer_tau.size() > 0;
+        const int nbg = has_bg ? dz_bg.size() : 0;
+        if (has_bg && (bg_tau.dim(2) != ngpt || (bg_cloudy && bg_cld_tau.dim(2) != nbnd)))
+            throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: the background's arrays are not (nbg, ngpt) and (nbg, nbnd)");
+        if (bg_hazy && (bg_aer_tau.dim(1) != nbg || bg_aer_tau.dim(2) != nbnd))
+            throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: the background's aerosol arrays are not (nbg, nbnd)");
+        if (!has_bg && bg_aer_tau.size() > 0)
+            throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: a background aerosol is set without a background");
+        const Float* none = nullptr;
+        RRX_CALL(rrx_raytracer_bw_aer, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1),
+                 tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
+                 cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
+                 dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), knx, kny, knz,
+                 sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers, rays_per_pixel, seed, max_events,
+                 radiance.ptr(), tallies.ptr(), tallies.ptr() + 1,
+                 has_table ? mu.dim(1) : 0, has_table ? phase.dim(2) : 0, re0, dre, has_table ? mu.ptr() : none, has_table ? phase.ptr() : none,
+                 has_table ? cdf.ptr() : none, has_table ? cld_re.ptr() : none,
+                 nbg, has_bg ? dz_bg.ptr() : none, has_bg ? bg_tau.ptr() : none, has_bg ? bg_ssa.ptr() : none,
+                 bg_cloudy ? bg_cld_tau.ptr() : none, bg_cloudy ? bg_cld_ssa.ptr() : none, bg_cloudy ? bg_cld_g.ptr() : none,
+                 hazy ? aer_tau.ptr() : none, hazy ? aer_ssa.ptr() : none, hazy ? aer_g.ptr() : none,
+                 bg_hazy ? bg_aer_tau.ptr() : none, bg_hazy ? bg_aer_ssa.ptr() : none, bg_hazy ? bg_aer_g.ptr() : none);
+    }
+    else if (has_bg)
     {
         const bool bg_cloudy = bg_cld_tau.size() > 0;
         if (bg_tau.dim(2) != ngpt || (bg_cloudy && bg_cld_tau.dim(2) != nbnd))
@@ -86,6 +113,22 @@ void Raytracer_bw_gpu::set_background(const Array<Float,1>& dz_in, const Array_g
         throw std::runtime_error("Raytracer_bw_gpu::set_background: the background's cloud arrays are all empty or all (nbg, nbnd)");
     dz_bg = dz_in; bg_tau = tau_in; bg_ssa = ssa_in; bg_cld_tau = ctau_in; bg_cld_ssa = cssa_in; bg_cld_g = cg_in;
     has_bg = true;
+}
+
+
+void Raytracer_bw_gpu::set_aerosol(const Array_gpu<Float,3>& tau_in, const Array_gpu<Float,3>& ssa_in, const Array_gpu<Float,3>& g_in,
+                        const Array_gpu<Float,2>& btau_in, const Array_gpu<Float,2>& bssa_in, const Array_gpu<Float,2>& bg_in)
+{
+    const bool grid = tau_in.size() > 0, aloft = btau_in.size() > 0;
+    if (grid ? (ssa_in.get_dims() != tau_in.get_dims() || g_in.get_dims() != tau_in.get_dims()) : (ssa_in.size() > 0 || g_in.size() > 0))
+        throw std::runtime_error("Raytracer_bw_gpu::set_aerosol: the aerosol arrays are all empty or all (nx ny, nz, nbnd)");
+    if (aloft ? (bssa_in.get_dims() != btau_in.get_dims() || bg_in.get_dims() != btau_in.get_dims()) : (bssa_in.size() > 0 || bg_in.size() > 0))
+        throw std::runtime_error("Raytracer_bw_gpu::set_aerosol: the background's aerosol arrays are all empty or all (nbg, nbnd)");
+    if (aloft && !has_bg) throw std::runtime_error("Raytracer_bw_gpu::set_aerosol: a background aerosol needs a background (set_background)");
+    if (aloft && btau_in.dim(1) != dz_bg.size())
+        throw std::runtime_error("Raytracer_bw_gpu::set_aerosol: the background's aerosol arrays are not (nbg, nbnd)");
+    aer_tau = tau_in; aer_ssa = ssa_in; aer_g = g_in; bg_aer_tau = btau_in; bg_aer_ssa = bssa_in; bg_aer_g = bg_in;
+    has_aer = grid || aloft;
 }
 
 void Raytracer_bw_gpu::set_phase_table(const Array_gpu<Float,1>& mu_in, const Array_gpu<Float,3>& phase_in, const Array_gpu<Float,3>& cdf_in,

@@ -205,14 +205,17 @@ int rrx_cxx_driver_fluxes(void* h, const Float** ptrs)
 // rrx_cxx_trace_rays_bg: the same after Raytracer_gpu::set_background(dz_bg (nbg) on the HOST, bg_tau, bg_ssa (nbg, ngpt), bg_cld_* (nbg, nbnd)
 // or all NULL); out5: device arrays toa_up, tod_dn_dir, tod_dn_dif (ncol), bg_abs_dir, bg_abs_dif (nbg). nbg = 0: no background is set
 // and out5 is not written.
-int rrx_cxx_trace_rays_bg(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+// rrx_cxx_trace_rays_aer: the same after Raytracer_gpu::set_aerosol(aer_* (ncol, nz, nbnd) or all NULL, bg_aer_* (nbg, nbnd) or all NULL), called
+// when any of the six is given; a background aerosol with nbg = 0 is handed over as one layer, so that the class refuses it.
+int rrx_cxx_trace_rays_aer(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
         const int top_at_1, const int independent_column, const Float* tau, const Float* ssa, const int* band_lims_gpt,
         const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
         const Float* inc_dir, const Float* inc_dif, const int knx, const int kny, const int knz, const long long photons_per_pixel,
         const unsigned long long seed, const int max_events, Float* const* out6, unsigned long long* n_capped, Float* const* out5,
         const int nmu, const int nre, const Float re0, const Float dre, const Float* mu, const Float* phase, const Float* cdf, const Float* cld_re,
         const int nbg, const Float* dz_bg, const Float* bg_tau, const Float* bg_ssa, const Float* bg_cld_tau, const Float* bg_cld_ssa,
-        const Float* bg_cld_g, void* stream)
+        const Float* bg_cld_g, const Float* aer_tau, const Float* aer_ssa, const Float* aer_g, const Float* bg_aer_tau, const Float* bg_aer_ssa,
+        const Float* bg_aer_g, void* stream)
 {
     return guarded([&]
     {
@@ -230,12 +233,20 @@ int rrx_cxx_trace_rays_bg(const int nx, const int ny, const int nz, const int ng
             Raytracer_gpu raytracer;
             if (mu != nullptr)
                 raytracer.set_phase_table(view1(mu, nmu), view3(phase, nmu, nre, nbnd), view3(cdf, nmu, nre, nbnd), re0, dre, view2(cld_re, ncol, nz));
+            const bool any_aer = aer_tau || aer_ssa || aer_g || bg_aer_tau || bg_aer_ssa || bg_aer_g;
+            const int nb = nbg > 0 ? nbg : 1;
             if (nbg > 0)
             {
                 Array<Float,1> h_dz({nbg});
                 for (int b=1; b<=nbg; ++b) h_dz({b}) = dz_bg[b-1];
                 raytracer.set_background(h_dz, bview(bg_tau, nbg, ngpt), bview(bg_ssa, nbg, ngpt), bview(bg_cld_tau, nbg, nbnd),
                                          bview(bg_cld_ssa, nbg, nbnd), bview(bg_cld_g, nbg, nbnd));
+            }
+            if (any_aer)
+                raytracer.set_aerosol(view3(aer_tau, ncol, nz, nbnd), view3(aer_ssa, ncol, nz, nbnd), view3(aer_g, ncol, nz, nbnd),
+                                      bview(bg_aer_tau, nb, nbnd), bview(bg_aer_ssa, nb, nbnd), bview(bg_aer_g, nb, nbnd));
+            if (nbg > 0)
+            {
                 Array_gpu<Float,1> b0 = view1(out5[0], ncol), b1 = view1(out5[1], ncol), b2 = view1(out5[2], ncol);
                 Array_gpu<Float,1> b3 = view1(out5[3], nbg), b4 = view1(out5[4], nbg);
                 *n_capped = raytracer.trace_rays(nx, ny, nz, dx, dy, dz, top_at_1 != 0, independent_column != 0,
@@ -252,6 +263,21 @@ int rrx_cxx_trace_rays_bg(const int nx, const int ny, const int nz, const int ng
         catch (...) { rrx_host::set_stream(before); throw; }
         rrx_host::set_stream(before);
     });
+}
+
+int rrx_cxx_trace_rays_bg(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+        const int top_at_1, const int independent_column, const Float* tau, const Float* ssa, const int* band_lims_gpt,
+        const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
+        const Float* inc_dir, const Float* inc_dif, const int knx, const int kny, const int knz, const long long photons_per_pixel,
+        const unsigned long long seed, const int max_events, Float* const* out6, unsigned long long* n_capped, Float* const* out5,
+        const int nmu, const int nre, const Float re0, const Float dre, const Float* mu, const Float* phase, const Float* cdf, const Float* cld_re,
+        const int nbg, const Float* dz_bg, const Float* bg_tau, const Float* bg_ssa, const Float* bg_cld_tau, const Float* bg_cld_ssa,
+        const Float* bg_cld_g, void* stream)
+{
+    return rrx_cxx_trace_rays_aer(nx, ny, nz, ngpt, nbnd, dx, dy, dz, top_at_1, independent_column, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g,
+                                  sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, photons_per_pixel, seed, max_events, out6, n_capped,
+                                  out5, nmu, nre, re0, dre, mu, phase, cdf, cld_re, nbg, dz_bg, bg_tau, bg_ssa, bg_cld_tau, bg_cld_ssa, bg_cld_g,
+                                  nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int rrx_cxx_trace_rays_phase(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
@@ -328,7 +354,8 @@ int rrx_cxx_trace_rays_bw_phase(const int nx, const int ny, const int nz, const 
 }
 
 // rrx_cxx_trace_rays_bw_bg: rrx_cxx_trace_rays_bw_phase after Raytracer_bw_gpu::set_background, as rrx_cxx_trace_rays_bg; nbg = 0: no background
-int rrx_cxx_trace_rays_bw_bg(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+// rrx_cxx_trace_rays_bw_aer: the same after Raytracer_bw_gpu::set_aerosol, as rrx_cxx_trace_rays_aer
+int rrx_cxx_trace_rays_bw_aer(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
         const int top_at_1, const Float* tau, const Float* ssa, const int* band_lims_gpt,
         const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
         const Float* inc_dir, const int knx, const int kny, const int knz, const int sensor_type, const int npx, const int npy, const Float fov,
@@ -336,7 +363,8 @@ int rrx_cxx_trace_rays_bw_bg(const int nx, const int ny, const int nz, const int
         unsigned long long* n_capped, unsigned long long* n_clamped,
         const int nmu, const int nre, const Float re0, const Float dre, const Float* mu, const Float* phase, const Float* cdf, const Float* cld_re,
         const int nbg, const Float* dz_bg, const Float* bg_tau, const Float* bg_ssa, const Float* bg_cld_tau, const Float* bg_cld_ssa,
-        const Float* bg_cld_g, void* stream)
+        const Float* bg_cld_g, const Float* aer_tau, const Float* aer_ssa, const Float* aer_g, const Float* bg_aer_tau, const Float* bg_aer_ssa,
+        const Float* bg_aer_g, void* stream)
 {
     return guarded([&]
     {
@@ -363,6 +391,13 @@ int rrx_cxx_trace_rays_bw_bg(const int nx, const int ny, const int nz, const int
                 raytracer.set_background(h_dz, bview(bg_tau, nbg, ngpt), bview(bg_ssa, nbg, ngpt), bview(bg_cld_tau, nbg, nbnd),
                                          bview(bg_cld_ssa, nbg, nbnd), bview(bg_cld_g, nbg, nbnd));
             }
+            if (aer_tau || aer_ssa || aer_g || bg_aer_tau || bg_aer_ssa || bg_aer_g)
+            {
+                auto bview = [](const Float* p, int a, int b) { return p ? Array_gpu<Float,2>(const_cast<Float*>(p), {a, b}) : Array_gpu<Float,2>(); };
+                const int nb = nbg > 0 ? nbg : 1;
+                raytracer.set_aerosol(view3(aer_tau, ncol, nz, nbnd), view3(aer_ssa, ncol, nz, nbnd), view3(aer_g, ncol, nz, nbnd),
+                                      bview(bg_aer_tau, nb, nbnd), bview(bg_aer_ssa, nb, nbnd), bview(bg_aer_g, nb, nbnd));
+            }
             *n_capped = raytracer.trace_rays_bw(nx, ny, nz, dx, dy, dz, top_at_1 != 0,
                     view3(tau, ncol, nz, ngpt), view3(ssa, ncol, nz, ngpt), Array_gpu<int,2>(const_cast<int*>(band_lims_gpt), {2, nbnd}),
                     view3(cld_tau, ncol, nz, nbnd), view3(cld_ssa, ncol, nz, nbnd), view3(cld_g, ncol, nz, nbnd), view1(sfc_albedo, ncol),
@@ -371,6 +406,22 @@ int rrx_cxx_trace_rays_bw_bg(const int nx, const int ny, const int nz, const int
         catch (...) { rrx_host::set_stream(before); throw; }
         rrx_host::set_stream(before);
     });
+}
+
+int rrx_cxx_trace_rays_bw_bg(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+        const int top_at_1, const Float* tau, const Float* ssa, const int* band_lims_gpt,
+        const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
+        const Float* inc_dir, const int knx, const int kny, const int knz, const int sensor_type, const int npx, const int npy, const Float fov,
+        const Float* sensor, const long long rays_per_pixel, const unsigned long long seed, const int max_events, Float* radiance,
+        unsigned long long* n_capped, unsigned long long* n_clamped,
+        const int nmu, const int nre, const Float re0, const Float dre, const Float* mu, const Float* phase, const Float* cdf, const Float* cld_re,
+        const int nbg, const Float* dz_bg, const Float* bg_tau, const Float* bg_ssa, const Float* bg_cld_tau, const Float* bg_cld_ssa,
+        const Float* bg_cld_g, void* stream)
+{
+    return rrx_cxx_trace_rays_bw_aer(nx, ny, nz, ngpt, nbnd, dx, dy, dz, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, sfc_albedo, mu0,
+                                     azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, rays_per_pixel, seed, max_events, radiance,
+                                     n_capped, n_clamped, nmu, nre, re0, dre, mu, phase, cdf, cld_re, nbg, dz_bg, bg_tau, bg_ssa, bg_cld_tau,
+                                     bg_cld_ssa, bg_cld_g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int rrx_cxx_trace_rays_bw(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,

@@ -183,7 +183,8 @@ def solve_sw(be, kd, atm, col_dry=None, cloud_lut=None, delta_cloud=False, do_br
 
 
 def raytrace_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, photons_per_pixel, seed, cloud_lut=None, kn_grid=None,
-                independent_column=False, sfc_albedo=None, max_events=None, phase_table=None, n_domain=None, z_lev=None):
+                independent_column=False, sfc_albedo=None, max_events=None, phase_table=None, n_domain=None, z_lev=None,
+                aerosol_lut=None):
     """3-D shortwave surface / top fluxes and absorption from the forward Monte Carlo ray tracer (rrx_raytracer_sw).
 
     The atmosphere's columns are the pixels of an nx x ny domain (column = ix + nx iy) of cells dx x dy x dz metres, periodic in x
@@ -197,41 +198,55 @@ def raytrace_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, photons_per_pixel, 
     n_domain < atm.nlay with z_lev (nlay+1,), the heights of the atmosphere's levels in metres in array order: the
     lowest n_domain layers are the grid (of thickness dz) and the layers above are a horizontally uniform background up to TOA, taken
     from column 0, with the thicknesses of z_lev; kn_grid then divides (nx, ny, n_domain) and inc_dir is incident at TOA.
+    aerosol_lut: the chain's band aerosol optics be.aerosol_optics(aerosol_lut, aermr01..11, rh, p_lev), not
+    delta-scaled (as the cloud is not), are a third scattering species of the tracer (rrx_raytracer_sw_aer), Henyey-Greenstein with
+    its own asymmetry parameter; with n_domain the layers above the grid carry column 0's aerosol.
     Returns sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up (ncol,) in W m-2, abs_dir, abs_dif (nlay, ncol) in W m-3 and n_capped; with
     n_domain also toa_up, tod_dn_dir, tod_dn_dif (ncol,) in W m-2 and bg_abs_dir, bg_abs_dif (nbg,) in W m-3 of a domain-wide layer,
     counted upward from the domain top (abs_dir, abs_dif are then (n_domain, ncol), and tod_up is the flux through the domain top)."""
     if n_domain is not None and kn_grid is None:
         kn_grid = (nx, ny, int(n_domain))
-    tau, ssa, cld, sfc_albedo, mu0, inc_dir, kn_grid = _raytracer_inputs("raytrace_sw", be, kd_sw, atm, nx, ny, cloud_lut, kn_grid, sfc_albedo)
+    tau, ssa, cld, sfc_albedo, mu0, inc_dir, kn_grid, aer = _raytracer_inputs("raytrace_sw", be, kd_sw, atm, nx, ny, cloud_lut, kn_grid,
+                                                                              sfc_albedo, aerosol_lut)
     if n_domain is not None:
-        tau, ssa, cld, rel, background = _raytracer_split("raytrace_sw", be, atm, tau, ssa, cld, n_domain, z_lev)
+        tau, ssa, cld, rel, background, aer = _raytracer_split("raytrace_sw", be, atm, tau, ssa, cld, n_domain, z_lev, aer)
         phase = _raytracer_phase("raytrace_sw", atm, cloud_lut, phase_table, rel)
         return be.raytracer_sw_bg(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, np.zeros_like(inc_dir), kn_grid,
                                   photons_per_pixel, seed, top_at_1=atm.top_at_1, independent_column=independent_column, cloud=cld,
-                                  band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase, background=background)
+                                  band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase, background=background, aerosol=aer)
     phase = _raytracer_phase("raytrace_sw", atm, cloud_lut, phase_table)
+    if aer is not None:
+        r = be.raytracer_sw_bg(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, np.zeros_like(inc_dir), kn_grid,
+                               photons_per_pixel, seed, top_at_1=atm.top_at_1, independent_column=independent_column, cloud=cld,
+                               band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase, aerosol=aer)
+        return {k: v for k, v in r.items() if k not in be.RT_BG_COUNTS}
     return be.raytracer_sw(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, np.zeros_like(inc_dir), kn_grid,
                            photons_per_pixel, seed, top_at_1=atm.top_at_1, independent_column=independent_column, cloud=cld,
                            band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase)
 
 
 def render_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, camera, rays_per_pixel, seed, cloud_lut=None, kn_grid=None,
-              sfc_albedo=None, max_events=None, phase_table=None, n_domain=None, z_lev=None):
+              sfc_albedo=None, max_events=None, phase_table=None, n_domain=None, z_lev=None, aerosol_lut=None):
     """Shortwave radiances for a virtual camera or a flux sensor from the backward Monte Carlo ray tracer (rrx_raytracer_bw, DESIGN
     4.15): the twin of raytrace_sw, on the same domain, sun, optics and albedo, with the same checks. camera: camera.perspective /
     fisheye / orthographic / flux_sensor. Returns radiance (npy, npx) in W m-2 sr-1 (scattered and reflected sunlight; the sun's
-    disk is not imaged), n_capped and n_clamped. phase_table, n_domain, z_lev: as in raytrace_sw; with a background the camera may
+    disk is not imaged), n_capped and n_clamped. phase_table, n_domain, z_lev, aerosol_lut: as in raytrace_sw; with a background the camera may
     sit inside it, and the orthographic and the downward flux sensor start at clamp(position.z, domain top, TOA)."""
     if n_domain is not None and kn_grid is None:
         kn_grid = (nx, ny, int(n_domain))
-    tau, ssa, cld, sfc_albedo, mu0, inc_dir, kn_grid = _raytracer_inputs("render_sw", be, kd_sw, atm, nx, ny, cloud_lut, kn_grid, sfc_albedo)
+    tau, ssa, cld, sfc_albedo, mu0, inc_dir, kn_grid, aer = _raytracer_inputs("render_sw", be, kd_sw, atm, nx, ny, cloud_lut, kn_grid,
+                                                                              sfc_albedo, aerosol_lut)
     if n_domain is not None:
-        tau, ssa, cld, rel, background = _raytracer_split("render_sw", be, atm, tau, ssa, cld, n_domain, z_lev)
+        tau, ssa, cld, rel, background, aer = _raytracer_split("render_sw", be, atm, tau, ssa, cld, n_domain, z_lev, aer)
         phase = _raytracer_phase("render_sw", atm, cloud_lut, phase_table, rel)
         return be.raytracer_bw_bg(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
                                   top_at_1=atm.top_at_1, cloud=cld, band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase,
-                                  background=background)
+                                  background=background, aerosol=aer)
     phase = _raytracer_phase("render_sw", atm, cloud_lut, phase_table)
+    if aer is not None:
+        return be.raytracer_bw_bg(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
+                                  top_at_1=atm.top_at_1, cloud=cld, band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase,
+                                  aerosol=aer)
     return be.raytracer_bw(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
                            top_at_1=atm.top_at_1, cloud=cld, band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase)
 
@@ -248,14 +263,14 @@ def _raytracer_phase(who, atm, cloud_lut, phase_table, rel=None):
 
 class Background:
     """The background atmosphere of the ray tracers, counted upward from the domain top: dz (nbg,) on the host, tau, ssa (ngpt, nbg)
-    and cloud, None or (tau, ssa, g) of (nbnd, nbg) each, on the device."""
-    def __init__(self, dz, tau, ssa, cloud=None):
-        self.dz, self.tau, self.ssa, self.cloud = dz, tau, ssa, cloud
+    and cloud and aerosol, None or (tau, ssa, g) of (nbnd, nbg) each, on the device."""
+    def __init__(self, dz, tau, ssa, cloud=None, aerosol=None):
+        self.dz, self.tau, self.ssa, self.cloud, self.aerosol = dz, tau, ssa, cloud, aerosol
 
 
-def _raytracer_split(who, be, atm, tau, ssa, cld, n_domain, z_lev):
+def _raytracer_split(who, be, atm, tau, ssa, cld, n_domain, z_lev, aer=None):
     """The lowest n_domain layers as the grid's arrays (in the atmosphere's layer order) and the layers above as a Background from
-    column 0; also the grid's part of atm.rel."""
+    column 0; also the grid's part of atm.rel. The aerosol triple is cut like the cloud's."""
     nlay, n_domain = atm.nlay, int(n_domain)
     if not 1 <= n_domain < nlay:
         raise ValueError(f"{who}: n_domain must be in [1, nlay = {nlay})")
@@ -271,15 +286,18 @@ def _raytracer_split(who, be, atm, tau, ssa, cld, n_domain, z_lev):
     if not np.all(dz_bg > 0):
         raise ValueError(f"{who}: z_lev must be strictly monotonic")
     column0 = lambda t: t[:, above, 0].contiguous()
-    background = Background(dz_bg, column0(tau), column0(ssa), None if cld is None else tuple(column0(c) for c in cld))
+    background = Background(dz_bg, column0(tau), column0(ssa), None if cld is None else tuple(column0(c) for c in cld),
+                            None if aer is None else tuple(column0(c) for c in aer))
     part = lambda t: t[:, grid, :].contiguous()
     rel = atm.rel[grid, :].contiguous() if getattr(atm, "rel", None) is not None else None
-    return part(tau), part(ssa), None if cld is None else tuple(part(c) for c in cld), rel, background
+    return (part(tau), part(ssa), None if cld is None else tuple(part(c) for c in cld), rel, background,
+            None if aer is None else tuple(part(c) for c in aer))
 
 
-def _raytracer_inputs(who, be, kd_sw, atm, nx, ny, cloud_lut, kn_grid, sfc_albedo):
+def _raytracer_inputs(who, be, kd_sw, atm, nx, ny, cloud_lut, kn_grid, sfc_albedo, aerosol_lut=None):
     """What both ray tracers take from the chain: the clear g-point tau, ssa, the band cloud triple (or None), the albedo (ncol,),
-    the one mu0, inc_dir (ngpt,) on the host and the k_null grid; one sun and one albedo are checked."""
+    the one mu0, inc_dir (ngpt,) on the host, the k_null grid and the band aerosol triple (or None); one sun and one albedo are
+    checked."""
     ncol, nlay, ngpt = atm.ncol, atm.nlay, kd_sw.ngpt
     if ncol != nx*ny:
         raise ValueError(f"{who}: ncol = {ncol} is not nx ny = {nx}*{ny}")
@@ -303,7 +321,10 @@ def _raytracer_inputs(who, be, kd_sw, atm, nx, ny, cloud_lut, kn_grid, sfc_albed
 
     F = be.np_dtype.type
     inc_dir = (be.to_numpy(kd_sw.solar_source).astype(be.np_dtype) * F(tsi[0])) * F(mu0[0])
-    return tau, ssa, cld, sfc_albedo, float(mu0[0]), inc_dir, kn_grid
+    aer = None
+    if aerosol_lut is not None:
+        aer = tuple(be.aerosol_optics(aerosol_lut, [atm.aermr["aermr%02d" % i] for i in range(1, 12)], atm.rh, atm.p_lev))
+    return tau, ssa, cld, sfc_albedo, float(mu0[0]), inc_dir, kn_grid, aer
 
 
 _STEP_ATMOSPHERE = None
