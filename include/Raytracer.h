@@ -71,6 +71,31 @@ class Raytracer_gpu
         void clear_aerosol() { has_aer = false; aer_tau = Array_gpu<Float,3>(); aer_ssa = Array_gpu<Float,3>(); aer_g = Array_gpu<Float,3>();
                                bg_aer_tau = Array_gpu<Float,2>(); bg_aer_ssa = Array_gpu<Float,2>(); bg_aer_g = Array_gpu<Float,2>(); }
 
+        // All g-points in one launch, photons dealt per g-point (rrx_raytracer_sw_spectral): trace_rays with
+        // photons_per_pixel_gpt (ngpt) on the host, the photons per pixel of every g-point, in place of photons_per_pixel. It
+        // honours the phase table, the background and the aerosol that are set; the five background outputs are filled with a
+        // background set and not touched without one (they may then be empty). ngpt <= 1024.
+        unsigned long long trace_rays_spectral(
+                const int nx, const int ny, const int nz,
+                const Float dx, const Float dy, const Float dz,
+                const bool top_at_1, const bool independent_column,
+                const Array_gpu<Float,3>& tau, const Array_gpu<Float,3>& ssa,
+                const Array_gpu<int,2>& band_lims_gpt,
+                const Array_gpu<Float,3>& cld_tau, const Array_gpu<Float,3>& cld_ssa, const Array_gpu<Float,3>& cld_g,
+                const Array_gpu<Float,1>& sfc_albedo,
+                const Float mu0, const Float azimuth,
+                const Array<Float,1>& inc_dir, const Array<Float,1>& inc_dif,
+                const int knx, const int kny, const int knz,
+                const Array<long long,1>& photons_per_pixel_gpt, const unsigned long long seed, const int max_events,
+                Array_gpu<Float,1>& sfc_dn_dir, Array_gpu<Float,1>& sfc_dn_dif, Array_gpu<Float,1>& sfc_up, Array_gpu<Float,1>& tod_up,
+                Array_gpu<Float,2>& abs_dir, Array_gpu<Float,2>& abs_dif,
+                Array_gpu<Float,1>& toa_up, Array_gpu<Float,1>& tod_dn_dir, Array_gpu<Float,1>& tod_dn_dif,
+                Array_gpu<Float,1>& bg_abs_dir, Array_gpu<Float,1>& bg_abs_dif);
+
+        // photons_per_pixel_gpt for a total of P photons per pixel: dealt over the g-points with inc > 0 in proportion to inc by
+        // largest remainders (ties to the lower g), at least min_per_gpt each; throws when P is below that floor.
+        static Array<long long,1> spectral_allocation(const Array<Float,1>& inc, const long long P, const long long min_per_gpt = 1);
+
     private:
         bool has_aer = false;
         Array_gpu<Float,3> aer_tau, aer_ssa, aer_g;

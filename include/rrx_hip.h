@@ -856,7 +856,55 @@ int rrx_raytracer_bw_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBoo
         F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
         int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
         int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, \
-        const F* aer_tau, const F* aer_ssa, const F* aer_g, const F* bg_aer_tau, const F* bg_aer_ssa, const F* bg_aer_g, void* stream);
+        const F* aer_tau, const F* aer_ssa, const F* aer_g, const F* bg_aer_tau, const F* bg_aer_ssa, const F* bg_aer_g, void* stream); \
+/* ---- The forward tracer with all g-points in one launch and photons dealt per g-point (csrc/rrx_rt_common.h). \
+   Forward only, ngpt <= 1024, built on the aerosol form (which covers nbg = 0 and NULL aerosol triples). The photons of a launch are \
+   the concatenation, in g-point order, of n_g = m_g ncol photons per g-point, m_g >= 0 photons per pixel; photon_end (ngpt+1) holds \
+   the prefix sums with photon_end[0] = 0. Global index p belongs to the g with photon_end[g] <= p < photon_end[g+1] (empty ranges are \
+   stepped over); its local index is q = p - photon_end[g], its Philox stream that of photon q of g-point g and its pixel q mod ncol: \
+   it is photon q of rrx_rt_trace_counts_aer(igpt = g), draw for draw. Only the deposits differ: every tally takes \
+   llrint(w weight0[g] 2^32). weight0[g] = (inc_g / F(m_g)) / (S / F(P)) for m_g > 0, inc_g = inc_dir[g] + inc_dif[g], S the sum of \
+   inc_g over the g-points with m_g > 0 in index order, P the sum of m_g; dif_frac[g] = inc_dif[g] / inc_g. The common unit is \
+   U = S / F(P): flux = counts 2^-32 U, abs_* with U / dz and bg_abs_*[b] with (U / dz_bg[b]) / F(ncol). With weight0[g] = 1 the integers \
+   are the sums over g of those of the per-g-point entry. \
+   rrx_rt_k_null_all: k_null (ngpt, knz, kny, knx); slice g is bit for bit rrx_rt_k_null_aer(igpt = g). \
+   rrx_rt_bg_profile_all: bg_profile (ngpt, 7, nbg+1); slice g is bit for bit rrx_rt_bg_profile_aer(igpt = g). \
+   rrx_rt_trace_counts_spectral: rrx_rt_trace_counts_aer without igpt, inc_dir, inc_dif and with the DEVICE arrays photon_end (ngpt+1), \
+   weight0, dif_frac (ngpt); k_null and bg_profile are those of all g-points; photon0 / nphotons address the concatenated list and the \
+   counts are additive over its ranges. The entry cannot look into device arrays: a photon beyond photon_end[ngpt] is stepped over and \
+   the kernel stays inside its arrays whatever photon_end holds; the callers that form the list on the host refuse one that does not \
+   ascend. \
+   rrx_raytracer_sw_spectral: rrx_raytracer_sw_aer with photons_per_pixel_gpt (ngpt, HOST) = m_g in place of photons_per_pixel. It forms \
+   photon_end, weight0 and dif_frac as above, builds k_null and the profile, traces chunks of consecutive g-points (the largest chunk \
+   whose k_null fits 1 GiB; RRX_RT_SPECTRAL_GPT_PER_LAUNCH in the environment overrides it, read at every call), adds the counts of \
+   all chunks in integers and converts them once: the result does not depend on the chunking. It waits for its stream once, after \
+   copying the photon list. Refused before any HIP call: what the _aer counterpart refuses, ngpt > 1024, m_g < 0, m_g > 0 where \
+   inc_g <= 0. All m_g = 0: the outputs are zeroed and it returns 0. */ \
+int rrx_rt_k_null_all##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, const F* tau, const int* band_lims_gpt, \
+        const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, const F* aer_tau, void* stream); \
+int rrx_rt_bg_profile_all##SFX(int nbg, int ngpt, int nbnd, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const int* band_lims_gpt, \
+        const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* bg_profile, \
+        const F* bg_aer_tau, const F* bg_aer_ssa, const F* bg_aer_g, void* stream); \
+int rrx_rt_trace_counts_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const long long* photon_end, const F* weight0, const F* dif_frac, \
+        int knx, int kny, int knz, const F* k_null, \
+        unsigned long long seed, long long photon0, long long nphotons, int max_events, \
+        unsigned long long* sfc_dn_dir, unsigned long long* sfc_dn_dif, unsigned long long* sfc_up, unsigned long long* tod_up, \
+        unsigned long long* abs_dir, unsigned long long* abs_dif, unsigned long long* n_capped, \
+        unsigned long long* toa_up, unsigned long long* tod_dn_dir, unsigned long long* tod_dn_dif, \
+        unsigned long long* bg_abs_dir, unsigned long long* bg_abs_dif, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_profile, const F* aer_tau, const F* aer_ssa, const F* aer_g, void* stream); \
+int rrx_raytracer_sw_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
+        const long long* photons_per_pixel_gpt, unsigned long long seed, int max_events, \
+        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, \
+        F* toa_up, F* tod_dn_dir, F* tod_dn_dif, F* bg_abs_dir, F* bg_abs_dif, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, \
+        const F* const* aer, const F* const* bg_aer, void* stream);
 
 RRX_DECLARE(double, _f64)
 RRX_DECLARE(float, _f32)

@@ -106,6 +106,17 @@ int   rrx_cxx_trace_rays_aer(int nx, int ny, int nz, int ngpt, int nbnd, Real dx
                          const Real* cld_re, int nbg, const Real* dz_bg, const Real* bg_tau, const Real* bg_ssa, const Real* bg_cld_tau,
                          const Real* bg_cld_ssa, const Real* bg_cld_g, const Real* aer_tau, const Real* aer_ssa, const Real* aer_g,
                          const Real* bg_aer_tau, const Real* bg_aer_ssa, const Real* bg_aer_g, void* stream);
+/* the same through Raytracer_gpu::trace_rays_spectral: photons_per_pixel_gpt (ngpt) on the HOST in place of photons_per_pixel;
+ * out5 is written with nbg > 0 only. rrx_cxx_spectral_allocation: Raytracer_gpu::spectral_allocation of P over inc (ngpt, HOST) into m (ngpt, HOST). */
+int   rrx_cxx_trace_rays_spectral(int nx, int ny, int nz, int ngpt, int nbnd, Real dx, Real dy, Real dz, int top_at_1, int independent_column,
+                         const Real* tau, const Real* ssa, const int* band_lims_gpt, const Real* cld_tau, const Real* cld_ssa, const Real* cld_g,
+                         const Real* sfc_albedo, Real mu0, Real azimuth, const Real* inc_dir, const Real* inc_dif, int knx, int kny, int knz,
+                         const long long* photons_per_pixel_gpt, unsigned long long seed, int max_events, Real* const* out6,
+                         unsigned long long* n_capped, Real* const* out5, int nmu, int nre, Real re0, Real dre, const Real* mu, const Real* phase,
+                         const Real* cdf, const Real* cld_re, int nbg, const Real* dz_bg, const Real* bg_tau, const Real* bg_ssa,
+                         const Real* bg_cld_tau, const Real* bg_cld_ssa, const Real* bg_cld_g, const Real* aer_tau, const Real* aer_ssa,
+                         const Real* aer_g, const Real* bg_aer_tau, const Real* bg_aer_ssa, const Real* bg_aer_g, void* stream);
+int   rrx_cxx_spectral_allocation(int ngpt, const Real* inc, long long P, long long min_per_gpt, long long* m);
 int   rrx_cxx_trace_rays_bw_aer(int nx, int ny, int nz, int ngpt, int nbnd, Real dx, Real dy, Real dz, int top_at_1,
                             const Real* tau, const Real* ssa, const int* band_lims_gpt, const Real* cld_tau, const Real* cld_ssa, const Real* cld_g,
                             const Real* sfc_albedo, Real mu0, Real azimuth, const Real* inc_dir, int knx, int kny, int knz,

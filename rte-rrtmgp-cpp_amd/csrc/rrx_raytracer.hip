@@ -66,15 +66,13 @@ namespace
 using namespace rrx;
 using namespace rrx::rt;
 
-// k_null_kernel with aerosol: the maximum of ((tau + tau_c) + tau_a)/dz
+// the maximum of ((tau + tau_c) + tau_a)/dz over the cells of block n of the k_null grid, for g-point igpt
 template<typename F>
-__global__ void __launch_bounds__(256) k_null_aer_kernel(
-        const int nx, const int ny, const int nz, const int nbnd, const int igpt, const int top_at_1,
+__device__ __forceinline__ F k_null_aer_of_block(
+        const int n, const int nx, const int ny, const int nz, const int nbnd, const int igpt, const int top_at_1,
         const F* __restrict__ tau, const int* __restrict__ band_lims_gpt, const F* __restrict__ cld_tau, const F* __restrict__ aer_tau,
-        const F dz, const int knx, const int kny, const int knz, F* __restrict__ k_null)
+        const F dz, const int knx, const int kny, const int knz)
 {
-    const int n = blockIdx.x*blockDim.x + threadIdx.x;
-    if (n >= knx*kny*knz) return;
     const int in = n % knx, jn = (n / knx) % kny, kn = n / (knx*kny);
     const int rx = nx/knx, ry = ny/kny, rz = nz/knz;
     const size_t ncol = size_t(nx)*ny;
@@ -92,7 +90,33 @@ __global__ void __launch_bounds__(256) k_null_aer_kernel(
                 m = max(m, k_ext_of(tau[cell + ncol*nz*igpt], tc, ta, dz));
             }
     }
-    k_null[n] = m;
+    return m;
+}
+
+// k_null_kernel with aerosol
+template<typename F>
+__global__ void __launch_bounds__(256) k_null_aer_kernel(
+        const int nx, const int ny, const int nz, const int nbnd, const int igpt, const int top_at_1,
+        const F* __restrict__ tau, const int* __restrict__ band_lims_gpt, const F* __restrict__ cld_tau, const F* __restrict__ aer_tau,
+        const F dz, const int knx, const int kny, const int knz, F* __restrict__ k_null)
+{
+    const int n = blockIdx.x*blockDim.x + threadIdx.x;
+    if (n >= knx*kny*knz) return;
+    k_null[n] = k_null_aer_of_block<F>(n, nx, ny, nz, nbnd, igpt, top_at_1, tau, band_lims_gpt, cld_tau, aer_tau, dz, knx, kny, knz);
+}
+
+// k_null_aer_kernel for the ng g-points from g0 on, blockIdx.y counting them: slice g - g0 of k_null (ng, knz, kny, knx)
+// holds what k_null_aer_kernel(igpt = g) writes
+template<typename F>
+__global__ void __launch_bounds__(256) k_null_all_kernel(
+        const int nx, const int ny, const int nz, const int nbnd, const int g0, const int top_at_1,
+        const F* __restrict__ tau, const int* __restrict__ band_lims_gpt, const F* __restrict__ cld_tau, const F* __restrict__ aer_tau,
+        const F dz, const int knx, const int kny, const int knz, F* __restrict__ k_null)
+{
+    const int n = blockIdx.x*blockDim.x + threadIdx.x;
+    if (n >= knx*kny*knz) return;
+    k_null[size_t(blockIdx.y)*(size_t(knx)*kny*knz) + n] =
+        k_null_aer_of_block<F>(n, nx, ny, nz, nbnd, g0 + int(blockIdx.y), top_at_1, tau, band_lims_gpt, cld_tau, aer_tau, dz, knx, kny, knz);
 }
 
 // k_null(in, jn, kn) = the maximum of k_ext over the block's cells, for one g-point
@@ -148,18 +172,33 @@ struct TraceArgs
 // without a background: the integers of the other instantiations.
 template<typename F>
 struct BgTallies { u64* toa_up; u64* tod_dn_dir; u64* tod_dn_dif; u64* bg_abs_dir; u64* bg_abs_dif; };
-template<typename F, bool BG, bool AER = false> struct FwBg {};
-template<typename F> struct FwBg<F,true,false> { BgIn<F> in; BgTallies<F> t; };
-template<typename F> struct FwBg<F,true,true> { BgIn<F> in; BgTallies<F> t; AerIn<F> aer; };
+template<typename F, bool BG, bool AER = false, bool SPECTRAL = false> struct FwBg {};
+template<typename F> struct FwBg<F,true,false,false> { BgIn<F> in; BgTallies<F> t; };
+template<typename F> struct FwBg<F,true,true,false> { BgIn<F> in; BgTallies<F> t; AerIn<F> aer; };
+// the spectral form (below): in.profile is the profile of all g-points, (ngpt, BG_ROWS_AER, nbg+1)
+template<typename F> struct FwBg<F,true,true,true> { BgIn<F> in; BgTallies<F> t; AerIn<F> aer; SpecIn<F> sp; };
 
 // AER: aerosol as a third species (rrx_rt_common.h), built on top of the BG form only, which handles nbg = 0: the grid's
 // triple in bgin.aer (NULL: none in the grid), the background's in rows BG_K_SCA_AER and BG_G_AER of the 7-row profile.
-template<typename F, bool TABLE, bool BG, bool AER>
-__global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, const PhaseArgs<F,TABLE> ph, const FwBg<F,BG,AER> bgin)
+//
+// SPECTRAL: all g-points in one launch (rrx_rt_common.h), built on the aerosol form only. a.photon0 / a.nphotons address the
+// concatenated list; the g-point is state of the photon, set when a lane takes its next one, and the band, the tau / ssa / k_null slices
+// and the background's profile rows are derived from it at every event (carried, they cost a wave per SIMD in registers). a.igpt and
+// a.dif_frac are not read. The transport is that of photon q of g-point g in the per-g-point launch, draw for draw; every deposit is
+// to_count(w weight0[g]).
+template<typename F, bool TABLE, bool BG, bool AER, bool SPECTRAL = false>
+__global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, const PhaseArgs<F,TABLE> ph, const FwBg<F,BG,AER,SPECTRAL> bgin)
 {
     static_assert(BG || !AER, "the aerosol form is built on the background form");
+    static_assert(AER || !SPECTRAL, "the spectral form is built on the aerosol form");
     [[maybe_unused]] BgView<F> bg{};
-    if constexpr (BG)
+    [[maybe_unused]] SpecView sv{};
+    if constexpr (SPECTRAL)
+    {
+        extern __shared__ double bg_lds[];
+        sv = stage_spectral<F>(bgin.sp, bgin.in, a.nbnd, a.band_lims_gpt, bg_lds, bg);
+    }
+    else if constexpr (BG)
     {
         extern __shared__ double bg_lds[];
         bg = stage_background<F, AER ? BG_ROWS_AER : BG_ROWS>(bgin.in, reinterpret_cast<F*>(bg_lds));
@@ -173,13 +212,24 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
     const F kdx = F(rx)*a.dx, kdy = F(ry)*a.dy, kdz = F(rz)*a.dz;
     [[maybe_unused]] const F len_x = F(a.knx)*kdx, len_y = F(a.kny)*kdy;
     const bool ic = a.independent_column != 0;
-    const int ibnd = a.cld_tau != nullptr ? band_of(a.igpt, a.nbnd, a.band_lims_gpt) : -1;
-    const F* __restrict__ tau_g = a.tau + ncol*nz*a.igpt;
-    const F* __restrict__ ssa_g = a.ssa + ncol*nz*a.igpt;
+    // (what follows of the g-point is fixed for the launch, or under SPECTRAL set with every photon)
+    int igpt = SPECTRAL ? 0 : a.igpt;
+    int ibnd = -1;
+    const F* __restrict__ tau_g = a.tau;
+    const F* __restrict__ ssa_g = a.ssa;
+    const F* __restrict__ kn_g = a.k_null;
+    if constexpr (!SPECTRAL)
+    {
+        ibnd = a.cld_tau != nullptr ? band_of(a.igpt, a.nbnd, a.band_lims_gpt) : -1;
+        tau_g = a.tau + ncol*nz*a.igpt;
+        ssa_g = a.ssa + ncol*nz*a.igpt;
+    }
     const F inf = F(INFINITY);
     [[maybe_unused]] const F g_max = F(1.) - Lim<F>::eps();
     [[maybe_unused]] int ibnd_a = -1;
-    if constexpr (AER) ibnd_a = bgin.aer.tau != nullptr ? band_of(a.igpt, a.nbnd, a.band_lims_gpt) : -1;
+    if constexpr (AER && !SPECTRAL) ibnd_a = bgin.aer.tau != nullptr ? band_of(a.igpt, a.nbnd, a.band_lims_gpt) : -1;
+    // a deposit of weight w, in units of 2^-32 photon
+    const auto count_of = [&](const F w) { if constexpr (SPECTRAL) return to_count(w*bgin.sp.weight0[igpt]); else return to_count(w); };
 
     Stream rng; rng.k0 = a.k0; rng.k1 = a.k1; rng.used = 4; rng.block = 0u; rng.c0 = rng.c1 = rng.c2 = 0u;
     bool alive = false, pending = false;
@@ -191,9 +241,17 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
         if (!alive)
         {
             if (next_photon >= a.nphotons) break;          // the list is finite and every photon ends within max_events events
-            const u64 p = a.photon0 + u64(next_photon);
+            u64 p = a.photon0 + u64(next_photon);
             next_photon += nthreads;
-            rng.start(p, unsigned(a.igpt));
+            [[maybe_unused]] F dif_frac = a.dif_frac;
+            if constexpr (SPECTRAL)
+            {
+                igpt = gpt_of_photon(sv.photon_end, sv.ngpt, (long long)p);
+                if (igpt >= sv.ngpt) continue;          // (beyond the list)
+                p = p - u64(sv.photon_end[igpt]);
+                dif_frac = bgin.sp.dif_frac[igpt];
+            }
+            rng.start(p, unsigned(igpt));
             const int pix = int(p % u64(ncol));
             const int ix = pix % nx, iy = pix / nx;
             in = ix / rx; jn = iy / ry; kn = a.knz - 1;
@@ -201,12 +259,23 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
             y = clampf((F(iy) + rng.next<F>())*a.dy, F(jn)*kdy, F(jn+1)*kdy);
             z = F(a.knz)*kdz;
             if constexpr (BG) { if (bg.nbg > 0) { kn = a.knz + bg.nbg - 1; z = bg.z[bg.nbg]; } }
-            if (rng.next<F>() < a.dif_frac) { lambert(rng, F(-1.), ux, uy, uz); kind = 1; }
+            if (rng.next<F>() < dif_frac) { lambert(rng, F(-1.), ux, uy, uz); kind = 1; }
             else { ux = a.sun_x; uy = a.sun_y; uz = a.sun_z; kind = 0; }
             weight = F(1.); pending = false; nev = 0; alive = true;
         }
         if (nev >= a.max_events) { atomicAdd(a.n_capped, 1ull); alive = false; continue; }
         ++nev;
+        if constexpr (SPECTRAL)
+        {
+            // what the event reads of the photon's g-point, derived again at every event: the lane carries igpt only (weight0 is read at a deposit)
+            const int band = sv.band[igpt];
+            ibnd = a.cld_tau != nullptr ? band : -1;
+            ibnd_a = bgin.aer.tau != nullptr ? band : -1;
+            tau_g = a.tau + ncol*nz*igpt;
+            ssa_g = a.ssa + ncol*nz*igpt;
+            kn_g = a.k_null + (size_t(a.knx)*a.kny*a.knz)*size_t(igpt - bgin.sp.kn_g0);
+            if (bg.nbg > 0) bg_rows_of_gpt<F, BG_ROWS_AER>(bg, bgin.in.profile, igpt);
+        }
 
         // in_bg: the photon is in background layer kn - knz, a block with z faces only whose k_null is its own k_ext
         [[maybe_unused]] bool in_bg = false;
@@ -221,8 +290,8 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
         const F d_max = min(sz, min(sx, sy));
         const int axis = (sz <= sx && sz <= sy) ? 2 : (sx <= sy ? 0 : 1);
         F kn_val;
-        if constexpr (BG) kn_val = in_bg ? bg.k_ext[kn - a.knz] : a.k_null[in + a.knx*(jn + a.kny*min(kn, a.knz - 1))];
-        else kn_val = a.k_null[in + a.knx*(jn + a.kny*kn)];
+        if constexpr (BG) kn_val = in_bg ? bg.k_ext[kn - a.knz] : kn_g[in + a.knx*(jn + a.kny*min(kn, a.knz - 1))];
+        else kn_val = kn_g[in + a.knx*(jn + a.kny*kn)];
         if (!pending) tau = -log(rng.next<F>());
         pending = false;
         const bool empty = !(kn_val > F(0.));
@@ -251,7 +320,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
                         if (kn == a.knz + bg.nbg - 1)
                         {
                             const int pix = wrapped_cell(x, len_x, a.dx, nx) + nx*wrapped_cell(y, len_y, a.dy, ny);
-                            tally(bgin.t.toa_up, pix, to_count(weight));
+                            tally(bgin.t.toa_up, pix, count_of(weight));
                             alive = false;
                         }
                         else { ++kn; z = bg.z[kn - a.knz]; }
@@ -261,7 +330,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
                         if (!ic) { enter_grid(x, in, len_x, kdx, a.knx); enter_grid(y, jn, len_y, kdy, a.kny); }
                         kn = a.knz - 1; z = F(a.knz)*kdz;
                         const int pix = fine_cell(x, a.dx, in, rx) + nx*fine_cell(y, a.dy, jn, ry);
-                        tally(kind == 0 ? bgin.t.tod_dn_dir : bgin.t.tod_dn_dif, pix, to_count(weight));
+                        tally(kind == 0 ? bgin.t.tod_dn_dir : bgin.t.tod_dn_dif, pix, count_of(weight));
                     }
                     else { --kn; z = bg.z[kn - a.knz + 1]; }
                 }
@@ -282,7 +351,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
                 if (kn == a.knz - 1)          // out through the domain top
                 {
                     const int pix = fine_cell(x, a.dx, in, rx) + nx*fine_cell(y, a.dy, jn, ry);
-                    tally(a.tod_up, pix, to_count(weight));
+                    tally(a.tod_up, pix, count_of(weight));
                     alive = false;
                     if constexpr (BG) { if (bg.nbg > 0) { alive = true; kn = a.knz; z = bg.z[0]; } }
                 }
@@ -292,9 +361,9 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
             {
                 z = F(0.);
                 const int pix = fine_cell(x, a.dx, in, rx) + nx*fine_cell(y, a.dy, jn, ry);
-                tally(kind == 0 ? a.sfc_dn_dir : a.sfc_dn_dif, pix, to_count(weight));
+                tally(kind == 0 ? a.sfc_dn_dir : a.sfc_dn_dif, pix, count_of(weight));
                 weight = weight * a.sfc_albedo[pix];
-                tally(a.sfc_up, pix, to_count(weight));
+                tally(a.sfc_up, pix, count_of(weight));
                 if (weight < F(0.5)) weight = (rng.next<F>() > weight) ? F(0.) : F(1.);
                 if (weight > F(0.)) { lambert(rng, F(1.), ux, uy, uz); kind = 1; pending = false; }
                 else alive = false;
@@ -362,7 +431,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_kernel(const TraceArgs<F> a, c
                 k_sca_cld = (tc*wc) / a.dz;
             }
             const F f_no_abs = clampf(F(1.) - (k_ext - k_sca)/kn_val, F(0.), F(1.));
-            tally(abs_to, cell, to_count(weight*(F(1.) - f_no_abs)));
+            tally(abs_to, cell, count_of(weight*(F(1.) - f_no_abs)));
             weight = weight * f_no_abs;
             if (weight < F(0.5)) weight = (rng.next<F>() > weight) ? F(0.) : F(1.);
             if (!(weight > F(0.))) { alive = false; continue; }
@@ -749,6 +818,274 @@ int raytracer_sw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
     }
     RRX_CATCH(entry)
 }
+
+// ---- all g-points in one launch (rrx_rt_common.h)
+
+// bg_profile_aer_kernel for every g-point, blockIdx.y counting them: slice g of profile (ngpt, BG_ROWS_AER, nbg+1)
+template<typename F>
+__global__ void bg_profile_all_kernel(const int nbg, const int nbnd, const BgLevels<F> dz_bg,
+        const F* __restrict__ bg_tau, const F* __restrict__ bg_ssa, const int* __restrict__ band_lims_gpt,
+        const F* __restrict__ bg_cld_tau, const F* __restrict__ bg_cld_ssa, const F* __restrict__ bg_cld_g, const AerIn<F> aer,
+        F* __restrict__ profile)
+{
+    bg_profile_layer<F,true>(nbg, nbnd, int(blockIdx.y), dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, aer,
+                             profile + size_t(blockIdx.y)*BG_ROWS_AER*(nbg + 1));
+}
+
+// k_null of the ng g-points from g0 on
+template<typename F>
+void launch_k_null_all(int nx, int ny, int nz, int nbnd, int g0, int ng, int top_at_1, const F* tau, const int* band_lims_gpt,
+                       const F* cld_tau, const F* aer_tau, F dz, int knx, int kny, int knz, F* k_null, hipStream_t st)
+{
+    const dim3 grid(unsigned(ceil_div(knx*kny*knz, 256)), unsigned(ng));
+    k_null_all_kernel<F><<<grid, 256, 0, st>>>(nx, ny, nz, nbnd, g0, top_at_1, tau, band_lims_gpt, cld_tau, aer_tau, dz, knx, kny, knz, k_null);
+}
+
+template<typename F>
+void launch_bg_profile_all(int nbg, int ngpt, int nbnd, const BgLevels<F>& dz_bg, const F* bg_tau, const F* bg_ssa, const int* band_lims_gpt,
+                           const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, const AerIn<F>& aer, F* profile, hipStream_t st)
+{
+    const dim3 grid(unsigned(ceil_div(nbg + 1, 64)), unsigned(ngpt));
+    bg_profile_all_kernel<F><<<grid, 64, 0, st>>>(nbg, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, aer, profile);
+}
+
+// a.photon0 / a.nphotons: the range of the concatenated list; a.k_null: the slices from g-point b.sp.kn_g0 on
+template<typename F>
+void launch_trace_spectral(TraceArgs<F> a, const PhaseIn<F>& ph, const F mu0, const F azimuth, const u64 seed, hipStream_t st,
+                           const FwBg<F,true,true,true>& b)
+{
+    const double st_ = std::sqrt(std::max(0.0, 1.0 - double(mu0)*double(mu0)));
+    a.sun_x = F(st_*std::cos(double(azimuth))); a.sun_y = F(st_*std::sin(double(azimuth))); a.sun_z = -mu0;
+    a.k0 = unsigned(seed & 0xFFFFFFFFull); a.k1 = unsigned(seed >> 32);
+    const int blocks = int(std::min<long long>((a.nphotons + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
+    const size_t lds = spectral_lds_bytes(b.sp.ngpt, b.in.nbg, sizeof(F));
+    if (ph.given()) trace_kernel<F,true,true,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, b);
+    else trace_kernel<F,false,true,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, b);
+}
+
+inline void check_spectral_ngpt(const int ngpt)
+{
+    if (ngpt > RT_SPECTRAL_MAX_GPT) throw std::runtime_error("ngpt must be <= 1024 in the spectral form");
+}
+
+template<typename F>
+int k_null_all_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, const F* tau,
+                     const int* band_lims_gpt, const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, const F* aer_tau, void* stream)
+{
+    RRX_TRY
+    if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}})) return 0;
+    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
+    check_spectral_ngpt(ngpt);
+    check_needed({{"tau", tau}, {"k_null", k_null}});
+    if ((cld_tau != nullptr || aer_tau != nullptr) && band_lims_gpt == nullptr) throw std::runtime_error("band_lims_gpt is NULL");
+    if (aer_tau != nullptr && nbnd < 1) throw std::runtime_error("nbnd must be >= 1 with an aerosol triple");
+    if (!(dz > F(0.))) throw std::runtime_error("dz must be > 0");
+    check_grid(nx, ny, nz, knx, kny, knz);
+    launch_k_null_all<F>(nx, ny, nz, nbnd, 0, ngpt, top_at_1 ? 1 : 0, tau, band_lims_gpt, cld_tau, aer_tau, dz, knx, kny, knz, k_null,
+                         static_cast<hipStream_t>(stream));
+    RRX_CATCH(entry)
+}
+
+template<typename F>
+int bg_profile_all_entry(const char* entry, int nbg, int ngpt, int nbnd, const F* dz_bg, const F* bg_tau, const F* bg_ssa,
+                         const int* band_lims_gpt, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* profile,
+                         const AerIn<F> aer, void* stream)
+{
+    RRX_TRY
+    check_nbg(nbg);
+    if (check_extents({{"nbg", nbg}, {"ngpt", ngpt}})) return 0;
+    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
+    check_spectral_ngpt(ngpt);
+    check_bg_medium(nbg, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g);
+    check_aerosol("bg_aer_", nbnd, band_lims_gpt, aer.tau, aer.ssa, aer.g);
+    check_needed({{"bg_profile", profile}});
+    bg_levels<F>(nbg, dz_bg, 1, 1, F(1.));          // (the thicknesses are > 0)
+    launch_bg_profile_all<F>(nbg, ngpt, nbnd, bg_thicknesses(nbg, dz_bg), bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, aer,
+                             profile, static_cast<hipStream_t>(stream));
+    RRX_CATCH(entry)
+}
+
+// photon_end, weight0, dif_frac are device arrays: the entry cannot look into them. The kernel stays inside its arrays whatever
+// photon_end holds (the search is bounded by ngpt and a photon beyond photon_end[ngpt] is stepped over); the callers that form the
+// list on the host (rrx_raytracer_sw_spectral, the Python binding) refuse a list that does not ascend.
+template<typename F>
+int trace_spectral_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column,
+                         const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
+                         F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const long long* photon_end, const F* weight0, const F* dif_frac,
+                         int knx, int kny, int knz, const F* k_null, u64 seed, long long photon0, long long nphotons, int max_events,
+                         u64* sfc_dn_dir, u64* sfc_dn_dif, u64* sfc_up, u64* tod_up, u64* abs_dir, u64* abs_dif, u64* n_capped,
+                         const BgTallies<F> bt, const PhaseIn<F> ph, const int nbg, const F* dz_bg, const F* bg_profile, const AerIn<F> aer,
+                         void* stream)
+{
+    RRX_TRY
+    check_nbg(nbg);
+    if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"nphotons", nphotons}})) return 0;
+    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
+    check_spectral_ngpt(ngpt);
+    if (photon0 < 0) throw std::runtime_error("photon0 is negative");
+    check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"photon_end", photon_end}, {"weight0", weight0},
+                  {"dif_frac", dif_frac}, {"k_null", k_null}, {"sfc_dn_dir", sfc_dn_dir}, {"sfc_dn_dif", sfc_dn_dif}, {"sfc_up", sfc_up},
+                  {"tod_up", tod_up}, {"abs_dir", abs_dir}, {"abs_dif", abs_dif}, {"n_capped", n_capped}});
+    check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
+    check_aerosol("aer_", nbnd, band_lims_gpt, aer.tau, aer.ssa, aer.g);
+    check_phase(ph, cld_tau);
+    check_scene(dx, dy, dz, mu0);
+    if (max_events < 1) throw std::runtime_error("max_events must be >= 1");
+    check_grid(nx, ny, nz, knx, kny, knz);
+    TraceArgs<F> a{nx, ny, nz, nbnd, 0, top_at_1 ? 1 : 0, independent_column ? 1 : 0, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g,
+                   dx, dy, dz, sfc_albedo, F(0.), F(0.), F(0.), F(0.), knx, kny, knz, k_null, 0u, 0u, u64(photon0), nphotons, max_events,
+                   sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped};
+    FwBg<F,true,true,true> b{BgIn<F>{nbg, bg_profile, BgLevels<F>{}}, bt, aer, SpecIn<F>{ngpt, 0, photon_end, weight0, dif_frac}};
+    if (nbg > 0)
+    {
+        check_needed({{"dz_bg", dz_bg}, {"bg_profile", bg_profile}, {"toa_up", bt.toa_up}, {"tod_dn_dir", bt.tod_dn_dir},
+                      {"tod_dn_dif", bt.tod_dn_dif}, {"bg_abs_dir", bt.bg_abs_dir}, {"bg_abs_dif", bt.bg_abs_dif}});
+        b.in.z = bg_levels<F>(nbg, dz_bg, nz, knz, dz);
+    }
+    launch_trace_spectral<F>(a, ph, mu0, azimuth, seed, static_cast<hipStream_t>(stream), b);
+    RRX_CATCH(entry)
+}
+
+// g-points per trace launch of rrx_raytracer_sw_spectral: the largest chunk whose k_null fits 1 GiB, or
+// RRX_RT_SPECTRAL_GPT_PER_LAUNCH from the environment, read at every call. The result does not depend on it.
+inline int spectral_gpt_per_launch(const size_t k_null_bytes_per_gpt, const int ngpt)
+{
+    if (const char* e = std::getenv("RRX_RT_SPECTRAL_GPT_PER_LAUNCH")) { const int n = std::atoi(e); if (n >= 1) return std::min(n, ngpt); }
+    const size_t fit = (size_t(1) << 30) / std::max<size_t>(k_null_bytes_per_gpt, 1);
+    return int(std::min<size_t>(std::max<size_t>(fit, 1), size_t(ngpt)));
+}
+
+// rrx_raytracer_sw_aer with photons_per_pixel_gpt[g] = m_g photons per pixel of g-point g (host array): one trace launch per chunk of
+// consecutive g-points, the counts of all chunks added in integers and converted once with the common unit U = S/P
+template<typename F>
+int raytracer_sw_spectral_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column,
+                       const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
+                       F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif,
+                       int knx, int kny, int knz, const long long* m, u64 seed, int max_events,
+                       F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, u64* n_capped, void* stream,
+                       const PhaseIn<F> ph, F* const* bg_out, const int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa,
+                       const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, const AerIn<F> aer, const AerIn<F> bg_aer)
+{
+    RRX_TRY
+    check_nbg(nbg);
+    if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}})) return 0;
+    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
+    check_spectral_ngpt(ngpt);
+    check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"inc_dir", inc_dir}, {"inc_dif", inc_dif},
+                  {"photons_per_pixel_gpt", m}, {"sfc_dn_dir", sfc_dn_dir}, {"sfc_dn_dif", sfc_dn_dif}, {"sfc_up", sfc_up}, {"tod_up", tod_up},
+                  {"abs_dir", abs_dir}, {"abs_dif", abs_dif}, {"n_capped", n_capped}});
+    check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
+    check_aerosol("aer_", nbnd, band_lims_gpt, aer.tau, aer.ssa, aer.g);
+    check_phase(ph, cld_tau);
+    check_scene(dx, dy, dz, mu0);
+    const size_t ncol = size_t(nx)*ny;
+    // the photon list, the weights and the common unit U = S/P (rrx_rt_common.h)
+    std::vector<long long> photon_end(size_t(ngpt) + 1, 0);
+    std::vector<F> weight0(ngpt, F(0.)), dif_frac(ngpt, F(0.));
+    long long P = 0;
+    F S = F(0.);
+    for (int g=0; g<ngpt; ++g)
+    {
+        if (inc_dir[g] < F(0.) || inc_dif[g] < F(0.)) throw std::runtime_error("inc_dir, inc_dif must be >= 0");
+        if (m[g] < 0) throw std::runtime_error("photons_per_pixel_gpt is negative at g-point " + std::to_string(g));
+        if (m[g] > 0 && !(inc_dir[g] + inc_dif[g] > F(0.)))
+            throw std::runtime_error("photons_per_pixel_gpt is > 0 at g-point " + std::to_string(g) + ", which has no incident flux");
+        if (m[g] > (0x7FFFFFFFFFFFFFFFll - photon_end[g]) / (long long)ncol) throw std::runtime_error("the photon list exceeds 2^63 - 1");
+        photon_end[g+1] = photon_end[g] + m[g]*(long long)ncol;
+        P += m[g];
+        if (m[g] > 0) S = S + (inc_dir[g] + inc_dif[g]);
+    }
+    if (max_events < 1) throw std::runtime_error("max_events must be >= 1");
+    check_grid(nx, ny, nz, knx, kny, knz);
+    const F U = P > 0 ? S / F(P) : F(0.);
+    for (int g=0; g<ngpt; ++g)
+        if (m[g] > 0)
+        {
+            const F inc = inc_dir[g] + inc_dif[g];
+            weight0[g] = (inc / F(m[g])) / U;
+            dif_frac[g] = inc_dif[g] / inc;
+        }
+    const bool bg_on = nbg > 0;
+    BgLevels<F> lev{}, thick{};
+    AerIn<F> aer_bg{};
+    if (bg_on)
+    {
+        check_aerosol("bg_aer_", nbnd, band_lims_gpt, bg_aer.tau, bg_aer.ssa, bg_aer.g);
+        aer_bg = bg_aer;
+        check_bg_medium(nbg, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g);
+        check_needed({{"toa_up", bg_out[0]}, {"tod_dn_dir", bg_out[1]}, {"tod_dn_dif", bg_out[2]}, {"bg_abs_dir", bg_out[3]},
+                      {"bg_abs_dif", bg_out[4]}});
+        lev = bg_levels<F>(nbg, dz_bg, nz, knz, dz);
+        thick = bg_thicknesses(nbg, dz_bg);
+    }
+
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t n_sfc = 4*ncol, n_abs = 2*ncol*nz;
+    const size_t n_bgc = bg_on ? 3*ncol + 2*size_t(nbg) : 0, n_counts = n_sfc + n_abs + n_bgc;
+    const size_t nkn = size_t(knx)*kny*knz;
+    const int chunk = spectral_gpt_per_launch(nkn*sizeof(F), ngpt);
+    const auto words = [](const size_t bytes) { return (bytes + sizeof(u64) - 1) / sizeof(u64); };
+    const size_t n_kn = words(nkn*chunk*sizeof(F));
+    const size_t n_prof = bg_on ? words(size_t(ngpt)*BG_ROWS_AER*(nbg + 1)*sizeof(F)) : 0;
+    const size_t n_pe = size_t(ngpt) + 1, n_w = words(size_t(ngpt)*sizeof(F));
+    WorkspaceLease lease(st);
+    u64* counts = lease.get<u64>(n_counts + n_kn + n_prof + n_pe + 2*n_w);
+    F* k_null = reinterpret_cast<F*>(counts + n_counts);
+    F* profile = reinterpret_cast<F*>(counts + n_counts + n_kn);
+    long long* d_pe = reinterpret_cast<long long*>(counts + n_counts + n_kn + n_prof);
+    F* d_w0 = reinterpret_cast<F*>(counts + n_counts + n_kn + n_prof + n_pe);
+    F* d_df = reinterpret_cast<F*>(counts + n_counts + n_kn + n_prof + n_pe + n_w);
+    bool ok = hipMemsetAsync(n_capped, 0, sizeof(u64), st) == hipSuccess;
+    if (bg_on)
+    {
+        for (int n=0; n<3; ++n) ok = ok && hipMemsetAsync(bg_out[n], 0, ncol*sizeof(F), st) == hipSuccess;
+        for (int n=3; n<5; ++n) ok = ok && hipMemsetAsync(bg_out[n], 0, size_t(nbg)*sizeof(F), st) == hipSuccess;
+    }
+    for (F* out : {sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up}) ok = ok && hipMemsetAsync(out, 0, ncol*sizeof(F), st) == hipSuccess;
+    for (F* out : {abs_dir, abs_dif}) ok = ok && hipMemsetAsync(out, 0, ncol*nz*sizeof(F), st) == hipSuccess;
+    if (!ok) throw std::runtime_error("zeroing the outputs failed");
+    if (P == 0) return 0;
+    ok = hipMemsetAsync(counts, 0, n_counts*sizeof(u64), st) == hipSuccess
+      && hipMemcpyAsync(d_pe, photon_end.data(), n_pe*sizeof(long long), hipMemcpyHostToDevice, st) == hipSuccess
+      && hipMemcpyAsync(d_w0, weight0.data(), size_t(ngpt)*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess
+      && hipMemcpyAsync(d_df, dif_frac.data(), size_t(ngpt)*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess
+      && hipStreamSynchronize(st) == hipSuccess;          // (the host arrays end with this call)
+    if (!ok) throw std::runtime_error("zeroing the counts or copying the photon list failed");
+    if (bg_on) launch_bg_profile_all<F>(nbg, ngpt, nbnd, thick, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, aer_bg, profile, st);
+    u64* c = counts;
+    u64* cb = c + n_sfc + n_abs;
+    FwBg<F,true,true,true> b{BgIn<F>{bg_on ? nbg : 0, profile, lev}, BgTallies<F>{cb, cb + ncol, cb + 2*ncol, cb + 3*ncol, cb + 3*ncol + nbg}, aer,
+                             SpecIn<F>{ngpt, 0, d_pe, d_w0, d_df}};
+    for (int g0=0; g0<ngpt; g0+=chunk)
+    {
+        const int g1 = std::min(g0 + chunk, ngpt);
+        const long long n = photon_end[g1] - photon_end[g0];
+        if (n == 0) continue;
+        launch_k_null_all<F>(nx, ny, nz, nbnd, g0, g1 - g0, top_at_1 ? 1 : 0, tau, band_lims_gpt, cld_tau, aer.tau, dz, knx, kny, knz, k_null, st);
+        TraceArgs<F> a{nx, ny, nz, nbnd, 0, top_at_1 ? 1 : 0, independent_column ? 1 : 0, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g,
+                       dx, dy, dz, sfc_albedo, F(0.), F(0.), F(0.), F(0.), knx, kny, knz, k_null, 0u, 0u, u64(photon_end[g0]), n, max_events,
+                       c, c + ncol, c + 2*ncol, c + 3*ncol, c + n_sfc, c + n_sfc + ncol*nz, n_capped};
+        b.sp.kn_g0 = g0;
+        launch_trace_spectral<F>(a, ph, mu0, azimuth, seed, st, b);
+    }
+    if (bg_on)
+    {
+        launch_counts_to_flux<F>(ncol, b.t.toa_up, U, bg_out[0], st);
+        launch_counts_to_flux<F>(ncol, b.t.tod_dn_dir, U, bg_out[1], st);
+        launch_counts_to_flux<F>(ncol, b.t.tod_dn_dif, U, bg_out[2], st);
+        BgLevels<F> per_layer{};
+        for (int l=0; l<nbg; ++l) per_layer.v[l] = (U / dz_bg[l]) / F(ncol);
+        bg_counts_to_flux_kernel<F><<<ceil_div(nbg, 64), 64, 0, st>>>(nbg, b.t.bg_abs_dir, per_layer, bg_out[3]);
+        bg_counts_to_flux_kernel<F><<<ceil_div(nbg, 64), 64, 0, st>>>(nbg, b.t.bg_abs_dif, per_layer, bg_out[4]);
+    }
+    launch_counts_to_flux<F>(ncol, c, U, sfc_dn_dir, st);
+    launch_counts_to_flux<F>(ncol, c + ncol, U, sfc_dn_dif, st);
+    launch_counts_to_flux<F>(ncol, c + 2*ncol, U, sfc_up, st);
+    launch_counts_to_flux<F>(ncol, c + 3*ncol, U, tod_up, st);
+    launch_counts_to_flux<F>(ncol*nz, c + n_sfc, U / dz, abs_dir, st);
+    launch_counts_to_flux<F>(ncol*nz, c + n_sfc + ncol*nz, U / dz, abs_dif, st);
+    RRX_CATCH(entry)
+}
 }  // namespace
 
 extern "C"
@@ -873,7 +1210,50 @@ int rrx_raytracer_sw_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBoo
                                cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, \
                                photons_per_pixel, seed, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
                                PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, true, bg_out, nbg, dz_bg, bg_tau, bg_ssa, \
-                               bg_cld_tau, bg_cld_ssa, bg_cld_g, &aer, &bg_aer); }
+                               bg_cld_tau, bg_cld_ssa, bg_cld_g, &aer, &bg_aer); } \
+int rrx_rt_k_null_all##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, const F* tau, const int* band_lims_gpt, \
+        const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, const F* aer_tau, void* stream) \
+{ return k_null_all_entry<F>("rrx_rt_k_null_all" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null, \
+                             aer_tau, stream); } \
+int rrx_rt_bg_profile_all##SFX(int nbg, int ngpt, int nbnd, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const int* band_lims_gpt, \
+        const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* bg_profile, \
+        const F* bg_aer_tau, const F* bg_aer_ssa, const F* bg_aer_g, void* stream) \
+{ return bg_profile_all_entry<F>("rrx_rt_bg_profile_all" #SFX, nbg, ngpt, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, \
+                                 bg_cld_g, bg_profile, AerIn<F>{bg_aer_tau, bg_aer_ssa, bg_aer_g}, stream); } \
+int rrx_rt_trace_counts_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const long long* photon_end, const F* weight0, const F* dif_frac, \
+        int knx, int kny, int knz, const F* k_null, \
+        unsigned long long seed, long long photon0, long long nphotons, int max_events, \
+        unsigned long long* sfc_dn_dir, unsigned long long* sfc_dn_dif, unsigned long long* sfc_up, unsigned long long* tod_up, \
+        unsigned long long* abs_dir, unsigned long long* abs_dif, unsigned long long* n_capped, \
+        unsigned long long* toa_up, unsigned long long* tod_dn_dir, unsigned long long* tod_dn_dif, \
+        unsigned long long* bg_abs_dir, unsigned long long* bg_abs_dif, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_profile, const F* aer_tau, const F* aer_ssa, const F* aer_g, void* stream) \
+{ return trace_spectral_entry<F>("rrx_rt_trace_counts_spectral" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, independent_column, tau, ssa, \
+                                 band_lims_gpt, cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, photon_end, weight0, dif_frac, \
+                                 knx, kny, knz, k_null, seed, photon0, nphotons, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, \
+                                 abs_dif, n_capped, BgTallies<F>{toa_up, tod_dn_dir, tod_dn_dif, bg_abs_dir, bg_abs_dif}, \
+                                 PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, nbg, dz_bg, bg_profile, \
+                                 AerIn<F>{aer_tau, aer_ssa, aer_g}, stream); } \
+int rrx_raytracer_sw_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
+        const long long* photons_per_pixel_gpt, unsigned long long seed, int max_events, \
+        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, \
+        F* toa_up, F* tod_dn_dir, F* tod_dn_dif, F* bg_abs_dir, F* bg_abs_dif, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, \
+        const F* const* aer3, const F* const* bg_aer3, void* stream) \
+{ F* const bg_out[5] = {toa_up, tod_dn_dir, tod_dn_dif, bg_abs_dir, bg_abs_dif}; \
+  const AerIn<F> aer = aer3 != nullptr ? AerIn<F>{aer3[0], aer3[1], aer3[2]} : AerIn<F>{}; \
+  const AerIn<F> bg_aer = bg_aer3 != nullptr ? AerIn<F>{bg_aer3[0], bg_aer3[1], bg_aer3[2]} : AerIn<F>{}; \
+  return raytracer_sw_spectral_entry<F>("rrx_raytracer_sw_spectral" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, independent_column, tau, ssa, \
+                               band_lims_gpt, cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, \
+                               photons_per_pixel_gpt, seed, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
+                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, bg_out, nbg, dz_bg, bg_tau, bg_ssa, \
+                               bg_cld_tau, bg_cld_ssa, bg_cld_g, aer, bg_aer); }
 
 RRX_DEFINE_RT(double, _f64)
 RRX_DEFINE_RT(float, _f32)

@@ -239,6 +239,63 @@ template<typename F> __device__ __forceinline__ int wrapped_cell(const F pos, co
     return clampi(int((pos - floor(pos/len)*len) / d), 0, n - 1);
 }
 
+// ---- all g-points in one launch of the forward tracer: the photons of a launch are the concatenation, in g-point order,
+// of n_g photons per g-point; photon_end (ngpt + 1) holds the prefix sums, photon_end[0] = 0. Global index p belongs to the g with
+// photon_end[g] <= p < photon_end[g+1] (empty ranges are stepped over), its local index is q = p - photon_end[g], its stream
+// Stream::start(q, g) and its pixel q mod ncol: photon q of the per-g-point launch of g. Every deposit is to_count(w weight0[g]).
+constexpr int RT_SPECTRAL_MAX_GPT = 1024;          // photon_end and the band table live in LDS: 12 bytes per g-point
+
+// kn_g0: the g-point of the first slice of the k_null array that the launch is given (0 for the array of all g-points)
+template<typename F> struct SpecIn { int ngpt; int kn_g0; const long long* photon_end; const F* weight0; const F* dif_frac; };
+
+// photon_end and the band of every g-point (-1: in no band, or no band_lims_gpt) in LDS
+struct SpecView { const long long* photon_end; const int* band; int ngpt; };
+
+// LDS of the spectral form: photon_end, the background's levels, the band table (the profile rows stay in global memory)
+inline size_t spectral_lds_bytes(const int ngpt, const int nbg, const size_t size_of_f)
+{
+    return size_t(ngpt + 1)*sizeof(long long) + size_t(nbg + 1)*size_of_f + size_t(ngpt)*sizeof(int);
+}
+
+// every thread of the workgroup calls it before its loop; lds: spectral_lds_bytes. bg gets nbg and the levels; its profile rows are
+// set per photon (they point into the profile of all g-points)
+template<typename F>
+__device__ __forceinline__ SpecView stage_spectral(const SpecIn<F>& sp, const BgIn<F>& in, const int nbnd, const int* __restrict__ band_lims_gpt,
+                                                   double* lds, BgView<F>& bg)
+{
+    long long* pe = reinterpret_cast<long long*>(lds);
+    F* lev = reinterpret_cast<F*>(pe + sp.ngpt + 1);
+    int* band = reinterpret_cast<int*>(lev + in.nbg + 1);
+    for (int n=threadIdx.x; n<=sp.ngpt; n+=blockDim.x) pe[n] = sp.photon_end[n];
+    for (int n=threadIdx.x; n<in.nbg+1; n+=blockDim.x) lev[n] = in.nbg > 0 ? in.z.v[n] : F(0.);
+    for (int g=threadIdx.x; g<sp.ngpt; g+=blockDim.x) band[g] = band_lims_gpt != nullptr ? band_of(g, nbnd, band_lims_gpt) : -1;
+    __syncthreads();
+    bg = BgView<F>{in.nbg, nullptr, nullptr, nullptr, nullptr, nullptr, lev};
+    return SpecView{pe, band, sp.ngpt};
+}
+
+// the g-point of global photon p: the smallest g with photon_end[g+1] > p; ngpt when p lies beyond the list
+__device__ __forceinline__ int gpt_of_photon(const long long* photon_end, const int ngpt, const long long p)
+{
+    int lo = 0, hi = ngpt;
+    while (lo < hi)
+    {
+        const int mid = (lo + hi) >> 1;
+        if (photon_end[mid + 1] <= p) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// the profile rows of g-point igpt in the profile (ngpt, ROWS, nbg+1) of all g-points
+template<typename F, int ROWS>
+__device__ __forceinline__ void bg_rows_of_gpt(BgView<F>& bg, const F* __restrict__ profile_all, const int igpt)
+{
+    const int n1 = bg.nbg + 1;
+    const F* p = profile_all + size_t(igpt)*ROWS*n1;
+    bg.k_ext = p + BG_K_EXT*n1; bg.k_sca = p + BG_K_SCA*n1; bg.k_sca_cld = p + BG_K_SCA_CLD*n1; bg.g = p + BG_G*n1;
+    bg.tau_above = p + BG_TAU_ABOVE*n1;
+}
+
 // ---- host side: the argument checks of the entries (they throw; RRX_CATCH names the entry)
 
 inline void check_grid(const int nx, const int ny, const int nz, const int knx, const int kny, const int knz)

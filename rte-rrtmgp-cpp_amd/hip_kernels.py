@@ -861,6 +861,98 @@ class HipKernels:
         out["n_capped"] = int(n_capped.item())
         return out
 
+    # All g-points in one launch of the forward tracer, photons dealt per g-point (rrx_rt_k_null_all, rrx_rt_bg_profile_all,
+    # rrx_rt_trace_counts_spectral, rrx_raytracer_sw_spectral). Built on the aerosol form: aerosol= and
+    # background.aerosol as above, None for none. ngpt <= 1024.
+    def rt_k_null_all(self, tau, nx, ny, dz, kn_grid, top_at_1, cloud=None, band_lims=None, aerosol=None):
+        """k_null (ngpt, knz, kny, knx): slice g is rt_k_null(..., igpt=g, aerosol=...)"""
+        dims, (_, ct, _, _) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        knx, kny, knz = (int(k) for k in kn_grid)
+        at = None if aerosol is None else aerosol[0]
+        if at is not None and band_lims is None:
+            raise ValueError("raytracer: an aerosol triple needs band_lims")
+        out = self.empty((dims[3], knz, kny, knx))
+        self._c("rt_k_null_all", *dims, top_at_1, tau, band_lims if (cloud is not None or at is not None) else None, ct, dz, knx, kny, knz,
+                out, at)
+        return out
+
+    def rt_bg_profile_all(self, background, band_lims=None):
+        """The profile (ngpt, 7, nbg+1): slice g is rt_bg_profile(background, g, band_lims, aerosol=the background's triple)"""
+        dz = self._rt_bg_dz(background)
+        ngpt = background.tau.shape[0]
+        cloud = (None, None, None) if background.cloud is None else tuple(background.cloud)
+        bg_aer = self._rt_bg_aerosol(background)
+        if (background.cloud is not None or bg_aer[0] is not None) and band_lims is None:
+            raise ValueError("raytracer: a background cloud or aerosol triple needs band_lims")
+        nbnd = int(band_lims.shape[0]) if band_lims is not None else 0
+        out = self.empty((ngpt, 7, dz.size + 1))
+        self._c("rt_bg_profile_all", dz.size, ngpt, nbnd, dz, background.tau, background.ssa,
+                band_lims if (background.cloud is not None or bg_aer[0] is not None) else None, *cloud, out, *bg_aer)
+        return out
+
+    def rt_trace_counts_spectral(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, photon_end, weight0, dif_frac, kn_grid, k_null,
+                                 seed, photon0, nphotons, top_at_1=False, independent_column=False, cloud=None, band_lims=None, counts=None,
+                                 max_events=None, phase=None, background=None, bg_profile=None, aerosol=None):
+        """Adds the photons [photon0, photon0 + nphotons) of the concatenated list into counts (rt_zero_counts_bg; made when None).
+        photon_end (ngpt+1,) int64, weight0, dif_frac (ngpt,): arrays on the host, checked and uploaded here; k_null is
+        rt_k_null_all's and bg_profile rt_bg_profile_all's (made when None)."""
+        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        ngpt = dims[3]
+        knx, kny, knz = (int(k) for k in kn_grid)
+        photon_end = np.ascontiguousarray(np.asarray(photon_end, dtype=np.int64).reshape(-1))
+        weight0 = np.ascontiguousarray(np.asarray(weight0, dtype=self.np_dtype).reshape(-1))
+        dif_frac = np.ascontiguousarray(np.asarray(dif_frac, dtype=self.np_dtype).reshape(-1))
+        if photon_end.size != ngpt + 1 or weight0.size != ngpt or dif_frac.size != ngpt:
+            raise ValueError("raytracer: photon_end is (ngpt+1,) and weight0, dif_frac are (ngpt,)")
+        if photon_end[0] != 0 or np.any(np.diff(photon_end) < 0):
+            raise ValueError("raytracer: photon_end must start at 0 and must not descend")
+        if photon0 + nphotons > int(photon_end[-1]):
+            raise ValueError(f"raytracer: the range [{photon0}, {photon0 + nphotons}) ends beyond the list of {int(photon_end[-1])} photons")
+        nbg, dzb = (0, None) if background is None else (len(background.dz), self._rt_bg_dz(background))
+        _, aer_grid, _ = self._rt_aerosol(aerosol, background, band_lims)
+        if background is not None and bg_profile is None:
+            bg_profile = self.rt_bg_profile_all(background, band_lims)
+        counts = self.rt_zero_counts_bg(dims[2], dims[0]*dims[1], nbg) if counts is None else counts
+        dev = [torch.as_tensor(a, device=self.device) for a in (photon_end, weight0, dif_frac)]
+        self._c("rt_trace_counts_spectral", *dims, top_at_1, independent_column, tau, ssa,
+                band_lims if (cloud is not None or aer_grid[0] is not None) else None, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, *dev,
+                knx, kny, knz, k_null, int(seed) & 0xFFFFFFFFFFFFFFFF, photon0, nphotons,
+                self.RT_MAX_EVENTS if max_events is None else max_events, *(counts[k] for k in self.RT_COUNTS), counts["n_capped"],
+                *(counts[k] for k in self.RT_BG_COUNTS), *self._rt_table_args("rt_trace_counts_bg", phase, dims), nbg, dzb, bg_profile, *aer_grid)
+        return counts
+
+    def raytracer_sw_spectral(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, photons_per_pixel_gpt,
+                              seed, top_at_1=False, independent_column=False, cloud=None, band_lims=None, max_events=None, phase=None,
+                              background=None, aerosol=None):
+        """raytracer_sw_bg with photons_per_pixel_gpt (ngpt,) photons per pixel of each g-point (pipeline.spectral_allocation deals
+        them by flux) in place of photons_per_pixel, all g-points in one trace launch per chunk. The same outputs."""
+        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        nz, ngpt, ncol = dims[2], dims[3], dims[0]*dims[1]
+        knx, kny, knz = (int(k) for k in kn_grid)
+        inc_dir = np.ascontiguousarray(np.asarray(inc_dir, dtype=self.np_dtype).reshape(-1))
+        inc_dif = np.ascontiguousarray(np.asarray(inc_dif, dtype=self.np_dtype).reshape(-1))
+        m = np.ascontiguousarray(np.asarray(photons_per_pixel_gpt, dtype=np.int64).reshape(-1))
+        if inc_dir.size != ngpt or inc_dif.size != ngpt or m.size != ngpt:
+            raise ValueError("raytracer: inc_dir, inc_dif, photons_per_pixel_gpt are (ngpt,)")
+        medium = self._rt_bg_medium(background)
+        if background is not None and background.cloud is not None and band_lims is None:
+            raise ValueError("raytracer: a background cloud triple needs band_lims")
+        _, aer_grid, aer_bg = self._rt_aerosol(aerosol, background, band_lims)
+        lims_all = band_lims if (cloud is not None or (background is not None and background.cloud is not None)
+                                 or aer_grid[0] is not None or aer_bg[0] is not None) else None
+        out = {k: self.empty((ncol,)) for k in self.RT_COUNTS[:4]}
+        out.update({k: self.empty((nz, ncol)) for k in self.RT_COUNTS[4:]})
+        out.update({k: self.zeros((ncol,)) for k in self.RT_BG_COUNTS[:3]})
+        out.update({k: self.zeros((medium[0],)) for k in self.RT_BG_COUNTS[3:]})
+        n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        self._c("raytracer_sw_spectral", *dims, top_at_1, independent_column, tau, ssa, lims_all, ct, cw, cg, dx, dy,
+                dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, m, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                self.RT_MAX_EVENTS if max_events is None else max_events, *(out[k] for k in self.RT_COUNTS), n_capped,
+                *(out[k] if medium[0] else None for k in self.RT_BG_COUNTS), *self._rt_table_args("raytracer_sw_bg", phase, dims), *medium,
+                self._rt_triple(aer_grid), self._rt_triple(aer_bg))
+        out["n_capped"] = int(n_capped.item())
+        return out
+
     def rt_bw_trace_counts_bg(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, kn_grid, k_null, camera, seed, ray0, nrays,
                               top_at_1=False, cloud=None, band_lims=None, counts=None, max_events=None, phase=None, background=None,
                               bg_profile=None, aerosol=None):

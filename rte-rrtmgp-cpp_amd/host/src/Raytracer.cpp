@@ -1,5 +1,10 @@
 // Raytracer_gpu: checks the shapes and forwards to rrx_raytracer_sw; a non-zero status becomes std::runtime_error.
 #include "Raytracer.h"
+#include <algorithm>
+#include <cmath>
+#include <numeric>
+#include <string>
+#include <vector>
 
 unsigned long long Raytracer_gpu::trace_rays(
         const int nx, const int ny, const int nz,
@@ -158,6 +163,141 @@ unsigned long long Raytracer_gpu::trace_rays(
                  nbg, dz_bg.ptr(), bg_tau.ptr(), bg_ssa.ptr(), bg_cloudy ? bg_cld_tau.ptr() : none, bg_cloudy ? bg_cld_ssa.ptr() : none,
                  bg_cloudy ? bg_cld_g.ptr() : none);
     return n_capped({1});
+}
+
+unsigned long long Raytracer_gpu::trace_rays_spectral(
+        const int nx, const int ny, const int nz,
+        const Float dx, const Float dy, const Float dz,
+        const bool top_at_1, const bool independent_column,
+        const Array_gpu<Float,3>& tau, const Array_gpu<Float,3>& ssa,
+        const Array_gpu<int,2>& band_lims_gpt,
+        const Array_gpu<Float,3>& cld_tau, const Array_gpu<Float,3>& cld_ssa, const Array_gpu<Float,3>& cld_g,
+        const Array_gpu<Float,1>& sfc_albedo,
+        const Float mu0, const Float azimuth,
+        const Array<Float,1>& inc_dir, const Array<Float,1>& inc_dif,
+        const int knx, const int kny, const int knz,
+        const Array<long long,1>& photons_per_pixel_gpt, const unsigned long long seed, const int max_events,
+        Array_gpu<Float,1>& sfc_dn_dir, Array_gpu<Float,1>& sfc_dn_dif, Array_gpu<Float,1>& sfc_up, Array_gpu<Float,1>& tod_up,
+        Array_gpu<Float,2>& abs_dir, Array_gpu<Float,2>& abs_dif,
+        Array_gpu<Float,1>& toa_up, Array_gpu<Float,1>& tod_dn_dir, Array_gpu<Float,1>& tod_dn_dif,
+        Array_gpu<Float,1>& bg_abs_dir, Array_gpu<Float,1>& bg_abs_dif)
+{
+    const std::string who = "Raytracer_gpu::trace_rays_spectral: ";
+    if (nx < 0 || ny < 0 || nz < 0) throw std::runtime_error(who + "negative extent");
+    const long long ncol = (long long)nx*ny;
+    const int ngpt = tau.dim(3);
+    const int nbnd = band_lims_gpt.dim(2);
+    const int nbg = has_bg ? dz_bg.size() : 0;
+    if (tau.dim(1) != ncol || tau.dim(2) != nz || ssa.get_dims() != tau.get_dims()) throw std::runtime_error(who + "tau, ssa are not (nx ny, nz, ngpt)");
+    const bool cloudy = cld_tau.size() > 0;
+    if (cloudy && (cld_tau.dim(1) != ncol || cld_tau.dim(2) != nz || cld_tau.dim(3) != nbnd || cld_ssa.get_dims() != cld_tau.get_dims() ||
+                   cld_g.get_dims() != cld_tau.get_dims()))
+        throw std::runtime_error(who + "the cloud arrays are not (nx ny, nz, nbnd)");
+    if (!cloudy && (cld_ssa.size() > 0 || cld_g.size() > 0)) throw std::runtime_error(who + "the cloud arrays are all empty or all given");
+    if (sfc_albedo.size() != ncol || inc_dir.size() != ngpt || inc_dif.size() != ngpt || photons_per_pixel_gpt.size() != ngpt)
+        throw std::runtime_error(who + "sfc_albedo is not (nx ny) or inc_dir, inc_dif, photons_per_pixel_gpt are not (ngpt)");
+    for (const Array_gpu<Float,1>* a : {&sfc_dn_dir, &sfc_dn_dif, &sfc_up, &tod_up})
+        if (a->size() != ncol) throw std::runtime_error(who + "a flux array is not (nx ny)");
+    for (const Array_gpu<Float,2>* a : {&abs_dir, &abs_dif})
+        if (a->dim(1) != ncol || a->dim(2) != nz) throw std::runtime_error(who + "an absorption array is not (nx ny, nz)");
+    if (has_bg)
+    {
+        for (const Array_gpu<Float,1>* a : {&toa_up, &tod_dn_dir, &tod_dn_dif})
+            if (a->size() != ncol) throw std::runtime_error(who + "a flux array is not (nx ny)");
+        for (const Array_gpu<Float,1>* a : {&bg_abs_dir, &bg_abs_dif})
+            if (a->size() != nbg) throw std::runtime_error(who + "a background absorption array is not (nbg)");
+        if (bg_tau.dim(2) != ngpt) throw std::runtime_error(who + "the background's bg_tau, bg_ssa are not (nbg, ngpt)");
+    }
+    const bool bg_cloudy = has_bg && bg_cld_tau.size() > 0;
+    if (bg_cloudy && bg_cld_tau.dim(2) != nbnd) throw std::runtime_error(who + "the background's cloud arrays are not (nbg, nbnd)");
+    if (has_table && (cld_re.dim(1) != ncol || cld_re.dim(2) != nz || phase.dim(3) != nbnd))
+        throw std::runtime_error(who + "the phase table's cld_re is not (nx ny, nz) or its tables are not (nmu, nre, nbnd)");
+    const bool hazy = has_aer && aer_tau.size() > 0;
+    if (hazy && (aer_tau.dim(1) != ncol || aer_tau.dim(2) != nz || aer_tau.dim(3) != nbnd))
+        throw std::runtime_error(who + "the aerosol arrays are not (nx ny, nz, nbnd)");
+    const bool bg_hazy = has_aer && bg_aer_tau.size() > 0;
+    if (bg_hazy && !has_bg) throw std::runtime_error(who + "a background aerosol is set without a background");
+    if (bg_hazy && (bg_aer_tau.dim(1) != nbg || bg_aer_tau.dim(2) != nbnd))
+        throw std::runtime_error(who + "the background's aerosol arrays are not (nbg, nbnd)");
+
+    Array_gpu<unsigned long long,1> n_capped({1});
+    const Float* none = nullptr;
+    Float* no_out = nullptr;
+    const Float* const grid3[3] = {hazy ? aer_tau.ptr() : none, hazy ? aer_ssa.ptr() : none, hazy ? aer_g.ptr() : none};
+    const Float* const aloft3[3] = {bg_hazy ? bg_aer_tau.ptr() : none, bg_hazy ? bg_aer_ssa.ptr() : none, bg_hazy ? bg_aer_g.ptr() : none};
+    RRX_CALL(rrx_raytracer_sw_spectral, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
+             tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
+             cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
+             dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), inc_dif.ptr(), knx, kny, knz,
+             photons_per_pixel_gpt.ptr(), seed, max_events,
+             sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr(),
+             has_bg ? toa_up.ptr() : no_out, has_bg ? tod_dn_dir.ptr() : no_out, has_bg ? tod_dn_dif.ptr() : no_out,
+             has_bg ? bg_abs_dir.ptr() : no_out, has_bg ? bg_abs_dif.ptr() : no_out,
+             has_table ? mu.dim(1) : 0, has_table ? phase.dim(2) : 0, re0, dre, has_table ? mu.ptr() : none, has_table ? phase.ptr() : none,
+             has_table ? cdf.ptr() : none, has_table ? cld_re.ptr() : none,
+             nbg, has_bg ? dz_bg.ptr() : none, has_bg ? bg_tau.ptr() : none, has_bg ? bg_ssa.ptr() : none,
+             bg_cloudy ? bg_cld_tau.ptr() : none, bg_cloudy ? bg_cld_ssa.ptr() : none, bg_cloudy ? bg_cld_g.ptr() : none, grid3, aloft3);
+    return n_capped({1});
+}
+
+// The allocation of pipeline.spectral_allocation, operation for operation in double: the floor takes out the g-points whose
+// proportional share of what the others leave is below it, the rest is dealt by largest remainders, ties to the lower g.
+Array<long long,1> Raytracer_gpu::spectral_allocation(const Array<Float,1>& inc_in, const long long P, const long long floor_)
+{
+    const std::string who = "Raytracer_gpu::spectral_allocation: ";
+    const int ngpt = inc_in.size();
+    std::vector<double> inc(ngpt);
+    for (int g=0; g<ngpt; ++g)
+    {
+        inc[g] = double(inc_in({g+1}));
+        if (!(inc[g] >= 0.) || !std::isfinite(inc[g])) throw std::runtime_error(who + "inc must be finite and >= 0");
+    }
+    if (floor_ < 0) throw std::runtime_error(who + "min_per_gpt must be >= 0");
+    std::vector<char> active(ngpt), free_(ngpt);
+    long long n_active = 0;
+    for (int g=0; g<ngpt; ++g) { active[g] = inc[g] > 0.; free_[g] = active[g]; n_active += active[g]; }
+    if (P < 0 || P < floor_*n_active || (P > 0 && n_active == 0))
+        throw std::runtime_error(who + "P = " + std::to_string(P) + " photons per pixel cannot give " + std::to_string(floor_) + " to each of "
+                                 + std::to_string(n_active) + " active g-points");
+    std::vector<long long> m(ngpt);
+    for (int g=0; g<ngpt; ++g) m[g] = active[g] ? floor_ : 0;
+    const auto rest_and_total = [&](long long& rest, double& total, bool& any)
+    {
+        rest = P; total = 0.; any = false;
+        for (int g=0; g<ngpt; ++g) { if (free_[g]) { total += inc[g]; any = true; } else rest -= m[g]; }
+    };
+    long long rest; double total; bool any;
+    for (;;)
+    {
+        rest_and_total(rest, total, any);
+        if (!any || total <= 0.) break;
+        bool bound = false;
+        for (int g=0; g<ngpt; ++g)
+            if (free_[g] && double(rest)*(inc[g]/total) < double(floor_)) { free_[g] = 0; bound = true; }
+        if (!bound) break;
+    }
+    rest_and_total(rest, total, any);
+    std::vector<int> order(ngpt);
+    std::iota(order.begin(), order.end(), 0);
+    if (any)
+    {
+        std::vector<double> remainder(ngpt, -1.);
+        long long left = rest;
+        for (int g=0; g<ngpt; ++g)
+            if (free_[g])
+            {
+                const double quota = double(rest)*(inc[g]/total);
+                m[g] = (long long)std::floor(quota);
+                remainder[g] = quota - double(m[g]);
+                left -= m[g];
+            }
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return remainder[a] > remainder[b]; });
+        for (long long i=0; i<left; ++i) m[order[i]] += 1;
+    }
+    // (the floor never binds everywhere: the shares of the free g-points add up to what is left, which is at least their floors)
+    Array<long long,1> out({ngpt});
+    for (int g=0; g<ngpt; ++g) out({g+1}) = m[g];
+    return out;
 }
 
 void Raytracer_gpu::set_background(const Array<Float,1>& dz_in, const Array_gpu<Float,2>& tau_in, const Array_gpu<Float,2>& ssa_in,

@@ -207,10 +207,13 @@ int rrx_cxx_driver_fluxes(void* h, const Float** ptrs)
 // and out5 is not written.
 // rrx_cxx_trace_rays_aer: the same after Raytracer_gpu::set_aerosol(aer_* (ncol, nz, nbnd) or all NULL, bg_aer_* (nbg, nbnd) or all NULL), called
 // when any of the six is given; a background aerosol with nbg = 0 is handed over as one layer, so that the class refuses it.
-int rrx_cxx_trace_rays_aer(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+// rrx_cxx_trace_rays_spectral: the same through Raytracer_gpu::trace_rays_spectral with photons_per_pixel_gpt (ngpt) on the HOST
+// (DESIGN.md 4.19); rrx_cxx_spectral_allocation: Raytracer_gpu::spectral_allocation into m (ngpt) on the HOST.
+static int trace_rays_forward(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
         const int top_at_1, const int independent_column, const Float* tau, const Float* ssa, const int* band_lims_gpt,
         const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
         const Float* inc_dir, const Float* inc_dif, const int knx, const int kny, const int knz, const long long photons_per_pixel,
+        const long long* photons_per_pixel_gpt,
         const unsigned long long seed, const int max_events, Float* const* out6, unsigned long long* n_capped, Float* const* out5,
         const int nmu, const int nre, const Float re0, const Float dre, const Float* mu, const Float* phase, const Float* cdf, const Float* cld_re,
         const int nbg, const Float* dz_bg, const Float* bg_tau, const Float* bg_ssa, const Float* bg_cld_tau, const Float* bg_cld_ssa,
@@ -245,7 +248,18 @@ int rrx_cxx_trace_rays_aer(const int nx, const int ny, const int nz, const int n
             if (any_aer)
                 raytracer.set_aerosol(view3(aer_tau, ncol, nz, nbnd), view3(aer_ssa, ncol, nz, nbnd), view3(aer_g, ncol, nz, nbnd),
                                       bview(bg_aer_tau, nb, nbnd), bview(bg_aer_ssa, nb, nbnd), bview(bg_aer_g, nb, nbnd));
-            if (nbg > 0)
+            if (photons_per_pixel_gpt != nullptr)
+            {
+                Array<long long,1> h_m({ngpt});
+                for (int g=1; g<=ngpt; ++g) h_m({g}) = photons_per_pixel_gpt[g-1];
+                Array_gpu<Float,1> b0, b1, b2, b3, b4;
+                if (nbg > 0) { b0 = view1(out5[0], ncol); b1 = view1(out5[1], ncol); b2 = view1(out5[2], ncol); b3 = view1(out5[3], nbg); b4 = view1(out5[4], nbg); }
+                *n_capped = raytracer.trace_rays_spectral(nx, ny, nz, dx, dy, dz, top_at_1 != 0, independent_column != 0,
+                        view3(tau, ncol, nz, ngpt), view3(ssa, ncol, nz, ngpt), Array_gpu<int,2>(const_cast<int*>(band_lims_gpt), {2, nbnd}),
+                        view3(cld_tau, ncol, nz, nbnd), view3(cld_ssa, ncol, nz, nbnd), view3(cld_g, ncol, nz, nbnd), view1(sfc_albedo, ncol),
+                        mu0, azimuth, h_dir, h_dif, knx, kny, knz, h_m, seed, max_events, o0, o1, o2, o3, o4, o5, b0, b1, b2, b3, b4);
+            }
+            else if (nbg > 0)
             {
                 Array_gpu<Float,1> b0 = view1(out5[0], ncol), b1 = view1(out5[1], ncol), b2 = view1(out5[2], ncol);
                 Array_gpu<Float,1> b3 = view1(out5[3], nbg), b4 = view1(out5[4], nbg);
@@ -262,6 +276,50 @@ int rrx_cxx_trace_rays_aer(const int nx, const int ny, const int nz, const int n
         }
         catch (...) { rrx_host::set_stream(before); throw; }
         rrx_host::set_stream(before);
+    });
+}
+
+int rrx_cxx_trace_rays_aer(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+        const int top_at_1, const int independent_column, const Float* tau, const Float* ssa, const int* band_lims_gpt,
+        const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
+        const Float* inc_dir, const Float* inc_dif, const int knx, const int kny, const int knz, const long long photons_per_pixel,
+        const unsigned long long seed, const int max_events, Float* const* out6, unsigned long long* n_capped, Float* const* out5,
+        const int nmu, const int nre, const Float re0, const Float dre, const Float* mu, const Float* phase, const Float* cdf, const Float* cld_re,
+        const int nbg, const Float* dz_bg, const Float* bg_tau, const Float* bg_ssa, const Float* bg_cld_tau, const Float* bg_cld_ssa,
+        const Float* bg_cld_g, const Float* aer_tau, const Float* aer_ssa, const Float* aer_g, const Float* bg_aer_tau, const Float* bg_aer_ssa,
+        const Float* bg_aer_g, void* stream)
+{
+    return trace_rays_forward(nx, ny, nz, ngpt, nbnd, dx, dy, dz, top_at_1, independent_column, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g,
+                              sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, photons_per_pixel, nullptr, seed, max_events, out6, n_capped,
+                              out5, nmu, nre, re0, dre, mu, phase, cdf, cld_re, nbg, dz_bg, bg_tau, bg_ssa, bg_cld_tau, bg_cld_ssa, bg_cld_g,
+                              aer_tau, aer_ssa, aer_g, bg_aer_tau, bg_aer_ssa, bg_aer_g, stream);
+}
+
+int rrx_cxx_trace_rays_spectral(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+        const int top_at_1, const int independent_column, const Float* tau, const Float* ssa, const int* band_lims_gpt,
+        const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
+        const Float* inc_dir, const Float* inc_dif, const int knx, const int kny, const int knz, const long long* photons_per_pixel_gpt,
+        const unsigned long long seed, const int max_events, Float* const* out6, unsigned long long* n_capped, Float* const* out5,
+        const int nmu, const int nre, const Float re0, const Float dre, const Float* mu, const Float* phase, const Float* cdf, const Float* cld_re,
+        const int nbg, const Float* dz_bg, const Float* bg_tau, const Float* bg_ssa, const Float* bg_cld_tau, const Float* bg_cld_ssa,
+        const Float* bg_cld_g, const Float* aer_tau, const Float* aer_ssa, const Float* aer_g, const Float* bg_aer_tau, const Float* bg_aer_ssa,
+        const Float* bg_aer_g, void* stream)
+{
+    if (photons_per_pixel_gpt == nullptr) return guarded([&] { throw std::runtime_error("rrx_cxx_trace_rays_spectral: photons_per_pixel_gpt is NULL"); });
+    return trace_rays_forward(nx, ny, nz, ngpt, nbnd, dx, dy, dz, top_at_1, independent_column, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g,
+                              sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, 0, photons_per_pixel_gpt, seed, max_events, out6, n_capped,
+                              out5, nmu, nre, re0, dre, mu, phase, cdf, cld_re, nbg, dz_bg, bg_tau, bg_ssa, bg_cld_tau, bg_cld_ssa, bg_cld_g,
+                              aer_tau, aer_ssa, aer_g, bg_aer_tau, bg_aer_ssa, bg_aer_g, stream);
+}
+
+int rrx_cxx_spectral_allocation(const int ngpt, const Float* inc, const long long P, const long long min_per_gpt, long long* m)
+{
+    return guarded([&]
+    {
+        Array<Float,1> h_inc({ngpt});
+        for (int g=1; g<=ngpt; ++g) h_inc({g}) = inc[g-1];
+        const Array<long long,1> out = Raytracer_gpu::spectral_allocation(h_inc, P, min_per_gpt);
+        for (int g=1; g<=ngpt; ++g) m[g-1] = out({g});
     });
 }
 

@@ -182,9 +182,78 @@ def solve_sw(be, kd, atm, col_dry=None, cloud_lut=None, delta_cloud=False, do_br
     return out
 
 
+def spectral_allocation(inc, P, min_per_gpt=1):
+    """m (ngpt,) int64, photons per pixel of every g-point: P dealt over the active g-points (inc > 0) in proportion to inc by
+    largest remainders on the shares inc_g / sum(inc) in float64, ties to the lower g. Every active g-point gets at least min_per_gpt
+    (no g-point with flux is left out: the estimator stays unbiased), an inactive one 0. Raises when P < min_per_gpt x the number of
+    active g-points."""
+    inc = np.asarray(inc, dtype=np.float64).reshape(-1)
+    P, floor = int(P), int(min_per_gpt)
+    if np.any(inc < 0) or not np.all(np.isfinite(inc)):
+        raise ValueError("spectral_allocation: inc must be finite and >= 0")
+    if floor < 0:
+        raise ValueError("spectral_allocation: min_per_gpt must be >= 0")
+    active = inc > 0
+    n_active = int(active.sum())
+    if P < floor*n_active or (P > 0 and n_active == 0) or P < 0:
+        raise ValueError(f"spectral_allocation: P = {P} photons per pixel cannot give {floor} to each of {n_active} active g-points")
+    m = np.where(active, floor, 0).astype(np.int64)
+    free = active.copy()                                   # the g-points that the floor does not bind
+    # the floor binds a g-point whose proportional share of what the others leave is below it: take those out, deal the rest again
+    while True:
+        rest = P - int(m[~free].sum())
+        total = float(inc[free].sum())
+        if not free.any() or total <= 0.0:
+            break
+        quota = np.where(free, rest * (inc / total), 0.0)
+        bound = free & (quota < floor)
+        if not bound.any():
+            break
+        free &= ~bound
+    if free.any():
+        rest = P - int(m[~free].sum())
+        quota = np.where(free, rest * (inc / float(inc[free].sum())), 0.0)
+        base = np.floor(quota).astype(np.int64)
+        m = np.where(free, base, m)
+        left = rest - int(base[free].sum())
+        remainder = np.where(free, quota - base, -1.0)
+        order = np.argsort(-remainder, kind="stable")      # (stable: ties go to the lower g)
+        m[order[:left]] += 1
+    # (the floor never binds everywhere: the shares of the free g-points add up to what is left, which is at least their floors)
+    assert int(m.sum()) == P and np.all(m[active] >= floor) and not m[~active].any()
+    return m
+
+
+def spectral_photon_list(inc_dir, inc_dif, m, ncol, dtype):
+    """What rrx_raytracer_sw_spectral forms from m (ngpt,) photons per pixel, in the precision dtype: photon_end (ngpt+1,) int64,
+    weight0, dif_frac (ngpt,) and the common unit U = S / P (flux = counts 2^-32 U). weight0[g] = (inc_g / F(m_g)) / (S / F(P)),
+    S the sum of inc_g = inc_dir[g] + inc_dif[g] over the g-points with m_g > 0 in index order, P = sum(m)."""
+    dt = np.dtype(dtype)
+    F = dt.type
+    m = np.asarray(m, dtype=np.int64).reshape(-1)
+    inc_dir, inc_dif = np.asarray(inc_dir, dtype=dt).reshape(-1), np.asarray(inc_dif, dtype=dt).reshape(-1)
+    if np.any(m < 0):
+        raise ValueError("spectral_photon_list: photons_per_pixel_gpt is negative")
+    photon_end = np.concatenate([[0], np.cumsum(m * int(ncol))]).astype(np.int64)
+    P, S = int(m.sum()), F(0.)
+    for g in range(m.size):
+        if m[g] > 0:
+            if not inc_dir[g] + inc_dif[g] > 0:
+                raise ValueError(f"spectral_photon_list: g-point {g} has photons and no incident flux")
+            S = F(S + F(inc_dir[g] + inc_dif[g]))
+    U = F(S / F(P)) if P > 0 else F(0.)
+    weight0, dif_frac = np.zeros(m.size, dtype=dt), np.zeros(m.size, dtype=dt)
+    for g in range(m.size):
+        if m[g] > 0:
+            inc = F(inc_dir[g] + inc_dif[g])
+            weight0[g] = F(F(inc / F(m[g])) / U)
+            dif_frac[g] = F(inc_dif[g] / inc)
+    return photon_end, weight0, dif_frac, U
+
+
 def raytrace_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, photons_per_pixel, seed, cloud_lut=None, kn_grid=None,
                 independent_column=False, sfc_albedo=None, max_events=None, phase_table=None, n_domain=None, z_lev=None,
-                aerosol_lut=None):
+                aerosol_lut=None, allocation=None, min_per_gpt=1):
     """3-D shortwave surface / top fluxes and absorption from the forward Monte Carlo ray tracer (rrx_raytracer_sw).
 
     The atmosphere's columns are the pixels of an nx x ny domain (column = ix + nx iy) of cells dx x dy x dz metres, periodic in x
@@ -203,11 +272,26 @@ def raytrace_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, photons_per_pixel, 
     its own asymmetry parameter; with n_domain the layers above the grid carry column 0's aerosol.
     Returns sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up (ncol,) in W m-2, abs_dir, abs_dif (nlay, ncol) in W m-3 and n_capped; with
     n_domain also toa_up, tod_dn_dir, tod_dn_dif (ncol,) in W m-2 and bg_abs_dir, bg_abs_dif (nbg,) in W m-3 of a domain-wide layer,
-    counted upward from the domain top (abs_dir, abs_dif are then (n_domain, ncol), and tod_up is the flux through the domain top)."""
+    counted upward from the domain top (abs_dir, abs_dif are then (n_domain, ncol), and tod_up is the flux through the domain top).
+    allocation="flux" (DESIGN 4.19): photons_per_pixel is the TOTAL over all g-points, dealt by spectral_allocation(inc_dir,
+    photons_per_pixel, min_per_gpt) in proportion to the incident flux, and all g-points are traced in one launch per chunk
+    (rrx_raytracer_sw_spectral, ngpt <= 1024). The same dictionary comes back. allocation=None: every g-point gets photons_per_pixel."""
+    if allocation not in (None, "flux"):
+        raise ValueError(f"raytrace_sw: allocation is None or 'flux', got {allocation!r}")
     if n_domain is not None and kn_grid is None:
         kn_grid = (nx, ny, int(n_domain))
     tau, ssa, cld, sfc_albedo, mu0, inc_dir, kn_grid, aer = _raytracer_inputs("raytrace_sw", be, kd_sw, atm, nx, ny, cloud_lut, kn_grid,
                                                                               sfc_albedo, aerosol_lut)
+    if allocation == "flux":
+        m = spectral_allocation(inc_dir, photons_per_pixel, min_per_gpt)
+        background, rel = None, None
+        if n_domain is not None:
+            tau, ssa, cld, rel, background, aer = _raytracer_split("raytrace_sw", be, atm, tau, ssa, cld, n_domain, z_lev, aer)
+        phase = _raytracer_phase("raytrace_sw", atm, cloud_lut, phase_table, rel)
+        r = be.raytracer_sw_spectral(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, np.zeros_like(inc_dir), kn_grid, m, seed,
+                                     top_at_1=atm.top_at_1, independent_column=independent_column, cloud=cld,
+                                     band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase, background=background, aerosol=aer)
+        return r if n_domain is not None else {k: v for k, v in r.items() if k not in be.RT_BG_COUNTS}
     if n_domain is not None:
         tau, ssa, cld, rel, background, aer = _raytracer_split("raytrace_sw", be, atm, tau, ssa, cld, n_domain, z_lev, aer)
         phase = _raytracer_phase("raytrace_sw", atm, cloud_lut, phase_table, rel)
