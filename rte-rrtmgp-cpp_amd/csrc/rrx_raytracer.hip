@@ -59,7 +59,7 @@
 // Shape: one photon per lane at a time; a lane whose photon ends takes the next one of its list in the same loop, so the lanes
 // of a wave stay busy until the lists run out (the grid is capped and the photons dealt round-robin over the threads).
 #include "rrx_rt_phase.h"
-#include "rrx_hip.h"
+#include "rrx_rt_host.h"
 
 namespace
 {
@@ -465,46 +465,83 @@ __global__ void counts_to_flux_kernel(const size_t n, const u64* __restrict__ co
     if (i < n) out[i] = out[i] + F(double(counts[i]) * 2.3283064365386963e-10) * scale;
 }
 
-// ---- host side
+// ---- host side (rrx_rt_host.h)
 
-template<typename F>
-void launch_k_null(int nx, int ny, int nz, int nbnd, int igpt, int top_at_1, const F* tau, const int* band_lims_gpt,
-                   const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, hipStream_t st, const F* aer_tau = nullptr)
+// the tallies of a trace entry (T = u64) or the fluxes of a loop (T = F); the last five are read only with nbg > 0
+template<typename T>
+struct FwOut
 {
-    const int n = knx*kny*knz;
-    if (aer_tau != nullptr)
-        k_null_aer_kernel<F><<<ceil_div(n, 256), 256, 0, st>>>(nx, ny, nz, nbnd, igpt, top_at_1, tau, band_lims_gpt, cld_tau, aer_tau, dz,
-                                                               knx, kny, knz, k_null);
-    else
-        k_null_kernel<F><<<ceil_div(n, 256), 256, 0, st>>>(nx, ny, nz, nbnd, igpt, top_at_1, tau, band_lims_gpt, cld_tau, dz,
-                                                           knx, kny, knz, k_null);
+    T* sfc_dn_dir; T* sfc_dn_dif; T* sfc_up; T* tod_up; T* abs_dir; T* abs_dif;
+    u64* n_capped;
+    T* toa_up; T* tod_dn_dir; T* tod_dn_dif; T* bg_abs_dir; T* bg_abs_dif;
+};
+
+// the checks of the forward entries: check_entry with the names of the outputs
+template<typename F, typename T, typename A, typename B, typename C>
+bool check_forward(const Medium<F>& m, const Sun<F>& sun, const PhaseIn<F>& ph, const Background<F>& bg, const int max_events,
+                   Extents extents, Needed inputs, const FwOut<T>& o, A after_nbnd, B after_phase, C after_scene)
+{
+    return check_entry(m, sun, ph, bg, max_events, extents, inputs,
+                       {{"sfc_dn_dir", o.sfc_dn_dir}, {"sfc_dn_dif", o.sfc_dn_dif}, {"sfc_up", o.sfc_up}, {"tod_up", o.tod_up},
+                        {"abs_dir", o.abs_dir}, {"abs_dif", o.abs_dif}, {"n_capped", o.n_capped}}, after_nbnd, after_phase, after_scene, nothing);
 }
 
-template<typename F>
-void launch_trace(TraceArgs<F> a, const PhaseIn<F>& ph, const F mu0, const F azimuth, const F inc_dir, const F inc_dif, const u64 seed,
-                  hipStream_t st, const FwBg<F,true>* bg = nullptr, const AerIn<F>* aer = nullptr)
+template<typename T>
+void check_bg_outputs(const FwOut<T>& o)
 {
-    const double st_ = std::sqrt(std::max(0.0, 1.0 - double(mu0)*double(mu0)));
-    a.sun_x = F(st_*std::cos(double(azimuth))); a.sun_y = F(st_*std::sin(double(azimuth))); a.sun_z = -mu0;
+    check_needed({{"toa_up", o.toa_up}, {"tod_dn_dir", o.tod_dn_dir}, {"tod_dn_dif", o.tod_dn_dif}, {"bg_abs_dir", o.bg_abs_dir},
+                  {"bg_abs_dif", o.bg_abs_dif}});
+}
+
+// THE BUILDER of the kernel arguments; the sun, dif_frac and the key are the launch's (launch_trace, launch_trace_spectral)
+template<typename F>
+TraceArgs<F> trace_args(const Medium<F>& m, const int igpt, const F* k_null, const u64 photon0, const long long nphotons, const int max_events,
+                        const FwOut<u64>& t)
+{
+    TraceArgs<F> a{};
+    set_medium(a, m, igpt, k_null, max_events);
+    a.independent_column = m.independent_column ? 1 : 0;
+    a.photon0 = photon0; a.nphotons = nphotons;
+    a.sfc_dn_dir = t.sfc_dn_dir; a.sfc_dn_dif = t.sfc_dn_dif; a.sfc_up = t.sfc_up; a.tod_up = t.tod_up; a.abs_dir = t.abs_dir;
+    a.abs_dif = t.abs_dif; a.n_capped = t.n_capped;
+    return a;
+}
+
+template<typename F> BgTallies<F> bg_tallies(const FwOut<u64>& t) { return {t.toa_up, t.tod_dn_dir, t.tod_dn_dif, t.bg_abs_dir, t.bg_abs_dif}; }
+
+// aer_tau: NULL runs the kernel without aerosol
+template<typename F>
+void launch_k_null(const Medium<F>& m, const int igpt, const F* aer_tau, F* k_null, hipStream_t st)
+{
+    const int n = m.knx*m.kny*m.knz, top_at_1 = m.top_at_1 ? 1 : 0;
+    if (aer_tau != nullptr)
+        k_null_aer_kernel<F><<<ceil_div(n, 256), 256, 0, st>>>(m.nx, m.ny, m.nz, m.nbnd, igpt, top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, aer_tau,
+                                                               m.dz, m.knx, m.kny, m.knz, k_null);
+    else
+        k_null_kernel<F><<<ceil_div(n, 256), 256, 0, st>>>(m.nx, m.ny, m.nz, m.nbnd, igpt, top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, m.dz,
+                                                           m.knx, m.kny, m.knz, k_null);
+}
+
+// form: which instantiation runs; b is read in the forms with a background (its aerosol triple in FORM_AER, whose profile has
+// BG_ROWS_AER rows)
+template<typename F>
+void launch_trace(TraceArgs<F> a, const PhaseIn<F>& ph, const Sun<F>& sun, const F inc_dir, const F inc_dif, const u64 seed, hipStream_t st,
+                  const Form form, const FwBg<F,true,true>& b)
+{
+    set_sun_and_key(a, sun, seed);
     a.dif_frac = inc_dif / (inc_dir + inc_dif);
-    a.k0 = unsigned(seed & 0xFFFFFFFFull); a.k1 = unsigned(seed >> 32);
     const int blocks = int(std::min<long long>((a.nphotons + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
-    if (bg != nullptr && aer != nullptr)
+    const size_t lds = form == FORM_GRID ? 0 : bg_lds_numbers(b.in.nbg, form == FORM_AER ? BG_ROWS_AER : BG_ROWS)*sizeof(F);
+    const FwBg<F,true> bg{b.in, b.t};
+    switch (2*form + (ph.given() ? 1 : 0))
     {
-        // the aerosol form: the background's profile has BG_ROWS_AER rows
-        const size_t lds = bg_lds_numbers(bg->in.nbg, BG_ROWS_AER)*sizeof(F);
-        const FwBg<F,true,true> ba{bg->in, bg->t, *aer};
-        if (ph.given()) trace_kernel<F,true,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, ba);
-        else trace_kernel<F,false,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, ba);
+        case 2*FORM_AER + 1: trace_kernel<F,true,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, b); break;
+        case 2*FORM_AER: trace_kernel<F,false,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, b); break;
+        case 2*FORM_BG + 1: trace_kernel<F,true,true,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, bg); break;
+        case 2*FORM_BG: trace_kernel<F,false,true,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, bg); break;
+        case 2*FORM_GRID + 1: trace_kernel<F,true,false,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, FwBg<F,false>{}); break;
+        default: trace_kernel<F,false,false,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, FwBg<F,false>{});
     }
-    else if (bg != nullptr)
-    {
-        const size_t lds = bg_lds_numbers(bg->in.nbg)*sizeof(F);
-        if (ph.given()) trace_kernel<F,true,true,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, *bg);
-        else trace_kernel<F,false,true,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, *bg);
-    }
-    else if (ph.given()) trace_kernel<F,true,false,false><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,true>{ph}, FwBg<F,false>{});
-    else trace_kernel<F,false,false,false><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,false>{}, FwBg<F,false>{});
 }
 
 // one number per background layer: out[b] += F(counts[b] 2^-32) scale[b]
@@ -589,6 +626,17 @@ __global__ void bg_profile_aer_kernel(const int nbg, const int ngpt, const int n
     bg_profile_layer<F,true>(nbg, nbnd, igpt, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, aer, profile);
 }
 
+// bg_profile_aer_kernel for every g-point, blockIdx.y counting them: slice g of profile (ngpt, BG_ROWS_AER, nbg+1)
+template<typename F>
+__global__ void bg_profile_all_kernel(const int nbg, const int nbnd, const BgLevels<F> dz_bg,
+        const F* __restrict__ bg_tau, const F* __restrict__ bg_ssa, const int* __restrict__ band_lims_gpt,
+        const F* __restrict__ bg_cld_tau, const F* __restrict__ bg_cld_ssa, const F* __restrict__ bg_cld_g, const AerIn<F> aer,
+        F* __restrict__ profile)
+{
+    bg_profile_layer<F,true>(nbg, nbnd, int(blockIdx.y), dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, aer,
+                             profile + size_t(blockIdx.y)*BG_ROWS_AER*(nbg + 1));
+}
+
 template<typename F>
 BgLevels<F> bg_thicknesses(const int nbg, const F* dz_bg)
 {
@@ -597,36 +645,52 @@ BgLevels<F> bg_thicknesses(const int nbg, const F* dz_bg)
     return d;
 }
 
+// The profile of g-point igpt from a background's medium (bg.tau .. bg.cld_g). seven_rows: the BG_ROWS_AER profile with the triple aer
+// (NULLs write zeros into its two rows), otherwise the BG_ROWS one. lims: band_lims_gpt.
 template<typename F>
-void launch_bg_profile(int nbg, int ngpt, int nbnd, int igpt, const BgLevels<F>& dz_bg, const F* bg_tau, const F* bg_ssa,
-                       const int* band_lims_gpt, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* profile, hipStream_t st,
-                       const AerIn<F>* aer = nullptr)
+void launch_bg_profile(const Background<F>& bg, const int ngpt, const int nbnd, const int* lims, const int igpt, const BgLevels<F>& dz_bg,
+                       const bool seven_rows, const AerIn<F>& aer, F* profile, hipStream_t st)
 {
-    if (aer != nullptr)
-        bg_profile_aer_kernel<F><<<ceil_div(nbg + 1, 64), 64, 0, st>>>(nbg, ngpt, nbnd, igpt, dz_bg, bg_tau, bg_ssa, band_lims_gpt,
-                                                                      bg_cld_tau, bg_cld_ssa, bg_cld_g, *aer, profile);
+    if (seven_rows)
+        bg_profile_aer_kernel<F><<<ceil_div(bg.nbg + 1, 64), 64, 0, st>>>(bg.nbg, ngpt, nbnd, igpt, dz_bg, bg.tau, bg.ssa, lims,
+                                                                         bg.cld_tau, bg.cld_ssa, bg.cld_g, aer, profile);
     else
-        bg_profile_kernel<F><<<ceil_div(nbg + 1, 64), 64, 0, st>>>(nbg, ngpt, nbnd, igpt, dz_bg, bg_tau, bg_ssa, band_lims_gpt,
-                                                                  bg_cld_tau, bg_cld_ssa, bg_cld_g, profile);
+        bg_profile_kernel<F><<<ceil_div(bg.nbg + 1, 64), 64, 0, st>>>(bg.nbg, ngpt, nbnd, igpt, dz_bg, bg.tau, bg.ssa, lims,
+                                                                     bg.cld_tau, bg.cld_ssa, bg.cld_g, profile);
 }
 
+// the profiles of all g-points, (ngpt, BG_ROWS_AER, nbg+1)
 template<typename F>
-int bg_profile_entry(const char* entry, int nbg, int ngpt, int nbnd, int igpt, const F* dz_bg, const F* bg_tau, const F* bg_ssa,
-                     const int* band_lims_gpt, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* profile, void* stream,
-                     const AerIn<F>* aer = nullptr)
+void launch_bg_profile_all(const Background<F>& bg, const int ngpt, const int nbnd, const int* lims, const BgLevels<F>& dz_bg,
+                           const AerIn<F>& aer, F* profile, hipStream_t st)
 {
-    // aer: the 7-row profile of rrx_rt_bg_profile_aer (its triple may be NULL)
+    const dim3 grid(unsigned(ceil_div(bg.nbg + 1, 64)), unsigned(ngpt));
+    bg_profile_all_kernel<F><<<grid, 64, 0, st>>>(bg.nbg, nbnd, dz_bg, bg.tau, bg.ssa, lims, bg.cld_tau, bg.cld_ssa, bg.cld_g, aer, profile);
+}
+
+inline void check_spectral_ngpt(const int ngpt)
+{
+    if (ngpt > RT_SPECTRAL_MAX_GPT) throw std::runtime_error("ngpt must be <= 1024 in the spectral form");
+}
+
+// rrx_rt_bg_profile (bg.form = FORM_BG), _aer (FORM_AER: the 7-row profile, its triple may be NULL) and _all (FORM_AER, ALL: the
+// profiles of all g-points, igpt is not read)
+template<typename F, bool ALL>
+int bg_profile_entry(const char* entry, const Background<F>& bg, const int ngpt, const int nbnd, const int* lims, const int igpt, F* profile,
+                     void* stream)
+{
     RRX_TRY
-    check_nbg(nbg);
-    if (check_extents({{"nbg", nbg}, {"ngpt", ngpt}})) return 0;
+    check_nbg(bg.nbg);
+    if (check_extents({{"nbg", bg.nbg}, {"ngpt", ngpt}})) return 0;
     if (nbnd < 0) throw std::runtime_error("nbnd is negative");
-    if (igpt < 0 || igpt >= ngpt) throw std::runtime_error("igpt is outside [0, ngpt)");
-    check_bg_medium(nbg, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g);
-    if (aer != nullptr) check_aerosol("bg_aer_", nbnd, band_lims_gpt, aer->tau, aer->ssa, aer->g);
+    if constexpr (ALL) check_spectral_ngpt(ngpt); else check_igpt(igpt, ngpt);
+    check_bg_medium(bg.nbg, nbnd, bg.dz_bg, bg.tau, bg.ssa, lims, bg.cld_tau, bg.cld_ssa, bg.cld_g);
+    if (bg.form == FORM_AER) check_aerosol("bg_aer_", nbnd, lims, bg.aer.tau, bg.aer.ssa, bg.aer.g);
     check_needed({{"bg_profile", profile}});
-    bg_levels<F>(nbg, dz_bg, 1, 1, F(1.));          // (the thicknesses are > 0)
-    launch_bg_profile<F>(nbg, ngpt, nbnd, igpt, bg_thicknesses(nbg, dz_bg), bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa,
-                         bg_cld_g, profile, static_cast<hipStream_t>(stream), aer);
+    bg_levels<F>(bg.nbg, bg.dz_bg, 1, 1, F(1.));          // (the thicknesses are > 0)
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if constexpr (ALL) launch_bg_profile_all<F>(bg, ngpt, nbnd, lims, bg_thicknesses(bg.nbg, bg.dz_bg), bg.aer, profile, st);
+    else launch_bg_profile<F>(bg, ngpt, nbnd, lims, igpt, bg_thicknesses(bg.nbg, bg.dz_bg), bg.form == FORM_AER, bg.aer, profile, st);
     RRX_CATCH(entry)
 }
 
@@ -636,74 +700,75 @@ void launch_counts_to_flux(const size_t n, const u64* counts, const F scale, F* 
     counts_to_flux_kernel<F><<<unsigned(ceil_div((long long)n, 256)), 256, 0, st>>>(n, counts, scale, out);
 }
 
+// k_null of the ng g-points from g0 on
 template<typename F>
-int k_null_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, const F* tau,
-                 const int* band_lims_gpt, const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, void* stream,
-                 const F* aer_tau = nullptr)
+void launch_k_null_all(const Medium<F>& m, const int g0, const int ng, const F* aer_tau, F* k_null, hipStream_t st)
+{
+    const dim3 grid(unsigned(ceil_div(m.knx*m.kny*m.knz, 256)), unsigned(ng));
+    k_null_all_kernel<F><<<grid, 256, 0, st>>>(m.nx, m.ny, m.nz, m.nbnd, g0, m.top_at_1 ? 1 : 0, m.tau, m.band_lims_gpt, m.cld_tau, aer_tau, m.dz,
+                                               m.knx, m.kny, m.knz, k_null);
+}
+
+// rrx_rt_k_null, _aer (m.aer.tau may be NULL) and _all (ALL: every g-point, igpt is not read); of m only what k_null depends on is set
+template<typename F, bool ALL>
+int k_null_entry(const char* entry, const Medium<F>& m, const int igpt, F* k_null, void* stream)
 {
     RRX_TRY
-    if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}})) return 0;
-    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
-    check_needed({{"tau", tau}, {"k_null", k_null}});
-    if (cld_tau != nullptr && band_lims_gpt == nullptr) throw std::runtime_error("band_lims_gpt is NULL");
-    if (aer_tau != nullptr && band_lims_gpt == nullptr) throw std::runtime_error("band_lims_gpt is NULL");
-    if (aer_tau != nullptr && nbnd < 1) throw std::runtime_error("nbnd must be >= 1 with an aerosol triple");
-    if (igpt < 0 || igpt >= ngpt) throw std::runtime_error("igpt is outside [0, ngpt)");
-    if (!(dz > F(0.))) throw std::runtime_error("dz must be > 0");
-    check_grid(nx, ny, nz, knx, kny, knz);
-    launch_k_null<F>(nx, ny, nz, nbnd, igpt, top_at_1 ? 1 : 0, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null,
-                     static_cast<hipStream_t>(stream), aer_tau);
+    const F* aer_tau = m.aer.tau;
+    if (check_extents({{"nx", m.nx}, {"ny", m.ny}, {"nz", m.nz}, {"ngpt", m.ngpt}})) return 0;
+    if (m.nbnd < 0) throw std::runtime_error("nbnd is negative");
+    if constexpr (ALL) check_spectral_ngpt(m.ngpt);
+    check_needed({{"tau", m.tau}, {"k_null", k_null}});
+    if ((m.cld_tau != nullptr || aer_tau != nullptr) && m.band_lims_gpt == nullptr) throw std::runtime_error("band_lims_gpt is NULL");
+    if (aer_tau != nullptr && m.nbnd < 1) throw std::runtime_error("nbnd must be >= 1 with an aerosol triple");
+    if constexpr (!ALL) check_igpt(igpt, m.ngpt);
+    if (!(m.dz > F(0.))) throw std::runtime_error("dz must be > 0");
+    check_grid(m.nx, m.ny, m.nz, m.knx, m.kny, m.knz);
+    if constexpr (ALL) launch_k_null_all<F>(m, 0, m.ngpt, aer_tau, k_null, static_cast<hipStream_t>(stream));
+    else launch_k_null<F>(m, igpt, aer_tau, k_null, static_cast<hipStream_t>(stream));
     RRX_CATCH(entry)
 }
 
+// a.photon0 / a.nphotons: the range of the concatenated list; a.k_null: the slices from g-point b.sp.kn_g0 on
 template<typename F>
-int trace_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, RrxBool independent_column,
-                const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
-                F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, F inc_dir, F inc_dif,
-                int knx, int kny, int knz, const F* k_null, u64 seed, long long photon0, long long nphotons, int max_events,
-                u64* sfc_dn_dir, u64* sfc_dn_dif, u64* sfc_up, u64* tod_up, u64* abs_dir, u64* abs_dif, u64* n_capped, void* stream,
-                const PhaseIn<F> ph = PhaseIn<F>{}, const bool with_bg = false, const BgTallies<F> bt = BgTallies<F>{},
-                const int nbg = 0, const F* dz_bg = nullptr, const F* bg_profile = nullptr, const AerIn<F>* aer = nullptr)
+void launch_trace_spectral(TraceArgs<F> a, const PhaseIn<F>& ph, const Sun<F>& sun, const u64 seed, hipStream_t st,
+                           const FwBg<F,true,true,true>& b)
 {
-    // aer: rrx_rt_trace_counts_aer. With nbg > 0 bg_profile then has BG_ROWS_AER rows and the aerosol form runs whatever the grid's
-    // triple is; with nbg = 0 and a NULL triple it is the _bg entry.
-    RRX_TRY
-    check_nbg(nbg);
-    if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"nphotons", nphotons}})) return 0;
-    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
-    if (photon0 < 0) throw std::runtime_error("photon0 is negative");
-    check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"k_null", k_null}, {"sfc_dn_dir", sfc_dn_dir},
-                  {"sfc_dn_dif", sfc_dn_dif}, {"sfc_up", sfc_up}, {"tod_up", tod_up}, {"abs_dir", abs_dir}, {"abs_dif", abs_dif},
-                  {"n_capped", n_capped}});
-    check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
-    if (aer != nullptr) check_aerosol("aer_", nbnd, band_lims_gpt, aer->tau, aer->ssa, aer->g);
-    check_phase(ph, cld_tau);
-    if (igpt < 0 || igpt >= ngpt) throw std::runtime_error("igpt is outside [0, ngpt)");
-    check_scene(dx, dy, dz, mu0);
-    if (inc_dir < F(0.) || inc_dif < F(0.) || !(inc_dir + inc_dif > F(0.))) throw std::runtime_error("inc_dir, inc_dif must be >= 0 with a positive sum");
-    if (max_events < 1) throw std::runtime_error("max_events must be >= 1");
-    check_grid(nx, ny, nz, knx, kny, knz);
-    TraceArgs<F> a{nx, ny, nz, nbnd, igpt, top_at_1 ? 1 : 0, independent_column ? 1 : 0, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g,
-                   dx, dy, dz, sfc_albedo, F(0.), F(0.), F(0.), F(0.), knx, kny, knz, k_null, 0u, 0u, u64(photon0), nphotons, max_events,
-                   sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped};
-    if (with_bg)
+    set_sun_and_key(a, sun, seed);
+    const int blocks = int(std::min<long long>((a.nphotons + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
+    const size_t lds = spectral_lds_bytes(b.sp.ngpt, b.in.nbg, sizeof(F));
+    switch (ph.given() ? 1 : 0)
     {
-        FwBg<F,true> bg{BgIn<F>{nbg, bg_profile, BgLevels<F>{}}, bt};
-        if (nbg > 0)
-        {
-            check_needed({{"dz_bg", dz_bg}, {"bg_profile", bg_profile}, {"toa_up", bt.toa_up}, {"tod_dn_dir", bt.tod_dn_dir},
-                          {"tod_dn_dif", bt.tod_dn_dif}, {"bg_abs_dir", bt.bg_abs_dir}, {"bg_abs_dif", bt.bg_abs_dif}});
-            bg.in.z = bg_levels<F>(nbg, dz_bg, nz, knz, dz);
-        }
-        if (aer != nullptr && (aer->tau != nullptr || nbg > 0))
-        {
-            launch_trace<F>(a, ph, mu0, azimuth, inc_dir, inc_dif, seed, static_cast<hipStream_t>(stream), &bg, aer);
-            return 0;
-        }
-        launch_trace<F>(a, ph, mu0, azimuth, inc_dir, inc_dif, seed, static_cast<hipStream_t>(stream), &bg);
-        return 0;
+        case 1: trace_kernel<F,true,true,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, b); break;
+        default: trace_kernel<F,false,true,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, b);
     }
-    launch_trace<F>(a, ph, mu0, azimuth, inc_dir, inc_dif, seed, static_cast<hipStream_t>(stream));
+}
+
+// The single-launch trace entries: rrx_rt_trace_counts, _phase (bg.form = FORM_GRID), _bg, _aer, and with SPECTRAL
+// rrx_rt_trace_counts_spectral (sp is read; igpt, inc_dir, inc_dif are not). sp.photon_end, weight0, dif_frac are device arrays: the
+// entry cannot look into them. The kernel stays inside its arrays whatever photon_end holds (the search is bounded by ngpt and a photon
+// beyond photon_end[ngpt] is stepped over); the callers that form the list on the host (rrx_raytracer_sw_spectral, the Python binding)
+// refuse a list that does not ascend.
+template<typename F, bool SPECTRAL>
+int trace_entry(const char* entry, const Medium<F>& m, const Sun<F>& sun, const PhaseIn<F>& ph, const Background<F>& bg, const Run& run,
+                const int igpt, const F inc_dir, const F inc_dif, const SpecIn<F>& sp, const F* k_null, const long long photon0,
+                const long long nphotons, const FwOut<u64>& t)
+{
+    RRX_TRY
+    const Needed own = {{"k_null", k_null}};
+    const Needed own_spectral = {{"photon_end", sp.photon_end}, {"weight0", sp.weight0}, {"dif_frac", sp.dif_frac}, {"k_null", k_null}};
+    if (check_forward(m, sun, ph, bg, run.max_events, {{"nphotons", nphotons}}, SPECTRAL ? own_spectral : own, t,
+            [&] { if (SPECTRAL) check_spectral_ngpt(m.ngpt); if (photon0 < 0) throw std::runtime_error("photon0 is negative"); },
+            [&] { if (!SPECTRAL) check_igpt(igpt, m.ngpt); },
+            [&] { if (!SPECTRAL && (inc_dir < F(0.) || inc_dif < F(0.) || !(inc_dir + inc_dif > F(0.))))
+                      throw std::runtime_error("inc_dir, inc_dif must be >= 0 with a positive sum"); }))
+        return 0;
+    const TraceArgs<F> a = trace_args<F>(m, SPECTRAL ? 0 : igpt, k_null, u64(photon0), nphotons, run.max_events, t);
+    hipStream_t st = static_cast<hipStream_t>(run.stream);
+    FwBg<F,true,true> b{BgIn<F>{}, bg_tallies<F>(t), m.aer};
+    if (bg.form != FORM_GRID) b.in = background_of(bg, m, [&] { check_bg_outputs(t); });
+    if constexpr (SPECTRAL) launch_trace_spectral<F>(a, ph, sun, run.seed, st, FwBg<F,true,true,true>{b.in, b.t, b.aer, sp});
+    else launch_trace<F>(a, ph, sun, inc_dir, inc_dif, run.seed, st, form_of(bg, m), b);
     RRX_CATCH(entry)
 }
 
@@ -717,234 +782,74 @@ int counts_to_flux_entry(const char* entry, long long n, const u64* counts, F sc
     RRX_CATCH(entry)
 }
 
+// THE WORKSPACE of the forward loops, in u64 words: | the six grid tallies | the five background tallies (nbg > 0) | k_null | the
+// background's profile | photon_end, weight0, dif_frac (spectral_ngpt > 0) |
 template<typename F>
-int raytracer_sw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column,
-                       const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
-                       F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif,
-                       int knx, int kny, int knz, long long photons_per_pixel, u64 seed, int max_events,
-                       F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, u64* n_capped, void* stream,
-                       const PhaseIn<F> ph = PhaseIn<F>{}, const bool with_bg = false, F* const* bg_out = nullptr, const int nbg = 0,
-                       const F* dz_bg = nullptr, const F* bg_tau = nullptr, const F* bg_ssa = nullptr, const F* bg_cld_tau = nullptr,
-                       const F* bg_cld_ssa = nullptr, const F* bg_cld_g = nullptr, const AerIn<F>* aer = nullptr,
-                       const AerIn<F>* bg_aer = nullptr)
+struct FwWorkspace
 {
-    // bg_out: toa_up, tod_dn_dir, tod_dn_dif (ncol), bg_abs_dir, bg_abs_dif (nbg)
-    // aer, bg_aer: rrx_raytracer_sw_aer; with both triples NULL (bg_aer is not read when nbg = 0) it is the _bg entry
-    RRX_TRY
-    check_nbg(nbg);
-    if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"photons_per_pixel", photons_per_pixel}})) return 0;
-    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
-    check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"inc_dir", inc_dir}, {"inc_dif", inc_dif},
-                  {"sfc_dn_dir", sfc_dn_dir}, {"sfc_dn_dif", sfc_dn_dif}, {"sfc_up", sfc_up}, {"tod_up", tod_up}, {"abs_dir", abs_dir},
-                  {"abs_dif", abs_dif}, {"n_capped", n_capped}});
-    check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
-    if (aer != nullptr) check_aerosol("aer_", nbnd, band_lims_gpt, aer->tau, aer->ssa, aer->g);
-    check_phase(ph, cld_tau);
-    check_scene(dx, dy, dz, mu0);
-    for (int g=0; g<ngpt; ++g)
-        if (inc_dir[g] < F(0.) || inc_dif[g] < F(0.)) throw std::runtime_error("inc_dir, inc_dif must be >= 0");
-    if (max_events < 1) throw std::runtime_error("max_events must be >= 1");
-    check_grid(nx, ny, nz, knx, kny, knz);
-    const bool bg_on = with_bg && nbg > 0;
-    BgLevels<F> lev{}, thick{};
-    if (bg_on && bg_aer != nullptr) check_aerosol("bg_aer_", nbnd, band_lims_gpt, bg_aer->tau, bg_aer->ssa, bg_aer->g);
-    // the aerosol form runs when either triple is given
-    const AerIn<F> aer_grid = aer != nullptr ? *aer : AerIn<F>{}, aer_bg = (bg_on && bg_aer != nullptr) ? *bg_aer : AerIn<F>{};
-    const bool aer_on = with_bg && (aer_grid.tau != nullptr || aer_bg.tau != nullptr);
-    if (bg_on)
+    size_t ncol, nz, nbg, n_counts;
+    u64* counts; F* k_null; F* profile; long long* photon_end; F* weight0; F* dif_frac;
+    // nbg: 0 without a background; kn_numbers, profile_numbers: the F of k_null and of the profile
+    FwWorkspace(WorkspaceLease& lease, const Medium<F>& m, const int nbg, const size_t kn_numbers, const size_t profile_numbers,
+                const int spectral_ngpt)
+        : ncol(size_t(m.nx)*m.ny), nz(m.nz), nbg(nbg), n_counts(4*ncol + 2*ncol*nz + (nbg > 0 ? 3*ncol + 2*size_t(nbg) : 0))
     {
-        check_bg_medium(nbg, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g);
-        check_needed({{"toa_up", bg_out[0]}, {"tod_dn_dir", bg_out[1]}, {"tod_dn_dif", bg_out[2]}, {"bg_abs_dir", bg_out[3]},
-                      {"bg_abs_dif", bg_out[4]}});
-        lev = bg_levels<F>(nbg, dz_bg, nz, knz, dz);
-        thick = bg_thicknesses(nbg, dz_bg);
+        const size_t n_kn = words_of(kn_numbers*sizeof(F)), n_prof = words_of(profile_numbers*sizeof(F));
+        const size_t n_pe = spectral_ngpt > 0 ? size_t(spectral_ngpt) + 1 : 0, n_w = words_of(size_t(spectral_ngpt)*sizeof(F));
+        counts = lease.get<u64>(n_counts + n_kn + n_prof + n_pe + 2*n_w);
+        k_null = reinterpret_cast<F*>(counts + n_counts);
+        profile = reinterpret_cast<F*>(counts + n_counts + n_kn);
+        photon_end = reinterpret_cast<long long*>(counts + n_counts + n_kn + n_prof);
+        weight0 = reinterpret_cast<F*>(counts + n_counts + n_kn + n_prof + n_pe);
+        dif_frac = reinterpret_cast<F*>(counts + n_counts + n_kn + n_prof + n_pe + n_w);
     }
-
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t ncol = size_t(nx)*ny, n_sfc = 4*ncol, n_abs = 2*ncol*nz;
-    const size_t n_bgc = bg_on ? 3*ncol + 2*size_t(nbg) : 0, n_counts = n_sfc + n_abs + n_bgc;
-    const size_t n_kn = (size_t(knx)*kny*knz*sizeof(F) + sizeof(u64) - 1) / sizeof(u64);
-    const size_t n_prof = bg_on ? (size_t(aer_on ? BG_ROWS_AER : BG_ROWS)*(nbg + 1)*sizeof(F) + sizeof(u64) - 1) / sizeof(u64) : 0;
-    WorkspaceLease lease(st);
-    u64* counts = lease.get<u64>(n_counts + n_kn + n_prof);
-    F* k_null = reinterpret_cast<F*>(counts + n_counts);
-    F* profile = reinterpret_cast<F*>(counts + n_counts + n_kn);
-    bool ok = hipMemsetAsync(n_capped, 0, sizeof(u64), st) == hipSuccess;
-    if (bg_on)
+    FwOut<u64> tallies(u64* n_capped) const
     {
-        for (int n=0; n<3; ++n) ok = ok && hipMemsetAsync(bg_out[n], 0, ncol*sizeof(F), st) == hipSuccess;
-        for (int n=3; n<5; ++n) ok = ok && hipMemsetAsync(bg_out[n], 0, size_t(nbg)*sizeof(F), st) == hipSuccess;
-    }
-    for (F* out : {sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up}) ok = ok && hipMemsetAsync(out, 0, ncol*sizeof(F), st) == hipSuccess;
-    for (F* out : {abs_dir, abs_dif}) ok = ok && hipMemsetAsync(out, 0, ncol*nz*sizeof(F), st) == hipSuccess;
-    if (!ok) throw std::runtime_error("zeroing the outputs failed");
-    const long long nphotons = photons_per_pixel*(long long)ncol;
-    for (int g=0; g<ngpt; ++g)
-    {
-        if (!(inc_dir[g] + inc_dif[g] > F(0.))) continue;
-        if (hipMemsetAsync(counts, 0, n_counts*sizeof(u64), st) != hipSuccess) throw std::runtime_error("zeroing the counts failed");
-        launch_k_null<F>(nx, ny, nz, nbnd, g, top_at_1 ? 1 : 0, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null, st, aer_grid.tau);
         u64* c = counts;
-        TraceArgs<F> a{nx, ny, nz, nbnd, g, top_at_1 ? 1 : 0, independent_column ? 1 : 0, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g,
-                       dx, dy, dz, sfc_albedo, F(0.), F(0.), F(0.), F(0.), knx, kny, knz, k_null, 0u, 0u, 0ull, nphotons, max_events,
-                       c, c + ncol, c + 2*ncol, c + 3*ncol, c + n_sfc, c + n_sfc + ncol*nz, n_capped};
-        const F scale = (inc_dir[g] + inc_dif[g]) / F(photons_per_pixel);
-        if (with_bg)
-        {
-            u64* cb = c + n_sfc + n_abs;
-            FwBg<F,true> bg{BgIn<F>{bg_on ? nbg : 0, profile, lev}, BgTallies<F>{cb, cb + ncol, cb + 2*ncol, cb + 3*ncol, cb + 3*ncol + nbg}};
-            if (bg_on) launch_bg_profile<F>(nbg, ngpt, nbnd, g, thick, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, profile, st,
-                                            aer_on ? &aer_bg : nullptr);
-            launch_trace<F>(a, ph, mu0, azimuth, inc_dir[g], inc_dif[g], seed, st, &bg, aer_on ? &aer_grid : nullptr);
-            if (bg_on)
-            {
-                launch_counts_to_flux<F>(ncol, bg.t.toa_up, scale, bg_out[0], st);
-                launch_counts_to_flux<F>(ncol, bg.t.tod_dn_dir, scale, bg_out[1], st);
-                launch_counts_to_flux<F>(ncol, bg.t.tod_dn_dif, scale, bg_out[2], st);
-                // W m-3 of a domain-wide layer: the counts of all columns over the layer's thickness and the number of columns
-                BgLevels<F> per_layer{};
-                for (int b=0; b<nbg; ++b) per_layer.v[b] = (scale / dz_bg[b]) / F(ncol);
-                bg_counts_to_flux_kernel<F><<<ceil_div(nbg, 64), 64, 0, st>>>(nbg, bg.t.bg_abs_dir, per_layer, bg_out[3]);
-                bg_counts_to_flux_kernel<F><<<ceil_div(nbg, 64), 64, 0, st>>>(nbg, bg.t.bg_abs_dif, per_layer, bg_out[4]);
-            }
-        }
-        else launch_trace<F>(a, ph, mu0, azimuth, inc_dir[g], inc_dif[g], seed, st);
-        launch_counts_to_flux<F>(ncol, a.sfc_dn_dir, scale, sfc_dn_dir, st);
-        launch_counts_to_flux<F>(ncol, a.sfc_dn_dif, scale, sfc_dn_dif, st);
-        launch_counts_to_flux<F>(ncol, a.sfc_up, scale, sfc_up, st);
-        launch_counts_to_flux<F>(ncol, a.tod_up, scale, tod_up, st);
-        launch_counts_to_flux<F>(ncol*nz, a.abs_dir, scale / dz, abs_dir, st);
-        launch_counts_to_flux<F>(ncol*nz, a.abs_dif, scale / dz, abs_dif, st);
+        u64* cb = c + 4*ncol + 2*ncol*nz;
+        return {c, c + ncol, c + 2*ncol, c + 3*ncol, c + 4*ncol, c + 4*ncol + ncol*nz, n_capped,
+                cb, cb + ncol, cb + 2*ncol, cb + 3*ncol, cb + 3*ncol + nbg};
     }
-    RRX_CATCH(entry)
-}
-
-// ---- all g-points in one launch (rrx_rt_common.h)
-
-// bg_profile_aer_kernel for every g-point, blockIdx.y counting them: slice g of profile (ngpt, BG_ROWS_AER, nbg+1)
-template<typename F>
-__global__ void bg_profile_all_kernel(const int nbg, const int nbnd, const BgLevels<F> dz_bg,
-        const F* __restrict__ bg_tau, const F* __restrict__ bg_ssa, const int* __restrict__ band_lims_gpt,
-        const F* __restrict__ bg_cld_tau, const F* __restrict__ bg_cld_ssa, const F* __restrict__ bg_cld_g, const AerIn<F> aer,
-        F* __restrict__ profile)
-{
-    bg_profile_layer<F,true>(nbg, nbnd, int(blockIdx.y), dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, aer,
-                             profile + size_t(blockIdx.y)*BG_ROWS_AER*(nbg + 1));
-}
-
-// k_null of the ng g-points from g0 on
-template<typename F>
-void launch_k_null_all(int nx, int ny, int nz, int nbnd, int g0, int ng, int top_at_1, const F* tau, const int* band_lims_gpt,
-                       const F* cld_tau, const F* aer_tau, F dz, int knx, int kny, int knz, F* k_null, hipStream_t st)
-{
-    const dim3 grid(unsigned(ceil_div(knx*kny*knz, 256)), unsigned(ng));
-    k_null_all_kernel<F><<<grid, 256, 0, st>>>(nx, ny, nz, nbnd, g0, top_at_1, tau, band_lims_gpt, cld_tau, aer_tau, dz, knx, kny, knz, k_null);
-}
-
-template<typename F>
-void launch_bg_profile_all(int nbg, int ngpt, int nbnd, const BgLevels<F>& dz_bg, const F* bg_tau, const F* bg_ssa, const int* band_lims_gpt,
-                           const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, const AerIn<F>& aer, F* profile, hipStream_t st)
-{
-    const dim3 grid(unsigned(ceil_div(nbg + 1, 64)), unsigned(ngpt));
-    bg_profile_all_kernel<F><<<grid, 64, 0, st>>>(nbg, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, aer, profile);
-}
-
-// a.photon0 / a.nphotons: the range of the concatenated list; a.k_null: the slices from g-point b.sp.kn_g0 on
-template<typename F>
-void launch_trace_spectral(TraceArgs<F> a, const PhaseIn<F>& ph, const F mu0, const F azimuth, const u64 seed, hipStream_t st,
-                           const FwBg<F,true,true,true>& b)
-{
-    const double st_ = std::sqrt(std::max(0.0, 1.0 - double(mu0)*double(mu0)));
-    a.sun_x = F(st_*std::cos(double(azimuth))); a.sun_y = F(st_*std::sin(double(azimuth))); a.sun_z = -mu0;
-    a.k0 = unsigned(seed & 0xFFFFFFFFull); a.k1 = unsigned(seed >> 32);
-    const int blocks = int(std::min<long long>((a.nphotons + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
-    const size_t lds = spectral_lds_bytes(b.sp.ngpt, b.in.nbg, sizeof(F));
-    if (ph.given()) trace_kernel<F,true,true,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, b);
-    else trace_kernel<F,false,true,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, b);
-}
-
-inline void check_spectral_ngpt(const int ngpt)
-{
-    if (ngpt > RT_SPECTRAL_MAX_GPT) throw std::runtime_error("ngpt must be <= 1024 in the spectral form");
-}
-
-template<typename F>
-int k_null_all_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, const F* tau,
-                     const int* band_lims_gpt, const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, const F* aer_tau, void* stream)
-{
-    RRX_TRY
-    if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}})) return 0;
-    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
-    check_spectral_ngpt(ngpt);
-    check_needed({{"tau", tau}, {"k_null", k_null}});
-    if ((cld_tau != nullptr || aer_tau != nullptr) && band_lims_gpt == nullptr) throw std::runtime_error("band_lims_gpt is NULL");
-    if (aer_tau != nullptr && nbnd < 1) throw std::runtime_error("nbnd must be >= 1 with an aerosol triple");
-    if (!(dz > F(0.))) throw std::runtime_error("dz must be > 0");
-    check_grid(nx, ny, nz, knx, kny, knz);
-    launch_k_null_all<F>(nx, ny, nz, nbnd, 0, ngpt, top_at_1 ? 1 : 0, tau, band_lims_gpt, cld_tau, aer_tau, dz, knx, kny, knz, k_null,
-                         static_cast<hipStream_t>(stream));
-    RRX_CATCH(entry)
-}
-
-template<typename F>
-int bg_profile_all_entry(const char* entry, int nbg, int ngpt, int nbnd, const F* dz_bg, const F* bg_tau, const F* bg_ssa,
-                         const int* band_lims_gpt, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* profile,
-                         const AerIn<F> aer, void* stream)
-{
-    RRX_TRY
-    check_nbg(nbg);
-    if (check_extents({{"nbg", nbg}, {"ngpt", ngpt}})) return 0;
-    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
-    check_spectral_ngpt(ngpt);
-    check_bg_medium(nbg, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g);
-    check_aerosol("bg_aer_", nbnd, band_lims_gpt, aer.tau, aer.ssa, aer.g);
-    check_needed({{"bg_profile", profile}});
-    bg_levels<F>(nbg, dz_bg, 1, 1, F(1.));          // (the thicknesses are > 0)
-    launch_bg_profile_all<F>(nbg, ngpt, nbnd, bg_thicknesses(nbg, dz_bg), bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, aer,
-                             profile, static_cast<hipStream_t>(stream));
-    RRX_CATCH(entry)
-}
-
-// photon_end, weight0, dif_frac are device arrays: the entry cannot look into them. The kernel stays inside its arrays whatever
-// photon_end holds (the search is bounded by ngpt and a photon beyond photon_end[ngpt] is stepped over); the callers that form the
-// list on the host (rrx_raytracer_sw_spectral, the Python binding) refuse a list that does not ascend.
-template<typename F>
-int trace_spectral_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column,
-                         const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
-                         F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const long long* photon_end, const F* weight0, const F* dif_frac,
-                         int knx, int kny, int knz, const F* k_null, u64 seed, long long photon0, long long nphotons, int max_events,
-                         u64* sfc_dn_dir, u64* sfc_dn_dif, u64* sfc_up, u64* tod_up, u64* abs_dir, u64* abs_dif, u64* n_capped,
-                         const BgTallies<F> bt, const PhaseIn<F> ph, const int nbg, const F* dz_bg, const F* bg_profile, const AerIn<F> aer,
-                         void* stream)
-{
-    RRX_TRY
-    check_nbg(nbg);
-    if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"nphotons", nphotons}})) return 0;
-    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
-    check_spectral_ngpt(ngpt);
-    if (photon0 < 0) throw std::runtime_error("photon0 is negative");
-    check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"photon_end", photon_end}, {"weight0", weight0},
-                  {"dif_frac", dif_frac}, {"k_null", k_null}, {"sfc_dn_dir", sfc_dn_dir}, {"sfc_dn_dif", sfc_dn_dif}, {"sfc_up", sfc_up},
-                  {"tod_up", tod_up}, {"abs_dir", abs_dir}, {"abs_dif", abs_dif}, {"n_capped", n_capped}});
-    check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
-    check_aerosol("aer_", nbnd, band_lims_gpt, aer.tau, aer.ssa, aer.g);
-    check_phase(ph, cld_tau);
-    check_scene(dx, dy, dz, mu0);
-    if (max_events < 1) throw std::runtime_error("max_events must be >= 1");
-    check_grid(nx, ny, nz, knx, kny, knz);
-    TraceArgs<F> a{nx, ny, nz, nbnd, 0, top_at_1 ? 1 : 0, independent_column ? 1 : 0, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g,
-                   dx, dy, dz, sfc_albedo, F(0.), F(0.), F(0.), F(0.), knx, kny, knz, k_null, 0u, 0u, u64(photon0), nphotons, max_events,
-                   sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped};
-    FwBg<F,true,true,true> b{BgIn<F>{nbg, bg_profile, BgLevels<F>{}}, bt, aer, SpecIn<F>{ngpt, 0, photon_end, weight0, dif_frac}};
-    if (nbg > 0)
+    void zero_counts(hipStream_t st) const
     {
-        check_needed({{"dz_bg", dz_bg}, {"bg_profile", bg_profile}, {"toa_up", bt.toa_up}, {"tod_dn_dir", bt.tod_dn_dir},
-                      {"tod_dn_dif", bt.tod_dn_dif}, {"bg_abs_dir", bt.bg_abs_dir}, {"bg_abs_dif", bt.bg_abs_dif}});
-        b.in.z = bg_levels<F>(nbg, dz_bg, nz, knz, dz);
+        if (hipMemsetAsync(counts, 0, n_counts*sizeof(u64), st) != hipSuccess) throw std::runtime_error("zeroing the counts failed");
     }
-    launch_trace_spectral<F>(a, ph, mu0, azimuth, seed, static_cast<hipStream_t>(stream), b);
-    RRX_CATCH(entry)
-}
+    // THE OUTPUTS start at zero
+    void zero_outputs(const FwOut<F>& out, hipStream_t st) const
+    {
+        bool ok = hipMemsetAsync(out.n_capped, 0, sizeof(u64), st) == hipSuccess;
+        if (nbg > 0)
+        {
+            for (F* o : {out.toa_up, out.tod_dn_dir, out.tod_dn_dif}) ok = ok && hipMemsetAsync(o, 0, ncol*sizeof(F), st) == hipSuccess;
+            for (F* o : {out.bg_abs_dir, out.bg_abs_dif}) ok = ok && hipMemsetAsync(o, 0, nbg*sizeof(F), st) == hipSuccess;
+        }
+        for (F* o : {out.sfc_dn_dir, out.sfc_dn_dif, out.sfc_up, out.tod_up}) ok = ok && hipMemsetAsync(o, 0, ncol*sizeof(F), st) == hipSuccess;
+        for (F* o : {out.abs_dir, out.abs_dif}) ok = ok && hipMemsetAsync(o, 0, ncol*nz*sizeof(F), st) == hipSuccess;
+        if (!ok) throw std::runtime_error("zeroing the outputs failed");
+    }
+    // COUNTS TO FLUXES: out += counts 2^-32 scale; abs_* in W m-3 by scale / dz, bg_abs_* [b] in W m-3 of a domain-wide layer: the counts
+    // of all columns over the layer's thickness and the number of columns
+    void add_fluxes(const F scale, const F dz, const F* dz_bg, const FwOut<F>& out, hipStream_t st) const
+    {
+        const FwOut<u64> t = tallies(nullptr);
+        if (nbg > 0)
+        {
+            launch_counts_to_flux<F>(ncol, t.toa_up, scale, out.toa_up, st);
+            launch_counts_to_flux<F>(ncol, t.tod_dn_dir, scale, out.tod_dn_dir, st);
+            launch_counts_to_flux<F>(ncol, t.tod_dn_dif, scale, out.tod_dn_dif, st);
+            BgLevels<F> per_layer{};
+            for (size_t b=0; b<nbg; ++b) per_layer.v[b] = (scale / dz_bg[b]) / F(ncol);
+            bg_counts_to_flux_kernel<F><<<ceil_div(int(nbg), 64), 64, 0, st>>>(int(nbg), t.bg_abs_dir, per_layer, out.bg_abs_dir);
+            bg_counts_to_flux_kernel<F><<<ceil_div(int(nbg), 64), 64, 0, st>>>(int(nbg), t.bg_abs_dif, per_layer, out.bg_abs_dif);
+        }
+        launch_counts_to_flux<F>(ncol, t.sfc_dn_dir, scale, out.sfc_dn_dir, st);
+        launch_counts_to_flux<F>(ncol, t.sfc_dn_dif, scale, out.sfc_dn_dif, st);
+        launch_counts_to_flux<F>(ncol, t.sfc_up, scale, out.sfc_up, st);
+        launch_counts_to_flux<F>(ncol, t.tod_up, scale, out.tod_up, st);
+        launch_counts_to_flux<F>(ncol*nz, t.abs_dir, scale / dz, out.abs_dir, st);
+        launch_counts_to_flux<F>(ncol*nz, t.abs_dif, scale / dz, out.abs_dif, st);
+    }
+};
 
 // g-points per trace launch of rrx_raytracer_sw_spectral: the largest chunk whose k_null fits 1 GiB, or
 // RRX_RT_SPECTRAL_GPT_PER_LAUNCH from the environment, read at every call. The result does not depend on it.
@@ -955,305 +860,189 @@ inline int spectral_gpt_per_launch(const size_t k_null_bytes_per_gpt, const int 
     return int(std::min<size_t>(std::max<size_t>(fit, 1), size_t(ngpt)));
 }
 
-// rrx_raytracer_sw_aer with photons_per_pixel_gpt[g] = m_g photons per pixel of g-point g (host array): one trace launch per chunk of
-// consecutive g-points, the counts of all chunks added in integers and converted once with the common unit U = S/P
-template<typename F>
-int raytracer_sw_spectral_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column,
-                       const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
-                       F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif,
-                       int knx, int kny, int knz, const long long* m, u64 seed, int max_events,
-                       F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, u64* n_capped, void* stream,
-                       const PhaseIn<F> ph, F* const* bg_out, const int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa,
-                       const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, const AerIn<F> aer, const AerIn<F> bg_aer)
+// The loops over the g-points. photons_per_pixel: rrx_raytracer_sw, _phase, _bg, _aer, one k_null, profile and trace launch per
+// g-point with incident flux, each g-point's counts converted with its own scale. SPECTRAL (m_gpt, a host array; bg.form = FORM_AER):
+// rrx_raytracer_sw_spectral with m_gpt[g] photons per pixel of g-point g: one trace launch per chunk of consecutive g-points, the counts
+// of all chunks added in integers and converted once with the common unit U = S/P (rrx_rt_common.h).
+template<typename F, bool SPECTRAL>
+int raytracer_sw_entry(const char* entry, const Medium<F>& m, const Sun<F>& sun, const PhaseIn<F>& ph, const Background<F>& bg, const Run& run,
+                       const F* inc_dir, const F* inc_dif, const long long photons_per_pixel, const long long* m_gpt, const FwOut<F>& out)
 {
     RRX_TRY
-    check_nbg(nbg);
-    if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}})) return 0;
-    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
-    check_spectral_ngpt(ngpt);
-    check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"inc_dir", inc_dir}, {"inc_dif", inc_dif},
-                  {"photons_per_pixel_gpt", m}, {"sfc_dn_dir", sfc_dn_dir}, {"sfc_dn_dif", sfc_dn_dif}, {"sfc_up", sfc_up}, {"tod_up", tod_up},
-                  {"abs_dir", abs_dir}, {"abs_dif", abs_dif}, {"n_capped", n_capped}});
-    check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
-    check_aerosol("aer_", nbnd, band_lims_gpt, aer.tau, aer.ssa, aer.g);
-    check_phase(ph, cld_tau);
-    check_scene(dx, dy, dz, mu0);
-    const size_t ncol = size_t(nx)*ny;
-    // the photon list, the weights and the common unit U = S/P (rrx_rt_common.h)
-    std::vector<long long> photon_end(size_t(ngpt) + 1, 0);
-    std::vector<F> weight0(ngpt, F(0.)), dif_frac(ngpt, F(0.));
+    constexpr bool spectral = SPECTRAL;
+    const size_t ncol = size_t(m.nx)*m.ny;
+    // the spectral form's photon list, its weights and the sums of U = S/P
+    std::vector<long long> photon_end;
     long long P = 0;
     F S = F(0.);
-    for (int g=0; g<ngpt; ++g)
-    {
-        if (inc_dir[g] < F(0.) || inc_dif[g] < F(0.)) throw std::runtime_error("inc_dir, inc_dif must be >= 0");
-        if (m[g] < 0) throw std::runtime_error("photons_per_pixel_gpt is negative at g-point " + std::to_string(g));
-        if (m[g] > 0 && !(inc_dir[g] + inc_dif[g] > F(0.)))
-            throw std::runtime_error("photons_per_pixel_gpt is > 0 at g-point " + std::to_string(g) + ", which has no incident flux");
-        if (m[g] > (0x7FFFFFFFFFFFFFFFll - photon_end[g]) / (long long)ncol) throw std::runtime_error("the photon list exceeds 2^63 - 1");
-        photon_end[g+1] = photon_end[g] + m[g]*(long long)ncol;
-        P += m[g];
-        if (m[g] > 0) S = S + (inc_dir[g] + inc_dif[g]);
-    }
-    if (max_events < 1) throw std::runtime_error("max_events must be >= 1");
-    check_grid(nx, ny, nz, knx, kny, knz);
-    const F U = P > 0 ? S / F(P) : F(0.);
-    for (int g=0; g<ngpt; ++g)
-        if (m[g] > 0)
-        {
-            const F inc = inc_dir[g] + inc_dif[g];
-            weight0[g] = (inc / F(m[g])) / U;
-            dif_frac[g] = inc_dif[g] / inc;
-        }
-    const bool bg_on = nbg > 0;
-    BgLevels<F> lev{}, thick{};
-    AerIn<F> aer_bg{};
-    if (bg_on)
-    {
-        check_aerosol("bg_aer_", nbnd, band_lims_gpt, bg_aer.tau, bg_aer.ssa, bg_aer.g);
-        aer_bg = bg_aer;
-        check_bg_medium(nbg, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g);
-        check_needed({{"toa_up", bg_out[0]}, {"tod_dn_dir", bg_out[1]}, {"tod_dn_dif", bg_out[2]}, {"bg_abs_dir", bg_out[3]},
-                      {"bg_abs_dif", bg_out[4]}});
-        lev = bg_levels<F>(nbg, dz_bg, nz, knz, dz);
-        thick = bg_thicknesses(nbg, dz_bg);
-    }
+    const Needed own = {{"inc_dir", inc_dir}, {"inc_dif", inc_dif}};
+    const Needed own_spectral = {{"inc_dir", inc_dir}, {"inc_dif", inc_dif}, {"photons_per_pixel_gpt", m_gpt}};
+    const Extents work = {{"photons_per_pixel", photons_per_pixel}};
+    if (check_forward(m, sun, ph, bg, run.max_events, spectral ? Extents{} : work, spectral ? own_spectral : own, out,
+            [&] { if (spectral) check_spectral_ngpt(m.ngpt); }, nothing,
+            [&] {
+                if (spectral) photon_end.assign(size_t(m.ngpt) + 1, 0);
+                for (int g=0; g<m.ngpt; ++g)
+                {
+                    if (inc_dir[g] < F(0.) || inc_dif[g] < F(0.)) throw std::runtime_error("inc_dir, inc_dif must be >= 0");
+                    if (!spectral) continue;
+                    if (m_gpt[g] < 0) throw std::runtime_error("photons_per_pixel_gpt is negative at g-point " + std::to_string(g));
+                    if (m_gpt[g] > 0 && !(inc_dir[g] + inc_dif[g] > F(0.)))
+                        throw std::runtime_error("photons_per_pixel_gpt is > 0 at g-point " + std::to_string(g) + ", which has no incident flux");
+                    if (m_gpt[g] > (0x7FFFFFFFFFFFFFFFll - photon_end[g]) / (long long)ncol) throw std::runtime_error("the photon list exceeds 2^63 - 1");
+                    photon_end[g+1] = photon_end[g] + m_gpt[g]*(long long)ncol;
+                    P += m_gpt[g];
+                    if (m_gpt[g] > 0) S = S + (inc_dir[g] + inc_dif[g]);
+                }
+            }))
+        return 0;
+    const LoopBg<F> lb = loop_background(bg, m, [&] { check_bg_outputs(out); });
+    const BgLevels<F> thick = lb.on ? bg_thicknesses(bg.nbg, bg.dz_bg) : BgLevels<F>{};
 
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t n_sfc = 4*ncol, n_abs = 2*ncol*nz;
-    const size_t n_bgc = bg_on ? 3*ncol + 2*size_t(nbg) : 0, n_counts = n_sfc + n_abs + n_bgc;
-    const size_t nkn = size_t(knx)*kny*knz;
-    const int chunk = spectral_gpt_per_launch(nkn*sizeof(F), ngpt);
-    const auto words = [](const size_t bytes) { return (bytes + sizeof(u64) - 1) / sizeof(u64); };
-    const size_t n_kn = words(nkn*chunk*sizeof(F));
-    const size_t n_prof = bg_on ? words(size_t(ngpt)*BG_ROWS_AER*(nbg + 1)*sizeof(F)) : 0;
-    const size_t n_pe = size_t(ngpt) + 1, n_w = words(size_t(ngpt)*sizeof(F));
+    hipStream_t st = static_cast<hipStream_t>(run.stream);
+    const size_t nkn = size_t(m.knx)*m.kny*m.knz;
+    const int chunk = spectral ? spectral_gpt_per_launch(nkn*sizeof(F), m.ngpt) : 1;
+    const size_t profile_numbers = size_t(spectral ? m.ngpt : 1)*(spectral || lb.form == FORM_AER ? BG_ROWS_AER : BG_ROWS)*(lb.nbg + 1);
     WorkspaceLease lease(st);
-    u64* counts = lease.get<u64>(n_counts + n_kn + n_prof + n_pe + 2*n_w);
-    F* k_null = reinterpret_cast<F*>(counts + n_counts);
-    F* profile = reinterpret_cast<F*>(counts + n_counts + n_kn);
-    long long* d_pe = reinterpret_cast<long long*>(counts + n_counts + n_kn + n_prof);
-    F* d_w0 = reinterpret_cast<F*>(counts + n_counts + n_kn + n_prof + n_pe);
-    F* d_df = reinterpret_cast<F*>(counts + n_counts + n_kn + n_prof + n_pe + n_w);
-    bool ok = hipMemsetAsync(n_capped, 0, sizeof(u64), st) == hipSuccess;
-    if (bg_on)
+    const FwWorkspace<F> w(lease, m, lb.nbg, nkn*chunk, lb.on ? profile_numbers : 0, spectral ? m.ngpt : 0);
+    const FwOut<u64> t = w.tallies(out.n_capped);
+    w.zero_outputs(out, st);
+    FwBg<F,true,true> b{BgIn<F>{lb.nbg, w.profile, lb.lev}, bg_tallies<F>(t), m.aer};
+    if constexpr (!SPECTRAL)
     {
-        for (int n=0; n<3; ++n) ok = ok && hipMemsetAsync(bg_out[n], 0, ncol*sizeof(F), st) == hipSuccess;
-        for (int n=3; n<5; ++n) ok = ok && hipMemsetAsync(bg_out[n], 0, size_t(nbg)*sizeof(F), st) == hipSuccess;
+        const long long nphotons = photons_per_pixel*(long long)ncol;
+        for (int g=0; g<m.ngpt; ++g)
+        {
+            if (!(inc_dir[g] + inc_dif[g] > F(0.))) continue;
+            w.zero_counts(st);
+            launch_k_null<F>(m, g, m.aer.tau, w.k_null, st);
+            const F scale = (inc_dir[g] + inc_dif[g]) / F(photons_per_pixel);
+            if (lb.on) launch_bg_profile<F>(bg, m.ngpt, m.nbnd, m.band_lims_gpt, g, thick, lb.form == FORM_AER, lb.aer, w.profile, st);
+            launch_trace<F>(trace_args<F>(m, g, w.k_null, 0ull, nphotons, run.max_events, t), ph, sun, inc_dir[g], inc_dif[g], run.seed, st,
+                            lb.form, b);
+            w.add_fluxes(scale, m.dz, bg.dz_bg, out, st);
+        }
     }
-    for (F* out : {sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up}) ok = ok && hipMemsetAsync(out, 0, ncol*sizeof(F), st) == hipSuccess;
-    for (F* out : {abs_dir, abs_dif}) ok = ok && hipMemsetAsync(out, 0, ncol*nz*sizeof(F), st) == hipSuccess;
-    if (!ok) throw std::runtime_error("zeroing the outputs failed");
-    if (P == 0) return 0;
-    ok = hipMemsetAsync(counts, 0, n_counts*sizeof(u64), st) == hipSuccess
-      && hipMemcpyAsync(d_pe, photon_end.data(), n_pe*sizeof(long long), hipMemcpyHostToDevice, st) == hipSuccess
-      && hipMemcpyAsync(d_w0, weight0.data(), size_t(ngpt)*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess
-      && hipMemcpyAsync(d_df, dif_frac.data(), size_t(ngpt)*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess
-      && hipStreamSynchronize(st) == hipSuccess;          // (the host arrays end with this call)
-    if (!ok) throw std::runtime_error("zeroing the counts or copying the photon list failed");
-    if (bg_on) launch_bg_profile_all<F>(nbg, ngpt, nbnd, thick, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, aer_bg, profile, st);
-    u64* c = counts;
-    u64* cb = c + n_sfc + n_abs;
-    FwBg<F,true,true,true> b{BgIn<F>{bg_on ? nbg : 0, profile, lev}, BgTallies<F>{cb, cb + ncol, cb + 2*ncol, cb + 3*ncol, cb + 3*ncol + nbg}, aer,
-                             SpecIn<F>{ngpt, 0, d_pe, d_w0, d_df}};
-    for (int g0=0; g0<ngpt; g0+=chunk)
+    else
     {
-        const int g1 = std::min(g0 + chunk, ngpt);
-        const long long n = photon_end[g1] - photon_end[g0];
-        if (n == 0) continue;
-        launch_k_null_all<F>(nx, ny, nz, nbnd, g0, g1 - g0, top_at_1 ? 1 : 0, tau, band_lims_gpt, cld_tau, aer.tau, dz, knx, kny, knz, k_null, st);
-        TraceArgs<F> a{nx, ny, nz, nbnd, 0, top_at_1 ? 1 : 0, independent_column ? 1 : 0, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g,
-                       dx, dy, dz, sfc_albedo, F(0.), F(0.), F(0.), F(0.), knx, kny, knz, k_null, 0u, 0u, u64(photon_end[g0]), n, max_events,
-                       c, c + ncol, c + 2*ncol, c + 3*ncol, c + n_sfc, c + n_sfc + ncol*nz, n_capped};
-        b.sp.kn_g0 = g0;
-        launch_trace_spectral<F>(a, ph, mu0, azimuth, seed, st, b);
+        if (P == 0) return 0;
+        const F U = S / F(P);
+        std::vector<F> weight0(m.ngpt, F(0.)), dif_frac(m.ngpt, F(0.));
+        for (int g=0; g<m.ngpt; ++g)
+            if (m_gpt[g] > 0)
+            {
+                const F inc = inc_dir[g] + inc_dif[g];
+                weight0[g] = (inc / F(m_gpt[g])) / U;
+                dif_frac[g] = inc_dif[g] / inc;
+            }
+        const bool ok = hipMemsetAsync(w.counts, 0, w.n_counts*sizeof(u64), st) == hipSuccess
+          && hipMemcpyAsync(w.photon_end, photon_end.data(), photon_end.size()*sizeof(long long), hipMemcpyHostToDevice, st) == hipSuccess
+          && hipMemcpyAsync(w.weight0, weight0.data(), size_t(m.ngpt)*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess
+          && hipMemcpyAsync(w.dif_frac, dif_frac.data(), size_t(m.ngpt)*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess
+          && hipStreamSynchronize(st) == hipSuccess;          // (the host arrays end with this call)
+        if (!ok) throw std::runtime_error("zeroing the counts or copying the photon list failed");
+        if (lb.on) launch_bg_profile_all<F>(bg, m.ngpt, m.nbnd, m.band_lims_gpt, thick, lb.aer, w.profile, st);
+        FwBg<F,true,true,true> bs{b.in, b.t, b.aer, SpecIn<F>{m.ngpt, 0, w.photon_end, w.weight0, w.dif_frac}};
+        for (int g0=0; g0<m.ngpt; g0+=chunk)
+        {
+            const int g1 = std::min(g0 + chunk, m.ngpt);
+            const long long n = photon_end[g1] - photon_end[g0];
+            if (n == 0) continue;
+            launch_k_null_all<F>(m, g0, g1 - g0, m.aer.tau, w.k_null, st);
+            bs.sp.kn_g0 = g0;
+            launch_trace_spectral<F>(trace_args<F>(m, 0, w.k_null, u64(photon_end[g0]), n, run.max_events, t), ph, sun, run.seed, st, bs);
+        }
+        w.add_fluxes(U, m.dz, bg.dz_bg, out, st);
     }
-    if (bg_on)
-    {
-        launch_counts_to_flux<F>(ncol, b.t.toa_up, U, bg_out[0], st);
-        launch_counts_to_flux<F>(ncol, b.t.tod_dn_dir, U, bg_out[1], st);
-        launch_counts_to_flux<F>(ncol, b.t.tod_dn_dif, U, bg_out[2], st);
-        BgLevels<F> per_layer{};
-        for (int l=0; l<nbg; ++l) per_layer.v[l] = (U / dz_bg[l]) / F(ncol);
-        bg_counts_to_flux_kernel<F><<<ceil_div(nbg, 64), 64, 0, st>>>(nbg, b.t.bg_abs_dir, per_layer, bg_out[3]);
-        bg_counts_to_flux_kernel<F><<<ceil_div(nbg, 64), 64, 0, st>>>(nbg, b.t.bg_abs_dif, per_layer, bg_out[4]);
-    }
-    launch_counts_to_flux<F>(ncol, c, U, sfc_dn_dir, st);
-    launch_counts_to_flux<F>(ncol, c + ncol, U, sfc_dn_dif, st);
-    launch_counts_to_flux<F>(ncol, c + 2*ncol, U, sfc_up, st);
-    launch_counts_to_flux<F>(ncol, c + 3*ncol, U, tod_up, st);
-    launch_counts_to_flux<F>(ncol*nz, c + n_sfc, U / dz, abs_dir, st);
-    launch_counts_to_flux<F>(ncol*nz, c + n_sfc + ncol*nz, U / dz, abs_dif, st);
     RRX_CATCH(entry)
 }
 }  // namespace
 
+// ---- the C entries: each builds the structs and calls its family's one function
+#define RT_P_HEAD int nx, int ny, int nz, int ngpt, int nbnd
+#define RT_P_KNULL(F) RrxBool top_at_1, const F* tau, const int* band_lims_gpt, const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null
+#define RT_P_COUNTS \
+        unsigned long long* sfc_dn_dir, unsigned long long* sfc_dn_dif, unsigned long long* sfc_up, unsigned long long* tod_up, \
+        unsigned long long* abs_dir, unsigned long long* abs_dif, unsigned long long* n_capped
+#define RT_P_BG_COUNTS \
+        unsigned long long* toa_up, unsigned long long* tod_dn_dir, unsigned long long* tod_dn_dif, \
+        unsigned long long* bg_abs_dir, unsigned long long* bg_abs_dif
+#define RT_P_TRACE(F) \
+        RT_P_GRID(F), F inc_dir, F inc_dif, int knx, int kny, int knz, const F* k_null, \
+        unsigned long long seed, long long photon0, long long nphotons, int max_events, RT_P_COUNTS
+#define RT_P_LOOP(F, PHOTONS) \
+        RT_P_HEAD, RrxBool top_at_1, RrxBool independent_column, RT_P_GRID(F), const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
+        PHOTONS, unsigned long long seed, int max_events, \
+        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped
+#define RT_P_BG_FLUXES(F) F* toa_up, F* tod_dn_dir, F* tod_dn_dif, F* bg_abs_dir, F* bg_abs_dif
+#define RT_KNULL_MEDIUM(F, AER_TAU) \
+        Medium<F>{nx, ny, nz, ngpt, nbnd, top_at_1, 0, tau, nullptr, band_lims_gpt, cld_tau, nullptr, nullptr, F(0.), F(0.), dz, nullptr, \
+                  knx, kny, knz, AerIn<F>{AER_TAU, nullptr, nullptr}}
+#define RT_OUT(T) FwOut<T>{sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, nullptr, nullptr, nullptr, nullptr, nullptr}
+#define RT_OUT_BG(T) FwOut<T>{sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, toa_up, tod_dn_dir, tod_dn_dif, bg_abs_dir, bg_abs_dif}
+#define RT_TRACE(F, NAME, AER, PHASE, BG, OUT) \
+        trace_entry<F,false>(NAME, RT_MEDIUM(F, independent_column, AER), RT_SUN(F), PHASE, BG, RT_RUN, igpt, inc_dir, inc_dif, SpecIn<F>{}, k_null, \
+                       photon0, nphotons, OUT)
+#define RT_LOOP(F, NAME, AER, PHASE, BG, OUT) \
+        raytracer_sw_entry<F,false>(NAME, RT_MEDIUM(F, independent_column, AER), RT_SUN(F), PHASE, BG, RT_RUN, inc_dir, inc_dif, \
+                              photons_per_pixel, nullptr, OUT)
+
 extern "C"
 {
 #define RRX_DEFINE_RT(F, SFX) \
-int rrx_rt_k_null##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, const F* tau, const int* band_lims_gpt, \
-        const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, void* stream) \
-{ return k_null_entry<F>("rrx_rt_k_null" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null, stream); } \
-int rrx_rt_trace_counts##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, RrxBool independent_column, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, F inc_dir, F inc_dif, int knx, int kny, int knz, const F* k_null, \
-        unsigned long long seed, long long photon0, long long nphotons, int max_events, \
-        unsigned long long* sfc_dn_dir, unsigned long long* sfc_dn_dif, unsigned long long* sfc_up, unsigned long long* tod_up, \
-        unsigned long long* abs_dir, unsigned long long* abs_dif, unsigned long long* n_capped, void* stream) \
-{ return trace_entry<F>("rrx_rt_trace_counts" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
-                        cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, k_null, seed, \
-                        photon0, nphotons, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream); } \
+int rrx_rt_k_null##SFX(RT_P_HEAD, int igpt, RT_P_KNULL(F), void* stream) \
+{ return k_null_entry<F,false>("rrx_rt_k_null" #SFX, RT_KNULL_MEDIUM(F, nullptr), igpt, k_null, stream); } \
+int rrx_rt_trace_counts##SFX(RT_P_HEAD, int igpt, RrxBool top_at_1, RrxBool independent_column, RT_P_TRACE(F), void* stream) \
+{ return RT_TRACE(F, "rrx_rt_trace_counts" #SFX, AerIn<F>{}, PhaseIn<F>{}, RT_NO_BG(F), RT_OUT(u64)); } \
 int rrx_rt_counts_to_flux##SFX(long long n, const unsigned long long* counts, F scale, F* out, void* stream) \
 { return counts_to_flux_entry<F>("rrx_rt_counts_to_flux" #SFX, n, counts, scale, out, stream); } \
-int rrx_raytracer_sw##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
-        long long photons_per_pixel, unsigned long long seed, int max_events, \
-        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, void* stream) \
-{ return raytracer_sw_entry<F>("rrx_raytracer_sw" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
-                               cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, \
-                               photons_per_pixel, seed, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream); } \
-int rrx_rt_trace_counts_phase##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, RrxBool independent_column, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, F inc_dir, F inc_dif, int knx, int kny, int knz, const F* k_null, \
-        unsigned long long seed, long long photon0, long long nphotons, int max_events, \
-        unsigned long long* sfc_dn_dir, unsigned long long* sfc_dn_dif, unsigned long long* sfc_up, unsigned long long* tod_up, \
-        unsigned long long* abs_dir, unsigned long long* abs_dif, unsigned long long* n_capped, \
-        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, void* stream) \
-{ return trace_entry<F>("rrx_rt_trace_counts_phase" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
-                        cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, k_null, seed, \
-                        photon0, nphotons, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
-                        PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}); } \
-int rrx_raytracer_sw_phase##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
-        long long photons_per_pixel, unsigned long long seed, int max_events, \
-        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, \
-        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, void* stream) \
-{ return raytracer_sw_entry<F>("rrx_raytracer_sw_phase" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
-                               cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, \
-                               photons_per_pixel, seed, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
-                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}); } \
+int rrx_raytracer_sw##SFX(RT_P_LOOP(F, long long photons_per_pixel), void* stream) \
+{ return RT_LOOP(F, "rrx_raytracer_sw" #SFX, AerIn<F>{}, PhaseIn<F>{}, RT_NO_BG(F), RT_OUT(F)); } \
+int rrx_rt_trace_counts_phase##SFX(RT_P_HEAD, int igpt, RrxBool top_at_1, RrxBool independent_column, RT_P_TRACE(F), RT_P_PHASE(F), void* stream) \
+{ return RT_TRACE(F, "rrx_rt_trace_counts_phase" #SFX, AerIn<F>{}, RT_PHASE(F), RT_NO_BG(F), RT_OUT(u64)); } \
+int rrx_raytracer_sw_phase##SFX(RT_P_LOOP(F, long long photons_per_pixel), RT_P_PHASE(F), void* stream) \
+{ return RT_LOOP(F, "rrx_raytracer_sw_phase" #SFX, AerIn<F>{}, RT_PHASE(F), RT_NO_BG(F), RT_OUT(F)); } \
 int rrx_rt_bg_profile##SFX(int nbg, int ngpt, int nbnd, int igpt, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const int* band_lims_gpt, \
         const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* bg_profile, void* stream) \
-{ return bg_profile_entry<F>("rrx_rt_bg_profile" #SFX, nbg, ngpt, nbnd, igpt, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, \
-                             bg_cld_g, bg_profile, stream); } \
-int rrx_rt_trace_counts_bg##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, RrxBool independent_column, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, F inc_dir, F inc_dif, int knx, int kny, int knz, const F* k_null, \
-        unsigned long long seed, long long photon0, long long nphotons, int max_events, \
-        unsigned long long* sfc_dn_dir, unsigned long long* sfc_dn_dif, unsigned long long* sfc_up, unsigned long long* tod_up, \
-        unsigned long long* abs_dir, unsigned long long* abs_dif, unsigned long long* n_capped, \
-        unsigned long long* toa_up, unsigned long long* tod_dn_dir, unsigned long long* tod_dn_dif, \
-        unsigned long long* bg_abs_dir, unsigned long long* bg_abs_dif, \
-        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+{ return bg_profile_entry<F,false>("rrx_rt_bg_profile" #SFX, RT_BG_MEDIUM(F, FORM_BG, AerIn<F>{}), ngpt, nbnd, band_lims_gpt, igpt, bg_profile, stream); } \
+int rrx_rt_trace_counts_bg##SFX(RT_P_HEAD, int igpt, RrxBool top_at_1, RrxBool independent_column, RT_P_TRACE(F), RT_P_BG_COUNTS, RT_P_PHASE(F), \
         int nbg, const F* dz_bg, const F* bg_profile, void* stream) \
-{ return trace_entry<F>("rrx_rt_trace_counts_bg" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
-                        cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, k_null, seed, \
-                        photon0, nphotons, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
-                        PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, true, \
-                        BgTallies<F>{toa_up, tod_dn_dir, tod_dn_dif, bg_abs_dir, bg_abs_dif}, nbg, dz_bg, bg_profile); } \
-int rrx_raytracer_sw_bg##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
-        long long photons_per_pixel, unsigned long long seed, int max_events, \
-        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, \
-        F* toa_up, F* tod_dn_dir, F* tod_dn_dif, F* bg_abs_dir, F* bg_abs_dif, \
-        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
-        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, void* stream) \
-{ F* const bg_out[5] = {toa_up, tod_dn_dir, tod_dn_dif, bg_abs_dir, bg_abs_dif}; \
-  return raytracer_sw_entry<F>("rrx_raytracer_sw_bg" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
-                               cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, \
-                               photons_per_pixel, seed, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
-                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, true, bg_out, nbg, dz_bg, bg_tau, bg_ssa, \
-                               bg_cld_tau, bg_cld_ssa, bg_cld_g); } \
-int rrx_rt_k_null_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, const F* tau, const int* band_lims_gpt, \
-        const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, const F* aer_tau, void* stream) \
-{ return k_null_entry<F>("rrx_rt_k_null_aer" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null, \
-                         stream, aer_tau); } \
+{ return RT_TRACE(F, "rrx_rt_trace_counts_bg" #SFX, AerIn<F>{}, RT_PHASE(F), RT_BG_PROFILE(F, FORM_BG), RT_OUT_BG(u64)); } \
+int rrx_raytracer_sw_bg##SFX(RT_P_LOOP(F, long long photons_per_pixel), RT_P_BG_FLUXES(F), RT_P_PHASE(F), RT_P_BG(F), void* stream) \
+{ return RT_LOOP(F, "rrx_raytracer_sw_bg" #SFX, AerIn<F>{}, RT_PHASE(F), RT_BG_MEDIUM(F, FORM_BG, AerIn<F>{}), RT_OUT_BG(F)); } \
+int rrx_rt_k_null_aer##SFX(RT_P_HEAD, int igpt, RT_P_KNULL(F), const F* aer_tau, void* stream) \
+{ return k_null_entry<F,false>("rrx_rt_k_null_aer" #SFX, RT_KNULL_MEDIUM(F, aer_tau), igpt, k_null, stream); } \
 int rrx_rt_bg_profile_aer##SFX(int nbg, int ngpt, int nbnd, int igpt, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const int* band_lims_gpt, \
         const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* bg_profile, \
         const F* bg_aer_tau, const F* bg_aer_ssa, const F* bg_aer_g, void* stream) \
 { const AerIn<F> bg_aer{bg_aer_tau, bg_aer_ssa, bg_aer_g}; \
-  return bg_profile_entry<F>("rrx_rt_bg_profile_aer" #SFX, nbg, ngpt, nbnd, igpt, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, \
-                             bg_cld_g, bg_profile, stream, &bg_aer); } \
-int rrx_rt_trace_counts_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, RrxBool independent_column, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, F inc_dir, F inc_dif, int knx, int kny, int knz, const F* k_null, \
-        unsigned long long seed, long long photon0, long long nphotons, int max_events, \
-        unsigned long long* sfc_dn_dir, unsigned long long* sfc_dn_dif, unsigned long long* sfc_up, unsigned long long* tod_up, \
-        unsigned long long* abs_dir, unsigned long long* abs_dif, unsigned long long* n_capped, \
-        unsigned long long* toa_up, unsigned long long* tod_dn_dir, unsigned long long* tod_dn_dif, \
-        unsigned long long* bg_abs_dir, unsigned long long* bg_abs_dif, \
-        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+  return bg_profile_entry<F,false>("rrx_rt_bg_profile_aer" #SFX, RT_BG_MEDIUM(F, FORM_AER, bg_aer), ngpt, nbnd, band_lims_gpt, igpt, bg_profile, stream); } \
+int rrx_rt_trace_counts_aer##SFX(RT_P_HEAD, int igpt, RrxBool top_at_1, RrxBool independent_column, RT_P_TRACE(F), RT_P_BG_COUNTS, RT_P_PHASE(F), \
         int nbg, const F* dz_bg, const F* bg_profile, const F* aer_tau, const F* aer_ssa, const F* aer_g, void* stream) \
 { const AerIn<F> aer{aer_tau, aer_ssa, aer_g}; \
-  return trace_entry<F>("rrx_rt_trace_counts_aer" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
-                        cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, k_null, seed, \
-                        photon0, nphotons, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
-                        PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, true, \
-                        BgTallies<F>{toa_up, tod_dn_dir, tod_dn_dif, bg_abs_dir, bg_abs_dif}, nbg, dz_bg, bg_profile, &aer); } \
-int rrx_raytracer_sw_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
-        long long photons_per_pixel, unsigned long long seed, int max_events, \
-        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, \
-        F* toa_up, F* tod_dn_dir, F* tod_dn_dif, F* bg_abs_dir, F* bg_abs_dif, \
-        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
-        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, \
+  return RT_TRACE(F, "rrx_rt_trace_counts_aer" #SFX, aer, RT_PHASE(F), RT_BG_PROFILE(F, FORM_AER), RT_OUT_BG(u64)); } \
+int rrx_raytracer_sw_aer##SFX(RT_P_LOOP(F, long long photons_per_pixel), RT_P_BG_FLUXES(F), RT_P_PHASE(F), RT_P_BG(F), \
         const F* const* aer3, const F* const* bg_aer3, void* stream) \
-{ F* const bg_out[5] = {toa_up, tod_dn_dir, tod_dn_dif, bg_abs_dir, bg_abs_dif}; \
-  /* each triple is a host array of three device pointers (tau, ssa, g); a NULL array is a triple of NULLs */ \
-  const AerIn<F> aer = aer3 != nullptr ? AerIn<F>{aer3[0], aer3[1], aer3[2]} : AerIn<F>{}; \
-  const AerIn<F> bg_aer = bg_aer3 != nullptr ? AerIn<F>{bg_aer3[0], bg_aer3[1], bg_aer3[2]} : AerIn<F>{}; \
-  return raytracer_sw_entry<F>("rrx_raytracer_sw_aer" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, independent_column, tau, ssa, band_lims_gpt, \
-                               cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, \
-                               photons_per_pixel, seed, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
-                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, true, bg_out, nbg, dz_bg, bg_tau, bg_ssa, \
-                               bg_cld_tau, bg_cld_ssa, bg_cld_g, &aer, &bg_aer); } \
-int rrx_rt_k_null_all##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, const F* tau, const int* band_lims_gpt, \
-        const F* cld_tau, F dz, int knx, int kny, int knz, F* k_null, const F* aer_tau, void* stream) \
-{ return k_null_all_entry<F>("rrx_rt_k_null_all" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null, \
-                             aer_tau, stream); } \
+{ return RT_LOOP(F, "rrx_raytracer_sw_aer" #SFX, aer_of(aer3), RT_PHASE(F), RT_BG_MEDIUM(F, FORM_AER, aer_of(bg_aer3)), RT_OUT_BG(F)); } \
+int rrx_rt_k_null_all##SFX(RT_P_HEAD, RT_P_KNULL(F), const F* aer_tau, void* stream) \
+{ return k_null_entry<F,true>("rrx_rt_k_null_all" #SFX, RT_KNULL_MEDIUM(F, aer_tau), 0, k_null, stream); } \
 int rrx_rt_bg_profile_all##SFX(int nbg, int ngpt, int nbnd, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const int* band_lims_gpt, \
         const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, F* bg_profile, \
         const F* bg_aer_tau, const F* bg_aer_ssa, const F* bg_aer_g, void* stream) \
-{ return bg_profile_all_entry<F>("rrx_rt_bg_profile_all" #SFX, nbg, ngpt, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, \
-                                 bg_cld_g, bg_profile, AerIn<F>{bg_aer_tau, bg_aer_ssa, bg_aer_g}, stream); } \
-int rrx_rt_trace_counts_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const long long* photon_end, const F* weight0, const F* dif_frac, \
-        int knx, int kny, int knz, const F* k_null, \
-        unsigned long long seed, long long photon0, long long nphotons, int max_events, \
-        unsigned long long* sfc_dn_dir, unsigned long long* sfc_dn_dif, unsigned long long* sfc_up, unsigned long long* tod_up, \
-        unsigned long long* abs_dir, unsigned long long* abs_dif, unsigned long long* n_capped, \
-        unsigned long long* toa_up, unsigned long long* tod_dn_dir, unsigned long long* tod_dn_dif, \
-        unsigned long long* bg_abs_dir, unsigned long long* bg_abs_dif, \
-        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+{ const AerIn<F> bg_aer{bg_aer_tau, bg_aer_ssa, bg_aer_g}; \
+  return bg_profile_entry<F,true>("rrx_rt_bg_profile_all" #SFX, RT_BG_MEDIUM(F, FORM_AER, bg_aer), ngpt, nbnd, band_lims_gpt, 0, bg_profile, stream); } \
+int rrx_rt_trace_counts_spectral##SFX(RT_P_HEAD, RrxBool top_at_1, RrxBool independent_column, RT_P_GRID(F), \
+        const long long* photon_end, const F* weight0, const F* dif_frac, int knx, int kny, int knz, const F* k_null, \
+        unsigned long long seed, long long photon0, long long nphotons, int max_events, RT_P_COUNTS, RT_P_BG_COUNTS, RT_P_PHASE(F), \
         int nbg, const F* dz_bg, const F* bg_profile, const F* aer_tau, const F* aer_ssa, const F* aer_g, void* stream) \
-{ return trace_spectral_entry<F>("rrx_rt_trace_counts_spectral" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, independent_column, tau, ssa, \
-                                 band_lims_gpt, cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, photon_end, weight0, dif_frac, \
-                                 knx, kny, knz, k_null, seed, photon0, nphotons, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, \
-                                 abs_dif, n_capped, BgTallies<F>{toa_up, tod_dn_dir, tod_dn_dif, bg_abs_dir, bg_abs_dif}, \
-                                 PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, nbg, dz_bg, bg_profile, \
-                                 AerIn<F>{aer_tau, aer_ssa, aer_g}, stream); } \
-int rrx_raytracer_sw_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RrxBool independent_column, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, const F* inc_dif, int knx, int kny, int knz, \
-        const long long* photons_per_pixel_gpt, unsigned long long seed, int max_events, \
-        F* sfc_dn_dir, F* sfc_dn_dif, F* sfc_up, F* tod_up, F* abs_dir, F* abs_dif, unsigned long long* n_capped, \
-        F* toa_up, F* tod_dn_dir, F* tod_dn_dif, F* bg_abs_dir, F* bg_abs_dif, \
-        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
-        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, \
+{ const AerIn<F> aer{aer_tau, aer_ssa, aer_g}; \
+  const SpecIn<F> sp{ngpt, 0, photon_end, weight0, dif_frac}; \
+  return trace_entry<F,true>("rrx_rt_trace_counts_spectral" #SFX, RT_MEDIUM(F, independent_column, aer), RT_SUN(F), RT_PHASE(F), \
+                        RT_BG_PROFILE(F, FORM_AER), RT_RUN, 0, F(0.), F(0.), sp, k_null, photon0, nphotons, RT_OUT_BG(u64)); } \
+int rrx_raytracer_sw_spectral##SFX(RT_P_LOOP(F, const long long* photons_per_pixel_gpt), RT_P_BG_FLUXES(F), RT_P_PHASE(F), RT_P_BG(F), \
         const F* const* aer3, const F* const* bg_aer3, void* stream) \
-{ F* const bg_out[5] = {toa_up, tod_dn_dir, tod_dn_dif, bg_abs_dir, bg_abs_dif}; \
-  const AerIn<F> aer = aer3 != nullptr ? AerIn<F>{aer3[0], aer3[1], aer3[2]} : AerIn<F>{}; \
-  const AerIn<F> bg_aer = bg_aer3 != nullptr ? AerIn<F>{bg_aer3[0], bg_aer3[1], bg_aer3[2]} : AerIn<F>{}; \
-  return raytracer_sw_spectral_entry<F>("rrx_raytracer_sw_spectral" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, independent_column, tau, ssa, \
-                               band_lims_gpt, cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, \
-                               photons_per_pixel_gpt, seed, max_events, sfc_dn_dir, sfc_dn_dif, sfc_up, tod_up, abs_dir, abs_dif, n_capped, stream, \
-                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, bg_out, nbg, dz_bg, bg_tau, bg_ssa, \
-                               bg_cld_tau, bg_cld_ssa, bg_cld_g, aer, bg_aer); }
+{ return raytracer_sw_entry<F,true>("rrx_raytracer_sw_spectral" #SFX, RT_MEDIUM(F, independent_column, aer_of(aer3)), RT_SUN(F), RT_PHASE(F), \
+                               RT_BG_MEDIUM(F, FORM_AER, aer_of(bg_aer3)), RT_RUN, inc_dir, inc_dif, 0, photons_per_pixel_gpt, RT_OUT_BG(F)); }
 
 RRX_DEFINE_RT(double, _f64)
 RRX_DEFINE_RT(float, _f32)

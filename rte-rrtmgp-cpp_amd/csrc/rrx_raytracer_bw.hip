@@ -51,7 +51,7 @@
 // cell's radius: phase_eval towards the sun in the deposit, phase_sample for the new direction, the same draws in the same order.
 // The walk carries the radius where the Henyey-Greenstein form carries g_c; the nodes are staged in LDS once per workgroup.
 #include "rrx_rt_phase.h"
-#include "rrx_hip.h"
+#include "rrx_rt_host.h"
 
 namespace
 {
@@ -504,12 +504,18 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
     }
 }
 
-// ---- host side
+// ---- host side (rrx_rt_host.h)
 
+// the virtual camera: s is (12,): position, w, h, e_d
+template<typename F> struct Sensor { int type, npx, npy; F fov; const F* s; };
+
+// throws, or returns the bound of the walk to the sun
 template<typename F>
-void check_sensor(const int type, const F fov, const F* s, const F dx, const F dy, const F dz, const int nx, const int ny, const int nz,
-                  const F mu0, int& max_walk)
+int check_sensor(const Sensor<F>& sensor, const Medium<F>& m, const F mu0)
 {
+    const int type = sensor.type;
+    const F fov = sensor.fov;
+    const F* s = sensor.s;
     if (type < 0 || type > 3) throw std::runtime_error("sensor_type must be 0 (perspective), 1 (fisheye), 2 (orthographic) or 3 (flux sensor)");
     for (int i=0; i<12; ++i)
         if (!std::isfinite(double(s[i]))) throw std::runtime_error("sensor holds a number that is not finite");
@@ -524,178 +530,119 @@ void check_sensor(const int type, const F fov, const F* s, const F dx, const F d
     if (type == 2 && (std::fabs(len - 1.) > 1.e-5 || !(ez < 0.))) throw std::runtime_error("sensor e_d must be a unit vector with e_d.z < 0 for an orthographic sensor");
     if (type == 3 && ez == 0.) throw std::runtime_error("sensor e_d.z must be > 0 (at the surface, facing up) or < 0 (at the top, facing down) for a flux sensor");
     // the bound of the walk to the sun: nz + ceil(H tan / dx) + ceil(H tan / dy) + 2
-    const double tn = std::sqrt(std::max(0., 1. - double(mu0)*double(mu0))) / double(mu0), height = double(nz)*double(dz);
-    const double bound = double(nz) + std::ceil(height*tn/double(dx)) + std::ceil(height*tn/double(dy)) + 2.;
+    const double tn = std::sqrt(std::max(0., 1. - double(mu0)*double(mu0))) / double(mu0), height = double(m.nz)*double(m.dz);
+    const double bound = double(m.nz) + std::ceil(height*tn/double(m.dx)) + std::ceil(height*tn/double(m.dy)) + 2.;
     if (!(bound < 2.0e9)) throw std::runtime_error("mu0 is too small for this domain: the walk to the sun would take more than 2e9 cells");
-    max_walk = int(bound);
+    return int(bound);
 }
 
-template<typename F>
-void launch_trace_bw(BwArgs<F> a, const PhaseIn<F>& ph, const F mu0, const F azimuth, const int type, const int npx, const int npy, const F fov,
-                     const F* s, const u64 seed, hipStream_t st, const BgArgs<F,true>* bg = nullptr, const AerIn<F>* aer = nullptr)
+// the checks of the backward entries: check_entry with the sensor's extents and checks; max_walk: check_sensor's bound
+template<typename F, typename A, typename B, typename C>
+bool check_backward(const Medium<F>& m, const Sun<F>& sun, const PhaseIn<F>& ph, const Background<F>& bg, const int max_events,
+                    const Sensor<F>& sensor, std::pair<const char*, long long> work, Needed inputs, Needed outputs, int& max_walk,
+                    A after_nbnd, B after_phase, C after_scene)
 {
-    const double st_ = std::sqrt(std::max(0.0, 1.0 - double(mu0)*double(mu0)));
-    a.mu0 = mu0; a.sun_x = F(st_*std::cos(double(azimuth))); a.sun_y = F(st_*std::sin(double(azimuth))); a.sun_z = -mu0;
-    a.k0 = unsigned(seed & 0xFFFFFFFFull); a.k1 = unsigned(seed >> 32);
-    a.type = type; a.npx = npx; a.npy = npy; a.fov = fov;
-    a.px = s[0]; a.py = s[1]; a.pz = s[2]; a.wx = s[3]; a.wy = s[4]; a.wz = s[5]; a.hx = s[6]; a.hy = s[7]; a.hz = s[8];
-    a.ex = s[9]; a.ey = s[10]; a.ez = s[11];
-    const int blocks = int(std::min<long long>((a.nrays + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
-    if (bg != nullptr && aer != nullptr)
-    {
-        // the aerosol form: the background's profile has BG_ROWS_AER rows
-        const size_t lds = bg_lds_numbers(bg->in.nbg, BG_ROWS_AER)*sizeof(F);
-        const BgArgs<F,true,true> ba{bg->in, *aer};
-        if (ph.given()) trace_bw_kernel<F,true,true,true><<<blocks, RT_BLOCK, size_t(ph.nmu)*sizeof(F) + lds, st>>>(a, PhaseArgs<F,true>{ph}, ba);
-        else trace_bw_kernel<F,false,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, ba);
-    }
-    else if (bg != nullptr)
-    {
-        const size_t lds = bg_lds_numbers(bg->in.nbg)*sizeof(F);
-        if (ph.given()) trace_bw_kernel<F,true,true,false><<<blocks, RT_BLOCK, size_t(ph.nmu)*sizeof(F) + lds, st>>>(a, PhaseArgs<F,true>{ph}, *bg);
-        else trace_bw_kernel<F,false,true,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, *bg);
-    }
-    else if (ph.given()) trace_bw_kernel<F,true,false,false><<<blocks, RT_BLOCK, size_t(ph.nmu)*sizeof(F), st>>>(a, PhaseArgs<F,true>{ph}, BgArgs<F,false>{});
-    else trace_bw_kernel<F,false,false,false><<<blocks, RT_BLOCK, 0, st>>>(a, PhaseArgs<F,false>{}, BgArgs<F,false>{});
+    return check_entry(m, sun, ph, bg, max_events, {{"npx", sensor.npx}, {"npy", sensor.npy}, work}, inputs, outputs,
+                       after_nbnd, after_phase, after_scene, [&] {
+                           if ((long long)sensor.npx*sensor.npy > 0x7FFFFFFFll) throw std::runtime_error("npx npy exceeds 2^31 - 1");
+                           max_walk = check_sensor(sensor, m, sun.mu0);
+                       });
 }
 
+// THE BUILDER of the kernel arguments
 template<typename F>
-BwArgs<F> scene_args(int nx, int ny, int nz, int nbnd, int igpt, RrxBool top_at_1, const F* tau, const F* ssa, const int* band_lims_gpt,
-                     const F* cld_tau, const F* cld_ssa, const F* cld_g, F dx, F dy, F dz, const F* sfc_albedo,
-                     int knx, int kny, int knz, const F* k_null, u64 ray0, long long nrays, int max_events, int max_walk,
-                     u64* counts, u64* n_capped, u64* n_clamped)
+BwArgs<F> scene_args(const Medium<F>& m, const Sun<F>& sun, const Sensor<F>& sensor, const int igpt, const F* k_null, const u64 seed,
+                     const u64 ray0, const long long nrays, const int max_events, const int max_walk, u64* counts, u64* n_capped, u64* n_clamped)
 {
     BwArgs<F> a{};
-    a.nx = nx; a.ny = ny; a.nz = nz; a.nbnd = nbnd; a.igpt = igpt; a.top_at_1 = top_at_1 ? 1 : 0;
-    a.tau = tau; a.ssa = ssa; a.band_lims_gpt = band_lims_gpt; a.cld_tau = cld_tau; a.cld_ssa = cld_ssa; a.cld_g = cld_g;
-    a.dx = dx; a.dy = dy; a.dz = dz; a.sfc_albedo = sfc_albedo; a.knx = knx; a.kny = kny; a.knz = knz; a.k_null = k_null;
-    a.ray0 = ray0; a.nrays = nrays; a.max_events = max_events; a.max_walk = max_walk;
+    set_medium(a, m, igpt, k_null, max_events);
+    set_sun_and_key(a, sun, seed);
+    a.mu0 = sun.mu0;
+    a.ray0 = ray0; a.nrays = nrays; a.max_walk = max_walk;
     a.counts = counts; a.n_capped = n_capped; a.n_clamped = n_clamped;
+    const F* s = sensor.s;
+    a.type = sensor.type; a.npx = sensor.npx; a.npy = sensor.npy; a.fov = sensor.fov;
+    a.px = s[0]; a.py = s[1]; a.pz = s[2]; a.wx = s[3]; a.wy = s[4]; a.wz = s[5]; a.hx = s[6]; a.hy = s[7]; a.hz = s[8];
+    a.ex = s[9]; a.ey = s[10]; a.ez = s[11];
     return a;
 }
 
+// form: which instantiation runs; b is read in the forms with a background (its aerosol triple in FORM_AER, whose profile has
+// BG_ROWS_AER rows)
 template<typename F>
-int trace_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1,
-                   const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
-                   F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null,
-                   int sensor_type, int npx, int npy, F fov, const F* sensor, u64 seed, long long ray0, long long nrays, int max_events,
-                   u64* counts, u64* n_capped, u64* n_clamped, void* stream, const PhaseIn<F> ph = PhaseIn<F>{},
-                   const bool with_bg = false, const int nbg = 0, const F* dz_bg = nullptr, const F* bg_profile = nullptr,
-                   const AerIn<F>* aer = nullptr)
+void launch_trace_bw(const BwArgs<F>& a, const PhaseIn<F>& ph, hipStream_t st, const Form form, const BgArgs<F,true,true>& b)
 {
-    // aer: rrx_rt_bw_trace_counts_aer. With nbg > 0 bg_profile then has BG_ROWS_AER rows and the aerosol form runs whatever the grid's
-    // triple is; with nbg = 0 and a NULL triple it is the _bg entry.
-    RRX_TRY
-    check_nbg(nbg);
-    if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"npx", npx}, {"npy", npy}, {"nrays", nrays}})) return 0;
-    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
-    if (ray0 < 0) throw std::runtime_error("ray0 is negative");
-    check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"k_null", k_null}, {"sensor", sensor}, {"counts", counts},
-                  {"n_capped", n_capped}, {"n_clamped", n_clamped}});
-    check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
-    if (aer != nullptr) check_aerosol("aer_", nbnd, band_lims_gpt, aer->tau, aer->ssa, aer->g);
-    check_phase(ph, cld_tau);
-    if (igpt < 0 || igpt >= ngpt) throw std::runtime_error("igpt is outside [0, ngpt)");
-    check_scene(dx, dy, dz, mu0);
-    if (max_events < 1) throw std::runtime_error("max_events must be >= 1");
-    check_grid(nx, ny, nz, knx, kny, knz);
-    if ((long long)npx*npy > 0x7FFFFFFFll) throw std::runtime_error("npx npy exceeds 2^31 - 1");
-    int max_walk = 0;
-    check_sensor(sensor_type, fov, sensor, dx, dy, dz, nx, ny, nz, mu0, max_walk);
-    BwArgs<F> a = scene_args<F>(nx, ny, nz, nbnd, igpt, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo,
-                                knx, kny, knz, k_null, u64(ray0), nrays, max_events, max_walk, counts, n_capped, n_clamped);
-    if (with_bg)
+    const int blocks = int(std::min<long long>((a.nrays + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
+    const size_t lds = (ph.given() ? size_t(ph.nmu)*sizeof(F) : 0)
+                     + (form == FORM_GRID ? 0 : bg_lds_numbers(b.in.nbg, form == FORM_AER ? BG_ROWS_AER : BG_ROWS)*sizeof(F));
+    const BgArgs<F,true> bg{b.in};
+    switch (2*form + (ph.given() ? 1 : 0))
     {
-        BgArgs<F,true> bg{BgIn<F>{nbg, bg_profile, BgLevels<F>{}}};
-        if (nbg > 0)
-        {
-            check_needed({{"dz_bg", dz_bg}, {"bg_profile", bg_profile}});
-            bg.in.z = bg_levels<F>(nbg, dz_bg, nz, knz, dz);
-        }
-        if (aer != nullptr && (aer->tau != nullptr || nbg > 0))
-        {
-            launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, static_cast<hipStream_t>(stream), &bg, aer);
-            return 0;
-        }
-        launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, static_cast<hipStream_t>(stream), &bg);
-        return 0;
+        case 2*FORM_AER + 1: trace_bw_kernel<F,true,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, b); break;
+        case 2*FORM_AER: trace_bw_kernel<F,false,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, b); break;
+        case 2*FORM_BG + 1: trace_bw_kernel<F,true,true,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, bg); break;
+        case 2*FORM_BG: trace_bw_kernel<F,false,true,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, bg); break;
+        case 2*FORM_GRID + 1: trace_bw_kernel<F,true,false,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, BgArgs<F,false>{}); break;
+        default: trace_bw_kernel<F,false,false,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, BgArgs<F,false>{});
     }
-    launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, static_cast<hipStream_t>(stream));
+}
+
+// rrx_rt_bw_trace_counts, _phase (bg.form = FORM_GRID), _bg, _aer
+template<typename F>
+int trace_bw_entry(const char* entry, const Medium<F>& m, const Sun<F>& sun, const PhaseIn<F>& ph, const Background<F>& bg, const Run& run,
+                   const Sensor<F>& sensor, const int igpt, const F* k_null, const long long ray0, const long long nrays,
+                   u64* counts, u64* n_capped, u64* n_clamped)
+{
+    RRX_TRY
+    int max_walk = 0;
+    if (check_backward(m, sun, ph, bg, run.max_events, sensor, {"nrays", nrays}, {{"k_null", k_null}, {"sensor", sensor.s}},
+                       {{"counts", counts}, {"n_capped", n_capped}, {"n_clamped", n_clamped}}, max_walk,
+                       [&] { if (ray0 < 0) throw std::runtime_error("ray0 is negative"); }, [&] { check_igpt(igpt, m.ngpt); }, nothing))
+        return 0;
+    BgArgs<F,true,true> b{BgIn<F>{}, m.aer};
+    if (bg.form != FORM_GRID) b.in = background_of(bg, m, nothing);
+    launch_trace_bw<F>(scene_args<F>(m, sun, sensor, igpt, k_null, run.seed, u64(ray0), nrays, run.max_events, max_walk, counts, n_capped, n_clamped),
+                       ph, static_cast<hipStream_t>(run.stream), form_of(bg, m), b);
     RRX_CATCH(entry)
 }
 
-// the two small entries of the forward file that the spectral loop is made of, by precision
-inline int k_null_of(int nx, int ny, int nz, int ngpt, int nbnd, int g, RrxBool t, const double* tau, const int* lims, const double* ct,
-                     double dz, int knx, int kny, int knz, double* kn, void* st)
-{ return rrx_rt_k_null_f64(nx, ny, nz, ngpt, nbnd, g, t, tau, lims, ct, dz, knx, kny, knz, kn, st); }
-inline int k_null_of(int nx, int ny, int nz, int ngpt, int nbnd, int g, RrxBool t, const float* tau, const int* lims, const float* ct,
-                     float dz, int knx, int kny, int knz, float* kn, void* st)
-{ return rrx_rt_k_null_f32(nx, ny, nz, ngpt, nbnd, g, t, tau, lims, ct, dz, knx, kny, knz, kn, st); }
-inline int bg_profile_of(int nbg, int ngpt, int nbnd, int g, const double* dzb, const double* t, const double* w, const int* lims, const double* ct,
-                         const double* cw, const double* cg, double* prof, void* st)
-{ return rrx_rt_bg_profile_f64(nbg, ngpt, nbnd, g, dzb, t, w, lims, ct, cw, cg, prof, st); }
-inline int bg_profile_of(int nbg, int ngpt, int nbnd, int g, const float* dzb, const float* t, const float* w, const int* lims, const float* ct,
-                         const float* cw, const float* cg, float* prof, void* st)
-{ return rrx_rt_bg_profile_f32(nbg, ngpt, nbnd, g, dzb, t, w, lims, ct, cw, cg, prof, st); }
-inline int k_null_aer_of(int nx, int ny, int nz, int ngpt, int nbnd, int g, RrxBool t, const double* tau, const int* lims, const double* ct,
-                         double dz, int knx, int kny, int knz, double* kn, const double* at, void* st)
-{ return rrx_rt_k_null_aer_f64(nx, ny, nz, ngpt, nbnd, g, t, tau, lims, ct, dz, knx, kny, knz, kn, at, st); }
-inline int k_null_aer_of(int nx, int ny, int nz, int ngpt, int nbnd, int g, RrxBool t, const float* tau, const int* lims, const float* ct,
-                         float dz, int knx, int kny, int knz, float* kn, const float* at, void* st)
-{ return rrx_rt_k_null_aer_f32(nx, ny, nz, ngpt, nbnd, g, t, tau, lims, ct, dz, knx, kny, knz, kn, at, st); }
-inline int bg_profile_aer_of(int nbg, int ngpt, int nbnd, int g, const double* dzb, const double* t, const double* w, const int* lims,
-                             const double* ct, const double* cw, const double* cg, double* prof, const AerIn<double>& a, void* st)
-{ return rrx_rt_bg_profile_aer_f64(nbg, ngpt, nbnd, g, dzb, t, w, lims, ct, cw, cg, prof, a.tau, a.ssa, a.g, st); }
-inline int bg_profile_aer_of(int nbg, int ngpt, int nbnd, int g, const float* dzb, const float* t, const float* w, const int* lims,
-                             const float* ct, const float* cw, const float* cg, float* prof, const AerIn<float>& a, void* st)
-{ return rrx_rt_bg_profile_aer_f32(nbg, ngpt, nbnd, g, dzb, t, w, lims, ct, cw, cg, prof, a.tau, a.ssa, a.g, st); }
-inline int counts_to_flux_of(long long n, const u64* c, double scale, double* out, void* st) { return rrx_rt_counts_to_flux_f64(n, c, scale, out, st); }
-inline int counts_to_flux_of(long long n, const u64* c, float scale, float* out, void* st) { return rrx_rt_counts_to_flux_f32(n, c, scale, out, st); }
-
-template<typename F>
-int raytracer_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1,
-                       const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g,
-                       F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz,
-                       int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, u64 seed, int max_events,
-                       F* radiance, u64* n_capped, u64* n_clamped, void* stream, const PhaseIn<F> ph = PhaseIn<F>{},
-                       const bool with_bg = false, const int nbg = 0, const F* dz_bg = nullptr, const F* bg_tau = nullptr,
-                       const F* bg_ssa = nullptr, const F* bg_cld_tau = nullptr, const F* bg_cld_ssa = nullptr, const F* bg_cld_g = nullptr,
-                       const AerIn<F>* aer = nullptr, const AerIn<F>* bg_aer = nullptr)
+// The small entries of the forward file that the spectral loop is made of, by precision. They are called as a caller outside would:
+// their own checks run again and a refusal comes back with its text.
+template<typename F> struct ForwardEntries;
+template<> struct ForwardEntries<double>
 {
-    // aer, bg_aer: rrx_raytracer_bw_aer; with both triples NULL (bg_aer is not read when nbg = 0) it is the _bg entry
-    RRX_TRY
-    check_nbg(nbg);
-    if (check_extents({{"nx", nx}, {"ny", ny}, {"nz", nz}, {"ngpt", ngpt}, {"npx", npx}, {"npy", npy}, {"rays_per_pixel", rays_per_pixel}})) return 0;
-    if (nbnd < 0) throw std::runtime_error("nbnd is negative");
-    check_needed({{"tau", tau}, {"ssa", ssa}, {"sfc_albedo", sfc_albedo}, {"inc_dir", inc_dir}, {"sensor", sensor}, {"radiance", radiance},
-                  {"n_capped", n_capped}, {"n_clamped", n_clamped}});
-    check_cloud(nbnd, band_lims_gpt, cld_tau, cld_ssa, cld_g);
-    if (aer != nullptr) check_aerosol("aer_", nbnd, band_lims_gpt, aer->tau, aer->ssa, aer->g);
-    check_phase(ph, cld_tau);
-    check_scene(dx, dy, dz, mu0);
-    for (int g=0; g<ngpt; ++g)
-        if (inc_dir[g] < F(0.)) throw std::runtime_error("inc_dir must be >= 0");
-    if (max_events < 1) throw std::runtime_error("max_events must be >= 1");
-    check_grid(nx, ny, nz, knx, kny, knz);
-    if ((long long)npx*npy > 0x7FFFFFFFll) throw std::runtime_error("npx npy exceeds 2^31 - 1");
-    int max_walk = 0;
-    check_sensor(sensor_type, fov, sensor, dx, dy, dz, nx, ny, nz, mu0, max_walk);
-    const bool bg_on = with_bg && nbg > 0;
-    BgLevels<F> lev{};
-    if (bg_on && bg_aer != nullptr) check_aerosol("bg_aer_", nbnd, band_lims_gpt, bg_aer->tau, bg_aer->ssa, bg_aer->g);
-    // the aerosol form runs when either triple is given
-    const AerIn<F> aer_grid = aer != nullptr ? *aer : AerIn<F>{}, aer_bg = (bg_on && bg_aer != nullptr) ? *bg_aer : AerIn<F>{};
-    const bool aer_on = with_bg && (aer_grid.tau != nullptr || aer_bg.tau != nullptr);
-    if (bg_on)
-    {
-        check_bg_medium(nbg, nbnd, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g);
-        lev = bg_levels<F>(nbg, dz_bg, nz, knz, dz);
-    }
+    static constexpr auto k_null = rrx_rt_k_null_f64; static constexpr auto k_null_aer = rrx_rt_k_null_aer_f64;
+    static constexpr auto bg_profile = rrx_rt_bg_profile_f64; static constexpr auto bg_profile_aer = rrx_rt_bg_profile_aer_f64;
+    static constexpr auto counts_to_flux = rrx_rt_counts_to_flux_f64;
+};
+template<> struct ForwardEntries<float>
+{
+    static constexpr auto k_null = rrx_rt_k_null_f32; static constexpr auto k_null_aer = rrx_rt_k_null_aer_f32;
+    static constexpr auto bg_profile = rrx_rt_bg_profile_f32; static constexpr auto bg_profile_aer = rrx_rt_bg_profile_aer_f32;
+    static constexpr auto counts_to_flux = rrx_rt_counts_to_flux_f32;
+};
+inline void forward(const int status) { if (status != 0) throw std::runtime_error(rrx_last_error()); }
 
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t npix = size_t(npx)*npy;
-    const size_t n_kn = (size_t(knx)*kny*knz*sizeof(F) + sizeof(u64) - 1) / sizeof(u64);
-    const size_t n_prof = bg_on ? (size_t(aer_on ? BG_ROWS_AER : BG_ROWS)*(nbg + 1)*sizeof(F) + sizeof(u64) - 1) / sizeof(u64) : 0;
+// rrx_raytracer_bw, _phase (bg.form = FORM_GRID), _bg, _aer
+template<typename F>
+int raytracer_bw_entry(const char* entry, const Medium<F>& m, const Sun<F>& sun, const PhaseIn<F>& ph, const Background<F>& bg, const Run& run,
+                       const Sensor<F>& sensor, const F* inc_dir, const long long rays_per_pixel, F* radiance, u64* n_capped, u64* n_clamped)
+{
+    RRX_TRY
+    typedef ForwardEntries<F> Fw;
+    int max_walk = 0;
+    if (check_backward(m, sun, ph, bg, run.max_events, sensor, {"rays_per_pixel", rays_per_pixel}, {{"inc_dir", inc_dir}, {"sensor", sensor.s}},
+                       {{"radiance", radiance}, {"n_capped", n_capped}, {"n_clamped", n_clamped}}, max_walk, nothing, nothing,
+                       [&] { for (int g=0; g<m.ngpt; ++g)
+                                 if (inc_dir[g] < F(0.)) throw std::runtime_error("inc_dir must be >= 0"); }))
+        return 0;
+    const LoopBg<F> lb = loop_background(bg, m, nothing);
+
+    // the workspace, in u64 words: | counts (npix) | k_null | the background's profile |
+    hipStream_t st = static_cast<hipStream_t>(run.stream);
+    const size_t npix = size_t(sensor.npx)*sensor.npy;
+    const size_t n_kn = words_of(size_t(m.knx)*m.kny*m.knz*sizeof(F));
+    const size_t n_prof = lb.on ? words_of(size_t(lb.form == FORM_AER ? BG_ROWS_AER : BG_ROWS)*(lb.nbg + 1)*sizeof(F)) : 0;
     WorkspaceLease lease(st);
     u64* counts = lease.get<u64>(npix + n_kn + n_prof);
     F* k_null = reinterpret_cast<F*>(counts + npix);
@@ -705,120 +652,70 @@ int raytracer_bw_entry(const char* entry, int nx, int ny, int nz, int ngpt, int 
     ok = ok && hipMemsetAsync(radiance, 0, npix*sizeof(F), st) == hipSuccess;
     if (!ok) throw std::runtime_error("zeroing the outputs failed");
     const long long nrays = rays_per_pixel*(long long)npix;
-    for (int g=0; g<ngpt; ++g)
+    const BgArgs<F,true,true> b{BgIn<F>{lb.nbg, profile, lb.lev}, m.aer};
+    for (int g=0; g<m.ngpt; ++g)
     {
         if (!(inc_dir[g] > F(0.))) continue;
         if (hipMemsetAsync(counts, 0, npix*sizeof(u64), st) != hipSuccess) throw std::runtime_error("zeroing the counts failed");
-        if ((aer_grid.tau != nullptr
-                 ? k_null_aer_of(nx, ny, nz, ngpt, nbnd, g, top_at_1, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null, aer_grid.tau, stream)
-                 : k_null_of(nx, ny, nz, ngpt, nbnd, g, top_at_1, tau, band_lims_gpt, cld_tau, dz, knx, kny, knz, k_null, stream)) != 0)
-            throw std::runtime_error(rrx_last_error());
-        BwArgs<F> a = scene_args<F>(nx, ny, nz, nbnd, g, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_albedo,
-                                    knx, kny, knz, k_null, 0ull, nrays, max_events, max_walk, counts, n_capped, n_clamped);
-        if (with_bg)
-        {
-            BgArgs<F,true> bg{BgIn<F>{bg_on ? nbg : 0, profile, lev}};
-            if (bg_on && (aer_on
-                    ? bg_profile_aer_of(nbg, ngpt, nbnd, g, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, profile, aer_bg, stream)
-                    : bg_profile_of(nbg, ngpt, nbnd, g, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, profile, stream)) != 0)
-                throw std::runtime_error(rrx_last_error());
-            launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, st, &bg, aer_on ? &aer_grid : nullptr);
-        }
-        else launch_trace_bw<F>(a, ph, mu0, azimuth, sensor_type, npx, npy, fov, sensor, seed, st);
-        const F scale = inc_dir[g] / (mu0*F(rays_per_pixel));
-        if (counts_to_flux_of((long long)npix, counts, scale, radiance, stream) != 0) throw std::runtime_error(rrx_last_error());
+        if (m.aer.tau != nullptr)
+            forward(Fw::k_null_aer(m.nx, m.ny, m.nz, m.ngpt, m.nbnd, g, m.top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, m.dz, m.knx, m.kny, m.knz,
+                                   k_null, m.aer.tau, run.stream));
+        else
+            forward(Fw::k_null(m.nx, m.ny, m.nz, m.ngpt, m.nbnd, g, m.top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, m.dz, m.knx, m.kny, m.knz,
+                               k_null, run.stream));
+        if (lb.on && lb.form == FORM_AER)
+            forward(Fw::bg_profile_aer(bg.nbg, m.ngpt, m.nbnd, g, bg.dz_bg, bg.tau, bg.ssa, m.band_lims_gpt, bg.cld_tau, bg.cld_ssa, bg.cld_g, profile,
+                                       lb.aer.tau, lb.aer.ssa, lb.aer.g, run.stream));
+        else if (lb.on)
+            forward(Fw::bg_profile(bg.nbg, m.ngpt, m.nbnd, g, bg.dz_bg, bg.tau, bg.ssa, m.band_lims_gpt, bg.cld_tau, bg.cld_ssa, bg.cld_g, profile,
+                                   run.stream));
+        launch_trace_bw<F>(scene_args<F>(m, sun, sensor, g, k_null, run.seed, 0ull, nrays, run.max_events, max_walk, counts, n_capped, n_clamped),
+                           ph, st, lb.form, b);
+        const F scale = inc_dir[g] / (sun.mu0*F(rays_per_pixel));
+        forward(Fw::counts_to_flux((long long)npix, counts, scale, radiance, run.stream));
     }
     RRX_CATCH(entry)
 }
 }  // namespace
 
+// ---- the C entries: each builds the structs and calls its family's one function
+#define RT_P_BW_TRACE(F) \
+        int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, RT_P_GRID(F), int knx, int kny, int knz, const F* k_null, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
+        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped
+#define RT_P_BW_LOOP(F) \
+        int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RT_P_GRID(F), const F* inc_dir, int knx, int kny, int knz, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
+        F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped
+#define RT_SENSOR(F) Sensor<F>{sensor_type, npx, npy, fov, sensor}
+#define RT_BW_TRACE(F, NAME, AER, PHASE, BG) \
+        trace_bw_entry<F>(NAME, RT_MEDIUM(F, 0, AER), RT_SUN(F), PHASE, BG, RT_RUN, RT_SENSOR(F), igpt, k_null, ray0, nrays, counts, n_capped, n_clamped)
+#define RT_BW_LOOP(F, NAME, AER, PHASE, BG) \
+        raytracer_bw_entry<F>(NAME, RT_MEDIUM(F, 0, AER), RT_SUN(F), PHASE, BG, RT_RUN, RT_SENSOR(F), inc_dir, rays_per_pixel, radiance, n_capped, n_clamped)
+
 extern "C"
 {
 #define RRX_DEFINE_RT_BW(F, SFX) \
-int rrx_rt_bw_trace_counts##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null, \
-        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
-        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream) \
-{ return trace_bw_entry<F>("rrx_rt_bw_trace_counts" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, \
-                           cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, knx, kny, knz, k_null, sensor_type, npx, npy, fov, sensor, seed, ray0, \
-                           nrays, max_events, counts, n_capped, n_clamped, stream); } \
-int rrx_raytracer_bw##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz, \
-        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
-        F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream) \
-{ return raytracer_bw_entry<F>("rrx_raytracer_bw" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, \
-                               dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, \
-                               rays_per_pixel, seed, max_events, radiance, n_capped, n_clamped, stream); } \
-int rrx_rt_bw_trace_counts_phase##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null, \
-        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
-        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, \
-        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, void* stream) \
-{ return trace_bw_entry<F>("rrx_rt_bw_trace_counts_phase" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, \
-                           cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, knx, kny, knz, k_null, sensor_type, npx, npy, fov, sensor, seed, ray0, \
-                           nrays, max_events, counts, n_capped, n_clamped, stream, PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}); } \
-int rrx_raytracer_bw_phase##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz, \
-        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
-        F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
-        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, void* stream) \
-{ return raytracer_bw_entry<F>("rrx_raytracer_bw_phase" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, \
-                               dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, \
-                               rays_per_pixel, seed, max_events, radiance, n_capped, n_clamped, stream, \
-                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}); } \
-int rrx_rt_bw_trace_counts_bg##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null, \
-        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
-        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, \
-        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
-        int nbg, const F* dz_bg, const F* bg_profile, void* stream) \
-{ return trace_bw_entry<F>("rrx_rt_bw_trace_counts_bg" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, \
-                           cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, knx, kny, knz, k_null, sensor_type, npx, npy, fov, sensor, seed, ray0, \
-                           nrays, max_events, counts, n_capped, n_clamped, stream, PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, \
-                           true, nbg, dz_bg, bg_profile); } \
-int rrx_raytracer_bw_bg##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz, \
-        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
-        F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
-        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
-        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, void* stream) \
-{ return raytracer_bw_entry<F>("rrx_raytracer_bw_bg" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, \
-                               dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, \
-                               rays_per_pixel, seed, max_events, radiance, n_capped, n_clamped, stream, \
-                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, true, nbg, dz_bg, bg_tau, bg_ssa, bg_cld_tau, \
-                               bg_cld_ssa, bg_cld_g); } \
-int rrx_rt_bw_trace_counts_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, int knx, int kny, int knz, const F* k_null, \
-        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
-        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, \
-        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
-        int nbg, const F* dz_bg, const F* bg_profile, const F* aer_tau, const F* aer_ssa, const F* aer_g, void* stream) \
+int rrx_rt_bw_trace_counts##SFX(RT_P_BW_TRACE(F), void* stream) \
+{ return RT_BW_TRACE(F, "rrx_rt_bw_trace_counts" #SFX, AerIn<F>{}, PhaseIn<F>{}, RT_NO_BG(F)); } \
+int rrx_raytracer_bw##SFX(RT_P_BW_LOOP(F), void* stream) \
+{ return RT_BW_LOOP(F, "rrx_raytracer_bw" #SFX, AerIn<F>{}, PhaseIn<F>{}, RT_NO_BG(F)); } \
+int rrx_rt_bw_trace_counts_phase##SFX(RT_P_BW_TRACE(F), RT_P_PHASE(F), void* stream) \
+{ return RT_BW_TRACE(F, "rrx_rt_bw_trace_counts_phase" #SFX, AerIn<F>{}, RT_PHASE(F), RT_NO_BG(F)); } \
+int rrx_raytracer_bw_phase##SFX(RT_P_BW_LOOP(F), RT_P_PHASE(F), void* stream) \
+{ return RT_BW_LOOP(F, "rrx_raytracer_bw_phase" #SFX, AerIn<F>{}, RT_PHASE(F), RT_NO_BG(F)); } \
+int rrx_rt_bw_trace_counts_bg##SFX(RT_P_BW_TRACE(F), RT_P_PHASE(F), int nbg, const F* dz_bg, const F* bg_profile, void* stream) \
+{ return RT_BW_TRACE(F, "rrx_rt_bw_trace_counts_bg" #SFX, AerIn<F>{}, RT_PHASE(F), RT_BG_PROFILE(F, FORM_BG)); } \
+int rrx_raytracer_bw_bg##SFX(RT_P_BW_LOOP(F), RT_P_PHASE(F), RT_P_BG(F), void* stream) \
+{ return RT_BW_LOOP(F, "rrx_raytracer_bw_bg" #SFX, AerIn<F>{}, RT_PHASE(F), RT_BG_MEDIUM(F, FORM_BG, AerIn<F>{})); } \
+int rrx_rt_bw_trace_counts_aer##SFX(RT_P_BW_TRACE(F), RT_P_PHASE(F), int nbg, const F* dz_bg, const F* bg_profile, \
+        const F* aer_tau, const F* aer_ssa, const F* aer_g, void* stream) \
 { const AerIn<F> aer{aer_tau, aer_ssa, aer_g}; \
-  return trace_bw_entry<F>("rrx_rt_bw_trace_counts_aer" #SFX, nx, ny, nz, ngpt, nbnd, igpt, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, \
-                           cld_g, dx, dy, dz, sfc_albedo, mu0, azimuth, knx, kny, knz, k_null, sensor_type, npx, npy, fov, sensor, seed, ray0, \
-                           nrays, max_events, counts, n_capped, n_clamped, stream, PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, \
-                           true, nbg, dz_bg, bg_profile, &aer); } \
-int rrx_raytracer_bw_aer##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
-        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
-        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz, \
-        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
-        F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
-        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
-        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, \
+  return RT_BW_TRACE(F, "rrx_rt_bw_trace_counts_aer" #SFX, aer, RT_PHASE(F), RT_BG_PROFILE(F, FORM_AER)); } \
+int rrx_raytracer_bw_aer##SFX(RT_P_BW_LOOP(F), RT_P_PHASE(F), RT_P_BG(F), \
         const F* aer_tau, const F* aer_ssa, const F* aer_g, const F* bg_aer_tau, const F* bg_aer_ssa, const F* bg_aer_g, void* stream) \
 { const AerIn<F> aer{aer_tau, aer_ssa, aer_g}, bg_aer{bg_aer_tau, bg_aer_ssa, bg_aer_g}; \
-  return raytracer_bw_entry<F>("rrx_raytracer_bw_aer" #SFX, nx, ny, nz, ngpt, nbnd, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, \
-                               dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, \
-                               rays_per_pixel, seed, max_events, radiance, n_capped, n_clamped, stream, \
-                               PhaseIn<F>{nmu, nre, re0, dre, mu, phase, cdf, cld_re}, true, nbg, dz_bg, bg_tau, bg_ssa, bg_cld_tau, \
-                               bg_cld_ssa, bg_cld_g, &aer, &bg_aer); }
+  return RT_BW_LOOP(F, "rrx_raytracer_bw_aer" #SFX, aer, RT_PHASE(F), RT_BG_MEDIUM(F, FORM_AER, bg_aer)); }
 
 RRX_DEFINE_RT_BW(double, _f64)
 RRX_DEFINE_RT_BW(float, _f32)

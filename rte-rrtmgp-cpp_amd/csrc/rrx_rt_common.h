@@ -296,7 +296,7 @@ __device__ __forceinline__ void bg_rows_of_gpt(BgView<F>& bg, const F* __restric
     bg.tau_above = p + BG_TAU_ABOVE*n1;
 }
 
-// ---- host side: the argument checks of the entries (they throw; RRX_CATCH names the entry)
+// ---- host side: the argument checks of the entries (they throw; RRX_CATCH names the entry; rrx_rt_host.h runs them in their order)
 
 inline void check_grid(const int nx, const int ny, const int nz, const int knx, const int kny, const int knz)
 {

@@ -629,6 +629,43 @@ class HipKernels:
         out["n_capped"] = torch.zeros((1,), dtype=torch.int64, device=self.device)
         return out
 
+    # What the wrappers below share. Each of them gathers its arguments with these, calls its entry and unpacks.
+    def _rt_run(self, seed, max_events):
+        """(the seed as the unsigned 64-bit key, the cap on a photon's events)"""
+        return int(seed) & 0xFFFFFFFFFFFFFFFF, self.RT_MAX_EVENTS if max_events is None else max_events
+
+    def _rt_per_gpt(self, ngpt, **arrays):
+        """the (ngpt,) host arrays of a loop: the precision's numbers, photons_per_pixel_gpt int64"""
+        out = [np.ascontiguousarray(np.asarray(a, dtype=np.int64 if k == "photons_per_pixel_gpt" else self.np_dtype).reshape(-1))
+               for k, a in arrays.items()]
+        if any(a.size != ngpt for a in out):
+            raise ValueError(f"raytracer: {', '.join(arrays)} {'is' if len(out) == 1 else 'are'} (ngpt,)")
+        return out
+
+    def _rt_fluxes(self, dims, nbg=None):
+        """(the outputs of a forward loop, its n_capped): the grid's six, and the background's five when nbg is given"""
+        nz, ncol = dims[2], dims[0]*dims[1]
+        out = {k: self.empty((ncol,)) for k in self.RT_COUNTS[:4]}
+        out.update({k: self.empty((nz, ncol)) for k in self.RT_COUNTS[4:]})
+        if nbg is not None:
+            out.update({k: self.zeros((ncol,)) for k in self.RT_BG_COUNTS[:3]})
+            out.update({k: self.zeros((nbg,)) for k in self.RT_BG_COUNTS[3:]})
+        return out, torch.zeros((1,), dtype=torch.int64, device=self.device)
+
+    @staticmethod
+    def _rt_lims(band_lims, clouds, aerosols):
+        """the band_lims that an entry is passed: NULL unless one of its cloud triples (None: none) or aerosol triples (a triple of
+        None: none) is given"""
+        return band_lims if (any(c is not None for c in clouds) or any(a[0] is not None for a in aerosols)) else None
+
+    def _rt_entry(self, base, phase, dims, aer=None, spectral=False):
+        """(the entry, its phase-table arguments). aer None: base, or base_phase with a table. Otherwise base_spectral, base_aer or
+        base_bg, which always take the table's eight arguments (zeros and NULLs for none)."""
+        if aer is None:
+            return self._rt_phase(base, phase, dims)
+        table = self._rt_phase(base + "_bg", phase, dims)[1]
+        return base + ("_spectral" if spectral else "_aer" if aer else "_bg"), table if table else (0, 0, 0.0, 0.0, None, None, None, None)
+
     def rt_k_null(self, tau, igpt, nx, ny, dz, kn_grid, top_at_1, cloud=None, band_lims=None, aerosol=None):
         """k_null (knz, kny, knx), kn counted upward from the surface, for g-point igpt (0-based). aerosol=: None, or the grid's
         aerosol triple (rrx_rt_k_null_aer; a triple of None: its NULL pointer)."""
@@ -640,7 +677,7 @@ class HipKernels:
         else:
             if aerosol[0] is not None and band_lims is None:
                 raise ValueError("raytracer: an aerosol triple needs band_lims")
-            self._c("rt_k_null_aer", *dims, igpt, top_at_1, tau, band_lims if (cloud is not None or aerosol[0] is not None) else None, ct, dz,
+            self._c("rt_k_null_aer", *dims, igpt, top_at_1, tau, self._rt_lims(band_lims, (cloud,), (aerosol,)), ct, dz,
                     knx, kny, knz, out, aerosol[0])
         return out
 
@@ -649,12 +686,13 @@ class HipKernels:
                         max_events=None, phase=None):
         """Adds the photons [photon0, photon0 + nphotons) of g-point igpt into counts (rt_zero_counts; made when None)."""
         dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        knx, kny, knz = (int(k) for k in kn_grid)
+        kn = tuple(int(k) for k in kn_grid)
         counts = self.rt_zero_counts(dims[2], dims[0]*dims[1]) if counts is None else counts
-        entry, table = self._rt_phase("rt_trace_counts", phase, dims)
+        entry, table = self._rt_entry("rt_trace_counts", phase, dims)
+        seed, max_events = self._rt_run(seed, max_events)
         self._c(entry, *dims, igpt, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth,
-                inc_dir, inc_dif, knx, kny, knz, k_null, int(seed) & 0xFFFFFFFFFFFFFFFF, photon0, nphotons,
-                self.RT_MAX_EVENTS if max_events is None else max_events, *(counts[k] for k in self.RT_COUNTS), counts["n_capped"], *table)
+                inc_dir, inc_dif, *kn, k_null, seed, photon0, nphotons, max_events, *(counts[k] for k in self.RT_COUNTS),
+                counts["n_capped"], *table)
         return counts
 
     def rt_counts_to_flux(self, counts, scale, out):
@@ -667,19 +705,12 @@ class HipKernels:
         """The spectral loop in one call. inc_dir, inc_dif: (ngpt,) numbers on the host. Returns the four surface / top fluxes
         (ncol,) in W m-2, abs_dir / abs_dif (nz, ncol) in W m-3 and n_capped (int)."""
         dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        nz, ngpt, ncol = dims[2], dims[3], dims[0]*dims[1]
-        knx, kny, knz = (int(k) for k in kn_grid)
-        inc_dir = np.ascontiguousarray(np.asarray(inc_dir, dtype=self.np_dtype).reshape(-1))
-        inc_dif = np.ascontiguousarray(np.asarray(inc_dif, dtype=self.np_dtype).reshape(-1))
-        if inc_dir.size != ngpt or inc_dif.size != ngpt:
-            raise ValueError("raytracer: inc_dir, inc_dif are (ngpt,)")
-        out = {k: self.empty((ncol,)) for k in self.RT_COUNTS[:4]}
-        out.update({k: self.empty((nz, ncol)) for k in self.RT_COUNTS[4:]})
-        n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        entry, table = self._rt_phase("raytracer_sw", phase, dims)
+        kn = tuple(int(k) for k in kn_grid)
+        inc_dir, inc_dif = self._rt_per_gpt(dims[3], inc_dir=inc_dir, inc_dif=inc_dif)
+        out, n_capped = self._rt_fluxes(dims)
+        entry, table = self._rt_entry("raytracer_sw", phase, dims)
         self._c(entry, *dims, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir,
-                inc_dif, knx, kny, knz, photons_per_pixel, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                self.RT_MAX_EVENTS if max_events is None else max_events, *(out[k] for k in self.RT_COUNTS), n_capped, *table)
+                inc_dif, *kn, photons_per_pixel, *self._rt_run(seed, max_events), *(out[k] for k in self.RT_COUNTS), n_capped, *table)
         out["n_capped"] = int(n_capped.item())
         return out
 
@@ -692,18 +723,26 @@ class HipKernels:
     def rt_bw_zero_counts(self, npix):
         return {k: torch.zeros((n,), dtype=torch.int64, device=self.device) for k, n in (("counts", npix), ("n_capped", 1), ("n_clamped", 1))}
 
+    def _rt_bw_loop(self, entry, sensor, head, tail):
+        """a backward loop: entry(*head, the sensor, ..., the outputs, *tail), unpacked"""
+        radiance = self.empty((sensor[2], sensor[1]))
+        n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        n_clamped = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        self._c(entry, *head, radiance, n_capped, n_clamped, *tail)
+        return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
+
     def rt_bw_trace_counts(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, kn_grid, k_null, camera, seed, ray0, nrays,
                            top_at_1=False, cloud=None, band_lims=None, counts=None, max_events=None, phase=None):
         """Adds the rays [ray0, ray0 + nrays) of g-point igpt into counts (rt_bw_zero_counts; made when None): counts (npix,),
         n_capped, n_clamped, int64 tensors holding unsigned 64-bit numbers."""
         dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        knx, kny, knz = (int(k) for k in kn_grid)
+        kn = tuple(int(k) for k in kn_grid)
         sensor = self._rt_sensor(camera)
         counts = self.rt_bw_zero_counts(sensor[1]*sensor[2]) if counts is None else counts
-        entry, table = self._rt_phase("rt_bw_trace_counts", phase, dims)
-        self._c(entry, *dims, igpt, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, knx, kny, knz,
-                k_null, *sensor, int(seed) & 0xFFFFFFFFFFFFFFFF, ray0, nrays, self.RT_MAX_EVENTS if max_events is None else max_events,
-                counts["counts"], counts["n_capped"], counts["n_clamped"], *table)
+        entry, table = self._rt_entry("rt_bw_trace_counts", phase, dims)
+        seed, max_events = self._rt_run(seed, max_events)
+        self._c(entry, *dims, igpt, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, *kn,
+                k_null, *sensor, seed, ray0, nrays, max_events, counts["counts"], counts["n_capped"], counts["n_clamped"], *table)
         return counts
 
     def raytracer_bw(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
@@ -711,28 +750,17 @@ class HipKernels:
         """The spectral loop in one call. inc_dir: (ngpt,) numbers on the host. Returns radiance (npy, npx) in W m-2 sr-1, n_capped and
         n_clamped (ints)."""
         dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        knx, kny, knz = (int(k) for k in kn_grid)
-        inc_dir = np.ascontiguousarray(np.asarray(inc_dir, dtype=self.np_dtype).reshape(-1))
-        if inc_dir.size != dims[3]:
-            raise ValueError("raytracer: inc_dir is (ngpt,)")
+        kn = tuple(int(k) for k in kn_grid)
+        inc_dir, = self._rt_per_gpt(dims[3], inc_dir=inc_dir)
         sensor = self._rt_sensor(camera)
-        radiance = self.empty((sensor[2], sensor[1]))
-        n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        n_clamped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        entry, table = self._rt_phase("raytracer_bw", phase, dims)
-        self._c(entry, *dims, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, knx, kny, knz,
-                *sensor, rays_per_pixel, int(seed) & 0xFFFFFFFFFFFFFFFF, self.RT_MAX_EVENTS if max_events is None else max_events,
-                radiance, n_capped, n_clamped, *table)
-        return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
+        entry, table = self._rt_entry("raytracer_bw", phase, dims)
+        return self._rt_bw_loop(entry, sensor, (*dims, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir,
+                                                *kn, *sensor, rays_per_pixel, *self._rt_run(seed, max_events)), table)
 
     # A background atmosphere between the domain top and TOA (the rrx_*_bg entries; DESIGN 4.17). background=: None (nbg = 0, the
     # medium of the entries above) or an object with dz (nbg,) numbers on the host, tau, ssa (ngpt, nbg) and cloud, None or
     # (tau, ssa, g) of (nbnd, nbg) each; everything is counted upward from the domain top.
     RT_BG_COUNTS = ("toa_up", "tod_dn_dir", "tod_dn_dif", "bg_abs_dir", "bg_abs_dif")
-
-    def _rt_table_args(self, who, phase, dims):
-        table = self._rt_phase(who, phase, dims)[1]
-        return table if table else (0, 0, 0.0, 0.0, None, None, None, None)
 
     def _rt_bg_dz(self, background):
         dz = np.ascontiguousarray(np.asarray(background.dz, dtype=self.np_dtype).reshape(-1))
@@ -753,23 +781,17 @@ class HipKernels:
         """The profile (5, nbg+1) of g-point igpt: k_ext, k_sca, k_sca_cld, g, tau_above. aerosol=: the background's aerosol triple
         (a triple of None: no aerosol aloft) gives the profile (7, nbg+1) of rrx_rt_bg_profile_aer, which the _aer trace entries
         take: k_sca_aer and g_aer behind the five rows."""
-        dz = self._rt_bg_dz(background)
+        medium = self._rt_bg_medium(background)
         ngpt = background.tau.shape[0]
         if background.cloud is not None and band_lims is None:
             raise ValueError("raytracer: a background cloud triple needs band_lims")
         nbnd = int(band_lims.shape[0]) if band_lims is not None else 0
-        cloud = (None, None, None) if background.cloud is None else tuple(background.cloud)
-        if aerosol is None:
-            out = self.empty((5, dz.size + 1))
-            self._c("rt_bg_profile", dz.size, ngpt, nbnd, igpt, dz, background.tau, background.ssa,
-                    band_lims if background.cloud is not None else None, *cloud, out)
-            return out
-        bg_aer = tuple(aerosol)
-        if bg_aer[0] is not None and band_lims is None:
+        bg_aer = () if aerosol is None else tuple(aerosol)
+        if bg_aer and bg_aer[0] is not None and band_lims is None:
             raise ValueError("raytracer: a background aerosol triple needs band_lims")
-        out = self.empty((7, dz.size + 1))
-        self._c("rt_bg_profile_aer", dz.size, ngpt, nbnd, igpt, dz, background.tau, background.ssa,
-                band_lims if (background.cloud is not None or bg_aer[0] is not None) else None, *cloud, out, *bg_aer)
+        out = self.empty((7 if bg_aer else 5, medium[0] + 1))
+        self._c("rt_bg_profile_aer" if bg_aer else "rt_bg_profile", medium[0], ngpt, nbnd, igpt, *medium[1:4],
+                self._rt_lims(band_lims, (background.cloud,), (bg_aer,) if bg_aer else ()), *medium[4:], out, *bg_aer)
         return out
 
     # Aerosol as a third scattering species (the rrx_*_aer entries; DESIGN 4.18). aerosol=: None or the grid's band triple
@@ -796,6 +818,27 @@ class HipKernels:
             raise ValueError("raytracer: an aerosol triple needs band_lims")
         return given, grid, bg
 
+    def _rt_trace_background(self, igpt, cloud, band_lims, background, bg_profile, aerosol):
+        """The background and aerosol of a single-launch entry: (use the _aer entry, band_lims as passed, nbg, the tail nbg, dz_bg,
+        bg_profile, the grid's aerosol triple). bg_profile is made when None: rt_bg_profile's for igpt, rt_bg_profile_all's for
+        igpt None."""
+        nbg, dzb = (0, None) if background is None else (len(background.dz), self._rt_bg_dz(background))
+        aer, aer_grid, aer_bg = self._rt_aerosol(aerosol, background, band_lims)
+        if background is not None and bg_profile is None:
+            bg_profile = (self.rt_bg_profile_all(background, band_lims) if igpt is None
+                          else self.rt_bg_profile(background, igpt, band_lims, aerosol=aer_bg if aer else None))
+        return aer, self._rt_lims(band_lims, (cloud,), (aer_grid,)), nbg, (nbg, dzb, bg_profile), aer_grid
+
+    def _rt_loop_background(self, cloud, band_lims, background, aerosol):
+        """The background and aerosol of a loop: (use the _aer entry, band_lims as passed, the medium nbg, dz_bg, bg_tau, ..., the
+        grid's aerosol triple, the background's)"""
+        medium = self._rt_bg_medium(background)
+        if background is not None and background.cloud is not None and band_lims is None:
+            raise ValueError("raytracer: a background cloud triple needs band_lims")
+        aer, aer_grid, aer_bg = self._rt_aerosol(aerosol, background, band_lims)
+        lims = self._rt_lims(band_lims, (cloud, None if background is None else background.cloud), (aer_grid, aer_bg))
+        return aer, lims, medium, aer_grid, aer_bg
+
     def rt_zero_counts_bg(self, nz, ncol, nbg):
         out = self.rt_zero_counts(nz, ncol)
         out.update({k: torch.zeros((ncol,), dtype=torch.int64, device=self.device) for k in self.RT_BG_COUNTS[:3]})
@@ -808,26 +851,35 @@ class HipKernels:
         """rt_trace_counts with a background: bg_profile is rt_bg_profile's for igpt (made when None). The counts gain RT_BG_COUNTS.
         With aerosol= or background.aerosol it is rrx_rt_trace_counts_aer: k_null is then rt_k_null's with
         aerosol= and bg_profile the 7-row profile."""
-        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        knx, kny, knz = (int(k) for k in kn_grid)
-        nbg, dzb = (0, None) if background is None else (len(background.dz), self._rt_bg_dz(background))
-        aer, aer_grid, aer_bg = self._rt_aerosol(aerosol, background, band_lims)
-        if background is not None and bg_profile is None:
-            bg_profile = self.rt_bg_profile(background, igpt, band_lims, aerosol=aer_bg if aer else None)
+        dims, (_, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        kn = tuple(int(k) for k in kn_grid)
+        aer, lims, nbg, bg_tail, aer_grid = self._rt_trace_background(igpt, cloud, band_lims, background, bg_profile, aerosol)
         counts = self.rt_zero_counts_bg(dims[2], dims[0]*dims[1], nbg) if counts is None else counts
-        if aer:
-            self._c("rt_trace_counts_aer", *dims, igpt, top_at_1, independent_column, tau, ssa,
-                    band_lims if (cloud is not None or aer_grid[0] is not None) else None, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0,
-                    azimuth, inc_dir, inc_dif, knx, kny, knz, k_null, int(seed) & 0xFFFFFFFFFFFFFFFF, photon0, nphotons,
-                    self.RT_MAX_EVENTS if max_events is None else max_events, *(counts[k] for k in self.RT_COUNTS), counts["n_capped"],
-                    *(counts[k] for k in self.RT_BG_COUNTS), *self._rt_table_args("rt_trace_counts_bg", phase, dims), nbg, dzb, bg_profile,
-                    *aer_grid)
-            return counts
-        self._c("rt_trace_counts_bg", *dims, igpt, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0,
-                azimuth, inc_dir, inc_dif, knx, kny, knz, k_null, int(seed) & 0xFFFFFFFFFFFFFFFF, photon0, nphotons,
-                self.RT_MAX_EVENTS if max_events is None else max_events, *(counts[k] for k in self.RT_COUNTS), counts["n_capped"],
-                *(counts[k] for k in self.RT_BG_COUNTS), *self._rt_table_args("rt_trace_counts_bg", phase, dims), nbg, dzb, bg_profile)
+        entry, table = self._rt_entry("rt_trace_counts", phase, dims, aer)
+        seed, max_events = self._rt_run(seed, max_events)
+        self._c(entry, *dims, igpt, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0,
+                azimuth, inc_dir, inc_dif, *kn, k_null, seed, photon0, nphotons, max_events, *(counts[k] for k in self.RT_COUNTS),
+                counts["n_capped"], *(counts[k] for k in self.RT_BG_COUNTS), *table, *bg_tail, *(aer_grid if aer else ()))
         return counts
+
+    def _rt_sw_loop_bg(self, spectral, photons, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, seed,
+                       top_at_1, independent_column, cloud, band_lims, max_events, phase, background, aerosol):
+        """raytracer_sw_bg (photons: photons_per_pixel) and raytracer_sw_spectral (photons: photons_per_pixel_gpt)"""
+        dims, (_, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        kn = tuple(int(k) for k in kn_grid)
+        if spectral:
+            inc_dir, inc_dif, photons = self._rt_per_gpt(dims[3], inc_dir=inc_dir, inc_dif=inc_dif, photons_per_pixel_gpt=photons)
+        else:
+            inc_dir, inc_dif = self._rt_per_gpt(dims[3], inc_dir=inc_dir, inc_dif=inc_dif)
+        aer, lims, medium, aer_grid, aer_bg = self._rt_loop_background(cloud, band_lims, background, aerosol)
+        out, n_capped = self._rt_fluxes(dims, medium[0])
+        entry, table = self._rt_entry("raytracer_sw", phase, dims, aer, spectral)
+        self._c(entry, *dims, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir,
+                inc_dif, *kn, photons, *self._rt_run(seed, max_events), *(out[k] for k in self.RT_COUNTS), n_capped,
+                *(out[k] if medium[0] else None for k in self.RT_BG_COUNTS), *table, *medium,
+                *((self._rt_triple(aer_grid), self._rt_triple(aer_bg)) if (aer or spectral) else ()))
+        out["n_capped"] = int(n_capped.item())
+        return out
 
     def raytracer_sw_bg(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, photons_per_pixel, seed,
                         top_at_1=False, independent_column=False, cloud=None, band_lims=None, max_events=None, phase=None,
@@ -835,31 +887,8 @@ class HipKernels:
         """raytracer_sw with a background. Beside its outputs: toa_up, tod_dn_dir, tod_dn_dif (ncol,) in W m-2 and bg_abs_dir,
         bg_abs_dif (nbg,) in W m-3 of a domain-wide layer (zeros without a background). With aerosol= or
         background.aerosol it is rrx_raytracer_sw_aer."""
-        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        nz, ngpt, ncol = dims[2], dims[3], dims[0]*dims[1]
-        knx, kny, knz = (int(k) for k in kn_grid)
-        inc_dir = np.ascontiguousarray(np.asarray(inc_dir, dtype=self.np_dtype).reshape(-1))
-        inc_dif = np.ascontiguousarray(np.asarray(inc_dif, dtype=self.np_dtype).reshape(-1))
-        if inc_dir.size != ngpt or inc_dif.size != ngpt:
-            raise ValueError("raytracer: inc_dir, inc_dif are (ngpt,)")
-        medium = self._rt_bg_medium(background)
-        if background is not None and background.cloud is not None and band_lims is None:
-            raise ValueError("raytracer: a background cloud triple needs band_lims")
-        aer, aer_grid, aer_bg = self._rt_aerosol(aerosol, background, band_lims)
-        lims_all = band_lims if (cloud is not None or (background is not None and background.cloud is not None)
-                                 or aer_grid[0] is not None or aer_bg[0] is not None) else None
-        out = {k: self.empty((ncol,)) for k in self.RT_COUNTS[:4]}
-        out.update({k: self.empty((nz, ncol)) for k in self.RT_COUNTS[4:]})
-        out.update({k: self.zeros((ncol,)) for k in self.RT_BG_COUNTS[:3]})
-        out.update({k: self.zeros((medium[0],)) for k in self.RT_BG_COUNTS[3:]})
-        n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        self._c("raytracer_sw_aer" if aer else "raytracer_sw_bg", *dims, top_at_1, independent_column, tau, ssa, lims_all, ct, cw, cg, dx, dy,
-                dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, photons_per_pixel, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                self.RT_MAX_EVENTS if max_events is None else max_events, *(out[k] for k in self.RT_COUNTS), n_capped,
-                *(out[k] if medium[0] else None for k in self.RT_BG_COUNTS), *self._rt_table_args("raytracer_sw_bg", phase, dims), *medium,
-                *((self._rt_triple(aer_grid), self._rt_triple(aer_bg)) if aer else ()))
-        out["n_capped"] = int(n_capped.item())
-        return out
+        return self._rt_sw_loop_bg(False, photons_per_pixel, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid,
+                                   seed, top_at_1, independent_column, cloud, band_lims, max_events, phase, background, aerosol)
 
     # All g-points in one launch of the forward tracer, photons dealt per g-point (rrx_rt_k_null_all, rrx_rt_bg_profile_all,
     # rrx_rt_trace_counts_spectral, rrx_raytracer_sw_spectral; DESIGN 4.19). Built on the aerosol form: aerosol= and
@@ -872,22 +901,20 @@ class HipKernels:
         if at is not None and band_lims is None:
             raise ValueError("raytracer: an aerosol triple needs band_lims")
         out = self.empty((dims[3], knz, kny, knx))
-        self._c("rt_k_null_all", *dims, top_at_1, tau, band_lims if (cloud is not None or at is not None) else None, ct, dz, knx, kny, knz,
-                out, at)
+        self._c("rt_k_null_all", *dims, top_at_1, tau, self._rt_lims(band_lims, (cloud,), ((at,),)), ct, dz, knx, kny, knz, out, at)
         return out
 
     def rt_bg_profile_all(self, background, band_lims=None):
         """The profile (ngpt, 7, nbg+1): slice g is rt_bg_profile(background, g, band_lims, aerosol=the background's triple)"""
-        dz = self._rt_bg_dz(background)
+        medium = self._rt_bg_medium(background)
         ngpt = background.tau.shape[0]
-        cloud = (None, None, None) if background.cloud is None else tuple(background.cloud)
         bg_aer = self._rt_bg_aerosol(background)
-        if (background.cloud is not None or bg_aer[0] is not None) and band_lims is None:
+        lims = self._rt_lims(band_lims, (background.cloud,), (bg_aer,))
+        if lims is None and (background.cloud is not None or bg_aer[0] is not None):
             raise ValueError("raytracer: a background cloud or aerosol triple needs band_lims")
         nbnd = int(band_lims.shape[0]) if band_lims is not None else 0
-        out = self.empty((ngpt, 7, dz.size + 1))
-        self._c("rt_bg_profile_all", dz.size, ngpt, nbnd, dz, background.tau, background.ssa,
-                band_lims if (background.cloud is not None or bg_aer[0] is not None) else None, *cloud, out, *bg_aer)
+        out = self.empty((ngpt, 7, medium[0] + 1))
+        self._c("rt_bg_profile_all", medium[0], ngpt, nbnd, *medium[1:4], lims, *medium[4:], out, *bg_aer)
         return out
 
     def rt_trace_counts_spectral(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, photon_end, weight0, dif_frac, kn_grid, k_null,
@@ -896,9 +923,9 @@ class HipKernels:
         """Adds the photons [photon0, photon0 + nphotons) of the concatenated list into counts (rt_zero_counts_bg; made when None).
         photon_end (ngpt+1,) int64, weight0, dif_frac (ngpt,): arrays on the host, checked and uploaded here; k_null is
         rt_k_null_all's and bg_profile rt_bg_profile_all's (made when None)."""
-        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        dims, (_, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
         ngpt = dims[3]
-        knx, kny, knz = (int(k) for k in kn_grid)
+        kn = tuple(int(k) for k in kn_grid)
         photon_end = np.ascontiguousarray(np.asarray(photon_end, dtype=np.int64).reshape(-1))
         weight0 = np.ascontiguousarray(np.asarray(weight0, dtype=self.np_dtype).reshape(-1))
         dif_frac = np.ascontiguousarray(np.asarray(dif_frac, dtype=self.np_dtype).reshape(-1))
@@ -908,17 +935,14 @@ class HipKernels:
             raise ValueError("raytracer: photon_end must start at 0 and must not descend")
         if photon0 + nphotons > int(photon_end[-1]):
             raise ValueError(f"raytracer: the range [{photon0}, {photon0 + nphotons}) ends beyond the list of {int(photon_end[-1])} photons")
-        nbg, dzb = (0, None) if background is None else (len(background.dz), self._rt_bg_dz(background))
-        _, aer_grid, _ = self._rt_aerosol(aerosol, background, band_lims)
-        if background is not None and bg_profile is None:
-            bg_profile = self.rt_bg_profile_all(background, band_lims)
+        _, lims, nbg, bg_tail, aer_grid = self._rt_trace_background(None, cloud, band_lims, background, bg_profile, aerosol)
         counts = self.rt_zero_counts_bg(dims[2], dims[0]*dims[1], nbg) if counts is None else counts
         dev = [torch.as_tensor(a, device=self.device) for a in (photon_end, weight0, dif_frac)]
-        self._c("rt_trace_counts_spectral", *dims, top_at_1, independent_column, tau, ssa,
-                band_lims if (cloud is not None or aer_grid[0] is not None) else None, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, *dev,
-                knx, kny, knz, k_null, int(seed) & 0xFFFFFFFFFFFFFFFF, photon0, nphotons,
-                self.RT_MAX_EVENTS if max_events is None else max_events, *(counts[k] for k in self.RT_COUNTS), counts["n_capped"],
-                *(counts[k] for k in self.RT_BG_COUNTS), *self._rt_table_args("rt_trace_counts_bg", phase, dims), nbg, dzb, bg_profile, *aer_grid)
+        entry, table = self._rt_entry("rt_trace_counts", phase, dims, True, spectral=True)
+        seed, max_events = self._rt_run(seed, max_events)
+        self._c(entry, *dims, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, *dev,
+                *kn, k_null, seed, photon0, nphotons, max_events, *(counts[k] for k in self.RT_COUNTS), counts["n_capped"],
+                *(counts[k] for k in self.RT_BG_COUNTS), *table, *bg_tail, *aer_grid)
         return counts
 
     def raytracer_sw_spectral(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, photons_per_pixel_gpt,
@@ -926,32 +950,8 @@ class HipKernels:
                               background=None, aerosol=None):
         """raytracer_sw_bg with photons_per_pixel_gpt (ngpt,) photons per pixel of each g-point (pipeline.spectral_allocation deals
         them by flux) in place of photons_per_pixel, all g-points in one trace launch per chunk. The same outputs."""
-        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        nz, ngpt, ncol = dims[2], dims[3], dims[0]*dims[1]
-        knx, kny, knz = (int(k) for k in kn_grid)
-        inc_dir = np.ascontiguousarray(np.asarray(inc_dir, dtype=self.np_dtype).reshape(-1))
-        inc_dif = np.ascontiguousarray(np.asarray(inc_dif, dtype=self.np_dtype).reshape(-1))
-        m = np.ascontiguousarray(np.asarray(photons_per_pixel_gpt, dtype=np.int64).reshape(-1))
-        if inc_dir.size != ngpt or inc_dif.size != ngpt or m.size != ngpt:
-            raise ValueError("raytracer: inc_dir, inc_dif, photons_per_pixel_gpt are (ngpt,)")
-        medium = self._rt_bg_medium(background)
-        if background is not None and background.cloud is not None and band_lims is None:
-            raise ValueError("raytracer: a background cloud triple needs band_lims")
-        _, aer_grid, aer_bg = self._rt_aerosol(aerosol, background, band_lims)
-        lims_all = band_lims if (cloud is not None or (background is not None and background.cloud is not None)
-                                 or aer_grid[0] is not None or aer_bg[0] is not None) else None
-        out = {k: self.empty((ncol,)) for k in self.RT_COUNTS[:4]}
-        out.update({k: self.empty((nz, ncol)) for k in self.RT_COUNTS[4:]})
-        out.update({k: self.zeros((ncol,)) for k in self.RT_BG_COUNTS[:3]})
-        out.update({k: self.zeros((medium[0],)) for k in self.RT_BG_COUNTS[3:]})
-        n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        self._c("raytracer_sw_spectral", *dims, top_at_1, independent_column, tau, ssa, lims_all, ct, cw, cg, dx, dy,
-                dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, knx, kny, knz, m, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                self.RT_MAX_EVENTS if max_events is None else max_events, *(out[k] for k in self.RT_COUNTS), n_capped,
-                *(out[k] if medium[0] else None for k in self.RT_BG_COUNTS), *self._rt_table_args("raytracer_sw_bg", phase, dims), *medium,
-                self._rt_triple(aer_grid), self._rt_triple(aer_bg))
-        out["n_capped"] = int(n_capped.item())
-        return out
+        return self._rt_sw_loop_bg(True, photons_per_pixel_gpt, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid,
+                                   seed, top_at_1, independent_column, cloud, band_lims, max_events, phase, background, aerosol)
 
     def rt_bw_trace_counts_bg(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, kn_grid, k_null, camera, seed, ray0, nrays,
                               top_at_1=False, cloud=None, band_lims=None, counts=None, max_events=None, phase=None, background=None,
@@ -959,48 +959,31 @@ class HipKernels:
         """rt_bw_trace_counts with a background: bg_profile is rt_bg_profile's for igpt (made when None). With aerosol= or
         background.aerosol it is rrx_rt_bw_trace_counts_aer: k_null is then rt_k_null's with aerosol= and
         bg_profile the 7-row profile."""
-        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        knx, kny, knz = (int(k) for k in kn_grid)
+        dims, (_, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        kn = tuple(int(k) for k in kn_grid)
         sensor = self._rt_sensor(camera)
-        nbg, dzb = (0, None) if background is None else (len(background.dz), self._rt_bg_dz(background))
-        aer, aer_grid, aer_bg = self._rt_aerosol(aerosol, background, band_lims)
-        if background is not None and bg_profile is None:
-            bg_profile = self.rt_bg_profile(background, igpt, band_lims, aerosol=aer_bg if aer else None)
+        aer, lims, _, bg_tail, aer_grid = self._rt_trace_background(igpt, cloud, band_lims, background, bg_profile, aerosol)
         counts = self.rt_bw_zero_counts(sensor[1]*sensor[2]) if counts is None else counts
-        if aer and aer_grid[0] is not None:
-            lims = band_lims
-        self._c("rt_bw_trace_counts_aer" if aer else "rt_bw_trace_counts_bg", *dims, igpt, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz,
-                sfc_albedo, mu0, azimuth, knx, kny, knz,
-                k_null, *sensor, int(seed) & 0xFFFFFFFFFFFFFFFF, ray0, nrays, self.RT_MAX_EVENTS if max_events is None else max_events,
-                counts["counts"], counts["n_capped"], counts["n_clamped"], *self._rt_table_args("rt_bw_trace_counts_bg", phase, dims),
-                nbg, dzb, bg_profile, *(aer_grid if aer else ()))
+        entry, table = self._rt_entry("rt_bw_trace_counts", phase, dims, aer)
+        seed, max_events = self._rt_run(seed, max_events)
+        self._c(entry, *dims, igpt, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, *kn,
+                k_null, *sensor, seed, ray0, nrays, max_events, counts["counts"], counts["n_capped"], counts["n_clamped"], *table,
+                *bg_tail, *(aer_grid if aer else ()))
         return counts
 
     def raytracer_bw_bg(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
                         top_at_1=False, cloud=None, band_lims=None, max_events=None, phase=None, background=None, aerosol=None):
         """raytracer_bw with a background: radiance (npy, npx) in W m-2 sr-1, n_capped and n_clamped (ints). With aerosol= or
         background.aerosol it is rrx_raytracer_bw_aer."""
-        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        knx, kny, knz = (int(k) for k in kn_grid)
-        inc_dir = np.ascontiguousarray(np.asarray(inc_dir, dtype=self.np_dtype).reshape(-1))
-        if inc_dir.size != dims[3]:
-            raise ValueError("raytracer: inc_dir is (ngpt,)")
-        medium = self._rt_bg_medium(background)
-        if background is not None and background.cloud is not None and band_lims is None:
-            raise ValueError("raytracer: a background cloud triple needs band_lims")
-        aer, aer_grid, aer_bg = self._rt_aerosol(aerosol, background, band_lims)
-        lims_all = band_lims if (cloud is not None or (background is not None and background.cloud is not None)
-                                 or aer_grid[0] is not None or aer_bg[0] is not None) else None
+        dims, (_, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        kn = tuple(int(k) for k in kn_grid)
+        inc_dir, = self._rt_per_gpt(dims[3], inc_dir=inc_dir)
+        aer, lims, medium, aer_grid, aer_bg = self._rt_loop_background(cloud, band_lims, background, aerosol)
         sensor = self._rt_sensor(camera)
-        radiance = self.empty((sensor[2], sensor[1]))
-        n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        n_clamped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        self._c("raytracer_bw_aer" if aer else "raytracer_bw_bg", *dims, top_at_1, tau, ssa, lims_all, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0,
-                azimuth, inc_dir, knx, kny, knz,
-                *sensor, rays_per_pixel, int(seed) & 0xFFFFFFFFFFFFFFFF, self.RT_MAX_EVENTS if max_events is None else max_events,
-                radiance, n_capped, n_clamped, *self._rt_table_args("raytracer_bw_bg", phase, dims), *medium,
-                *((*aer_grid, *aer_bg) if aer else ()))
-        return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
+        entry, table = self._rt_entry("raytracer_bw", phase, dims, aer)
+        return self._rt_bw_loop(entry, sensor, (*dims, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir,
+                                                *kn, *sensor, rays_per_pixel, *self._rt_run(seed, max_events)),
+                                (*table, *medium, *((*aer_grid, *aer_bg) if aer else ())))
 
     def delta_scale_2str_k(self, tau, ssa, g):
         ngpt, nlay, ncol = tau.shape

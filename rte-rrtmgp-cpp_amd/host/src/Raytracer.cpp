@@ -1,10 +1,63 @@
 // Raytracer_gpu: checks the shapes and forwards to rrx_raytracer_sw; a non-zero status becomes std::runtime_error.
 #include "Raytracer.h"
+#include "Raytracer_members.h"
 #include <algorithm>
 #include <cmath>
 #include <numeric>
 #include <string>
 #include <vector>
+
+namespace
+{
+typedef std::initializer_list<const Array_gpu<Float,1>*> Arrays1;
+
+// THE SHAPE CHECK of the three trace_rays* methods, who: the prefix of its messages. per_gpt: the sizes of the (ngpt) host arrays, named
+// in per_gpt_names; flux: the (nx ny) outputs; with_bg: bg_flux (nx ny) and bg_abs (nbg) and the background's members are checked;
+// refuse_bg: the form without the background's outputs, which a background that is set makes an error.
+void check_shapes(const std::string& who, const Rt_members& m, const int nx, const int ny, const int nz,
+                  const Array_gpu<Float,3>& tau, const Array_gpu<Float,3>& ssa, const Array_gpu<int,2>& band_lims_gpt,
+                  const Array_gpu<Float,3>& cld_tau, const Array_gpu<Float,3>& cld_ssa, const Array_gpu<Float,3>& cld_g,
+                  const Array_gpu<Float,1>& sfc_albedo, std::initializer_list<int> per_gpt, const std::string& per_gpt_names,
+                  Arrays1 flux, const Array_gpu<Float,2>& abs_dir, const Array_gpu<Float,2>& abs_dif,
+                  const bool with_bg, Arrays1 bg_flux, Arrays1 bg_abs, const bool refuse_bg)
+{
+    if (nx < 0 || ny < 0 || nz < 0) throw std::runtime_error(who + "negative extent");
+    const long long ncol = (long long)nx*ny;
+    const int ngpt = tau.dim(3), nbnd = band_lims_gpt.dim(2);
+    if (tau.dim(1) != ncol || tau.dim(2) != nz || ssa.get_dims() != tau.get_dims()) throw std::runtime_error(who + "tau, ssa are not (nx ny, nz, ngpt)");
+    const bool cloudy = cld_tau.size() > 0;
+    if (cloudy && (cld_tau.dim(1) != ncol || cld_tau.dim(2) != nz || cld_tau.dim(3) != nbnd || cld_ssa.get_dims() != cld_tau.get_dims() ||
+                   cld_g.get_dims() != cld_tau.get_dims()))
+        throw std::runtime_error(who + "the cloud arrays are not (nx ny, nz, nbnd)");
+    if (!cloudy && (cld_ssa.size() > 0 || cld_g.size() > 0)) throw std::runtime_error(who + "the cloud arrays are all empty or all given");
+    if (sfc_albedo.size() != ncol || std::any_of(per_gpt.begin(), per_gpt.end(), [&](const int n) { return n != ngpt; }))
+        throw std::runtime_error(who + "sfc_albedo is not (nx ny) or " + per_gpt_names + " are not (ngpt)");
+    for (const Array_gpu<Float,1>* a : flux)
+        if (a->size() != ncol) throw std::runtime_error(who + "a flux array is not (nx ny)");
+    for (const Array_gpu<Float,2>* a : {&abs_dir, &abs_dif})
+        if (a->dim(1) != ncol || a->dim(2) != nz) throw std::runtime_error(who + "an absorption array is not (nx ny, nz)");
+    if (with_bg)
+    {
+        for (const Array_gpu<Float,1>* a : bg_flux)
+            if (a->size() != ncol) throw std::runtime_error(who + "a flux array is not (nx ny)");
+        for (const Array_gpu<Float,1>* a : bg_abs)
+            if (a->size() != m.nbg()) throw std::runtime_error(who + "a background absorption array is not (nbg)");
+        if (m.bg_tau.dim(2) != ngpt) throw std::runtime_error(who + "the background's bg_tau, bg_ssa are not (nbg, ngpt)");
+        if (m.bg_cloudy() && m.bg_cld_tau.dim(2) != nbnd) throw std::runtime_error(who + "the background's cloud arrays are not (nbg, nbnd)");
+    }
+    m.check_table(who, ncol, nz, nbnd);
+    if (refuse_bg && m.has_bg) throw std::runtime_error(who + "a background is set: call the form with the background's outputs");
+    m.check_aerosol(who, ncol, nz, nbnd);
+    m.check_no_bg_aerosol_alone(who);
+    m.check_bg_aerosol(who, nbnd);
+}
+}
+
+// the arguments that the five forward loops begin with
+#define RT_LOOP_HEAD(p, photons) \
+        nx, ny, nz, tau.dim(3), band_lims_gpt.dim(2), RrxBool(top_at_1), RrxBool(independent_column), tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(), \
+        RT_CLOUD(p), dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), inc_dif.ptr(), knx, kny, knz, photons, seed, max_events, \
+        sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr()
 
 unsigned long long Raytracer_gpu::trace_rays(
         const int nx, const int ny, const int nz,
@@ -21,65 +74,22 @@ unsigned long long Raytracer_gpu::trace_rays(
         Array_gpu<Float,1>& sfc_dn_dir, Array_gpu<Float,1>& sfc_dn_dif, Array_gpu<Float,1>& sfc_up, Array_gpu<Float,1>& tod_up,
         Array_gpu<Float,2>& abs_dir, Array_gpu<Float,2>& abs_dif)
 {
-    if (nx < 0 || ny < 0 || nz < 0) throw std::runtime_error("Raytracer_gpu::trace_rays: negative extent");
-    const long long ncol = (long long)nx*ny;
-    const int ngpt = tau.dim(3);
-    const int nbnd = band_lims_gpt.dim(2);
-    if (tau.dim(1) != ncol || tau.dim(2) != nz || ssa.get_dims() != tau.get_dims())
-        throw std::runtime_error("Raytracer_gpu::trace_rays: tau, ssa are not (nx ny, nz, ngpt)");
-    const bool cloudy = cld_tau.size() > 0;
-    if (cloudy && (cld_tau.dim(1) != ncol || cld_tau.dim(2) != nz || cld_tau.dim(3) != nbnd || cld_ssa.get_dims() != cld_tau.get_dims() ||
-                   cld_g.get_dims() != cld_tau.get_dims()))
-        throw std::runtime_error("Raytracer_gpu::trace_rays: the cloud arrays are not (nx ny, nz, nbnd)");
-    if (!cloudy && (cld_ssa.size() > 0 || cld_g.size() > 0))
-        throw std::runtime_error("Raytracer_gpu::trace_rays: the cloud arrays are all empty or all given");
-    if (sfc_albedo.size() != ncol || inc_dir.size() != ngpt || inc_dif.size() != ngpt)
-        throw std::runtime_error("Raytracer_gpu::trace_rays: sfc_albedo is not (nx ny) or inc_dir, inc_dif are not (ngpt)");
-    for (const Array_gpu<Float,1>* a : {&sfc_dn_dir, &sfc_dn_dif, &sfc_up, &tod_up})
-        if (a->size() != ncol) throw std::runtime_error("Raytracer_gpu::trace_rays: a flux array is not (nx ny)");
-    for (const Array_gpu<Float,2>* a : {&abs_dir, &abs_dif})
-        if (a->dim(1) != ncol || a->dim(2) != nz) throw std::runtime_error("Raytracer_gpu::trace_rays: an absorption array is not (nx ny, nz)");
-
-    if (has_table && (cld_re.dim(1) != ncol || cld_re.dim(2) != nz || phase.dim(3) != nbnd))
-        throw std::runtime_error("Raytracer_gpu::trace_rays: the phase table's cld_re is not (nx ny, nz) or its tables are not (nmu, nre, nbnd)");
-
-    if (has_bg) throw std::runtime_error("Raytracer_gpu::trace_rays: a background is set: call the form with the background's outputs");
+    const Rt_members m = RT_MEMBERS;
+    check_shapes("Raytracer_gpu::trace_rays: ", m, nx, ny, nz, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, sfc_albedo,
+                 {inc_dir.size(), inc_dif.size()}, "inc_dir, inc_dif", {&sfc_dn_dir, &sfc_dn_dif, &sfc_up, &tod_up}, abs_dir, abs_dif,
+                 false, {}, {}, true);
+    const Rt_pointers p(m, cld_tau, cld_ssa, cld_g);
     Array_gpu<unsigned long long,1> n_capped({1});
-    const bool hazy = has_aer && aer_tau.size() > 0;
-    if (hazy && (aer_tau.dim(1) != ncol || aer_tau.dim(2) != nz || aer_tau.dim(3) != nbnd))
-        throw std::runtime_error("Raytracer_gpu::trace_rays: the aerosol arrays are not (nx ny, nz, nbnd)");
-    const Float* none = nullptr;
     Float* no_out = nullptr;
-    if (has_aer && bg_aer_tau.size() > 0) throw std::runtime_error("Raytracer_gpu::trace_rays: a background aerosol is set without a background");
-    // (rrx_raytracer_sw_aer takes each triple as a host array of its three device pointers)
-    const Float* const grid3[3] = {hazy ? aer_tau.ptr() : none, hazy ? aer_ssa.ptr() : none, hazy ? aer_g.ptr() : none};
+    // (rrx_raytracer_sw_aer takes each triple as a host array of its three device pointers; there is no background here)
     const Float* const* no_triple = nullptr;
     if (has_aer)
-        RRX_CALL(rrx_raytracer_sw_aer, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
-                 tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
-                 cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
-                 dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), inc_dif.ptr(), knx, kny, knz,
-                 photons_per_pixel, seed, max_events,
-                 sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr(),
-                 no_out, no_out, no_out, no_out, no_out,
-                 has_table ? mu.dim(1) : 0, has_table ? phase.dim(2) : 0, re0, dre, has_table ? mu.ptr() : none, has_table ? phase.ptr() : none,
-                 has_table ? cdf.ptr() : none, has_table ? cld_re.ptr() : none,
-                 0, none, none, none, none, none, none, grid3, no_triple);
+        RRX_CALL(rrx_raytracer_sw_aer, RT_LOOP_HEAD(p, photons_per_pixel), no_out, no_out, no_out, no_out, no_out, RT_TABLE(p), RT_BACKGROUND(p),
+                 p.aer, no_triple);
     else if (has_table)
-        RRX_CALL(rrx_raytracer_sw_phase, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
-                 tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
-                 cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
-                 dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), inc_dif.ptr(), knx, kny, knz,
-                 photons_per_pixel, seed, max_events,
-                 sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr(),
-                 mu.dim(1), phase.dim(2), re0, dre, mu.ptr(), phase.ptr(), cdf.ptr(), cld_re.ptr());
+        RRX_CALL(rrx_raytracer_sw_phase, RT_LOOP_HEAD(p, photons_per_pixel), RT_TABLE(p));
     else
-    RRX_CALL(rrx_raytracer_sw, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
-             tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
-             cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
-             dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), inc_dif.ptr(), knx, kny, knz,
-             photons_per_pixel, seed, max_events,
-             sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr());
+        RRX_CALL(rrx_raytracer_sw, RT_LOOP_HEAD(p, photons_per_pixel));
     return n_capped({1});
 }
 
@@ -101,67 +111,19 @@ unsigned long long Raytracer_gpu::trace_rays(
         Array_gpu<Float,1>& bg_abs_dir, Array_gpu<Float,1>& bg_abs_dif)
 {
     if (!has_bg) throw std::runtime_error("Raytracer_gpu::trace_rays: no background is set (set_background)");
-    if (nx < 0 || ny < 0 || nz < 0) throw std::runtime_error("Raytracer_gpu::trace_rays: negative extent");
-    const long long ncol = (long long)nx*ny;
-    const int ngpt = tau.dim(3);
-    const int nbnd = band_lims_gpt.dim(2);
-    const int nbg = dz_bg.size();
-    if (tau.dim(1) != ncol || tau.dim(2) != nz || ssa.get_dims() != tau.get_dims())
-        throw std::runtime_error("Raytracer_gpu::trace_rays: tau, ssa are not (nx ny, nz, ngpt)");
-    const bool cloudy = cld_tau.size() > 0;
-    if (cloudy && (cld_tau.dim(1) != ncol || cld_tau.dim(2) != nz || cld_tau.dim(3) != nbnd || cld_ssa.get_dims() != cld_tau.get_dims() ||
-                   cld_g.get_dims() != cld_tau.get_dims()))
-        throw std::runtime_error("Raytracer_gpu::trace_rays: the cloud arrays are not (nx ny, nz, nbnd)");
-    if (!cloudy && (cld_ssa.size() > 0 || cld_g.size() > 0))
-        throw std::runtime_error("Raytracer_gpu::trace_rays: the cloud arrays are all empty or all given");
-    if (sfc_albedo.size() != ncol || inc_dir.size() != ngpt || inc_dif.size() != ngpt)
-        throw std::runtime_error("Raytracer_gpu::trace_rays: sfc_albedo is not (nx ny) or inc_dir, inc_dif are not (ngpt)");
-    for (const Array_gpu<Float,1>* a : {&sfc_dn_dir, &sfc_dn_dif, &sfc_up, &tod_up, &toa_up, &tod_dn_dir, &tod_dn_dif})
-        if (a->size() != ncol) throw std::runtime_error("Raytracer_gpu::trace_rays: a flux array is not (nx ny)");
-    for (const Array_gpu<Float,2>* a : {&abs_dir, &abs_dif})
-        if (a->dim(1) != ncol || a->dim(2) != nz) throw std::runtime_error("Raytracer_gpu::trace_rays: an absorption array is not (nx ny, nz)");
-    for (const Array_gpu<Float,1>* a : {&bg_abs_dir, &bg_abs_dif})
-        if (a->size() != nbg) throw std::runtime_error("Raytracer_gpu::trace_rays: a background absorption array is not (nbg)");
-    if (bg_tau.dim(2) != ngpt) throw std::runtime_error("Raytracer_gpu::trace_rays: the background's bg_tau, bg_ssa are not (nbg, ngpt)");
-    const bool bg_cloudy = bg_cld_tau.size() > 0;
-    if (bg_cloudy && bg_cld_tau.dim(2) != nbnd) throw std::runtime_error("Raytracer_gpu::trace_rays: the background's cloud arrays are not (nbg, nbnd)");
-    if (has_table && (cld_re.dim(1) != ncol || cld_re.dim(2) != nz || phase.dim(3) != nbnd))
-        throw std::runtime_error("Raytracer_gpu::trace_rays: the phase table's cld_re is not (nx ny, nz) or its tables are not (nmu, nre, nbnd)");
-
+    const Rt_members m = RT_MEMBERS;
+    check_shapes("Raytracer_gpu::trace_rays: ", m, nx, ny, nz, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, sfc_albedo,
+                 {inc_dir.size(), inc_dif.size()}, "inc_dir, inc_dif",
+                 {&sfc_dn_dir, &sfc_dn_dif, &sfc_up, &tod_up, &toa_up, &tod_dn_dir, &tod_dn_dif}, abs_dir, abs_dif,
+                 true, {}, {&bg_abs_dir, &bg_abs_dif}, false);
+    const Rt_pointers p(m, cld_tau, cld_ssa, cld_g);
     Array_gpu<unsigned long long,1> n_capped({1});
-    const Float* none = nullptr;
-    const bool hazy = has_aer && aer_tau.size() > 0;
-    if (hazy && (aer_tau.dim(1) != ncol || aer_tau.dim(2) != nz || aer_tau.dim(3) != nbnd))
-        throw std::runtime_error("Raytracer_gpu::trace_rays: the aerosol arrays are not (nx ny, nz, nbnd)");
-    const bool bg_hazy = has_aer && bg_aer_tau.size() > 0;
-    if (bg_hazy && (bg_aer_tau.dim(1) != nbg || bg_aer_tau.dim(2) != nbnd))
-        throw std::runtime_error("Raytracer_gpu::trace_rays: the background's aerosol arrays are not (nbg, nbnd)");
-    const Float* const grid3[3] = {hazy ? aer_tau.ptr() : none, hazy ? aer_ssa.ptr() : none, hazy ? aer_g.ptr() : none};
-    const Float* const aloft3[3] = {bg_hazy ? bg_aer_tau.ptr() : none, bg_hazy ? bg_aer_ssa.ptr() : none, bg_hazy ? bg_aer_g.ptr() : none};
     if (has_aer)
-        RRX_CALL(rrx_raytracer_sw_aer, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
-                 tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
-                 cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
-                 dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), inc_dif.ptr(), knx, kny, knz,
-                 photons_per_pixel, seed, max_events,
-                 sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr(),
-                 toa_up.ptr(), tod_dn_dir.ptr(), tod_dn_dif.ptr(), bg_abs_dir.ptr(), bg_abs_dif.ptr(),
-                 has_table ? mu.dim(1) : 0, has_table ? phase.dim(2) : 0, re0, dre, has_table ? mu.ptr() : none, has_table ? phase.ptr() : none,
-                 has_table ? cdf.ptr() : none, has_table ? cld_re.ptr() : none,
-                 nbg, dz_bg.ptr(), bg_tau.ptr(), bg_ssa.ptr(), bg_cloudy ? bg_cld_tau.ptr() : none, bg_cloudy ? bg_cld_ssa.ptr() : none,
-                 bg_cloudy ? bg_cld_g.ptr() : none, grid3, aloft3);
+        RRX_CALL(rrx_raytracer_sw_aer, RT_LOOP_HEAD(p, photons_per_pixel), toa_up.ptr(), tod_dn_dir.ptr(), tod_dn_dif.ptr(), bg_abs_dir.ptr(),
+                 bg_abs_dif.ptr(), RT_TABLE(p), RT_BACKGROUND(p), p.aer, p.bg_aer);
     else
-        RRX_CALL(rrx_raytracer_sw_bg, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
-                 tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
-                 cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
-                 dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), inc_dif.ptr(), knx, kny, knz,
-                 photons_per_pixel, seed, max_events,
-                 sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr(),
-                 toa_up.ptr(), tod_dn_dir.ptr(), tod_dn_dif.ptr(), bg_abs_dir.ptr(), bg_abs_dif.ptr(),
-                 has_table ? mu.dim(1) : 0, has_table ? phase.dim(2) : 0, re0, dre, has_table ? mu.ptr() : none, has_table ? phase.ptr() : none,
-                 has_table ? cdf.ptr() : none, has_table ? cld_re.ptr() : none,
-                 nbg, dz_bg.ptr(), bg_tau.ptr(), bg_ssa.ptr(), bg_cloudy ? bg_cld_tau.ptr() : none, bg_cloudy ? bg_cld_ssa.ptr() : none,
-                 bg_cloudy ? bg_cld_g.ptr() : none);
+        RRX_CALL(rrx_raytracer_sw_bg, RT_LOOP_HEAD(p, photons_per_pixel), toa_up.ptr(), tod_dn_dir.ptr(), tod_dn_dif.ptr(), bg_abs_dir.ptr(),
+                 bg_abs_dif.ptr(), RT_TABLE(p), RT_BACKGROUND(p));
     return n_capped({1});
 }
 
@@ -182,61 +144,17 @@ unsigned long long Raytracer_gpu::trace_rays_spectral(
         Array_gpu<Float,1>& toa_up, Array_gpu<Float,1>& tod_dn_dir, Array_gpu<Float,1>& tod_dn_dif,
         Array_gpu<Float,1>& bg_abs_dir, Array_gpu<Float,1>& bg_abs_dif)
 {
-    const std::string who = "Raytracer_gpu::trace_rays_spectral: ";
-    if (nx < 0 || ny < 0 || nz < 0) throw std::runtime_error(who + "negative extent");
-    const long long ncol = (long long)nx*ny;
-    const int ngpt = tau.dim(3);
-    const int nbnd = band_lims_gpt.dim(2);
-    const int nbg = has_bg ? dz_bg.size() : 0;
-    if (tau.dim(1) != ncol || tau.dim(2) != nz || ssa.get_dims() != tau.get_dims()) throw std::runtime_error(who + "tau, ssa are not (nx ny, nz, ngpt)");
-    const bool cloudy = cld_tau.size() > 0;
-    if (cloudy && (cld_tau.dim(1) != ncol || cld_tau.dim(2) != nz || cld_tau.dim(3) != nbnd || cld_ssa.get_dims() != cld_tau.get_dims() ||
-                   cld_g.get_dims() != cld_tau.get_dims()))
-        throw std::runtime_error(who + "the cloud arrays are not (nx ny, nz, nbnd)");
-    if (!cloudy && (cld_ssa.size() > 0 || cld_g.size() > 0)) throw std::runtime_error(who + "the cloud arrays are all empty or all given");
-    if (sfc_albedo.size() != ncol || inc_dir.size() != ngpt || inc_dif.size() != ngpt || photons_per_pixel_gpt.size() != ngpt)
-        throw std::runtime_error(who + "sfc_albedo is not (nx ny) or inc_dir, inc_dif, photons_per_pixel_gpt are not (ngpt)");
-    for (const Array_gpu<Float,1>* a : {&sfc_dn_dir, &sfc_dn_dif, &sfc_up, &tod_up})
-        if (a->size() != ncol) throw std::runtime_error(who + "a flux array is not (nx ny)");
-    for (const Array_gpu<Float,2>* a : {&abs_dir, &abs_dif})
-        if (a->dim(1) != ncol || a->dim(2) != nz) throw std::runtime_error(who + "an absorption array is not (nx ny, nz)");
-    if (has_bg)
-    {
-        for (const Array_gpu<Float,1>* a : {&toa_up, &tod_dn_dir, &tod_dn_dif})
-            if (a->size() != ncol) throw std::runtime_error(who + "a flux array is not (nx ny)");
-        for (const Array_gpu<Float,1>* a : {&bg_abs_dir, &bg_abs_dif})
-            if (a->size() != nbg) throw std::runtime_error(who + "a background absorption array is not (nbg)");
-        if (bg_tau.dim(2) != ngpt) throw std::runtime_error(who + "the background's bg_tau, bg_ssa are not (nbg, ngpt)");
-    }
-    const bool bg_cloudy = has_bg && bg_cld_tau.size() > 0;
-    if (bg_cloudy && bg_cld_tau.dim(2) != nbnd) throw std::runtime_error(who + "the background's cloud arrays are not (nbg, nbnd)");
-    if (has_table && (cld_re.dim(1) != ncol || cld_re.dim(2) != nz || phase.dim(3) != nbnd))
-        throw std::runtime_error(who + "the phase table's cld_re is not (nx ny, nz) or its tables are not (nmu, nre, nbnd)");
-    const bool hazy = has_aer && aer_tau.size() > 0;
-    if (hazy && (aer_tau.dim(1) != ncol || aer_tau.dim(2) != nz || aer_tau.dim(3) != nbnd))
-        throw std::runtime_error(who + "the aerosol arrays are not (nx ny, nz, nbnd)");
-    const bool bg_hazy = has_aer && bg_aer_tau.size() > 0;
-    if (bg_hazy && !has_bg) throw std::runtime_error(who + "a background aerosol is set without a background");
-    if (bg_hazy && (bg_aer_tau.dim(1) != nbg || bg_aer_tau.dim(2) != nbnd))
-        throw std::runtime_error(who + "the background's aerosol arrays are not (nbg, nbnd)");
-
+    const Rt_members m = RT_MEMBERS;
+    check_shapes("Raytracer_gpu::trace_rays_spectral: ", m, nx, ny, nz, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, sfc_albedo,
+                 {inc_dir.size(), inc_dif.size(), photons_per_pixel_gpt.size()}, "inc_dir, inc_dif, photons_per_pixel_gpt",
+                 {&sfc_dn_dir, &sfc_dn_dif, &sfc_up, &tod_up}, abs_dir, abs_dif,
+                 has_bg, {&toa_up, &tod_dn_dir, &tod_dn_dif}, {&bg_abs_dir, &bg_abs_dif}, false);
+    const Rt_pointers p(m, cld_tau, cld_ssa, cld_g);
     Array_gpu<unsigned long long,1> n_capped({1});
-    const Float* none = nullptr;
     Float* no_out = nullptr;
-    const Float* const grid3[3] = {hazy ? aer_tau.ptr() : none, hazy ? aer_ssa.ptr() : none, hazy ? aer_g.ptr() : none};
-    const Float* const aloft3[3] = {bg_hazy ? bg_aer_tau.ptr() : none, bg_hazy ? bg_aer_ssa.ptr() : none, bg_hazy ? bg_aer_g.ptr() : none};
-    RRX_CALL(rrx_raytracer_sw_spectral, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), RrxBool(independent_column),
-             tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
-             cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
-             dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), inc_dif.ptr(), knx, kny, knz,
-             photons_per_pixel_gpt.ptr(), seed, max_events,
-             sfc_dn_dir.ptr(), sfc_dn_dif.ptr(), sfc_up.ptr(), tod_up.ptr(), abs_dir.ptr(), abs_dif.ptr(), n_capped.ptr(),
+    RRX_CALL(rrx_raytracer_sw_spectral, RT_LOOP_HEAD(p, photons_per_pixel_gpt.ptr()),
              has_bg ? toa_up.ptr() : no_out, has_bg ? tod_dn_dir.ptr() : no_out, has_bg ? tod_dn_dif.ptr() : no_out,
-             has_bg ? bg_abs_dir.ptr() : no_out, has_bg ? bg_abs_dif.ptr() : no_out,
-             has_table ? mu.dim(1) : 0, has_table ? phase.dim(2) : 0, re0, dre, has_table ? mu.ptr() : none, has_table ? phase.ptr() : none,
-             has_table ? cdf.ptr() : none, has_table ? cld_re.ptr() : none,
-             nbg, has_bg ? dz_bg.ptr() : none, has_bg ? bg_tau.ptr() : none, has_bg ? bg_ssa.ptr() : none,
-             bg_cloudy ? bg_cld_tau.ptr() : none, bg_cloudy ? bg_cld_ssa.ptr() : none, bg_cloudy ? bg_cld_g.ptr() : none, grid3, aloft3);
+             has_bg ? bg_abs_dir.ptr() : no_out, has_bg ? bg_abs_dif.ptr() : no_out, RT_TABLE(p), RT_BACKGROUND(p), p.aer, p.bg_aer);
     return n_capped({1});
 }
 

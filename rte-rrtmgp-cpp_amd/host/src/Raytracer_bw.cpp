@@ -1,5 +1,35 @@
 // Raytracer_bw_gpu: checks the shapes and forwards to rrx_raytracer_bw; a non-zero status becomes std::runtime_error.
 #include "Raytracer_bw.h"
+#include "Raytracer_members.h"
+
+namespace
+{
+// THE SHAPE CHECK of trace_rays_bw
+void check_shapes(const std::string& who, const Rt_members& m, const int nx, const int ny, const int nz,
+                  const Array_gpu<Float,3>& tau, const Array_gpu<Float,3>& ssa, const Array_gpu<int,2>& band_lims_gpt,
+                  const Array_gpu<Float,3>& cld_tau, const Array_gpu<Float,3>& cld_ssa, const Array_gpu<Float,3>& cld_g,
+                  const Array_gpu<Float,1>& sfc_albedo, const Array<Float,1>& inc_dir, const Sensor_bw& sensor, const Array_gpu<Float,2>& radiance)
+{
+    if (nx < 0 || ny < 0 || nz < 0) throw std::runtime_error(who + "negative extent");
+    const long long ncol = (long long)nx*ny;
+    const int ngpt = tau.dim(3), nbnd = band_lims_gpt.dim(2);
+    if (tau.dim(1) != ncol || tau.dim(2) != nz || ssa.get_dims() != tau.get_dims()) throw std::runtime_error(who + "tau, ssa are not (nx ny, nz, ngpt)");
+    const bool cloudy = cld_tau.size() > 0;
+    if (cloudy && (cld_tau.dim(1) != ncol || cld_tau.dim(2) != nz || cld_tau.dim(3) != nbnd || cld_ssa.get_dims() != cld_tau.get_dims() ||
+                   cld_g.get_dims() != cld_tau.get_dims()))
+        throw std::runtime_error(who + "the cloud arrays are not (nx ny, nz, nbnd)");
+    if (!cloudy && (cld_ssa.size() > 0 || cld_g.size() > 0)) throw std::runtime_error(who + "the cloud arrays are all empty or all given");
+    if (sfc_albedo.size() != ncol || inc_dir.size() != ngpt) throw std::runtime_error(who + "sfc_albedo is not (nx ny) or inc_dir is not (ngpt)");
+    if (sensor.npx < 0 || sensor.npy < 0 || radiance.dim(1) != sensor.npx || radiance.dim(2) != sensor.npy)
+        throw std::runtime_error(who + "radiance is not (npx, npy)");
+    m.check_table(who, ncol, nz, nbnd);
+    m.check_aerosol(who, ncol, nz, nbnd);
+    if (m.has_bg && (m.bg_tau.dim(2) != ngpt || (m.bg_cloudy() && m.bg_cld_tau.dim(2) != nbnd)))
+        throw std::runtime_error(who + "the background's arrays are not (nbg, ngpt) and (nbg, nbnd)");
+    m.check_bg_aerosol(who, nbnd);
+    m.check_no_bg_aerosol_alone(who);
+}
+}
 
 unsigned long long Raytracer_bw_gpu::trace_rays_bw(
         const int nx, const int ny, const int nz,
@@ -16,87 +46,27 @@ unsigned long long Raytracer_bw_gpu::trace_rays_bw(
         const long long rays_per_pixel, const unsigned long long seed, const int max_events,
         Array_gpu<Float,2>& radiance, unsigned long long* n_clamped_out)
 {
-    if (nx < 0 || ny < 0 || nz < 0) throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: negative extent");
-    const long long ncol = (long long)nx*ny;
-    const int ngpt = tau.dim(3);
-    const int nbnd = band_lims_gpt.dim(2);
-    if (tau.dim(1) != ncol || tau.dim(2) != nz || ssa.get_dims() != tau.get_dims())
-        throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: tau, ssa are not (nx ny, nz, ngpt)");
-    const bool cloudy = cld_tau.size() > 0;
-    if (cloudy && (cld_tau.dim(1) != ncol || cld_tau.dim(2) != nz || cld_tau.dim(3) != nbnd || cld_ssa.get_dims() != cld_tau.get_dims() ||
-                   cld_g.get_dims() != cld_tau.get_dims()))
-        throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: the cloud arrays are not (nx ny, nz, nbnd)");
-    if (!cloudy && (cld_ssa.size() > 0 || cld_g.size() > 0))
-        throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: the cloud arrays are all empty or all given");
-    if (sfc_albedo.size() != ncol || inc_dir.size() != ngpt)
-        throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: sfc_albedo is not (nx ny) or inc_dir is not (ngpt)");
-    if (sensor.npx < 0 || sensor.npy < 0 || radiance.dim(1) != sensor.npx || radiance.dim(2) != sensor.npy)
-        throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: radiance is not (npx, npy)");
-
+    const Rt_members m = RT_MEMBERS;
+    check_shapes("Raytracer_bw_gpu::trace_rays_bw: ", m, nx, ny, nz, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, sfc_albedo, inc_dir, sensor,
+                 radiance);
+    const Rt_pointers p(m, cld_tau, cld_ssa, cld_g);
     const Float numbers[12] = {sensor.position[0], sensor.position[1], sensor.position[2], sensor.e_w[0], sensor.e_w[1], sensor.e_w[2],
                                sensor.e_h[0], sensor.e_h[1], sensor.e_h[2], sensor.e_d[0], sensor.e_d[1], sensor.e_d[2]};
-    if (has_table && (cld_re.dim(1) != ncol || cld_re.dim(2) != nz || phase.dim(3) != nbnd))
-        throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: the phase table's cld_re is not (nx ny, nz) or its tables are not (nmu, nre, nbnd)");
     Array_gpu<unsigned long long,1> tallies({2});
-    const bool hazy = has_aer && aer_tau.size() > 0;
-    if (hazy && (aer_tau.dim(1) != ncol || aer_tau.dim(2) != nz || aer_tau.dim(3) != nbnd))
-        throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: the aerosol arrays are not (nx ny, nz, nbnd)");
+// the arguments that the four backward loops begin with
+#define RT_BW_LOOP_HEAD \
+        nx, ny, nz, tau.dim(3), band_lims_gpt.dim(2), RrxBool(top_at_1), tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(), RT_CLOUD(p), \
+        dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), knx, kny, knz, \
+        sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers, rays_per_pixel, seed, max_events, \
+        radiance.ptr(), tallies.ptr(), tallies.ptr() + 1
     if (has_aer)
-    {
-        const bool bg_cloudy = has_bg && bg_cld_tau.size() > 0, bg_hazy = has_bg && bg_aer_tau.size() > 0;
-        const int nbg = has_bg ? dz_bg.size() : 0;
-        if (has_bg && (bg_tau.dim(2) != ngpt || (bg_cloudy && bg_cld_tau.dim(2) != nbnd)))
-            throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: the background's arrays are not (nbg, ngpt) and (nbg, nbnd)");
-        if (bg_hazy && (bg_aer_tau.dim(1) != nbg || bg_aer_tau.dim(2) != nbnd))
-            throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: the background's aerosol arrays are not (nbg, nbnd)");
-        if (!has_bg && bg_aer_tau.size() > 0)
-            throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: a background aerosol is set without a background");
-        const Float* none = nullptr;
-        RRX_CALL(rrx_raytracer_bw_aer, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1),
-                 tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
-                 cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
-                 dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), knx, kny, knz,
-                 sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers, rays_per_pixel, seed, max_events,
-                 radiance.ptr(), tallies.ptr(), tallies.ptr() + 1,
-                 has_table ? mu.dim(1) : 0, has_table ? phase.dim(2) : 0, re0, dre, has_table ? mu.ptr() : none, has_table ? phase.ptr() : none,
-                 has_table ? cdf.ptr() : none, has_table ? cld_re.ptr() : none,
-                 nbg, has_bg ? dz_bg.ptr() : none, has_bg ? bg_tau.ptr() : none, has_bg ? bg_ssa.ptr() : none,
-                 bg_cloudy ? bg_cld_tau.ptr() : none, bg_cloudy ? bg_cld_ssa.ptr() : none, bg_cloudy ? bg_cld_g.ptr() : none,
-                 hazy ? aer_tau.ptr() : none, hazy ? aer_ssa.ptr() : none, hazy ? aer_g.ptr() : none,
-                 bg_hazy ? bg_aer_tau.ptr() : none, bg_hazy ? bg_aer_ssa.ptr() : none, bg_hazy ? bg_aer_g.ptr() : none);
-    }
+        RRX_CALL(rrx_raytracer_bw_aer, RT_BW_LOOP_HEAD, RT_TABLE(p), RT_BACKGROUND(p), p.aer[0], p.aer[1], p.aer[2], p.bg_aer[0], p.bg_aer[1], p.bg_aer[2]);
     else if (has_bg)
-    {
-        const bool bg_cloudy = bg_cld_tau.size() > 0;
-        if (bg_tau.dim(2) != ngpt || (bg_cloudy && bg_cld_tau.dim(2) != nbnd))
-            throw std::runtime_error("Raytracer_bw_gpu::trace_rays_bw: the background's arrays are not (nbg, ngpt) and (nbg, nbnd)");
-        const Float* none = nullptr;
-        RRX_CALL(rrx_raytracer_bw_bg, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1),
-                 tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
-                 cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
-                 dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), knx, kny, knz,
-                 sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers, rays_per_pixel, seed, max_events,
-                 radiance.ptr(), tallies.ptr(), tallies.ptr() + 1,
-                 has_table ? mu.dim(1) : 0, has_table ? phase.dim(2) : 0, re0, dre, has_table ? mu.ptr() : none, has_table ? phase.ptr() : none,
-                 has_table ? cdf.ptr() : none, has_table ? cld_re.ptr() : none,
-                 dz_bg.size(), dz_bg.ptr(), bg_tau.ptr(), bg_ssa.ptr(), bg_cloudy ? bg_cld_tau.ptr() : none,
-                 bg_cloudy ? bg_cld_ssa.ptr() : none, bg_cloudy ? bg_cld_g.ptr() : none);
-    }
+        RRX_CALL(rrx_raytracer_bw_bg, RT_BW_LOOP_HEAD, RT_TABLE(p), RT_BACKGROUND(p));
     else if (has_table)
-        RRX_CALL(rrx_raytracer_bw_phase, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1),
-                 tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
-                 cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
-                 dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), knx, kny, knz,
-                 sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers, rays_per_pixel, seed, max_events,
-                 radiance.ptr(), tallies.ptr(), tallies.ptr() + 1,
-                 mu.dim(1), phase.dim(2), re0, dre, mu.ptr(), phase.ptr(), cdf.ptr(), cld_re.ptr());
+        RRX_CALL(rrx_raytracer_bw_phase, RT_BW_LOOP_HEAD, RT_TABLE(p));
     else
-    RRX_CALL(rrx_raytracer_bw, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1),
-             tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(),
-             cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
-             dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), knx, kny, knz,
-             sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers, rays_per_pixel, seed, max_events,
-             radiance.ptr(), tallies.ptr(), tallies.ptr() + 1);
+        RRX_CALL(rrx_raytracer_bw, RT_BW_LOOP_HEAD);
     if (n_clamped_out != nullptr) *n_clamped_out = tallies({2});
     return tallies({1});
 }
