@@ -43,6 +43,28 @@ class Raytracer_bw_gpu
                 const long long rays_per_pixel, const unsigned long long seed, const int max_events,
                 Array_gpu<Float,2>& radiance, unsigned long long* n_clamped = nullptr);
 
+        // The rays of all g-points in one launch, tallied by band, and a channel matrix from bands to what the sensor sees
+        // (rrx_camera_render_spectral): trace_rays_bw with rays_per_pixel_gpt (ngpt) on the host, the rays per pixel of
+        // every g-point (Raytracer_gpu::spectral_allocation deals a total by flux, or the caller brings its own), in place of
+        // rays_per_pixel, and chan_weights (nbnd, nchan) on the host: channel c sees sum_b chan_weights(b, c) x the radiance of band b.
+        // radiance (npx, npy, nchan) in W m-2 sr-1 is overwritten. It honours the phase table, the background and the aerosol that are
+        // set. ngpt <= 1024.
+        unsigned long long trace_rays_bw_spectral(
+                const int nx, const int ny, const int nz,
+                const Float dx, const Float dy, const Float dz,
+                const bool top_at_1,
+                const Array_gpu<Float,3>& tau, const Array_gpu<Float,3>& ssa,
+                const Array_gpu<int,2>& band_lims_gpt,
+                const Array_gpu<Float,3>& cld_tau, const Array_gpu<Float,3>& cld_ssa, const Array_gpu<Float,3>& cld_g,
+                const Array_gpu<Float,1>& sfc_albedo,
+                const Float mu0, const Float azimuth,
+                const Array<Float,1>& inc_dir,
+                const int knx, const int kny, const int knz,
+                const Sensor_bw& sensor,
+                const Array<long long,1>& rays_per_pixel_gpt, const unsigned long long seed, const int max_events,
+                const Array<Float,2>& chan_weights,
+                Array_gpu<Float,3>& radiance, unsigned long long* n_clamped = nullptr);
+
         // Tabulated cloud phase functions (rrx_*_phase): with a table set, cloud scatters by the phase function of the
         // cell's radius in place of Henyey-Greenstein. mu (nmu); phase, cdf (nmu, nre, nbnd) as rrx_rt_phase_tables makes them
         // (rrx_rt_phase_tables); the radii re0 + dre ire; cld_re (ncol, nz) in the unit of re0. The arrays are copied.

@@ -904,7 +904,51 @@ int rrx_raytracer_sw_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, R
         F* toa_up, F* tod_dn_dir, F* tod_dn_dif, F* bg_abs_dir, F* bg_abs_dif, \
         int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
         int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, \
-        const F* const* aer, const F* const* bg_aer, void* stream);
+        const F* const* aer, const F* const* bg_aer, void* stream); \
+/* ---- The backward tracer with the rays of all g-points in one launch, counts kept by band, and a channel matrix from bands to what a \
+   sensor sees (csrc/rrx_raytracer_bw.hip). The backward counterpart of the entries above, ngpt <= 1024, built on the \
+   aerosol form. The symbols begin rrx_camera_: the set of rrx_rt_ and rrx_raytracer_ symbols is closed. The rays of a launch are the \
+   concatenation, in g-point order, of n_g = m_g npix rays per g-point, m_g >= 0 rays per pixel; ray_end (ngpt+1) holds the prefix sums \
+   with ray_end[0] = 0. Global index p belongs to the g with ray_end[g] <= p < ray_end[g+1] (empty ranges are stepped over); its local \
+   index is q = p - ray_end[g], its Philox stream that of ray q of g-point g and its pixel q mod npix: it is ray q of \
+   rrx_rt_bw_trace_counts_aer(igpt = g), draw for draw. Only the deposits differ: a deposit d is tallied as \
+   llrint(min(d weight0[g], 2^20) 2^32) into counts[band(g) npix + pix], counts (nbnd, npix); a clamped one is counted in n_clamped. \
+   band_lims_gpt is always needed; a g-point that lies in no band has no row and its deposits are dropped. With weight0[g] = 1 the \
+   counts of a band are the integer sums over its g-points of those of the per-g-point entry. \
+   rrx_camera_trace_counts_spectral: rrx_rt_bw_trace_counts_aer without igpt and with the DEVICE arrays ray_end (ngpt+1) and weight0 \
+   (ngpt); k_null is rrx_rt_k_null_all's and bg_profile rrx_rt_bg_profile_all's; ray0 / nrays are a range of the list; counts, n_capped, \
+   n_clamped are caller-zeroed, added into, and additive over ranges of the list. The entry cannot look into device arrays: a ray \
+   beyond ray_end[ngpt] is stepped over and the kernel stays inside its arrays whatever ray_end holds; the callers that form the list \
+   on the host refuse one that does not ascend. \
+   rrx_camera_channels: out[c, pix] = scale sum_b chan_weights[c, b] (counts[b, pix] 2^-32), the sum in band order in F; chan_weights \
+   (nchan, nbnd) on the DEVICE, out (nchan, npix) is written, not added into. The identity gives radiance by band, a row of ones \
+   broadband, three rows of colour-matching weights colour. npix = 0: returns 0 without a launch. \
+   rrx_camera_render_spectral: rrx_raytracer_bw_aer with rays_per_pixel_gpt (ngpt, HOST) = m_g in place of rays_per_pixel, and nchan, \
+   chan_weights (nchan, nbnd, HOST) and radiance (nchan, npix) in W m-2 sr-1. weight0[g] = (inc_dir[g] / F(m_g)) / U, U = S / F(P), S \
+   the sum of inc_dir[g] over the g-points with m_g > 0 in index order, P the sum of m_g. It builds the profile, traces chunks of \
+   consecutive g-points (the largest chunk whose k_null fits 1 GiB; RRX_RT_SPECTRAL_GPT_PER_LAUNCH in the environment overrides it, read \
+   at every call), adds the counts of all chunks in integers and converts them once with scale = U / mu0: the result does not depend on \
+   the chunking. It waits for its stream once, after copying the ray list. All m_g = 0: the outputs are zeroed and it returns 0. \
+   Refused before any HIP call: what the _aer counterparts refuse, ngpt > 1024, nbnd < 1, a NULL band_lims_gpt, m_g < 0, m_g > 0 where \
+   inc_dir[g] <= 0, nchan < 1, a NULL chan_weights. */ \
+int rrx_camera_trace_counts_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const long long* ray_end, const F* weight0, \
+        int knx, int kny, int knz, const F* k_null, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
+        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_profile, const F* aer_tau, const F* aer_ssa, const F* aer_g, void* stream); \
+int rrx_camera_channels##SFX(long long npix, int nbnd, int nchan, const unsigned long long* counts, const F* chan_weights, F scale, F* out, \
+        void* stream); \
+int rrx_camera_render_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_albedo, F mu0, F azimuth, const F* inc_dir, int knx, int kny, int knz, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, const long long* rays_per_pixel_gpt, unsigned long long seed, int max_events, \
+        int nchan, const F* chan_weights, F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
+        int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
+        int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, \
+        const F* aer_tau, const F* aer_ssa, const F* aer_g, const F* bg_aer_tau, const F* bg_aer_ssa, const F* bg_aer_g, void* stream);
 
 RRX_DECLARE(double, _f64)
 RRX_DECLARE(float, _f32)

@@ -668,11 +668,6 @@ void launch_bg_profile_all(const Background<F>& bg, const int ngpt, const int nb
     bg_profile_all_kernel<F><<<grid, 64, 0, st>>>(bg.nbg, nbnd, dz_bg, bg.tau, bg.ssa, lims, bg.cld_tau, bg.cld_ssa, bg.cld_g, aer, profile);
 }
 
-inline void check_spectral_ngpt(const int ngpt)
-{
-    if (ngpt > RT_SPECTRAL_MAX_GPT) throw std::runtime_error("ngpt must be <= 1024 in the spectral form");
-}
-
 // rrx_rt_bg_profile (bg.form = FORM_BG), _aer (FORM_AER: the 7-row profile, its triple may be NULL) and _all (FORM_AER, ALL: the
 // profiles of all g-points, igpt is not read)
 template<typename F, bool ALL>
@@ -850,15 +845,6 @@ struct FwWorkspace
         launch_counts_to_flux<F>(ncol*nz, t.abs_dif, scale / dz, out.abs_dif, st);
     }
 };
-
-// g-points per trace launch of rrx_raytracer_sw_spectral: the largest chunk whose k_null fits 1 GiB, or
-// RRX_RT_SPECTRAL_GPT_PER_LAUNCH from the environment, read at every call. The result does not depend on it.
-inline int spectral_gpt_per_launch(const size_t k_null_bytes_per_gpt, const int ngpt)
-{
-    if (const char* e = std::getenv("RRX_RT_SPECTRAL_GPT_PER_LAUNCH")) { const int n = std::atoi(e); if (n >= 1) return std::min(n, ngpt); }
-    const size_t fit = (size_t(1) << 30) / std::max<size_t>(k_null_bytes_per_gpt, 1);
-    return int(std::min<size_t>(std::max<size_t>(fit, 1), size_t(ngpt)));
-}
 
 // The loops over the g-points. photons_per_pixel: rrx_raytracer_sw, _phase, _bg, _aer, one k_null, profile and trace launch per
 // g-point with incident flux, each g-point's counts converted with its own scale. SPECTRAL (m_gpt, a host array; bg.form = FORM_AER):

@@ -131,10 +131,34 @@ __device__ __forceinline__ bool after_surface(Stream& rng, F& weight, F& ux, F& 
 // direction from it, in the grid (after the walk: then = 3) and aloft, with a phase table too. DEPARTURE: the reference draws
 // aerosol, cloud, gas in that order; cloud comes first here so that a scene without aerosol draws exactly what it draws without
 // this form.
-template<typename F, bool TABLE, bool BG, bool AER>
-__global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, const PhaseArgs<F,TABLE> ph, const BgArgs<F,BG,AER> bgin)
+//
+// SPECTRAL (trace_bw_kernel<F,TABLE,true,true,true>, the rrx_camera_* entries; rrx_rt_common.h): the rays of all g-points in
+// one launch, built on the aerosol form only. a.ray0 / a.nrays address the concatenated list whose prefix sums are sp.photon_end (here:
+// ray_end); the g-point is state of the ray, set when a lane takes its next one. The band, the tau / ssa / cloud / aerosol slices, the
+// k_null slice, the background's profile rows and the band's phase table are derived from it at the event and at every cell of the
+// walk: the lane carries no pointers. The transport is that of ray q of g-point g in the per-g-point launch, draw for draw; a deposit
+// is min(d weight0[g], 2^20), tallied into counts[band(g) npix + pix]; a.igpt is not read. A g-point that lies in no band has no
+// row of counts: its deposits are dropped.
+template<typename F> struct BwSpecArgs { BgIn<F> in; AerIn<F> aer; SpecIn<F> sp; };
+template<typename F, bool BG, bool AER, bool SPECTRAL>
+using BwBgArgs = std::conditional_t<SPECTRAL, BwSpecArgs<F>, BgArgs<F,BG,AER>>;
+
+// LDS of the spectral form: what stage_spectral lays out (ray_end, the levels, the band table: spectral_lds_bytes), rounded up to 8
+// bytes, then the phase nodes
+__host__ __device__ inline size_t bw_nodes_offset(const int ngpt, const int nbg, const size_t size_of_f)
+{
+    return (size_t(ngpt + 1)*sizeof(long long) + size_t(nbg + 1)*size_of_f + size_t(ngpt)*sizeof(int) + 7)/8*8;
+}
+inline size_t bw_spectral_lds_bytes(const int ngpt, const int nbg, const int nmu, const size_t size_of_f)
+{
+    return bw_nodes_offset(ngpt, nbg, size_of_f) + size_t(nmu)*size_of_f;
+}
+
+template<typename F, bool TABLE, bool BG, bool AER, bool SPECTRAL = false>
+__global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, const PhaseArgs<F,TABLE> ph, const BwBgArgs<F,BG,AER,SPECTRAL> bgin)
 {
     static_assert(BG || !AER, "the aerosol form is built on the background form");
+    static_assert(AER || !SPECTRAL, "the spectral form is built on the aerosol form");
     const long long nthreads = (long long)gridDim.x*blockDim.x;
     long long next_ray = (long long)blockIdx.x*blockDim.x + threadIdx.x;
 
@@ -143,7 +167,19 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
     [[maybe_unused]] const F* mu_s = nullptr;
     [[maybe_unused]] PhaseTable<F> tab{};
     [[maybe_unused]] BgView<F> bg{};
-    if constexpr (TABLE || BG)
+    [[maybe_unused]] SpecView sv{};
+    if constexpr (SPECTRAL)
+    {
+        extern __shared__ double phase_lds[];
+        if constexpr (TABLE)
+        {
+            F* nodes = reinterpret_cast<F*>(reinterpret_cast<char*>(phase_lds) + bw_nodes_offset(bgin.sp.ngpt, bgin.in.nbg, sizeof(F)));
+            for (int n=threadIdx.x; n<ph.in.nmu; n+=blockDim.x) nodes[n] = ph.in.mu[n];
+            mu_s = nodes;
+        }
+        sv = stage_spectral<F>(bgin.sp, bgin.in, a.nbnd, a.band_lims_gpt, phase_lds, bg);          // (it ends with the barrier)
+    }
+    else if constexpr (TABLE || BG)
     {
         extern __shared__ double phase_lds[];
         F* stage = reinterpret_cast<F*>(phase_lds);
@@ -163,17 +199,27 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
     const F kdx = F(rx)*a.dx, kdy = F(ry)*a.dy, kdz = F(rz)*a.dz;
     const F len_x = F(a.knx)*kdx, len_y = F(a.kny)*kdy, z_top = F(a.knz)*kdz;
     const int npix = a.npx*a.npy;
-    const int ibnd = a.cld_tau != nullptr ? band_of(a.igpt, a.nbnd, a.band_lims_gpt) : -1;
-    const F* __restrict__ tau_g = a.tau + ncol*nz*a.igpt;
-    const F* __restrict__ ssa_g = a.ssa + ncol*nz*a.igpt;
-    const F* __restrict__ ctau_b = ibnd >= 0 ? a.cld_tau + ncol*nz*ibnd : nullptr;
-    if constexpr (TABLE) tab = table_of_band(ph.in, ibnd);
+    // (what follows of the g-point is fixed for the launch, or under SPECTRAL derived from the lane's igpt by of_gpt below)
+    [[maybe_unused]] int igpt = SPECTRAL ? 0 : a.igpt;
+    int ibnd = -1;
+    const F* __restrict__ tau_g = a.tau;
+    const F* __restrict__ ssa_g = a.ssa;
+    const F* __restrict__ ctau_b = nullptr;
+    [[maybe_unused]] const F* __restrict__ kn_g = a.k_null;
     [[maybe_unused]] int ibnd_a = -1;
     [[maybe_unused]] const F* __restrict__ atau_b = nullptr;
-    if constexpr (AER)
+    if constexpr (!SPECTRAL)
     {
-        ibnd_a = bgin.aer.tau != nullptr ? band_of(a.igpt, a.nbnd, a.band_lims_gpt) : -1;
-        atau_b = ibnd_a >= 0 ? bgin.aer.tau + ncol*nz*ibnd_a : nullptr;
+        ibnd = a.cld_tau != nullptr ? band_of(a.igpt, a.nbnd, a.band_lims_gpt) : -1;
+        tau_g = a.tau + ncol*nz*a.igpt;
+        ssa_g = a.ssa + ncol*nz*a.igpt;
+        ctau_b = ibnd >= 0 ? a.cld_tau + ncol*nz*ibnd : nullptr;
+        if constexpr (TABLE) tab = table_of_band(ph.in, ibnd);
+        if constexpr (AER)
+        {
+            ibnd_a = bgin.aer.tau != nullptr ? band_of(a.igpt, a.nbnd, a.band_lims_gpt) : -1;
+            atau_b = ibnd_a >= 0 ? bgin.aer.tau + ncol*nz*ibnd_a : nullptr;
+        }
     }
     const F inf = F(INFINITY);
     [[maybe_unused]] const F g_max = F(1.) - Lim<F>::eps();
@@ -183,7 +229,40 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
     const F dtx = vx != F(0.) ? a.dx/fabs(vx) : inf, dty = vy != F(0.) ? a.dy/fabs(vy) : inf, dtz = a.dz/vz;
     // the top of the medium, and the slant optical path of the whole background
     [[maybe_unused]] F z_toa = z_top, tau_bg_sun = F(0.);
-    if constexpr (BG) { if (bg.nbg > 0) { z_toa = bg.z[bg.nbg]; tau_bg_sun = bg.tau_above[bg.nbg]/a.mu0; } }
+    if constexpr (SPECTRAL) { if (bg.nbg > 0) z_toa = bg.z[bg.nbg]; }          // (tau_bg_sun is the g-point's: formed where its walk ends)
+    else if constexpr (BG) { if (bg.nbg > 0) { z_toa = bg.z[bg.nbg]; tau_bg_sun = bg.tau_above[bg.nbg]/a.mu0; } }
+    // SPECTRAL: what a pass reads of the lane's g-point, derived again in every pass
+    [[maybe_unused]] const auto of_gpt = [&]() {
+        if constexpr (SPECTRAL)
+        {
+            const int band = sv.band[igpt];
+            ibnd = a.cld_tau != nullptr ? band : -1;
+            ibnd_a = bgin.aer.tau != nullptr ? band : -1;
+            tau_g = a.tau + ncol*nz*igpt;
+            ssa_g = a.ssa + ncol*nz*igpt;
+            ctau_b = ibnd >= 0 ? a.cld_tau + ncol*nz*ibnd : nullptr;
+            atau_b = ibnd_a >= 0 ? bgin.aer.tau + ncol*nz*ibnd_a : nullptr;
+            kn_g = a.k_null + (size_t(a.knx)*a.kny*a.knz)*size_t(igpt - bgin.sp.kn_g0);
+            if constexpr (TABLE) tab = table_of_band(ph.in, ibnd);
+            // (unconditional, like every line here: a value kept from the pass before would be carried around the loop, which cost 30 - 38
+            // VGPRs; with nbg = 0 the rows are not read)
+            bg_rows_of_gpt<F, BG_ROWS_AER>(bg, bgin.in.profile, igpt);
+        }
+    };
+    // a deposit d of the lane's ray: clamped at 2^20 (after the g-point's weight under SPECTRAL) and tallied into its pixel
+    const auto deposit = [&](F d, const int pix) {
+        size_t slot = size_t(pix);
+        if constexpr (SPECTRAL)
+        {
+            const int band = sv.band[igpt];
+            if (band < 0) return;
+            d = d*bgin.sp.weight0[igpt];
+            slot += size_t(band)*size_t(npix);
+        }
+        const bool clamped = d > F(1048576.);
+        if (clamped) atomicAdd(a.n_clamped, 1ull);
+        tally(a.counts, slot, to_count(clamped ? F(1048576.) : d));
+    };
 
     Stream rng; rng.k0 = a.k0; rng.k1 = a.k1; rng.used = 4; rng.block = 0u; rng.c0 = rng.c1 = rng.c2 = 0u;
     bool alive = false, pending = false, walking = false;
@@ -200,6 +279,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
         if (walking)
         {
             // ---- one cell of the walk to the sun
+            of_gpt();
             const F tn = min(w.tz, min(w.tx, w.ty));
             const int axis = (w.tz <= w.tx && w.tz <= w.ty) ? 2 : (w.tx <= w.ty ? 0 : 1);
             const int lay = a.top_at_1 ? nz-1-w.k : w.k;
@@ -222,12 +302,11 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
             ++w.steps;
             if (w.k == nz)
             {
+                if constexpr (SPECTRAL) tau_bg_sun = bg.nbg > 0 ? bg.tau_above[bg.nbg]/a.mu0 : F(0.);
                 F d;
                 if constexpr (BG) d = w.dep*exp(-(w.tau + tau_bg_sun));
                 else d = w.dep*exp(-w.tau);
-                const bool clamped = d > F(1048576.);
-                if (clamped) atomicAdd(a.n_clamped, 1ull);
-                tally(a.counts, size_t(pix), to_count(clamped ? F(1048576.) : d));
+                deposit(d, pix);
                 walking = false;
                 if (w.then == 0) { alive = after_surface(rng, weight, ux, uy, uz); pending = false; }
                 else if (AER && w.then == 3) scatter_direction(rng, true, w.gc, g_max, ux, uy, uz);
@@ -245,9 +324,15 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
                 if (!alive)
                 {
                     if (next_ray >= a.nrays) { done = true; break; }          // the list is finite, every ray ends within max_events events and every walk is bounded
-                    const u64 r = a.ray0 + u64(next_ray);
+                    u64 r = a.ray0 + u64(next_ray);
                     next_ray += nthreads;
-                    rng.start(r, unsigned(a.igpt) | 0x80000000u);
+                    if constexpr (SPECTRAL)
+                    {
+                        igpt = gpt_of_photon(sv.photon_end, sv.ngpt, (long long)r);
+                        if (igpt >= sv.ngpt) { igpt = 0; break; }          // (beyond the list)
+                        r = r - u64(sv.photon_end[igpt]);
+                    }
+                    rng.start(r, unsigned(igpt) | 0x80000000u);
                     pix = int(r % u64(npix));
                     const int ipx = pix % a.npx, ipy = pix / a.npx;
                     const F fa = (F(ipx) + rng.next<F>()) / F(a.npx);
@@ -310,6 +395,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
                 }
                 if (nev >= a.max_events) { atomicAdd(a.n_capped, 1ull); alive = false; break; }
                 ++nev;
+                of_gpt();
 
                 // in_bg: the ray is in background layer kn - knz, a block with z faces only whose k_null is its own k_ext
                 [[maybe_unused]] bool in_bg = false;
@@ -323,8 +409,8 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
                 const F d_max = min(sz, min(sx, sy));
                 const int axis = (sz <= sx && sz <= sy) ? 2 : (sx <= sy ? 0 : 1);
                 F kn_val;
-                if constexpr (BG) kn_val = in_bg ? bg.k_ext[kn - a.knz] : a.k_null[in + a.knx*(jn + a.kny*min(kn, a.knz - 1))];
-                else kn_val = a.k_null[in + a.knx*(jn + a.kny*kn)];
+                if constexpr (BG) kn_val = in_bg ? bg.k_ext[kn - a.knz] : kn_g[in + a.knx*(jn + a.kny*min(kn, a.knz - 1))];
+                else kn_val = kn_g[in + a.knx*(jn + a.kny*kn)];
                 if (!pending) tau = -log(rng.next<F>());
                 pending = false;
                 const bool empty = !(kn_val > F(0.));
@@ -473,10 +559,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
                                 }
                                 else phase = F(0.75)*(F(1.) + cs*cs);
                                 const F dep = (weight*phase)/(F(4.)*pi);
-                                const F d = dep*exp(-((k_ext*(z_hi - z) + bg.tau_above[cell])/a.mu0));
-                                const bool clamped = d > F(1048576.);
-                                if (clamped) atomicAdd(a.n_clamped, 1ull);
-                                tally(a.counts, size_t(pix), to_count(clamped ? F(1048576.) : d));
+                                deposit(dep*exp(-((k_ext*(z_hi - z) + bg.tau_above[cell])/a.mu0)), pix);
                                 scatter_direction(rng, cloud || aerosol, gc, g_max, ux, uy, uz);
                             }
                         }
@@ -569,11 +652,15 @@ BwArgs<F> scene_args(const Medium<F>& m, const Sun<F>& sun, const Sensor<F>& sen
 
 // form: which instantiation runs; b is read in the forms with a background (its aerosol triple in FORM_AER, whose profile has
 // BG_ROWS_AER rows)
+// FORM_SPECTRAL: a.ray0 / a.nrays are a range of the concatenated list sp.photon_end, a.k_null holds the slices from g-point sp.kn_g0 on
+// and b.in.profile is the profile of all g-points
 template<typename F>
-void launch_trace_bw(const BwArgs<F>& a, const PhaseIn<F>& ph, hipStream_t st, const Form form, const BgArgs<F,true,true>& b)
+void launch_trace_bw(const BwArgs<F>& a, const PhaseIn<F>& ph, hipStream_t st, const Form form, const BgArgs<F,true,true>& b,
+                     const SpecIn<F>& sp = SpecIn<F>{})
 {
     const int blocks = int(std::min<long long>((a.nrays + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
-    const size_t lds = (ph.given() ? size_t(ph.nmu)*sizeof(F) : 0)
+    const size_t lds = form == FORM_SPECTRAL ? bw_spectral_lds_bytes(sp.ngpt, b.in.nbg, ph.given() ? ph.nmu : 0, sizeof(F))
+                     : (ph.given() ? size_t(ph.nmu)*sizeof(F) : 0)
                      + (form == FORM_GRID ? 0 : bg_lds_numbers(b.in.nbg, form == FORM_AER ? BG_ROWS_AER : BG_ROWS)*sizeof(F));
     const BgArgs<F,true> bg{b.in};
     switch (2*form + (ph.given() ? 1 : 0))
@@ -583,6 +670,10 @@ void launch_trace_bw(const BwArgs<F>& a, const PhaseIn<F>& ph, hipStream_t st, c
         case 2*FORM_BG + 1: trace_bw_kernel<F,true,true,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, bg); break;
         case 2*FORM_BG: trace_bw_kernel<F,false,true,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, bg); break;
         case 2*FORM_GRID + 1: trace_bw_kernel<F,true,false,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, BgArgs<F,false>{}); break;
+        case 2*FORM_SPECTRAL + 1:
+            trace_bw_kernel<F,true,true,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,true>{ph}, BwSpecArgs<F>{b.in, b.aer, sp}); break;
+        case 2*FORM_SPECTRAL:
+            trace_bw_kernel<F,false,true,true,true><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, BwSpecArgs<F>{b.in, b.aer, sp}); break;
         default: trace_bw_kernel<F,false,false,false><<<blocks, RT_BLOCK, lds, st>>>(a, PhaseArgs<F,false>{}, BgArgs<F,false>{});
     }
 }
@@ -614,12 +705,14 @@ template<> struct ForwardEntries<double>
     static constexpr auto k_null = rrx_rt_k_null_f64; static constexpr auto k_null_aer = rrx_rt_k_null_aer_f64;
     static constexpr auto bg_profile = rrx_rt_bg_profile_f64; static constexpr auto bg_profile_aer = rrx_rt_bg_profile_aer_f64;
     static constexpr auto counts_to_flux = rrx_rt_counts_to_flux_f64;
+    static constexpr auto k_null_all = rrx_rt_k_null_all_f64; static constexpr auto bg_profile_all = rrx_rt_bg_profile_all_f64;
 };
 template<> struct ForwardEntries<float>
 {
     static constexpr auto k_null = rrx_rt_k_null_f32; static constexpr auto k_null_aer = rrx_rt_k_null_aer_f32;
     static constexpr auto bg_profile = rrx_rt_bg_profile_f32; static constexpr auto bg_profile_aer = rrx_rt_bg_profile_aer_f32;
     static constexpr auto counts_to_flux = rrx_rt_counts_to_flux_f32;
+    static constexpr auto k_null_all = rrx_rt_k_null_all_f32; static constexpr auto bg_profile_all = rrx_rt_bg_profile_all_f32;
 };
 inline void forward(const int status) { if (status != 0) throw std::runtime_error(rrx_last_error()); }
 
@@ -676,6 +769,165 @@ int raytracer_bw_entry(const char* entry, const Medium<F>& m, const Sun<F>& sun,
     }
     RRX_CATCH(entry)
 }
+
+// ---- the camera's spectral form: rays of all g-points in one launch, counts by band, bands to channels
+
+// out[c, pix] = scale sum_b M[c, b] (counts[b, pix] 2^-32), the sum in band order in F: one thread per pixel and channel
+template<typename F>
+__global__ void channels_kernel(const size_t npix, const int nbnd, const int nchan, const u64* __restrict__ counts, const F* __restrict__ M,
+                                const F scale, F* __restrict__ out)
+{
+    const size_t i = size_t(blockIdx.x)*blockDim.x + threadIdx.x;
+    if (i >= npix*size_t(nchan)) return;
+    const size_t c = i / npix, pix = i - c*npix;
+    F sum = F(0.);
+    for (int b=0; b<nbnd; ++b) sum = sum + M[c*nbnd + b]*F(double(counts[size_t(b)*npix + pix]) * 2.3283064365386963e-10);
+    out[i] = scale*sum;
+}
+
+template<typename F>
+void launch_channels(const size_t npix, const int nbnd, const int nchan, const u64* counts, const F* M, const F scale, F* out, hipStream_t st)
+{
+    channels_kernel<F><<<unsigned(ceil_div((long long)(npix*size_t(nchan)), 256)), 256, 0, st>>>(npix, nbnd, nchan, counts, M, scale, out);
+}
+
+inline void check_channels(const int nbnd, const int nchan)
+{
+    if (nbnd < 1) throw std::runtime_error("nbnd must be >= 1: the counts are kept by band");
+    if (nchan < 1) throw std::runtime_error("nchan must be >= 1");
+}
+
+// rrx_camera_channels
+template<typename F>
+int camera_channels_entry(const char* entry, const long long npix, const int nbnd, const int nchan, const u64* counts, const F* chan_weights,
+                          const F scale, F* out, void* stream)
+{
+    RRX_TRY
+    if (check_extents({{"npix", npix}})) return 0;
+    check_channels(nbnd, nchan);
+    if (npix > 0x7FFFFFFFll) throw std::runtime_error("npix exceeds 2^31 - 1");
+    if ((long long)nchan > (0x7FFFFFFFll << 8) / npix) throw std::runtime_error("nchan npix exceeds 2^39: one thread per pixel and channel");
+    check_needed({{"counts", counts}, {"chan_weights", chan_weights}, {"out", out}});
+    launch_channels<F>(size_t(npix), nbnd, nchan, counts, chan_weights, scale, out, static_cast<hipStream_t>(stream));
+    RRX_CATCH(entry)
+}
+
+// rrx_camera_trace_counts_spectral: sp.photon_end (the ray list's prefix sums) and sp.weight0 are device arrays that the entry cannot
+// look into. The kernel stays inside its arrays whatever they hold (the search is bounded by ngpt, a ray beyond the list is stepped over,
+// the pixel is taken modulo npix); the callers that form the list on the host refuse one that does not ascend. k_null and bg.profile
+// are those of all g-points.
+template<typename F>
+int camera_trace_entry(const char* entry, const Medium<F>& m, const Sun<F>& sun, const PhaseIn<F>& ph, const Background<F>& bg, const Run& run,
+                       const Sensor<F>& sensor, const SpecIn<F>& sp, const F* k_null, const long long ray0, const long long nrays,
+                       u64* counts, u64* n_capped, u64* n_clamped)
+{
+    RRX_TRY
+    int max_walk = 0;
+    if (check_backward(m, sun, ph, bg, run.max_events, sensor, {"nrays", nrays},
+                       {{"band_lims_gpt", m.band_lims_gpt}, {"ray_end", sp.photon_end}, {"weight0", sp.weight0}, {"k_null", k_null}, {"sensor", sensor.s}},
+                       {{"counts", counts}, {"n_capped", n_capped}, {"n_clamped", n_clamped}}, max_walk,
+                       [&] { check_spectral_ngpt(m.ngpt);
+                             if (m.nbnd < 1) throw std::runtime_error("nbnd must be >= 1: the counts are kept by band");
+                             if (ray0 < 0) throw std::runtime_error("ray0 is negative"); }, nothing, nothing))
+        return 0;
+    const BgArgs<F,true,true> b{background_of(bg, m, nothing), m.aer};
+    launch_trace_bw<F>(scene_args<F>(m, sun, sensor, 0, k_null, run.seed, u64(ray0), nrays, run.max_events, max_walk, counts, n_capped, n_clamped),
+                       ph, static_cast<hipStream_t>(run.stream), FORM_SPECTRAL, b, sp);
+    RRX_CATCH(entry)
+}
+
+// rrx_camera_render_spectral: m_gpt[g] rays per pixel of g-point g (a host array). One trace launch per chunk of consecutive g-points,
+// the counts of all chunks added in integers by band and converted once, with the common unit U = S/P over mu0, through the channel
+// matrix. THE WORKSPACE, in u64 words: | counts (nbnd, npix) | k_null of a chunk | the profile of all g-points | ray_end | weight0 |
+// the channel matrix |
+template<typename F>
+int camera_render_entry(const char* entry, const Medium<F>& m, const Sun<F>& sun, const PhaseIn<F>& ph, const Background<F>& bg, const Run& run,
+                        const Sensor<F>& sensor, const F* inc_dir, const long long* m_gpt, const int nchan, const F* chan_weights,
+                        F* radiance, u64* n_capped, u64* n_clamped)
+{
+    RRX_TRY
+    typedef ForwardEntries<F> Fw;
+    int max_walk = 0;
+    const long long npix_ll = (long long)sensor.npx*sensor.npy;
+    std::vector<long long> ray_end;
+    long long P = 0;
+    F S = F(0.);
+    if (check_backward(m, sun, ph, bg, run.max_events, sensor, {"ngpt", m.ngpt},
+                       {{"band_lims_gpt", m.band_lims_gpt}, {"inc_dir", inc_dir}, {"rays_per_pixel_gpt", m_gpt}, {"chan_weights", chan_weights},
+                        {"sensor", sensor.s}},
+                       {{"radiance", radiance}, {"n_capped", n_capped}, {"n_clamped", n_clamped}}, max_walk,
+                       [&] { check_spectral_ngpt(m.ngpt); check_channels(m.nbnd, nchan); }, nothing,
+                       [&] {
+                           if (npix_ll > 0x7FFFFFFFll) throw std::runtime_error("npx npy exceeds 2^31 - 1");
+                           ray_end.assign(size_t(m.ngpt) + 1, 0);
+                           for (int g=0; g<m.ngpt; ++g)
+                           {
+                               if (inc_dir[g] < F(0.)) throw std::runtime_error("inc_dir must be >= 0");
+                               if (m_gpt[g] < 0) throw std::runtime_error("rays_per_pixel_gpt is negative at g-point " + std::to_string(g));
+                               if (m_gpt[g] > 0 && !(inc_dir[g] > F(0.)))
+                                   throw std::runtime_error("rays_per_pixel_gpt is > 0 at g-point " + std::to_string(g) + ", which has no incident flux");
+                               if (m_gpt[g] > (0x7FFFFFFFFFFFFFFFll - ray_end[g]) / npix_ll) throw std::runtime_error("the ray list exceeds 2^63 - 1");
+                               ray_end[g+1] = ray_end[g] + m_gpt[g]*npix_ll;
+                               P += m_gpt[g];
+                               if (m_gpt[g] > 0) S = S + inc_dir[g];
+                           }
+                       }))
+        return 0;
+    const LoopBg<F> lb = loop_background(bg, m, nothing);
+
+    hipStream_t st = static_cast<hipStream_t>(run.stream);
+    const size_t npix = size_t(npix_ll), nkn = size_t(m.knx)*m.kny*m.knz, n_counts = size_t(m.nbnd)*npix;
+    const int chunk = spectral_gpt_per_launch(nkn*sizeof(F), m.ngpt);
+    bool ok = hipMemsetAsync(n_capped, 0, sizeof(u64), st) == hipSuccess;
+    ok = ok && hipMemsetAsync(n_clamped, 0, sizeof(u64), st) == hipSuccess;
+    ok = ok && hipMemsetAsync(radiance, 0, size_t(nchan)*npix*sizeof(F), st) == hipSuccess;
+    if (!ok) throw std::runtime_error("zeroing the outputs failed");
+    if (P == 0) return 0;
+    const F U = S / F(P);
+    std::vector<F> weight0(m.ngpt, F(0.));
+    for (int g=0; g<m.ngpt; ++g)
+        if (m_gpt[g] > 0) weight0[g] = (inc_dir[g] / F(m_gpt[g])) / U;
+
+    const size_t n_kn = words_of(nkn*size_t(chunk)*sizeof(F));
+    const size_t n_prof = lb.on ? words_of(size_t(m.ngpt)*BG_ROWS_AER*(lb.nbg + 1)*sizeof(F)) : 0;
+    const size_t n_re = size_t(m.ngpt) + 1, n_w = words_of(size_t(m.ngpt)*sizeof(F)), n_cw = words_of(size_t(nchan)*m.nbnd*sizeof(F));
+    WorkspaceLease lease(st);
+    u64* counts = lease.get<u64>(n_counts + n_kn + n_prof + n_re + n_w + n_cw);
+    F* k_null = reinterpret_cast<F*>(counts + n_counts);
+    F* profile = reinterpret_cast<F*>(counts + n_counts + n_kn);
+    long long* ray_end_d = reinterpret_cast<long long*>(counts + n_counts + n_kn + n_prof);
+    F* weight0_d = reinterpret_cast<F*>(counts + n_counts + n_kn + n_prof + n_re);
+    F* chan_d = reinterpret_cast<F*>(counts + n_counts + n_kn + n_prof + n_re + n_w);
+    ok = hipMemsetAsync(counts, 0, n_counts*sizeof(u64), st) == hipSuccess
+      && hipMemcpyAsync(ray_end_d, ray_end.data(), ray_end.size()*sizeof(long long), hipMemcpyHostToDevice, st) == hipSuccess
+      && hipMemcpyAsync(weight0_d, weight0.data(), size_t(m.ngpt)*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess
+      && hipMemcpyAsync(chan_d, chan_weights, size_t(nchan)*m.nbnd*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess
+      && hipStreamSynchronize(st) == hipSuccess;          // (the host arrays end with this call)
+    if (!ok) throw std::runtime_error("zeroing the counts or copying the ray list failed");
+    if (lb.on)
+        forward(Fw::bg_profile_all(bg.nbg, m.ngpt, m.nbnd, bg.dz_bg, bg.tau, bg.ssa, m.band_lims_gpt, bg.cld_tau, bg.cld_ssa, bg.cld_g, profile,
+                                   lb.aer.tau, lb.aer.ssa, lb.aer.g, run.stream));
+    const BgArgs<F,true,true> b{BgIn<F>{lb.nbg, profile, lb.lev}, m.aer};
+    for (int g0=0; g0<m.ngpt; g0+=chunk)
+    {
+        const int g1 = std::min(g0 + chunk, m.ngpt);
+        const long long n = ray_end[g1] - ray_end[g0];
+        if (n == 0) continue;
+        // k_null of the chunk's g-points: rrx_rt_k_null_all when the chunk is the whole list, otherwise slice by slice (the same bits)
+        if (chunk == m.ngpt)
+            forward(Fw::k_null_all(m.nx, m.ny, m.nz, m.ngpt, m.nbnd, m.top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, m.dz, m.knx, m.kny, m.knz,
+                                   k_null, m.aer.tau, run.stream));
+        else
+            for (int g=g0; g<g1; ++g)
+                if (ray_end[g+1] > ray_end[g])
+                    forward(Fw::k_null_aer(m.nx, m.ny, m.nz, m.ngpt, m.nbnd, g, m.top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, m.dz, m.knx, m.kny,
+                                           m.knz, k_null + nkn*size_t(g - g0), m.aer.tau, run.stream));
+        launch_trace_bw<F>(scene_args<F>(m, sun, sensor, 0, k_null, run.seed, u64(ray_end[g0]), n, run.max_events, max_walk, counts, n_capped, n_clamped),
+                           ph, st, FORM_SPECTRAL, b, SpecIn<F>{m.ngpt, g0, ray_end_d, weight0_d, nullptr});
+    }
+    launch_channels<F>(npix, m.nbnd, nchan, counts, chan_d, U / sun.mu0, radiance, st);
+    RRX_CATCH(entry)
+}
 }  // namespace
 
 // ---- the C entries: each builds the structs and calls its family's one function
@@ -719,4 +971,29 @@ int rrx_raytracer_bw_aer##SFX(RT_P_BW_LOOP(F), RT_P_PHASE(F), RT_P_BG(F), \
 
 RRX_DEFINE_RT_BW(double, _f64)
 RRX_DEFINE_RT_BW(float, _f32)
+
+// The camera's spectral form. The prefix is rrx_camera_: the set of rrx_rt_ / rrx_raytracer_ symbols is closed.
+#define RRX_DEFINE_CAMERA(F, SFX) \
+int rrx_camera_trace_counts_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RT_P_GRID(F), \
+        const long long* ray_end, const F* weight0, int knx, int kny, int knz, const F* k_null, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
+        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, \
+        RT_P_PHASE(F), int nbg, const F* dz_bg, const F* bg_profile, const F* aer_tau, const F* aer_ssa, const F* aer_g, void* stream) \
+{ const AerIn<F> aer{aer_tau, aer_ssa, aer_g}; \
+  return camera_trace_entry<F>("rrx_camera_trace_counts_spectral" #SFX, RT_MEDIUM(F, 0, aer), RT_SUN(F), RT_PHASE(F), RT_BG_PROFILE(F, FORM_AER), \
+                               RT_RUN, RT_SENSOR(F), SpecIn<F>{ngpt, 0, ray_end, weight0, nullptr}, k_null, ray0, nrays, counts, n_capped, n_clamped); } \
+int rrx_camera_channels##SFX(long long npix, int nbnd, int nchan, const unsigned long long* counts, const F* chan_weights, F scale, F* out, \
+        void* stream) \
+{ return camera_channels_entry<F>("rrx_camera_channels" #SFX, npix, nbnd, nchan, counts, chan_weights, scale, out, stream); } \
+int rrx_camera_render_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, RT_P_GRID(F), const F* inc_dir, \
+        int knx, int kny, int knz, int sensor_type, int npx, int npy, F fov, const F* sensor, const long long* rays_per_pixel_gpt, \
+        unsigned long long seed, int max_events, int nchan, const F* chan_weights, \
+        F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, RT_P_PHASE(F), RT_P_BG(F), \
+        const F* aer_tau, const F* aer_ssa, const F* aer_g, const F* bg_aer_tau, const F* bg_aer_ssa, const F* bg_aer_g, void* stream) \
+{ const AerIn<F> aer{aer_tau, aer_ssa, aer_g}, bg_aer{bg_aer_tau, bg_aer_ssa, bg_aer_g}; \
+  return camera_render_entry<F>("rrx_camera_render_spectral" #SFX, RT_MEDIUM(F, 0, aer), RT_SUN(F), RT_PHASE(F), RT_BG_MEDIUM(F, FORM_AER, bg_aer), \
+                                RT_RUN, RT_SENSOR(F), inc_dir, rays_per_pixel_gpt, nchan, chan_weights, radiance, n_capped, n_clamped); }
+
+RRX_DEFINE_CAMERA(double, _f64)
+RRX_DEFINE_CAMERA(float, _f32)
 }

@@ -30,8 +30,9 @@ template<typename F> struct Sun { F mu0, azimuth; };
 struct Run { u64 seed; int max_events; void* stream; };
 
 // The generation of an entry, which is also the kernel form it asks for: the plain and _phase entries have no background argument
-// (the instantiations without the BG flag), the _bg entries no aerosol argument, the _aer and _spectral entries both.
-enum Form { FORM_GRID = 0, FORM_BG = 1, FORM_AER = 2 };
+// (the instantiations without the BG flag), the _bg entries no aerosol argument, the _aer and _spectral entries both. FORM_SPECTRAL
+// is a launcher's alone (launch_trace_bw): an entry of the spectral form is checked as FORM_AER, on which the form is built.
+enum Form { FORM_GRID = 0, FORM_BG = 1, FORM_AER = 2, FORM_SPECTRAL = 3 };
 
 // The optional background. profile: the single-g-point entries, what rrx_rt_bg_profile* wrote; the medium (tau .. aer): the loops.
 // With nbg = 0 nothing but nbg is read.
@@ -160,6 +161,21 @@ void set_medium(Args& a, const Medium<F>& m, const int igpt, const F* k_null, co
     a.tau = m.tau; a.ssa = m.ssa; a.band_lims_gpt = m.band_lims_gpt; a.cld_tau = m.cld_tau; a.cld_ssa = m.cld_ssa; a.cld_g = m.cld_g;
     a.dx = m.dx; a.dy = m.dy; a.dz = m.dz; a.sfc_albedo = m.sfc_albedo; a.knx = m.knx; a.kny = m.kny; a.knz = m.knz; a.k_null = k_null;
     a.max_events = max_events;
+}
+
+// ---- all g-points in one launch
+inline void check_spectral_ngpt(const int ngpt)
+{
+    if (ngpt > RT_SPECTRAL_MAX_GPT) throw std::runtime_error("ngpt must be <= 1024 in the spectral form");
+}
+
+// g-points per trace launch of rrx_raytracer_sw_spectral and rrx_camera_render_spectral: the largest chunk whose k_null fits 1 GiB, or
+// RRX_RT_SPECTRAL_GPT_PER_LAUNCH from the environment, read at every call. The result does not depend on it.
+inline int spectral_gpt_per_launch(const size_t k_null_bytes_per_gpt, const int ngpt)
+{
+    if (const char* e = std::getenv("RRX_RT_SPECTRAL_GPT_PER_LAUNCH")) { const int n = std::atoi(e); if (n >= 1) return std::min(n, ngpt); }
+    const size_t fit = (size_t(1) << 30) / std::max<size_t>(k_null_bytes_per_gpt, 1);
+    return int(std::min<size_t>(std::max<size_t>(fit, 1), size_t(ngpt)));
 }
 
 inline size_t words_of(const size_t bytes) { return (bytes + sizeof(u64) - 1) / sizeof(u64); }

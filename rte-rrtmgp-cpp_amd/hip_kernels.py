@@ -985,6 +985,79 @@ class HipKernels:
                                                 *kn, *sensor, rays_per_pixel, *self._rt_run(seed, max_events)),
                                 (*table, *medium, *((*aer_grid, *aer_bg) if aer else ())))
 
+    # The backward tracer with the rays of all g-points in one launch, counts by band and a channel matrix (rrx_camera_trace_counts_spectral,
+    # rrx_camera_channels, rrx_camera_render_spectral). Built on the aerosol form like the forward entries above; band_lims
+    # is always needed (the counts are kept by band). ngpt <= 1024.
+    def camera_zero_counts(self, nbnd, npix):
+        return {k: torch.zeros(shape, dtype=torch.int64, device=self.device)
+                for k, shape in (("counts", (nbnd, npix)), ("n_capped", (1,)), ("n_clamped", (1,)))}
+
+    def camera_trace_counts_spectral(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, ray_end, weight0, kn_grid, k_null, camera,
+                                     seed, ray0, nrays, band_lims, top_at_1=False, cloud=None, counts=None, max_events=None, phase=None,
+                                     background=None, bg_profile=None, aerosol=None):
+        """Adds the rays [ray0, ray0 + nrays) of the concatenated list into counts (camera_zero_counts; made when None): counts
+        (nbnd, npix), n_capped, n_clamped. ray_end (ngpt+1,) int64 and weight0 (ngpt,): arrays on the host, checked and uploaded here;
+        k_null is rt_k_null_all's and bg_profile rt_bg_profile_all's (made when None)."""
+        if band_lims is None:
+            raise ValueError("raytracer: the camera's spectral form needs band_lims")
+        dims, (_, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        ngpt = dims[3]
+        kn = tuple(int(k) for k in kn_grid)
+        sensor = self._rt_sensor(camera)
+        ray_end = np.ascontiguousarray(np.asarray(ray_end, dtype=np.int64).reshape(-1))
+        weight0 = np.ascontiguousarray(np.asarray(weight0, dtype=self.np_dtype).reshape(-1))
+        if ray_end.size != ngpt + 1 or weight0.size != ngpt:
+            raise ValueError("raytracer: ray_end is (ngpt+1,) and weight0 is (ngpt,)")
+        if ray_end[0] != 0 or np.any(np.diff(ray_end) < 0):
+            raise ValueError("raytracer: ray_end must start at 0 and must not descend")
+        if ray0 + nrays > int(ray_end[-1]):
+            raise ValueError(f"raytracer: the range [{ray0}, {ray0 + nrays}) ends beyond the list of {int(ray_end[-1])} rays")
+        _, _, _, bg_tail, aer_grid = self._rt_trace_background(None, cloud, band_lims, background, bg_profile, aerosol)
+        counts = self.camera_zero_counts(dims[4], sensor[1]*sensor[2]) if counts is None else counts
+        dev = [torch.as_tensor(a, device=self.device) for a in (ray_end, weight0)]
+        entry, table = self._rt_entry("camera_trace_counts", phase, dims, True, spectral=True)
+        seed, max_events = self._rt_run(seed, max_events)
+        self._c(entry, *dims, top_at_1, tau, ssa, band_lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, *dev, *kn, k_null, *sensor,
+                seed, ray0, nrays, max_events, counts["counts"], counts["n_capped"], counts["n_clamped"], *table, *bg_tail, *aer_grid)
+        return counts
+
+    def camera_channels(self, counts, chan_weights, scale, out=None):
+        """out (nchan, npix) = scale x chan_weights (nchan, nbnd) @ (counts (nbnd, npix) 2^-32), the sum in band order"""
+        nbnd, npix = counts.shape
+        M = chan_weights if torch.is_tensor(chan_weights) else self.asarray(np.ascontiguousarray(np.asarray(chan_weights, dtype=self.np_dtype)))
+        if M.dim() != 2 or M.shape[1] != nbnd:
+            raise ValueError(f"raytracer: chan_weights is (nchan, nbnd = {nbnd}), got {tuple(M.shape)}")
+        out = self.empty((M.shape[0], npix)) if out is None else out
+        self._c("camera_channels", npix, nbnd, int(M.shape[0]), counts, M, scale, out)
+        return out
+
+    def camera_render_spectral(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel_gpt, seed,
+                               band_lims, chan_weights, top_at_1=False, cloud=None, max_events=None, phase=None, background=None,
+                               aerosol=None):
+        """raytracer_bw_bg with rays_per_pixel_gpt (ngpt,) rays per pixel of each g-point (pipeline.spectral_allocation deals them by
+        flux) in place of rays_per_pixel, all g-points in one trace launch per chunk, and chan_weights (nchan, nbnd) on the host, the
+        matrix from bands to channels. Returns radiance (nchan, npy, npx) in W m-2 sr-1, n_capped and n_clamped (ints)."""
+        if band_lims is None:
+            raise ValueError("raytracer: the camera's spectral form needs band_lims")
+        dims, (_, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
+        kn = tuple(int(k) for k in kn_grid)
+        inc_dir, = self._rt_per_gpt(dims[3], inc_dir=inc_dir)
+        rays = np.ascontiguousarray(np.asarray(rays_per_pixel_gpt, dtype=np.int64).reshape(-1))
+        if rays.size != dims[3]:
+            raise ValueError("raytracer: rays_per_pixel_gpt is (ngpt,)")
+        M = np.ascontiguousarray(np.asarray(chan_weights, dtype=self.np_dtype))
+        if M.ndim != 2 or M.shape[1] != dims[4]:
+            raise ValueError(f"raytracer: chan_weights is (nchan, nbnd = {dims[4]}), got {M.shape}")
+        _, _, medium, aer_grid, aer_bg = self._rt_loop_background(cloud, band_lims, background, aerosol)
+        sensor = self._rt_sensor(camera)
+        entry, table = self._rt_entry("camera_render", phase, dims, True, spectral=True)
+        radiance = self.empty((M.shape[0], sensor[2], sensor[1]))
+        n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        n_clamped = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        self._c(entry, *dims, top_at_1, tau, ssa, band_lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, *kn, *sensor, rays,
+                *self._rt_run(seed, max_events), int(M.shape[0]), M, radiance, n_capped, n_clamped, *table, *medium, *aer_grid, *aer_bg)
+        return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
+
     def delta_scale_2str_k(self, tau, ssa, g):
         ngpt, nlay, ncol = tau.shape
         self._c("delta_scale_2str_k", ncol, nlay, ngpt, tau, ssa, g)

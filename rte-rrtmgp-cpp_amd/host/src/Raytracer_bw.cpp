@@ -1,4 +1,5 @@
-// Raytracer_bw_gpu: checks the shapes and forwards to rrx_raytracer_bw; a non-zero status becomes std::runtime_error.
+// Raytracer_bw_gpu: checks the shapes and forwards to rrx_raytracer_bw or rrx_camera_render_spectral; a non-zero status becomes
+// std::runtime_error.
 #include "Raytracer_bw.h"
 #include "Raytracer_members.h"
 
@@ -67,6 +68,44 @@ unsigned long long Raytracer_bw_gpu::trace_rays_bw(
         RRX_CALL(rrx_raytracer_bw_phase, RT_BW_LOOP_HEAD, RT_TABLE(p));
     else
         RRX_CALL(rrx_raytracer_bw, RT_BW_LOOP_HEAD);
+    if (n_clamped_out != nullptr) *n_clamped_out = tallies({2});
+    return tallies({1});
+}
+
+unsigned long long Raytracer_bw_gpu::trace_rays_bw_spectral(
+        const int nx, const int ny, const int nz,
+        const Float dx, const Float dy, const Float dz,
+        const bool top_at_1,
+        const Array_gpu<Float,3>& tau, const Array_gpu<Float,3>& ssa,
+        const Array_gpu<int,2>& band_lims_gpt,
+        const Array_gpu<Float,3>& cld_tau, const Array_gpu<Float,3>& cld_ssa, const Array_gpu<Float,3>& cld_g,
+        const Array_gpu<Float,1>& sfc_albedo,
+        const Float mu0, const Float azimuth,
+        const Array<Float,1>& inc_dir,
+        const int knx, const int kny, const int knz,
+        const Sensor_bw& sensor,
+        const Array<long long,1>& rays_per_pixel_gpt, const unsigned long long seed, const int max_events,
+        const Array<Float,2>& chan_weights,
+        Array_gpu<Float,3>& radiance, unsigned long long* n_clamped_out)
+{
+    const std::string who = "Raytracer_bw_gpu::trace_rays_bw_spectral: ";
+    const int nchan = chan_weights.dim(2);
+    if (chan_weights.dim(1) != band_lims_gpt.dim(2) || nchan < 1) throw std::runtime_error(who + "chan_weights is not (nbnd, nchan >= 1)");
+    if (rays_per_pixel_gpt.size() != tau.dim(3)) throw std::runtime_error(who + "rays_per_pixel_gpt is not (ngpt)");
+    if (radiance.dim(3) != nchan) throw std::runtime_error(who + "radiance is not (npx, npy, nchan)");
+    const Rt_members m = RT_MEMBERS;
+    // (the image of one channel has the shape that trace_rays_bw checks)
+    Array_gpu<Float,2> image(radiance.ptr(), {radiance.dim(1), radiance.dim(2)});
+    check_shapes(who, m, nx, ny, nz, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, sfc_albedo, inc_dir, sensor, image);
+    const Rt_pointers p(m, cld_tau, cld_ssa, cld_g);
+    const Float numbers[12] = {sensor.position[0], sensor.position[1], sensor.position[2], sensor.e_w[0], sensor.e_w[1], sensor.e_w[2],
+                               sensor.e_h[0], sensor.e_h[1], sensor.e_h[2], sensor.e_d[0], sensor.e_d[1], sensor.e_d[2]};
+    Array_gpu<unsigned long long,1> tallies({2});
+    RRX_CALL(rrx_camera_render_spectral, nx, ny, nz, tau.dim(3), band_lims_gpt.dim(2), RrxBool(top_at_1), tau.ptr(), ssa.ptr(),
+             band_lims_gpt.ptr(), RT_CLOUD(p), dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), knx, kny, knz,
+             sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers, rays_per_pixel_gpt.ptr(), seed, max_events,
+             nchan, chan_weights.ptr(), radiance.ptr(), tallies.ptr(), tallies.ptr() + 1,
+             RT_TABLE(p), RT_BACKGROUND(p), p.aer[0], p.aer[1], p.aer[2], p.bg_aer[0], p.bg_aer[1], p.bg_aer[2]);
     if (n_clamped_out != nullptr) *n_clamped_out = tallies({2});
     return tallies({1});
 }

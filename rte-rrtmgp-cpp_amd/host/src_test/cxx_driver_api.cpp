@@ -413,11 +413,15 @@ int rrx_cxx_trace_rays_bw_phase(const int nx, const int ny, const int nz, const 
 
 // rrx_cxx_trace_rays_bw_bg: rrx_cxx_trace_rays_bw_phase after Raytracer_bw_gpu::set_background, as rrx_cxx_trace_rays_bg; nbg = 0: no background
 // rrx_cxx_trace_rays_bw_aer: the same after Raytracer_bw_gpu::set_aerosol, as rrx_cxx_trace_rays_aer
-int rrx_cxx_trace_rays_bw_aer(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+}
+
+// what rrx_cxx_trace_rays_bw_aer and rrx_cxx_trace_rays_bw_spectral (rays_per_pixel_gpt given) share
+static int trace_rays_bw_any(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
         const int top_at_1, const Float* tau, const Float* ssa, const int* band_lims_gpt,
         const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
         const Float* inc_dir, const int knx, const int kny, const int knz, const int sensor_type, const int npx, const int npy, const Float fov,
-        const Float* sensor, const long long rays_per_pixel, const unsigned long long seed, const int max_events, Float* radiance,
+        const Float* sensor, const long long rays_per_pixel, const long long* rays_per_pixel_gpt, const int nchan, const Float* chan_weights,
+        const unsigned long long seed, const int max_events, Float* radiance,
         unsigned long long* n_capped, unsigned long long* n_clamped,
         const int nmu, const int nre, const Float re0, const Float dre, const Float* mu, const Float* phase, const Float* cdf, const Float* cld_re,
         const int nbg, const Float* dz_bg, const Float* bg_tau, const Float* bg_ssa, const Float* bg_cld_tau, const Float* bg_cld_ssa,
@@ -456,6 +460,24 @@ int rrx_cxx_trace_rays_bw_aer(const int nx, const int ny, const int nz, const in
                 raytracer.set_aerosol(view3(aer_tau, ncol, nz, nbnd), view3(aer_ssa, ncol, nz, nbnd), view3(aer_g, ncol, nz, nbnd),
                                       bview(bg_aer_tau, nb, nbnd), bview(bg_aer_ssa, nb, nbnd), bview(bg_aer_g, nb, nbnd));
             }
+            if (rays_per_pixel_gpt != nullptr)
+            {
+                // the spectral form: m_g from the caller, or (total_rays >= 0) dealt by Raytracer_gpu::spectral_allocation
+                Array<long long,1> h_m({ngpt});
+                for (int g=1; g<=ngpt; ++g) h_m({g}) = rays_per_pixel_gpt[g-1];
+                if (rays_per_pixel >= 0) h_m = Raytracer_gpu::spectral_allocation(h_dir, rays_per_pixel, 1);
+                if (chan_weights == nullptr) throw std::runtime_error("rrx_cxx_trace_rays_bw_spectral: chan_weights is NULL");
+                if (nchan < 1 || nbnd < 1) throw std::runtime_error("rrx_cxx_trace_rays_bw_spectral: nchan and nbnd must be >= 1");
+                Array<Float,2> h_w({nbnd, nchan});
+                for (int c=1; c<=nchan; ++c)
+                    for (int b=1; b<=nbnd; ++b) h_w({b, c}) = chan_weights[(c-1)*nbnd + (b-1)];
+                Array_gpu<Float,3> out3(radiance, {npx, npy, nchan});
+                *n_capped = raytracer.trace_rays_bw_spectral(nx, ny, nz, dx, dy, dz, top_at_1 != 0,
+                        view3(tau, ncol, nz, ngpt), view3(ssa, ncol, nz, ngpt), Array_gpu<int,2>(const_cast<int*>(band_lims_gpt), {2, nbnd}),
+                        view3(cld_tau, ncol, nz, nbnd), view3(cld_ssa, ncol, nz, nbnd), view3(cld_g, ncol, nz, nbnd), view1(sfc_albedo, ncol),
+                        mu0, azimuth, h_dir, knx, kny, knz, s, h_m, seed, max_events, h_w, out3, n_clamped);
+            }
+            else
             *n_capped = raytracer.trace_rays_bw(nx, ny, nz, dx, dy, dz, top_at_1 != 0,
                     view3(tau, ncol, nz, ngpt), view3(ssa, ncol, nz, ngpt), Array_gpu<int,2>(const_cast<int*>(band_lims_gpt), {2, nbnd}),
                     view3(cld_tau, ncol, nz, nbnd), view3(cld_ssa, ncol, nz, nbnd), view3(cld_g, ncol, nz, nbnd), view1(sfc_albedo, ncol),
@@ -464,6 +486,47 @@ int rrx_cxx_trace_rays_bw_aer(const int nx, const int ny, const int nz, const in
         catch (...) { rrx_host::set_stream(before); throw; }
         rrx_host::set_stream(before);
     });
+}
+
+extern "C"
+{
+int rrx_cxx_trace_rays_bw_aer(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,
+        const int top_at_1, const Float* tau, const Float* ssa, const int* band_lims_gpt,
+        const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
+        const Float* inc_dir, const int knx, const int kny, const int knz, const int sensor_type, const int npx, const int npy, const Float fov,
+        const Float* sensor, const long long rays_per_pixel, const unsigned long long seed, const int max_events, Float* radiance,
+        unsigned long long* n_capped, unsigned long long* n_clamped,
+        const int nmu, const int nre, const Float re0, const Float dre, const Float* mu, const Float* phase, const Float* cdf, const Float* cld_re,
+        const int nbg, const Float* dz_bg, const Float* bg_tau, const Float* bg_ssa, const Float* bg_cld_tau, const Float* bg_cld_ssa,
+        const Float* bg_cld_g, const Float* aer_tau, const Float* aer_ssa, const Float* aer_g, const Float* bg_aer_tau, const Float* bg_aer_ssa,
+        const Float* bg_aer_g, void* stream)
+{
+    return trace_rays_bw_any(nx, ny, nz, ngpt, nbnd, dx, dy, dz, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, sfc_albedo, mu0,
+                             azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, rays_per_pixel, nullptr, 0, nullptr, seed,
+                             max_events, radiance, n_capped, n_clamped, nmu, nre, re0, dre, mu, phase, cdf, cld_re, nbg, dz_bg, bg_tau, bg_ssa,
+                             bg_cld_tau, bg_cld_ssa, bg_cld_g, aer_tau, aer_ssa, aer_g, bg_aer_tau, bg_aer_ssa, bg_aer_g, stream);
+}
+
+// rrx_cxx_trace_rays_bw_spectral: the same through Raytracer_bw_gpu::trace_rays_bw_spectral. rays_per_pixel_gpt (ngpt,
+// HOST): the rays per pixel of every g-point when total_rays < 0; otherwise total_rays is dealt by Raytracer_gpu::spectral_allocation
+// over inc_dir and the array's contents are not used. chan_weights (nchan, nbnd) on the HOST; radiance: a device array (nchan, npy, npx).
+int rrx_cxx_trace_rays_bw_spectral(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy,
+        const Float dz, const int top_at_1, const Float* tau, const Float* ssa, const int* band_lims_gpt,
+        const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_albedo, const Float mu0, const Float azimuth,
+        const Float* inc_dir, const int knx, const int kny, const int knz, const int sensor_type, const int npx, const int npy, const Float fov,
+        const Float* sensor, const long long* rays_per_pixel_gpt, const long long total_rays, const unsigned long long seed, const int max_events,
+        const int nchan, const Float* chan_weights, Float* radiance, unsigned long long* n_capped, unsigned long long* n_clamped,
+        const int nmu, const int nre, const Float re0, const Float dre, const Float* mu, const Float* phase, const Float* cdf, const Float* cld_re,
+        const int nbg, const Float* dz_bg, const Float* bg_tau, const Float* bg_ssa, const Float* bg_cld_tau, const Float* bg_cld_ssa,
+        const Float* bg_cld_g, const Float* aer_tau, const Float* aer_ssa, const Float* aer_g, const Float* bg_aer_tau, const Float* bg_aer_ssa,
+        const Float* bg_aer_g, void* stream)
+{
+    if (rays_per_pixel_gpt == nullptr) return guarded([&] { throw std::runtime_error("rrx_cxx_trace_rays_bw_spectral: rays_per_pixel_gpt is NULL"); });
+    return trace_rays_bw_any(nx, ny, nz, ngpt, nbnd, dx, dy, dz, top_at_1, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, sfc_albedo, mu0,
+                             azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, total_rays, rays_per_pixel_gpt, nchan,
+                             chan_weights, seed, max_events, radiance, n_capped, n_clamped, nmu, nre, re0, dre, mu, phase, cdf, cld_re, nbg,
+                             dz_bg, bg_tau, bg_ssa, bg_cld_tau, bg_cld_ssa, bg_cld_g, aer_tau, aer_ssa, aer_g, bg_aer_tau, bg_aer_ssa, bg_aer_g,
+                             stream);
 }
 
 int rrx_cxx_trace_rays_bw_bg(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy, const Float dz,

@@ -310,16 +310,49 @@ def raytrace_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, photons_per_pixel, 
 
 
 def render_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, camera, rays_per_pixel, seed, cloud_lut=None, kn_grid=None,
-              sfc_albedo=None, max_events=None, phase_table=None, n_domain=None, z_lev=None, aerosol_lut=None):
+              sfc_albedo=None, max_events=None, phase_table=None, n_domain=None, z_lev=None, aerosol_lut=None, allocation=None,
+              min_per_gpt=1, channels=None):
     """Shortwave radiances for a virtual camera or a flux sensor from the backward Monte Carlo ray tracer (rrx_raytracer_bw, DESIGN
     4.15): the twin of raytrace_sw, on the same domain, sun, optics and albedo, with the same checks. camera: camera.perspective /
     fisheye / orthographic / flux_sensor. Returns radiance (npy, npx) in W m-2 sr-1 (scattered and reflected sunlight; the sun's
     disk is not imaged), n_capped and n_clamped. phase_table, n_domain, z_lev, aerosol_lut: as in raytrace_sw; with a background the camera may
-    sit inside it, and the orthographic and the downward flux sensor start at clamp(position.z, domain top, TOA)."""
+    sit inside it, and the orthographic and the downward flux sensor start at clamp(position.z, domain top, TOA).
+    allocation="flux" (DESIGN 4.21): rays_per_pixel is the TOTAL over all g-points, dealt by spectral_allocation(inc_dir,
+    rays_per_pixel, min_per_gpt) in proportion to the incident flux; the rays of all g-points are traced in one launch per chunk and
+    tallied by band (rrx_camera_render_spectral, ngpt <= 1024). channels then says what the sensor sees: None, broadband radiance
+    (npy, npx) as without allocation; "bands", radiance by band (nbnd, npy, npx); an array (nchan, nbnd), such as
+    camera.band_weights gives, (nchan, npy, npx). allocation=None: every g-point gets rays_per_pixel, broadband only."""
+    if allocation not in (None, "flux"):
+        raise ValueError(f"render_sw: allocation is None or 'flux', got {allocation!r}")
+    if allocation is None and channels is not None:
+        raise ValueError("render_sw: channels needs allocation='flux' (the per-g-point loop tallies broadband only)")
     if n_domain is not None and kn_grid is None:
         kn_grid = (nx, ny, int(n_domain))
     tau, ssa, cld, sfc_albedo, mu0, inc_dir, kn_grid, aer = _raytracer_inputs("render_sw", be, kd_sw, atm, nx, ny, cloud_lut, kn_grid,
                                                                               sfc_albedo, aerosol_lut)
+    if allocation == "flux":
+        nbnd = int(kd_sw.band_lims_gpt.shape[0])
+        if channels is None:
+            M = np.ones((1, nbnd))
+        elif isinstance(channels, str):
+            if channels != "bands":
+                raise ValueError(f"render_sw: channels is None, 'bands' or an array (nchan, nbnd), got {channels!r}")
+            M = np.eye(nbnd)
+        else:
+            M = np.asarray(channels, dtype=np.float64)
+            if M.ndim != 2 or M.shape[1] != nbnd:
+                raise ValueError(f"render_sw: channels is (nchan, nbnd = {nbnd}), got {M.shape}")
+        m = spectral_allocation(inc_dir, rays_per_pixel, min_per_gpt)
+        background, rel = None, None
+        if n_domain is not None:
+            tau, ssa, cld, rel, background, aer = _raytracer_split("render_sw", be, atm, tau, ssa, cld, n_domain, z_lev, aer)
+        phase = _raytracer_phase("render_sw", atm, cloud_lut, phase_table, rel)
+        r = be.camera_render_spectral(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, m, seed,
+                                      kd_sw.band_lims_gpt, M, top_at_1=atm.top_at_1, cloud=cld, max_events=max_events, phase=phase,
+                                      background=background, aerosol=aer)
+        if channels is None:
+            r["radiance"] = r["radiance"][0]
+        return r
     if n_domain is not None:
         tau, ssa, cld, rel, background, aer = _raytracer_split("render_sw", be, atm, tau, ssa, cld, n_domain, z_lev, aer)
         phase = _raytracer_phase("render_sw", atm, cloud_lut, phase_table, rel)
