@@ -488,7 +488,13 @@ int rrx_lw_solver_noscat_fractions_rescaled##SFX( \
 /* ---- Optical_props_kernels_cuda : include_kernels_cuda/optical_props_kernels_cuda.h:33-56 ---- */ \
 /* Empty problems, for the entries from here to rrx_fill that say so: an extent of 0 returns 0 and writes nothing (no launch is \
    made, so no launch error is left behind); a negative extent returns non-zero. The _bybnd increments: the g-points of no band \
-   (outside every [lo, hi], or of a band with hi < lo) are left as they are; ncol, nlay, ngpt or nbnd = 0: returns 0. */ \
+   (outside every [lo, hi], or of a band with hi < lo) are left as they are; ncol, nlay, ngpt or nbnd = 0: returns 0. \
+   The full g-point increments, rrx_delta_scale_2str_k, rrx_net_broadband_precalc, rrx_get_col_dry, rrx_spread_col, \
+   rrx_scaling_to_subset, rrx_aerosol_optics and the three rrx_cloud_optics_* follow the same rule for every extent they take \
+   (ncol, nlay, nlev, ngpt, nbnd): 0 returns 0 without a launch, a negative one returns 1 with "<entry>: negative extent" in \
+   rrx_last_error(), decided on the host before any launch. rrx_sum_broadband alike for ncol and nlev; its ngpt = 0 with a \
+   non-empty (ncol, nlev) is no empty problem: flux is written, as zeros (ngpt < 0 is refused). rrx_toa_source refuses \
+   ncol <= 0 or ngpt <= 0 ("empty problem"). The floors of the quotients: 3*tiny of F in the increments and in delta scaling. */ \
 int rrx_increment_1scalar_by_1scalar##SFX(int ncol, int nlay, int ngpt, F* tau_inout, const F* tau_in, void* stream); \
 int rrx_increment_2stream_by_2stream##SFX(int ncol, int nlay, int ngpt, F* tau_inout, F* ssa_inout, F* g_inout, const F* tau_in, const F* ssa_in, const F* g_in, void* stream); \
 int rrx_inc_1scalar_by_1scalar_bybnd##SFX(int ncol, int nlay, int ngpt, F* tau_inout, const F* tau_in, int nbnd, const int* band_lims_gpoint, void* stream); \
@@ -535,11 +541,22 @@ int rrx_toa_source##SFX(int ncol, int ngpt, F* toa_src, const F* solar_source, c
    aermr: HOST array of 11 device pointers (aermr01..aermr11), each (ncol,nlay) or, where aermr_per_column[a] == 0, one (nlay) \
    profile shared by all columns (the reference materialises the broadcast, fill_aerosols_3d); aermr_per_column may be NULL \
    (all per column). rh, tau, ssa, g: (ncol,nlay[,nbnd]); plev (ncol,nlay+1); rh_upper (nhum); hydrophobic tables \
-   (nbnd,nphobic), hydrophilic tables (nbnd,nhum,nphilic), band index fastest (Radiation_solver.cu:366-401) */ \
+   (nbnd,nphobic), hydrophilic tables (nbnd,nhum,nphilic), band index fastest (Radiation_solver.cu:366-401). The humidity class of a \
+   cell is the first one whose upper bound is >= rh; above every bound the last class is used (the reference reads past the table). \
+   ssa and g are floored with the machine epsilon of F: a cell with all mixing ratios 0 gives tau = ssa = g = 0. ncol, nlay or \
+   nbnd = 0: returns 0, writes nothing; a negative extent, nhum < 1, nphobic < 11, nphilic < 5 or a NULL mixing ratio: non-zero. */ \
 int rrx_aerosol_optics##SFX(int ncol, int nlay, int nbnd, int nhum, int nphobic, int nphilic, const F* const* aermr, const int* aermr_per_column, \
         const F* rh, const F* plev, const F* rh_upper, const F* mext_phobic, const F* ssa_phobic, const F* g_phobic, \
         const F* mext_philic, const F* ssa_philic, const F* g_philic, F* tau, F* ssa, F* g, void* stream); \
-/* src_cuda/Cloud_optics.cu:31-127,181-329: LUT cloud optics per band; luts are (nsize,nbnd) */ \
+/* src_cuda/Cloud_optics.cu:31-127,181-329: LUT cloud optics per band; luts are (nsize,nbnd), their nodes equidistant from *_lwr to \
+   *_upr. With step = (upr - lwr)/(nsize - 1) and x = (size - lwr)/step, a phase with water path > 0 is interpolated between the \
+   nodes index-1 and index (1-based), index = max(1, min(int(x)+1, nsize-1)): a size outside the table is extrapolated linearly \
+   from the first / last interval and nothing outside the table is read (the reference clamps from above only and reads in front \
+   of the table for x <= -1). NaN or infinite sizes in cloudy cells are outside the contract. A phase with water path <= 0 \
+   contributes exact zeros whatever its size holds; a cell without either phase gives tau = ssa = g = 0 in all three forms. ssa and \
+   g are floored with the machine epsilon of F, the delta step of the _delta form with 3*tiny as rrx_delta_scale_2str_k. \
+   ncol, nlay or nbnd = 0: returns 0, writes nothing. A negative extent, or nsize_liq < 2 or nsize_ice < 2 (no interval; the step \
+   would divide by zero): non-zero, before any launch. */ \
 int rrx_cloud_optics_2str##SFX(int ncol, int nlay, int nbnd, int nsize_liq, int nsize_ice, \
         F radliq_lwr, F radliq_upr, F diamice_lwr, F diamice_upr, \
         const F* lut_extliq, const F* lut_ssaliq, const F* lut_asyliq, \

@@ -106,6 +106,14 @@ inline size_t extent(const std::initializer_list<long long> dims)
     for (const long long d : dims) { if (d < 0) throw std::runtime_error("negative extent"); n *= size_t(d); }
     return n;
 }
+// The cloud entries' checks: a size table of fewer than 2 entries has no interval (and its step (upr - lwr)/(nsize - 1) no value);
+// returns the number of cells, 0 for an empty problem (ncol, nlay or nbnd = 0)
+inline size_t cloud_cells(const int ncol, const int nlay, const int nbnd, const int nsize_liq, const int nsize_ice)
+{
+    if (nsize_liq < 2 || nsize_ice < 2) throw std::runtime_error("cloud size tables need at least 2 entries");
+    const size_t ncl = extent({ncol, nlay});
+    return extent({nbnd}) == 0 ? 0 : ncl;
+}
 #define RRX_GRID_STRIDE(i, n) for (size_t i = size_t(blockIdx.x)*blockDim.x + threadIdx.x; i < (n); i += size_t(gridDim.x)*blockDim.x)
 
 // heating rate of a layer from the net (down - up) broadband flux at its two levels: dT/dt = -(g/cp) d(F_dn - F_up)/dp [K/s]
@@ -346,23 +354,7 @@ __global__ void toa_source_kernel(const int ncol, const int ngpt, F* __restrict_
     for (int icol = blockIdx.x*blockDim.x + threadIdx.x; icol < ncol; icol += gridDim.x*blockDim.x) out[icol + size_t(blockIdx.y)*ncol] = v * fac[icol];
 }
 
-// /root/reference/src/Cloud_optics.cpp:72-107 (and src_cuda/Cloud_optics.cu:31-70)
-template<typename F>
-__device__ __forceinline__ void cloud_from_table(const F cwp, const F re, const int nsteps, const F step_size, const F offset,
-        const F* __restrict__ tau_table, const F* __restrict__ ssa_table, const F* __restrict__ asy_table,
-        F& tau, F& taussa, F& taussag)
-{
-    if (cwp > F(0.))
-    {
-        const int index = min(int((re - offset) / step_size)+1, nsteps-1);
-        const F fint = (re - offset) / step_size - (index-1);
-        tau = cwp * (tau_table[index-1] + fint * (tau_table[index] - tau_table[index-1]));
-        taussa = tau * (ssa_table[index-1] + fint * (ssa_table[index] - ssa_table[index-1]));
-        taussag = taussa * (asy_table[index-1] + fint * (asy_table[index] - asy_table[index-1]));
-    }
-    else { tau = F(0.); taussa = F(0.); taussag = F(0.); }
-}
-
+// /root/reference/src/Cloud_optics.cpp:72-107 (and src_cuda/Cloud_optics.cu:31-70).
 // One thread per (column, layer): water paths and particle sizes are read once, the table position (it depends on the size only) is
 // found once, and the thread walks over the bands (round 4; a thread per (cell, band) re-read the four inputs and redid the two
 // divisions nbnd times). DELTA: delta_scale_2str_k (optical_props_kernels.cu:103-136) applied to the values before they are stored --
@@ -380,10 +372,12 @@ __global__ void cloud_optics_kernel(const size_t ncl, const int nbnd, const int 
     RRX_GRID_STRIDE(i, ncl)
     {
         const F lw = clwp[i], iw = ciwp[i], rl = reliq[i], di = deice[i];
-        // /root/reference/src/Cloud_optics.cpp:72-107: position in the size tables
+        // /root/reference/src/Cloud_optics.cpp:72-107: position in the size tables. The index is clamped at both ends (the reference
+        // clamps from above only and reads in front of the table for a size more than one step below it): outside the table the
+        // first / last interval is extrapolated linearly; no bit changes for x > -1
         int il = 1, ii = 1; F fl = F(0.), fi = F(0.);
-        if (lw > F(0.)) { il = min(int((rl - radliq_lwr) / liq_step)+1, nsize_liq-1); fl = (rl - radliq_lwr) / liq_step - (il-1); }
-        if (iw > F(0.)) { ii = min(int((di - diamice_lwr) / ice_step)+1, nsize_ice-1); fi = (di - diamice_lwr) / ice_step - (ii-1); }
+        if (lw > F(0.)) { il = max(1, min(int((rl - radliq_lwr) / liq_step)+1, nsize_liq-1)); fl = (rl - radliq_lwr) / liq_step - (il-1); }
+        if (iw > F(0.)) { ii = max(1, min(int((di - diamice_lwr) / ice_step)+1, nsize_ice-1)); fi = (di - diamice_lwr) / ice_step - (ii-1); }
         for (int ibnd=0; ibnd<nbnd; ++ibnd)
         {
             F lt = F(0.), lts = F(0.), ltsg = F(0.), it = F(0.), its = F(0.), itsg = F(0.);
@@ -625,10 +619,10 @@ int rrx_subset_nd(void* out, const void* in, int elem_bytes, int ndim, const int
 
 #define RRX_DEFINE_MISC(F, SFX) \
 int rrx_increment_1scalar_by_1scalar##SFX(int ncol, int nlay, int ngpt, F* tau_inout, const F* tau_in, void* stream) \
-{ RRX_TRY const size_t n = size_t(ncol)*nlay*ngpt; \
+{ RRX_TRY const size_t n = extent({ncol, nlay, ngpt}); if (n == 0) return 0; \
   inc_1scl_kernel<F><<<grid1d(n), 256, 0, ST>>>(n, tau_inout, tau_in); RRX_CATCH("rrx_increment_1scalar_by_1scalar") } \
 int rrx_increment_2stream_by_2stream##SFX(int ncol, int nlay, int ngpt, F* tau_inout, F* ssa_inout, F* g_inout, const F* tau_in, const F* ssa_in, const F* g_in, void* stream) \
-{ RRX_TRY const size_t n = size_t(ncol)*nlay*ngpt; \
+{ RRX_TRY const size_t n = extent({ncol, nlay, ngpt}); if (n == 0) return 0; \
   inc_2str_kernel<F><<<grid1d(n), 256, 0, ST>>>(n, rrx::Lim<F>::tiny()*F(3.), tau_inout, ssa_inout, g_inout, tau_in, ssa_in, g_in); RRX_CATCH("rrx_increment_2stream_by_2stream") } \
 int rrx_inc_1scalar_by_1scalar_bybnd##SFX(int ncol, int nlay, int ngpt, F* tau_inout, const F* tau_in, int nbnd, const int* band_lims_gpoint, void* stream) \
 { RRX_TRY const size_t ncl = extent({ncol, nlay}); if (extent({ngpt, nbnd}) == 0 || ncl == 0) return 0; \
@@ -637,13 +631,14 @@ int rrx_inc_2stream_by_2stream_bybnd##SFX(int ncol, int nlay, int ngpt, F* tau_i
 { RRX_TRY const size_t ncl = extent({ncol, nlay}); if (extent({ngpt, nbnd}) == 0 || ncl == 0) return 0; \
   inc_2str_bybnd_kernel<F><<<dim3(std::min(grid1d(ncl), 1024), ngpt), 256, 0, ST>>>(ncl, rrx::Lim<F>::tiny()*F(3.), tau_inout, ssa_inout, g_inout, tau_in, ssa_in, g_in, nbnd, band_lims_gpoint); RRX_CATCH("rrx_inc_2stream_by_2stream_bybnd") } \
 int rrx_delta_scale_2str_k##SFX(int ncol, int nlay, int ngpt, F* tau_inout, F* ssa_inout, F* g_inout, void* stream) \
-{ RRX_TRY const size_t n = size_t(ncol)*nlay*ngpt; \
+{ RRX_TRY const size_t n = extent({ncol, nlay, ngpt}); if (n == 0) return 0; \
   delta_scale_kernel<F><<<grid1d(n), 256, 0, ST>>>(n, rrx::Lim<F>::tiny()*F(3.), tau_inout, ssa_inout, g_inout); RRX_CATCH("rrx_delta_scale_2str_k") } \
 int rrx_sum_broadband##SFX(int ncol, int nlev, int ngpt, const F* gpt_flux, F* flux, void* stream) \
-{ RRX_TRY const size_t n = size_t(ncol)*nlev; \
+{ RRX_TRY const size_t n = extent({ncol, nlev}); (void)extent({ngpt});   /* ngpt = 0 is no empty problem: zeros are written */ \
+  if (n == 0) return 0; \
   sum_broadband_kernel<F><<<grid1d(n), 256, 0, ST>>>(n, ngpt, gpt_flux, flux); RRX_CATCH("rrx_sum_broadband") } \
 int rrx_net_broadband_precalc##SFX(int ncol, int nlev, const F* flux_dn, const F* flux_up, F* flux_net, void* stream) \
-{ RRX_TRY const size_t n = size_t(ncol)*nlev; \
+{ RRX_TRY const size_t n = extent({ncol, nlev}); if (n == 0) return 0; \
   net_kernel<F><<<grid1d(n), 256, 0, ST>>>(n, flux_dn, flux_up, flux_net); RRX_CATCH("rrx_net_broadband_precalc") } \
 int rrx_heating_rate##SFX(int ncol, int nlay, F g_over_cp, const F* flux_net, const F* plev, F* heating_rate, void* stream) \
 { RRX_TRY const size_t n = extent({ncol, nlay}); if (n == 0) return 0; \
@@ -669,14 +664,17 @@ int rrx_fill_gases_all##SFX(int ncol, int nlay, int ngas, const F* const* vmr_in
   GasTable<F> gt; for (int i=0; i<ngas; ++i) { gt.vmr[i] = vmr_in[i]; gt.dim1[i] = dim1[i]; gt.dim2[i] = dim2[i]; } \
   fill_gases_all_kernel<F><<<grid1d(size_t(ncol)*nlay), 256, 0, ST>>>(ncol, nlay, ngas, gt, col_gas, col_dry); RRX_CATCH("rrx_fill_gases_all") } \
 int rrx_get_col_dry##SFX(int ncol, int nlay, const F* vmr_h2o, const F* plev, F* col_dry, void* stream) \
-{ RRX_TRY col_dry_kernel<F><<<grid1d(size_t(ncol)*nlay), 256, 0, ST>>>(ncol, nlay, vmr_h2o, plev, col_dry); RRX_CATCH("rrx_get_col_dry") } \
+{ RRX_TRY const size_t n = extent({ncol, nlay}); if (n == 0) return 0; \
+  col_dry_kernel<F><<<grid1d(n), 256, 0, ST>>>(ncol, nlay, vmr_h2o, plev, col_dry); RRX_CATCH("rrx_get_col_dry") } \
 int rrx_expand_and_transpose##SFX(int ncol, int nbnd, const int* band_lims_gpt, const F* arr_in, F* arr_out, void* stream) \
 { RRX_TRY if (extent({ncol, nbnd}) == 0) return 0; \
   expand_and_transpose_kernel<F><<<dim3(std::min(grid1d(ncol), 1024), nbnd), 256, 0, ST>>>(ncol, nbnd, band_lims_gpt, arr_in, arr_out); RRX_CATCH("rrx_expand_and_transpose") } \
 int rrx_spread_col##SFX(int ncol, int ngpt, F* toa_src, const F* solar_source, void* stream) \
-{ RRX_TRY spread_col_kernel<F><<<dim3(std::min(ceil_div(ncol, 256), 64), ngpt), 256, 0, ST>>>(ncol, ngpt, toa_src, solar_source); RRX_CATCH("rrx_spread_col") } \
+{ RRX_TRY if (extent({ncol, ngpt}) == 0) return 0; \
+  spread_col_kernel<F><<<dim3(std::min(ceil_div(ncol, 256), 64), ngpt), 256, 0, ST>>>(ncol, ngpt, toa_src, solar_source); RRX_CATCH("rrx_spread_col") } \
 int rrx_scaling_to_subset##SFX(int ncol, int ngpt, F* toa_src, const F* tsi_scaling, void* stream) \
-{ RRX_TRY scale_cols_kernel<F><<<dim3(std::min(ceil_div(ncol, 256), 64), ngpt), 256, 0, ST>>>(ncol, ngpt, toa_src, tsi_scaling); RRX_CATCH("rrx_scaling_to_subset") } \
+{ RRX_TRY if (extent({ncol, ngpt}) == 0) return 0; \
+  scale_cols_kernel<F><<<dim3(std::min(ceil_div(ncol, 256), 64), ngpt), 256, 0, ST>>>(ncol, ngpt, toa_src, tsi_scaling); RRX_CATCH("rrx_scaling_to_subset") } \
 int rrx_toa_source##SFX(int ncol, int ngpt, F* toa_src, const F* solar_source, const F* tsi_scaling, void* stream) \
 { RRX_TRY if (ncol <= 0 || ngpt <= 0) throw std::runtime_error("empty problem"); \
   if (tsi_scaling == nullptr) spread_col_kernel<F><<<dim3(std::min(ceil_div(ncol, 256), 64), ngpt), 256, 0, ST>>>(ncol, ngpt, toa_src, solar_source); \
@@ -686,14 +684,15 @@ int rrx_aerosol_optics##SFX(int ncol, int nlay, int nbnd, int nhum, int nphobic,
         const F* mext_philic, const F* ssa_philic, const F* g_philic, F* tau, F* ssa, F* g, void* stream) \
 { RRX_TRY if (nphobic < 11 || nphilic < 5) throw std::runtime_error("aerosol tables need >= 11 hydrophobic and >= 5 hydrophilic species"); \
   if (nhum < 1) throw std::runtime_error("no humidity classes"); \
+  const size_t ncl = extent({ncol, nlay}); if (extent({nbnd}) == 0 || ncl == 0) return 0; \
   AerosolSpecies<F> sp; for (int a=0; a<11; ++a) { if (!aermr[a]) throw std::runtime_error("missing aerosol mixing ratio"); sp.mmr[a] = aermr[a]; sp.per_column[a] = aermr_per_column ? aermr_per_column[a] : 1; } \
-  aerosol_optics_kernel<F><<<grid1d(size_t(ncol)*nlay), 256, 0, ST>>>(ncol, nlay, nbnd, nhum, sp, rh, plev, rh_upper, \
+  aerosol_optics_kernel<F><<<grid1d(ncl), 256, 0, ST>>>(ncol, nlay, nbnd, nhum, sp, rh, plev, rh_upper, \
       mext_phobic, ssa_phobic, g_phobic, mext_philic, ssa_philic, g_philic, tau, ssa, g); RRX_CATCH("rrx_aerosol_optics") } \
 int rrx_cloud_optics_2str##SFX(int ncol, int nlay, int nbnd, int nsize_liq, int nsize_ice, \
         F radliq_lwr, F radliq_upr, F diamice_lwr, F diamice_upr, \
         const F* lut_extliq, const F* lut_ssaliq, const F* lut_asyliq, const F* lut_extice, const F* lut_ssaice, const F* lut_asyice, \
         const F* clwp, const F* ciwp, const F* reliq, const F* deice, F* tau, F* ssa, F* g, void* stream) \
-{ RRX_TRY const size_t ncl = size_t(ncol)*nlay; \
+{ RRX_TRY const size_t ncl = cloud_cells(ncol, nlay, nbnd, nsize_liq, nsize_ice); if (ncl == 0) return 0; \
   cloud_optics_kernel<F,true,false><<<grid1d(ncl), 256, 0, ST>>>(ncl, nbnd, nsize_liq, nsize_ice, \
       radliq_lwr, (radliq_upr - radliq_lwr)/(nsize_liq - F(1.)), diamice_lwr, (diamice_upr - diamice_lwr)/(nsize_ice - F(1.)), \
       lut_extliq, lut_ssaliq, lut_asyliq, lut_extice, lut_ssaice, lut_asyice, clwp, ciwp, reliq, deice, tau, ssa, g); RRX_CATCH("rrx_cloud_optics_2str") } \
@@ -701,7 +700,7 @@ int rrx_cloud_optics_2str_delta##SFX(int ncol, int nlay, int nbnd, int nsize_liq
         F radliq_lwr, F radliq_upr, F diamice_lwr, F diamice_upr, \
         const F* lut_extliq, const F* lut_ssaliq, const F* lut_asyliq, const F* lut_extice, const F* lut_ssaice, const F* lut_asyice, \
         const F* clwp, const F* ciwp, const F* reliq, const F* deice, F* tau, F* ssa, F* g, void* stream) \
-{ RRX_TRY const size_t ncl = size_t(ncol)*nlay; \
+{ RRX_TRY const size_t ncl = cloud_cells(ncol, nlay, nbnd, nsize_liq, nsize_ice); if (ncl == 0) return 0; \
   cloud_optics_kernel<F,true,true><<<grid1d(ncl), 256, 0, ST>>>(ncl, nbnd, nsize_liq, nsize_ice, \
       radliq_lwr, (radliq_upr - radliq_lwr)/(nsize_liq - F(1.)), diamice_lwr, (diamice_upr - diamice_lwr)/(nsize_ice - F(1.)), \
       lut_extliq, lut_ssaliq, lut_asyliq, lut_extice, lut_ssaice, lut_asyice, clwp, ciwp, reliq, deice, tau, ssa, g); RRX_CATCH("rrx_cloud_optics_2str_delta") } \
@@ -709,7 +708,7 @@ int rrx_cloud_optics_1scl##SFX(int ncol, int nlay, int nbnd, int nsize_liq, int 
         F radliq_lwr, F radliq_upr, F diamice_lwr, F diamice_upr, \
         const F* lut_extliq, const F* lut_ssaliq, const F* lut_asyliq, const F* lut_extice, const F* lut_ssaice, const F* lut_asyice, \
         const F* clwp, const F* ciwp, const F* reliq, const F* deice, F* tau, void* stream) \
-{ RRX_TRY const size_t ncl = size_t(ncol)*nlay; \
+{ RRX_TRY const size_t ncl = cloud_cells(ncol, nlay, nbnd, nsize_liq, nsize_ice); if (ncl == 0) return 0; \
   cloud_optics_kernel<F,false,false><<<grid1d(ncl), 256, 0, ST>>>(ncl, nbnd, nsize_liq, nsize_ice, \
       radliq_lwr, (radliq_upr - radliq_lwr)/(nsize_liq - F(1.)), diamice_lwr, (diamice_upr - diamice_lwr)/(nsize_ice - F(1.)), \
       lut_extliq, lut_ssaliq, lut_asyliq, lut_extice, lut_ssaice, lut_asyice, clwp, ciwp, reliq, deice, tau, (F*)nullptr, (F*)nullptr); RRX_CATCH("rrx_cloud_optics_1scl") } \
