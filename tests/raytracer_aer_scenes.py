@@ -1,14 +1,11 @@
 """The fixed-seed scenes of the aerosol tests (test_raytracer_aer_ref.py on the numpy restatement, test_gpu_raytracer_aer.py on the
-GPU) as (raytracer_aer_ref.AerScene, raytracer_aer_ref.AerBackground) pairs on the grid of raytracer_bg_scenes: 4 x 3 x 4
+GPU) as (raytracer_ref.Scene, raytracer_ref.Background) pairs with aerosol on the grid of raytracer_bg_scenes: 4 x 3 x 4
 cells, a (2, 1, 2) k_null grid, 3 background layers of unequal thickness, 2 g-points in 2 bands. The statistical bound is that of
 raytracer_scenes.sigma: five sigma of a per-photon contribution in [0, 1]."""
-import dataclasses
-
 import numpy as np
 
 import raytracer_scenes as S
 import raytracer_bg_scenes as SB
-from raytracer_aer_ref import AerScene, AerBackground
 
 NX, NY, NZ, KN, DZ_BG, LIMS = SB.NX, SB.NY, SB.NZ, SB.KN, SB.DZ_BG, SB.LIMS
 _arr = S._arr
@@ -16,13 +13,6 @@ ONE = 1 << 32
 PPP_BEER = 2048
 # forward against backward: the restatement's own run of the general direct scene stays far below these (test_raytracer_aer_ref.py)
 MAX_EVENTS = 1 << 16
-
-
-def with_aerosol(sc, bg, aerosol=None, bg_aerosol=None):
-    """a (Scene, Background) pair of raytracer_bg_scenes as an (AerScene, AerBackground) pair"""
-    sc = AerScene(**{f.name: getattr(sc, f.name) for f in dataclasses.fields(sc)}, aerosol=aerosol)
-    bg = None if bg is None else AerBackground(dz=bg.dz, tau=bg.tau, ssa=bg.ssa, cloud=bg.cloud, aerosol=bg_aerosol)
-    return sc, bg
 
 
 def zeros(dtype, nbg=3):
@@ -53,7 +43,8 @@ def general(dtype, top_at_1=True, inc_dif=(160., 60.)):
     sc.tau, sc.ssa, sc.cloud = tau, ssa, (ct, cw, cg)
     bg_aer = (_arr([[0.25, 0., 0.], [0.4, 0., 0.]], dtype), _arr([[0.9, 0.9, 0.9], [0.95, 0.9, 0.9]], dtype),
               _arr([[0.7, 0.7, 0.7], [0.65, 0.7, 0.7]], dtype))
-    return with_aerosol(sc, bg, (_arr(at, dtype), _arr(aw, dtype), _arr(ag, dtype)), bg_aer)
+    sc.aerosol, bg.aerosol = (_arr(at, dtype), _arr(aw, dtype), _arr(ag, dtype)), bg_aer
+    return sc, bg
 
 
 def general_direct(dtype, top_at_1=True):
@@ -66,9 +57,8 @@ def general_direct(dtype, top_at_1=True):
 def swap(dtype, top_at_1=True):
     """((scene A, background A), (scene B, background B)): general of raytracer_bg_scenes with its band triple T as cloud and no
     aerosol (A), and with no cloud and T as aerosol (B), in the grid and in the background."""
-    sc, bg = SB.general(dtype, top_at_1)
-    a = with_aerosol(sc, bg)
-    b = with_aerosol(sc, bg, sc.cloud, bg.cloud)
+    a, b = SB.general(dtype, top_at_1), SB.general(dtype, top_at_1)
+    b[0].aerosol, b[1].aerosol = b[0].cloud, b[1].cloud
     b[0].cloud, b[1].cloud = None, None
     return a, b
 
@@ -83,7 +73,8 @@ def beer(dtype, independent_column=False):
     z = np.zeros((2, NZ, ncol))
     bg.tau = _arr(np.zeros((2, 3)), dtype)
     bg_aer = (_arr([[0.2, 0.0, 0.35], [0.05, 0.0, 0.6]], dtype), _arr(np.zeros((2, 3)), dtype), _arr(np.full((2, 3), 0.7), dtype))
-    return with_aerosol(sc, bg, (_arr(at, dtype), _arr(z, dtype), _arr(np.full_like(z, 0.7), dtype)), bg_aer)
+    sc.aerosol, bg.aerosol = (_arr(at, dtype), _arr(z, dtype), _arr(np.full_like(z, 0.7), dtype)), bg_aer
+    return sc, bg
 
 
 def beer_expected(sc, bg):
@@ -116,7 +107,8 @@ def conservative(dtype):
     at = np.where(rng.uniform(0., 1., (2, NZ, ncol)) < 0.5, rng.uniform(0.2, 1.0, (2, NZ, ncol)), 0.0)
     aer = (_arr(at, dtype), _arr(np.ones_like(at), dtype), _arr(np.full_like(at, 0.7), dtype))
     bg_aer = (_arr([[0.2, 0., 0.1], [0., 0., 0.3]], dtype), _arr(np.ones((2, 3)), dtype), _arr(np.full((2, 3), 0.7), dtype))
-    return with_aerosol(sc, bg, aer, bg_aer)
+    sc.aerosol, bg.aerosol = aer, bg_aer
+    return sc, bg
 
 
 def aerosol_only(dtype):

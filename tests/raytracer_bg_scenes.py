@@ -1,5 +1,5 @@
 """The fixed-seed scenes of the background-atmosphere tests (test_raytracer_bg_ref.py on the numpy restatement,
-test_gpu_raytracer_bg.py on the GPU) as (raytracer_ref.Scene, raytracer_bg_ref.Background) pairs. The basic shape is a
+test_gpu_raytracer_bg.py on the GPU) as (raytracer_ref.Scene, raytracer_ref.Background) pairs. The basic shape is a
 4 x 3 x 4 grid with a (2, 1, 2) k_null grid under 3 background layers of unequal thickness, one of them with k_ext = 0, and 2
 g-points in 2 bands. The statistical bound is that of raytracer_scenes.sigma: five sigma of a per-photon contribution in [0, 1]."""
 import math
@@ -8,8 +8,7 @@ import numpy as np
 
 import raytracer_scenes as S
 import raytracer_bw_ref as B
-from raytracer_ref import Scene
-from raytracer_bg_ref import Background, profile
+from raytracer_ref import Scene, Background, profile
 
 NX, NY, NZ = 4, 3, 4
 KN = (2, 1, 2)

@@ -1,19 +1,15 @@
 """numpy restatement of the backward tracer with the rays of all g-points in one launch (the SPECTRAL instantiation of
-csrc/rrx_raytracer_bw.hip), in the scene's precision. Only what differs from the per-g-point aerosol form is stated here:
+csrc/rrx_raytracer_bw.hip), in the scene's precision. What is stated here is the spectral form's own:
   - the allocation's ray list: ray_end, weight0 and the common unit U (ray_list);
   - the ranges per g-point of a range of the list (raytracer_spectral_ref.ranges_by_gpt: the kernel's search);
-  - the deposit: llrint(min(d weight0[g], 2^20) 2^32), clamped AFTER the weight (weighted, the context that patches
-    raytracer_ref.to_count as raytracer_spectral_ref.weighted does and moves the clamp behind the weight);
   - the tally by band: counts (nbnd, npix), the counts of g-point g added into row band(g);
   - the channel matrix (channels).
-The transport of a ray is that of ray q of g-point g in raytracer_aer_ref.trace_counts_bw: no event loop is restated."""
-import contextlib
-
+The transport of a ray is that of ray q of g-point g in raytracer_bw_ref.trace_counts_bw, called with weight0[g]: the deposit is
+llrint(min(d weight0[g], 2^20) 2^32) there, clamped AFTER the weight."""
 import numpy as np
 
 import raytracer_ref as R
 import raytracer_bw_ref as B
-import raytracer_aer_ref as A
 from raytracer_spectral_ref import ranges_by_gpt
 
 
@@ -39,25 +35,6 @@ def ray_list(scene, sensor, m):
     return ray_end, weight0, U
 
 
-@contextlib.contextmanager
-def weighted(w0, tally):
-    """the deposits of the event loop take to_count(min(d w0, 2^20)), w0 in the precision of the deposits; a clamped one is counted
-    in tally["n_clamped"] (the loop's own clamp, in front of the weight, is switched off)"""
-    plain, d_max = R.to_count, B.D_MAX
-
-    def to_count(d):
-        F = d.dtype.type
-        d = d*F(w0)
-        clamped = d > F(d_max)
-        tally["n_clamped"] += int(clamped.sum())
-        return plain(np.where(clamped, F(d_max), d))
-    try:
-        R.to_count, B.D_MAX = to_count, np.inf
-        yield
-    finally:
-        R.to_count, B.D_MAX = plain, d_max
-
-
 def trace_counts(scene, bg, sensor, ray_end, weight0, ray0, nrays, max_events=1 << 20, table=None):
     """rrx_camera_trace_counts_spectral: counts (nbnd, npix) uint64, n_dep (nbnd, npix), n_capped, n_clamped and events, added in
     integers over the g-points that the range meets"""
@@ -67,14 +44,13 @@ def trace_counts(scene, bg, sensor, ray_end, weight0, ray0, nrays, max_events=1 
     out = dict(counts=np.zeros((nbnd, npix), dtype=np.uint64), n_dep=np.zeros((nbnd, npix), dtype=np.int64), n_capped=0, n_clamped=0,
                events=0)
     for g, q0, n in ranges_by_gpt(ray_end, ray0, nrays):
-        with weighted(weight0[g], out):
-            c = A.trace_counts_bw(scene, bg, sensor, g, q0, n, max_events, table=table)
+        c = B.trace_counts_bw(scene, sensor, g, q0, n, max_events, table=table, bg=bg, weight0=weight0[g])
         b = int(band[g])
         if b >= 0:
             out["counts"][b] = out["counts"][b] + c["counts"]
             out["n_dep"][b] += c["n_dep"]
-        out["n_capped"] += c["n_capped"]
-        out["events"] += c["events"]
+        for k in ("n_capped", "n_clamped", "events"):
+            out[k] += c[k]
     return out
 
 

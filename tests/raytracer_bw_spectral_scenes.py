@@ -10,7 +10,7 @@ import numpy as np
 import raytracer_bw_ref as B
 import raytracer_scenes as S
 import raytracer_spectral_scenes as SS
-from raytracer_aer_ref import AerScene
+from raytracer_ref import Scene
 
 NGPT, NBND, LIMS, INC, EMPTY, ONE = SS.NGPT, SS.NBND, SS.LIMS, SS.INC, SS.EMPTY, SS.ONE
 ACTIVE = (0, 1, 3, 4)
@@ -44,10 +44,10 @@ def bernoulli(dtype):
     rng = np.random.default_rng(2101)
     tau = np.repeat(rng.uniform(0.02, 0.3, (NGPT, nz, 1)), nx*ny, axis=2)
     arr = S._arr
-    return AerScene(nx=nx, ny=ny, nz=nz, dx=100.0, dy=130.0, dz=80.0, tau=arr(tau, dtype), ssa=arr(np.zeros_like(tau), dtype),
-                    sfc_albedo=arr(np.full(nx*ny, ALBEDO), dtype), mu0=0.5, azimuth=0.9, inc_dir=arr(INC, dtype),
-                    inc_dif=arr(np.zeros(NGPT), dtype), kn_grid=(nx, ny, nz), cloud=None, band_lims=LIMS, top_at_1=False,
-                    independent_column=False, seed=S.SEED + 51, aerosol=None)
+    return Scene(nx=nx, ny=ny, nz=nz, dx=100.0, dy=130.0, dz=80.0, tau=arr(tau, dtype), ssa=arr(np.zeros_like(tau), dtype),
+                 sfc_albedo=arr(np.full(nx*ny, ALBEDO), dtype), mu0=0.5, azimuth=0.9, inc_dir=arr(INC, dtype),
+                 inc_dif=arr(np.zeros(NGPT), dtype), kn_grid=(nx, ny, nz), cloud=None, band_lims=LIMS, top_at_1=False,
+                 independent_column=False, seed=S.SEED + 51, aerosol=None)
 
 
 def bernoulli_expected(sc):

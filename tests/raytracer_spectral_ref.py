@@ -1,19 +1,13 @@
 """numpy restatement of the forward tracer with all g-points in one launch (the SPECTRAL instantiation of csrc/rrx_raytracer.hip,
-csrc/rrx_rt_common.h), in the scene's precision. Only what differs from the per-g-point aerosol form is stated here:
+csrc/rrx_rt_common.h), in the scene's precision. What is stated here is the spectral form's own:
   - the allocation's photon list: photon_end, weight0, dif_frac and the common unit U (photon_list);
   - the g-point and the local index of a global photon index (gpt_of_photon, the kernel's search, and its ranges);
-  - the deposit: every to_count(w) of the tallies becomes to_count(w weight0[g]) (weighted, the context that patches
-    raytracer_ref.to_count the way raytracer_aer_ref.steps patches the transport steps).
-The transport of a photon is that of photon q of g-point g in raytracer_aer_ref.trace_counts: no event loop is restated."""
-import contextlib
-
+  - the sum in integers over the g-points that a range meets, and the one conversion to fluxes with U.
+The transport of a photon is that of photon q of g-point g in raytracer_ref.trace_counts, called with weight0[g]: every
+to_count(w) of the tallies becomes to_count(w weight0[g]) there."""
 import numpy as np
 
 import raytracer_ref as R
-import raytracer_bg_ref as BG
-import raytracer_aer_ref as A
-
-ALL_COUNTS = R.COUNT_NAMES + BG.BG_COUNT_NAMES
 
 
 def photon_list(scene, m):
@@ -65,51 +59,24 @@ def ranges_by_gpt(photon_end, photon0, nphotons):
     return out
 
 
-@contextlib.contextmanager
-def weighted(w0):
-    """the deposits of the event loops take to_count(w w0), w0 in the precision of the weights"""
-    plain = R.to_count
-    try:
-        R.to_count = lambda weight: plain(weight*weight.dtype.type(w0))
-        yield
-    finally:
-        R.to_count = plain
-
-
 def trace_counts(scene, bg, photon_end, weight0, photon0, nphotons, max_events=1 << 20, table=None):
-    """rrx_rt_trace_counts_spectral: the counts of raytracer_aer_ref.trace_counts, added in integers over the g-points that the
-    range meets, every deposit weighted; n_capped and events are sums too. (dif_frac is the scene's own inc_dif / (inc_dir + inc_dif),
-    which raytracer_aer_ref forms per g-point.)"""
-    nbg = bg.nbg if bg is not None else 0
-    out = {k: np.zeros(scene.ncol, dtype=np.uint64) for k in R.COUNT_NAMES[:4] + BG.BG_COUNT_NAMES[:3]}
-    out.update({k: np.zeros((scene.nz, scene.ncol), dtype=np.uint64) for k in R.COUNT_NAMES[4:]})
-    out.update({k: np.zeros(nbg, dtype=np.uint64) for k in BG.BG_COUNT_NAMES[3:]})
+    """rrx_rt_trace_counts_spectral: the counts of raytracer_ref.trace_counts, added in integers over the g-points that the range
+    meets, every deposit weighted; n_capped and events are sums too. (dif_frac is the scene's own inc_dif / (inc_dir + inc_dif),
+    which raytracer_ref.trace_counts forms per g-point.)"""
+    out = R.tallies(scene, bg, np.uint64)
     out["n_capped"], out["events"] = 0, 0
     for g, q0, n in ranges_by_gpt(photon_end, photon0, nphotons):
-        with weighted(weight0[g]):
-            c = A.trace_counts(scene, bg, g, q0, n, max_events, table)
-        for k in ALL_COUNTS:
+        c = R.trace_counts(scene, g, q0, n, max_events, table, bg, weight0[g])
+        for k in R.ALL_COUNTS + ("n_capped", "events"):
             out[k] = out[k] + c[k]
-        out["n_capped"] += c["n_capped"]
-        out["events"] += c["events"]
     return out
 
 
 def raytracer_sw(scene, bg, m, max_events=1 << 20, table=None):
-    """rrx_raytracer_sw_spectral: the fluxes of raytracer_bg_ref.raytracer_sw from one conversion with the common unit U"""
-    dt = scene.dtype
-    F = dt.type
+    """rrx_raytracer_sw_spectral: the fluxes of raytracer_ref.raytracer_sw from one conversion with the common unit U"""
     photon_end, weight0, _, U = photon_list(scene, m)
     c = trace_counts(scene, bg, photon_end, weight0, 0, int(photon_end[-1]), max_events, table)
-    nbg = bg.nbg if bg is not None else 0
-    flux = {}
-    for k in R.COUNT_NAMES[:4] + BG.BG_COUNT_NAMES[:3]:
-        flux[k] = R.counts_to_flux(c[k], U, np.zeros(scene.ncol, dtype=dt))
-    for k in R.COUNT_NAMES[4:]:
-        flux[k] = R.counts_to_flux(c[k], U / F(scene.dz), np.zeros((scene.nz, scene.ncol), dtype=dt))
-    for k in BG.BG_COUNT_NAMES[3:]:
-        flux[k] = np.zeros(nbg, dtype=dt)
-        for b in range(nbg):
-            flux[k][b:b+1] = R.counts_to_flux(c[k][b:b+1], (U / F(bg.dz[b])) / F(scene.ncol), flux[k][b:b+1])
+    flux = R.tallies(scene, bg, scene.dtype)
+    R.add_fluxes(flux, c, U, scene, bg)
     flux["n_capped"], flux["events"], flux["U"], flux["weight0"] = c["n_capped"], c["events"], U, weight0
     return flux

@@ -1,12 +1,12 @@
 """The fixed-seed scenes of the tests of the forward tracer with all g-points in one launch (test_raytracer_spectral_ref.py and
-test_raytracer_spectral_abi.py on the CPU, test_gpu_raytracer_spectral.py on the GPU) as (raytracer_aer_ref.AerScene,
-raytracer_aer_ref.AerBackground or None) pairs: 5 g-points in 2 bands (g-points 1-3 and 4-5), g-point 2 (0-based) without incident
+test_raytracer_spectral_abi.py on the CPU, test_gpu_raytracer_spectral.py on the GPU) as (raytracer_ref.Scene,
+raytracer_ref.Background or None) pairs: 5 g-points in 2 bands (g-points 1-3 and 4-5), g-point 2 (0-based) without incident
 flux, so that its range of the photon list is empty, and incident fluxes that span a factor of 80. The statistical bound is derived
 in beer_sigma, not measured."""
 import numpy as np
 
 import raytracer_scenes as S
-from raytracer_aer_ref import AerScene, AerBackground
+from raytracer_ref import Scene, Background
 
 NGPT, NBND = 5, 2
 LIMS = np.array([[1, 3], [4, 5]], dtype=np.int32)
@@ -32,17 +32,17 @@ def general(dtype, top_at_1=True, nx=4, ny=4, nz=6, kn=(2, 2, 3), dif_share=0.2)
     aer = (_arr(at, dtype), _arr(rng.uniform(0.85, 0.99, at.shape), dtype), _arr(rng.uniform(0.6, 0.75, at.shape), dtype))
     inc = np.array(INC)
     share = dif_share*np.array([1.0, 0.5, 0.0, 1.5, 0.0])
-    sc = AerScene(nx=nx, ny=ny, nz=nz, dx=100.0, dy=140.0, dz=60.0, tau=_arr(tau, dtype), ssa=_arr(ssa, dtype),
-                  sfc_albedo=_arr(np.full(ncol, 0.3), dtype), mu0=0.8, azimuth=4.0, inc_dir=_arr(inc*(1 - share), dtype),
-                  inc_dif=_arr(inc*share, dtype), kn_grid=kn, cloud=cloud, band_lims=LIMS, top_at_1=top_at_1, independent_column=False,
-                  seed=S.SEED + 41, aerosol=aer)
+    sc = Scene(nx=nx, ny=ny, nz=nz, dx=100.0, dy=140.0, dz=60.0, tau=_arr(tau, dtype), ssa=_arr(ssa, dtype),
+               sfc_albedo=_arr(np.full(ncol, 0.3), dtype), mu0=0.8, azimuth=4.0, inc_dir=_arr(inc*(1 - share), dtype),
+               inc_dif=_arr(inc*share, dtype), kn_grid=kn, cloud=cloud, band_lims=LIMS, top_at_1=top_at_1, independent_column=False,
+               seed=S.SEED + 41, aerosol=aer)
     bt = rng.uniform(0.05, 0.3, (NGPT, 3)); bt[:, 1] = 0.0
     bw = rng.uniform(0.5, 0.999, (NGPT, 3))
     bc = (_arr([[0., 0., 0.], [0., 0., 0.4]], dtype), _arr([[0.9, 0.9, 0.9], [0.9, 0.9, 0.95]], dtype),
           _arr([[0.8, 0.8, 0.8], [0.8, 0.8, 0.85]], dtype))
     ba = (_arr([[0.25, 0., 0.], [0.4, 0., 0.]], dtype), _arr([[0.9, 0.9, 0.9], [0.95, 0.9, 0.9]], dtype),
           _arr([[0.7, 0.7, 0.7], [0.65, 0.7, 0.7]], dtype))
-    bg = AerBackground(dz=_arr(DZ_BG, dtype), tau=_arr(bt, dtype), ssa=_arr(bw, dtype), cloud=bc, aerosol=ba)
+    bg = Background(dz=_arr(DZ_BG, dtype), tau=_arr(bt, dtype), ssa=_arr(bw, dtype), cloud=bc, aerosol=ba)
     return sc, bg
 
 
@@ -67,11 +67,11 @@ def beer(dtype):
     rng = np.random.default_rng(1902)
     ncol = nx*ny
     tau = rng.uniform(0.02, 0.35, (NGPT, nz, ncol))
-    sc = AerScene(nx=nx, ny=ny, nz=nz, dx=120.0, dy=90.0, dz=50.0, tau=_arr(tau, dtype), ssa=_arr(np.zeros_like(tau), dtype),
-                  sfc_albedo=_arr(np.zeros(ncol), dtype), mu0=0.6, azimuth=0.7, inc_dir=_arr(INC, dtype), inc_dif=_arr(np.zeros(NGPT), dtype),
-                  kn_grid=(2, 2, 3), cloud=None, band_lims=LIMS, top_at_1=True, independent_column=True, seed=S.SEED + 42, aerosol=None)
+    sc = Scene(nx=nx, ny=ny, nz=nz, dx=120.0, dy=90.0, dz=50.0, tau=_arr(tau, dtype), ssa=_arr(np.zeros_like(tau), dtype),
+               sfc_albedo=_arr(np.zeros(ncol), dtype), mu0=0.6, azimuth=0.7, inc_dir=_arr(INC, dtype), inc_dif=_arr(np.zeros(NGPT), dtype),
+               kn_grid=(2, 2, 3), cloud=None, band_lims=LIMS, top_at_1=True, independent_column=True, seed=S.SEED + 42, aerosol=None)
     bt = rng.uniform(0.02, 0.3, (NGPT, 3)); bt[:, 1] = 0.0
-    bg = AerBackground(dz=_arr(DZ_BG, dtype), tau=_arr(bt, dtype), ssa=_arr(np.zeros((NGPT, 3)), dtype), cloud=None, aerosol=None)
+    bg = Background(dz=_arr(DZ_BG, dtype), tau=_arr(bt, dtype), ssa=_arr(np.zeros((NGPT, 3)), dtype), cloud=None, aerosol=None)
     return sc, bg
 
 

@@ -1,6 +1,6 @@
 """GPU tests of aerosol as a third scattering species of the two ray tracers (rrx_rt_k_null_aer, rrx_rt_bg_profile_aer and the
 rrx_*_aer entries; csrc/rrx_rt_common.h). Scenes: tests/raytracer_aer_scenes.py (the 4 x 3 x 4 grid under 3
-background layers of raytracer_bg_scenes; 2 g-points in 2 bands; fixed seeds); restatement: tests/raytracer_aer_ref.py. The tallies
+background layers of raytracer_bg_scenes; 2 g-points in 2 bands; fixed seeds); restatement: tests/raytracer_ref.py (Scene.aerosol, Background.aerosol). The tallies
 are integers added with integer atomics, so a run that passes once passes always. Bounds are derived, not measured, and are those
 of test_gpu_raytracer_bg.py: five sigma of sqrt(p (1 - p)/N) for the closed forms, the forward bound combined with the standard
 error of 16 disjoint ray ranges for forward against backward, 2 ulp of a row's largest term for the profile. Against the
@@ -12,94 +12,19 @@ import pytest
 
 import raytracer_ref as R
 import raytracer_bw_ref as B
-import raytracer_bg_ref as BG
 import raytracer_bg_scenes as SB
 import raytracer_bw_scenes as BS
 import raytracer_scenes as S
 import raytracer_phase_scenes as PS
-import raytracer_aer_ref as A
 import raytracer_aer_scenes as SA
-from raytracer_dev import _be, _dev, _u64
-from rte_rrtmgp_cpp_amd import phase_tables
+from raytracer_dev import (_be, NO_TRIPLE, DevBackground, dev, device_table, numbers, clean, k_null, forward_bg, backward_bg, solve_fw_bg,
+                           solve_bw_bg)
 
 pytestmark = pytest.mark.gpu
 ONE = float(1 << 32)
 FW = R.COUNT_NAMES
-NEW = BG.BG_COUNT_NAMES
+NEW = R.BG_COUNT_NAMES
 BWK = ("counts", "n_capped", "n_clamped")
-NO_TRIPLE = (None, None, None)          # an aerosol triple of NULL pointers: the _aer entries are called with it, the _bg entries with None
-
-
-class DevBackground:
-    def __init__(self, be, bg):
-        self.dz = np.ascontiguousarray(bg.dz, dtype=be.np_dtype)
-        self.tau, self.ssa = be.asarray(bg.tau), be.asarray(bg.ssa)
-        self.cloud = None if bg.cloud is None else tuple(be.asarray(c) for c in bg.cloud)
-        aer = getattr(bg, "aerosol", None)
-        self.aerosol = None if aer is None else tuple(be.asarray(c) for c in aer)
-
-
-def dev(be, sc, bg):
-    """the scene, its aerosol triple and its background on the device"""
-    d = _dev(be, sc)
-    aer = getattr(sc, "aerosol", None)
-    d["aer"] = NO_TRIPLE if aer is None else tuple(be.asarray(c) for c in aer)
-    return d, (None if bg is None else DevBackground(be, bg))
-
-
-def k_null(be, sc, d, g, aerosol=True):
-    return be.rt_k_null(d["tau"], g, sc.nx, sc.ny, sc.dz, sc.kn_grid, sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"],
-                        aerosol=d["aer"] if aerosol else None)          # (a triple of None: rrx_rt_k_null_aer with a NULL aer_tau)
-
-
-def forward(be, sc, d, dbg, g, photon0, nphotons, phase=None, counts=None, aer=True, max_events=None):
-    """aer: rrx_rt_trace_counts_aer with the scene's triple, of NULL pointers when it has none; not aer: rrx_rt_trace_counts_bg (the
-    scene's aerosol is not passed)"""
-    return be.rt_trace_counts_bg(d["tau"], d["ssa"], g, sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, float(sc.inc_dir[g]),
-                                 float(sc.inc_dif[g]), sc.kn_grid, k_null(be, sc, d, g, aer), sc.seed, photon0, nphotons, top_at_1=sc.top_at_1,
-                                 independent_column=sc.independent_column, cloud=d["cloud"], band_lims=d["lims"], counts=counts, phase=phase,
-                                 background=dbg, aerosol=d["aer"] if aer else None, max_events=max_events)
-
-
-def backward(be, sc, d, dbg, sensor, g, ray0, nrays, phase=None, counts=None, aer=True, max_events=None):
-    return be.rt_bw_trace_counts_bg(d["tau"], d["ssa"], g, sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, sc.kn_grid,
-                                    k_null(be, sc, d, g, aer), sensor, sc.seed, ray0, nrays, top_at_1=sc.top_at_1, cloud=d["cloud"],
-                                    band_lims=d["lims"], counts=counts, phase=phase, background=dbg, aerosol=d["aer"] if aer else None,
-                                    max_events=max_events)
-
-
-def solve_fw(be, sc, d, dbg, ppp, phase=None, aer=True):
-    r = be.raytracer_sw_bg(d["tau"], d["ssa"], sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, sc.inc_dir, sc.inc_dif,
-                           sc.kn_grid, ppp, sc.seed, top_at_1=sc.top_at_1, independent_column=sc.independent_column, cloud=d["cloud"],
-                           band_lims=d["lims"], phase=phase, background=dbg, aerosol=d["aer"] if aer else None)
-    return {k: (be.to_numpy(v) if k != "n_capped" else v) for k, v in r.items()}
-
-
-def solve_bw(be, sc, d, dbg, sensor, rpp, phase=None, aer=True):
-    return be.raytracer_bw_bg(d["tau"], d["ssa"], sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, sc.inc_dir, sc.kn_grid,
-                              sensor, rpp, sc.seed, top_at_1=sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"], phase=phase, background=dbg,
-                              aerosol=d["aer"] if aer else None)
-
-
-def device_table(be, sc, raw=None):
-    """the double Henyey-Greenstein tables of raytracer_phase_scenes (or raw: mu, phase) with a radius for every cell of the scene"""
-    t = phase_tables.build(be, *(PS.double_hg33() if raw is None else raw), PS.RE0, PS.DRE)
-    return t.with_radius(be.asarray(PS.cell_radii(sc, be.np_dtype)))
-
-
-def numbers(be, c):
-    return {k: _u64(be, v) for k, v in c.items()}
-
-
-def clean(be, c):
-    assert int(_u64(be, c["n_capped"])[0]) == 0 and int(_u64(be, c["n_clamped"])[0]) == 0
-    return _u64(be, c["counts"])
-
-
-class _NoAerosol:
-    """a device background without its aerosol: what the _bg entries see"""
-    def __init__(self, dbg):
-        self.dz, self.tau, self.ssa, self.cloud, self.aerosol = dbg.dz, dbg.tau, dbg.ssa, dbg.cloud, None
 
 
 # ---- 1: the profile and k_null
@@ -115,7 +40,7 @@ def test_profile_and_k_null_against_numpy(dt, hip_f64, hip_f32):
         d, dbg = dev(be, sc, bg)
         for g in range(2):
             got = be.to_numpy(be.rt_bg_profile(dbg, g, d["lims"], aerosol=dbg.aerosol))
-            want = A.profile(sc, bg, g)
+            want = R.profile(sc, bg, g)
             assert got.shape == (7, bg.nbg + 1)
             for row in range(7):
                 tol = 2*eps*float(np.max(np.abs(want[row])))
@@ -123,7 +48,7 @@ def test_profile_and_k_null_against_numpy(dt, hip_f64, hip_f32):
                 assert err <= tol, (make.__name__, g, row, err, tol)
             assert np.all(got[:4, bg.nbg] == 0) and np.all(got[5:, bg.nbg] == 0) and got[4, bg.nbg] >= got[4, 0] >= got[4, bg.nbg - 1] == 0
             assert got[5].any() == (make is not SA.beer)          # (an aerosol that only absorbs has k_sca_aer = 0)
-            got, want = be.to_numpy(k_null(be, sc, d, g)), A.k_null(sc, g)
+            got, want = be.to_numpy(k_null(be, sc, d, g, aer=True)), R.k_null(sc, g)
             assert got.shape == want.shape
             assert float(np.max(np.abs(got.astype(np.float64) - want))) <= 2*eps*float(want.max()), (make.__name__, g)
     # a NULL triple writes zeros into the two new rows and the five rows of rrx_rt_bg_profile
@@ -149,22 +74,24 @@ def test_without_aerosol_the_aer_entries_give_the_integers_of_the_bg_entries(dt,
     d0, dbg0 = dev(be, sc0, bg0)
     phase = device_table(be, sc0) if with_table else None
     n, m = 16*sc0.ncol, 16*12
-    want = numbers(be, forward(be, sc0, d0, dbg0, 1, 3, n, phase=phase, aer=False))
-    want_bw = {s: numbers(be, backward(be, sc0, d0, dbg0, cam[s], 1, 2, m, phase=phase, aer=False)) for s in sensors}
+    want = numbers(be, forward_bg(be, sc0, d0, dbg0, 1, 3, n, phase=phase, aer=False))
+    want_bw = {s: numbers(be, backward_bg(be, sc0, d0, dbg0, cam[s], 1, 2, m, phase=phase, aer=False)) for s in sensors}
     assert want["abs_dif"].any() and all(w["counts"].any() for w in want_bw.values())
-    for how, (sc, bg) in (("NULL", SA.with_aerosol(sc0, bg0)), ("zeros", SA.with_aerosol(sc0, bg0, grid, aloft if with_bg else None))):
-        d, dbg = dev(be, sc, bg)
-        got = numbers(be, forward(be, sc, d, dbg, 1, 3, n, phase=phase))
+    for how, in_grid, in_bg in (("NULL", None, None), ("zeros", grid, aloft)):
+        sc, bg = SB.general(be.np_dtype)
+        sc.aerosol, bg.aerosol = in_grid, in_bg
+        d, dbg = dev(be, sc, bg if with_bg else None)
+        got = numbers(be, forward_bg(be, sc, d, dbg, 1, 3, n, phase=phase, aer=True))
         for k in FW + NEW + ("n_capped",):
             assert np.array_equal(want[k], got[k]), (how, k)
         for s in sensors:
-            got = numbers(be, backward(be, sc, d, dbg, cam[s], 1, 2, m, phase=phase))
+            got = numbers(be, backward_bg(be, sc, d, dbg, cam[s], 1, 2, m, phase=phase, aer=True))
             for k in BWK:
                 assert np.array_equal(want_bw[s][k], got[k]), (how, s, k)
-        a, b = solve_fw(be, sc0, d0, dbg0, 8, phase=phase, aer=False), solve_fw(be, sc, d, dbg, 8, phase=phase)
+        a, b = solve_fw_bg(be, sc0, d0, dbg0, 8, phase=phase, aer=False), solve_fw_bg(be, sc, d, dbg, 8, phase=phase, aer=True)
         for k in FW + NEW:
             assert np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), (how, k)
-        a, b = solve_bw(be, sc0, d0, dbg0, cam["nadir"], 8, phase=phase, aer=False), solve_bw(be, sc, d, dbg, cam["nadir"], 8, phase=phase)
+        a, b = solve_bw_bg(be, sc0, d0, dbg0, cam["nadir"], 8, phase=phase, aer=False), solve_bw_bg(be, sc, d, dbg, cam["nadir"], 8, phase=phase, aer=True)
         assert np.array_equal(be.to_numpy(a["radiance"]).view(np.uint8), be.to_numpy(b["radiance"]).view(np.uint8)), how
 
 
@@ -180,12 +107,12 @@ def test_swap_cloud_and_aerosol(dt, top_at_1, hip_f64, hip_f32):
     (da, dba), (db, dbb) = dev(be, sa, ba), dev(be, sb, bb)
     n = 32*sa.ncol
     for g in range(2):
-        ca, cb = numbers(be, forward(be, sa, da, dba, g, 0, n)), numbers(be, forward(be, sb, db, dbb, g, 0, n))
+        ca, cb = numbers(be, forward_bg(be, sa, da, dba, g, 0, n, aer=True)), numbers(be, forward_bg(be, sb, db, dbb, g, 0, n, aer=True))
         for k in FW + NEW + ("n_capped",):
             assert np.array_equal(ca[k], cb[k]), (g, k)
         assert ca["abs_dif"].any() and ca["toa_up"].any()
         for name, cam in SB.cameras(sa, ba).items():
-            ra, rb = numbers(be, backward(be, sa, da, dba, cam, g, 0, 32*12)), numbers(be, backward(be, sb, db, dbb, cam, g, 0, 32*12))
+            ra, rb = numbers(be, backward_bg(be, sa, da, dba, cam, g, 0, 32*12, aer=True)), numbers(be, backward_bg(be, sb, db, dbb, cam, g, 0, 32*12, aer=True))
             for k in BWK:
                 assert np.array_equal(ra[k], rb[k]), (g, name, k)
             assert ra["counts"].any()
@@ -210,8 +137,8 @@ def test_photon_for_photon(top_at_1, hip_f64):
     d, dbg = dev(be, sc, bg)
     n = 32*sc.ncol
     for g in range(2):
-        ref = A.trace_counts(sc, bg, g, 0, n, table=_ref_table(sc))
-        got = numbers(be, forward(be, sc, d, dbg, g, 0, n, phase=device_table(be, sc)))
+        ref = R.trace_counts(sc, g, 0, n, table=_ref_table(sc), bg=bg)
+        got = numbers(be, forward_bg(be, sc, d, dbg, g, 0, n, phase=device_table(be, sc), aer=True))
         assert ref["n_capped"] == 0 and int(got["n_capped"][0]) == 0
         for k in FW + NEW:
             off = np.abs(got[k].reshape(-1).astype(np.int64) - ref[k].reshape(-1).astype(np.int64))
@@ -230,9 +157,9 @@ def test_ray_for_ray(kind, top_at_1, hip_f64):
     d, dbg = dev(be, sc, bg)
     n = 32*12
     for g in range(2):
-        ref = A.trace_counts_bw(sc, bg, sensor, g, 0, n, table=_ref_table(sc))
+        ref = B.trace_counts_bw(sc, sensor, g, 0, n, table=_ref_table(sc), bg=bg)
         assert ref["n_capped"] == 0 and ref["n_clamped"] == 0
-        got = clean(be, backward(be, sc, d, dbg, sensor, g, 0, n, phase=device_table(be, sc)))
+        got = clean(be, backward_bg(be, sc, d, dbg, sensor, g, 0, n, phase=device_table(be, sc), aer=True))
         off = np.abs(got.astype(np.int64) - ref["counts"].astype(np.int64))
         print(f"raytracer_aer ray for ray {kind} top_at_1={top_at_1} g-point {g}: worst difference {int(off.max())} counts of 2^-32, "
               f"{int(ref['n_dep'].sum())} deposits")
@@ -249,7 +176,7 @@ def test_a_purely_absorbing_aerosol_is_beer(independent_column, dt, hip_f64, hip
     sc, bg = SA.beer(be.np_dtype, independent_column)
     d, dbg = dev(be, sc, bg)
     for g in range(2):
-        c = numbers(be, forward(be, sc, d, dbg, g, 0, SA.PPP_BEER*sc.ncol))
+        c = numbers(be, forward_bg(be, sc, d, dbg, g, 0, SA.PPP_BEER*sc.ncol, aer=True))
         assert int(c["n_capped"][0]) == 0
         SA.check_beer(sc, bg, g, c, SA.PPP_BEER, f"{dt} ic={independent_column}")
 
@@ -264,10 +191,10 @@ def test_forward_against_backward(dt, hip_f64, hip_f32):
     per_range = (BS.S3_RAYS//BS.S3_RANGES)*sc.ncol
     worst = 0.0
     for g in range(2):
-        fwd = numbers(be, forward(be, sc, d, dbg, g, 0, BS.S3_PHOTONS*sc.ncol, max_events=SA.MAX_EVENTS))
+        fwd = numbers(be, forward_bg(be, sc, d, dbg, g, 0, BS.S3_PHOTONS*sc.ncol, max_events=SA.MAX_EVENTS, aer=True))
         assert int(fwd["n_capped"][0]) == 0
         for name, sensor in SB.flux_sensors(sc).items():
-            ranges = np.stack([clean(be, backward(be, sc, d, dbg, sensor, g, n*per_range, per_range, max_events=SA.MAX_EVENTS))
+            ranges = np.stack([clean(be, backward_bg(be, sc, d, dbg, sensor, g, n*per_range, per_range, max_events=SA.MAX_EVENTS, aer=True))
                                for n in range(BS.S3_RANGES)])
             worst = max(worst, BS.compare_forward_backward(sc, g, name, fwd[name], ranges, f"aer {dt}"))
     print(f"raytracer_aer forward against backward {dt}: worst difference {worst:.2f} combined sigma (bound 5)")
@@ -284,19 +211,19 @@ def test_the_table_is_the_cloud_s_alone(hip_f64):
     peaked = np.broadcast_to(np.exp(40.*(mu - 1.)) + 1.e-6, (2, 3, mu.size)).copy()
     phase = device_table(be, sc, (mu, peaked))
     n = 32*sc.ncol
-    hg, tab = numbers(be, forward(be, sc, d, dbg, 1, 0, n)), numbers(be, forward(be, sc, d, dbg, 1, 0, n, phase=phase))
+    hg, tab = numbers(be, forward_bg(be, sc, d, dbg, 1, 0, n, aer=True)), numbers(be, forward_bg(be, sc, d, dbg, 1, 0, n, phase=phase, aer=True))
     for k in FW + NEW + ("n_capped",):
         assert np.array_equal(hg[k], tab[k]), k
     assert hg["sfc_dn_dif"].any() and hg["toa_up"].any()
     for name, cam in SB.cameras(sc, bg).items():
-        a, b = numbers(be, backward(be, sc, d, dbg, cam, 1, 0, 32*12)), numbers(be, backward(be, sc, d, dbg, cam, 1, 0, 32*12, phase=phase))
+        a, b = numbers(be, backward_bg(be, sc, d, dbg, cam, 1, 0, 32*12, aer=True)), numbers(be, backward_bg(be, sc, d, dbg, cam, 1, 0, 32*12, phase=phase, aer=True))
         for k in BWK:
             assert np.array_equal(a[k], b[k]), (name, k)
         assert a["counts"].any()
     # the same table on a scene whose cloud scatters does change the counts
     sc, bg = SA.general(np.float64)
     d, dbg = dev(be, sc, bg)
-    hg, tab = numbers(be, forward(be, sc, d, dbg, 1, 0, n)), numbers(be, forward(be, sc, d, dbg, 1, 0, n, phase=device_table(be, sc, (mu, peaked))))
+    hg, tab = numbers(be, forward_bg(be, sc, d, dbg, 1, 0, n, aer=True)), numbers(be, forward_bg(be, sc, d, dbg, 1, 0, n, phase=device_table(be, sc, (mu, peaked)), aer=True))
     assert any(not np.array_equal(hg[k], tab[k]) for k in FW + NEW)
 
 
@@ -310,17 +237,17 @@ def test_counts_are_additive_reproducible_and_the_loops_are_the_entries(with_tab
     d, dbg = dev(be, sc, bg)
     phase = device_table(be, sc) if with_table else None
     n = 32*sc.ncol
-    whole, again = numbers(be, forward(be, sc, d, dbg, 1, 0, n, phase=phase)), numbers(be, forward(be, sc, d, dbg, 1, 0, n, phase=phase))
-    parts = forward(be, sc, d, dbg, 1, 0, n//3, phase=phase)
-    parts = numbers(be, forward(be, sc, d, dbg, 1, n//3, n - n//3, phase=phase, counts=parts))
+    whole, again = numbers(be, forward_bg(be, sc, d, dbg, 1, 0, n, phase=phase, aer=True)), numbers(be, forward_bg(be, sc, d, dbg, 1, 0, n, phase=phase, aer=True))
+    parts = forward_bg(be, sc, d, dbg, 1, 0, n//3, phase=phase, aer=True)
+    parts = numbers(be, forward_bg(be, sc, d, dbg, 1, n//3, n - n//3, phase=phase, counts=parts, aer=True))
     for k in FW + NEW + ("n_capped",):
         assert np.array_equal(whole[k], again[k]) and np.array_equal(whole[k], parts[k]), k
     assert int(whole["n_capped"][0]) == 0 and all(whole[k].any() for k in NEW)
     cam = SB.cameras(sc, bg)["aloft"]
     m = 32*12
-    whole, again = numbers(be, backward(be, sc, d, dbg, cam, 1, 0, m, phase=phase)), numbers(be, backward(be, sc, d, dbg, cam, 1, 0, m, phase=phase))
-    parts = backward(be, sc, d, dbg, cam, 1, 0, m//3, phase=phase)
-    parts = numbers(be, backward(be, sc, d, dbg, cam, 1, m//3, m - m//3, phase=phase, counts=parts))
+    whole, again = numbers(be, backward_bg(be, sc, d, dbg, cam, 1, 0, m, phase=phase, aer=True)), numbers(be, backward_bg(be, sc, d, dbg, cam, 1, 0, m, phase=phase, aer=True))
+    parts = backward_bg(be, sc, d, dbg, cam, 1, 0, m//3, phase=phase, aer=True)
+    parts = numbers(be, backward_bg(be, sc, d, dbg, cam, 1, m//3, m - m//3, phase=phase, counts=parts, aer=True))
     for k in BWK:
         assert np.array_equal(whole[k], again[k]) and np.array_equal(whole[k], parts[k]), k
     assert whole["counts"].all()
@@ -333,22 +260,22 @@ def test_counts_are_additive_reproducible_and_the_loops_are_the_entries(with_tab
     radiance = be.zeros((12,))
     for g in range(2):
         inc = F(sc.inc_dir[g]) + F(sc.inc_dif[g])
-        c = forward(be, sc, d, dbg, g, 0, ppp*sc.ncol, phase=phase)
+        c = forward_bg(be, sc, d, dbg, g, 0, ppp*sc.ncol, phase=phase, aer=True)
         scale = inc / F(ppp)
         for k in FW + NEW[:3]:
             be.rt_counts_to_flux(c[k], float(scale if k in FW[:4] + NEW[:3] else scale / F(sc.dz)), flux[k])
         for k in NEW[3:]:
             for b in range(bg.nbg):
                 be.rt_counts_to_flux(c[k][b:b+1], float((scale / F(bg.dz[b])) / F(sc.ncol)), flux[k][b:b+1])
-        cb = backward(be, sc, d, dbg, cam, g, 0, ppp*12, phase=phase)
+        cb = backward_bg(be, sc, d, dbg, cam, g, 0, ppp*12, phase=phase, aer=True)
         be.rt_counts_to_flux(cb["counts"], float(F(sc.inc_dir[g]) / (F(sc.mu0)*F(ppp))), radiance)
-    r = solve_fw(be, sc, d, dbg, ppp, phase=phase)
+    r = solve_fw_bg(be, sc, d, dbg, ppp, phase=phase, aer=True)
     for k in FW + NEW:
         assert np.array_equal(be.to_numpy(flux[k]).view(np.uint8), r[k].view(np.uint8)), k
-    rb = solve_bw(be, sc, d, dbg, cam, ppp, phase=phase)
+    rb = solve_bw_bg(be, sc, d, dbg, cam, ppp, phase=phase, aer=True)
     assert np.array_equal(be.to_numpy(radiance).view(np.uint8), be.to_numpy(rb["radiance"]).reshape(-1).view(np.uint8))
     # and they are not the loops without aerosol
-    plain = solve_fw(be, sc, d, _NoAerosol(dbg), ppp, phase=phase, aer=False)
+    plain = solve_fw_bg(be, sc, d, dbg, ppp, phase=phase, aer=False)
     assert any(not np.array_equal(plain[k], r[k]) for k in FW + NEW)
 
 
@@ -497,14 +424,14 @@ def test_cxx_classes_with_aerosol_give_the_entries_bit_for_bit_and_throw(dt, top
                                           H(inc_dir), H(inc_dif), *sc.kn_grid, ctypes.c_longlong(ppp), ctypes.c_ulonglong(sc.seed), be.RT_MAX_EVENTS,
                                           out6, ctypes.byref(n_capped), out5, *table, *medium, *aer, *bg_aer, stream)
 
-    want = solve_fw(be, sc, d, dbg, ppp)
+    want = solve_fw_bg(be, sc, d, dbg, ppp, aer=True)
     assert call(with_bg, grid, aloft) == 0, lib.rrx_cxx_driver_error().decode()
     torch.cuda.synchronize()
     assert n_capped.value == 0 and want["n_capped"] == 0
     for k, t in zip(FW + NEW, outs + news):
         assert np.array_equal(be.to_numpy(t).view(np.uint8), want[k].view(np.uint8)), k
     # the grid's aerosol alone, without a background
-    want = solve_fw(be, sc, d, None, ppp)
+    want = solve_fw_bg(be, sc, d, None, ppp, aer=True)
     assert call(no_bg, grid, (none, none, none)) == 0, lib.rrx_cxx_driver_error().decode()
     torch.cuda.synchronize()
     for k, t in zip(FW, outs):
@@ -516,7 +443,7 @@ def test_cxx_classes_with_aerosol_give_the_entries_bit_for_bit_and_throw(dt, top
         assert "Raytracer_gpu::set_aerosol" in msg and word in msg, msg
 
     cam = SB.cameras(sc, bg)["aloft"]
-    wantb = solve_bw(be, sc, d, dbg, cam, ppp)
+    wantb = solve_bw_bg(be, sc, d, dbg, cam, ppp, aer=True)
     out = be.empty((cam.npy, cam.npx))
     nums = np.concatenate([np.asarray(v, dtype=np.float64) for v in (cam.position, cam.e_w, cam.e_h, cam.e_d)]).astype(be.np_dtype)
 

@@ -1,6 +1,6 @@
 """GPU tests of the background atmosphere of the two ray tracers (rrx_rt_bg_profile and the rrx_*_bg entries; csrc/rrx_rt_common.h,
 DESIGN 4.17). Scenes: tests/raytracer_bg_scenes.py (a 4 x 3 x 4 grid under 3 background layers of unequal thickness, one of them
-empty; 2 g-points in 2 bands; fixed seeds); restatement: tests/raytracer_bg_ref.py. The tallies are integers added with integer
+empty; 2 g-points in 2 bands; fixed seeds); restatement: tests/raytracer_ref.py (bg=). The tallies are integers added with integer
 atomics, so a run that passes once passes always. Bounds are derived, not measured: five sigma of sqrt(p (1 - p)/N) for the
 closed forms, the forward bound combined with the standard error of 16 disjoint ray ranges for forward against backward, one count
 per deposit (half a count per event, forward) plus 4 eps of the deposited sum ray for ray (two exp / log implementations within
@@ -17,67 +17,20 @@ import pytest
 
 import raytracer_ref as R
 import raytracer_bw_ref as B
-import raytracer_bg_ref as BG
 import raytracer_bg_scenes as SB
 import raytracer_bw_scenes as BS
 import raytracer_scenes as S
 import raytracer_phase_scenes as PS
-from raytracer_dev import _be, _dev, _u64, k_null, forward, backward, solve_fw, solve_bw
+from raytracer_dev import (_be, _dev, DevBackground, device_table, numbers, clean, forward, backward, solve_fw, solve_bw, forward_bg,
+                           backward_bg, solve_fw_bg, solve_bw_bg)
 from raytracer_bg_scenes import (check_absorbing, check_conservative, check_split, shadow_full_count, PPP_ABSORBING, PPP_CONSERVATIVE,
                                  PPP_SPLIT)
-from rte_rrtmgp_cpp_amd import synthetic, pipeline, phase_tables
+from rte_rrtmgp_cpp_amd import synthetic, pipeline
 
 pytestmark = pytest.mark.gpu
 ONE = float(1 << 32)
 FW = R.COUNT_NAMES
-NEW = BG.BG_COUNT_NAMES
-
-
-class DevBackground:
-    def __init__(self, be, bg):
-        self.dz = np.ascontiguousarray(bg.dz, dtype=be.np_dtype)
-        self.tau, self.ssa = be.asarray(bg.tau), be.asarray(bg.ssa)
-        self.cloud = None if bg.cloud is None else tuple(be.asarray(c) for c in bg.cloud)
-
-
-def forward_bg(be, sc, d, dbg, g, photon0, nphotons, phase=None, counts=None):
-    return be.rt_trace_counts_bg(d["tau"], d["ssa"], g, sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, float(sc.inc_dir[g]),
-                                 float(sc.inc_dif[g]), sc.kn_grid, k_null(be, sc, d, g), sc.seed, photon0, nphotons, top_at_1=sc.top_at_1,
-                                 independent_column=sc.independent_column, cloud=d["cloud"], band_lims=d["lims"], counts=counts, phase=phase,
-                                 background=dbg)
-
-
-def backward_bg(be, sc, d, dbg, sensor, g, ray0, nrays, phase=None, counts=None):
-    return be.rt_bw_trace_counts_bg(d["tau"], d["ssa"], g, sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, sc.kn_grid,
-                                    k_null(be, sc, d, g), sensor, sc.seed, ray0, nrays, top_at_1=sc.top_at_1, cloud=d["cloud"],
-                                    band_lims=d["lims"], counts=counts, phase=phase, background=dbg)
-
-
-def solve_fw_bg(be, sc, d, dbg, ppp, phase=None):
-    r = be.raytracer_sw_bg(d["tau"], d["ssa"], sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, sc.inc_dir, sc.inc_dif,
-                           sc.kn_grid, ppp, sc.seed, top_at_1=sc.top_at_1, independent_column=sc.independent_column, cloud=d["cloud"],
-                           band_lims=d["lims"], phase=phase, background=dbg)
-    return {k: (be.to_numpy(v) if k != "n_capped" else v) for k, v in r.items()}
-
-
-def solve_bw_bg(be, sc, d, dbg, sensor, rpp, phase=None):
-    return be.raytracer_bw_bg(d["tau"], d["ssa"], sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, sc.inc_dir, sc.kn_grid,
-                              sensor, rpp, sc.seed, top_at_1=sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"], phase=phase, background=dbg)
-
-
-def device_table(be, sc):
-    """the double Henyey-Greenstein tables of raytracer_phase_scenes with a radius for every cell of the scene"""
-    t = phase_tables.build(be, *PS.double_hg33(), PS.RE0, PS.DRE)
-    return t.with_radius(be.asarray(PS.cell_radii(sc, be.np_dtype)))
-
-
-def numbers(be, c):
-    return {k: _u64(be, v) for k, v in c.items()}
-
-
-def clean(be, c):
-    assert int(_u64(be, c["n_capped"])[0]) == 0 and int(_u64(be, c["n_clamped"])[0]) == 0
-    return _u64(be, c["counts"])
+NEW = R.BG_COUNT_NAMES
 
 
 # ---- 3: the profile
@@ -94,7 +47,7 @@ def test_bg_profile_against_numpy(dt, hip_f64, hip_f32):
         dbg = DevBackground(be, bg)
         for g in range(2):
             got = be.to_numpy(be.rt_bg_profile(dbg, g, be.asarray(sc.band_lims)))
-            want = BG.profile(sc, bg, g)
+            want = R.profile(sc, bg, g, aerosol=False)
             assert got.shape == (5, bg.nbg + 1)
             for row in range(5):
                 tol = 2*eps*float(np.max(np.abs(want[row])))
@@ -139,7 +92,7 @@ def test_without_layers_the_bg_entries_give_the_integers_of_the_existing_entries
 @pytest.fixture(scope="module")
 def general_reference():
     sc, bg = SB.general(np.float64)
-    return sc, bg, BG.raytracer_sw(sc, bg, 32)
+    return sc, bg, R.raytracer_sw(sc, 32, bg=bg)
 
 
 def test_photon_for_photon(general_reference, hip_f64):
@@ -165,7 +118,7 @@ def test_ray_for_ray(kind, hip_f64):
     sc, bg = SB.general(np.float64)
     sensor = SB.cameras(sc, bg)[kind]
     rpp = 32
-    ref = BG.raytracer_bw(sc, bg, sensor, rpp)
+    ref = B.raytracer_bw(sc, sensor, rpp, bg=bg)
     assert ref["n_capped"] == 0 and ref["n_clamped"] == 0
     r = solve_bw_bg(be, sc, _dev(be, sc), DevBackground(be, bg), sensor, rpp)
     assert r["n_capped"] == 0 and r["n_clamped"] == 0
@@ -322,7 +275,7 @@ def test_a_phase_table_applies_inside_the_grid_only(hip_f64):
     import raytracer_phase_ref as P
     ref_table = P.build_tables(*PS.double_hg33(), np.float64, PS.RE0, PS.DRE)
     ref_table.cld_re = PS.cell_radii(sc, np.float64)
-    ref = BG.trace_counts(sc, bg, 1, 0, n, table=ref_table)
+    ref = R.trace_counts(sc, 1, 0, n, table=ref_table, bg=bg)
     assert ref["n_capped"] == 0
     for k in FW + NEW:          # each deposit rounds once: half a count per event
         off = np.abs(tab[k].reshape(-1).astype(np.int64) - ref[k].reshape(-1).astype(np.int64))

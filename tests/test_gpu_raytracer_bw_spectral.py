@@ -13,73 +13,13 @@ import pytest
 import raytracer_phase_scenes as PS
 import raytracer_bw_spectral_ref as BSP
 import raytracer_bw_spectral_scenes as BSS
-from raytracer_dev import _be, _dev, _u64
-from rte_rrtmgp_cpp_amd import phase_tables, pipeline
+from raytracer_dev import _be, _u64, dev, device_table, numbers, k_null_all, backward_bg, backward_spectral, solve_bw_bg, render_spectral
+from rte_rrtmgp_cpp_amd import pipeline
 
 pytestmark = pytest.mark.gpu
-NO_TRIPLE = (None, None, None)
 BWK = ("counts", "n_capped", "n_clamped")
 CHUNK = "RRX_RT_SPECTRAL_GPT_PER_LAUNCH"
 NPIX = BSS.NPX*BSS.NPY
-
-
-class DevBackground:
-    def __init__(self, be, bg):
-        self.dz = np.ascontiguousarray(bg.dz, dtype=be.np_dtype)
-        self.tau, self.ssa = be.asarray(bg.tau), be.asarray(bg.ssa)
-        self.cloud = None if bg.cloud is None else tuple(be.asarray(c) for c in bg.cloud)
-        self.aerosol = None if bg.aerosol is None else tuple(be.asarray(c) for c in bg.aerosol)
-
-
-def dev(be, sc, bg):
-    d = _dev(be, sc)
-    d["aer"] = NO_TRIPLE if sc.aerosol is None else tuple(be.asarray(c) for c in sc.aerosol)
-    return d, (None if bg is None else DevBackground(be, bg))
-
-
-def device_table(be, sc):
-    t = phase_tables.build(be, *PS.double_hg33(), PS.RE0, PS.DRE)
-    return t.with_radius(be.asarray(PS.cell_radii(sc, be.np_dtype)))
-
-
-def per_gpt(be, sc, d, dbg, sensor, g, ray0, n, phase=None):
-    """rrx_rt_bw_trace_counts_aer of g-point g with the per-g-point k_null and profile"""
-    kn = be.rt_k_null(d["tau"], g, sc.nx, sc.ny, sc.dz, sc.kn_grid, sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"], aerosol=d["aer"])
-    return be.rt_bw_trace_counts_bg(d["tau"], d["ssa"], g, sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, sc.kn_grid, kn,
-                                    sensor, sc.seed, ray0, n, top_at_1=sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"], phase=phase,
-                                    background=dbg, aerosol=d["aer"])
-
-
-def k_null_all(be, sc, d):
-    return be.rt_k_null_all(d["tau"], sc.nx, sc.ny, sc.dz, sc.kn_grid, sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"], aerosol=d["aer"])
-
-
-def spectral(be, sc, d, dbg, sensor, lists, ray0, n, phase=None, counts=None, kn=None):
-    ray_end, w0 = lists
-    return be.camera_trace_counts_spectral(d["tau"], d["ssa"], sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, ray_end, w0,
-                                           sc.kn_grid, k_null_all(be, sc, d) if kn is None else kn, sensor, sc.seed, ray0, n, d["lims"],
-                                           top_at_1=sc.top_at_1, cloud=d["cloud"], counts=counts, phase=phase, background=dbg,
-                                           aerosol=d["aer"])
-
-
-def render(be, sc, d, dbg, sensor, m, M, phase=None):
-    r = be.camera_render_spectral(d["tau"], d["ssa"], sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, sc.inc_dir, sc.kn_grid,
-                                  sensor, m, sc.seed, d["lims"], M, top_at_1=sc.top_at_1, cloud=d["cloud"], phase=phase, background=dbg,
-                                  aerosol=d["aer"])
-    r["radiance"] = be.to_numpy(r["radiance"]).reshape(-1, NPIX)
-    return r
-
-
-def loop(be, sc, d, dbg, sensor, rpp, phase=None):
-    r = be.raytracer_bw_bg(d["tau"], d["ssa"], sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, sc.inc_dir, sc.kn_grid,
-                           sensor, rpp, sc.seed, top_at_1=sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"], phase=phase, background=dbg,
-                           aerosol=d["aer"])
-    r["radiance"] = be.to_numpy(r["radiance"]).reshape(-1)
-    return r
-
-
-def numbers(be, c):
-    return {k: _u64(be, c[k]) for k in BWK}
 
 
 # ---- 1: the sum over the band's g-points
@@ -98,14 +38,14 @@ def test_with_unit_weights_a_band_s_counts_are_the_integer_sum_over_its_g_points
     phase = device_table(be, sc) if with_table else None
     m = np.array([3, 3, 0, 3, 3])
     ray_end, _, _ = BSP.ray_list(sc, sensor, m)
-    got = numbers(be, spectral(be, sc, d, dbg, sensor, (ray_end, np.ones(BSS.NGPT)), 0, int(ray_end[-1]), phase=phase))
+    got = numbers(be, backward_spectral(be, sc, d, dbg, sensor, (ray_end, np.ones(BSS.NGPT)), 0, int(ray_end[-1]), phase=phase))
     assert got["counts"].shape == (BSS.NBND, NPIX)
     capped = clamped = 0
     for b, band in enumerate(BSS.BANDS):
         want = np.zeros(NPIX, dtype=np.uint64)
         for g in band:
             if m[g] > 0:
-                c = numbers(be, per_gpt(be, sc, d, dbg, sensor, g, 0, 3*NPIX, phase=phase))
+                c = numbers(be, backward_bg(be, sc, d, dbg, sensor, g, 0, 3*NPIX, phase=phase, aer=True))
                 want = want + c["counts"]
                 capped += int(c["n_capped"][0]); clamped += int(c["n_clamped"][0])
         assert np.array_equal(got["counts"][b], want) and want.any(), b
@@ -128,26 +68,26 @@ def test_ranges_add_up_and_the_dealing_does_not_matter(dt, hip_f64, hip_f32, mon
     n = int(ray_end[-1])
     assert n > 4*256 and ray_end[2] == ray_end[3]
     kn = k_null_all(be, sc, d)
-    whole = numbers(be, spectral(be, sc, d, dbg, sensor, (ray_end, w0), 0, n, kn=kn))
+    whole = numbers(be, backward_spectral(be, sc, d, dbg, sensor, (ray_end, w0), 0, n, kn=kn))
     assert int(whole["n_capped"][0]) == 0 and whole["counts"].any(axis=1).all()
     for cuts in ((0, int(ray_end[1]) - 5, int(ray_end[2]), n), (0, int(ray_end[1]), int(ray_end[3]) + 7, n)):
         parts = None
         for a, b in zip(cuts[:-1], cuts[1:]):
-            parts = spectral(be, sc, d, dbg, sensor, (ray_end, w0), a, b - a, kn=kn, counts=parts)
+            parts = backward_spectral(be, sc, d, dbg, sensor, (ray_end, w0), a, b - a, kn=kn, counts=parts)
         parts = numbers(be, parts)
         for k in BWK:
             assert np.array_equal(whole[k], parts[k]), (cuts, k)
     monkeypatch.setenv("RRX_RT_MAX_BLOCKS", "1")
-    deep = numbers(be, spectral(be, sc, d, dbg, sensor, (ray_end, w0), 0, n, kn=kn))
+    deep = numbers(be, backward_spectral(be, sc, d, dbg, sensor, (ray_end, w0), 0, n, kn=kn))
     monkeypatch.delenv("RRX_RT_MAX_BLOCKS")
     for k in BWK:
         assert np.array_equal(whole[k], deep[k]), k
     # the binding refuses a list that does not ascend and a range beyond the list
     bad = ray_end.copy(); bad[2] = bad[1] - 1
     with pytest.raises(ValueError, match="must not descend"):
-        spectral(be, sc, d, dbg, sensor, (bad, w0), 0, 8, kn=kn)
+        backward_spectral(be, sc, d, dbg, sensor, (bad, w0), 0, 8, kn=kn)
     with pytest.raises(ValueError, match="beyond the list"):
-        spectral(be, sc, d, dbg, sensor, (ray_end, w0), n - 4, 8, kn=kn)
+        backward_spectral(be, sc, d, dbg, sensor, (ray_end, w0), n - 4, 8, kn=kn)
 
 
 # ---- 3: chunking
@@ -162,21 +102,21 @@ def test_the_result_does_not_depend_on_the_chunking(dt, scene, hip_f64, hip_f32,
     m = pipeline.spectral_allocation(sc.inc_dir.astype(np.float64), 24)
     M = np.eye(BSS.NBND)
     monkeypatch.delenv(CHUNK, raising=False)
-    whole = render(be, sc, d, dbg, sensor, m, M)
+    whole = render_spectral(be, sc, d, dbg, sensor, m, M)
     assert whole["n_capped"] == 0 and whole["n_clamped"] == 0 and whole["radiance"].any(axis=1).all()
     for chunk in ("1", "2"):
         monkeypatch.setenv(CHUNK, chunk)
-        got = render(be, sc, d, dbg, sensor, m, M)
+        got = render_spectral(be, sc, d, dbg, sensor, m, M)
         assert np.array_equal(whole["radiance"].view(np.uint8), got["radiance"].view(np.uint8)), chunk
         assert got["n_capped"] == 0 and got["n_clamped"] == 0
     monkeypatch.delenv(CHUNK)
     # no rays at all: zeroed outputs; refused lists
-    none = render(be, sc, d, dbg, sensor, np.zeros(BSS.NGPT, dtype=np.int64), M)
+    none = render_spectral(be, sc, d, dbg, sensor, np.zeros(BSS.NGPT, dtype=np.int64), M)
     assert none["n_capped"] == 0 and not none["radiance"].any()
     with pytest.raises(RuntimeError, match="no incident flux"):
-        render(be, sc, d, dbg, sensor, np.array([1, 1, 1, 1, 1]), M)
+        render_spectral(be, sc, d, dbg, sensor, np.array([1, 1, 1, 1, 1]), M)
     with pytest.raises(RuntimeError, match="negative at g-point 3"):
-        render(be, sc, d, dbg, sensor, np.array([1, 1, 0, -1, 1]), M)
+        render_spectral(be, sc, d, dbg, sensor, np.array([1, 1, 0, -1, 1]), M)
 
 
 # ---- 4: the weights against the restatement
@@ -197,7 +137,7 @@ def test_counts_with_uneven_weights_against_the_restatement(top_at_1, hip_f64):
     table.cld_re = PS.cell_radii(sc, np.float64)
     ray_end, w0, _ = BSP.ray_list(sc, sensor, m)
     ref = BSP.trace_counts(sc, bg, sensor, ray_end, w0, 0, int(ray_end[-1]), table=table)
-    got = numbers(be, spectral(be, sc, d, dbg, sensor, (ray_end, w0), 0, int(ray_end[-1]), phase=device_table(be, sc)))
+    got = numbers(be, backward_spectral(be, sc, d, dbg, sensor, (ray_end, w0), 0, int(ray_end[-1]), phase=device_table(be, sc)))
     assert ref["n_capped"] == 0 == int(got["n_capped"][0]) and ref["n_clamped"] == 0 == int(got["n_clamped"][0])
     off = np.abs(got["counts"].astype(np.int64) - ref["counts"].astype(np.int64))
     print(f"raytracer_bw_spectral against the restatement top_at_1={top_at_1}: worst difference {int(off.max())} counts of 2^-32, "
@@ -218,7 +158,7 @@ def test_the_weighted_estimate_is_unbiased(dt, hip_f64, hip_f32):
     d, dbg = dev(be, sc, None)
     m = pipeline.spectral_allocation(sc.inc_dir.astype(np.float64), 256)
     _, w0, U = BSP.ray_list(sc, sensor, m)
-    got = render(be, sc, d, dbg, sensor, m, np.eye(BSS.NBND))
+    got = render_spectral(be, sc, d, dbg, sensor, m, np.eye(BSS.NBND))
     assert got["n_capped"] == 0 and got["n_clamped"] == 0
     mean, sigma = BSS.bernoulli_sigma(sc, m, w0, U)
     p, c = BSS.bernoulli_expected(sc)
@@ -246,13 +186,13 @@ def test_channels(dt, hip_f64, hip_f32):
     d, dbg = dev(be, sc, bg)
     m = np.array([4, 1, 0, 2, 1])
     ray_end, w0, U = BSP.ray_list(sc, sensor, m)
-    c = spectral(be, sc, d, dbg, sensor, (ray_end, w0), 0, int(ray_end[-1]))
+    c = backward_spectral(be, sc, d, dbg, sensor, (ray_end, w0), 0, int(ray_end[-1]))
     F = np.dtype(be.np_dtype).type
     scale = float(F(U) / F(sc.mu0))          # (as the entry forms it, in the precision)
     x = (_u64(be, c["counts"]).astype(np.float64) * 2.0**-32).astype(F)
     bands = be.to_numpy(be.camera_channels(c["counts"], np.eye(BSS.NBND), scale))
     assert np.array_equal(bands, F(scale)*x) and np.all(bands > 0)
-    by_entry = render(be, sc, d, dbg, sensor, m, np.eye(BSS.NBND))["radiance"]
+    by_entry = render_spectral(be, sc, d, dbg, sensor, m, np.eye(BSS.NBND))["radiance"]
     assert np.array_equal(by_entry.view(np.uint8), bands.view(np.uint8))
     ones = be.to_numpy(be.camera_channels(c["counts"], np.ones((1, BSS.NBND)), scale))[0]
     in_order = bands[0] + bands[1]
@@ -281,8 +221,9 @@ def test_one_launch_against_the_loop(hip_f64):
     m = np.where(np.array(BSS.INC) > 0, 4, 0)
     ray_end, w0, U = BSP.ray_list(sc, sensor, m)
     n_dep = BSP.trace_counts(sc, bg, sensor, ray_end, w0, 0, int(ray_end[-1]))["n_dep"].sum(axis=0)
-    one = render(be, sc, d, dbg, sensor, m, np.ones((1, BSS.NBND)))
-    many = loop(be, sc, d, dbg, sensor, 4)
+    one = render_spectral(be, sc, d, dbg, sensor, m, np.ones((1, BSS.NBND)))
+    many = solve_bw_bg(be, sc, d, dbg, sensor, 4, aer=True)
+    many["radiance"] = be.to_numpy(many["radiance"]).reshape(-1)
     assert one["n_capped"] == many["n_capped"] == 0 and one["n_clamped"] == many["n_clamped"] == 0
     err = np.abs(one["radiance"][0] - many["radiance"])
     tol = 0.5*n_dep*2.0**-32*float(U)/sc.mu0
@@ -390,7 +331,7 @@ def test_cxx_class_gives_the_entry_bit_for_bit_and_throws(dt, scene, hip_f64, hi
     m = np.array([5, 1, 0, 2, 2])
     for given, total in ((m, -1), (np.zeros(BSS.NGPT, dtype=np.int64), 24)):
         dealt = given if total < 0 else pipeline.spectral_allocation(inc_dir, total)
-        want = render(be, sc, d, dbg, sensor, dealt, M, phase=phase)
+        want = render_spectral(be, sc, d, dbg, sensor, dealt, M, phase=phase)
         assert call(given, total) == 0, lib.rrx_cxx_driver_error().decode()
         torch.cuda.synchronize()
         assert n_capped.value == 0 == want["n_capped"] and n_clamped.value == 0 == want["n_clamped"]

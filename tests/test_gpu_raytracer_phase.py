@@ -231,7 +231,7 @@ def test_4_backward_ray_for_ray(kind, peaked, hip_f64):
     tol = np.zeros(npix)
     eps = np.finfo(np.float64).eps
     for g in range(2):
-        c = B.trace_counts(sc, sensor, g, 0, rpp*npix, table=ref_t)
+        c = B.trace_counts_bw(sc, sensor, g, 0, rpp*npix, table=ref_t)
         assert c["n_capped"] == 0 and c["n_clamped"] == 0
         scale = sc.inc_dir[g] / (sc.mu0*rpp)
         want = R.counts_to_flux(c["counts"], scale, want)

@@ -10,69 +10,16 @@ import numpy as np
 import pytest
 
 import raytracer_ref as R
-import raytracer_bg_ref as BG
 import raytracer_phase_scenes as PS
 import raytracer_spectral_ref as SP
 import raytracer_spectral_scenes as SS
-from raytracer_dev import _be, _dev, _u64
-from rte_rrtmgp_cpp_amd import phase_tables, pipeline
+from raytracer_dev import _be, NO_TRIPLE, dev, device_table, numbers, k_null, k_null_all, forward_bg, forward_spectral, solve_fw_spectral
+from rte_rrtmgp_cpp_amd import pipeline
 
 pytestmark = pytest.mark.gpu
-FW, NEW = R.COUNT_NAMES, BG.BG_COUNT_NAMES
-NO_TRIPLE = (None, None, None)
+FW, NEW = R.COUNT_NAMES, R.BG_COUNT_NAMES
 ACTIVE = (0, 1, 3, 4)
 CHUNK = "RRX_RT_SPECTRAL_GPT_PER_LAUNCH"
-
-
-class DevBackground:
-    def __init__(self, be, bg):
-        self.dz = np.ascontiguousarray(bg.dz, dtype=be.np_dtype)
-        self.tau, self.ssa = be.asarray(bg.tau), be.asarray(bg.ssa)
-        self.cloud = None if bg.cloud is None else tuple(be.asarray(c) for c in bg.cloud)
-        self.aerosol = None if bg.aerosol is None else tuple(be.asarray(c) for c in bg.aerosol)
-
-
-def dev(be, sc, bg):
-    d = _dev(be, sc)
-    d["aer"] = NO_TRIPLE if sc.aerosol is None else tuple(be.asarray(c) for c in sc.aerosol)
-    return d, (None if bg is None else DevBackground(be, bg))
-
-
-def device_table(be, sc):
-    t = phase_tables.build(be, *PS.double_hg33(), PS.RE0, PS.DRE)
-    return t.with_radius(be.asarray(PS.cell_radii(sc, be.np_dtype)))
-
-
-def per_gpt(be, sc, d, dbg, g, photon0, n, phase=None):
-    """rrx_rt_trace_counts_aer of g-point g with the per-g-point k_null and profile"""
-    kn = be.rt_k_null(d["tau"], g, sc.nx, sc.ny, sc.dz, sc.kn_grid, sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"], aerosol=d["aer"])
-    return be.rt_trace_counts_bg(d["tau"], d["ssa"], g, sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, float(sc.inc_dir[g]),
-                                 float(sc.inc_dif[g]), sc.kn_grid, kn, sc.seed, photon0, n, top_at_1=sc.top_at_1,
-                                 independent_column=sc.independent_column, cloud=d["cloud"], band_lims=d["lims"], phase=phase,
-                                 background=dbg, aerosol=d["aer"])
-
-
-def k_null_all(be, sc, d):
-    return be.rt_k_null_all(d["tau"], sc.nx, sc.ny, sc.dz, sc.kn_grid, sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"], aerosol=d["aer"])
-
-
-def spectral(be, sc, d, dbg, lists, photon0, n, phase=None, counts=None, kn=None):
-    pe, w0, df = lists
-    return be.rt_trace_counts_spectral(d["tau"], d["ssa"], sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, pe, w0, df,
-                                       sc.kn_grid, k_null_all(be, sc, d) if kn is None else kn, sc.seed, photon0, n, top_at_1=sc.top_at_1,
-                                       independent_column=sc.independent_column, cloud=d["cloud"], band_lims=d["lims"], counts=counts,
-                                       phase=phase, background=dbg, aerosol=d["aer"])
-
-
-def solve(be, sc, d, dbg, m, phase=None):
-    r = be.raytracer_sw_spectral(d["tau"], d["ssa"], sc.nx, sc.ny, sc.dx, sc.dy, sc.dz, d["alb"], sc.mu0, sc.azimuth, sc.inc_dir, sc.inc_dif,
-                                 sc.kn_grid, m, sc.seed, top_at_1=sc.top_at_1, independent_column=sc.independent_column, cloud=d["cloud"],
-                                 band_lims=d["lims"], phase=phase, background=dbg, aerosol=d["aer"])
-    return {k: (be.to_numpy(v) if k != "n_capped" else v) for k, v in r.items()}
-
-
-def numbers(be, c):
-    return {k: _u64(be, v) for k, v in c.items()}
 
 
 def keys_of(bg):
@@ -90,8 +37,7 @@ def test_k_null_all_and_bg_profile_all_are_the_per_g_point_entries_slice_by_slic
         kn = be.to_numpy(k_null_all(be, sc, d))
         assert kn.shape == (SS.NGPT,) + tuple(sc.kn_grid[::-1])
         for g in range(SS.NGPT):
-            one = be.to_numpy(be.rt_k_null(d["tau"], g, sc.nx, sc.ny, sc.dz, sc.kn_grid, sc.top_at_1, cloud=d["cloud"], band_lims=d["lims"],
-                                           aerosol=d["aer"]))
+            one = be.to_numpy(k_null(be, sc, d, g, aer=True))
             assert np.array_equal(kn[g].view(np.uint8), one.view(np.uint8)) and one.max() > 0, (make.__name__, g)
         if bg is not None:
             prof = be.to_numpy(be.rt_bg_profile_all(dbg, d["lims"]))
@@ -122,10 +68,10 @@ def test_with_unit_weights_the_counts_are_the_integer_sum_over_g_points(dt, scen
     m = np.array([8, 8, 0, 8, 8])
     pe, w0, df, _ = SP.photon_list(sc, m)
     w0 = np.where(m > 0, 1.0, 0.0)
-    got = numbers(be, spectral(be, sc, d, dbg, (pe, w0, df), 0, int(pe[-1]), phase=phase))
+    got = numbers(be, forward_spectral(be, sc, d, dbg, (pe, w0, df), 0, int(pe[-1]), phase=phase))
     want = None
     for g in ACTIVE:
-        c = numbers(be, per_gpt(be, sc, d, dbg, g, 0, 8*sc.ncol, phase=phase))
+        c = numbers(be, forward_bg(be, sc, d, dbg, g, 0, 8*sc.ncol, phase=phase, aer=True))
         want = c if want is None else {k: want[k] + c[k] for k in c}
     assert int(got["n_capped"][0]) == 0
     for k in keys_of(bg) + ("n_capped",):
@@ -147,26 +93,26 @@ def test_ranges_add_up_and_the_dealing_does_not_matter(dt, hip_f64, hip_f32, mon
     n = int(pe[-1])
     assert n > 4*256 and pe[2] == pe[3]
     kn = k_null_all(be, sc, d)
-    whole = numbers(be, spectral(be, sc, d, dbg, (pe, w0, df), 0, n, kn=kn))
+    whole = numbers(be, forward_spectral(be, sc, d, dbg, (pe, w0, df), 0, n, kn=kn))
     assert int(whole["n_capped"][0]) == 0 and all(whole[k].any() for k in NEW)
     for cuts in ((0, int(pe[1]) - 5, int(pe[2]), n), (0, int(pe[1]), int(pe[3]) + 7, n)):
         parts = None
         for a, b in zip(cuts[:-1], cuts[1:]):
-            parts = spectral(be, sc, d, dbg, (pe, w0, df), a, b - a, kn=kn, counts=parts)
+            parts = forward_spectral(be, sc, d, dbg, (pe, w0, df), a, b - a, kn=kn, counts=parts)
         parts = numbers(be, parts)
         for k in FW + NEW + ("n_capped",):
             assert np.array_equal(whole[k], parts[k]), (cuts, k)
     monkeypatch.setenv("RRX_RT_MAX_BLOCKS", "1")
-    deep = numbers(be, spectral(be, sc, d, dbg, (pe, w0, df), 0, n, kn=kn))
+    deep = numbers(be, forward_spectral(be, sc, d, dbg, (pe, w0, df), 0, n, kn=kn))
     monkeypatch.delenv("RRX_RT_MAX_BLOCKS")
     for k in FW + NEW + ("n_capped",):
         assert np.array_equal(whole[k], deep[k]), k
     # the binding refuses a list that does not ascend and a range beyond the list
     bad = pe.copy(); bad[2] = bad[1] - 1
     with pytest.raises(ValueError, match="must not descend"):
-        spectral(be, sc, d, dbg, (bad, w0, df), 0, 8, kn=kn)
+        forward_spectral(be, sc, d, dbg, (bad, w0, df), 0, 8, kn=kn)
     with pytest.raises(ValueError, match="beyond the list"):
-        spectral(be, sc, d, dbg, (pe, w0, df), n - 4, 8, kn=kn)
+        forward_spectral(be, sc, d, dbg, (pe, w0, df), n - 4, 8, kn=kn)
 
 
 # ---- 8: chunking
@@ -179,22 +125,22 @@ def test_the_result_does_not_depend_on_the_chunking(dt, scene, hip_f64, hip_f32,
     d, dbg = dev(be, sc, bg)
     m = pipeline.spectral_allocation(sc.inc_dir.astype(np.float64) + sc.inc_dif, 24)
     monkeypatch.delenv(CHUNK, raising=False)
-    whole = solve(be, sc, d, dbg, m)
+    whole = solve_fw_spectral(be, sc, d, dbg, m)
     assert whole["n_capped"] == 0 and whole["abs_dif"].any()
     for chunk in ("1", "2"):
         monkeypatch.setenv(CHUNK, chunk)
-        got = solve(be, sc, d, dbg, m)
+        got = solve_fw_spectral(be, sc, d, dbg, m)
         for k in keys_of(bg):
             assert np.array_equal(whole[k].view(np.uint8), got[k].view(np.uint8)), (chunk, k)
         assert got["n_capped"] == 0
     monkeypatch.delenv(CHUNK)
     # no photons at all: zeroed outputs; a refused list
-    none = solve(be, sc, d, dbg, np.zeros(SS.NGPT, dtype=np.int64))
+    none = solve_fw_spectral(be, sc, d, dbg, np.zeros(SS.NGPT, dtype=np.int64))
     assert none["n_capped"] == 0 and not any(none[k].any() for k in keys_of(bg))
     with pytest.raises(RuntimeError, match="no incident flux"):
-        solve(be, sc, d, dbg, np.array([1, 1, 1, 1, 1]))
+        solve_fw_spectral(be, sc, d, dbg, np.array([1, 1, 1, 1, 1]))
     with pytest.raises(RuntimeError, match="negative at g-point 3"):
-        solve(be, sc, d, dbg, np.array([1, 1, 0, -1, 1]))
+        solve_fw_spectral(be, sc, d, dbg, np.array([1, 1, 0, -1, 1]))
 
 
 # ---- 9: the weights against the restatement
@@ -213,7 +159,7 @@ def test_fluxes_with_uneven_weights_against_the_restatement(top_at_1, hip_f64):
     table = P.build_tables(*PS.double_hg33(), np.float64, PS.RE0, PS.DRE)
     table.cld_re = PS.cell_radii(sc, np.float64)
     ref = SP.raytracer_sw(sc, bg, m, table=table)
-    got = solve(be, sc, d, dbg, m, phase=device_table(be, sc))
+    got = solve_fw_spectral(be, sc, d, dbg, m, phase=device_table(be, sc))
     assert ref["n_capped"] == 0 and got["n_capped"] == 0
     tol = ref["events"] * 2.0**-33 * float(ref["U"]) * max(float(ref["weight0"].max()), 1.0)
     for k in FW + NEW:
@@ -236,7 +182,7 @@ def test_the_weighted_estimate_is_unbiased(dt, hip_f64, hip_f32):
     d, dbg = dev(be, sc, bg)
     m = pipeline.spectral_allocation(sc.inc_dir.astype(np.float64) + sc.inc_dif, 64)
     _, w0, _, U = SP.photon_list(sc, m)
-    got = solve(be, sc, d, dbg, m)
+    got = solve_fw_spectral(be, sc, d, dbg, m)
     assert got["n_capped"] == 0
     mean, sigma = SS.beer_sigma(sc, bg, m, w0, U)
     want = (np.array(SS.INC)[:, None]*SS.beer_expected(sc, bg)).sum(axis=0)
@@ -346,7 +292,7 @@ def test_cxx_class_gives_the_entry_bit_for_bit_and_throws(dt, scene, hip_f64, hi
                                                ctypes.c_ulonglong(sc.seed), be.RT_MAX_EVENTS, out6, ctypes.byref(n_capped), out5, *table, *medium,
                                                *aer, *aloft, stream)
 
-    want = solve(be, sc, d, dbg, m, phase=phase)
+    want = solve_fw_spectral(be, sc, d, dbg, m, phase=phase)
     assert call(m) == 0, lib.rrx_cxx_driver_error().decode()
     torch.cuda.synchronize()
     assert n_capped.value == 0 and want["n_capped"] == 0

@@ -16,7 +16,7 @@ def test_s1_bernoulli_surface(view):
     sc = S.bernoulli(np.float64)
     sensor = S.bernoulli_sensors()[view]
     for g in range(2):
-        c = B.trace_counts(sc, sensor, g, 0, S.S1_RAYS*16)
+        c = B.trace_counts_bw(sc, sensor, g, 0, S.S1_RAYS*16)
         assert c["n_capped"] == 0 and c["n_clamped"] == 0
         S.check_bernoulli(sc, sensor, g, c["counts"], f"ref {view}")
         # every deposit is the same number: the count is a multiple of it up to one unit per deposit
@@ -27,7 +27,7 @@ def test_s1_bernoulli_surface(view):
 def test_s1_float32_runs_the_same_algorithm():
     sc = S.bernoulli(np.float32)
     sensor = S.bernoulli_sensors()["slant"]
-    c = B.trace_counts(sc, sensor, 0, 0, S.S1_RAYS*16)
+    c = B.trace_counts_bw(sc, sensor, 0, 0, S.S1_RAYS*16)
     assert c["n_capped"] == 0
     S.check_bernoulli(sc, sensor, 0, c["counts"], "ref f32 slant")
 
@@ -39,7 +39,7 @@ def test_s2_shadow_in_integers(along, top_at_1):
     dark, full = S.shadow_classes(sc)
     assert dark.sum() == 6 + 4 and full.sum() == sc.ncol - 6 - 8
     rays = 16
-    c = B.trace_counts(sc, B.orthographic(sc.nx, sc.ny, (0., 0., -1.)), 0, 0, rays*sc.ncol)
+    c = B.trace_counts_bw(sc, B.orthographic(sc.nx, sc.ny, (0., 0., -1.)), 0, 0, rays*sc.ncol)
     assert c["n_capped"] == 0 and c["n_clamped"] == 0
     assert np.all(c["counts"][dark] == 0), c["counts"][dark]
     assert np.all(c["counts"][full] == S.shadow_full_count(sc, rays)), c["counts"][full] / S.ONE
@@ -61,10 +61,10 @@ def test_s3_forward_against_backward(name, forward_general):
     worst = 0.0
     for g in range(2):
         assert fwd[g]["n_capped"] == 0
-        c = B.trace_counts(sc, sensor, g, 0, S.S3_RANGES*per_range, ranges=S.S3_RANGES)
+        c = B.trace_counts_bw(sc, sensor, g, 0, S.S3_RANGES*per_range, ranges=S.S3_RANGES)
         assert c["n_capped"] == 0 and c["n_clamped"] == 0
         if g == 0:          # a range tallied apart is the range traced alone
-            assert np.array_equal(B.trace_counts(sc, sensor, g, 3*per_range, per_range)["counts"], c["counts"][3])
+            assert np.array_equal(B.trace_counts_bw(sc, sensor, g, 3*per_range, per_range)["counts"], c["counts"][3])
         worst = max(worst, S.compare_forward_backward(sc, g, name, fwd[g][name], c["counts"], "ref"))
     print(f"raytracer_bw S3 ref {name}: worst {worst:.2f} combined sigma")
 
@@ -73,14 +73,14 @@ def test_counts_are_additive_over_ray_ranges_and_the_cap_is_counted():
     sc = S.general_direct(np.float64)
     sensor = B.Sensor(0, 6, 4, 0.0, (330., 250., 170.), (0.5, 0., 0.), (0., 0.4, 0.1), (0.2, 0.3, -0.9))
     n = 16*24
-    whole = B.trace_counts(sc, sensor, 1, 0, n)
-    a, b = B.trace_counts(sc, sensor, 1, 0, n//3), B.trace_counts(sc, sensor, 1, n//3, n - n//3)
+    whole = B.trace_counts_bw(sc, sensor, 1, 0, n)
+    a, b = B.trace_counts_bw(sc, sensor, 1, 0, n//3), B.trace_counts_bw(sc, sensor, 1, n//3, n - n//3)
     assert np.array_equal(whole["counts"], a["counts"] + b["counts"]) and np.array_equal(whole["n_dep"], a["n_dep"] + b["n_dep"])
     assert whole["events"] == a["events"] + b["events"] and whole["walk_cells"] == a["walk_cells"] + b["walk_cells"]
     assert whole["counts"].all() and whole["n_capped"] == 0 and whole["n_clamped"] == 0
     # the walk to the sun is bounded by construction
     assert whole["walk_cells"] <= whole["n_dep"].sum()*B.max_walk(sc)
-    capped = B.trace_counts(sc, sensor, 1, 0, n, max_events=1)
+    capped = B.trace_counts_bw(sc, sensor, 1, 0, n, max_events=1)
     assert 0 < capped["n_capped"] <= n
 
 
@@ -88,11 +88,11 @@ def test_a_sensor_that_looks_away_from_the_domain_sees_nothing():
     sc = S.general_direct(np.float64)
     z_top = sc.nz*sc.dz
     up = B.Sensor(0, 2, 2, 0.0, (100., 100., z_top + 50.), (0.1, 0., 0.), (0., 0.1, 0.), (0., 0., 1.))
-    c = B.trace_counts(sc, up, 0, 0, 64)
+    c = B.trace_counts_bw(sc, up, 0, 0, 64)
     assert not c["counts"].any() and c["events"] == 0 and c["n_capped"] == 0
     # from above the top, looking down: moved along the ray to the top, the same counts as the orthographic nadir view's geometry allows
     down = B.Sensor(0, 2, 2, 0.0, (100., 100., z_top + 50.), (0.1, 0., 0.), (0., 0.1, 0.), (0., 0., -1.))
-    assert B.trace_counts(sc, down, 0, 0, 64)["counts"].any()
+    assert B.trace_counts_bw(sc, down, 0, 0, 64)["counts"].any()
 
 
 def test_camera_helper_builds_orthonormal_axes_from_the_geometry():

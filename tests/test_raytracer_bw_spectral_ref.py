@@ -1,10 +1,10 @@
 """CPU tests of the restatement of the backward tracer with the rays of all g-points in one launch (raytracer_bw_spectral_ref.py,
-DESIGN 4.21): with unit weights the counts of a band are the integer sum of raytracer_aer_ref.trace_counts_bw over its g-points,
+DESIGN 4.21): with unit weights the counts of a band are the integer sum of raytracer_bw_ref.trace_counts_bw over its g-points,
 ranges of the list add up, the clamp follows the weight, and the channel matrix is a sum in band order."""
 import numpy as np
 import pytest
 
-import raytracer_aer_ref as A
+import raytracer_bw_ref as B
 import raytracer_bw_spectral_ref as BSP
 import raytracer_bw_spectral_scenes as BSS
 
@@ -26,7 +26,7 @@ def test_unit_weights_give_the_integer_sum_over_the_band_s_g_points(scene):
         want = np.zeros(npix, dtype=np.uint64)
         for g in band:
             if m[g] > 0:
-                want = want + A.trace_counts_bw(sc, bg, sensor, g, 0, int(m[g])*npix)["counts"]
+                want = want + B.trace_counts_bw(sc, sensor, g, 0, int(m[g])*npix, bg=bg)["counts"]
         assert np.array_equal(got["counts"][b], want) and want.any(), b
     assert got["n_capped"] == 0 and got["n_clamped"] == 0
 

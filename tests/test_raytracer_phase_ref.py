@@ -134,7 +134,7 @@ def test_backward_restatement_with_an_isotropic_table_is_the_hg_restatement_with
     t = P.build_tables(*PS.isotropic(2, 1), np.float64, PS.RE0, PS.DRE)
     t.cld_re = PS.cell_radii_with_nan(sc, np.float64)
     sensor = B.flux_sensor(sc.nx, sc.ny, True)
-    a, b = B.trace_counts(sc, sensor, 0, 0, 320), B.trace_counts(sc, sensor, 0, 0, 320, table=t)
+    a, b = B.trace_counts_bw(sc, sensor, 0, 0, 320), B.trace_counts_bw(sc, sensor, 0, 0, 320, table=t)
     for k in ("counts", "n_dep", "n_capped", "n_clamped", "events", "walk_cells"):
         assert np.array_equal(a[k], b[k]), k
     assert a["counts"].any()

@@ -5,12 +5,14 @@ import numpy as np
 import pytest
 
 import raytracer_ref as R
-import raytracer_aer_ref as A
+import raytracer_bw_ref as B
+import raytracer_phase_ref as P
 import raytracer_spectral_ref as SP
+import raytracer_bw_spectral_ref as BSP
 import raytracer_spectral_scenes as SS
 from rte_rrtmgp_cpp_amd import pipeline, synthetic
 
-COUNTS = SP.ALL_COUNTS + ("n_capped", "events")
+COUNTS = R.ALL_COUNTS + ("n_capped", "events")
 
 
 # ---- 1: the allocation
@@ -92,14 +94,12 @@ def test_with_unit_weights_the_counts_are_the_integer_sum_over_g_points(with_bg)
     got = SP.trace_counts(sc, bg, pe, np.ones(5), 0, int(pe[-1]))
     want = None
     for g in (0, 1, 3, 4):
-        c = A.trace_counts(sc, bg, g, 0, 2*sc.ncol)
+        c = R.trace_counts(sc, g, 0, 2*sc.ncol, bg=bg)
         want = c if want is None else {k: want[k] + c[k] for k in COUNTS}
     for k in COUNTS:
         assert np.array_equal(got[k], want[k]), k
     assert got["n_capped"] == 0 and got["abs_dif"].any() and got["sfc_dn_dif"].any()
     assert got["toa_up"].any() == with_bg
-    # to_count is back in place
-    assert R.to_count.__module__ == "raytracer_ref"
 
 
 def test_ranges_add_up_exactly_inside_a_g_point_and_on_a_boundary():
@@ -122,12 +122,29 @@ def test_ranges_add_up_exactly_inside_a_g_point_and_on_a_boundary():
     assert two["events"] == one["events"]
 
 
-def test_the_restatement_leaves_to_count_alone_when_it_raises():
-    plain = R.to_count
-    with pytest.raises(ZeroDivisionError):
-        with SP.weighted(2.0):
-            1/0
-    assert R.to_count is plain
+def test_the_restatement_binds_nothing_while_it_runs():
+    """The weight, the background, the aerosol and the table are arguments of the event loops: after a forward and a backward
+    spectral call, and after a call that raises part-way (its second g-point has no weight), every attribute of every restatement
+    module is bound to the object it was bound to before."""
+    import raytracer_bw_spectral_scenes as BSS
+    modules = (R, B, P, SP, BSP)
+    before = [dict(vars(mod)) for mod in modules]
+    sc, bg = SS.general(np.float64)
+    sensor = BSS.sensors(sc)["inside"]
+    m = np.array([1, 1, 0, 1, 1])
+    pe, w0, _, _ = SP.photon_list(sc, m)
+    assert SP.trace_counts(sc, bg, pe, w0, 0, int(pe[-1]))["abs_dif"].any()
+    re, rw0, _ = BSP.ray_list(sc, sensor, m)
+    assert BSP.trace_counts(sc, bg, sensor, re, rw0, 0, int(re[-1]))["counts"].any()
+    with pytest.raises(IndexError):
+        SP.trace_counts(sc, bg, pe, w0[:1], 0, int(pe[-1]))
+    with pytest.raises(IndexError):
+        BSP.trace_counts(sc, bg, sensor, re, rw0[:1], 0, int(re[-1]))
+    for mod, was in zip(modules, before):
+        now = vars(mod)
+        assert set(now) == set(was), mod.__name__
+        for k, v in was.items():
+            assert now[k] is v, (mod.__name__, k)
 
 
 # ---- 4: what the allocation is for

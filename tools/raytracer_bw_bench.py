@@ -46,7 +46,7 @@ def restatement_counts(C, tau, ssa, cloud, lims, albedo, nx, ny, nz, cut, rays_p
     out = {}
     for name, cam in cameras(C, cut, cut, nz, cut, cut).items():
         nrays = rays_per_pixel*cam.npix
-        c = B.trace_counts(sc, cam, 0, 0, nrays)
+        c = B.trace_counts_bw(sc, cam, 0, 0, nrays)
         out[name] = dict(rays=nrays, events_per_ray=round(c["events"]/nrays, 3), walk_cells_per_ray=round(c["walk_cells"]/nrays, 3),
                          deposits_per_ray=round(int(c["n_dep"].sum())/nrays, 3), n_capped=c["n_capped"], walk_bound=B.max_walk(sc))
     return out

@@ -50,7 +50,7 @@ def scatterings_on_cut(C, tau, ssa, cloud, lims, albedo, re, nx, nz, cut, table_
     f = R.trace_counts(sc, 0, 0, n, table=table_np)
     out = {"forward": dict(photons=n, events_per_photon=round(f["events"]/n, 3), cloud_scatterings_per_photon=round(f["cloud_scatterings"]/n, 3))}
     for name, cam in cameras(C, cut, cut, nz, cut, cut).items():
-        b = B.trace_counts(sc, cam, 0, 0, 4*cam.npix, table=table_np)
+        b = B.trace_counts_bw(sc, cam, 0, 0, 4*cam.npix, table=table_np)
         out[name] = dict(rays=4*cam.npix, events_per_ray=round(b["events"]/(4*cam.npix), 3),
                          cloud_scatterings_per_ray=round(b["cloud_scatterings"]/(4*cam.npix), 3))
     return out
