@@ -31,7 +31,7 @@
 //     collision: deposit weight (1 - f_no_abs), weight *= f_no_abs;  weight < 0.5: u -> roulette as above;
 //              survivor: u -> scatter or null collision;  scatter: u -> species;  u -> cos of the scattering angle;  u -> phi
 //
-// WITH A BACKGROUND (trace_kernel<F,TABLE,true>, the rrx_*_bg entries; rrx_rt_common.h; tests/raytracer_bg_ref.py
+// WITH A BACKGROUND (trace_kernel<F,TABLE,true>, the rrx_*_bg entries; rrx_rt_common.h; tests/raytracer_ref.py
 // restates it) the DRAW ORDER is the same:
 //   start:     the same draws; the photon starts at TOA, z = z_bg[nbg], in layer nbg-1 (block index knz + nbg - 1) with the x, y,
 //              pixel and block (in, jn) of the start without a background
@@ -48,7 +48,7 @@
 // The spectral loop scales toa_up, tod_dn_dir, tod_dn_dif like the other fluxes and bg_abs_* [b] by (scale/dz_bg[b])/F(ncol): W m-3 of
 // a layer that spans the whole domain.
 //
-// WITH AEROSOL (trace_kernel<F,TABLE,true,true>, the rrx_*_aer entries; rrx_rt_common.h; tests/raytracer_aer_ref.py restates
+// WITH AEROSOL (trace_kernel<F,TABLE,true,true>, the rrx_*_aer entries; rrx_rt_common.h; tests/raytracer_ref.py restates
 // it): a third species with its own band triple in the grid and in the background. k_ext, k_sca and k_null take tau_a as
 // rrx_rt_common.h writes them, abs_* and bg_abs_* take what aerosol absorbs through f_no_abs, and the draw count and DRAW ORDER are
 // unchanged: the species uniform u picks cloud iff u k_sca < k_sca_cld, otherwise aerosol iff u k_sca < k_sca_cld + k_sca_aer,
@@ -66,9 +66,10 @@ namespace
 using namespace rrx;
 using namespace rrx::rt;
 
-// the maximum of ((tau + tau_c) + tau_a)/dz over the cells of block n of the k_null grid, for g-point igpt
-template<typename F>
-__device__ __forceinline__ F k_null_aer_of_block(
+// the maximum of k_ext over the cells of block n of the k_null grid, for g-point igpt: ((tau + tau_c) + tau_a)/dz with AER (aer_tau is
+// then not NULL), otherwise the two-term (tau + tau_c)/dz, not (tau + tau_c) + 0
+template<typename F, bool AER>
+__device__ __forceinline__ F k_null_of_block(
         const int n, const int nx, const int ny, const int nz, const int nbnd, const int igpt, const int top_at_1,
         const F* __restrict__ tau, const int* __restrict__ band_lims_gpt, const F* __restrict__ cld_tau, const F* __restrict__ aer_tau,
         const F dz, const int knx, const int kny, const int knz)
@@ -76,7 +77,7 @@ __device__ __forceinline__ F k_null_aer_of_block(
     const int in = n % knx, jn = (n / knx) % kny, kn = n / (knx*kny);
     const int rx = nx/knx, ry = ny/kny, rz = nz/knz;
     const size_t ncol = size_t(nx)*ny;
-    const int ibnd = (cld_tau != nullptr || aer_tau != nullptr) ? band_of(igpt, nbnd, band_lims_gpt) : -1;
+    const int ibnd = (cld_tau != nullptr || AER) ? band_of(igpt, nbnd, band_lims_gpt) : -1;
     F m = F(0.);
     for (int k=kn*rz; k<(kn+1)*rz; ++k)
     {
@@ -86,65 +87,27 @@ __device__ __forceinline__ F k_null_aer_of_block(
             {
                 const size_t cell = size_t(i) + size_t(j)*nx + ncol*lay;
                 const F tc = (ibnd >= 0 && cld_tau != nullptr) ? cld_tau[cell + ncol*nz*ibnd] : F(0.);
-                const F ta = (ibnd >= 0 && aer_tau != nullptr) ? aer_tau[cell + ncol*nz*ibnd] : F(0.);
-                m = max(m, k_ext_of(tau[cell + ncol*nz*igpt], tc, ta, dz));
+                if constexpr (AER) m = max(m, k_ext_of(tau[cell + ncol*nz*igpt], tc, ibnd >= 0 ? aer_tau[cell + ncol*nz*ibnd] : F(0.), dz));
+                else m = max(m, k_ext_of(tau[cell + ncol*nz*igpt], tc, dz));
             }
     }
     return m;
 }
 
-// k_null_kernel with aerosol
+// k_null (ng, knz, kny, knx) of the ng g-points from g0 on (one of them: rrx_rt_k_null and the per-g-point loops),
+// blockIdx.y counting them. aer_tau: NULL for a medium without aerosol; the test is uniform over the launch.
 template<typename F>
-__global__ void __launch_bounds__(256) k_null_aer_kernel(
-        const int nx, const int ny, const int nz, const int nbnd, const int igpt, const int top_at_1,
-        const F* __restrict__ tau, const int* __restrict__ band_lims_gpt, const F* __restrict__ cld_tau, const F* __restrict__ aer_tau,
-        const F dz, const int knx, const int kny, const int knz, F* __restrict__ k_null)
-{
-    const int n = blockIdx.x*blockDim.x + threadIdx.x;
-    if (n >= knx*kny*knz) return;
-    k_null[n] = k_null_aer_of_block<F>(n, nx, ny, nz, nbnd, igpt, top_at_1, tau, band_lims_gpt, cld_tau, aer_tau, dz, knx, kny, knz);
-}
-
-// k_null_aer_kernel for the ng g-points from g0 on, blockIdx.y counting them: slice g - g0 of k_null (ng, knz, kny, knx)
-// holds what k_null_aer_kernel(igpt = g) writes
-template<typename F>
-__global__ void __launch_bounds__(256) k_null_all_kernel(
+__global__ void __launch_bounds__(256) k_null_kernel(
         const int nx, const int ny, const int nz, const int nbnd, const int g0, const int top_at_1,
         const F* __restrict__ tau, const int* __restrict__ band_lims_gpt, const F* __restrict__ cld_tau, const F* __restrict__ aer_tau,
         const F dz, const int knx, const int kny, const int knz, F* __restrict__ k_null)
 {
     const int n = blockIdx.x*blockDim.x + threadIdx.x;
     if (n >= knx*kny*knz) return;
-    k_null[size_t(blockIdx.y)*(size_t(knx)*kny*knz) + n] =
-        k_null_aer_of_block<F>(n, nx, ny, nz, nbnd, g0 + int(blockIdx.y), top_at_1, tau, band_lims_gpt, cld_tau, aer_tau, dz, knx, kny, knz);
-}
-
-// k_null(in, jn, kn) = the maximum of k_ext over the block's cells, for one g-point
-template<typename F>
-__global__ void __launch_bounds__(256) k_null_kernel(
-        const int nx, const int ny, const int nz, const int nbnd, const int igpt, const int top_at_1,
-        const F* __restrict__ tau, const int* __restrict__ band_lims_gpt, const F* __restrict__ cld_tau, const F dz,
-        const int knx, const int kny, const int knz, F* __restrict__ k_null)
-{
-    const int n = blockIdx.x*blockDim.x + threadIdx.x;
-    if (n >= knx*kny*knz) return;
-    const int in = n % knx, jn = (n / knx) % kny, kn = n / (knx*kny);
-    const int rx = nx/knx, ry = ny/kny, rz = nz/knz;
-    const size_t ncol = size_t(nx)*ny;
-    const int ibnd = cld_tau != nullptr ? band_of(igpt, nbnd, band_lims_gpt) : -1;
-    F m = F(0.);
-    for (int k=kn*rz; k<(kn+1)*rz; ++k)
-    {
-        const int lay = top_at_1 ? nz-1-k : k;
-        for (int j=jn*ry; j<(jn+1)*ry; ++j)
-            for (int i=in*rx; i<(in+1)*rx; ++i)
-            {
-                const size_t cell = size_t(i) + size_t(j)*nx + ncol*lay;
-                const F tc = ibnd >= 0 ? cld_tau[cell + ncol*nz*ibnd] : F(0.);
-                m = max(m, k_ext_of(tau[cell + ncol*nz*igpt], tc, dz));
-            }
-    }
-    k_null[n] = m;
+    const int igpt = g0 + int(blockIdx.y);
+    k_null[size_t(blockIdx.y)*(size_t(knx)*kny*knz) + n] = aer_tau != nullptr
+        ? k_null_of_block<F,true>(n, nx, ny, nz, nbnd, igpt, top_at_1, tau, band_lims_gpt, cld_tau, aer_tau, dz, knx, kny, knz)
+        : k_null_of_block<F,false>(n, nx, ny, nz, nbnd, igpt, top_at_1, tau, band_lims_gpt, cld_tau, aer_tau, dz, knx, kny, knz);
 }
 
 template<typename F>
@@ -509,17 +472,13 @@ TraceArgs<F> trace_args(const Medium<F>& m, const int igpt, const F* k_null, con
 
 template<typename F> BgTallies<F> bg_tallies(const FwOut<u64>& t) { return {t.toa_up, t.tod_dn_dir, t.tod_dn_dif, t.bg_abs_dir, t.bg_abs_dif}; }
 
-// aer_tau: NULL runs the kernel without aerosol
+// k_null of the ng g-points from g0 on; aer_tau: NULL for a medium without aerosol
 template<typename F>
-void launch_k_null(const Medium<F>& m, const int igpt, const F* aer_tau, F* k_null, hipStream_t st)
+void launch_k_null(const Medium<F>& m, const int g0, const int ng, const F* aer_tau, F* k_null, hipStream_t st)
 {
-    const int n = m.knx*m.kny*m.knz, top_at_1 = m.top_at_1 ? 1 : 0;
-    if (aer_tau != nullptr)
-        k_null_aer_kernel<F><<<ceil_div(n, 256), 256, 0, st>>>(m.nx, m.ny, m.nz, m.nbnd, igpt, top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, aer_tau,
-                                                               m.dz, m.knx, m.kny, m.knz, k_null);
-    else
-        k_null_kernel<F><<<ceil_div(n, 256), 256, 0, st>>>(m.nx, m.ny, m.nz, m.nbnd, igpt, top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, m.dz,
-                                                           m.knx, m.kny, m.knz, k_null);
+    const dim3 grid(unsigned(ceil_div(m.knx*m.kny*m.knz, 256)), unsigned(ng));
+    k_null_kernel<F><<<grid, 256, 0, st>>>(m.nx, m.ny, m.nz, m.nbnd, g0, m.top_at_1 ? 1 : 0, m.tau, m.band_lims_gpt, m.cld_tau, aer_tau, m.dz,
+                                           m.knx, m.kny, m.knz, k_null);
 }
 
 // form: which instantiation runs; b is read in the forms with a background (its aerosol triple in FORM_AER, whose profile has
@@ -609,32 +568,15 @@ __device__ __forceinline__ void bg_profile_layer(const int nbg, const int nbnd, 
     if constexpr (AER) { profile[BG_K_SCA_AER*n1 + b] = k_sca_aer; profile[BG_G_AER*n1 + b] = g_aer; }
 }
 
-template<typename F>
-__global__ void bg_profile_kernel(const int nbg, const int ngpt, const int nbnd, const int igpt, const BgLevels<F> dz_bg,
-        const F* __restrict__ bg_tau, const F* __restrict__ bg_ssa, const int* __restrict__ band_lims_gpt,
-        const F* __restrict__ bg_cld_tau, const F* __restrict__ bg_cld_ssa, const F* __restrict__ bg_cld_g, F* __restrict__ profile)
-{
-    bg_profile_layer<F,false>(nbg, nbnd, igpt, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, AerIn<F>{}, profile);
-}
-
-template<typename F>
-__global__ void bg_profile_aer_kernel(const int nbg, const int ngpt, const int nbnd, const int igpt, const BgLevels<F> dz_bg,
+// the profiles (ng, ROWS, nbg+1) of the ng g-points from g0 on, blockIdx.y counting them; ROWS: BG_ROWS_AER with AER, else BG_ROWS
+template<typename F, bool AER>
+__global__ void bg_profile_kernel(const int nbg, const int nbnd, const int g0, const BgLevels<F> dz_bg,
         const F* __restrict__ bg_tau, const F* __restrict__ bg_ssa, const int* __restrict__ band_lims_gpt,
         const F* __restrict__ bg_cld_tau, const F* __restrict__ bg_cld_ssa, const F* __restrict__ bg_cld_g, const AerIn<F> aer,
         F* __restrict__ profile)
 {
-    bg_profile_layer<F,true>(nbg, nbnd, igpt, dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, aer, profile);
-}
-
-// bg_profile_aer_kernel for every g-point, blockIdx.y counting them: slice g of profile (ngpt, BG_ROWS_AER, nbg+1)
-template<typename F>
-__global__ void bg_profile_all_kernel(const int nbg, const int nbnd, const BgLevels<F> dz_bg,
-        const F* __restrict__ bg_tau, const F* __restrict__ bg_ssa, const int* __restrict__ band_lims_gpt,
-        const F* __restrict__ bg_cld_tau, const F* __restrict__ bg_cld_ssa, const F* __restrict__ bg_cld_g, const AerIn<F> aer,
-        F* __restrict__ profile)
-{
-    bg_profile_layer<F,true>(nbg, nbnd, int(blockIdx.y), dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, aer,
-                             profile + size_t(blockIdx.y)*BG_ROWS_AER*(nbg + 1));
+    bg_profile_layer<F,AER>(nbg, nbnd, g0 + int(blockIdx.y), dz_bg, bg_tau, bg_ssa, band_lims_gpt, bg_cld_tau, bg_cld_ssa, bg_cld_g, aer,
+                            profile + size_t(blockIdx.y)*(AER ? BG_ROWS_AER : BG_ROWS)*(nbg + 1));
 }
 
 template<typename F>
@@ -645,27 +587,18 @@ BgLevels<F> bg_thicknesses(const int nbg, const F* dz_bg)
     return d;
 }
 
-// The profile of g-point igpt from a background's medium (bg.tau .. bg.cld_g). seven_rows: the BG_ROWS_AER profile with the triple aer
-// (NULLs write zeros into its two rows), otherwise the BG_ROWS one. lims: band_lims_gpt.
+// The profiles of the ng g-points from g0 on from a background's medium (bg.tau .. bg.cld_g). seven_rows: the BG_ROWS_AER profile with
+// the triple aer (NULLs write zeros into its two rows), otherwise the BG_ROWS one. lims: band_lims_gpt.
 template<typename F>
-void launch_bg_profile(const Background<F>& bg, const int ngpt, const int nbnd, const int* lims, const int igpt, const BgLevels<F>& dz_bg,
+void launch_bg_profile(const Background<F>& bg, const int nbnd, const int* lims, const int g0, const int ng, const BgLevels<F>& dz_bg,
                        const bool seven_rows, const AerIn<F>& aer, F* profile, hipStream_t st)
 {
+    const dim3 grid(unsigned(ceil_div(bg.nbg + 1, 64)), unsigned(ng));
     if (seven_rows)
-        bg_profile_aer_kernel<F><<<ceil_div(bg.nbg + 1, 64), 64, 0, st>>>(bg.nbg, ngpt, nbnd, igpt, dz_bg, bg.tau, bg.ssa, lims,
-                                                                         bg.cld_tau, bg.cld_ssa, bg.cld_g, aer, profile);
+        bg_profile_kernel<F,true><<<grid, 64, 0, st>>>(bg.nbg, nbnd, g0, dz_bg, bg.tau, bg.ssa, lims, bg.cld_tau, bg.cld_ssa, bg.cld_g, aer, profile);
     else
-        bg_profile_kernel<F><<<ceil_div(bg.nbg + 1, 64), 64, 0, st>>>(bg.nbg, ngpt, nbnd, igpt, dz_bg, bg.tau, bg.ssa, lims,
-                                                                     bg.cld_tau, bg.cld_ssa, bg.cld_g, profile);
-}
-
-// the profiles of all g-points, (ngpt, BG_ROWS_AER, nbg+1)
-template<typename F>
-void launch_bg_profile_all(const Background<F>& bg, const int ngpt, const int nbnd, const int* lims, const BgLevels<F>& dz_bg,
-                           const AerIn<F>& aer, F* profile, hipStream_t st)
-{
-    const dim3 grid(unsigned(ceil_div(bg.nbg + 1, 64)), unsigned(ngpt));
-    bg_profile_all_kernel<F><<<grid, 64, 0, st>>>(bg.nbg, nbnd, dz_bg, bg.tau, bg.ssa, lims, bg.cld_tau, bg.cld_ssa, bg.cld_g, aer, profile);
+        bg_profile_kernel<F,false><<<grid, 64, 0, st>>>(bg.nbg, nbnd, g0, dz_bg, bg.tau, bg.ssa, lims, bg.cld_tau, bg.cld_ssa, bg.cld_g, AerIn<F>{},
+                                                        profile);
 }
 
 // rrx_rt_bg_profile (bg.form = FORM_BG), _aer (FORM_AER: the 7-row profile, its triple may be NULL) and _all (FORM_AER, ALL: the
@@ -684,8 +617,7 @@ int bg_profile_entry(const char* entry, const Background<F>& bg, const int ngpt,
     check_needed({{"bg_profile", profile}});
     bg_levels<F>(bg.nbg, bg.dz_bg, 1, 1, F(1.));          // (the thicknesses are > 0)
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if constexpr (ALL) launch_bg_profile_all<F>(bg, ngpt, nbnd, lims, bg_thicknesses(bg.nbg, bg.dz_bg), bg.aer, profile, st);
-    else launch_bg_profile<F>(bg, ngpt, nbnd, lims, igpt, bg_thicknesses(bg.nbg, bg.dz_bg), bg.form == FORM_AER, bg.aer, profile, st);
+    launch_bg_profile<F>(bg, nbnd, lims, ALL ? 0 : igpt, ALL ? ngpt : 1, bg_thicknesses(bg.nbg, bg.dz_bg), bg.form == FORM_AER, bg.aer, profile, st);
     RRX_CATCH(entry)
 }
 
@@ -693,15 +625,6 @@ template<typename F>
 void launch_counts_to_flux(const size_t n, const u64* counts, const F scale, F* out, hipStream_t st)
 {
     counts_to_flux_kernel<F><<<unsigned(ceil_div((long long)n, 256)), 256, 0, st>>>(n, counts, scale, out);
-}
-
-// k_null of the ng g-points from g0 on
-template<typename F>
-void launch_k_null_all(const Medium<F>& m, const int g0, const int ng, const F* aer_tau, F* k_null, hipStream_t st)
-{
-    const dim3 grid(unsigned(ceil_div(m.knx*m.kny*m.knz, 256)), unsigned(ng));
-    k_null_all_kernel<F><<<grid, 256, 0, st>>>(m.nx, m.ny, m.nz, m.nbnd, g0, m.top_at_1 ? 1 : 0, m.tau, m.band_lims_gpt, m.cld_tau, aer_tau, m.dz,
-                                               m.knx, m.kny, m.knz, k_null);
 }
 
 // rrx_rt_k_null, _aer (m.aer.tau may be NULL) and _all (ALL: every g-point, igpt is not read); of m only what k_null depends on is set
@@ -719,8 +642,7 @@ int k_null_entry(const char* entry, const Medium<F>& m, const int igpt, F* k_nul
     if constexpr (!ALL) check_igpt(igpt, m.ngpt);
     if (!(m.dz > F(0.))) throw std::runtime_error("dz must be > 0");
     check_grid(m.nx, m.ny, m.nz, m.knx, m.kny, m.knz);
-    if constexpr (ALL) launch_k_null_all<F>(m, 0, m.ngpt, aer_tau, k_null, static_cast<hipStream_t>(stream));
-    else launch_k_null<F>(m, igpt, aer_tau, k_null, static_cast<hipStream_t>(stream));
+    launch_k_null<F>(m, ALL ? 0 : igpt, ALL ? m.ngpt : 1, aer_tau, k_null, static_cast<hipStream_t>(stream));
     RRX_CATCH(entry)
 }
 
@@ -901,9 +823,9 @@ int raytracer_sw_entry(const char* entry, const Medium<F>& m, const Sun<F>& sun,
         {
             if (!(inc_dir[g] + inc_dif[g] > F(0.))) continue;
             w.zero_counts(st);
-            launch_k_null<F>(m, g, m.aer.tau, w.k_null, st);
+            launch_k_null<F>(m, g, 1, m.aer.tau, w.k_null, st);
             const F scale = (inc_dir[g] + inc_dif[g]) / F(photons_per_pixel);
-            if (lb.on) launch_bg_profile<F>(bg, m.ngpt, m.nbnd, m.band_lims_gpt, g, thick, lb.form == FORM_AER, lb.aer, w.profile, st);
+            if (lb.on) launch_bg_profile<F>(bg, m.nbnd, m.band_lims_gpt, g, 1, thick, lb.form == FORM_AER, lb.aer, w.profile, st);
             launch_trace<F>(trace_args<F>(m, g, w.k_null, 0ull, nphotons, run.max_events, t), ph, sun, inc_dir[g], inc_dif[g], run.seed, st,
                             lb.form, b);
             w.add_fluxes(scale, m.dz, bg.dz_bg, out, st);
@@ -927,14 +849,14 @@ int raytracer_sw_entry(const char* entry, const Medium<F>& m, const Sun<F>& sun,
           && hipMemcpyAsync(w.dif_frac, dif_frac.data(), size_t(m.ngpt)*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess
           && hipStreamSynchronize(st) == hipSuccess;          // (the host arrays end with this call)
         if (!ok) throw std::runtime_error("zeroing the counts or copying the photon list failed");
-        if (lb.on) launch_bg_profile_all<F>(bg, m.ngpt, m.nbnd, m.band_lims_gpt, thick, lb.aer, w.profile, st);
+        if (lb.on) launch_bg_profile<F>(bg, m.nbnd, m.band_lims_gpt, 0, m.ngpt, thick, true, lb.aer, w.profile, st);
         FwBg<F,true,true,true> bs{b.in, b.t, b.aer, SpecIn<F>{m.ngpt, 0, w.photon_end, w.weight0, w.dif_frac}};
         for (int g0=0; g0<m.ngpt; g0+=chunk)
         {
             const int g1 = std::min(g0 + chunk, m.ngpt);
             const long long n = photon_end[g1] - photon_end[g0];
             if (n == 0) continue;
-            launch_k_null_all<F>(m, g0, g1 - g0, m.aer.tau, w.k_null, st);
+            launch_k_null<F>(m, g0, g1 - g0, m.aer.tau, w.k_null, st);
             bs.sp.kn_g0 = g0;
             launch_trace_spectral<F>(trace_args<F>(m, 0, w.k_null, u64(photon_end[g0]), n, run.max_events, t), ph, sun, run.seed, st, bs);
         }

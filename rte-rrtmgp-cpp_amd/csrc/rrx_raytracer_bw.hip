@@ -108,7 +108,7 @@ __device__ __forceinline__ bool after_surface(Stream& rng, F& weight, F& ux, F& 
     return true;
 }
 
-// DRAW ORDER WITH A BACKGROUND (tests/raytracer_bg_ref.py restates it): that of the header. start: the same draws. each event in layer b: u -> tau = -log(u) unless the
+// DRAW ORDER WITH A BACKGROUND (tests/raytracer_bw_ref.py restates it): that of the header. start: the same draws. each event in layer b: u -> tau = -log(u) unless the
 // previous event was a crossing (between layers, between blocks or through the domain top in either direction); a crossing draws
 // nothing; collision: weight *= f_no_abs; weight < 0.5: u -> roulette; survivor: u -> scatter or null (it always scatters);
 // u -> species; deposit (no walk); u -> cos of the scattering angle; u -> phi.
@@ -123,7 +123,7 @@ __device__ __forceinline__ bool after_surface(Stream& rng, F& weight, F& ux, F& 
 // with exp(-(tau_walk + tau_above[nbg]/mu0)): one exp of the summed path. The draw order is that of the header. nbg = 0: the
 // integers of the other instantiations.
 //
-// AER (trace_bw_kernel<F,TABLE,true,true>, the rrx_*_aer entries; rrx_rt_common.h; tests/raytracer_aer_ref.py restates it):
+// AER (trace_bw_kernel<F,TABLE,true,true>, the rrx_*_aer entries; rrx_rt_common.h; tests/raytracer_bw_ref.py restates it):
 // aerosol as a third species, built on top of the BG form only, which handles nbg = 0. k_ext and k_sca take tau_a as rrx_rt_common.h
 // writes them, the walk to the sun sums that k_ext and tau_above holds the aerosol's share. The draw count and DRAW ORDER are
 // unchanged: the species uniform u picks cloud iff u k_sca < k_sca_cld, otherwise aerosol iff u k_sca < k_sca_cld + k_sca_aer,

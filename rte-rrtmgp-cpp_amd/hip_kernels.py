@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from ._ffi import Lib, PtrArg, HEADER_PATH
+from .raytracer_args import RtScene
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "librrx_hip.so")
@@ -569,38 +570,21 @@ class HipKernels:
         self._c("mcica_cloud_mask", ncol, nlay, ngpt, *head, mask)
         return mask
 
-    # Forward Monte Carlo ray tracer (rrx_rt_*, rrx_raytracer_sw). tau, ssa (ngpt, nz, ncol) with ncol = nx ny, x fastest;
-    # cloud None or (tau, ssa, g), (nbnd, nz, ncol) each, with band_lims (nbnd, 2); sfc_albedo (ncol,); kn_grid = (knx, kny, knz).
+    # The Monte Carlo ray tracers. Every wrapper below gathers its arguments into a raytracer_args.RtScene, makes
+    # or accepts the outputs, calls the entry the scene names with the scene's argument groups, and unpacks.
+    #   tau, ssa (ngpt, nz, ncol) with ncol = nx ny, x fastest; sfc_albedo (ncol,); kn_grid = (knx, kny, knz);
+    #   cloud: None or (tau, ssa, g), (nbnd, nz, ncol) each, with band_lims (nbnd, 2);
+    #   phase: None (Henyey-Greenstein from cld_g) or an object with mu (nmu,), phase, cdf (nbnd, nre, nmu), re0, dre and cld_re
+    #     (nz, ncol), such as phase_tables.PhaseTable (the rrx_*_phase twins of the four plain entries);
+    #   background: None (nbg = 0) or an object with dz (nbg,) numbers on the host, tau, ssa (ngpt, nbg), cloud, None or (tau, ssa, g)
+    #     of (nbnd, nbg) each, and aerosol likewise, everything counted upward from the domain top (the rrx_*_bg entries);
+    #   aerosol: None or the grid's band triple (tau, ssa, g) of (nbnd, nz, ncol) each, a third scattering species. The wrappers with
+    #     aerosol= go through the rrx_*_aer entries when it or background.aerosol is given; a triple of None is given too: NULL
+    #     pointers.
     # Counts are int64 tensors holding the unsigned 64-bit tallies (units of 2^-32 photon).
     RT_COUNTS = ("sfc_dn_dir", "sfc_dn_dif", "sfc_up", "tod_up", "abs_dir", "abs_dif")
+    RT_BG_COUNTS = ("toa_up", "tod_dn_dir", "tod_dn_dif", "bg_abs_dir", "bg_abs_dif")
     RT_MAX_EVENTS = 1 << 22
-
-    def _rt_scene(self, tau, nx, ny, cloud, band_lims):
-        ngpt, nz, ncol = tau.shape
-        if ncol != nx*ny:
-            raise ValueError(f"raytracer: ncol = {ncol} is not nx ny = {nx}*{ny}")
-        ct, cw, cg = (None, None, None) if cloud is None else cloud
-        if cloud is not None and band_lims is None:
-            raise ValueError("raytracer: a cloud triple needs band_lims")
-        nbnd = int(band_lims.shape[0]) if band_lims is not None else 0
-        return (int(nx), int(ny), nz, ngpt, nbnd), (band_lims if cloud is not None else None, ct, cw, cg)
-
-    # Tabulated cloud phase functions (rrx_rt_phase_*, the rrx_*_phase twins of the four tracer entries). phase=: None
-    # (Henyey-Greenstein from cld_g, the entries above) or an object with mu (nmu,), phase, cdf (nbnd, nre, nmu), re0, dre and
-    # cld_re (nz, ncol), such as phase_tables.PhaseTable.
-    def _rt_phase(self, who, phase, dims):
-        """(the entry's name, the eight arguments in front of the stream)"""
-        if phase is None:
-            return who, ()
-        if phase.cld_re is None:
-            raise ValueError(f"{who}: the phase table has no cell radius (PhaseTable.with_radius)")
-        nbnd, nre, nmu = phase.phase.shape
-        if nbnd != dims[4] or tuple(phase.cdf.shape) != (nbnd, nre, nmu) or tuple(phase.mu.shape) != (nmu,):
-            raise ValueError(f"{who}: phase, cdf are (nbnd = {dims[4]}, nre, nmu) and mu (nmu,), got {tuple(phase.phase.shape)}, "
-                             f"{tuple(phase.cdf.shape)}, {tuple(phase.mu.shape)}")
-        if tuple(phase.cld_re.shape) != (dims[2], dims[0]*dims[1]):
-            raise ValueError(f"{who}: cld_re is (nz, ncol) = {(dims[2], dims[0]*dims[1])}, got {tuple(phase.cld_re.shape)}")
-        return who + "_phase", (nmu, nre, phase.re0, phase.dre, phase.mu, phase.phase, phase.cdf, phase.cld_re)
 
     def rt_phase_tables(self, mu, phase_raw):
         """phase, cdf (nbnd, nre, nmu) from the nodes mu (nmu,) and phase_raw (nbnd, nre, nmu) >= 0 of any normalisation."""
@@ -623,227 +607,127 @@ class HipKernels:
         """P(cs) at radius re: the density of rt_phase_sample."""
         return self._rt_phase_array("rt_phase_eval", table, ibnd, cs, re)
 
+    def _rt_zeros(self, **shapes):
+        return {k: torch.zeros(shape, dtype=torch.int64, device=self.device) for k, shape in shapes.items()}
+
     def rt_zero_counts(self, nz, ncol):
-        out = {k: torch.zeros((ncol,), dtype=torch.int64, device=self.device) for k in self.RT_COUNTS[:4]}
-        out.update({k: torch.zeros((nz, ncol), dtype=torch.int64, device=self.device) for k in self.RT_COUNTS[4:]})
-        out["n_capped"] = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        return out
+        return self._rt_zeros(**{k: (ncol,) for k in self.RT_COUNTS[:4]}, **{k: (nz, ncol) for k in self.RT_COUNTS[4:]}, n_capped=(1,))
 
-    # What the wrappers below share. Each of them gathers its arguments with these, calls its entry and unpacks.
-    def _rt_run(self, seed, max_events):
-        """(the seed as the unsigned 64-bit key, the cap on a photon's events)"""
-        return int(seed) & 0xFFFFFFFFFFFFFFFF, self.RT_MAX_EVENTS if max_events is None else max_events
+    def rt_zero_counts_bg(self, nz, ncol, nbg):
+        return {**self.rt_zero_counts(nz, ncol), **self._rt_zeros(**{k: (ncol,) for k in self.RT_BG_COUNTS[:3]},
+                                                                  **{k: (max(nbg, 1),) for k in self.RT_BG_COUNTS[3:]})}
 
-    def _rt_per_gpt(self, ngpt, **arrays):
-        """the (ngpt,) host arrays of a loop: the precision's numbers, photons_per_pixel_gpt int64"""
-        out = [np.ascontiguousarray(np.asarray(a, dtype=np.int64 if k == "photons_per_pixel_gpt" else self.np_dtype).reshape(-1))
-               for k, a in arrays.items()]
-        if any(a.size != ngpt for a in out):
-            raise ValueError(f"raytracer: {', '.join(arrays)} {'is' if len(out) == 1 else 'are'} (ngpt,)")
-        return out
+    def rt_bw_zero_counts(self, npix):
+        return self._rt_zeros(counts=(npix,), n_capped=(1,), n_clamped=(1,))
 
-    def _rt_fluxes(self, dims, nbg=None):
-        """(the outputs of a forward loop, its n_capped): the grid's six, and the background's five when nbg is given"""
-        nz, ncol = dims[2], dims[0]*dims[1]
-        out = {k: self.empty((ncol,)) for k in self.RT_COUNTS[:4]}
-        out.update({k: self.empty((nz, ncol)) for k in self.RT_COUNTS[4:]})
-        if nbg is not None:
-            out.update({k: self.zeros((ncol,)) for k in self.RT_BG_COUNTS[:3]})
-            out.update({k: self.zeros((nbg,)) for k in self.RT_BG_COUNTS[3:]})
-        return out, torch.zeros((1,), dtype=torch.int64, device=self.device)
-
-    @staticmethod
-    def _rt_lims(band_lims, clouds, aerosols):
-        """the band_lims that an entry is passed: NULL unless one of its cloud triples (None: none) or aerosol triples (a triple of
-        None: none) is given"""
-        return band_lims if (any(c is not None for c in clouds) or any(a[0] is not None for a in aerosols)) else None
-
-    def _rt_entry(self, base, phase, dims, aer=None, spectral=False):
-        """(the entry, its phase-table arguments). aer None: base, or base_phase with a table. Otherwise base_spectral, base_aer or
-        base_bg, which always take the table's eight arguments (zeros and NULLs for none)."""
-        if aer is None:
-            return self._rt_phase(base, phase, dims)
-        table = self._rt_phase(base + "_bg", phase, dims)[1]
-        return base + ("_spectral" if spectral else "_aer" if aer else "_bg"), table if table else (0, 0, 0.0, 0.0, None, None, None, None)
-
-    def rt_k_null(self, tau, igpt, nx, ny, dz, kn_grid, top_at_1, cloud=None, band_lims=None, aerosol=None):
-        """k_null (knz, kny, knx), kn counted upward from the surface, for g-point igpt (0-based). aerosol=: None, or the grid's
-        aerosol triple (rrx_rt_k_null_aer; a triple of None: its NULL pointer)."""
-        dims, (lims, ct, _, _) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        knx, kny, knz = (int(k) for k in kn_grid)
-        out = self.empty((knz, kny, knx))
-        if aerosol is None:
-            self._c("rt_k_null", *dims, igpt, top_at_1, tau, lims, ct, dz, knx, kny, knz, out)
-        else:
-            if aerosol[0] is not None and band_lims is None:
-                raise ValueError("raytracer: an aerosol triple needs band_lims")
-            self._c("rt_k_null_aer", *dims, igpt, top_at_1, tau, self._rt_lims(band_lims, (cloud,), (aerosol,)), ct, dz,
-                    knx, kny, knz, out, aerosol[0])
-        return out
-
-    def rt_trace_counts(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, k_null, seed,
-                        photon0, nphotons, top_at_1=False, independent_column=False, cloud=None, band_lims=None, counts=None,
-                        max_events=None, phase=None):
-        """Adds the photons [photon0, photon0 + nphotons) of g-point igpt into counts (rt_zero_counts; made when None)."""
-        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        kn = tuple(int(k) for k in kn_grid)
-        counts = self.rt_zero_counts(dims[2], dims[0]*dims[1]) if counts is None else counts
-        entry, table = self._rt_entry("rt_trace_counts", phase, dims)
-        seed, max_events = self._rt_run(seed, max_events)
-        self._c(entry, *dims, igpt, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth,
-                inc_dir, inc_dif, *kn, k_null, seed, photon0, nphotons, max_events, *(counts[k] for k in self.RT_COUNTS),
-                counts["n_capped"], *table)
-        return counts
+    def camera_zero_counts(self, nbnd, npix):
+        return self._rt_zeros(counts=(nbnd, npix), n_capped=(1,), n_clamped=(1,))
 
     def rt_counts_to_flux(self, counts, scale, out):
         """out += counts 2^-32 scale"""
         self._c("rt_counts_to_flux", counts.numel(), counts, scale, out)
         return out
 
-    def raytracer_sw(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, photons_per_pixel, seed,
-                     top_at_1=False, independent_column=False, cloud=None, band_lims=None, max_events=None, phase=None):
-        """The spectral loop in one call. inc_dir, inc_dif: (ngpt,) numbers on the host. Returns the four surface / top fluxes
-        (ncol,) in W m-2, abs_dir / abs_dif (nz, ncol) in W m-3 and n_capped (int)."""
-        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        kn = tuple(int(k) for k in kn_grid)
-        inc_dir, inc_dif = self._rt_per_gpt(dims[3], inc_dir=inc_dir, inc_dif=inc_dif)
-        out, n_capped = self._rt_fluxes(dims)
-        entry, table = self._rt_entry("raytracer_sw", phase, dims)
-        self._c(entry, *dims, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir,
-                inc_dif, *kn, photons_per_pixel, *self._rt_run(seed, max_events), *(out[k] for k in self.RT_COUNTS), n_capped, *table)
-        out["n_capped"] = int(n_capped.item())
+    # What the wrappers share beside the scene.
+    def _rt_per_gpt(self, ngpt, **arrays):
+        """the (ngpt,) host arrays of a loop: the precision's numbers, photons_per_pixel_gpt and rays_per_pixel_gpt int64"""
+        out = [np.ascontiguousarray(a, dtype=np.int64 if k.endswith("_per_pixel_gpt") else self.np_dtype).reshape(-1) for k, a in arrays.items()]
+        if any(a.size != ngpt for a in out):
+            raise ValueError(f"raytracer: {', '.join(arrays)} {'is' if len(out) == 1 else 'are'} (ngpt,)")
         return out
 
-    # Backward Monte Carlo ray tracer (rrx_rt_bw_trace_counts, rrx_raytracer_bw; DESIGN 4.15): the scene arguments of the forward
-    # tracer, k_null from rt_k_null, and a sensor (camera.Camera, or any object with type, npx, npy, fov, position, e_w, e_h, e_d).
+    def _rt_list(self, ngpt, unit, first, n, **arrays):
+        """The concatenated list of a spectral single-launch entry on the device: its ends (ngpt+1,) int64, the first of arrays, and
+        the (ngpt,) numbers per g-point, the others; the range [first, first + n) must lie within it."""
+        (name, end), *weights = arrays.items()
+        end = np.ascontiguousarray(np.asarray(end, dtype=np.int64).reshape(-1))
+        host = [np.ascontiguousarray(np.asarray(a, dtype=self.np_dtype).reshape(-1)) for _, a in weights]
+        if end.size != ngpt + 1 or any(a.size != ngpt for a in host):
+            raise ValueError(f"raytracer: {name} is (ngpt+1,) and {', '.join(k for k, _ in weights)} {'is' if len(host) == 1 else 'are'} (ngpt,)")
+        if end[0] != 0 or np.any(np.diff(end) < 0):
+            raise ValueError(f"raytracer: {name} must start at 0 and must not descend")
+        if first + n > int(end[-1]):
+            raise ValueError(f"raytracer: the range [{first}, {first + n}) ends beyond the list of {int(end[-1])} {unit}")
+        return [torch.as_tensor(a, device=self.device) for a in (end, *host)]
+
+    def _rt_chan_weights(self, chan_weights, nbnd):
+        """chan_weights (nchan, nbnd): a tensor as it is, anything else as a host array of the precision"""
+        M = chan_weights if torch.is_tensor(chan_weights) else np.ascontiguousarray(np.asarray(chan_weights, dtype=self.np_dtype))
+        if M.ndim != 2 or M.shape[1] != nbnd:
+            raise ValueError(f"raytracer: chan_weights is (nchan, nbnd = {nbnd}), got {tuple(M.shape)}")
+        return M
+
     def _rt_sensor(self, camera):
+        """a sensor (camera.Camera, or any object with type, npx, npy, fov, position, e_w, e_h, e_d) as the backward entries take it"""
         numbers = np.concatenate([np.asarray(v, dtype=np.float64).reshape(3) for v in (camera.position, camera.e_w, camera.e_h, camera.e_d)])
         return (int(camera.type), int(camera.npx), int(camera.npy), camera.fov, np.ascontiguousarray(numbers.astype(self.np_dtype)))
 
-    def rt_bw_zero_counts(self, npix):
-        return {k: torch.zeros((n,), dtype=torch.int64, device=self.device) for k, n in (("counts", npix), ("n_capped", 1), ("n_clamped", 1))}
+    def _rt_radiance(self, shape):
+        """(radiance, n_capped, n_clamped): the outputs of a backward loop"""
+        return (self.empty(shape), *self._rt_zeros(n_capped=(1,), n_clamped=(1,)).values())
 
-    def _rt_bw_loop(self, entry, sensor, head, tail):
-        """a backward loop: entry(*head, the sensor, ..., the outputs, *tail), unpacked"""
-        radiance = self.empty((sensor[2], sensor[1]))
-        n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        n_clamped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        self._c(entry, *head, radiance, n_capped, n_clamped, *tail)
-        return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
+    # ---- k_null and the background's profile
+    def _rt_k_null(self, entry, tau, igpt, nx, ny, dz, kn_grid, top_at_1, cloud, band_lims, aerosol, tail):
+        sc = RtScene(self, band_lims).set_grid(tau, nx, ny, dz, kn_grid, top_at_1, cloud).set_aerosol(aerosol)
+        knx, kny, knz = sc.kn
+        out = self.empty((knz, kny, knx) if igpt is not None else (sc.ngpt, knz, kny, knx))
+        self._c(entry, *sc.dims, *(() if igpt is None else (igpt,)), top_at_1, tau, sc.lims("k_null"), sc.cloud[0], dz, *sc.kn, out, *((sc.aer[0],) if tail else ()))
+        return out
 
-    def rt_bw_trace_counts(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, kn_grid, k_null, camera, seed, ray0, nrays,
-                           top_at_1=False, cloud=None, band_lims=None, counts=None, max_events=None, phase=None):
-        """Adds the rays [ray0, ray0 + nrays) of g-point igpt into counts (rt_bw_zero_counts; made when None): counts (npix,),
-        n_capped, n_clamped, int64 tensors holding unsigned 64-bit numbers."""
-        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        kn = tuple(int(k) for k in kn_grid)
-        sensor = self._rt_sensor(camera)
-        counts = self.rt_bw_zero_counts(sensor[1]*sensor[2]) if counts is None else counts
-        entry, table = self._rt_entry("rt_bw_trace_counts", phase, dims)
-        seed, max_events = self._rt_run(seed, max_events)
-        self._c(entry, *dims, igpt, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, *kn,
-                k_null, *sensor, seed, ray0, nrays, max_events, counts["counts"], counts["n_capped"], counts["n_clamped"], *table)
-        return counts
+    def rt_k_null(self, tau, igpt, nx, ny, dz, kn_grid, top_at_1, cloud=None, band_lims=None, aerosol=None):
+        """k_null (knz, kny, knx), kn counted upward from the surface, for g-point igpt (0-based). aerosol=: None, or the grid's
+        aerosol triple (rrx_rt_k_null_aer; a triple of None: its NULL pointer)."""
+        return self._rt_k_null("rt_k_null" if aerosol is None else "rt_k_null_aer", tau, igpt, nx, ny, dz, kn_grid, top_at_1, cloud, band_lims,
+                               aerosol, aerosol is not None)
 
-    def raytracer_bw(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
-                     top_at_1=False, cloud=None, band_lims=None, max_events=None, phase=None):
-        """The spectral loop in one call. inc_dir: (ngpt,) numbers on the host. Returns radiance (npy, npx) in W m-2 sr-1, n_capped and
-        n_clamped (ints)."""
-        dims, (lims, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        kn = tuple(int(k) for k in kn_grid)
-        inc_dir, = self._rt_per_gpt(dims[3], inc_dir=inc_dir)
-        sensor = self._rt_sensor(camera)
-        entry, table = self._rt_entry("raytracer_bw", phase, dims)
-        return self._rt_bw_loop(entry, sensor, (*dims, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir,
-                                                *kn, *sensor, rays_per_pixel, *self._rt_run(seed, max_events)), table)
-
-    # A background atmosphere between the domain top and TOA (the rrx_*_bg entries; DESIGN 4.17). background=: None (nbg = 0, the
-    # medium of the entries above) or an object with dz (nbg,) numbers on the host, tau, ssa (ngpt, nbg) and cloud, None or
-    # (tau, ssa, g) of (nbnd, nbg) each; everything is counted upward from the domain top.
-    RT_BG_COUNTS = ("toa_up", "tod_dn_dir", "tod_dn_dif", "bg_abs_dir", "bg_abs_dif")
-
-    def _rt_bg_dz(self, background):
-        dz = np.ascontiguousarray(np.asarray(background.dz, dtype=self.np_dtype).reshape(-1))
-        if tuple(background.tau.shape[1:]) != (dz.size,) or tuple(background.ssa.shape) != tuple(background.tau.shape):
-            raise ValueError(f"raytracer: the background's tau, ssa are (ngpt, nbg = {dz.size}), got {tuple(background.tau.shape)}, "
-                             f"{tuple(background.ssa.shape)}")
-        return dz
-
-    def _rt_bg_medium(self, background):
-        """nbg, dz_bg, bg_tau, bg_ssa and the background's cloud triple, as the spectral _bg entries take them"""
-        if background is None:
-            return (0, None, None, None, None, None, None)
-        dz = self._rt_bg_dz(background)
-        cloud = (None, None, None) if background.cloud is None else tuple(background.cloud)
-        return (dz.size, dz, background.tau, background.ssa, *cloud)
+    def rt_k_null_all(self, tau, nx, ny, dz, kn_grid, top_at_1, cloud=None, band_lims=None, aerosol=None):
+        """k_null (ngpt, knz, kny, knx): slice g is rt_k_null(..., igpt=g, aerosol=...) (ngpt <= 1024)"""
+        return self._rt_k_null("rt_k_null_all", tau, None, nx, ny, dz, kn_grid, top_at_1, cloud, band_lims, aerosol, True)
 
     def rt_bg_profile(self, background, igpt, band_lims=None, aerosol=None):
         """The profile (5, nbg+1) of g-point igpt: k_ext, k_sca, k_sca_cld, g, tau_above. aerosol=: the background's aerosol triple
         (a triple of None: no aerosol aloft) gives the profile (7, nbg+1) of rrx_rt_bg_profile_aer, which the _aer trace entries
         take: k_sca_aer and g_aer behind the five rows."""
-        medium = self._rt_bg_medium(background)
+        sc = RtScene(self, band_lims).set_background(background, aerosol=aerosol)
+        sc.need_lims("a background cloud triple", "bg_cloud")
+        sc.need_lims("a background aerosol triple", "bg_aer")
+        out = self.empty((5 if aerosol is None else 7, sc.nbg + 1))
+        self._c("rt_bg_profile" if aerosol is None else "rt_bg_profile_aer", sc.nbg, background.tau.shape[0], sc.nbnd, igpt, sc.dz_bg,
+                sc.bg_tau, sc.bg_ssa, sc.lims("profile"), *sc.bg_cloud, out, *(() if aerosol is None else sc.bg_aer))
+        return out
+
+    def rt_bg_profile_all(self, background, band_lims=None):
+        """The profile (ngpt, 7, nbg+1): slice g is rt_bg_profile(background, g, band_lims, aerosol=the background's triple)"""
+        sc = RtScene(self, band_lims).set_background(background)
+        sc.need_lims("a background cloud or aerosol triple", "bg_cloud", "bg_aer")
         ngpt = background.tau.shape[0]
-        if background.cloud is not None and band_lims is None:
-            raise ValueError("raytracer: a background cloud triple needs band_lims")
-        nbnd = int(band_lims.shape[0]) if band_lims is not None else 0
-        bg_aer = () if aerosol is None else tuple(aerosol)
-        if bg_aer and bg_aer[0] is not None and band_lims is None:
-            raise ValueError("raytracer: a background aerosol triple needs band_lims")
-        out = self.empty((7 if bg_aer else 5, medium[0] + 1))
-        self._c("rt_bg_profile_aer" if bg_aer else "rt_bg_profile", medium[0], ngpt, nbnd, igpt, *medium[1:4],
-                self._rt_lims(band_lims, (background.cloud,), (bg_aer,) if bg_aer else ()), *medium[4:], out, *bg_aer)
+        out = self.empty((ngpt, 7, sc.nbg + 1))
+        self._c("rt_bg_profile_all", sc.nbg, ngpt, sc.nbnd, sc.dz_bg, sc.bg_tau, sc.bg_ssa, sc.lims("profile"), *sc.bg_cloud, out, *sc.bg_aer)
         return out
 
-    # Aerosol as a third scattering species (the rrx_*_aer entries; DESIGN 4.18). aerosol=: None or the grid's band triple
-    # (tau, ssa, g) of (nbnd, nz, ncol) each; the background's is background.aerosol, None or (tau, ssa, g) of (nbnd, nbg) each.
-    # The four wrappers below go through the _aer entries when either is given; a triple of None is given too: NULL pointers.
-    @staticmethod
-    def _rt_bg_aerosol(background):
-        aer = None if background is None else getattr(background, "aerosol", None)
-        return (None, None, None) if aer is None else tuple(aer)
+    # ---- the forward tracer (rrx_rt_trace_counts, rrx_raytracer_sw and their forms; DESIGN 4.14, 4.19)
+    def _rt_fw_counts(self, sc, grid, counts):
+        """(the counts of a forward single launch, made when None; the entry's tally arguments)"""
+        if counts is None:
+            counts = self.rt_zero_counts(sc.nz, sc.ncol) if grid else self.rt_zero_counts_bg(sc.nz, sc.ncol, sc.nbg)
+        return counts, tuple(counts[k] for k in (*self.RT_COUNTS, "n_capped", *(() if grid else self.RT_BG_COUNTS)))
 
-    @staticmethod
-    def _rt_triple(triple):
-        """a triple as rrx_raytracer_sw_aer takes it: a host array of its three device pointers, None for no triple"""
-        if triple[0] is None:
-            return None
-        return (ctypes.c_void_p * 3)(*[t.data_ptr() for t in triple])
+    def _rt_trace_counts(self, grid, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, k_null, seed,
+                         photon0, nphotons, top_at_1, independent_column, cloud, band_lims, counts, max_events, phase, background=None,
+                         bg_profile=None, aerosol=None):
+        sc = RtScene(self, band_lims).set_grid(tau, nx, ny, dz, kn_grid, top_at_1, cloud, ssa, dx, dy, sfc_albedo, mu0, azimuth, independent_column)
+        sc.set_medium("trace", "rt_trace_counts", phase, background, aerosol, grid=grid, igpt=igpt, bg_profile=bg_profile)
+        counts, tallies = self._rt_fw_counts(sc, grid, counts)
+        self._c(sc.entry, *sc.dims, igpt, *sc.flags, *sc.grid("trace"), inc_dir, inc_dif, *sc.kn, k_null,
+                *sc.run(seed, max_events, photon0, nphotons), *tallies, *sc.table, *sc.bg_tail, *sc.aer_tail("trace"))
+        return counts
 
-    def _rt_aerosol(self, aerosol, background, band_lims):
-        """(use the _aer entries, the grid's triple, the background's triple)"""
-        given = aerosol is not None or (background is not None and getattr(background, "aerosol", None) is not None)
-        grid = (None, None, None) if aerosol is None else tuple(aerosol)
-        bg = self._rt_bg_aerosol(background)
-        if (grid[0] is not None or bg[0] is not None) and band_lims is None:
-            raise ValueError("raytracer: an aerosol triple needs band_lims")
-        return given, grid, bg
-
-    def _rt_trace_background(self, igpt, cloud, band_lims, background, bg_profile, aerosol):
-        """The background and aerosol of a single-launch entry: (use the _aer entry, band_lims as passed, nbg, the tail nbg, dz_bg,
-        bg_profile, the grid's aerosol triple). bg_profile is made when None: rt_bg_profile's for igpt, rt_bg_profile_all's for
-        igpt None."""
-        nbg, dzb = (0, None) if background is None else (len(background.dz), self._rt_bg_dz(background))
-        aer, aer_grid, aer_bg = self._rt_aerosol(aerosol, background, band_lims)
-        if background is not None and bg_profile is None:
-            bg_profile = (self.rt_bg_profile_all(background, band_lims) if igpt is None
-                          else self.rt_bg_profile(background, igpt, band_lims, aerosol=aer_bg if aer else None))
-        return aer, self._rt_lims(band_lims, (cloud,), (aer_grid,)), nbg, (nbg, dzb, bg_profile), aer_grid
-
-    def _rt_loop_background(self, cloud, band_lims, background, aerosol):
-        """The background and aerosol of a loop: (use the _aer entry, band_lims as passed, the medium nbg, dz_bg, bg_tau, ..., the
-        grid's aerosol triple, the background's)"""
-        medium = self._rt_bg_medium(background)
-        if background is not None and background.cloud is not None and band_lims is None:
-            raise ValueError("raytracer: a background cloud triple needs band_lims")
-        aer, aer_grid, aer_bg = self._rt_aerosol(aerosol, background, band_lims)
-        lims = self._rt_lims(band_lims, (cloud, None if background is None else background.cloud), (aer_grid, aer_bg))
-        return aer, lims, medium, aer_grid, aer_bg
-
-    def rt_zero_counts_bg(self, nz, ncol, nbg):
-        out = self.rt_zero_counts(nz, ncol)
-        out.update({k: torch.zeros((ncol,), dtype=torch.int64, device=self.device) for k in self.RT_BG_COUNTS[:3]})
-        out.update({k: torch.zeros((max(nbg, 1),), dtype=torch.int64, device=self.device) for k in self.RT_BG_COUNTS[3:]})
-        return out
+    def rt_trace_counts(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, k_null, seed,
+                        photon0, nphotons, top_at_1=False, independent_column=False, cloud=None, band_lims=None, counts=None,
+                        max_events=None, phase=None):
+        """Adds the photons [photon0, photon0 + nphotons) of g-point igpt into counts (rt_zero_counts; made when None)."""
+        return self._rt_trace_counts(True, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, k_null, seed,
+                                     photon0, nphotons, top_at_1, independent_column, cloud, band_lims, counts, max_events, phase)
 
     def rt_trace_counts_bg(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, k_null, seed,
                            photon0, nphotons, top_at_1=False, independent_column=False, cloud=None, band_lims=None, counts=None,
@@ -851,71 +735,9 @@ class HipKernels:
         """rt_trace_counts with a background: bg_profile is rt_bg_profile's for igpt (made when None). The counts gain RT_BG_COUNTS.
         With aerosol= or background.aerosol it is rrx_rt_trace_counts_aer: k_null is then rt_k_null's with
         aerosol= and bg_profile the 7-row profile."""
-        dims, (_, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        kn = tuple(int(k) for k in kn_grid)
-        aer, lims, nbg, bg_tail, aer_grid = self._rt_trace_background(igpt, cloud, band_lims, background, bg_profile, aerosol)
-        counts = self.rt_zero_counts_bg(dims[2], dims[0]*dims[1], nbg) if counts is None else counts
-        entry, table = self._rt_entry("rt_trace_counts", phase, dims, aer)
-        seed, max_events = self._rt_run(seed, max_events)
-        self._c(entry, *dims, igpt, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0,
-                azimuth, inc_dir, inc_dif, *kn, k_null, seed, photon0, nphotons, max_events, *(counts[k] for k in self.RT_COUNTS),
-                counts["n_capped"], *(counts[k] for k in self.RT_BG_COUNTS), *table, *bg_tail, *(aer_grid if aer else ()))
-        return counts
-
-    def _rt_sw_loop_bg(self, spectral, photons, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, seed,
-                       top_at_1, independent_column, cloud, band_lims, max_events, phase, background, aerosol):
-        """raytracer_sw_bg (photons: photons_per_pixel) and raytracer_sw_spectral (photons: photons_per_pixel_gpt)"""
-        dims, (_, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        kn = tuple(int(k) for k in kn_grid)
-        if spectral:
-            inc_dir, inc_dif, photons = self._rt_per_gpt(dims[3], inc_dir=inc_dir, inc_dif=inc_dif, photons_per_pixel_gpt=photons)
-        else:
-            inc_dir, inc_dif = self._rt_per_gpt(dims[3], inc_dir=inc_dir, inc_dif=inc_dif)
-        aer, lims, medium, aer_grid, aer_bg = self._rt_loop_background(cloud, band_lims, background, aerosol)
-        out, n_capped = self._rt_fluxes(dims, medium[0])
-        entry, table = self._rt_entry("raytracer_sw", phase, dims, aer, spectral)
-        self._c(entry, *dims, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir,
-                inc_dif, *kn, photons, *self._rt_run(seed, max_events), *(out[k] for k in self.RT_COUNTS), n_capped,
-                *(out[k] if medium[0] else None for k in self.RT_BG_COUNTS), *table, *medium,
-                *((self._rt_triple(aer_grid), self._rt_triple(aer_bg)) if (aer or spectral) else ()))
-        out["n_capped"] = int(n_capped.item())
-        return out
-
-    def raytracer_sw_bg(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, photons_per_pixel, seed,
-                        top_at_1=False, independent_column=False, cloud=None, band_lims=None, max_events=None, phase=None,
-                        background=None, aerosol=None):
-        """raytracer_sw with a background. Beside its outputs: toa_up, tod_dn_dir, tod_dn_dif (ncol,) in W m-2 and bg_abs_dir,
-        bg_abs_dif (nbg,) in W m-3 of a domain-wide layer (zeros without a background). With aerosol= or
-        background.aerosol it is rrx_raytracer_sw_aer."""
-        return self._rt_sw_loop_bg(False, photons_per_pixel, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid,
-                                   seed, top_at_1, independent_column, cloud, band_lims, max_events, phase, background, aerosol)
-
-    # All g-points in one launch of the forward tracer, photons dealt per g-point (rrx_rt_k_null_all, rrx_rt_bg_profile_all,
-    # rrx_rt_trace_counts_spectral, rrx_raytracer_sw_spectral; DESIGN 4.19). Built on the aerosol form: aerosol= and
-    # background.aerosol as above, None for none. ngpt <= 1024.
-    def rt_k_null_all(self, tau, nx, ny, dz, kn_grid, top_at_1, cloud=None, band_lims=None, aerosol=None):
-        """k_null (ngpt, knz, kny, knx): slice g is rt_k_null(..., igpt=g, aerosol=...)"""
-        dims, (_, ct, _, _) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        knx, kny, knz = (int(k) for k in kn_grid)
-        at = None if aerosol is None else aerosol[0]
-        if at is not None and band_lims is None:
-            raise ValueError("raytracer: an aerosol triple needs band_lims")
-        out = self.empty((dims[3], knz, kny, knx))
-        self._c("rt_k_null_all", *dims, top_at_1, tau, self._rt_lims(band_lims, (cloud,), ((at,),)), ct, dz, knx, kny, knz, out, at)
-        return out
-
-    def rt_bg_profile_all(self, background, band_lims=None):
-        """The profile (ngpt, 7, nbg+1): slice g is rt_bg_profile(background, g, band_lims, aerosol=the background's triple)"""
-        medium = self._rt_bg_medium(background)
-        ngpt = background.tau.shape[0]
-        bg_aer = self._rt_bg_aerosol(background)
-        lims = self._rt_lims(band_lims, (background.cloud,), (bg_aer,))
-        if lims is None and (background.cloud is not None or bg_aer[0] is not None):
-            raise ValueError("raytracer: a background cloud or aerosol triple needs band_lims")
-        nbnd = int(band_lims.shape[0]) if band_lims is not None else 0
-        out = self.empty((ngpt, 7, medium[0] + 1))
-        self._c("rt_bg_profile_all", medium[0], ngpt, nbnd, *medium[1:4], lims, *medium[4:], out, *bg_aer)
-        return out
+        return self._rt_trace_counts(False, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, k_null, seed,
+                                     photon0, nphotons, top_at_1, independent_column, cloud, band_lims, counts, max_events, phase, background,
+                                     bg_profile, aerosol)
 
     def rt_trace_counts_spectral(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, photon_end, weight0, dif_frac, kn_grid, k_null,
                                  seed, photon0, nphotons, top_at_1=False, independent_column=False, cloud=None, band_lims=None, counts=None,
@@ -923,35 +745,75 @@ class HipKernels:
         """Adds the photons [photon0, photon0 + nphotons) of the concatenated list into counts (rt_zero_counts_bg; made when None).
         photon_end (ngpt+1,) int64, weight0, dif_frac (ngpt,): arrays on the host, checked and uploaded here; k_null is
         rt_k_null_all's and bg_profile rt_bg_profile_all's (made when None)."""
-        dims, (_, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        ngpt = dims[3]
-        kn = tuple(int(k) for k in kn_grid)
-        photon_end = np.ascontiguousarray(np.asarray(photon_end, dtype=np.int64).reshape(-1))
-        weight0 = np.ascontiguousarray(np.asarray(weight0, dtype=self.np_dtype).reshape(-1))
-        dif_frac = np.ascontiguousarray(np.asarray(dif_frac, dtype=self.np_dtype).reshape(-1))
-        if photon_end.size != ngpt + 1 or weight0.size != ngpt or dif_frac.size != ngpt:
-            raise ValueError("raytracer: photon_end is (ngpt+1,) and weight0, dif_frac are (ngpt,)")
-        if photon_end[0] != 0 or np.any(np.diff(photon_end) < 0):
-            raise ValueError("raytracer: photon_end must start at 0 and must not descend")
-        if photon0 + nphotons > int(photon_end[-1]):
-            raise ValueError(f"raytracer: the range [{photon0}, {photon0 + nphotons}) ends beyond the list of {int(photon_end[-1])} photons")
-        _, lims, nbg, bg_tail, aer_grid = self._rt_trace_background(None, cloud, band_lims, background, bg_profile, aerosol)
-        counts = self.rt_zero_counts_bg(dims[2], dims[0]*dims[1], nbg) if counts is None else counts
-        dev = [torch.as_tensor(a, device=self.device) for a in (photon_end, weight0, dif_frac)]
-        entry, table = self._rt_entry("rt_trace_counts", phase, dims, True, spectral=True)
-        seed, max_events = self._rt_run(seed, max_events)
-        self._c(entry, *dims, top_at_1, independent_column, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, *dev,
-                *kn, k_null, seed, photon0, nphotons, max_events, *(counts[k] for k in self.RT_COUNTS), counts["n_capped"],
-                *(counts[k] for k in self.RT_BG_COUNTS), *table, *bg_tail, *aer_grid)
+        sc = RtScene(self, band_lims).set_grid(tau, nx, ny, dz, kn_grid, top_at_1, cloud, ssa, dx, dy, sfc_albedo, mu0, azimuth, independent_column)
+        lists = self._rt_list(sc.ngpt, "photons", photon0, nphotons, photon_end=photon_end, weight0=weight0, dif_frac=dif_frac)
+        sc.set_medium("trace", "rt_trace_counts", phase, background, aerosol, spectral=True, bg_profile=bg_profile)
+        counts, tallies = self._rt_fw_counts(sc, False, counts)
+        self._c(sc.entry, *sc.dims, *sc.flags, *sc.grid("trace"), *lists, *sc.kn, k_null, *sc.run(seed, max_events, photon0, nphotons),
+                *tallies, *sc.table, *sc.bg_tail, *sc.aer_tail("trace"))
         return counts
+
+    def _rt_sw_loop(self, grid, spectral, photons, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, seed,
+                    top_at_1, independent_column, cloud, band_lims, max_events, phase, background=None, aerosol=None):
+        """raytracer_sw, raytracer_sw_bg (photons: photons_per_pixel) and raytracer_sw_spectral (photons: photons_per_pixel_gpt)"""
+        sc = RtScene(self, band_lims).set_grid(tau, nx, ny, dz, kn_grid, top_at_1, cloud, ssa, dx, dy, sfc_albedo, mu0, azimuth, independent_column)
+        per_gpt = self._rt_per_gpt(sc.ngpt, inc_dir=inc_dir, inc_dif=inc_dif, **({"photons_per_pixel_gpt": photons} if spectral else {}))
+        sc.set_medium("loop", "raytracer_sw", phase, background, aerosol, grid=grid, spectral=spectral)
+        # the grid's six are written by the entry; the background's five are added to (and stay zeros without a background)
+        out = {k: self.empty((sc.ncol,)) for k in self.RT_COUNTS[:4]}
+        out.update({k: self.empty((sc.nz, sc.ncol)) for k in self.RT_COUNTS[4:]})
+        if not grid:
+            out.update({k: self.zeros((sc.ncol,)) for k in self.RT_BG_COUNTS[:3]})
+            out.update({k: self.zeros((sc.nbg,)) for k in self.RT_BG_COUNTS[3:]})
+        n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        self._c(sc.entry, *sc.dims, *sc.flags, *sc.grid("loop"), *per_gpt[:2], *sc.kn, per_gpt[2] if spectral else photons,
+                *sc.run(seed, max_events), *(out[k] for k in self.RT_COUNTS), n_capped,
+                *(() if grid else (out[k] if sc.nbg else None for k in self.RT_BG_COUNTS)), *sc.table, *sc.bg_medium, *sc.aer_tail("arrays"))
+        out["n_capped"] = int(n_capped.item())
+        return out
+
+    def raytracer_sw(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, photons_per_pixel, seed,
+                     top_at_1=False, independent_column=False, cloud=None, band_lims=None, max_events=None, phase=None):
+        """The spectral loop in one call. inc_dir, inc_dif: (ngpt,) numbers on the host. Returns the four surface / top fluxes
+        (ncol,) in W m-2, abs_dir / abs_dif (nz, ncol) in W m-3 and n_capped (int)."""
+        return self._rt_sw_loop(True, False, photons_per_pixel, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid,
+                                seed, top_at_1, independent_column, cloud, band_lims, max_events, phase)
+
+    def raytracer_sw_bg(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, photons_per_pixel, seed,
+                        top_at_1=False, independent_column=False, cloud=None, band_lims=None, max_events=None, phase=None,
+                        background=None, aerosol=None):
+        """raytracer_sw with a background. Beside its outputs: toa_up, tod_dn_dir, tod_dn_dif (ncol,) in W m-2 and bg_abs_dir,
+        bg_abs_dif (nbg,) in W m-3 of a domain-wide layer (zeros without a background). With aerosol= or
+        background.aerosol it is rrx_raytracer_sw_aer."""
+        return self._rt_sw_loop(False, False, photons_per_pixel, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid,
+                                seed, top_at_1, independent_column, cloud, band_lims, max_events, phase, background, aerosol)
 
     def raytracer_sw_spectral(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid, photons_per_pixel_gpt,
                               seed, top_at_1=False, independent_column=False, cloud=None, band_lims=None, max_events=None, phase=None,
                               background=None, aerosol=None):
         """raytracer_sw_bg with photons_per_pixel_gpt (ngpt,) photons per pixel of each g-point (pipeline.spectral_allocation deals
         them by flux) in place of photons_per_pixel, all g-points in one trace launch per chunk. The same outputs."""
-        return self._rt_sw_loop_bg(True, photons_per_pixel_gpt, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif, kn_grid,
-                                   seed, top_at_1, independent_column, cloud, band_lims, max_events, phase, background, aerosol)
+        return self._rt_sw_loop(False, True, photons_per_pixel_gpt, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, inc_dif,
+                                kn_grid, seed, top_at_1, independent_column, cloud, band_lims, max_events, phase, background, aerosol)
+
+    # ---- the backward tracer (rrx_rt_bw_trace_counts, rrx_raytracer_bw and their forms; DESIGN 4.15): the scene arguments of the
+    # forward tracer, k_null from rt_k_null, and a sensor
+    def _rt_bw_trace_counts(self, grid, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, kn_grid, k_null, camera, seed, ray0, nrays,
+                            top_at_1, cloud, band_lims, counts, max_events, phase, background=None, bg_profile=None, aerosol=None):
+        sc = RtScene(self, band_lims).set_grid(tau, nx, ny, dz, kn_grid, top_at_1, cloud, ssa, dx, dy, sfc_albedo, mu0, azimuth)
+        sensor = self._rt_sensor(camera)
+        sc.set_medium("trace", "rt_bw_trace_counts", phase, background, aerosol, grid=grid, igpt=igpt, bg_profile=bg_profile)
+        counts = self.rt_bw_zero_counts(sensor[1]*sensor[2]) if counts is None else counts
+        self._c(sc.entry, *sc.dims, igpt, sc.flags[0], *sc.grid("trace"), *sc.kn, k_null, *sensor, *sc.run(seed, max_events, ray0, nrays),
+                counts["counts"], counts["n_capped"], counts["n_clamped"], *sc.table, *sc.bg_tail, *sc.aer_tail("trace"))
+        return counts
+
+    def rt_bw_trace_counts(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, kn_grid, k_null, camera, seed, ray0, nrays,
+                           top_at_1=False, cloud=None, band_lims=None, counts=None, max_events=None, phase=None):
+        """Adds the rays [ray0, ray0 + nrays) of g-point igpt into counts (rt_bw_zero_counts; made when None): counts (npix,),
+        n_capped, n_clamped, int64 tensors holding unsigned 64-bit numbers."""
+        return self._rt_bw_trace_counts(True, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, kn_grid, k_null, camera, seed, ray0,
+                                        nrays, top_at_1, cloud, band_lims, counts, max_events, phase)
 
     def rt_bw_trace_counts_bg(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, kn_grid, k_null, camera, seed, ray0, nrays,
                               top_at_1=False, cloud=None, band_lims=None, counts=None, max_events=None, phase=None, background=None,
@@ -959,74 +821,56 @@ class HipKernels:
         """rt_bw_trace_counts with a background: bg_profile is rt_bg_profile's for igpt (made when None). With aerosol= or
         background.aerosol it is rrx_rt_bw_trace_counts_aer: k_null is then rt_k_null's with aerosol= and
         bg_profile the 7-row profile."""
-        dims, (_, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        kn = tuple(int(k) for k in kn_grid)
+        return self._rt_bw_trace_counts(False, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, kn_grid, k_null, camera, seed, ray0,
+                                        nrays, top_at_1, cloud, band_lims, counts, max_events, phase, background, bg_profile, aerosol)
+
+    def _rt_bw_loop(self, grid, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
+                    top_at_1, cloud, band_lims, max_events, phase, background=None, aerosol=None):
+        sc = RtScene(self, band_lims).set_grid(tau, nx, ny, dz, kn_grid, top_at_1, cloud, ssa, dx, dy, sfc_albedo, mu0, azimuth)
+        inc_dir, = self._rt_per_gpt(sc.ngpt, inc_dir=inc_dir)
+        sc.set_medium("loop", "raytracer_bw", phase, background, aerosol, grid=grid)
         sensor = self._rt_sensor(camera)
-        aer, lims, _, bg_tail, aer_grid = self._rt_trace_background(igpt, cloud, band_lims, background, bg_profile, aerosol)
-        counts = self.rt_bw_zero_counts(sensor[1]*sensor[2]) if counts is None else counts
-        entry, table = self._rt_entry("rt_bw_trace_counts", phase, dims, aer)
-        seed, max_events = self._rt_run(seed, max_events)
-        self._c(entry, *dims, igpt, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, *kn,
-                k_null, *sensor, seed, ray0, nrays, max_events, counts["counts"], counts["n_capped"], counts["n_clamped"], *table,
-                *bg_tail, *(aer_grid if aer else ()))
-        return counts
+        radiance, n_capped, n_clamped = self._rt_radiance((sensor[2], sensor[1]))
+        self._c(sc.entry, *sc.dims, sc.flags[0], *sc.grid("loop"), inc_dir, *sc.kn, *sensor, rays_per_pixel, *sc.run(seed, max_events),
+                radiance, n_capped, n_clamped, *sc.table, *sc.bg_medium, *sc.aer_tail("pointers"))
+        return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
+
+    def raytracer_bw(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
+                     top_at_1=False, cloud=None, band_lims=None, max_events=None, phase=None):
+        """The spectral loop in one call. inc_dir: (ngpt,) numbers on the host. Returns radiance (npy, npx) in W m-2 sr-1, n_capped and
+        n_clamped (ints)."""
+        return self._rt_bw_loop(True, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
+                                top_at_1, cloud, band_lims, max_events, phase)
 
     def raytracer_bw_bg(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
                         top_at_1=False, cloud=None, band_lims=None, max_events=None, phase=None, background=None, aerosol=None):
         """raytracer_bw with a background: radiance (npy, npx) in W m-2 sr-1, n_capped and n_clamped (ints). With aerosol= or
         background.aerosol it is rrx_raytracer_bw_aer."""
-        dims, (_, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        kn = tuple(int(k) for k in kn_grid)
-        inc_dir, = self._rt_per_gpt(dims[3], inc_dir=inc_dir)
-        aer, lims, medium, aer_grid, aer_bg = self._rt_loop_background(cloud, band_lims, background, aerosol)
-        sensor = self._rt_sensor(camera)
-        entry, table = self._rt_entry("raytracer_bw", phase, dims, aer)
-        return self._rt_bw_loop(entry, sensor, (*dims, top_at_1, tau, ssa, lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir,
-                                                *kn, *sensor, rays_per_pixel, *self._rt_run(seed, max_events)),
-                                (*table, *medium, *((*aer_grid, *aer_bg) if aer else ())))
+        return self._rt_bw_loop(False, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
+                                top_at_1, cloud, band_lims, max_events, phase, background, aerosol)
 
     # The backward tracer with the rays of all g-points in one launch, counts by band and a channel matrix (rrx_camera_trace_counts_spectral,
-    # rrx_camera_channels, rrx_camera_render_spectral; DESIGN 4.21). Built on the aerosol form like the forward entries above; band_lims
+    # rrx_camera_channels, rrx_camera_render_spectral; DESIGN 4.21). Built on the aerosol form like the forward spectral entries; band_lims
     # is always needed (the counts are kept by band). ngpt <= 1024.
-    def camera_zero_counts(self, nbnd, npix):
-        return {k: torch.zeros(shape, dtype=torch.int64, device=self.device)
-                for k, shape in (("counts", (nbnd, npix)), ("n_capped", (1,)), ("n_clamped", (1,)))}
-
     def camera_trace_counts_spectral(self, tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, ray_end, weight0, kn_grid, k_null, camera,
                                      seed, ray0, nrays, band_lims, top_at_1=False, cloud=None, counts=None, max_events=None, phase=None,
                                      background=None, bg_profile=None, aerosol=None):
         """Adds the rays [ray0, ray0 + nrays) of the concatenated list into counts (camera_zero_counts; made when None): counts
         (nbnd, npix), n_capped, n_clamped. ray_end (ngpt+1,) int64 and weight0 (ngpt,): arrays on the host, checked and uploaded here;
         k_null is rt_k_null_all's and bg_profile rt_bg_profile_all's (made when None)."""
-        if band_lims is None:
-            raise ValueError("raytracer: the camera's spectral form needs band_lims")
-        dims, (_, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        ngpt = dims[3]
-        kn = tuple(int(k) for k in kn_grid)
+        sc = RtScene(self, band_lims, camera=True).set_grid(tau, nx, ny, dz, kn_grid, top_at_1, cloud, ssa, dx, dy, sfc_albedo, mu0, azimuth)
         sensor = self._rt_sensor(camera)
-        ray_end = np.ascontiguousarray(np.asarray(ray_end, dtype=np.int64).reshape(-1))
-        weight0 = np.ascontiguousarray(np.asarray(weight0, dtype=self.np_dtype).reshape(-1))
-        if ray_end.size != ngpt + 1 or weight0.size != ngpt:
-            raise ValueError("raytracer: ray_end is (ngpt+1,) and weight0 is (ngpt,)")
-        if ray_end[0] != 0 or np.any(np.diff(ray_end) < 0):
-            raise ValueError("raytracer: ray_end must start at 0 and must not descend")
-        if ray0 + nrays > int(ray_end[-1]):
-            raise ValueError(f"raytracer: the range [{ray0}, {ray0 + nrays}) ends beyond the list of {int(ray_end[-1])} rays")
-        _, _, _, bg_tail, aer_grid = self._rt_trace_background(None, cloud, band_lims, background, bg_profile, aerosol)
-        counts = self.camera_zero_counts(dims[4], sensor[1]*sensor[2]) if counts is None else counts
-        dev = [torch.as_tensor(a, device=self.device) for a in (ray_end, weight0)]
-        entry, table = self._rt_entry("camera_trace_counts", phase, dims, True, spectral=True)
-        seed, max_events = self._rt_run(seed, max_events)
-        self._c(entry, *dims, top_at_1, tau, ssa, band_lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, *dev, *kn, k_null, *sensor,
-                seed, ray0, nrays, max_events, counts["counts"], counts["n_capped"], counts["n_clamped"], *table, *bg_tail, *aer_grid)
+        lists = self._rt_list(sc.ngpt, "rays", ray0, nrays, ray_end=ray_end, weight0=weight0)
+        sc.set_medium("trace", "camera_trace_counts", phase, background, aerosol, spectral=True, bg_profile=bg_profile)
+        counts = self.camera_zero_counts(sc.nbnd, sensor[1]*sensor[2]) if counts is None else counts
+        self._c(sc.entry, *sc.dims, sc.flags[0], *sc.grid("camera"), *lists, *sc.kn, k_null, *sensor, *sc.run(seed, max_events, ray0, nrays),
+                counts["counts"], counts["n_capped"], counts["n_clamped"], *sc.table, *sc.bg_tail, *sc.aer_tail("trace"))
         return counts
 
     def camera_channels(self, counts, chan_weights, scale, out=None):
         """out (nchan, npix) = scale x chan_weights (nchan, nbnd) @ (counts (nbnd, npix) 2^-32), the sum in band order"""
         nbnd, npix = counts.shape
-        M = chan_weights if torch.is_tensor(chan_weights) else self.asarray(np.ascontiguousarray(np.asarray(chan_weights, dtype=self.np_dtype)))
-        if M.dim() != 2 or M.shape[1] != nbnd:
-            raise ValueError(f"raytracer: chan_weights is (nchan, nbnd = {nbnd}), got {tuple(M.shape)}")
+        M = self.asarray(self._rt_chan_weights(chan_weights, nbnd))
         out = self.empty((M.shape[0], npix)) if out is None else out
         self._c("camera_channels", npix, nbnd, int(M.shape[0]), counts, M, scale, out)
         return out
@@ -1037,25 +881,15 @@ class HipKernels:
         """raytracer_bw_bg with rays_per_pixel_gpt (ngpt,) rays per pixel of each g-point (pipeline.spectral_allocation deals them by
         flux) in place of rays_per_pixel, all g-points in one trace launch per chunk, and chan_weights (nchan, nbnd) on the host, the
         matrix from bands to channels. Returns radiance (nchan, npy, npx) in W m-2 sr-1, n_capped and n_clamped (ints)."""
-        if band_lims is None:
-            raise ValueError("raytracer: the camera's spectral form needs band_lims")
-        dims, (_, ct, cw, cg) = self._rt_scene(tau, nx, ny, cloud, band_lims)
-        kn = tuple(int(k) for k in kn_grid)
-        inc_dir, = self._rt_per_gpt(dims[3], inc_dir=inc_dir)
-        rays = np.ascontiguousarray(np.asarray(rays_per_pixel_gpt, dtype=np.int64).reshape(-1))
-        if rays.size != dims[3]:
-            raise ValueError("raytracer: rays_per_pixel_gpt is (ngpt,)")
-        M = np.ascontiguousarray(np.asarray(chan_weights, dtype=self.np_dtype))
-        if M.ndim != 2 or M.shape[1] != dims[4]:
-            raise ValueError(f"raytracer: chan_weights is (nchan, nbnd = {dims[4]}), got {M.shape}")
-        _, _, medium, aer_grid, aer_bg = self._rt_loop_background(cloud, band_lims, background, aerosol)
+        sc = RtScene(self, band_lims, camera=True).set_grid(tau, nx, ny, dz, kn_grid, top_at_1, cloud, ssa, dx, dy, sfc_albedo, mu0, azimuth)
+        inc_dir, = self._rt_per_gpt(sc.ngpt, inc_dir=inc_dir)
+        rays, = self._rt_per_gpt(sc.ngpt, rays_per_pixel_gpt=rays_per_pixel_gpt)
+        M = self._rt_chan_weights(np.asarray(chan_weights), sc.nbnd)
+        sc.set_medium("loop", "camera_render", phase, background, aerosol, spectral=True)
         sensor = self._rt_sensor(camera)
-        entry, table = self._rt_entry("camera_render", phase, dims, True, spectral=True)
-        radiance = self.empty((M.shape[0], sensor[2], sensor[1]))
-        n_capped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        n_clamped = torch.zeros((1,), dtype=torch.int64, device=self.device)
-        self._c(entry, *dims, top_at_1, tau, ssa, band_lims, ct, cw, cg, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, *kn, *sensor, rays,
-                *self._rt_run(seed, max_events), int(M.shape[0]), M, radiance, n_capped, n_clamped, *table, *medium, *aer_grid, *aer_bg)
+        radiance, n_capped, n_clamped = self._rt_radiance((M.shape[0], sensor[2], sensor[1]))
+        self._c(sc.entry, *sc.dims, sc.flags[0], *sc.grid("camera"), inc_dir, *sc.kn, *sensor, rays, *sc.run(seed, max_events),
+                int(M.shape[0]), M, radiance, n_capped, n_clamped, *sc.table, *sc.bg_medium, *sc.aer_tail("pointers"))
         return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
 
     def delta_scale_2str_k(self, tau, ssa, g):

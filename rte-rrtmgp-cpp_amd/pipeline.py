@@ -282,31 +282,18 @@ def raytrace_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, photons_per_pixel, 
         kn_grid = (nx, ny, int(n_domain))
     tau, ssa, cld, sfc_albedo, mu0, inc_dir, kn_grid, aer = _raytracer_inputs("raytrace_sw", be, kd_sw, atm, nx, ny, cloud_lut, kn_grid,
                                                                               sfc_albedo, aerosol_lut)
+    m = spectral_allocation(inc_dir, photons_per_pixel, min_per_gpt) if allocation == "flux" else None
+    tau, ssa, cld, phase, medium = _raytracer_medium("raytrace_sw", be, atm, tau, ssa, cld, aer, cloud_lut, phase_table, n_domain, z_lev)
+    scene = (tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, np.zeros_like(inc_dir), kn_grid)
+    kw = dict(top_at_1=atm.top_at_1, independent_column=independent_column, cloud=cld, band_lims=kd_sw.band_lims_gpt, max_events=max_events,
+              phase=phase)
     if allocation == "flux":
-        m = spectral_allocation(inc_dir, photons_per_pixel, min_per_gpt)
-        background, rel = None, None
-        if n_domain is not None:
-            tau, ssa, cld, rel, background, aer = _raytracer_split("raytrace_sw", be, atm, tau, ssa, cld, n_domain, z_lev, aer)
-        phase = _raytracer_phase("raytrace_sw", atm, cloud_lut, phase_table, rel)
-        r = be.raytracer_sw_spectral(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, np.zeros_like(inc_dir), kn_grid, m, seed,
-                                     top_at_1=atm.top_at_1, independent_column=independent_column, cloud=cld,
-                                     band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase, background=background, aerosol=aer)
-        return r if n_domain is not None else {k: v for k, v in r.items() if k not in be.RT_BG_COUNTS}
-    if n_domain is not None:
-        tau, ssa, cld, rel, background, aer = _raytracer_split("raytrace_sw", be, atm, tau, ssa, cld, n_domain, z_lev, aer)
-        phase = _raytracer_phase("raytrace_sw", atm, cloud_lut, phase_table, rel)
-        return be.raytracer_sw_bg(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, np.zeros_like(inc_dir), kn_grid,
-                                  photons_per_pixel, seed, top_at_1=atm.top_at_1, independent_column=independent_column, cloud=cld,
-                                  band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase, background=background, aerosol=aer)
-    phase = _raytracer_phase("raytrace_sw", atm, cloud_lut, phase_table)
-    if aer is not None:
-        r = be.raytracer_sw_bg(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, np.zeros_like(inc_dir), kn_grid,
-                               photons_per_pixel, seed, top_at_1=atm.top_at_1, independent_column=independent_column, cloud=cld,
-                               band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase, aerosol=aer)
-        return {k: v for k, v in r.items() if k not in be.RT_BG_COUNTS}
-    return be.raytracer_sw(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, np.zeros_like(inc_dir), kn_grid,
-                           photons_per_pixel, seed, top_at_1=atm.top_at_1, independent_column=independent_column, cloud=cld,
-                           band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase)
+        r = be.raytracer_sw_spectral(*scene, m, seed, **kw, background=medium.get("background"), aerosol=medium.get("aerosol"))
+    elif medium:
+        r = be.raytracer_sw_bg(*scene, photons_per_pixel, seed, **kw, **medium)
+    else:
+        r = be.raytracer_sw(*scene, photons_per_pixel, seed, **kw)
+    return r if n_domain is not None else {k: v for k, v in r.items() if k not in be.RT_BG_COUNTS}
 
 
 def render_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, camera, rays_per_pixel, seed, cloud_lut=None, kn_grid=None,
@@ -343,29 +330,30 @@ def render_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, camera, rays_per_pixe
             if M.ndim != 2 or M.shape[1] != nbnd:
                 raise ValueError(f"render_sw: channels is (nchan, nbnd = {nbnd}), got {M.shape}")
         m = spectral_allocation(inc_dir, rays_per_pixel, min_per_gpt)
-        background, rel = None, None
-        if n_domain is not None:
-            tau, ssa, cld, rel, background, aer = _raytracer_split("render_sw", be, atm, tau, ssa, cld, n_domain, z_lev, aer)
-        phase = _raytracer_phase("render_sw", atm, cloud_lut, phase_table, rel)
-        r = be.camera_render_spectral(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, m, seed,
-                                      kd_sw.band_lims_gpt, M, top_at_1=atm.top_at_1, cloud=cld, max_events=max_events, phase=phase,
-                                      background=background, aerosol=aer)
+    tau, ssa, cld, phase, medium = _raytracer_medium("render_sw", be, atm, tau, ssa, cld, aer, cloud_lut, phase_table, n_domain, z_lev)
+    scene = (tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera)
+    kw = dict(top_at_1=atm.top_at_1, cloud=cld, max_events=max_events, phase=phase)
+    if allocation == "flux":
+        r = be.camera_render_spectral(*scene, m, seed, kd_sw.band_lims_gpt, M, **kw, background=medium.get("background"),
+                                      aerosol=medium.get("aerosol"))
         if channels is None:
             r["radiance"] = r["radiance"][0]
         return r
+    if medium:
+        return be.raytracer_bw_bg(*scene, rays_per_pixel, seed, band_lims=kd_sw.band_lims_gpt, **kw, **medium)
+    return be.raytracer_bw(*scene, rays_per_pixel, seed, band_lims=kd_sw.band_lims_gpt, **kw)
+
+
+def _raytracer_medium(who, be, atm, tau, ssa, cld, aer, cloud_lut, phase_table, n_domain, z_lev):
+    """What raytrace_sw and render_sw do with the chain's optics before they call the binding: with n_domain the split into the
+    grid's arrays and a Background, the phase table with the (grid's) radius, and the medium that goes to the binding as keywords:
+    none (the plain methods), aerosol= alone (the _bg methods on the whole atmosphere), or background= and aerosol= (split)."""
+    background, rel = None, None
     if n_domain is not None:
-        tau, ssa, cld, rel, background, aer = _raytracer_split("render_sw", be, atm, tau, ssa, cld, n_domain, z_lev, aer)
-        phase = _raytracer_phase("render_sw", atm, cloud_lut, phase_table, rel)
-        return be.raytracer_bw_bg(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
-                                  top_at_1=atm.top_at_1, cloud=cld, band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase,
-                                  background=background, aerosol=aer)
-    phase = _raytracer_phase("render_sw", atm, cloud_lut, phase_table)
-    if aer is not None:
-        return be.raytracer_bw_bg(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
-                                  top_at_1=atm.top_at_1, cloud=cld, band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase,
-                                  aerosol=aer)
-    return be.raytracer_bw(tau, ssa, nx, ny, dx, dy, dz, sfc_albedo, mu0, azimuth, inc_dir, kn_grid, camera, rays_per_pixel, seed,
-                           top_at_1=atm.top_at_1, cloud=cld, band_lims=kd_sw.band_lims_gpt, max_events=max_events, phase=phase)
+        tau, ssa, cld, rel, background, aer = _raytracer_split(who, be, atm, tau, ssa, cld, n_domain, z_lev, aer)
+    phase = _raytracer_phase(who, atm, cloud_lut, phase_table, rel)
+    medium = dict(background=background, aerosol=aer) if background is not None else dict(aerosol=aer) if aer is not None else {}
+    return tau, ssa, cld, phase, medium
 
 
 def _raytracer_phase(who, atm, cloud_lut, phase_table, rel=None):

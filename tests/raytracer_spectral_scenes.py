@@ -59,6 +59,25 @@ def plain(dtype, top_at_1=True):
     return sc, None
 
 
+def setup(dtype, top_at_1, nx=4, ny=2, nz=4, kn=(2, 1, 2), nbg=3):
+    """The scene of the set-up kernels' tests: 3 g-points in 2 bands (1-2 and 3), cloud in a third and aerosol in half of the cells,
+    both in both bands, under nbg background layers with cloud and aerosol; nothing is traced. The default k_null grid has blocks of
+    2 x 2 x 2 cells."""
+    rng = np.random.default_rng(1903)
+    ncol = nx*ny
+    tau = rng.uniform(0.02, 0.4, (3, nz, ncol))
+    cloud = S._cloud(rng, NBND, nz, ncol, 1./3., (0.9, 0.999), dtype)
+    at = np.where(rng.uniform(0., 1., (NBND, nz, ncol)) < 0.5, rng.uniform(0.2, 1.5, (NBND, nz, ncol)), 0.0)
+    aer = (_arr(at, dtype), _arr(rng.uniform(0.85, 0.99, at.shape), dtype), _arr(rng.uniform(0.6, 0.75, at.shape), dtype))
+    sc = Scene(nx=nx, ny=ny, nz=nz, dx=100.0, dy=140.0, dz=60.0, tau=_arr(tau, dtype), ssa=_arr(rng.uniform(0.3, 0.999, tau.shape), dtype),
+               sfc_albedo=_arr(np.full(ncol, 0.3), dtype), mu0=0.8, azimuth=4.0, inc_dir=_arr(INC[:3], dtype), inc_dif=_arr(np.zeros(3), dtype),
+               kn_grid=kn, cloud=cloud, band_lims=np.array([[1, 2], [3, 3]], dtype=np.int32), top_at_1=top_at_1, seed=S.SEED + 43, aerosol=aer)
+    triple = lambda lo, hi: tuple(_arr(rng.uniform(a, b, (NBND, nbg)), dtype) for a, b in ((0.05, 0.4), lo, hi))
+    bg = Background(dz=_arr(DZ_BG[:nbg], dtype), tau=_arr(rng.uniform(0.05, 0.3, (3, nbg)), dtype), ssa=_arr(rng.uniform(0.5, 0.999, (3, nbg)), dtype),
+                    cloud=triple((0.9, 0.999), (0.8, 0.85)), aerosol=triple((0.85, 0.99), (0.6, 0.75)))
+    return sc, bg
+
+
 def beer(dtype):
     """A clear scene for the unbiasedness test: purely absorbing gas in the grid and the background, no cloud, no aerosol, a black
     surface, independent columns that differ, direct light only: sfc_dn_dir of a pixel is the sum over g of Bernoulli means with

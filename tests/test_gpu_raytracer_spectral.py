@@ -4,6 +4,7 @@ tests/raytracer_spectral_scenes.py (5 g-points in 2 bands, one of them dark, 4 x
 tests/raytracer_spectral_ref.py. The tallies are integers added with integer atomics, so a run that passes once passes always; the
 integer comparisons are exact, the statistical bound is derived in raytracer_spectral_scenes.beer_sigma."""
 import ctypes
+import dataclasses
 import os
 
 import numpy as np
@@ -51,6 +52,59 @@ def test_k_null_all_and_bg_profile_all_are_the_per_g_point_entries_slice_by_slic
     prof = be.to_numpy(be.rt_bg_profile_all(dbg))
     for g in range(SS.NGPT):
         assert np.array_equal(prof[g].view(np.uint8), be.to_numpy(be.rt_bg_profile(dbg, g, aerosol=NO_TRIPLE)).view(np.uint8))
+
+
+def _same(be, a, b):
+    """bit for bit; a, b: tensors, or numpy arrays of the backend's precision"""
+    a, b = (x if isinstance(x, np.ndarray) else be.to_numpy(x) for x in (a, b))
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+@pytest.mark.parametrize("top_at_1", [False, True])
+@pytest.mark.parametrize("grid", ["blocks", "cells"])
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+def test_one_k_null_kernel_writes_what_the_three_wrote(dt, grid, top_at_1, hip_f64, hip_f32):
+    """rrx_rt_k_null, _aer and _all launch one kernel: without aerosol the two-term k_ext, whichever entry, and
+    slice g of _all is the per-g-point entry's; all of it the restatement's, bit for bit. blocks: 4 x 2 x 4 cells in blocks of
+    2 x 2 x 2. cells: 8 x 8 x 5 with one block per cell, 320 blocks in two workgroups along x, where the slices must not overlap."""
+    be = _be(dt, hip_f64, hip_f32)
+    sc, _ = SS.setup(be.np_dtype, top_at_1) if grid == "blocks" else SS.setup(be.np_dtype, top_at_1, nx=8, ny=8, nz=5, kn=(8, 8, 5))
+    d, _ = dev(be, sc, None)
+    null = dict(d, aer=NO_TRIPLE)
+    all_null, all_aer = k_null_all(be, sc, null), k_null_all(be, sc, d)
+    assert tuple(all_aer.shape) == (3,) + tuple(sc.kn_grid[::-1])
+    sc_no_aerosol = dataclasses.replace(sc, aerosol=None)
+    for g in range(3):
+        two_term = k_null(be, sc, d, g)
+        assert _same(be, two_term, k_null(be, sc, null, g, aer=True)), g
+        assert _same(be, two_term, all_null[g]) and _same(be, k_null(be, sc, d, g, aer=True), all_aer[g]), g
+        assert _same(be, two_term, R.k_null(sc_no_aerosol, g)) and _same(be, all_aer[g], R.k_null(sc, g)), g
+        assert not _same(be, two_term, all_aer[g])          # (the aerosol counts)
+    if grid == "cells":
+        for g in range(2):          # other inputs for slice g+1 leave slice g as it was
+            tau = d["tau"].clone()
+            tau[g + 1] *= 2
+            changed = k_null_all(be, sc, dict(d, tau=tau))
+            assert _same(be, changed[g], all_aer[g]) and not _same(be, changed[g + 1], all_aer[g + 1]), g
+
+
+@pytest.mark.parametrize("nbg", [3, 1])
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+def test_one_profile_kernel_writes_what_the_three_wrote(dt, nbg, hip_f64, hip_f32):
+    """rrx_rt_bg_profile, _aer and _all launch one kernel in two instantiations: the five rows are the first five of
+    the seven, a NULL triple leaves zeros in the other two, slice g of _all is the per-g-point entry's, and all of it is the
+    restatement's, bit for bit. (The profile is counted upward from the domain top: top_at_1 is not among its inputs.)"""
+    be = _be(dt, hip_f64, hip_f32)
+    sc, bg = SS.setup(be.np_dtype, True, nbg=nbg)
+    d, dbg = dev(be, sc, bg)
+    every = be.rt_bg_profile_all(dbg, d["lims"])
+    assert tuple(every.shape) == (3, 7, nbg + 1)
+    for g in range(3):
+        five, seven = be.to_numpy(be.rt_bg_profile(dbg, g, d["lims"])), be.to_numpy(be.rt_bg_profile(dbg, g, d["lims"], aerosol=NO_TRIPLE))
+        assert _same(be, five, seven[:5].copy()) and not seven[5:].any(), g
+        assert _same(be, every[g], be.rt_bg_profile(dbg, g, d["lims"], aerosol=dbg.aerosol)), g
+        assert _same(be, five, np.ascontiguousarray(R.profile(sc, bg, g, aerosol=False))) and _same(be, every[g], R.profile(sc, bg, g)), g
+        assert every[g][5].any()          # (the aerosol aloft counts)
 
 
 # ---- 6: the sum over g-points
