@@ -965,7 +965,43 @@ int rrx_camera_render_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, 
         int nchan, const F* chan_weights, F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
         int nmu, int nre, F re0, F dre, const F* mu, const F* phase, const F* cdf, const F* cld_re, \
         int nbg, const F* dz_bg, const F* bg_tau, const F* bg_ssa, const F* bg_cld_tau, const F* bg_cld_ssa, const F* bg_cld_g, \
-        const F* aer_tau, const F* aer_ssa, const F* aer_g, const F* bg_aer_tau, const F* bg_aer_ssa, const F* bg_aer_g, void* stream);
+        const F* aer_tau, const F* aer_ssa, const F* aer_g, const F* bg_aer_tau, const F* bg_aer_ssa, const F* bg_aer_g, void* stream); \
+/* ---- Thermal emission in the backward tracer: longwave radiances for a virtual camera, 3-D longwave fluxes for a flux sensor \
+   (csrc/rrx_raytracer_thermal.hip). The symbols begin rrx_thermal_: the set of rrx_rt_ and rrx_raytracer_ symbols is \
+   closed. Rays start at the sensor as in rrx_rt_bw_trace_counts (the same four sensors, the same start) and travel through the grid \
+   with that entry's tracking, draw for draw; there is no sun and no walk. The medium per g-point: k_ext = (tau + cld_tau)/dz, \
+   k_sca = (tau ssa + cld_tau cld_ssa)/dz; ssa may be NULL: the gas does not scatter (what the LW gas optics give); k_null is \
+   rrx_rt_k_null's. The sources are RADIANCES in W m-2 sr-1, the arrays the 1-D LW solver takes (its flux is pi w radiance): \
+   lay_src (ncol, nz, ngpt), the layout of tau, constant within a cell; sfc_src (ncol, ngpt); sfc_emis (ncol), one broadband \
+   Lambertian emissivity per pixel (the surface reflects 1 - sfc_emis); top_radiance, one isotropic downward radiance per g-point \
+   at the domain top (it closes the medium when the grid does not reach TOA). A ray deposits, each before the weight changes: \
+   at a collision weight (1 - f_no_abs) lay_src[cell, g], then weight *= f_no_abs; at the surface weight sfc_emis sfc_src[col, g], \
+   then weight *= 1 - sfc_emis; where it ends at the top (it leaves through it, or starts at or above it looking away from the \
+   medium) weight top_radiance. Nothing is deposited at a scattering. \
+   rrx_thermal_trace_counts: traces the rays [ray0, ray0 + nrays) of g-point igpt (ray r belongs to pixel r mod (npx npy); \
+   Philox4x32-10 keyed by seed with counter (r low, r high, igpt | 0xC0000000, block)) and ADDS into the caller-zeroed counts \
+   (npx npy), unsigned 64-bit in units of 2^-32: llrint(min(d, 2^20) 2^32) per deposit d; n_clamped and n_capped as in \
+   rrx_rt_bw_trace_counts. Integer adds: independent of the order of arrival, additive over ray ranges. Radiance of the g-point = \
+   counts 2^-32 / rays_per_pixel. \
+   rrx_thermal_render: the loop over all g-points. top_radiance: ngpt numbers on the HOST, NULL = 0. Zeroes radiance, n_capped and \
+   n_clamped, then for igpt = 0 .. ngpt-1: zeroes counts in the stream's workspace, rrx_rt_k_null, rrx_thermal_trace_counts of \
+   rays_per_pixel npx npy rays from 0, rrx_rt_counts_to_flux with scale = 1/F(rays_per_pixel) into radiance (npx npy) (by_band = 0: \
+   the sum over g-points) or into the g-point's band's slice of radiance (npx npy, nbnd) (by_band = 1: band_lims_gpt is needed; a \
+   g-point of no band is dropped): the same bits as that loop made by hand. With a flux sensor pi x radiance is an irradiance. \
+   An extent of 0 (nx, ny, nz, ngpt, npx, npy, nrays, rays_per_pixel): returns 0 without a launch. Refused, non-zero, before any HIP \
+   call: what the backward entries refuse of grid, cloud triple and sensor; a NULL tau, lay_src, sfc_src, sfc_emis, k_null, sensor, \
+   counts, radiance or counter; a negative or non-finite top_radiance. LIMITS: no background layers, no aerosol, no phase table, one \
+   g-point per launch, a cell-constant source, no brightness temperatures. */ \
+int rrx_thermal_trace_counts##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_emis, const F* lay_src, const F* sfc_src, F top_radiance, int knx, int kny, int knz, const F* k_null, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
+        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream); \
+int rrx_thermal_render##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_emis, const F* lay_src, const F* sfc_src, const F* top_radiance, int knx, int kny, int knz, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
+        RrxBool by_band, F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream);
 
 RRX_DECLARE(double, _f64)
 RRX_DECLARE(float, _f32)

@@ -139,6 +139,14 @@ int   rrx_cxx_trace_rays_bw_spectral(int nx, int ny, int nz, int ngpt, int nbnd,
                             int nbg, const Real* dz_bg, const Real* bg_tau, const Real* bg_ssa, const Real* bg_cld_tau, const Real* bg_cld_ssa,
                             const Real* bg_cld_g, const Real* aer_tau, const Real* aer_ssa, const Real* aer_g,
                             const Real* bg_aer_tau, const Real* bg_aer_ssa, const Real* bg_aer_g, void* stream);
+/* Raytracer_thermal_gpu::trace_rays_thermal (include/Raytracer_thermal.h) on device arrays of the caller; needs no handle.
+ * ssa NULL: the gas does not scatter; top_radiance: ngpt numbers on the host or NULL; sensor: 12 numbers on the host; radiance (npx, npy)
+ * on the device, with by_band (npx, npy, nbnd); n_capped, n_clamped: one number each on the host. */
+int   rrx_cxx_trace_rays_thermal(int nx, int ny, int nz, int ngpt, int nbnd, Real dx, Real dy, Real dz, int top_at_1,
+                            const Real* tau, const Real* ssa, const int* band_lims_gpt, const Real* cld_tau, const Real* cld_ssa, const Real* cld_g,
+                            const Real* sfc_emis, const Real* lay_src, const Real* sfc_src, const Real* top_radiance, int knx, int kny, int knz,
+                            int sensor_type, int npx, int npy, Real fov, const Real* sensor, long long rays_per_pixel, unsigned long long seed,
+                            int max_events, int by_band, Real* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream);
 /* one LW + one SW solve_gpu (fluxes only) enqueued on `stream`; DEVICE arrays: (ncol,nlay) / (ncol,nlay+1) fields, (ncol) vectors,
    surface properties (nbnd,ncol); lwp, iwp, rel, dei NULL without clouds; out7: seven (ncol, nlay+1) arrays for LW up, dn, net and
    SW up, dn, dn_dir, net, or NULL (the driver then keeps them: rrx_cxx_driver_fluxes) */

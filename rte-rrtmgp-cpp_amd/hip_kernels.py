@@ -570,7 +570,7 @@ class HipKernels:
         self._c("mcica_cloud_mask", ncol, nlay, ngpt, *head, mask)
         return mask
 
-    # The Monte Carlo ray tracers (DESIGN 4.14 - 4.22). Every wrapper below gathers its arguments into a raytracer_args.RtScene, makes
+    # The Monte Carlo ray tracers (DESIGN 4.14 - 4.23). Every wrapper below gathers its arguments into a raytracer_args.RtScene, makes
     # or accepts the outputs, calls the entry the scene names with the scene's argument groups, and unpacks.
     #   tau, ssa (ngpt, nz, ncol) with ncol = nx ny, x fastest; sfc_albedo (ncol,); kn_grid = (knx, kny, knz);
     #   cloud: None or (tau, ssa, g), (nbnd, nz, ncol) each, with band_lims (nbnd, 2);
@@ -890,6 +890,46 @@ class HipKernels:
         radiance, n_capped, n_clamped = self._rt_radiance((M.shape[0], sensor[2], sensor[1]))
         self._c(sc.entry, *sc.dims, sc.flags[0], *sc.grid("camera"), inc_dir, *sc.kn, *sensor, rays, *sc.run(seed, max_events),
                 int(M.shape[0]), M, radiance, n_capped, n_clamped, *sc.table, *sc.bg_medium, *sc.aer_tail("pointers"))
+        return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
+
+    # Thermal emission in the backward tracer (rrx_thermal_trace_counts, rrx_thermal_render): the grid form of the backward
+    # tracer's scene without a sun. ssa: (ngpt, nz, ncol) or None for a gas that does not scatter; sfc_emis (ncol,); the sources are
+    # radiances in W m-2 sr-1: lay_src (ngpt, nz, ncol), sfc_src (ngpt, ncol); k_null from rt_k_null.
+    def _thermal_scene(self, tau, ssa, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src, kn_grid, top_at_1, cloud, band_lims):
+        """(the gathered scene; tau ... sfc_src in the header's order)"""
+        sc = RtScene(self, band_lims).set_grid(tau, nx, ny, dz, kn_grid, top_at_1, cloud, ssa, dx, dy, sfc_emis)
+        if tuple(lay_src.shape) != tuple(tau.shape) or tuple(sfc_src.shape) != (sc.ngpt, sc.ncol) or tuple(sfc_emis.shape) != (sc.ncol,):
+            raise ValueError(f"thermal: lay_src is (ngpt, nz, ncol) = {tuple(tau.shape)}, sfc_src (ngpt, ncol) and sfc_emis (ncol,), got "
+                             f"{tuple(lay_src.shape)}, {tuple(sfc_src.shape)}, {tuple(sfc_emis.shape)}")
+        return sc, (sc.tau, sc.ssa, sc.lims("trace"), *sc.cloud, *sc.geometry[:4], lay_src, sfc_src)
+
+    def thermal_trace_counts(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src, top_radiance, kn_grid, k_null, camera, seed,
+                             ray0, nrays, top_at_1=False, cloud=None, band_lims=None, counts=None, max_events=None):
+        """Adds the rays [ray0, ray0 + nrays) of g-point igpt into counts (rt_bw_zero_counts; made when None): counts (npix,), n_capped,
+        n_clamped, int64 tensors holding unsigned 64-bit numbers. top_radiance: one number, the isotropic downward radiance at the domain
+        top. Radiance of the g-point = counts 2^-32 / rays_per_pixel."""
+        sc, scene = self._thermal_scene(tau, ssa, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src, kn_grid, top_at_1, cloud, band_lims)
+        sensor = self._rt_sensor(camera)
+        counts = self.rt_bw_zero_counts(sensor[1]*sensor[2]) if counts is None else counts
+        self._c("thermal_trace_counts", *sc.dims, igpt, sc.flags[0], *scene, float(top_radiance), *sc.kn, k_null, *sensor,
+                *sc.run(seed, max_events, ray0, nrays), counts["counts"], counts["n_capped"], counts["n_clamped"])
+        return counts
+
+    def thermal_render(self, tau, ssa, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src, kn_grid, camera, rays_per_pixel, seed, top_at_1=False,
+                       cloud=None, band_lims=None, max_events=None, top_radiance=None, by_band=False):
+        """The loop over all g-points in one call. top_radiance: None (0) or (ngpt,) numbers on the host. Returns radiance in W m-2 sr-1,
+        (npy, npx), or with by_band (which needs band_lims) (nbnd, npy, npx), n_capped and n_clamped (ints). With a flux sensor
+        pi x radiance is the irradiance of the pixel."""
+        sc, scene = self._thermal_scene(tau, ssa, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src, kn_grid, top_at_1, cloud, band_lims)
+        if by_band and band_lims is None:
+            raise ValueError("thermal: by_band needs band_lims")
+        if top_radiance is not None:
+            top_radiance, = self._rt_per_gpt(sc.ngpt, top_radiance=top_radiance)
+        sensor = self._rt_sensor(camera)
+        radiance, n_capped, n_clamped = self._rt_radiance((sc.nbnd, sensor[2], sensor[1]) if by_band else (sensor[2], sensor[1]))
+        lims = band_lims if by_band else scene[2]
+        self._c("thermal_render", *sc.dims, sc.flags[0], *scene[:2], lims, *scene[3:], top_radiance, *sc.kn, *sensor, rays_per_pixel,
+                *sc.run(seed, max_events), by_band, radiance, n_capped, n_clamped)
         return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
 
     def delta_scale_2str_k(self, tau, ssa, g):

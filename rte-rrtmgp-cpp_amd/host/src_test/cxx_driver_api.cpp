@@ -9,6 +9,7 @@
 #include "Radiation_solver.h"
 #include "Raytracer.h"
 #include "Raytracer_bw.h"
+#include "Raytracer_thermal.h"
 #include "rrx_cxx_driver.h"
 
 namespace
@@ -556,4 +557,43 @@ int rrx_cxx_trace_rays_bw(const int nx, const int ny, const int nz, const int ng
                                        mu0, azimuth, inc_dir, knx, kny, knz, sensor_type, npx, npy, fov, sensor, rays_per_pixel, seed, max_events,
                                        radiance, n_capped, n_clamped, 0, 0, Float(0.), Float(0.), nullptr, nullptr, nullptr, nullptr, stream);
 }
+}
+
+// Raytracer_thermal_gpu::trace_rays_thermal on device arrays the caller owns (views; needs no driver handle). ssa NULL: the
+// gas does not scatter; top_radiance (ngpt) and sensor (12 numbers) on the HOST, top_radiance NULL: none; radiance: a device array
+// (npy, npx), or with by_band (nbnd, npy, npx). Runs on `stream` and waits for the counts of dropped rays and clamped deposits.
+extern "C" int rrx_cxx_trace_rays_thermal(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy,
+        const Float dz, const int top_at_1, const Float* tau, const Float* ssa, const int* band_lims_gpt,
+        const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_emis, const Float* lay_src, const Float* sfc_src,
+        const Float* top_radiance, const int knx, const int kny, const int knz, const int sensor_type, const int npx, const int npy, const Float fov,
+        const Float* sensor, const long long rays_per_pixel, const unsigned long long seed, const int max_events, const int by_band, Float* radiance,
+        unsigned long long* n_capped, unsigned long long* n_clamped, void* stream)
+{
+    return guarded([&]
+    {
+        void* const before = rrx_host::current_stream();
+        rrx_host::set_stream(stream);
+        try
+        {
+            const int ncol = nx*ny;
+            auto view3 = [](const Float* p, int a, int b, int c) { return p ? Array_gpu<Float,3>(const_cast<Float*>(p), {a, b, c}) : Array_gpu<Float,3>(); };
+            Array<Float,1> h_top;
+            if (top_radiance != nullptr)
+            {
+                h_top.set_dims({ngpt});
+                for (int g=1; g<=ngpt; ++g) h_top({g}) = top_radiance[g-1];
+            }
+            Sensor_bw s;
+            s.sensor_type = sensor_type; s.npx = npx; s.npy = npy; s.fov = fov;
+            for (int i=0; i<3; ++i) { s.position[i] = sensor[i]; s.e_w[i] = sensor[3+i]; s.e_h[i] = sensor[6+i]; s.e_d[i] = sensor[9+i]; }
+            Array_gpu<Float,3> out(radiance, {npx, npy, by_band ? nbnd : 1});
+            Raytracer_thermal_gpu raytracer;
+            *n_capped = raytracer.trace_rays_thermal(nx, ny, nz, dx, dy, dz, top_at_1 != 0, view3(tau, ncol, nz, ngpt), view3(ssa, ncol, nz, ngpt),
+                    Array_gpu<int,2>(const_cast<int*>(band_lims_gpt), {2, nbnd}), view3(cld_tau, ncol, nz, nbnd), view3(cld_ssa, ncol, nz, nbnd),
+                    view3(cld_g, ncol, nz, nbnd), view1(sfc_emis, ncol), view3(lay_src, ncol, nz, ngpt), view2(sfc_src, ncol, ngpt), h_top,
+                    knx, kny, knz, s, rays_per_pixel, seed, max_events, out, n_clamped);
+        }
+        catch (...) { rrx_host::set_stream(before); throw; }
+        rrx_host::set_stream(before);
+    });
 }

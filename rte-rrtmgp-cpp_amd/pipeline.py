@@ -344,6 +344,51 @@ def render_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, camera, rays_per_pixe
     return be.raytracer_bw(*scene, rays_per_pixel, seed, band_lims=kd_sw.band_lims_gpt, **kw)
 
 
+def render_lw(be, kd_lw, atm, nx, ny, dx, dy, dz, camera, rays_per_pixel, seed, cloud_lut=None, kn_grid=None, sfc_emis=None,
+              max_events=None, channels=None, top_radiance=None):
+    """Longwave radiances for a virtual camera or a flux sensor from the backward Monte Carlo ray tracer with thermal emission
+    (rrx_thermal_render): the twin of render_sw on the LW chain's own arrays: the clear g-point tau of
+    gas_optics_lw_direct (the gas does not scatter), the Planck sources of planck_source_direct (lay_src, constant within a cell, and
+    sfc_src) and, with cloud_lut (the LW table), the band cloud triple of cloud_optics_2str. sfc_emis: (ncol,), one broadband
+    emissivity per pixel; None takes atm.emis_sfc, which must then be the same in every band. top_radiance: None (0) or (ngpt,), the
+    isotropic downward radiance at the domain top per g-point, which closes the medium when the grid does not reach TOA. channels:
+    None, broadband radiance (npy, npx); "bands", radiance by band (nbnd, npy, npx); an array (nchan, nbnd), applied to the band
+    radiances, (nchan, npy, npx). Returns radiance in W m-2 sr-1, n_capped and n_clamped. With a camera.flux_sensor pi x radiance is
+    the irradiance of the pixel in W m-2 (pi x the mean radiance over the hemisphere): the surface downwelling (facing up) or the
+    outgoing longwave at the domain top (facing down). Every g-point gets rays_per_pixel rays."""
+    ncol, nlay, ngpt = atm.ncol, atm.nlay, kd_lw.ngpt
+    if ncol != nx*ny:
+        raise ValueError(f"render_lw: ncol = {ncol} is not nx ny = {nx}*{ny}")
+    nbnd = int(kd_lw.band_lims_gpt.shape[0])
+    M = None
+    if isinstance(channels, str):
+        if channels != "bands":
+            raise ValueError(f"render_lw: channels is None, 'bands' or an array (nchan, nbnd), got {channels!r}")
+    elif channels is not None:
+        M = np.asarray(channels, dtype=be.np_dtype)
+        if M.ndim != 2 or M.shape[1] != nbnd:
+            raise ValueError(f"render_lw: channels is (nchan, nbnd = {nbnd}), got {M.shape}")
+    if sfc_emis is None:
+        emis = be.to_numpy(atm.emis_sfc)
+        if np.any(emis != emis[:, :1]):
+            raise ValueError("render_lw: the atmosphere's emissivity differs between bands; pass sfc_emis")
+        sfc_emis = np.ascontiguousarray(emis[:, 0])
+    sfc_emis = be.asarray(sfc_emis)
+    kn_grid = (nx, ny, nlay) if kn_grid is None else tuple(int(k) for k in kn_grid)
+
+    _, col_gas, _ = gas_state(be, kd_lw, atm, None, interpolate=False)
+    tau = be.gas_optics_lw_direct(kd_lw, atm.p_lay, atm.t_lay, col_gas, be.empty((ngpt, nlay, ncol)))
+    src = be.planck_source_direct(kd_lw, atm.p_lay, atm.t_lay, atm.t_lev, atm.t_sfc, _sfc_lay(atm), col_gas)
+    cld = be.cloud_optics_2str(cloud_lut, atm.lwp, atm.iwp, atm.rel, atm.dei) if cloud_lut is not None else None
+    r = be.thermal_render(tau, None, nx, ny, dx, dy, dz, sfc_emis, src["lay_src"], src["sfc_src"], kn_grid, camera, rays_per_pixel, seed,
+                          top_at_1=atm.top_at_1, cloud=cld, band_lims=kd_lw.band_lims_gpt, max_events=max_events,
+                          top_radiance=top_radiance, by_band=channels is not None)
+    if M is not None:
+        band = r["radiance"]
+        r["radiance"] = (be.asarray(M) @ band.reshape(nbnd, -1)).reshape(M.shape[0], *band.shape[1:])
+    return r
+
+
 def _raytracer_medium(who, be, atm, tau, ssa, cld, aer, cloud_lut, phase_table, n_domain, z_lev):
     """What raytrace_sw and render_sw do with the chain's optics before they call the binding: with n_domain the split into the
     grid's arrays and a Background, the phase table with the (grid's) radius, and the medium that goes to the binding as keywords:
