@@ -1,5 +1,5 @@
 /* Raytracer_thermal_gpu -- thermal emission in the backward Monte Carlo ray tracer: longwave radiances for a virtual camera, 3-D
- * longwave fluxes for a flux sensor (rrx_thermal_render). The longwave twin of Raytracer_bw_gpu, with the same
+ * longwave fluxes for a flux sensor (rrx_thermal_render; rrx_thermal_render_spectral). The longwave twin of Raytracer_bw_gpu, with the same
  * Sensor_bw: it takes the clear g-point optical depth, the Planck sources and the band cloud triple as the LW gas and cloud optics
  * write them. No background, no aerosol, no phase table. */
 #ifndef RAYTRACER_THERMAL_H
@@ -31,6 +31,26 @@ class Raytracer_thermal_gpu
                 const int knx, const int kny, const int knz,
                 const Sensor_bw& sensor,
                 const long long rays_per_pixel, const unsigned long long seed, const int max_events,
+                Array_gpu<Float,3>& radiance, unsigned long long* n_clamped = nullptr);
+
+        // The rays of all g-points in one launch, tallied by band, and a channel matrix from bands to what the sensor sees
+        // (rrx_thermal_render_spectral): trace_rays_thermal with rays_per_pixel_gpt (ngpt) on the host, the rays per
+        // pixel of every g-point (the caller's, or Raytracer_gpu::spectral_allocation's over the g-points' emission; a g-point with
+        // none is left out of the result), and chan_weights (nbnd, nchan) on the host. radiance (npx, npy, nchan) is overwritten.
+        unsigned long long trace_rays_thermal_spectral(
+                const int nx, const int ny, const int nz,
+                const Float dx, const Float dy, const Float dz,
+                const bool top_at_1,
+                const Array_gpu<Float,3>& tau, const Array_gpu<Float,3>& ssa,
+                const Array_gpu<int,2>& band_lims_gpt,
+                const Array_gpu<Float,3>& cld_tau, const Array_gpu<Float,3>& cld_ssa, const Array_gpu<Float,3>& cld_g,
+                const Array_gpu<Float,1>& sfc_emis,
+                const Array_gpu<Float,3>& lay_src, const Array_gpu<Float,2>& sfc_src,
+                const Array<Float,1>& top_radiance,
+                const int knx, const int kny, const int knz,
+                const Sensor_bw& sensor,
+                const Array<long long,1>& rays_per_pixel_gpt, const unsigned long long seed, const int max_events,
+                const Array<Float,2>& chan_weights,
                 Array_gpu<Float,3>& radiance, unsigned long long* n_clamped = nullptr);
 };
 #endif

@@ -990,8 +990,30 @@ int rrx_camera_render_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, 
    g-point of no band is dropped): the same bits as that loop made by hand. With a flux sensor pi x radiance is an irradiance. \
    An extent of 0 (nx, ny, nz, ngpt, npx, npy, nrays, rays_per_pixel): returns 0 without a launch. Refused, non-zero, before any HIP \
    call: what the backward entries refuse of grid, cloud triple and sensor; a NULL tau, lay_src, sfc_src, sfc_emis, k_null, sensor, \
-   counts, radiance or counter; a negative or non-finite top_radiance. LIMITS: no background layers, no aerosol, no phase table, one \
-   g-point per launch, a cell-constant source, no brightness temperatures. */ \
+   counts, radiance or counter; a negative or non-finite top_radiance. LIMITS: no background layers, no aerosol, no phase table, a \
+   cell-constant source, no brightness temperatures. \
+   ---- The thermal tracer with the rays of all g-points in one launch, counts kept by band, and a channel matrix from bands to what a \
+   sensor sees, ngpt <= 1024: the longwave counterpart of the rrx_camera_ entries. The rays of a launch are the \
+   concatenation, in g-point order, of n_g = m_g npix rays per g-point, m_g >= 0 rays per pixel; ray_end (ngpt+1) holds the prefix sums \
+   with ray_end[0] = 0. Global index p belongs to the g with ray_end[g] <= p < ray_end[g+1] (empty ranges are stepped over); its local \
+   index is q = p - ray_end[g], its stream that of ray q of rrx_thermal_trace_counts(igpt = g) and its pixel q mod npix: the same path, \
+   draw for draw. Only the source that a deposit reads is scaled, and it is scaled first: (weight (1 - f_no_abs)) (lay_src weight0[g]), \
+   (weight sfc_emis) (sfc_src weight0[g]), weight (top_radiance[g] weight0[g]); then the clamp at 2^20 and the tally into \
+   counts[band(g), pix] (nbnd, npix). band_lims_gpt is always needed; a g-point that lies in no band has no row and its deposits are \
+   dropped. With weight0[g] = 1 the counts of a band are the integer sums over its g-points of those of rrx_thermal_trace_counts. \
+   rrx_thermal_trace_counts_spectral: rrx_thermal_trace_counts without igpt; top_radiance is a DEVICE array (ngpt) or NULL for 0, and \
+   behind it stand the DEVICE arrays ray_end (ngpt+1) and weight0 (ngpt); k_null is rrx_rt_k_null_all's (with a NULL aer_tau); ray0 / \
+   nrays are a range of the list; counts, n_capped, n_clamped are caller-zeroed, added into, and additive over ranges of the list. The \
+   entry cannot look into device arrays: a ray beyond ray_end[ngpt] is stepped over and the kernel stays inside its arrays whatever \
+   ray_end holds; the callers that form the list on the host refuse one that does not ascend. \
+   rrx_thermal_render_spectral: rrx_thermal_render with rays_per_pixel_gpt (ngpt, HOST) = m_g in place of rays_per_pixel, and nchan, \
+   chan_weights (nchan, nbnd, HOST) and radiance (nchan, npix) in W m-2 sr-1 in place of by_band and radiance; top_radiance (ngpt, HOST) \
+   or NULL. weight0[g] = (F(1) / F(m_g)) / U, U = F(n_act) / F(P), n_act the number of g-points with m_g > 0, P the sum of m_g: exactly 1 \
+   for equal m_g. It traces chunks of consecutive g-points (as many as keep k_null within 1 GiB, or RRX_RT_SPECTRAL_GPT_PER_LAUNCH), \
+   adds all chunks' counts in integers and converts once with rrx_camera_channels and scale = U; the result does not depend on the \
+   chunking. A g-point with m_g = 0 is left out of the result: the caller answers for its sources being 0. All m_g = 0: zeroes its \
+   outputs and returns 0. It waits for its stream once. Refused before any HIP call: what the two entries above refuse, ngpt > 1024, \
+   nbnd < 1, a NULL band_lims_gpt, ray_end, weight0 or rays_per_pixel_gpt, m_g < 0, nchan < 1, a NULL chan_weights, a negative ray0. */ \
 int rrx_thermal_trace_counts##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, \
         const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
         F dx, F dy, F dz, const F* sfc_emis, const F* lay_src, const F* sfc_src, F top_radiance, int knx, int kny, int knz, const F* k_null, \
@@ -1001,7 +1023,19 @@ int rrx_thermal_render##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool 
         const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
         F dx, F dy, F dz, const F* sfc_emis, const F* lay_src, const F* sfc_src, const F* top_radiance, int knx, int kny, int knz, \
         int sensor_type, int npx, int npy, F fov, const F* sensor, long long rays_per_pixel, unsigned long long seed, int max_events, \
-        RrxBool by_band, F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream);
+        RrxBool by_band, F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream); \
+int rrx_thermal_trace_counts_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_emis, const F* lay_src, const F* sfc_src, const F* top_radiance, \
+        const long long* ray_end, const F* weight0, int knx, int kny, int knz, const F* k_null, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
+        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream); \
+int rrx_thermal_render_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_emis, const F* lay_src, const F* sfc_src, const F* top_radiance, int knx, int kny, int knz, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, const long long* rays_per_pixel_gpt, unsigned long long seed, \
+        int max_events, int nchan, const F* chan_weights, F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
+        void* stream);
 
 RRX_DECLARE(double, _f64)
 RRX_DECLARE(float, _f32)

@@ -38,10 +38,22 @@
 // mean radiance is an irradiance). A start at or above the top with a downward direction is moved along the ray to the top.
 //
 // SHAPE. One ray per lane, lanes refill from a round-robin list inside the one event loop, RT_BLOCK threads, the grid capped by
-// max_blocks(). No LDS. Registers: DESIGN 4.23.
+// max_blocks(). No LDS in the per-g-point form. Registers: DESIGN 4.23.
 //
-// LIMITS: no background layers above the grid (top_radiance closes the medium), no aerosol, no phase table, one g-point per launch, a
-// cell-constant source (no interpolation between level sources), no brightness temperatures.
+// SPECTRAL (trace_thermal_kernel<F,true>, the _spectral entries; rrx_rt_common.h): the rays of all g-points in one launch.
+// a.ray0 / a.nrays address the concatenated list whose prefix sums are sp.photon_end (here: ray_end); the g-point is state of the ray,
+// set when a lane takes its next one. Ray p of the list is ray q = p - ray_end[g] of g-point g in the per-g-point launch, draw for draw.
+// The g-point is not a register of its own: it is read back from word 2 of the ray's Philox counter (g | 0xC0000000), which the lane
+// carries anyway. The k_null slice, the tau / ssa / lay_src / cloud slices and the sfc_src slice are derived from it where they are
+// read (the block's k_null, the collision, the surface hit): the lane carries no pointers around the loop (registers: DESIGN 4.24).
+// Only the source that a deposit reads is scaled, and it is scaled first:
+//   d = (weight (1 - f_no_abs)) (lay_src[cell, g] weight0[g]),  (weight sfc_emis[col]) (sfc_src[col, g] weight0[g]),
+//   weight (top_radiance[g] weight0[g]);  top_radiance is a device array here, NULL = 0;
+// then the clamp at 2^20, and the tally into counts[band(g) npix + pix]; a.igpt and a.top_radiance are not read. A g-point that lies
+// in no band has no row of counts: its deposits are dropped (a clamped one is still counted). ray_end and the band table live in LDS.
+//
+// LIMITS: no background layers above the grid (top_radiance closes the medium), no aerosol, no phase table, a cell-constant source (no
+// interpolation between level sources), no brightness temperatures.
 #include "rrx_rt_host.h"
 
 namespace
@@ -66,9 +78,21 @@ struct ThermalArgs
     u64* counts; u64* n_capped; u64* n_clamped;
 };
 
-template<typename F>
-__global__ void __launch_bounds__(RT_BLOCK) trace_thermal_kernel(const ThermalArgs<F> a)
+// what the spectral form takes beside ThermalArgs: the ray list and the weights (SpecIn; dif_frac is not read) and the top radiance of
+// every g-point on the device (NULL: 0); empty in the per-g-point form
+template<typename F, bool SPECTRAL> struct ThermalSpecArgs {};
+template<typename F> struct ThermalSpecArgs<F,true> { SpecIn<F> sp; const F* top_radiance; };
+
+template<typename F, bool SPECTRAL>
+__global__ void __launch_bounds__(RT_BLOCK) trace_thermal_kernel(const ThermalArgs<F> a, const ThermalSpecArgs<F,SPECTRAL> s)
 {
+    [[maybe_unused]] SpecView sv{};
+    if constexpr (SPECTRAL)
+    {
+        extern __shared__ double spectral_lds[];
+        BgView<F> no_bg{};
+        sv = stage_spectral<F>(s.sp, BgIn<F>{}, a.nbnd, a.band_lims_gpt, spectral_lds, no_bg);          // (it ends with the barrier)
+    }
     const long long nthreads = (long long)gridDim.x*blockDim.x;
     long long next_ray = (long long)blockIdx.x*blockDim.x + threadIdx.x;
 
@@ -78,23 +102,49 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_thermal_kernel(const ThermalAr
     const F kdx = F(rx)*a.dx, kdy = F(ry)*a.dy, kdz = F(rz)*a.dz;
     const F len_x = F(a.knx)*kdx, len_y = F(a.kny)*kdy, z_top = F(a.knz)*kdz;
     const int npix = a.npx*a.npy;
-    // the g-point is fixed for the launch
-    const int ibnd = a.cld_tau != nullptr ? band_of(a.igpt, a.nbnd, a.band_lims_gpt) : -1;
-    const F* __restrict__ tau_g = a.tau + ncol*nz*a.igpt;
-    const F* __restrict__ ssa_g = a.ssa != nullptr ? a.ssa + ncol*nz*a.igpt : nullptr;
-    const F* __restrict__ lay_src_g = a.lay_src + ncol*nz*a.igpt;
-    const F* __restrict__ sfc_src_g = a.sfc_src + ncol*a.igpt;
+    // the g-point is fixed for the launch, or under SPECTRAL state of the lane's ray (word 2 of its Philox counter): what follows is
+    // then derived from it where it is read
+    Stream rng; rng.k0 = a.k0; rng.k1 = a.k1; rng.used = 4; rng.block = 0u; rng.c0 = rng.c1 = rng.c2 = 0u;
+    const auto gpt = [&]() {
+        if constexpr (SPECTRAL) return int(rng.c2 & 0x3FFFFFFFu);
+        else return a.igpt;
+    };
+    int ibnd = -1;
+    const F* __restrict__ tau_g = a.tau;
+    const F* __restrict__ ssa_g = a.ssa;
+    const F* __restrict__ lay_src_g = a.lay_src;
+    const F* __restrict__ sfc_src_g = a.sfc_src;
     const F* __restrict__ kn_g = a.k_null;
+    if constexpr (!SPECTRAL)
+    {
+        ibnd = a.cld_tau != nullptr ? band_of(a.igpt, a.nbnd, a.band_lims_gpt) : -1;
+        tau_g = a.tau + ncol*nz*a.igpt;
+        ssa_g = a.ssa != nullptr ? a.ssa + ncol*nz*a.igpt : nullptr;
+        lay_src_g = a.lay_src + ncol*nz*a.igpt;
+        sfc_src_g = a.sfc_src + ncol*a.igpt;
+    }
     const F inf = F(INFINITY);
     const F g_max = F(1.) - Lim<F>::eps();
-    // a deposit d of the lane's ray: clamped at 2^20 and tallied into its pixel
+    // a source as a deposit reads it: under SPECTRAL scaled by the g-point's weight, before anything else
+    const auto source = [&](const F v) {
+        if constexpr (SPECTRAL) return v*s.sp.weight0[gpt()];
+        else return v;
+    };
+    const auto top_source = [&]() {
+        if constexpr (SPECTRAL) return (s.top_radiance != nullptr ? s.top_radiance[gpt()] : F(0.))*s.sp.weight0[gpt()];
+        else return a.top_radiance;
+    };
+    // a deposit d of the lane's ray: clamped at 2^20 and tallied into its pixel (SPECTRAL: of its g-point's band)
     const auto deposit = [&](const F d, const int pix) {
+        size_t slot = size_t(pix);
+        [[maybe_unused]] int band = 0;
+        if constexpr (SPECTRAL) { band = sv.band[gpt()]; slot += size_t(band < 0 ? 0 : band)*size_t(npix); }
         const bool clamped = d > F(1048576.);
         if (clamped) atomicAdd(a.n_clamped, 1ull);
-        tally(a.counts, size_t(pix), to_count(clamped ? F(1048576.) : d));
+        if constexpr (SPECTRAL) { if (band < 0) return; }
+        tally(a.counts, slot, to_count(clamped ? F(1048576.) : d));
     };
 
-    Stream rng; rng.k0 = a.k0; rng.k1 = a.k1; rng.used = 4; rng.block = 0u; rng.c0 = rng.c1 = rng.c2 = 0u;
     bool alive = false, pending = false;
     int in = 0, jn = 0, kn = 0, nev = 0, pix = 0;
     F x = F(0.), y = F(0.), z = F(0.), ux = F(0.), uy = F(0.), uz = F(-1.), weight = F(0.), tau = F(0.);
@@ -105,9 +155,16 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_thermal_kernel(const ThermalAr
         if (!alive)
         {
             if (next_ray >= a.nrays) break;          // the list is finite and every ray ends within max_events events
-            const u64 r = a.ray0 + u64(next_ray);
+            u64 r = a.ray0 + u64(next_ray);
             next_ray += nthreads;
-            rng.start(r, unsigned(a.igpt) | 0xC0000000u);
+            int igpt = a.igpt;
+            if constexpr (SPECTRAL)
+            {
+                igpt = gpt_of_photon(sv.photon_end, sv.ngpt, (long long)r);
+                if (igpt >= sv.ngpt) continue;          // (beyond the list)
+                r = r - u64(sv.photon_end[igpt]);
+            }
+            rng.start(r, unsigned(igpt) | 0xC0000000u);
             pix = int(r % u64(npix));
             const int ipx = pix % a.npx, ipy = pix / a.npx;
             const F fa = (F(ipx) + rng.next<F>()) / F(a.npx);
@@ -140,7 +197,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_thermal_kernel(const ThermalAr
             if (sz >= z_top)
             {
                 // it looks away from the medium: the ray ends at the top, with what comes down through it
-                if (!(uz < F(0.))) { deposit(a.top_radiance, pix); continue; }
+                if (!(uz < F(0.))) { deposit(top_source(), pix); continue; }
                 if (sz > z_top) { const F t = (z_top - sz)/uz; sx = sx + ux*t; sy = sy + uy*t; }
                 sz = z_top;
             }
@@ -158,6 +215,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_thermal_kernel(const ThermalAr
         const F sy = uy > F(0.) ? (y_hi - y)/uy : (uy < F(0.) ? (y_lo - y)/uy : inf);
         const F d_max = min(sz, min(sx, sy));
         const int axis = (sz <= sx && sz <= sy) ? 2 : (sx <= sy ? 0 : 1);
+        if constexpr (SPECTRAL) kn_g = a.k_null + (size_t(a.knx)*a.kny*a.knz)*size_t(gpt() - s.sp.kn_g0);
         const F kn_val = kn_g[in + a.knx*(jn + a.kny*kn)];
         if (!pending) tau = -log(rng.next<F>());
         pending = false;
@@ -182,7 +240,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_thermal_kernel(const ThermalAr
             }
             else if (uz > F(0.))
             {
-                if (kn == a.knz - 1) { deposit(weight*a.top_radiance, pix); alive = false; }          // out through the domain top
+                if (kn == a.knz - 1) { deposit(weight*top_source(), pix); alive = false; }          // out through the domain top
                 else { ++kn; z = F(kn)*kdz; }
             }
             else if (kn == 0)                 // the surface: it emits, and reflects the rest
@@ -190,7 +248,8 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_thermal_kernel(const ThermalAr
                 z = F(0.);
                 const int col = fine_cell(x, a.dx, in, rx) + nx*fine_cell(y, a.dy, jn, ry);
                 const F emis = a.sfc_emis[col];
-                deposit((weight*emis)*sfc_src_g[col], pix);
+                if constexpr (SPECTRAL) sfc_src_g = a.sfc_src + ncol*gpt();
+                deposit((weight*emis)*source(sfc_src_g[col]), pix);
                 weight = weight * (F(1.) - emis);
                 if (weight < F(0.5)) weight = (rng.next<F>() > weight) ? F(0.) : F(1.);
                 if (!(weight > F(0.))) { alive = false; continue; }
@@ -207,6 +266,13 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_thermal_kernel(const ThermalAr
             const int i = fine_cell(x, a.dx, in, rx), j = fine_cell(y, a.dy, jn, ry), k = fine_cell(z, a.dz, kn, rz);
             const int lay = a.top_at_1 ? nz-1-k : k;
             const size_t cell = size_t(i) + size_t(j)*nx + ncol*lay;
+            if constexpr (SPECTRAL)
+            {
+                ibnd = a.cld_tau != nullptr ? sv.band[gpt()] : -1;
+                tau_g = a.tau + ncol*nz*gpt();
+                ssa_g = a.ssa != nullptr ? a.ssa + ncol*nz*gpt() : nullptr;
+                lay_src_g = a.lay_src + ncol*nz*gpt();
+            }
             const F t = tau_g[cell], w0 = ssa_g != nullptr ? ssa_g[cell] : F(0.);
             F tc = F(0.), wc = F(0.), gc = F(0.);
             if (ibnd >= 0)
@@ -218,7 +284,7 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_thermal_kernel(const ThermalAr
             const F k_sca = (t*w0 + tc*wc) / a.dz;
             const F k_sca_cld = (tc*wc) / a.dz;
             const F f_no_abs = clampf(F(1.) - (k_ext - k_sca)/kn_val, F(0.), F(1.));
-            deposit((weight*(F(1.) - f_no_abs))*lay_src_g[cell], pix);
+            deposit((weight*(F(1.) - f_no_abs))*source(lay_src_g[cell]), pix);
             weight = weight * f_no_abs;
             if (weight < F(0.5)) weight = (rng.next<F>() > weight) ? F(0.) : F(1.);
             if (!(weight > F(0.))) { alive = false; continue; }
@@ -308,7 +374,16 @@ template<typename F>
 void launch_trace_thermal(const ThermalArgs<F>& a, hipStream_t st)
 {
     const int blocks = int(std::min<long long>((a.nrays + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
-    trace_thermal_kernel<F><<<blocks, RT_BLOCK, 0, st>>>(a);
+    trace_thermal_kernel<F,false><<<blocks, RT_BLOCK, 0, st>>>(a, ThermalSpecArgs<F,false>{});
+}
+
+// the spectral form: a.ray0 / a.nrays are a range of the concatenated list sp.photon_end, a.k_null holds the slices from g-point
+// sp.kn_g0 on, top_radiance is a device array (ngpt) or NULL
+template<typename F>
+void launch_trace_thermal_spectral(const ThermalArgs<F>& a, const SpecIn<F>& sp, const F* top_radiance, hipStream_t st)
+{
+    const int blocks = int(std::min<long long>((a.nrays + RT_BLOCK - 1) / RT_BLOCK, max_blocks()));
+    trace_thermal_kernel<F,true><<<blocks, RT_BLOCK, spectral_lds_bytes(sp.ngpt, 0, sizeof(F)), st>>>(a, ThermalSpecArgs<F,true>{sp, top_radiance});
 }
 
 // rrx_thermal_trace_counts
@@ -402,6 +477,132 @@ int thermal_render_entry(const char* entry, const Medium<F>& m, const ThermalSou
     }
     RRX_CATCH(entry)
 }
+
+// ---- the spectral form: rays of all g-points in one launch, counts by band, bands to channels
+
+inline void check_thermal_channels(const int nbnd, const int nchan)
+{
+    if (nbnd < 1) throw std::runtime_error("nbnd must be >= 1: the counts are kept by band");
+    if (nchan < 1) throw std::runtime_error("nchan must be >= 1");
+}
+
+// rrx_thermal_trace_counts_spectral: top_radiance, sp.photon_end (the ray list's prefix sums) and sp.weight0 are device arrays that the
+// entry cannot look into. The kernel stays inside its arrays whatever they hold (the search is bounded by ngpt, a ray beyond the list is
+// stepped over, the pixel is taken modulo npix); the callers that form the list on the host refuse one that does not ascend. k_null is
+// that of all g-points.
+template<typename F>
+int thermal_trace_spectral_entry(const char* entry, const Medium<F>& m, const ThermalSources<F>& src, const F* top_radiance, const Run& run,
+                                 const ThermalSensor<F>& sensor, const SpecIn<F>& sp, const F* k_null, const long long ray0, const long long nrays,
+                                 u64* counts, u64* n_capped, u64* n_clamped)
+{
+    RRX_TRY
+    if (check_thermal(m, src, run.max_events, sensor, {"nrays", nrays},
+                      {{"band_lims_gpt", m.band_lims_gpt}, {"ray_end", sp.photon_end}, {"weight0", sp.weight0}, {"k_null", k_null}, {"sensor", sensor.s}},
+                      {{"counts", counts}, {"n_capped", n_capped}, {"n_clamped", n_clamped}},
+                      [&] { check_spectral_ngpt(m.ngpt);
+                            if (m.nbnd < 1) throw std::runtime_error("nbnd must be >= 1: the counts are kept by band");
+                            if (ray0 < 0) throw std::runtime_error("ray0 is negative"); }, nothing, nothing))
+        return 0;
+    launch_trace_thermal_spectral<F>(thermal_args<F>(m, src, F(0.), sensor, 0, k_null, run.seed, u64(ray0), nrays, run.max_events,
+                                                     counts, n_capped, n_clamped), sp, top_radiance, static_cast<hipStream_t>(run.stream));
+    RRX_CATCH(entry)
+}
+
+// the small entries that the spectral loop is made of beside LoopEntries, by precision
+template<typename F> struct SpectralEntries;
+template<> struct SpectralEntries<double>
+{
+    static constexpr auto k_null_all = rrx_rt_k_null_all_f64; static constexpr auto channels = rrx_camera_channels_f64;
+};
+template<> struct SpectralEntries<float>
+{
+    static constexpr auto k_null_all = rrx_rt_k_null_all_f32; static constexpr auto channels = rrx_camera_channels_f32;
+};
+
+// rrx_thermal_render_spectral: m_gpt[g] rays per pixel of g-point g (a host array). One trace launch per chunk of consecutive g-points,
+// the counts of all chunks added in integers by band and converted once, with the common unit U = n_act / P, through the channel
+// matrix. THE WORKSPACE, in u64 words: | counts (nbnd, npix) | k_null of a chunk | ray_end | weight0 | top_radiance | the channel matrix |
+template<typename F>
+int thermal_render_spectral_entry(const char* entry, const Medium<F>& m, const ThermalSources<F>& src, const F* top_radiance, const Run& run,
+                                  const ThermalSensor<F>& sensor, const long long* m_gpt, const int nchan, const F* chan_weights,
+                                  F* radiance, u64* n_capped, u64* n_clamped)
+{
+    RRX_TRY
+    typedef LoopEntries<F> E;
+    typedef SpectralEntries<F> S;
+    const long long npix_ll = (long long)sensor.npx*sensor.npy;
+    std::vector<long long> ray_end;
+    long long P = 0, n_act = 0;
+    if (check_thermal(m, src, run.max_events, sensor, {"ngpt", m.ngpt},
+                      {{"band_lims_gpt", m.band_lims_gpt}, {"rays_per_pixel_gpt", m_gpt}, {"chan_weights", chan_weights}, {"sensor", sensor.s}},
+                      {{"radiance", radiance}, {"n_capped", n_capped}, {"n_clamped", n_clamped}},
+                      [&] { check_spectral_ngpt(m.ngpt); check_thermal_channels(m.nbnd, nchan); }, nothing,
+                      [&] {
+                          if (npix_ll > 0x7FFFFFFFll) throw std::runtime_error("npx npy exceeds 2^31 - 1");
+                          if (top_radiance != nullptr) for (int g=0; g<m.ngpt; ++g) check_top_radiance(double(top_radiance[g]));
+                          ray_end.assign(size_t(m.ngpt) + 1, 0);
+                          for (int g=0; g<m.ngpt; ++g)
+                          {
+                              if (m_gpt[g] < 0) throw std::runtime_error("rays_per_pixel_gpt is negative at g-point " + std::to_string(g));
+                              if (m_gpt[g] > (0x7FFFFFFFFFFFFFFFll - ray_end[g]) / npix_ll) throw std::runtime_error("the ray list exceeds 2^63 - 1");
+                              ray_end[g+1] = ray_end[g] + m_gpt[g]*npix_ll;
+                              P += m_gpt[g];
+                              if (m_gpt[g] > 0) ++n_act;
+                          }
+                      }))
+        return 0;
+
+    hipStream_t st = static_cast<hipStream_t>(run.stream);
+    const size_t npix = size_t(npix_ll), nkn = size_t(m.knx)*m.kny*m.knz, n_counts = size_t(m.nbnd)*npix;
+    const int chunk = spectral_gpt_per_launch(nkn*sizeof(F), m.ngpt);
+    bool ok = hipMemsetAsync(n_capped, 0, sizeof(u64), st) == hipSuccess;
+    ok = ok && hipMemsetAsync(n_clamped, 0, sizeof(u64), st) == hipSuccess;
+    ok = ok && hipMemsetAsync(radiance, 0, size_t(nchan)*npix*sizeof(F), st) == hipSuccess;
+    if (!ok) throw std::runtime_error("zeroing the outputs failed");
+    if (P == 0) return 0;
+    const F U = F(n_act) / F(P);
+    std::vector<F> weight0(m.ngpt, F(0.));
+    for (int g=0; g<m.ngpt; ++g)
+        if (m_gpt[g] > 0) weight0[g] = (F(1.) / F(m_gpt[g])) / U;
+
+    const size_t n_kn = words_of(nkn*size_t(chunk)*sizeof(F));
+    const size_t n_re = size_t(m.ngpt) + 1, n_w = words_of(size_t(m.ngpt)*sizeof(F)), n_cw = words_of(size_t(nchan)*m.nbnd*sizeof(F));
+    WorkspaceLease lease(st);
+    u64* counts = lease.get<u64>(n_counts + n_kn + n_re + 2*n_w + n_cw);
+    F* k_null = reinterpret_cast<F*>(counts + n_counts);
+    long long* ray_end_d = reinterpret_cast<long long*>(counts + n_counts + n_kn);
+    F* weight0_d = reinterpret_cast<F*>(counts + n_counts + n_kn + n_re);
+    F* top_d = reinterpret_cast<F*>(counts + n_counts + n_kn + n_re + n_w);
+    F* chan_d = reinterpret_cast<F*>(counts + n_counts + n_kn + n_re + 2*n_w);
+    ok = hipMemsetAsync(counts, 0, n_counts*sizeof(u64), st) == hipSuccess
+      && hipMemcpyAsync(ray_end_d, ray_end.data(), ray_end.size()*sizeof(long long), hipMemcpyHostToDevice, st) == hipSuccess
+      && hipMemcpyAsync(weight0_d, weight0.data(), size_t(m.ngpt)*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess
+      && (top_radiance == nullptr
+          || hipMemcpyAsync(top_d, top_radiance, size_t(m.ngpt)*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess)
+      && hipMemcpyAsync(chan_d, chan_weights, size_t(nchan)*m.nbnd*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess
+      && hipStreamSynchronize(st) == hipSuccess;          // (the host arrays end with this call)
+    if (!ok) throw std::runtime_error("zeroing the counts or copying the ray list failed");
+    for (int g0=0; g0<m.ngpt; g0+=chunk)
+    {
+        const int g1 = std::min(g0 + chunk, m.ngpt);
+        const long long n = ray_end[g1] - ray_end[g0];
+        if (n == 0) continue;
+        // k_null of the chunk's g-points: rrx_rt_k_null_all when the chunk is the whole list, otherwise slice by slice (the same bits)
+        if (chunk == m.ngpt)
+            forward(S::k_null_all(m.nx, m.ny, m.nz, m.ngpt, m.nbnd, m.top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, m.dz, m.knx, m.kny, m.knz,
+                                  k_null, nullptr, run.stream));
+        else
+            for (int g=g0; g<g1; ++g)
+                if (ray_end[g+1] > ray_end[g])
+                    forward(E::k_null(m.nx, m.ny, m.nz, m.ngpt, m.nbnd, g, m.top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, m.dz, m.knx, m.kny, m.knz,
+                                      k_null + nkn*size_t(g - g0), run.stream));
+        launch_trace_thermal_spectral<F>(thermal_args<F>(m, src, F(0.), sensor, 0, k_null, run.seed, u64(ray_end[g0]), n, run.max_events,
+                                                         counts, n_capped, n_clamped),
+                                         SpecIn<F>{m.ngpt, g0, ray_end_d, weight0_d, nullptr}, top_radiance != nullptr ? top_d : nullptr, st);
+    }
+    forward(S::channels(npix_ll, m.nbnd, nchan, counts, chan_d, U, radiance, run.stream));
+    RRX_CATCH(entry)
+}
 }  // namespace
 
 // ---- the C entries: each builds the structs and calls its one function
@@ -428,7 +629,19 @@ int rrx_thermal_render##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool 
         unsigned long long seed, int max_events, RrxBool by_band, F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
         void* stream) \
 { return thermal_render_entry<F>("rrx_thermal_render" #SFX, TH_MEDIUM(F), TH_SOURCES(F), top_radiance, RT_RUN, TH_SENSOR(F), rays_per_pixel, \
-                                 by_band != 0, radiance, n_capped, n_clamped); }
+                                 by_band != 0, radiance, n_capped, n_clamped); } \
+int rrx_thermal_trace_counts_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, TH_P_SCENE(F), const F* top_radiance, \
+        const long long* ray_end, const F* weight0, int knx, int kny, int knz, const F* k_null, \
+        int sensor_type, int npx, int npy, F fov, const F* sensor, unsigned long long seed, long long ray0, long long nrays, int max_events, \
+        unsigned long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream) \
+{ return thermal_trace_spectral_entry<F>("rrx_thermal_trace_counts_spectral" #SFX, TH_MEDIUM(F), TH_SOURCES(F), top_radiance, RT_RUN, TH_SENSOR(F), \
+                                         SpecIn<F>{ngpt, 0, ray_end, weight0, nullptr}, k_null, ray0, nrays, counts, n_capped, n_clamped); } \
+int rrx_thermal_render_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, TH_P_SCENE(F), const F* top_radiance, \
+        int knx, int kny, int knz, int sensor_type, int npx, int npy, F fov, const F* sensor, const long long* rays_per_pixel_gpt, \
+        unsigned long long seed, int max_events, int nchan, const F* chan_weights, F* radiance, unsigned long long* n_capped, \
+        unsigned long long* n_clamped, void* stream) \
+{ return thermal_render_spectral_entry<F>("rrx_thermal_render_spectral" #SFX, TH_MEDIUM(F), TH_SOURCES(F), top_radiance, RT_RUN, TH_SENSOR(F), \
+                                          rays_per_pixel_gpt, nchan, chan_weights, radiance, n_capped, n_clamped); }
 
 RRX_DEFINE_THERMAL(double, _f64)
 RRX_DEFINE_THERMAL(float, _f32)

@@ -570,7 +570,7 @@ class HipKernels:
         self._c("mcica_cloud_mask", ncol, nlay, ngpt, *head, mask)
         return mask
 
-    # The Monte Carlo ray tracers (DESIGN 4.14 - 4.23). Every wrapper below gathers its arguments into a raytracer_args.RtScene, makes
+    # The Monte Carlo ray tracers (DESIGN 4.14 - 4.24). Every wrapper below gathers its arguments into a raytracer_args.RtScene, makes
     # or accepts the outputs, calls the entry the scene names with the scene's argument groups, and unpacks.
     #   tau, ssa (ngpt, nz, ncol) with ncol = nx ny, x fastest; sfc_albedo (ncol,); kn_grid = (knx, kny, knz);
     #   cloud: None or (tau, ssa, g), (nbnd, nz, ncol) each, with band_lims (nbnd, 2);
@@ -930,6 +930,51 @@ class HipKernels:
         lims = band_lims if by_band else scene[2]
         self._c("thermal_render", *sc.dims, sc.flags[0], *scene[:2], lims, *scene[3:], top_radiance, *sc.kn, *sensor, rays_per_pixel,
                 *sc.run(seed, max_events), by_band, radiance, n_capped, n_clamped)
+        return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
+
+    # The thermal tracer with the rays of all g-points in one launch, counts by band and a channel matrix
+    # (rrx_thermal_trace_counts_spectral, rrx_thermal_render_spectral). band_lims is always needed (the counts are kept by
+    # band); the counts are converted by camera_channels. ngpt <= 1024.
+    def _thermal_spectral_scene(self, who, tau, ssa, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src, kn_grid, top_at_1, cloud, band_lims):
+        """(the gathered scene; tau ... sfc_src with band_lims whether there is cloud or not)"""
+        if band_lims is None:
+            raise ValueError(f"thermal: {who} needs band_lims (the counts are kept by band)")
+        sc, scene = self._thermal_scene(tau, ssa, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src, kn_grid, top_at_1, cloud, band_lims)
+        return sc, (*scene[:2], band_lims, *scene[3:])
+
+    def thermal_trace_counts_spectral(self, tau, ssa, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src, top_radiance, ray_end, weight0, kn_grid,
+                                      k_null, camera, seed, ray0, nrays, band_lims, top_at_1=False, cloud=None, counts=None, max_events=None):
+        """Adds the rays [ray0, ray0 + nrays) of the concatenated list into counts (camera_zero_counts; made when None): counts
+        (nbnd, npix), n_capped, n_clamped. ray_end (ngpt+1,) int64, weight0 (ngpt,) and top_radiance, None (0) or (ngpt,): arrays on the
+        host, checked and uploaded here; k_null is rt_k_null_all's."""
+        sc, scene = self._thermal_spectral_scene("thermal_trace_counts_spectral", tau, ssa, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src,
+                                                 kn_grid, top_at_1, cloud, band_lims)
+        sensor = self._rt_sensor(camera)
+        if top_radiance is None:
+            top, lists = None, self._rt_list(sc.ngpt, "rays", ray0, nrays, ray_end=ray_end, weight0=weight0)
+        else:
+            *lists, top = self._rt_list(sc.ngpt, "rays", ray0, nrays, ray_end=ray_end, weight0=weight0, top_radiance=top_radiance)
+        counts = self.camera_zero_counts(sc.nbnd, sensor[1]*sensor[2]) if counts is None else counts
+        self._c("thermal_trace_counts_spectral", *sc.dims, sc.flags[0], *scene, top, *lists, *sc.kn, k_null, *sensor,
+                *sc.run(seed, max_events, ray0, nrays), counts["counts"], counts["n_capped"], counts["n_clamped"])
+        return counts
+
+    def thermal_render_spectral(self, tau, ssa, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src, kn_grid, camera, rays_per_pixel_gpt, seed,
+                                band_lims, chan_weights, top_at_1=False, cloud=None, max_events=None, top_radiance=None):
+        """thermal_render with rays_per_pixel_gpt (ngpt,) rays per pixel of each g-point (pipeline.spectral_allocation deals them by
+        emission) in place of rays_per_pixel, all g-points in one trace launch per chunk, and chan_weights (nchan, nbnd) on the host, the
+        matrix from bands to channels. A g-point with no rays is left out of the result. Returns radiance (nchan, npy, npx) in
+        W m-2 sr-1, n_capped and n_clamped (ints)."""
+        sc, scene = self._thermal_spectral_scene("thermal_render_spectral", tau, ssa, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src,
+                                                 kn_grid, top_at_1, cloud, band_lims)
+        rays, = self._rt_per_gpt(sc.ngpt, rays_per_pixel_gpt=rays_per_pixel_gpt)
+        if top_radiance is not None:
+            top_radiance, = self._rt_per_gpt(sc.ngpt, top_radiance=top_radiance)
+        M = self._rt_chan_weights(np.asarray(chan_weights), sc.nbnd)
+        sensor = self._rt_sensor(camera)
+        radiance, n_capped, n_clamped = self._rt_radiance((M.shape[0], sensor[2], sensor[1]))
+        self._c("thermal_render_spectral", *sc.dims, sc.flags[0], *scene, top_radiance, *sc.kn, *sensor, rays, *sc.run(seed, max_events),
+                int(M.shape[0]), M, radiance, n_capped, n_clamped)
         return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
 
     def delta_scale_2str_k(self, tau, ssa, g):

@@ -597,3 +597,60 @@ extern "C" int rrx_cxx_trace_rays_thermal(const int nx, const int ny, const int 
         rrx_host::set_stream(before);
     });
 }
+
+// Raytracer_thermal_gpu::trace_rays_thermal_spectral on device arrays the caller owns. rays_per_pixel_gpt (ngpt, HOST): the
+// rays per pixel of every g-point when total_rays < 0; otherwise total_rays is dealt by Raytracer_gpu::spectral_allocation over emission
+// (ngpt, HOST), the g-points' emission, and the array's contents are not used. chan_weights (nchan, nbnd) on the HOST; radiance: a device
+// array (nchan, npy, npx).
+extern "C" int rrx_cxx_trace_rays_thermal_spectral(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx,
+        const Float dy, const Float dz, const int top_at_1, const Float* tau, const Float* ssa, const int* band_lims_gpt,
+        const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_emis, const Float* lay_src, const Float* sfc_src,
+        const Float* top_radiance, const int knx, const int kny, const int knz, const int sensor_type, const int npx, const int npy, const Float fov,
+        const Float* sensor, const long long* rays_per_pixel_gpt, const long long total_rays, const Float* emission, const unsigned long long seed,
+        const int max_events, const int nchan, const Float* chan_weights, Float* radiance, unsigned long long* n_capped, unsigned long long* n_clamped,
+        void* stream)
+{
+    return guarded([&]
+    {
+        const std::string who = "rrx_cxx_trace_rays_thermal_spectral: ";
+        if (rays_per_pixel_gpt == nullptr) throw std::runtime_error(who + "rays_per_pixel_gpt is NULL");
+        if (chan_weights == nullptr) throw std::runtime_error(who + "chan_weights is NULL");
+        if (nchan < 1 || nbnd < 1) throw std::runtime_error(who + "nchan and nbnd must be >= 1");
+        if (total_rays >= 0 && emission == nullptr) throw std::runtime_error(who + "emission is NULL");
+        void* const before = rrx_host::current_stream();
+        rrx_host::set_stream(stream);
+        try
+        {
+            const int ncol = nx*ny;
+            auto view3 = [](const Float* p, int a, int b, int c) { return p ? Array_gpu<Float,3>(const_cast<Float*>(p), {a, b, c}) : Array_gpu<Float,3>(); };
+            Array<Float,1> h_top;
+            if (top_radiance != nullptr)
+            {
+                h_top.set_dims({ngpt});
+                for (int g=1; g<=ngpt; ++g) h_top({g}) = top_radiance[g-1];
+            }
+            Array<long long,1> h_m({ngpt});
+            for (int g=1; g<=ngpt; ++g) h_m({g}) = rays_per_pixel_gpt[g-1];
+            if (total_rays >= 0)
+            {
+                Array<Float,1> h_e({ngpt});
+                for (int g=1; g<=ngpt; ++g) h_e({g}) = emission[g-1];
+                h_m = Raytracer_gpu::spectral_allocation(h_e, total_rays, 1);
+            }
+            Array<Float,2> h_w({nbnd, nchan});
+            for (int c=1; c<=nchan; ++c)
+                for (int b=1; b<=nbnd; ++b) h_w({b, c}) = chan_weights[(c-1)*nbnd + (b-1)];
+            Sensor_bw s;
+            s.sensor_type = sensor_type; s.npx = npx; s.npy = npy; s.fov = fov;
+            for (int i=0; i<3; ++i) { s.position[i] = sensor[i]; s.e_w[i] = sensor[3+i]; s.e_h[i] = sensor[6+i]; s.e_d[i] = sensor[9+i]; }
+            Array_gpu<Float,3> out(radiance, {npx, npy, nchan});
+            Raytracer_thermal_gpu raytracer;
+            *n_capped = raytracer.trace_rays_thermal_spectral(nx, ny, nz, dx, dy, dz, top_at_1 != 0, view3(tau, ncol, nz, ngpt),
+                    view3(ssa, ncol, nz, ngpt), Array_gpu<int,2>(const_cast<int*>(band_lims_gpt), {2, nbnd}), view3(cld_tau, ncol, nz, nbnd),
+                    view3(cld_ssa, ncol, nz, nbnd), view3(cld_g, ncol, nz, nbnd), view1(sfc_emis, ncol), view3(lay_src, ncol, nz, ngpt),
+                    view2(sfc_src, ncol, ngpt), h_top, knx, kny, knz, s, h_m, seed, max_events, h_w, out, n_clamped);
+        }
+        catch (...) { rrx_host::set_stream(before); throw; }
+        rrx_host::set_stream(before);
+    });
+}

@@ -344,8 +344,24 @@ def render_sw(be, kd_sw, atm, nx, ny, dx, dy, dz, azimuth, camera, rays_per_pixe
     return be.raytracer_bw(*scene, rays_per_pixel, seed, band_lims=kd_sw.band_lims_gpt, **kw)
 
 
+def emission_allocation(e, lay_max, top_radiance, P, min_per_gpt=1):
+    """render_lw(allocation="emission"): m (ngpt,) int64 = spectral_allocation(e, P, min_per_gpt) with e_g the surface emission of
+    g-point g summed over the columns. A g-point with e_g = 0 gets no rays and is left out of the result, so it is refused when its
+    largest lay_src, lay_max[g], or its top_radiance[g] (None: 0) is positive: the result would be biased."""
+    e = np.asarray(e, dtype=np.float64).reshape(-1)
+    lay_max = np.asarray(lay_max, dtype=np.float64).reshape(-1)
+    top = np.zeros(e.size) if top_radiance is None else np.asarray(top_radiance, dtype=np.float64).reshape(-1)
+    if lay_max.size != e.size or top.size != e.size:
+        raise ValueError(f"render_lw: lay_src and top_radiance are per g-point (ngpt = {e.size}), got {lay_max.size}, {top.size}")
+    bad = np.flatnonzero((e == 0) & ((lay_max > 0) | (top > 0)))
+    if bad.size:
+        raise ValueError(f"render_lw: g-point {int(bad[0])} has no surface emission, so allocation='emission' gives it no rays, but its "
+                         "lay_src or top_radiance is positive: it would be left out of the result")
+    return spectral_allocation(e, P, min_per_gpt)
+
+
 def render_lw(be, kd_lw, atm, nx, ny, dx, dy, dz, camera, rays_per_pixel, seed, cloud_lut=None, kn_grid=None, sfc_emis=None,
-              max_events=None, channels=None, top_radiance=None):
+              max_events=None, channels=None, top_radiance=None, allocation=None, min_per_gpt=1):
     """Longwave radiances for a virtual camera or a flux sensor from the backward Monte Carlo ray tracer with thermal emission
     (rrx_thermal_render): the twin of render_sw on the LW chain's own arrays: the clear g-point tau of
     gas_optics_lw_direct (the gas does not scatter), the Planck sources of planck_source_direct (lay_src, constant within a cell, and
@@ -355,7 +371,14 @@ def render_lw(be, kd_lw, atm, nx, ny, dx, dy, dz, camera, rays_per_pixel, seed, 
     None, broadband radiance (npy, npx); "bands", radiance by band (nbnd, npy, npx); an array (nchan, nbnd), applied to the band
     radiances, (nchan, npy, npx). Returns radiance in W m-2 sr-1, n_capped and n_clamped. With a camera.flux_sensor pi x radiance is
     the irradiance of the pixel in W m-2 (pi x the mean radiance over the hemisphere): the surface downwelling (facing up) or the
-    outgoing longwave at the domain top (facing down). Every g-point gets rays_per_pixel rays."""
+    outgoing longwave at the domain top (facing down). Every g-point gets rays_per_pixel rays.
+    allocation="emission" (DESIGN 4.24): rays_per_pixel is the TOTAL over all g-points, dealt by spectral_allocation(e, rays_per_pixel,
+    min_per_gpt) in proportion to e_g, the sum over the columns of sfc_src[g] (taken on the host in float64); the rays of all g-points
+    are traced in one launch per chunk and tallied by band (rrx_thermal_render_spectral, ngpt <= 1024), and channels becomes the
+    matrix of that one call. The same dictionary comes back. A g-point with e_g = 0 gets no rays and is left out: it is refused
+    when its lay_src or top_radiance is positive (Planck sources never are where the surface's is 0)."""
+    if allocation not in (None, "emission"):
+        raise ValueError(f"render_lw: allocation is None or 'emission', got {allocation!r}")
     ncol, nlay, ngpt = atm.ncol, atm.nlay, kd_lw.ngpt
     if ncol != nx*ny:
         raise ValueError(f"render_lw: ncol = {ncol} is not nx ny = {nx}*{ny}")
@@ -380,6 +403,17 @@ def render_lw(be, kd_lw, atm, nx, ny, dx, dy, dz, camera, rays_per_pixel, seed, 
     tau = be.gas_optics_lw_direct(kd_lw, atm.p_lay, atm.t_lay, col_gas, be.empty((ngpt, nlay, ncol)))
     src = be.planck_source_direct(kd_lw, atm.p_lay, atm.t_lay, atm.t_lev, atm.t_sfc, _sfc_lay(atm), col_gas)
     cld = be.cloud_optics_2str(cloud_lut, atm.lwp, atm.iwp, atm.rel, atm.dei) if cloud_lut is not None else None
+    if allocation == "emission":
+        e = be.to_numpy(src["sfc_src"]).astype(np.float64).sum(axis=1)
+        lay_max = be.to_numpy(src["lay_src"].reshape(ngpt, -1).max(dim=1).values) if np.any(e == 0) else np.zeros(ngpt)
+        m = emission_allocation(e, lay_max, top_radiance, rays_per_pixel, min_per_gpt)
+        matrix = np.ones((1, nbnd)) if channels is None else np.eye(nbnd) if M is None else M
+        r = be.thermal_render_spectral(tau, None, nx, ny, dx, dy, dz, sfc_emis, src["lay_src"], src["sfc_src"], kn_grid, camera, m, seed,
+                                       kd_lw.band_lims_gpt, matrix, top_at_1=atm.top_at_1, cloud=cld, max_events=max_events,
+                                       top_radiance=top_radiance)
+        if channels is None:
+            r["radiance"] = r["radiance"][0]
+        return r
     r = be.thermal_render(tau, None, nx, ny, dx, dy, dz, sfc_emis, src["lay_src"], src["sfc_src"], kn_grid, camera, rays_per_pixel, seed,
                           top_at_1=atm.top_at_1, cloud=cld, band_lims=kd_lw.band_lims_gpt, max_events=max_events,
                           top_radiance=top_radiance, by_band=channels is not None)
