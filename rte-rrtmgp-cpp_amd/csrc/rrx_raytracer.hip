@@ -444,7 +444,7 @@ template<typename F, typename T, typename A, typename B, typename C>
 bool check_forward(const Medium<F>& m, const Sun<F>& sun, const PhaseIn<F>& ph, const Background<F>& bg, const int max_events,
                    Extents extents, Needed inputs, const FwOut<T>& o, A after_nbnd, B after_phase, C after_scene)
 {
-    return check_entry(m, sun, ph, bg, max_events, extents, inputs,
+    return check_entry(m, RT_NEEDED_SOLAR(m), &sun, ph, bg, max_events, extents, inputs,
                        {{"sfc_dn_dir", o.sfc_dn_dir}, {"sfc_dn_dif", o.sfc_dn_dif}, {"sfc_up", o.sfc_up}, {"tod_up", o.tod_up},
                         {"abs_dir", o.abs_dir}, {"abs_dif", o.abs_dif}, {"n_capped", o.n_capped}}, after_nbnd, after_phase, after_scene, nothing);
 }
@@ -463,6 +463,7 @@ TraceArgs<F> trace_args(const Medium<F>& m, const int igpt, const F* k_null, con
 {
     TraceArgs<F> a{};
     set_medium(a, m, igpt, k_null, max_events);
+    a.sfc_albedo = m.sfc_albedo;
     a.independent_column = m.independent_column ? 1 : 0;
     a.photon0 = photon0; a.nphotons = nphotons;
     a.sfc_dn_dir = t.sfc_dn_dir; a.sfc_dn_dif = t.sfc_dn_dif; a.sfc_up = t.sfc_up; a.tod_up = t.tod_up; a.abs_dir = t.abs_dir;

@@ -589,47 +589,14 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_bw_kernel(const BwArgs<F> a, c
 
 // ---- host side (rrx_rt_host.h)
 
-// the virtual camera: s is (12,): position, w, h, e_d
-template<typename F> struct Sensor { int type, npx, npy; F fov; const F* s; };
-
-// throws, or returns the bound of the walk to the sun
-template<typename F>
-int check_sensor(const Sensor<F>& sensor, const Medium<F>& m, const F mu0)
-{
-    const int type = sensor.type;
-    const F fov = sensor.fov;
-    const F* s = sensor.s;
-    if (type < 0 || type > 3) throw std::runtime_error("sensor_type must be 0 (perspective), 1 (fisheye), 2 (orthographic) or 3 (flux sensor)");
-    for (int i=0; i<12; ++i)
-        if (!std::isfinite(double(s[i]))) throw std::runtime_error("sensor holds a number that is not finite");
-    const double ex = s[9], ey = s[10], ez = s[11];
-    const double len = std::sqrt(ex*ex + ey*ey + ez*ez);
-    if (type == 0 || type == 1)
-    {
-        if (!(len > 0.)) throw std::runtime_error("sensor e_d is zero");
-        if (s[2] < F(0.)) throw std::runtime_error("sensor position lies below the surface");
-    }
-    if (type == 1 && (!(fov > F(0.)) || double(fov) > 6.283185307179586 + 1e-6)) throw std::runtime_error("fov must be in (0, 2 pi] for a fisheye sensor");
-    if (type == 2 && (std::fabs(len - 1.) > 1.e-5 || !(ez < 0.))) throw std::runtime_error("sensor e_d must be a unit vector with e_d.z < 0 for an orthographic sensor");
-    if (type == 3 && ez == 0.) throw std::runtime_error("sensor e_d.z must be > 0 (at the surface, facing up) or < 0 (at the top, facing down) for a flux sensor");
-    // the bound of the walk to the sun: nz + ceil(H tan / dx) + ceil(H tan / dy) + 2
-    const double tn = std::sqrt(std::max(0., 1. - double(mu0)*double(mu0))) / double(mu0), height = double(m.nz)*double(m.dz);
-    const double bound = double(m.nz) + std::ceil(height*tn/double(m.dx)) + std::ceil(height*tn/double(m.dy)) + 2.;
-    if (!(bound < 2.0e9)) throw std::runtime_error("mu0 is too small for this domain: the walk to the sun would take more than 2e9 cells");
-    return int(bound);
-}
-
-// the checks of the backward entries: check_entry with the sensor's extents and checks; max_walk: check_sensor's bound
+// the checks of the backward entries: check_entry with the sensor's extents and checks; max_walk: the bound of the walk to the sun
 template<typename F, typename A, typename B, typename C>
 bool check_backward(const Medium<F>& m, const Sun<F>& sun, const PhaseIn<F>& ph, const Background<F>& bg, const int max_events,
                     const Sensor<F>& sensor, std::pair<const char*, long long> work, Needed inputs, Needed outputs, int& max_walk,
                     A after_nbnd, B after_phase, C after_scene)
 {
-    return check_entry(m, sun, ph, bg, max_events, {{"npx", sensor.npx}, {"npy", sensor.npy}, work}, inputs, outputs,
-                       after_nbnd, after_phase, after_scene, [&] {
-                           if ((long long)sensor.npx*sensor.npy > 0x7FFFFFFFll) throw std::runtime_error("npx npy exceeds 2^31 - 1");
-                           max_walk = check_sensor(sensor, m, sun.mu0);
-                       });
+    return check_entry(m, RT_NEEDED_SOLAR(m), &sun, ph, bg, max_events, {{"npx", sensor.npx}, {"npy", sensor.npy}, work}, inputs, outputs,
+                       after_nbnd, after_phase, after_scene, [&] { check_sensor(sensor); max_walk = walk_bound(m, sun.mu0); });
 }
 
 // THE BUILDER of the kernel arguments
@@ -640,13 +607,10 @@ BwArgs<F> scene_args(const Medium<F>& m, const Sun<F>& sun, const Sensor<F>& sen
     BwArgs<F> a{};
     set_medium(a, m, igpt, k_null, max_events);
     set_sun_and_key(a, sun, seed);
-    a.mu0 = sun.mu0;
+    set_sensor(a, sensor);
+    a.sfc_albedo = m.sfc_albedo; a.mu0 = sun.mu0;
     a.ray0 = ray0; a.nrays = nrays; a.max_walk = max_walk;
     a.counts = counts; a.n_capped = n_capped; a.n_clamped = n_clamped;
-    const F* s = sensor.s;
-    a.type = sensor.type; a.npx = sensor.npx; a.npy = sensor.npy; a.fov = sensor.fov;
-    a.px = s[0]; a.py = s[1]; a.pz = s[2]; a.wx = s[3]; a.wy = s[4]; a.wz = s[5]; a.hx = s[6]; a.hy = s[7]; a.hz = s[8];
-    a.ex = s[9]; a.ey = s[10]; a.ez = s[11];
     return a;
 }
 
@@ -697,25 +661,6 @@ int trace_bw_entry(const char* entry, const Medium<F>& m, const Sun<F>& sun, con
     RRX_CATCH(entry)
 }
 
-// The small entries of the forward file that the spectral loop is made of, by precision. They are called as a caller outside would:
-// their own checks run again and a refusal comes back with its text.
-template<typename F> struct ForwardEntries;
-template<> struct ForwardEntries<double>
-{
-    static constexpr auto k_null = rrx_rt_k_null_f64; static constexpr auto k_null_aer = rrx_rt_k_null_aer_f64;
-    static constexpr auto bg_profile = rrx_rt_bg_profile_f64; static constexpr auto bg_profile_aer = rrx_rt_bg_profile_aer_f64;
-    static constexpr auto counts_to_flux = rrx_rt_counts_to_flux_f64;
-    static constexpr auto k_null_all = rrx_rt_k_null_all_f64; static constexpr auto bg_profile_all = rrx_rt_bg_profile_all_f64;
-};
-template<> struct ForwardEntries<float>
-{
-    static constexpr auto k_null = rrx_rt_k_null_f32; static constexpr auto k_null_aer = rrx_rt_k_null_aer_f32;
-    static constexpr auto bg_profile = rrx_rt_bg_profile_f32; static constexpr auto bg_profile_aer = rrx_rt_bg_profile_aer_f32;
-    static constexpr auto counts_to_flux = rrx_rt_counts_to_flux_f32;
-    static constexpr auto k_null_all = rrx_rt_k_null_all_f32; static constexpr auto bg_profile_all = rrx_rt_bg_profile_all_f32;
-};
-inline void forward(const int status) { if (status != 0) throw std::runtime_error(rrx_last_error()); }
-
 // rrx_raytracer_bw, _phase (bg.form = FORM_GRID), _bg, _aer
 template<typename F>
 int raytracer_bw_entry(const char* entry, const Medium<F>& m, const Sun<F>& sun, const PhaseIn<F>& ph, const Background<F>& bg, const Run& run,
@@ -740,10 +685,7 @@ int raytracer_bw_entry(const char* entry, const Medium<F>& m, const Sun<F>& sun,
     u64* counts = lease.get<u64>(npix + n_kn + n_prof);
     F* k_null = reinterpret_cast<F*>(counts + npix);
     F* profile = reinterpret_cast<F*>(counts + npix + n_kn);
-    bool ok = hipMemsetAsync(n_capped, 0, sizeof(u64), st) == hipSuccess;
-    ok = ok && hipMemsetAsync(n_clamped, 0, sizeof(u64), st) == hipSuccess;
-    ok = ok && hipMemsetAsync(radiance, 0, npix*sizeof(F), st) == hipSuccess;
-    if (!ok) throw std::runtime_error("zeroing the outputs failed");
+    zero_outputs(radiance, npix, n_capped, n_clamped, st);
     const long long nrays = rays_per_pixel*(long long)npix;
     const BgArgs<F,true,true> b{BgIn<F>{lb.nbg, profile, lb.lev}, m.aer};
     for (int g=0; g<m.ngpt; ++g)
@@ -791,12 +733,6 @@ void launch_channels(const size_t npix, const int nbnd, const int nchan, const u
     channels_kernel<F><<<unsigned(ceil_div((long long)(npix*size_t(nchan)), 256)), 256, 0, st>>>(npix, nbnd, nchan, counts, M, scale, out);
 }
 
-inline void check_channels(const int nbnd, const int nchan)
-{
-    if (nbnd < 1) throw std::runtime_error("nbnd must be >= 1: the counts are kept by band");
-    if (nchan < 1) throw std::runtime_error("nchan must be >= 1");
-}
-
 // rrx_camera_channels
 template<typename F>
 int camera_channels_entry(const char* entry, const long long npix, const int nbnd, const int nchan, const u64* counts, const F* chan_weights,
@@ -838,8 +774,7 @@ int camera_trace_entry(const char* entry, const Medium<F>& m, const Sun<F>& sun,
 
 // rrx_camera_render_spectral: m_gpt[g] rays per pixel of g-point g (a host array). One trace launch per chunk of consecutive g-points,
 // the counts of all chunks added in integers by band and converted once, with the common unit U = S/P over mu0, through the channel
-// matrix. THE WORKSPACE, in u64 words: | counts (nbnd, npix) | k_null of a chunk | the profile of all g-points | ray_end | weight0 |
-// the channel matrix |
+// matrix. The list, the workspace and the chunk loop are rrx_rt_host.h's; the workspace's mid section is the profile of all g-points.
 template<typename F>
 int camera_render_entry(const char* entry, const Medium<F>& m, const Sun<F>& sun, const PhaseIn<F>& ph, const Background<F>& bg, const Run& run,
                         const Sensor<F>& sensor, const F* inc_dir, const long long* m_gpt, const int nchan, const F* chan_weights,
@@ -858,74 +793,41 @@ int camera_render_entry(const char* entry, const Medium<F>& m, const Sun<F>& sun
                        {{"radiance", radiance}, {"n_capped", n_capped}, {"n_clamped", n_clamped}}, max_walk,
                        [&] { check_spectral_ngpt(m.ngpt); check_channels(m.nbnd, nchan); }, nothing,
                        [&] {
-                           if (npix_ll > 0x7FFFFFFFll) throw std::runtime_error("npx npy exceeds 2^31 - 1");
-                           ray_end.assign(size_t(m.ngpt) + 1, 0);
-                           for (int g=0; g<m.ngpt; ++g)
-                           {
+                           check_npix(sensor);
+                           ray_list(m.ngpt, npix_ll, m_gpt, ray_end, P, [&](const int g) {
                                if (inc_dir[g] < F(0.)) throw std::runtime_error("inc_dir must be >= 0");
-                               if (m_gpt[g] < 0) throw std::runtime_error("rays_per_pixel_gpt is negative at g-point " + std::to_string(g));
-                               if (m_gpt[g] > 0 && !(inc_dir[g] > F(0.)))
+                               if (!(m_gpt[g] > 0)) return;
+                               if (!(inc_dir[g] > F(0.)))
                                    throw std::runtime_error("rays_per_pixel_gpt is > 0 at g-point " + std::to_string(g) + ", which has no incident flux");
-                               if (m_gpt[g] > (0x7FFFFFFFFFFFFFFFll - ray_end[g]) / npix_ll) throw std::runtime_error("the ray list exceeds 2^63 - 1");
-                               ray_end[g+1] = ray_end[g] + m_gpt[g]*npix_ll;
-                               P += m_gpt[g];
-                               if (m_gpt[g] > 0) S = S + inc_dir[g];
-                           }
+                               S = S + inc_dir[g];
+                           });
                        }))
         return 0;
     const LoopBg<F> lb = loop_background(bg, m, nothing);
 
     hipStream_t st = static_cast<hipStream_t>(run.stream);
-    const size_t npix = size_t(npix_ll), nkn = size_t(m.knx)*m.kny*m.knz, n_counts = size_t(m.nbnd)*npix;
-    const int chunk = spectral_gpt_per_launch(nkn*sizeof(F), m.ngpt);
-    bool ok = hipMemsetAsync(n_capped, 0, sizeof(u64), st) == hipSuccess;
-    ok = ok && hipMemsetAsync(n_clamped, 0, sizeof(u64), st) == hipSuccess;
-    ok = ok && hipMemsetAsync(radiance, 0, size_t(nchan)*npix*sizeof(F), st) == hipSuccess;
-    if (!ok) throw std::runtime_error("zeroing the outputs failed");
+    const size_t npix = size_t(npix_ll);
+    zero_outputs(radiance, size_t(nchan)*npix, n_capped, n_clamped, st);
     if (P == 0) return 0;
     const F U = S / F(P);
     std::vector<F> weight0(m.ngpt, F(0.));
     for (int g=0; g<m.ngpt; ++g)
         if (m_gpt[g] > 0) weight0[g] = (inc_dir[g] / F(m_gpt[g])) / U;
 
-    const size_t n_kn = words_of(nkn*size_t(chunk)*sizeof(F));
     const size_t n_prof = lb.on ? words_of(size_t(m.ngpt)*BG_ROWS_AER*(lb.nbg + 1)*sizeof(F)) : 0;
-    const size_t n_re = size_t(m.ngpt) + 1, n_w = words_of(size_t(m.ngpt)*sizeof(F)), n_cw = words_of(size_t(nchan)*m.nbnd*sizeof(F));
-    WorkspaceLease lease(st);
-    u64* counts = lease.get<u64>(n_counts + n_kn + n_prof + n_re + n_w + n_cw);
-    F* k_null = reinterpret_cast<F*>(counts + n_counts);
-    F* profile = reinterpret_cast<F*>(counts + n_counts + n_kn);
-    long long* ray_end_d = reinterpret_cast<long long*>(counts + n_counts + n_kn + n_prof);
-    F* weight0_d = reinterpret_cast<F*>(counts + n_counts + n_kn + n_prof + n_re);
-    F* chan_d = reinterpret_cast<F*>(counts + n_counts + n_kn + n_prof + n_re + n_w);
-    ok = hipMemsetAsync(counts, 0, n_counts*sizeof(u64), st) == hipSuccess
-      && hipMemcpyAsync(ray_end_d, ray_end.data(), ray_end.size()*sizeof(long long), hipMemcpyHostToDevice, st) == hipSuccess
-      && hipMemcpyAsync(weight0_d, weight0.data(), size_t(m.ngpt)*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess
-      && hipMemcpyAsync(chan_d, chan_weights, size_t(nchan)*m.nbnd*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess
-      && hipStreamSynchronize(st) == hipSuccess;          // (the host arrays end with this call)
-    if (!ok) throw std::runtime_error("zeroing the counts or copying the ray list failed");
+    SpectralWork<F> w(m, st, npix, nchan, ray_end, weight0, chan_weights, n_prof, 0, nullptr, 0);
     if (lb.on)
-        forward(Fw::bg_profile_all(bg.nbg, m.ngpt, m.nbnd, bg.dz_bg, bg.tau, bg.ssa, m.band_lims_gpt, bg.cld_tau, bg.cld_ssa, bg.cld_g, profile,
+        forward(Fw::bg_profile_all(bg.nbg, m.ngpt, m.nbnd, bg.dz_bg, bg.tau, bg.ssa, m.band_lims_gpt, bg.cld_tau, bg.cld_ssa, bg.cld_g, w.mid,
                                    lb.aer.tau, lb.aer.ssa, lb.aer.g, run.stream));
-    const BgArgs<F,true,true> b{BgIn<F>{lb.nbg, profile, lb.lev}, m.aer};
-    for (int g0=0; g0<m.ngpt; g0+=chunk)
-    {
-        const int g1 = std::min(g0 + chunk, m.ngpt);
-        const long long n = ray_end[g1] - ray_end[g0];
-        if (n == 0) continue;
-        // k_null of the chunk's g-points: rrx_rt_k_null_all when the chunk is the whole list, otherwise slice by slice (the same bits)
-        if (chunk == m.ngpt)
-            forward(Fw::k_null_all(m.nx, m.ny, m.nz, m.ngpt, m.nbnd, m.top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, m.dz, m.knx, m.kny, m.knz,
-                                   k_null, m.aer.tau, run.stream));
-        else
-            for (int g=g0; g<g1; ++g)
-                if (ray_end[g+1] > ray_end[g])
-                    forward(Fw::k_null_aer(m.nx, m.ny, m.nz, m.ngpt, m.nbnd, g, m.top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, m.dz, m.knx, m.kny,
-                                           m.knz, k_null + nkn*size_t(g - g0), m.aer.tau, run.stream));
-        launch_trace_bw<F>(scene_args<F>(m, sun, sensor, 0, k_null, run.seed, u64(ray_end[g0]), n, run.max_events, max_walk, counts, n_capped, n_clamped),
-                           ph, st, FORM_SPECTRAL, b, SpecIn<F>{m.ngpt, g0, ray_end_d, weight0_d, nullptr});
-    }
-    launch_channels<F>(npix, m.nbnd, nchan, counts, chan_d, U / sun.mu0, radiance, st);
+    const BgArgs<F,true,true> b{BgIn<F>{lb.nbg, w.mid, lb.lev}, m.aer};
+    w.trace(m, run.stream,
+            [&](const int g, F* k_null) {
+                forward(Fw::k_null_aer(m.nx, m.ny, m.nz, m.ngpt, m.nbnd, g, m.top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, m.dz, m.knx, m.kny, m.knz,
+                                       k_null, m.aer.tau, run.stream)); },
+            [&](const SpecIn<F>& sp, const u64 ray0, const long long n) {
+                launch_trace_bw<F>(scene_args<F>(m, sun, sensor, 0, w.k_null, run.seed, ray0, n, run.max_events, max_walk, w.counts, n_capped, n_clamped),
+                                   ph, st, FORM_SPECTRAL, b, sp); });
+    launch_channels<F>(npix, m.nbnd, nchan, w.counts, w.chan, U / sun.mu0, radiance, st);
     RRX_CATCH(entry)
 }
 }  // namespace

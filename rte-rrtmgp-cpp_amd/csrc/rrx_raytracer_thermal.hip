@@ -2,7 +2,8 @@
 // sensor. The longwave twin of rrx_raytracer_bw.hip: the same sensors, the same start, the same
 // tracking through the grid, operation for operation, and NO SUN: the source that scores a ray is the Planck emission of the medium,
 // of the surface and of whatever lies above the domain top. There is no walk, so this is a kernel of its own and not a flag of
-// trace_bw_kernel; it states its tracking itself, as the two other trace kernels do.
+// trace_bw_kernel; the kernel states its start and its tracking itself, as the two other trace kernels do (DESIGN 4.23 has what was
+// tried of sharing them). Its host side is rrx_rt_host.h's: the sensor, the checks, the ray list and the spectral loop.
 //
 // THE ESTIMATOR. Rays start at the sensor and travel AGAINST the light through the medium of one g-point: k_ext = (tau + tau_c)/dz,
 // k_sca = (tau ssa + tau_c ssa_c)/dz, k_sca_cld = (tau_c ssa_c)/dz from the clear tau, ssa (ncol, nz, ngpt) and the band cloud triple;
@@ -297,36 +298,10 @@ __global__ void __launch_bounds__(RT_BLOCK) trace_thermal_kernel(const ThermalAr
     }
 }
 
-// ---- host side (rrx_rt_host.h): the scene structs and the one check sequence of the two other tracers. The slots of that
-// sequence that this tracer has no use for are filled so that they pass: Medium::sfc_albedo carries sfc_emis (refused under its own
-// name first), a NULL ssa stands behind tau in the NULL check, and the sun stands at the zenith.
+// ---- host side (rrx_rt_host.h): the scene structs, the sensor with its checks and the one check sequence of the two other
+// tracers, which is told what this tracer needs of the medium (tau and the sources below; ssa may be NULL) and that it has no sun.
 
-// the virtual camera: s is (12,): position, w, h, e_d
-template<typename F> struct ThermalSensor { int type, npx, npy; F fov; const F* s; };
-
-// what the backward entries refuse of a sensor (there is no sun, so no bound of a walk)
-template<typename F>
-void check_thermal_sensor(const ThermalSensor<F>& sensor)
-{
-    const int type = sensor.type;
-    const F fov = sensor.fov;
-    const F* s = sensor.s;
-    if ((long long)sensor.npx*sensor.npy > 0x7FFFFFFFll) throw std::runtime_error("npx npy exceeds 2^31 - 1");
-    if (type < 0 || type > 3) throw std::runtime_error("sensor_type must be 0 (perspective), 1 (fisheye), 2 (orthographic) or 3 (flux sensor)");
-    for (int i=0; i<12; ++i)
-        if (!std::isfinite(double(s[i]))) throw std::runtime_error("sensor holds a number that is not finite");
-    const double ex = s[9], ey = s[10], ez = s[11];
-    const double len = std::sqrt(ex*ex + ey*ey + ez*ez);
-    if (type == 0 || type == 1)
-    {
-        if (!(len > 0.)) throw std::runtime_error("sensor e_d is zero");
-        if (s[2] < F(0.)) throw std::runtime_error("sensor position lies below the surface");
-    }
-    if (type == 1 && (!(fov > F(0.)) || double(fov) > 6.283185307179586 + 1e-6)) throw std::runtime_error("fov must be in (0, 2 pi] for a fisheye sensor");
-    if (type == 2 && (std::fabs(len - 1.) > 1.e-5 || !(ez < 0.))) throw std::runtime_error("sensor e_d must be a unit vector with e_d.z < 0 for an orthographic sensor");
-    if (type == 3 && ez == 0.) throw std::runtime_error("sensor e_d.z must be > 0 (at the surface, facing up) or < 0 (at the top, facing down) for a flux sensor");
-}
-
+// the surface and the sources
 template<typename F> struct ThermalSources { const F* sfc_emis; const F* lay_src; const F* sfc_src; };
 
 inline void check_top_radiance(const double v)
@@ -334,39 +309,30 @@ inline void check_top_radiance(const double v)
     if (!std::isfinite(v) || v < 0.) throw std::runtime_error("top_radiance must be finite and >= 0");
 }
 
-// the checks of both thermal entries: check_entry with the sensor's extents and checks. m.ssa may be NULL.
+// the checks of the thermal entries: check_entry with the sensor's extents and checks
 template<typename F, typename A, typename B, typename C>
-bool check_thermal(const Medium<F>& m, const ThermalSources<F>& src, const int max_events, const ThermalSensor<F>& sensor,
+bool check_thermal(const Medium<F>& m, const ThermalSources<F>& src, const int max_events, const Sensor<F>& sensor,
                    std::pair<const char*, long long> work, Needed inputs, Needed outputs, A after_nbnd, B after_phase, C after_scene)
 {
-    Medium<F> mc = m;
-    if (mc.ssa == nullptr) mc.ssa = mc.tau;
-    mc.sfc_albedo = src.sfc_emis;
-    return check_entry(mc, Sun<F>{F(1.), F(0.)}, PhaseIn<F>{}, RT_NO_BG(F), max_events, {{"npx", sensor.npx}, {"npy", sensor.npy}, work},
-                       inputs, outputs,
-                       [&] { after_nbnd();
-                             check_needed({{"tau", m.tau}, {"sfc_emis", src.sfc_emis}, {"lay_src", src.lay_src}, {"sfc_src", src.sfc_src}}); },
-                       after_phase, after_scene, [&] { check_thermal_sensor(sensor); });
+    const Sun<F>* no_sun = nullptr;
+    return check_entry(m, {{"tau", m.tau}, {"sfc_emis", src.sfc_emis}, {"lay_src", src.lay_src}, {"sfc_src", src.sfc_src}}, no_sun, PhaseIn<F>{},
+                       RT_NO_BG(F), max_events, {{"npx", sensor.npx}, {"npy", sensor.npy}, work}, inputs, outputs,
+                       after_nbnd, after_phase, after_scene, [&] { check_sensor(sensor); });
 }
 
 // THE BUILDER of the kernel arguments
 template<typename F>
-ThermalArgs<F> thermal_args(const Medium<F>& m, const ThermalSources<F>& src, const F top_radiance, const ThermalSensor<F>& sensor, const int igpt,
+ThermalArgs<F> thermal_args(const Medium<F>& m, const ThermalSources<F>& src, const F top_radiance, const Sensor<F>& sensor, const int igpt,
                             const F* k_null, const u64 seed, const u64 ray0, const long long nrays, const int max_events,
                             u64* counts, u64* n_capped, u64* n_clamped)
 {
     ThermalArgs<F> a{};
-    a.nx = m.nx; a.ny = m.ny; a.nz = m.nz; a.nbnd = m.nbnd; a.igpt = igpt; a.top_at_1 = m.top_at_1 ? 1 : 0;
-    a.tau = m.tau; a.ssa = m.ssa; a.band_lims_gpt = m.band_lims_gpt; a.cld_tau = m.cld_tau; a.cld_ssa = m.cld_ssa; a.cld_g = m.cld_g;
-    a.dx = m.dx; a.dy = m.dy; a.dz = m.dz; a.knx = m.knx; a.kny = m.kny; a.knz = m.knz; a.k_null = k_null; a.max_events = max_events;
+    set_medium(a, m, igpt, k_null, max_events);
+    set_key(a, seed);
+    set_sensor(a, sensor);
     a.sfc_emis = src.sfc_emis; a.lay_src = src.lay_src; a.sfc_src = src.sfc_src; a.top_radiance = top_radiance;
-    a.k0 = unsigned(seed & 0xFFFFFFFFull); a.k1 = unsigned(seed >> 32);
     a.ray0 = ray0; a.nrays = nrays;
     a.counts = counts; a.n_capped = n_capped; a.n_clamped = n_clamped;
-    const F* s = sensor.s;
-    a.type = sensor.type; a.npx = sensor.npx; a.npy = sensor.npy; a.fov = sensor.fov;
-    a.px = s[0]; a.py = s[1]; a.pz = s[2]; a.wx = s[3]; a.wy = s[4]; a.wz = s[5]; a.hx = s[6]; a.hy = s[7]; a.hz = s[8];
-    a.ex = s[9]; a.ey = s[10]; a.ez = s[11];
     return a;
 }
 
@@ -389,7 +355,7 @@ void launch_trace_thermal_spectral(const ThermalArgs<F>& a, const SpecIn<F>& sp,
 // rrx_thermal_trace_counts
 template<typename F>
 int thermal_trace_entry(const char* entry, const Medium<F>& m, const ThermalSources<F>& src, const F top_radiance, const Run& run,
-                        const ThermalSensor<F>& sensor, const int igpt, const F* k_null, const long long ray0, const long long nrays,
+                        const Sensor<F>& sensor, const int igpt, const F* k_null, const long long ray0, const long long nrays,
                         u64* counts, u64* n_capped, u64* n_clamped)
 {
     RRX_TRY
@@ -403,29 +369,16 @@ int thermal_trace_entry(const char* entry, const Medium<F>& m, const ThermalSour
     RRX_CATCH(entry)
 }
 
-// the small entries of the forward file and this file's own trace entry that the loop is made of, by precision. They are called as a
-// caller outside would: their own checks run again and a refusal comes back with its text.
-template<typename F> struct LoopEntries;
-template<> struct LoopEntries<double>
-{
-    static constexpr auto k_null = rrx_rt_k_null_f64; static constexpr auto counts_to_flux = rrx_rt_counts_to_flux_f64;
-    static constexpr auto trace = rrx_thermal_trace_counts_f64;
-};
-template<> struct LoopEntries<float>
-{
-    static constexpr auto k_null = rrx_rt_k_null_f32; static constexpr auto counts_to_flux = rrx_rt_counts_to_flux_f32;
-    static constexpr auto trace = rrx_thermal_trace_counts_f32;
-};
-inline void forward(const int status) { if (status != 0) throw std::runtime_error(rrx_last_error()); }
-
 // rrx_thermal_render: the loop over all g-points. by_band: the band of a g-point is looked up in a host copy of band_lims_gpt, for which
 // the call waits for its stream once, before its first launch.
 template<typename F>
 int thermal_render_entry(const char* entry, const Medium<F>& m, const ThermalSources<F>& src, const F* top_radiance, const Run& run,
-                         const ThermalSensor<F>& sensor, const long long rays_per_pixel, const bool by_band, F* radiance, u64* n_capped, u64* n_clamped)
+                         const Sensor<F>& sensor, const long long rays_per_pixel, const bool by_band, F* radiance, u64* n_capped, u64* n_clamped)
 {
     RRX_TRY
-    typedef LoopEntries<F> E;
+    typedef ForwardEntries<F> Fw;
+    // (the loop calls this file's own trace entry as a caller outside would, like the entries of the forward file)
+    constexpr auto trace = [] { if constexpr (sizeof(F) == 8) return rrx_thermal_trace_counts_f64; else return rrx_thermal_trace_counts_f32; }();
     if (check_thermal(m, src, run.max_events, sensor, {"rays_per_pixel", rays_per_pixel}, {{"sensor", sensor.s}},
                       {{"radiance", radiance}, {"n_capped", n_capped}, {"n_clamped", n_clamped}},
                       [&] { if (by_band && m.band_lims_gpt == nullptr) throw std::runtime_error("band_lims_gpt is NULL");
@@ -442,10 +395,7 @@ int thermal_render_entry(const char* entry, const Medium<F>& m, const ThermalSou
     WorkspaceLease lease(st);
     u64* counts = lease.get<u64>(npix + n_kn);
     F* k_null = reinterpret_cast<F*>(counts + npix);
-    bool ok = hipMemsetAsync(n_capped, 0, sizeof(u64), st) == hipSuccess;
-    ok = ok && hipMemsetAsync(n_clamped, 0, sizeof(u64), st) == hipSuccess;
-    ok = ok && hipMemsetAsync(radiance, 0, n_out*sizeof(F), st) == hipSuccess;
-    if (!ok) throw std::runtime_error("zeroing the outputs failed");
+    zero_outputs(radiance, n_out, n_capped, n_clamped, st);
     std::vector<int> lims;
     if (by_band)
     {
@@ -467,24 +417,18 @@ int thermal_render_entry(const char* entry, const Medium<F>& m, const ThermalSou
             out = radiance + npix*size_t(band);
         }
         if (hipMemsetAsync(counts, 0, npix*sizeof(u64), st) != hipSuccess) throw std::runtime_error("zeroing the counts failed");
-        forward(E::k_null(m.nx, m.ny, m.nz, m.ngpt, m.nbnd, g, m.top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, m.dz, m.knx, m.kny, m.knz,
-                          k_null, run.stream));
-        forward(E::trace(m.nx, m.ny, m.nz, m.ngpt, m.nbnd, g, m.top_at_1, m.tau, m.ssa, m.band_lims_gpt, m.cld_tau, m.cld_ssa, m.cld_g,
-                         m.dx, m.dy, m.dz, src.sfc_emis, src.lay_src, src.sfc_src, top_radiance != nullptr ? top_radiance[g] : F(0.),
-                         m.knx, m.kny, m.knz, k_null, sensor.type, sensor.npx, sensor.npy, sensor.fov, sensor.s, run.seed, 0ll, nrays,
-                         run.max_events, counts, n_capped, n_clamped, run.stream));
-        forward(E::counts_to_flux((long long)npix, counts, F(1.)/F(rays_per_pixel), out, run.stream));
+        forward(Fw::k_null(m.nx, m.ny, m.nz, m.ngpt, m.nbnd, g, m.top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, m.dz, m.knx, m.kny, m.knz,
+                           k_null, run.stream));
+        forward(trace(m.nx, m.ny, m.nz, m.ngpt, m.nbnd, g, m.top_at_1, m.tau, m.ssa, m.band_lims_gpt, m.cld_tau, m.cld_ssa, m.cld_g,
+                      m.dx, m.dy, m.dz, src.sfc_emis, src.lay_src, src.sfc_src, top_radiance != nullptr ? top_radiance[g] : F(0.),
+                      m.knx, m.kny, m.knz, k_null, sensor.type, sensor.npx, sensor.npy, sensor.fov, sensor.s, run.seed, 0ll, nrays,
+                      run.max_events, counts, n_capped, n_clamped, run.stream));
+        forward(Fw::counts_to_flux((long long)npix, counts, F(1.)/F(rays_per_pixel), out, run.stream));
     }
     RRX_CATCH(entry)
 }
 
 // ---- the spectral form: rays of all g-points in one launch, counts by band, bands to channels
-
-inline void check_thermal_channels(const int nbnd, const int nchan)
-{
-    if (nbnd < 1) throw std::runtime_error("nbnd must be >= 1: the counts are kept by band");
-    if (nchan < 1) throw std::runtime_error("nchan must be >= 1");
-}
 
 // rrx_thermal_trace_counts_spectral: top_radiance, sp.photon_end (the ray list's prefix sums) and sp.weight0 are device arrays that the
 // entry cannot look into. The kernel stays inside its arrays whatever they hold (the search is bounded by ngpt, a ray beyond the list is
@@ -492,7 +436,7 @@ inline void check_thermal_channels(const int nbnd, const int nchan)
 // that of all g-points.
 template<typename F>
 int thermal_trace_spectral_entry(const char* entry, const Medium<F>& m, const ThermalSources<F>& src, const F* top_radiance, const Run& run,
-                                 const ThermalSensor<F>& sensor, const SpecIn<F>& sp, const F* k_null, const long long ray0, const long long nrays,
+                                 const Sensor<F>& sensor, const SpecIn<F>& sp, const F* k_null, const long long ray0, const long long nrays,
                                  u64* counts, u64* n_capped, u64* n_clamped)
 {
     RRX_TRY
@@ -508,99 +452,47 @@ int thermal_trace_spectral_entry(const char* entry, const Medium<F>& m, const Th
     RRX_CATCH(entry)
 }
 
-// the small entries that the spectral loop is made of beside LoopEntries, by precision
-template<typename F> struct SpectralEntries;
-template<> struct SpectralEntries<double>
-{
-    static constexpr auto k_null_all = rrx_rt_k_null_all_f64; static constexpr auto channels = rrx_camera_channels_f64;
-};
-template<> struct SpectralEntries<float>
-{
-    static constexpr auto k_null_all = rrx_rt_k_null_all_f32; static constexpr auto channels = rrx_camera_channels_f32;
-};
-
 // rrx_thermal_render_spectral: m_gpt[g] rays per pixel of g-point g (a host array). One trace launch per chunk of consecutive g-points,
 // the counts of all chunks added in integers by band and converted once, with the common unit U = n_act / P, through the channel
-// matrix. THE WORKSPACE, in u64 words: | counts (nbnd, npix) | k_null of a chunk | ray_end | weight0 | top_radiance | the channel matrix |
+// matrix. The list, the workspace and the chunk loop are rrx_rt_host.h's; the workspace's late section is top_radiance.
 template<typename F>
 int thermal_render_spectral_entry(const char* entry, const Medium<F>& m, const ThermalSources<F>& src, const F* top_radiance, const Run& run,
-                                  const ThermalSensor<F>& sensor, const long long* m_gpt, const int nchan, const F* chan_weights,
+                                  const Sensor<F>& sensor, const long long* m_gpt, const int nchan, const F* chan_weights,
                                   F* radiance, u64* n_capped, u64* n_clamped)
 {
     RRX_TRY
-    typedef LoopEntries<F> E;
-    typedef SpectralEntries<F> S;
+    typedef ForwardEntries<F> Fw;
     const long long npix_ll = (long long)sensor.npx*sensor.npy;
     std::vector<long long> ray_end;
     long long P = 0, n_act = 0;
     if (check_thermal(m, src, run.max_events, sensor, {"ngpt", m.ngpt},
                       {{"band_lims_gpt", m.band_lims_gpt}, {"rays_per_pixel_gpt", m_gpt}, {"chan_weights", chan_weights}, {"sensor", sensor.s}},
                       {{"radiance", radiance}, {"n_capped", n_capped}, {"n_clamped", n_clamped}},
-                      [&] { check_spectral_ngpt(m.ngpt); check_thermal_channels(m.nbnd, nchan); }, nothing,
+                      [&] { check_spectral_ngpt(m.ngpt); check_channels(m.nbnd, nchan); }, nothing,
                       [&] {
-                          if (npix_ll > 0x7FFFFFFFll) throw std::runtime_error("npx npy exceeds 2^31 - 1");
+                          check_npix(sensor);
                           if (top_radiance != nullptr) for (int g=0; g<m.ngpt; ++g) check_top_radiance(double(top_radiance[g]));
-                          ray_end.assign(size_t(m.ngpt) + 1, 0);
-                          for (int g=0; g<m.ngpt; ++g)
-                          {
-                              if (m_gpt[g] < 0) throw std::runtime_error("rays_per_pixel_gpt is negative at g-point " + std::to_string(g));
-                              if (m_gpt[g] > (0x7FFFFFFFFFFFFFFFll - ray_end[g]) / npix_ll) throw std::runtime_error("the ray list exceeds 2^63 - 1");
-                              ray_end[g+1] = ray_end[g] + m_gpt[g]*npix_ll;
-                              P += m_gpt[g];
-                              if (m_gpt[g] > 0) ++n_act;
-                          }
+                          ray_list(m.ngpt, npix_ll, m_gpt, ray_end, P, [&](const int g) { if (m_gpt[g] > 0) ++n_act; });
                       }))
         return 0;
 
     hipStream_t st = static_cast<hipStream_t>(run.stream);
-    const size_t npix = size_t(npix_ll), nkn = size_t(m.knx)*m.kny*m.knz, n_counts = size_t(m.nbnd)*npix;
-    const int chunk = spectral_gpt_per_launch(nkn*sizeof(F), m.ngpt);
-    bool ok = hipMemsetAsync(n_capped, 0, sizeof(u64), st) == hipSuccess;
-    ok = ok && hipMemsetAsync(n_clamped, 0, sizeof(u64), st) == hipSuccess;
-    ok = ok && hipMemsetAsync(radiance, 0, size_t(nchan)*npix*sizeof(F), st) == hipSuccess;
-    if (!ok) throw std::runtime_error("zeroing the outputs failed");
+    zero_outputs(radiance, size_t(nchan)*size_t(npix_ll), n_capped, n_clamped, st);
     if (P == 0) return 0;
     const F U = F(n_act) / F(P);
     std::vector<F> weight0(m.ngpt, F(0.));
     for (int g=0; g<m.ngpt; ++g)
         if (m_gpt[g] > 0) weight0[g] = (F(1.) / F(m_gpt[g])) / U;
 
-    const size_t n_kn = words_of(nkn*size_t(chunk)*sizeof(F));
-    const size_t n_re = size_t(m.ngpt) + 1, n_w = words_of(size_t(m.ngpt)*sizeof(F)), n_cw = words_of(size_t(nchan)*m.nbnd*sizeof(F));
-    WorkspaceLease lease(st);
-    u64* counts = lease.get<u64>(n_counts + n_kn + n_re + 2*n_w + n_cw);
-    F* k_null = reinterpret_cast<F*>(counts + n_counts);
-    long long* ray_end_d = reinterpret_cast<long long*>(counts + n_counts + n_kn);
-    F* weight0_d = reinterpret_cast<F*>(counts + n_counts + n_kn + n_re);
-    F* top_d = reinterpret_cast<F*>(counts + n_counts + n_kn + n_re + n_w);
-    F* chan_d = reinterpret_cast<F*>(counts + n_counts + n_kn + n_re + 2*n_w);
-    ok = hipMemsetAsync(counts, 0, n_counts*sizeof(u64), st) == hipSuccess
-      && hipMemcpyAsync(ray_end_d, ray_end.data(), ray_end.size()*sizeof(long long), hipMemcpyHostToDevice, st) == hipSuccess
-      && hipMemcpyAsync(weight0_d, weight0.data(), size_t(m.ngpt)*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess
-      && (top_radiance == nullptr
-          || hipMemcpyAsync(top_d, top_radiance, size_t(m.ngpt)*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess)
-      && hipMemcpyAsync(chan_d, chan_weights, size_t(nchan)*m.nbnd*sizeof(F), hipMemcpyHostToDevice, st) == hipSuccess
-      && hipStreamSynchronize(st) == hipSuccess;          // (the host arrays end with this call)
-    if (!ok) throw std::runtime_error("zeroing the counts or copying the ray list failed");
-    for (int g0=0; g0<m.ngpt; g0+=chunk)
-    {
-        const int g1 = std::min(g0 + chunk, m.ngpt);
-        const long long n = ray_end[g1] - ray_end[g0];
-        if (n == 0) continue;
-        // k_null of the chunk's g-points: rrx_rt_k_null_all when the chunk is the whole list, otherwise slice by slice (the same bits)
-        if (chunk == m.ngpt)
-            forward(S::k_null_all(m.nx, m.ny, m.nz, m.ngpt, m.nbnd, m.top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, m.dz, m.knx, m.kny, m.knz,
-                                  k_null, nullptr, run.stream));
-        else
-            for (int g=g0; g<g1; ++g)
-                if (ray_end[g+1] > ray_end[g])
-                    forward(E::k_null(m.nx, m.ny, m.nz, m.ngpt, m.nbnd, g, m.top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, m.dz, m.knx, m.kny, m.knz,
-                                      k_null + nkn*size_t(g - g0), run.stream));
-        launch_trace_thermal_spectral<F>(thermal_args<F>(m, src, F(0.), sensor, 0, k_null, run.seed, u64(ray_end[g0]), n, run.max_events,
-                                                         counts, n_capped, n_clamped),
-                                         SpecIn<F>{m.ngpt, g0, ray_end_d, weight0_d, nullptr}, top_radiance != nullptr ? top_d : nullptr, st);
-    }
-    forward(S::channels(npix_ll, m.nbnd, nchan, counts, chan_d, U, radiance, run.stream));
+    SpectralWork<F> w(m, st, size_t(npix_ll), nchan, ray_end, weight0, chan_weights, 0, words_of(size_t(m.ngpt)*sizeof(F)), top_radiance, m.ngpt);
+    w.trace(m, run.stream,
+            [&](const int g, F* k_null) {
+                forward(Fw::k_null(m.nx, m.ny, m.nz, m.ngpt, m.nbnd, g, m.top_at_1, m.tau, m.band_lims_gpt, m.cld_tau, m.dz, m.knx, m.kny, m.knz,
+                                   k_null, run.stream)); },
+            [&](const SpecIn<F>& sp, const u64 ray0, const long long n) {
+                launch_trace_thermal_spectral<F>(thermal_args<F>(m, src, F(0.), sensor, 0, w.k_null, run.seed, ray0, n, run.max_events,
+                                                                 w.counts, n_capped, n_clamped), sp, top_radiance != nullptr ? w.late : nullptr, st); });
+    forward(Fw::channels(npix_ll, m.nbnd, nchan, w.counts, w.chan, U, radiance, run.stream));
     RRX_CATCH(entry)
 }
 }  // namespace
@@ -610,10 +502,10 @@ int thermal_render_spectral_entry(const char* entry, const Medium<F>& m, const T
         const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
         F dx, F dy, F dz, const F* sfc_emis, const F* lay_src, const F* sfc_src
 #define TH_MEDIUM(F) \
-        rrx::rt::Medium<F>{nx, ny, nz, ngpt, nbnd, top_at_1, 0, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, dx, dy, dz, sfc_emis, \
+        rrx::rt::Medium<F>{nx, ny, nz, ngpt, nbnd, top_at_1, 0, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, dx, dy, dz, nullptr, \
                            knx, kny, knz, rrx::rt::AerIn<F>{}}
 #define TH_SOURCES(F) ThermalSources<F>{sfc_emis, lay_src, sfc_src}
-#define TH_SENSOR(F) ThermalSensor<F>{sensor_type, npx, npy, fov, sensor}
+#define TH_SENSOR(F) Sensor<F>{sensor_type, npx, npy, fov, sensor}
 
 extern "C"
 {

@@ -334,11 +334,12 @@ inline void check_needed(std::initializer_list<std::pair<const char*, const void
         if (p.second == nullptr) throw std::runtime_error(std::string(p.first) + " is NULL");
 }
 
+// mu0: NULL for a tracer without a sun
 template<typename F>
-void check_scene(const F dx, const F dy, const F dz, const F mu0)
+void check_scene(const F dx, const F dy, const F dz, const F* mu0)
 {
     if (!(dx > F(0.)) || !(dy > F(0.)) || !(dz > F(0.))) throw std::runtime_error("dx, dy, dz must be > 0");
-    if (!(mu0 > F(0.)) || mu0 > F(1.)) throw std::runtime_error("mu0 must be in (0, 1]");
+    if (mu0 != nullptr && (!(*mu0 > F(0.)) || *mu0 > F(1.))) throw std::runtime_error("mu0 must be in (0, 1]");
 }
 
 // ---- the background's arguments

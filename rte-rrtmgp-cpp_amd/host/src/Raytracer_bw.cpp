@@ -51,14 +51,13 @@ unsigned long long Raytracer_bw_gpu::trace_rays_bw(
     check_shapes("Raytracer_bw_gpu::trace_rays_bw: ", m, nx, ny, nz, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, sfc_albedo, inc_dir, sensor,
                  radiance);
     const Rt_pointers p(m, cld_tau, cld_ssa, cld_g);
-    const Float numbers[12] = {sensor.position[0], sensor.position[1], sensor.position[2], sensor.e_w[0], sensor.e_w[1], sensor.e_w[2],
-                               sensor.e_h[0], sensor.e_h[1], sensor.e_h[2], sensor.e_d[0], sensor.e_d[1], sensor.e_d[2]};
+    const Rt_sensor_numbers numbers(sensor);
     Array_gpu<unsigned long long,1> tallies({2});
 // the arguments that the four backward loops begin with
 #define RT_BW_LOOP_HEAD \
         nx, ny, nz, tau.dim(3), band_lims_gpt.dim(2), RrxBool(top_at_1), tau.ptr(), ssa.ptr(), band_lims_gpt.ptr(), RT_CLOUD(p), \
         dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), knx, kny, knz, \
-        sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers, rays_per_pixel, seed, max_events, \
+        sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers.s, rays_per_pixel, seed, max_events, \
         radiance.ptr(), tallies.ptr(), tallies.ptr() + 1
     if (has_aer)
         RRX_CALL(rrx_raytracer_bw_aer, RT_BW_LOOP_HEAD, RT_TABLE(p), RT_BACKGROUND(p), p.aer[0], p.aer[1], p.aer[2], p.bg_aer[0], p.bg_aer[1], p.bg_aer[2]);
@@ -98,12 +97,11 @@ unsigned long long Raytracer_bw_gpu::trace_rays_bw_spectral(
     Array_gpu<Float,2> image(radiance.ptr(), {radiance.dim(1), radiance.dim(2)});
     check_shapes(who, m, nx, ny, nz, tau, ssa, band_lims_gpt, cld_tau, cld_ssa, cld_g, sfc_albedo, inc_dir, sensor, image);
     const Rt_pointers p(m, cld_tau, cld_ssa, cld_g);
-    const Float numbers[12] = {sensor.position[0], sensor.position[1], sensor.position[2], sensor.e_w[0], sensor.e_w[1], sensor.e_w[2],
-                               sensor.e_h[0], sensor.e_h[1], sensor.e_h[2], sensor.e_d[0], sensor.e_d[1], sensor.e_d[2]};
+    const Rt_sensor_numbers numbers(sensor);
     Array_gpu<unsigned long long,1> tallies({2});
     RRX_CALL(rrx_camera_render_spectral, nx, ny, nz, tau.dim(3), band_lims_gpt.dim(2), RrxBool(top_at_1), tau.ptr(), ssa.ptr(),
              band_lims_gpt.ptr(), RT_CLOUD(p), dx, dy, dz, sfc_albedo.ptr(), mu0, azimuth, inc_dir.ptr(), knx, kny, knz,
-             sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers, rays_per_pixel_gpt.ptr(), seed, max_events,
+             sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers.s, rays_per_pixel_gpt.ptr(), seed, max_events,
              nchan, chan_weights.ptr(), radiance.ptr(), tallies.ptr(), tallies.ptr() + 1,
              RT_TABLE(p), RT_BACKGROUND(p), p.aer[0], p.aer[1], p.aer[2], p.bg_aer[0], p.bg_aer[1], p.bg_aer[2]);
     if (n_clamped_out != nullptr) *n_clamped_out = tallies({2});

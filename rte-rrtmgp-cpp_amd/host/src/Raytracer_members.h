@@ -1,5 +1,6 @@
 // What Raytracer_gpu and Raytracer_bw_gpu share behind their headers: a view of the optional members that both classes keep (the
-// phase table, the background, the aerosol triples) and THE ONE PLACE that turns them into the pointer groups of the C entries.
+// phase table, the background, the aerosol triples) and THE ONE PLACE that turns them into the pointer groups of the C entries; and,
+// for Raytracer_bw_gpu and Raytracer_thermal_gpu, the one place that lays a sensor out as the C entries take it.
 // Everything here has internal linkage: the libraries export what they exported.
 #ifndef RAYTRACER_MEMBERS_H
 #define RAYTRACER_MEMBERS_H
@@ -72,6 +73,18 @@ struct Rt_pointers
         bg[3] = bg_cloudy ? m.bg_cld_tau.ptr() : none; bg[4] = bg_cloudy ? m.bg_cld_ssa.ptr() : none; bg[5] = bg_cloudy ? m.bg_cld_g.ptr() : none;
         aer[0] = hazy ? m.aer_tau.ptr() : none; aer[1] = hazy ? m.aer_ssa.ptr() : none; aer[2] = hazy ? m.aer_g.ptr() : none;
         bg_aer[0] = bg_hazy ? m.bg_aer_tau.ptr() : none; bg_aer[1] = bg_hazy ? m.bg_aer_ssa.ptr() : none; bg_aer[2] = bg_hazy ? m.bg_aer_g.ptr() : none;
+    }
+};
+
+// a sensor (Sensor_bw) laid out as the 12 numbers of the C entries: position, e_w, e_h, e_d
+struct Rt_sensor_numbers
+{
+    Float s[12];
+
+    template<typename Sensor>
+    explicit Rt_sensor_numbers(const Sensor& sensor)
+    {
+        for (int i=0; i<3; ++i) { s[i] = sensor.position[i]; s[3+i] = sensor.e_w[i]; s[6+i] = sensor.e_h[i]; s[9+i] = sensor.e_d[i]; }
     }
 };
 

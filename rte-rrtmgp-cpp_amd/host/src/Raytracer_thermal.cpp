@@ -1,6 +1,7 @@
 // Raytracer_thermal_gpu: checks the shapes and forwards to rrx_thermal_render or rrx_thermal_render_spectral; a non-zero status becomes
 // std::runtime_error.
 #include "Raytracer_thermal.h"
+#include "Raytracer_members.h"
 
 namespace
 {
@@ -50,13 +51,12 @@ unsigned long long Raytracer_thermal_gpu::trace_rays_thermal(
     if (sensor.npx < 0 || sensor.npy < 0 || radiance.dim(1) != sensor.npx || radiance.dim(2) != sensor.npy ||
         (radiance.dim(3) != 1 && radiance.dim(3) != nbnd))
         throw std::runtime_error(who + "radiance is not (npx, npy, 1) or (npx, npy, nbnd)");
-    const Float numbers[12] = {sensor.position[0], sensor.position[1], sensor.position[2], sensor.e_w[0], sensor.e_w[1], sensor.e_w[2],
-                               sensor.e_h[0], sensor.e_h[1], sensor.e_h[2], sensor.e_d[0], sensor.e_d[1], sensor.e_d[2]};
+    const Rt_sensor_numbers numbers(sensor);
     Array_gpu<unsigned long long,1> tallies({2});
     RRX_CALL(rrx_thermal_render, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), tau.ptr(), ssa.size() > 0 ? ssa.ptr() : nullptr,
              band_lims_gpt.ptr(), cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
              dx, dy, dz, sfc_emis.ptr(), lay_src.ptr(), sfc_src.ptr(), top_radiance.size() > 0 ? top_radiance.ptr() : nullptr, knx, kny, knz,
-             sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers, rays_per_pixel, seed, max_events,
+             sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers.s, rays_per_pixel, seed, max_events,
              RrxBool(by_band), radiance.ptr(), tallies.ptr(), tallies.ptr() + 1);
     if (n_clamped_out != nullptr) *n_clamped_out = tallies({2});
     return tallies({1});
@@ -86,13 +86,12 @@ unsigned long long Raytracer_thermal_gpu::trace_rays_thermal_spectral(
     if (rays_per_pixel_gpt.size() != ngpt) throw std::runtime_error(who + "rays_per_pixel_gpt is not (ngpt)");
     if (sensor.npx < 0 || sensor.npy < 0 || radiance.dim(1) != sensor.npx || radiance.dim(2) != sensor.npy || radiance.dim(3) != nchan)
         throw std::runtime_error(who + "radiance is not (npx, npy, nchan)");
-    const Float numbers[12] = {sensor.position[0], sensor.position[1], sensor.position[2], sensor.e_w[0], sensor.e_w[1], sensor.e_w[2],
-                               sensor.e_h[0], sensor.e_h[1], sensor.e_h[2], sensor.e_d[0], sensor.e_d[1], sensor.e_d[2]};
+    const Rt_sensor_numbers numbers(sensor);
     Array_gpu<unsigned long long,1> tallies({2});
     RRX_CALL(rrx_thermal_render_spectral, nx, ny, nz, ngpt, nbnd, RrxBool(top_at_1), tau.ptr(), ssa.size() > 0 ? ssa.ptr() : nullptr,
              band_lims_gpt.ptr(), cloudy ? cld_tau.ptr() : nullptr, cloudy ? cld_ssa.ptr() : nullptr, cloudy ? cld_g.ptr() : nullptr,
              dx, dy, dz, sfc_emis.ptr(), lay_src.ptr(), sfc_src.ptr(), top_radiance.size() > 0 ? top_radiance.ptr() : nullptr, knx, kny, knz,
-             sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers, rays_per_pixel_gpt.ptr(), seed, max_events,
+             sensor.sensor_type, sensor.npx, sensor.npy, sensor.fov, numbers.s, rays_per_pixel_gpt.ptr(), seed, max_events,
              nchan, chan_weights.ptr(), radiance.ptr(), tallies.ptr(), tallies.ptr() + 1);
     if (n_clamped_out != nullptr) *n_clamped_out = tallies({2});
     return tallies({1});
