@@ -110,8 +110,11 @@ class Rte_lw_gpu
                 const Array_gpu<Float,2>& sfc_emis, const Array_gpu<Float,2>& inc_flux,
                 Array_gpu<Float,3>& gpt_flux_up, Array_gpu<Float,3>& gpt_flux_dn, Array_gpu<Float,3>* flux_up_jac, const int n_gauss_angles,
                 const Array_gpu<Float,2>* optimal_angle_fit = nullptr, const Array_gpu<Float,2>* lw_Ds = nullptr);
-        // Gauss-Jacobi secants and weights on the device, uploaded once per object and angle count (an upload per call is a host
-        // copy the stream is synchronised for: the solver launch then waits for the gas optics to finish before it is even enqueued)
+        // Gauss-Jacobi secants (the whole table, in gauss_Ds_gpu) and the weights of the rule with n angles on the device, uploaded once
+        // per object and angle count (an upload per call is a host copy the stream is synchronised for: the solver launch then waits
+        // for the gas optics to finish before it is even enqueued). gauss_weights(n) does that and returns the weights; gauss_Ds_gpu is
+        // good to read after it.
+        const Float* gauss_weights(const int n);
         Array_gpu<Float,2> gauss_Ds_gpu, gauss_wts_gpu;
         int gauss_angles_cached = 0;
 };

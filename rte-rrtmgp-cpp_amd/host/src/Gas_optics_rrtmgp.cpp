@@ -6,7 +6,6 @@
 #include <numeric>
 #include "Gas_optics_rrtmgp.h"
 #include "gas_optics_rrtmgp_kernels_cuda.h"
-#include "rte_solver_kernels_cuda.h"
 
 namespace
 {
@@ -419,15 +418,20 @@ void Gas_optics_rrtmgp_gpu::fill_col_gas(
 
 // The "direct" entry points compute the interpolation state (interpolation_kernel of the reference) inside its consumers:
 // same expressions and bits as interpolation -> compute_tau_absorption -> ..., without the seven intermediate arrays.
-#define RRX_MINOR_ARGS \
-        ncol, nlay, this->get_nband(), this->get_ngpt(), ngas, this->get_nflav(), neta, npres, ntemp, \
-        nminorlower, nminorklower, nminorupper, nminorkupper, idx_h2o, \
-        gpoint_flavor_gpu.ptr(), this->get_band_lims_gpoint_gpu().ptr(), kmajor_gpu.ptr(), kminor_lower_gpu.ptr(), kminor_upper_gpu.ptr(), \
+// The argument runs of the gas-optics entries. RRX_MINOR_ARGS is three of them in a row; rrx_gas_optics_lw_fractions_allsky takes
+// nPlanckTemp after the extents and gpoint_bands after band_lims.
+#define RRX_EXTENT_ARGS \
+        ncol, nlay, this->get_nband(), this->get_ngpt(), ngas, this->get_nflav(), neta, npres, ntemp
+#define RRX_MINOR_COUNT_ARGS \
+        nminorlower, nminorklower, nminorupper, nminorkupper, idx_h2o, gpoint_flavor_gpu.ptr(), this->get_band_lims_gpoint_gpu().ptr()
+#define RRX_TABLE_ARGS \
+        kmajor_gpu.ptr(), kminor_lower_gpu.ptr(), kminor_upper_gpu.ptr(), \
         minor_limits_gpt_lower_gpu.ptr(), minor_limits_gpt_upper_gpu.ptr(), \
         minor_scales_with_density_lower_gpu.ptr(), minor_scales_with_density_upper_gpu.ptr(), \
         scale_by_complement_lower_gpu.ptr(), scale_by_complement_upper_gpu.ptr(), \
         idx_minor_lower_gpu.ptr(), idx_minor_upper_gpu.ptr(), idx_minor_scaling_lower_gpu.ptr(), idx_minor_scaling_upper_gpu.ptr(), \
         kminor_start_lower_gpu.ptr(), kminor_start_upper_gpu.ptr()
+#define RRX_MINOR_ARGS RRX_EXTENT_ARGS, RRX_MINOR_COUNT_ARGS, RRX_TABLE_ARGS
 #define RRX_INTERP_ARGS \
         flavor_gpu.ptr(), press_ref_log_gpu.ptr(), temp_ref_gpu.ptr(), press_ref_log_delta, temp_ref_min, temp_ref_delta, press_ref_trop_log, \
         vmr_ref_gpu.ptr()
@@ -463,15 +467,7 @@ void Gas_optics_rrtmgp_gpu::gas_optics(
     {
         // optical depths + Planck fractions + band Planck functions in one pass; the broadband solver forms the sources
         RRX_CALL(rrx_gas_optics_lw_fractions_allsky,
-                ncol, nlay, this->get_nband(), this->get_ngpt(), ngas, this->get_nflav(), neta, npres, ntemp, this->get_nPlanckTemp(),
-                nminorlower, nminorklower, nminorupper, nminorkupper, idx_h2o,
-                gpoint_flavor_gpu.ptr(), this->get_band_lims_gpoint_gpu().ptr(), this->get_gpoint_bands_gpu().ptr(),
-                kmajor_gpu.ptr(), kminor_lower_gpu.ptr(), kminor_upper_gpu.ptr(),
-                minor_limits_gpt_lower_gpu.ptr(), minor_limits_gpt_upper_gpu.ptr(),
-                minor_scales_with_density_lower_gpu.ptr(), minor_scales_with_density_upper_gpu.ptr(),
-                scale_by_complement_lower_gpu.ptr(), scale_by_complement_upper_gpu.ptr(),
-                idx_minor_lower_gpu.ptr(), idx_minor_upper_gpu.ptr(), idx_minor_scaling_lower_gpu.ptr(), idx_minor_scaling_upper_gpu.ptr(),
-                kminor_start_lower_gpu.ptr(), kminor_start_upper_gpu.ptr(), RRX_INTERP_ARGS,
+                RRX_EXTENT_ARGS, this->get_nPlanckTemp(), RRX_MINOR_COUNT_ARGS, this->get_gpoint_bands_gpu().ptr(), RRX_TABLE_ARGS, RRX_INTERP_ARGS,
                 play.ptr(), tlay.ptr(), tlev.ptr(), tsfc.ptr(), sfc_lay, col_gas.ptr(),
                 planck_frac_gpu.ptr(), totplnk_delta, totplnk_gpu.ptr(),
                 optical_props->get_tau().ptr(), sources.get_planck_frac().ptr(), sources.get_planck_lay().ptr(), sources.get_planck_lev().ptr(),
@@ -482,8 +478,7 @@ void Gas_optics_rrtmgp_gpu::gas_optics(
     RRX_CALL(rrx_gas_optics_lw_direct_allsky, RRX_MINOR_ARGS, RRX_INTERP_ARGS, play.ptr(), tlay.ptr(), col_gas.ptr(), optical_props->get_tau().ptr(), by_band_tau);
     sources.ensure_full_arrays();
     sources.set_fractions_valid(false);
-    RRX_CALL(rrx_planck_source_direct,
-            ncol, nlay, this->get_nband(), this->get_ngpt(), ngas, this->get_nflav(), neta, npres, ntemp, this->get_nPlanckTemp(),
+    RRX_CALL(rrx_planck_source_direct, RRX_EXTENT_ARGS, this->get_nPlanckTemp(),
             play.ptr(), tlay.ptr(), tlev.ptr(), tsfc.ptr(), sfc_lay, col_gas.ptr(), RRX_INTERP_ARGS,
             this->get_gpoint_bands_gpu().ptr(), this->get_band_lims_gpoint_gpu().ptr(), planck_frac_gpu.ptr(),
             totplnk_delta, totplnk_gpu.ptr(), gpoint_flavor_gpu.ptr(),
@@ -546,6 +541,6 @@ void Gas_optics_rrtmgp_gpu::compute_optimal_angles(const Optical_props_arry_gpu&
         throw std::runtime_error("Gas_optics_rrtmgp_gpu::compute_optimal_angles: the optical properties are not on this k-distribution's g-points");
     if (optimal_angles.dim(1) != ncol || optimal_angles.dim(2) != ngpt)
         throw std::runtime_error("Gas_optics_rrtmgp_gpu::compute_optimal_angles: optimal_angles must be (ncol, ngpt)");
-    Rte_solver_kernels_cuda::lw_optimal_secants(ncol, nlay, ngpt, this->get_nband(), optical_props.get_gpoint_bands_gpu().ptr(),
-                                                optimal_angle_fit_gpu.ptr(), optical_props.get_tau().ptr(), optimal_angles.ptr());
+    RRX_CALL(rrx_lw_optimal_secants, ncol, nlay, ngpt, this->get_nband(), optical_props.get_gpoint_bands_gpu().ptr(),
+             optimal_angle_fit_gpu.ptr(), optical_props.get_tau().ptr(), optimal_angles.ptr());
 }

@@ -1,7 +1,6 @@
 """GPU tests of the by-band form of the fused broadband solvers (rrx_lw_solver_noscat_fractions_byband, rrx_sw_solver_2stream_byband):
 against the per-g-point solvers + band sums on the same inputs, against the CPU oracle, on uneven / degenerate bands, over the tilings
 (and the route outside them), through the C++ driver (--byband-solvers) and through pipeline.ResidentSolver(byband=True)."""
-import ctypes
 import os
 import types
 
@@ -9,11 +8,11 @@ import numpy as np
 import pytest
 
 import cases
+from host_driver import run_driver
 from rte_rrtmgp_cpp_amd import synthetic, synthetic_files, rrxio, pipeline
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOSTLIB = os.path.join(ROOT, "rte-rrtmgp-cpp_amd", "lib", "librte_rrtmgp_hip.so")
 
 
 def band_layout(sizes):
@@ -233,25 +232,6 @@ def test_geometries(dt, ncol, nlay, hip_f64, hip_f32):
 
 # ---- C++ driver ---------------------------------------------------------------------------------------------------------------
 KW = dict(ngpt=48, nbnd=3, npres=12, nflav=4, nminor_lower=7, nminor_upper=4)
-
-
-def run_driver(workdir, *flags, env=None):
-    lib = ctypes.CDLL(HOSTLIB)
-    argv = [b"test_rte_rrtmgp_gpu"] + [f.encode() for f in flags]
-    arr = (ctypes.c_char_p * len(argv))(*argv)
-    old = os.getcwd()
-    saved = {}
-    for k, v in (env or {}).items():
-        saved[k] = os.environ.get(k); os.environ[k] = v
-    try:
-        os.chdir(workdir)
-        rc = lib.rrx_host_main(len(argv), arr)
-    finally:
-        os.chdir(old)
-        for k, v in saved.items():
-            if v is None: os.environ.pop(k, None)
-            else: os.environ[k] = v
-    return rc
 
 
 def read_output(d):

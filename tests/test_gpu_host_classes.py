@@ -9,31 +9,13 @@ import numpy as np
 import pytest
 
 import cases
+from host_driver import run_driver
 from rte_rrtmgp_cpp_amd import synthetic, synthetic_files, rrxio, pipeline
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOSTLIB = os.path.join(ROOT, "rte-rrtmgp-cpp_amd", "lib", "librte_rrtmgp_hip.so")
 KW = dict(ngpt=48, nbnd=3, npres=12, nflav=4, nminor_lower=7, nminor_upper=4)
-
-
-def run_driver(workdir, *flags, env=None):
-    lib = ctypes.CDLL(HOSTLIB)
-    argv = [b"test_rte_rrtmgp_gpu"] + [f.encode() for f in flags]
-    arr = (ctypes.c_char_p * len(argv))(*argv)
-    old = os.getcwd()
-    saved = {}
-    for k, v in (env or {}).items():
-        saved[k] = os.environ.get(k); os.environ[k] = v
-    try:
-        os.chdir(workdir)
-        rc = lib.rrx_host_main(len(argv), arr)
-    finally:
-        os.chdir(old)
-        for k, v in saved.items():
-            if v is None: os.environ.pop(k, None)
-            else: os.environ[k] = v
-    return rc
 
 
 @pytest.fixture(scope="module")
@@ -136,6 +118,81 @@ def test_delta_scale_on_lazy_zero_g_is_the_identity():
     hand the stale g array to the kernel (C++ self-check exported by the host library)."""
     lib = ctypes.CDLL(HOSTLIB)
     assert lib.rrx_host_selftest_delta_scale_gzero() == 0
+
+
+RTE_EQUALITIES = {
+    0: "rte_lw_Ds with the Gauss secant everywhere = rte_lw with one angle: broadband arrays, Planck-lite sources",
+    1: "the same with flux_up_jac",
+    2: "rte_lw_Ds with the Gauss secant everywhere = rte_lw with one angle: per-g-point arrays",
+    3: "the same with flux_up_jac",
+    4: "rte_lw on arrays with one slab per band = bnd_flux_up/dn of rte_lw_byband",
+    5: "rte_sw on arrays with one slab per band = bnd_flux_up/dn/dir of rte_sw_byband, mu0 (ncol)",
+    6: "the same with mu0 (ncol, nlay)",
+    7: "broadband flux_up_jac on sources without fractions (jac_bb) = the per-g-point Jacobian added over the g-points from zero",
+    8: "rte_lw_optimal on per-g-point arrays = rte_lw_Ds on the output of rrx_lw_optimal_secants",
+    9: "the same with flux_up_jac",
+}
+# one call per throw of host/src/Rte.cpp, exactly one bad argument each
+RTE_REFUSALS = {
+    100: "rte_lw: no Jacobian for by-band flux arrays",
+    101: "rte_lw: flux_up_jac must be shaped like the flux arrays",
+    102: "rte_lw_optimal: optimal angles need one quadrature angle",
+    103: "rte_lw_optimal: optimal_angle_fit must be (2, nbnd)",
+    104: "rte_lw_Ds: lw_Ds needs one quadrature angle",
+    105: "rte_lw_Ds: lw_Ds must be (ncol, ngpt)",
+    106: "rte_lw: n_gauss_angles must be 1..4",
+    107: "rte_lw: no by-band flux arrays with optimal angles / lw_Ds",
+    108: "rte_lw: flux_up_jac must be shaped like the flux arrays",                # through rte_lw_Ds: the check of solve
+    109: "rte_lw: by-band fluxes need one quadrature angle",
+    110: "rte_lw_byband: needs the Planck-lite sources (enable_planck_lite)",
+    111: "rte_lw_byband: flux arrays need one slab per band",
+    112: "rte_lw_2stream: needs the Planck-lite sources (enable_planck_lite)",
+    113: "rte_lw_2stream: needs broadband flux arrays (third dimension 1)",
+    114: "rte_lw_2stream: the cloud optical properties must be (ncol, nlay, nbnd)",
+    115: "rte_lw_rescaled: needs the Planck-lite sources (enable_planck_lite)",
+    116: "rte_lw_rescaled: needs broadband flux arrays (third dimension 1)",
+    117: "rte_lw_rescaled: the cloud optical properties must be (ncol, nlay, nbnd)",
+    118: "rte_sw_byband: flux arrays need one slab per band",
+    119: "rte_sw: mu0 by layer must be (ncol, nlay)",
+    120: "rte_sw_byband: mu0 by layer must be (ncol, nlay)",
+    121: "rte_sw_byband: flux arrays need one slab per band",
+}
+# two checks broken in one call: the first one speaks
+RTE_REFUSAL_ORDER = {
+    122: "rte_lw: no Jacobian for by-band flux arrays",                            # before the shape of flux_up_jac
+    123: "rte_lw: flux_up_jac must be shaped like the flux arrays",                # before the angle count
+    124: "rte_lw_optimal: optimal angles need one quadrature angle",               # before the shape of the fit
+    125: "rte_lw_Ds: lw_Ds needs one quadrature angle",                            # before the shape of lw_Ds
+    126: "rte_lw: n_gauss_angles must be 1..4",                                    # before one angle for by-band arrays
+    127: "rte_lw: no by-band flux arrays with optimal angles / lw_Ds",             # before the shape of flux_up_jac
+    128: "rte_lw_byband: needs the Planck-lite sources (enable_planck_lite)",      # before the band slabs
+    129: "rte_lw_2stream: needs the Planck-lite sources (enable_planck_lite)",     # before broadband arrays and the cloud shape
+    130: "rte_lw_2stream: needs broadband flux arrays (third dimension 1)",        # before the cloud shape
+    131: "rte_lw_rescaled: needs the Planck-lite sources (enable_planck_lite)",
+    132: "rte_lw_rescaled: needs broadband flux arrays (third dimension 1)",
+    133: "rte_sw_byband: mu0 by layer must be (ncol, nlay)",                       # before the band slabs
+    # by-band flux arrays leave rte_sw / rte_lw ahead of their own checks
+    134: "rte_sw_byband: mu0 by layer must be (ncol, nlay)",
+    135: "rte_lw_byband: needs the Planck-lite sources (enable_planck_lite)",
+    136: "rte_lw: no by-band flux arrays with optimal angles / lw_Ds",             # through rte_lw_optimal
+}
+
+
+def test_rte_classes_route_equalities_and_refusals():
+    """Rte_lw_gpu / Rte_sw_gpu (host/src/Rte.cpp) through rrx_host_selftest_rte, in both precisions, on 5 columns x 4 layers x 6 g-points
+    in 2 bands with the Planck-lite state set by hand: routes of the classes that no driver run reaches (rte_lw_Ds, band-shaped
+    arrays given to rte_lw / rte_sw, the broadband Jacobian of the general solver) agree in bits with the routes that are reached,
+    and every refusal of the file reads as written here, the first of two applicable ones first."""
+    for name in ("librte_rrtmgp_hip.so", "librte_rrtmgp_hip_sp.so"):
+        lib = ctypes.CDLL(os.path.join(os.path.dirname(HOSTLIB), name))
+        lib.rrx_host_selftest_rte.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+        lib.rrx_host_selftest_rte.restype = ctypes.c_int
+        msg = ctypes.create_string_buffer(512)
+        for which, what in RTE_EQUALITIES.items():
+            assert lib.rrx_host_selftest_rte(which, msg, len(msg)) == 0, (name, which, what, msg.value.decode())
+        for which, text in {**RTE_REFUSALS, **RTE_REFUSAL_ORDER}.items():
+            assert lib.rrx_host_selftest_rte(which, msg, len(msg)) == -1, (name, which, "was not refused")
+            assert msg.value.decode() == text, (name, which)
 
 
 def test_driver_heating_rates_and_async_mode(case, hip_f64):

@@ -2,7 +2,6 @@
 against the general kernel's per-g-point Jacobian + rrx_sum_broadband on the same inputs over the tilings (and the route outside them),
 against the CPU oracle, fluxes bit for bit those of rrx_lw_solver_noscat_fractions, a finite difference through the whole LW chain,
 and through pipeline.ResidentSolver(jacobian=True), the C++ solver (set_jacobian) and the driver (--lw-jacobian)."""
-import ctypes
 import os
 import types
 
@@ -10,11 +9,11 @@ import numpy as np
 import pytest
 
 import cases
+from host_driver import run_driver
 from rte_rrtmgp_cpp_amd import synthetic, synthetic_files, rrxio, pipeline
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOSTLIB = os.path.join(ROOT, "rte-rrtmgp-cpp_amd", "lib", "librte_rrtmgp_hip.so")
 
 
 def inputs(ncol, nlay, ngpt, nbnd, seed, dtype):
@@ -195,25 +194,6 @@ def test_cxx_solver_jacobian_matches_pipeline(clouds, broadband, hip_f64, monkey
 
 
 KW = dict(ngpt=48, nbnd=3, npres=12, nflav=4, nminor_lower=7, nminor_upper=4)
-
-
-def run_driver(workdir, *flags, env=None):
-    lib = ctypes.CDLL(HOSTLIB)
-    argv = [b"test_rte_rrtmgp_gpu"] + [f.encode() for f in flags]
-    arr = (ctypes.c_char_p * len(argv))(*argv)
-    old = os.getcwd()
-    saved = {}
-    for k, v in (env or {}).items():
-        saved[k] = os.environ.get(k); os.environ[k] = v
-    try:
-        os.chdir(workdir)
-        rc = lib.rrx_host_main(len(argv), arr)
-    finally:
-        os.chdir(old)
-        for k, v in saved.items():
-            if v is None: os.environ.pop(k, None)
-            else: os.environ[k] = v
-    return rc
 
 
 def test_driver_lw_jacobian(tmp_path, hip_f64):

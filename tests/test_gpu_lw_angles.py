@@ -3,7 +3,6 @@ route on the same inputs (Planck sources from fractions -> general kernel with n
 tilings and the route outside them, with a per-column secants array, one angle bit for bit the one-angle entries, against the CPU
 oracle, an isothermal column set whose upward flux is known in closed form, and through the layers: pipeline.ResidentSolver
 (n_gauss_angles=3), the C++ solver (set_gauss_angles) and the driver (--lw-gauss-angles)."""
-import ctypes
 import os
 import types
 
@@ -11,11 +10,12 @@ import numpy as np
 import pytest
 
 import cases
+from host_driver import run_driver
+from test_gpu_jacobian import _chain
 from rte_rrtmgp_cpp_amd import synthetic, synthetic_files, rrxio, pipeline
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOSTLIB = os.path.join(ROOT, "rte-rrtmgp-cpp_amd", "lib", "librte_rrtmgp_hip.so")
 
 
 def inputs(ncol, nlay, ngpt, nbnd, seed, dtype):
@@ -210,23 +210,11 @@ def test_resident_solver_with_three_angles(dt, jacobian, hip_f64, hip_f32, monke
         pipeline.ResidentSolver(be, kl, ks, atm, do_broadband=True, byband=True, n_gauss_angles=3)
 
 
-def _chain(ncol, nlay, seed, clouds=False, spread=False):
-    """the case builder of tests/test_gpu_jacobian.py"""
-    kw = dict(ngpt=32, nbnd=4, npres=20, nflav=4, nminor_lower=9, nminor_upper=5)
-    kl0, ks0 = synthetic.make_kdist("lw", **kw), synthetic.make_kdist("sw", **kw)
-    atm0 = synthetic.make_atmosphere(ncol, nlay, nbnd_lw=4, nbnd_sw=4, clouds=clouds, seed=seed)
-    if spread:
-        f = np.random.default_rng(seed + 1).uniform(0.65, 1.35, ncol)
-        atm0.p_lay = np.ascontiguousarray(atm0.p_lay * f); atm0.p_lev = np.ascontiguousarray(atm0.p_lev * f)
-    luts0 = (synthetic.make_cloud_lut(4, "lw"), synthetic.make_cloud_lut(4, "sw")) if clouds else None
-    return atm0, kl0, ks0, luts0
-
-
 def test_resident_solver_three_angles_sorted_and_padded(hip_f64, monkeypatch):
     """ResidentSolver(n_gauss_angles=3) on 16 385 columns (padded to 16 400) with a surface-pressure spread that switches sorting on,
     against an unsorted, unpadded run; the SW outputs are those of one angle bit for bit; by-band outputs are refused."""
     be = hip_f64
-    atm0, kl0, ks0, _ = _chain(16385, 30, seed=5, spread=True)
+    atm0, kl0, ks0, _ = _chain(be, 16385, 30, seed=5, spread=True)
     kl, ks = be.upload_kdist(kl0), be.upload_kdist(ks0)
     atm = pipeline.upload_atmosphere(be, atm0)
     monkeypatch.setenv("RRX_PAD_COLUMNS", "0")
@@ -257,7 +245,7 @@ def test_finite_difference_with_three_angles(dt, hip_f64, hip_f32, monkeypatch):
     three-angle solver; only sfc_src depends on t_sfc, so the change of flux_up is the Jacobian to rounding."""
     be, npdt = backend(dt, hip_f64, hip_f32)
     monkeypatch.setenv("RRX_PAD_COLUMNS", "0")
-    atm0, kl0, ks0, _ = _chain(64, 140, seed=3)
+    atm0, kl0, ks0, _ = _chain(be, 64, 140, seed=3)
     atm = pipeline.upload_atmosphere(be, atm0.astype(be.np_dtype))
     sv = pipeline.ResidentSolver(be, be.upload_kdist(kl0), be.upload_kdist(ks0), atm, do_broadband=True, sort_columns="0", jacobian=True,
                                  n_gauss_angles=3)
@@ -279,7 +267,7 @@ def test_cxx_solver_three_angles_matches_pipeline(clouds, broadband, hip_f64):
     ResidentSolver(n_gauss_angles=3): 1e-11 on the broadband solvers (the same kernel), the general-route bound on the per-g-point ones."""
     from rte_rrtmgp_cpp_amd import cxx_driver
     be = hip_f64
-    atm0, kl0, ks0, luts0 = _chain(2500, 30, seed=31, clouds=clouds, spread=True)
+    atm0, kl0, ks0, luts0 = _chain(be, 2500, 30, seed=31, clouds=clouds, spread=True)
     sv = pipeline.ResidentSolver(be, be.upload_kdist(kl0), be.upload_kdist(ks0), pipeline.upload_atmosphere(be, atm0), do_broadband=True,
                                  cloud_luts=None if luts0 is None else tuple(be.upload_lut(l) for l in luts0), jacobian=True,
                                  n_gauss_angles=3)
@@ -303,25 +291,6 @@ def test_cxx_solver_three_angles_matches_pipeline(clouds, broadband, hip_f64):
 
 
 KW = dict(ngpt=48, nbnd=3, npres=12, nflav=4, nminor_lower=7, nminor_upper=4)
-
-
-def run_driver(workdir, *flags, env=None):
-    lib = ctypes.CDLL(HOSTLIB)
-    argv = [b"test_rte_rrtmgp_gpu"] + [f.encode() for f in flags]
-    arr = (ctypes.c_char_p * len(argv))(*argv)
-    old = os.getcwd()
-    saved = {}
-    for k, v in (env or {}).items():
-        saved[k] = os.environ.get(k); os.environ[k] = v
-    try:
-        os.chdir(workdir)
-        rc = lib.rrx_host_main(len(argv), arr)
-    finally:
-        os.chdir(old)
-        for k, v in saved.items():
-            if v is None: os.environ.pop(k, None)
-            else: os.environ[k] = v
-    return rc
 
 
 def test_driver_lw_gauss_angles(tmp_path, hip_f64):

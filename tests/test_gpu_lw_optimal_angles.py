@@ -246,7 +246,7 @@ def test_resident_solver_optimal_angles_sorted_and_padded(hip_f64, monkeypatch):
     """ResidentSolver(optimal_angles=True) on 16 385 columns (padded to 16 400) with a surface-pressure spread that switches sorting
     on, against an unsorted, unpadded run at 1e-11; the SW outputs are those of the plain solver bit for bit."""
     be = hip_f64
-    atm0, kl0, ks0, _ = _chain(16385, 30, seed=5, spread=True)
+    atm0, kl0, ks0, _ = _chain(be, 16385, 30, seed=5, spread=True)
     kl, ks = be.upload_kdist(kl0), be.upload_kdist(ks0)
     atm = pipeline.upload_atmosphere(be, atm0)
     monkeypatch.setenv("RRX_PAD_COLUMNS", "0")
@@ -274,7 +274,7 @@ def test_cxx_solver_optimal_angles_matches_pipeline(clouds, hip_f64):
     one angle with them is refused at the solve."""
     from rte_rrtmgp_cpp_amd import cxx_driver
     be = hip_f64
-    atm0, kl0, ks0, luts0 = _chain(2500, 30, seed=31, clouds=clouds, spread=True)
+    atm0, kl0, ks0, luts0 = _chain(be, 2500, 30, seed=31, clouds=clouds, spread=True)
     luts = None if luts0 is None else tuple(be.upload_lut(l) for l in luts0)
     sv = pipeline.ResidentSolver(be, be.upload_kdist(kl0), be.upload_kdist(ks0), pipeline.upload_atmosphere(be, atm0), do_broadband=True,
                                  cloud_luts=luts, jacobian=True, optimal_angles=True)

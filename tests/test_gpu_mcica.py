@@ -2,13 +2,13 @@
 (tests/mcica_ref.py) bit for bit, the column identities through permutations and splits, pipeline.ResidentSolver(cloud_fraction=...)
 against today's all-sky route where the fractions are 0 or 1, the bracketing of a half-cloudy solve, the refused pairs, and the C++
 classes and driver against ResidentSolver."""
-import ctypes
 import os
 
 import numpy as np
 import pytest
 
 import cases
+from host_driver import run_driver
 import mcica_ref as M
 from rte_rrtmgp_cpp_amd import synthetic, synthetic_files, rrxio, pipeline
 
@@ -357,24 +357,6 @@ def test_cxx_classes_match_resident_solver(overlap, hip_f64):
     e_lw, e_sw = lw_sw_err(got, ref)
     assert e_lw <= 1e-11 and e_sw <= 1e-7
     assert not np.array_equal(other, got)
-
-
-def run_driver(workdir, *flags, env=None):
-    """rrx_host_main of the host library in workdir: the command-line driver's behaviour and exit status"""
-    lib = ctypes.CDLL(os.path.join(ROOT, "rte-rrtmgp-cpp_amd", "lib", "librte_rrtmgp_hip.so"))
-    argv = [b"test_rte_rrtmgp_gpu"] + [f.encode() for f in flags]
-    old, saved = os.getcwd(), {k: os.environ.get(k) for k in (env or {})}
-    os.environ.update(env or {})
-    try:
-        os.chdir(workdir)
-        return lib.rrx_host_main(len(argv), (ctypes.c_char_p * len(argv))(*argv))
-    finally:
-        os.chdir(old)
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def read_output(d):

@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 import cases
+from host_driver import run_driver
 import cpu_boundary
 import support_ref
 import sw_mu0_ref
@@ -428,18 +429,6 @@ def test_resident_solver_on_the_sunlit_columns_only(mode, dt, hip_f64, hip_f32):
 
 
 # ---- 10: the C++ host classes and the driver ---------------------------------------------------------------------------------------
-def _run_driver(workdir, *flags):
-    import ctypes
-    import os
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = ctypes.CDLL(os.path.join(root, "rte-rrtmgp-cpp_amd", "lib", "librte_rrtmgp_hip.so"))
-    argv = [b"test_rte_rrtmgp_gpu"] + [f.encode() for f in flags]
-    old = os.getcwd()
-    try:
-        os.chdir(workdir)
-        return lib.rrx_host_main(len(argv), (ctypes.c_char_p * len(argv))(*argv))
-    finally:
-        os.chdir(old)
 
 
 def test_driver_with_spherical_mu0_matches_the_resident_solver(tmp_path, hip_f64):
@@ -459,20 +448,20 @@ def test_driver_with_spherical_mu0_matches_the_resident_solver(tmp_path, hip_f64
 
     # (the driver against the Python pipeline on the same kernels: the tolerances of tests/test_gpu_host_classes.py)
     for flags in ((), ("--no-broadband-solvers",), ("--output-bnd-fluxes", "--byband-solvers"), ("--device-sort-columns",)):
-        assert _run_driver(d, "--sw-spherical-mu0", *flags) == 0, flags
+        assert run_driver(d, "--sw-spherical-mu0", *flags) == 0, flags
         out = output()
         for i, k in enumerate(names):
             e = cases.rel_err(out[k], ref[i]); print(f"driver {flags} {k}: {e:.3e}")
             assert e <= (1e-7 if k.startswith("sw_") else 1e-11), (flags, k)
     assert cases.rel_err(out["sw_flux_dn"], plain[4]) > 1e-3             # (the flag does something)
     # without the flag: the plain solve; z_lay missing: a message and a non-zero status
-    assert _run_driver(d) == 0
+    assert run_driver(d) == 0
     assert cases.rel_err(output()["sw_flux_dn"], plain[4]) <= 1e-7
     synthetic_files.write_input(os.path.join(d, "rte_rrtmgp_input.nc"), atm0, kl0.nbnd, ks0.nbnd)
-    assert _run_driver(d, "--sw-spherical-mu0") != 0
+    assert run_driver(d, "--sw-spherical-mu0") != 0
     # z_ref absent: mu0 holds at altitude 0
     synthetic_files.write_input(os.path.join(d, "rte_rrtmgp_input.nc"), atm0, kl0.nbnd, ks0.nbnd, z_lay=alt)
-    assert _run_driver(d, "--sw-spherical-mu0") == 0
+    assert run_driver(d, "--sw-spherical-mu0") == 0
     _, ref0, _ = _solve(be, "f64", altitude=alt)
     out = output()
     for i, k in enumerate(names):
