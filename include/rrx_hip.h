@@ -419,6 +419,12 @@ int rrx_lw_solver_noscat_fractions_optimal##SFX( \
         const F* tau, const F* pfrac, const F* blay, const F* blev, const int* gpoint_bands, const F* optimal_angle_fit, \
         const F* sfc_emis, const F* sfc_src, const F* inc_flux, F* flux_up_loc, F* flux_dn_loc, \
         const F* sfc_src_jac, F* flux_up_jac, F* secants_out, void* stream); \
+/* Test entry (no counterpart in the reference library): the solvers' device math primitives of csrc/rrx_common.h applied element-wise, \
+   y[i] = f(x[i]) for i < n, so that their documented accuracy can be measured on the device. which = 0: exp_neg (fp64: the \
+   polynomial form; fp32: the v_exp_f32 form), 1: exp_neg in its LDS-table form, the table filled as the fused LW solver fills it \
+   (fp32: the same function as 0), 2: fast_rcp, 3: sqrt_pos, 4: sqrt_nonneg. The arguments must lie in the primitive's documented \
+   domain. Any other `which`, a negative n, or a NULL x or y with n > 0: non-zero, nothing launched; n = 0 returns 0. */ \
+int rrx_math_selftest##SFX(int which, int n, const F* x, F* y, void* stream); \
 /* lw_solver_2stream: the LW two-stream solver WITH scattering (current RTE+RRTMGP; the reference has none). Per g-point and column, \
    layers and levels in sweep order from the top, D = 1.66: \
      gamma1 = D (1 - ssa (1 + g)/2), gamma2 = D ssa (1 - g)/2, k = sqrt(max((gamma1 - gamma2)(gamma1 + gamma2), 1e-12)), \

@@ -1286,6 +1286,50 @@ int lw_solver_noscat_fractions_byband_impl(
                                bnd_net, flux_up, flux_dn, (F*)nullptr);
     RRX_CATCH("rrx_lw_solver_noscat_fractions_byband")
 }
+
+// The math primitives of rrx_common.h applied element-wise (rrx_math_selftest), so that a test can measure on the device what their
+// comments claim: y[i] = f(x[i]) with f chosen by `which`. Compiled in this file, i.e. under the solver's contraction mode; the table
+// form reads a table that exp_table_fill wrote to LDS behind a barrier, as lw_noscat_bb_kernel does.
+enum MathPrimitive { MATH_EXP_NEG = 0, MATH_EXP_NEG_TABLE = 1, MATH_FAST_RCP = 2, MATH_SQRT_POS = 3, MATH_SQRT_NONNEG = 4, MATH_COUNT = 5 };
+
+template<typename F>
+__global__ void __launch_bounds__(256)
+math_selftest_kernel(const int which, const size_t n, const F* __restrict__ x, F* __restrict__ y)
+{
+    constexpr bool ETAB = sizeof(F) == 8;                // (fp32: the table form forwards to the fp32 exp_neg)
+    __shared__ F lds_etab[ETAB ? 64 : 1];
+    if constexpr (ETAB) { exp_table_fill(lds_etab); __syncthreads(); }
+    for (size_t i = size_t(blockIdx.x)*blockDim.x + threadIdx.x; i < n; i += size_t(gridDim.x)*blockDim.x)
+    {
+        const F v = x[i];
+        F r;
+        switch (which)
+        {
+            case MATH_EXP_NEG:       r = exp_neg(v); break;
+            case MATH_EXP_NEG_TABLE: r = exp_neg(v, lds_etab); break;
+            case MATH_FAST_RCP:      r = fast_rcp(v); break;
+            case MATH_SQRT_POS:      r = sqrt_pos(v); break;
+            default:                 r = sqrt_nonneg(v); break;
+        }
+        y[i] = r;
+    }
+}
+
+template<typename F>
+int math_selftest_impl(const int which, const int n, const F* x, F* y, void* stream)
+{
+    const char* entry = "rrx_math_selftest";
+    const char* bad = nullptr;
+    if (which < 0 || which >= MATH_COUNT) bad = "which must be 0 (exp_neg), 1 (exp_neg, table form), 2 (fast_rcp), 3 (sqrt_pos) or 4 (sqrt_nonneg)";
+    else if (n < 0) bad = "n is negative";
+    else if (n > 0 && x == nullptr) bad = "x is null";
+    else if (n > 0 && y == nullptr) bad = "y is null";
+    if (bad != nullptr) { set_error(std::string(entry) + ": " + bad); return 1; }
+    if (n == 0) return 0;
+    RRX_TRY
+    math_selftest_kernel<F><<<std::min(ceil_div(n, 256), 1024), 256, 0, static_cast<hipStream_t>(stream)>>>(which, size_t(n), x, y);
+    RRX_CATCH(entry)
+}
 }  // namespace
 
 
@@ -1411,7 +1455,9 @@ int rrx_lw_solver_noscat_fractions_optimal##SFX( \
 { \
     return lw_solver_noscat_fractions_optimal_impl<F>(ncol, nlay, ngpt, nbnd, top_at_1, weights, tau, pfrac, blay, blev, gpoint_bands, \
             optimal_angle_fit, sfc_emis, sfc_src, inc_flux, flux_up_loc, flux_dn_loc, sfc_src_jac, flux_up_jac, secants_out, stream); \
-}
+} \
+int rrx_math_selftest##SFX(int which, int n, const F* x, F* y, void* stream) \
+{ return math_selftest_impl<F>(which, n, x, y, stream); }
 
 RRX_DEFINE_LW_FRACTIONS(double, _f64)
 RRX_DEFINE_LW_FRACTIONS(float, _f32)

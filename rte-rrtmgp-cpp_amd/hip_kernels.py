@@ -403,6 +403,19 @@ class HipKernels:
         self._c("lw_flux_up_adjust", ncol, nlev, flux_up_jac, t_sfc_old, t_sfc_new, flux_up, flux_net)
         return flux_up
 
+    MATH_PRIMITIVES = ("exp_neg", "exp_neg_table", "fast_rcp", "sqrt_pos", "sqrt_nonneg")
+
+    def math_selftest(self, primitive, x, out=None):
+        """Test entry (rrx_math_selftest): one of the solvers' device math primitives (MATH_PRIMITIVES, csrc/rrx_common.h) applied
+        element-wise to the 1-D tensor x"""
+        if primitive not in self.MATH_PRIMITIVES:
+            raise ValueError(f"{primitive!r} is not one of {self.MATH_PRIMITIVES}")
+        if x.dim() != 1 or not x.is_contiguous():
+            raise ValueError("math_selftest: x must be a contiguous 1-D tensor")
+        out = torch.empty_like(x) if out is None else out
+        self._c("math_selftest", self.MATH_PRIMITIVES.index(primitive), x.shape[0], x, out)
+        return out
+
     def lw_solver_noscat_fractions_byband(self, top_at_1, kd, secants, weights, tau, fr, sfc_emis, inc_flux=None, out=None,
                                           net=True, broadband=True, band_lims=None, gpoint_bands=None):
         """By-band fluxes of lw_solver_noscat_fractions: bnd_flux_up/dn (nbnd, nlev, ncol), bnd_flux_net = dn - up, and the broadband
