@@ -1041,7 +1041,54 @@ int rrx_thermal_render_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd,
         F dx, F dy, F dz, const F* sfc_emis, const F* lay_src, const F* sfc_src, const F* top_radiance, int knx, int kny, int knz, \
         int sensor_type, int npx, int npy, F fov, const F* sensor, const long long* rays_per_pixel_gpt, unsigned long long seed, \
         int max_events, int nchan, const F* chan_weights, F* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, \
-        void* stream);
+        void* stream); \
+/* ---- 3-D longwave heating from cell sensors (csrc/rrx_raytracer_heating.hip): the net radiative power that every \
+   cell of the grid takes up per unit horizontal area, flux_conv in W m-2, by emission reciprocity. The symbols begin rrx_heating3d_: \
+   the set of rrx_thermal_ symbols is closed. The scene is that of \
+   rrx_thermal_trace_counts without the sensor, the tracking that entry's, draw for draw. Ray r belongs to cell c = r mod (nx ny nz), \
+   i = c mod nx, j = (c / nx) mod ny, k = c / (nx ny) counted upward from the surface; it starts at a uniform point of the cell in an \
+   isotropic direction (five draws: x, y, z, uz = 1 - 2u, phi); Philox4x32-10 keyed by seed with counter (r low, r high, \
+   igpt | 0x40000000, block). Its reference is read once from its own cell: B0 = lay_src[cell0, g] and \
+   s0 = F(4 pi) (tau (1 - ssa) + cld_tau (1 - cld_ssa)); a cell with s0 = 0 ends its ray at once. The deposits are signed differences, \
+   each made before the weight changes: at a collision (weight (1 - f_no_abs)) ((lay_src[cell, g] - B0) s0), at the surface \
+   (weight sfc_emis) ((sfc_src[col, g] - B0) s0), through the top weight ((top_radiance - B0) s0). Each is rounded by itself, \
+   llrint(clamp(d, -2^20, 2^20) 2^32) (a clamped one counts in n_clamped), summed in 64-bit integers along the ray and added with one \
+   integer atomic into counts[cell0] when the ray ends (the roulette, the top, max_events, no face: the last two count in n_capped). \
+   rrx_heating3d_counts: traces the rays [ray0, ray0 + nrays) of g-point igpt and ADDS into the caller-zeroed counts (nx ny nz), \
+   SIGNED 64-bit in units of 2^-32 W m-2, in the layout of lay_src (cell = icol + ncol lay), and into n_capped and n_clamped. Integer \
+   adds: bit-reproducible, independent of the order of arrival, additive over ray ranges. With m rays per cell \
+   flux_conv of the g-point = counts 2^-32 / m. \
+   rrx_heating3d_counts_spectral: the same without igpt for the rays of all g-points in one launch, ngpt <= 1024, with the DEVICE \
+   arrays top_radiance (ngpt, or NULL for 0), ray_end (ngpt+1) and weight0 (ngpt) as rrx_thermal_trace_counts_spectral has them: the \
+   list is the concatenation in g-point order of m_g nx ny nz rays, m_g >= 0 rays per cell; ray p of the list is ray \
+   q = p - ray_end[g] of rrx_heating3d_counts(igpt = g), draw for draw; s0 is multiplied by weight0[g]. All g-points add into \
+   the same nx ny nz counts: the result is broadband. band_lims_gpt is always needed and only finds the cloud triple; a g-point \
+   that lies in no band has no cloud and is still tallied. k_null is rrx_rt_k_null_all's (with a NULL aer_tau). \
+   rrx_heating3d_render: rays_per_cell_gpt (ngpt, HOST) = m_g and top_radiance (ngpt, HOST, or NULL for 0). Forms the list and \
+   weight0[g] = (F(1) / F(m_g)) / U, U = F(n_act) / F(P) as rrx_thermal_render_spectral does, traces chunks of consecutive g-points (as \
+   many as keep k_null within 1 GiB, or RRX_RT_SPECTRAL_GPT_PER_LAUNCH), adds the chunks in integers and converts once: \
+   flux_conv[cell] = F(counts 2^-32) U, (ncol, nz) in the layout of lay_src, W m-2. The result does not depend on the chunking. A \
+   g-point with m_g = 0 is left out of the result. All m_g = 0: zeroes its outputs and returns 0. It waits for its stream once. \
+   An extent of 0 (nx, ny, nz, ngpt, nrays): returns 0 without a launch. Refused before any HIP call: what the thermal entries refuse \
+   of grid, cloud triple, sources and top_radiance; a NULL counts, flux_conv, counter, k_null, ray_end, weight0 or rays_per_cell_gpt; \
+   m_g < 0; a negative ray0; ngpt > 1024 and a NULL band_lims_gpt in the spectral forms. LIMITS: those of the thermal tracer; no \
+   heating by band. */ \
+int rrx_heating3d_counts##SFX(int nx, int ny, int nz, int ngpt, int nbnd, int igpt, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_emis, const F* lay_src, const F* sfc_src, F top_radiance, int knx, int kny, int knz, const F* k_null, \
+        unsigned long long seed, long long ray0, long long nrays, int max_events, \
+        long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream); \
+int rrx_heating3d_counts_spectral##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_emis, const F* lay_src, const F* sfc_src, const F* top_radiance, \
+        const long long* ray_end, const F* weight0, int knx, int kny, int knz, const F* k_null, \
+        unsigned long long seed, long long ray0, long long nrays, int max_events, \
+        long long* counts, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream); \
+int rrx_heating3d_render##SFX(int nx, int ny, int nz, int ngpt, int nbnd, RrxBool top_at_1, \
+        const F* tau, const F* ssa, const int* band_lims_gpt, const F* cld_tau, const F* cld_ssa, const F* cld_g, \
+        F dx, F dy, F dz, const F* sfc_emis, const F* lay_src, const F* sfc_src, const F* top_radiance, int knx, int kny, int knz, \
+        const long long* rays_per_cell_gpt, unsigned long long seed, int max_events, \
+        F* flux_conv, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream);
 
 RRX_DECLARE(double, _f64)
 RRX_DECLARE(float, _f32)

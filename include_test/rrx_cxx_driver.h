@@ -156,6 +156,13 @@ int   rrx_cxx_trace_rays_thermal_spectral(int nx, int ny, int nz, int ngpt, int 
                             int sensor_type, int npx, int npy, Real fov, const Real* sensor, const long long* rays_per_pixel_gpt,
                             long long total_rays, const Real* emission, unsigned long long seed, int max_events, int nchan,
                             const Real* chan_weights, Real* radiance, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream);
+/* Raytracer_thermal_gpu::trace_heating: 3-D longwave heating from cell sensors on the same device arrays.
+ * rays_per_cell_gpt (ngpt) and top_radiance (ngpt, or NULL) on the HOST; flux_conv (ncol, nz) on the device, W m-2. */
+int   rrx_cxx_trace_heating(int nx, int ny, int nz, int ngpt, int nbnd, Real dx, Real dy, Real dz, int top_at_1,
+                            const Real* tau, const Real* ssa, const int* band_lims_gpt, const Real* cld_tau, const Real* cld_ssa, const Real* cld_g,
+                            const Real* sfc_emis, const Real* lay_src, const Real* sfc_src, const Real* top_radiance, int knx, int kny, int knz,
+                            const long long* rays_per_cell_gpt, unsigned long long seed, int max_events, Real* flux_conv,
+                            unsigned long long* n_capped, unsigned long long* n_clamped, void* stream);
 /* one LW + one SW solve_gpu (fluxes only) enqueued on `stream`; DEVICE arrays: (ncol,nlay) / (ncol,nlay+1) fields, (ncol) vectors,
    surface properties (nbnd,ncol); lwp, iwp, rel, dei NULL without clouds; out7: seven (ncol, nlay+1) arrays for LW up, dn, net and
    SW up, dn, dn_dir, net, or NULL (the driver then keeps them: rrx_cxx_driver_fluxes) */

@@ -990,6 +990,55 @@ class HipKernels:
                 int(M.shape[0]), M, radiance, n_capped, n_clamped)
         return dict(radiance=radiance, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
 
+    # 3-D longwave heating from cell sensors (rrx_heating3d_counts, rrx_heating3d_counts_spectral,
+    # rrx_heating3d_render): the thermal tracer's scene without a sensor. Ray r belongs to cell r mod (nx ny nz);
+    # counts (nz, ncol) are int64 tensors holding SIGNED 64-bit numbers in units of 2^-32 W m-2, in the layout of lay_src[g].
+    def thermal_heating_zero_counts(self, nz, ncol):
+        return self._rt_zeros(counts=(nz, ncol), n_capped=(1,), n_clamped=(1,))
+
+    def thermal_heating_counts(self, tau, ssa, igpt, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src, top_radiance, kn_grid, k_null, seed,
+                               ray0, nrays, top_at_1=False, cloud=None, band_lims=None, counts=None, max_events=None):
+        """Adds the rays [ray0, ray0 + nrays) of g-point igpt into counts (thermal_heating_zero_counts; made when None): counts
+        (nz, ncol), n_capped, n_clamped. top_radiance: one number. With m rays per cell flux_conv of the g-point = counts 2^-32 / m."""
+        sc, scene = self._thermal_scene(tau, ssa, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src, kn_grid, top_at_1, cloud, band_lims)
+        counts = self.thermal_heating_zero_counts(sc.nz, sc.ncol) if counts is None else counts
+        self._c("heating3d_counts", *sc.dims, igpt, sc.flags[0], *scene, float(top_radiance), *sc.kn, k_null,
+                *sc.run(seed, max_events, ray0, nrays), counts["counts"], counts["n_capped"], counts["n_clamped"])
+        return counts
+
+    def thermal_heating_counts_spectral(self, tau, ssa, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src, top_radiance, ray_end, weight0, kn_grid,
+                                        k_null, seed, ray0, nrays, band_lims, top_at_1=False, cloud=None, counts=None, max_events=None):
+        """Adds the rays [ray0, ray0 + nrays) of the concatenated list into counts (thermal_heating_zero_counts; made when None): one
+        (nz, ncol) for all g-points, n_capped, n_clamped. ray_end (ngpt+1,) int64, weight0 (ngpt,) and top_radiance, None (0) or
+        (ngpt,): arrays on the host, checked and uploaded here; k_null is rt_k_null_all's."""
+        sc, scene = self._thermal_spectral_scene("thermal_heating_counts_spectral", tau, ssa, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src,
+                                                 kn_grid, top_at_1, cloud, band_lims)
+        if top_radiance is None:
+            top, lists = None, self._rt_list(sc.ngpt, "rays", ray0, nrays, ray_end=ray_end, weight0=weight0)
+        else:
+            *lists, top = self._rt_list(sc.ngpt, "rays", ray0, nrays, ray_end=ray_end, weight0=weight0, top_radiance=top_radiance)
+        counts = self.thermal_heating_zero_counts(sc.nz, sc.ncol) if counts is None else counts
+        self._c("heating3d_counts_spectral", *sc.dims, sc.flags[0], *scene, top, *lists, *sc.kn, k_null,
+                *sc.run(seed, max_events, ray0, nrays), counts["counts"], counts["n_capped"], counts["n_clamped"])
+        return counts
+
+    def thermal_heating_render(self, tau, ssa, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src, kn_grid, rays_per_cell_gpt, seed, band_lims,
+                               top_at_1=False, cloud=None, max_events=None, top_radiance=None):
+        """rays_per_cell_gpt (ngpt,) rays per cell of each g-point, all g-points in one trace launch per chunk, one conversion. A g-point
+        with no rays is left out of the result. Returns flux_conv (nz, ncol) in W m-2, the net radiative power that a cell takes up per
+        unit horizontal area, n_capped and n_clamped (ints)."""
+        sc, scene = self._thermal_spectral_scene("thermal_heating_render", tau, ssa, nx, ny, dx, dy, dz, sfc_emis, lay_src, sfc_src,
+                                                 kn_grid, top_at_1, cloud, band_lims)
+        rays = np.ascontiguousarray(rays_per_cell_gpt, dtype=np.int64).reshape(-1)
+        if rays.size != sc.ngpt:
+            raise ValueError("thermal: rays_per_cell_gpt is (ngpt,)")
+        if top_radiance is not None:
+            top_radiance, = self._rt_per_gpt(sc.ngpt, top_radiance=top_radiance)
+        flux_conv, n_capped, n_clamped = self._rt_radiance((sc.nz, sc.ncol))
+        self._c("heating3d_render", *sc.dims, sc.flags[0], *scene, top_radiance, *sc.kn, rays, *sc.run(seed, max_events),
+                flux_conv, n_capped, n_clamped)
+        return dict(flux_conv=flux_conv, n_capped=int(n_capped.item()), n_clamped=int(n_clamped.item()))
+
     def delta_scale_2str_k(self, tau, ssa, g):
         ngpt, nlay, ncol = tau.shape
         self._c("delta_scale_2str_k", ncol, nlay, ngpt, tau, ssa, g)

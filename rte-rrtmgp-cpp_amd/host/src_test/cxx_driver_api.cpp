@@ -654,3 +654,40 @@ extern "C" int rrx_cxx_trace_rays_thermal_spectral(const int nx, const int ny, c
         rrx_host::set_stream(before);
     });
 }
+
+// Raytracer_thermal_gpu::trace_heating on device arrays the caller owns. rays_per_cell_gpt (ngpt) and top_radiance (ngpt,
+// or NULL: none) on the HOST; flux_conv: a device array (nz, ncol).
+extern "C" int rrx_cxx_trace_heating(const int nx, const int ny, const int nz, const int ngpt, const int nbnd, const Float dx, const Float dy,
+        const Float dz, const int top_at_1, const Float* tau, const Float* ssa, const int* band_lims_gpt,
+        const Float* cld_tau, const Float* cld_ssa, const Float* cld_g, const Float* sfc_emis, const Float* lay_src, const Float* sfc_src,
+        const Float* top_radiance, const int knx, const int kny, const int knz, const long long* rays_per_cell_gpt, const unsigned long long seed,
+        const int max_events, Float* flux_conv, unsigned long long* n_capped, unsigned long long* n_clamped, void* stream)
+{
+    return guarded([&]
+    {
+        if (rays_per_cell_gpt == nullptr) throw std::runtime_error("rrx_cxx_trace_heating: rays_per_cell_gpt is NULL");
+        void* const before = rrx_host::current_stream();
+        rrx_host::set_stream(stream);
+        try
+        {
+            const int ncol = nx*ny;
+            auto view3 = [](const Float* p, int a, int b, int c) { return p ? Array_gpu<Float,3>(const_cast<Float*>(p), {a, b, c}) : Array_gpu<Float,3>(); };
+            Array<Float,1> h_top;
+            if (top_radiance != nullptr)
+            {
+                h_top.set_dims({ngpt});
+                for (int g=1; g<=ngpt; ++g) h_top({g}) = top_radiance[g-1];
+            }
+            Array<long long,1> h_m({ngpt});
+            for (int g=1; g<=ngpt; ++g) h_m({g}) = rays_per_cell_gpt[g-1];
+            Array_gpu<Float,2> out(flux_conv, {ncol, nz});
+            Raytracer_thermal_gpu raytracer;
+            *n_capped = raytracer.trace_heating(nx, ny, nz, dx, dy, dz, top_at_1 != 0, view3(tau, ncol, nz, ngpt), view3(ssa, ncol, nz, ngpt),
+                    Array_gpu<int,2>(const_cast<int*>(band_lims_gpt), {2, nbnd}), view3(cld_tau, ncol, nz, nbnd), view3(cld_ssa, ncol, nz, nbnd),
+                    view3(cld_g, ncol, nz, nbnd), view1(sfc_emis, ncol), view3(lay_src, ncol, nz, ngpt), view2(sfc_src, ncol, ngpt), h_top,
+                    knx, kny, knz, h_m, seed, max_events, out, n_clamped);
+        }
+        catch (...) { rrx_host::set_stream(before); throw; }
+        rrx_host::set_stream(before);
+    });
+}

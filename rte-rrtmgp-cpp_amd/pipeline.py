@@ -423,6 +423,80 @@ def render_lw(be, kd_lw, atm, nx, ny, dx, dy, dz, camera, rays_per_pixel, seed, 
     return r
 
 
+def absorbed_emission(tau, lay_src, band_lims, cld):
+    """heating_lw(allocation="emission"): e (ngpt,) float64 on the host, e_g = sum over the cells of tau_abs lay_src[g] with
+    tau_abs = tau + cld_tau (1 - cld_ssa) of the g-point's band (the gas does not scatter): the power that the atmosphere emits in g
+    per unit horizontal area, up to 4 pi / ncol. Formed on the device in float64; ngpt numbers are copied."""
+    tau_abs = tau.double()
+    if cld is not None:
+        tau_abs = tau_abs.clone()
+        lims = band_lims.cpu().numpy()
+        for b in range(lims.shape[0]):
+            tau_abs[int(lims[b, 0]) - 1:int(lims[b, 1])] += (cld[0][b].double()*(1.0 - cld[1][b].double()))[None]
+    return (tau_abs*lay_src.double()).flatten(1).sum(dim=1).cpu().numpy()
+
+
+def heating_allocation(e, sfc_max, top_radiance, P, min_per_gpt=1):
+    """heating_lw(allocation="emission"): m (ngpt,) int64 = spectral_allocation(e, P, min_per_gpt) with e_g the power that the
+    atmosphere emits in g-point g (absorbed_emission). A g-point with e_g = 0 gets no rays and is left out of the result, so it is
+    refused when its largest sfc_src, sfc_max[g], or its top_radiance[g] (None: 0) is positive: the result would be biased."""
+    e = np.asarray(e, dtype=np.float64).reshape(-1)
+    sfc_max = np.asarray(sfc_max, dtype=np.float64).reshape(-1)
+    top = np.zeros(e.size) if top_radiance is None else np.asarray(top_radiance, dtype=np.float64).reshape(-1)
+    if sfc_max.size != e.size or top.size != e.size:
+        raise ValueError(f"heating_lw: sfc_src and top_radiance are per g-point (ngpt = {e.size}), got {sfc_max.size}, {top.size}")
+    bad = np.flatnonzero((e == 0) & ((sfc_max > 0) | (top > 0)))
+    if bad.size:
+        raise ValueError(f"heating_lw: g-point {int(bad[0])} has no emission in the atmosphere, so allocation='emission' gives it no rays, "
+                         "but its sfc_src or top_radiance is positive: it would be left out of the result")
+    return spectral_allocation(e, P, min_per_gpt)
+
+
+def heating_lw(be, kd_lw, atm, nx, ny, dx, dy, dz, rays_per_cell, seed, cloud_lut=None, kn_grid=None, sfc_emis=None, max_events=None,
+               top_radiance=None, allocation=None, min_per_gpt=1, p_lev=None):
+    """3-D longwave heating from the thermal ray tracer's cell sensors (rrx_heating3d_render), on the chain of
+    render_lw: the clear g-point tau of gas_optics_lw_direct (the gas does not scatter), the Planck sources of planck_source_direct
+    and, with cloud_lut, the band cloud triple of cloud_optics_2str; sfc_emis and top_radiance as in render_lw. Returns flux_conv
+    (nlay, ncol) in W m-2, the net radiative power that every cell takes up per unit horizontal area (negative: it cools), n_capped,
+    n_clamped, rays_per_cell_gpt (ngpt,) and, given p_lev (nlay+1, ncol) in Pa, heating_rate = g/cp flux_conv / |dp| in K s-1.
+    allocation=None: every g-point gets rays_per_cell rays per cell. allocation="emission": rays_per_cell is the TOTAL over all
+    g-points, dealt by spectral_allocation(e, rays_per_cell, min_per_gpt) in proportion to e_g = sum over the cells of
+    tau_abs lay_src[g], the power that the atmosphere emits in g; a g-point with e_g = 0 gets no rays, and is refused when its sfc_src
+    or top_radiance is positive. What this allocation gains in variance over the equal split has not been measured."""
+    if allocation not in (None, "emission"):
+        raise ValueError(f"heating_lw: allocation is None or 'emission', got {allocation!r}")
+    ncol, nlay, ngpt = atm.ncol, atm.nlay, kd_lw.ngpt
+    if ncol != nx*ny:
+        raise ValueError(f"heating_lw: ncol = {ncol} is not nx ny = {nx}*{ny}")
+    if sfc_emis is None:
+        emis = be.to_numpy(atm.emis_sfc)
+        if np.any(emis != emis[:, :1]):
+            raise ValueError("heating_lw: the atmosphere's emissivity differs between bands; pass sfc_emis")
+        sfc_emis = np.ascontiguousarray(emis[:, 0])
+    sfc_emis = be.asarray(sfc_emis)
+    kn_grid = (nx, ny, nlay) if kn_grid is None else tuple(int(k) for k in kn_grid)
+
+    _, col_gas, _ = gas_state(be, kd_lw, atm, None, interpolate=False)
+    tau = be.gas_optics_lw_direct(kd_lw, atm.p_lay, atm.t_lay, col_gas, be.empty((ngpt, nlay, ncol)))
+    src = be.planck_source_direct(kd_lw, atm.p_lay, atm.t_lay, atm.t_lev, atm.t_sfc, _sfc_lay(atm), col_gas)
+    cld = be.cloud_optics_2str(cloud_lut, atm.lwp, atm.iwp, atm.rel, atm.dei) if cloud_lut is not None else None
+    if allocation == "emission":
+        e = absorbed_emission(tau, src["lay_src"], kd_lw.band_lims_gpt, cld)
+        sfc_max = be.to_numpy(src["sfc_src"].max(dim=1).values) if np.any(e == 0) else np.zeros(ngpt)
+        m = heating_allocation(e, sfc_max, top_radiance, rays_per_cell, min_per_gpt)
+    else:
+        m = np.full(ngpt, int(rays_per_cell), dtype=np.int64)
+    r = be.thermal_heating_render(tau, None, nx, ny, dx, dy, dz, sfc_emis, src["lay_src"], src["sfc_src"], kn_grid, m, seed,
+                                  kd_lw.band_lims_gpt, top_at_1=atm.top_at_1, cloud=cld, max_events=max_events, top_radiance=top_radiance)
+    r["rays_per_cell_gpt"] = m
+    if p_lev is not None:
+        p_lev = be.asarray(p_lev)
+        if tuple(p_lev.shape) != (nlay + 1, ncol):
+            raise ValueError(f"heating_lw: p_lev is (nlay+1, ncol) = {(nlay + 1, ncol)}, got {tuple(p_lev.shape)}")
+        r["heating_rate"] = (9.80665/1004.64)*r["flux_conv"]/(p_lev[1:] - p_lev[:-1]).abs()
+    return r
+
+
 def _raytracer_medium(who, be, atm, tau, ssa, cld, aer, cloud_lut, phase_table, n_domain, z_lev):
     """What raytrace_sw and render_sw do with the chain's optics before they call the binding: with n_domain the split into the
     grid's arrays and a Background, the phase table with the (grid's) radius, and the medium that goes to the binding as keywords:
