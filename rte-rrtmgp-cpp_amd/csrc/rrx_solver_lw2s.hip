@@ -25,7 +25,7 @@ namespace
 using namespace rrx;
 
 template<typename F>
-struct Lw2sLayer { F r, t, su, sd; };
+struct Lw2sLayer { F r, t, su, sd, ab; };      // ab: the absorptance 1 - Rdif - Tdif, formed without that subtraction
 
 // 1 - exp(-x) for x >= 0 to a relative error of a few eps, given e1 = exp(-x): below 1/4 the series x (1 - x/2 (1 - x/3 ...)) (its first
 // neglected term is below eps/2 of the sum), from there on the difference, which loses at most two bits
@@ -50,6 +50,8 @@ __device__ __forceinline__ F one_minus_exp_neg(const F x, const F e1)
 //   src_up = pi ( (lev_bot - lev_top) c + lev_bot (1 - Tdif) - Rdif lev_top)
 //   src_dn = pi (-(lev_bot - lev_top) c + lev_top (1 - Tdif) - Rdif lev_bot)
 // which is the same function of the inputs; what is left is an absolute error of a few eps in c, times lev_bot - lev_top.
+// The absorptance 1 - Rdif - Tdif = RT (k u^2 + (gamma1 - gamma2) m) comes with it (for the fused kernel's albedo scan); it is clamped at 0,
+// since gamma1 - gamma2 of a conservative layer may round to -1 ulp.
 template<typename F, bool TAB>
 __device__ __forceinline__ Lw2sLayer<F> lw_two_stream(const F tau, const F ssa, const F g, const F lev_top, const F lev_bot, const F* etab)
 {
@@ -70,6 +72,7 @@ __device__ __forceinline__ Lw2sLayer<F> lw_two_stream(const F tau, const F ssa, 
     o.r = rt * gamma2 * m;
     o.t = rt * F(2.) * k * e1;
     const F omt = rt * (ku2 + g1m);
+    o.ab = max(rt * (ku2 + (gamma1 - gamma2) * m), F(0.));
     const bool thick = tau > F(1.e-8);
     const F itg = fast_rcp(thick ? tau * gsum : F(1.));
     const F c = rt * ((ku2 * itg - g1m) + (m * gsum * itg - kp));
@@ -275,7 +278,14 @@ lw_2stream_bb_kernel(
     F sb[K];      // src_up -> beta -> src at level t0+j
     F qb[K];      // src_dn -> q = src_dn*denom -> b
 
-    // ---- (a) layers: every one independent of the others
+    // ---- (a) layers: every one independent of the others; (b) with them the Moebius composite of this lane's layers for the albedo
+    // scan, normalised to m11 = 1 below. The composite acts on the CO-ALBEDO b = 1 - albedo: with rho = 1 - Rdif = Tdif + ab the
+    // adding step a' = r + t^2 a/(1 - r a) is b' = ((rho r + t^2) b + ab (rho + t))/(r b + rho), a map whose four coefficients are
+    // non-negative, so neither a lane's product nor the compositions of the scan (n11 = m10 p01 + 1 >= 1) subtract anything. In albedo
+    // space the same normalisation is 1 - R R' of two sub-stacks, which cancels as both reflectances near 1: a conservative column of
+    // 500 layers left the albedo at the lanes' chunk boundaries 7e2 eps off (the sequential recurrence: 8 eps) and the fluxes of that
+    // g-point 30 x further from truth than the serial kernel's (tests/test_gpu_lw2s_truth.py).
+    F m00 = F(1.), m01 = F(0.), m10 = F(0.), m11 = F(1.);
     F lva = level_src(0);
     #pragma unroll
     for (int j=0; j<K; ++j)
@@ -300,21 +310,19 @@ lw_2stream_bb_kernel(
         const Lw2sLayer<F> L = lw_two_stream<F,ETAB>(tt, ssa, gc, lva, lvb, lds_etab);
         lva = lvb;
         rp[j] = L.r; al[j] = L.t; sb[j] = L.su; qb[j] = L.sd;
+        {
+            // M <- M * L_j (layer 0 is the outermost map): the same product as applying layer K-1 first
+            const F rho = L.t + L.ab;
+            const F l00 = rho*L.r + L.t*L.t, l01 = L.ab*(rho + L.t);
+            const F n00 = m00*l00 + m01*L.r, n01 = m00*l01 + m01*rho;
+            const F n10 = m10*l00 + m11*L.r, n11 = m10*l01 + m11*rho;
+            m00 = n00; m01 = n01; m10 = n10; m11 = n11;
+        }
     }
     __builtin_amdgcn_sched_barrier(0);
     const F emis = n_emis, ssrc = n_ssrc, dn_top = (inc_flux != nullptr) ? n_inc : F(0.);
 
-    // ---- (b) albedo: Moebius composite of this lane's layers (layer K-1 applied first), normalised to m11 = 1
-    F m00 = F(1.), m01 = F(0.), m10 = F(0.), m11 = F(1.);
-    #pragma unroll
-    for (int j=K-1; j>=0; --j)
-    {
-        const F r = rp[j], t = al[j];
-        const F e = t*t - r*r;
-        const F n00 = e*m00 + r*m10, n01 = e*m01 + r*m11;
-        const F n10 = m10 - r*m00,   n11 = m11 - r*m01;
-        m00 = n00; m01 = n01; m10 = n10; m11 = n11;
-    }
+    // ---- (b) albedo: this lane's composite, normalised to m11 = 1 (m11 > 0: a product of sums of non-negative terms with rho > 0)
     {
         const F inv = fast_rcp(m11);
         m00 *= inv; m01 *= inv; m10 *= inv; m11 = F(1.);
@@ -363,8 +371,8 @@ lw_2stream_bb_kernel(
     }
     F e00 = shfl(m00, lane + CL), e01 = shfl(m01, lane + CL), e10 = shfl(m10, lane + CL);
     if (ll == LL-1) { e00 = x00; e01 = x01; e10 = x10; }
-    const F alb_sfc = F(1.) - emis;
-    F a = (e00*alb_sfc + e01) * fast_rcp(e10*alb_sfc + F(1.));      // albedo at the bottom of this lane's chunk
+    // albedo at the bottom of this lane's chunk: 1 - the co-albedo there; the surface's co-albedo is emis
+    F a = F(1.) - (e00*emis + e01) * fast_rcp(e10*emis + F(1.));
 
     // replay the albedo upward; build alpha, beta, p, q and the lane's affine composites
     F As = F(1.), Bs = F(0.), Bd = F(0.);    // As: product of alpha (shared); Bs: source (upward); Bd: down

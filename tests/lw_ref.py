@@ -21,6 +21,7 @@ of tests/test_gpu_lw_truth.py rejects such kernels.
 
 Arrays follow hip_kernels.py: C-contiguous with reversed dimensions, tau(ncol, nlay, ngpt) <-> shape (ngpt, nlay, ncol); secants
 (nmus, ngpt, ncol), weights (nmus). Layers and levels are in memory order; top_at_1 says which end is the top of the atmosphere."""
+import contextlib
 import functools
 
 import numpy as np
@@ -170,11 +171,11 @@ def regimes(dt, ncol, nlay):
     return out
 
 
-def column_regimes(reg):
+def column_regimes(reg, regimes=REGIMES):
     """The regime of a column's g-point SUM, (ncol,): among the profiles that enter it, the one where the reference is farthest from
-    truth (the last in REGIMES)"""
-    rank = np.vectorize(REGIMES.index)(reg)
-    return np.array(REGIMES, dtype="U12")[rank.max(axis=0)]
+    truth (the last in `regimes`, lw_ref's own REGIMES unless a follow-up module passes its tuple)"""
+    rank = np.vectorize(regimes.index)(reg)
+    return np.array(regimes, dtype="U20")[rank.max(axis=0)]
 
 
 # ---- Planck-lite sources and optimal-angle secants -------------------------------------------------------------------------------------
@@ -371,15 +372,20 @@ def bound_eps(oracle_eps):
 
 
 class Report:
-    """Prints every figure of a test, then asserts them all. `got` is a kernel's output -- or, in tests/test_lw_ref.py, a model's."""
-    def __init__(self, dt, label="kernel", quiet=False):
+    """Prints every figure of a test, then asserts them all. `got` is a kernel's output -- or, in tests/test_lw_ref.py, a model's.
+    The follow-up modules (tests/lw2s_truth.py, tests/lw1r_truth.py) pass their own regime tuple, quantity tuple, print prefix and the
+    name of what stands behind E_regime; with fraction=True a line also gives the bound as a plain fraction of the profile's largest
+    flux. The defaults are this module's, unchanged."""
+    def __init__(self, dt, label="kernel", quiet=False, regimes=REGIMES, quantities=QUANTITIES, prefix="LWTRUTH", ref_name="oracle",
+                 fraction=False):
         self.dt, self.eps, self.label, self.quiet = dt, float(np.finfo(np_dtype(dt)).eps), label, quiet
-        self.failures, self.outside, self.worst = [], set(), {}
+        self.regimes, self.quantities, self.prefix, self.ref_name, self.fraction = regimes, quantities, prefix, ref_name, fraction
+        self.failures, self.outside, self.outside_cells, self.worst = [], set(), set(), {}
 
     def check(self, what, got, orc, truth_, reg):
         """got, orc: dicts quantity -> per-g-point (ngpt, nlev, ncol) or summed (nlev, ncol) arrays of the run's dtype; truth_: the same
         keys (or more), per g-point longdouble; reg: the regime of each profile of got"""
-        for q in QUANTITIES:
+        for q in self.quantities:
             if q not in got:
                 continue
             k = profile_error(got[q], truth_[q]) / self.eps
@@ -387,24 +393,42 @@ class Report:
             assert k.shape == reg.shape == e.shape, (k.shape, e.shape, reg.shape)
             if not np.isfinite(np.asarray(got[q], dtype=np.float64)).all():
                 self.failures.append(f"{what} {q}: not finite")
-            for r in REGIMES:
+            for r in self.regimes:
                 m = reg == r
                 if not m.any():
                     continue
                 kc, ec = float(k[m].max()), float(e[m].max())
                 bound = bound_eps(ec)
                 if not self.quiet:
-                    print(f"LWTRUTH {what} {q} {self.dt} {r} n={int(m.sum())}: {self.label} {kc:.4g} eps, oracle {ec:.4g} eps, "
-                          f"ratio {kc / max(ec, 1e-300):.3g}, bound {bound:.4g} eps")
+                    print(f"{self.prefix} {what} {q} {self.dt} {r} n={int(m.sum())}: {self.label} {kc:.4g} eps, {self.ref_name} {ec:.4g} eps, "
+                          f"ratio {kc / max(ec, 1e-300):.3g}, bound {bound:.4g} eps" + (f" = {bound * self.eps:.3g} of the largest flux" if self.fraction else ""))
                 key = (q, r)
                 if kc > self.worst.get(key, (-1.0,))[0]:
                     self.worst[key] = (kc, ec, bound)
                 if not kc <= bound:
                     self.outside.add(r)
-                    self.failures.append(f"{what} {q} {r}: {self.label} {kc:.4g} eps > {bound:.4g} eps (oracle {ec:.4g} eps)")
+                    self.outside_cells.add((r, q))
+                    self.failures.append(f"{what} {q} {r}: {self.label} {kc:.4g} eps > {bound:.4g} eps ({self.ref_name} {ec:.4g} eps)")
 
     def done(self):
         assert not self.failures, "\n".join(self.failures)
+
+
+@contextlib.contextmanager
+def one_range(be):
+    """the fused forms of a backend without the g-point split"""
+    be.set_broadband_min_groups(1)
+    be.set_broadband_gsplit(1)
+    try:
+        yield
+    finally:
+        be.set_broadband_min_groups(512)
+        be.set_broadband_gsplit(0)
+
+
+def splits(be):
+    """the two ways the GPU truth tests run every fused form: (label, context manager)"""
+    return (("automatic split", contextlib.nullcontext()), ("one range", one_range(be)))
 
 
 def as_dict(fluxes, gpts=None, summed=False):

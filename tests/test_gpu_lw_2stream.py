@@ -25,9 +25,15 @@ F64_FLOOR, F32_FLOOR = 1e-6, 1e-2
 #         general per g-point vs numpy 1.09e-8: single g-points whose flux is 1e-6 of the largest carry the absolute error of the thin
 #         layers' source terms AS THE REFERENCE EVALUATES THEM (Z = (lev_bot - lev_top)/(tau (gamma1 + gamma2)) reaches 1e5 at
 #         tau = 1e-4 and Z (1 + Rdif - Tdif) cancels to rounding). The kernels evaluate the same terms regrouped, without that
-#         cancellation, so this figure is the reference's own error -> twice the 1.02e-8 first observed; not widened since
+#         cancellation -> twice the 1.02e-8 first observed; not widened since
 #   fp32  broadband: general 1.83e-4, fused vs materialised 5.1e-7, fused vs numpy 1.83e-4 -> 3.7e-4; per g-point 4.51e-2 -> 9.1e-2
-#         (again the float32 reference's cancellation, not the kernels')
+#   Whose error the two per-g-point figures are, measured against a longdouble truth per profile (tests/lw2s_truth.py,
+#   tests/test_lw2s_truth.py on a CPU, tests/test_gpu_lw2s_truth.py on an MI355X; eps of the dtype, worst over its regimes and shapes): on
+#   thin g-points (tau 1e-8 ... 1e-4) this reference is 2e6 ... 8e10 eps from truth in fp64 and 3e6 ... 5e10 eps in fp32, i.e. up to 2e-5
+#   and of order one of the g-point's own flux; the general kernel is at 1e2 ... 2e2 eps where a flux is lit and at 6e3 ... 3e4 eps where
+#   flux_dn is layer emission alone, within 1.5 x of the regrouped formula in numpy. So all but 6e-12 (fp64) and 3e-3 (fp32; dark thin
+#   flux_dn only) of a thin profile's flux in these two tolerances is the as-written reference's share, the rest the regrouped formula's, which the kernel
+#   reproduces; in the norm of this file they say nothing about a thin g-point, and tests/test_gpu_lw2s_truth.py is what holds those.
 F64_TOL = 1e-10
 F64_GPT_TOL = 2.1e-8
 F32_TOL = 3.7e-4

@@ -51,8 +51,6 @@ In fp64 the kernels reproduce the oracle's error to three digits in every ill-co
 formula's cancellation on these inputs, which both evaluate alike, and the LDS-table exp_neg, fast_rcp and the re-associated scans add
 nothing visible to it. Where the formula is well-conditioned (opaque, moderate) the kernels sit at 1 ... 7 eps.
 """
-import contextlib
-
 import numpy as np
 import pytest
 import types
@@ -86,20 +84,8 @@ class Dev:
         return {k: self.be.to_numpy(v) for k, v in r.items()}
 
 
-@contextlib.contextmanager
-def one_range(be):
-    """the fused forms without the g-point split"""
-    be.set_broadband_min_groups(1)
-    be.set_broadband_gsplit(1)
-    try:
-        yield
-    finally:
-        be.set_broadband_min_groups(512)
-        be.set_broadband_gsplit(0)
-
-
 def _splits(be):
-    return (("automatic split", contextlib.nullcontext()), ("one range", one_range(be)))
+    return lw_ref.splits(be)
 
 
 def _check_summed(rep, what, dt, shape, top_at_1, angles, with_inc, got, gpts=None, from_fractions=True):
